@@ -12,12 +12,17 @@ and relays rank 0's JSON line and the exit code.  Environments shard across rank
 scaling: 65536 envs per GPU); the barrier + max-over-ranks timing uses RCCL; `--gather-obs` adds the one optional
 exchange of the path, an all-gather of the observations (12.3 MB per GPU per step at 65536 envs).
 
-Rank 0 prints ONE JSON line.  `roofline.achieved` prices the dominant kernel (env_kernel<Dyn, STEP>) with the
-algorithmic bytes of SURVEY.md §8(d) (418 B per env-step) against the HBM peak; the kernel's duration is measured
-live with HIP events on the launch stream (urgym_enable_timing).  `cpu_baseline` times the CPU oracle
-(oracle/, kind "port": the reference's PyBullet path cannot run here) on rank 0's host cores over a bounded
-sample of the same workload, and -- SURVEY.md section 8d "outputs compared at the end of the timed loop" -- steps a slice
-of the GPU's final state once on both sides and reports the largest deviations (`parity_check`).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline figure
+(`value`, `ms_per_step`); `--dump-outputs DIR` also writes what the last timed step returned to a caller as
+DIR/<name>.npy.  Everything else is measured only with `--full`:
+  * `roofline`: prices the dominant kernel (env_kernel<Dyn, STEP>) with the algorithmic bytes of SURVEY.md §8(d) (418 B per
+    env-step) against the HBM peak; the kernel's duration is measured live with HIP events on the launch stream
+    (urgym_enable_timing), so the timed loop of a --full run carries those events;
+  * the per-status-bit census of the envs after the loop (`anomalous_envs`, `envs_by_status_bit`, ...);
+  * `cpu_baseline` (unless --no-cpu-baseline): times the CPU oracle (oracle/, kind "port": the reference's PyBullet path
+    cannot run here) on rank 0's host cores over a bounded sample of the same workload, and -- SURVEY.md section 8d
+    "outputs compared at the end of the timed loop" -- steps a slice of the GPU's final state once on both sides and
+    reports the largest deviations (`parity_check`).
 """
 import argparse
 import json
@@ -147,6 +152,32 @@ def parity_check(env, actions, m=512):
     return out
 
 
+# what VectorEnv.step() hands its caller: the observation dict, reward, terminated, truncated and info (is_success, collision,
+# status, final_observation).  The final_* rows are valid only where the env finished in that step; the others are written as 0.
+DUMP_FIELDS = ("observation", "achieved_goal", "desired_goal", "reward", "terminated", "truncated", "is_success", "collision", "status",
+               "final_observation", "final_achieved_goal", "final_desired_goal")
+DUMP_BUDGET = 60 * 10**6  # bytes of array data over all files: under 64 MB with the .npy headers
+DUMP_SEED = 20240611    # fixed row sample when the whole output would not fit the budget
+
+
+def dump_outputs(env, out_dir):
+    """Write this rank's outputs of the last step as out_dir/<field>.npy (float32; flags and status words are exact in it) plus
+    env_index.npy (float64), the env row of each written row: every row, or a fixed seeded sample of rows if N is too large."""
+    n = env.num_envs
+    host = {k: env.buf[k].cpu().numpy() for k in DUMP_FIELDS}
+    done = (host["terminated"] | host["truncated"]).astype(bool)
+    for k in ("final_observation", "final_achieved_goal", "final_desired_goal"):
+        host[k] = np.where(done[:, None], host[k], 0)
+    row_bytes = 8 + sum(4 * v[0].size for v in host.values())
+    rows = np.arange(n)
+    if n * row_bytes > DUMP_BUDGET:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_BUDGET // row_bytes, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "env_index.npy"), rows.astype(np.float64))
+    for k, v in host.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.ascontiguousarray(v[rows], dtype=np.float32))
+
+
 def spawn_ranks(args):
     """`python bench.py --gpus N` with N > 1 outside a launcher: this process has not touched the GPU (torch is only imported);
     it starts one rank per GPU through torch.distributed.run as a child, relays rank 0's JSON line and the exit code."""
@@ -179,7 +210,10 @@ def main():
     ap.add_argument("--num-envs", type=int, default=65536, help="environments PER GPU")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--gather-obs", action="store_true", help="all-gather observations over RCCL every step (optional)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline (HIP events in the timed loop), the status census and the CPU baseline + parity check")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write rank 0's outputs of the last timed step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline and its parity check")
     ap.add_argument("--gjk-start", choices=("bullet", "guided"), default="bullet",
                     help="bullet = the reference's search start (parity-grade, default); guided = opt-in, NOT parity-grade")
     ap.add_argument("--no-collision", action="store_true",
@@ -289,8 +323,10 @@ def main():
     torch.cuda.synchronize(dev)
     # HIP events around every k-th step launch (an event pair costs the stream ~6 us, i.e. ~3 % of a 0.2 ms step if every launch carried
     # one): every 8th launch in the default 200-step run (25 launches timed), every 2nd in a short one (the driver's 20-step run: 10)
+    # (--full only: a plain run times the steps and nothing inside them)
+    kernel_timing = args.full and not args.no_kernel_timing
     every = 8 if args.steps >= 128 else (4 if args.steps >= 64 else 2)
-    env.enable_timing(not args.no_kernel_timing, every=every)
+    env.enable_timing(kernel_timing, every=every)
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize(dev)
@@ -308,30 +344,24 @@ def main():
         dist.barrier()
         torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
-    step_us, reset_us, launches = (0.0, 0.0, 0) if args.no_kernel_timing else env.query_timing()
+    step_us, reset_us, launches = env.query_timing() if kernel_timing else (0.0, 0.0, 0)
     env.enable_timing(False)
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if dist.get_backend() == "gloo" else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(env, args.dump_outputs)
 
-    status = env.buf["status"]
-    anomalies = int(((status & ~INFORMATIONAL_BITS) != 0).sum().item())   # nan, reset exhausted / collision, iteration cap, stale record
-    informational = int(((status & INFORMATIONAL_BITS) != 0).sum().item())
-    anomaly_bits = {name: int(((status & bit) != 0).sum().item()) for bit, name in STATUS_BITS.items()}
-    episodes = int(env.buf["episode_id"].sum().item())
+    if args.full:
+        status = env.buf["status"]
+        anomalies = int(((status & ~INFORMATIONAL_BITS) != 0).sum().item())   # nan, reset exhausted / collision, iteration cap, stale record
+        informational = int(((status & INFORMATIONAL_BITS) != 0).sum().item())
+        anomaly_bits = {name: int(((status & bit) != 0).sum().item()) for bit, name in STATUS_BITS.items()}
+        episodes = int(env.buf["episode_id"].sum().item())
     if rank == 0:
         total_envs = n * world
         value = total_envs * args.steps / elapsed
-        algo = ALGO_BYTES[args.env] * n  # bytes one launch of the step kernel has to move, per rank
-        label = config_label(args.env, n, args.no_collision, args.rollout)
-        prof_kernel, traffic, valu = profiled_counters(label)
-        achieved = algo / (step_us * 1e-6) / 1e9 if step_us > 0 else 0.0
-        fused = args.env != "UR5OriReach-v1"
-        kind_no = {"UR5OriReach-v1": 0, "UR5ObsReach-v1": 1, "UR5DynReach-v1": 2, "UR5StaReach-v1": 3}[args.env]
-        epa = (args.env == "UR5ObsReach-v1") or args.no_collision
-        kernel = (f"env_step_fused<{kind_no}, {str(epa).lower()}> (STEP workgroups + the refill of the previous step's episode records)" if fused
-                  else f"env_kernel<{kind_no}, 0, false> (STEP; finished envs reset inside the launch)")
         out = {
             "metric": "env-steps/sec (whole node)",
             "value": value,
@@ -349,6 +379,24 @@ def main():
                                    + (", collision checks OFF (FK + reward only)" if args.no_collision else ""),
                        "envs_total": total_envs, "gather_obs": bool(gathered is not None), "rollout_api": bool(args.rollout),
                        "gjk_start": args.gjk_start},
+        }
+        if gathered is not None:
+            out["config"]["gather_bytes_per_gpu_per_step"] = n * env.obs_dim * 4
+            last = (args.warmup + args.steps - 1) & 1
+            out["config"]["gather_overlapped_with_next_step"] = True
+            out["config"]["gather_own_shard_intact"] = bool(torch.equal(gathered[last].view(world, n, env.obs_dim)[rank].to(dev), env.buf["observation"]))
+            out["config"]["gather_delivered_step_t_while_step_t_plus_1_ran"] = check["ok"]
+    if rank == 0 and args.full:
+        algo = ALGO_BYTES[args.env] * n  # bytes one launch of the step kernel has to move, per rank
+        label = config_label(args.env, n, args.no_collision, args.rollout)
+        prof_kernel, traffic, valu = profiled_counters(label)
+        achieved = algo / (step_us * 1e-6) / 1e9 if step_us > 0 else 0.0
+        fused = args.env != "UR5OriReach-v1"
+        kind_no = {"UR5OriReach-v1": 0, "UR5ObsReach-v1": 1, "UR5DynReach-v1": 2, "UR5StaReach-v1": 3}[args.env]
+        epa = (args.env == "UR5ObsReach-v1") or args.no_collision
+        kernel = (f"env_step_fused<{kind_no}, {str(epa).lower()}> (STEP workgroups + the refill of the previous step's episode records)" if fused
+                  else f"env_kernel<{kind_no}, 0, false> (STEP; finished envs reset inside the launch)")
+        out.update({
             # `achieved` / `peak` / `frac` price the kernel against the HBM roofline with the algorithmic bytes of SURVEY.md section 8(d), as
             # the measurement contract asks; `bound` names what really limits it: float64 VALU issue while the chip is full (three waves
             # per SIMD keep the vector pipes saturated), then the latency of the longest GJK chains in the tail of the launch
@@ -371,16 +419,11 @@ def main():
             "informational_envs": informational,               # penetration depth consumed / joint past its URDF limit
             "envs_by_status_bit": anomaly_bits,                # include/urgym.h URGYM_STATUS_*
             "episodes_started": episodes,
-        }
-        if gathered is not None:
-            out["config"]["gather_bytes_per_gpu_per_step"] = n * env.obs_dim * 4
-            last = (args.warmup + args.steps - 1) & 1
-            out["config"]["gather_overlapped_with_next_step"] = True
-            out["config"]["gather_own_shard_intact"] = bool(torch.equal(gathered[last].view(world, n, env.obs_dim)[rank].to(dev), env.buf["observation"]))
-            out["config"]["gather_delivered_step_t_while_step_t_plus_1_ran"] = check["ok"]
+        })
         if not args.no_cpu_baseline:  # rank 0 at any world size
             out["cpu_baseline"] = cpu_baseline(args.env, args.seed)
             out["cpu_baseline"]["parity_check"] = parity_check(env, actions[(args.warmup + args.steps) % n_act])
+    if rank == 0:
         print(json.dumps(out), flush=True)
     env.close()
     if dist is not None:

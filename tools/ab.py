@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A/B runner for kernel experiments on the GPU box: each variant is one `bench.py --no-cpu-baseline` child process with its own
+"""A/B runner for kernel experiments on an MI355X: each variant is one `bench.py --full --no-cpu-baseline` child process with its own
 library (URGYM_LIB) and environment switches; variants are interleaved over the repetitions so that clock drift hits all alike.
 
     python tools/ab.py --out gpurun_out/exp_x/results.jsonl --reps 2 \
@@ -29,7 +29,7 @@ for v in args.variant:
 with open(args.out, "a") as f:
     for rep in range(args.reps):
         for name, env in variants:
-            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline"] + args.bench_args
+            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline"] + args.bench_args
             try:
                 p = subprocess.run(cmd, env=dict(os.environ, **env), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=args.timeout)
                 lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

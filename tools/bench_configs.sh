@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/bench_configs.jsonl
 : > $OUT
-run() { timeout -k 10 300 python $R/bench.py --no-cpu-baseline "$@" | grep '^{' >> $OUT; }
+run() { timeout -k 10 300 python $R/bench.py --full --no-cpu-baseline "$@" | grep '^{' >> $OUT; }
 run --env UR5OriReach-v1 --num-envs 4096 --steps 300 --warmup 20
 run --env UR5OriReach-v1 --num-envs 4096 --steps 300 --warmup 20 --rollout
 run --env UR5OriReach-v1 --num-envs 4096 --steps 300 --warmup 20 --rollout --no-collision

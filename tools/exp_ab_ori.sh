@@ -8,7 +8,7 @@ mkdir -p $OUT
 cd $R
 B=$R/ur_gym_amd/csrc/build
 run() { name=$1; lib=$2; shift 2
-  URGYM_LIB=$lib timeout -k 10 300 python bench.py --no-cpu-baseline "$@" | grep '^{' | python -c "
+  URGYM_LIB=$lib timeout -k 10 300 python bench.py --full --no-cpu-baseline "$@" | grep '^{' | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 print(json.dumps({'variant': '$name', 'args': '$*', 'value_M': round(d['value'] / 1e6, 2), 'ms_per_step': round(d['ms_per_step'], 5), 'kernel_us': round(d['roofline']['kernel_us'], 2)}))" | tee -a $OUT/results.jsonl; }

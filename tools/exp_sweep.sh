@@ -8,7 +8,7 @@ mkdir -p $OUT
 cd $R
 : > $OUT/sweep.jsonl
 for E in 32 40 44 46 48 52 56 64; do
-  URGYM_STEP_ENVS=$E timeout -k 10 120 python bench.py --no-cpu-baseline --steps 200 --warmup 20 2>/dev/null | python -c "
+  URGYM_STEP_ENVS=$E timeout -k 10 120 python bench.py --full --no-cpu-baseline --steps 200 --warmup 20 2>/dev/null | python -c "
 import sys, json
 b = json.loads(sys.stdin.readline())
 print(json.dumps({'E': $E, 'value': b['value'], 'ms_per_step': b['ms_per_step'], 'kernel_us': b['roofline']['kernel_us']}))" >> $OUT/sweep.jsonl

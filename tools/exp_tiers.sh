@@ -8,7 +8,7 @@ mkdir -p $OUT
 cd $R
 : > $OUT/tiers.jsonl
 one() {
-  env "$@" timeout -k 10 120 python bench.py --no-cpu-baseline --steps 200 --warmup 20 2>/dev/null | python -c "
+  env "$@" timeout -k 10 120 python bench.py --full --no-cpu-baseline --steps 200 --warmup 20 2>/dev/null | python -c "
 import sys, json
 b = json.loads(sys.stdin.readline())
 print(json.dumps({'cfg': '$*', 'value': b['value'], 'ms_per_step': b['ms_per_step'], 'kernel_us': b['roofline']['kernel_us']}))" >> $OUT/tiers.jsonl

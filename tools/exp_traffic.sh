@@ -9,7 +9,7 @@ mkdir -p $OUT
 cd $R
 : > $OUT/speed.jsonl
 one() {
-  env "$@" timeout -k 10 120 python bench.py --no-cpu-baseline --steps 200 --warmup 20 2>/dev/null | python -c "
+  env "$@" timeout -k 10 120 python bench.py --full --no-cpu-baseline --steps 200 --warmup 20 2>/dev/null | python -c "
 import sys, json
 b = json.loads(sys.stdin.readline())
 print(json.dumps({'cfg': '$*', 'value_M': round(b['value'] / 1e6, 2), 'ms_per_step': round(b['ms_per_step'], 5), 'kernel_us': round(b['roofline']['kernel_us'], 2)}))" >> $OUT/speed.jsonl

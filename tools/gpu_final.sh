@@ -9,7 +9,7 @@ cd $R
 : > $OUT/batch_sweep.jsonl
 for n in 1024 4096 16384 65536 131072 262144 524288 1048576; do
   steps=200; [ $n -ge 262144 ] && steps=60; [ $n -ge 1048576 ] && steps=30
-  timeout -k 10 300 python bench.py --env UR5DynReach-v1 --num-envs $n --steps $steps --warmup 10 --no-cpu-baseline 2>/dev/null | grep '^{' >> $OUT/batch_sweep.jsonl
+  timeout -k 10 300 python bench.py --env UR5DynReach-v1 --num-envs $n --steps $steps --warmup 10 --full --no-cpu-baseline 2>/dev/null | grep '^{' >> $OUT/batch_sweep.jsonl
 done
 python - <<PY
 import json

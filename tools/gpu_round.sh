@@ -15,14 +15,14 @@ for w in $WHAT; do
       timeout -k 10 900 python -m pytest tests -m gpu -q -rA > $OUT/gpu_tests.log 2>&1; echo "exit $?" >> $OUT/gpu_tests.log
       grep -E "passed|failed" $OUT/gpu_tests.log | tail -2 ;;
     bench)
-      timeout -k 10 300 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench exit $?"
+      timeout -k 10 300 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench exit $?"
       head -c 600 $OUT/bench_default.json; echo ;;
     rehearse)
-      URGYM_BENCH_REHEARSE=1 timeout -k 10 300 python bench.py --gpus 2 --num-envs 16384 --steps 20 --warmup 5 --gather-obs > $OUT/rehearse2.json 2> $OUT/rehearse2.err; echo "rehearse exit $?"
+      URGYM_BENCH_REHEARSE=1 timeout -k 10 300 python bench.py --full --gpus 2 --num-envs 16384 --steps 20 --warmup 5 --gather-obs > $OUT/rehearse2.json 2> $OUT/rehearse2.err; echo "rehearse exit $?"
       head -c 400 $OUT/rehearse2.json; echo ;;
     configs)
       : > $OUT/bench_configs.jsonl
-      run() { timeout -k 10 300 python $R/bench.py --no-cpu-baseline "$@" | grep '^{' >> $OUT/bench_configs.jsonl; }
+      run() { timeout -k 10 300 python $R/bench.py --full --no-cpu-baseline "$@" | grep '^{' >> $OUT/bench_configs.jsonl; }
       run --env UR5OriReach-v1 --num-envs 4096 --steps 300 --warmup 20
       run --env UR5OriReach-v1 --num-envs 4096 --steps 300 --warmup 20 --rollout --no-collision
       run --env UR5ObsReach-v1 --num-envs 16384 --steps 200 --warmup 20
