@@ -38,6 +38,7 @@
 #include "../../include/urgym.h"
 #include "../../data/ur5e_model.h"
 #include "urgym_device.h"
+#include "urgym_launch_plan.h"
 #include "urgym_tables_host.h"
 
 using namespace urgym;
@@ -45,16 +46,7 @@ using namespace urgym;
 
 namespace {
 
-constexpr int GROUP = 64;       // env slots per wave-wide pass
-#ifndef URGYM_MAX_ENVS
-#define URGYM_MAX_ENVS 64
-#endif
-constexpr int PREFETCH_MAX_ENVS = 32;       // envs per PREFETCH workgroup at most
-constexpr int MAX_ENVS = URGYM_MAX_ENVS;   // most envs one RESET / REFRESH workgroup serves (one wave of per-env lanes)
-// A STEP workgroup may serve up to two waves' worth of envs: with its link distances parked in a global scratch array instead
-// of LDS the per-env LDS footprint is 12 bytes, so the 53.7 KB that three resident workgroups allow are not exceeded, and
-// N = 65536 fits ONE round of resident workgroups (E = 90) instead of two rounds of 46 with a ragged second one.
-constexpr int STEP_MAX_ENVS = 128;
+// GROUP, STEP_MAX_ENVS, MAX_ENVS, PREFETCH_MAX_ENVS: urgym_launch_plan.h
 #ifndef URGYM_WAVES
 #define URGYM_WAVES 4
 #endif
@@ -1625,40 +1617,59 @@ __global__ void build_list_kernel(const uint8_t* mask, int N, int* list, int* co
 }
 
 // ------------------------------------------------------------------------------------------------- host side
+// The kernel instances a handle launches
+struct Kernels {
+  void (*mode[4])(KParams, const float*);              // by MODE_*
+  void (*fused)(KParams, KParams, const float*, int);  // env_step_fused (none for Ori)
+};
+
+// Which launches can consume a penetration depth (need_epa in the kernel): Ori's never (no obstacle), Obs's always, Sta's and
+// Dyn's unless a STEP launch checks collisions.  Only these instances are compiled.
+template <int KIND, bool STEP_EPA>
+Kernels kernels_of() {
+  constexpr bool EPA = KIND != URGYM_ENV_ORI;
+  Kernels k{{env_kernel<KIND, MODE_STEP, STEP_EPA>, env_kernel<KIND, MODE_RESET, EPA>, env_kernel<KIND, MODE_REFRESH, EPA>,
+             env_kernel<KIND, MODE_PREFETCH, EPA>}, nullptr};
+  if constexpr (KIND != URGYM_ENV_ORI) k.fused = env_step_fused<KIND, STEP_EPA>;
+  return k;
+}
+
+Kernels kernels_for(const urgym_config& c) {
+  switch (c.env_kind) {
+    case URGYM_ENV_ORI: return kernels_of<URGYM_ENV_ORI, false>();
+    case URGYM_ENV_OBS: return kernels_of<URGYM_ENV_OBS, true>();
+    case URGYM_ENV_STA: return c.check_collision ? kernels_of<URGYM_ENV_STA, false>() : kernels_of<URGYM_ENV_STA, true>();
+    default: return c.check_collision ? kernels_of<URGYM_ENV_DYN, false>() : kernels_of<URGYM_ENV_DYN, true>();
+  }
+}
+
 struct Handle {
   urgym_config cfg;
   urgym_buffers buf;
   bool bound = false;
   int device = 0;
   int obs_dim = 0, goal_dim = 0;
+  LaunchPlan plan;                 // launch geometry and paths (urgym_launch_plan.h), fixed at urgym_create
+  Kernels k;
   double* d_ld_scratch = nullptr;  // [5][N] link distances of the running step
-  double* d_sc_scratch = nullptr;  // [SC_FIELDS][N] set-up cache of the running step
-  bool sc_frames = false;          // ... with the link frames (URGYM_SETUP_CACHE=2; default 1: without them; 0: no cache at all)
+  double* d_sc_scratch = nullptr;  // [SC_FIELDS][N] set-up cache of the running step (plan.setup_cache)
   CandRec* d_recs = nullptr;          // support map: candidate records ...
   unsigned short* d_cell = nullptr;   // ... and the cube map of directions that points into them
   uint64_t seed = 0;
   int pp = 0;
-  int step_envs = GROUP;  // envs per workgroup of the step kernel (see urgym_create)
-  int big_blocks = 0, tail_envs = 0;  // two-tier geometry of the step launch: the first big_blocks workgroups serve step_envs, the rest tail_envs
-  int reset_envs = 4;   // envs per workgroup of the auto-reset kernel (latency-bound: few envs, spread wide)
   char err[512] = {0};
-  bool launch_refused = false;  // a launch was not issued because its geometry failed validation (err says why)
   // timing
   bool timing = false;
   int timing_every = 1;   // time every k-th step (an event pair costs the stream ~6 us: sampling keeps the measurement out of the measured)
   long timing_tick = 0;
   std::vector<hipEvent_t> ev;  // pairs: [2i] start, [2i+1] stop ; kind in ev_kind
-  std::vector<int> ev_kind;    // 0 = step kernel, 1 = reset kernel(s) on the caller's stream, 2 = overlapped refill
+  std::vector<int> ev_kind;    // 0 = step kernel, 1 = reset kernel(s) on the caller's stream
   size_t ev_used = 0;
-  double last_refill_us = 0.0;
   // prefetched episode records (DESIGN.md "auto-reset off the critical path")
-  bool prefetch = false;
-  bool inline_ori = false;  // UR5OriReach-v1: finished envs are reset inside the step kernel (no RESET launch per step)
   float neutral_ach[6] = {0, 0, 0, 0, 0, 0};
   double* d_rec = nullptr;      // [2][REC_FIELDS][N]
   int32_t* d_reci = nullptr;    // [2][2][N]
-  int2* d_rl[4] = {nullptr, nullptr, nullptr, nullptr};  // refill lists: three rotating asynchronous ones, one synchronous (index 3)
-  int rl_cap[4] = {0, 0, 0, 0};
+  int2* d_rl[4] = {nullptr, nullptr, nullptr, nullptr};  // refill lists (capacities: plan.rl_cap)
   int* d_rcount = nullptr;      // their counters
   int parity = 0;
   uint64_t rec_seed = 0;
@@ -1667,15 +1678,7 @@ struct Handle {
   // urgym_invalidate_records / a reset that did not cover every env): only then does a step carry the fallback launches.
   // An env that falls back gets fresh records for its next two episodes, and every env finishes within max_episode_steps.
   int dirty_steps = 0;
-  int refill_blocks_override = 0;   // URGYM_REFILL_BLOCKS (tuning / tests): refill workgroups per fused launch, 0 = the policy of launch_fused
   long steps_since_full_reset = -1; // step launches since the last urgym_reset of every env (-1: none yet)
-  // the refill of a step's finished envs rides in the NEXT launch: a burst that happens in step k * max_episode_steps (counted from 1)
-  // is served one launch later; allow a step of slack on either side
-  bool burst_due() const {
-    if (steps_since_full_reset < 0 || cfg.max_episode_steps < 4) return true;
-    const long r = steps_since_full_reset % cfg.max_episode_steps;
-    return steps_since_full_reset >= cfg.max_episode_steps - 1 && (r <= 2 || r == cfg.max_episode_steps - 1);
-  }
 };
 thread_local char g_err[512] = {0};
 
@@ -1742,7 +1745,7 @@ void fill_default(int env_kind, int num_envs, urgym_config* c) {
 }
 
 KParams make_params(Handle* h, int copy_final) {
-  KParams P;
+  KParams P{};  // no refill list, nothing to zero (see use_list / do_step)
   P.cfg = h->cfg;
   P.buf = h->buf;
   P.graph.recs = h->d_recs;
@@ -1753,103 +1756,41 @@ KParams make_params(Handle* h, int copy_final) {
   P.seed_hi = (uint32_t)(h->seed >> 32);
   P.pp = h->pp;
   P.copy_final = copy_final;
-  P.envs = GROUP;
-  P.big_blocks = 0;
-  P.envs_tail = 0;
+  P.envs = h->plan.step_envs;
+  P.big_blocks = h->plan.big_blocks;
+  P.envs_tail = h->plan.tail_envs;
   P.rec_d = h->d_rec;
   P.rec_i = h->d_reci;
-  P.rlist = nullptr;
-  P.rcount = nullptr;
-  P.rcap = 0;
   P.ld_scratch = h->d_ld_scratch;
   P.sc_scratch = h->d_sc_scratch;
-  P.sc_frames = h->sc_frames ? 1 : 0;
-  P.rzero = nullptr;
-  P.rzero2 = nullptr;
+  P.sc_frames = h->plan.setup_cache >= 2 ? 1 : 0;
   P.fallback_on = 1;
-  P.prefetch = 0;
-  P.inline_ori = h->inline_ori ? 1 : 0;
+  P.inline_ori = h->plan.inline_ori ? 1 : 0;
   for (int i = 0; i < 6; i++) P.neutral_ach[i] = h->neutral_ach[i];
   return P;
 }
 
-// A STEP grid must cover env 0 .. n-1 exactly once with workgroups of at most STEP_MAX_ENVS envs: the kernel derives every per-env
-// index (LDS slots, rows of the scratch arrays, observation rows) from (workgroup index, P.envs, P.big_blocks, P.envs_tail).
-bool step_geometry_ok(const KParams& P, long n, long blocks) {
-  if (P.envs < 1 || P.envs > STEP_MAX_ENVS || blocks < 1) return false;
-  if (P.envs_tail == 0) return (blocks - 1) * P.envs < n && blocks * P.envs >= n;
-  if (P.envs_tail < 1 || P.envs_tail > STEP_MAX_ENVS || P.big_blocks < 1 || P.big_blocks >= blocks) return false;
-  const long covered_before_last = (long)P.big_blocks * P.envs + (blocks - P.big_blocks - 1) * P.envs_tail;
-  return covered_before_last < n && covered_before_last + P.envs_tail >= n;
-}
-
+// A STEP launch (the plan's grid, parameters of make_params) or a RESET / REFRESH / PREFETCH launch of `envs` envs per workgroup
+// over `items` envs or list entries (-1: N; list-driven launches: an upper bound of the list length)
 template <int MODE>
-void launch_mode(Handle* h, KParams P, const float* actions, int envs, hipStream_t s, long items = -1) {
-  const int cap = (MODE == MODE_PREFETCH) ? PREFETCH_MAX_ENVS : ((MODE == MODE_STEP) ? STEP_MAX_ENVS : MAX_ENVS);
-  envs = envs < 1 ? 1 : (envs > cap ? cap : envs);              // the kernel's LDS is sized for that many
-  P.envs = envs;
-  if (items < 0) items = h->cfg.num_envs;                       // list-driven launches: an upper bound of the list length
-  long blocks = (items + envs - 1) / envs;
-  if (MODE == MODE_STEP && h->tail_envs > 0 && h->big_blocks > 0 && (long)h->big_blocks * envs < items) {
-    P.big_blocks = h->big_blocks;
-    P.envs_tail = h->tail_envs;
-    blocks = h->big_blocks + (items - (long)h->big_blocks * envs + h->tail_envs - 1) / h->tail_envs;
+void launch_mode(Handle* h, KParams P, const float* actions, hipStream_t s, int envs = 0, long items = -1) {
+  long blocks = h->plan.step_blocks;
+  if (MODE != MODE_STEP) {
+    const int cap = (MODE == MODE_PREFETCH) ? PREFETCH_MAX_ENVS : MAX_ENVS;
+    P.envs = envs < 1 ? 1 : (envs > cap ? cap : envs);  // the kernel's LDS is sized for that many
+    if (items < 0) items = h->cfg.num_envs;
+    blocks = (items + P.envs - 1) / P.envs;
   }
-  dim3 grid((unsigned)blocks), block(THREADS);
-  if (MODE == MODE_STEP && !step_geometry_ok(P, items, blocks)) { snprintf(h->err, sizeof(h->err), "step launch geometry does not cover the envs exactly once"); h->launch_refused = true; return; }
-  // which launches can consume a penetration depth: see need_epa in the kernel
-  const bool epa = (MODE != MODE_STEP) || !h->cfg.check_collision;
-  switch (h->cfg.env_kind) {
-    case URGYM_ENV_ORI: hipLaunchKernelGGL((env_kernel<URGYM_ENV_ORI, MODE, false>), grid, block, 0, s, P, actions); break;
-    case URGYM_ENV_OBS: hipLaunchKernelGGL((env_kernel<URGYM_ENV_OBS, MODE, true>), grid, block, 0, s, P, actions); break;
-    case URGYM_ENV_STA:
-      if (epa) hipLaunchKernelGGL((env_kernel<URGYM_ENV_STA, MODE, true>), grid, block, 0, s, P, actions);
-      else hipLaunchKernelGGL((env_kernel<URGYM_ENV_STA, MODE, false>), grid, block, 0, s, P, actions);
-      break;
-    default:
-      if (epa) hipLaunchKernelGGL((env_kernel<URGYM_ENV_DYN, MODE, true>), grid, block, 0, s, P, actions);
-      else hipLaunchKernelGGL((env_kernel<URGYM_ENV_DYN, MODE, false>), grid, block, 0, s, P, actions);
-      break;
-  }
+  hipLaunchKernelGGL(h->k.mode[MODE], dim3((unsigned)blocks), dim3(THREADS), 0, s, P, actions);
 }
 
 // The steady-state step of the obstacle envs: STEP workgroups + the PREFETCH workgroups that refill what the previous step consumed
 // (env_step_fused).  Ps / Pr: parameters of the two parts.
 void launch_fused(Handle* h, KParams Ps, KParams Pr, const float* actions, hipStream_t s) {
-  const int envs = h->step_envs < 1 ? 1 : (h->step_envs > STEP_MAX_ENVS ? STEP_MAX_ENVS : h->step_envs);
-  const long n = h->cfg.num_envs;
-  Ps.envs = envs;
-  long step_blocks = (n + envs - 1) / envs;
-  if (h->tail_envs > 0 && h->big_blocks > 0 && (long)h->big_blocks * envs < n) {
-    Ps.big_blocks = h->big_blocks;
-    Ps.envs_tail = h->tail_envs;
-    step_blocks = h->big_blocks + (n - (long)h->big_blocks * envs + h->tail_envs - 1) / h->tail_envs;
-  }
   Pr.envs = PREFETCH_MAX_ENVS;
-  // Refill workgroups: they stride over the list, so their number only decides how parallel the refill is.  About 1.6 % of the envs
-  // finish per step under a random policy (N / 1920 chunks of 32); the grid carries four times that, at least 64 -- and the whole
-  // list's worth (one workgroup per possible chunk) in the steps where a burst is due: every env that survives from a full reset is
-  // truncated max_episode_steps later, all in the same step (and their successors again a period later).
-  const long full = ((long)Pr.rcap + PREFETCH_MAX_ENVS - 1) / PREFETCH_MAX_ENVS;
-  long refill_blocks = std::max(64L, 4 * (n / 1920 + 1));
-  if (h->refill_blocks_override > 0) refill_blocks = h->refill_blocks_override;
-  else if (h->burst_due()) refill_blocks = full;
-  if (refill_blocks > full) refill_blocks = full;
-  dim3 grid((unsigned)(step_blocks + refill_blocks)), block(THREADS);
-  if (!step_geometry_ok(Ps, n, step_blocks)) { snprintf(h->err, sizeof(h->err), "step launch geometry does not cover the envs exactly once"); h->launch_refused = true; return; }
-  const bool epa = !h->cfg.check_collision;  // (which STEP launches can consume a penetration depth: see need_epa in the kernel)
-  const int sb = (int)step_blocks;
-  switch (h->cfg.env_kind) {
-    case URGYM_ENV_OBS: hipLaunchKernelGGL((env_step_fused<URGYM_ENV_OBS, true>), grid, block, 0, s, Ps, Pr, actions, sb); break;
-    case URGYM_ENV_STA:
-      if (epa) hipLaunchKernelGGL((env_step_fused<URGYM_ENV_STA, true>), grid, block, 0, s, Ps, Pr, actions, sb);
-      else hipLaunchKernelGGL((env_step_fused<URGYM_ENV_STA, false>), grid, block, 0, s, Ps, Pr, actions, sb);
-      break;
-    default:
-      if (epa) hipLaunchKernelGGL((env_step_fused<URGYM_ENV_DYN, true>), grid, block, 0, s, Ps, Pr, actions, sb);
-      else hipLaunchKernelGGL((env_step_fused<URGYM_ENV_DYN, false>), grid, block, 0, s, Ps, Pr, actions, sb);
-      break;
-  }
+  const int sb = h->plan.step_blocks;
+  const long grid = sb + refill_blocks(h->plan, h->steps_since_full_reset, h->cfg.max_episode_steps);
+  hipLaunchKernelGGL(h->k.fused, dim3((unsigned)grid), dim3(THREADS), 0, s, Ps, Pr, actions, sb);
 }
 
 int time_begin(Handle* h, int kind, hipStream_t s) {
@@ -1873,39 +1814,49 @@ void time_end(Handle* h, int slot, hipStream_t s) {
   h->ev_used = slot + 2;
 }
 
-int check_bound(Handle* h) {
+// the checks of a call that needs bound buffers, and its device made current
+int enter_bound(Handle* h) {
   if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
   if (!h->bound) return fail(h, URGYM_ERR_STATE, "urgym_bind() has not been called");
+  HIP_TRY(h, hipSetDevice(h->device));
   return URGYM_OK;
 }
 
-void release_prefetch(Handle* h) {
-  if (h->d_rec) { hipFree(h->d_rec); h->d_rec = nullptr; }
-  if (h->d_reci) { hipFree(h->d_reci); h->d_reci = nullptr; }
-  for (int i = 0; i < 4; i++)
-    if (h->d_rl[i]) { hipFree(h->d_rl[i]); h->d_rl[i] = nullptr; }
-  if (h->d_rcount) { hipFree(h->d_rcount); h->d_rcount = nullptr; }
+// every failure path of urgym_create and urgym_destroy: frees whatever the handle holds
+void release(Handle* h) {
+  for (void* p : {(void*)h->d_ld_scratch, (void*)h->d_sc_scratch, (void*)h->d_recs, (void*)h->d_cell, (void*)h->d_rec,
+                  (void*)h->d_reci, (void*)h->d_rl[0], (void*)h->d_rl[1], (void*)h->d_rl[2], (void*)h->d_rl[3], (void*)h->d_rcount})
+    if (p) hipFree(p);
+  for (auto e : h->ev) hipEventDestroy(e);
+  delete h;
+}
+
+// wipe every record key and every pending refill entry: the next max_episode_steps + 1 steps carry the fallback launches
+int forget_records(Handle* h) {
+  HIP_TRY(h, hipMemset(h->d_reci, 0xFF, sizeof(int32_t) * 4 * (size_t)h->cfg.num_envs));
+  HIP_TRY(h, hipMemset(h->d_rcount, 0, sizeof(int) * 5));
+  h->dirty_steps = h->cfg.max_episode_steps + 1;
+  return URGYM_OK;
 }
 
 // list `which` (0 .. 2: asynchronous, 3: synchronous) as the refill list of a launch
 void use_list(Handle* h, KParams& P, int which) {
   P.rlist = h->d_rl[which];
   P.rcount = h->d_rcount + which;
-  P.rcap = h->rl_cap[which];
+  P.rcap = h->plan.rl_cap[which];
   P.prefetch = 1;
 }
 
 int do_step(Handle* h, const float* actions, hipStream_t s) {
   KParams P = make_params(h, 1);
-  const bool pf = h->prefetch && h->cfg.auto_reset;
   int slot;
-  if (!pf) {
+  if (!h->plan.fused) {
     slot = time_begin(h, 0, s);
-    launch_mode<MODE_STEP>(h, P, actions, h->step_envs, s);
+    launch_mode<MODE_STEP>(h, P, actions, s);
     time_end(h, slot, s);
-    if (h->cfg.auto_reset && !h->inline_ori) {
+    if (h->cfg.auto_reset && !h->plan.inline_ori) {
       slot = time_begin(h, 1, s);
-      launch_mode<MODE_RESET>(h, P, nullptr, h->reset_envs, s);  // ~1 % of the envs per step: small workgroups, many CUs
+      launch_mode<MODE_RESET>(h, P, nullptr, s, h->plan.reset_envs);  // ~1 % of the envs per step: small workgroups, many CUs
       time_end(h, slot, s);
     }
   } else {
@@ -1935,14 +1886,13 @@ int do_step(Handle* h, const float* actions, hipStream_t s) {
       KParams Pf = P;
       use_list(h, Pf, 3);
       Pf.rzero = Pf.rzero2 = nullptr;
-      launch_mode<MODE_RESET>(h, Pf, nullptr, GROUP, s);
-      launch_mode<MODE_PREFETCH>(h, Pf, nullptr, 8, s, h->rl_cap[3]);
+      launch_mode<MODE_RESET>(h, Pf, nullptr, s, GROUP);
+      launch_mode<MODE_PREFETCH>(h, Pf, nullptr, s, 8, h->plan.rl_cap[3]);
       time_end(h, slot, s);
       h->dirty_steps--;
     }
     h->parity = nxt;
   }
-  if (h->launch_refused) { h->launch_refused = false; return URGYM_ERR_STATE; }
   if (h->steps_since_full_reset >= 0) h->steps_since_full_reset++;
   h->pp ^= 1;
   HIP_TRY(h, hipGetLastError());
@@ -1955,7 +1905,7 @@ int do_masked(Handle* h, const uint8_t* mask, int mode, hipStream_t s) {
   hipLaunchKernelGGL(build_list_kernel, dim3((N + 255) / 256), dim3(256), 0, s, mask, N, h->buf.done_list, h->buf.done_count + h->pp);
   KParams P = make_params(h, 0);
   if (mode == MODE_RESET) {
-    const bool pf = h->prefetch && h->cfg.auto_reset;
+    const bool pf = h->plan.fused;  // (auto-reset from prefetched records)
     if (pf) {
       if (!h->rec_seed_valid || h->rec_seed != h->seed) {  // records are keyed with the seed: a new one invalidates them all
         HIP_TRY(h, hipMemsetAsync(h->d_reci, 0xFF, sizeof(int32_t) * 4 * (size_t)N, s));
@@ -1966,24 +1916,99 @@ int do_masked(Handle* h, const uint8_t* mask, int mode, hipStream_t s) {
         // the slots the last step consumed are refilled by the NEXT step's launch; a partial reset must not lose them
         KParams Pp = P;
         use_list(h, Pp, (h->parity + 2) % 3);
-        launch_mode<MODE_PREFETCH>(h, Pp, nullptr, PREFETCH_MAX_ENVS, s, h->rl_cap[0]);
+        launch_mode<MODE_PREFETCH>(h, Pp, nullptr, s, PREFETCH_MAX_ENVS, h->plan.rl_cap[0]);
       }
       HIP_TRY(h, hipMemsetAsync(h->d_rcount, 0, 5 * sizeof(int), s));
       use_list(h, P, 3);
     }
-    launch_mode<MODE_RESET>(h, P, nullptr, GROUP, s);
+    launch_mode<MODE_RESET>(h, P, nullptr, s, GROUP);
     if (pf) {
-      launch_mode<MODE_PREFETCH>(h, P, nullptr, 8, s, h->rl_cap[3]);  // the next two episodes of every env just reset
+      launch_mode<MODE_PREFETCH>(h, P, nullptr, s, 8, h->plan.rl_cap[3]);  // the next two episodes of every env just reset
       if (mask == nullptr) h->dirty_steps = 0;                          // every env now has valid records
     }
     if (mask == nullptr) h->steps_since_full_reset = 0;                 // every step counter is 0: the truncation bursts are now predictable
   } else {
-    launch_mode<MODE_REFRESH>(h, P, nullptr, GROUP, s);
+    launch_mode<MODE_REFRESH>(h, P, nullptr, s, GROUP);
   }
   // leave the consumed counter zeroed so the next step can append to either slot
   HIP_TRY(h, hipMemsetAsync(h->buf.done_count, 0, 2 * sizeof(int32_t), s));
   HIP_TRY(h, hipGetLastError());
   return URGYM_OK;
+}
+
+// ---- the parts of urgym_create.  If one of them fails, urgym_create hands its message on to g_err and releases the handle.
+
+// The launch plan of a new handle (urgym_launch_plan.h), checked before anything is allocated.  per_cu: the residency of the kernel
+// the steady-state step launches.  The API over-reports near the LDS limit (DESIGN.md section 4 "toolchain hazards"); the residency
+// census, tools/diag/census.hip, is what the cap URGYM_RESIDENT = 3 rests on.
+int plan_handle(Handle* h, const Tuning& t) {
+  h->k = kernels_for(h->cfg);
+  h->plan = plan_paths(h->cfg.env_kind, h->cfg.num_envs, h->cfg.auto_reset != 0, t);
+  int cus = 256, per_cu = 3;
+  hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
+  const hipError_t oe = h->plan.fused ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, h->k.fused, THREADS, 0)
+                                      : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, h->k.mode[MODE_STEP], THREADS, 0);
+  if (oe != hipSuccess || per_cu < 1) per_cu = 3;
+  if (per_cu > URGYM_RESIDENT) per_cu = URGYM_RESIDENT;
+  plan_grids(h->plan, cus, per_cu, t);
+  const LaunchPlan& p = h->plan;
+  if (t.verbose) {
+    fprintf(stderr, "[urgym] device %d: %d CUs x %d resident step workgroups; N = %d -> %d envs per step workgroup (%d of them, then %d envs each), %d per reset workgroup\n[urgym] prefetched episode records: %s\n",
+            h->device, cus, per_cu, p.num_envs, p.step_envs, p.big_blocks > 0 ? p.big_blocks : p.step_blocks, p.tail_envs, p.reset_envs, p.prefetch ? "on" : "off");
+  }
+  if (!step_geometry_ok(p)) return fail(h, URGYM_ERR_STATE, "urgym_create: the step launch geometry does not cover the envs exactly once");
+  return URGYM_OK;
+}
+
+// the constant tables: chain constants, and the support map of the link hulls (built once per process, uploaded per handle)
+int upload_tables(Handle* h) {
+  const HostTables* tabs = nullptr;
+  try {
+    tabs = &build_host_tables();
+  } catch (const std::exception& ex) {  // (std::system_error of its worker threads, std::bad_alloc)
+    char msg[256];
+    snprintf(msg, sizeof(msg), "urgym_create: building the support map failed: %s", ex.what());
+    return fail(h, URGYM_ERR_STATE, msg);
+  }
+  if (!tabs->ok) return fail(h, URGYM_ERR_STATE, "urgym_create: support map has more records than a 16-bit cell code addresses");
+  DevTables t;
+  memcpy(t.joint_rot, UR5E_JOINT_ROT, sizeof(t.joint_rot));
+  memcpy(t.joint_xyz, UR5E_JOINT_XYZ, sizeof(t.joint_xyz));
+  memcpy(t.capsule, UR5E_CAPSULE, sizeof(t.capsule));
+  HIP_TRY(h, hipMemcpyToSymbol(HIP_SYMBOL(c_tab), &t, sizeof(t)));
+  const size_t rec_bytes = tabs->recs.size() * sizeof(CandRec), cell_bytes = tabs->cell.size() * sizeof(unsigned short);
+  HIP_TRY(h, hipMalloc((void**)&h->d_recs, rec_bytes));
+  HIP_TRY(h, hipMemcpy(h->d_recs, tabs->recs.data(), rec_bytes, hipMemcpyHostToDevice));
+  HIP_TRY(h, hipMalloc((void**)&h->d_cell, cell_bytes));
+  HIP_TRY(h, hipMemcpy(h->d_cell, tabs->cell.data(), cell_bytes, hipMemcpyHostToDevice));
+  return URGYM_OK;
+}
+
+// the library's own scratch: link distances and set-up cache of the running step; episode records and refill lists
+int allocate_scratch(Handle* h) {
+  const size_t n = (size_t)h->cfg.num_envs;
+  HIP_TRY(h, hipMalloc((void**)&h->d_ld_scratch, sizeof(double) * 5 * n));
+  if (h->plan.setup_cache != 0)
+    HIP_TRY(h, hipMalloc((void**)&h->d_sc_scratch, sizeof(double) * (h->plan.setup_cache >= 2 ? SC_FIELDS : SC_FRAMES) * n));
+  if (!h->plan.prefetch) return URGYM_OK;
+  HIP_TRY(h, hipMalloc((void**)&h->d_rec, sizeof(double) * 2 * REC_FIELDS * n));
+  HIP_TRY(h, hipMalloc((void**)&h->d_reci, sizeof(int32_t) * 4 * n));
+  for (int i = 0; i < 4; i++) HIP_TRY(h, hipMalloc((void**)&h->d_rl[i], sizeof(int2) * (size_t)h->plan.rl_cap[i]));
+  HIP_TRY(h, hipMalloc((void**)&h->d_rcount, sizeof(int) * 5));
+  return forget_records(h);  // no record exists yet
+}
+
+// the neutral pose's end-effector frame (the first six slots of every reset observation), by the device code itself
+int eval_neutral_pose(Handle* h) {
+  double* dq = nullptr;  // the joint vector, then the six floats of the pose
+  hipError_t e = hipMalloc((void**)&dq, sizeof(double) * 9);
+  if (e == hipSuccess) e = hipMemcpy(dq, h->cfg.neutral_q, sizeof(double) * 6, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(ee_pose_kernel, dim3(1), dim3(1), 0, 0, dq, (float*)(dq + 6));
+    e = hipMemcpy(h->neutral_ach, dq + 6, sizeof(float) * 6, hipMemcpyDeviceToHost);
+  }
+  if (dq) hipFree(dq);
+  return e == hipSuccess ? URGYM_OK : fail(h, URGYM_ERR_HIP, "urgym_create: neutral pose", e);
 }
 
 }  // namespace
@@ -2022,166 +2047,14 @@ int urgym_create(const urgym_config* cfg, int device, void** handle) {
   h->cfg = *cfg;
   h->device = device;
   urgym_obs_dims(cfg->env_kind, &h->obs_dim, &h->goal_dim);
-  // constant tables
-  DevTables t;
-  memcpy(t.joint_rot, UR5E_JOINT_ROT, sizeof(t.joint_rot));
-  memcpy(t.joint_xyz, UR5E_JOINT_XYZ, sizeof(t.joint_xyz));
-  memcpy(t.capsule, UR5E_CAPSULE, sizeof(t.capsule));
-  const HostTables& tabs = build_host_tables();
-  if (!tabs.ok) { delete h; return fail(nullptr, URGYM_ERR_STATE, "urgym_create: support map has more records than a 16-bit cell code addresses"); }
-  e = hipMemcpyToSymbol(HIP_SYMBOL(c_tab), &t, sizeof(t));
-  if (e != hipSuccess) { delete h; return fail(nullptr, URGYM_ERR_HIP, "hipMemcpyToSymbol(c_tab)", e); }
-  auto upload = [&](void** dst, const void* src, size_t bytes) -> hipError_t {
-    hipError_t r = hipMalloc(dst, bytes);
-    if (r != hipSuccess) return r;
-    return hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
-  };
-  e = hipMalloc((void**)&h->d_ld_scratch, sizeof(double) * 5 * (size_t)cfg->num_envs);
-  // URGYM_SETUP_CACHE (tuning / tests): 0 = every draw recomputes its operands, 1 (default) = sin / cos of the joints + obstacle pose
-  // cached, 2 = the link frames too.  Measured at N = 65536 Dyn (profiles/r2/exp_setup_cache_levels.txt): 186.3 / 195.4 / 197.7 M
-  // env-steps/s at 108 / 140 / 201 MB of L2 <-> fabric traffic per launch: the frames buy 1 % for 61 MB, so they stay opt-in.
-  const int sc_level = getenv("URGYM_SETUP_CACHE") ? atoi(getenv("URGYM_SETUP_CACHE")) : 1;
-  h->sc_frames = sc_level >= 2;
-  if (e == hipSuccess && sc_level != 0)
-    e = hipMalloc((void**)&h->d_sc_scratch, sizeof(double) * (h->sc_frames ? SC_FIELDS : SC_FRAMES) * (size_t)cfg->num_envs);
-  if (e == hipSuccess) e = upload((void**)&h->d_recs, tabs.recs.data(), tabs.recs.size() * sizeof(CandRec));
-  if (e == hipSuccess) e = upload((void**)&h->d_cell, tabs.cell.data(), tabs.cell.size() * sizeof(unsigned short));
-  if (e != hipSuccess) {
-    if (h->d_ld_scratch) hipFree(h->d_ld_scratch);
-    if (h->d_sc_scratch) hipFree(h->d_sc_scratch);
-    if (h->d_recs) hipFree(h->d_recs);
-    if (h->d_cell) hipFree(h->d_cell);
-    delete h;
-    return fail(nullptr, URGYM_ERR_HIP, "hull table upload", e);
-  }
-  // Envs per step workgroup (E <= STEP_MAX_ENVS = 128).  Measured on MI355X (DESIGN.md "launch geometry"): the kernel is bound
-  // by the latency of the GJK iteration chains; a workgroup's lifetime grows slowly with E (145 us at 46 envs, 177 us at 64),
-  // while every additional ROUND of workgroups costs a whole lifetime plus a ragged tail.  So the fewest rounds win:
-  //   * N fits one round of <= 128-env workgroups: E = ceil(N / slots), but at least 8, rounded up to a multiple of 8 below
-  //     64 (64-byte runs of the float64 state arrays) -- 65536 envs -> 91 per workgroup, all 721 resident at once; 16384 -> 24;
-  //   * otherwise R = ceil(N / (128 slots)) rounds of equal workgroups: E = ceil(N / (R slots)).
-  // URGYM_STEP_ENVS / URGYM_STEP_TIERS / URGYM_RESET_ENVS override the choices (tuning / tests).
-  {
-    int cus = 256, per_cu = 3;
-    hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-    hipError_t oe = hipSuccess;
-    // (of the kernel instance the steady-state step really launches: the fused STEP + PREFETCH kernel for the obstacle envs with
-    //  auto-reset, the plain STEP kernel otherwise.  The API over-reports near the LDS limit -- DESIGN.md section 4 "toolchain hazards";
-    //  the residency census, tools/diag/census.hip, is what the cap URGYM_RESIDENT = 3 below rests on.)
-    const bool fused = cfg->env_kind != URGYM_ENV_ORI && cfg->auto_reset && !(getenv("URGYM_PREFETCH") && atoi(getenv("URGYM_PREFETCH")) == 0);
-    const bool epa = !cfg->check_collision;
-    auto occ = [&](auto kernel) { return hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, THREADS, 0); };
-    switch (cfg->env_kind) {
-      case URGYM_ENV_ORI: oe = occ(env_kernel<URGYM_ENV_ORI, MODE_STEP, false>); break;
-      case URGYM_ENV_OBS: oe = fused ? occ(env_step_fused<URGYM_ENV_OBS, true>) : occ(env_kernel<URGYM_ENV_OBS, MODE_STEP, true>); break;
-      case URGYM_ENV_STA:
-        if (fused) oe = epa ? occ(env_step_fused<URGYM_ENV_STA, true>) : occ(env_step_fused<URGYM_ENV_STA, false>);
-        else oe = epa ? occ(env_kernel<URGYM_ENV_STA, MODE_STEP, true>) : occ(env_kernel<URGYM_ENV_STA, MODE_STEP, false>);
-        break;
-      default:
-        if (fused) oe = epa ? occ(env_step_fused<URGYM_ENV_DYN, true>) : occ(env_step_fused<URGYM_ENV_DYN, false>);
-        else oe = epa ? occ(env_kernel<URGYM_ENV_DYN, MODE_STEP, true>) : occ(env_kernel<URGYM_ENV_DYN, MODE_STEP, false>);
-        break;
-    }
-    if (oe != hipSuccess || per_cu < 1) per_cu = 3;
-    if (per_cu > URGYM_RESIDENT) per_cu = URGYM_RESIDENT;
-    long slots = (long)cus * per_cu;
-    const long n = cfg->num_envs;
-    // prefetched episode records (below): the refill of ~2 % of the envs runs beside the step kernel, 32 envs per workgroup
-    bool want_prefetch = cfg->env_kind != URGYM_ENV_ORI;
-    if (const char* ov = getenv("URGYM_PREFETCH")) want_prefetch = want_prefetch && atoi(ov) != 0;  // (Ori: inline reset, below)
-    if (want_prefetch && cfg->auto_reset) {
-      const long refill = n / 1600;
-      slots -= refill < slots / 8 ? refill : slots / 8;
-    }
-    const long rounds = (n + slots * STEP_MAX_ENVS - 1) / (slots * STEP_MAX_ENVS);
-    long envs = (n + slots * rounds - 1) / (slots * rounds);
-    if (envs < 8) envs = 8;
-    if (envs < GROUP) envs = (envs + 7) / 8 * 8;
-    if (envs > STEP_MAX_ENVS) envs = STEP_MAX_ENVS;
-    h->step_envs = (int)envs;
-    // One round, three workgroups per CU: the first 2 x CUs workgroups (two per CU, dispatched first) serve E1 envs each, the third
-    // one of a CU 0.7 E1.  A CU with three resident workgroups advances each of them more slowly than one with two, and the third
-    // starts last; giving it less work evens the finishing times out (N = 65536: 512 x 100 + 205 x 70 instead of 721 x 91, +5 %,
-    // profiles/r2/exp_two_tier_one_round.jsonl).  URGYM_STEP_TIERS=0 keeps the uniform geometry.
-    if (rounds == 1 && per_cu == 3 && slots > 2L * cus) {
-      const long big = 2L * cus, rest = slots - big;
-      const long e1 = (10 * n + (10 * big + 7 * rest) - 1) / (10 * big + 7 * rest);
-      if (e1 >= 64 && e1 <= STEP_MAX_ENVS && n > big * e1) {  // (below ~40 000 envs the uniform geometry is as fast or faster)
-        const long e2 = (n - big * e1 + rest - 1) / rest;
-        h->step_envs = (int)e1; h->big_blocks = (int)big; h->tail_envs = (int)(e2 < 1 ? 1 : e2);
-      }
-    }
-    // auto-reset kernel: ~1 % of the envs finish per step; keep that to about one workgroup per CU (4 envs at N = 65536,
-    // 8 at 262144): it is pure latency, smaller workgroups shorten the wave-wide maxima, more than one per CU queue up
-    int renvs = 4;
-    while (renvs < GROUP && n / 100 > (long)renvs * (cus + cus / 4)) renvs *= 2;
-    h->reset_envs = renvs;
-    if (const char* ov = getenv("URGYM_STEP_ENVS")) {
-      const int v = atoi(ov);
-      if (v >= 1 && v <= STEP_MAX_ENVS) { h->step_envs = v; h->big_blocks = 0; h->tail_envs = 0; }
-    }
-    if (const char* ov = getenv("URGYM_STEP_TIERS")) {  // "E1,B,E2": B workgroups of E1 envs, then workgroups of E2 (tuning / tests)
-      int e1 = 0, b = 0, e2 = 0;
-      if (sscanf(ov, "%d,%d,%d", &e1, &b, &e2) == 3 && e1 >= 1 && e1 <= STEP_MAX_ENVS && e2 >= 1 && e2 <= STEP_MAX_ENVS && b >= 1) {
-        h->step_envs = e1; h->big_blocks = b; h->tail_envs = e2;
-      } else if (atoi(ov) == 0) {  // "0": uniform workgroups
-        h->step_envs = (int)envs; h->big_blocks = 0; h->tail_envs = 0;
-      }
-    }
-    if (const char* ov = getenv("URGYM_REFILL_BLOCKS")) {
-      const int r = atoi(ov);
-      if (r >= 1) h->refill_blocks_override = r;
-    }
-    if (const char* ov = getenv("URGYM_RESET_ENVS")) {
-      const int r = atoi(ov);
-      if (r >= 1 && r <= MAX_ENVS) h->reset_envs = r;
-    }
-    // prefetched episode records: on unless URGYM_PREFETCH=0 (then finished envs are reset by a kernel after each step)
-    // (Ori's reset is a goal draw, no distance query: there the extra launches cost more than the reset kernel they replace)
-    {  // the neutral pose's end-effector frame (the first six slots of every reset observation), by the device code itself
-      double* dq = nullptr;
-      float* dout = nullptr;
-      hipError_t ne = hipMalloc((void**)&dq, sizeof(double) * 6);
-      if (ne == hipSuccess) ne = hipMalloc((void**)&dout, sizeof(float) * 6);
-      if (ne == hipSuccess) ne = hipMemcpy(dq, cfg->neutral_q, sizeof(double) * 6, hipMemcpyHostToDevice);
-      if (ne == hipSuccess) {
-        hipLaunchKernelGGL(ee_pose_kernel, dim3(1), dim3(1), 0, 0, dq, dout);
-        ne = hipMemcpy(h->neutral_ach, dout, sizeof(float) * 6, hipMemcpyDeviceToHost);
-      }
-      if (dq) hipFree(dq);
-      if (dout) hipFree(dout);
-      // UR5OriReach-v1: inline reset unless URGYM_PREFETCH=0 asks for the reset kernel (the switch of the obstacle envs, same meaning)
-      bool want_inline = cfg->env_kind == URGYM_ENV_ORI && ne == hipSuccess;
-      if (const char* ov = getenv("URGYM_PREFETCH")) want_inline = want_inline && atoi(ov) != 0;
-      h->inline_ori = want_inline;
-    }
-    h->prefetch = want_prefetch;
-    if (h->prefetch) {
-      const size_t nn = (size_t)n;
-      h->rl_cap[0] = h->rl_cap[1] = h->rl_cap[2] = (int)n;   // at most one entry per env and step: no entry is ever dropped
-      h->rl_cap[3] = (int)(2 * n);
-      h->dirty_steps = cfg->max_episode_steps + 1;             // no record exists yet
-      hipError_t pe = hipMalloc((void**)&h->d_rec, sizeof(double) * 2 * REC_FIELDS * nn);
-      if (pe == hipSuccess) pe = hipMalloc((void**)&h->d_reci, sizeof(int32_t) * 4 * nn);
-      for (int i = 0; i < 4 && pe == hipSuccess; i++) pe = hipMalloc((void**)&h->d_rl[i], sizeof(int2) * (size_t)h->rl_cap[i]);
-      if (pe == hipSuccess) pe = hipMalloc((void**)&h->d_rcount, sizeof(int) * 5);
-      if (pe == hipSuccess) pe = hipMemset(h->d_reci, 0xFF, sizeof(int32_t) * 4 * nn);
-      if (pe == hipSuccess) pe = hipMemset(h->d_rcount, 0, sizeof(int) * 5);
-      if (pe != hipSuccess) {
-        release_prefetch(h);
-        if (h->d_ld_scratch) hipFree(h->d_ld_scratch);
-        if (h->d_sc_scratch) hipFree(h->d_sc_scratch);
-        if (h->d_recs) hipFree(h->d_recs);
-        if (h->d_cell) hipFree(h->d_cell);
-        delete h;
-        return fail(nullptr, URGYM_ERR_HIP, "prefetch buffers", pe);
-      }
-    }
-    if (getenv("URGYM_VERBOSE"))
-      fprintf(stderr, "[urgym] device %d: %d CUs x %d resident step workgroups; N = %ld -> %d envs per step workgroup (%d of them, then %d envs each), %d per reset workgroup\n",
-              device, cus, per_cu, n, h->step_envs, h->big_blocks > 0 ? h->big_blocks : (int)((n + h->step_envs - 1) / h->step_envs), h->tail_envs, h->reset_envs);
-    if (getenv("URGYM_VERBOSE")) fprintf(stderr, "[urgym] prefetched episode records: %s\n", h->prefetch ? "on" : "off");
+  int rc = plan_handle(h, read_tuning());
+  if (rc == URGYM_OK) rc = upload_tables(h);
+  if (rc == URGYM_OK) rc = allocate_scratch(h);
+  if (rc == URGYM_OK) rc = eval_neutral_pose(h);
+  if (rc != URGYM_OK) {
+    memcpy(g_err, h->err, sizeof(g_err));
+    release(h);
+    return rc;
   }
   *handle = h;
   return URGYM_OK;
@@ -2191,13 +2064,7 @@ int urgym_destroy(void* handle) {
   Handle* h = (Handle*)handle;
   if (!h) return URGYM_OK;
   hipSetDevice(h->device);
-  release_prefetch(h);
-  for (auto e : h->ev) hipEventDestroy(e);
-  if (h->d_ld_scratch) hipFree(h->d_ld_scratch);
-  if (h->d_sc_scratch) hipFree(h->d_sc_scratch);
-  if (h->d_recs) hipFree(h->d_recs);
-  if (h->d_cell) hipFree(h->d_cell);
-  delete h;
+  release(h);
   return URGYM_OK;
 }
 
@@ -2211,12 +2078,10 @@ int urgym_bind(void* handle, const urgym_buffers* b) {
     return fail(h, URGYM_ERR_ARG, "urgym_bind: a required buffer pointer is null");
   if (obst && (!b->obst_start || !b->obst_end || !b->obst_pos || !b->obst_quat || !b->obst_vel || !b->link_dist))
     return fail(h, URGYM_ERR_ARG, "urgym_bind: an obstacle buffer pointer is null");
-  if (h->prefetch) {  // records belong to the state that was bound before
+  if (h->plan.prefetch) {  // records belong to the state that was bound before
     hipSetDevice(h->device);
-    HIP_TRY(h, hipMemset(h->d_reci, 0xFF, sizeof(int32_t) * 4 * (size_t)h->cfg.num_envs));
-    HIP_TRY(h, hipMemset(h->d_rcount, 0, sizeof(int) * 5));
+    if (int rc = forget_records(h)) return rc;
     h->rec_seed_valid = false;
-    h->dirty_steps = h->cfg.max_episode_steps + 1;
   }
   h->steps_since_full_reset = -1;
   h->buf = *b;
@@ -2226,9 +2091,7 @@ int urgym_bind(void* handle, const urgym_buffers* b) {
 
 int urgym_reset(void* handle, const uint8_t* mask_dev, uint64_t seed, void* stream) {
   Handle* h = (Handle*)handle;
-  int rc = check_bound(h);
-  if (rc) return rc;
-  HIP_TRY(h, hipSetDevice(h->device));
+  if (int rc = enter_bound(h)) return rc;
   if (seed != UINT64_MAX) h->seed = seed;
   return do_masked(h, mask_dev, MODE_RESET, (hipStream_t)stream);
 }
@@ -2236,7 +2099,7 @@ int urgym_reset(void* handle, const uint8_t* mask_dev, uint64_t seed, void* stre
 int urgym_invalidate_records(void* handle) {
   Handle* h = (Handle*)handle;
   if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
-  if (h->prefetch) {
+  if (h->plan.prefetch) {
     // Really invalidate (like urgym_bind): wipe every record key and every pending refill entry, so that EVERY env takes the
     // kernel fallback at its first finish and comes out of it with fresh records for its next two episodes -- which is what makes the
     // max_episode_steps + 1 window sufficient.  Merely opening the window is not: after an episode_id edit one of an env's two slots
@@ -2245,8 +2108,7 @@ int urgym_invalidate_records(void* handle) {
     // The caller has just edited the bound buffers from the host side, i.e. between launches: wait for whatever is in flight.
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipDeviceSynchronize());
-    HIP_TRY(h, hipMemset(h->d_reci, 0xFF, sizeof(int32_t) * 4 * (size_t)h->cfg.num_envs));
-    HIP_TRY(h, hipMemset(h->d_rcount, 0, sizeof(int) * 5));
+    if (int rc = forget_records(h)) return rc;
   }
   h->dirty_steps = h->cfg.max_episode_steps + 1;
   h->steps_since_full_reset = -1;  // step counters were edited: no longer known when many envs finish at once
@@ -2255,10 +2117,8 @@ int urgym_invalidate_records(void* handle) {
 
 int urgym_derive_obstacle_motion(void* handle, void* stream) {
   Handle* h = (Handle*)handle;
-  int rc = check_bound(h);
-  if (rc) return rc;
+  if (int rc = enter_bound(h)) return rc;
   if (h->cfg.env_kind == URGYM_ENV_ORI) return URGYM_OK;  // no obstacle
-  HIP_TRY(h, hipSetDevice(h->device));
   const int N = h->cfg.num_envs;
   hipLaunchKernelGGL(derive_displacement_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->buf.obst_vel, N, h->cfg.dt);
   HIP_TRY(h, hipGetLastError());
@@ -2267,27 +2127,22 @@ int urgym_derive_obstacle_motion(void* handle, void* stream) {
 
 int urgym_refresh(void* handle, const uint8_t* mask_dev, void* stream) {
   Handle* h = (Handle*)handle;
-  int rc = check_bound(h);
-  if (rc) return rc;
-  HIP_TRY(h, hipSetDevice(h->device));
+  if (int rc = enter_bound(h)) return rc;
   return do_masked(h, mask_dev, MODE_REFRESH, (hipStream_t)stream);
 }
 
 int urgym_step(void* handle, const float* actions_dev, void* stream) {
   Handle* h = (Handle*)handle;
-  int rc = check_bound(h);
-  if (rc) return rc;
+  if (int rc = enter_bound(h)) return rc;
   if (!actions_dev) return fail(h, URGYM_ERR_ARG, "urgym_step: null actions");
-  HIP_TRY(h, hipSetDevice(h->device));
   return do_step(h, actions_dev, (hipStream_t)stream);
 }
 
 int urgym_rollout(void* handle, const float* actions_dev, int num_steps, void* stream) {
   Handle* h = (Handle*)handle;
-  int rc = check_bound(h);
+  int rc = enter_bound(h);
   if (rc) return rc;
   if (!actions_dev || num_steps < 0) return fail(h, URGYM_ERR_ARG, "urgym_rollout: bad argument");
-  HIP_TRY(h, hipSetDevice(h->device));
   for (int k = 0; k < num_steps; k++) {
     rc = do_step(h, actions_dev + (size_t)k * h->cfg.num_envs * 6, (hipStream_t)stream);
     if (rc) return rc;
@@ -2333,8 +2188,8 @@ int urgym_query_timing(void* handle, double* step_us, double* reset_us, int* lau
   Handle* h = (Handle*)handle;
   if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
   if (!h->timing) return fail(h, URGYM_ERR_STATE, "timing not enabled");
-  double acc[3] = {0, 0, 0};
-  int cnt[3] = {0, 0, 0};
+  double acc[2] = {0, 0};
+  int cnt[2] = {0, 0};
   for (size_t i = 0; i + 1 < h->ev_used; i += 2) {
     HIP_TRY(h, hipEventSynchronize(h->ev[i + 1]));
     float ms = 0;
@@ -2345,7 +2200,6 @@ int urgym_query_timing(void* handle, double* step_us, double* reset_us, int* lau
   }
   if (step_us) *step_us = cnt[0] ? acc[0] / cnt[0] : 0.0;
   if (reset_us) *reset_us = cnt[1] ? acc[1] / cnt[1] : 0.0;
-  h->last_refill_us = cnt[2] ? acc[2] / cnt[2] : 0.0;
   if (launches) *launches = cnt[0];
   h->ev_used = 0;
   return URGYM_OK;
@@ -2363,7 +2217,7 @@ int urgym_debug_stamps(unsigned long long* out, int count) {
 int urgym_query_refill_timing(void* handle, double* refill_us) {
   Handle* h = (Handle*)handle;
   if (!h || !refill_us) return fail(h, URGYM_ERR_ARG, "urgym_query_refill_timing: null argument");
-  *refill_us = h->last_refill_us;
+  *refill_us = 0.0;  // the refill rides in the step's launch (env_step_fused): there is no launch of its own to time
   return URGYM_OK;
 }
 
