@@ -167,11 +167,9 @@ int urgym_obs_dims(int env_kind, int* obs_dim, int* goal_dim);
  * changes a result (scheduling / tuning / tests): URGYM_STEP_ENVS (envs per workgroup of the step kernel, 1..128),
  * URGYM_STEP_TIERS="E1,B,E2" (B workgroups of E1 envs, then workgroups of E2), URGYM_RESET_ENVS (envs per workgroup of the
  * auto-reset kernel, 1..64), URGYM_PREFETCH (0: reset finished envs with a kernel after each step instead of inline from
- * prefetched episode records), URGYM_SETUP_CACHE (0: every draw of a query recomputes the joint sines / cosines instead of
- * reading them from the per-env cache; 1 = default; 2: the cache also carries the link frames, +576 B per env),
- * URGYM_STEP_TIERS=0 (uniform workgroups where the default would be two-tier), URGYM_REFILL_BLOCKS (refill workgroups per
- * step launch of the obstacle envs, >= 1; default: a policy that widens the grid in the steps where many envs finish),
- * URGYM_VERBOSE (print the chosen geometry to stderr). */
+ * prefetched episode records), URGYM_STEP_TIERS=0 (uniform workgroups where the default would be two-tier),
+ * URGYM_REFILL_BLOCKS (refill workgroups per step launch of the obstacle envs, >= 1; default: a policy that widens the grid in
+ * the steps where many envs finish), URGYM_VERBOSE (print the chosen geometry to stderr). */
 int urgym_create(const urgym_config* cfg, int device, void** handle);
 int urgym_destroy(void* handle);
 

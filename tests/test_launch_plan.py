@@ -11,8 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SO = os.path.join(HERE, "_build", "libplan_harness.so")
 ORI, OBS, DYN, STA = 0, 1, 2, 3
-TUNING = ["URGYM_STEP_ENVS", "URGYM_STEP_TIERS", "URGYM_RESET_ENVS", "URGYM_REFILL_BLOCKS", "URGYM_PREFETCH", "URGYM_SETUP_CACHE",
-          "URGYM_VERBOSE"]
+TUNING = ["URGYM_STEP_ENVS", "URGYM_STEP_TIERS", "URGYM_RESET_ENVS", "URGYM_REFILL_BLOCKS", "URGYM_PREFETCH", "URGYM_VERBOSE"]
 FIELDS = ["step_envs", "big_blocks", "tail_envs", "step_blocks", "reset_envs", "prefetch", "fused", "inline_ori", "setup_cache",
           "rl_cap0", "rl_cap1", "rl_cap2", "rl_cap3", "refill_blocks", "ok"]
 
@@ -78,12 +77,7 @@ def test_paths(harness, env):
     assert (dyn_manual["prefetch"], dyn_manual["fused"]) == (1, 0)
     env.setenv("URGYM_PREFETCH", "0")
     assert [plan(harness, k, 1000)[f] for k in (DYN, ORI) for f in ("prefetch", "fused", "inline_ori")] == [0] * 6
-    for value, level in [(None, 1), ("0", 0), ("1", 1), ("2", 2), ("5", 2), ("-1", 1)]:
-        if value is None:
-            env.delenv("URGYM_SETUP_CACHE", raising=False)
-        else:
-            env.setenv("URGYM_SETUP_CACHE", value)
-        assert plan(harness, DYN, 1000)["setup_cache"] == level
+    assert [p["setup_cache"] for p in (dyn, ori, dyn_manual, plan(harness, DYN, 1000))] == [1] * 4  # one form of the set-up cache
 
 
 def test_overrides(harness, env):

@@ -47,22 +47,14 @@ using namespace urgym;
 namespace {
 
 // GROUP, STEP_MAX_ENVS, MAX_ENVS, PREFETCH_MAX_ENVS: urgym_launch_plan.h
-#ifndef URGYM_WAVES
-#define URGYM_WAVES 4
-#endif
-constexpr int WAVES = URGYM_WAVES;  // waves per workgroup
+constexpr int WAVES = 4;  // waves per workgroup
 constexpr int THREADS = GROUP * WAVES;
 constexpr uint32_t NO_ITEM = 0xFFFFFFFFu;
-#ifndef URGYM_REFILL_MIN
-#define URGYM_REFILL_MIN 16
-#endif
-constexpr int REFILL_MIN = URGYM_REFILL_MIN;
-// Resident STEP workgroups per CU the kernels are compiled for (launch bounds -> VGPR budget: 3 -> 168, 2 -> 256).  3 is the product;
-// 2 exists to MEASURE the register-rich variant (profiles/r3/EXPERIMENTS.md), it is not shipped.
-#ifndef URGYM_RESIDENT
-#define URGYM_RESIDENT 3
-#endif
-constexpr int SC_FRAMES = 19, SC_FIELDS = SC_FRAMES + 72;  // rows of KParams::sc_scratch
+constexpr int REFILL_MIN = 16;
+// Resident STEP / PREFETCH workgroups per CU the kernels are compiled for (launch bounds -> VGPR budget 168) and the cap of the
+// step grid's residency (plan_handle)
+constexpr int RESIDENT = 3;
+constexpr int SC_ROWS = 19;  // rows of KParams::sc_scratch
 // bits of the per-env culling mask: table vs links 2..6, track vs links 2..6, the nine self pairs
 constexpr int PAIR_TABLE = 0, PAIR_TRACK = 5, PAIR_SELF = 10;
 __host__ __device__ constexpr int self_pair_bit(int la, int lb) {  // (1,3)(1,4)(1,5)(1,6)(2,4)(2,5)(2,6)(3,5)(3,6)
@@ -118,17 +110,16 @@ struct KParams {
   int* rcount;      // number of entries in rlist
   int rcap;         // capacity of rlist
   double* ld_scratch;  // [5][N]: the link distances of the running step (STEP keeps them here, not in LDS)
-  double* sc_scratch;  // [SC_FIELDS][N]: STEP's per-env set-up cache, written by the env's P1 lane and read by every later draw of the
+  double* sc_scratch;  // [SC_ROWS][N]: STEP's per-env set-up cache, written by the env's P1 lane and read by every later draw of the
                        // same workgroup: rows 2k / 2k+1 = sin / cos of joint k after the action, rows 12..18 = obstacle position +
                        // quaternion after this step's motion (the six float64 sincos of a full forward-kinematics pass were three
-                       // quarters of a set-up); with check_collision, rows SC_FRAMES + 12 (link - 1) .. + 11 = the frame of each
-                       // link from P1's culling pass (3 x 3 rotation, then position), so that a draw loads its operand frame
-                       // instead of multiplying the chain up again.
+                       // quarters of a set-up).  Caching the link frames of P1's culling pass as well (72 more rows) was measured
+                       // at +1 % env-steps/s for +61 MB of L2 <-> fabric traffic per launch (N = 65536 Dyn: 186.3 M without the
+                       // cache, 195.4 M with these rows, 197.7 M with the frames; profiles/r2/exp_setup_cache_levels.txt), and dropped.
   int* rzero;       // a list counter this launch arms (sets to 0) for a later launch, or null
   int* rzero2;      // a second one
   int fallback_on;  // STEP with prefetch: 1 = the RESET / PREFETCH fallback launches follow this step (records may be stale)
   int prefetch;     // 1: STEP resets finished envs inline from valid records; RESET files refill entries
-  int sc_frames;    // 1: sc_scratch also carries the link frames (rows SC_FRAMES ..)
   int inline_ori;   // 1: STEP of UR5OriReach-v1 resets finished envs inline (its reset is one goal draw, reach.py:197-200): no RESET launch
   float neutral_ach[6];  // end-effector position + Euler angles of the neutral pose, float32 as _get_obs casts them (set at create)
 };
@@ -503,25 +494,6 @@ __device__ __forceinline__ void obstacle_of_step(const KParams& P, int n, double
   }
 }
 
-// Diagnostic build only (-DURGYM_STAMPS): per-wave s_memtime stamps of the step kernel's phases (tools/phase_stamps.py).
-// The stamps go to a buffer of their own; no output value depends on them.  Not compiled into the product.
-#ifdef URGYM_STAMPS
-#ifndef URGYM_STAMP_MODE
-#define URGYM_STAMP_MODE 0  /* MODE_STEP; 1 = the auto-reset kernel */
-#endif
-constexpr int STAMP_BLOCKS = 8192, STAMP_SLOTS = 44;  // 0..11 phases (tools/phase_stamps.py), 12..17 + 20..23 cycles per section of the loop, 24..43 lane counters
-__device__ unsigned long long g_stamps[STAMP_BLOCKS * WAVES * STAMP_SLOTS];
-#define STAMP(k, v)                                                                                         \
-  do {                                                                                                      \
-    if (MODE == URGYM_STAMP_MODE && lane == 0 && bidx < STAMP_BLOCKS)                                              \
-      g_stamps[((size_t)bidx * WAVES + wv) * STAMP_SLOTS + (k)] = (unsigned long long)(v);                  \
-  } while (0)
-#define STAMP_TIME(k) STAMP(k, __builtin_amdgcn_s_memtime())
-#else
-#define STAMP(k, v) do {} while (0)
-#define STAMP_TIME(k) do {} while (0)
-#endif
-
 // LDS of one workgroup, per launch mode.  A struct (not function-local __shared__ arrays) so that the fused step launch can
 // overlay the layouts of its two kinds of workgroups (STEP and PREFETCH) in one allocation.
 template <int MODE>
@@ -556,9 +528,6 @@ struct EnvLds {
   double s_kind[(MODE == MODE_STEP) ? 8 : 1][5];
   // ... and per-lane slots
   double s_pose[GJK_SLOT_DOUBLES][THREADS];  // GJK operand: pose of shape A in B's frame + the simplex
-#ifdef URGYM_STAMPS
-  unsigned long long s_clk[WAVES][PROF_WORDS];  // diagnostic build: per-wave profile of the loop (urgym_device.h: section clock + lane counters)
-#endif
 };
 
 // WITH_EPA: compiled with the penetration-depth phase (the host picks the instance: a STEP launch of Dyn / Sta with the
@@ -658,11 +627,6 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
     s_flags[tid] = 0;
     s_pairs[tid] = 0;
   }
-  STAMP_TIME(0);
-  STAMP(8, __builtin_amdgcn_s_memrealtime());
-#ifdef URGYM_STAMPS
-  { unsigned hw; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw)); unsigned xcc; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc)); STAMP(10, hw); STAMP(11, xcc); }
-#endif
   __syncthreads();
   // ---- P1 (waves 0..G-1, one lane per env slot): which env, joint update, obstacle motion, and the conservative
   //      bounding-capsule culling of the table / track / self pairs of check_collision (pyb_setup.py:407-427) -> LDS
@@ -713,7 +677,7 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
     const bool live = (n >= 0 && finite);
     // (the set-up cache serves the draws of closest-distance queries: a launch that runs none -- UR5OriReach-v1 with the collision checks
     //  off -- does not fill it; its six sin / cos evaluations were a third of that launch's span)
-    const bool use_cache = (MODE == MODE_STEP) && P.sc_scratch != nullptr && (HAS_OBST || cfg.check_collision);
+    const bool use_cache = (MODE == MODE_STEP) && (HAS_OBST || cfg.check_collision);
     if (use_cache && live) {  // the set-up cache of this env (KParams::sc_scratch)
 #pragma unroll 1
       for (int k = 0; k < 6; k++) {
@@ -752,13 +716,6 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
         if (use_cache) { sn = SOA(P.sc_scratch, 2 * k, n, N); cs = SOA(P.sc_scratch, 2 * k + 1, n, N); }  // (this lane stored them above)
         else sincos(q[k], &sn, &cs);
         fk_joint(T, k, sn, cs);
-        if (use_cache && P.sc_frames) {  // the frame of link k + 1: later draws read it instead of multiplying the chain up again
-#pragma unroll
-          for (int j = 0; j < 9; j++) SOA(P.sc_scratch, SC_FRAMES + 12 * k + j, n, N) = T.r[j];
-          SOA(P.sc_scratch, SC_FRAMES + 12 * k + 9, n, N) = T.t.x;
-          SOA(P.sc_scratch, SC_FRAMES + 12 * k + 10, n, N) = T.t.y;
-          SOA(P.sc_scratch, SC_FRAMES + 12 * k + 11, n, N) = T.t.z;
-        }
         const int link = k + 1;
         const double* c = c_tab.capsule[k];
         const D3 b0 = apply(T, d3(c[0], c[1], c[2])), b1 = apply(T, d3(c[3], c[4], c[5]));
@@ -791,7 +748,6 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
     s_pairs[e] = pairs;
     if (pairs) atomicAdd(&s_pending, __popc(pairs));
   }
-  STAMP_TIME(1);
   if (MODE == MODE_STEP) {
     if (wv >= WAVES - G && lane == 0) __hip_atomic_fetch_add(&s_p1done, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
   } else {
@@ -854,31 +810,20 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
       if (e >= E || lb < 1 || lb > 6 || (kind == Q_SELF && (la < 1 || la > 6))) return false;
       const int n = s_env[e];
       if (n < 0) return false;
-      const bool cached = (MODE == MODE_STEP) && p1_ok && P.sc_scratch != nullptr;  // (then s_env already carries P1's verdict on the joints)
+      const bool cached = (MODE == MODE_STEP) && p1_ok;  // (then s_env already carries P1's verdict on the joints)
       if (MODE == MODE_STEP && !cached) {  // P1 may not have judged this env yet: non-finite joints -> no query (same rule as P1)
         bool finite = true;
         for (int k = 0; k < 6; k++) finite = finite && (fabs(joint_of_step<MODE>(P, actions, n, k)) < 1.0e6);
         if (!finite) return false;
       }
       X3 T = identity_x3(), TA = identity_x3();
-      if (cached && P.sc_frames && cfg.check_collision) {  // P1's culling pass left the link frames in the cache (same fk_joint chain, same bits)
-        auto frame = [&](int link, X3& F) {
-#pragma unroll
-          for (int j = 0; j < 9; j++) F.r[j] = SOA(P.sc_scratch, SC_FRAMES + 12 * (link - 1) + j, n, N);
-          F.t = d3(SOA(P.sc_scratch, SC_FRAMES + 12 * (link - 1) + 9, n, N), SOA(P.sc_scratch, SC_FRAMES + 12 * (link - 1) + 10, n, N),
-                   SOA(P.sc_scratch, SC_FRAMES + 12 * (link - 1) + 11, n, N));
-        };
-        frame(lb, T);
-        if (kind == Q_SELF) frame(la, TA);
-      } else {
 #pragma unroll 1
-        for (int k = 0; k < lb; k++) {
-          double sn, cs;
-          if (cached) { sn = SOA(P.sc_scratch, 2 * k, n, N); cs = SOA(P.sc_scratch, 2 * k + 1, n, N); }
-          else sincos(LDS_Q ? s_q[k][e] : joint_of_step<MODE>(P, actions, n, k), &sn, &cs);
-          fk_joint(T, k, sn, cs);
-          if (k + 1 == la) TA = T;
-        }
+      for (int k = 0; k < lb; k++) {
+        double sn, cs;
+        if (cached) { sn = SOA(P.sc_scratch, 2 * k, n, N); cs = SOA(P.sc_scratch, 2 * k + 1, n, N); }
+        else sincos(LDS_Q ? s_q[k][e] : joint_of_step<MODE>(P, actions, n, k), &sn, &cs);
+        fk_joint(T, k, sn, cs);
+        if (k + 1 == la) TA = T;
       }
       if (kind == 3) {
         X3 To;
@@ -947,38 +892,12 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
 
     GjkRun run;
     bool busy = false;
-    STAMP_TIME(2);
     if (MODE == MODE_STEP) p1_ok = __hip_atomic_load(&s_p1done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) >= G;
     if (tid < n_tickets) {
       busy = setup(ticket_item(tid));
       if (busy) gjk_begin(run, v0);
     }
-    STAMP_TIME(3);
-    int trips = 0, draws = 0;
-#ifdef URGYM_STAMPS
-    // cycles of this wave per section of a loop trip (a section ends at its mark): 1 support of A, 2 support of B + exits, 3 simplex +
-    // reduction + convergence tests, 4 result handling, 5 polling + draw + set-up (a mark that no lane of a trip reaches adds its
-    // time to the next section)
-    URGYM_LDS unsigned long long* clk = (URGYM_LDS unsigned long long*)&L.s_clk[wv][0];
-    if (lane < PROF_WORDS) clk[lane] = 0;
-    if (busy) run.clk = clk;
-    clk[0] = __builtin_amdgcn_s_memtime();
-#define SECTION(i) trip_mark(clk, i)
-#else
-#define SECTION(i) do {} while (0)
-#endif
-#ifdef URGYM_STAMPS
-    unsigned long long n_boxq = 0, n_selfq = 0, trips_self = 0;  // census of the pair queries this wave ran / trips that carried a hull <-> hull query
-#endif
     for (;;) {
-      trips++;
-#ifdef URGYM_STAMPS
-      trips_self += (__ballot(busy && kind == Q_SELF) != 0ull) ? 1 : 0;
-      {  // counter 0: one execution per trip, lanes = the busy ones
-        const unsigned long long bm = __ballot(busy);
-        if (lane == 0) { URGYM_LDS unsigned int* w = (URGYM_LDS unsigned int*)(clk + 1 + PROF_SECTIONS); w[0] += 1u; w[1] += (unsigned int)__popcll(bm); }
-      }
-#endif
       if (busy) {
         // exact queries (link distances): Bullet's early-out distance of getClosestPoints(distance = 5.0).  Boolean queries ("closer
         // than the contact margin?", check_collision): both bounds of the search are compared with the margin itself -- the search
@@ -995,11 +914,7 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
           const double verdict_d = wants_distance ? 0.0 : margin_sum() + cfg.collision_margin;
           gjk_iterate(run, P.graph, shape_a(), pose_slot, shape_b(), wants_distance ? margin_sum() + 0.02 + 5.0 : verdict_d, verdict_d);
         }
-        SECTION(3);
         if (run.done) {
-#ifdef URGYM_STAMPS
-          lane_mark(clk, 15);
-#endif
           const double msum = margin_sum();
           if (kind == 3 || exact) {
             double dist = run.core - msum;
@@ -1019,7 +934,6 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
           busy = false;
         }
       }
-      SECTION(4);
       // (atomic loads: other waves change both words while this one polls them; a plain read could legally be hoisted)
       // one 16-byte LDS read of the pool's words (three dependent round trips when they were polled one by one), then the acquire:
       // what the P1 lanes wrote before they counted themselves in s_p1done (pair masks, the set-up cache) is visible to what follows
@@ -1042,33 +956,13 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
           if (atomicSub(&s_pending, 1) > 0) item = claim_pair();
         }
         if (item != NO_ITEM) {
-          draws++;  // (diagnostic: the draws of the lane that reports the stamps)
-#ifdef URGYM_STAMPS
-          lane_mark(clk, 14);
-#endif
           busy = setup(item);
           if (busy) gjk_begin(run, v0);
-#ifdef URGYM_STAMPS
-          if (busy) run.clk = clk;
-          n_boxq += __popcll(__ballot(busy && (kind == Q_TABLE || kind == Q_TRACK)));
-          n_selfq += __popcll(__ballot(busy && kind == Q_SELF));
-#endif
         }
       }
-      SECTION(5);
       // nothing left for this wave to draw (STEP: and the pair masks have been published)
       if (__ballot(busy) == 0ull && !more_tickets && !more_pairs && p1_published) break;
     }
-#ifdef URGYM_STAMPS
-    for (int i = 0; i < 6; i++) STAMP(12 + i, clk[1 + i]);
-    for (int i = 6; i < PROF_SECTIONS; i++) STAMP(20 + i - 6, clk[1 + i]);
-    for (int i = 0; i < PROF_COUNTERS; i++) STAMP(24 + i, clk[1 + PROF_SECTIONS + i]);
-    STAMP(18, n_boxq | (n_selfq << 32));
-    STAMP(19, trips_self);
-#endif
-    STAMP_TIME(4);
-    STAMP(5, (unsigned long long)trips | ((unsigned long long)draws << 32));
-    (void)trips; (void)draws;  // (diagnostic counters of the stamps build)
     // ---- EPA: penetration depth of the marked queries, one wave per query (urgym_device.h epa_wave).  A wave that has left
     //      the pool turns into a service wave: it keeps looking for marks and serves them while the other waves still iterate
     //      (overlapping cores are found within a few GJK iterations, an EPA takes 70-250 us: starting it at once instead of
@@ -1132,7 +1026,6 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
     }
     __syncthreads();
   }
-  STAMP_TIME(6);
 
   // ---- P4: one lane per env re-derives the end-effector frame (link 6 == ee_link 7, urdf:294-298) and finishes the step
   const int pe = (wv - (WAVES - G)) * GROUP + lane;  // env slot of this lane in P4 (waves WAVES-G .. WAVES-1)
@@ -1168,7 +1061,7 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
       if (LDS_STATE) {
         opos[0] = s_obst[0][pe]; opos[1] = s_obst[1][pe]; opos[2] = s_obst[2][pe];
         oq = Q4{s_obst[3][pe], s_obst[4][pe], s_obst[5][pe], s_obst[6][pe]};
-      } else if (s_env[pe] >= 0 && P.sc_scratch != nullptr) {  // the P1 lane of this env (this very lane) cached the advanced pose
+      } else if (s_env[pe] >= 0) {  // the P1 lane of this env (this very lane) cached the advanced pose
         for (int i = 0; i < 3; i++) opos[i] = SOA(P.sc_scratch, 12 + i, n, N);
         oq = Q4{SOA(P.sc_scratch, 15, n, N), SOA(P.sc_scratch, 16, n, N), SOA(P.sc_scratch, 17, n, N), SOA(P.sc_scratch, 18, n, N)};
       } else {
@@ -1437,8 +1330,6 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
     if (flags) atomicOr(&B.status[n], flags);
     }  // MODE != MODE_PREFETCH
   }
-  STAMP_TIME(7);
-  STAMP(9, __builtin_amdgcn_s_memrealtime());
   __syncthreads();
 
   // ---- write-back of the observation rows staged in LDS (coalesced for STEP: the group's rows are contiguous)
@@ -1471,7 +1362,7 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
 }
 
 template <int KIND, int MODE, bool WITH_EPA>
-__global__ void __launch_bounds__(THREADS, ((MODE == MODE_STEP || MODE == MODE_PREFETCH) ? URGYM_RESIDENT : 2)) env_kernel(const KParams P, const float* __restrict__ actions) {
+__global__ void __launch_bounds__(THREADS, ((MODE == MODE_STEP || MODE == MODE_PREFETCH) ? RESIDENT : 2)) env_kernel(const KParams P, const float* __restrict__ actions) {
   __shared__ EnvLds<MODE> lds;
   env_body<KIND, MODE, WITH_EPA>(P, actions, lds, (int)blockIdx.x, (int)gridDim.x);
 }
@@ -1482,7 +1373,7 @@ __global__ void __launch_bounds__(THREADS, ((MODE == MODE_STEP || MODE == MODE_P
 // the slots the step workgroups free in the tail of the launch.  The two kinds never touch the same data (the refill writes record
 // slots the concurrent step cannot read -- episode parity -- and reads nothing the step writes: the episode id travels in its list).
 template <int KIND, bool WITH_EPA>
-__global__ void __launch_bounds__(THREADS, URGYM_RESIDENT) env_step_fused(const KParams Ps, const KParams Pr, const float* __restrict__ actions, const int step_blocks) {
+__global__ void __launch_bounds__(THREADS, RESIDENT) env_step_fused(const KParams Ps, const KParams Pr, const float* __restrict__ actions, const int step_blocks) {
   __shared__ union FusedLds {
     EnvLds<MODE_STEP> step;
     EnvLds<MODE_PREFETCH> refill;
@@ -1652,7 +1543,7 @@ struct Handle {
   LaunchPlan plan;                 // launch geometry and paths (urgym_launch_plan.h), fixed at urgym_create
   Kernels k;
   double* d_ld_scratch = nullptr;  // [5][N] link distances of the running step
-  double* d_sc_scratch = nullptr;  // [SC_FIELDS][N] set-up cache of the running step (plan.setup_cache)
+  double* d_sc_scratch = nullptr;  // [SC_ROWS][N] set-up cache of the running step
   CandRec* d_recs = nullptr;          // support map: candidate records ...
   unsigned short* d_cell = nullptr;   // ... and the cube map of directions that points into them
   uint64_t seed = 0;
@@ -1763,7 +1654,6 @@ KParams make_params(Handle* h, int copy_final) {
   P.rec_i = h->d_reci;
   P.ld_scratch = h->d_ld_scratch;
   P.sc_scratch = h->d_sc_scratch;
-  P.sc_frames = h->plan.setup_cache >= 2 ? 1 : 0;
   P.fallback_on = 1;
   P.inline_ori = h->plan.inline_ori ? 1 : 0;
   for (int i = 0; i < 6; i++) P.neutral_ach[i] = h->neutral_ach[i];
@@ -1940,16 +1830,16 @@ int do_masked(Handle* h, const uint8_t* mask, int mode, hipStream_t s) {
 
 // The launch plan of a new handle (urgym_launch_plan.h), checked before anything is allocated.  per_cu: the residency of the kernel
 // the steady-state step launches.  The API over-reports near the LDS limit (DESIGN.md section 4 "toolchain hazards"); the residency
-// census, tools/diag/census.hip, is what the cap URGYM_RESIDENT = 3 rests on.
+// census, tools/diag/census.hip, is what the cap RESIDENT = 3 rests on.
 int plan_handle(Handle* h, const Tuning& t) {
   h->k = kernels_for(h->cfg);
   h->plan = plan_paths(h->cfg.env_kind, h->cfg.num_envs, h->cfg.auto_reset != 0, t);
-  int cus = 256, per_cu = 3;
+  int cus = 256, per_cu = RESIDENT;
   hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
   const hipError_t oe = h->plan.fused ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, h->k.fused, THREADS, 0)
                                       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, h->k.mode[MODE_STEP], THREADS, 0);
-  if (oe != hipSuccess || per_cu < 1) per_cu = 3;
-  if (per_cu > URGYM_RESIDENT) per_cu = URGYM_RESIDENT;
+  if (oe != hipSuccess || per_cu < 1) per_cu = RESIDENT;
+  if (per_cu > RESIDENT) per_cu = RESIDENT;
   plan_grids(h->plan, cus, per_cu, t);
   const LaunchPlan& p = h->plan;
   if (t.verbose) {
@@ -1988,8 +1878,7 @@ int upload_tables(Handle* h) {
 int allocate_scratch(Handle* h) {
   const size_t n = (size_t)h->cfg.num_envs;
   HIP_TRY(h, hipMalloc((void**)&h->d_ld_scratch, sizeof(double) * 5 * n));
-  if (h->plan.setup_cache != 0)
-    HIP_TRY(h, hipMalloc((void**)&h->d_sc_scratch, sizeof(double) * (h->plan.setup_cache >= 2 ? SC_FIELDS : SC_FRAMES) * n));
+  HIP_TRY(h, hipMalloc((void**)&h->d_sc_scratch, sizeof(double) * SC_ROWS * n));
   if (!h->plan.prefetch) return URGYM_OK;
   HIP_TRY(h, hipMalloc((void**)&h->d_rec, sizeof(double) * 2 * REC_FIELDS * n));
   HIP_TRY(h, hipMalloc((void**)&h->d_reci, sizeof(int32_t) * 4 * n));
@@ -2204,15 +2093,6 @@ int urgym_query_timing(void* handle, double* step_us, double* reset_us, int* lau
   h->ev_used = 0;
   return URGYM_OK;
 }
-
-#ifdef URGYM_STAMPS
-int urgym_debug_occupancy(int* blocks_per_cu) {
-  return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, env_kernel<URGYM_ENV_DYN, MODE_STEP, false>, THREADS, 0);
-}
-int urgym_debug_stamps(unsigned long long* out, int count) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamps), sizeof(unsigned long long) * (size_t)count, 0, hipMemcpyDeviceToHost);
-}
-#endif
 
 int urgym_query_refill_timing(void* handle, double* refill_us) {
   Handle* h = (Handle*)handle;

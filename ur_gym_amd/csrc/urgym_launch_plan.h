@@ -13,11 +13,8 @@
 namespace urgym {
 
 constexpr int GROUP = 64;                  // env slots per wave-wide pass
-#ifndef URGYM_MAX_ENVS
-#define URGYM_MAX_ENVS 64
-#endif
 constexpr int PREFETCH_MAX_ENVS = 32;      // envs per PREFETCH workgroup at most
-constexpr int MAX_ENVS = URGYM_MAX_ENVS;   // most envs one RESET / REFRESH workgroup serves (one wave of per-env lanes)
+constexpr int MAX_ENVS = 64;               // most envs one RESET / REFRESH workgroup serves (one wave of per-env lanes)
 // A STEP workgroup may serve up to two waves' worth of envs: with its link distances parked in a global scratch array instead
 // of LDS the per-env LDS footprint is 12 bytes, so the 53.7 KB that three resident workgroups allow are not exceeded, and
 // N = 65536 fits ONE round of resident workgroups (E = 90) instead of two rounds of 46 with a ragged second one.
@@ -28,11 +25,6 @@ struct Tuning {
   int step_envs, reset_envs, refill_blocks;  // URGYM_STEP_ENVS (1 .. STEP_MAX_ENVS), URGYM_RESET_ENVS (1 .. MAX_ENVS), URGYM_REFILL_BLOCKS
   int tiers = -1, tier_envs = 0, tier_blocks = 0, tier_tail = 0;  // URGYM_STEP_TIERS: -1 not set, 0 "0" (uniform), 1 "E1,B,E2"
   bool prefetch;     // URGYM_PREFETCH (0: the auto-reset kernel after each step)
-  // URGYM_SETUP_CACHE: 0 = every draw recomputes its operands, 1 = sin / cos of the joints + obstacle pose cached, 2 = the link
-  // frames too (other values >= 2: 2, other non-zero ones: 1).  Measured at N = 65536 Dyn (profiles/r2/exp_setup_cache_levels.txt):
-  // 186.3 / 195.4 / 197.7 M env-steps/s at 108 / 140 / 201 MB of L2 <-> fabric traffic per launch: the frames buy 1 % for 61 MB,
-  // so they stay opt-in.
-  int setup_cache;
   bool verbose;      // URGYM_VERBOSE (set: print the plan to stderr)
 };
 
@@ -49,8 +41,6 @@ inline Tuning read_tuning() {
   t.refill_blocks = number("URGYM_REFILL_BLOCKS", 1, INT_MAX);
   const char* pf = getenv("URGYM_PREFETCH");
   t.prefetch = !pf || atoi(pf) != 0;
-  const char* sc = getenv("URGYM_SETUP_CACHE");
-  t.setup_cache = !sc ? 1 : (atoi(sc) >= 2 ? 2 : atoi(sc) != 0);
   t.verbose = getenv("URGYM_VERBOSE") != nullptr;
   if (const char* v = getenv("URGYM_STEP_TIERS")) {
     int e1 = 0, b = 0, e2 = 0;
@@ -70,7 +60,9 @@ struct LaunchPlan {
   bool prefetch = false;     // obstacle envs: prefetched episode records (DESIGN.md "auto-reset off the critical path")
   bool fused = false;        // ... and the steady-state step is the fused STEP + PREFETCH launch (prefetch with auto-reset)
   bool inline_ori = false;   // UR5OriReach-v1: finished envs are reset inside the step kernel (no RESET launch per step)
-  int setup_cache = 1;       // 0: no set-up cache, 1: sin / cos of the joints + obstacle pose, 2: the link frames too
+  // the set-up cache of the step kernel has one form, level 1 of the former three: sin / cos of the joints + the advanced obstacle
+  // pose (level 2 added the link frames: +1 % for +61 MB of traffic per launch; profiles/r2/exp_setup_cache_levels.txt)
+  static constexpr int setup_cache = 1;
   int rl_cap[4] = {0, 0, 0, 0};  // refill lists: three rotating asynchronous ones, one synchronous (index 3)
   int refill_blocks = 0;     // URGYM_REFILL_BLOCKS: refill workgroups per fused launch, 0 = the policy of refill_blocks()
 };
@@ -85,7 +77,6 @@ inline LaunchPlan plan_paths(int env_kind, int num_envs, bool auto_reset, const 
   p.prefetch = env_kind != URGYM_ENV_ORI && t.prefetch;
   p.fused = p.prefetch && auto_reset;
   p.inline_ori = env_kind == URGYM_ENV_ORI && t.prefetch;
-  p.setup_cache = t.setup_cache;
   p.refill_blocks = t.refill_blocks;
   if (p.prefetch) {
     p.rl_cap[0] = p.rl_cap[1] = p.rl_cap[2] = num_envs;  // at most one entry per env and step: no entry is ever dropped
