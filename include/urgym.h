@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define URGYM_ABI_VERSION 3
+#define URGYM_ABI_VERSION 4
 
 /* env kinds = the reference's registered ids (UR_gym/__init__.py:19-42, UR_gym/envs/ur_tasks.py:37-90) */
 enum {
@@ -186,6 +186,63 @@ int urgym_step(void* handle, const float* actions_dev, void* stream);
 
 /* K consecutive urgym_step calls enqueued back to back: actions_dev is [K][N][6]. */
 int urgym_rollout(void* handle, const float* actions_dev, int num_steps, void* stream);
+
+/* ---- ABI v4: a policy in the loop (the reference's model_test.py:26-61 evaluates a stable-baselines3 SAC checkpoint with
+ * model.predict(obs, deterministic=True) between env.step calls; here actor and environment stay on the device) ---- */
+
+/* The deterministic SAC actor of SB3's MultiInputPolicy as model_test.py:21 loads it (SAC.load): features = the Dict observation
+ * concatenated in sorted key order achieved_goal | desired_goal | observation, latent_pi = Linear-ReLU-Linear-ReLU, mu = Linear,
+ * action = tanh(mu).  All six arrays are HOST pointers, float32, torch's [out][in] row-major layout; they are copied (re-packed for
+ * the kernel) by urgym_actor_create and not kept.  Supported: hidden_width a multiple of 32, at most 512; in_features = obs_dim +
+ * 2 * goal_dim of the handle's env kind; action_dim = 6. */
+typedef struct urgym_actor_desc {
+  int32_t in_features;  /* 30 | 32 | 41 | 47 (Ori | Obs | Sta | Dyn) */
+  int32_t hidden_width; /* width of both hidden layers (256 in the shipped checkpoints) */
+  int32_t action_dim;   /* 6 (UR5.py:251) */
+  int32_t reserved0;    /* must be 0 */
+  const float* w0;      /* latent_pi.0.weight [hidden_width][in_features] */
+  const float* b0;      /* latent_pi.0.bias   [hidden_width] */
+  const float* w1;      /* latent_pi.2.weight [hidden_width][hidden_width] */
+  const float* b1;      /* latent_pi.2.bias   [hidden_width] */
+  const float* w_mu;    /* mu.weight [action_dim][hidden_width] */
+  const float* b_mu;    /* mu.bias   [action_dim] */
+} urgym_actor_desc;
+
+/* What urgym_rollout_actor records: DEVICE pointers owned by the caller, each may be NULL (= not recorded).  K = num_steps.
+ * Step k's row of the first four is what the actor saw before step k and what it answered; of the next six, what step k returned
+ * (RobotTaskEnv.step, core.py:303-317; the replay buffer rows train.py's SAC collects).  The episode summary is the bookkeeping
+ * of model_test.py:38-50 for the FIRST episode of every env within the call. */
+typedef struct urgym_trajectory {
+  float* observation;       /* [K][N][obs_dim]  */
+  float* achieved_goal;     /* [K][N][goal_dim] */
+  float* desired_goal;      /* [K][N][goal_dim] */
+  float* action;            /* [K][N][6] */
+  float* reward;            /* [K][N] */
+  uint8_t* terminated;      /* [K][N] */
+  uint8_t* truncated;       /* [K][N] */
+  uint8_t* is_success;      /* [K][N] */
+  uint8_t* collision;       /* [K][N] */
+  float* final_observation; /* [K][N][obs_dim]: rows written where terminated | truncated, only with auto_reset */
+  double* episode_return;   /* [N] sum of the rewards up to and including the env's first terminated step, or step K - 1 */
+  int32_t* episode_last_step; /* [N] index of that step (model_test.py:46-49) */
+  uint8_t* episode_success; /* [N] info["is_success"] of that step */
+  uint8_t* episode_done;    /* [N] 1 once the three above are final (every env after a complete call) */
+} urgym_trajectory;
+
+/* Replaces SAC.load (model_test.py:21) for the actor: checks the shape, uploads the weights.  The actor belongs to the handle
+ * (urgym_destroy releases the ones still alive) and may be used with it until urgym_actor_destroy. */
+int urgym_actor_create(void* handle, const urgym_actor_desc* desc, void** actor);
+int urgym_actor_destroy(void* handle, void* actor);
+
+/* Replaces model.predict(observation, deterministic=True) (model_test.py:41) for all N envs: one forward pass from the bound
+ * observation / achieved_goal / desired_goal buffers into actions_dev, float32 [N][6]. */
+int urgym_actor_forward(void* handle, void* actor, float* actions_dev, void* stream);
+
+/* Replaces the loop of model_test.py:38-50 (predict, step, bookkeeping): enqueues num_steps x (forward pass + records, step) and a
+ * last record pass on `stream`.  No host synchronisation and no allocation; everything is validated before the first launch.
+ * Afterwards the bound buffers hold what num_steps calls of urgym_step would have left.  traj may be NULL.  Needs observations:
+ * urgym_reset or urgym_refresh must have run on this binding. */
+int urgym_rollout_actor(void* handle, void* actor, int num_steps, const urgym_trajectory* traj, void* stream);
 
 /* Replaces Reach*.set_goal / set_goal_and_obstacle (reach.py:202-204, 328-335, 702-713): the caller has
  * overwritten goal / obst_start / obst_end (and possibly q) for the masked envs; this recomputes obstacle pose,

@@ -1,0 +1,140 @@
+#!/usr/bin/env python
+"""Closed-loop rollout with a policy in the loop: what it costs per step, three ways, in ONE process on one MI355X.
+
+  (a) host        the loop as shipped before the device actor: HipBackend.observe() copies three tensors to the host,
+                  DeterministicActor (numpy) runs there, the actions are copied back, env.step.
+  (b) torch       what a user could build without the device actor: the actor as three torch.nn.functional.linear calls in
+                  float32 on the device (cat, relu, tanh around them), then env.step -- no host copies.
+  (c) device      env.rollout_policy (urgym_rollout_actor): K x (HIP actor kernel + records, step) enqueued by one native call;
+                  once without records and once with all of them.
+
+Every figure is wall time around work that ends in a device synchronise, per step, median of `--repeats` windows that alternate
+between the variants.  The actor launch alone is timed with device events around back-to-back urgym_actor_forward calls and set
+against the step launch (urgym_query_timing) and the float32 matrix peak.  One JSON line on stdout; --out also writes it to a file.
+
+    python tools/bench_policy_rollout.py --out profiles/policy_rollout/dyn65536.json
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+F32_MATRIX_PEAK_TFLOPS = 157.3  # MI355X, v_mfma_f32_32x32x2_f32 / v_mfma_f32_16x16x4_f32 (AMD's specification)
+ACTOR_NPZ = {"UR5OriReach-v1": "ori", "UR5ObsReach-v1": "obs", "UR5StaReach-v1": "sta", "UR5DynReach-v1": "dyn"}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--env", default="UR5DynReach-v1", choices=sorted(ACTOR_NPZ))
+    ap.add_argument("--num-envs", type=int, default=65536)
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--host-steps", type=int, default=20, help="steps of a window of the host loop (it is ~100x slower)")
+    ap.add_argument("--warmup", type=int, default=110, help="steps before the first window (past the common truncation at step 100)")
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+
+    import torch
+    import torch.nn.functional as F
+
+    from ur_gym_amd import make_vec
+    from ur_gym_amd.evaluation import DeterministicActor, DeviceActor, HipBackend
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_policy_rollout.py measures on a GPU; none is visible")
+    dev = "cuda:0"
+    n, K = args.num_envs, args.steps
+    path = os.path.join(ROOT, "tests", "golden", "actors", f"actor_{ACTOR_NPZ[args.env]}.npz")
+    w = dict(np.load(path))
+    env = make_vec(args.env, num_envs=n, device=dev, seed=0, auto_reset=True)
+    env.reset(seed=0)
+    actor = DeviceActor.load(path, env)
+    host_actor, backend = DeterministicActor(w), HipBackend(env)
+    tw = {k: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(dev) for k, v in w.items()}
+    sync = lambda: torch.cuda.synchronize(env.device)
+
+    def host_loop(steps):
+        for _ in range(steps):
+            backend.step(host_actor(*backend.observe()))
+
+    def torch_loop(steps):
+        b = env.buf
+        for _ in range(steps):
+            x = torch.cat([b["achieved_goal"], b["desired_goal"], b["observation"]], dim=1)
+            h = F.relu(F.linear(x, tw["latent_pi_0_weight"], tw["latent_pi_0_bias"]))
+            h = F.relu(F.linear(h, tw["latent_pi_2_weight"], tw["latent_pi_2_bias"]))
+            env.step(torch.tanh(F.linear(h, tw["mu_weight"], tw["mu_bias"])))
+
+    def device_loop(steps):
+        env.rollout_policy(actor, steps, record=())
+
+    def device_loop_recorded(steps):
+        return env.rollout_policy(actor, steps, record="all")
+
+    variants = [("host_numpy_actor", host_loop, args.host_steps), ("torch_linear_actor", torch_loop, K),
+                ("device_actor", device_loop, K), ("device_actor_all_records", device_loop_recorded, K)]
+    # warm-up: every variant once (code objects, BLAS algorithm choice, the allocator's blocks for the records), then past step 100
+    for _, fn, steps in variants:
+        fn(min(steps, 10))
+    device_loop(args.warmup)
+    sync()
+    times = {name: [] for name, _, _ in variants}
+    for _ in range(args.repeats):
+        for name, fn, steps in variants:
+            sync()
+            t0 = time.perf_counter()
+            fn(steps)
+            sync()
+            times[name].append((time.perf_counter() - t0) / steps * 1e6)
+    per_step = {name: float(np.median(v)) for name, v in times.items()}
+
+    # the actor launch alone (device events around back-to-back launches), and the step launch as the library times it
+    out = torch.empty((n, 6), dtype=torch.float32, device=dev)
+    for _ in range(10):
+        env.policy_actions(actor, out=out)
+    reps = 200
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    sync()
+    e0.record()
+    for _ in range(reps):
+        env.policy_actions(actor, out=out)
+    e1.record()
+    sync()
+    actor_us = e0.elapsed_time(e1) * 1e3 / reps
+    env.enable_timing(True, every=8)
+    device_loop(K)
+    sync()
+    step_us, _, launches = env.query_timing()
+    env.enable_timing(False)
+    flop = 2.0 * n * (actor.in_features * actor.hidden_width + actor.hidden_width ** 2 + actor.hidden_width * 6)
+    result = {
+        "tool": "bench_policy_rollout", "env": args.env, "num_envs": n, "steps": K, "host_steps": args.host_steps, "repeats": args.repeats,
+        "device": torch.cuda.get_device_name(0),
+        "us_per_step_median": per_step, "us_per_step_all": {k: [round(x, 2) for x in v] for k, v in times.items()},
+        "env_steps_per_s": {k: n / v * 1e6 for k, v in per_step.items()},
+        "device_not_slower_than_torch": per_step["device_actor"] <= per_step["torch_linear_actor"],
+        "speedup_device_over_torch": per_step["torch_linear_actor"] / per_step["device_actor"],
+        "speedup_device_over_host": per_step["host_numpy_actor"] / per_step["device_actor"],
+        "actor_launch_us": actor_us, "step_launch_us": step_us, "step_launches_timed": launches,
+        "actor_over_step_launch": actor_us / step_us if step_us > 0 else None,
+        "actor_gflop_per_step": flop / 1e9, "actor_tflops": flop / actor_us / 1e6,
+        "actor_fraction_of_f32_matrix_peak": flop / actor_us / 1e6 / F32_MATRIX_PEAK_TFLOPS,
+    }
+    actor.close()
+    env.close()
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -1,7 +1,7 @@
 """ctypes mirror of include/urgym.h (struct layouts and constants only; no library is loaded here)."""
 import ctypes as C
 
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 ENV_ORI, ENV_OBS, ENV_DYN, ENV_STA = 0, 1, 2, 3
 ENV_IDS = {"UR5OriReach-v1": ENV_ORI, "UR5ObsReach-v1": ENV_OBS, "UR5DynReach-v1": ENV_DYN, "UR5StaReach-v1": ENV_STA}
@@ -90,6 +90,45 @@ class Buffers(C.Structure):
     _fields_ = [(name, C.POINTER(ct)) for name, ct, _ in BUFFER_FIELDS]
 
 
+class ActorDesc(C.Structure):
+    """urgym_actor_desc: dimensions + six HOST pointers to float32 arrays in torch's [out][in] layout."""
+    _fields_ = [
+        ("in_features", C.c_int32),
+        ("hidden_width", C.c_int32),
+        ("action_dim", C.c_int32),
+        ("reserved0", C.c_int32),
+        ("w0", C.POINTER(C.c_float)),
+        ("b0", C.POINTER(C.c_float)),
+        ("w1", C.POINTER(C.c_float)),
+        ("b1", C.POINTER(C.c_float)),
+        ("w_mu", C.POINTER(C.c_float)),
+        ("b_mu", C.POINTER(C.c_float)),
+    ]
+
+
+# urgym_trajectory: name -> (ctype of element, shape given (K, N, obs_dim, goal_dim)); every pointer may be NULL
+TRAJECTORY_FIELDS = [
+    ("observation", C.c_float, lambda K, N, od, gd: (K, N, od)),
+    ("achieved_goal", C.c_float, lambda K, N, od, gd: (K, N, gd)),
+    ("desired_goal", C.c_float, lambda K, N, od, gd: (K, N, gd)),
+    ("action", C.c_float, lambda K, N, od, gd: (K, N, 6)),
+    ("reward", C.c_float, lambda K, N, od, gd: (K, N)),
+    ("terminated", C.c_uint8, lambda K, N, od, gd: (K, N)),
+    ("truncated", C.c_uint8, lambda K, N, od, gd: (K, N)),
+    ("is_success", C.c_uint8, lambda K, N, od, gd: (K, N)),
+    ("collision", C.c_uint8, lambda K, N, od, gd: (K, N)),
+    ("final_observation", C.c_float, lambda K, N, od, gd: (K, N, od)),
+    ("episode_return", C.c_double, lambda K, N, od, gd: (N,)),
+    ("episode_last_step", C.c_int32, lambda K, N, od, gd: (N,)),
+    ("episode_success", C.c_uint8, lambda K, N, od, gd: (N,)),
+    ("episode_done", C.c_uint8, lambda K, N, od, gd: (N,)),
+]
+
+
+class Trajectory(C.Structure):
+    _fields_ = [(name, C.POINTER(ct)) for name, ct, _ in TRAJECTORY_FIELDS]
+
+
 # Every symbol include/urgym.h declares (tests check that the built library exports each of them).
 EXPORTED_SYMBOLS = [
     "urgym_abi_version",
@@ -101,6 +140,10 @@ EXPORTED_SYMBOLS = [
     "urgym_reset",
     "urgym_step",
     "urgym_rollout",
+    "urgym_actor_create",
+    "urgym_actor_destroy",
+    "urgym_actor_forward",
+    "urgym_rollout_actor",
     "urgym_refresh",
     "urgym_invalidate_records",
     "urgym_derive_obstacle_motion",

@@ -58,6 +58,10 @@ def lib():
     L.urgym_reset.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
     L.urgym_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.urgym_rollout.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.urgym_actor_create.argtypes = [C.c_void_p, C.POINTER(_abi.ActorDesc), C.POINTER(C.c_void_p)]
+    L.urgym_actor_destroy.argtypes = [C.c_void_p, C.c_void_p]
+    L.urgym_actor_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.urgym_rollout_actor.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(_abi.Trajectory), C.c_void_p]
     L.urgym_refresh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.urgym_invalidate_records.argtypes = [C.c_void_p]
     L.urgym_derive_obstacle_motion.argtypes = [C.c_void_p, C.c_void_p]

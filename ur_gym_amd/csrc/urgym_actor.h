@@ -1,0 +1,44 @@
+// urgym_actor.h — seam between the two translation units of liburgym_hip.so: urgym_actor.hip (the actor / record kernels, compiled
+// with fma contraction) offers these; urgym_hip.hip (handle, C-ABI, step launches) calls them.  Nothing here is exported.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/urgym.h"
+
+namespace urgym {
+
+struct Actor;  // packed weights and scratch on the device (urgym_actor.hip)
+
+// Where a pass reads the environment's outputs (the bound buffers of the handle)
+struct ActorEnv {
+  int N, obs_dim, goal_dim, auto_reset;
+  const float *observation, *achieved_goal, *desired_goal, *reward, *final_observation;
+  const uint8_t *terminated, *truncated, *is_success, *collision;
+};
+
+// The records of one pass of a rollout (every pointer may be null).  Pass k runs before step k: obs / ach / des are the rows of
+// step k (what the actor sees now), reward .. final_obs the rows of step k - 1 (what that step left in the bound buffers); the
+// episode arrays are per env.  k = 0 initialises the episode summary; k = num_steps is the last pass, without a forward pass.
+struct ActorPass {
+  float *obs, *ach, *des;
+  float* reward;
+  uint8_t *terminated, *truncated, *is_success, *collision;
+  float* final_obs;
+  double* ep_return;
+  int32_t* ep_last;
+  uint8_t *ep_success, *ep_done;  // ep_done: the summary's own state, never null while one of the three others is recorded
+  int k, num_steps;
+};
+
+// checks desc (shape only; in_features is compared with `in_features`), uploads the packed weights; on failure writes a message
+int actor_create(const urgym_actor_desc* desc, int in_features, int num_envs, Actor** out, char* err, size_t err_len);
+void actor_destroy(Actor* a);
+int actor_in_features(const Actor* a);
+float* actor_action_scratch(Actor* a);  // [N][6], the actions of a rollout that does not record them
+uint8_t* actor_done_scratch(Actor* a);  // [N], ActorPass::ep_done of a rollout that does not record it
+
+// forward pass (actions != nullptr) and / or records (pass != nullptr) in ONE launch on `s`
+void actor_launch(Actor* a, const ActorEnv& env, float* actions, const ActorPass* pass, hipStream_t s);
+
+}  // namespace urgym

@@ -39,6 +39,7 @@
 #include "../../data/ur5e_model.h"
 #include "urgym_device.h"
 #include "urgym_launch_plan.h"
+#include "urgym_actor.h"
 #include "urgym_tables_host.h"
 
 using namespace urgym;
@@ -1570,6 +1571,9 @@ struct Handle {
   // An env that falls back gets fresh records for its next two episodes, and every env finishes within max_episode_steps.
   int dirty_steps = 0;
   long steps_since_full_reset = -1; // step launches since the last urgym_reset of every env (-1: none yet)
+  // policies (urgym_actor.hip)
+  std::vector<Actor*> actors;  // alive, released by urgym_destroy at the latest
+  bool observed = false;       // a reset / refresh has filled the bound observation buffers: an actor has something to read
 };
 thread_local char g_err[512] = {0};
 
@@ -1718,6 +1722,7 @@ void release(Handle* h) {
                   (void*)h->d_reci, (void*)h->d_rl[0], (void*)h->d_rl[1], (void*)h->d_rl[2], (void*)h->d_rl[3], (void*)h->d_rcount})
     if (p) hipFree(p);
   for (auto e : h->ev) hipEventDestroy(e);
+  for (Actor* a : h->actors) actor_destroy(a);
   delete h;
 }
 
@@ -1823,6 +1828,7 @@ int do_masked(Handle* h, const uint8_t* mask, int mode, hipStream_t s) {
   // leave the consumed counter zeroed so the next step can append to either slot
   HIP_TRY(h, hipMemsetAsync(h->buf.done_count, 0, 2 * sizeof(int32_t), s));
   HIP_TRY(h, hipGetLastError());
+  h->observed = true;
   return URGYM_OK;
 }
 
@@ -1900,6 +1906,63 @@ int eval_neutral_pose(Handle* h) {
   return e == hipSuccess ? URGYM_OK : fail(h, URGYM_ERR_HIP, "urgym_create: neutral pose", e);
 }
 
+
+// ---- policies: the checks and the per-pass arguments of urgym_actor_forward / urgym_rollout_actor
+
+// an actor of THIS handle, still alive
+Actor* find_actor(Handle* h, void* actor) {
+  for (Actor* a : h->actors)
+    if (a == actor) return a;
+  return nullptr;
+}
+
+int actor_features(const Handle* h) { return h->obs_dim + 2 * h->goal_dim; }
+
+ActorEnv actor_env(const Handle* h) {
+  const urgym_buffers& b = h->buf;
+  return ActorEnv{h->cfg.num_envs, h->obs_dim, h->goal_dim, h->cfg.auto_reset, b.observation, b.achieved_goal, b.desired_goal,
+                  b.reward, b.final_observation, b.terminated, b.truncated, b.is_success, b.collision};
+}
+
+// the records of pass k (ActorPass): rows k of what the actor sees, rows k - 1 of what the step before returned
+ActorPass actor_pass(const Handle* h, Actor* a, const urgym_trajectory& t, int k, int num_steps) {
+  const size_t n = (size_t)h->cfg.num_envs, od = (size_t)h->obs_dim, gd = (size_t)h->goal_dim;
+  const size_t pre = (size_t)k * n, post = (size_t)(k > 0 ? k - 1 : 0) * n;
+  auto at = [](auto* p, size_t off) { return p ? p + off : p; };
+  ActorPass r;
+  r.obs = at(t.observation, pre * od), r.ach = at(t.achieved_goal, pre * gd), r.des = at(t.desired_goal, pre * gd);
+  r.reward = at(t.reward, post);
+  r.terminated = at(t.terminated, post), r.truncated = at(t.truncated, post), r.is_success = at(t.is_success, post);
+  r.collision = at(t.collision, post);
+  r.final_obs = at(t.final_observation, post * od);
+  r.ep_return = t.episode_return, r.ep_last = t.episode_last_step, r.ep_success = t.episode_success;
+  const bool summary = t.episode_return || t.episode_last_step || t.episode_success || t.episode_done;
+  r.ep_done = t.episode_done ? t.episode_done : (summary ? actor_done_scratch(a) : nullptr);
+  r.k = k, r.num_steps = num_steps;
+  return r;
+}
+
+// the checks urgym_actor_forward and urgym_rollout_actor share; *out = the actor
+int enter_actor(Handle* h, void* actor, const char* who, Actor** out) {
+  if (int rc = enter_bound(h)) return rc;
+  char msg[200];
+  Actor* a = find_actor(h, actor);
+  if (!a) {
+    snprintf(msg, sizeof(msg), "%s: not an actor of this handle (actors belong to the handle they were created with)", who);
+    return fail(h, URGYM_ERR_ARG, msg);
+  }
+  if (actor_in_features(a) != actor_features(h)) {
+    snprintf(msg, sizeof(msg), "%s: the actor takes %d features, this env kind offers %d", who, actor_in_features(a), actor_features(h));
+    return fail(h, URGYM_ERR_ARG, msg);
+  }
+  if (!h->observed) {
+    snprintf(msg, sizeof(msg), "%s: no observations yet: call urgym_reset (or urgym_refresh) first", who);
+    return fail(h, URGYM_ERR_STATE, msg);
+  }
+  *out = a;
+  return URGYM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1975,6 +2038,7 @@ int urgym_bind(void* handle, const urgym_buffers* b) {
   h->steps_since_full_reset = -1;
   h->buf = *b;
   h->bound = true;
+  h->observed = false;
   return URGYM_OK;
 }
 
@@ -2036,6 +2100,70 @@ int urgym_rollout(void* handle, const float* actions_dev, int num_steps, void* s
     rc = do_step(h, actions_dev + (size_t)k * h->cfg.num_envs * 6, (hipStream_t)stream);
     if (rc) return rc;
   }
+  return URGYM_OK;
+}
+
+int urgym_actor_create(void* handle, const urgym_actor_desc* desc, void** actor) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (!actor) return fail(h, URGYM_ERR_ARG, "urgym_actor_create: null argument");
+  HIP_TRY(h, hipSetDevice(h->device));
+  Actor* a = nullptr;
+  if (int rc = actor_create(desc, actor_features(h), h->cfg.num_envs, &a, h->err, sizeof(h->err))) return rc;
+  h->actors.push_back(a);
+  *actor = a;
+  return URGYM_OK;
+}
+
+int urgym_actor_destroy(void* handle, void* actor) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (!actor) return URGYM_OK;
+  for (size_t i = 0; i < h->actors.size(); i++)
+    if (h->actors[i] == actor) {
+      hipSetDevice(h->device);
+      hipDeviceSynchronize();  // launches that read its weights may still be in flight
+      actor_destroy(h->actors[i]);
+      h->actors.erase(h->actors.begin() + i);
+      return URGYM_OK;
+    }
+  return fail(h, URGYM_ERR_ARG, "urgym_actor_destroy: not an actor of this handle");
+}
+
+int urgym_actor_forward(void* handle, void* actor, float* actions_dev, void* stream) {
+  Handle* h = (Handle*)handle;
+  Actor* a = nullptr;
+  if (int rc = enter_actor(h, actor, "urgym_actor_forward", &a)) return rc;
+  if (!actions_dev) return fail(h, URGYM_ERR_ARG, "urgym_actor_forward: null actions");
+  actor_launch(a, actor_env(h), actions_dev, nullptr, (hipStream_t)stream);
+  HIP_TRY(h, hipGetLastError());
+  return URGYM_OK;
+}
+
+int urgym_rollout_actor(void* handle, void* actor, int num_steps, const urgym_trajectory* traj, void* stream) {
+  Handle* h = (Handle*)handle;
+  Actor* a = nullptr;
+  if (int rc = enter_actor(h, actor, "urgym_rollout_actor", &a)) return rc;
+  if (num_steps < 0) return fail(h, URGYM_ERR_ARG, "urgym_rollout_actor: num_steps < 0");
+  if (num_steps == 0) return URGYM_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const ActorEnv env = actor_env(h);
+  const size_t row = (size_t)h->cfg.num_envs * 6;
+  // Every launch below goes to `s`, and so does everything do_step launches (the step or fused launch, the RESET / PREFETCH
+  // fallbacks of a dirty step, the timing events): stream order alone puts step k - 1 before the pass that reads its outputs and
+  // that pass before the step that reads its actions.
+  for (int k = 0; k <= num_steps; k++) {
+    ActorPass pass;
+    if (traj) pass = actor_pass(h, a, *traj, k, num_steps);
+    if (k == num_steps) {
+      if (traj) actor_launch(a, env, nullptr, &pass, s);  // the result of the last step; no forward pass
+      break;
+    }
+    float* actions = traj && traj->action ? traj->action + (size_t)k * row : actor_action_scratch(a);
+    actor_launch(a, env, actions, traj ? &pass : nullptr, s);
+    if (int rc = do_step(h, actions, s)) return rc;
+  }
+  HIP_TRY(h, hipGetLastError());
   return URGYM_OK;
 }
 

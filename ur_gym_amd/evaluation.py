@@ -9,6 +9,10 @@ VectorEnv verbs (the HIP environment of this package, or, in tests, the CPU orac
 The actor is re-implemented from the checkpoint's tensors (SB3 ``MultiInputPolicy``: features = concat of the Dict
 observation in sorted key order achieved_goal | desired_goal | observation; ``latent_pi`` = Linear-ReLU-Linear-ReLU;
 ``mu`` = Linear; deterministic action = tanh(mu)); stable-baselines3 itself is not needed.
+
+Two forms of the same loop: ``run_closed_loop`` with ``DeterministicActor`` (numpy, on the host: works on any backend, the CPU
+oracle included) and ``run_closed_loop_device`` with ``DeviceActor`` (the HIP actor kernel: observations, actions and the
+bookkeeping of model_test.py:38-50 stay on the GPU for the whole episode).
 """
 import numpy as np
 
@@ -88,3 +92,83 @@ class HipBackend:
     def step(self, actions):
         obs, rew, term, trunc, info = self.env.step(self.torch.from_numpy(actions).to(self.env.device))
         return rew.cpu().numpy().astype(np.float64), term.cpu().numpy(), info["is_success"].cpu().numpy()
+
+
+ACTOR_ARRAYS = ("latent_pi_0_weight", "latent_pi_0_bias", "latent_pi_2_weight", "latent_pi_2_bias", "mu_weight", "mu_bias")
+
+
+class DeviceActor:
+    """The same actor as ``DeterministicActor``, evaluated by the HIP kernel of the extension (urgym_actor_create).
+
+    It belongs to the environment it was loaded for (the native actor lives in that environment's handle) and is consumed by
+    ``env.policy_actions(actor)``, ``env.rollout_policy(actor, K)`` and ``run_closed_loop_device(env, actor)``.
+    """
+
+    def __init__(self, weights, env):
+        import ctypes as C
+
+        from . import _abi, _native
+
+        w = {k: v for k, v in dict(weights).items()}
+        self.in_features, self.hidden_width = self.check_shapes(w, env.env_kind)
+        self.env = env
+        arrays = [np.ascontiguousarray(w[k], dtype=np.float32) for k in ACTOR_ARRAYS]  # copied by the library during the call
+        desc = _abi.ActorDesc(self.in_features, self.hidden_width, 6, 0, *[a.ctypes.data_as(C.POINTER(C.c_float)) for a in arrays])
+        self._a = C.c_void_p()
+        _native.check(env.lib.urgym_actor_create(env._h, C.byref(desc), C.byref(self._a)), env._h)
+
+    @classmethod
+    def load(cls, npz_path, env):
+        return cls(np.load(npz_path), env)
+
+    @staticmethod
+    def check_shapes(weights, env_kind):
+        """Raises ValueError unless `weights` is an ``in -> H -> H -> 6`` actor the kernel supports for `env_kind`
+        (in = obs_dim + 2 goal_dim of that env, H a multiple of 32 and at most 512).  Returns (in_features, H).  Needs no GPU."""
+        from . import _abi
+
+        missing = [k for k in ACTOR_ARRAYS if k not in weights]
+        if missing:
+            raise ValueError(f"actor arrays missing: {missing}")
+        shape = {k: tuple(np.shape(weights[k])) for k in ACTOR_ARRAYS}
+        if any(len(shape[k]) != 2 for k in ACTOR_ARRAYS[0::2]) or any(len(shape[k]) != 1 for k in ACTOR_ARRAYS[1::2]):
+            raise ValueError(f"actor weights must be 2-d and biases 1-d, got {shape}")
+        (h0, in_features), (h1, h0_in), (out, h1_in) = shape["latent_pi_0_weight"], shape["latent_pi_2_weight"], shape["mu_weight"]
+        obs_dim, goal_dim = _abi.OBS_DIMS[env_kind]
+        if in_features != obs_dim + 2 * goal_dim:
+            raise ValueError(f"actor takes {in_features} features, this env offers {obs_dim + 2 * goal_dim} (achieved_goal | desired_goal | observation)")
+        if not (h0 == h1 == h0_in == h1_in):
+            raise ValueError(f"the two hidden layers must have one width, got {shape}")
+        if h0 % 32 != 0 or not 0 < h0 <= 512:
+            raise ValueError(f"hidden width must be a multiple of 32 and at most 512, got {h0}")
+        if out != 6:
+            raise ValueError(f"the actor must have 6 outputs, got {out}")
+        if shape["latent_pi_0_bias"] != (h0,) or shape["latent_pi_2_bias"] != (h0,) or shape["mu_bias"] != (6,):
+            raise ValueError(f"bias shapes do not match the weights: {shape}")
+        return in_features, h0
+
+    def close(self):
+        if getattr(self, "_a", None) and getattr(self.env, "_h", None):
+            self.env.lib.urgym_actor_destroy(self.env._h, self._a)
+        self._a = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def run_closed_loop_device(env, actor, max_steps=100):
+    """``run_closed_loop`` with everything on the device: `env` is a UR5ReachVectorEnv (auto-reset off, like there), `actor` a
+    DeviceActor of it.  One native call enqueues the max_steps x (actor, step) launches; the per-trial reward, success flag and
+    last step come from the episode summary the launches keep (model_test.py:38-50).  Returns the same dictionary."""
+    import torch
+
+    rec = env.rollout_policy(actor, max_steps, record=("episode_return", "episode_last_step", "episode_success"))
+    torch.cuda.synchronize(env.device)
+    reward = rec["episode_return"].cpu().numpy()
+    success = rec["episode_success"].cpu().numpy().astype(bool)
+    last = rec["episode_last_step"].cpu().numpy().astype(np.float64)
+    return {"success_rate_percent": 100.0 * success.mean(), "mean_episode_reward": float(reward.mean()),
+            "mean_last_step_index": float(last.mean()), "success": success, "reward": reward, "last_step": last}

@@ -191,6 +191,55 @@ class UR5ReachVectorEnv:
             raise ValueError("actions must be [K, N, 6]")
         _native.check(self.lib.urgym_rollout(self._h, C.c_void_p(a.data_ptr()), int(a.shape[0]), self._stream()), self._h)
 
+    # ------------------------------------------------------------------------------------------------ policy in the loop
+    RECORD_KEYS = tuple(name for name, _, _ in _abi.TRAJECTORY_FIELDS)
+
+    def _actor_ptr(self, actor):
+        if getattr(actor, "env", None) is not self or not getattr(actor, "_a", None):
+            raise ValueError("actor must be a live DeviceActor loaded for this environment (DeviceActor.load(npz, env))")
+        return actor._a
+
+    def policy_actions(self, actor, out=None):
+        """model.predict(obs, deterministic=True) (model_test.py:41) for all envs, by the HIP actor kernel, from the live
+        observation buffers: float32 [N, 6] on the device."""
+        a = self._actor_ptr(actor)
+        if out is None:
+            out = torch.empty((self.num_envs, 6), dtype=torch.float32, device=self.device)
+        elif out.shape != (self.num_envs, 6) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"out must be a contiguous float32 [{self.num_envs}, 6] tensor on {self.device}")
+        _native.check(self.lib.urgym_actor_forward(self._h, a, C.c_void_p(out.data_ptr()), self._stream()), self._h)
+        return out
+
+    def rollout_policy(self, actor, num_steps, record=("reward", "terminated", "truncated", "is_success")):
+        """`num_steps` x (actor, step) without returning to Python: the loop of model_test.py:38-50, or an on-policy collection.
+
+        `record` names what to keep (RECORD_KEYS; "all" = every one): per step ``observation`` / ``achieved_goal`` / ``desired_goal``
+        (what the actor saw) and ``action`` as [K, N, dim]; ``reward``, ``terminated``, ``truncated``, ``is_success``, ``collision``
+        as [K, N]; ``final_observation`` [K, N, obs_dim] (auto-reset only; rows valid where terminated | truncated); and per env the
+        summary of its first episode, ``episode_return`` (float64), ``episode_last_step``, ``episode_success``, ``episode_done``.
+        Returns a dict of fresh device tensors (flags as bool views).  Nothing is synchronised: the tensors are valid in stream
+        order.  Afterwards the environment is where `num_steps` calls of ``step`` would have left it."""
+        a = self._actor_ptr(actor)
+        K = int(num_steps)
+        if K < 0:
+            raise ValueError("num_steps must be >= 0")
+        names = self.RECORD_KEYS if record == "all" else tuple(record)
+        if record == "all" and not self.cfg.auto_reset:
+            names = tuple(n for n in names if n != "final_observation")
+        unknown = [n for n in names if n not in self.RECORD_KEYS]
+        if unknown:
+            raise ValueError(f"unknown record {unknown}; available: {self.RECORD_KEYS}")
+        if "final_observation" in names and not self.cfg.auto_reset:
+            raise ValueError("final_observation exists only with auto_reset")
+        traj, out = _abi.Trajectory(), {}
+        for name, ct, shape in _abi.TRAJECTORY_FIELDS:
+            if name in names:
+                t = torch.zeros(shape(K, self.num_envs, self.obs_dim, self.goal_dim), dtype=_TORCH_DTYPE[ct], device=self.device)
+                setattr(traj, name, C.cast(t.data_ptr(), C.POINTER(ct)))
+                out[name] = t.view(torch.bool) if ct is C.c_uint8 else t
+        _native.check(self.lib.urgym_rollout_actor(self._h, a, K, C.byref(traj) if names else None, self._stream()), self._h)
+        return out
+
     def close(self):
         if getattr(self, "_h", None):
             torch.cuda.synchronize(self.device)
