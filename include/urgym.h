@@ -244,6 +244,65 @@ int urgym_actor_forward(void* handle, void* actor, float* actions_dev, void* str
  * urgym_reset or urgym_refresh must have run on this binding. */
 int urgym_rollout_actor(void* handle, void* actor, int num_steps, const urgym_trajectory* traj, void* stream);
 
+/* ---- the stochastic half of the SAC policy (train.py: SAC("MultiInputPolicy", env, ...).learn collects experience with sampled
+ * actions, SB3's SquashedDiagGaussianDistribution; before learning_starts with uniform ones).  Added WITHIN ABI version 4: no
+ * struct above changed and URGYM_ABI_VERSION did not move, so a caller that may meet an older version-4 library finds
+ * urgym_actor_set_log_std / urgym_actor_sample / urgym_rollout_sampled by symbol lookup (dlsym) and does without them if absent.
+ *
+ * With h = latent_pi(x) of one env:
+ *   mu = W_mu h + b_mu,  log_std = min(max(W_ls h + b_ls, -20), 2)  (SB3's LOG_STD_MIN / LOG_STD_MAX),
+ *   pre = mu + exp(log_std) eps,  action = tanh(pre),
+ *   log_prob = sum_j [-eps_j^2 / 2 - log_std_j - log(2 pi) / 2] - sum_j log(1 - action_j^2 + 1e-6),
+ * the second sum being SB3's squash correction (epsilon = 1e-6) of the float32 action.  Everything is float32.
+ *
+ * The noise is a pure function of (seed, draw, env, component); the library keeps no random-number state.
+ *   Philox4x32-10 (Salmon et al., SC'11; the generator of the reset sampler), key = (seed & 0xFFFFFFFF, seed >> 32),
+ *   counter = (env, draw & 0xFFFFFFFF, draw >> 32, 0x504F4C00 | block), block = 0, 1.  The reset sampler's counters end in a block
+ *   number 0..4, so the two never meet, whatever the seeds.  Block 0 gives the words w0 w1 w2 w3, block 1 gives w4 w5 w6 w7
+ *   (w6, w7 are not used).  For a word w, m(w) = w >> 8 is a 24-bit integer and converts to float32 exactly.
+ *   UNIFORM   u_j = m(w_j) * 2^-24 in [0, 1), j = 0..5;  action_j = 2 u_j - 1 (exact in float32);  log_prob = -6 log 2, the density
+ *             of the uniform distribution on [-1, 1]^6.  There is no forward pass: mean_action and log_std are not written.
+ *   GAUSSIAN  Box-Muller on the pairs p = 0, 1, 2:  u1 = (m(w_2p) + 1) * 2^-24 in (0, 1],  u2 = m(w_2p+1) * 2^-24 in [0, 1),
+ *             r = sqrt(-2 ln u1),  eps_2p = r cos(2 pi u2),  eps_2p+1 = r sin(2 pi u2).  u1 and u2 are exact; ln, sqrt, cos and sin
+ *             are the float32 functions of whoever evaluates them, so two implementations agree to their rounding, not bitwise.
+ *   MEAN      eps = 0: action = tanh(mu), bitwise what urgym_actor_forward / urgym_rollout_actor give; log_prob is the formula
+ *             above at eps = 0.
+ * Pass k of a rollout uses draw = first_draw + k: K steps in one call and the same K steps in two calls (the second with
+ * first_draw advanced) draw the same noise, and the noise depends neither on N nor on the launch geometry. */
+enum { URGYM_SAMPLE_MEAN = 0, URGYM_SAMPLE_GAUSSIAN = 1, URGYM_SAMPLE_UNIFORM = 2 };
+
+typedef struct urgym_sampling {
+  int32_t mode;        /* URGYM_SAMPLE_* */
+  int32_t reserved0;   /* must be 0 */
+  uint64_t seed;       /* the Philox key */
+  uint64_t first_draw; /* draw index of the (first) pass */
+} urgym_sampling;
+
+/* What urgym_rollout_sampled records beyond urgym_trajectory: DEVICE pointers owned by the caller, each may be NULL.
+ * K = num_steps; row k belongs to the action of step k.  MEAN and GAUSSIAN need the log_std head for any of them. */
+typedef struct urgym_sample_records {
+  float* log_prob;    /* [K][N] */
+  float* noise;       /* [K][N][6] eps (GAUSSIAN), u (UNIFORM), 0 (MEAN) */
+  float* mean_action; /* [K][N][6] tanh(mu); not written by UNIFORM */
+  float* log_std;     /* [K][N][6] after the clamp; not written by UNIFORM */
+} urgym_sample_records;
+
+/* Attaches (or replaces) the log_std head of an actor: actor.log_std.weight [6][hidden_width] and actor.log_std.bias [6] of the
+ * checkpoint, HOST pointers, float32, copied during the call.  Synchronises the device (launches may be reading the old head). */
+int urgym_actor_set_log_std(void* handle, void* actor, const float* w_log_std, const float* b_log_std);
+
+/* Replaces model.predict(observation, deterministic=False) / SAC's _sample_action for all N envs: one launch from the bound
+ * observation buffers into actions_dev, float32 [N][6], with draw = how->first_draw.  log_prob_dev, float32 [N], may be NULL.
+ * Refused: how == NULL, an unknown mode, reserved0 != 0, GAUSSIAN (or MEAN with log_prob_dev) on an actor without log_std head. */
+int urgym_actor_sample(void* handle, void* actor, const urgym_sampling* how, float* actions_dev, float* log_prob_dev, void* stream);
+
+/* urgym_rollout_actor with sampled actions: the same contract (no host synchronisation, no allocation, everything validated
+ * before the first launch; traj and extra may be NULL) and the same refusals as urgym_actor_sample.  The sample records ride in
+ * the actor launch like the others.  With mode MEAN and no sample records this IS urgym_rollout_actor: the call is forwarded after
+ * the checks above, so an error met later (a HIP error of a launch) carries that name in urgym_last_error. */
+int urgym_rollout_sampled(void* handle, void* actor, const urgym_sampling* how, int num_steps, const urgym_trajectory* traj,
+                          const urgym_sample_records* extra, void* stream);
+
 /* Replaces Reach*.set_goal / set_goal_and_obstacle (reach.py:202-204, 328-335, 702-713): the caller has
  * overwritten goal / obst_start / obst_end (and possibly q) for the masked envs; this recomputes obstacle pose,
  * velocity, collision, link_dist and the observation for them, leaving step_count untouched. */

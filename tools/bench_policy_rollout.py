@@ -37,6 +37,12 @@ def main():
     ap.add_argument("--host-steps", type=int, default=20, help="steps of a window of the host loop (it is ~100x slower)")
     ap.add_argument("--warmup", type=int, default=110, help="steps before the first window (past the common truncation at step 100)")
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--sample", action="store_true",
+                    help="also time the stochastic half: the GAUSSIAN launch interleaved with the deterministic one, and a sampled "
+                         "rollout without records and with all of them (sample records included)")
+    ap.add_argument("--added-valu-per-wave", type=int, default=1858,
+                    help="--sample: vector instructions the sampling instance executes beyond the deterministic one (from the ISA)")
+    ap.add_argument("--clock-ghz", type=float, default=2.4)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
@@ -52,9 +58,11 @@ def main():
     n, K = args.num_envs, args.steps
     path = os.path.join(ROOT, "tests", "golden", "actors", f"actor_{ACTOR_NPZ[args.env]}.npz")
     w = dict(np.load(path))
+    if args.sample:
+        w.update(np.load(os.path.join(ROOT, "tests", "golden", "actors", f"log_std_{ACTOR_NPZ[args.env]}.npz")))
     env = make_vec(args.env, num_envs=n, device=dev, seed=0, auto_reset=True)
     env.reset(seed=0)
-    actor = DeviceActor.load(path, env)
+    actor = DeviceActor(w, env)
     host_actor, backend = DeterministicActor(w), HipBackend(env)
     tw = {k: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(dev) for k, v in w.items()}
     sync = lambda: torch.cuda.synchronize(env.device)
@@ -79,6 +87,17 @@ def main():
 
     variants = [("host_numpy_actor", host_loop, args.host_steps), ("torch_linear_actor", torch_loop, K),
                 ("device_actor", device_loop, K), ("device_actor_all_records", device_loop_recorded, K)]
+    if args.sample:
+        draws = [0]  # every window continues the draw sequence
+
+        def sampled(record):
+            def run(steps):
+                out = env.rollout_policy(actor, steps, record=record, sample=dict(mode="gaussian", seed=1, first_draw=draws[0]))
+                draws[0] += steps
+                return out
+            return run
+
+        variants += [("device_actor_gaussian", sampled(()), K), ("device_actor_gaussian_all_records", sampled("all"), K)]
     # warm-up: every variant once (code objects, BLAS algorithm choice, the allocator's blocks for the records), then past step 100
     for _, fn, steps in variants:
         fn(min(steps, 10))
@@ -107,6 +126,34 @@ def main():
     e1.record()
     sync()
     actor_us = e0.elapsed_time(e1) * 1e3 / reps
+    launch_pairs = None
+    if args.sample:
+        # Deterministic and GAUSSIAN launches of the same build, alternating windows of `reps` back-to-back launches in this process.
+        # Both go straight to the C ABI with fixed buffers, so the two windows differ in the kernel alone.
+        import ctypes as C
+
+        from ur_gym_amd import _abi
+
+        how = _abi.Sampling(_abi.SAMPLE_GAUSSIAN, 0, 1, 0)
+        log_prob = torch.empty((n,), dtype=torch.float32, device=dev)
+        h, a, stream = env._h, actor._a, env._stream()
+        act_p, lp_p = C.c_void_p(out.data_ptr()), C.c_void_p(log_prob.data_ptr())
+
+        def window(fn):
+            sync()
+            e0.record()
+            for _ in range(reps):
+                fn()
+            e1.record()
+            sync()
+            return e0.elapsed_time(e1) * 1e3 / reps
+
+        kinds = (lambda: env.lib.urgym_actor_forward(h, a, act_p, stream),
+                 lambda: env.lib.urgym_actor_sample(h, a, C.byref(how), act_p, lp_p, stream))
+        for fn in kinds:
+            for _ in range(10):
+                fn()
+        launch_pairs = [tuple(window(fn) for fn in kinds) for _ in range(10)]
     env.enable_timing(True, every=8)
     device_loop(K)
     sync()
@@ -126,6 +173,19 @@ def main():
         "actor_gflop_per_step": flop / 1e9, "actor_tflops": flop / actor_us / 1e6,
         "actor_fraction_of_f32_matrix_peak": flop / actor_us / 1e6 / F32_MATRIX_PEAK_TFLOPS,
     }
+    if launch_pairs:
+        det, gau = [p[0] for p in launch_pairs], [p[1] for p in launch_pairs]
+        det_med, gau_med, spread = float(np.median(det)), float(np.median(gau)), float(max(det) - min(det))
+        # what the added vector instructions would cost if none of them hid behind the matrix pipe: 4 cycles of issue each for
+        # one wave, two waves per SIMD (DESIGN.md section 8 counts them in the final ISA of the width-256 instance)
+        unhidden = args.added_valu_per_wave * 4 * 2 / (args.clock_ghz * 1e3)
+        result["sampling_launch"] = {
+            "deterministic_us_windows": [round(x, 3) for x in det], "gaussian_us_windows": [round(x, 3) for x in gau],
+            "deterministic_us_median": det_med, "gaussian_us_median": gau_med, "deterministic_us_spread": spread,
+            "gaussian_minus_deterministic_us": gau_med - det_med, "added_valu_per_wave": args.added_valu_per_wave,
+            "unhidden_valu_us": unhidden, "bar_us": det_med + unhidden + spread, "within_bar": gau_med <= det_med + unhidden + spread,
+            "parent_deterministic_us": 90.7,
+        }
     actor.close()
     env.close()
     line = json.dumps(result)

@@ -129,6 +129,29 @@ class Trajectory(C.Structure):
     _fields_ = [(name, C.POINTER(ct)) for name, ct, _ in TRAJECTORY_FIELDS]
 
 
+SAMPLE_MEAN, SAMPLE_GAUSSIAN, SAMPLE_UNIFORM = 0, 1, 2  # urgym_sampling.mode
+SAMPLE_MODES = {"mean": SAMPLE_MEAN, "gaussian": SAMPLE_GAUSSIAN, "uniform": SAMPLE_UNIFORM}
+NOISE_TAG = 0x504F4C00  # word 3 of the policy noise's Philox counter is NOISE_TAG | block
+
+
+class Sampling(C.Structure):
+    """urgym_sampling: how urgym_actor_sample / urgym_rollout_sampled draw."""
+    _fields_ = [("mode", C.c_int32), ("reserved0", C.c_int32), ("seed", C.c_uint64), ("first_draw", C.c_uint64)]
+
+
+# urgym_sample_records: name -> (ctype of element, shape given (K, N)); every pointer may be NULL
+SAMPLE_RECORD_FIELDS = [
+    ("log_prob", C.c_float, lambda K, N: (K, N)),
+    ("noise", C.c_float, lambda K, N: (K, N, 6)),
+    ("mean_action", C.c_float, lambda K, N: (K, N, 6)),
+    ("log_std", C.c_float, lambda K, N: (K, N, 6)),
+]
+
+
+class SampleRecords(C.Structure):
+    _fields_ = [(name, C.POINTER(ct)) for name, ct, _ in SAMPLE_RECORD_FIELDS]
+
+
 # Every symbol include/urgym.h declares (tests check that the built library exports each of them).
 EXPORTED_SYMBOLS = [
     "urgym_abi_version",
@@ -144,6 +167,9 @@ EXPORTED_SYMBOLS = [
     "urgym_actor_destroy",
     "urgym_actor_forward",
     "urgym_rollout_actor",
+    "urgym_actor_set_log_std",
+    "urgym_actor_sample",
+    "urgym_rollout_sampled",
     "urgym_refresh",
     "urgym_invalidate_records",
     "urgym_derive_obstacle_motion",

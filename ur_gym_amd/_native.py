@@ -62,6 +62,10 @@ def lib():
     L.urgym_actor_destroy.argtypes = [C.c_void_p, C.c_void_p]
     L.urgym_actor_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.urgym_rollout_actor.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(_abi.Trajectory), C.c_void_p]
+    L.urgym_actor_set_log_std.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.urgym_actor_sample.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.Sampling), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.urgym_rollout_sampled.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.Sampling), C.c_int, C.POINTER(_abi.Trajectory),
+                                        C.POINTER(_abi.SampleRecords), C.c_void_p]
     L.urgym_refresh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.urgym_invalidate_records.argtypes = [C.c_void_p]
     L.urgym_derive_obstacle_motion.argtypes = [C.c_void_p, C.c_void_p]

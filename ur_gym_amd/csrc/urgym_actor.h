@@ -41,4 +41,18 @@ uint8_t* actor_done_scratch(Actor* a);  // [N], ActorPass::ep_done of a rollout 
 // forward pass (actions != nullptr) and / or records (pass != nullptr) in ONE launch on `s`
 void actor_launch(Actor* a, const ActorEnv& env, float* actions, const ActorPass* pass, hipStream_t s);
 
+// How one pass samples (include/urgym.h, "the stochastic half"): the rows of this pass in the sample records, each may be null
+struct ActorSample {
+  int mode;  // URGYM_SAMPLE_*
+  uint64_t seed, draw;
+  float *log_prob, *noise, *mean_action, *log_std;
+};
+
+// attaches the log_std head ([6][hidden], [6], host pointers); the caller has made sure that no launch is reading the weights
+int actor_set_log_std(Actor* a, const float* w, const float* b, char* err, size_t err_len);
+bool actor_has_log_std(const Actor* a);
+
+// actor_launch with sampled actions (actions != nullptr).  UNIFORM runs no forward pass; MEAN and GAUSSIAN need the log_std head.
+void actor_launch_sampled(Actor* a, const ActorEnv& env, float* actions, const ActorPass* pass, const ActorSample& how, hipStream_t s);
+
 }  // namespace urgym

@@ -1,4 +1,4 @@
-// urgym_actor.hip — the deterministic SAC actor of the reference's checkpoints (SB3 MultiInputPolicy: tanh(mu(relu(L2(relu(L0(x)))))),
+// urgym_actor.hip — the SAC actor of the reference's checkpoints (SB3 MultiInputPolicy: tanh(mu(relu(L2(relu(L0(x)))))),
 // model_test.py:21,41) as one HIP kernel for MI355X (gfx950), and the records of a closed-loop rollout that ride in the same launch.
 //
 // float32 in, float32 weights, float32 accumulate on the f32-input matrix instruction v_mfma_f32_32x32x2_f32: D[32 x 32] +=
@@ -21,15 +21,24 @@
 //              buffered -- the next chunk is loaded into registers before the MFMAs of the current one and written to the other
 //              buffer after them, one barrier per chunk.  Biases and the layer-3 weights (8 HP + 8 floats) are staged once.
 //
+// The stochastic half (SB3's SquashedDiagGaussianDistribution; include/urgym.h states the semantics and the noise) is a second set
+// of instances of the same kernel, actor_kernel<HT, true>: layer 3 gets a second head, log_std (96 more fma per tile and lane, 12 sums
+// per env; its weights sit behind w_mu in the same packing, 14 HP + 16 floats staged once), and the epilogue draws the env's noise
+// (Philox4x32-10, urgym_philox.h: the reset sampler's function), squashes and evaluates the log-probability.  The deterministic
+// instances actor_kernel<HT, false> are compiled from the same text they were before.  URGYM_SAMPLE_UNIFORM needs no network:
+// uniform_kernel draws and records.
+//
 // This unit may contract a * b + c to fma (the step kernels in urgym_hip.hip may not).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "urgym_actor.h"
+#include "urgym_philox.h"
 
 namespace urgym {
 
@@ -47,12 +56,37 @@ constexpr int L1_CHUNK4 = 4 * L1_TILE4;          // float4 per staged layer-1 ch
 struct ActorKParams {
   const float4* p1;    // layer 1, packed [HT][L1_STEPS4][64 lanes] float4
   const float4* p2;    // layer 2, packed [HT][HT * 4][64 lanes] float4
-  const float4* small; // b0[HP] | b1[HP] | w_mu as [HP / 4][6][4] | b_mu[8]
+  const float4* small; // b0[HP] | b1[HP] | w_mu as [HP / 4][6][4] | b_mu[8] | w_log_std as [HP / 4][6][4] | b_log_std[8]
   ActorEnv env;
   float* actions;      // null: records only
   int record;          // pass is valid
   ActorPass pass;
 };
+struct ActorSParams : ActorKParams {  // the sampling instances and uniform_kernel
+  ActorSample how;
+};
+
+constexpr uint32_t NOISE_TAG = 0x504F4C00u;  // counter word 3 of the policy noise is NOISE_TAG | block (include/urgym.h)
+constexpr float TWO_M24 = 1.0f / 16777216.0f;
+constexpr float HALF_LOG_2PI = 0.918938533204672742f;
+constexpr float SIX_LOG_2 = 4.15888308335967186f;
+
+// the six words of (seed, draw, env) as their 24-bit integers m(w) = w >> 8, exact in float32
+__device__ __forceinline__ void noise_words(const ActorSample& S, uint32_t env, float m[6]) {
+  uint32_t a[4], b[4];
+  const uint32_t k0 = (uint32_t)S.seed, k1 = (uint32_t)(S.seed >> 32), d0 = (uint32_t)S.draw, d1 = (uint32_t)(S.draw >> 32);
+  philox4x32_10(k0, k1, env, d0, d1, NOISE_TAG | 0u, a);
+  philox4x32_10(k0, k1, env, d0, d1, NOISE_TAG | 1u, b);
+  m[0] = (float)(a[0] >> 8), m[1] = (float)(a[1] >> 8), m[2] = (float)(a[2] >> 8), m[3] = (float)(a[3] >> 8);
+  m[4] = (float)(b[0] >> 8), m[5] = (float)(b[1] >> 8);
+}
+
+__device__ __forceinline__ void store6(float* rows, size_t env, const float v[6]) {
+  float2* out = reinterpret_cast<float2*>(rows + env * 6);
+  out[0] = make_float2(v[0], v[1]);
+  out[1] = make_float2(v[2], v[3]);
+  out[2] = make_float2(v[4], v[5]);
+}
 
 __device__ __forceinline__ float feature(const ActorEnv& E, size_t e, int k) {
   const int gd = E.goal_dim;
@@ -113,14 +147,17 @@ __device__ void record_rows(const ActorEnv& E, const ActorPass& R, int env0, int
   }
 }
 
-// HT = tiles of 32 neurons per hidden layer (4, 8, 12, 16).  Up to HT = 8 the kernel fits 256 registers and 72 KB of LDS: two
+// HT = tiles of 32 neurons per hidden layer (4, 8, 12, 16).  Up to HT = 8 the kernel fits 256 registers and 80 KB of LDS: two
 // workgroups per CU, i.e. two waves per SIMD, one of which computes while the other waits at a barrier or for its weights.
-template <int HT>
-__global__ void __launch_bounds__(ACTOR_THREADS, (HT <= 8 ? 2 : 1)) actor_kernel(const ActorKParams P) {
+// SAMPLE: the log_std head next to mu and the sampling epilogue (MEAN or GAUSSIAN; P.how).
+template <int HT, bool SAMPLE>
+__global__ void __launch_bounds__(ACTOR_THREADS, (HT <= 8 ? 2 : 1))
+actor_kernel(const std::conditional_t<SAMPLE, ActorSParams, ActorKParams> P) {
   constexpr int HP = HT * 32;
   constexpr int L2_TILE4 = HT * 4 * 64;  // float4 per packed layer-2 tile
   constexpr int BUF4 = L1_CHUNK4 > L2_TILE4 ? L1_CHUNK4 : L2_TILE4;
-  constexpr int SMALL4 = (HP * 8 + 8) / 4;
+  constexpr int HEAD4 = (HP * 6 + 8) / 4;  // float4 per layer-3 head: weights, then the bias
+  constexpr int SMALL4 = (HP * 2) / 4 + (SAMPLE ? 2 : 1) * HEAD4;
   constexpr int L1_CHUNKS = HT / 4;
   constexpr int PF1 = L1_CHUNK4 / ACTOR_THREADS, PF2 = L2_TILE4 / ACTOR_THREADS;  // float4 per thread and staged chunk (6, HT)
   constexpr int PF = PF1 > PF2 ? PF1 : PF2;
@@ -195,6 +232,35 @@ __global__ void __launch_bounds__(ACTOR_THREADS, (HT <= 8 ? 2 : 1)) actor_kernel
 
   // ---- layer 2 tile by tile, each tile straight into layer 3
   float mu[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  float ls[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};  // SAMPLE only
+  // layer 3 of tile t on r = this lane's 16 relu'd neurons of the tile: w_mu packed [neuron / 4][6][neuron % 4]; the log_std head
+  // (SAMPLE) has the same packing, one head further
+  auto layer3 = [&](const f32x16& r, int t) {
+    const float4* wm = small4 + (2 * HP) / 4 + (size_t)((32 * t + 4 * h) / 4) * 6;
+#pragma unroll
+    for (int g = 0; g < 4; g++) {
+#pragma unroll
+      for (int o = 0; o < 6; o++) {
+        const float4 w = wm[2 * g * 6 + o];
+        mu[o] = fmaf(w.x, r[4 * g + 0], mu[o]);
+        mu[o] = fmaf(w.y, r[4 * g + 1], mu[o]);
+        mu[o] = fmaf(w.z, r[4 * g + 2], mu[o]);
+        mu[o] = fmaf(w.w, r[4 * g + 3], mu[o]);
+      }
+    }
+#pragma unroll
+    for (int g = 0; g < 4; g++) {
+#pragma unroll
+      for (int o = 0; o < 6; o++) {
+        const float4 w = wm[HEAD4 + 2 * g * 6 + o];
+        ls[o] = fmaf(w.x, r[4 * g + 0], ls[o]);
+        ls[o] = fmaf(w.y, r[4 * g + 1], ls[o]);
+        ls[o] = fmaf(w.z, r[4 * g + 2], ls[o]);
+        ls[o] = fmaf(w.w, r[4 * g + 3], ls[o]);
+      }
+    }
+  };
+  f32x16 prev;  // SAMPLE only: the tile before, through ReLU
 #pragma unroll 1
   for (int t = 0; t < HT; t++) {
     const int cur = (L1_CHUNKS + t) & 1;
@@ -208,6 +274,12 @@ __global__ void __launch_bounds__(ACTOR_THREADS, (HT <= 8 ? 2 : 1)) actor_kernel
       const float4 b = small4[(HP + 32 * t + 8 * g + 4 * h) / 4];
       acc[4 * g + 0] = b.x, acc[4 * g + 1] = b.y, acc[4 * g + 2] = b.z, acc[4 * g + 3] = b.w;
     }
+    if constexpr (SAMPLE) {
+      // Twice the layer-3 work does not fit behind the other wave's MFMAs any more (measured: none of it hid), so it is software
+      // pipelined: tile t - 1 goes through layer 3 next to the MFMAs of tile t, which do not depend on it -- each MFMA waits 64
+      // cycles for the one before, and the vector ALU fills those gaps.  Same fma order per output as the deterministic instance.
+      if (t > 0) layer3(prev, t - 1);
+    }
 #pragma unroll
     for (int sq = 0; sq < HT * 4; sq++) {  // sq = 4 u + g: registers 4 g .. 4 g + 3 of layer-1 tile u
       const float4 a = wb[sq * 64 + lane];
@@ -216,17 +288,22 @@ __global__ void __launch_bounds__(ACTOR_THREADS, (HT <= 8 ? 2 : 1)) actor_kernel
       acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, h1[4 * sq + 2], acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, h1[4 * sq + 3], acc, 0, 0, 0);
     }
-    // layer 3, this lane's 16 neurons of the tile: w_mu packed [neuron / 4][6][neuron % 4]
-    const float4* wm = small4 + (2 * HP) / 4 + (size_t)((32 * t + 4 * h) / 4) * 6;
+    if constexpr (SAMPLE) {
 #pragma unroll
-    for (int g = 0; g < 4; g++) {
+      for (int v = 0; v < 16; v++) prev[v] = fmaxf(acc[v], 0.0f);
+    } else {
+      // layer 3, this lane's 16 neurons of the tile: w_mu packed [neuron / 4][6][neuron % 4]
+      const float4* wm = small4 + (2 * HP) / 4 + (size_t)((32 * t + 4 * h) / 4) * 6;
 #pragma unroll
-      for (int o = 0; o < 6; o++) {
-        const float4 w = wm[2 * g * 6 + o];
-        mu[o] = fmaf(w.x, fmaxf(acc[4 * g + 0], 0.0f), mu[o]);
-        mu[o] = fmaf(w.y, fmaxf(acc[4 * g + 1], 0.0f), mu[o]);
-        mu[o] = fmaf(w.z, fmaxf(acc[4 * g + 2], 0.0f), mu[o]);
-        mu[o] = fmaf(w.w, fmaxf(acc[4 * g + 3], 0.0f), mu[o]);
+      for (int g = 0; g < 4; g++) {
+#pragma unroll
+        for (int o = 0; o < 6; o++) {
+          const float4 w = wm[2 * g * 6 + o];
+          mu[o] = fmaf(w.x, fmaxf(acc[4 * g + 0], 0.0f), mu[o]);
+          mu[o] = fmaf(w.y, fmaxf(acc[4 * g + 1], 0.0f), mu[o]);
+          mu[o] = fmaf(w.z, fmaxf(acc[4 * g + 2], 0.0f), mu[o]);
+          mu[o] = fmaf(w.w, fmaxf(acc[4 * g + 3], 0.0f), mu[o]);
+        }
       }
     }
     float4* wn = wbuf[cur ^ 1];
@@ -234,22 +311,86 @@ __global__ void __launch_bounds__(ACTOR_THREADS, (HT <= 8 ? 2 : 1)) actor_kernel
     for (int i = 0; i < PF2; i++) wn[tid + ACTOR_THREADS * i] = pf[i];
     __syncthreads();
   }
+  if constexpr (SAMPLE) layer3(prev, HT - 1);
 
-  float act[6];
+  if constexpr (!SAMPLE) {
+    float act[6];
 #pragma unroll
-  for (int o = 0; o < 6; o++) act[o] = tanhf(mu[o] + __shfl_xor(mu[o], 32) + small[HP * 8 + o]);
-  if (live && h == 0) {
-    float2* out = reinterpret_cast<float2*>(P.actions + (size_t)env * 6);
-    out[0] = make_float2(act[0], act[1]);
-    out[1] = make_float2(act[2], act[3]);
-    out[2] = make_float2(act[4], act[5]);
+    for (int o = 0; o < 6; o++) act[o] = tanhf(mu[o] + __shfl_xor(mu[o], 32) + small[HP * 8 + o]);
+    if (live && h == 0) {
+      float2* out = reinterpret_cast<float2*>(P.actions + (size_t)env * 6);
+      out[0] = make_float2(act[0], act[1]);
+      out[1] = make_float2(act[2], act[3]);
+      out[2] = make_float2(act[4], act[5]);
+    }
+  } else {
+    // Both lane halves hold the env's 12 sums after the cross-lane add and run the same epilogue; half 0 stores the action and the
+    // log-probability, half 1 the three optional records.
+    const ActorSample& S = P.how;
+    const bool gauss = S.mode == URGYM_SAMPLE_GAUSSIAN;
+    float eps[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (gauss) {
+      float m[6];
+      noise_words(S, (uint32_t)env, m);
+#pragma unroll
+      for (int p = 0; p < 3; p++) {  // Box-Muller: u1 in (0, 1], u2 in [0, 1), both exact
+        const float r = sqrtf(-2.0f * logf((m[2 * p] + 1.0f) * TWO_M24));
+        const float turn = 2.0f * (m[2 * p + 1] * TWO_M24);  // angle / pi: exact
+        eps[2 * p] = r * cospif(turn);
+        eps[2 * p + 1] = r * sinpif(turn);
+      }
+    }
+    float mean[6], lstd[6], act[6];
+    float lp = 0.0f;
+#pragma unroll
+    for (int o = 0; o < 6; o++) {
+      mean[o] = mu[o] + __shfl_xor(mu[o], 32) + small[HP * 8 + o];  // the deterministic instance's expression: MEAN is bitwise that path
+      lstd[o] = fminf(fmaxf(ls[o] + __shfl_xor(ls[o], 32) + small[HP * 14 + 8 + o], -20.0f), 2.0f);
+      act[o] = tanhf(gauss ? fmaf(expf(lstd[o]), eps[o], mean[o]) : mean[o]);
+      lp += -0.5f * eps[o] * eps[o] - lstd[o] - HALF_LOG_2PI - logf(1.0f - act[o] * act[o] + 1e-6f);
+    }
+    if (live && h == 0) {
+      store6(P.actions, (size_t)env, act);
+      if (S.log_prob) S.log_prob[env] = lp;
+    }
+    if (live && h == 1) {
+      if (S.noise) store6(S.noise, (size_t)env, eps);
+      if (S.log_std) store6(S.log_std, (size_t)env, lstd);
+      if (S.mean_action) {
+#pragma unroll
+        for (int o = 0; o < 6; o++) mean[o] = tanhf(mean[o]);
+        store6(S.mean_action, (size_t)env, mean);
+      }
+    }
   }
 }
 
-template <int HT>
-void launch(const ActorKParams& P, hipStream_t s) {
+// URGYM_SAMPLE_UNIFORM: SAC's warm-up before learning_starts.  No forward pass; the records ride here as they do in actor_kernel,
+// with the same geometry (128 envs per workgroup).
+__global__ void __launch_bounds__(ACTOR_THREADS) uniform_kernel(const ActorSParams P) {
+  const int tid = threadIdx.x;
+  const int N = P.env.N;
+  const int env0 = blockIdx.x * ACTOR_ENVS;
+  if (P.record) record_rows(P.env, P.pass, env0, min(ACTOR_ENVS, N - env0), tid);
+  const int env = env0 + tid;
+  if (!P.actions || tid >= ACTOR_ENVS || env >= N) return;
+  const ActorSample& S = P.how;
+  float u[6], act[6];
+  noise_words(S, (uint32_t)env, u);
+#pragma unroll
+  for (int o = 0; o < 6; o++) {
+    u[o] *= TWO_M24;             // exact
+    act[o] = 2.0f * u[o] - 1.0f;  // exact: a multiple of 2^-23 in [-1, 1)
+  }
+  store6(P.actions, (size_t)env, act);
+  if (S.log_prob) S.log_prob[env] = -SIX_LOG_2;
+  if (S.noise) store6(S.noise, (size_t)env, u);
+}
+
+template <int HT, bool SAMPLE, class Params>
+void launch(const Params& P, hipStream_t s) {
   const unsigned grid = (unsigned)((P.env.N + ACTOR_ENVS - 1) / ACTOR_ENVS);
-  hipLaunchKernelGGL(actor_kernel<HT>, dim3(grid), dim3(ACTOR_THREADS), 0, s, P);
+  hipLaunchKernelGGL((actor_kernel<HT, SAMPLE>), dim3(grid), dim3(ACTOR_THREADS), 0, s, P);
 }
 
 }  // namespace
@@ -258,6 +399,7 @@ struct Actor {
   int in_features = 0, hidden = 0, ht = 0, num_envs = 0;
   float* d_weights = nullptr;  // p1 | p2 | small
   size_t p2_off = 0, small_off = 0;  // in floats
+  bool has_log_std = false;    // the second head of `small` is filled (actor_set_log_std); zeros until then
   float* d_actions = nullptr;  // [N][6]
   uint8_t* d_done = nullptr;   // [N]
 };
@@ -283,7 +425,7 @@ int actor_create(const urgym_actor_desc* d, int in_features, int num_envs, Actor
   Actor* a = new (std::nothrow) Actor();
   if (!a) return refuse("out of memory");
   a->in_features = in, a->hidden = H, a->ht = HT, a->num_envs = num_envs;
-  const size_t n1 = (size_t)HT * L1_TILE4 * 4, n2 = (size_t)HT * HT * 4 * 64 * 4, ns = (size_t)HP * 8 + 8;
+  const size_t n1 = (size_t)HT * L1_TILE4 * 4, n2 = (size_t)HT * HT * 4 * 64 * 4, ns = (size_t)HP * 14 + 16;
   a->p2_off = n1, a->small_off = n1 + n2;
   std::vector<float> w(n1 + n2 + ns, 0.0f);
   // layer 1: float c of lane l's read sq of tile t = W0[32 t + (l & 31)][2 (4 sq + c) + (l >> 5)]
@@ -323,6 +465,21 @@ int actor_create(const urgym_actor_desc* d, int in_features, int num_envs, Actor
   return URGYM_OK;
 }
 
+int actor_set_log_std(Actor* a, const float* w_ls, const float* b_ls, char* err, size_t err_len) {
+  const int H = a->hidden, HP = a->ht * 32;
+  std::vector<float> head((size_t)HP * 6 + 8, 0.0f);  // w_log_std in w_mu's packing [neuron / 4][6][neuron % 4], then the bias
+  for (int n = 0; n < H; n++)
+    for (int o = 0; o < 6; o++) head[((size_t)(n / 4) * 6 + o) * 4 + n % 4] = w_ls[(size_t)o * H + n];
+  for (int o = 0; o < 6; o++) head[(size_t)HP * 6 + o] = b_ls[o];
+  const hipError_t e = hipMemcpy(a->d_weights + a->small_off + (size_t)HP * 8 + 8, head.data(), head.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    snprintf(err, err_len, "urgym_actor_set_log_std: %s", hipGetErrorString(e));
+    return URGYM_ERR_HIP;
+  }
+  a->has_log_std = true;
+  return URGYM_OK;
+}
+
 void actor_destroy(Actor* a) {
   if (!a) return;
   for (void* p : {(void*)a->d_weights, (void*)a->d_actions, (void*)a->d_done})
@@ -331,11 +488,13 @@ void actor_destroy(Actor* a) {
 }
 
 int actor_in_features(const Actor* a) { return a->in_features; }
+bool actor_has_log_std(const Actor* a) { return a->has_log_std; }
 float* actor_action_scratch(Actor* a) { return a->d_actions; }
 uint8_t* actor_done_scratch(Actor* a) { return a->d_done; }
 
-void actor_launch(Actor* a, const ActorEnv& env, float* actions, const ActorPass* pass, hipStream_t s) {
-  ActorKParams P;
+namespace {
+
+void fill_params(ActorKParams& P, Actor* a, const ActorEnv& env, float* actions, const ActorPass* pass) {
   P.p1 = reinterpret_cast<const float4*>(a->d_weights);
   P.p2 = reinterpret_cast<const float4*>(a->d_weights + a->p2_off);
   P.small = reinterpret_cast<const float4*>(a->d_weights + a->small_off);
@@ -343,11 +502,35 @@ void actor_launch(Actor* a, const ActorEnv& env, float* actions, const ActorPass
   P.actions = actions;
   P.record = pass != nullptr;
   if (pass) P.pass = *pass; else memset(&P.pass, 0, sizeof(P.pass));
+}
+
+}  // namespace
+
+void actor_launch(Actor* a, const ActorEnv& env, float* actions, const ActorPass* pass, hipStream_t s) {
+  ActorKParams P;
+  fill_params(P, a, env, actions, pass);
   switch (a->ht) {
-    case 4: launch<4>(P, s); break;
-    case 8: launch<8>(P, s); break;
-    case 12: launch<12>(P, s); break;
-    default: launch<16>(P, s); break;
+    case 4: launch<4, false>(P, s); break;
+    case 8: launch<8, false>(P, s); break;
+    case 12: launch<12, false>(P, s); break;
+    default: launch<16, false>(P, s); break;
+  }
+}
+
+void actor_launch_sampled(Actor* a, const ActorEnv& env, float* actions, const ActorPass* pass, const ActorSample& how, hipStream_t s) {
+  ActorSParams P;
+  fill_params(P, a, env, actions, pass);
+  P.how = how;
+  if (how.mode == URGYM_SAMPLE_UNIFORM) {
+    const unsigned grid = (unsigned)((env.N + ACTOR_ENVS - 1) / ACTOR_ENVS);
+    hipLaunchKernelGGL(uniform_kernel, dim3(grid), dim3(ACTOR_THREADS), 0, s, P);
+    return;
+  }
+  switch (a->ht) {
+    case 4: launch<4, true>(P, s); break;
+    case 8: launch<8, true>(P, s); break;
+    case 12: launch<12, true>(P, s); break;
+    default: launch<16, true>(P, s); break;
   }
 }
 

@@ -19,6 +19,7 @@ using std::fma; using std::sqrt; using std::fabs; using std::fmin; using std::fm
 #include <hip/hip_runtime.h>
 #define URGYM_LDS __attribute__((address_space(3)))
 #endif
+#include "urgym_philox.h"
 
 namespace urgym {
 
@@ -175,20 +176,7 @@ __device__ __forceinline__ double pos_distance(const double a[3], const double b
   return sqrt(dx * dx + dy * dy + dz * dz);
 }
 
-// ---------------------------------------------------------------------------------------------- Philox4x32-10
-__device__ __forceinline__ void philox4x32_10(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                              uint32_t out[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; r++) {
-    uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
+// ---------------------------------------------------------------------------------------------- Philox4x32-10 (urgym_philox.h)
 __device__ __forceinline__ double u01(uint32_t x) { return ((double)x + 0.5) * (1.0 / 4294967296.0); }
 
 // ---------------------------------------------------------------------------------------------- shapes / GJK

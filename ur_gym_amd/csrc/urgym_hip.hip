@@ -1963,6 +1963,21 @@ int enter_actor(Handle* h, void* actor, const char* who, Actor** out) {
   return URGYM_OK;
 }
 
+// the checks urgym_actor_sample and urgym_rollout_sampled share; wants_density: a log-probability or a sample record is asked for
+int check_sampling(Handle* h, const Actor* a, const urgym_sampling* how, bool wants_density, const char* who) {
+  char msg[200];
+  const char* what = nullptr;
+  if (!how) what = "null sampling description";
+  else if (how->reserved0 != 0) what = "urgym_sampling.reserved0 must be 0";
+  else if (how->mode != URGYM_SAMPLE_MEAN && how->mode != URGYM_SAMPLE_GAUSSIAN && how->mode != URGYM_SAMPLE_UNIFORM)
+    what = "unknown sampling mode (URGYM_SAMPLE_MEAN, _GAUSSIAN or _UNIFORM)";
+  else if (!actor_has_log_std(a) && (how->mode == URGYM_SAMPLE_GAUSSIAN || (how->mode == URGYM_SAMPLE_MEAN && wants_density)))
+    what = "the actor has no log_std head (urgym_actor_set_log_std)";
+  if (!what) return URGYM_OK;
+  snprintf(msg, sizeof(msg), "%s: %s", who, what);
+  return fail(h, URGYM_ERR_ARG, msg);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2161,6 +2176,66 @@ int urgym_rollout_actor(void* handle, void* actor, int num_steps, const urgym_tr
     }
     float* actions = traj && traj->action ? traj->action + (size_t)k * row : actor_action_scratch(a);
     actor_launch(a, env, actions, traj ? &pass : nullptr, s);
+    if (int rc = do_step(h, actions, s)) return rc;
+  }
+  HIP_TRY(h, hipGetLastError());
+  return URGYM_OK;
+}
+
+int urgym_actor_set_log_std(void* handle, void* actor, const float* w_log_std, const float* b_log_std) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  Actor* a = find_actor(h, actor);
+  if (!a) return fail(h, URGYM_ERR_ARG, "urgym_actor_set_log_std: not an actor of this handle");
+  if (!w_log_std || !b_log_std) return fail(h, URGYM_ERR_ARG, "urgym_actor_set_log_std: a weight or bias pointer is null");
+  HIP_TRY(h, hipSetDevice(h->device));
+  HIP_TRY(h, hipDeviceSynchronize());  // launches that read the head may still be in flight
+  return actor_set_log_std(a, w_log_std, b_log_std, h->err, sizeof(h->err));
+}
+
+int urgym_actor_sample(void* handle, void* actor, const urgym_sampling* how, float* actions_dev, float* log_prob_dev, void* stream) {
+  Handle* h = (Handle*)handle;
+  Actor* a = nullptr;
+  if (int rc = enter_actor(h, actor, "urgym_actor_sample", &a)) return rc;
+  if (int rc = check_sampling(h, a, how, log_prob_dev != nullptr, "urgym_actor_sample")) return rc;
+  if (!actions_dev) return fail(h, URGYM_ERR_ARG, "urgym_actor_sample: null actions");
+  if (how->mode == URGYM_SAMPLE_MEAN && !log_prob_dev)
+    actor_launch(a, actor_env(h), actions_dev, nullptr, (hipStream_t)stream);
+  else
+    actor_launch_sampled(a, actor_env(h), actions_dev, nullptr,
+                         ActorSample{how->mode, how->seed, how->first_draw, log_prob_dev, nullptr, nullptr, nullptr}, (hipStream_t)stream);
+  HIP_TRY(h, hipGetLastError());
+  return URGYM_OK;
+}
+
+int urgym_rollout_sampled(void* handle, void* actor, const urgym_sampling* how, int num_steps, const urgym_trajectory* traj,
+                          const urgym_sample_records* extra, void* stream) {
+  Handle* h = (Handle*)handle;
+  Actor* a = nullptr;
+  if (int rc = enter_actor(h, actor, "urgym_rollout_sampled", &a)) return rc;
+  const bool wants = extra && (extra->log_prob || extra->noise || extra->mean_action || extra->log_std);
+  if (int rc = check_sampling(h, a, how, wants, "urgym_rollout_sampled")) return rc;
+  if (num_steps < 0) return fail(h, URGYM_ERR_ARG, "urgym_rollout_sampled: num_steps < 0");
+  if (how->mode == URGYM_SAMPLE_MEAN && !wants) return urgym_rollout_actor(handle, actor, num_steps, traj, stream);
+  if (num_steps == 0) return URGYM_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const ActorEnv env = actor_env(h);
+  const size_t n = (size_t)h->cfg.num_envs, row = n * 6;
+  auto at = [](float* p, size_t off) { return p ? p + off : p; };
+  for (int k = 0; k <= num_steps; k++) {  // the launches and their order are urgym_rollout_actor's
+    ActorPass pass;
+    if (traj) pass = actor_pass(h, a, *traj, k, num_steps);
+    if (k == num_steps) {
+      if (traj) actor_launch(a, env, nullptr, &pass, s);
+      break;
+    }
+    float* actions = traj && traj->action ? traj->action + (size_t)k * row : actor_action_scratch(a);
+    ActorSample smp{how->mode, how->seed, how->first_draw + (uint64_t)k, nullptr, nullptr, nullptr, nullptr};
+    if (extra) {
+      smp.log_prob = at(extra->log_prob, (size_t)k * n), smp.noise = at(extra->noise, (size_t)k * row);
+      smp.mean_action = at(extra->mean_action, (size_t)k * row), smp.log_std = at(extra->log_std, (size_t)k * row);
+    }
+    actor_launch_sampled(a, env, actions, traj ? &pass : nullptr, smp, s);
     if (int rc = do_step(h, actions, s)) return rc;
   }
   HIP_TRY(h, hipGetLastError());

@@ -36,6 +36,81 @@ class DeterministicActor:
         return np.tanh(h @ self.w["mu_weight"].T + self.w["mu_bias"]).astype(np.float32)
 
 
+def philox4x32_10(key, counter):
+    """Philox4x32-10 (Salmon et al., SC'11) in numpy: key = (k0, k1) ints, counter = four uint32 arrays (broadcast together).
+    Returns the four output words as uint32 arrays.  The function of ur_gym_amd/csrc/urgym_philox.h."""
+    mask = np.uint64(0xFFFFFFFF)
+    c = [np.asarray(x, dtype=np.uint64) & mask for x in np.broadcast_arrays(*counter)]
+    k0, k1 = int(key[0]) & 0xFFFFFFFF, int(key[1]) & 0xFFFFFFFF
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]  # 32 x 32 bits: fits 64
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ np.uint64(k0), p1 & mask, (p0 >> np.uint64(32)) ^ c[3] ^ np.uint64(k1), p0 & mask]
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return [x.astype(np.uint32) for x in c]
+
+
+def policy_noise(seed, draw, env_ids, mode, dtype=np.float32):
+    """The noise of the device's sampled policy, restated from include/urgym.h ("the stochastic half"): a pure function of
+    (seed, draw, env, component).  `draw` and `env_ids` are integers or integer arrays that broadcast together; returns their
+    shape + (6,): eps ~ N(0, 1) for mode "gaussian", u in [0, 1) for "uniform" (the action is 2 u - 1), zeros for "mean".
+    `dtype` is the precision of ln / sqrt / cos / sin; the words and the uniforms are exact in either."""
+    from . import _abi
+
+    mode = _abi.SAMPLE_MODES.get(mode, mode)
+    env, draw = np.broadcast_arrays(np.asarray(env_ids, dtype=np.uint64), np.asarray(draw, dtype=np.uint64))
+    if mode == _abi.SAMPLE_MEAN:
+        return np.zeros(env.shape + (6,), dtype)
+    if mode not in (_abi.SAMPLE_GAUSSIAN, _abi.SAMPLE_UNIFORM):
+        raise ValueError(f"unknown sampling mode {mode!r}")
+    seed = int(seed)
+    key = (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
+    lo, hi = draw & np.uint64(0xFFFFFFFF), draw >> np.uint64(32)
+    a = philox4x32_10(key, (env, lo, hi, np.uint64(_abi.NOISE_TAG | 0)))
+    b = philox4x32_10(key, (env, lo, hi, np.uint64(_abi.NOISE_TAG | 1)))
+    m = np.stack([w >> np.uint32(8) for w in (a[0], a[1], a[2], a[3], b[0], b[1])], axis=-1).astype(dtype)  # 24 bits: exact
+    scale = dtype(2.0 ** -24)
+    if mode == _abi.SAMPLE_UNIFORM:
+        return m * scale
+    u1, u2 = (m[..., 0::2] + dtype(1)) * scale, m[..., 1::2] * scale  # (0, 1], [0, 1)
+    r, angle = np.sqrt(dtype(-2) * np.log(u1)), dtype(2 * np.pi) * u2
+    out = np.empty_like(m)
+    out[..., 0::2], out[..., 1::2] = r * np.cos(angle), r * np.sin(angle)
+    return out
+
+
+LOG_STD_MIN, LOG_STD_MAX = -20.0, 2.0  # SB3 sac/policies.py
+LOG_STD_ARRAYS = ("log_std_weight", "log_std_bias")
+
+
+class StochasticActor(DeterministicActor):
+    """The sampled half of the same policy (SB3 SquashedDiagGaussianDistribution) on the host, float32: needs the two log_std
+    arrays (tests/golden/gen_log_std_fixtures.py) next to DeterministicActor's six."""
+
+    def heads(self, achieved_goal, desired_goal, observation):
+        """(mu, log_std after the clamp), float32 [N, 6] each."""
+        x = np.concatenate([achieved_goal, desired_goal, observation], axis=1).astype(np.float32)
+        assert x.shape[1] == self.in_features, (x.shape, self.in_features)
+        h = np.maximum(x @ self.w["latent_pi_0_weight"].T + self.w["latent_pi_0_bias"], 0.0)
+        h = np.maximum(h @ self.w["latent_pi_2_weight"].T + self.w["latent_pi_2_bias"], 0.0)
+        mu = (h @ self.w["mu_weight"].T + self.w["mu_bias"]).astype(np.float32)
+        log_std = h @ self.w["log_std_weight"].T + self.w["log_std_bias"]
+        return mu, np.clip(log_std, LOG_STD_MIN, LOG_STD_MAX).astype(np.float32)
+
+    @staticmethod
+    def gaussian_log_prob(eps, log_std):
+        """sum_j [-eps_j^2 / 2 - log_std_j - log(2 pi) / 2] in the arrays' precision."""
+        t = eps.dtype.type
+        return (t(-0.5) * eps * eps - log_std - t(0.5 * np.log(2 * np.pi))).sum(axis=1)
+
+    def __call__(self, achieved_goal, desired_goal, observation, eps):
+        """eps: float32 [N, 6] (policy_noise(..., "gaussian"), or zeros for the mean).  Returns (action, log_prob)."""
+        mu, log_std = self.heads(achieved_goal, desired_goal, observation)
+        eps = np.asarray(eps, dtype=np.float32)
+        action = np.tanh(mu + np.exp(log_std) * eps).astype(np.float32)
+        squash = np.log(np.float32(1.0) - action * action + np.float32(1e-6)).sum(axis=1)
+        return action, (self.gaussian_log_prob(eps, log_std) - squash).astype(np.float32)
+
+
 def goal_grid(low, high, step=0.05, repeats=5):
     """utils/generate.py:29-43, 63-80: every grid node of the goal range, `repeats` times (float arithmetic as there)."""
     n = [int((high[i] - low[i]) / step) + 1 for i in range(3)]
@@ -116,6 +191,10 @@ class DeviceActor:
         desc = _abi.ActorDesc(self.in_features, self.hidden_width, 6, 0, *[a.ctypes.data_as(C.POINTER(C.c_float)) for a in arrays])
         self._a = C.c_void_p()
         _native.check(env.lib.urgym_actor_create(env._h, C.byref(desc), C.byref(self._a)), env._h)
+        self.has_log_std = all(k in w for k in LOG_STD_ARRAYS)  # the stochastic half: sample= of policy_actions / rollout_policy
+        if self.has_log_std:
+            head = [np.ascontiguousarray(w[k], dtype=np.float32) for k in LOG_STD_ARRAYS]
+            _native.check(env.lib.urgym_actor_set_log_std(env._h, self._a, *[a.ctypes.data_as(C.POINTER(C.c_float)) for a in head]), env._h)
 
     @classmethod
     def load(cls, npz_path, env):
@@ -145,6 +224,13 @@ class DeviceActor:
             raise ValueError(f"the actor must have 6 outputs, got {out}")
         if shape["latent_pi_0_bias"] != (h0,) or shape["latent_pi_2_bias"] != (h0,) or shape["mu_bias"] != (6,):
             raise ValueError(f"bias shapes do not match the weights: {shape}")
+        present = [k for k in LOG_STD_ARRAYS if k in weights]
+        if present:  # optional; both or neither, shaped like mu's
+            if len(present) != 2:
+                raise ValueError(f"log_std head needs both {LOG_STD_ARRAYS}, got only {present}")
+            got = tuple(tuple(np.shape(weights[k])) for k in LOG_STD_ARRAYS)
+            if got != ((6, h0), (6,)):
+                raise ValueError(f"log_std head must be [6, {h0}] and [6], got {got}")
         return in_features, h0
 
     def close(self):

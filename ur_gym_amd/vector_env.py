@@ -199,19 +199,51 @@ class UR5ReachVectorEnv:
             raise ValueError("actor must be a live DeviceActor loaded for this environment (DeviceActor.load(npz, env))")
         return actor._a
 
-    def policy_actions(self, actor, out=None):
+    SAMPLE_RECORD_KEYS = tuple(name for name, _, _ in _abi.SAMPLE_RECORD_FIELDS)
+
+    @staticmethod
+    def _sampling(sample):
+        """`sample`: a dict or object with ``mode`` ("mean" | "gaussian" | "uniform", or the URGYM_SAMPLE_* number), ``seed`` and
+        ``first_draw`` (both default 0) -> _abi.Sampling."""
+        get = sample.get if isinstance(sample, dict) else lambda k, d=None: getattr(sample, k, d)
+        mode = get("mode", "gaussian")
+        if isinstance(mode, str):
+            if mode not in _abi.SAMPLE_MODES:
+                raise ValueError(f"unknown sampling mode {mode!r}; available: {sorted(_abi.SAMPLE_MODES)}")
+            mode = _abi.SAMPLE_MODES[mode]
+        return _abi.Sampling(int(mode), 0, int(get("seed", 0) or 0), int(get("first_draw", 0) or 0))
+
+    def policy_actions(self, actor, out=None, sample=None):
         """model.predict(obs, deterministic=True) (model_test.py:41) for all envs, by the HIP actor kernel, from the live
-        observation buffers: float32 [N, 6] on the device."""
+        observation buffers: float32 [N, 6] on the device.
+
+        With `sample` (see ``rollout_policy``) the actions are drawn -- model.predict(obs, deterministic=False) -- and the return
+        value is ``(actions, log_prob)``, log_prob float32 [N] (None for mode "mean" on an actor without log_std head)."""
         a = self._actor_ptr(actor)
         if out is None:
             out = torch.empty((self.num_envs, 6), dtype=torch.float32, device=self.device)
         elif out.shape != (self.num_envs, 6) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
             raise ValueError(f"out must be a contiguous float32 [{self.num_envs}, 6] tensor on {self.device}")
-        _native.check(self.lib.urgym_actor_forward(self._h, a, C.c_void_p(out.data_ptr()), self._stream()), self._h)
-        return out
+        if sample is None:
+            _native.check(self.lib.urgym_actor_forward(self._h, a, C.c_void_p(out.data_ptr()), self._stream()), self._h)
+            return out
+        how = self._sampling(sample)
+        log_prob = None
+        if how.mode != _abi.SAMPLE_MEAN or actor.has_log_std:
+            log_prob = torch.empty((self.num_envs,), dtype=torch.float32, device=self.device)
+        _native.check(self.lib.urgym_actor_sample(self._h, a, C.byref(how), C.c_void_p(out.data_ptr()),
+                                                  C.c_void_p(log_prob.data_ptr()) if log_prob is not None else None, self._stream()), self._h)
+        return out, log_prob
 
-    def rollout_policy(self, actor, num_steps, record=("reward", "terminated", "truncated", "is_success")):
+    def rollout_policy(self, actor, num_steps, record=("reward", "terminated", "truncated", "is_success"), sample=None):
         """`num_steps` x (actor, step) without returning to Python: the loop of model_test.py:38-50, or an on-policy collection.
+
+        `sample` = dict(mode=, seed=, first_draw=) makes the actor stochastic, as SAC collects (train.py): mode "gaussian" draws
+        tanh(mu + exp(log_std) eps) (the actor needs its log_std arrays), "uniform" draws 2 u - 1 without a forward pass (SAC's
+        warm-up before learning_starts), "mean" is the deterministic policy.  Pass k uses draw first_draw + k, so a rollout split
+        in two calls (the second with first_draw advanced) draws the same noise; ``evaluation.policy_noise`` restates it.  With
+        `sample`, `record` may also name SAMPLE_RECORD_KEYS: ``log_prob`` [K, N], ``noise`` (eps, or u), ``mean_action`` =
+        tanh(mu) and ``log_std`` (clamped) as [K, N, 6]; "uniform" leaves the last two zero.  Without `sample` nothing changes.
 
         `record` names what to keep (RECORD_KEYS; "all" = every one): per step ``observation`` / ``achieved_goal`` / ``desired_goal``
         (what the actor saw) and ``action`` as [K, N, dim]; ``reward``, ``terminated``, ``truncated``, ``is_success``, ``collision``
@@ -223,12 +255,15 @@ class UR5ReachVectorEnv:
         K = int(num_steps)
         if K < 0:
             raise ValueError("num_steps must be >= 0")
-        names = self.RECORD_KEYS if record == "all" else tuple(record)
+        how = self._sampling(sample) if sample is not None else None
+        density = how is not None and (how.mode == _abi.SAMPLE_UNIFORM or actor.has_log_std)  # the sample records exist
+        names = self.RECORD_KEYS + (self.SAMPLE_RECORD_KEYS if density else ()) if record == "all" else tuple(record)
         if record == "all" and not self.cfg.auto_reset:
             names = tuple(n for n in names if n != "final_observation")
-        unknown = [n for n in names if n not in self.RECORD_KEYS]
+        known = self.RECORD_KEYS + (self.SAMPLE_RECORD_KEYS if how is not None else ())
+        unknown = [n for n in names if n not in known]
         if unknown:
-            raise ValueError(f"unknown record {unknown}; available: {self.RECORD_KEYS}")
+            raise ValueError(f"unknown record {unknown}; available: {known}")
         if "final_observation" in names and not self.cfg.auto_reset:
             raise ValueError("final_observation exists only with auto_reset")
         traj, out = _abi.Trajectory(), {}
@@ -237,7 +272,15 @@ class UR5ReachVectorEnv:
                 t = torch.zeros(shape(K, self.num_envs, self.obs_dim, self.goal_dim), dtype=_TORCH_DTYPE[ct], device=self.device)
                 setattr(traj, name, C.cast(t.data_ptr(), C.POINTER(ct)))
                 out[name] = t.view(torch.bool) if ct is C.c_uint8 else t
-        _native.check(self.lib.urgym_rollout_actor(self._h, a, K, C.byref(traj) if names else None, self._stream()), self._h)
+        if how is None:
+            _native.check(self.lib.urgym_rollout_actor(self._h, a, K, C.byref(traj) if names else None, self._stream()), self._h)
+            return out
+        extra = _abi.SampleRecords()
+        for name, ct, shape in _abi.SAMPLE_RECORD_FIELDS:
+            if name in names:
+                out[name] = torch.zeros(shape(K, self.num_envs), dtype=_TORCH_DTYPE[ct], device=self.device)
+                setattr(extra, name, C.cast(out[name].data_ptr(), C.POINTER(ct)))
+        _native.check(self.lib.urgym_rollout_sampled(self._h, a, C.byref(how), K, C.byref(traj), C.byref(extra), self._stream()), self._h)
         return out
 
     def close(self):
