@@ -136,22 +136,24 @@ def test_actor_kernel_against_float64(name):
         env.close()
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("name,n,steps", [("dyn", 4096, 130), ("obs", 1000, 20)])
-def test_teacher_forced_replay_is_bitwise(name, n, steps):
+def replay_teacher_forced(name, n, steps, w, sample=None, seed=17, min_finished=None):
+    """The body of the teacher-forced replay tests (tests/test_policy_sampling.py and tests/test_actor_widths.py run it too): a
+    recorded rollout of `steps` steps with the actor of the arrays `w` -- sampled if `sample` is given --, then a second environment
+    stepped from Python with the recorded actions, which must reproduce every recorded row and the final state BITWISE.  More than
+    `min_finished` (default n // 2) episodes must have ended on the way, so that final_observation had rows to be compared on.
+    Returns the records."""
     import torch
 
     from ur_gym_amd import make_vec
 
-    seed = 17
     env_a = make_vec(ENVS[name], num_envs=n, device="cuda:0", seed=seed, auto_reset=True)
     env_b = make_vec(ENVS[name], num_envs=n, device="cuda:0", seed=seed, auto_reset=True)
     env_a.reset(seed=seed)
     env_b.reset(seed=seed)
-    actor = DeviceActor.load(os.path.join(ACTORS, f"actor_{name}.npz"), env_a)
-    rec = env_a.rollout_policy(actor, steps, record="all")
+    actor = DeviceActor(w, env_a)
+    rec = env_a.rollout_policy(actor, steps, record="all", sample=sample)
     torch.cuda.synchronize()
-    assert set(rec) == set(env_a.RECORD_KEYS)
+    assert set(rec) == set(env_a.RECORD_KEYS + (env_a.SAMPLE_RECORD_KEYS if sample is not None else ()))
     finished = 0
     for k in range(steps):
         for key in ("observation", "achieved_goal", "desired_goal"):
@@ -163,7 +165,7 @@ def test_teacher_forced_replay_is_bitwise(name, n, steps):
         fin = term | trunc
         assert _same_bits(rec["final_observation"][k][fin], info["final_observation"]["observation"][fin]), ("final_observation", k)
         finished += int(fin.sum())
-    assert finished > n // 2  # the check above had rows to look at
+    assert finished > (n // 2 if min_finished is None else min_finished)  # the check above had rows to look at
     if steps > 100:
         assert bool(rec["truncated"].any())  # K passes the common truncation at step 100
     torch.cuda.synchronize()
@@ -174,6 +176,13 @@ def test_teacher_forced_replay_is_bitwise(name, n, steps):
     actor.close()
     env_a.close()
     env_b.close()
+    return rec
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,n,steps", [("dyn", 4096, 130), ("obs", 1000, 20)])
+def test_teacher_forced_replay_is_bitwise(name, n, steps):
+    replay_teacher_forced(name, n, steps, dict(np.load(os.path.join(ACTORS, f"actor_{name}.npz"))))
 
 
 @pytest.mark.gpu

@@ -248,16 +248,23 @@ def test_noise_record_is_policy_noise():
         assert np.array_equal(got[mode, 65536][:, :4097], got[mode, 4097]) and np.array_equal(got[mode, 4097][:, :1], got[mode, 1])
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("name", ["ori", "obs", "sta", "dyn"])
-def test_sampled_actions_and_log_prob_step_by_step(name):
-    """Every recorded step on its own (closed loops diverge): recorded observations and noise in, action / mean_action / log_std /
-    log_prob out, against float64.  No row is excluded."""
+def sampled_steps_against_float64(name, w, n, K, label=None, warm_steps=0):
+    """The body of the step-by-step test (tests/test_actor_widths.py runs it at the other hidden widths, after `warm_steps` random
+    steps): every recorded step of a GAUSSIAN rollout with the arrays `w` on its own (closed loops diverge): recorded observations
+    and noise in, action / mean_action / log_std / log_prob out, against float64.  No row is excluded.  Returns, per quantity,
+    [numpy float32 vs float64, device vs float64], and the records as numpy arrays."""
     import torch
 
-    n, K = 2048, 12
-    env, actor = _make(name, n, 23)
-    w = weights(name)
+    from ur_gym_amd import make_vec
+
+    label = label or name
+    env = make_vec(ENVS[name], num_envs=n, device="cuda:0", seed=23)
+    env.reset(seed=23)
+    g = torch.Generator(device="cuda:0")
+    g.manual_seed(5)
+    for _ in range(warm_steps):  # leave the neutral pose
+        env.step(torch.rand((n, 6), device="cuda:0", generator=g) * 2.0 - 1.0)
+    actor = DeviceActor(w, env)
     host = StochasticActor(w)
     rec = env.rollout_policy(actor, K, record=("observation", "achieved_goal", "desired_goal", "action") + env.SAMPLE_RECORD_KEYS,
                              sample=dict(mode="gaussian", seed=99, first_draw=1000))
@@ -285,23 +292,38 @@ def test_sampled_actions_and_log_prob_step_by_step(name):
                 worst[key][1] = max(worst[key][1], float(np.abs(devv[key].astype(np.float64) - ref[key]).max()))
         rows.append((np.abs(r["log_prob"][k].astype(np.float64) - (ref["gauss"] - squash)), (4 * U24 / (1.0 - a64 ** 2 + 1e-6)).sum(axis=1)))
     for key in ("action", "mean_action", "log_std"):
-        print(f"{name} {key}: numpy float32 vs float64 {worst[key][0]:.3e}, device vs float64 {worst[key][1]:.3e}, bound {4 * worst[key][0]:.3e}")
-        assert worst[key][1] <= 4.0 * worst[key][0], (name, key, worst[key])
+        print(f"{label} {key}: numpy float32 vs float64 {worst[key][0]:.3e}, device vs float64 {worst[key][1]:.3e}, bound {4 * worst[key][0]:.3e}")
+        assert worst[key][1] <= 4.0 * worst[key][0], (label, key, worst[key])
     dev = np.concatenate([d for d, _ in rows])
     bound = 4.0 * worst["gauss"][0] + np.concatenate([s for _, s in rows])
-    print(f"{name} log_prob: Gaussian part numpy float32 vs float64 {worst['gauss'][0]:.3e}; device vs float64 worst {dev.max():.3e}, "
+    print(f"{label} log_prob: Gaussian part numpy float32 vs float64 {worst['gauss'][0]:.3e}; device vs float64 worst {dev.max():.3e}, "
           f"worst excess over its row's bound {float((dev - bound).max()):.3e}, largest row bound {bound.max():.3e}")
-    assert np.all(dev <= bound), (name, float((dev - bound).max()))
+    assert np.all(dev <= bound), (label, float((dev - bound).max()))
+    return worst, r
 
 
 @pytest.mark.gpu
-def test_mean_mode_is_bitwise_the_deterministic_path():
+@pytest.mark.parametrize("name", ["ori", "obs", "sta", "dyn"])
+def test_sampled_actions_and_log_prob_step_by_step(name):
+    sampled_steps_against_float64(name, weights(name), 2048, 12)
+
+
+def mean_mode_is_bitwise_the_deterministic_path(name, n, K, w):
+    """The body of the MEAN-mode test (tests/test_actor_widths.py runs it at the other hidden widths): with the arrays `w`, MEAN
+    through the sampling instance, through the C ABI, and in a rollout with and without sample records is bitwise the deterministic
+    path, records and final state included."""
     import torch
 
-    n, K = 3000, 110
-    env_a, actor_a = _make("dyn", n, 31)
-    env_b, actor_b = _make("dyn", n, 31)
-    env_c, actor_c = _make("dyn", n, 31)
+    from ur_gym_amd import make_vec
+
+    def make():
+        env = make_vec(ENVS[name], num_envs=n, device="cuda:0", seed=31)
+        env.reset(seed=31)
+        return env, DeviceActor(w, env)
+
+    env_a, actor_a = make()
+    env_b, actor_b = make()
+    env_c, actor_c = make()
     a0 = env_a.policy_actions(actor_a)
     a1, lp = env_b.policy_actions(actor_b, sample=dict(mode="mean"))  # log_prob asked for: the sampling instance
     assert _same_bits(a0, a1) and lp.shape == (n,) and bool(torch.isfinite(lp).all())
@@ -320,10 +342,18 @@ def test_mean_mode_is_bitwise_the_deterministic_path():
     _same_state(env_a, env_b)
     _same_state(env_a, env_c)
     assert not bool(rec_c["noise"].any()) and _same_bits(rec_c["mean_action"], rec_c["action"])
-    assert bool(rec_a["truncated"].any())
+    if K > 100:
+        assert bool(rec_a["truncated"].any())  # K passes the common truncation at step 100
     for actor, env in ((actor_a, env_a), (actor_b, env_b), (actor_c, env_c)):
         actor.close()
         env.close()
+
+
+@pytest.mark.gpu
+def test_mean_mode_is_bitwise_the_deterministic_path():
+    import torch
+
+    mean_mode_is_bitwise_the_deterministic_path("dyn", 3000, 110, weights("dyn"))
     # the clamp of log_std: a synthetic head driven past both ends
     w = weights("dyn")
     w["log_std_weight"] = np.zeros_like(w["log_std_weight"])
@@ -343,35 +373,10 @@ def test_mean_mode_is_bitwise_the_deterministic_path():
 
 @pytest.mark.gpu
 def test_teacher_forced_replay_of_a_sampled_rollout_is_bitwise():
-    import torch
+    from test_policy_rollout import replay_teacher_forced
 
-    from ur_gym_amd import make_vec
-
-    name, n, steps, seed = "dyn", 4096, 130, 17
-    env_a, actor = _make(name, n, seed, auto_reset=True)
-    env_b = make_vec(ENVS[name], num_envs=n, device="cuda:0", seed=seed, auto_reset=True)
-    env_b.reset(seed=seed)
-    rec = env_a.rollout_policy(actor, steps, record="all", sample=dict(mode="gaussian", seed=7, first_draw=0))
-    torch.cuda.synchronize()
-    assert set(rec) == set(env_a.RECORD_KEYS + env_a.SAMPLE_RECORD_KEYS)
-    finished = 0
-    for k in range(steps):
-        for key in ("observation", "achieved_goal", "desired_goal"):
-            assert _same_bits(rec[key][k], env_b.buf[key]), (key, k)
-        obs, rew, term, trunc, info = env_b.step(rec["action"][k])
-        assert _same_bits(rec["reward"][k], rew), ("reward", k)
-        assert torch.equal(rec["terminated"][k], term) and torch.equal(rec["truncated"][k], trunc), ("flags", k)
-        assert torch.equal(rec["is_success"][k], info["is_success"]) and torch.equal(rec["collision"][k], info["collision"]), ("info", k)
-        fin = term | trunc
-        assert _same_bits(rec["final_observation"][k][fin], info["final_observation"]["observation"][fin]), ("final_observation", k)
-        finished += int(fin.sum())
-    assert finished > n // 2 and bool(rec["truncated"].any())  # K passes the common truncation at step 100
+    rec = replay_teacher_forced("dyn", 4096, 130, weights("dyn"), sample=dict(mode="gaussian", seed=7, first_draw=0))
     assert bool((rec["action"] != rec["mean_action"]).any())
-    torch.cuda.synchronize()
-    _same_state(env_a, env_b)
-    actor.close()
-    env_a.close()
-    env_b.close()
 
 
 @pytest.mark.gpu
