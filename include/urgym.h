@@ -303,6 +303,85 @@ int urgym_actor_sample(void* handle, void* actor, const urgym_sampling* how, flo
 int urgym_rollout_sampled(void* handle, void* actor, const urgym_sampling* how, int num_steps, const urgym_trajectory* traj,
                           const urgym_sample_records* extra, void* stream);
 
+/* ---- the critics of the SAC agent (train.py:40-48: SAC("MultiInputPolicy", env, gamma=0.95, batch_size=256); SB3's ContinuousCritic
+ * holds two Q-networks qf0, qf1, each Linear-ReLU-Linear-ReLU-Linear on cat([features, action]), features = achieved_goal |
+ * desired_goal | observation as for the actor).  Added WITHIN ABI version 4 like the sampling calls: no struct above changed,
+ * URGYM_ABI_VERSION did not move, the new symbols (urgym_critic_create / _destroy / _evaluate, urgym_actor_sample_rows) are found by
+ * lookup.  Inference only: no gradients, no optimiser, no Polyak update.
+ *
+ * For row m, with x = achieved_goal[m] | desired_goal[m] | observation[m] | action[m], everything float32:
+ *   q_i     = w_q,i . relu(W1,i relu(W0,i x + b0,i) + b1,i) + b_q,i,   i = 0, 1
+ *   q_min   = fminf(q_0, q_1)
+ *   v       = log_prob ? q_min - (ent_coef * log_prob[m]) : q_min
+ *   target  = reward[m] + ((gamma * nd) * v),   nd = (terminated && terminated[m]) ? 0.0f : 1.0f
+ * -- SAC's y = r + gamma (1 - done) (min_i Q_i(s', a') - alpha log pi(a'|s')).  In q_min, v and target every operation is one float32
+ * operation rounded on its own, in the association the parentheses show (no fused multiply-add), so a float32 restatement of these
+ * three lines is bitwise given q_0, q_1.  The sums of q_i are float32 fused-multiply-add chains in the kernel's own order: two
+ * implementations agree to rounding, and bitwise where every partial sum is exact.  A row's result depends on nothing but the row:
+ * not on count, not on the row's position, not on the launch geometry. */
+
+/* One Q-network: HOST pointers, float32, torch's [out][in] row-major layout; copied (re-packed) by urgym_critic_create, not kept. */
+typedef struct urgym_q_network {
+  const float* w0;  /* qf{i}.0.weight [hidden_width][in_features] */
+  const float* b0;  /* qf{i}.0.bias   [hidden_width] */
+  const float* w1;  /* qf{i}.2.weight [hidden_width][hidden_width] */
+  const float* b1;  /* qf{i}.2.bias   [hidden_width] */
+  const float* w_q; /* qf{i}.4.weight [1][hidden_width] */
+  const float* b_q; /* qf{i}.4.bias   [1] */
+} urgym_q_network;
+
+/* Supported: hidden_width a multiple of 32, at most 512; in_features = obs_dim + 2 * goal_dim + 6 of the handle's env kind. */
+typedef struct urgym_critic_desc {
+  int32_t in_features;  /* 36 | 38 | 47 | 53 (Ori | Obs | Sta | Dyn) */
+  int32_t hidden_width; /* width of both hidden layers of both networks (256 in the shipped checkpoints) */
+  int32_t n_critics;    /* must be 2 */
+  int32_t reserved0;    /* must be 0 */
+  urgym_q_network qf[2];
+} urgym_critic_desc;
+
+/* The rows an evaluation reads: DEVICE pointers, float32 row-major, `count` rows each.  observation == NULL means the handle's bound
+ * observation / achieved_goal / desired_goal buffers (then count must be num_envs, and achieved_goal / desired_goal are ignored). */
+typedef struct urgym_critic_rows {
+  const float* observation;   /* [count][obs_dim] or NULL */
+  const float* achieved_goal; /* [count][goal_dim] */
+  const float* desired_goal;  /* [count][goal_dim] */
+  const float* action;        /* [count][6]; always given to urgym_critic_evaluate, ignored by urgym_actor_sample_rows */
+} urgym_critic_rows;
+
+/* The terms of the SAC target: DEVICE pointers, each may be NULL. */
+typedef struct urgym_critic_terms {
+  const float* reward;       /* [count]; needed for target */
+  const uint8_t* terminated; /* [count]; NULL = no row is terminal */
+  const float* log_prob;     /* [count]; NULL = no entropy term */
+  float gamma;               /* 0.95 in the shipped checkpoints */
+  float ent_coef;            /* alpha = exp(log_ent_coef) */
+} urgym_critic_terms;
+
+/* What an evaluation writes: DEVICE pointers, each may be NULL, at least one is not. */
+typedef struct urgym_critic_out {
+  float* q;      /* [2][count] */
+  float* q_min;  /* [count] */
+  float* target; /* [count] */
+} urgym_critic_out;
+
+/* Checks the shapes, uploads the weights of both networks.  The critic belongs to the handle like an actor (urgym_destroy releases
+ * the ones still alive).  Refused: NULL arguments or weight pointers, n_critics != 2, reserved0 != 0, an unsupported hidden_width,
+ * in_features other than the env kind's. */
+int urgym_critic_create(void* handle, const urgym_critic_desc* desc, void** critic);
+int urgym_critic_destroy(void* handle, void* critic);
+
+/* Both Q-networks on `count` rows in ONE launch on `stream`; a recorded trajectory [K][N] is K * N rows.  No allocation and no host
+ * synchronisation; everything is validated before the launch.  terms may be NULL when no target is asked for.  Refused
+ * (URGYM_ERR_ARG): NULL handle / critic / rows / out / rows->action, a critic of another handle, count <= 0, observation == NULL with
+ * count != num_envs, observation given without achieved_goal and desired_goal, out->target without terms->reward, no output at all. */
+int urgym_critic_evaluate(void* handle, void* critic, const urgym_critic_rows* rows, int count, const urgym_critic_terms* terms, const urgym_critic_out* out, void* stream);
+
+/* urgym_actor_sample on explicit rows (SAC draws a' ~ pi(.|s') on next-observation rows, which are not the bound buffers): actions_dev
+ * float32 [count][6], log_prob_dev float32 [count] or NULL, draw = how->first_draw, and the `env` word of the noise counter is the row
+ * index -- on copies of the bound buffers the result is bitwise urgym_actor_sample's.  rows->observation == NULL means the bound
+ * buffers as above.  The refusals of urgym_actor_sample, and those of urgym_critic_evaluate that concern rows and count. */
+int urgym_actor_sample_rows(void* handle, void* actor, const urgym_sampling* how, const urgym_critic_rows* rows, int count, float* actions_dev, float* log_prob_dev, void* stream);
+
 /* Replaces Reach*.set_goal / set_goal_and_obstacle (reach.py:202-204, 328-335, 702-713): the caller has
  * overwritten goal / obst_start / obst_end (and possibly q) for the masked envs; this recomputes obstacle pose,
  * velocity, collision, link_dist and the observation for them, leaving step_count untouched. */

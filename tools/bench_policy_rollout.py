@@ -13,6 +13,13 @@ between the variants.  The actor launch alone is timed with device events around
 against the step launch (urgym_query_timing) and the float32 matrix peak.  One JSON line on stdout; --out also writes it to a file.
 
     python tools/bench_policy_rollout.py --out profiles/policy_rollout/dyn65536.json
+
+--critic measures the twin Q critic launch instead (urgym_critic_evaluate with q, q_min and the SAC target on the N bound rows):
+ten alternating windows of 200 back-to-back launches of (1) the deterministic actor, (2) the critic kernel, (3) the same evaluation
+in torch float32 on the device (cat, 2 x (3 F.linear, relu), minimum, target arithmetic).  Bar 1: critic median <= 2496 / 1216 x
+actor median + the spread of the actor's windows (the matrix instructions per wave of the two kernels at width 256).
+
+    python tools/bench_policy_rollout.py --critic --out profiles/policy_rollout/dyn65536_critic.json
 """
 import argparse
 import json
@@ -29,6 +36,101 @@ F32_MATRIX_PEAK_TFLOPS = 157.3  # MI355X, v_mfma_f32_32x32x2_f32 / v_mfma_f32_16
 ACTOR_NPZ = {"UR5OriReach-v1": "ori", "UR5ObsReach-v1": "obs", "UR5StaReach-v1": "sta", "UR5DynReach-v1": "dyn"}
 
 
+def critic_mode(args):
+    import ctypes as C
+
+    import torch
+    import torch.nn.functional as F
+
+    from ur_gym_amd import _abi, make_vec
+    from ur_gym_amd.evaluation import CRITIC_ARRAYS, DeviceActor, DeviceCritic
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_policy_rollout.py measures on a GPU; none is visible")
+    dev, n, kind = "cuda:0", args.num_envs, ACTOR_NPZ[args.env]
+    golden = os.path.join(ROOT, "tests", "golden")
+    env = make_vec(args.env, num_envs=n, device=dev, seed=0, auto_reset=True)
+    env.reset(seed=0)
+    actor = DeviceActor.load(os.path.join(golden, "actors", f"actor_{kind}.npz"), env)
+    paths = [os.path.join(golden, "critics", f"critic_{kind}_qf{i}.npz") for i in (0, 1)]
+    critic = DeviceCritic.load(paths, env)
+    with open(os.path.join(golden, "critics", "sac_hyperparameters.json")) as f:
+        hyp = json.load(f)[kind]
+    gamma, alpha = hyp["gamma"], float(np.exp(hyp["log_ent_coef"]))
+    tw = [{k: torch.from_numpy(np.ascontiguousarray(np.load(p)[k], dtype=np.float32)).to(dev) for k in CRITIC_ARRAYS} for p in paths]
+    for _ in range(20):
+        env.step(torch.rand((n, 6), device=dev) * 2.0 - 1.0)
+    b = env.buf
+    actions = torch.rand((n, 6), device=dev) * 2.0 - 1.0
+    log_prob = torch.randn((n,), device=dev) * 2.0 - 3.0
+    reward, term = b["reward"].clone(), b["terminated"].clone()
+    out = {k: torch.empty(shape, dtype=torch.float32, device=dev) for k, shape in (("a", (n, 6)), ("q", (2, n)), ("q_min", (n,)), ("target", (n,)))}
+    fp = lambda t: C.cast(t.data_ptr(), C.POINTER(C.c_float))  # noqa: E731
+    rows = _abi.CriticRows(None, None, None, fp(actions))
+    terms = _abi.CriticTerms(fp(reward), C.cast(term.data_ptr(), C.POINTER(C.c_uint8)), fp(log_prob), gamma, alpha)
+    outs = _abi.CriticOut(fp(out["q"]), fp(out["q_min"]), fp(out["target"]))
+    h, stream, a_p = env._h, env._stream(), C.c_void_p(out["a"].data_ptr())
+
+    def torch_critic():
+        x = torch.cat([b["achieved_goal"], b["desired_goal"], b["observation"], actions], dim=1)
+        q = []
+        for w in tw:
+            y = F.relu(F.linear(x, w["q_0_weight"], w["q_0_bias"]))
+            y = F.relu(F.linear(y, w["q_2_weight"], w["q_2_bias"]))
+            q.append(F.linear(y, w["q_4_weight"], w["q_4_bias"])[:, 0])
+        q_min = torch.minimum(q[0], q[1])
+        return q, q_min, reward + gamma * (1.0 - term.float()) * (q_min - alpha * log_prob)
+
+    def check(rc):
+        if rc != 0:
+            raise SystemExit(env.lib.urgym_last_error(h).decode())
+
+    kinds = {"actor": lambda: check(env.lib.urgym_actor_forward(h, actor._a, a_p, stream)),
+             "critic": lambda: check(env.lib.urgym_critic_evaluate(h, critic._c, C.byref(rows), n, C.byref(terms), C.byref(outs), stream)),
+             "torch_critic": torch_critic}
+    sync = lambda: torch.cuda.synchronize(env.device)  # noqa: E731
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for fn in kinds.values():
+        for _ in range(10):
+            fn()
+    # faster and different is not faster: the two evaluations agree to float32 rounding on these rows
+    sync()
+    tq, tq_min, tt = torch_critic()
+    agree = {"q": float((torch.stack(tq) - out["q"]).abs().max()), "q_min": float((tq_min - out["q_min"]).abs().max()),
+             "target": float((tt - out["target"]).abs().max()), "q_abs_max": float(out["q"].abs().max())}
+    windows = {k: [] for k in kinds}
+    for _ in range(args.windows):
+        for name, fn in kinds.items():
+            sync()
+            e0.record()
+            for _ in range(args.launches):
+                fn()
+            e1.record()
+            sync()
+            windows[name].append(e0.elapsed_time(e1) * 1e3 / args.launches)
+    med = {k: float(np.median(v)) for k, v in windows.items()}
+    spread = float(max(windows["actor"]) - min(windows["actor"]))
+    H = critic.hidden_width
+    flop = 2.0 * n * 2 * (critic.in_features * H + H * H + H)
+    result = {"tool": "bench_policy_rollout --critic", "env": args.env, "num_envs": n, "hidden_width": H, "windows": args.windows,
+              "launches_per_window": args.launches, "device": torch.cuda.get_device_name(0),
+              "us_windows": {k: [round(x, 3) for x in v] for k, v in windows.items()}, "us_median": med, "actor_us_spread": spread,
+              "mfma_per_wave": {"actor": 1216, "critic": 2496}, "bar1_us": 2496.0 / 1216.0 * med["actor"] + spread,
+              "within_bar1": med["critic"] <= 2496.0 / 1216.0 * med["actor"] + spread, "critic_over_actor": med["critic"] / med["actor"],
+              "not_slower_than_torch": med["critic"] <= med["torch_critic"], "speedup_over_torch": med["torch_critic"] / med["critic"],
+              "critic_gflop_per_launch": flop / 1e9, "critic_tflops": flop / med["critic"] / 1e6,
+              "critic_fraction_of_f32_matrix_peak": flop / med["critic"] / 1e6 / F32_MATRIX_PEAK_TFLOPS, "max_abs_difference_from_torch": agree}
+    critic.close()
+    actor.close()
+    env.close()
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--env", default="UR5DynReach-v1", choices=sorted(ACTOR_NPZ))
@@ -43,8 +145,13 @@ def main():
     ap.add_argument("--added-valu-per-wave", type=int, default=1858,
                     help="--sample: vector instructions the sampling instance executes beyond the deterministic one (from the ISA)")
     ap.add_argument("--clock-ghz", type=float, default=2.4)
+    ap.add_argument("--critic", action="store_true", help="measure the twin Q critic launch against the actor launch and torch (see above)")
+    ap.add_argument("--windows", type=int, default=10, help="--critic: alternating windows per kind")
+    ap.add_argument("--launches", type=int, default=200, help="--critic: back-to-back launches per window")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.critic:
+        return critic_mode(args)
 
     import torch
     import torch.nn.functional as F

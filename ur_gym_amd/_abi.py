@@ -152,6 +152,43 @@ class SampleRecords(C.Structure):
     _fields_ = [(name, C.POINTER(ct)) for name, ct, _ in SAMPLE_RECORD_FIELDS]
 
 
+class QNetwork(C.Structure):
+    """urgym_q_network: six HOST pointers to float32 arrays in torch's [out][in] layout."""
+    _fields_ = [(name, C.POINTER(C.c_float)) for name in ("w0", "b0", "w1", "b1", "w_q", "b_q")]
+
+
+class CriticDesc(C.Structure):
+    """urgym_critic_desc: dimensions + the two Q-networks."""
+    _fields_ = [
+        ("in_features", C.c_int32),
+        ("hidden_width", C.c_int32),
+        ("n_critics", C.c_int32),
+        ("reserved0", C.c_int32),
+        ("qf", QNetwork * 2),
+    ]
+
+
+class CriticRows(C.Structure):
+    """urgym_critic_rows: DEVICE pointers to `count` rows; observation NULL = the bound buffers."""
+    _fields_ = [(name, C.POINTER(C.c_float)) for name in ("observation", "achieved_goal", "desired_goal", "action")]
+
+
+class CriticTerms(C.Structure):
+    """urgym_critic_terms: the terms of the SAC target; every pointer may be NULL."""
+    _fields_ = [
+        ("reward", C.POINTER(C.c_float)),
+        ("terminated", C.POINTER(C.c_uint8)),
+        ("log_prob", C.POINTER(C.c_float)),
+        ("gamma", C.c_float),
+        ("ent_coef", C.c_float),
+    ]
+
+
+class CriticOut(C.Structure):
+    """urgym_critic_out: what urgym_critic_evaluate writes; every pointer may be NULL, not all."""
+    _fields_ = [(name, C.POINTER(C.c_float)) for name in ("q", "q_min", "target")]
+
+
 # Every symbol include/urgym.h declares (tests check that the built library exports each of them).
 EXPORTED_SYMBOLS = [
     "urgym_abi_version",
@@ -170,6 +207,10 @@ EXPORTED_SYMBOLS = [
     "urgym_actor_set_log_std",
     "urgym_actor_sample",
     "urgym_rollout_sampled",
+    "urgym_critic_create",
+    "urgym_critic_destroy",
+    "urgym_critic_evaluate",
+    "urgym_actor_sample_rows",
     "urgym_refresh",
     "urgym_invalidate_records",
     "urgym_derive_obstacle_motion",

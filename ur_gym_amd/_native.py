@@ -66,6 +66,12 @@ def lib():
     L.urgym_actor_sample.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.Sampling), C.c_void_p, C.c_void_p, C.c_void_p]
     L.urgym_rollout_sampled.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.Sampling), C.c_int, C.POINTER(_abi.Trajectory),
                                         C.POINTER(_abi.SampleRecords), C.c_void_p]
+    L.urgym_critic_create.argtypes = [C.c_void_p, C.POINTER(_abi.CriticDesc), C.POINTER(C.c_void_p)]
+    L.urgym_critic_destroy.argtypes = [C.c_void_p, C.c_void_p]
+    L.urgym_critic_evaluate.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.CriticRows), C.c_int, C.POINTER(_abi.CriticTerms),
+                                        C.POINTER(_abi.CriticOut), C.c_void_p]
+    L.urgym_actor_sample_rows.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.Sampling), C.POINTER(_abi.CriticRows), C.c_int, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]
     L.urgym_refresh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.urgym_invalidate_records.argtypes = [C.c_void_p]
     L.urgym_derive_obstacle_motion.argtypes = [C.c_void_p, C.c_void_p]

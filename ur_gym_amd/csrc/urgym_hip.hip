@@ -40,6 +40,7 @@
 #include "urgym_device.h"
 #include "urgym_launch_plan.h"
 #include "urgym_actor.h"
+#include "urgym_critic.h"
 #include "urgym_tables_host.h"
 
 using namespace urgym;
@@ -1573,6 +1574,7 @@ struct Handle {
   long steps_since_full_reset = -1; // step launches since the last urgym_reset of every env (-1: none yet)
   // policies (urgym_actor.hip)
   std::vector<Actor*> actors;  // alive, released by urgym_destroy at the latest
+  std::vector<Critic*> critics;  // the same for the twin Q-networks (urgym_critic.hip)
   bool observed = false;       // a reset / refresh has filled the bound observation buffers: an actor has something to read
 };
 thread_local char g_err[512] = {0};
@@ -1723,6 +1725,7 @@ void release(Handle* h) {
     if (p) hipFree(p);
   for (auto e : h->ev) hipEventDestroy(e);
   for (Actor* a : h->actors) actor_destroy(a);
+  for (Critic* c : h->critics) critic_destroy(c);
   delete h;
 }
 
@@ -1976,6 +1979,30 @@ int check_sampling(Handle* h, const Actor* a, const urgym_sampling* how, bool wa
   if (!what) return URGYM_OK;
   snprintf(msg, sizeof(msg), "%s: %s", who, what);
   return fail(h, URGYM_ERR_ARG, msg);
+}
+
+// ---- explicit rows (urgym_critic_evaluate, urgym_actor_sample_rows): the checks that concern rows and count; on success obs / ach /
+// des are the pointers to read (the bound buffers where rows->observation is null)
+int resolve_rows(Handle* h, const urgym_critic_rows* rows, int count, const char* who, const float** obs, const float** ach, const float** des) {
+  char msg[200];
+  const char* what = nullptr;
+  if (!rows) what = "null rows";
+  else if (count <= 0) what = "count must be positive";
+  else if (!rows->observation && count != h->cfg.num_envs) what = "rows->observation is null (the bound buffers): count must be num_envs";
+  else if (rows->observation && (!rows->achieved_goal || !rows->desired_goal)) what = "rows->achieved_goal or rows->desired_goal is null";
+  if (what) {
+    snprintf(msg, sizeof(msg), "%s: %s", who, what);
+    return fail(h, URGYM_ERR_ARG, msg);
+  }
+  if (!rows->observation && !h->observed) {
+    snprintf(msg, sizeof(msg), "%s: no observations yet: call urgym_reset (or urgym_refresh) first", who);
+    return fail(h, URGYM_ERR_STATE, msg);
+  }
+  const bool bound = !rows->observation;
+  *obs = bound ? h->buf.observation : rows->observation;
+  *ach = bound ? h->buf.achieved_goal : rows->achieved_goal;
+  *des = bound ? h->buf.desired_goal : rows->desired_goal;
+  return URGYM_OK;
 }
 
 }  // namespace
@@ -2238,6 +2265,83 @@ int urgym_rollout_sampled(void* handle, void* actor, const urgym_sampling* how, 
     actor_launch_sampled(a, env, actions, traj ? &pass : nullptr, smp, s);
     if (int rc = do_step(h, actions, s)) return rc;
   }
+  HIP_TRY(h, hipGetLastError());
+  return URGYM_OK;
+}
+
+int urgym_actor_sample_rows(void* handle, void* actor, const urgym_sampling* how, const urgym_critic_rows* rows, int count, float* actions_dev, float* log_prob_dev, void* stream) {
+  const char* who = "urgym_actor_sample_rows";
+  Handle* h = (Handle*)handle;
+  if (int rc = enter_bound(h)) return rc;
+  Actor* a = find_actor(h, actor);
+  if (!a) return fail(h, URGYM_ERR_ARG, "urgym_actor_sample_rows: not an actor of this handle (actors belong to the handle they were created with)");
+  if (actor_in_features(a) != actor_features(h)) return fail(h, URGYM_ERR_ARG, "urgym_actor_sample_rows: the actor does not take this env kind's features");
+  if (int rc = check_sampling(h, a, how, log_prob_dev != nullptr, who)) return rc;
+  if (!actions_dev) return fail(h, URGYM_ERR_ARG, "urgym_actor_sample_rows: null actions");
+  ActorEnv env;
+  memset(&env, 0, sizeof(env));  // no records ride in this launch: the step outputs are not read
+  if (int rc = resolve_rows(h, rows, count, who, &env.observation, &env.achieved_goal, &env.desired_goal)) return rc;
+  env.N = count, env.obs_dim = h->obs_dim, env.goal_dim = h->goal_dim;
+  if (how->mode == URGYM_SAMPLE_MEAN && !log_prob_dev)
+    actor_launch(a, env, actions_dev, nullptr, (hipStream_t)stream);
+  else
+    actor_launch_sampled(a, env, actions_dev, nullptr, ActorSample{how->mode, how->seed, how->first_draw, log_prob_dev, nullptr, nullptr, nullptr},
+                         (hipStream_t)stream);
+  HIP_TRY(h, hipGetLastError());
+  return URGYM_OK;
+}
+
+int urgym_critic_create(void* handle, const urgym_critic_desc* desc, void** critic) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (!critic) return fail(h, URGYM_ERR_ARG, "urgym_critic_create: null argument");
+  HIP_TRY(h, hipSetDevice(h->device));
+  Critic* c = nullptr;
+  if (int rc = critic_create(desc, actor_features(h) + 6, &c, h->err, sizeof(h->err))) return rc;
+  h->critics.push_back(c);
+  *critic = c;
+  return URGYM_OK;
+}
+
+int urgym_critic_destroy(void* handle, void* critic) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (!critic) return URGYM_OK;
+  for (size_t i = 0; i < h->critics.size(); i++)
+    if (h->critics[i] == critic) {
+      hipSetDevice(h->device);
+      hipDeviceSynchronize();  // launches that read its weights may still be in flight
+      critic_destroy(h->critics[i]);
+      h->critics.erase(h->critics.begin() + i);
+      return URGYM_OK;
+    }
+  return fail(h, URGYM_ERR_ARG, "urgym_critic_destroy: not a critic of this handle");
+}
+
+int urgym_critic_evaluate(void* handle, void* critic, const urgym_critic_rows* rows, int count, const urgym_critic_terms* terms, const urgym_critic_out* out, void* stream) {
+  const char* who = "urgym_critic_evaluate";
+  Handle* h = (Handle*)handle;
+  if (int rc = enter_bound(h)) return rc;
+  Critic* c = nullptr;
+  for (Critic* x : h->critics)
+    if (x == critic) c = x;
+  if (!c) return fail(h, URGYM_ERR_ARG, "urgym_critic_evaluate: not a critic of this handle (critics belong to the handle they were created with)");
+  if (critic_in_features(c) != actor_features(h) + 6) return fail(h, URGYM_ERR_ARG, "urgym_critic_evaluate: the critic does not take this env kind's features");
+  CriticCall call;
+  memset(&call, 0, sizeof(call));
+  if (int rc = resolve_rows(h, rows, count, who, &call.observation, &call.achieved_goal, &call.desired_goal)) return rc;
+  if (!rows->action) return fail(h, URGYM_ERR_ARG, "urgym_critic_evaluate: rows->action is null");
+  if (!out) return fail(h, URGYM_ERR_ARG, "urgym_critic_evaluate: null out");
+  if (!out->q && !out->q_min && !out->target) return fail(h, URGYM_ERR_ARG, "urgym_critic_evaluate: no output requested (q, q_min and target are all null)");
+  if (out->target && (!terms || !terms->reward)) return fail(h, URGYM_ERR_ARG, "urgym_critic_evaluate: target requested without terms->reward");
+  call.M = count, call.obs_dim = h->obs_dim, call.goal_dim = h->goal_dim;
+  call.action = rows->action;
+  if (terms && out->target) {
+    call.reward = terms->reward, call.terminated = terms->terminated, call.log_prob = terms->log_prob;
+    call.gamma = terms->gamma, call.ent_coef = terms->ent_coef;
+  }
+  call.q = out->q, call.q_min = out->q_min, call.target = out->target;
+  critic_launch(c, call, (hipStream_t)stream);
   HIP_TRY(h, hipGetLastError());
   return URGYM_OK;
 }

@@ -245,6 +245,119 @@ class DeviceActor:
             pass
 
 
+CRITIC_ARRAYS = ("q_0_weight", "q_0_bias", "q_2_weight", "q_2_bias", "q_4_weight", "q_4_bias")
+
+
+class TwinCritic:
+    """The two Q-networks of the SAC agent (SB3 ContinuousCritic of MultiInputPolicy: q_i = Linear-ReLU-Linear-ReLU-Linear on
+    achieved_goal | desired_goal | observation | action) on the host, float32, and the SAC target as include/urgym.h states it.
+    `weights`: the two networks, each a mapping with CRITIC_ARRAYS (tests/golden/gen_critic_fixtures.py writes one file each)."""
+
+    def __init__(self, weights):
+        self.qf = [{k: np.asarray(dict(w)[k], dtype=np.float32) for k in CRITIC_ARRAYS} for w in weights]
+        self.in_features = self.qf[0]["q_0_weight"].shape[1]
+
+    @classmethod
+    def load(cls, npz_paths):
+        return cls([np.load(p) for p in npz_paths])
+
+    def __call__(self, achieved_goal, desired_goal, observation, action):
+        """(q0, q1), float32 [M] each."""
+        x = np.concatenate([achieved_goal, desired_goal, observation, action], axis=1).astype(np.float32)
+        assert x.shape[1] == self.in_features, (x.shape, self.in_features)
+        out = []
+        for w in self.qf:
+            h = np.maximum(x @ w["q_0_weight"].T + w["q_0_bias"], 0.0)
+            h = np.maximum(h @ w["q_2_weight"].T + w["q_2_bias"], 0.0)
+            out.append((h @ w["q_4_weight"].T + w["q_4_bias"])[:, 0].astype(np.float32))
+        return tuple(out)
+
+    @staticmethod
+    def target(q0, q1, reward, gamma, terminated=None, log_prob=None, ent_coef=0.0):
+        """(q_min, target) in float32, operation by operation as urgym_critic_evaluate does:
+        target = reward + ((gamma * not_done) * (q_min - (ent_coef * log_prob)))."""
+        f = np.float32
+        q_min = np.minimum(np.asarray(q0, f), np.asarray(q1, f))
+        v = q_min
+        if log_prob is not None:
+            v = q_min - f(ent_coef) * np.asarray(log_prob, f)
+        not_done = np.ones_like(q_min) if terminated is None else np.where(np.asarray(terminated).astype(bool), f(0), f(1))
+        return q_min, (np.asarray(reward, f) + (f(gamma) * not_done) * v).astype(f)
+
+
+class DeviceCritic:
+    """The same two networks as ``TwinCritic``, evaluated by the HIP kernel of the extension (urgym_critic_create).  Belongs to the
+    environment it was loaded for, like ``DeviceActor``; consumed by ``env.critic_values(critic, actions, ...)``."""
+
+    def __init__(self, weights, env):
+        import ctypes as C
+
+        from . import _abi, _native
+
+        weights = [dict(w) for w in weights]
+        self.in_features, self.hidden_width = self.check_shapes(weights, env.env_kind)
+        self.env = env
+        desc = _abi.CriticDesc(self.in_features, self.hidden_width, 2, 0)
+        keep = []  # copied by the library during the call
+        for i, w in enumerate(weights):
+            arrays = [np.ascontiguousarray(w[k], dtype=np.float32) for k in CRITIC_ARRAYS]
+            keep.append(arrays)
+            desc.qf[i] = _abi.QNetwork(*[a.ctypes.data_as(C.POINTER(C.c_float)) for a in arrays])
+        self._c = C.c_void_p()
+        _native.check(env.lib.urgym_critic_create(env._h, C.byref(desc), C.byref(self._c)), env._h)
+
+    @classmethod
+    def load(cls, npz_paths, env):
+        return cls([np.load(p) for p in npz_paths], env)
+
+    @staticmethod
+    def check_shapes(weights, env_kind):
+        """Raises ValueError unless `weights` is a pair of ``in -> H -> H -> 1`` networks the kernel supports for `env_kind`
+        (in = obs_dim + 2 goal_dim + 6 of that env, one H for all four hidden layers, a multiple of 32 and at most 512).
+        Returns (in_features, H).  Needs no GPU."""
+        from . import _abi
+
+        weights = list(weights)
+        if len(weights) != 2:
+            raise ValueError(f"a twin critic has two Q-networks, got {len(weights)}")
+        obs_dim, goal_dim = _abi.OBS_DIMS[env_kind]
+        want_in = obs_dim + 2 * goal_dim + 6
+        widths = []
+        for i, w in enumerate(weights):
+            missing = [k for k in CRITIC_ARRAYS if k not in w]
+            if missing:
+                raise ValueError(f"qf{i}: critic arrays missing: {missing}")
+            shape = {k: tuple(np.shape(w[k])) for k in CRITIC_ARRAYS}
+            if any(len(shape[k]) != 2 for k in CRITIC_ARRAYS[0::2]) or any(len(shape[k]) != 1 for k in CRITIC_ARRAYS[1::2]):
+                raise ValueError(f"qf{i}: critic weights must be 2-d and biases 1-d, got {shape}")
+            (h0, in_features), (h1, h0_in), (out, h1_in) = shape["q_0_weight"], shape["q_2_weight"], shape["q_4_weight"]
+            if in_features != want_in:
+                raise ValueError(f"qf{i} takes {in_features} features, this env offers {want_in} (achieved_goal | desired_goal | observation | action)")
+            if not (h0 == h1 == h0_in == h1_in):
+                raise ValueError(f"qf{i}: the two hidden layers must have one width, got {shape}")
+            if h0 % 32 != 0 or not 0 < h0 <= 512:
+                raise ValueError(f"qf{i}: hidden width must be a multiple of 32 and at most 512, got {h0}")
+            if out != 1:
+                raise ValueError(f"qf{i} must have 1 output, got {out}")
+            if shape["q_0_bias"] != (h0,) or shape["q_2_bias"] != (h0,) or shape["q_4_bias"] != (1,):
+                raise ValueError(f"qf{i}: bias shapes do not match the weights: {shape}")
+            widths.append(h0)
+        if widths[0] != widths[1]:
+            raise ValueError(f"both Q-networks must have one hidden width, got {widths}")
+        return want_in, widths[0]
+
+    def close(self):
+        if getattr(self, "_c", None) and getattr(self.env, "_h", None):
+            self.env.lib.urgym_critic_destroy(self.env._h, self._c)
+        self._c = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def run_closed_loop_device(env, actor, max_steps=100):
     """``run_closed_loop`` with everything on the device: `env` is a UR5ReachVectorEnv (auto-reset off, like there), `actor` a
     DeviceActor of it.  One native call enqueues the max_steps x (actor, step) launches; the per-trial reward, success flag and

@@ -213,13 +213,103 @@ class UR5ReachVectorEnv:
             mode = _abi.SAMPLE_MODES[mode]
         return _abi.Sampling(int(mode), 0, int(get("seed", 0) or 0), int(get("first_draw", 0) or 0))
 
-    def policy_actions(self, actor, out=None, sample=None):
+    ROW_KEYS = ("observation", "achieved_goal", "desired_goal")
+
+    def _rows(self, rows, action=None):
+        """`rows` (see ``critic_values``) -> (_abi.CriticRows, leading shape, the tensors to keep alive).  None = the bound buffers."""
+        dims = dict(observation=self.obs_dim, achieved_goal=self.goal_dim, desired_goal=self.goal_dim, action=6)
+        given = {}
+        if rows is not None:
+            given = dict(zip(self.ROW_KEYS, rows)) if isinstance(rows, (tuple, list)) else {k: rows[k] for k in self.ROW_KEYS if k in rows}
+            if set(given) != set(self.ROW_KEYS):
+                raise ValueError(f"rows must give {self.ROW_KEYS} (the dict rollout_policy returns with these records, or a tuple in this order)")
+        if action is not None:
+            given["action"] = action
+        lead, keep, cr = None, [], _abi.CriticRows()
+        for name, t in given.items():
+            t = torch.as_tensor(t, device=self.device)
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                t = t.to(torch.float32).contiguous()
+            if t.dim() not in (2, 3) or t.shape[-1] != dims[name]:
+                raise ValueError(f"{name} must be [M, {dims[name]}] or [K, N, {dims[name]}], got {tuple(t.shape)}")
+            if lead is None:
+                lead = tuple(t.shape[:-1])
+            elif tuple(t.shape[:-1]) != lead:
+                raise ValueError(f"{name} has leading shape {tuple(t.shape[:-1])}, the others {lead}")
+            keep.append(t)
+            setattr(cr, name, C.cast(t.data_ptr(), C.POINTER(C.c_float)))
+        if rows is None:
+            if lead is None:
+                lead = (self.num_envs,)
+            elif lead != (self.num_envs,):
+                raise ValueError(f"without rows the bound buffers are read: actions must be [{self.num_envs}, 6], got leading shape {lead}")
+        return cr, lead, keep
+
+    def critic_values(self, critic, actions, rows=None, reward=None, terminated=None, log_prob=None, gamma=None, ent_coef=0.0):
+        """Both Q-networks of `critic` (a DeviceCritic of this environment) on (rows, actions), one launch of the HIP critic kernel:
+        returns a dict of fresh device tensors ``q`` [2, ...], ``q_min`` [...] = min(q0, q1) and, when `reward` is given,
+        ``target`` [...] = reward + gamma (1 - terminated) (q_min - ent_coef log_prob) -- SAC's y, with `actions` = a' drawn on the
+        next observations (``policy_actions(..., rows=)``) and `log_prob` theirs; without `log_prob` the entropy term is absent.
+
+        `rows`: None = the live observation buffers ([N] rows); or the dict ``rollout_policy`` returns (its ``observation``,
+        ``achieved_goal``, ``desired_goal`` records), or a tuple of tensors in that order, with leading shape [K, N] or [M] -- all
+        K N rows go into one launch.  `actions`, `reward`, `terminated`, `log_prob` have the same leading shape.  Nothing is
+        synchronised: the tensors are valid in stream order."""
+        if getattr(critic, "env", None) is not self or not getattr(critic, "_c", None):
+            raise ValueError("critic must be a live DeviceCritic loaded for this environment (DeviceCritic.load(paths, env))")
+        cr, lead, keep = self._rows(rows, action=actions)
+        count = int(np.prod(lead))
+        terms = _abi.CriticTerms()
+        if reward is not None:
+            if gamma is None:
+                raise ValueError("the target needs gamma (tests/golden/critics/sac_hyperparameters.json has the checkpoints': 0.95)")
+            terms.gamma, terms.ent_coef = float(gamma), float(ent_coef)
+            for name, t, dt, ct in (("reward", reward, torch.float32, C.c_float), ("terminated", terminated, torch.uint8, C.c_uint8),
+                                    ("log_prob", log_prob, torch.float32, C.c_float)):
+                if t is None:
+                    continue
+                t = torch.as_tensor(t, device=self.device)
+                t = t.view(torch.uint8) if t.dtype == torch.bool else t
+                if t.dtype != dt or not t.is_contiguous():
+                    t = t.to(dt).contiguous()
+                if tuple(t.shape) != lead:
+                    raise ValueError(f"{name} must have shape {lead}, got {tuple(t.shape)}")
+                keep.append(t)
+                setattr(terms, name, C.cast(t.data_ptr(), C.POINTER(ct)))
+        elif terminated is not None or log_prob is not None:
+            raise ValueError("terminated / log_prob are terms of the target, which needs reward")
+        res = {"q": torch.empty((2,) + lead, dtype=torch.float32, device=self.device),
+               "q_min": torch.empty(lead, dtype=torch.float32, device=self.device)}
+        if reward is not None:
+            res["target"] = torch.empty(lead, dtype=torch.float32, device=self.device)
+        out = _abi.CriticOut(*[C.cast(res[k].data_ptr(), C.POINTER(C.c_float)) if k in res else None for k in ("q", "q_min", "target")])
+        _native.check(self.lib.urgym_critic_evaluate(self._h, critic._c, C.byref(cr), count, C.byref(terms), C.byref(out), self._stream()), self._h)
+        return res
+
+    def policy_actions(self, actor, out=None, sample=None, rows=None):
         """model.predict(obs, deterministic=True) (model_test.py:41) for all envs, by the HIP actor kernel, from the live
         observation buffers: float32 [N, 6] on the device.
 
         With `sample` (see ``rollout_policy``) the actions are drawn -- model.predict(obs, deterministic=False) -- and the return
-        value is ``(actions, log_prob)``, log_prob float32 [N] (None for mode "mean" on an actor without log_std head)."""
+        value is ``(actions, log_prob)``, log_prob float32 [N] (None for mode "mean" on an actor without log_std head).
+
+        With `rows` (as in ``critic_values``: leading shape [K, N] or [M]) the policy is evaluated on those rows instead of the live
+        buffers (urgym_actor_sample_rows): SAC's a' ~ pi(.|s') on next-observation rows.  The noise of row i is that of env i, so on
+        copies of the live buffers the result is bitwise the same.  Returns [..., 6] (and [...]); without `sample`, the mean action."""
         a = self._actor_ptr(actor)
+        if rows is not None:
+            cr, lead, keep = self._rows(rows)
+            if out is None:
+                out = torch.empty(lead + (6,), dtype=torch.float32, device=self.device)
+            elif tuple(out.shape) != lead + (6,) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
+                raise ValueError(f"out must be a contiguous float32 {lead + (6,)} tensor on {self.device}")
+            how = self._sampling(sample if sample is not None else dict(mode="mean"))
+            log_prob = None
+            if sample is not None and (how.mode != _abi.SAMPLE_MEAN or actor.has_log_std):
+                log_prob = torch.empty(lead, dtype=torch.float32, device=self.device)
+            _native.check(self.lib.urgym_actor_sample_rows(self._h, a, C.byref(how), C.byref(cr), int(np.prod(lead)), C.c_void_p(out.data_ptr()),
+                                                           C.c_void_p(log_prob.data_ptr()) if log_prob is not None else None, self._stream()), self._h)
+            return out if sample is None else (out, log_prob)
         if out is None:
             out = torch.empty((self.num_envs, 6), dtype=torch.float32, device=self.device)
         elif out.shape != (self.num_envs, 6) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
