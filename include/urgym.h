@@ -382,6 +382,73 @@ int urgym_critic_evaluate(void* handle, void* critic, const urgym_critic_rows* r
  * buffers as above.  The refusals of urgym_actor_sample, and those of urgym_critic_evaluate that concern rows and count. */
 int urgym_actor_sample_rows(void* handle, void* actor, const urgym_sampling* how, const urgym_critic_rows* rows, int count, float* actions_dev, float* log_prob_dev, void* stream);
 
+/* ---- the replay buffer of the SAC agent (train.py:40-48: SAC(..., buffer_size=int(1e7), batch_size=256); SB3's DictReplayBuffer):
+ * the transitions of a policy rollout written into a ring on the device as they happen, and minibatches drawn from it in the row
+ * layout urgym_critic_rows takes.  Added WITHIN ABI version 4 like the sampling and critic calls: no struct above changed,
+ * URGYM_ABI_VERSION did not move, the new symbols (urgym_rollout_collect, urgym_replay_sample) are found by lookup.  The library
+ * allocates nothing and keeps no state: the ring, its cursor and its fill level are the caller's. */
+
+/* The ring: DEVICE pointers owned by the caller, C = capacity_steps slots of N transitions each, every array [C][N][...].  All are
+ * required except truncated and is_success (NULL = not kept).
+ * `terminated` is the environment's own flag, NOT terminated | truncated: an episode that ends at the time limit is bootstrapped
+ * through, target = r + gamma Q(s', a'), as stable-baselines3 does with handle_timeout_termination=True (SB3
+ * common/buffers.py, ReplayBuffer.add / _get_samples: dones * (1 - timeouts)). */
+typedef struct urgym_replay_ring {
+  int32_t capacity_steps;     /* C > 0 */
+  int32_t reserved0;          /* must be 0 */
+  float* observation;         /* [C][N][obs_dim]  what the actor saw before the step */
+  float* achieved_goal;       /* [C][N][goal_dim] */
+  float* desired_goal;        /* [C][N][goal_dim] */
+  float* action;              /* [C][N][6]        what it answered */
+  float* reward;              /* [C][N]           what the step returned */
+  float* next_observation;    /* [C][N][obs_dim]  final_* where auto_reset && (terminated | truncated), else the live rows after the step */
+  float* next_achieved_goal;  /* [C][N][goal_dim] */
+  float* next_desired_goal;   /* [C][N][goal_dim] */
+  uint8_t* terminated;        /* [C][N] */
+  uint8_t* truncated;         /* [C][N] or NULL */
+  uint8_t* is_success;        /* [C][N] or NULL */
+} urgym_replay_ring;
+
+/* A minibatch: DEVICE pointers owned by the caller, `count` rows each, each may be NULL (= not gathered), at least one is not.
+ * observation / achieved_goal / desired_goal / action are a urgym_critic_rows as they stand, the three next_* fields a second one. */
+typedef struct urgym_replay_batch {
+  float* observation;         /* [count][obs_dim]  */
+  float* achieved_goal;       /* [count][goal_dim] */
+  float* desired_goal;        /* [count][goal_dim] */
+  float* action;              /* [count][6] */
+  float* reward;              /* [count] */
+  float* next_observation;    /* [count][obs_dim]  */
+  float* next_achieved_goal;  /* [count][goal_dim] */
+  float* next_desired_goal;   /* [count][goal_dim] */
+  uint8_t* terminated;        /* [count] */
+  uint8_t* truncated;         /* [count]; only from a ring that keeps it */
+  uint8_t* is_success;        /* [count]; only from a ring that keeps it */
+  int64_t* index;             /* [count] the flat ring entry slot * N + env the row came from */
+} urgym_replay_batch;
+
+/* urgym_rollout_sampled (all three modes, the same refusals) that writes the transition of step k, k = 0 .. num_steps - 1, into slot
+ * (first_slot + k) % C of `ring`; num_steps may exceed C (later steps overwrite earlier ones).  Afterwards the bound buffers hold
+ * what num_steps calls of urgym_step would have left.  Of step k and env n the slot holds: observation / achieved_goal / desired_goal
+ * = what the actor saw before step k, action = what it answered, reward / terminated / truncated / is_success = what step k returned,
+ * next_* = the three final_* rows where auto_reset && (terminated | truncated), else the three live rows after the step.  A slot is
+ * complete when the call returns, and no launch writes into a slot other than those of the call's own steps.  3 num_steps + 1
+ * launches on `stream` (store pass, actor, step; a last store pass); the actor writes its actions straight into the slot and the
+ * step reads them there.  No host synchronisation, no allocation, everything validated before the first launch.
+ * Refused (URGYM_ERR_ARG) beyond urgym_rollout_sampled's: ring == NULL, a NULL required pointer, capacity_steps <= 0, first_slot
+ * outside [0, C), reserved0 != 0, num_steps <= 0. */
+int urgym_rollout_collect(void* handle, void* actor, const urgym_sampling* how, int num_steps, const urgym_replay_ring* ring, int first_slot, void* stream);
+
+/* Draws `count` rows with replacement, uniformly over the size = filled_steps * N entries of the slots (oldest_slot + j) % C,
+ * j < filled_steps, in ONE gather launch on `stream`.  Entry e_i of row i is a pure function of (seed, draw, i, size):
+ *   Philox4x32-10 (urgym_philox.h), key = (seed & 0xFFFFFFFF, seed >> 32) as for the policy noise,
+ *   counter = (i, draw & 0xFFFFFFFF, draw >> 32, 0x52504C00) -- the last word meets neither the policy noise's 0x504F4C00 | block
+ *   nor the reset sampler's blocks 0..4;  w = (w0 << 32) | w1;  e = (w * size) >> 64, the high half of the 128-bit product;
+ *   slot = (oldest_slot + e / N) % C,  env = e % N,  index = slot * N + env.
+ * It depends on nothing else: not on count, not on the launch geometry.  ur_gym_amd.evaluation.replay_indices restates it.
+ * Refused (URGYM_ERR_ARG): the ring refusals of urgym_rollout_collect, filled_steps outside [1, C], oldest_slot outside [0, C),
+ * count <= 0, batch == NULL or without any output, truncated / is_success asked from a ring that does not keep it. */
+int urgym_replay_sample(void* handle, const urgym_replay_ring* ring, int oldest_slot, int filled_steps, uint64_t seed, uint64_t draw, int count, const urgym_replay_batch* batch, void* stream);
+
 /* Replaces Reach*.set_goal / set_goal_and_obstacle (reach.py:202-204, 328-335, 702-713): the caller has
  * overwritten goal / obst_start / obst_end (and possibly q) for the masked envs; this recomputes obstacle pose,
  * velocity, collision, link_dist and the observation for them, leaving step_count untouched. */

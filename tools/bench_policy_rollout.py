@@ -20,6 +20,17 @@ in torch float32 on the device (cat, 2 x (3 F.linear, relu), minimum, target ari
 actor median + the spread of the actor's windows (the matrix instructions per wave of the two kernels at width 256).
 
     python tools/bench_policy_rollout.py --critic --out profiles/policy_rollout/dyn65536_critic.json
+
+--replay measures the device replay ring (DeviceReplay, capacity --capacity slots), GAUSSIAN policy, auto-reset.  Bar 1: per-step
+wall time of ``collect`` (urgym_rollout_collect) against the Python loop that produces the same ring without it -- per step
+policy_actions(sample=) into the slot, env.step, and the torch assembly of the transition (three copies of s, three
+where(done, final, live) for s', reward and flags) into the preallocated ring tensors -- and against ``rollout_policy`` with all
+records; alternating windows, median of --repeats.  The copy bandwidth of the same run (a device-to-device copy_ of one ring
+array) prices the bytes collect writes beyond the recorded rollout.  Bar 2: the gather launch (all eleven fields and the index,
+preallocated outputs) at batch 256 and 65536 against torch.randint + one index_select per field on the same ring, device events
+around --launches back-to-back repetitions.
+
+    python tools/bench_policy_rollout.py --replay --out profiles/policy_rollout/dyn65536_replay.json
 """
 import argparse
 import json
@@ -131,6 +142,151 @@ def critic_mode(args):
             f.write(line + "\n")
 
 
+def replay_mode(args):
+    import torch
+
+    from ur_gym_amd import _abi, make_vec
+    from ur_gym_amd.evaluation import DeviceActor, DeviceReplay
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_policy_rollout.py measures on a GPU; none is visible")
+    dev, n, K, cap, kind = "cuda:0", args.num_envs, args.steps, args.capacity, ACTOR_NPZ[args.env]
+    w = dict(np.load(os.path.join(ROOT, "tests", "golden", "actors", f"actor_{kind}.npz")))
+    w.update(np.load(os.path.join(ROOT, "tests", "golden", "actors", f"log_std_{kind}.npz")))
+    env = make_vec(args.env, num_envs=n, device=dev, seed=0, auto_reset=True)
+    env.reset(seed=0)
+    actor = DeviceActor(w, env)
+    replay, loop_ring = DeviceReplay(env, cap), DeviceReplay(env, cap)  # the second one is filled by the Python loop
+    sync = lambda: torch.cuda.synchronize(env.device)  # noqa: E731
+    draws = [0]  # every window continues the draw sequence
+    rows = ("observation", "achieved_goal", "desired_goal")
+
+    def how(steps):
+        d = dict(mode="gaussian", seed=1, first_draw=draws[0])
+        draws[0] += steps
+        return d
+
+    def collect(steps):
+        replay.collect(actor, steps, sample=how(steps))
+
+    def python_loop(steps):
+        r, b = loop_ring.ring, env.buf
+        first = how(steps)["first_draw"]
+        for k in range(steps):
+            slot = (loop_ring.cursor + k) % cap
+            for key in rows:
+                r[key][slot].copy_(b[key])
+            env.policy_actions(actor, out=r["action"][slot], sample=dict(mode="gaussian", seed=1, first_draw=first + k))
+            obs, rew, term, trunc, info = env.step(r["action"][slot])
+            done = (term | trunc)[:, None]
+            for key in rows:
+                torch.where(done, info["final_observation"][key], obs[key], out=r["next_" + key][slot])
+            r["reward"][slot].copy_(rew)
+            r["terminated"][slot].copy_(term)
+            r["truncated"][slot].copy_(trunc)
+            r["is_success"][slot].copy_(info["is_success"])
+        loop_ring.cursor = (loop_ring.cursor + steps) % cap
+        loop_ring.filled = min(cap, loop_ring.filled + steps)
+
+    def recorded(steps):
+        return env.rollout_policy(actor, steps, record="all", sample=how(steps))
+
+    def plain(steps):
+        env.rollout_policy(actor, steps, record=(), sample=how(steps))
+
+    variants = [("collect", collect), ("python_loop_into_ring", python_loop), ("rollout_all_records", recorded), ("rollout_no_records", plain)]
+    for _, fn in variants:
+        fn(10)
+    plain(args.warmup)
+    sync()
+    times = {name: [] for name, _ in variants}
+    for _ in range(args.repeats):
+        for name, fn in variants:
+            sync()
+            t0 = time.perf_counter()
+            fn(K)
+            sync()
+            times[name].append((time.perf_counter() - t0) / K * 1e6)
+    per_step = {k: float(np.median(v)) for k, v in times.items()}
+    spread = {k: float(max(v) - min(v)) for k, v in times.items()}
+
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def window(fn, reps):
+        sync()
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        sync()
+        return e0.elapsed_time(e1) * 1e3 / reps
+
+    # the copy bandwidth of this run: one ring array onto another, read + write counted
+    src, dst = replay.ring["observation"], loop_ring.ring["observation"]
+    copy_bytes = 2 * src.numel() * 4
+    window(lambda: dst.copy_(src), 3)
+    copy_us = float(np.median([window(lambda: dst.copy_(src), 5) for _ in range(args.repeats)]))
+    copy_bw = copy_bytes / copy_us * 1e6
+    row_bytes = (2 * (env.obs_dim + 2 * env.goal_dim) + 6 + 1) * 4 + 3  # a transition in the ring
+    # rollout_policy(record="all", sample=): s, action, reward, four flags, the four sample records (final_observation only where done)
+    record_bytes = (env.obs_dim + 2 * env.goal_dim + 6 + 1 + 19) * 4 + 4
+    extra = per_step["collect"] - per_step["rollout_all_records"]
+    byte_cost = (row_bytes - record_bytes) * n / copy_bw * 1e6
+
+    # bar 2: the gather against torch on the same (full) ring
+    while replay.filled < cap:
+        collect(min(K, cap - replay.filled))
+    sync()
+    size, gather = replay.filled * n, {}
+    flat = {name: t.reshape((cap * n,) + tuple(t.shape[2:])) for name, t in replay.ring.items()}
+    for B in (256, 65536):
+        out = {name: torch.empty((B,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev) for name, t in flat.items()}
+        ours = dict(out, index=torch.empty((B,), dtype=torch.int64, device=dev))
+        tick = [0]
+
+        def device_gather():
+            tick[0] += 1
+            replay.sample_into(ours, 3, tick[0])
+
+        def torch_gather():
+            idx = torch.randint(0, size, (B,), device=dev)
+            for name, t in flat.items():
+                torch.index_select(t, 0, idx, out=out[name])
+
+        kinds = {"device": device_gather, "torch": torch_gather}
+        for fn in kinds.values():
+            for _ in range(10):
+                fn()
+        wins = {k: [] for k in kinds}
+        for _ in range(args.repeats):
+            for name, fn in kinds.items():
+                wins[name].append(window(fn, args.launches))
+        med = {k: float(np.median(v)) for k, v in wins.items()}
+        moved = B * (2 * row_bytes + 8)
+        gather[str(B)] = {"us_windows": {k: [round(x, 3) for x in v] for k, v in wins.items()}, "us_median": med,
+                          "not_slower_than_torch": med["device"] <= med["torch"], "speedup_over_torch": med["torch"] / med["device"],
+                          "bytes_read_and_written": moved, "device_bytes_per_s": moved / med["device"] * 1e6}
+    result = {"tool": "bench_policy_rollout --replay", "env": args.env, "num_envs": n, "steps": K, "capacity_steps": cap, "repeats": args.repeats,
+              "device": torch.cuda.get_device_name(0), "us_per_step_median": per_step, "us_per_step_spread": spread,
+              "us_per_step_all": {k: [round(x, 2) for x in v] for k, v in times.items()},
+              "collect_not_slower_than_python_loop": per_step["collect"] <= per_step["python_loop_into_ring"],
+              "speedup_over_python_loop": per_step["python_loop_into_ring"] / per_step["collect"],
+              "ring_bytes_per_env_step": row_bytes, "record_bytes_per_env_step": record_bytes,
+              "collect_minus_rollout_all_records_us": extra, "copy_bytes_per_s": copy_bw, "extra_bytes_at_copy_bandwidth_us": byte_cost,
+              "extra_within_spread_plus_byte_cost": extra <= spread["collect"] + spread["rollout_all_records"] + byte_cost,
+              "collect_minus_rollout_no_records_us": per_step["collect"] - per_step["rollout_no_records"],
+              "store_bytes_per_s": (row_bytes - 24) * n / max(per_step["collect"] - per_step["rollout_no_records"], 1e-9) * 1e6,
+              "gather": gather, "parent_rollout_all_records_us": 466.0}
+    actor.close()
+    env.close()
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--env", default="UR5DynReach-v1", choices=sorted(ACTOR_NPZ))
@@ -148,10 +304,14 @@ def main():
     ap.add_argument("--critic", action="store_true", help="measure the twin Q critic launch against the actor launch and torch (see above)")
     ap.add_argument("--windows", type=int, default=10, help="--critic: alternating windows per kind")
     ap.add_argument("--launches", type=int, default=200, help="--critic: back-to-back launches per window")
+    ap.add_argument("--replay", action="store_true", help="measure the device replay ring: collect against a Python loop, the gather against torch (see above)")
+    ap.add_argument("--capacity", type=int, default=256, help="--replay: slots of the ring")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.critic:
         return critic_mode(args)
+    if args.replay:
+        return replay_mode(args)
 
     import torch
     import torch.nn.functional as F

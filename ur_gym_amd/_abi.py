@@ -189,6 +189,34 @@ class CriticOut(C.Structure):
     _fields_ = [(name, C.POINTER(C.c_float)) for name in ("q", "q_min", "target")]
 
 
+REPLAY_TAG = 0x52504C00  # word 3 of the Philox counter of urgym_replay_sample's index draw
+
+# urgym_replay_ring after capacity_steps / reserved0: name -> (ctype of element, shape given (C, N, obs_dim, goal_dim), required)
+REPLAY_RING_FIELDS = [
+    ("observation", C.c_float, lambda Cs, N, od, gd: (Cs, N, od), True),
+    ("achieved_goal", C.c_float, lambda Cs, N, od, gd: (Cs, N, gd), True),
+    ("desired_goal", C.c_float, lambda Cs, N, od, gd: (Cs, N, gd), True),
+    ("action", C.c_float, lambda Cs, N, od, gd: (Cs, N, 6), True),
+    ("reward", C.c_float, lambda Cs, N, od, gd: (Cs, N), True),
+    ("next_observation", C.c_float, lambda Cs, N, od, gd: (Cs, N, od), True),
+    ("next_achieved_goal", C.c_float, lambda Cs, N, od, gd: (Cs, N, gd), True),
+    ("next_desired_goal", C.c_float, lambda Cs, N, od, gd: (Cs, N, gd), True),
+    ("terminated", C.c_uint8, lambda Cs, N, od, gd: (Cs, N), True),
+    ("truncated", C.c_uint8, lambda Cs, N, od, gd: (Cs, N), False),
+    ("is_success", C.c_uint8, lambda Cs, N, od, gd: (Cs, N), False),
+]
+
+
+class ReplayRing(C.Structure):
+    """urgym_replay_ring: the caller's ring of C slots x N transitions (DEVICE pointers)."""
+    _fields_ = [("capacity_steps", C.c_int32), ("reserved0", C.c_int32)] + [(name, C.POINTER(ct)) for name, ct, _, _ in REPLAY_RING_FIELDS]
+
+
+class ReplayBatch(C.Structure):
+    """urgym_replay_batch: what urgym_replay_sample writes, `count` rows each; every pointer may be NULL, not all."""
+    _fields_ = [(name, C.POINTER(ct)) for name, ct, _, _ in REPLAY_RING_FIELDS] + [("index", C.POINTER(C.c_int64))]
+
+
 # Every symbol include/urgym.h declares (tests check that the built library exports each of them).
 EXPORTED_SYMBOLS = [
     "urgym_abi_version",
@@ -211,6 +239,8 @@ EXPORTED_SYMBOLS = [
     "urgym_critic_destroy",
     "urgym_critic_evaluate",
     "urgym_actor_sample_rows",
+    "urgym_rollout_collect",
+    "urgym_replay_sample",
     "urgym_refresh",
     "urgym_invalidate_records",
     "urgym_derive_obstacle_motion",

@@ -72,6 +72,9 @@ def lib():
                                         C.POINTER(_abi.CriticOut), C.c_void_p]
     L.urgym_actor_sample_rows.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.Sampling), C.POINTER(_abi.CriticRows), C.c_int, C.c_void_p,
                                           C.c_void_p, C.c_void_p]
+    L.urgym_rollout_collect.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.Sampling), C.c_int, C.POINTER(_abi.ReplayRing), C.c_int, C.c_void_p]
+    L.urgym_replay_sample.argtypes = [C.c_void_p, C.POINTER(_abi.ReplayRing), C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_int,
+                                      C.POINTER(_abi.ReplayBatch), C.c_void_p]
     L.urgym_refresh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.urgym_invalidate_records.argtypes = [C.c_void_p]
     L.urgym_derive_obstacle_motion.argtypes = [C.c_void_p, C.c_void_p]

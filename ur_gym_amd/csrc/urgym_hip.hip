@@ -41,6 +41,7 @@
 #include "urgym_launch_plan.h"
 #include "urgym_actor.h"
 #include "urgym_critic.h"
+#include "urgym_replay.h"
 #include "urgym_tables_host.h"
 
 using namespace urgym;
@@ -2005,6 +2006,44 @@ int resolve_rows(Handle* h, const urgym_critic_rows* rows, int count, const char
   return URGYM_OK;
 }
 
+// ---- the replay ring (urgym_rollout_collect, urgym_replay_sample): the checks that concern the ring itself
+int check_ring(Handle* h, const urgym_replay_ring* r, const char* who) {
+  char msg[200];
+  const char* what = nullptr;
+  if (!r) what = "null ring";
+  else if (r->capacity_steps <= 0) what = "ring->capacity_steps must be positive";
+  else if (r->reserved0 != 0) what = "urgym_replay_ring.reserved0 must be 0";
+  else if (!r->observation || !r->achieved_goal || !r->desired_goal || !r->action || !r->reward || !r->next_observation ||
+           !r->next_achieved_goal || !r->next_desired_goal || !r->terminated)
+    what = "a required ring pointer is null (all but truncated and is_success)";
+  if (!what) return URGYM_OK;
+  snprintf(msg, sizeof(msg), "%s: %s", who, what);
+  return fail(h, URGYM_ERR_ARG, msg);
+}
+
+// the store pass before step k of a collection that started at first_slot: the s of slot k (k < num_steps), the outcome of slot k - 1
+ReplayStore replay_store(const Handle* h, const urgym_replay_ring& r, int first_slot, int k, int num_steps) {
+  const urgym_buffers& b = h->buf;
+  const size_t n = (size_t)h->cfg.num_envs, od = (size_t)h->obs_dim, gd = (size_t)h->goal_dim, C = (size_t)r.capacity_steps;
+  ReplayStore p;
+  memset(&p, 0, sizeof(p));
+  p.N = h->cfg.num_envs, p.obs_dim = h->obs_dim, p.goal_dim = h->goal_dim, p.auto_reset = h->cfg.auto_reset;
+  p.observation = b.observation, p.achieved_goal = b.achieved_goal, p.desired_goal = b.desired_goal, p.reward = b.reward;
+  p.final_observation = b.final_observation, p.final_achieved_goal = b.final_achieved_goal, p.final_desired_goal = b.final_desired_goal;
+  p.terminated = b.terminated, p.truncated = b.truncated, p.is_success = b.is_success;
+  if (k < num_steps) {
+    const size_t at = (((size_t)first_slot + (size_t)k) % C) * n;
+    p.obs = r.observation + at * od, p.ach = r.achieved_goal + at * gd, p.des = r.desired_goal + at * gd;
+  }
+  if (k > 0) {
+    const size_t at = (((size_t)first_slot + (size_t)k - 1) % C) * n;
+    p.reward_out = r.reward + at, p.terminated_out = r.terminated + at;
+    p.truncated_out = r.truncated ? r.truncated + at : nullptr, p.is_success_out = r.is_success ? r.is_success + at : nullptr;
+    p.next_obs = r.next_observation + at * od, p.next_ach = r.next_achieved_goal + at * gd, p.next_des = r.next_desired_goal + at * gd;
+  }
+  return p;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2287,6 +2326,61 @@ int urgym_actor_sample_rows(void* handle, void* actor, const urgym_sampling* how
   else
     actor_launch_sampled(a, env, actions_dev, nullptr, ActorSample{how->mode, how->seed, how->first_draw, log_prob_dev, nullptr, nullptr, nullptr},
                          (hipStream_t)stream);
+  HIP_TRY(h, hipGetLastError());
+  return URGYM_OK;
+}
+
+int urgym_rollout_collect(void* handle, void* actor, const urgym_sampling* how, int num_steps, const urgym_replay_ring* ring, int first_slot, void* stream) {
+  const char* who = "urgym_rollout_collect";
+  Handle* h = (Handle*)handle;
+  Actor* a = nullptr;
+  if (int rc = enter_actor(h, actor, who, &a)) return rc;
+  if (int rc = check_sampling(h, a, how, false, who)) return rc;
+  if (int rc = check_ring(h, ring, who)) return rc;
+  if (first_slot < 0 || first_slot >= ring->capacity_steps) return fail(h, URGYM_ERR_ARG, "urgym_rollout_collect: first_slot outside [0, capacity_steps)");
+  if (num_steps <= 0) return fail(h, URGYM_ERR_ARG, "urgym_rollout_collect: num_steps must be positive");
+  hipStream_t s = (hipStream_t)stream;
+  const ActorEnv env = actor_env(h);
+  const size_t row = (size_t)h->cfg.num_envs * 6;
+  // The launches of urgym_rollout_sampled without records, a store pass before each actor and one after the last step; all on `s`,
+  // so stream order puts step k - 1 before the pass that files its outcome and that pass before the actor of step k.
+  for (int k = 0; k <= num_steps; k++) {
+    replay_store_launch(replay_store(h, *ring, first_slot, k, num_steps), s);
+    if (k == num_steps) break;
+    float* actions = ring->action + (size_t)((first_slot + (int64_t)k) % ring->capacity_steps) * row;  // the actor writes the slot, the step reads it
+    if (how->mode == URGYM_SAMPLE_MEAN)
+      actor_launch(a, env, actions, nullptr, s);
+    else
+      actor_launch_sampled(a, env, actions, nullptr, ActorSample{how->mode, how->seed, how->first_draw + (uint64_t)k, nullptr, nullptr, nullptr, nullptr}, s);
+    if (int rc = do_step(h, actions, s)) return rc;
+  }
+  HIP_TRY(h, hipGetLastError());
+  return URGYM_OK;
+}
+
+int urgym_replay_sample(void* handle, const urgym_replay_ring* ring, int oldest_slot, int filled_steps, uint64_t seed, uint64_t draw, int count, const urgym_replay_batch* batch, void* stream) {
+  const char* who = "urgym_replay_sample";
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (int rc = check_ring(h, ring, who)) return rc;
+  if (filled_steps < 1 || filled_steps > ring->capacity_steps) return fail(h, URGYM_ERR_ARG, "urgym_replay_sample: filled_steps outside [1, capacity_steps]");
+  if (oldest_slot < 0 || oldest_slot >= ring->capacity_steps) return fail(h, URGYM_ERR_ARG, "urgym_replay_sample: oldest_slot outside [0, capacity_steps)");
+  if (count <= 0) return fail(h, URGYM_ERR_ARG, "urgym_replay_sample: count must be positive");
+  if (!batch) return fail(h, URGYM_ERR_ARG, "urgym_replay_sample: null batch");
+  const urgym_replay_batch& b = *batch;
+  if (!b.observation && !b.achieved_goal && !b.desired_goal && !b.action && !b.reward && !b.next_observation && !b.next_achieved_goal &&
+      !b.next_desired_goal && !b.terminated && !b.truncated && !b.is_success && !b.index)
+    return fail(h, URGYM_ERR_ARG, "urgym_replay_sample: no output requested (every batch pointer is null)");
+  if ((b.truncated && !ring->truncated) || (b.is_success && !ring->is_success))
+    return fail(h, URGYM_ERR_ARG, "urgym_replay_sample: truncated / is_success asked from a ring that does not keep it");
+  HIP_TRY(h, hipSetDevice(h->device));
+  ReplayGather g;
+  g.N = h->cfg.num_envs, g.obs_dim = h->obs_dim, g.goal_dim = h->goal_dim, g.capacity = ring->capacity_steps;
+  g.oldest_slot = oldest_slot, g.count = count;
+  g.size = (uint64_t)filled_steps * (uint64_t)h->cfg.num_envs;
+  g.seed = seed, g.draw = draw;
+  g.ring = *ring, g.batch = b;
+  replay_gather_launch(g, (hipStream_t)stream);
   HIP_TRY(h, hipGetLastError());
   return URGYM_OK;
 }

@@ -1,0 +1,118 @@
+// urgym_replay.hip — the device replay ring of the SAC agent (include/urgym.h, "the replay buffer"): the store pass that
+// urgym_rollout_collect runs between the steps, and the gather of urgym_replay_sample.  Both kernels only move bytes; float32 rows
+// travel as 32-bit words, so a copy is bitwise whatever the value.  Built with the flags of urgym_actor.hip.
+//
+// Layout.  A transition row is 72 to 188 bytes of float32 per side (s and s'), far from any power of two, and a slot starts wherever
+// slot * N * dim falls: no 16-byte alignment can be assumed.  Both kernels therefore lay the lanes along the FLOATS of consecutive
+// rows, one dword per lane: a wave touches 256 contiguous bytes per access whatever dim is.  The flags are one byte per env.
+#include "urgym_replay.h"
+
+#include "urgym_philox.h"
+
+namespace urgym {
+
+namespace {
+
+constexpr int STORE_THREADS = 256;
+constexpr int STORE_ENVS = 64;  // envs per workgroup: 1024 workgroups at N = 65536, several per CU
+
+// Rows [env0, env0 + cnt) of one of the three observation arrays: the live value goes to `pre` (the s of slot k) and, unless the env
+// finished under auto-reset (then the final_* row), to `next` (the s' of slot k - 1).  The live row is read once for both.
+__device__ __forceinline__ void store_rows(const float* __restrict__ live, const float* __restrict__ fin, float* __restrict__ pre,
+                                           float* __restrict__ next, const uint8_t* done, int dim, int env0, int cnt, int tid) {
+  const size_t first = (size_t)env0 * dim;
+  const int total = cnt * dim;
+  // env of element i = i / dim, by a float product: i < 64 * 35 and (i + 0.5) / dim is at least 0.5 / 35 away from an integer, far
+  // more than the rounding of the two float operations, so the truncation is the exact quotient
+  const float inv = 1.0f / (float)dim;
+  for (int i = tid; i < total; i += STORE_THREADS) {
+    const float v = live[first + i];
+    if (pre) pre[first + i] = v;
+    if (next) next[first + i] = done[(int)(((float)i + 0.5f) * inv)] ? fin[first + i] : v;
+  }
+}
+
+__global__ void __launch_bounds__(STORE_THREADS) replay_store_kernel(const ReplayStore P) {
+  __shared__ uint8_t done[STORE_ENVS];
+  const int tid = threadIdx.x, env0 = blockIdx.x * STORE_ENVS, cnt = min(STORE_ENVS, P.N - env0);
+  const bool outcome = P.next_obs != nullptr;
+  if (outcome) {
+    if (tid < cnt) {
+      const int e = env0 + tid;
+      const uint8_t term = P.terminated[e], trunc = P.truncated[e];
+      done[tid] = P.auto_reset && (term | trunc);
+      P.reward_out[e] = P.reward[e];
+      P.terminated_out[e] = term;
+      if (P.truncated_out) P.truncated_out[e] = trunc;
+      if (P.is_success_out) P.is_success_out[e] = P.is_success[e];
+    }
+    __syncthreads();
+  }
+  store_rows(P.observation, P.final_observation, P.obs, P.next_obs, done, P.obs_dim, env0, cnt, tid);
+  store_rows(P.achieved_goal, P.final_achieved_goal, P.ach, P.next_ach, done, P.goal_dim, env0, cnt, tid);
+  store_rows(P.desired_goal, P.final_desired_goal, P.des, P.next_des, done, P.goal_dim, env0, cnt, tid);
+}
+
+// The gather: one wave takes 64 samples.  Lane l computes the ring entry of sample l (once per sample; it also moves that sample's
+// scalars: index, reward, flags -- written coalesced), then the wave works through its samples four at a time, a group of 16 lanes
+// per sample with the lanes along the row's floats.  16 lanes are one 64-byte run: a row is a few such runs (35 floats = 3 trips,
+// a goal or an action 1), and the four groups of a wave write four neighbouring output rows, i.e. one contiguous stretch.
+constexpr int GATHER_THREADS = 64;
+constexpr int GATHER_GROUP = 16;
+constexpr int GATHER_ROUNDS = GATHER_THREADS / (GATHER_THREADS / GATHER_GROUP);  // 16 rounds of 4 samples
+
+__device__ __forceinline__ void gather_row(float* __restrict__ dst, const float* __restrict__ src, int dim, size_t sample, size_t entry, int l) {
+  if (!dst) return;
+  for (int i = l; i < dim; i += GATHER_GROUP) dst[sample * dim + i] = src[entry * dim + i];
+}
+
+__global__ void __launch_bounds__(GATHER_THREADS) replay_gather_kernel(const ReplayGather P) {
+  const int lane = threadIdx.x;
+  const int base = blockIdx.x * GATHER_THREADS;  // count is an int: so is every sample number
+  const urgym_replay_ring& R = P.ring;
+  const urgym_replay_batch& B = P.batch;
+  int64_t entry = 0;
+  if (base + lane < P.count) {
+    const int i = base + lane;
+    uint32_t w[4];
+    philox4x32_10((uint32_t)P.seed, (uint32_t)(P.seed >> 32), (uint32_t)i, (uint32_t)P.draw, (uint32_t)(P.draw >> 32), 0x52504C00u, w);
+    const uint64_t e = __umul64hi(((uint64_t)w[0] << 32) | w[1], P.size);  // uniform on [0, size)
+    const uint64_t step = e / (uint64_t)P.N, env = e - step * (uint64_t)P.N;
+    uint64_t slot = (uint64_t)P.oldest_slot + step;  // < 2 C
+    if (slot >= (uint64_t)P.capacity) slot -= (uint64_t)P.capacity;
+    entry = (int64_t)(slot * (uint64_t)P.N + env);
+    if (B.index) B.index[i] = entry;
+    if (B.reward) B.reward[i] = R.reward[entry];
+    if (B.terminated) B.terminated[i] = R.terminated[entry];
+    if (B.truncated) B.truncated[i] = R.truncated[entry];
+    if (B.is_success) B.is_success[i] = R.is_success[entry];
+  }
+  const int group = lane / GATHER_GROUP, l = lane % GATHER_GROUP;
+  const int lo = (int)(uint32_t)entry, hi = (int)(uint32_t)((uint64_t)entry >> 32);
+  for (int r = 0; r < GATHER_ROUNDS; r++) {
+    const int from = r * (GATHER_THREADS / GATHER_GROUP) + group;  // the lane that holds this group's sample
+    const uint32_t e_lo = (uint32_t)__shfl(lo, from), e_hi = (uint32_t)__shfl(hi, from);  // every lane takes part
+    const int sample = base + from;
+    if (sample >= P.count) continue;
+    const size_t e = (size_t)(((uint64_t)e_hi << 32) | e_lo), s = (size_t)sample;
+    gather_row(B.observation, R.observation, P.obs_dim, s, e, l);
+    gather_row(B.achieved_goal, R.achieved_goal, P.goal_dim, s, e, l);
+    gather_row(B.desired_goal, R.desired_goal, P.goal_dim, s, e, l);
+    gather_row(B.action, R.action, 6, s, e, l);
+    gather_row(B.next_observation, R.next_observation, P.obs_dim, s, e, l);
+    gather_row(B.next_achieved_goal, R.next_achieved_goal, P.goal_dim, s, e, l);
+    gather_row(B.next_desired_goal, R.next_desired_goal, P.goal_dim, s, e, l);
+  }
+}
+
+}  // namespace
+
+void replay_store_launch(const ReplayStore& p, hipStream_t s) {
+  hipLaunchKernelGGL(replay_store_kernel, dim3((p.N + STORE_ENVS - 1) / STORE_ENVS), dim3(STORE_THREADS), 0, s, p);
+}
+
+void replay_gather_launch(const ReplayGather& p, hipStream_t s) {
+  hipLaunchKernelGGL(replay_gather_kernel, dim3((p.count + GATHER_THREADS - 1) / GATHER_THREADS), dim3(GATHER_THREADS), 0, s, p);
+}
+
+}  // namespace urgym

@@ -78,6 +78,22 @@ def policy_noise(seed, draw, env_ids, mode, dtype=np.float32):
     return out
 
 
+def replay_indices(seed, draw, count, size):
+    """The ring entries urgym_replay_sample draws, restated from include/urgym.h ("the replay buffer"): e_i for i < count, a pure
+    function of (seed, draw, i, size) -- e = (w * size) >> 64 with w = (w0 << 32) | w1 of Philox4x32-10 at the counter
+    (i, draw lo, draw hi, REPLAY_TAG).  The 128-bit product is taken in Python integers.  Returns int64 [count], each in [0, size);
+    the caller maps e to slot (oldest_slot + e // N) % C and env e % N."""
+    from . import _abi
+
+    seed, draw, count, size = int(seed), int(draw), int(count), int(size)
+    if count < 0 or not 0 < size < 1 << 63:
+        raise ValueError(f"count must be >= 0 and size in [1, 2^63), got {count}, {size}")
+    key = (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
+    w = philox4x32_10(key, (np.arange(count, dtype=np.uint64), np.uint64(draw & 0xFFFFFFFF), np.uint64((draw >> 32) & 0xFFFFFFFF),
+                            np.uint64(_abi.REPLAY_TAG)))
+    return np.array([((int(hi) << 32 | int(lo)) * size) >> 64 for hi, lo in zip(w[0], w[1])], dtype=np.int64).reshape(count)
+
+
 LOG_STD_MIN, LOG_STD_MAX = -20.0, 2.0  # SB3 sac/policies.py
 LOG_STD_ARRAYS = ("log_std_weight", "log_std_bias")
 
@@ -356,6 +372,140 @@ class DeviceCritic:
             self.close()
         except Exception:
             pass
+
+
+class DeviceReplay:
+    """SAC's replay buffer (train.py:40-48, SB3 DictReplayBuffer) as a ring of `capacity_steps` slots x N transitions in device
+    memory, filled by ``collect`` (urgym_rollout_collect: the transitions are written as the rollout runs, terminal observations
+    and goals included) and read by ``sample`` (urgym_replay_sample: one gather launch).  The ring tensors are ``self.ring[name]``
+    ([C, N, ...]; _abi.REPLAY_RING_FIELDS).  ``cursor`` (the slot the next step goes to) and ``filled`` (valid slots) live on the
+    host: pushes are host-driven, so both are known without a synchronisation.  ``terminated`` is the environment's own flag, not
+    terminated | truncated: a time-limit end is bootstrapped through, as SB3 does (handle_timeout_termination)."""
+
+    def __init__(self, env, capacity_steps):
+        import ctypes as C
+
+        import torch
+
+        from . import _abi
+        from .vector_env import _TORCH_DTYPE
+
+        self.capacity = self.check_args(capacity_steps)
+        self.env, self.cursor, self.filled = env, 0, 0
+        self.ring = {}
+        self._ring = _abi.ReplayRing(self.capacity, 0)
+        for name, ct, shape, _ in _abi.REPLAY_RING_FIELDS:
+            t = torch.zeros(shape(self.capacity, env.num_envs, env.obs_dim, env.goal_dim), dtype=_TORCH_DTYPE[ct], device=env.device)
+            self.ring[name] = t
+            setattr(self._ring, name, C.cast(t.data_ptr(), C.POINTER(ct)))
+
+    @staticmethod
+    def check_args(capacity_steps, num_steps=None, first_slot=None, filled_steps=None, oldest_slot=None, batch_size=None):
+        """Raises ValueError for what urgym_rollout_collect / urgym_replay_sample refuse about the ring's sizes (include/urgym.h):
+        capacity_steps <= 0, num_steps <= 0, first_slot or oldest_slot outside [0, C), filled_steps outside [1, C], batch_size <= 0.
+        Arguments left None are not checked.  Returns the capacity.  Needs no GPU."""
+        def integer(name, v):
+            if isinstance(v, bool) or int(v) != v:
+                raise ValueError(f"{name} must be an integer, got {v!r}")
+            return int(v)
+
+        cap = integer("capacity_steps", capacity_steps)
+        if not 0 < cap < 1 << 31:
+            raise ValueError(f"capacity_steps must be positive (and fit int32), got {cap}")
+        if num_steps is not None and not 0 < integer("num_steps", num_steps) < 1 << 31:
+            raise ValueError(f"num_steps must be positive, got {num_steps}")
+        for name, v in (("first_slot", first_slot), ("oldest_slot", oldest_slot)):
+            if v is not None and not 0 <= integer(name, v) < cap:
+                raise ValueError(f"{name} must be in [0, {cap}), got {v}")
+        if filled_steps is not None and not 1 <= integer("filled_steps", filled_steps) <= cap:
+            raise ValueError(f"filled_steps must be in [1, {cap}] (nothing has been collected yet?), got {filled_steps}")
+        if batch_size is not None and not 0 < integer("batch_size", batch_size) < 1 << 31:
+            raise ValueError(f"batch_size must be positive, got {batch_size}")
+        return cap
+
+    @property
+    def oldest_slot(self):
+        return (self.cursor - self.filled) % self.capacity
+
+    def __len__(self):
+        return self.filled * self.env.num_envs
+
+    def collect(self, actor, num_steps, sample=None):
+        """`num_steps` x (store pass, actor, step) from slot ``cursor`` on, without returning to Python; `sample` as in
+        ``env.rollout_policy`` (None = the deterministic policy).  Advances ``cursor`` and ``filled``."""
+        K = int(num_steps)
+        self.env.collect(actor, K, self, sample=sample, first_slot=self.cursor)
+        self.cursor = (self.cursor + K) % self.capacity
+        self.filled = min(self.capacity, self.filled + K)
+
+    def sample_into(self, out, seed, draw):
+        """The gather itself: `out` maps ring field names (and ``index``, int64) to contiguous device tensors with one leading
+        length, the batch size; only those are written.  The rows are ``replay_indices(seed, draw, count, len(self))``."""
+        import ctypes as C
+
+        import torch
+
+        from . import _abi, _native
+        from .vector_env import _TORCH_DTYPE
+
+        env = self.env
+        kinds = {name: (ct, shape(1, 1, env.obs_dim, env.goal_dim)[2:]) for name, ct, shape, _ in _abi.REPLAY_RING_FIELDS}
+        kinds["index"] = (C.c_int64, ())
+        batch, count = _abi.ReplayBatch(), None
+        for name, t in out.items():
+            if name not in kinds:
+                raise ValueError(f"unknown batch field {name!r}; available: {sorted(kinds)}")
+            ct, tail = kinds[name]
+            want = torch.int64 if ct is C.c_int64 else _TORCH_DTYPE[ct]
+            t = t.view(torch.uint8) if t.dtype == torch.bool else t
+            if t.dtype != want or not t.is_contiguous() or t.device != env.device or t.dim() != 1 + len(tail) or tuple(t.shape[1:]) != tail:
+                raise ValueError(f"{name} must be a contiguous {want} [count{''.join(f', {d}' for d in tail)}] tensor on {env.device}")
+            if count is None:
+                count = int(t.shape[0])
+            elif int(t.shape[0]) != count:
+                raise ValueError(f"{name} has {int(t.shape[0])} rows, the others {count}")
+            setattr(batch, name, C.cast(t.data_ptr(), C.POINTER(ct)))
+        if count is None:
+            raise ValueError("no output requested")
+        self.check_args(self.capacity, filled_steps=self.filled, oldest_slot=self.oldest_slot, batch_size=count)
+        _native.check(env.lib.urgym_replay_sample(env._h, C.byref(self._ring), self.oldest_slot, self.filled, int(seed), int(draw), count,
+                                                  C.byref(batch), env._stream()), env._h)
+
+    def sample(self, batch_size, seed, draw):
+        """A minibatch of `batch_size` transitions drawn uniformly with replacement, one launch: a dict of fresh device tensors --
+        ``observations`` and ``next_observations`` (each {observation, achieved_goal, desired_goal}: the `rows` of
+        ``env.policy_actions`` / ``env.critic_values``), ``actions``, ``rewards``, ``terminated``, ``truncated``, ``is_success``
+        (bool views) and ``index`` (int64: the flat ring entry slot * N + env of each row).  Nothing is synchronised."""
+        import ctypes as C
+
+        import torch
+
+        from . import _abi
+        from .vector_env import _TORCH_DTYPE
+
+        self.check_args(self.capacity, batch_size=batch_size)
+        env, B = self.env, int(batch_size)
+        flat = {name: torch.empty((B,) + tuple(shape(1, 1, env.obs_dim, env.goal_dim)[2:]), dtype=_TORCH_DTYPE[ct], device=env.device)
+                for name, ct, shape, _ in _abi.REPLAY_RING_FIELDS}
+        flat["index"] = torch.empty((B,), dtype=torch.int64, device=env.device)
+        self.sample_into(flat, seed, draw)
+        rows = ("observation", "achieved_goal", "desired_goal")
+        return {"observations": {k: flat[k] for k in rows}, "next_observations": {k: flat["next_" + k] for k in rows},
+                "actions": flat["action"], "rewards": flat["reward"], "terminated": flat["terminated"].view(torch.bool),
+                "truncated": flat["truncated"].view(torch.bool), "is_success": flat["is_success"].view(torch.bool), "index": flat["index"]}
+
+    def sample_targets(self, actor, critic, batch_size, seed, draw, gamma, ent_coef, sample=None):
+        """``sample``, then a' ~ pi(.|s') on the gathered next observations (``env.policy_actions(rows=)``), then SAC's target
+        y = r + gamma (1 - terminated) (min_i Q_i(s', a') - ent_coef log pi(a'|s')) (``env.critic_values``): three launches.
+        `sample` = how a' is drawn (default: gaussian with this call's seed and draw).  Returns the batch with ``next_actions``,
+        ``next_log_prob`` and ``target`` added."""
+        batch = self.sample(batch_size, seed, draw)
+        how = dict(mode="gaussian", seed=seed, first_draw=draw) if sample is None else sample
+        nxt = batch["next_observations"]
+        batch["next_actions"], batch["next_log_prob"] = self.env.policy_actions(actor, sample=how, rows=nxt)
+        batch["target"] = self.env.critic_values(critic, batch["next_actions"], rows=nxt, reward=batch["rewards"], terminated=batch["terminated"],
+                                                 log_prob=batch["next_log_prob"], gamma=gamma, ent_coef=ent_coef)["target"]
+        return batch
 
 
 def run_closed_loop_device(env, actor, max_steps=100):

@@ -373,6 +373,19 @@ class UR5ReachVectorEnv:
         _native.check(self.lib.urgym_rollout_sampled(self._h, a, C.byref(how), K, C.byref(traj), C.byref(extra), self._stream()), self._h)
         return out
 
+    def collect(self, actor, num_steps, replay, sample=None, first_slot=None):
+        """``rollout_policy`` that files every transition in `replay` (an ``evaluation.DeviceReplay`` of this environment) as it
+        happens (urgym_rollout_collect): step k goes to slot (first_slot + k) % capacity, complete with the terminal observation
+        and goals of envs that were auto-reset.  `sample` as in ``rollout_policy`` (None = the deterministic policy); `first_slot`
+        defaults to the ring's cursor, which this method does NOT move -- ``replay.collect`` does.  Nothing is synchronised."""
+        a = self._actor_ptr(actor)
+        if getattr(replay, "env", None) is not self or not hasattr(replay, "_ring"):
+            raise ValueError("replay must be a DeviceReplay allocated for this environment (DeviceReplay(env, capacity_steps))")
+        first = replay.cursor if first_slot is None else first_slot
+        replay.check_args(replay.capacity, num_steps=num_steps, first_slot=first)
+        how = self._sampling(sample if sample is not None else dict(mode="mean"))
+        _native.check(self.lib.urgym_rollout_collect(self._h, a, C.byref(how), int(num_steps), C.byref(replay._ring), int(first), self._stream()), self._h)
+
     def close(self):
         if getattr(self, "_h", None):
             torch.cuda.synchronize(self.device)
