@@ -31,6 +31,16 @@ preallocated outputs) at batch 256 and 65536 against torch.randint + one index_s
 around --launches back-to-back repetitions.
 
     python tools/bench_policy_rollout.py --replay --out profiles/policy_rollout/dyn65536_replay.json
+
+With --refresh: what it costs to hand new weights to a device actor / critic, at hidden width 256 and 512.
+`actor_load`, `critic_load_tau1` and `critic_load_polyak` (tau = 0.005) are load_parameters from device tensors, one launch each;
+`*_host_route` is the only route there was before: every tensor .cpu().numpy(), destroy and create the object (the actor's head by
+set_log_std); `*_copy` is the floor, one torch device-to-device copy_ of as many bytes as the packed buffer.  Wall time around
+--launches calls that end in a device synchronise (the host route: --host-steps calls), alternating windows, median of --windows.
+Bar 1: each load is not slower than its host route.  Bar 2 (no threshold): the ratio to the copy and the bytes written per second.
+Then one SACLearner.update at batch 256 and the share of it that the two loads take.
+
+    python tools/bench_policy_rollout.py --refresh --out profiles/policy_rollout/dyn65536_refresh.json
 """
 import argparse
 import json
@@ -287,6 +297,112 @@ def replay_mode(args):
             f.write(line + "\n")
 
 
+def refresh_mode(args):
+    import torch
+
+    from ur_gym_amd import make_vec
+    from ur_gym_amd.evaluation import ACTOR_ARRAYS, CRITIC_ARRAYS, LOG_STD_ARRAYS, DeviceActor, DeviceCritic, DeviceReplay
+    from ur_gym_amd.training import SACLearner
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_policy_rollout.py measures on a GPU; none is visible")
+    dev, n = "cuda:0", args.num_envs
+    env = make_vec(args.env, num_envs=n, device=dev, seed=0, auto_reset=True)
+    env.reset(seed=0)
+    sync = lambda: torch.cuda.synchronize(env.device)  # noqa: E731
+    n_in = env.obs_dim + 2 * env.goal_dim
+    rng = np.random.default_rng(0)
+
+    def window(fn, calls):
+        sync()
+        t0 = time.perf_counter()
+        for _ in range(calls):
+            fn()
+        sync()
+        return (time.perf_counter() - t0) * 1e6 / calls
+
+    rows = {}
+    for H in (256, 512):
+        shapes_a = dict(zip(ACTOR_ARRAYS + LOG_STD_ARRAYS, ((H, n_in), (H,), (H, H), (H,), (6, H), (6,), (6, H), (6,))))
+        shapes_c = dict(zip(CRITIC_ARRAYS, ((H, n_in + 6), (H,), (H, H), (H,), (1, H), (1,))))
+        wa = {k: (rng.standard_normal(sh) * 0.1).astype(np.float32) for k, sh in shapes_a.items()}
+        wc = [{k: (rng.standard_normal(sh) * 0.1).astype(np.float32) for k, sh in shapes_c.items()} for _ in range(2)]
+        ta = {k: torch.from_numpy(v).to(dev) for k, v in wa.items()}
+        tc = [{k: torch.from_numpy(v).to(dev) for k, v in w.items()} for w in wc]
+        obj = {"actor": DeviceActor(wa, env), "critic": DeviceCritic(wc, env)}
+        bytes_a, bytes_c = obj["actor"].packed().nbytes, obj["critic"].packed().nbytes
+        flat = {"a": (torch.empty(bytes_a // 4, device=dev), torch.empty(bytes_a // 4, device=dev)),
+                "c": (torch.empty(bytes_c // 4, device=dev), torch.empty(bytes_c // 4, device=dev))}
+
+        def actor_host_route():
+            w = {k: v.cpu().numpy() for k, v in ta.items()}
+            obj["actor"].close()
+            obj["actor"] = DeviceActor(w, env)
+
+        def critic_host_route():
+            w = [{k: v.cpu().numpy() for k, v in net.items()} for net in tc]
+            obj["critic"].close()
+            obj["critic"] = DeviceCritic(w, env)
+
+        kinds = {"actor_load": (lambda: obj["actor"].load_parameters(ta), args.launches),
+                 "critic_load_tau1": (lambda: obj["critic"].load_parameters(tc, tau=1.0), args.launches),
+                 "critic_load_polyak": (lambda: obj["critic"].load_parameters(tc, tau=0.005), args.launches),
+                 "actor_copy": (lambda: flat["a"][0].copy_(flat["a"][1]), args.launches),
+                 "critic_copy": (lambda: flat["c"][0].copy_(flat["c"][1]), args.launches),
+                 "actor_host_route": (actor_host_route, args.host_steps),
+                 "critic_host_route": (critic_host_route, args.host_steps)}
+        for fn, _ in kinds.values():
+            for _ in range(3):
+                fn()
+        wins = {k: [] for k in kinds}
+        for _ in range(args.windows):
+            for name, (fn, calls) in kinds.items():
+                wins[name].append(window(fn, calls))
+        med = {k: float(np.median(v)) for k, v in wins.items()}
+        row = {"packed_bytes": {"actor": bytes_a, "critic": bytes_c}, "us_median": med,
+               "us_windows": {k: [round(x, 3) for x in v] for k, v in wins.items()}}
+        for load, base, copy, nbytes in (("actor_load", "actor_host_route", "actor_copy", bytes_a),
+                                         ("critic_load_tau1", "critic_host_route", "critic_copy", bytes_c),
+                                         ("critic_load_polyak", "critic_host_route", "critic_copy", bytes_c)):
+            row[load] = {"not_slower_than_host_route": med[load] <= med[base], "host_route_over_load": med[base] / med[load],
+                         "load_over_copy": med[load] / med[copy], "packed_gbytes_per_s": nbytes / med[load] / 1e3}
+        rows[str(H)] = row
+        obj["actor"].close()
+        obj["critic"].close()
+
+    # one SACLearner.update at batch 256 and the share of the two loads
+    learner = SACLearner(env, seed=0, batch_size=256, hidden_width=256)
+    replay = DeviceReplay(env, 4)
+    learner.collect(replay, 4)
+    for i in range(5):
+        learner.update(replay, 1, i)
+    loads = lambda: (learner.device_actor.load_parameters(learner.actor.tensors()),  # noqa: E731
+                     learner.target.load_parameters(learner.critic.tensors(), tau=learner.hp["tau"]))
+    draw = [100]
+
+    def one_update():
+        draw[0] += 1
+        learner.update(replay, 1, draw[0])
+
+    up, ld = [], []
+    for _ in range(args.windows):
+        up.append(window(one_update, 20))
+        ld.append(window(loads, 20))
+    up_med, ld_med = float(np.median(up)), float(np.median(ld))
+    learner.close()
+    result = {"tool": "bench_policy_rollout --refresh", "env": args.env, "num_envs": n, "windows": args.windows, "launches_per_window": args.launches,
+              "host_route_calls_per_window": args.host_steps, "device": torch.cuda.get_device_name(0), "hidden_width": rows,
+              "learner_update": {"batch_size": 256, "hidden_width": 256, "us_median": up_med, "us_windows": [round(x, 2) for x in up],
+                                 "two_loads_us_median": ld_med, "two_loads_share": ld_med / up_med}}
+    env.close()
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--env", default="UR5DynReach-v1", choices=sorted(ACTOR_NPZ))
@@ -306,12 +422,15 @@ def main():
     ap.add_argument("--launches", type=int, default=200, help="--critic: back-to-back launches per window")
     ap.add_argument("--replay", action="store_true", help="measure the device replay ring: collect against a Python loop, the gather against torch (see above)")
     ap.add_argument("--capacity", type=int, default=256, help="--replay: slots of the ring")
+    ap.add_argument("--refresh", action="store_true", help="measure reloading actor / critic weights from device tensors against the host route and a copy (see above)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.critic:
         return critic_mode(args)
     if args.replay:
         return replay_mode(args)
+    if args.refresh:
+        return refresh_mode(args)
 
     import torch
     import torch.nn.functional as F

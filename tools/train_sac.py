@@ -1,0 +1,69 @@
+"""Runs ur_gym_amd.training.SACLearner: the loop of the reference's train.py:40-60 (SAC.learn) on the device pieces, printing the
+mean episode return and the success rate of the deterministic policy (evaluation.run_closed_loop_device on a second, auto-reset-off
+environment, as model_test.py evaluates) every so many updates.
+
+    python tools/train_sac.py --env UR5OriReach-v1 --num-envs 1024 --steps 2000 --updates-per-step 4 --eval-every 200
+
+One loop trip = one env step of all N envs into the ring, then `--updates-per-step` gradient steps.  Prints one JSON line per
+evaluation.  No checkpoint is written.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--env", default="UR5OriReach-v1")
+    ap.add_argument("--num-envs", type=int, default=1024)
+    ap.add_argument("--steps", type=int, default=2000, help="env steps (of all N envs) to collect")
+    ap.add_argument("--updates-per-step", type=int, default=4)
+    ap.add_argument("--capacity", type=int, default=1024, help="slots of the replay ring (N transitions each)")
+    ap.add_argument("--eval-every", type=int, default=200, help="updates between evaluations")
+    ap.add_argument("--eval-envs", type=int, default=1024)
+    ap.add_argument("--hidden-width", type=int, default=256)
+    ap.add_argument("--batch-size", type=int, default=256)
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args()
+
+    import torch
+
+    from ur_gym_amd import make_vec
+    from ur_gym_amd.evaluation import DeviceActor, DeviceReplay, run_closed_loop_device
+    from ur_gym_amd.training import SACLearner, host_arrays
+
+    if not torch.cuda.is_available():
+        raise SystemExit("train_sac.py trains on a GPU; none is visible")
+    env = make_vec(args.env, num_envs=args.num_envs, seed=args.seed, auto_reset=True)
+    env.reset(seed=args.seed)
+    test_env = make_vec(args.env, num_envs=args.eval_envs, seed=args.seed + 1, auto_reset=False)
+    learner = SACLearner(env, seed=args.seed, hidden_width=args.hidden_width, batch_size=args.batch_size)
+    eval_actor = DeviceActor(host_arrays(learner.actor.tensors()), test_env)  # actors belong to the environment they were made for
+    replay = DeviceReplay(env, args.capacity)
+    updates, t0 = 0, time.perf_counter()
+    for step in range(args.steps):
+        learner.collect(replay, 1)
+        if learner.env_steps * env.num_envs < learner.hp["learning_starts"]:
+            continue
+        for _ in range(args.updates_per_step):
+            learner.update(replay, args.seed, updates)
+            updates += 1
+            if updates % args.eval_every == 0:
+                eval_actor.load_parameters(learner.actor.tensors())
+                test_env.reset(seed=args.seed + 1)
+                res = run_closed_loop_device(test_env, eval_actor)
+                print(json.dumps({"updates": updates, "env_steps": learner.env_steps * env.num_envs, "seconds": round(time.perf_counter() - t0, 1),
+                                  "mean_episode_return": res["mean_episode_reward"], "success_rate_percent": res["success_rate_percent"]}), flush=True)
+    eval_actor.close()
+    learner.close()
+    test_env.close()
+    env.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -217,6 +217,24 @@ class ReplayBatch(C.Structure):
     _fields_ = [(name, C.POINTER(ct)) for name, ct, _, _ in REPLAY_RING_FIELDS] + [("index", C.POINTER(C.c_int64))]
 
 
+ACTOR_DEV_ARRAYS = ("w0", "b0", "w1", "b1", "w_mu", "b_mu", "w_log_std", "b_log_std")  # the last two may be NULL, together
+
+
+class ActorParamsDev(C.Structure):
+    """urgym_actor_params_dev: the shape for checking + eight DEVICE pointers to float32 tensors in torch's [out][in] layout."""
+    _fields_ = [("in_features", C.c_int32), ("hidden_width", C.c_int32), ("reserved0", C.c_int32)] + [(name, C.POINTER(C.c_float)) for name in ACTOR_DEV_ARRAYS]
+
+
+class QNetworkDev(C.Structure):
+    """urgym_q_network_dev: six DEVICE pointers to float32 tensors in torch's [out][in] layout."""
+    _fields_ = [(name, C.POINTER(C.c_float)) for name in ("w0", "b0", "w1", "b1", "w_q", "b_q")]
+
+
+class CriticParamsDev(C.Structure):
+    """urgym_critic_params_dev: the shape for checking + the two Q-networks."""
+    _fields_ = [("in_features", C.c_int32), ("hidden_width", C.c_int32), ("reserved0", C.c_int32), ("qf", QNetworkDev * 2)]
+
+
 # Every symbol include/urgym.h declares (tests check that the built library exports each of them).
 EXPORTED_SYMBOLS = [
     "urgym_abi_version",
@@ -241,6 +259,10 @@ EXPORTED_SYMBOLS = [
     "urgym_actor_sample_rows",
     "urgym_rollout_collect",
     "urgym_replay_sample",
+    "urgym_actor_load",
+    "urgym_critic_load",
+    "urgym_actor_read_packed",
+    "urgym_critic_read_packed",
     "urgym_refresh",
     "urgym_invalidate_records",
     "urgym_derive_obstacle_motion",

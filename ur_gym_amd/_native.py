@@ -75,6 +75,10 @@ def lib():
     L.urgym_rollout_collect.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.Sampling), C.c_int, C.POINTER(_abi.ReplayRing), C.c_int, C.c_void_p]
     L.urgym_replay_sample.argtypes = [C.c_void_p, C.POINTER(_abi.ReplayRing), C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_int,
                                       C.POINTER(_abi.ReplayBatch), C.c_void_p]
+    L.urgym_actor_load.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.ActorParamsDev), C.c_void_p]
+    L.urgym_critic_load.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.CriticParamsDev), C.c_float, C.c_void_p]
+    L.urgym_actor_read_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.urgym_critic_read_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.urgym_refresh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.urgym_invalidate_records.argtypes = [C.c_void_p]
     L.urgym_derive_obstacle_motion.argtypes = [C.c_void_p, C.c_void_p]

@@ -52,6 +52,15 @@ struct ActorSample {
 int actor_set_log_std(Actor* a, const float* w, const float* b, char* err, size_t err_len);
 bool actor_has_log_std(const Actor* a);
 
+// The packed buffer p1 | p2 | small (device, `floats` long) and the shape it was packed for: what a reload (urgym_weights.h) writes.
+struct ActorPacked {
+  float* weights;
+  size_t floats;
+  int in_features, hidden;
+};
+ActorPacked actor_packed(Actor* a);
+void actor_mark_log_std(Actor* a);  // a reload has filled the log_std head
+
 // actor_launch with sampled actions (actions != nullptr).  UNIFORM runs no forward pass; MEAN and GAUSSIAN need the log_std head.
 void actor_launch_sampled(Actor* a, const ActorEnv& env, float* actions, const ActorPass* pass, const ActorSample& how, hipStream_t s);
 

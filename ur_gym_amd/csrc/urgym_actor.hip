@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "urgym_actor.h"
+#include "urgym_pack_host.h"
 #include "urgym_philox.h"
 
 namespace urgym {
@@ -425,32 +426,7 @@ int actor_create(const urgym_actor_desc* d, int in_features, int num_envs, Actor
   Actor* a = new (std::nothrow) Actor();
   if (!a) return refuse("out of memory");
   a->in_features = in, a->hidden = H, a->ht = HT, a->num_envs = num_envs;
-  const size_t n1 = (size_t)HT * L1_TILE4 * 4, n2 = (size_t)HT * HT * 4 * 64 * 4, ns = (size_t)HP * 14 + 16;
-  a->p2_off = n1, a->small_off = n1 + n2;
-  std::vector<float> w(n1 + n2 + ns, 0.0f);
-  // layer 1: float c of lane l's read sq of tile t = W0[32 t + (l & 31)][2 (4 sq + c) + (l >> 5)]
-  for (int t = 0; t < HT; t++)
-    for (int sq = 0; sq < L1_STEPS4; sq++)
-      for (int l = 0; l < 64; l++)
-        for (int c = 0; c < 4; c++) {
-          const int n = 32 * t + (l & 31), k = 2 * (4 * sq + c) + (l >> 5);
-          if (n < H && k < in) w[((((size_t)t * L1_STEPS4 + sq) * 64 + l) * 4) + c] = d->w0[(size_t)n * in + k];
-        }
-  // layer 2: read sq = 4 u + g of tile t pairs, in float c, the neurons 32 u + 8 g + 4 (l >> 5) + c of layer 1
-  for (int t = 0; t < HT; t++)
-    for (int sq = 0; sq < HT * 4; sq++)
-      for (int l = 0; l < 64; l++)
-        for (int c = 0; c < 4; c++) {
-          const int n = 32 * t + (l & 31), k = 32 * (sq / 4) + 8 * (sq % 4) + 4 * (l >> 5) + c;
-          if (n < H && k < H) w[n1 + ((((size_t)t * HT * 4 + sq) * 64 + l) * 4) + c] = d->w1[(size_t)n * H + k];
-        }
-  float* sm = w.data() + n1 + n2;
-  for (int n = 0; n < H; n++) {
-    sm[n] = d->b0[n];
-    sm[HP + n] = d->b1[n];
-    for (int o = 0; o < 6; o++) sm[2 * HP + ((size_t)(n / 4) * 6 + o) * 4 + n % 4] = d->w_mu[(size_t)o * H + n];
-  }
-  for (int o = 0; o < 6; o++) sm[(size_t)HP * 8 + o] = d->b_mu[o];
+  const std::vector<float> w = pack_actor_host(d, &a->p2_off, &a->small_off);  // the packing loops: urgym_pack_host.h
 
   hipError_t e = hipMalloc((void**)&a->d_weights, w.size() * sizeof(float));
   if (e == hipSuccess) e = hipMemcpy(a->d_weights, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice);
@@ -467,10 +443,7 @@ int actor_create(const urgym_actor_desc* d, int in_features, int num_envs, Actor
 
 int actor_set_log_std(Actor* a, const float* w_ls, const float* b_ls, char* err, size_t err_len) {
   const int H = a->hidden, HP = a->ht * 32;
-  std::vector<float> head((size_t)HP * 6 + 8, 0.0f);  // w_log_std in w_mu's packing [neuron / 4][6][neuron % 4], then the bias
-  for (int n = 0; n < H; n++)
-    for (int o = 0; o < 6; o++) head[((size_t)(n / 4) * 6 + o) * 4 + n % 4] = w_ls[(size_t)o * H + n];
-  for (int o = 0; o < 6; o++) head[(size_t)HP * 6 + o] = b_ls[o];
+  const std::vector<float> head = pack_log_std_host(H, HP, w_ls, b_ls);
   const hipError_t e = hipMemcpy(a->d_weights + a->small_off + (size_t)HP * 8 + 8, head.data(), head.size() * sizeof(float), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
     snprintf(err, err_len, "urgym_actor_set_log_std: %s", hipGetErrorString(e));
@@ -489,6 +462,8 @@ void actor_destroy(Actor* a) {
 
 int actor_in_features(const Actor* a) { return a->in_features; }
 bool actor_has_log_std(const Actor* a) { return a->has_log_std; }
+void actor_mark_log_std(Actor* a) { a->has_log_std = true; }
+ActorPacked actor_packed(Actor* a) { return ActorPacked{a->d_weights, a->small_off + (size_t)a->ht * 32 * 14 + 16, a->in_features, a->hidden}; }
 float* actor_action_scratch(Actor* a) { return a->d_actions; }
 uint8_t* actor_done_scratch(Actor* a) { return a->d_done; }
 

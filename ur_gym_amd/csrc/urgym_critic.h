@@ -26,6 +26,14 @@ int critic_create(const urgym_critic_desc* desc, int in_features, Critic** out, 
 void critic_destroy(Critic* c);
 int critic_in_features(const Critic* c);
 
+// The packed buffer of both networks (device, `floats` long) and the shape it was packed for: what a reload (urgym_weights.h) writes.
+struct CriticPacked {
+  float* weights;
+  size_t floats;
+  int in_features, hidden;
+};
+CriticPacked critic_packed(Critic* c);
+
 // ONE launch on `s`; the caller has validated `call`
 void critic_launch(Critic* c, const CriticCall& call, hipStream_t s);
 

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "urgym_critic.h"
+#include "urgym_pack_host.h"
 
 namespace urgym {
 
@@ -253,33 +254,7 @@ int critic_create(const urgym_critic_desc* d, int in_features, Critic** out, cha
   Critic* c = new (std::nothrow) Critic();
   if (!c) return refuse("out of memory");
   c->in_features = in, c->hidden = H, c->ht = HT;
-  const size_t n1 = (size_t)HT * C1_TILE4 * 4, n2 = (size_t)HT * HT * 4 * 64 * 4, ns = (size_t)HP * 3 + 4;
-  c->small_off = 2 * (n1 + n2);
-  std::vector<float> w(2 * (n1 + n2 + ns), 0.0f);
-  for (int net = 0; net < 2; net++) {
-    const urgym_q_network& q = d->qf[net];
-    float* w1 = w.data() + (size_t)net * (n1 + n2);
-    float* w2 = w1 + n1;
-    // layer 1: float c of lane l's read sq of tile t = W0[32 t + (l & 31)][2 (4 sq + c) + (l >> 5)]
-    for (int t = 0; t < HT; t++)
-      for (int sq = 0; sq < C1_STEPS4; sq++)
-        for (int l = 0; l < 64; l++)
-          for (int cc = 0; cc < 4; cc++) {
-            const int n = 32 * t + (l & 31), k = 2 * (4 * sq + cc) + (l >> 5);
-            if (n < H && k < in) w1[((((size_t)t * C1_STEPS4 + sq) * 64 + l) * 4) + cc] = q.w0[(size_t)n * in + k];
-          }
-    // layer 2: read sq = 4 u + g of tile t pairs, in float c, the neurons 32 u + 8 g + 4 (l >> 5) + c of layer 1
-    for (int t = 0; t < HT; t++)
-      for (int sq = 0; sq < HT * 4; sq++)
-        for (int l = 0; l < 64; l++)
-          for (int cc = 0; cc < 4; cc++) {
-            const int n = 32 * t + (l & 31), k = 32 * (sq / 4) + 8 * (sq % 4) + 4 * (l >> 5) + cc;
-            if (n < H && k < H) w2[((((size_t)t * HT * 4 + sq) * 64 + l) * 4) + cc] = q.w1[(size_t)n * H + k];
-          }
-    float* sm = w.data() + c->small_off + (size_t)net * ns;
-    for (int n = 0; n < H; n++) sm[n] = q.b0[n], sm[HP + n] = q.b1[n], sm[2 * HP + n] = q.w_q[n];
-    sm[3 * HP] = q.b_q[0];
-  }
+  const std::vector<float> w = pack_critic_host(d, &c->small_off);  // the packing loops: urgym_pack_host.h
   hipError_t e = hipMalloc((void**)&c->d_weights, w.size() * sizeof(float));
   if (e == hipSuccess) e = hipMemcpy(c->d_weights, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
@@ -298,6 +273,7 @@ void critic_destroy(Critic* c) {
 }
 
 int critic_in_features(const Critic* c) { return c->in_features; }
+CriticPacked critic_packed(Critic* c) { return CriticPacked{c->d_weights, c->small_off + 2 * ((size_t)c->ht * 32 * 3 + 4), c->in_features, c->hidden}; }
 
 void critic_launch(Critic* c, const CriticCall& call, hipStream_t s) {
   CriticKParams P;

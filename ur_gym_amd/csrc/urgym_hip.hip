@@ -41,6 +41,8 @@
 #include "urgym_launch_plan.h"
 #include "urgym_actor.h"
 #include "urgym_critic.h"
+#include "urgym_pack_map.h"
+#include "urgym_weights.h"
 #include "urgym_replay.h"
 #include "urgym_tables_host.h"
 
@@ -2157,6 +2159,103 @@ int urgym_derive_obstacle_motion(void* handle, void* stream) {
   hipLaunchKernelGGL(derive_displacement_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->buf.obst_vel, N, h->cfg.dt);
   HIP_TRY(h, hipGetLastError());
   return URGYM_OK;
+}
+
+// ---- weights from the device (urgym_weights.hip): everything is checked here, before the launch
+int urgym_actor_load(void* handle, void* actor, const urgym_actor_params_dev* p, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  Actor* a = find_actor(h, actor);
+  if (!a) return fail(h, URGYM_ERR_ARG, "urgym_actor_load: not an actor of this handle (actors belong to the handle they were created with)");
+  if (!p) return fail(h, URGYM_ERR_ARG, "urgym_actor_load: null params");
+  if (p->reserved0 != 0) return fail(h, URGYM_ERR_ARG, "urgym_actor_load: reserved0 must be 0");
+  const ActorPacked buf = actor_packed(a);
+  if (p->in_features != buf.in_features || p->hidden_width != buf.hidden) {
+    char msg[200];
+    snprintf(msg, sizeof(msg), "urgym_actor_load: params are %d -> %d, the actor is %d -> %d", p->in_features, p->hidden_width, buf.in_features, buf.hidden);
+    return fail(h, URGYM_ERR_ARG, msg);
+  }
+  if (!p->w0 || !p->b0 || !p->w1 || !p->b1 || !p->w_mu || !p->b_mu) return fail(h, URGYM_ERR_ARG, "urgym_actor_load: a weight or bias pointer is null");
+  if (!p->w_log_std != !p->b_log_std) return fail(h, URGYM_ERR_ARG, "urgym_actor_load: the log_std head needs both w_log_std and b_log_std, or neither");
+  HIP_TRY(h, hipSetDevice(h->device));
+  const float* src[PACK_ACTOR_TENSORS] = {p->w0, p->b0, p->w1, p->b1, p->w_mu, p->b_mu, p->w_log_std, p->b_log_std};
+  actor_pack_launch(buf, src, (hipStream_t)stream);
+  HIP_TRY(h, hipGetLastError());
+  if (p->w_log_std) actor_mark_log_std(a);  // the checks of later calls are made in program order, which is stream order for this stream
+  return URGYM_OK;
+}
+
+namespace {
+Critic* find_critic(Handle* h, void* critic) {
+  for (Critic* c : h->critics)
+    if (c == critic) return c;
+  return nullptr;
+}
+}  // namespace
+
+int urgym_critic_load(void* handle, void* critic, const urgym_critic_params_dev* p, float tau, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  Critic* c = find_critic(h, critic);
+  if (!c) return fail(h, URGYM_ERR_ARG, "urgym_critic_load: not a critic of this handle (critics belong to the handle they were created with)");
+  if (!p) return fail(h, URGYM_ERR_ARG, "urgym_critic_load: null params");
+  if (p->reserved0 != 0) return fail(h, URGYM_ERR_ARG, "urgym_critic_load: reserved0 must be 0");
+  if (!(tau > 0.0f && tau <= 1.0f)) return fail(h, URGYM_ERR_ARG, "urgym_critic_load: tau must be in (0, 1]");  // refuses NaN too
+  const CriticPacked buf = critic_packed(c);
+  if (p->in_features != buf.in_features || p->hidden_width != buf.hidden) {
+    char msg[200];
+    snprintf(msg, sizeof(msg), "urgym_critic_load: params are %d -> %d, the critic is %d -> %d", p->in_features, p->hidden_width, buf.in_features, buf.hidden);
+    return fail(h, URGYM_ERR_ARG, msg);
+  }
+  const float* src[2 * PACK_CRITIC_TENSORS];
+  for (int net = 0; net < 2; net++) {
+    const urgym_q_network_dev& q = p->qf[net];
+    if (!q.w0 || !q.b0 || !q.w1 || !q.b1 || !q.w_q || !q.b_q) return fail(h, URGYM_ERR_ARG, "urgym_critic_load: a weight or bias pointer is null");
+    const float* one[PACK_CRITIC_TENSORS] = {q.w0, q.b0, q.w1, q.b1, q.w_q, q.b_q};
+    for (int i = 0; i < PACK_CRITIC_TENSORS; i++) src[PACK_CRITIC_TENSORS * net + i] = one[i];
+  }
+  HIP_TRY(h, hipSetDevice(h->device));
+  critic_pack_launch(buf, src, tau, (hipStream_t)stream);
+  HIP_TRY(h, hipGetLastError());
+  return URGYM_OK;
+}
+
+namespace {
+int read_packed(Handle* h, const char* who, const float* dev, size_t floats, float* host_out, uint64_t capacity, uint64_t* count) {
+  char msg[160];
+  if (!count) {
+    snprintf(msg, sizeof(msg), "%s: null count", who);
+    return fail(h, URGYM_ERR_ARG, msg);
+  }
+  *count = floats;
+  if (!host_out) return URGYM_OK;
+  if (capacity < floats) {
+    snprintf(msg, sizeof(msg), "%s: capacity is %llu floats, the packed buffer has %llu", who, (unsigned long long)capacity, (unsigned long long)floats);
+    return fail(h, URGYM_ERR_ARG, msg);
+  }
+  HIP_TRY(h, hipSetDevice(h->device));
+  HIP_TRY(h, hipDeviceSynchronize());
+  HIP_TRY(h, hipMemcpy(host_out, dev, floats * sizeof(float), hipMemcpyDeviceToHost));
+  return URGYM_OK;
+}
+}  // namespace
+
+int urgym_actor_read_packed(void* handle, void* actor, float* host_out, uint64_t capacity, uint64_t* count) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  Actor* a = find_actor(h, actor);
+  if (!a) return fail(h, URGYM_ERR_ARG, "urgym_actor_read_packed: not an actor of this handle");
+  const ActorPacked buf = actor_packed(a);
+  return read_packed(h, "urgym_actor_read_packed", buf.weights, buf.floats, host_out, capacity, count);
+}
+
+int urgym_critic_read_packed(void* handle, void* critic, float* host_out, uint64_t capacity, uint64_t* count) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  Critic* c = find_critic(h, critic);
+  if (!c) return fail(h, URGYM_ERR_ARG, "urgym_critic_read_packed: not a critic of this handle");
+  const CriticPacked buf = critic_packed(c);
+  return read_packed(h, "urgym_critic_read_packed", buf.weights, buf.floats, host_out, capacity, count);
 }
 
 int urgym_refresh(void* handle, const uint8_t* mask_dev, void* stream) {

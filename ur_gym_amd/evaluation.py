@@ -94,6 +94,55 @@ def replay_indices(seed, draw, count, size):
     return np.array([((int(hi) << 32 | int(lo)) * size) >> 64 for hi, lo in zip(w[0], w[1])], dtype=np.int64).reshape(count)
 
 
+def polyak(old, src, tau):
+    """The blend of urgym_critic_load, restated from include/urgym.h in numpy float32: ``src`` at tau == 1 (the old value is not
+    read), otherwise ``(old * omt) + (tau * src)`` with ``omt = float32(1) - float32(tau)``, three operations each rounded to
+    float32 on its own -- not the fused ``old + tau (src - old)``.  `old` and `src` are arrays of one shape (packed buffers:
+    ``DeviceCritic.packed()``); padding that is +0 in both stays +0."""
+    f = np.float32
+    tau = f(tau)
+    if not (np.isfinite(tau) and f(0) < tau <= f(1)):
+        raise ValueError(f"tau must be in (0, 1], got {tau}")
+    old, src = np.asarray(old, dtype=f), np.asarray(src, dtype=f)
+    if old.shape != src.shape:
+        raise ValueError(f"old and src must have one shape, got {old.shape} and {src.shape}")
+    if tau == f(1):
+        return src.copy()
+    omt = f(1) - tau
+    return ((old * omt).astype(f) + (tau * src).astype(f)).astype(f)
+
+
+def _check_device_tensors(tensors, wanted, device, who):
+    """`wanted`: name -> shape.  Raises ValueError unless every one is a contiguous float32 torch tensor of that shape on `device`."""
+    import torch
+
+    device = torch.device(device)
+    for name, shape in wanted.items():
+        t = tensors[name]
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{who}: {name} must be a torch tensor on {device}, got {type(t).__name__}")
+        if t.device != device:
+            raise ValueError(f"{who}: {name} is on {t.device}, the object lives on {device}")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{who}: {name} must be float32, got {t.dtype}")
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{who}: {name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be contiguous (row-major [out][in])")
+
+
+def _read_packed(env, call, obj):
+    import ctypes as C
+
+    from . import _native
+
+    count = C.c_uint64()
+    _native.check(call(env._h, obj, None, 0, C.byref(count)), env._h)
+    out = np.empty(count.value, dtype=np.float32)
+    _native.check(call(env._h, obj, C.c_void_p(out.ctypes.data), count.value, C.byref(count)), env._h)
+    return out
+
+
 LOG_STD_MIN, LOG_STD_MAX = -20.0, 2.0  # SB3 sac/policies.py
 LOG_STD_ARRAYS = ("log_std_weight", "log_std_bias")
 
@@ -249,6 +298,50 @@ class DeviceActor:
                 raise ValueError(f"log_std head must be [6, {h0}] and [6], got {got}")
         return in_features, h0
 
+    @staticmethod
+    def check_parameters(tensors, in_features, hidden_width, device):
+        """Raises ValueError unless `tensors` (a dict under ACTOR_ARRAYS, optionally with both LOG_STD_ARRAYS) holds contiguous
+        float32 torch tensors on `device` shaped for an ``in_features -> hidden_width -> hidden_width -> 6`` actor.  Returns whether
+        the log_std head is present.  Needs no GPU."""
+        missing = [k for k in ACTOR_ARRAYS if k not in tensors]
+        if missing:
+            raise ValueError(f"load_parameters: actor tensors missing: {missing}")
+        unknown = [k for k in tensors if k not in ACTOR_ARRAYS + LOG_STD_ARRAYS]
+        if unknown:
+            raise ValueError(f"load_parameters: unknown actor tensors {unknown}; expected {ACTOR_ARRAYS + LOG_STD_ARRAYS}")
+        present = [k for k in LOG_STD_ARRAYS if k in tensors]
+        if len(present) == 1:
+            raise ValueError(f"load_parameters: the log_std head needs both {LOG_STD_ARRAYS}, got only {present}")
+        n, H = int(in_features), int(hidden_width)
+        wanted = dict(zip(ACTOR_ARRAYS, ((H, n), (H,), (H, H), (H,), (6, H), (6,))))
+        if present:
+            wanted.update(zip(LOG_STD_ARRAYS, ((6, H), (6,))))
+        _check_device_tensors(tensors, wanted, device, "load_parameters")
+        return bool(present)
+
+    def load_parameters(self, tensors):
+        """Reloads the actor from device tensors (urgym_actor_load): `tensors` as ``check_parameters`` takes them, e.g. the
+        parameters of a torch module as they lie.  ONE launch on torch's current stream, nothing is synchronised: passes enqueued
+        before it see the old weights, later ones the new; the tensors are read when the launch runs, so whatever writes them must
+        come before it on that stream, and they must stay alive until it has run (a tensor freed earlier is safe only if torch
+        reuses its memory on the same stream).  Without the log_std tensors the head keeps what it held."""
+        import ctypes as C
+
+        from . import _abi, _native
+
+        env = self.env
+        head = self.check_parameters(tensors, self.in_features, self.hidden_width, env.device)
+        p = _abi.ActorParamsDev(self.in_features, self.hidden_width, 0)
+        for field, key in zip(_abi.ACTOR_DEV_ARRAYS, ACTOR_ARRAYS + (LOG_STD_ARRAYS if head else ())):
+            setattr(p, field, C.cast(tensors[key].data_ptr(), C.POINTER(C.c_float)))
+        _native.check(env.lib.urgym_actor_load(env._h, self._a, C.byref(p), env._stream()), env._h)
+        self.has_log_std = self.has_log_std or head
+
+    def packed(self):
+        """The packed weight buffer as the kernel reads it (float32 numpy array; urgym_actor_read_packed).  A verification aid:
+        synchronises the device."""
+        return _read_packed(self.env, self.env.lib.urgym_actor_read_packed, self._a)
+
     def close(self):
         if getattr(self, "_a", None) and getattr(self.env, "_h", None):
             self.env.lib.urgym_actor_destroy(self.env._h, self._a)
@@ -361,6 +454,48 @@ class DeviceCritic:
         if widths[0] != widths[1]:
             raise ValueError(f"both Q-networks must have one hidden width, got {widths}")
         return want_in, widths[0]
+
+    @staticmethod
+    def check_parameters(tensors, in_features, hidden_width, device):
+        """Raises ValueError unless `tensors` is a pair of dicts under CRITIC_ARRAYS holding contiguous float32 torch tensors on
+        `device` shaped for ``in_features -> hidden_width -> hidden_width -> 1`` networks.  Needs no GPU."""
+        tensors = list(tensors)
+        if len(tensors) != 2:
+            raise ValueError(f"load_parameters: a twin critic has two Q-networks, got {len(tensors)}")
+        n, H = int(in_features), int(hidden_width)
+        wanted = dict(zip(CRITIC_ARRAYS, ((H, n), (H,), (H, H), (H,), (1, H), (1,))))
+        for i, w in enumerate(tensors):
+            missing = [k for k in CRITIC_ARRAYS if k not in w]
+            if missing:
+                raise ValueError(f"load_parameters: qf{i}: critic tensors missing: {missing}")
+            unknown = [k for k in w if k not in CRITIC_ARRAYS]
+            if unknown:
+                raise ValueError(f"load_parameters: qf{i}: unknown critic tensors {unknown}; expected {CRITIC_ARRAYS}")
+            _check_device_tensors(w, wanted, device, f"load_parameters: qf{i}")
+
+    def load_parameters(self, tensors, tau=1.0):
+        """Reloads both Q-networks from device tensors (urgym_critic_load), blending with what the critic holds: tau == 1 replaces,
+        otherwise ``packed = (packed * (1 - tau)) + (tau * src)`` -- SAC's Polyak update of a target critic (``polyak`` restates
+        it).  ONE launch on torch's current stream, nothing is synchronised; stream order as for ``DeviceActor.load_parameters``."""
+        import ctypes as C
+
+        from . import _abi, _native
+
+        env = self.env
+        tensors = [dict(w) for w in tensors]
+        self.check_parameters(tensors, self.in_features, self.hidden_width, env.device)
+        tau = float(tau)
+        if not (np.isfinite(tau) and 0.0 < tau <= 1.0):
+            raise ValueError(f"tau must be in (0, 1], got {tau}")
+        p = _abi.CriticParamsDev(self.in_features, self.hidden_width, 0)
+        for i, w in enumerate(tensors):
+            p.qf[i] = _abi.QNetworkDev(*[C.cast(w[k].data_ptr(), C.POINTER(C.c_float)) for k in CRITIC_ARRAYS])
+        _native.check(env.lib.urgym_critic_load(env._h, self._c, C.byref(p), tau, env._stream()), env._h)
+
+    def packed(self):
+        """The packed weight buffer of both networks as the kernel reads it (float32 numpy array; urgym_critic_read_packed).  A
+        verification aid: synchronises the device."""
+        return _read_packed(self.env, self.env.lib.urgym_critic_read_packed, self._c)
 
     def close(self):
         if getattr(self, "_c", None) and getattr(self.env, "_h", None):

@@ -1,0 +1,155 @@
+"""A small SAC learner on the device pieces: the call pattern of the reference's ``train.py:40-60`` (stable-baselines3
+``SAC("MultiInputPolicy", env, gamma=0.95, batch_size=256).learn``) with collection, a' ~ pi(.|s'), the bootstrapped target and the
+minibatch gather on the HIP kernels, and gradients and optimisers in torch autograd.
+
+    collect   replay.collect with the DeviceActor: uniform actions before ``learning_starts`` env steps, the sampled policy after.
+    update    1. replay.sample_targets with the DeviceActor and the TARGET DeviceCritic: the batch, a', log pi(a'|s') and the
+                 bootstrapped part of the target, r + gamma (1 - terminated) min_i Q_i'(s', a'), from three launches.  The entropy
+                 coefficient is a torch parameter; handing it to the kernel as a number would need a host synchronisation, so the
+                 kernel is given ent_coef = 0 and the entropy term, -gamma (1 - terminated) alpha log pi(a'|s'), is added in torch.
+              2. critic, actor and entropy-coefficient losses as SB3's SAC.train states them; one Adam step each.
+              3. DeviceActor.load_parameters(the torch actor's parameters): one launch.
+              4. target.load_parameters(the torch critic's parameters, tau): one launch, the Polyak update while it packs.
+    Neither synchronises with the host.  There is no logging, no callback and no checkpoint format here; tools/train_sac.py runs it.
+"""
+import numpy as np
+import torch
+from torch import nn
+
+from .evaluation import ACTOR_ARRAYS, CRITIC_ARRAYS, LOG_STD_ARRAYS, LOG_STD_MAX, LOG_STD_MIN, DeviceActor, DeviceCritic
+
+# SB3's SAC defaults where train.py does not set them (tests/golden/critics/sac_hyperparameters.json has the checkpoints' gamma, tau)
+SAC_DEFAULTS = dict(gamma=0.95, tau=0.005, learning_rate=1e-4, batch_size=256, learning_starts=100, hidden_width=256, target_entropy=-6.0,
+                    ent_coef_init=1.0)
+
+
+def _mlp(n_in, hidden, n_out=None):
+    layers = [nn.Linear(n_in, hidden), nn.ReLU(), nn.Linear(hidden, hidden), nn.ReLU()]
+    if n_out is not None:
+        layers.append(nn.Linear(hidden, n_out))
+    return nn.Sequential(*layers)
+
+
+class TorchActor(nn.Module):
+    """SB3's SAC actor: latent_pi = Linear-ReLU-Linear-ReLU, mu and log_std heads, squashed diagonal Gaussian."""
+
+    def __init__(self, in_features, hidden):
+        super().__init__()
+        self.latent_pi, self.mu, self.log_std = _mlp(in_features, hidden), nn.Linear(hidden, 6), nn.Linear(hidden, 6)
+
+    def tensors(self):
+        """The parameters under the names DeviceActor takes (ACTOR_ARRAYS + LOG_STD_ARRAYS), as they lie."""
+        p = (self.latent_pi[0].weight, self.latent_pi[0].bias, self.latent_pi[2].weight, self.latent_pi[2].bias, self.mu.weight, self.mu.bias,
+             self.log_std.weight, self.log_std.bias)
+        return dict(zip(ACTOR_ARRAYS + LOG_STD_ARRAYS, p))
+
+    def sample(self, x, eps):
+        """(action, log_prob) of tanh(mu + exp(log_std) eps), reparameterised; the density as include/urgym.h states it."""
+        h = self.latent_pi(x)
+        mu, log_std = self.mu(h), self.log_std(h).clamp(LOG_STD_MIN, LOG_STD_MAX)
+        action = torch.tanh(mu + log_std.exp() * eps)
+        log_prob = (-0.5 * eps * eps - log_std - 0.5 * np.log(2 * np.pi)).sum(1) - torch.log(1.0 - action * action + 1e-6).sum(1)
+        return action, log_prob
+
+
+class TorchTwinCritic(nn.Module):
+    """SB3's ContinuousCritic with two Q-networks on cat([features, action])."""
+
+    def __init__(self, in_features, hidden):
+        super().__init__()
+        self.qf = nn.ModuleList([_mlp(in_features, hidden, 1) for _ in range(2)])
+
+    def tensors(self):
+        """The parameters of both networks under CRITIC_ARRAYS, as they lie."""
+        return [dict(zip(CRITIC_ARRAYS, (q[0].weight, q[0].bias, q[2].weight, q[2].bias, q[4].weight, q[4].bias))) for q in self.qf]
+
+    def forward(self, x, action):
+        xa = torch.cat([x, action], dim=1)
+        return self.qf[0](xa)[:, 0], self.qf[1](xa)[:, 0]
+
+
+def _features(rows):
+    return torch.cat([rows["achieved_goal"], rows["desired_goal"], rows["observation"]], dim=1)
+
+
+def host_arrays(tensors):
+    """A dict (or a list of dicts) of tensors as numpy arrays: what DeviceActor / DeviceCritic are created from.  Synchronises."""
+    if isinstance(tensors, dict):
+        return {k: v.detach().cpu().numpy().copy() for k, v in tensors.items()}
+    return [host_arrays(t) for t in tensors]
+
+
+class SACLearner:
+    """Torch modules for the actor and the twin critic with Adam on each and on ``log_ent_coef``; a DeviceActor that follows the
+    torch actor and a target DeviceCritic that follows the torch critic by Polyak averaging.  `env`: a UR5ReachVectorEnv with
+    auto_reset.  Keyword arguments override SAC_DEFAULTS."""
+
+    def __init__(self, env, seed=0, **overrides):
+        unknown = [k for k in overrides if k not in SAC_DEFAULTS]
+        if unknown:
+            raise TypeError(f"unknown hyperparameters {unknown}; available: {sorted(SAC_DEFAULTS)}")
+        hp = dict(SAC_DEFAULTS, **overrides)
+        self.env, self.hp, self.seed = env, hp, int(seed)
+        n_in, H, dev = env.obs_dim + 2 * env.goal_dim, int(hp["hidden_width"]), env.device
+        torch.manual_seed(self.seed)
+        self.actor = TorchActor(n_in, H).to(dev)
+        self.critic = TorchTwinCritic(n_in + 6, H).to(dev)
+        self.log_ent_coef = torch.full((1,), float(np.log(hp["ent_coef_init"])), device=dev, requires_grad=True)
+        lr = hp["learning_rate"]
+        self.actor_opt = torch.optim.Adam(self.actor.parameters(), lr=lr)
+        self.critic_opt = torch.optim.Adam(self.critic.parameters(), lr=lr)
+        self.ent_opt = torch.optim.Adam([self.log_ent_coef], lr=lr)
+        self.noise = torch.Generator(device=dev)
+        self.noise.manual_seed(self.seed)
+        self.device_actor = DeviceActor(host_arrays(self.actor.tensors()), env)
+        self.target = DeviceCritic(host_arrays(self.critic.tensors()), env)  # starts as a copy of the online critic
+        self.env_steps = 0  # per env; decides between the warm-up and the policy
+        self.draw = 0       # draw index of the next collection pass
+
+    def collect(self, replay, num_steps):
+        """`num_steps` env steps of all N envs into `replay`, with uniform actions before ``learning_starts`` env steps and the sampled
+        policy afterwards (a call is one or the other: the mode is decided when it starts)."""
+        mode = "uniform" if self.env_steps * self.env.num_envs < self.hp["learning_starts"] else "gaussian"
+        replay.collect(self.device_actor, num_steps, sample=dict(mode=mode, seed=self.seed, first_draw=self.draw))
+        self.env_steps += int(num_steps)
+        self.draw += int(num_steps)
+
+    def update(self, replay, seed, draw):
+        """One gradient step on a minibatch drawn with (seed, draw), then the two reloads.  Returns the three losses as device
+        tensors (not synchronised)."""
+        hp = self.hp
+        gamma = float(hp["gamma"])
+        batch = replay.sample_targets(self.device_actor, self.target, hp["batch_size"], seed, draw, gamma, 0.0)
+        x = _features(batch["observations"])
+        with torch.no_grad():
+            ent_coef = self.log_ent_coef.exp()
+            discount = gamma * (~batch["terminated"]).to(torch.float32)
+            y = batch["target"] - discount * ent_coef * batch["next_log_prob"]
+
+        eps = torch.randn((x.shape[0], 6), device=x.device, generator=self.noise)
+        action_pi, log_prob = self.actor.sample(x, eps)
+
+        ent_loss = -(self.log_ent_coef * (log_prob.detach() + hp["target_entropy"])).mean()
+        self.ent_opt.zero_grad(set_to_none=True)
+        ent_loss.backward()
+        self.ent_opt.step()
+
+        q0, q1 = self.critic(x, batch["actions"])
+        critic_loss = 0.5 * (((q0 - y) ** 2).mean() + ((q1 - y) ** 2).mean())
+        self.critic_opt.zero_grad(set_to_none=True)
+        critic_loss.backward()
+        self.critic_opt.step()
+
+        q_pi = torch.min(*self.critic(x, action_pi))
+        actor_loss = (ent_coef * log_prob - q_pi).mean()
+        self.actor_opt.zero_grad(set_to_none=True)
+        actor_loss.backward()  # also fills the critic's gradients, which its next zero_grad discards
+        self.actor_opt.step()
+
+        self.device_actor.load_parameters(self.actor.tensors())
+        self.target.load_parameters(self.critic.tensors(), tau=hp["tau"])
+        return {"critic_loss": critic_loss.detach(), "actor_loss": actor_loss.detach(), "ent_coef_loss": ent_loss.detach()}
+
+    def close(self):
+        self.device_actor.close()
+        self.target.close()
