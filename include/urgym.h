@@ -377,6 +377,31 @@ int urgym_critic_destroy(void* handle, void* critic);
  * count != num_envs, observation given without achieved_goal and desired_goal, out->target without terms->reward, no output at all. */
 int urgym_critic_evaluate(void* handle, void* critic, const urgym_critic_rows* rows, int count, const urgym_critic_terms* terms, const urgym_critic_out* out, void* stream);
 
+/* ---- the action gradient of the critics (SAC's actor loss, mean(alpha log pi(a|s) - min_i Q_i(s, a)), needs d min_i Q_i / d a at
+ * a = the policy's action and nothing else of the critic's backward pass).  Added WITHIN ABI version 4: no struct above changed,
+ * URGYM_ABI_VERSION did not move, urgym_critic_action_gradient is found by lookup.
+ *
+ * For row m and network i, with z1 = W0,i x + b0,i and z2 = W1,i relu(z1) + b1,i the pre-activations of urgym_critic_evaluate's q_i:
+ *   dq_da[i]  = W0,i[:, action columns]^T  D1  W1,i^T  D2  w_q,i,     D = diag(z > 0),   action columns = in_features - 6 .. in_features - 1
+ *   dqmin_da  = dq_da[sel],   sel = (q_1 < q_0) ? 1 : 0 by this launch's own q
+ * A pre-activation of exactly 0 has derivative 0 (torch's relu).  A tie q_0 == q_1 takes qf0; torch.min halves the gradient between
+ * the two on an exact tie, a set of measure zero.  q and q_min are bitwise urgym_critic_evaluate's.  The sums are float32
+ * fused-multiply-add chains in the kernel's own order: two implementations agree to rounding, and bitwise where every partial sum
+ * is exact.  A row's result depends on nothing but the row. */
+
+/* What the gradient call writes: DEVICE pointers, each may be NULL, at least one of the first two is not. */
+typedef struct urgym_critic_grad_out {
+  float* dq_da;    /* [2][count][6]  d q_i / d action */
+  float* dqmin_da; /* [count][6]     dq_da[sel] */
+  float* q;        /* [2][count] */
+  float* q_min;    /* [count] */
+} urgym_critic_grad_out;
+
+/* ONE launch on `stream`; no allocation and no host synchronisation; everything is validated before the launch.  Refused
+ * (URGYM_ERR_ARG): what urgym_critic_evaluate refuses about handle, critic, rows and count; out == NULL; dq_da == dqmin_da == NULL;
+ * a critic with hidden_width above 256 (the gradient kernel is built for widths up to 256, the shipped checkpoints'). */
+int urgym_critic_action_gradient(void* handle, void* critic, const urgym_critic_rows* rows, int count, const urgym_critic_grad_out* out, void* stream);
+
 /* urgym_actor_sample on explicit rows (SAC draws a' ~ pi(.|s') on next-observation rows, which are not the bound buffers): actions_dev
  * float32 [count][6], log_prob_dev float32 [count] or NULL, draw = how->first_draw, and the `env` word of the noise counter is the row
  * index -- on copies of the bound buffers the result is bitwise urgym_actor_sample's.  rows->observation == NULL means the bound

@@ -32,6 +32,14 @@ around --launches back-to-back repetitions.
 
     python tools/bench_policy_rollout.py --replay --out profiles/policy_rollout/dyn65536_replay.json
 
+--action-gradient measures urgym_critic_action_gradient on the checkpoint's critic (H = 256) at M = 256 (the
+learner's batch) and M = --num-envs explicit rows: alternating windows of (1) the gradient launch, (2) critic_kernel on the same rows,
+(3) the torch route (cat, two MLPs, minimum, sum().backward() onto a.grad).  Bar 1, at the larger M: gradient median <= (28 HT + 32 HT^2)
+/ (28 HT + 16 HT^2) x forward median + the spread of the forward windows (the kernels' own MFMA counts; 1.82 at HT = 8).  Bar 2:
+not slower than torch at both M.  Also one SACLearner.update at batch 256 with and without device_action_gradient.  Hidden widths above
+256 are not measured: the call refuses them.
+    python tools/bench_policy_rollout.py --action-gradient --out profiles/policy_rollout/dyn65536_action_gradient.json
+
 With --refresh: what it costs to hand new weights to a device actor / critic, at hidden width 256 and 512.
 `actor_load`, `critic_load_tau1` and `critic_load_polyak` (tau = 0.005) are load_parameters from device tensors, one launch each;
 `*_host_route` is the only route there was before: every tensor .cpu().numpy(), destroy and create the object (the actor's head by
@@ -403,6 +411,105 @@ def refresh_mode(args):
             f.write(line + "\n")
 
 
+def action_gradient_mode(args):
+    import torch
+    import torch.nn.functional as F
+
+    from ur_gym_amd import make_vec
+    from ur_gym_amd.evaluation import CRITIC_ARRAYS, DeviceCritic, DeviceReplay
+    from ur_gym_amd.training import SACLearner
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_policy_rollout.py measures on a GPU; none is visible")
+    dev, n, kind = "cuda:0", args.num_envs, ACTOR_NPZ[args.env]
+    golden = os.path.join(ROOT, "tests", "golden")
+    env = make_vec(args.env, num_envs=n, device=dev, seed=0, auto_reset=True)
+    env.reset(seed=0)
+    paths = [os.path.join(golden, "critics", f"critic_{kind}_qf{i}.npz") for i in (0, 1)]
+    critic = DeviceCritic.load(paths, env)
+    tw = [{k: torch.from_numpy(np.ascontiguousarray(np.load(p)[k], dtype=np.float32)).to(dev) for k in CRITIC_ARRAYS} for p in paths]
+    for _ in range(20):
+        env.step(torch.rand((n, 6), device=dev) * 2.0 - 1.0)
+    sync = lambda: torch.cuda.synchronize(env.device)  # noqa: E731
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def window(fn, count):
+        sync()
+        e0.record()
+        for _ in range(count):
+            fn()
+        e1.record()
+        sync()
+        return e0.elapsed_time(e1) * 1e3 / count
+
+    HT = (critic.hidden_width + 127) // 128 * 4
+    ratio = (28.0 * HT + 32.0 * HT * HT) / (28.0 * HT + 16.0 * HT * HT)
+    sizes = {}
+    for m in sorted({256, n}):
+        rows = {k: env.buf[k][:m].clone() for k in env.ROW_KEYS}
+        actions = torch.rand((m, 6), device=dev) * 2.0 - 1.0
+        feat = torch.cat([rows["achieved_goal"], rows["desired_goal"], rows["observation"]], dim=1)
+
+        def torch_route():
+            a = actions.clone().requires_grad_(True)
+            x = torch.cat([feat, a], dim=1)
+            q = []
+            for w in tw:
+                y = F.relu(F.linear(x, w["q_0_weight"], w["q_0_bias"]))
+                y = F.relu(F.linear(y, w["q_2_weight"], w["q_2_bias"]))
+                q.append(F.linear(y, w["q_4_weight"], w["q_4_bias"])[:, 0])
+            torch.minimum(q[0], q[1]).sum().backward()
+            return a.grad
+
+        kinds = {"gradient": lambda: env.critic_action_gradient(critic, actions, rows=rows),
+                 "forward": lambda: env.critic_values(critic, actions, rows=rows), "torch": torch_route}
+        for fn in kinds.values():
+            for _ in range(5):
+                fn()
+        sync()
+        got, ref = env.critic_action_gradient(critic, actions, rows=rows)["dqmin_da"], torch_route()
+        agree = {"max_abs_difference_from_torch": float((got - ref).abs().max()), "g_abs_max": float(ref.abs().max())}
+        windows = {k: [] for k in kinds}
+        for _ in range(args.windows):
+            for name, fn in kinds.items():
+                windows[name].append(window(fn, args.launches))
+        med = {k: float(np.median(v)) for k, v in windows.items()}
+        spread = float(max(windows["forward"]) - min(windows["forward"]))
+        sizes[str(m)] = {"us_median": med, "us_windows": {k: [round(x, 3) for x in v] for k, v in windows.items()}, "forward_us_spread": spread,
+                         "gradient_over_forward": med["gradient"] / med["forward"], "bar1_us": ratio * med["forward"] + spread,
+                         "within_bar1": med["gradient"] <= ratio * med["forward"] + spread,
+                         "not_slower_than_torch": med["gradient"] <= med["torch"], "speedup_over_torch": med["torch"] / med["gradient"], **agree}
+    critic.close()
+    updates = {}
+    for label, option in (("parent_route", False), ("device_action_gradient", True)):
+        learner = SACLearner(env, seed=0, batch_size=256, hidden_width=256, device_action_gradient=option)
+        replay = DeviceReplay(env, 4)
+        learner.collect(replay, 4)
+        draw = [0]
+
+        def one_update():
+            draw[0] += 1
+            learner.update(replay, 1, draw[0])
+
+        for _ in range(5):
+            one_update()
+        w = [window(one_update, 20) for _ in range(args.windows)]
+        updates[label] = {"us_median": float(np.median(w)), "us_windows": [round(x, 2) for x in w]}
+        learner.close()
+    result = {"tool": "bench_policy_rollout --action-gradient", "env": args.env, "hidden_width": critic.hidden_width, "windows": args.windows,
+              "launches_per_window": args.launches, "device": torch.cuda.get_device_name(0), "mfma_ratio": ratio, "rows": sizes,
+              "bar1_at_rows": n, "within_bar1": sizes[str(n)]["within_bar1"],
+              "not_slower_than_torch": all(v["not_slower_than_torch"] for v in sizes.values()),
+              "learner_update_batch256": updates, "hidden_512": "not measured: urgym_critic_action_gradient refuses hidden widths above 256"}
+    env.close()
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--env", default="UR5DynReach-v1", choices=sorted(ACTOR_NPZ))
@@ -423,8 +530,11 @@ def main():
     ap.add_argument("--replay", action="store_true", help="measure the device replay ring: collect against a Python loop, the gather against torch (see above)")
     ap.add_argument("--capacity", type=int, default=256, help="--replay: slots of the ring")
     ap.add_argument("--refresh", action="store_true", help="measure reloading actor / critic weights from device tensors against the host route and a copy (see above)")
+    ap.add_argument("--action-gradient", action="store_true", help="measure the critics' action gradient launch against critic_kernel and torch autograd (see above)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.action_gradient:
+        return action_gradient_mode(args)
     if args.critic:
         return critic_mode(args)
     if args.replay:

@@ -189,6 +189,11 @@ class CriticOut(C.Structure):
     _fields_ = [(name, C.POINTER(C.c_float)) for name in ("q", "q_min", "target")]
 
 
+class CriticGradOut(C.Structure):
+    """urgym_critic_grad_out: what urgym_critic_action_gradient writes; every pointer may be NULL, not both of the first two."""
+    _fields_ = [(name, C.POINTER(C.c_float)) for name in ("dq_da", "dqmin_da", "q", "q_min")]
+
+
 REPLAY_TAG = 0x52504C00  # word 3 of the Philox counter of urgym_replay_sample's index draw
 
 # urgym_replay_ring after capacity_steps / reserved0: name -> (ctype of element, shape given (C, N, obs_dim, goal_dim), required)
@@ -256,6 +261,7 @@ EXPORTED_SYMBOLS = [
     "urgym_critic_create",
     "urgym_critic_destroy",
     "urgym_critic_evaluate",
+    "urgym_critic_action_gradient",
     "urgym_actor_sample_rows",
     "urgym_rollout_collect",
     "urgym_replay_sample",

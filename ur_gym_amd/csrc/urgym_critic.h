@@ -8,6 +8,9 @@
 
 namespace urgym {
 
+// The geometry both critic units (urgym_critic.hip, urgym_critic_grad.hip) are written for; each asserts its own constants against it.
+constexpr int CRITIC_GEOMETRY_THREADS = 256, CRITIC_GEOMETRY_ROWS = 128, CRITIC_GEOMETRY_CIN_PAD = 56;
+
 struct Critic;  // the packed weights of both Q-networks on the device (urgym_critic.hip)
 
 // One evaluation: M rows of inputs (DEVICE pointers, row-major), the optional terms of the SAC target and the optional outputs.
@@ -33,8 +36,24 @@ struct CriticPacked {
   int in_features, hidden;
 };
 CriticPacked critic_packed(Critic* c);
+// where the small arrays (per network b0[HP] | b1[HP] | w_q[HP] | b_q, 0, 0, 0) begin in the packed buffer, in floats
+inline size_t critic_small_offset(const CriticPacked& p) { return p.floats - 2 * ((size_t)((p.hidden + 127) / 128 * 128) * 3 + 4); }
 
 // ONE launch on `s`; the caller has validated `call`
 void critic_launch(Critic* c, const CriticCall& call, hipStream_t s);
+
+// The action gradient of both networks on M rows (urgym_critic_grad.hip): the inputs of CriticCall, the outputs of
+// urgym_critic_grad_out (DEVICE pointers, each may be null).
+struct CriticGradCall {
+  int M, obs_dim, goal_dim;
+  const float *observation, *achieved_goal, *desired_goal, *action;  // [M][obs_dim], [M][goal_dim], [M][goal_dim], [M][6]
+  float *dq_da, *dqmin_da, *q, *q_min;                               // [2][M][6], [M][6], [2][M], [M]
+};
+
+// the gradient kernel is built for hidden widths up to this (urgym_critic_grad.hip says why)
+constexpr int CRITIC_GRAD_MAX_HIDDEN = 256;
+bool critic_grad_supported(Critic* c);
+// ONE launch on `s`; the caller has validated `call` and critic_grad_supported(c)
+void critic_grad_launch(Critic* c, const CriticGradCall& call, hipStream_t s);
 
 }  // namespace urgym

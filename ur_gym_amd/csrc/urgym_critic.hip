@@ -39,6 +39,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int CRITIC_THREADS = 256;  // 4 waves
 constexpr int CRITIC_ROWS = 128;     // rows per workgroup (32 per wave)
 constexpr int CIN_PAD = 56;          // layer-1 K, padded with zero weights (in_features <= 53)
+static_assert(CRITIC_THREADS == CRITIC_GEOMETRY_THREADS && CRITIC_ROWS == CRITIC_GEOMETRY_ROWS && CIN_PAD == CRITIC_GEOMETRY_CIN_PAD, "urgym_critic.h");
 constexpr int C1_STEPS4 = CIN_PAD / 8;          // float4 reads per lane and layer-1 tile (4 MFMA steps, 2 k each)
 constexpr int C1_TILE4 = C1_STEPS4 * 64;        // float4 per packed layer-1 tile
 constexpr int C1_CHUNK4 = 4 * C1_TILE4;         // float4 per staged layer-1 chunk (4 tiles, 28 KB)

@@ -2539,6 +2539,28 @@ int urgym_critic_evaluate(void* handle, void* critic, const urgym_critic_rows* r
   return URGYM_OK;
 }
 
+int urgym_critic_action_gradient(void* handle, void* critic, const urgym_critic_rows* rows, int count, const urgym_critic_grad_out* out, void* stream) {
+  const char* who = "urgym_critic_action_gradient";
+  Handle* h = (Handle*)handle;
+  if (int rc = enter_bound(h)) return rc;
+  Critic* c = find_critic(h, critic);
+  if (!c) return fail(h, URGYM_ERR_ARG, "urgym_critic_action_gradient: not a critic of this handle (critics belong to the handle they were created with)");
+  if (critic_in_features(c) != actor_features(h) + 6) return fail(h, URGYM_ERR_ARG, "urgym_critic_action_gradient: the critic does not take this env kind's features");
+  if (!critic_grad_supported(c)) return fail(h, URGYM_ERR_ARG, "urgym_critic_action_gradient: the gradient kernel is built for hidden widths up to 256");
+  CriticGradCall call;
+  memset(&call, 0, sizeof(call));
+  if (int rc = resolve_rows(h, rows, count, who, &call.observation, &call.achieved_goal, &call.desired_goal)) return rc;
+  if (!rows->action) return fail(h, URGYM_ERR_ARG, "urgym_critic_action_gradient: rows->action is null");
+  if (!out) return fail(h, URGYM_ERR_ARG, "urgym_critic_action_gradient: null out");
+  if (!out->dq_da && !out->dqmin_da) return fail(h, URGYM_ERR_ARG, "urgym_critic_action_gradient: no gradient requested (dq_da and dqmin_da are both null)");
+  call.M = count, call.obs_dim = h->obs_dim, call.goal_dim = h->goal_dim;
+  call.action = rows->action;
+  call.dq_da = out->dq_da, call.dqmin_da = out->dqmin_da, call.q = out->q, call.q_min = out->q_min;
+  critic_grad_launch(c, call, (hipStream_t)stream);
+  HIP_TRY(h, hipGetLastError());
+  return URGYM_OK;
+}
+
 int urgym_probe_closest(void* handle, int count, const int* type_a, const double* par_a, const double* pose_a, const int* type_b,
                         const double* par_b, const double* pose_b, double threshold, double* out_dist, int* out_info, void* stream) {
   Handle* h = (Handle*)handle;

@@ -381,6 +381,25 @@ class TwinCritic:
             out.append((h @ w["q_4_weight"].T + w["q_4_bias"])[:, 0].astype(np.float32))
         return tuple(out)
 
+    def action_gradient(self, achieved_goal, desired_goal, observation, action):
+        """(dq_da [2, M, 6], dqmin_da [M, 6], q [2, M]) in float32 as include/urgym.h states urgym_critic_action_gradient:
+        dq_da[i] = W0[:, action columns]^T D1 W1^T D2 w_q with D = diag(pre-activation > 0) -- a pre-activation of exactly 0 has
+        derivative 0 -- and dqmin_da = dq_da[sel], sel = 1 where q_1 < q_0, else 0 (a tie takes qf0)."""
+        x = np.concatenate([achieved_goal, desired_goal, observation, action], axis=1).astype(np.float32)
+        assert x.shape[1] == self.in_features, (x.shape, self.in_features)
+        f, zero = np.float32, np.float32(0.0)
+        grads, qs = [], []
+        for w in self.qf:
+            z1 = x @ w["q_0_weight"].T + w["q_0_bias"]
+            z2 = np.maximum(z1, zero) @ w["q_2_weight"].T + w["q_2_bias"]
+            qs.append((np.maximum(z2, zero) @ w["q_4_weight"].T + w["q_4_bias"])[:, 0].astype(f))
+            d2 = np.where(z2 > 0.0, w["q_4_weight"][0][None, :], zero).astype(f)
+            d1 = np.where(z1 > 0.0, d2 @ w["q_2_weight"], zero).astype(f)
+            grads.append((d1 @ w["q_0_weight"][:, self.in_features - 6:] + zero).astype(f))
+        dq_da, q = np.stack(grads), np.stack(qs)
+        dqmin_da = np.where((q[1] < q[0])[:, None], dq_da[1], dq_da[0])
+        return dq_da, dqmin_da, q
+
     @staticmethod
     def target(q0, q1, reward, gamma, terminated=None, log_prob=None, ent_coef=0.0):
         """(q_min, target) in float32, operation by operation as urgym_critic_evaluate does:

@@ -10,6 +10,9 @@ minibatch gather on the HIP kernels, and gradients and optimisers in torch autog
               2. critic, actor and entropy-coefficient losses as SB3's SAC.train states them; one Adam step each.
               3. DeviceActor.load_parameters(the torch actor's parameters): one launch.
               4. target.load_parameters(the torch critic's parameters, tau): one launch, the Polyak update while it packs.
+    With ``device_action_gradient=True`` the actor loss does not run the torch critic a second time: an ONLINE DeviceCritic is reloaded
+    after the critic's Adam step (tau = 1) and one launch of the gradient kernel gives g = d min_i Q_i / d a and q_min at the policy's
+    action; ``(ent_coef * log_prob - (action_pi * g).sum(1)).mean()`` has the actor loss's gradient with respect to the actor.
     Neither synchronises with the host.  There is no logging, no callback and no checkpoint format here; tools/train_sac.py runs it.
 """
 import numpy as np
@@ -20,7 +23,7 @@ from .evaluation import ACTOR_ARRAYS, CRITIC_ARRAYS, LOG_STD_ARRAYS, LOG_STD_MAX
 
 # SB3's SAC defaults where train.py does not set them (tests/golden/critics/sac_hyperparameters.json has the checkpoints' gamma, tau)
 SAC_DEFAULTS = dict(gamma=0.95, tau=0.005, learning_rate=1e-4, batch_size=256, learning_starts=100, hidden_width=256, target_entropy=-6.0,
-                    ent_coef_init=1.0)
+                    ent_coef_init=1.0, device_action_gradient=False)
 
 
 def _mlp(n_in, hidden, n_out=None):
@@ -103,6 +106,8 @@ class SACLearner:
         self.noise.manual_seed(self.seed)
         self.device_actor = DeviceActor(host_arrays(self.actor.tensors()), env)
         self.target = DeviceCritic(host_arrays(self.critic.tensors()), env)  # starts as a copy of the online critic
+        # the online critic on the device, only where the actor loss takes its action gradient from the kernel
+        self.online = DeviceCritic(host_arrays(self.critic.tensors()), env) if hp["device_action_gradient"] else None
         self.env_steps = 0  # per env; decides between the warm-up and the policy
         self.draw = 0       # draw index of the next collection pass
 
@@ -140,10 +145,16 @@ class SACLearner:
         critic_loss.backward()
         self.critic_opt.step()
 
-        q_pi = torch.min(*self.critic(x, action_pi))
-        actor_loss = (ent_coef * log_prob - q_pi).mean()
         self.actor_opt.zero_grad(set_to_none=True)
-        actor_loss.backward()  # also fills the critic's gradients, which its next zero_grad discards
+        if self.online is None:
+            q_pi = torch.min(*self.critic(x, action_pi))
+            actor_loss = (ent_coef * log_prob - q_pi).mean()
+            actor_loss.backward()  # also fills the critic's gradients, which its next zero_grad discards
+        else:
+            self.online.load_parameters(self.critic.tensors(), tau=1.0)
+            grad = self.env.critic_action_gradient(self.online, action_pi.detach(), rows=batch["observations"])
+            (ent_coef * log_prob - (action_pi * grad["dqmin_da"]).sum(1)).mean().backward()  # through the torch actor only
+            actor_loss = (ent_coef * log_prob.detach() - grad["q_min"]).mean()
         self.actor_opt.step()
 
         self.device_actor.load_parameters(self.actor.tensors())
@@ -153,3 +164,5 @@ class SACLearner:
     def close(self):
         self.device_actor.close()
         self.target.close()
+        if self.online is not None:
+            self.online.close()

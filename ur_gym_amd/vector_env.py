@@ -286,6 +286,23 @@ class UR5ReachVectorEnv:
         _native.check(self.lib.urgym_critic_evaluate(self._h, critic._c, C.byref(cr), count, C.byref(terms), C.byref(out), self._stream()), self._h)
         return res
 
+    def critic_action_gradient(self, critic, actions, rows=None):
+        """The gradient of both Q-networks of `critic` with respect to `actions`, one launch of the HIP gradient kernel
+        (urgym_critic_action_gradient): a dict of fresh device tensors ``dq_da`` [2, ..., 6], ``dqmin_da`` [..., 6] = the gradient of
+        min(q0, q1) (of qf0 on a tie), and ``q`` [2, ...], ``q_min`` [...] as ``critic_values`` gives them, bitwise.  `rows` and the
+        leading shapes are ``critic_values``'; nothing is synchronised."""
+        if getattr(critic, "env", None) is not self or not getattr(critic, "_c", None):
+            raise ValueError("critic must be a live DeviceCritic loaded for this environment (DeviceCritic.load(paths, env))")
+        cr, lead, keep = self._rows(rows, action=actions)
+        count = int(np.prod(lead))
+        res = {"dq_da": torch.empty((2,) + lead + (6,), dtype=torch.float32, device=self.device),
+               "dqmin_da": torch.empty(lead + (6,), dtype=torch.float32, device=self.device),
+               "q": torch.empty((2,) + lead, dtype=torch.float32, device=self.device),
+               "q_min": torch.empty(lead, dtype=torch.float32, device=self.device)}
+        out = _abi.CriticGradOut(*[C.cast(res[k].data_ptr(), C.POINTER(C.c_float)) for k in ("dq_da", "dqmin_da", "q", "q_min")])
+        _native.check(self.lib.urgym_critic_action_gradient(self._h, critic._c, C.byref(cr), count, C.byref(out), self._stream()), self._h)
+        return res
+
     def policy_actions(self, actor, out=None, sample=None, rows=None):
         """model.predict(obs, deterministic=True) (model_test.py:41) for all envs, by the HIP actor kernel, from the live
         observation buffers: float32 [N, 6] on the device.
