@@ -535,6 +535,61 @@ int urgym_actor_load(void* handle, void* actor, const urgym_actor_params_dev* pa
  * required), and tau outside (0, 1] or not finite. */
 int urgym_critic_load(void* handle, void* critic, const urgym_critic_params_dev* params, float tau, void* stream);
 
+/* ---- the parameter gradients of the critics (SAC's critic loss, 0.5 (mse(q_0, y) + mse(q_1, y)), needs d loss / d parameters of
+ * both Q-networks).  Added WITHIN ABI version 4: no struct above changed, URGYM_ABI_VERSION did not move, the new symbols
+ * (urgym_critic_parameter_gradients, urgym_critic_parameter_gradients_workspace) are found by lookup.
+ *
+ * Per network i, with x[m] row m of urgym_critic_rows (features | action) and dq_i[m] = d loss / d q_i[m], everything float32:
+ *   z1 = W0 x + b0    h1 = relu(z1)    z2 = W1 h1 + b1    h2 = relu(z2)    q = w_q . h2 + b_q
+ *   d2[m] = dq[m] * w_q   where z2 > 0, else 0        d1[m] = (W1^T d2[m])   where z1 > 0, else 0
+ *   g_wq = sum_m dq[m] h2[m]      g_bq = sum_m dq[m]
+ *   g_W1 = sum_m d2[m] h1[m]^T    g_b1 = sum_m d2[m]
+ *   g_W0 = sum_m d1[m] x[m]^T     g_b0 = sum_m d1[m]
+ * The mask convention is urgym_critic_action_gradient's (a pre-activation of exactly 0, or NaN, has derivative 0) and q is bitwise
+ * urgym_critic_evaluate's.  Unlike every call above the results SUM over the rows.  The sum runs in a fixed order that depends on
+ * nothing but count (ur_gym_amd/csrc/urgym_critic_backward.hip states it): rows ascending within a split of 1024 rows, then the
+ * splits ascending; no floating-point atomics; two calls on the same inputs give bitwise the same tensors.  Two sums are carried in
+ * float64 and rounded to float32 once: g_bq within a split (a single scalar out of up to 1024 terms) and the addition of the splits.
+ *
+ * The upstream gradient: exactly one of `dq` and `target` is given.
+ *   dq      DEVICE [2][count], used as it is.
+ *   target  DEVICE [count], with `scale` (finite): dq_i[m] = (q_i[m] - target[m]) * scale, one float32 subtraction and one float32
+ *           multiplication, each rounded on its own, with this call's own q.  scale = 1 / count gives SB3's critic loss above. */
+
+/* Where the gradients go: DEVICE pointers, float32, torch's [out][in] row-major layout, 4-byte aligned -- a torch parameter's .grad
+ * as it lies.  All twelve are required.  Every float of every tensor is written by every call. */
+typedef struct urgym_q_network_grad {
+  float* w0;  /* [hidden_width][in_features] */
+  float* b0;  /* [hidden_width] */
+  float* w1;  /* [hidden_width][hidden_width] */
+  float* b1;  /* [hidden_width] */
+  float* w_q; /* [1][hidden_width] */
+  float* b_q; /* [1] */
+} urgym_q_network_grad;
+
+typedef struct urgym_critic_param_grads {
+  urgym_q_network_grad qf[2];
+  float* q; /* [2][count], or NULL */
+} urgym_critic_param_grads;
+
+#define URGYM_CRITIC_GRADIENTS_MAX_COUNT 65536
+
+/* The size of the workspace a call with this critic and count needs, in bytes: the per-row quantities h1, h2, d2, d1 of both
+ * networks, x, dq, and above 1024 rows the partial sums.  For hidden_width 256, in_features 53 and count 65,536 it is 592,970,240
+ * bytes.  Refused: NULL handle / critic / bytes, a critic of another handle or wider than 256, count outside
+ * [1, URGYM_CRITIC_GRADIENTS_MAX_COUNT]. */
+int urgym_critic_parameter_gradients_workspace(void* handle, void* critic, int count, uint64_t* bytes);
+
+/* TWO launches on `stream` up to 1024 rows (per row; the sums), THREE above (per row; the sums per split of 1024 rows; the splits
+ * added up).  The caller owns the workspace (DEVICE, 16-byte aligned, at least the queried size): the library allocates nothing and
+ * keeps no state between calls, every workspace float that is read was written earlier in the same call, and what the workspace or
+ * the outputs held before does not matter.  No host synchronisation; everything is validated before the first launch.  Refused
+ * (URGYM_ERR_ARG, nothing is launched): what urgym_critic_evaluate refuses about handle, critic, rows and count; a critic with
+ * hidden_width above 256 (like urgym_critic_action_gradient); count above URGYM_CRITIC_GRADIENTS_MAX_COUNT; both or neither of dq
+ * and target; target with a scale that is not finite; out == NULL or one of its twelve tensor pointers; workspace NULL, misaligned
+ * or workspace_bytes below the queried size. */
+int urgym_critic_parameter_gradients(void* handle, void* critic, const urgym_critic_rows* rows, int count, const float* dq, const float* target, float scale, const urgym_critic_param_grads* out, void* workspace, uint64_t workspace_bytes, void* stream);
+
 /* Verification aid, not a hot path: synchronises the device, then copies the object's packed buffer (the kernel's own layout,
  * ur_gym_amd/csrc/urgym_pack_map.h) to host_out and stores its length in floats in *count.  host_out == NULL only reports *count;
  * otherwise capacity (in floats) must be at least that.  Refused: NULL handle / object / count, an object of another handle,

@@ -1,0 +1,575 @@
+"""The parameter gradients of the twin critics: urgym_critic_parameter_gradients through ``env.critic_parameter_gradients``, the numpy
+restatement ``TwinCritic.parameter_gradients`` and the learner's ``device_critic_gradient`` option.
+
+Where the checks come from (no number is taken from what the kernels give):
+  * the formulas of include/urgym.h are pinned by torch.autograd in float64 on the four checkpoints' critics, on the 1680 recorded rows
+    with dq = (q - y) / M and y the recorded rewards, to 1e-10 relative per tensor.
+  * the exact network (tests/test_critic.py's construction, restated): W0 / W1 dense +-1, inputs and hidden biases in {-1, 0, 1}, head
+    +-2^-13, dq in {-1, 0, 1} 2^-4.  Every term of every sum is an integer multiple of one unit; the test computes the largest sum of
+    absolute terms over any output element in units from the float64 pass and asserts it is below 2^24, so every partial sum in any
+    order is a float32 number and float32, float64 and the device agree BITWISE.
+  * on the checkpoints a row is excluded where a float64 pre-activation is within 4 x numpy float32's largest deviation on that layer
+    (test_action_gradient.py's rule; at most 5 % of the rows, asserted); the batch is the kept rows, so no mask flips inside a sum.  The
+    device may deviate from float64 by 4 x numpy float32's deviation per tensor: the project's rule for a second float32 order.
+  * the learner: the device route's critic gradients may deviate from float64 autograd by 4 x the default route's deviation plus one
+    float32 ulp of the tensor's largest gradient.
+  * tests/backward_harness.cpp enumerates the kernels' index arithmetic on the host under the address and undefined-behaviour
+    sanitizers: bounds, the bijection between stage 1's writes and stage 2's reads, every output element written once.
+"""
+import ctypes as C
+import functools
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from ur_gym_amd import _abi, _native
+from ur_gym_amd.evaluation import CRITIC_ARRAYS, DeviceCritic, TwinCritic
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+CSRC = os.path.join(ROOT, "ur_gym_amd", "csrc")
+CRITICS = os.path.join(ROOT, "tests", "golden", "critics")
+NAMES = ("ori", "obs", "sta", "dyn")
+ENVS = {"ori": "UR5OriReach-v1", "obs": "UR5ObsReach-v1", "sta": "UR5StaReach-v1", "dyn": "UR5DynReach-v1"}
+KINDS = {"ori": _abi.ENV_ORI, "obs": _abi.ENV_OBS, "sta": _abi.ENV_STA, "dyn": _abi.ENV_DYN}
+IN_FEATURES = {"ori": 36, "obs": 38, "sta": 47, "dyn": 53}
+GRID = 2.0 ** -13
+DQ_UNIT = 2.0 ** -4
+WIDTHS = (32, 96, 128, 160, 256, 288, 384, 416, 512)
+CASES = [("dyn", H) for H in WIDTHS] + [(kind, H) for kind in ("ori", "obs", "sta") for H in (96, 160, 384, 512)]
+GPU_WIDTHS = (32, 128, 160, 256)
+REFUSED_WIDTHS = (288, 512)
+SPLIT = 1024  # rows per split of stage 2 (urgym_backward_map.h: BW_SPLIT_ROWS)
+# one lane, a second wave, a full workgroup, a second workgroup with one row, ragged; stage 2's split boundary and its neighbours
+GPU_COUNTS = (1, 33, 128, 129, 417, SPLIT - 1, SPLIT, SPLIT + 1)
+SYMBOLS = ("urgym_critic_parameter_gradients", "urgym_critic_parameter_gradients_workspace")
+
+
+def critic_weights(name):
+    return [dict(np.load(os.path.join(CRITICS, f"critic_{name}_qf{i}.npz"))) for i in (0, 1)]
+
+
+def split(name, x):
+    od, gd = _abi.OBS_DIMS[KINDS[name]]
+    return x[:, :gd], x[:, gd:2 * gd], x[:, 2 * gd:2 * gd + od], x[:, 2 * gd + od:]
+
+
+def trace_rows(name):
+    z = np.load(os.path.join(ROOT, "tests", "golden", f"step_trace_{name}.npz"))
+    parts = [z["step_achieved_goal"][:-1], z["step_desired_goal"][:-1], z["step_observation"][:-1], z["actions"][1:]]
+    return np.concatenate([p.reshape(-1, p.shape[-1]) for p in parts], axis=1).astype(np.float32)
+
+
+def trace_rewards(name):
+    z = np.load(os.path.join(ROOT, "tests", "golden", f"step_trace_{name}.npz"))
+    return z["step_reward"][1:].reshape(-1).astype(np.float32)
+
+
+def exact_inputs(kind, n):
+    rng = np.random.default_rng([n, IN_FEATURES[kind], 11])
+    return rng.integers(-1, 2, (n, IN_FEATURES[kind])).astype(np.float32)
+
+
+def exact_critic(kind, H):
+    """tests/test_critic.py::exact_critic, restated."""
+    n_in = IN_FEATURES[kind]
+    nets = []
+    bias = (np.random.default_rng([H, n_in, 12]).integers(-1024, 1025, 1) * GRID).astype(np.float32)
+    for i in (1, 2):
+        rng = np.random.default_rng([H, n_in, 12 + i])
+        sign = lambda shape: (rng.integers(0, 2, shape) * 2 - 1).astype(np.float32)  # noqa: E731
+        plus = H // 2 + int(np.ceil(0.45 * np.sqrt(H)))
+        w1 = rng.permuted(np.where(np.arange(H) < plus, 1.0, -1.0)[None, :].repeat(H, axis=0), axis=1).astype(np.float32)
+        nets.append({"q_0_weight": sign((H, n_in)), "q_0_bias": rng.integers(-1, 2, H).astype(np.float32),
+                     "q_2_weight": w1, "q_2_bias": rng.integers(-1, 2, H).astype(np.float32),
+                     "q_4_weight": rng.permutation(np.where(np.arange(H) < H // 2, 1.0, -1.0))[None, :].astype(np.float32) * np.float32(GRID), "q_4_bias": bias})
+    return nets
+
+
+def exact_dq(kind, n):
+    rng = np.random.default_rng([n, IN_FEATURES[kind], 17])
+    return (rng.integers(-1, 2, (2, n)) * DQ_UNIT).astype(np.float32)
+
+
+def forward_f64(w, x):
+    w = {k: np.asarray(v, dtype=np.float64) for k, v in w.items()}
+    x = x.astype(np.float64)
+    z1 = x @ w["q_0_weight"].T + w["q_0_bias"]
+    z2 = np.maximum(z1, 0.0) @ w["q_2_weight"].T + w["q_2_bias"]
+    return z1, z2, (np.maximum(z2, 0.0) @ w["q_4_weight"].T + w["q_4_bias"])[:, 0]
+
+
+def gradients_f64(w, x, dq, wrong=None, magnitudes=False):
+    """The six gradient tensors of one network in float64, keyed by CRITIC_ARRAYS.  `wrong` names one of four WRONG references, for the
+    sensitivity checks.  With `magnitudes` also the largest sum of absolute terms over any element of each tensor (and of d1)."""
+    w = {k: np.asarray(v, dtype=np.float64) for k, v in w.items()}
+    x, dq = x.astype(np.float64), np.asarray(dq, dtype=np.float64)
+    z1, z2, _ = forward_f64(w, x)
+    mask = np.greater_equal if wrong == "mask >=" else np.greater
+    h1, h2 = np.maximum(z1, 0.0), np.maximum(z2, 0.0)
+    d2 = np.where(mask(z2, 0.0), dq[:, None] * w["q_4_weight"][0][None, :], 0.0)
+    d1 = np.where(mask(z1, 0.0), d2 @ (w["q_2_weight"].T if wrong == "W1 for W1^T" else w["q_2_weight"]), 0.0)
+    g = (d1.T @ x, (d2 if wrong == "d2 for d1 in g_b0" else d1).sum(axis=0), d2.T @ h1, d2.sum(axis=0),
+         (dq @ (h1 if wrong == "h1 for h2 in g_wq" else h2))[None, :], dq.sum(keepdims=True))
+    out = {k: v + 0.0 for k, v in zip(CRITIC_ARRAYS, g)}
+    if not magnitudes:
+        return out
+    a1, a2 = np.abs(d1), np.abs(d2)
+    mags = (a1.T @ np.abs(x), a1.sum(axis=0), a2.T @ h1, a2.sum(axis=0), np.abs(dq) @ h2, np.abs(dq).sum(), a2 @ np.abs(w["q_2_weight"]))
+    return out, [float(np.max(m)) for m in mags]
+
+
+def bits_equal(a32, b64):
+    a32 = np.asarray(a32)
+    return a32.dtype == np.float32 and a32.shape == b64.shape and np.array_equal(a32.view(np.uint32), b64.astype(np.float32).view(np.uint32))
+
+
+def assert_exact(nets, x, dq, unit):
+    """The float64 gradients of both networks, after asserting that every sum of absolute terms is below 2^24 units."""
+    refs = []
+    for i, w in enumerate(nets):
+        g, mags = gradients_f64(w, x, dq[i], magnitudes=True)
+        # g_wq, g_bq: terms dq h2, multiples of `unit`; every other term carries the head's 2^-13 as well
+        units = [unit * GRID, unit * GRID, unit * GRID, unit * GRID, unit, unit, unit * GRID]
+        worst = max(m / u for m, u in zip(mags, units))
+        assert worst < 2.0 ** 24, (i, worst)
+        refs.append((g, worst))
+    return [r[0] for r in refs], max(r[1] for r in refs)
+
+
+# ------------------------------------------------------------------------------------------------ CPU
+def test_struct_and_symbols_mirror_the_header():
+    hdr = open(os.path.join(ROOT, "include", "urgym.h")).read()
+    body = hdr[hdr.index("typedef struct urgym_q_network_grad"):hdr.index("} urgym_q_network_grad;")]
+    got = re.findall(r"^\s*(float\*)\s+(\w+);", body, flags=re.M)
+    assert [(n, C.POINTER(C.c_float)) for _, n in got] == list(_abi.QNetworkGrad._fields_)
+    assert [n for _, n in got] == [n for n, _ in _abi.QNetworkDev._fields_]  # the six tensors of urgym_q_network_dev, non-const
+    body = hdr[hdr.index("typedef struct urgym_critic_param_grads"):hdr.index("} urgym_critic_param_grads;")]
+    got = re.findall(r"^\s*(float\*|urgym_q_network_grad)\s+(\w+)(\[2\])?;", body, flags=re.M)
+    assert got == [("urgym_q_network_grad", "qf", "[2]"), ("float*", "q", "")]
+    assert _abi.CriticParamGrads._fields_[0] == ("qf", _abi.QNetworkGrad * 2) and _abi.CriticParamGrads._fields_[1] == ("q", C.POINTER(C.c_float))
+    assert C.sizeof(_abi.CriticParamGrads) == 13 * C.sizeof(C.c_void_p)
+    assert f"#define URGYM_CRITIC_GRADIENTS_MAX_COUNT {_abi.CRITIC_GRADIENTS_MAX_COUNT}" in hdr and _abi.CRITIC_GRADIENTS_MAX_COUNT >= 65536
+    assert _abi.ABI_VERSION == 4 and "#define URGYM_ABI_VERSION 4" in hdr  # added within version 4
+    lib = _native.lib()
+    for sym in SYMBOLS:
+        assert sym in _abi.EXPORTED_SYMBOLS and hasattr(lib, sym), sym
+        assert re.search(rf"^int {sym}\(.*\);$", hdr, flags=re.M), sym
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_formula_against_autograd_float64(name):
+    import torch
+
+    nets, x, y = critic_weights(name), trace_rows(name), trace_rewards(name).astype(np.float64)
+    assert x.shape == (1680, IN_FEATURES[name]) and y.shape == (1680,)
+    xa = torch.from_numpy(x.astype(np.float64))
+    for i, w in enumerate(nets):
+        t = {k: torch.from_numpy(np.asarray(v, dtype=np.float64)).requires_grad_(True) for k, v in w.items()}
+        h = torch.relu(xa @ t["q_0_weight"].T + t["q_0_bias"])
+        h = torch.relu(h @ t["q_2_weight"].T + t["q_2_bias"])
+        q = (h @ t["q_4_weight"].T + t["q_4_bias"])[:, 0]
+        (0.5 * ((q - torch.from_numpy(y)) ** 2).mean()).backward()
+        q64 = forward_f64(w, x)[2]
+        g64 = gradients_f64(w, x, (q64 - y) / len(x))
+        for k in CRITIC_ARRAYS:
+            want = t[k].grad.numpy()
+            rel = float(np.abs(g64[k] - want).max() / np.abs(want).max())
+            print(f"{name} qf{i} {k}: formula vs autograd (float64) {rel:.3e} relative, |g| up to {np.abs(want).max():.4g}")
+            assert g64[k].shape == want.shape and rel <= 1e-10, (name, i, k, rel)
+
+
+@pytest.mark.parametrize("kind,H", CASES, ids=[f"{k}-{H}" for k, H in CASES])
+def test_exact_network_float32_is_float64_bitwise(kind, H):
+    nets = exact_critic(kind, H)
+    n = 417
+    x, dq = exact_inputs(kind, n), exact_dq(kind, n)
+    refs, worst = assert_exact(nets, x, dq, DQ_UNIT)
+    print(f"{kind} H={H}: largest sum of absolute terms {worst:.4g} units (2^24 = {2.0 ** 24:.4g})")
+    grads, q32 = TwinCritic(nets).parameter_gradients(*split(kind, x), dq=dq)
+    for i in (0, 1):
+        assert bits_equal(q32[i], forward_f64(nets[i], x)[2])
+        for k in CRITIC_ARRAYS:
+            assert bits_equal(grads[i][k], refs[i][k]), (kind, H, i, k)
+            assert (refs[i][k] != 0.0).any(), (kind, H, i, k)  # an output nobody wrote cannot pass
+    shares = {}
+    for label in ("W1 for W1^T", "mask >=", "h1 for h2 in g_wq", "d2 for d1 in g_b0"):
+        bad = gradients_f64(nets[0], x, dq[0], wrong=label)
+        shares[label] = float(np.mean(np.concatenate([(bad[k] != refs[0][k]).ravel() for k in CRITIC_ARRAYS])))
+    print(f"{kind} H={H}: share of elements on which a wrong reference differs: {shares}")
+    assert all(s > 0.0 for s in shares.values()), (kind, H, shares)
+
+
+@functools.lru_cache(maxsize=None)
+def checkpoint_case(name):
+    """The checkpoint on the kept trace rows: x, y, dq [2, M] (float32, from float64 q), the float64 gradients and numpy float32's
+    deviation per network and tensor, and the number of rows excluded per network."""
+    nets, x, y = critic_weights(name), trace_rows(name), trace_rewards(name)
+    keep, dropped = np.ones(len(x), bool), []
+    for w in nets:
+        z1, z2, _ = forward_f64(w, x)
+        s1 = x @ w["q_0_weight"].T + w["q_0_bias"]  # numpy float32, as TwinCritic evaluates them
+        s2 = np.maximum(s1, np.float32(0.0)) @ w["q_2_weight"].T + w["q_2_bias"]
+        k = (np.abs(z1) >= 4.0 * np.abs(s1 - z1).max()).all(axis=1) & (np.abs(z2) >= 4.0 * np.abs(s2 - z2).max()).all(axis=1)
+        assert np.array_equal(s1[k] > 0, z1[k] > 0) and np.array_equal(s2[k] > 0, z2[k] > 0)  # what the rule is for
+        dropped.append(int((~k).sum()))
+        keep &= k
+    x, y = x[keep], y[keep]
+    dq = np.stack([((forward_f64(w, x)[2] - y) / len(x)).astype(np.float32) for w in nets])
+    g64 = [gradients_f64(w, x, dq[i]) for i, w in enumerate(nets)]
+    g32, _ = TwinCritic(nets).parameter_gradients(*split(name, x), dq=dq)
+    dev32 = [{k: float(np.abs(g32[i][k].astype(np.float64) - g64[i][k]).max()) for k in CRITIC_ARRAYS} for i in (0, 1)]
+    return dict(nets=nets, x=x, y=y, dq=dq, g64=g64, dev32=dev32, dropped=dropped)
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_checkpoints_float32_against_float64(name):
+    case = checkpoint_case(name)
+    print(f"{name}: rows excluded per network {case['dropped']} of 1680, batch of {len(case['x'])} kept rows")
+    assert all(d <= 0.05 * 1680 for d in case["dropped"]) and len(case["x"]) >= 0.9 * 1680
+    for i in (0, 1):
+        for k in CRITIC_ARRAYS:
+            top = float(np.abs(case["g64"][i][k]).max())
+            print(f"{name} qf{i} {k}: numpy float32 vs float64 {case['dev32'][i][k]:.3e} at |g| up to {top:.4g}")
+            assert np.isfinite(case["dev32"][i][k]) and case["dev32"][i][k] <= 2.0 ** -10 * top
+
+
+def test_index_arithmetic_on_the_host_under_sanitizers():
+    exe = os.path.join(HERE, "_build", "backward_harness")
+    os.makedirs(os.path.dirname(exe), exist_ok=True)
+    src = os.path.join(HERE, "backward_harness.cpp")
+    deps = [src, os.path.join(CSRC, "urgym_backward_map.h")]
+    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe, src])
+    run = subprocess.run([exe], capture_output=True, text=True)
+    out = run.stdout
+    assert run.returncode == 0 and "FAIL" not in out and "runtime error" not in run.stderr, (out[-2000:], run.stderr[-2000:])
+    lines = out.splitlines()
+    counts = (1, 33, 128, 129, 417, SPLIT - 1, SPLIT, SPLIT + 1, 2 * SPLIT + 1)
+    assert lines[-1] == f"ok {4 * 4 * len(counts)}"
+    for n_in in IN_FEATURES.values():
+        for H in GPU_WIDTHS:
+            for count in counts:
+                assert any(l.startswith(f"backward in={n_in} H={H} count={count} ") for l in lines), (n_in, H, count)
+    # the launches and the size include/urgym.h states
+    assert any(l.startswith(f"backward in=53 H=256 count={SPLIT} ") and l.endswith("splits=1 launches=2") for l in lines)
+    assert any(l.startswith(f"backward in=53 H=256 count={SPLIT + 1} ") and l.endswith("splits=2 launches=3") for l in lines)
+    hdr = open(os.path.join(ROOT, "include", "urgym.h")).read()
+    size = int(re.search(r"^workspace in=53 H=256 count=65536 bytes=(\d+)$", out, flags=re.M).group(1))
+    assert f"{size:,}" in hdr
+
+
+# ------------------------------------------------------------------------------------------------ GPU
+def _env(kind, n, seed=1, **kw):
+    from ur_gym_amd import make_vec
+
+    env = make_vec(ENVS[kind], num_envs=n, device="cuda:0", seed=seed, **kw)
+    env.reset(seed=seed)
+    return env
+
+
+def _dev(a):
+    import torch
+
+    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
+
+
+def _same(a, b):
+    import torch
+
+    return a.shape == b.shape and bool(torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32)))
+
+
+def _rows(kind, x):
+    ach, des, obs, act = (_dev(p) for p in split(kind, x))
+    return dict(observation=obs, achieved_goal=ach, desired_goal=des), act
+
+
+def _fp(t):
+    return C.cast(t.data_ptr(), C.POINTER(C.c_float))
+
+
+def _all_same(a, b):
+    return _same(a["q"], b["q"]) and all(_same(a["grads"][i][k], b["grads"][i][k]) for i in (0, 1) for k in CRITIC_ARRAYS)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", NAMES)
+@pytest.mark.parametrize("H", GPU_WIDTHS)
+def test_exact_network_on_the_device(kind, H):
+    import torch
+
+    nets = exact_critic(kind, H)
+    n_env = 417
+    env = _env(kind, n_env)
+    critic = DeviceCritic(nets, env)
+    scale = 2.0 ** -3
+    for n in GPU_COUNTS:
+        x, dq = exact_inputs(kind, n), exact_dq(kind, n)
+        refs, _ = assert_exact(nets, x, dq, DQ_UNIT)
+        q64 = np.stack([forward_f64(w, x)[2] for w in nets])
+        rows, act = _rows(kind, x)
+        got = env.critic_parameter_gradients(critic, act, dq=_dev(dq), rows=rows)
+        # the target form, on the n of 4 n candidate rows on which the float64 q_0 and q_1 lie closest: y a few grid steps from q_0, so
+        # that q_i - y are small multiples of the grid, dq = (q - y) 2^-3 is exact and the sums stay below 2^24 units (asserted)
+        cand = exact_inputs(kind, 4 * n)
+        qc = np.stack([forward_f64(w, cand)[2] for w in nets])
+        pick = np.sort(np.argsort(np.abs(qc[1] - qc[0]), kind="stable")[:n])
+        x_t, q64_t = cand[pick], qc[:, pick]
+        k = np.random.default_rng([n, H, 19]).integers(-2, 3, n)
+        y = (q64_t[0] - k * GRID).astype(np.float32)
+        assert np.array_equal(y.astype(np.float64), q64_t[0] - k * GRID)
+        dq_t = (q64_t - y.astype(np.float64)[None, :]) * scale
+        refs_t, _ = assert_exact(nets, x_t, dq_t, GRID * scale)
+        rows_t, act_t = _rows(kind, x_t)
+        got_t = env.critic_parameter_gradients(critic, act_t, target=_dev(y), scale=scale, rows=rows_t)
+        torch.cuda.synchronize()
+        for res, want, q_want in ((got, refs, q64), (got_t, refs_t, q64_t)):
+            assert bits_equal(res["q"].cpu().numpy(), q_want), (kind, H, n)
+            for i in (0, 1):
+                for key in CRITIC_ARRAYS:
+                    assert bits_equal(res["grads"][i][key].cpu().numpy(), want[i][key]), (kind, H, n, i, key)
+        if n == n_env:  # the bound buffers
+            for key in env.ROW_KEYS:
+                env.buf[key].copy_(rows[key])
+            bound = env.critic_parameter_gradients(critic, act, dq=_dev(dq))
+            torch.cuda.synchronize()
+            assert _all_same(bound, got), (kind, H)
+    critic.close()
+    env.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", NAMES)
+def test_checkpoints_on_the_device(name):
+    import torch
+
+    case = checkpoint_case(name)
+    M = len(case["x"])
+    assert SPLIT < M <= 1680  # two splits: the partial sums and the third launch
+    env = _env(name, 8)
+    critic = DeviceCritic(case["nets"], env)
+    rows, act = _rows(name, case["x"])
+    got = env.critic_parameter_gradients(critic, act, dq=_dev(case["dq"]), rows=rows)
+    # the target form equals the dq form bitwise, with dq formed in numpy float32 from the call's own q by the two stated operations
+    scale = np.float32(1.0 / M)
+    by_target = env.critic_parameter_gradients(critic, act, target=_dev(case["y"]), scale=float(scale), rows=rows)
+    torch.cuda.synchronize()
+    own = ((by_target["q"].cpu().numpy() - case["y"][None, :]).astype(np.float32) * scale).astype(np.float32)
+    by_dq = env.critic_parameter_gradients(critic, act, dq=_dev(own), rows=rows)
+    torch.cuda.synchronize()
+    assert _all_same(by_target, by_dq)
+    for i in (0, 1):
+        for k in CRITIC_ARRAYS:
+            dev = float(np.abs(got["grads"][i][k].cpu().numpy().astype(np.float64) - case["g64"][i][k]).max())
+            dev32 = case["dev32"][i][k]
+            print(f"{name} qf{i} {k}: kernels vs float64 {dev:.3e}, numpy float32 vs float64 {dev32:.3e} (bound {4 * dev32:.3e}) on {M} rows")
+            assert dev <= 4.0 * dev32, (name, i, k, dev, dev32)
+    critic.close()
+    env.close()
+
+
+@pytest.fixture(scope="module")
+def dyn():
+    """The dyn checkpoint on its kept trace rows (two splits): env, critic, rows, actions, dq and one call's result."""
+    case = checkpoint_case("dyn")
+    env = _env("dyn", 8)
+    critic = DeviceCritic(case["nets"], env)
+    rows, act = _rows("dyn", case["x"])
+    dq = _dev(case["dq"])
+    whole = env.critic_parameter_gradients(critic, act, dq=dq, rows=rows)
+    yield dict(env=env, critic=critic, nets=case["nets"], rows=rows, act=act, dq=dq, whole=whole, M=len(case["x"]), y=_dev(case["y"]))
+    critic.close()
+    env.close()
+
+
+@pytest.mark.gpu
+def test_two_calls_agree_and_nothing_depends_on_old_contents(dyn):
+    import torch
+
+    env, critic, rows, act, dq, whole, M = (dyn[k] for k in ("env", "critic", "rows", "act", "dq", "whole", "M"))
+    assert _all_same(env.critic_parameter_gradients(critic, act, dq=dq, rows=rows), whole)
+    results = []
+    for fill in (float("nan"), 0.0):
+        ws = env.critic_gradient_workspace(critic, M)
+        ws.fill_(fill)
+        out = [{k: torch.full_like(v, fill) for k, v in w.items()} for w in whole["grads"]]
+        results.append(env.critic_parameter_gradients(critic, act, dq=dq, rows=rows, out=out, workspace=ws))
+        assert results[-1]["grads"] is out
+    torch.cuda.synchronize()
+    assert _all_same(results[0], results[1]) and _all_same(results[0], whole)
+    assert all(bool(torch.isfinite(results[0]["grads"][i][k]).all()) for i in (0, 1) for k in CRITIC_ARRAYS)
+    # a batch within one split (two launches) as well
+    m = 300
+    part = {k: v[:m] for k, v in rows.items()}
+    a = env.critic_parameter_gradients(critic, act[:m], dq=dq[:, :m].contiguous(), rows=part)
+    ws = env.critic_gradient_workspace(critic, m)
+    ws.fill_(float("nan"))
+    b = env.critic_parameter_gradients(critic, act[:m], dq=dq[:, :m].contiguous(), rows=part, workspace=ws)
+    torch.cuda.synchronize()
+    assert _all_same(a, b)
+
+
+def _raw(dyn, m, pad=64, fill=-12345.0, with_q=True):
+    """A call through the C interface with guard words round every output and the workspace."""
+    import torch
+
+    env, critic, rows, act = (dyn[k] for k in ("env", "critic", "rows", "act"))
+    n, H = critic.in_features, critic.hidden_width
+    sizes = dict(zip(CRITIC_ARRAYS, (H * n, H, H * H, H, H, 1)))
+    big = [{k: torch.full((s + 2 * pad,), fill, dtype=torch.float32, device="cuda:0") for k, s in sizes.items()} for _ in range(2)]
+    q = torch.full((2 * m + 2 * pad,), fill, dtype=torch.float32, device="cuda:0")
+    need = C.c_uint64()
+    assert env.lib.urgym_critic_parameter_gradients_workspace(env._h, critic._c, m, C.byref(need)) == 0 and need.value % 4 == 0
+    ws = torch.full((need.value // 4 + 2 * pad,), fill, dtype=torch.float32, device="cuda:0")
+    cr = _abi.CriticRows(_fp(rows["observation"]), _fp(rows["achieved_goal"]), _fp(rows["desired_goal"]), _fp(act))
+    out = _abi.CriticParamGrads()
+    for i in (0, 1):
+        out.qf[i] = _abi.QNetworkGrad(*[_fp(big[i][k][pad:]) for k in CRITIC_ARRAYS])
+    out.q = _fp(q[pad:]) if with_q else None
+    return dict(sizes=sizes, big=big, q=q, ws=ws, need=need.value, cr=cr, out=out, pad=pad, fill=fill)
+
+
+def _untouched(r):
+    tensors = [t for w in r["big"] for t in w.values()] + [r["q"], r["ws"]]
+    return all(bool((t == r["fill"]).all()) for t in tensors)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("m", (129, SPLIT + 1))
+def test_no_stray_writes(dyn, m):
+    import torch
+
+    env, critic, rows, act, dq = (dyn[k] for k in ("env", "critic", "rows", "act", "dq"))
+    r = _raw(dyn, m, with_q=False)
+    pad, fill = r["pad"], r["fill"]
+    d = dq[:, :m].contiguous()
+    rc = env.lib.urgym_critic_parameter_gradients(env._h, critic._c, C.byref(r["cr"]), m, C.c_void_p(d.data_ptr()), None, 0.0, C.byref(r["out"]),
+                                                  C.c_void_p(r["ws"][pad:].data_ptr()), r["need"], env._stream())
+    assert rc == 0, env.lib.urgym_last_error(env._h)
+    want = env.critic_parameter_gradients(critic, act[:m], dq=d, rows={k: v[:m] for k, v in rows.items()})
+    torch.cuda.synchronize()
+    assert bool((r["q"] == fill).all())  # q is not written when NULL
+    assert bool((r["ws"][:pad] == fill).all()) and bool((r["ws"][pad + r["need"] // 4:] == fill).all())
+    for i in (0, 1):
+        for k, size in r["sizes"].items():
+            t = r["big"][i][k]
+            assert bool((t[:pad] == fill).all()) and bool((t[pad + size:] == fill).all()), (i, k)
+            assert _same(t[pad:pad + size], want["grads"][i][k].reshape(-1)), (i, k)
+
+
+@pytest.mark.gpu
+def test_reload_without_synchronisation(dyn):
+    import torch
+
+    env, nets, rows, act, dq, whole = (dyn[k] for k in ("env", "nets", "rows", "act", "dq", "whole"))
+    swapped = DeviceCritic([nets[1], nets[0]], env)
+    other = env.critic_parameter_gradients(swapped, act, dq=dq, rows=rows)
+    again = DeviceCritic(nets, env)
+    tensors = [{k: _dev(np.asarray(w[k], dtype=np.float32)) for k in CRITIC_ARRAYS} for w in (nets[1], nets[0])]
+    first = env.critic_parameter_gradients(again, act, dq=dq, rows=rows)
+    again.load_parameters(tensors, tau=1.0)
+    reloaded = env.critic_parameter_gradients(again, act, dq=dq, rows=rows)
+    torch.cuda.synchronize()
+    assert _all_same(first, whole) and _all_same(reloaded, other) and not _all_same(reloaded, whole)
+    swapped.close()
+    again.close()
+
+
+@pytest.mark.gpu
+def test_refusals_launch_nothing(dyn):
+    import torch
+
+    env, critic, rows, act, dq, y, whole, M = (dyn[k] for k in ("env", "critic", "rows", "act", "dq", "y", "whole", "M"))
+    m = 129
+    r = _raw(dyn, m)
+    lib, h, s = env.lib, env._h, env._stream()
+    cr, out, ws, need = r["cr"], r["out"], C.c_void_p(r["ws"][r["pad"]:].data_ptr()), r["need"]
+    d, t = C.c_void_p(dq.data_ptr()), C.c_void_p(y.data_ptr())
+    pg = lib.urgym_critic_parameter_gradients
+    wide = [DeviceCritic(exact_critic("dyn", H), env) for H in REFUSED_WIDTHS]
+    size = C.c_uint64(7)
+    no_w1 = _abi.CriticParamGrads()
+    no_w1.qf[0], no_w1.qf[1], no_w1.q = out.qf[0], _abi.QNetworkGrad(out.qf[1].w0, out.qf[1].b0, None, out.qf[1].b1, out.qf[1].w_q, out.qf[1].b_q), out.q
+    calls = [pg(h, None, C.byref(cr), m, d, None, 0.0, C.byref(out), ws, need, s), pg(h, C.c_void_p(1), C.byref(cr), m, d, None, 0.0, C.byref(out), ws, need, s),
+             pg(h, critic._c, None, m, d, None, 0.0, C.byref(out), ws, need, s), pg(h, critic._c, C.byref(cr), 0, d, None, 0.0, C.byref(out), ws, need, s),
+             pg(h, critic._c, C.byref(_abi.CriticRows(None, None, None, cr.action)), m, d, None, 0.0, C.byref(out), ws, need, s),  # bound: count == N
+             pg(h, critic._c, C.byref(_abi.CriticRows(cr.observation, cr.achieved_goal, cr.desired_goal, None)), m, d, None, 0.0, C.byref(out), ws, need, s),
+             pg(h, critic._c, C.byref(cr), m, d, t, 1.0, C.byref(out), ws, need, s),  # both forms
+             pg(h, critic._c, C.byref(cr), m, None, None, 1.0, C.byref(out), ws, need, s),  # neither
+             pg(h, critic._c, C.byref(cr), m, None, t, float("inf"), C.byref(out), ws, need, s),
+             pg(h, critic._c, C.byref(cr), m, None, t, float("nan"), C.byref(out), ws, need, s),
+             pg(h, critic._c, C.byref(cr), m, d, None, 0.0, None, ws, need, s), pg(h, critic._c, C.byref(cr), m, d, None, 0.0, C.byref(no_w1), ws, need, s),
+             pg(h, critic._c, C.byref(cr), m, d, None, 0.0, C.byref(out), None, need, s),  # no workspace
+             pg(h, critic._c, C.byref(cr), m, d, None, 0.0, C.byref(out), ws, need - 4, s),  # a short one
+             pg(h, critic._c, C.byref(cr), _abi.CRITIC_GRADIENTS_MAX_COUNT + 1, d, None, 0.0, C.byref(out), ws, 1 << 40, s),
+             lib.urgym_critic_parameter_gradients_workspace(h, critic._c, _abi.CRITIC_GRADIENTS_MAX_COUNT + 1, C.byref(size)),
+             lib.urgym_critic_parameter_gradients_workspace(h, critic._c, 0, C.byref(size)),
+             lib.urgym_critic_parameter_gradients_workspace(h, critic._c, m, None)]
+    calls += [pg(h, w._c, C.byref(cr), m, d, None, 0.0, C.byref(out), ws, 1 << 40, s) for w in wide]
+    calls += [lib.urgym_critic_parameter_gradients_workspace(h, w._c, m, C.byref(size)) for w in wide]
+    for i, rc in enumerate(calls):
+        assert rc == _abi.ERR_ARG, i
+    assert size.value == 7 and "256" in lib.urgym_last_error(h).decode()
+    torch.cuda.synchronize()
+    assert _untouched(r)  # nothing was launched
+    assert lib.urgym_critic_parameter_gradients_workspace(h, critic._c, _abi.CRITIC_GRADIENTS_MAX_COUNT, C.byref(size)) == 0 and size.value == 592970240
+    assert _all_same(env.critic_parameter_gradients(critic, act, dq=dq, rows=rows), whole)  # the handle is as usable as before
+    for w in wide:
+        w.close()
+
+
+@pytest.mark.gpu
+def test_learner_critic_gradients():
+    """Learners from one seed on the same ring and (seed, draw): the critic gradients of the first update against float64 autograd, and
+    with the option off the same losses as without it, bit for bit."""
+    import torch
+
+    from ur_gym_amd.evaluation import DeviceReplay
+    from ur_gym_amd.training import SAC_DEFAULTS, SACLearner, TorchTwinCritic, _features
+
+    assert SAC_DEFAULTS["device_critic_gradient"] is False
+    env = _env("dyn", 161, seed=3, auto_reset=True)
+    replay = DeviceReplay(env, 4)
+    kw = dict(seed=5, hidden_width=32, batch_size=64)
+    # the action gradient on in both, so that the actor loss's backward pass leaves the critic's .grad alone
+    learners = {"default": SACLearner(env, device_action_gradient=True, **kw),
+                "device": SACLearner(env, device_action_gradient=True, device_critic_gradient=True, **kw)}
+    assert learners["default"].critic_grads is None and isinstance(learners["device"].online, DeviceCritic)
+    learners["default"].collect(replay, 4)
+    dev, ref_max, losses = {}, {}, {}
+    for label, ln in learners.items():
+        gamma = float(ln.hp["gamma"])
+        batch = replay.sample_targets(ln.device_actor, ln.target, 64, 9, 2, gamma, 0.0)
+        alpha = ln.log_ent_coef.detach().exp().double()
+        y = batch["target"].double() - gamma * (~batch["terminated"]).double() * alpha * batch["next_log_prob"].double()
+        critic64 = TorchTwinCritic(ln.critic.qf[0][0].in_features - 6 + 6, 32).to("cuda:0").double()
+        critic64.load_state_dict({k: v.double() for k, v in ln.critic.state_dict().items()})
+        q0, q1 = critic64(_features(batch["observations"]).double(), batch["actions"].double())
+        (0.5 * (((q0 - y) ** 2).mean() + ((q1 - y) ** 2).mean())).backward()
+        losses[label] = ln.update(replay, 9, 2)
+        grads = {k: p.grad.detach().double() for k, p in ln.critic.named_parameters()}
+        dev[label] = {k: float((grads[k] - p.grad).abs().max()) for k, p in critic64.named_parameters()}
+        ref_max[label] = {k: float(p.grad.abs().max()) for k, p in critic64.named_parameters()}
+    if learners["device"].critic_grads is not None:  # the gradient tensors ARE the parameters' .grad
+        assert all(p.grad is g[k] for w, g in zip(learners["device"].critic.tensors(), learners["device"].critic_grads) for k, p in w.items())
+    for k in dev["device"]:
+        ulp = float(np.spacing(np.float32(ref_max["device"][k])))
+        print(f"{k}: device route {dev['device'][k]:.3e}, default route {dev['default'][k]:.3e}, largest gradient {ref_max['device'][k]:.3e}, ulp {ulp:.3e}")
+        assert ref_max["device"][k] == ref_max["default"][k] and ref_max["device"][k] > 0.0
+        assert dev["device"][k] <= 4.0 * dev["default"][k] + ulp, k
+    rel = abs(float(losses["device"]["critic_loss"]) - float(losses["default"]["critic_loss"])) / abs(float(losses["default"]["critic_loss"]))
+    assert rel <= 1e-5, rel  # one loss, two float32 evaluation orders
+    # the option off is the option absent
+    plain = {"absent": SACLearner(env, **kw), "off": SACLearner(env, device_critic_gradient=False, **kw)}
+    out = {label: [ln.update(replay, 9 + j, 2 + j) for j in range(2)] for label, ln in plain.items()}
+    torch.cuda.synchronize()
+    for a, b in zip(out["absent"], out["off"]):
+        assert all(_same(a[k].reshape(1), b[k].reshape(1)) for k in a)
+    assert plain["off"].online is None and plain["off"].critic_grads is None
+    for ln in list(learners.values()) + list(plain.values()):
+        ln.close()
+    env.close()

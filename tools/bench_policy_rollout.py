@@ -40,6 +40,12 @@ not slower than torch at both M.  Also one SACLearner.update at batch 256 with a
 256 are not measured: the call refuses them.
     python tools/bench_policy_rollout.py --action-gradient --out profiles/policy_rollout/dyn65536_action_gradient.json
 
+--critic-gradient measures urgym_critic_parameter_gradients on the checkpoint's critic (H = 256) at M = 256 and
+M = --num-envs rows: alternating windows of (1) the call (its two or three launches, `target` form, preallocated outputs and workspace)
+and (2) torch float32 for the same quantities: critic forward, loss, backward().  Bar: the call is not slower than torch at either M
+beyond the spread of the windows.  Also one SACLearner.update at batch 256: default, device_action_gradient, both options.
+    python tools/bench_policy_rollout.py --critic-gradient --windows 6 --launches 100 --out profiles/policy_rollout/dyn65536_critic_gradient.json
+
 With --refresh: what it costs to hand new weights to a device actor / critic, at hidden width 256 and 512.
 `actor_load`, `critic_load_tau1` and `critic_load_polyak` (tau = 0.005) are load_parameters from device tensors, one launch each;
 `*_host_route` is the only route there was before: every tensor .cpu().numpy(), destroy and create the object (the actor's head by
@@ -510,6 +516,105 @@ def action_gradient_mode(args):
             f.write(line + "\n")
 
 
+def critic_gradient_mode(args):
+    import torch
+    import torch.nn.functional as F
+
+    from ur_gym_amd import make_vec
+    from ur_gym_amd.evaluation import CRITIC_ARRAYS, DeviceCritic, DeviceReplay
+    from ur_gym_amd.training import SACLearner
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_policy_rollout.py measures on a GPU; none is visible")
+    dev, n, kind = "cuda:0", args.num_envs, ACTOR_NPZ[args.env]
+    golden = os.path.join(ROOT, "tests", "golden")
+    env = make_vec(args.env, num_envs=n, device=dev, seed=0, auto_reset=True)
+    env.reset(seed=0)
+    paths = [os.path.join(golden, "critics", f"critic_{kind}_qf{i}.npz") for i in (0, 1)]
+    critic = DeviceCritic.load(paths, env)
+    tw = [{k: torch.from_numpy(np.ascontiguousarray(np.load(p)[k], dtype=np.float32)).to(dev).requires_grad_(True) for k in CRITIC_ARRAYS} for p in paths]
+    for _ in range(20):
+        env.step(torch.rand((n, 6), device=dev) * 2.0 - 1.0)
+    sync = lambda: torch.cuda.synchronize(env.device)  # noqa: E731
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def window(fn, count):
+        sync()
+        e0.record()
+        for _ in range(count):
+            fn()
+        e1.record()
+        sync()
+        return e0.elapsed_time(e1) * 1e3 / count
+
+    sizes = {}
+    for m in sorted({256, n}):
+        rows = {k: env.buf[k][:m].clone() for k in env.ROW_KEYS}
+        actions = torch.rand((m, 6), device=dev) * 2.0 - 1.0
+        y = torch.randn((m,), device=dev)
+        x = torch.cat([rows["achieved_goal"], rows["desired_goal"], rows["observation"], actions], dim=1)
+        out = [{k: torch.empty_like(v) for k, v in w.items()} for w in tw]
+        ws = env.critic_gradient_workspace(critic, m)
+
+        def torch_route():  # critic forward, loss, backward(): the same quantities in torch float32
+            q = []
+            for w in tw:
+                w_grad = [w[k] for k in CRITIC_ARRAYS]
+                for p in w_grad:
+                    p.grad = None
+                h = F.relu(F.linear(x, w["q_0_weight"], w["q_0_bias"]))
+                h = F.relu(F.linear(h, w["q_2_weight"], w["q_2_bias"]))
+                q.append(F.linear(h, w["q_4_weight"], w["q_4_bias"])[:, 0])
+            (0.5 * (((q[0] - y) ** 2).mean() + ((q[1] - y) ** 2).mean())).backward()
+
+        kinds = {"gradients": lambda: env.critic_parameter_gradients(critic, actions, target=y, scale=1.0 / m, rows=rows, out=out, workspace=ws),
+                 "torch": torch_route}
+        for fn in kinds.values():
+            for _ in range(5):
+                fn()
+        sync()
+        agree = {k: {"max_abs_difference_from_torch": float((out[0][k] - tw[0][k].grad).abs().max()), "g_abs_max": float(tw[0][k].grad.abs().max())}
+                 for k in CRITIC_ARRAYS}
+        windows = {k: [] for k in kinds}
+        for _ in range(args.windows):
+            for name, fn in kinds.items():
+                windows[name].append(window(fn, args.launches))
+        med = {k: float(np.median(v)) for k, v in windows.items()}
+        spread = float(max(windows["torch"]) - min(windows["torch"]))
+        sizes[str(m)] = {"us_median": med, "us_windows": {k: [round(v, 3) for v in vs] for k, vs in windows.items()}, "torch_us_spread": spread,
+                         "launches_per_call": 2 if m <= 1024 else 3, "workspace_bytes": int(ws.numel()) * 4,
+                         "not_slower_than_torch": med["gradients"] <= med["torch"] + spread, "speedup_over_torch": med["torch"] / med["gradients"],
+                         "qf0": agree}
+    critic.close()
+    updates = {}
+    for label, options in (("parent_route", {}), ("device_action_gradient", dict(device_action_gradient=True)),
+                           ("both_options", dict(device_action_gradient=True, device_critic_gradient=True))):
+        learner = SACLearner(env, seed=0, batch_size=256, hidden_width=256, **options)
+        replay = DeviceReplay(env, 4)
+        learner.collect(replay, 4)
+        draw = [0]
+
+        def one_update():
+            draw[0] += 1
+            learner.update(replay, 1, draw[0])
+
+        for _ in range(5):
+            one_update()
+        w = [window(one_update, 20) for _ in range(args.windows)]
+        updates[label] = {"us_median": float(np.median(w)), "us_windows": [round(v, 2) for v in w]}
+        learner.close()
+    result = {"tool": "bench_policy_rollout --critic-gradient", "env": args.env, "hidden_width": critic.hidden_width, "windows": args.windows,
+              "launches_per_window": args.launches, "device": torch.cuda.get_device_name(0), "rows": sizes,
+              "not_slower_than_torch": all(v["not_slower_than_torch"] for v in sizes.values()), "learner_update_batch256": updates}
+    env.close()
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--env", default="UR5DynReach-v1", choices=sorted(ACTOR_NPZ))
@@ -531,10 +636,13 @@ def main():
     ap.add_argument("--capacity", type=int, default=256, help="--replay: slots of the ring")
     ap.add_argument("--refresh", action="store_true", help="measure reloading actor / critic weights from device tensors against the host route and a copy (see above)")
     ap.add_argument("--action-gradient", action="store_true", help="measure the critics' action gradient launch against critic_kernel and torch autograd (see above)")
+    ap.add_argument("--critic-gradient", action="store_true", help="measure the critics' parameter gradients (two or three launches) against torch autograd (see above)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.action_gradient:
         return action_gradient_mode(args)
+    if args.critic_gradient:
+        return critic_gradient_mode(args)
     if args.critic:
         return critic_mode(args)
     if args.replay:

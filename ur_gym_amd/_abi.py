@@ -194,6 +194,18 @@ class CriticGradOut(C.Structure):
     _fields_ = [(name, C.POINTER(C.c_float)) for name in ("dq_da", "dqmin_da", "q", "q_min")]
 
 
+class QNetworkGrad(C.Structure):
+    """urgym_q_network_grad: six DEVICE pointers the gradients of one Q-network are written to, torch's [out][in] layout."""
+    _fields_ = [(name, C.POINTER(C.c_float)) for name in ("w0", "b0", "w1", "b1", "w_q", "b_q")]
+
+
+class CriticParamGrads(C.Structure):
+    """urgym_critic_param_grads: where urgym_critic_parameter_gradients writes; q may be NULL."""
+    _fields_ = [("qf", QNetworkGrad * 2), ("q", C.POINTER(C.c_float))]
+
+
+CRITIC_GRADIENTS_MAX_COUNT = 65536  # URGYM_CRITIC_GRADIENTS_MAX_COUNT
+
 REPLAY_TAG = 0x52504C00  # word 3 of the Philox counter of urgym_replay_sample's index draw
 
 # urgym_replay_ring after capacity_steps / reserved0: name -> (ctype of element, shape given (C, N, obs_dim, goal_dim), required)
@@ -262,6 +274,8 @@ EXPORTED_SYMBOLS = [
     "urgym_critic_destroy",
     "urgym_critic_evaluate",
     "urgym_critic_action_gradient",
+    "urgym_critic_parameter_gradients_workspace",
+    "urgym_critic_parameter_gradients",
     "urgym_actor_sample_rows",
     "urgym_rollout_collect",
     "urgym_replay_sample",

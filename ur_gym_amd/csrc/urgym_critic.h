@@ -56,4 +56,27 @@ bool critic_grad_supported(Critic* c);
 // ONE launch on `s`; the caller has validated `call` and critic_grad_supported(c)
 void critic_grad_launch(Critic* c, const CriticGradCall& call, hipStream_t s);
 
+// The parameter gradients of both networks summed over M rows (urgym_critic_backward.hip): the inputs of CriticCall, the upstream
+// gradient (exactly one of dq and target), the twelve outputs in the order of urgym_q_network_dev, the optional q and the caller's
+// workspace (all DEVICE pointers).
+struct CriticBackwardCall {
+  int M, obs_dim, goal_dim;
+  const float *observation, *achieved_goal, *desired_goal, *action;  // [M][obs_dim], [M][goal_dim], [M][goal_dim], [M][6]
+  const float* dq;      // [2][M] or null
+  const float* target;  // [M] or null: dq = (q - target) * scale
+  float scale;
+  float* grad[2][6];    // per network: W0, b0, W1, b1, w_q, b_q
+  float* q;             // [2][M] or null
+  float* workspace;     // critic_backward_workspace_bytes(c, M), 16-byte aligned
+};
+
+// built for the widths of the action gradient (CRITIC_GRAD_MAX_HIDDEN)
+bool critic_backward_supported(Critic* c);
+constexpr int CRITIC_BACKWARD_MAX_COUNT = 65536;
+uint64_t critic_backward_workspace_bytes(Critic* c, int count);
+// the launches of one call: 2 up to 1024 rows, 3 above (urgym_critic_backward.hip)
+int critic_backward_launches(int count);
+// on `s`; the caller has validated `call` and critic_backward_supported(c)
+void critic_backward_launch(Critic* c, const CriticBackwardCall& call, hipStream_t s);
+
 }  // namespace urgym

@@ -2561,6 +2561,71 @@ int urgym_critic_action_gradient(void* handle, void* critic, const urgym_critic_
   return URGYM_OK;
 }
 
+// the checks urgym_critic_parameter_gradients and its workspace query share: the critic is one of this handle's, takes this env kind's
+// features, is no wider than the kernels are built for, and count is within [1, URGYM_CRITIC_GRADIENTS_MAX_COUNT]
+static int backward_critic(Handle* h, void* critic, int count, const char* who, Critic** out) {
+  static_assert(URGYM_CRITIC_GRADIENTS_MAX_COUNT == CRITIC_BACKWARD_MAX_COUNT, "include/urgym.h");
+  char msg[200];
+  const char* what = nullptr;
+  Critic* c = find_critic(h, critic);
+  if (!c) what = "not a critic of this handle (critics belong to the handle they were created with)";
+  else if (critic_in_features(c) != actor_features(h) + 6) what = "the critic does not take this env kind's features";
+  else if (!critic_backward_supported(c)) what = "the gradient kernels are built for hidden widths up to 256";
+  else if (count <= 0) what = "count must be positive";
+  else if (count > CRITIC_BACKWARD_MAX_COUNT) what = "count is above URGYM_CRITIC_GRADIENTS_MAX_COUNT (65536)";
+  if (what) {
+    snprintf(msg, sizeof(msg), "%s: %s", who, what);
+    return fail(h, URGYM_ERR_ARG, msg);
+  }
+  *out = c;
+  return URGYM_OK;
+}
+
+int urgym_critic_parameter_gradients_workspace(void* handle, void* critic, int count, uint64_t* bytes) {
+  const char* who = "urgym_critic_parameter_gradients_workspace";
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (!bytes) return fail(h, URGYM_ERR_ARG, "urgym_critic_parameter_gradients_workspace: null bytes");
+  Critic* c = nullptr;
+  if (int rc = backward_critic(h, critic, count, who, &c)) return rc;
+  *bytes = critic_backward_workspace_bytes(c, count);
+  return URGYM_OK;
+}
+
+int urgym_critic_parameter_gradients(void* handle, void* critic, const urgym_critic_rows* rows, int count, const float* dq, const float* target, float scale, const urgym_critic_param_grads* out, void* workspace, uint64_t workspace_bytes, void* stream) {
+  const char* who = "urgym_critic_parameter_gradients";
+  Handle* h = (Handle*)handle;
+  if (int rc = enter_bound(h)) return rc;
+  Critic* c = nullptr;
+  CriticBackwardCall call;
+  memset(&call, 0, sizeof(call));
+  if (int rc = backward_critic(h, critic, count, who, &c)) return rc;
+  if (int rc = resolve_rows(h, rows, count, who, &call.observation, &call.achieved_goal, &call.desired_goal)) return rc;
+  if (!rows->action) return fail(h, URGYM_ERR_ARG, "urgym_critic_parameter_gradients: rows->action is null");
+  if ((dq != nullptr) == (target != nullptr)) return fail(h, URGYM_ERR_ARG, "urgym_critic_parameter_gradients: exactly one of dq and target must be given");
+  if (target && !(fabsf(scale) < INFINITY)) return fail(h, URGYM_ERR_ARG, "urgym_critic_parameter_gradients: scale must be finite");
+  if (!out) return fail(h, URGYM_ERR_ARG, "urgym_critic_parameter_gradients: null out");
+  for (int net = 0; net < 2; net++) {
+    const urgym_q_network_grad& g = out->qf[net];
+    float* one[6] = {g.w0, g.b0, g.w1, g.b1, g.w_q, g.b_q};
+    for (int i = 0; i < 6; i++) {
+      if (!one[i]) return fail(h, URGYM_ERR_ARG, "urgym_critic_parameter_gradients: a gradient pointer is null (all twelve are required)");
+      call.grad[net][i] = one[i];
+    }
+  }
+  if (!workspace) return fail(h, URGYM_ERR_ARG, "urgym_critic_parameter_gradients: null workspace");
+  if ((uintptr_t)workspace % 16 != 0) return fail(h, URGYM_ERR_ARG, "urgym_critic_parameter_gradients: the workspace must be 16-byte aligned");
+  if (workspace_bytes < critic_backward_workspace_bytes(c, count))
+    return fail(h, URGYM_ERR_ARG, "urgym_critic_parameter_gradients: the workspace is smaller than urgym_critic_parameter_gradients_workspace reports");
+  call.M = count, call.obs_dim = h->obs_dim, call.goal_dim = h->goal_dim;
+  call.action = rows->action;
+  call.dq = dq, call.target = target, call.scale = target ? scale : 0.0f;
+  call.q = out->q, call.workspace = (float*)workspace;
+  critic_backward_launch(c, call, (hipStream_t)stream);
+  HIP_TRY(h, hipGetLastError());
+  return URGYM_OK;
+}
+
 int urgym_probe_closest(void* handle, int count, const int* type_a, const double* par_a, const double* pose_a, const int* type_b,
                         const double* par_b, const double* pose_b, double threshold, double* out_dist, int* out_info, void* stream) {
   Handle* h = (Handle*)handle;

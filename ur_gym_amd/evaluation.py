@@ -400,6 +400,31 @@ class TwinCritic:
         dqmin_da = np.where((q[1] < q[0])[:, None], dq_da[1], dq_da[0])
         return dq_da, dqmin_da, q
 
+    def parameter_gradients(self, achieved_goal, desired_goal, observation, action, dq=None, target=None, scale=None):
+        """(grads, q) in float32 as include/urgym.h states urgym_critic_parameter_gradients: `grads` a list of two dicts keyed by
+        CRITIC_ARRAYS, the gradients of a loss with d loss / d q_i[m] = dq[i][m] summed over the rows; q [2, M].  Exactly one of `dq`
+        [2, M] and `target` [M] with `scale` is given; with `target`, dq = (q - target) * scale in two rounded float32 operations.
+        A pre-activation of exactly 0 has derivative 0.  (The order of the sums is numpy's, not the kernel's.)"""
+        if (dq is None) == (target is None):
+            raise ValueError("exactly one of dq and target must be given")
+        x = np.concatenate([achieved_goal, desired_goal, observation, action], axis=1).astype(np.float32)
+        assert x.shape[1] == self.in_features, (x.shape, self.in_features)
+        f, zero = np.float32, np.float32(0.0)
+        grads, qs = [], []
+        for i, w in enumerate(self.qf):
+            z1 = x @ w["q_0_weight"].T + w["q_0_bias"]
+            h1 = np.maximum(z1, zero)
+            z2 = h1 @ w["q_2_weight"].T + w["q_2_bias"]
+            h2 = np.maximum(z2, zero)
+            q = (h2 @ w["q_4_weight"].T + w["q_4_bias"])[:, 0].astype(f)
+            up = np.asarray(dq[i], f) if dq is not None else ((q - np.asarray(target, f)).astype(f) * f(scale)).astype(f)
+            d2 = np.where(z2 > 0.0, up[:, None] * w["q_4_weight"][0][None, :], zero).astype(f)
+            d1 = np.where(z1 > 0.0, d2 @ w["q_2_weight"], zero).astype(f)
+            g = (d1.T @ x, d1.sum(axis=0), d2.T @ h1, d2.sum(axis=0), (up @ h2)[None, :], up.sum(keepdims=True))
+            grads.append({k: np.asarray(v, dtype=f) for k, v in zip(CRITIC_ARRAYS, g)})
+            qs.append(q)
+        return grads, np.stack(qs)
+
     @staticmethod
     def target(q0, q1, reward, gamma, terminated=None, log_prob=None, ent_coef=0.0):
         """(q_min, target) in float32, operation by operation as urgym_critic_evaluate does:

@@ -13,6 +13,10 @@ minibatch gather on the HIP kernels, and gradients and optimisers in torch autog
     With ``device_action_gradient=True`` the actor loss does not run the torch critic a second time: an ONLINE DeviceCritic is reloaded
     after the critic's Adam step (tau = 1) and one launch of the gradient kernel gives g = d min_i Q_i / d a and q_min at the policy's
     action; ``(ent_coef * log_prob - (action_pi * g).sum(1)).mean()`` has the actor loss's gradient with respect to the actor.
+    With ``device_critic_gradient=True`` the critic loss does not run the torch critic either: the online DeviceCritic (shared with the
+    option above) holds the torch critic's parameters when ``update`` starts, ``env.critic_parameter_gradients(target=y, scale=1/M)``
+    writes d loss / d parameters into preallocated tensors that ARE the parameters' ``.grad``, the loss value is formed from the
+    returned q, Adam steps, and the online critic is reloaded.
     Neither synchronises with the host.  There is no logging, no callback and no checkpoint format here; tools/train_sac.py runs it.
 """
 import numpy as np
@@ -23,7 +27,7 @@ from .evaluation import ACTOR_ARRAYS, CRITIC_ARRAYS, LOG_STD_ARRAYS, LOG_STD_MAX
 
 # SB3's SAC defaults where train.py does not set them (tests/golden/critics/sac_hyperparameters.json has the checkpoints' gamma, tau)
 SAC_DEFAULTS = dict(gamma=0.95, tau=0.005, learning_rate=1e-4, batch_size=256, learning_starts=100, hidden_width=256, target_entropy=-6.0,
-                    ent_coef_init=1.0, device_action_gradient=False)
+                    ent_coef_init=1.0, device_action_gradient=False, device_critic_gradient=False)
 
 
 def _mlp(n_in, hidden, n_out=None):
@@ -107,7 +111,15 @@ class SACLearner:
         self.device_actor = DeviceActor(host_arrays(self.actor.tensors()), env)
         self.target = DeviceCritic(host_arrays(self.critic.tensors()), env)  # starts as a copy of the online critic
         # the online critic on the device, only where the actor loss takes its action gradient from the kernel
-        self.online = DeviceCritic(host_arrays(self.critic.tensors()), env) if hp["device_action_gradient"] else None
+        self.online = DeviceCritic(host_arrays(self.critic.tensors()), env) if hp["device_action_gradient"] or hp["device_critic_gradient"] else None
+        # with device_critic_gradient the critic parameters' .grad are tensors of the learner's, written by the gradient kernels
+        self.critic_grads = self.critic_workspace = None
+        if hp["device_critic_gradient"]:
+            self.critic_grads = [{k: torch.zeros_like(p) for k, p in w.items()} for w in self.critic.tensors()]
+            for w, g in zip(self.critic.tensors(), self.critic_grads):
+                for k, p in w.items():
+                    p.grad = g[k]
+            self.critic_workspace = env.critic_gradient_workspace(self.online, int(hp["batch_size"]))
         self.env_steps = 0  # per env; decides between the warm-up and the policy
         self.draw = 0       # draw index of the next collection pass
 
@@ -139,19 +151,28 @@ class SACLearner:
         ent_loss.backward()
         self.ent_opt.step()
 
-        q0, q1 = self.critic(x, batch["actions"])
-        critic_loss = 0.5 * (((q0 - y) ** 2).mean() + ((q1 - y) ** 2).mean())
-        self.critic_opt.zero_grad(set_to_none=True)
-        critic_loss.backward()
-        self.critic_opt.step()
+        if self.critic_grads is None:
+            q0, q1 = self.critic(x, batch["actions"])
+            critic_loss = 0.5 * (((q0 - y) ** 2).mean() + ((q1 - y) ** 2).mean())
+            self.critic_opt.zero_grad(set_to_none=True)
+            critic_loss.backward()
+            self.critic_opt.step()
+        else:
+            # the online DeviceCritic holds the torch critic's parameters here (loaded at construction and after every Adam step)
+            got = self.env.critic_parameter_gradients(self.online, batch["actions"], target=y, scale=1.0 / x.shape[0], rows=batch["observations"],
+                                                      out=self.critic_grads, workspace=self.critic_workspace)
+            critic_loss = 0.5 * (((got["q"][0] - y) ** 2).mean() + ((got["q"][1] - y) ** 2).mean())
+            self.critic_opt.step()  # on the .grad tensors the launches wrote
+            self.online.load_parameters(self.critic.tensors(), tau=1.0)
 
         self.actor_opt.zero_grad(set_to_none=True)
-        if self.online is None:
+        if not hp["device_action_gradient"]:
             q_pi = torch.min(*self.critic(x, action_pi))
             actor_loss = (ent_coef * log_prob - q_pi).mean()
             actor_loss.backward()  # also fills the critic's gradients, which its next zero_grad discards
         else:
-            self.online.load_parameters(self.critic.tensors(), tau=1.0)
+            if self.critic_grads is None:
+                self.online.load_parameters(self.critic.tensors(), tau=1.0)
             grad = self.env.critic_action_gradient(self.online, action_pi.detach(), rows=batch["observations"])
             (ent_coef * log_prob - (action_pi * grad["dqmin_da"]).sum(1)).mean().backward()  # through the torch actor only
             actor_loss = (ent_coef * log_prob.detach() - grad["q_min"]).mean()

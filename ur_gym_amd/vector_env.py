@@ -303,6 +303,59 @@ class UR5ReachVectorEnv:
         _native.check(self.lib.urgym_critic_action_gradient(self._h, critic._c, C.byref(cr), count, C.byref(out), self._stream()), self._h)
         return res
 
+    def critic_gradient_workspace(self, critic, count):
+        """A fresh workspace for ``critic_parameter_gradients`` on `count` rows: a float32 device tensor of the size the library reports."""
+        size = C.c_uint64()
+        _native.check(self.lib.urgym_critic_parameter_gradients_workspace(self._h, critic._c, int(count), C.byref(size)), self._h)
+        return torch.empty(((size.value + 3) // 4,), dtype=torch.float32, device=self.device)
+
+    def critic_parameter_gradients(self, critic, actions, *, dq=None, target=None, scale=None, rows=None, out=None, workspace=None):
+        """The gradients of a loss on both Q-networks of `critic` with respect to their parameters, summed over the rows
+        (urgym_critic_parameter_gradients: two launches up to 1024 rows, three above).  The upstream gradient d loss / d q is either
+        `dq` [2, ...] or ``(q - target) * scale`` with `target` [...] and the call's own q (``scale = 1 / rows`` gives SB3's critic
+        loss).  Returns a dict: ``grads``, a list of two dicts keyed by CRITIC_ARRAYS (tensors shaped like the parameters, so a
+        parameter's ``.grad`` can be handed in through `out`, a list of two such dicts), and ``q`` [2, ...].  `workspace`: a float32 device tensor from
+        ``critic_gradient_workspace`` (allocated where not given).  `rows` and the leading shapes are ``critic_values``'; nothing is
+        synchronised, and the sums have a fixed order: two calls give the same bits."""
+        from .evaluation import CRITIC_ARRAYS
+
+        if getattr(critic, "env", None) is not self or not getattr(critic, "_c", None):
+            raise ValueError("critic must be a live DeviceCritic loaded for this environment (DeviceCritic.load(paths, env))")
+        if (dq is None) == (target is None):
+            raise ValueError("exactly one of dq and target must be given")
+        if target is not None and scale is None:
+            raise ValueError("target needs scale (1 / rows for the mean squared error of SB3's critic loss)")
+        cr, lead, keep = self._rows(rows, action=actions)
+        count = int(np.prod(lead))
+        up = torch.as_tensor(dq if dq is not None else target, device=self.device)
+        if up.dtype != torch.float32 or not up.is_contiguous():
+            up = up.to(torch.float32).contiguous()
+        want = ((2,) + lead) if dq is not None else lead
+        if tuple(up.shape) != want:
+            raise ValueError(f"{'dq' if dq is not None else 'target'} must have shape {want}, got {tuple(up.shape)}")
+        n, H = critic.in_features, critic.hidden_width
+        shapes = dict(zip(CRITIC_ARRAYS, ((H, n), (H,), (H, H), (H,), (1, H), (1,))))
+        if out is None:
+            out = [{k: torch.empty(sh, dtype=torch.float32, device=self.device) for k, sh in shapes.items()} for _ in range(2)]
+        grads = _abi.CriticParamGrads()
+        for i, w in enumerate(out):
+            for k in CRITIC_ARRAYS:
+                t = w[k]
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != torch.device(self.device) or tuple(t.shape) != shapes[k]:
+                    raise ValueError(f"out[{i}][{k!r}] must be a contiguous float32 tensor of shape {shapes[k]} on {self.device}")
+            grads.qf[i] = _abi.QNetworkGrad(*[C.cast(w[k].data_ptr(), C.POINTER(C.c_float)) for k in CRITIC_ARRAYS])
+        q = torch.empty((2,) + lead, dtype=torch.float32, device=self.device)
+        grads.q = C.cast(q.data_ptr(), C.POINTER(C.c_float))
+        if workspace is None:
+            workspace = self.critic_gradient_workspace(critic, count)
+        if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.float32 or not workspace.is_contiguous() or workspace.device != torch.device(self.device):
+            raise ValueError(f"workspace must be a contiguous float32 tensor on {self.device} (critic_gradient_workspace)")
+        ptr = C.c_void_p(up.data_ptr())
+        _native.check(self.lib.urgym_critic_parameter_gradients(self._h, critic._c, C.byref(cr), count, ptr if dq is not None else None,
+                                                                None if dq is not None else ptr, float(scale or 0.0), C.byref(grads),
+                                                                C.c_void_p(workspace.data_ptr()), workspace.numel() * 4, self._stream()), self._h)
+        return {"grads": out, "q": q}
+
     def policy_actions(self, actor, out=None, sample=None, rows=None):
         """model.predict(obs, deterministic=True) (model_test.py:41) for all envs, by the HIP actor kernel, from the live
         observation buffers: float32 [N, 6] on the device.
