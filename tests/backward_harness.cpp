@@ -10,22 +10,26 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <algorithm>
+#include <atomic>
+#include <string>
+#include <thread>
 #include <vector>
 
 #include "../ur_gym_amd/csrc/urgym_backward_map.h"
 
 using namespace urgym;
 
-static int failures = 0;
-#define CHECK(cond, ...)                         \
-  do {                                           \
-    if (!(cond)) {                               \
-      if (failures++ < 20) {                     \
-        printf("FAIL %s: ", #cond);              \
-        printf(__VA_ARGS__);                     \
-        printf("\n");                            \
-      }                                          \
-    }                                            \
+static std::atomic<int> failures{0};  // the cases run on several threads: one printf per message
+#define CHECK(cond, ...)                            \
+  do {                                              \
+    if (!(cond)) {                                  \
+      if (failures++ < 20) {                        \
+        char msg[256];                              \
+        snprintf(msg, sizeof msg, __VA_ARGS__);     \
+        printf("FAIL %s: %s\n", #cond, msg);        \
+      }                                             \
+    }                                               \
   } while (0)
 
 struct Marks {
@@ -38,7 +42,7 @@ struct Marks {
   }
 };
 
-static void run_case(int in, int H, int count) {
+static std::string run_case(int in, int H, int count) {
   const BwDims d = bw_dims(in, H, count);
   const int HT = d.HP / 32;
   CHECK(d.x_off % 4 == 0 && d.dq_off % 4 == 0 && d.partial_off % 4 == 0, "float4 alignment");
@@ -171,22 +175,44 @@ static void run_case(int in, int H, int count) {
   }
   for (int net = 0; net < 2; net++)
     for (size_t i = 0; i < d.P; i++) CHECK(out[net].n[i] == 1, "output float %zu of network %d written %d times", i, net, out[net].n[i]);
-  printf("backward in=%d H=%d count=%d floats=%zu splits=%d launches=%d\n", in, H, count, d.floats, d.S, d.S > 1 ? 3 : 2);
+  char line[160];
+  snprintf(line, sizeof line, "backward in=%d H=%d count=%d floats=%zu splits=%d launches=%d\n", in, H, count, d.floats, d.S, d.S > 1 ? 3 : 2);
+  return line;
 }
 
 int main() {
-  const int ins[4] = {36, 38, 47, 53}, widths[4] = {32, 128, 160, 256}, counts[9] = {1, 33, 128, 129, 417, 1023, 1024, 1025, 2049};
-  int cases = 0;
+  const int ins[4] = {36, 38, 47, 53}, widths[4] = {32, 128, 160, 256}, counts[11] = {1, 33, 128, 129, 417, 1023, 1024, 1025, 2049, 3072, 4513};
+  struct Case {
+    int in, H, count;
+  };
+  std::vector<Case> todo;
   for (int in : ins)
     for (int H : widths)
-      for (int count : counts) run_case(in, H, count), cases++;
+      for (int count : counts) todo.push_back({in, H, count});
+  // 64 splits, with a last split of one row and at the largest count: at H = 32 only.  The enumeration visits every float of the
+  // workspace several times; at H = 256 these two cases alone take half a minute under the sanitizers.
+  for (int count : {63 * BW_SPLIT_ROWS + 1, BW_MAX_COUNT}) todo.push_back({53, 32, count});
+  // the cases are independent: a few threads take them from one list, the two longest (the last two) first; the lines are printed in the list's order
+  const int cases = (int)todo.size();
+  std::vector<std::string> lines(cases);
+  std::atomic<int> next{0};
+  auto worker = [&] {
+    for (int k; (k = next++) < cases;) {
+      const int c = k < 2 ? cases - 2 + k : k - 2;
+      lines[c] = run_case(todo[c].in, todo[c].H, todo[c].count);
+    }
+  };
+  std::vector<std::thread> pool;
+  for (unsigned t = 0; t < std::min(8u, std::max(1u, std::thread::hardware_concurrency())); t++) pool.emplace_back(worker);
+  for (auto& t : pool) t.join();
+  for (const auto& l : lines) fputs(l.c_str(), stdout);
   // the size include/urgym.h states, and the largest offsets in size_t (no enumeration at this size)
   const BwDims big = bw_dims(53, 256, BW_MAX_COUNT);
   printf("workspace in=53 H=256 count=%d bytes=%zu\n", BW_MAX_COUNT, big.floats * sizeof(float));
   CHECK(bw_offset(big, 1, BW_D1, BW_MAX_COUNT - 1, big.HP - 1) + 1 == big.x_off, "last array float");
   CHECK(bw_partial_offset(big, big.S - 1, 1) + big.P == big.floats, "last partial float");
   if (failures) {
-    printf("FAIL %d checks\n", failures);
+    printf("FAIL %d checks\n", failures.load());
     return 1;
   }
   printf("ok %d\n", cases);

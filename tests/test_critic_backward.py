@@ -94,6 +94,24 @@ def exact_dq(kind, n):
     return (rng.integers(-1, 2, (2, n)) * DQ_UNIT).astype(np.float32)
 
 
+def exact_target(nets, kind, H, n, scale, live_tail=False, pool=4):
+    """The target form on exact numbers: the n of `pool` x n candidate rows on which the float64 q_0 and q_1 lie closest, y a few grid steps
+    from q_0, so that q_i - y are small multiples of the grid, dq = (q - y) * scale is exact and the sums stay small (the caller
+    asserts them below 2^24 units of GRID * scale).  Returns x, y (float32), the float64 q [2, n] and dq [2, n].  With `live_tail` the
+    last row's step is chosen so that its dq is nonzero in both networks."""
+    cand = exact_inputs(kind, pool * n)
+    qc = np.stack([forward_f64(w, cand)[2] for w in nets])
+    pick = np.sort(np.argsort(np.abs(qc[1] - qc[0]), kind="stable")[:n])
+    x_t, q64_t = cand[pick], qc[:, pick]
+    k = np.random.default_rng([n, H, 19]).integers(-2, 3, n)
+    if live_tail:
+        k[-1] = next(c for c in (1, 2, -1, -2) if q64_t[1, -1] - q64_t[0, -1] + c * GRID != 0.0)
+    y = (q64_t[0] - k * GRID).astype(np.float32)
+    assert np.array_equal(y.astype(np.float64), q64_t[0] - k * GRID)
+    dq_t = (q64_t - y.astype(np.float64)[None, :]) * scale
+    return x_t, y, q64_t, dq_t
+
+
 def forward_f64(w, x):
     w = {k: np.asarray(v, dtype=np.float64) for k, v in w.items()}
     x = x.astype(np.float64)
@@ -243,17 +261,21 @@ def test_index_arithmetic_on_the_host_under_sanitizers():
     src = os.path.join(HERE, "backward_harness.cpp")
     deps = [src, os.path.join(CSRC, "urgym_backward_map.h")]
     if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe, src])
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe, src])
     run = subprocess.run([exe], capture_output=True, text=True)
     out = run.stdout
     assert run.returncode == 0 and "FAIL" not in out and "runtime error" not in run.stderr, (out[-2000:], run.stderr[-2000:])
     lines = out.splitlines()
-    counts = (1, 33, 128, 129, 417, SPLIT - 1, SPLIT, SPLIT + 1, 2 * SPLIT + 1)
-    assert lines[-1] == f"ok {4 * 4 * len(counts)}"
+    counts = (1, 33, 128, 129, 417, SPLIT - 1, SPLIT, SPLIT + 1, 2 * SPLIT + 1, 3 * SPLIT, 4 * SPLIT + 417)
+    cap_counts = (63 * SPLIT + 1, _abi.CRITIC_GRADIENTS_MAX_COUNT)  # 64 splits: in = 53, H = 32 only (H = 256 takes half a minute here)
+    assert lines[-1] == f"ok {4 * 4 * len(counts) + len(cap_counts)}"
     for n_in in IN_FEATURES.values():
         for H in GPU_WIDTHS:
             for count in counts:
                 assert any(l.startswith(f"backward in={n_in} H={H} count={count} ") for l in lines), (n_in, H, count)
+    for count in cap_counts:
+        assert any(l.startswith(f"backward in=53 H=32 count={count} ") and l.endswith("splits=64 launches=3") for l in lines), count
+    assert any(l.startswith(f"backward in=53 H=256 count={4 * SPLIT + 417} ") and l.endswith("splits=5 launches=3") for l in lines)
     # the launches and the size include/urgym.h states
     assert any(l.startswith(f"backward in=53 H=256 count={SPLIT} ") and l.endswith("splits=1 launches=2") for l in lines)
     assert any(l.startswith(f"backward in=53 H=256 count={SPLIT + 1} ") and l.endswith("splits=2 launches=3") for l in lines)
@@ -313,16 +335,7 @@ def test_exact_network_on_the_device(kind, H):
         q64 = np.stack([forward_f64(w, x)[2] for w in nets])
         rows, act = _rows(kind, x)
         got = env.critic_parameter_gradients(critic, act, dq=_dev(dq), rows=rows)
-        # the target form, on the n of 4 n candidate rows on which the float64 q_0 and q_1 lie closest: y a few grid steps from q_0, so
-        # that q_i - y are small multiples of the grid, dq = (q - y) 2^-3 is exact and the sums stay below 2^24 units (asserted)
-        cand = exact_inputs(kind, 4 * n)
-        qc = np.stack([forward_f64(w, cand)[2] for w in nets])
-        pick = np.sort(np.argsort(np.abs(qc[1] - qc[0]), kind="stable")[:n])
-        x_t, q64_t = cand[pick], qc[:, pick]
-        k = np.random.default_rng([n, H, 19]).integers(-2, 3, n)
-        y = (q64_t[0] - k * GRID).astype(np.float32)
-        assert np.array_equal(y.astype(np.float64), q64_t[0] - k * GRID)
-        dq_t = (q64_t - y.astype(np.float64)[None, :]) * scale
+        x_t, y, q64_t, dq_t = exact_target(nets, kind, H, n, scale)
         refs_t, _ = assert_exact(nets, x_t, dq_t, GRID * scale)
         rows_t, act_t = _rows(kind, x_t)
         got_t = env.critic_parameter_gradients(critic, act_t, target=_dev(y), scale=scale, rows=rows_t)
@@ -414,7 +427,8 @@ def test_two_calls_agree_and_nothing_depends_on_old_contents(dyn):
 
 
 def _raw(dyn, m, pad=64, fill=-12345.0, with_q=True):
-    """A call through the C interface with guard words round every output and the workspace."""
+    """A call through the C interface with guard words round every output and the workspace.  `dyn`: the fixture, or any dict with
+    ``env``, ``critic``, ``rows`` and ``act`` (at least m rows)."""
     import torch
 
     env, critic, rows, act = (dyn[k] for k in ("env", "critic", "rows", "act"))
