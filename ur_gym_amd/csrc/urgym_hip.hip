@@ -33,6 +33,7 @@
 #include <string.h>
 #include <math.h>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/urgym.h"
@@ -801,8 +802,11 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
     };
     // builds the operands of one work item (e | kind << 8 | lb << 10 | la << 13); false when there is nothing to run
     // p1_ok: the P1 lanes of this workgroup have published (s_p1done acquired) -- their set-up cache may be read
-    bool p1_ok = false;
-    auto setup = [&](uint32_t item) -> bool {
+    // after_p1 (std::true_type / std::false_type): the call site knows that they have.  Only the lanes' own first tickets, set up
+    // before the loop, may run ahead of P1 and compute sin / cos and the obstacle pose themselves; the set-up inside the loop and the
+    // EPA service's are compiled without that path (two float64 sincos expansions and the finite check less in the loop).
+    bool p1_ok = (MODE != MODE_STEP);
+    auto setup = [&](uint32_t item, auto after_p1) -> bool {
       e = item & 255;
       kind = (item >> 8) & 3;
       exact = ((item >> 16) & 1) != 0;
@@ -815,7 +819,7 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
       if (e >= E || lb < 1 || lb > 6 || (kind == Q_SELF && (la < 1 || la > 6))) return false;
       const int n = s_env[e];
       if (n < 0) return false;
-      const bool cached = (MODE == MODE_STEP) && p1_ok;  // (then s_env already carries P1's verdict on the joints)
+      const bool cached = (MODE == MODE_STEP) && (decltype(after_p1)::value || p1_ok);  // (then s_env already carries P1's verdict on the joints)
       if (MODE == MODE_STEP && !cached) {  // P1 may not have judged this env yet: non-finite joints -> no query (same rule as P1)
         bool finite = true;
         for (int k = 0; k < 6; k++) finite = finite && (fabs(joint_of_step<MODE>(P, actions, n, k)) < 1.0e6);
@@ -899,10 +903,12 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
     bool busy = false;
     if (MODE == MODE_STEP) p1_ok = __hip_atomic_load(&s_p1done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) >= G;
     if (tid < n_tickets) {
-      busy = setup(ticket_item(tid));
+      busy = setup(ticket_item(tid), std::false_type{});
       if (busy) gjk_begin(run, v0);
     }
-    for (;;) {
+    // One loop trip of a lane: its query advances by one GJK iteration and, when that ends it, files its result.  The body is inlined
+    // twice, into the steady loop and into the drain loop below; neither holds anything else.
+    auto trip = [&]() __attribute__((always_inline)) {
       if (busy) {
         // exact queries (link distances): Bullet's early-out distance of getClosestPoints(distance = 5.0).  Boolean queries ("closer
         // than the contact margin?", check_collision): both bounds of the search are compared with the margin itself -- the search
@@ -939,9 +945,20 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
           busy = false;
         }
       }
-      // (atomic loads: other waves change both words while this one polls them; a plain read could legally be hoisted)
-      // one 16-byte LDS read of the pool's words (three dependent round trips when they were polled one by one), then the acquire:
-      // what the P1 lanes wrote before they counted themselves in s_p1done (pair masks, the set-up cache) is visible to what follows
+    };
+    // Three loop shapes.  The STEADY loop runs trips and nothing else while fewer than REFILL_MIN lanes are idle: drawing an item
+    // costs the whole wave a set-up (FK + operands), so idle lanes draw together, and until enough of them wait the pool is not
+    // even looked at.  (A wave without a query runs its one trip with every lane masked off and falls through.)  The DRAW step
+    // polls the pool and draws -- in a STEP launch only once the per-env phase has published: a draw is then loads from its set-up
+    // cache, and until then idle lanes stay idle, as they do while the pool is empty.  Once it has seen the pool dry for good -- tickets only count up, and s_pending only falls once
+    // the pair masks are published -- the wave finishes what its lanes hold in the DRAIN loop and leaves.  While the pool is empty
+    // but the pair masks are not published yet, the wave comes back to the draw step after every trip.
+    for (;;) {
+      do trip(); while (__popcll(__ballot(!busy)) < REFILL_MIN);
+      // The pool's four words in ONE 16-byte LDS read (polled one by one they were three dependent round trips), then the acquire
+      // fence: what the P1 lanes wrote before they counted themselves in s_p1done (pair masks, the set-up cache) is visible to
+      // what follows.  The read is volatile, not atomic: other waves change the words meanwhile, so what it returns is a hint --
+      // a draw claims its item with an atomic of its own, and leaving the pool is confirmed with atomic loads below.
       typedef int pool_words __attribute__((ext_vector_type(4)));
       const pool_words pool = *(volatile URGYM_LDS pool_words*)(URGYM_LDS void*)&s_ticket;
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -949,10 +966,7 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
       const bool p1_published = (MODE != MODE_STEP) || pool.z >= G;
       const bool more_pairs = pool.y > 0;
       if (MODE == MODE_STEP) p1_ok = p1_published;
-      // drawing an item costs the whole wave a set-up (FK + operands), so idle lanes
-      // draw together: once REFILL_MIN of them are waiting, or when none is busy any more
-      const int idle_lanes = __popcll(__ballot(!busy));
-      if (!busy && (idle_lanes >= REFILL_MIN || idle_lanes == 64)) {
+      if (!busy && p1_ok) {  // (at least REFILL_MIN lanes are here; STEP: before P1 has published they stay idle)
         uint32_t item = NO_ITEM;
         if (more_tickets) {
           const int t = atomicAdd(&s_ticket, 1);
@@ -961,12 +975,25 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
           if (atomicSub(&s_pending, 1) > 0) item = claim_pair();
         }
         if (item != NO_ITEM) {
-          busy = setup(item);
+          busy = setup(item, std::true_type{});
           if (busy) gjk_begin(run, v0);
         }
       }
-      // nothing left for this wave to draw (STEP: and the pair masks have been published)
-      if (__ballot(busy) == 0ull && !more_tickets && !more_pairs && p1_published) break;
+      // nothing left for this wave to draw, now or later (STEP: and the pair masks have been published)
+      if (!more_tickets && !more_pairs && p1_published) {
+        // Confirm it, once per wave and launch, with the ordering the wide read does not promise: s_p1done with acquire, THEN
+        // s_pending -- a stale s_pending == 0 beside a fresh s_p1done would leave pair bits unclaimed.  (s_ticket never falls.)
+        bool dry = true;
+        if (MODE == MODE_STEP) {
+          const int done = __hip_atomic_load(&s_p1done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
+          const int pending = __hip_atomic_load(&s_pending, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          dry = done >= G && pending <= 0;
+        }
+        if (dry) {
+          while (__ballot(busy) != 0ull) trip();
+          break;
+        }
+      }
     }
     // ---- EPA: penetration depth of the marked queries, one wave per query (urgym_device.h epa_wave).  A wave that has left
     //      the pool turns into a service wave: it keeps looking for marks and serves them while the other waves still iterate
@@ -1002,7 +1029,7 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
             const int body = b / 5, link = 2 + b - 5 * body;
             const uint32_t item = (uint32_t)ee | ((uint32_t)(body == 0 ? 3 : (body == 1 ? Q_TABLE : Q_TRACK)) << 8) | ((uint32_t)link << 10) |
                                   ((body ? 1u : 0u) << 16);
-            if (!setup(item)) continue;
+            if (!setup(item, std::true_type{})) continue;  // (this wave has left the pool: it has seen P1's publication)
             epa_wave_sync();
             bool capped;
             const double depth = epa_wave(P.graph, shape_a(), shape_b(), ws, lane, capped);
