@@ -54,6 +54,8 @@ def lib():
         L.urgym_oracle_integrate_obstacle.argtypes = [dp, dp, C.c_double]
         L.urgym_oracle_set_primitive_margin.argtypes = [C.c_double]
         L.urgym_oracle_last_epa_iterations.restype = C.c_int
+        L.urgym_oracle_last_epa_census.argtypes = [C.POINTER(C.c_int)]
+        L.urgym_oracle_last_epa_census.restype = None
         L.urgym_oracle_philox.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, dp]
         L.urgym_oracle_hardware_threads.restype = C.c_int
         _lib = L
@@ -238,6 +240,15 @@ def set_collision_groups(bits):
 
 def last_epa_iterations():
     return lib().urgym_oracle_last_epa_iterations()
+
+
+def last_epa_census():
+    """Census of the calling thread's last EPA: dict(max_nc, degenerate_faces, max_face_slot, overflowed) -- the largest
+    rim-candidate count of one expansion, the degenerate faces made (the initial four included), the highest face slot written,
+    and whether the search ended because no face slot was free."""
+    out = (C.c_int * 4)()
+    lib().urgym_oracle_last_epa_census(out)
+    return dict(max_nc=out[0], degenerate_faces=out[1], max_face_slot=out[2], overflowed=bool(out[3]))
 
 
 def philox(seed, env, episode, attempt):

@@ -500,6 +500,12 @@ struct EpaResult {
   bool capped;
 };
 thread_local int g_last_epa_iterations = 0;  // probe for tests / sizing of the device workspace
+// Census of the last search on this thread (tests only; no result depends on it): which paths of the slot-for-slot twin on the
+// device (urgym_device.h epa_wave) an input takes -- the largest rim-candidate count nc of one expansion (the device reads the
+// list back from LDS instead of from its lanes once nc > 64), the degenerate faces made (the initial four included), the
+// highest face slot written (faces 126, 127 live in another workspace row there) and whether the search ran out of face slots.
+struct EpaCensus { int max_nc, degenerate_faces, max_face_slot, overflowed; };
+thread_local EpaCensus g_last_epa_census = {0, 0, 0, 0};
 const double EPA_TOL = 1.0e-9;
 // The polytope lives in fixed slots exactly like the HIP path's LDS workspace (urgym_device.h epa_wave), so that both
 // sides pick the same faces, in the same order, with the same arithmetic: at most EPA_MAX_VERTS points, hence at most
@@ -510,6 +516,13 @@ const double EPA_TOL = 1.0e-9;
 // EPA_CAP_RESIDUAL to gain is flagged URGYM_STATUS_GJK_ITER.
 const int EPA_MAX_VERTS = 48, EPA_MAX_FACES = 128;
 const double EPA_CAP_RESIDUAL = 1.0e-5;
+// A face sees the new point w when w lies more than EPA_VISIBLE_EPS outside its plane.  This was 1e-14, below the rounding noise
+// of the test itself (n . w - d with |w| ~ 0.3 and a normal from a cross product: 1e-15 .. 1e-13): where w is coplanar with whole
+// fans of faces -- a box on the axis of the cylinder, flat caps parallel -- noise decided which of them were seen, the seen set
+// stopped being a disc, faces came out inverted and piled up past 2 V - 4.  19 of 110 such poses ended flagged with depths off by
+// centimetres, and which ones depended on the compiler's fused multiply-adds (tests/penetration_cases.py).
+// 1e-12 is above that noise and a thousand times below EPA_TOL.
+const double EPA_VISIBLE_EPS = 1.0e-12;
 
 // Works in B's frame like the device: X = pose of A in B's frame, w(n) = X S_A(X^T n) - S_B(-n).
 EpaResult epa_core_depth(const Shape& A, const Shape& B) {
@@ -523,6 +536,8 @@ EpaResult epa_core_depth(const Shape& A, const Shape& B) {
   Face faces[EPA_MAX_FACES];
   for (auto& f : faces) f = Face{0, 0, 0, v3(0, 0, 0), 0.0, false, false};
   int nv = 0;
+  EpaCensus& census = g_last_epa_census;
+  census = EpaCensus{0, 0, 3, 0};
   auto make_face = [&](int i, int j, int k, V3 pi, V3 pj, V3 pk) {
     Face f{i, j, k, v3(0, 0, 0), 1e300, true, true};
     V3 n = cross(pj - pi, pk - pi);
@@ -532,6 +547,7 @@ EpaResult epa_core_depth(const Shape& A, const Shape& B) {
       f.d = dot(f.n, pi);
       f.degenerate = false;
     }
+    census.degenerate_faces += f.degenerate ? 1 : 0;
     return f;
   };
   // initial tetrahedron: support points of the four tetrahedral directions (it need not contain the origin yet: faces that
@@ -566,11 +582,12 @@ EpaResult epa_core_depth(const Shape& A, const Shape& B) {
     for (int f = 0; f < EPA_MAX_FACES; f++) {
       Face& F = faces[f];
       if (!F.alive) continue;
-      if (F.degenerate || dot(F.n, w) - F.d > 1e-14) {
+      if (F.degenerate || dot(F.n, w) - F.d > EPA_VISIBLE_EPS) {
         F.alive = false;
         cand[nc++] = (F.i << 8) | F.j; cand[nc++] = (F.j << 8) | F.k; cand[nc++] = (F.k << 8) | F.i;
       }
     }
+    census.max_nc = std::max(census.max_nc, nc);
     // horizon = candidates whose reverse is not a candidate; new faces fill the free slots in ascending order
     int slot = 0;
     for (int c = 0; c < nc; c++) {
@@ -579,7 +596,9 @@ EpaResult epa_core_depth(const Shape& A, const Shape& B) {
       for (int x = 0; x < nc; x++) found = found || cand[x] == rev;
       if (found) continue;
       while (slot < EPA_MAX_FACES && faces[slot].alive) slot++;
-      if (slot >= EPA_MAX_FACES) {  // cannot happen while 2 V - 4 <= EPA_MAX_FACES; mirrors the device's exit
+      // no free slot (cannot happen while the polytope stays a closed surface: 2 V - 4 <= EPA_MAX_FACES); mirrors the device's exit
+      if (slot >= EPA_MAX_FACES) {
+        census.overflowed = 1;
         res.capped = true;
         res.depth = bf.d > 0 ? bf.d : 0.0;
         g_last_epa_iterations = res.iterations;
@@ -587,6 +606,7 @@ EpaResult epa_core_depth(const Shape& A, const Shape& B) {
       }
       const int a = cand[c] >> 8, b = cand[c] & 255;
       faces[slot] = make_face(a, b, nv, pts[a], pts[b], w);
+      census.max_face_slot = std::max(census.max_face_slot, slot);
     }
     pts[nv++] = w;
   }
@@ -1423,6 +1443,12 @@ int urgym_oracle_query(const double* q, const double* obst_pose, int has_obstacl
 void urgym_oracle_set_emulation(int flags) { g_emulate = flags; }
 void urgym_oracle_set_collision_groups(int bits) { g_collision_groups = bits; }
 int urgym_oracle_last_epa_iterations(void) { return g_last_epa_iterations; }
+// out4 = {largest rim-candidate count, degenerate faces made, highest face slot written, 1 if the search ended because no face
+// slot was free} of the calling thread's last EPA
+void urgym_oracle_last_epa_census(int* out4) {
+  out4[0] = g_last_epa_census.max_nc; out4[1] = g_last_epa_census.degenerate_faces; out4[2] = g_last_epa_census.max_face_slot;
+  out4[3] = g_last_epa_census.overflowed;
+}
 void urgym_oracle_set_primitive_margin(double m) { g_prim_margin_override = m; }
 void urgym_oracle_philox(uint64_t seed, uint32_t env, uint32_t episode, uint32_t attempt, double* u20) {
   Draws d = draw_attempt(seed, env, episode, attempt);

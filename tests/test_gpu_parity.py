@@ -51,7 +51,10 @@ def obs_diff(kind, a, b):
 def link_dist_slack(oracle, gpu_ld, ref_ld, q, obst_pos, obst_quat, gjk_start=0, scope=0):
     """Per-env allowance for |gpu - oracle| link distances [5, N]: zero where they agree to LD_TOL; where they do not,
     the query must be one at which the oracle itself is unstable — re-run the oracle under 1e-14 pose perturbations and
-    require the HIP value inside the range of its answers.  Returns the measured |difference| (0 where within LD_TOL)."""
+    require the HIP value inside the range of its answers.  Returns the measured |difference| (0 where within LD_TOL).
+    Under scope = WORKBENCH the cell may be a link <-> table / track distance, which the obstacle's pose does not enter: there
+    the joint angles are perturbed by 1e-14 as well (moving the obstacle alone called such a query well-conditioned whatever
+    the oracle does at it)."""
     diff = np.abs(gpu_ld - ref_ld)
     slack = np.where(diff > LD_TOL, diff, 0.0)
     rng = np.random.default_rng(0)
@@ -59,7 +62,8 @@ def link_dist_slack(oracle, gpu_ld, ref_ld, q, obst_pos, obst_quat, gjk_start=0,
         vals = []
         for _ in range(200):
             pose = np.r_[obst_pos[:, n] + rng.normal(0, 1e-14, 3), obst_quat[:, n]]
-            vals.append(oracle.query(q[:, n], pose, gjk_start=gjk_start, scope=scope)[0][i])
+            qn = q[:, n] + rng.normal(0, 1e-14, 6) if scope else q[:, n]
+            vals.append(oracle.query(qn, pose, gjk_start=gjk_start, scope=scope)[0][i])
         lo, hi = min(vals), max(vals)
         assert hi - lo >= 0.9 * diff[i, n], f"link {i + 2} env {n}: differs by {diff[i, n]:.3e} at a WELL-conditioned query (oracle spread {hi - lo:.3e})"
         assert lo - 1e-8 <= gpu_ld[i, n] <= hi + 1e-8, f"link {i + 2} env {n}: {gpu_ld[i, n]} outside the oracle's range [{lo}, {hi}]"

@@ -580,6 +580,7 @@ __device__ __forceinline__ void gjk_iterate(GjkRun& r, const HullMap& g, const S
 constexpr int EPA_MAX_VERTS = 48, EPA_MAX_FACES = 128;   // (the oracle's header comment has the census behind the cap)
 constexpr int EPA_FACE_GROUPS = EPA_MAX_FACES / 64;       // faces per lane
 constexpr double EPA_TOL = 1.0e-9, EPA_CAP_RESIDUAL = 1.0e-5;
+constexpr double EPA_VISIBLE_EPS = 1.0e-12;  // a face sees a point this far outside its plane (above the test's own rounding noise: see the oracle)
 #if !defined(URGYM_HOST_HARNESS)
 struct EpaWs {
   URGYM_LDS double* base;  // &M[0][0]
@@ -685,7 +686,7 @@ __device__ inline double epa_wave(const HullMap& g, const ShapeDesc& A, const Sh
         word[gi] = *ws.face_word(f);
         const bool alive = (word[gi] >> 24) & 1, degen = (word[gi] >> 25) & 1;
         const D3 n = d3(*ws.plane(f, 0), *ws.plane(f, 1), *ws.plane(f, 2));
-        vis[gi] = alive && (degen || dot(n, w) - *ws.plane(f, 3) > 1e-14);
+        vis[gi] = alive && (degen || dot(n, w) - *ws.plane(f, 3) > EPA_VISIBLE_EPS);
       }
 #pragma unroll
       for (int gi = 0; gi < EPA_FACE_GROUPS; gi++) {
