@@ -404,6 +404,52 @@ def test_split_invariance_and_seed():
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("mode", ["mean", "gaussian", "uniform"])
+def test_rollout_branches_are_bitwise_single_calls(mode):
+    """What a rollout may leave out, each against the same steps made one call at a time (urgym_actor_sample, urgym_actor_forward for
+    the actions of "mean", urgym_step): no steps at all, no trajectory and no records, sample records without a trajectory (for
+    "mean" this is the sampling kernel, without them the deterministic one), a trajectory without its actions (they pass through the
+    actor's scratch) and one with them.  65 envs: one more than a wave.  3 steps: a first, a middle and a closing pass.
+    max_episode_steps = 2: every env is truncated and auto-reset at the second step, so the third acts on a reset observation."""
+    import torch
+
+    n, K = 65, 3
+    sample = dict(mode=mode, seed=19, first_draw=(1 << 32) - 2)  # the draws cross 2^32
+    ref, ref_actor = _make("dyn", n, 7, max_episode_steps=2)
+    actions, log_prob, reward = [], [], []
+    for k in range(K):
+        a, lp = ref.policy_actions(ref_actor, sample=dict(sample, first_draw=sample["first_draw"] + k))
+        if mode == "mean":
+            a = ref.policy_actions(ref_actor)
+        rew = ref.step(a)[1]
+        actions.append(a.clone()), log_prob.append(lp.clone()), reward.append(rew.clone())
+    actions, log_prob, reward = torch.stack(actions), torch.stack(log_prob), torch.stack(reward)
+    assert int(ref.buf["episode_id"].min()) >= 1  # on the single-call side alone
+
+    lib = _native.lib()
+    made = [_make("dyn", n, 7, max_episode_steps=2) for _ in range(4)]
+    (env_a, actor_a), (env_b, actor_b), (env_c, actor_c), (env_d, actor_d) = made
+    how = env_a._sampling(sample)
+    assert lib.urgym_rollout_sampled(env_a._h, actor_a._a, C.byref(how), 0, None, None, env_a._stream()) == _abi.OK  # launches nothing
+    assert lib.urgym_rollout_sampled(env_a._h, actor_a._a, C.byref(how), K, None, None, env_a._stream()) == _abi.OK
+    _same_state(env_a, ref)
+    lp_b = torch.zeros((K, n), dtype=torch.float32, device="cuda:0")
+    extra = _abi.SampleRecords(log_prob=C.cast(lp_b.data_ptr(), C.POINTER(C.c_float)))
+    assert lib.urgym_rollout_sampled(env_b._h, actor_b._a, C.byref(how), K, None, C.byref(extra), env_b._stream()) == _abi.OK
+    assert _same_bits(lp_b, log_prob)
+    _same_state(env_b, ref)
+    rec_c = env_c.rollout_policy(actor_c, K, record=("reward", "log_prob"), sample=sample)
+    assert _same_bits(rec_c["reward"], reward) and _same_bits(rec_c["log_prob"], log_prob)
+    _same_state(env_c, ref)
+    rec_d = env_d.rollout_policy(actor_d, K, record=("action",), sample=sample)
+    assert _same_bits(rec_d["action"], actions)
+    _same_state(env_d, ref)
+    for env, actor in made + [(ref, ref_actor)]:
+        actor.close()
+        env.close()
+
+
+@pytest.mark.gpu
 def test_warm_up_then_policy():
     """SAC's collection schedule: learning_starts = 100 uniform steps, then the policy."""
     import torch

@@ -131,17 +131,20 @@ def _collected(name, splits=(K,), cap=CAP):
 
 
 @functools.lru_cache(maxsize=None)
-def python_stepped(name):
+def python_stepped(name, n=N, num_steps=K, mode=HOW["mode"], step_limit=STEP_LIMIT):
     """The reference: a second env with the same seed stepped from Python, every transition assembled in torch from what step()
-    returns (info['final_observation'], all three keys).  Returns (transitions of all K steps, the env's final buffers)."""
+    returns (info['final_observation'], all three keys).  Returns (transitions of all steps, the env's final buffers)."""
     import torch
 
-    env, actor = _make(name, N, ENV_SEED, max_episode_steps=STEP_LIMIT)
+    env, actor = _make(name, n, ENV_SEED, max_episode_steps=step_limit)
     rows = ("observation", "achieved_goal", "desired_goal")
     steps = []
-    for k in range(K):
+    for k in range(num_steps):
         t = {key: env.buf[key].clone() for key in rows}
-        a, _ = env.policy_actions(actor, sample=dict(HOW, first_draw=HOW["first_draw"] + k))
+        if mode == "mean":
+            a = env.policy_actions(actor)  # urgym_actor_forward
+        else:
+            a, _ = env.policy_actions(actor, sample=dict(HOW, mode=mode, first_draw=HOW["first_draw"] + k))
         obs, rew, term, trunc, info = env.step(a)
         done = (term | trunc)[:, None]
         t["action"], t["reward"] = a.clone(), rew.clone()
@@ -178,6 +181,31 @@ def test_collect_is_bitwise_a_python_stepped_loop(name):
         for key in RING_KEYS:
             assert _same_bits(replay.ring[key][k % CAP], steps[k][key]), (name, k, key)
     for key, want in final.items():  # and the environment is where the Python loop left its own
+        if key not in ("done_list", "done_count"):
+            assert _same_bits(env.buf[key], want), key
+    actor.close()
+    env.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", ["mean", "gaussian", "uniform"])
+def test_collect_in_every_mode_wraps_a_small_ring(mode):
+    """65 envs (one more than a wave), 3 steps from slot 1 of a 2-slot ring: slots 1, 0, 1, so the first, a middle and the closing
+    store pass all occur and the last step overwrites the first.  max_episode_steps = 2: every env is auto-reset at the second step.
+    "mean" is the deterministic kernel (the reference takes its actions from urgym_actor_forward), "uniform" runs no forward pass."""
+    import torch
+
+    n, steps_k, cap = 65, 3, 2
+    steps, final = python_stepped("dyn", n, steps_k, mode, 2)
+    assert bool(torch.stack([t["truncated"] for t in steps]).any())  # on the Python-stepped side alone
+    env, actor = _make("dyn", n, ENV_SEED, max_episode_steps=2)
+    replay = DeviceReplay(env, cap)
+    env.collect(actor, steps_k, replay, sample=None if mode == "mean" else dict(HOW, mode=mode), first_slot=1)
+    torch.cuda.synchronize()
+    for k, slot in ((1, 0), (2, 1)):
+        for key in RING_KEYS:
+            assert _same_bits(replay.ring[key][slot], steps[k][key]), (mode, k, key)
+    for key, want in final.items():
         if key not in ("done_list", "done_count"):
             assert _same_bits(env.buf[key], want), key
     actor.close()

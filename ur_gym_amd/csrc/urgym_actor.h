@@ -1,5 +1,5 @@
-// urgym_actor.h — seam between the two translation units of liburgym_hip.so: urgym_actor.hip (the actor / record kernels, compiled
-// with fma contraction) offers these; urgym_hip.hip (handle, C-ABI, step launches) calls them.  Nothing here is exported.
+// urgym_actor.h — seam between two translation units of liburgym_hip.so: urgym_actor.hip (the actor / record kernels, compiled
+// with fma contraction) offers these; urgym_policy_abi.hip (the learner's entry points) calls them.  Nothing here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

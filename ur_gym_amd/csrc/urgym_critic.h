@@ -1,5 +1,5 @@
 // urgym_critic.h — seam between urgym_critic.hip (the twin Q-network kernel, compiled with fma contraction like urgym_actor.hip) and
-// urgym_hip.hip (handle, C-ABI), beside urgym_actor.h.  Nothing here is exported.
+// urgym_policy_abi.hip (the learner's entry points), beside urgym_actor.h.  Nothing here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

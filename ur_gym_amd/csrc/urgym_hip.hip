@@ -1,4 +1,5 @@
-// urgym_hip.hip — fused UR5e reach environment kernels for MI355X (gfx950) + the C-ABI of include/urgym.h.
+// urgym_hip.hip — fused UR5e reach environment kernels for MI355X (gfx950) + the environment's half of the C-ABI of include/urgym.h.
+// The learner's half (actors, replay ring, critics) is urgym_policy_abi.hip; they share urgym_handle.h, and that unit calls do_step here.
 //
 // One body template env_body<KIND, MODE> (MODE = STEP | RESET | REFRESH | PREFETCH) behind env_kernel<KIND, MODE> (one mode per launch)
 // and env_step_fused<KIND> (the steady-state step: STEP workgroups + the PREFETCH refill of the previous step); device math in
@@ -39,12 +40,7 @@
 #include "../../include/urgym.h"
 #include "../../data/ur5e_model.h"
 #include "urgym_device.h"
-#include "urgym_launch_plan.h"
-#include "urgym_actor.h"
-#include "urgym_critic.h"
-#include "urgym_pack_map.h"
-#include "urgym_weights.h"
-#include "urgym_replay.h"
+#include "urgym_handle.h"
 #include "urgym_tables_host.h"
 
 using namespace urgym;
@@ -1540,20 +1536,19 @@ __global__ void build_list_kernel(const uint8_t* mask, int N, int* list, int* co
 }
 
 // ------------------------------------------------------------------------------------------------- host side
-// The kernel instances a handle launches
-struct Kernels {
-  void (*mode[4])(KParams, const float*);              // by MODE_*
-  void (*fused)(KParams, KParams, const float*, int);  // env_step_fused (none for Ori)
-};
+// The kernel instances a handle launches: Handle::k keeps them untyped (urgym_handle.h says why), these are their types
+using ModeKernel = void (*)(KParams, const float*);                // Kernels::mode
+using FusedKernel = void (*)(KParams, KParams, const float*, int);  // Kernels::fused
+using AnyKernel = void (*)();
 
 // Which launches can consume a penetration depth (need_epa in the kernel): Ori's never (no obstacle), Obs's always, Sta's and
 // Dyn's unless a STEP launch checks collisions.  Only these instances are compiled.
 template <int KIND, bool STEP_EPA>
 Kernels kernels_of() {
   constexpr bool EPA = KIND != URGYM_ENV_ORI;
-  Kernels k{{env_kernel<KIND, MODE_STEP, STEP_EPA>, env_kernel<KIND, MODE_RESET, EPA>, env_kernel<KIND, MODE_REFRESH, EPA>,
-             env_kernel<KIND, MODE_PREFETCH, EPA>}, nullptr};
-  if constexpr (KIND != URGYM_ENV_ORI) k.fused = env_step_fused<KIND, STEP_EPA>;
+  Kernels k{{(AnyKernel)(ModeKernel)env_kernel<KIND, MODE_STEP, STEP_EPA>, (AnyKernel)(ModeKernel)env_kernel<KIND, MODE_RESET, EPA>,
+             (AnyKernel)(ModeKernel)env_kernel<KIND, MODE_REFRESH, EPA>, (AnyKernel)(ModeKernel)env_kernel<KIND, MODE_PREFETCH, EPA>}, nullptr};
+  if constexpr (KIND != URGYM_ENV_ORI) k.fused = (AnyKernel)(FusedKernel)env_step_fused<KIND, STEP_EPA>;
   return k;
 }
 
@@ -1565,63 +1560,6 @@ Kernels kernels_for(const urgym_config& c) {
     default: return c.check_collision ? kernels_of<URGYM_ENV_DYN, false>() : kernels_of<URGYM_ENV_DYN, true>();
   }
 }
-
-struct Handle {
-  urgym_config cfg;
-  urgym_buffers buf;
-  bool bound = false;
-  int device = 0;
-  int obs_dim = 0, goal_dim = 0;
-  LaunchPlan plan;                 // launch geometry and paths (urgym_launch_plan.h), fixed at urgym_create
-  Kernels k;
-  double* d_ld_scratch = nullptr;  // [5][N] link distances of the running step
-  double* d_sc_scratch = nullptr;  // [SC_ROWS][N] set-up cache of the running step
-  CandRec* d_recs = nullptr;          // support map: candidate records ...
-  unsigned short* d_cell = nullptr;   // ... and the cube map of directions that points into them
-  uint64_t seed = 0;
-  int pp = 0;
-  char err[512] = {0};
-  // timing
-  bool timing = false;
-  int timing_every = 1;   // time every k-th step (an event pair costs the stream ~6 us: sampling keeps the measurement out of the measured)
-  long timing_tick = 0;
-  std::vector<hipEvent_t> ev;  // pairs: [2i] start, [2i+1] stop ; kind in ev_kind
-  std::vector<int> ev_kind;    // 0 = step kernel, 1 = reset kernel(s) on the caller's stream
-  size_t ev_used = 0;
-  // prefetched episode records (DESIGN.md "auto-reset off the critical path")
-  float neutral_ach[6] = {0, 0, 0, 0, 0, 0};
-  double* d_rec = nullptr;      // [2][REC_FIELDS][N]
-  int32_t* d_reci = nullptr;    // [2][2][N]
-  int2* d_rl[4] = {nullptr, nullptr, nullptr, nullptr};  // refill lists (capacities: plan.rl_cap)
-  int* d_rcount = nullptr;      // their counters
-  int parity = 0;
-  uint64_t rec_seed = 0;
-  bool rec_seed_valid = false;
-  // Steps left in which a finished env may still meet a record that is not valid for its episode (after create / bind /
-  // urgym_invalidate_records / a reset that did not cover every env): only then does a step carry the fallback launches.
-  // An env that falls back gets fresh records for its next two episodes, and every env finishes within max_episode_steps.
-  int dirty_steps = 0;
-  long steps_since_full_reset = -1; // step launches since the last urgym_reset of every env (-1: none yet)
-  // policies (urgym_actor.hip)
-  std::vector<Actor*> actors;  // alive, released by urgym_destroy at the latest
-  std::vector<Critic*> critics;  // the same for the twin Q-networks (urgym_critic.hip)
-  bool observed = false;       // a reset / refresh has filled the bound observation buffers: an actor has something to read
-};
-thread_local char g_err[512] = {0};
-
-int fail(Handle* h, int code, const char* what, hipError_t e = hipSuccess) {
-  char* dst = h ? h->err : g_err;
-  if (e != hipSuccess)
-    snprintf(dst, 512, "%s: %s", what, hipGetErrorString(e));
-  else
-    snprintf(dst, 512, "%s", what);
-  return code;
-}
-#define HIP_TRY(h, call)                                              \
-  do {                                                                \
-    hipError_t _e = (call);                                           \
-    if (_e != hipSuccess) return fail(h, URGYM_ERR_HIP, #call, _e);   \
-  } while (0)
 
 void fill_default(int env_kind, int num_envs, urgym_config* c) {
   memset(c, 0, sizeof(*c));
@@ -1707,7 +1645,7 @@ void launch_mode(Handle* h, KParams P, const float* actions, hipStream_t s, int 
     if (items < 0) items = h->cfg.num_envs;
     blocks = (items + P.envs - 1) / P.envs;
   }
-  hipLaunchKernelGGL(h->k.mode[MODE], dim3((unsigned)blocks), dim3(THREADS), 0, s, P, actions);
+  hipLaunchKernelGGL((ModeKernel)h->k.mode[MODE], dim3((unsigned)blocks), dim3(THREADS), 0, s, P, actions);
 }
 
 // The steady-state step of the obstacle envs: STEP workgroups + the PREFETCH workgroups that refill what the previous step consumed
@@ -1716,7 +1654,7 @@ void launch_fused(Handle* h, KParams Ps, KParams Pr, const float* actions, hipSt
   Pr.envs = PREFETCH_MAX_ENVS;
   const int sb = h->plan.step_blocks;
   const long grid = sb + refill_blocks(h->plan, h->steps_since_full_reset, h->cfg.max_episode_steps);
-  hipLaunchKernelGGL(h->k.fused, dim3((unsigned)grid), dim3(THREADS), 0, s, Ps, Pr, actions, sb);
+  hipLaunchKernelGGL((FusedKernel)h->k.fused, dim3((unsigned)grid), dim3(THREADS), 0, s, Ps, Pr, actions, sb);
 }
 
 int time_begin(Handle* h, int kind, hipStream_t s) {
@@ -1740,22 +1678,13 @@ void time_end(Handle* h, int slot, hipStream_t s) {
   h->ev_used = slot + 2;
 }
 
-// the checks of a call that needs bound buffers, and its device made current
-int enter_bound(Handle* h) {
-  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
-  if (!h->bound) return fail(h, URGYM_ERR_STATE, "urgym_bind() has not been called");
-  HIP_TRY(h, hipSetDevice(h->device));
-  return URGYM_OK;
-}
-
 // every failure path of urgym_create and urgym_destroy: frees whatever the handle holds
 void release(Handle* h) {
   for (void* p : {(void*)h->d_ld_scratch, (void*)h->d_sc_scratch, (void*)h->d_recs, (void*)h->d_cell, (void*)h->d_rec,
                   (void*)h->d_reci, (void*)h->d_rl[0], (void*)h->d_rl[1], (void*)h->d_rl[2], (void*)h->d_rl[3], (void*)h->d_rcount})
     if (p) hipFree(p);
   for (auto e : h->ev) hipEventDestroy(e);
-  for (Actor* a : h->actors) actor_destroy(a);
-  for (Critic* c : h->critics) critic_destroy(c);
+  release_policies(h);
   delete h;
 }
 
@@ -1773,58 +1702,6 @@ void use_list(Handle* h, KParams& P, int which) {
   P.rcount = h->d_rcount + which;
   P.rcap = h->plan.rl_cap[which];
   P.prefetch = 1;
-}
-
-int do_step(Handle* h, const float* actions, hipStream_t s) {
-  KParams P = make_params(h, 1);
-  int slot;
-  if (!h->plan.fused) {
-    slot = time_begin(h, 0, s);
-    launch_mode<MODE_STEP>(h, P, actions, s);
-    time_end(h, slot, s);
-    if (h->cfg.auto_reset && !h->plan.inline_ori) {
-      slot = time_begin(h, 1, s);
-      launch_mode<MODE_RESET>(h, P, nullptr, s, h->plan.reset_envs);  // ~1 % of the envs per step: small workgroups, many CUs
-      time_end(h, slot, s);
-    }
-  } else {
-    // Finished envs are reset inline from their prefetched episode records, and the record slots a step consumes are refilled by
-    // PREFETCH workgroups that ride in the NEXT step's launch.  Three refill lists rotate: the STEP part of launch t appends to list
-    // t % 3, the PREFETCH part of launch t + 1 reads it, and the STEP part of launch t + 2 re-arms it (its reader belongs to a
-    // launch that has completed by then) -- no extra launch, memset, event or second stream.  A record consumed at step t is
-    // whole again when launch t + 1 ends, i.e. before step t + 2 could need it; at step t + 1 the env uses its other slot.
-    const int cur = h->parity, nxt = (cur + 1) % 3, prv = (cur + 2) % 3;
-    const bool dirty = h->dirty_steps > 0;
-    use_list(h, P, cur);
-    P.rzero = h->d_rcount + nxt;
-    P.rzero2 = dirty ? h->d_rcount + 3 : nullptr;  // the synchronous list of this step's fallback launches
-    P.fallback_on = dirty ? 1 : 0;
-    KParams Pr = P;
-    use_list(h, Pr, prv);
-    Pr.rzero = Pr.rzero2 = nullptr;
-    slot = time_begin(h, 0, s);
-    launch_fused(h, P, Pr, actions, s);
-    time_end(h, slot, s);
-    // In steady state every record is valid (an env's two slots hold its next two episodes, and a consumed slot is refilled before
-    // the env can need it again).  Only while records may be stale (h->dirty_steps > 0: first use, a new binding,
-    // urgym_invalidate_records) does the step carry the fallback: the RESET kernel for envs that found no valid record, then
-    // PREFETCH for their next two episodes -- unbounded, so that an env that fell back comes out clean.
-    if (dirty) {
-      slot = time_begin(h, 1, s);
-      KParams Pf = P;
-      use_list(h, Pf, 3);
-      Pf.rzero = Pf.rzero2 = nullptr;
-      launch_mode<MODE_RESET>(h, Pf, nullptr, s, GROUP);
-      launch_mode<MODE_PREFETCH>(h, Pf, nullptr, s, 8, h->plan.rl_cap[3]);
-      time_end(h, slot, s);
-      h->dirty_steps--;
-    }
-    h->parity = nxt;
-  }
-  if (h->steps_since_full_reset >= 0) h->steps_since_full_reset++;
-  h->pp ^= 1;
-  HIP_TRY(h, hipGetLastError());
-  return URGYM_OK;
 }
 
 int do_masked(Handle* h, const uint8_t* mask, int mode, hipStream_t s) {
@@ -1895,9 +1772,7 @@ int upload_tables(Handle* h) {
   try {
     tabs = &build_host_tables();
   } catch (const std::exception& ex) {  // (std::system_error of its worker threads, std::bad_alloc)
-    char msg[256];
-    snprintf(msg, sizeof(msg), "urgym_create: building the support map failed: %s", ex.what());
-    return fail(h, URGYM_ERR_STATE, msg);
+    return failf(h, URGYM_ERR_STATE, "urgym_create: building the support map failed: %s", ex.what());
   }
   if (!tabs->ok) return fail(h, URGYM_ERR_STATE, "urgym_create: support map has more records than a 16-bit cell code addresses");
   DevTables t;
@@ -1939,141 +1814,60 @@ int eval_neutral_pose(Handle* h) {
   return e == hipSuccess ? URGYM_OK : fail(h, URGYM_ERR_HIP, "urgym_create: neutral pose", e);
 }
 
-
-// ---- policies: the checks and the per-pass arguments of urgym_actor_forward / urgym_rollout_actor
-
-// an actor of THIS handle, still alive
-Actor* find_actor(Handle* h, void* actor) {
-  for (Actor* a : h->actors)
-    if (a == actor) return a;
-  return nullptr;
-}
-
-int actor_features(const Handle* h) { return h->obs_dim + 2 * h->goal_dim; }
-
-ActorEnv actor_env(const Handle* h) {
-  const urgym_buffers& b = h->buf;
-  return ActorEnv{h->cfg.num_envs, h->obs_dim, h->goal_dim, h->cfg.auto_reset, b.observation, b.achieved_goal, b.desired_goal,
-                  b.reward, b.final_observation, b.terminated, b.truncated, b.is_success, b.collision};
-}
-
-// the records of pass k (ActorPass): rows k of what the actor sees, rows k - 1 of what the step before returned
-ActorPass actor_pass(const Handle* h, Actor* a, const urgym_trajectory& t, int k, int num_steps) {
-  const size_t n = (size_t)h->cfg.num_envs, od = (size_t)h->obs_dim, gd = (size_t)h->goal_dim;
-  const size_t pre = (size_t)k * n, post = (size_t)(k > 0 ? k - 1 : 0) * n;
-  auto at = [](auto* p, size_t off) { return p ? p + off : p; };
-  ActorPass r;
-  r.obs = at(t.observation, pre * od), r.ach = at(t.achieved_goal, pre * gd), r.des = at(t.desired_goal, pre * gd);
-  r.reward = at(t.reward, post);
-  r.terminated = at(t.terminated, post), r.truncated = at(t.truncated, post), r.is_success = at(t.is_success, post);
-  r.collision = at(t.collision, post);
-  r.final_obs = at(t.final_observation, post * od);
-  r.ep_return = t.episode_return, r.ep_last = t.episode_last_step, r.ep_success = t.episode_success;
-  const bool summary = t.episode_return || t.episode_last_step || t.episode_success || t.episode_done;
-  r.ep_done = t.episode_done ? t.episode_done : (summary ? actor_done_scratch(a) : nullptr);
-  r.k = k, r.num_steps = num_steps;
-  return r;
-}
-
-// the checks urgym_actor_forward and urgym_rollout_actor share; *out = the actor
-int enter_actor(Handle* h, void* actor, const char* who, Actor** out) {
-  if (int rc = enter_bound(h)) return rc;
-  char msg[200];
-  Actor* a = find_actor(h, actor);
-  if (!a) {
-    snprintf(msg, sizeof(msg), "%s: not an actor of this handle (actors belong to the handle they were created with)", who);
-    return fail(h, URGYM_ERR_ARG, msg);
-  }
-  if (actor_in_features(a) != actor_features(h)) {
-    snprintf(msg, sizeof(msg), "%s: the actor takes %d features, this env kind offers %d", who, actor_in_features(a), actor_features(h));
-    return fail(h, URGYM_ERR_ARG, msg);
-  }
-  if (!h->observed) {
-    snprintf(msg, sizeof(msg), "%s: no observations yet: call urgym_reset (or urgym_refresh) first", who);
-    return fail(h, URGYM_ERR_STATE, msg);
-  }
-  *out = a;
-  return URGYM_OK;
-}
-
-// the checks urgym_actor_sample and urgym_rollout_sampled share; wants_density: a log-probability or a sample record is asked for
-int check_sampling(Handle* h, const Actor* a, const urgym_sampling* how, bool wants_density, const char* who) {
-  char msg[200];
-  const char* what = nullptr;
-  if (!how) what = "null sampling description";
-  else if (how->reserved0 != 0) what = "urgym_sampling.reserved0 must be 0";
-  else if (how->mode != URGYM_SAMPLE_MEAN && how->mode != URGYM_SAMPLE_GAUSSIAN && how->mode != URGYM_SAMPLE_UNIFORM)
-    what = "unknown sampling mode (URGYM_SAMPLE_MEAN, _GAUSSIAN or _UNIFORM)";
-  else if (!actor_has_log_std(a) && (how->mode == URGYM_SAMPLE_GAUSSIAN || (how->mode == URGYM_SAMPLE_MEAN && wants_density)))
-    what = "the actor has no log_std head (urgym_actor_set_log_std)";
-  if (!what) return URGYM_OK;
-  snprintf(msg, sizeof(msg), "%s: %s", who, what);
-  return fail(h, URGYM_ERR_ARG, msg);
-}
-
-// ---- explicit rows (urgym_critic_evaluate, urgym_actor_sample_rows): the checks that concern rows and count; on success obs / ach /
-// des are the pointers to read (the bound buffers where rows->observation is null)
-int resolve_rows(Handle* h, const urgym_critic_rows* rows, int count, const char* who, const float** obs, const float** ach, const float** des) {
-  char msg[200];
-  const char* what = nullptr;
-  if (!rows) what = "null rows";
-  else if (count <= 0) what = "count must be positive";
-  else if (!rows->observation && count != h->cfg.num_envs) what = "rows->observation is null (the bound buffers): count must be num_envs";
-  else if (rows->observation && (!rows->achieved_goal || !rows->desired_goal)) what = "rows->achieved_goal or rows->desired_goal is null";
-  if (what) {
-    snprintf(msg, sizeof(msg), "%s: %s", who, what);
-    return fail(h, URGYM_ERR_ARG, msg);
-  }
-  if (!rows->observation && !h->observed) {
-    snprintf(msg, sizeof(msg), "%s: no observations yet: call urgym_reset (or urgym_refresh) first", who);
-    return fail(h, URGYM_ERR_STATE, msg);
-  }
-  const bool bound = !rows->observation;
-  *obs = bound ? h->buf.observation : rows->observation;
-  *ach = bound ? h->buf.achieved_goal : rows->achieved_goal;
-  *des = bound ? h->buf.desired_goal : rows->desired_goal;
-  return URGYM_OK;
-}
-
-// ---- the replay ring (urgym_rollout_collect, urgym_replay_sample): the checks that concern the ring itself
-int check_ring(Handle* h, const urgym_replay_ring* r, const char* who) {
-  char msg[200];
-  const char* what = nullptr;
-  if (!r) what = "null ring";
-  else if (r->capacity_steps <= 0) what = "ring->capacity_steps must be positive";
-  else if (r->reserved0 != 0) what = "urgym_replay_ring.reserved0 must be 0";
-  else if (!r->observation || !r->achieved_goal || !r->desired_goal || !r->action || !r->reward || !r->next_observation ||
-           !r->next_achieved_goal || !r->next_desired_goal || !r->terminated)
-    what = "a required ring pointer is null (all but truncated and is_success)";
-  if (!what) return URGYM_OK;
-  snprintf(msg, sizeof(msg), "%s: %s", who, what);
-  return fail(h, URGYM_ERR_ARG, msg);
-}
-
-// the store pass before step k of a collection that started at first_slot: the s of slot k (k < num_steps), the outcome of slot k - 1
-ReplayStore replay_store(const Handle* h, const urgym_replay_ring& r, int first_slot, int k, int num_steps) {
-  const urgym_buffers& b = h->buf;
-  const size_t n = (size_t)h->cfg.num_envs, od = (size_t)h->obs_dim, gd = (size_t)h->goal_dim, C = (size_t)r.capacity_steps;
-  ReplayStore p;
-  memset(&p, 0, sizeof(p));
-  p.N = h->cfg.num_envs, p.obs_dim = h->obs_dim, p.goal_dim = h->goal_dim, p.auto_reset = h->cfg.auto_reset;
-  p.observation = b.observation, p.achieved_goal = b.achieved_goal, p.desired_goal = b.desired_goal, p.reward = b.reward;
-  p.final_observation = b.final_observation, p.final_achieved_goal = b.final_achieved_goal, p.final_desired_goal = b.final_desired_goal;
-  p.terminated = b.terminated, p.truncated = b.truncated, p.is_success = b.is_success;
-  if (k < num_steps) {
-    const size_t at = (((size_t)first_slot + (size_t)k) % C) * n;
-    p.obs = r.observation + at * od, p.ach = r.achieved_goal + at * gd, p.des = r.desired_goal + at * gd;
-  }
-  if (k > 0) {
-    const size_t at = (((size_t)first_slot + (size_t)k - 1) % C) * n;
-    p.reward_out = r.reward + at, p.terminated_out = r.terminated + at;
-    p.truncated_out = r.truncated ? r.truncated + at : nullptr, p.is_success_out = r.is_success ? r.is_success + at : nullptr;
-    p.next_obs = r.next_observation + at * od, p.next_ach = r.next_achieved_goal + at * gd, p.next_des = r.next_desired_goal + at * gd;
-  }
-  return p;
-}
-
 }  // namespace
+
+// One environment step: the only function of this unit that the learner's entry points call (urgym_handle.h)
+int urgym::do_step(Handle* h, const float* actions, hipStream_t s) {
+  KParams P = make_params(h, 1);
+  int slot;
+  if (!h->plan.fused) {
+    slot = time_begin(h, 0, s);
+    launch_mode<MODE_STEP>(h, P, actions, s);
+    time_end(h, slot, s);
+    if (h->cfg.auto_reset && !h->plan.inline_ori) {
+      slot = time_begin(h, 1, s);
+      launch_mode<MODE_RESET>(h, P, nullptr, s, h->plan.reset_envs);  // ~1 % of the envs per step: small workgroups, many CUs
+      time_end(h, slot, s);
+    }
+  } else {
+    // Finished envs are reset inline from their prefetched episode records, and the record slots a step consumes are refilled by
+    // PREFETCH workgroups that ride in the NEXT step's launch.  Three refill lists rotate: the STEP part of launch t appends to list
+    // t % 3, the PREFETCH part of launch t + 1 reads it, and the STEP part of launch t + 2 re-arms it (its reader belongs to a
+    // launch that has completed by then) -- no extra launch, memset, event or second stream.  A record consumed at step t is
+    // whole again when launch t + 1 ends, i.e. before step t + 2 could need it; at step t + 1 the env uses its other slot.
+    const int cur = h->parity, nxt = (cur + 1) % 3, prv = (cur + 2) % 3;
+    const bool dirty = h->dirty_steps > 0;
+    use_list(h, P, cur);
+    P.rzero = h->d_rcount + nxt;
+    P.rzero2 = dirty ? h->d_rcount + 3 : nullptr;  // the synchronous list of this step's fallback launches
+    P.fallback_on = dirty ? 1 : 0;
+    KParams Pr = P;
+    use_list(h, Pr, prv);
+    Pr.rzero = Pr.rzero2 = nullptr;
+    slot = time_begin(h, 0, s);
+    launch_fused(h, P, Pr, actions, s);
+    time_end(h, slot, s);
+    // In steady state every record is valid (an env's two slots hold its next two episodes, and a consumed slot is refilled before
+    // the env can need it again).  Only while records may be stale (h->dirty_steps > 0: first use, a new binding,
+    // urgym_invalidate_records) does the step carry the fallback: the RESET kernel for envs that found no valid record, then
+    // PREFETCH for their next two episodes -- unbounded, so that an env that fell back comes out clean.
+    if (dirty) {
+      slot = time_begin(h, 1, s);
+      KParams Pf = P;
+      use_list(h, Pf, 3);
+      Pf.rzero = Pf.rzero2 = nullptr;
+      launch_mode<MODE_RESET>(h, Pf, nullptr, s, GROUP);
+      launch_mode<MODE_PREFETCH>(h, Pf, nullptr, s, 8, h->plan.rl_cap[3]);
+      time_end(h, slot, s);
+      h->dirty_steps--;
+    }
+    h->parity = nxt;
+  }
+  if (h->steps_since_full_reset >= 0) h->steps_since_full_reset++;
+  h->pp ^= 1;
+  return launched(h);
+}
+
 
 extern "C" {
 
@@ -2184,105 +1978,7 @@ int urgym_derive_obstacle_motion(void* handle, void* stream) {
   if (h->cfg.env_kind == URGYM_ENV_ORI) return URGYM_OK;  // no obstacle
   const int N = h->cfg.num_envs;
   hipLaunchKernelGGL(derive_displacement_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->buf.obst_vel, N, h->cfg.dt);
-  HIP_TRY(h, hipGetLastError());
-  return URGYM_OK;
-}
-
-// ---- weights from the device (urgym_weights.hip): everything is checked here, before the launch
-int urgym_actor_load(void* handle, void* actor, const urgym_actor_params_dev* p, void* stream) {
-  Handle* h = (Handle*)handle;
-  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
-  Actor* a = find_actor(h, actor);
-  if (!a) return fail(h, URGYM_ERR_ARG, "urgym_actor_load: not an actor of this handle (actors belong to the handle they were created with)");
-  if (!p) return fail(h, URGYM_ERR_ARG, "urgym_actor_load: null params");
-  if (p->reserved0 != 0) return fail(h, URGYM_ERR_ARG, "urgym_actor_load: reserved0 must be 0");
-  const ActorPacked buf = actor_packed(a);
-  if (p->in_features != buf.in_features || p->hidden_width != buf.hidden) {
-    char msg[200];
-    snprintf(msg, sizeof(msg), "urgym_actor_load: params are %d -> %d, the actor is %d -> %d", p->in_features, p->hidden_width, buf.in_features, buf.hidden);
-    return fail(h, URGYM_ERR_ARG, msg);
-  }
-  if (!p->w0 || !p->b0 || !p->w1 || !p->b1 || !p->w_mu || !p->b_mu) return fail(h, URGYM_ERR_ARG, "urgym_actor_load: a weight or bias pointer is null");
-  if (!p->w_log_std != !p->b_log_std) return fail(h, URGYM_ERR_ARG, "urgym_actor_load: the log_std head needs both w_log_std and b_log_std, or neither");
-  HIP_TRY(h, hipSetDevice(h->device));
-  const float* src[PACK_ACTOR_TENSORS] = {p->w0, p->b0, p->w1, p->b1, p->w_mu, p->b_mu, p->w_log_std, p->b_log_std};
-  actor_pack_launch(buf, src, (hipStream_t)stream);
-  HIP_TRY(h, hipGetLastError());
-  if (p->w_log_std) actor_mark_log_std(a);  // the checks of later calls are made in program order, which is stream order for this stream
-  return URGYM_OK;
-}
-
-namespace {
-Critic* find_critic(Handle* h, void* critic) {
-  for (Critic* c : h->critics)
-    if (c == critic) return c;
-  return nullptr;
-}
-}  // namespace
-
-int urgym_critic_load(void* handle, void* critic, const urgym_critic_params_dev* p, float tau, void* stream) {
-  Handle* h = (Handle*)handle;
-  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
-  Critic* c = find_critic(h, critic);
-  if (!c) return fail(h, URGYM_ERR_ARG, "urgym_critic_load: not a critic of this handle (critics belong to the handle they were created with)");
-  if (!p) return fail(h, URGYM_ERR_ARG, "urgym_critic_load: null params");
-  if (p->reserved0 != 0) return fail(h, URGYM_ERR_ARG, "urgym_critic_load: reserved0 must be 0");
-  if (!(tau > 0.0f && tau <= 1.0f)) return fail(h, URGYM_ERR_ARG, "urgym_critic_load: tau must be in (0, 1]");  // refuses NaN too
-  const CriticPacked buf = critic_packed(c);
-  if (p->in_features != buf.in_features || p->hidden_width != buf.hidden) {
-    char msg[200];
-    snprintf(msg, sizeof(msg), "urgym_critic_load: params are %d -> %d, the critic is %d -> %d", p->in_features, p->hidden_width, buf.in_features, buf.hidden);
-    return fail(h, URGYM_ERR_ARG, msg);
-  }
-  const float* src[2 * PACK_CRITIC_TENSORS];
-  for (int net = 0; net < 2; net++) {
-    const urgym_q_network_dev& q = p->qf[net];
-    if (!q.w0 || !q.b0 || !q.w1 || !q.b1 || !q.w_q || !q.b_q) return fail(h, URGYM_ERR_ARG, "urgym_critic_load: a weight or bias pointer is null");
-    const float* one[PACK_CRITIC_TENSORS] = {q.w0, q.b0, q.w1, q.b1, q.w_q, q.b_q};
-    for (int i = 0; i < PACK_CRITIC_TENSORS; i++) src[PACK_CRITIC_TENSORS * net + i] = one[i];
-  }
-  HIP_TRY(h, hipSetDevice(h->device));
-  critic_pack_launch(buf, src, tau, (hipStream_t)stream);
-  HIP_TRY(h, hipGetLastError());
-  return URGYM_OK;
-}
-
-namespace {
-int read_packed(Handle* h, const char* who, const float* dev, size_t floats, float* host_out, uint64_t capacity, uint64_t* count) {
-  char msg[160];
-  if (!count) {
-    snprintf(msg, sizeof(msg), "%s: null count", who);
-    return fail(h, URGYM_ERR_ARG, msg);
-  }
-  *count = floats;
-  if (!host_out) return URGYM_OK;
-  if (capacity < floats) {
-    snprintf(msg, sizeof(msg), "%s: capacity is %llu floats, the packed buffer has %llu", who, (unsigned long long)capacity, (unsigned long long)floats);
-    return fail(h, URGYM_ERR_ARG, msg);
-  }
-  HIP_TRY(h, hipSetDevice(h->device));
-  HIP_TRY(h, hipDeviceSynchronize());
-  HIP_TRY(h, hipMemcpy(host_out, dev, floats * sizeof(float), hipMemcpyDeviceToHost));
-  return URGYM_OK;
-}
-}  // namespace
-
-int urgym_actor_read_packed(void* handle, void* actor, float* host_out, uint64_t capacity, uint64_t* count) {
-  Handle* h = (Handle*)handle;
-  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
-  Actor* a = find_actor(h, actor);
-  if (!a) return fail(h, URGYM_ERR_ARG, "urgym_actor_read_packed: not an actor of this handle");
-  const ActorPacked buf = actor_packed(a);
-  return read_packed(h, "urgym_actor_read_packed", buf.weights, buf.floats, host_out, capacity, count);
-}
-
-int urgym_critic_read_packed(void* handle, void* critic, float* host_out, uint64_t capacity, uint64_t* count) {
-  Handle* h = (Handle*)handle;
-  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
-  Critic* c = find_critic(h, critic);
-  if (!c) return fail(h, URGYM_ERR_ARG, "urgym_critic_read_packed: not a critic of this handle");
-  const CriticPacked buf = critic_packed(c);
-  return read_packed(h, "urgym_critic_read_packed", buf.weights, buf.floats, host_out, capacity, count);
+  return launched(h);
 }
 
 int urgym_refresh(void* handle, const uint8_t* mask_dev, void* stream) {
@@ -2310,349 +2006,6 @@ int urgym_rollout(void* handle, const float* actions_dev, int num_steps, void* s
   return URGYM_OK;
 }
 
-int urgym_actor_create(void* handle, const urgym_actor_desc* desc, void** actor) {
-  Handle* h = (Handle*)handle;
-  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
-  if (!actor) return fail(h, URGYM_ERR_ARG, "urgym_actor_create: null argument");
-  HIP_TRY(h, hipSetDevice(h->device));
-  Actor* a = nullptr;
-  if (int rc = actor_create(desc, actor_features(h), h->cfg.num_envs, &a, h->err, sizeof(h->err))) return rc;
-  h->actors.push_back(a);
-  *actor = a;
-  return URGYM_OK;
-}
-
-int urgym_actor_destroy(void* handle, void* actor) {
-  Handle* h = (Handle*)handle;
-  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
-  if (!actor) return URGYM_OK;
-  for (size_t i = 0; i < h->actors.size(); i++)
-    if (h->actors[i] == actor) {
-      hipSetDevice(h->device);
-      hipDeviceSynchronize();  // launches that read its weights may still be in flight
-      actor_destroy(h->actors[i]);
-      h->actors.erase(h->actors.begin() + i);
-      return URGYM_OK;
-    }
-  return fail(h, URGYM_ERR_ARG, "urgym_actor_destroy: not an actor of this handle");
-}
-
-int urgym_actor_forward(void* handle, void* actor, float* actions_dev, void* stream) {
-  Handle* h = (Handle*)handle;
-  Actor* a = nullptr;
-  if (int rc = enter_actor(h, actor, "urgym_actor_forward", &a)) return rc;
-  if (!actions_dev) return fail(h, URGYM_ERR_ARG, "urgym_actor_forward: null actions");
-  actor_launch(a, actor_env(h), actions_dev, nullptr, (hipStream_t)stream);
-  HIP_TRY(h, hipGetLastError());
-  return URGYM_OK;
-}
-
-int urgym_rollout_actor(void* handle, void* actor, int num_steps, const urgym_trajectory* traj, void* stream) {
-  Handle* h = (Handle*)handle;
-  Actor* a = nullptr;
-  if (int rc = enter_actor(h, actor, "urgym_rollout_actor", &a)) return rc;
-  if (num_steps < 0) return fail(h, URGYM_ERR_ARG, "urgym_rollout_actor: num_steps < 0");
-  if (num_steps == 0) return URGYM_OK;
-  hipStream_t s = (hipStream_t)stream;
-  const ActorEnv env = actor_env(h);
-  const size_t row = (size_t)h->cfg.num_envs * 6;
-  // Every launch below goes to `s`, and so does everything do_step launches (the step or fused launch, the RESET / PREFETCH
-  // fallbacks of a dirty step, the timing events): stream order alone puts step k - 1 before the pass that reads its outputs and
-  // that pass before the step that reads its actions.
-  for (int k = 0; k <= num_steps; k++) {
-    ActorPass pass;
-    if (traj) pass = actor_pass(h, a, *traj, k, num_steps);
-    if (k == num_steps) {
-      if (traj) actor_launch(a, env, nullptr, &pass, s);  // the result of the last step; no forward pass
-      break;
-    }
-    float* actions = traj && traj->action ? traj->action + (size_t)k * row : actor_action_scratch(a);
-    actor_launch(a, env, actions, traj ? &pass : nullptr, s);
-    if (int rc = do_step(h, actions, s)) return rc;
-  }
-  HIP_TRY(h, hipGetLastError());
-  return URGYM_OK;
-}
-
-int urgym_actor_set_log_std(void* handle, void* actor, const float* w_log_std, const float* b_log_std) {
-  Handle* h = (Handle*)handle;
-  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
-  Actor* a = find_actor(h, actor);
-  if (!a) return fail(h, URGYM_ERR_ARG, "urgym_actor_set_log_std: not an actor of this handle");
-  if (!w_log_std || !b_log_std) return fail(h, URGYM_ERR_ARG, "urgym_actor_set_log_std: a weight or bias pointer is null");
-  HIP_TRY(h, hipSetDevice(h->device));
-  HIP_TRY(h, hipDeviceSynchronize());  // launches that read the head may still be in flight
-  return actor_set_log_std(a, w_log_std, b_log_std, h->err, sizeof(h->err));
-}
-
-int urgym_actor_sample(void* handle, void* actor, const urgym_sampling* how, float* actions_dev, float* log_prob_dev, void* stream) {
-  Handle* h = (Handle*)handle;
-  Actor* a = nullptr;
-  if (int rc = enter_actor(h, actor, "urgym_actor_sample", &a)) return rc;
-  if (int rc = check_sampling(h, a, how, log_prob_dev != nullptr, "urgym_actor_sample")) return rc;
-  if (!actions_dev) return fail(h, URGYM_ERR_ARG, "urgym_actor_sample: null actions");
-  if (how->mode == URGYM_SAMPLE_MEAN && !log_prob_dev)
-    actor_launch(a, actor_env(h), actions_dev, nullptr, (hipStream_t)stream);
-  else
-    actor_launch_sampled(a, actor_env(h), actions_dev, nullptr,
-                         ActorSample{how->mode, how->seed, how->first_draw, log_prob_dev, nullptr, nullptr, nullptr}, (hipStream_t)stream);
-  HIP_TRY(h, hipGetLastError());
-  return URGYM_OK;
-}
-
-int urgym_rollout_sampled(void* handle, void* actor, const urgym_sampling* how, int num_steps, const urgym_trajectory* traj,
-                          const urgym_sample_records* extra, void* stream) {
-  Handle* h = (Handle*)handle;
-  Actor* a = nullptr;
-  if (int rc = enter_actor(h, actor, "urgym_rollout_sampled", &a)) return rc;
-  const bool wants = extra && (extra->log_prob || extra->noise || extra->mean_action || extra->log_std);
-  if (int rc = check_sampling(h, a, how, wants, "urgym_rollout_sampled")) return rc;
-  if (num_steps < 0) return fail(h, URGYM_ERR_ARG, "urgym_rollout_sampled: num_steps < 0");
-  if (how->mode == URGYM_SAMPLE_MEAN && !wants) return urgym_rollout_actor(handle, actor, num_steps, traj, stream);
-  if (num_steps == 0) return URGYM_OK;
-  hipStream_t s = (hipStream_t)stream;
-  const ActorEnv env = actor_env(h);
-  const size_t n = (size_t)h->cfg.num_envs, row = n * 6;
-  auto at = [](float* p, size_t off) { return p ? p + off : p; };
-  for (int k = 0; k <= num_steps; k++) {  // the launches and their order are urgym_rollout_actor's
-    ActorPass pass;
-    if (traj) pass = actor_pass(h, a, *traj, k, num_steps);
-    if (k == num_steps) {
-      if (traj) actor_launch(a, env, nullptr, &pass, s);
-      break;
-    }
-    float* actions = traj && traj->action ? traj->action + (size_t)k * row : actor_action_scratch(a);
-    ActorSample smp{how->mode, how->seed, how->first_draw + (uint64_t)k, nullptr, nullptr, nullptr, nullptr};
-    if (extra) {
-      smp.log_prob = at(extra->log_prob, (size_t)k * n), smp.noise = at(extra->noise, (size_t)k * row);
-      smp.mean_action = at(extra->mean_action, (size_t)k * row), smp.log_std = at(extra->log_std, (size_t)k * row);
-    }
-    actor_launch_sampled(a, env, actions, traj ? &pass : nullptr, smp, s);
-    if (int rc = do_step(h, actions, s)) return rc;
-  }
-  HIP_TRY(h, hipGetLastError());
-  return URGYM_OK;
-}
-
-int urgym_actor_sample_rows(void* handle, void* actor, const urgym_sampling* how, const urgym_critic_rows* rows, int count, float* actions_dev, float* log_prob_dev, void* stream) {
-  const char* who = "urgym_actor_sample_rows";
-  Handle* h = (Handle*)handle;
-  if (int rc = enter_bound(h)) return rc;
-  Actor* a = find_actor(h, actor);
-  if (!a) return fail(h, URGYM_ERR_ARG, "urgym_actor_sample_rows: not an actor of this handle (actors belong to the handle they were created with)");
-  if (actor_in_features(a) != actor_features(h)) return fail(h, URGYM_ERR_ARG, "urgym_actor_sample_rows: the actor does not take this env kind's features");
-  if (int rc = check_sampling(h, a, how, log_prob_dev != nullptr, who)) return rc;
-  if (!actions_dev) return fail(h, URGYM_ERR_ARG, "urgym_actor_sample_rows: null actions");
-  ActorEnv env;
-  memset(&env, 0, sizeof(env));  // no records ride in this launch: the step outputs are not read
-  if (int rc = resolve_rows(h, rows, count, who, &env.observation, &env.achieved_goal, &env.desired_goal)) return rc;
-  env.N = count, env.obs_dim = h->obs_dim, env.goal_dim = h->goal_dim;
-  if (how->mode == URGYM_SAMPLE_MEAN && !log_prob_dev)
-    actor_launch(a, env, actions_dev, nullptr, (hipStream_t)stream);
-  else
-    actor_launch_sampled(a, env, actions_dev, nullptr, ActorSample{how->mode, how->seed, how->first_draw, log_prob_dev, nullptr, nullptr, nullptr},
-                         (hipStream_t)stream);
-  HIP_TRY(h, hipGetLastError());
-  return URGYM_OK;
-}
-
-int urgym_rollout_collect(void* handle, void* actor, const urgym_sampling* how, int num_steps, const urgym_replay_ring* ring, int first_slot, void* stream) {
-  const char* who = "urgym_rollout_collect";
-  Handle* h = (Handle*)handle;
-  Actor* a = nullptr;
-  if (int rc = enter_actor(h, actor, who, &a)) return rc;
-  if (int rc = check_sampling(h, a, how, false, who)) return rc;
-  if (int rc = check_ring(h, ring, who)) return rc;
-  if (first_slot < 0 || first_slot >= ring->capacity_steps) return fail(h, URGYM_ERR_ARG, "urgym_rollout_collect: first_slot outside [0, capacity_steps)");
-  if (num_steps <= 0) return fail(h, URGYM_ERR_ARG, "urgym_rollout_collect: num_steps must be positive");
-  hipStream_t s = (hipStream_t)stream;
-  const ActorEnv env = actor_env(h);
-  const size_t row = (size_t)h->cfg.num_envs * 6;
-  // The launches of urgym_rollout_sampled without records, a store pass before each actor and one after the last step; all on `s`,
-  // so stream order puts step k - 1 before the pass that files its outcome and that pass before the actor of step k.
-  for (int k = 0; k <= num_steps; k++) {
-    replay_store_launch(replay_store(h, *ring, first_slot, k, num_steps), s);
-    if (k == num_steps) break;
-    float* actions = ring->action + (size_t)((first_slot + (int64_t)k) % ring->capacity_steps) * row;  // the actor writes the slot, the step reads it
-    if (how->mode == URGYM_SAMPLE_MEAN)
-      actor_launch(a, env, actions, nullptr, s);
-    else
-      actor_launch_sampled(a, env, actions, nullptr, ActorSample{how->mode, how->seed, how->first_draw + (uint64_t)k, nullptr, nullptr, nullptr, nullptr}, s);
-    if (int rc = do_step(h, actions, s)) return rc;
-  }
-  HIP_TRY(h, hipGetLastError());
-  return URGYM_OK;
-}
-
-int urgym_replay_sample(void* handle, const urgym_replay_ring* ring, int oldest_slot, int filled_steps, uint64_t seed, uint64_t draw, int count, const urgym_replay_batch* batch, void* stream) {
-  const char* who = "urgym_replay_sample";
-  Handle* h = (Handle*)handle;
-  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
-  if (int rc = check_ring(h, ring, who)) return rc;
-  if (filled_steps < 1 || filled_steps > ring->capacity_steps) return fail(h, URGYM_ERR_ARG, "urgym_replay_sample: filled_steps outside [1, capacity_steps]");
-  if (oldest_slot < 0 || oldest_slot >= ring->capacity_steps) return fail(h, URGYM_ERR_ARG, "urgym_replay_sample: oldest_slot outside [0, capacity_steps)");
-  if (count <= 0) return fail(h, URGYM_ERR_ARG, "urgym_replay_sample: count must be positive");
-  if (!batch) return fail(h, URGYM_ERR_ARG, "urgym_replay_sample: null batch");
-  const urgym_replay_batch& b = *batch;
-  if (!b.observation && !b.achieved_goal && !b.desired_goal && !b.action && !b.reward && !b.next_observation && !b.next_achieved_goal &&
-      !b.next_desired_goal && !b.terminated && !b.truncated && !b.is_success && !b.index)
-    return fail(h, URGYM_ERR_ARG, "urgym_replay_sample: no output requested (every batch pointer is null)");
-  if ((b.truncated && !ring->truncated) || (b.is_success && !ring->is_success))
-    return fail(h, URGYM_ERR_ARG, "urgym_replay_sample: truncated / is_success asked from a ring that does not keep it");
-  HIP_TRY(h, hipSetDevice(h->device));
-  ReplayGather g;
-  g.N = h->cfg.num_envs, g.obs_dim = h->obs_dim, g.goal_dim = h->goal_dim, g.capacity = ring->capacity_steps;
-  g.oldest_slot = oldest_slot, g.count = count;
-  g.size = (uint64_t)filled_steps * (uint64_t)h->cfg.num_envs;
-  g.seed = seed, g.draw = draw;
-  g.ring = *ring, g.batch = b;
-  replay_gather_launch(g, (hipStream_t)stream);
-  HIP_TRY(h, hipGetLastError());
-  return URGYM_OK;
-}
-
-int urgym_critic_create(void* handle, const urgym_critic_desc* desc, void** critic) {
-  Handle* h = (Handle*)handle;
-  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
-  if (!critic) return fail(h, URGYM_ERR_ARG, "urgym_critic_create: null argument");
-  HIP_TRY(h, hipSetDevice(h->device));
-  Critic* c = nullptr;
-  if (int rc = critic_create(desc, actor_features(h) + 6, &c, h->err, sizeof(h->err))) return rc;
-  h->critics.push_back(c);
-  *critic = c;
-  return URGYM_OK;
-}
-
-int urgym_critic_destroy(void* handle, void* critic) {
-  Handle* h = (Handle*)handle;
-  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
-  if (!critic) return URGYM_OK;
-  for (size_t i = 0; i < h->critics.size(); i++)
-    if (h->critics[i] == critic) {
-      hipSetDevice(h->device);
-      hipDeviceSynchronize();  // launches that read its weights may still be in flight
-      critic_destroy(h->critics[i]);
-      h->critics.erase(h->critics.begin() + i);
-      return URGYM_OK;
-    }
-  return fail(h, URGYM_ERR_ARG, "urgym_critic_destroy: not a critic of this handle");
-}
-
-int urgym_critic_evaluate(void* handle, void* critic, const urgym_critic_rows* rows, int count, const urgym_critic_terms* terms, const urgym_critic_out* out, void* stream) {
-  const char* who = "urgym_critic_evaluate";
-  Handle* h = (Handle*)handle;
-  if (int rc = enter_bound(h)) return rc;
-  Critic* c = nullptr;
-  for (Critic* x : h->critics)
-    if (x == critic) c = x;
-  if (!c) return fail(h, URGYM_ERR_ARG, "urgym_critic_evaluate: not a critic of this handle (critics belong to the handle they were created with)");
-  if (critic_in_features(c) != actor_features(h) + 6) return fail(h, URGYM_ERR_ARG, "urgym_critic_evaluate: the critic does not take this env kind's features");
-  CriticCall call;
-  memset(&call, 0, sizeof(call));
-  if (int rc = resolve_rows(h, rows, count, who, &call.observation, &call.achieved_goal, &call.desired_goal)) return rc;
-  if (!rows->action) return fail(h, URGYM_ERR_ARG, "urgym_critic_evaluate: rows->action is null");
-  if (!out) return fail(h, URGYM_ERR_ARG, "urgym_critic_evaluate: null out");
-  if (!out->q && !out->q_min && !out->target) return fail(h, URGYM_ERR_ARG, "urgym_critic_evaluate: no output requested (q, q_min and target are all null)");
-  if (out->target && (!terms || !terms->reward)) return fail(h, URGYM_ERR_ARG, "urgym_critic_evaluate: target requested without terms->reward");
-  call.M = count, call.obs_dim = h->obs_dim, call.goal_dim = h->goal_dim;
-  call.action = rows->action;
-  if (terms && out->target) {
-    call.reward = terms->reward, call.terminated = terms->terminated, call.log_prob = terms->log_prob;
-    call.gamma = terms->gamma, call.ent_coef = terms->ent_coef;
-  }
-  call.q = out->q, call.q_min = out->q_min, call.target = out->target;
-  critic_launch(c, call, (hipStream_t)stream);
-  HIP_TRY(h, hipGetLastError());
-  return URGYM_OK;
-}
-
-int urgym_critic_action_gradient(void* handle, void* critic, const urgym_critic_rows* rows, int count, const urgym_critic_grad_out* out, void* stream) {
-  const char* who = "urgym_critic_action_gradient";
-  Handle* h = (Handle*)handle;
-  if (int rc = enter_bound(h)) return rc;
-  Critic* c = find_critic(h, critic);
-  if (!c) return fail(h, URGYM_ERR_ARG, "urgym_critic_action_gradient: not a critic of this handle (critics belong to the handle they were created with)");
-  if (critic_in_features(c) != actor_features(h) + 6) return fail(h, URGYM_ERR_ARG, "urgym_critic_action_gradient: the critic does not take this env kind's features");
-  if (!critic_grad_supported(c)) return fail(h, URGYM_ERR_ARG, "urgym_critic_action_gradient: the gradient kernel is built for hidden widths up to 256");
-  CriticGradCall call;
-  memset(&call, 0, sizeof(call));
-  if (int rc = resolve_rows(h, rows, count, who, &call.observation, &call.achieved_goal, &call.desired_goal)) return rc;
-  if (!rows->action) return fail(h, URGYM_ERR_ARG, "urgym_critic_action_gradient: rows->action is null");
-  if (!out) return fail(h, URGYM_ERR_ARG, "urgym_critic_action_gradient: null out");
-  if (!out->dq_da && !out->dqmin_da) return fail(h, URGYM_ERR_ARG, "urgym_critic_action_gradient: no gradient requested (dq_da and dqmin_da are both null)");
-  call.M = count, call.obs_dim = h->obs_dim, call.goal_dim = h->goal_dim;
-  call.action = rows->action;
-  call.dq_da = out->dq_da, call.dqmin_da = out->dqmin_da, call.q = out->q, call.q_min = out->q_min;
-  critic_grad_launch(c, call, (hipStream_t)stream);
-  HIP_TRY(h, hipGetLastError());
-  return URGYM_OK;
-}
-
-// the checks urgym_critic_parameter_gradients and its workspace query share: the critic is one of this handle's, takes this env kind's
-// features, is no wider than the kernels are built for, and count is within [1, URGYM_CRITIC_GRADIENTS_MAX_COUNT]
-static int backward_critic(Handle* h, void* critic, int count, const char* who, Critic** out) {
-  static_assert(URGYM_CRITIC_GRADIENTS_MAX_COUNT == CRITIC_BACKWARD_MAX_COUNT, "include/urgym.h");
-  char msg[200];
-  const char* what = nullptr;
-  Critic* c = find_critic(h, critic);
-  if (!c) what = "not a critic of this handle (critics belong to the handle they were created with)";
-  else if (critic_in_features(c) != actor_features(h) + 6) what = "the critic does not take this env kind's features";
-  else if (!critic_backward_supported(c)) what = "the gradient kernels are built for hidden widths up to 256";
-  else if (count <= 0) what = "count must be positive";
-  else if (count > CRITIC_BACKWARD_MAX_COUNT) what = "count is above URGYM_CRITIC_GRADIENTS_MAX_COUNT (65536)";
-  if (what) {
-    snprintf(msg, sizeof(msg), "%s: %s", who, what);
-    return fail(h, URGYM_ERR_ARG, msg);
-  }
-  *out = c;
-  return URGYM_OK;
-}
-
-int urgym_critic_parameter_gradients_workspace(void* handle, void* critic, int count, uint64_t* bytes) {
-  const char* who = "urgym_critic_parameter_gradients_workspace";
-  Handle* h = (Handle*)handle;
-  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
-  if (!bytes) return fail(h, URGYM_ERR_ARG, "urgym_critic_parameter_gradients_workspace: null bytes");
-  Critic* c = nullptr;
-  if (int rc = backward_critic(h, critic, count, who, &c)) return rc;
-  *bytes = critic_backward_workspace_bytes(c, count);
-  return URGYM_OK;
-}
-
-int urgym_critic_parameter_gradients(void* handle, void* critic, const urgym_critic_rows* rows, int count, const float* dq, const float* target, float scale, const urgym_critic_param_grads* out, void* workspace, uint64_t workspace_bytes, void* stream) {
-  const char* who = "urgym_critic_parameter_gradients";
-  Handle* h = (Handle*)handle;
-  if (int rc = enter_bound(h)) return rc;
-  Critic* c = nullptr;
-  CriticBackwardCall call;
-  memset(&call, 0, sizeof(call));
-  if (int rc = backward_critic(h, critic, count, who, &c)) return rc;
-  if (int rc = resolve_rows(h, rows, count, who, &call.observation, &call.achieved_goal, &call.desired_goal)) return rc;
-  if (!rows->action) return fail(h, URGYM_ERR_ARG, "urgym_critic_parameter_gradients: rows->action is null");
-  if ((dq != nullptr) == (target != nullptr)) return fail(h, URGYM_ERR_ARG, "urgym_critic_parameter_gradients: exactly one of dq and target must be given");
-  if (target && !(fabsf(scale) < INFINITY)) return fail(h, URGYM_ERR_ARG, "urgym_critic_parameter_gradients: scale must be finite");
-  if (!out) return fail(h, URGYM_ERR_ARG, "urgym_critic_parameter_gradients: null out");
-  for (int net = 0; net < 2; net++) {
-    const urgym_q_network_grad& g = out->qf[net];
-    float* one[6] = {g.w0, g.b0, g.w1, g.b1, g.w_q, g.b_q};
-    for (int i = 0; i < 6; i++) {
-      if (!one[i]) return fail(h, URGYM_ERR_ARG, "urgym_critic_parameter_gradients: a gradient pointer is null (all twelve are required)");
-      call.grad[net][i] = one[i];
-    }
-  }
-  if (!workspace) return fail(h, URGYM_ERR_ARG, "urgym_critic_parameter_gradients: null workspace");
-  if ((uintptr_t)workspace % 16 != 0) return fail(h, URGYM_ERR_ARG, "urgym_critic_parameter_gradients: the workspace must be 16-byte aligned");
-  if (workspace_bytes < critic_backward_workspace_bytes(c, count))
-    return fail(h, URGYM_ERR_ARG, "urgym_critic_parameter_gradients: the workspace is smaller than urgym_critic_parameter_gradients_workspace reports");
-  call.M = count, call.obs_dim = h->obs_dim, call.goal_dim = h->goal_dim;
-  call.action = rows->action;
-  call.dq = dq, call.target = target, call.scale = target ? scale : 0.0f;
-  call.q = out->q, call.workspace = (float*)workspace;
-  critic_backward_launch(c, call, (hipStream_t)stream);
-  HIP_TRY(h, hipGetLastError());
-  return URGYM_OK;
-}
-
 int urgym_probe_closest(void* handle, int count, const int* type_a, const double* par_a, const double* pose_a, const int* type_b,
                         const double* par_b, const double* pose_b, double threshold, double* out_dist, int* out_info, void* stream) {
   Handle* h = (Handle*)handle;
@@ -2663,8 +2016,7 @@ int urgym_probe_closest(void* handle, int count, const int* type_a, const double
   g.recs = h->d_recs; g.cell = h->d_cell;
   hipLaunchKernelGGL(probe_closest_kernel, dim3((count + 63) / 64), dim3(64), 0, (hipStream_t)stream, g, count, type_a, par_a, pose_a,
                      type_b, par_b, pose_b, threshold, out_dist, out_info);
-  HIP_TRY(h, hipGetLastError());
-  return URGYM_OK;
+  return launched(h);
 }
 
 int urgym_probe_pose_distance(void* handle, int count, const double* a6, const double* b6, double* out2, void* stream) {
@@ -2673,8 +2025,7 @@ int urgym_probe_pose_distance(void* handle, int count, const double* a6, const d
   HIP_TRY(h, hipSetDevice(h->device));
   if (count == 0) return URGYM_OK;
   hipLaunchKernelGGL(probe_pose_distance_kernel, dim3((count + 63) / 64), dim3(64), 0, (hipStream_t)stream, count, a6, b6, out2);
-  HIP_TRY(h, hipGetLastError());
-  return URGYM_OK;
+  return launched(h);
 }
 
 int urgym_enable_timing(void* handle, int enable) {

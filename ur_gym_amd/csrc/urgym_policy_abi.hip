@@ -1,0 +1,541 @@
+// urgym_policy_abi.hip — the learner's half of the C-ABI of include/urgym.h: actors (create / forward / sample / rollouts), the replay
+// ring, the weight reloads, the twin critic and its two gradients.  Host code only: every check is made here, before the first launch,
+// and every launch goes through urgym_actor.h, urgym_critic.h, urgym_replay.h and urgym_weights.h, or through do_step of urgym_hip.hip
+// (urgym_handle.h).  No kernel lives in this unit, so adding a check here leaves the step kernels' object file alone.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+
+#include "../../include/urgym.h"
+#include "urgym_handle.h"
+#include "urgym_actor.h"
+#include "urgym_critic.h"
+#include "urgym_pack_map.h"
+#include "urgym_weights.h"
+#include "urgym_replay.h"
+
+using namespace urgym;
+
+// every failure path of urgym_create and urgym_destroy (release() of urgym_hip.hip)
+void urgym::release_policies(Handle* h) {
+  for (Actor* a : h->actors) actor_destroy(a);
+  for (Critic* c : h->critics) critic_destroy(c);
+}
+
+namespace {
+
+const char* const NOT_OBSERVED = "no observations yet: call urgym_reset (or urgym_refresh) first";
+
+// p as a T* if it is an element of v -- an actor or a critic of THIS handle, still alive -- else null
+template <class T>
+T* member(const std::vector<T*>& v, const void* p) {
+  return std::find(v.begin(), v.end(), p) != v.end() ? (T*)p : nullptr;
+}
+
+// urgym_actor_destroy / urgym_critic_destroy
+template <class T>
+int destroy_member(Handle* h, std::vector<T*>& v, void* p, void (*destroy)(T*), const char* refusal) {
+  if (!p) return URGYM_OK;
+  T* x = member(v, p);
+  if (!x) return fail(h, URGYM_ERR_ARG, refusal);
+  hipSetDevice(h->device);
+  hipDeviceSynchronize();  // launches that read its weights may still be in flight
+  destroy(x);
+  v.erase(std::find(v.begin(), v.end(), x));
+  return URGYM_OK;
+}
+
+// ---- policies: the checks and the per-pass arguments of the entry points that run an actor
+
+int actor_features(const Handle* h) { return h->obs_dim + 2 * h->goal_dim; }
+
+ActorEnv actor_env(const Handle* h) {
+  const urgym_buffers& b = h->buf;
+  return ActorEnv{h->cfg.num_envs, h->obs_dim, h->goal_dim, h->cfg.auto_reset, b.observation, b.achieved_goal, b.desired_goal,
+                  b.reward, b.final_observation, b.terminated, b.truncated, b.is_success, b.collision};
+}
+
+// the records of pass k (ActorPass): rows k of what the actor sees, rows k - 1 of what the step before returned
+ActorPass actor_pass(const Handle* h, Actor* a, const urgym_trajectory& t, int k, int num_steps) {
+  const size_t n = (size_t)h->cfg.num_envs, od = (size_t)h->obs_dim, gd = (size_t)h->goal_dim;
+  const size_t pre = (size_t)k * n, post = (size_t)(k > 0 ? k - 1 : 0) * n;
+  auto at = [](auto* p, size_t off) { return p ? p + off : p; };
+  ActorPass r;
+  r.obs = at(t.observation, pre * od), r.ach = at(t.achieved_goal, pre * gd), r.des = at(t.desired_goal, pre * gd);
+  r.reward = at(t.reward, post);
+  r.terminated = at(t.terminated, post), r.truncated = at(t.truncated, post), r.is_success = at(t.is_success, post);
+  r.collision = at(t.collision, post);
+  r.final_obs = at(t.final_observation, post * od);
+  r.ep_return = t.episode_return, r.ep_last = t.episode_last_step, r.ep_success = t.episode_success;
+  const bool summary = t.episode_return || t.episode_last_step || t.episode_success || t.episode_done;
+  r.ep_done = t.episode_done ? t.episode_done : (summary ? actor_done_scratch(a) : nullptr);
+  r.k = k, r.num_steps = num_steps;
+  return r;
+}
+
+// The checks of every entry point that runs an actor; *out = the actor.  One that reads the bound buffers (own_rows null) is refused
+// with both feature counts, and before anything has been observed.  One that takes the caller's rows words the feature refusal itself
+// (own_rows) and leaves the observations to resolve_rows.
+int enter_actor(Handle* h, void* actor, const char* who, Actor** out, const char* own_rows = nullptr) {
+  if (int rc = enter_bound(h)) return rc;
+  Actor* a = member(h->actors, actor);
+  if (!a) return fail_in(h, URGYM_ERR_ARG, who, "not an actor of this handle (actors belong to the handle they were created with)");
+  if (actor_in_features(a) != actor_features(h)) {
+    if (own_rows) return fail_in(h, URGYM_ERR_ARG, who, own_rows);
+    return failf(h, URGYM_ERR_ARG, "%s: the actor takes %d features, this env kind offers %d", who, actor_in_features(a), actor_features(h));
+  }
+  if (!own_rows && !h->observed) return fail_in(h, URGYM_ERR_STATE, who, NOT_OBSERVED);
+  *out = a;
+  return URGYM_OK;
+}
+
+// the checks of every entry point that samples; wants_density: a log-probability or a sample record is asked for
+int check_sampling(Handle* h, const Actor* a, const urgym_sampling* how, bool wants_density, const char* who) {
+  const char* what = nullptr;
+  if (!how) what = "null sampling description";
+  else if (how->reserved0 != 0) what = "urgym_sampling.reserved0 must be 0";
+  else if (how->mode != URGYM_SAMPLE_MEAN && how->mode != URGYM_SAMPLE_GAUSSIAN && how->mode != URGYM_SAMPLE_UNIFORM)
+    what = "unknown sampling mode (URGYM_SAMPLE_MEAN, _GAUSSIAN or _UNIFORM)";
+  else if (!actor_has_log_std(a) && (how->mode == URGYM_SAMPLE_GAUSSIAN || (how->mode == URGYM_SAMPLE_MEAN && wants_density)))
+    what = "the actor has no log_std head (urgym_actor_set_log_std)";
+  return what ? fail_in(h, URGYM_ERR_ARG, who, what) : URGYM_OK;
+}
+
+// The one launch of a policy pass.  MEAN with no density asked for (no log-probability, no sample record) is the deterministic kernel.
+void policy_launch(Actor* a, const ActorEnv& env, float* actions, const ActorPass* pass, const ActorSample& smp, hipStream_t s) {
+  if (smp.mode == URGYM_SAMPLE_MEAN && !smp.log_prob && !smp.noise && !smp.mean_action && !smp.log_std)
+    actor_launch(a, env, actions, pass, s);
+  else
+    actor_launch_sampled(a, env, actions, pass, smp, s);
+}
+
+// ---- explicit rows (the critic's entry points, urgym_actor_sample_rows): the checks that concern rows and count; on success obs / ach /
+// des are the pointers to read (the bound buffers where rows->observation is null)
+int resolve_rows(Handle* h, const urgym_critic_rows* rows, int count, const char* who, const float** obs, const float** ach, const float** des) {
+  const char* what = nullptr;
+  if (!rows) what = "null rows";
+  else if (count <= 0) what = "count must be positive";
+  else if (!rows->observation && count != h->cfg.num_envs) what = "rows->observation is null (the bound buffers): count must be num_envs";
+  else if (rows->observation && (!rows->achieved_goal || !rows->desired_goal)) what = "rows->achieved_goal or rows->desired_goal is null";
+  if (what) return fail_in(h, URGYM_ERR_ARG, who, what);
+  const bool bound = !rows->observation;
+  if (bound && !h->observed) return fail_in(h, URGYM_ERR_STATE, who, NOT_OBSERVED);
+  *obs = bound ? h->buf.observation : rows->observation;
+  *ach = bound ? h->buf.achieved_goal : rows->achieved_goal;
+  *des = bound ? h->buf.desired_goal : rows->desired_goal;
+  return URGYM_OK;
+}
+
+// ---- the replay ring (urgym_rollout_collect, urgym_replay_sample): the checks that concern the ring itself
+int check_ring(Handle* h, const urgym_replay_ring* r, const char* who) {
+  const char* what = nullptr;
+  if (!r) what = "null ring";
+  else if (r->capacity_steps <= 0) what = "ring->capacity_steps must be positive";
+  else if (r->reserved0 != 0) what = "urgym_replay_ring.reserved0 must be 0";
+  else if (!r->observation || !r->achieved_goal || !r->desired_goal || !r->action || !r->reward || !r->next_observation ||
+           !r->next_achieved_goal || !r->next_desired_goal || !r->terminated)
+    what = "a required ring pointer is null (all but truncated and is_success)";
+  return what ? fail_in(h, URGYM_ERR_ARG, who, what) : URGYM_OK;
+}
+
+// the store pass before step k of a collection that started at first_slot: the s of slot k (k < num_steps), the outcome of slot k - 1
+ReplayStore replay_store(const Handle* h, const urgym_replay_ring& r, int first_slot, int k, int num_steps) {
+  const urgym_buffers& b = h->buf;
+  const size_t n = (size_t)h->cfg.num_envs, od = (size_t)h->obs_dim, gd = (size_t)h->goal_dim, C = (size_t)r.capacity_steps;
+  ReplayStore p;
+  memset(&p, 0, sizeof(p));
+  p.N = h->cfg.num_envs, p.obs_dim = h->obs_dim, p.goal_dim = h->goal_dim, p.auto_reset = h->cfg.auto_reset;
+  p.observation = b.observation, p.achieved_goal = b.achieved_goal, p.desired_goal = b.desired_goal, p.reward = b.reward;
+  p.final_observation = b.final_observation, p.final_achieved_goal = b.final_achieved_goal, p.final_desired_goal = b.final_desired_goal;
+  p.terminated = b.terminated, p.truncated = b.truncated, p.is_success = b.is_success;
+  if (k < num_steps) {
+    const size_t at = (((size_t)first_slot + (size_t)k) % C) * n;
+    p.obs = r.observation + at * od, p.ach = r.achieved_goal + at * gd, p.des = r.desired_goal + at * gd;
+  }
+  if (k > 0) {
+    const size_t at = (((size_t)first_slot + (size_t)k - 1) % C) * n;
+    p.reward_out = r.reward + at, p.terminated_out = r.terminated + at;
+    p.truncated_out = r.truncated ? r.truncated + at : nullptr, p.is_success_out = r.is_success ? r.is_success + at : nullptr;
+    p.next_obs = r.next_observation + at * od, p.next_ach = r.next_achieved_goal + at * gd, p.next_des = r.next_desired_goal + at * gd;
+  }
+  return p;
+}
+
+// ---- the rollout loop of urgym_rollout_actor, urgym_rollout_sampled and urgym_rollout_collect
+
+// What a rollout keeps besides stepping; every pointer may be null.  A ring excludes the two kinds of records.
+struct RolloutSinks {
+  const urgym_trajectory* traj;
+  const urgym_sample_records* extra;
+  const urgym_replay_ring* ring;  // its slots (first_slot + k) % capacity_steps
+  int first_slot;
+};
+
+// num_steps policy passes, each followed by its step, and a closing pass for the outcome of the last step; the callers have checked
+// everything.  how: null = the deterministic actor.
+// Every launch below goes to `s`, and so does everything do_step launches (the step or fused launch, the RESET / PREFETCH fallbacks of
+// a dirty step, the timing events): stream order alone puts step k - 1 before the passes that read its outputs (the store pass files
+// its outcome, the actor's pass records it) and those before the step that reads their actions.
+int rollout(Handle* h, Actor* a, const urgym_sampling* how, int num_steps, const RolloutSinks& to, hipStream_t s) {
+  if (num_steps == 0) return URGYM_OK;
+  const ActorEnv env = actor_env(h);
+  const size_t n = (size_t)h->cfg.num_envs, row = n * 6;
+  auto at = [](float* p, size_t off) { return p ? p + off : p; };
+  for (int k = 0; k <= num_steps; k++) {
+    if (to.ring) replay_store_launch(replay_store(h, *to.ring, to.first_slot, k, num_steps), s);
+    ActorPass pass;
+    if (to.traj) pass = actor_pass(h, a, *to.traj, k, num_steps);
+    if (k == num_steps) {
+      if (to.traj) actor_launch(a, env, nullptr, &pass, s);  // the result of the last step; no forward pass
+      break;
+    }
+    float* actions = actor_action_scratch(a);
+    if (to.ring)  // the actor writes the slot, the step reads it
+      actions = to.ring->action + (size_t)((to.first_slot + (int64_t)k) % to.ring->capacity_steps) * row;
+    else if (to.traj && to.traj->action)
+      actions = to.traj->action + (size_t)k * row;
+    ActorSample smp{how ? how->mode : URGYM_SAMPLE_MEAN, how ? how->seed : 0, how ? how->first_draw + (uint64_t)k : 0, nullptr, nullptr, nullptr, nullptr};
+    if (to.extra) {
+      smp.log_prob = at(to.extra->log_prob, (size_t)k * n), smp.noise = at(to.extra->noise, (size_t)k * row);
+      smp.mean_action = at(to.extra->mean_action, (size_t)k * row), smp.log_std = at(to.extra->log_std, (size_t)k * row);
+    }
+    policy_launch(a, env, actions, to.traj ? &pass : nullptr, smp, s);
+    if (int rc = do_step(h, actions, s)) return rc;
+  }
+  return launched(h);
+}
+
+// ---- the twin critic
+
+// The checks of every entry point that runs a critic: one of this handle's, taking this env kind's features and, where the kernels of
+// the call are built for some widths only (supported), one of those; *out = the critic
+int enter_critic(Handle* h, void* critic, const char* who, Critic** out, bool (*supported)(Critic*) = nullptr, const char* unsupported = nullptr) {
+  Critic* c = member(h->critics, critic);
+  if (!c) return fail_in(h, URGYM_ERR_ARG, who, "not a critic of this handle (critics belong to the handle they were created with)");
+  if (critic_in_features(c) != actor_features(h) + 6) return fail_in(h, URGYM_ERR_ARG, who, "the critic does not take this env kind's features");
+  if (supported && !supported(c)) return fail_in(h, URGYM_ERR_ARG, who, unsupported);
+  *out = c;
+  return URGYM_OK;
+}
+
+// the rows of a critic call (its first fields are CriticCall's in all three kinds): resolve_rows, then the action and the sizes
+template <class Call>
+int critic_rows(Handle* h, const urgym_critic_rows* rows, int count, const char* who, Call* call) {
+  memset(call, 0, sizeof(*call));
+  if (int rc = resolve_rows(h, rows, count, who, &call->observation, &call->achieved_goal, &call->desired_goal)) return rc;
+  if (!rows->action) return fail_in(h, URGYM_ERR_ARG, who, "rows->action is null");
+  call->M = count, call->obs_dim = h->obs_dim, call->goal_dim = h->goal_dim;
+  call->action = rows->action;
+  return URGYM_OK;
+}
+
+// the checks urgym_critic_parameter_gradients and its workspace query share: enter_critic with the widths the kernels are built for,
+// and count within [1, URGYM_CRITIC_GRADIENTS_MAX_COUNT]
+int backward_critic(Handle* h, void* critic, int count, const char* who, Critic** out) {
+  static_assert(URGYM_CRITIC_GRADIENTS_MAX_COUNT == CRITIC_BACKWARD_MAX_COUNT, "include/urgym.h");
+  if (int rc = enter_critic(h, critic, who, out, critic_backward_supported, "the gradient kernels are built for hidden widths up to 256")) return rc;
+  if (count <= 0) return fail_in(h, URGYM_ERR_ARG, who, "count must be positive");
+  if (count > CRITIC_BACKWARD_MAX_COUNT) return fail_in(h, URGYM_ERR_ARG, who, "count is above URGYM_CRITIC_GRADIENTS_MAX_COUNT (65536)");
+  return URGYM_OK;
+}
+
+// urgym_actor_read_packed / urgym_critic_read_packed
+int read_packed(Handle* h, const char* who, const float* dev, size_t floats, float* host_out, uint64_t capacity, uint64_t* count) {
+  if (!count) return fail_in(h, URGYM_ERR_ARG, who, "null count");
+  *count = floats;
+  if (!host_out) return URGYM_OK;
+  if (capacity < floats)
+    return failf(h, URGYM_ERR_ARG, "%s: capacity is %llu floats, the packed buffer has %llu", who, (unsigned long long)capacity, (unsigned long long)floats);
+  HIP_TRY(h, hipSetDevice(h->device));
+  HIP_TRY(h, hipDeviceSynchronize());
+  HIP_TRY(h, hipMemcpy(host_out, dev, floats * sizeof(float), hipMemcpyDeviceToHost));
+  return URGYM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- weights from the device (urgym_weights.hip): everything is checked here, before the launch
+int urgym_actor_load(void* handle, void* actor, const urgym_actor_params_dev* p, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  Actor* a = member(h->actors, actor);
+  if (!a) return fail(h, URGYM_ERR_ARG, "urgym_actor_load: not an actor of this handle (actors belong to the handle they were created with)");
+  if (!p) return fail(h, URGYM_ERR_ARG, "urgym_actor_load: null params");
+  if (p->reserved0 != 0) return fail(h, URGYM_ERR_ARG, "urgym_actor_load: reserved0 must be 0");
+  const ActorPacked buf = actor_packed(a);
+  if (p->in_features != buf.in_features || p->hidden_width != buf.hidden)
+    return failf(h, URGYM_ERR_ARG, "urgym_actor_load: params are %d -> %d, the actor is %d -> %d", p->in_features, p->hidden_width, buf.in_features, buf.hidden);
+  if (!p->w0 || !p->b0 || !p->w1 || !p->b1 || !p->w_mu || !p->b_mu) return fail(h, URGYM_ERR_ARG, "urgym_actor_load: a weight or bias pointer is null");
+  if (!p->w_log_std != !p->b_log_std) return fail(h, URGYM_ERR_ARG, "urgym_actor_load: the log_std head needs both w_log_std and b_log_std, or neither");
+  HIP_TRY(h, hipSetDevice(h->device));
+  const float* src[PACK_ACTOR_TENSORS] = {p->w0, p->b0, p->w1, p->b1, p->w_mu, p->b_mu, p->w_log_std, p->b_log_std};
+  actor_pack_launch(buf, src, (hipStream_t)stream);
+  HIP_TRY(h, hipGetLastError());
+  if (p->w_log_std) actor_mark_log_std(a);  // the checks of later calls are made in program order, which is stream order for this stream
+  return URGYM_OK;
+}
+
+int urgym_critic_load(void* handle, void* critic, const urgym_critic_params_dev* p, float tau, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  Critic* c = member(h->critics, critic);
+  if (!c) return fail(h, URGYM_ERR_ARG, "urgym_critic_load: not a critic of this handle (critics belong to the handle they were created with)");
+  if (!p) return fail(h, URGYM_ERR_ARG, "urgym_critic_load: null params");
+  if (p->reserved0 != 0) return fail(h, URGYM_ERR_ARG, "urgym_critic_load: reserved0 must be 0");
+  if (!(tau > 0.0f && tau <= 1.0f)) return fail(h, URGYM_ERR_ARG, "urgym_critic_load: tau must be in (0, 1]");  // refuses NaN too
+  const CriticPacked buf = critic_packed(c);
+  if (p->in_features != buf.in_features || p->hidden_width != buf.hidden)
+    return failf(h, URGYM_ERR_ARG, "urgym_critic_load: params are %d -> %d, the critic is %d -> %d", p->in_features, p->hidden_width, buf.in_features, buf.hidden);
+  const float* src[2 * PACK_CRITIC_TENSORS];
+  for (int net = 0; net < 2; net++) {
+    const urgym_q_network_dev& q = p->qf[net];
+    if (!q.w0 || !q.b0 || !q.w1 || !q.b1 || !q.w_q || !q.b_q) return fail(h, URGYM_ERR_ARG, "urgym_critic_load: a weight or bias pointer is null");
+    const float* one[PACK_CRITIC_TENSORS] = {q.w0, q.b0, q.w1, q.b1, q.w_q, q.b_q};
+    for (int i = 0; i < PACK_CRITIC_TENSORS; i++) src[PACK_CRITIC_TENSORS * net + i] = one[i];
+  }
+  HIP_TRY(h, hipSetDevice(h->device));
+  critic_pack_launch(buf, src, tau, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_actor_read_packed(void* handle, void* actor, float* host_out, uint64_t capacity, uint64_t* count) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  Actor* a = member(h->actors, actor);
+  if (!a) return fail(h, URGYM_ERR_ARG, "urgym_actor_read_packed: not an actor of this handle");
+  const ActorPacked buf = actor_packed(a);
+  return read_packed(h, "urgym_actor_read_packed", buf.weights, buf.floats, host_out, capacity, count);
+}
+
+int urgym_critic_read_packed(void* handle, void* critic, float* host_out, uint64_t capacity, uint64_t* count) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  Critic* c = member(h->critics, critic);
+  if (!c) return fail(h, URGYM_ERR_ARG, "urgym_critic_read_packed: not a critic of this handle");
+  const CriticPacked buf = critic_packed(c);
+  return read_packed(h, "urgym_critic_read_packed", buf.weights, buf.floats, host_out, capacity, count);
+}
+
+int urgym_actor_create(void* handle, const urgym_actor_desc* desc, void** actor) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (!actor) return fail(h, URGYM_ERR_ARG, "urgym_actor_create: null argument");
+  HIP_TRY(h, hipSetDevice(h->device));
+  Actor* a = nullptr;
+  if (int rc = actor_create(desc, actor_features(h), h->cfg.num_envs, &a, h->err, sizeof(h->err))) return rc;
+  h->actors.push_back(a);
+  *actor = a;
+  return URGYM_OK;
+}
+
+int urgym_actor_destroy(void* handle, void* actor) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  return destroy_member(h, h->actors, actor, actor_destroy, "urgym_actor_destroy: not an actor of this handle");
+}
+
+int urgym_actor_forward(void* handle, void* actor, float* actions_dev, void* stream) {
+  Handle* h = (Handle*)handle;
+  Actor* a = nullptr;
+  if (int rc = enter_actor(h, actor, "urgym_actor_forward", &a)) return rc;
+  if (!actions_dev) return fail(h, URGYM_ERR_ARG, "urgym_actor_forward: null actions");
+  actor_launch(a, actor_env(h), actions_dev, nullptr, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_rollout_actor(void* handle, void* actor, int num_steps, const urgym_trajectory* traj, void* stream) {
+  Handle* h = (Handle*)handle;
+  Actor* a = nullptr;
+  if (int rc = enter_actor(h, actor, "urgym_rollout_actor", &a)) return rc;
+  if (num_steps < 0) return fail(h, URGYM_ERR_ARG, "urgym_rollout_actor: num_steps < 0");
+  return rollout(h, a, nullptr, num_steps, RolloutSinks{traj, nullptr, nullptr, 0}, (hipStream_t)stream);
+}
+
+int urgym_actor_set_log_std(void* handle, void* actor, const float* w_log_std, const float* b_log_std) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  Actor* a = member(h->actors, actor);
+  if (!a) return fail(h, URGYM_ERR_ARG, "urgym_actor_set_log_std: not an actor of this handle");
+  if (!w_log_std || !b_log_std) return fail(h, URGYM_ERR_ARG, "urgym_actor_set_log_std: a weight or bias pointer is null");
+  HIP_TRY(h, hipSetDevice(h->device));
+  HIP_TRY(h, hipDeviceSynchronize());  // launches that read the head may still be in flight
+  return actor_set_log_std(a, w_log_std, b_log_std, h->err, sizeof(h->err));
+}
+
+int urgym_actor_sample(void* handle, void* actor, const urgym_sampling* how, float* actions_dev, float* log_prob_dev, void* stream) {
+  Handle* h = (Handle*)handle;
+  Actor* a = nullptr;
+  if (int rc = enter_actor(h, actor, "urgym_actor_sample", &a)) return rc;
+  if (int rc = check_sampling(h, a, how, log_prob_dev != nullptr, "urgym_actor_sample")) return rc;
+  if (!actions_dev) return fail(h, URGYM_ERR_ARG, "urgym_actor_sample: null actions");
+  policy_launch(a, actor_env(h), actions_dev, nullptr, ActorSample{how->mode, how->seed, how->first_draw, log_prob_dev, nullptr, nullptr, nullptr},
+                (hipStream_t)stream);
+  return launched(h);
+}
+
+// With mode MEAN and no sample record asked for, every policy pass is the deterministic kernel: the launches of urgym_rollout_actor.
+int urgym_rollout_sampled(void* handle, void* actor, const urgym_sampling* how, int num_steps, const urgym_trajectory* traj,
+                          const urgym_sample_records* extra, void* stream) {
+  Handle* h = (Handle*)handle;
+  Actor* a = nullptr;
+  if (int rc = enter_actor(h, actor, "urgym_rollout_sampled", &a)) return rc;
+  const bool wants = extra && (extra->log_prob || extra->noise || extra->mean_action || extra->log_std);
+  if (int rc = check_sampling(h, a, how, wants, "urgym_rollout_sampled")) return rc;
+  if (num_steps < 0) return fail(h, URGYM_ERR_ARG, "urgym_rollout_sampled: num_steps < 0");
+  return rollout(h, a, how, num_steps, RolloutSinks{traj, extra, nullptr, 0}, (hipStream_t)stream);
+}
+
+int urgym_actor_sample_rows(void* handle, void* actor, const urgym_sampling* how, const urgym_critic_rows* rows, int count, float* actions_dev, float* log_prob_dev, void* stream) {
+  const char* who = "urgym_actor_sample_rows";
+  Handle* h = (Handle*)handle;
+  Actor* a = nullptr;
+  if (int rc = enter_actor(h, actor, who, &a, "the actor does not take this env kind's features")) return rc;
+  if (int rc = check_sampling(h, a, how, log_prob_dev != nullptr, who)) return rc;
+  if (!actions_dev) return fail(h, URGYM_ERR_ARG, "urgym_actor_sample_rows: null actions");
+  ActorEnv env;
+  memset(&env, 0, sizeof(env));  // no records ride in this launch: the step outputs are not read
+  if (int rc = resolve_rows(h, rows, count, who, &env.observation, &env.achieved_goal, &env.desired_goal)) return rc;
+  env.N = count, env.obs_dim = h->obs_dim, env.goal_dim = h->goal_dim;
+  policy_launch(a, env, actions_dev, nullptr, ActorSample{how->mode, how->seed, how->first_draw, log_prob_dev, nullptr, nullptr, nullptr},
+                (hipStream_t)stream);
+  return launched(h);
+}
+
+// The launches of urgym_rollout_sampled without records, a store pass before each actor and one after the last step.
+int urgym_rollout_collect(void* handle, void* actor, const urgym_sampling* how, int num_steps, const urgym_replay_ring* ring, int first_slot, void* stream) {
+  const char* who = "urgym_rollout_collect";
+  Handle* h = (Handle*)handle;
+  Actor* a = nullptr;
+  if (int rc = enter_actor(h, actor, who, &a)) return rc;
+  if (int rc = check_sampling(h, a, how, false, who)) return rc;
+  if (int rc = check_ring(h, ring, who)) return rc;
+  if (first_slot < 0 || first_slot >= ring->capacity_steps) return fail(h, URGYM_ERR_ARG, "urgym_rollout_collect: first_slot outside [0, capacity_steps)");
+  if (num_steps <= 0) return fail(h, URGYM_ERR_ARG, "urgym_rollout_collect: num_steps must be positive");
+  return rollout(h, a, how, num_steps, RolloutSinks{nullptr, nullptr, ring, first_slot}, (hipStream_t)stream);
+}
+
+int urgym_replay_sample(void* handle, const urgym_replay_ring* ring, int oldest_slot, int filled_steps, uint64_t seed, uint64_t draw, int count, const urgym_replay_batch* batch, void* stream) {
+  const char* who = "urgym_replay_sample";
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (int rc = check_ring(h, ring, who)) return rc;
+  if (filled_steps < 1 || filled_steps > ring->capacity_steps) return fail(h, URGYM_ERR_ARG, "urgym_replay_sample: filled_steps outside [1, capacity_steps]");
+  if (oldest_slot < 0 || oldest_slot >= ring->capacity_steps) return fail(h, URGYM_ERR_ARG, "urgym_replay_sample: oldest_slot outside [0, capacity_steps)");
+  if (count <= 0) return fail(h, URGYM_ERR_ARG, "urgym_replay_sample: count must be positive");
+  if (!batch) return fail(h, URGYM_ERR_ARG, "urgym_replay_sample: null batch");
+  const urgym_replay_batch& b = *batch;
+  if (!b.observation && !b.achieved_goal && !b.desired_goal && !b.action && !b.reward && !b.next_observation && !b.next_achieved_goal &&
+      !b.next_desired_goal && !b.terminated && !b.truncated && !b.is_success && !b.index)
+    return fail(h, URGYM_ERR_ARG, "urgym_replay_sample: no output requested (every batch pointer is null)");
+  if ((b.truncated && !ring->truncated) || (b.is_success && !ring->is_success))
+    return fail(h, URGYM_ERR_ARG, "urgym_replay_sample: truncated / is_success asked from a ring that does not keep it");
+  HIP_TRY(h, hipSetDevice(h->device));
+  ReplayGather g;
+  g.N = h->cfg.num_envs, g.obs_dim = h->obs_dim, g.goal_dim = h->goal_dim, g.capacity = ring->capacity_steps;
+  g.oldest_slot = oldest_slot, g.count = count;
+  g.size = (uint64_t)filled_steps * (uint64_t)h->cfg.num_envs;
+  g.seed = seed, g.draw = draw;
+  g.ring = *ring, g.batch = b;
+  replay_gather_launch(g, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_critic_create(void* handle, const urgym_critic_desc* desc, void** critic) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (!critic) return fail(h, URGYM_ERR_ARG, "urgym_critic_create: null argument");
+  HIP_TRY(h, hipSetDevice(h->device));
+  Critic* c = nullptr;
+  if (int rc = critic_create(desc, actor_features(h) + 6, &c, h->err, sizeof(h->err))) return rc;
+  h->critics.push_back(c);
+  *critic = c;
+  return URGYM_OK;
+}
+
+int urgym_critic_destroy(void* handle, void* critic) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  return destroy_member(h, h->critics, critic, critic_destroy, "urgym_critic_destroy: not a critic of this handle");
+}
+
+int urgym_critic_evaluate(void* handle, void* critic, const urgym_critic_rows* rows, int count, const urgym_critic_terms* terms, const urgym_critic_out* out, void* stream) {
+  const char* who = "urgym_critic_evaluate";
+  Handle* h = (Handle*)handle;
+  if (int rc = enter_bound(h)) return rc;
+  Critic* c = nullptr;
+  if (int rc = enter_critic(h, critic, who, &c)) return rc;
+  CriticCall call;
+  if (int rc = critic_rows(h, rows, count, who, &call)) return rc;
+  if (!out) return fail(h, URGYM_ERR_ARG, "urgym_critic_evaluate: null out");
+  if (!out->q && !out->q_min && !out->target) return fail(h, URGYM_ERR_ARG, "urgym_critic_evaluate: no output requested (q, q_min and target are all null)");
+  if (out->target && (!terms || !terms->reward)) return fail(h, URGYM_ERR_ARG, "urgym_critic_evaluate: target requested without terms->reward");
+  if (terms && out->target) {
+    call.reward = terms->reward, call.terminated = terms->terminated, call.log_prob = terms->log_prob;
+    call.gamma = terms->gamma, call.ent_coef = terms->ent_coef;
+  }
+  call.q = out->q, call.q_min = out->q_min, call.target = out->target;
+  critic_launch(c, call, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_critic_action_gradient(void* handle, void* critic, const urgym_critic_rows* rows, int count, const urgym_critic_grad_out* out, void* stream) {
+  const char* who = "urgym_critic_action_gradient";
+  Handle* h = (Handle*)handle;
+  if (int rc = enter_bound(h)) return rc;
+  Critic* c = nullptr;
+  if (int rc = enter_critic(h, critic, who, &c, critic_grad_supported, "the gradient kernel is built for hidden widths up to 256")) return rc;
+  CriticGradCall call;
+  if (int rc = critic_rows(h, rows, count, who, &call)) return rc;
+  if (!out) return fail(h, URGYM_ERR_ARG, "urgym_critic_action_gradient: null out");
+  if (!out->dq_da && !out->dqmin_da) return fail(h, URGYM_ERR_ARG, "urgym_critic_action_gradient: no gradient requested (dq_da and dqmin_da are both null)");
+  call.dq_da = out->dq_da, call.dqmin_da = out->dqmin_da, call.q = out->q, call.q_min = out->q_min;
+  critic_grad_launch(c, call, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_critic_parameter_gradients_workspace(void* handle, void* critic, int count, uint64_t* bytes) {
+  const char* who = "urgym_critic_parameter_gradients_workspace";
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (!bytes) return fail(h, URGYM_ERR_ARG, "urgym_critic_parameter_gradients_workspace: null bytes");
+  Critic* c = nullptr;
+  if (int rc = backward_critic(h, critic, count, who, &c)) return rc;
+  *bytes = critic_backward_workspace_bytes(c, count);
+  return URGYM_OK;
+}
+
+int urgym_critic_parameter_gradients(void* handle, void* critic, const urgym_critic_rows* rows, int count, const float* dq, const float* target, float scale, const urgym_critic_param_grads* out, void* workspace, uint64_t workspace_bytes, void* stream) {
+  const char* who = "urgym_critic_parameter_gradients";
+  Handle* h = (Handle*)handle;
+  if (int rc = enter_bound(h)) return rc;
+  Critic* c = nullptr;
+  CriticBackwardCall call;
+  if (int rc = backward_critic(h, critic, count, who, &c)) return rc;
+  if (int rc = critic_rows(h, rows, count, who, &call)) return rc;
+  if ((dq != nullptr) == (target != nullptr)) return fail(h, URGYM_ERR_ARG, "urgym_critic_parameter_gradients: exactly one of dq and target must be given");
+  if (target && !(fabsf(scale) < INFINITY)) return fail(h, URGYM_ERR_ARG, "urgym_critic_parameter_gradients: scale must be finite");
+  if (!out) return fail(h, URGYM_ERR_ARG, "urgym_critic_parameter_gradients: null out");
+  for (int net = 0; net < 2; net++) {
+    const urgym_q_network_grad& g = out->qf[net];
+    float* one[6] = {g.w0, g.b0, g.w1, g.b1, g.w_q, g.b_q};
+    for (int i = 0; i < 6; i++) {
+      if (!one[i]) return fail(h, URGYM_ERR_ARG, "urgym_critic_parameter_gradients: a gradient pointer is null (all twelve are required)");
+      call.grad[net][i] = one[i];
+    }
+  }
+  if (!workspace) return fail(h, URGYM_ERR_ARG, "urgym_critic_parameter_gradients: null workspace");
+  if ((uintptr_t)workspace % 16 != 0) return fail(h, URGYM_ERR_ARG, "urgym_critic_parameter_gradients: the workspace must be 16-byte aligned");
+  if (workspace_bytes < critic_backward_workspace_bytes(c, count))
+    return fail(h, URGYM_ERR_ARG, "urgym_critic_parameter_gradients: the workspace is smaller than urgym_critic_parameter_gradients_workspace reports");
+  call.dq = dq, call.target = target, call.scale = target ? scale : 0.0f;
+  call.q = out->q, call.workspace = (float*)workspace;
+  critic_backward_launch(c, call, (hipStream_t)stream);
+  return launched(h);
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // urgym_replay.h — seam between urgym_replay.hip (the store pass and the gather of the device replay ring, compiled with the flags of
-// urgym_actor.hip) and urgym_hip.hip (handle, C-ABI), beside urgym_actor.h and urgym_critic.h.  Nothing here is exported.
+// urgym_actor.hip) and urgym_policy_abi.hip (the learner's entry points), beside urgym_actor.h and urgym_critic.h.  Nothing here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

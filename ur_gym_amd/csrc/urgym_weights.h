@@ -1,5 +1,5 @@
 // urgym_weights.h — seam between urgym_weights.hip (the pack kernels that reload an actor's or a critic's packed weights from device
-// tensors, compiled with the flags of urgym_actor.hip) and urgym_hip.hip (handle, C-ABI), beside urgym_actor.h / urgym_critic.h.
+// tensors, compiled with the flags of urgym_actor.hip) and urgym_policy_abi.hip (the learner's entry points), beside urgym_actor.h / urgym_critic.h.
 // Nothing here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
