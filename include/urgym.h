@@ -590,6 +590,105 @@ int urgym_critic_parameter_gradients_workspace(void* handle, void* critic, int c
  * or workspace_bytes below the queried size. */
 int urgym_critic_parameter_gradients(void* handle, void* critic, const urgym_critic_rows* rows, int count, const float* dq, const float* target, float scale, const urgym_critic_param_grads* out, void* workspace, uint64_t workspace_bytes, void* stream);
 
+/* ---- the parameter gradients of the actor (SAC's policy loss, mean(alpha log pi(a|s) - min_i Q_i(s, a)) with a = the policy's
+ * reparameterised action, needs d loss / d parameters of the actor).  The mirror of urgym_critic_parameter_gradients.  Added WITHIN ABI
+ * version 4: no struct above changed, URGYM_ABI_VERSION did not move, the new symbols (urgym_actor_parameter_gradients,
+ * urgym_actor_parameter_gradients_workspace) are found by lookup.
+ *
+ * Per row m, with x[m] the row's features (achieved_goal | desired_goal | observation) and eps[m] the noise of (how->seed,
+ * how->first_draw, env word = m) -- zeros in mode MEAN -- everything float32:
+ *   z1 = W0 x + b0          h1 = relu(z1)
+ *   z2 = W1 h1 + b1         h2 = relu(z2)
+ *   mu = W_mu h2 + b_mu     r  = W_ls h2 + b_ls
+ *   ls = min(max(r, -20), 2)
+ *   pre = mu + exp(ls) eps  a  = tanh(pre)
+ *   log_prob = sum_j [-eps_j^2 / 2 - ls_j - log(2 pi) / 2 - log(1 - a_j^2 + 1e-6)]
+ * as "the stochastic half" above states it: `action` and `log_prob` of this call are bitwise what urgym_actor_sample_rows gives for
+ * the same `how` and rows.
+ *
+ * The upstream gradient: exactly one of two forms is given in urgym_actor_upstream.
+ *   HEADS   d_mu and d_log_std, DEVICE [count][6] each: the gradient of a loss with respect to mu and to the clamped log_std ls, used
+ *           as they are.
+ *   SAMPLE  d_action DEVICE [count][6] and d_log_prob DEVICE [count] (NULL means 0): the gradient with respect to this call's action
+ *           and log_prob outputs.  The noise is a constant (the reparameterised gradient).  Per component, each line one float32
+ *           operation rounded on its own (no fused multiply-add), in the association shown:
+ *             p = a * a
+ *             t = 1 - p
+ *             c = (2 a) / (t + 1e-6f)            (IEEE division)
+ *             A = d_action + (d_log_prob * c)
+ *             d_pre = A * t
+ *             d_mu = d_pre
+ *             e = exp(ls) * eps                  (exp(ls) is the forward pass's own value)
+ *             d_log_std = (d_pre * e) - d_log_prob
+ * The clamp:  dr = d_log_std where -20 <= r <= 2, else 0 (both edges inclusive: torch.clamp's backward; a NaN r gives 0).
+ * Backward, with the mask convention of the critics' gradients (a pre-activation of exactly 0, or NaN, has derivative 0):
+ *   d_h2 = W_mu^T d_mu + W_ls^T dr
+ *   d2   = d_h2 where z2 > 0, else 0
+ *   d1   = W1^T d2 where z1 > 0, else 0
+ * The sums over the rows, eight tensors in torch's [out][in] layout:
+ *   g_W0  = sum_m d1 x^T       g_b0  = sum_m d1
+ *   g_W1  = sum_m d2 h1^T      g_b1  = sum_m d2
+ *   g_Wmu = sum_m d_mu h2^T    g_bmu = sum_m d_mu
+ *   g_Wls = sum_m dr h2^T      g_bls = sum_m dr
+ * in a fixed order that depends on nothing but count (ur_gym_amd/csrc/urgym_actor_backward.hip states it): rows ascending within a
+ * split of 1024 rows, then the splits ascending; no floating-point atomics; two calls on the same inputs give bitwise the same
+ * tensors.  Two kinds of sums are carried in float64 and rounded to float32 once: the twelve head-bias sums g_bmu, g_bls within a split,
+ * and the addition of the splits.  Near tanh saturation 1 - a^2 has no relative accuracy in float32, in this or any implementation
+ * of the SAMPLE form. */
+
+/* The upstream gradient: DEVICE pointers.  SAMPLE form: d_action given, d_log_prob given or NULL, d_mu == d_log_std == NULL.  HEADS
+ * form: d_mu and d_log_std given, d_action == d_log_prob == NULL. */
+typedef struct urgym_actor_upstream {
+  const float* d_action;   /* [count][6] */
+  const float* d_log_prob; /* [count], or NULL: 0 */
+  const float* d_mu;       /* [count][6] */
+  const float* d_log_std;  /* [count][6], with respect to the clamped log_std */
+} urgym_actor_upstream;
+
+/* Where the gradients go: DEVICE pointers, float32, torch's [out][in] row-major layout, 4-byte aligned -- a torch parameter's .grad
+ * as it lies; the eight tensors are named like urgym_actor_params_dev's and all required; every float of every tensor is written
+ * by every call.  Then the optional per-row outputs, each may be NULL: feeding d_mu and d_log_std back in the HEADS form reproduces
+ * the call. */
+typedef struct urgym_actor_param_grads {
+  float* w0;        /* [hidden_width][in_features] */
+  float* b0;        /* [hidden_width] */
+  float* w1;        /* [hidden_width][hidden_width] */
+  float* b1;        /* [hidden_width] */
+  float* w_mu;      /* [6][hidden_width] */
+  float* b_mu;      /* [6] */
+  float* w_log_std; /* [6][hidden_width] */
+  float* b_log_std; /* [6] */
+  float* action;    /* [count][6], or NULL */
+  float* log_prob;  /* [count], or NULL */
+  float* noise;     /* [count][6], or NULL: eps */
+  float* log_std;   /* [count][6], or NULL: after the clamp */
+  float* d_mu;      /* [count][6], or NULL */
+  float* d_log_std; /* [count][6], or NULL: before the clamp derivative */
+  float* std;       /* [count][6], or NULL: exp(ls) as the forward pass formed it, the factor of e in the SAMPLE form (the device's expf
+                       and a host's float32 exp are different functions, each good to an ulp) */
+} urgym_actor_param_grads;
+
+#define URGYM_ACTOR_GRADIENTS_MAX_COUNT 65536
+
+/* The size of the workspace a call with this actor and count needs, in bytes: the per-row quantities h1, h2, d2, d1, x, the twelve
+ * head gradients, and above 1024 rows the partial sums.  For hidden_width 256, in_features 47 and count 65,536 it is 304,942,080
+ * bytes.  Refused: NULL handle / actor / bytes, an actor of another handle, without a log_std head or wider than 256, count outside
+ * [1, URGYM_ACTOR_GRADIENTS_MAX_COUNT]. */
+int urgym_actor_parameter_gradients_workspace(void* handle, void* actor, int count, uint64_t* bytes);
+
+/* TWO launches on `stream` up to 1024 rows (per row; the sums), THREE above (per row; the sums per split of 1024 rows; the splits
+ * added up).  how: mode GAUSSIAN or MEAN, first_draw is the draw, and the noise counter's env word is the row index, as in
+ * urgym_actor_sample_rows.  rows: a urgym_critic_rows whose action member is ignored; observation == NULL means the bound buffers.
+ * The caller owns the workspace (DEVICE, 16-byte aligned, at least the queried size): the library allocates nothing and keeps no
+ * state between calls, every workspace float that is read was written earlier in the same call, and what the workspace or the
+ * outputs held before does not matter.  No host synchronisation; everything is validated before the first launch.  Refused
+ * (URGYM_ERR_ARG, nothing is launched): what urgym_actor_sample_rows refuses about handle, actor, how, rows and count; mode UNIFORM;
+ * an actor without a log_std head; an actor with hidden_width above 256 (the same cap as the critic's gradients: the per-row kernel is
+ * built for widths up to 256, the shipped checkpoints'); count above URGYM_ACTOR_GRADIENTS_MAX_COUNT; upstream == NULL, both forms,
+ * neither, or a half-given HEADS form; out == NULL or one of its eight tensor pointers; workspace NULL, misaligned or workspace_bytes
+ * below the queried size. */
+int urgym_actor_parameter_gradients(void* handle, void* actor, const urgym_sampling* how, const urgym_critic_rows* rows, int count, const urgym_actor_upstream* upstream, const urgym_actor_param_grads* out, void* workspace, uint64_t workspace_bytes, void* stream);
+
 /* Verification aid, not a hot path: synchronises the device, then copies the object's packed buffer (the kernel's own layout,
  * ur_gym_amd/csrc/urgym_pack_map.h) to host_out and stores its length in floats in *count.  host_out == NULL only reports *count;
  * otherwise capacity (in floats) must be at least that.  Refused: NULL handle / object / count, an object of another handle,

@@ -1,0 +1,672 @@
+"""The parameter gradients of the actor: urgym_actor_parameter_gradients through ``env.actor_parameter_gradients``, the numpy
+restatement ``StochasticActor.parameter_gradients`` / ``sample_head_gradients`` and the learner's ``device_actor_gradient`` option
+(DESIGN.md section 14).
+
+Where the checks come from (no number is taken from what the kernels give):
+  * the formulas of include/urgym.h, both forms chained in float64, are pinned by torch.autograd in float64 through
+    ``TorchActor.sample`` on the four checkpoints' actors, on the 1680 recorded rows with ``policy_noise`` as eps, to 1e-10 relative
+    per tensor (the bound of the two existing formula tests).  The upstream is the policy loss's own shape, d_log_prob = 1 / n and
+    d_action normal / n.  What float64 leaves: on rows near saturation (|pre| up to 8.7, t = 1 - a^2 about 1e-7) t carries an absolute
+    error of about 1e-16, so t / (t + 1e-6) and with it the row's share of d_mu from d_log_prob is good to about 1e-9 relative -- in
+    this formula and in autograd alike, which round in different places.  Summed with one sign of d_log_prob that stays below the bound.
+  * the exact network (tests/test_actor_widths.py's ``exact_network`` with its second log_std head and ``edge_bias``): W0 / W1 dense
+    +-1, inputs and hidden biases in {-1, 0, 1}, heads +-2^-13, head gradients in {-1, 0, 1} 2^-4.  Every term of every sum is an
+    integer multiple of one unit; the test computes the largest sum of absolute terms over any output element in units from the
+    float64 pass and asserts it below 2^24, so every partial sum in any order is a float32 number and float32, float64 and the device
+    agree BITWISE.  Rows sit exactly on both clamp edges (where the derivative passes) and beyond them.
+  * on the checkpoints a row is excluded where a float64 pre-activation is within 4 x numpy float32's largest deviation on that layer
+    (test_action_gradient.py's rule; at most 5 % of the rows, asserted); no r of a kept row lies within that distance of a clamp edge.
+    The device may deviate from float64 by 4 x numpy float32's deviation per tensor: the project's rule for a second float32 order.
+  * the SAMPLE form on the checkpoints is compared piece by piece, never end to end with float64: near tanh saturation 1 - a^2 has no
+    relative accuracy in float32 in any implementation.  action and log_prob are bitwise the forward call's; the head gradients are
+    bitwise ``sample_head_gradients`` on the call's own records (its ``std`` record among them: exp(log_std) is the device's expf); the HEADS form on those reproduces the eight tensors bitwise.
+  * the learner: the device route's actor gradients may deviate from float64 autograd by 4 x the torch float32 route's deviation on
+    the same noise plus one float32 ulp of the tensor's largest gradient.
+  * tests/actor_backward_harness.cpp enumerates the kernels' index arithmetic on the host under the address and undefined-behaviour
+    sanitizers: bounds, the bijection between stage 1's writes and stage 2's reads, every output element written once.
+"""
+import ctypes as C
+import functools
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from test_actor_widths import CASES, GRID, edge_bias, exact_inputs, exact_network, features
+from test_policy_sampling import ENVS, KINDS, weights
+from ur_gym_amd import _abi, _native
+from ur_gym_amd.evaluation import ACTOR_ARRAYS, LOG_STD_ARRAYS, DeviceActor, StochasticActor, policy_noise, sample_head_gradients
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+CSRC = os.path.join(ROOT, "ur_gym_amd", "csrc")
+NAMES = ("ori", "obs", "sta", "dyn")
+KEYS = ACTOR_ARRAYS + LOG_STD_ARRAYS
+UP_UNIT = 2.0 ** -4
+GPU_WIDTHS = (32, 128, 160, 256)
+REFUSED_WIDTHS = (288, 512)
+SPLIT = 1024  # rows per split of stage 2 (urgym_actor_backward_map.h: AB_SPLIT_ROWS)
+# one lane, a second wave, a full workgroup, a second workgroup with one row, ragged; stage 2's split boundary and its neighbours
+GPU_COUNTS = (1, 33, 128, 129, 417, SPLIT - 1, SPLIT, SPLIT + 1)
+SYMBOLS = ("urgym_actor_parameter_gradients", "urgym_actor_parameter_gradients_workspace")
+WRONG = ("W1 for W1^T", "mask >=", "clamp strict", "heads exchanged", "head columns shifted", "d2 for d1 in g_b0")
+
+
+def split(kind, x):
+    gd = features(kind)[2]
+    return x[:, :gd], x[:, gd:2 * gd], x[:, 2 * gd:]
+
+
+def trace_rows(name):
+    z = np.load(os.path.join(ROOT, "tests", "golden", f"step_trace_{name}.npz"))
+    parts = [z["step_achieved_goal"][:-1], z["step_desired_goal"][:-1], z["step_observation"][:-1]]
+    return np.concatenate([p.reshape(-1, p.shape[-1]) for p in parts], axis=1).astype(np.float32)
+
+
+def forward_f64(w, x):
+    """z1, z2, mu, r (log_std before the clamp) in float64."""
+    w = {k: np.asarray(v, dtype=np.float64) for k, v in w.items()}
+    x = x.astype(np.float64)
+    z1 = x @ w["latent_pi_0_weight"].T + w["latent_pi_0_bias"]
+    z2 = np.maximum(z1, 0.0) @ w["latent_pi_2_weight"].T + w["latent_pi_2_bias"]
+    h2 = np.maximum(z2, 0.0)
+    return z1, z2, h2 @ w["mu_weight"].T + w["mu_bias"], h2 @ w["log_std_weight"].T + w["log_std_bias"]
+
+
+def sample_heads_f64(mu, r, eps, d_action, d_log_prob):
+    """The SAMPLE form's head arithmetic of include/urgym.h in float64: (action, log_prob, d_mu, d_log_std)."""
+    ls = np.clip(r, -20.0, 2.0)
+    a = np.tanh(mu + np.exp(ls) * eps)
+    log_prob = (-0.5 * eps * eps - ls - 0.5 * np.log(2.0 * np.pi)).sum(axis=1) - np.log(1.0 - a * a + 1e-6).sum(axis=1)
+    t = 1.0 - a * a
+    d_pre = (d_action + d_log_prob[:, None] * (2.0 * a) / (t + 1e-6)) * t
+    return a, log_prob, d_pre, d_pre * (np.exp(ls) * eps) - d_log_prob[:, None]
+
+
+def gradients_f64(w, x, d_mu, d_log_std, wrong=None, magnitudes=False):
+    """The eight gradient tensors of the HEADS form in float64, keyed by KEYS.  `wrong` names one of the WRONG references, for the
+    sensitivity checks.  With `magnitudes` also the largest sum of absolute terms over any element of each tensor, of d_h2 and of d1."""
+    z1, z2, _, r = forward_f64(w, x)
+    w = {k: np.asarray(v, dtype=np.float64) for k, v in w.items()}
+    x, d_mu, d_log_std = x.astype(np.float64), np.asarray(d_mu, dtype=np.float64), np.asarray(d_log_std, dtype=np.float64)
+    mask = np.greater_equal if wrong == "mask >=" else np.greater
+    h1, h2 = np.maximum(z1, 0.0), np.maximum(z2, 0.0)
+    passes = ((r > -20.0) & (r < 2.0)) if wrong == "clamp strict" else ((r >= -20.0) & (r <= 2.0))
+    dr = np.where(passes, d_log_std, 0.0)
+    dm = np.roll(d_mu, 1, axis=1) if wrong == "head columns shifted" else d_mu
+    w_mu, w_ls = (w["log_std_weight"], w["mu_weight"]) if wrong == "heads exchanged" else (w["mu_weight"], w["log_std_weight"])
+    w1 = w["latent_pi_2_weight"]
+    d2 = np.where(mask(z2, 0.0), dm @ w_mu + dr @ w_ls, 0.0)
+    d1 = np.where(mask(z1, 0.0), d2 @ (w1.T if wrong == "W1 for W1^T" else w1), 0.0)
+    g = (d1.T @ x, (d2 if wrong == "d2 for d1 in g_b0" else d1).sum(axis=0), d2.T @ h1, d2.sum(axis=0),
+         dm.T @ h2, dm.sum(axis=0), dr.T @ h2, dr.sum(axis=0))
+    out = {k: v + 0.0 for k, v in zip(KEYS, g)}
+    if not magnitudes:
+        return out
+    a1, a2, am, ar = np.abs(d1), np.abs(d2), np.abs(dm), np.abs(dr)
+    mags = (a1.T @ np.abs(x), a1.sum(axis=0), a2.T @ h1, a2.sum(axis=0), am.T @ h2, am.sum(axis=0), ar.T @ h2, ar.sum(axis=0),
+            am @ np.abs(w_mu) + ar @ np.abs(w_ls), a2 @ np.abs(w1))
+    return out, [float(np.max(m)) for m in mags]
+
+
+def bits_equal(a32, b64):
+    a32 = np.asarray(a32)
+    return a32.dtype == np.float32 and a32.shape == b64.shape and np.array_equal(a32.view(np.uint32), b64.astype(np.float32).view(np.uint32))
+
+
+def edge_network(kind, H, x):
+    """``exact_network`` with its second log_std head, whose biases put r exactly on the clamp's edges on some of the rows `x`."""
+    w, w_ls2 = exact_network(kind, H)
+    return dict(w, log_std_weight=w_ls2, log_std_bias=edge_bias(w, w_ls2, x))
+
+
+def exact_upstream(net, x, dense=True, tag=23):
+    """Head gradients in {-1, 0, 1} 2^-4 (d_mu, d_log_std), float32 [n, 6] each; d_log_std is nonzero wherever r sits exactly on a clamp
+    edge (the inclusive derivative must pass it) and on the last row.  Not `dense`: one nonzero component per row, in a random one of
+    the twelve columns."""
+    n = len(x)
+    rng = np.random.default_rng([n, x.shape[1], tag])
+    if dense:
+        up = rng.integers(-1, 2, (n, 12)).astype(np.float64)
+    else:
+        up = np.zeros((n, 12))
+        up[np.arange(n), rng.integers(0, 12, n)] = rng.integers(0, 2, n) * 2.0 - 1.0
+    r = forward_f64(net, x)[3]
+    if dense:
+        on_edge = (r == 2.0) | (r == -20.0)
+        up[:, 6:][on_edge & (up[:, 6:] == 0.0)] = 1.0
+        up[-1, :4], up[-1, 6:] = (1.0, -1.0, 1.0, 1.0), 1.0
+    else:
+        up[-1], up[-1, 0] = 0.0, 1.0  # the last row's one component is a d_mu: no clamp stands in its way
+    return (up[:, :6] * UP_UNIT).astype(np.float32), (up[:, 6:] * UP_UNIT).astype(np.float32)
+
+
+def assert_exact(net, x, d_mu, d_log_std):
+    """The float64 gradients, after asserting that every sum of absolute terms is below 2^24 units.  Returns them and the largest sum."""
+    g, mags = gradients_f64(net, x, d_mu, d_log_std, magnitudes=True)
+    ug = UP_UNIT * GRID  # every term through a head weight carries the head's 2^-13; g_Wmu, g_bmu, g_Wls, g_bls do not
+    units = [ug, ug, ug, ug, UP_UNIT, UP_UNIT, UP_UNIT, UP_UNIT, ug, ug]
+    worst = max(m / u for m, u in zip(mags, units))
+    assert worst < 2.0 ** 24, worst
+    return g, worst
+
+
+# ------------------------------------------------------------------------------------------------ CPU
+def test_struct_and_symbols_mirror_the_header():
+    hdr = open(os.path.join(ROOT, "include", "urgym.h")).read()
+    body = hdr[hdr.index("typedef struct urgym_actor_upstream"):hdr.index("} urgym_actor_upstream;")]
+    got = re.findall(r"^\s*(const float\*)\s+(\w+);", body, flags=re.M)
+    assert [(n, C.POINTER(C.c_float)) for _, n in got] == list(_abi.ActorUpstream._fields_) and len(got) == 4
+    body = hdr[hdr.index("typedef struct urgym_actor_param_grads"):hdr.index("} urgym_actor_param_grads;")]
+    got = re.findall(r"^\s*(float\*)\s+(\w+);", body, flags=re.M)
+    assert [(n, C.POINTER(C.c_float)) for _, n in got] == list(_abi.ActorParamGrads._fields_)
+    assert tuple(n for _, n in got[:8]) == _abi.ACTOR_DEV_ARRAYS == _abi.ACTOR_GRAD_ARRAYS  # named like urgym_actor_params_dev's
+    assert tuple(n for _, n in got[8:]) == _abi.ACTOR_GRAD_RECORDS and C.sizeof(_abi.ActorParamGrads) == 15 * C.sizeof(C.c_void_p)
+    assert f"#define URGYM_ACTOR_GRADIENTS_MAX_COUNT {_abi.ACTOR_GRADIENTS_MAX_COUNT}" in hdr and _abi.ACTOR_GRADIENTS_MAX_COUNT == 65536
+    assert _abi.ABI_VERSION == 4 and "#define URGYM_ABI_VERSION 4" in hdr  # added within version 4
+    lib = _native.lib()
+    for sym in SYMBOLS:
+        assert sym in _abi.EXPORTED_SYMBOLS and hasattr(lib, sym), sym
+        assert re.search(rf"^int {sym}\(.*\);$", hdr, flags=re.M), sym
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_formula_against_autograd_float64(name):
+    import torch
+
+    from ur_gym_amd.training import TorchActor
+
+    w, x = weights(name), trace_rows(name)
+    n = len(x)
+    assert x.shape == (1680, features(name)[0])
+    eps = policy_noise(11, 4, np.arange(n), "gaussian", dtype=np.float64)
+    rng = np.random.default_rng([n, 31])
+    # the upstream of SAC's policy loss mean(alpha log_prob - q): d_log_prob = alpha / n with alpha = 1, d_action = -dq/da / n (normal here)
+    d_action, d_log_prob = rng.normal(size=(n, 6)) / n, np.full(n, 1.0 / n)
+    actor = TorchActor(x.shape[1], 256).double()
+    for k, p in actor.tensors().items():
+        p.data.copy_(torch.from_numpy(np.asarray(w[k], dtype=np.float64)))
+    action, log_prob = actor.sample(torch.from_numpy(x.astype(np.float64)), torch.from_numpy(eps))
+    ((action * torch.from_numpy(d_action)).sum() + (log_prob * torch.from_numpy(d_log_prob)).sum()).backward()
+    _, _, mu, r = forward_f64(w, x)
+    a64, lp64, d_mu, d_ls = sample_heads_f64(mu, r, eps, d_action, d_log_prob)
+    assert np.abs(a64 - action.detach().numpy()).max() <= 1e-12 and np.abs(lp64 - log_prob.detach().numpy()).max() <= 1e-9
+    g64 = gradients_f64(w, x, d_mu, d_ls)
+    for k, p in actor.tensors().items():
+        want = p.grad.numpy()
+        rel = float(np.abs(g64[k] - want).max() / np.abs(want).max())
+        print(f"{name} {k}: formula vs autograd (float64) {rel:.3e} relative, |g| up to {np.abs(want).max():.4g}")
+        assert g64[k].shape == want.shape and rel <= 1e-10, (name, k, rel)
+
+
+@pytest.mark.parametrize("kind,H", CASES, ids=[f"{k}-{H}" for k, H in CASES])
+def test_exact_network_float32_is_float64_bitwise(kind, H):
+    n = 417
+    x = exact_inputs(kind, n)
+    net = edge_network(kind, H, x)
+    d_mu, d_ls = exact_upstream(net, x)
+    ref, worst = assert_exact(net, x, d_mu, d_ls)
+    print(f"{kind} H={H}: largest sum of absolute terms {worst:.4g} units (2^24 = {2.0 ** 24:.4g})")
+    r = forward_f64(net, x)[3]
+    assert (r[:, 0] == 2.0).any() and (r[:, 1] == -20.0).any() and (r[:, 2] == 2.0).any() and (r[:, 3] == -20.0).any()  # exactly at the edges
+    assert (r[:, 4] > 2.0).all() and (r[:, 5] < -20.0).all() and (r[:, 0] > 2.0).any() and (r[:, 1] < -20.0).any()  # and beyond
+    assert (d_ls[(r == 2.0) | (r == -20.0)] != 0.0).all()
+    grads, rec = StochasticActor(net).parameter_gradients(*split(kind, x), d_mu=d_mu, d_log_std=d_ls)
+    assert bits_equal(rec["log_std"], np.clip(r, -20.0, 2.0))
+    for k in KEYS:
+        assert bits_equal(grads[k], ref[k]), (kind, H, k)
+        assert (ref[k] != 0.0).any(), (kind, H, k)  # an output nobody wrote cannot pass
+    shares = {}
+    for label in WRONG:
+        bad = gradients_f64(net, x, d_mu, d_ls, wrong=label)
+        shares[label] = float(np.mean(np.concatenate([(bad[k] != ref[k]).ravel() for k in KEYS])))
+    print(f"{kind} H={H}: share of elements on which a wrong reference differs: {shares}")
+    assert all(s > 0.0 for s in shares.values()), (kind, H, shares)
+
+
+@functools.lru_cache(maxsize=None)
+def checkpoint_case(name):
+    """The checkpoint on the kept trace rows in the HEADS form: x, seeded float32 normal d_mu and d_log_std, the float64 gradients,
+    numpy float32's deviation per tensor, the number of rows excluded and the closest a kept r comes to a clamp edge, in units of the
+    rule's distance."""
+    w, x = weights(name), trace_rows(name)
+    z1, z2, _, r = forward_f64(w, x)
+    f = np.float32
+    s1 = x @ w["latent_pi_0_weight"].T + w["latent_pi_0_bias"]  # numpy float32, as StochasticActor evaluates them
+    s2 = np.maximum(s1, f(0.0)) @ w["latent_pi_2_weight"].T + w["latent_pi_2_bias"]
+    sr = np.maximum(s2, f(0.0)) @ w["log_std_weight"].T + w["log_std_bias"]
+    keep = (np.abs(z1) >= 4.0 * np.abs(s1 - z1).max()).all(axis=1) & (np.abs(z2) >= 4.0 * np.abs(s2 - z2).max()).all(axis=1)
+    assert np.array_equal(s1[keep] > 0, z1[keep] > 0) and np.array_equal(s2[keep] > 0, z2[keep] > 0)  # what the rule is for
+    edge = float(np.minimum(np.abs(r - 2.0), np.abs(r + 20.0))[keep].min() / (4.0 * np.abs(sr - r).max()))
+    x = x[keep]
+    rng = np.random.default_rng([len(x), 37])
+    d_mu, d_ls = (rng.normal(size=(len(x), 6)).astype(f) for _ in range(2))
+    g64 = gradients_f64(w, x, d_mu, d_ls)
+    g32, _ = StochasticActor(w).parameter_gradients(*split(name, x), d_mu=d_mu, d_log_std=d_ls)
+    dev32 = {k: float(np.abs(g32[k].astype(np.float64) - g64[k]).max()) for k in KEYS}
+    return dict(w=w, x=x, d_mu=d_mu, d_ls=d_ls, g64=g64, dev32=dev32, dropped=int((~keep).sum()), edge=edge)
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_checkpoints_float32_against_float64(name):
+    case = checkpoint_case(name)
+    print(f"{name}: {case['dropped']} of 1680 rows excluded; the closest kept r lies {case['edge']:.3g} rule distances from a clamp edge")
+    assert case["dropped"] <= 0.05 * 1680 and case["edge"] >= 1.0
+    for k in KEYS:
+        top = float(np.abs(case["g64"][k]).max())
+        print(f"{name} {k}: numpy float32 vs float64 {case['dev32'][k]:.3e} at |g| up to {top:.4g}")
+        assert np.isfinite(case["dev32"][k]) and case["dev32"][k] <= 2.0 ** -10 * top
+
+
+def test_index_arithmetic_on_the_host_under_sanitizers():
+    exe = os.path.join(HERE, "_build", "actor_backward_harness")
+    os.makedirs(os.path.dirname(exe), exist_ok=True)
+    src = os.path.join(HERE, "actor_backward_harness.cpp")
+    deps = [src, os.path.join(CSRC, "urgym_actor_backward_map.h")]
+    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe, src])
+    run = subprocess.run([exe], capture_output=True, text=True)
+    out = run.stdout
+    assert run.returncode == 0 and "FAIL" not in out and "runtime error" not in run.stderr, (out[-2000:], run.stderr[-2000:])
+    lines = out.splitlines()
+    counts = (1, 33, 128, 129, 417, SPLIT - 1, SPLIT, SPLIT + 1, 2 * SPLIT + 1, 3 * SPLIT, 4 * SPLIT + 417)
+    cap_counts = (63 * SPLIT + 1, _abi.ACTOR_GRADIENTS_MAX_COUNT)  # 64 splits: in = 47, H = 32 only
+    assert lines[-1] == f"ok {4 * 4 * len(counts) + len(cap_counts)}"
+    for kind in NAMES:
+        for H in GPU_WIDTHS:
+            for count in counts:
+                assert any(l.startswith(f"actor backward in={features(kind)[0]} H={H} count={count} ") for l in lines), (kind, H, count)
+    for count in cap_counts:
+        assert any(l.startswith(f"actor backward in=47 H=32 count={count} ") and l.endswith("splits=64 launches=3") for l in lines), count
+    assert any(l.startswith(f"actor backward in=47 H=256 count={4 * SPLIT + 417} ") and l.endswith("splits=5 launches=3") for l in lines)
+    assert any(l.startswith(f"actor backward in=47 H=256 count={SPLIT} ") and l.endswith("splits=1 launches=2") for l in lines)
+    assert any(l.startswith(f"actor backward in=47 H=256 count={SPLIT + 1} ") and l.endswith("splits=2 launches=3") for l in lines)
+    hdr = open(os.path.join(ROOT, "include", "urgym.h")).read()
+    size = int(re.search(r"^workspace in=47 H=256 count=65536 bytes=(\d+)$", out, flags=re.M).group(1))
+    assert f"{size:,}" in hdr
+
+
+# ------------------------------------------------------------------------------------------------ GPU
+def _env(kind, n, seed=1, **kw):
+    from ur_gym_amd import make_vec
+
+    env = make_vec(ENVS[kind], num_envs=n, device="cuda:0", seed=seed, **kw)
+    env.reset(seed=seed)
+    return env
+
+
+def _dev(a):
+    import torch
+
+    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
+
+
+def _same(a, b):
+    import torch
+
+    return a.shape == b.shape and bool(torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32)))
+
+
+def _rows(kind, x):
+    ach, des, obs = (_dev(p) for p in split(kind, x))
+    return dict(observation=obs, achieved_goal=ach, desired_goal=des)
+
+
+def _fp(t):
+    return C.cast(t.data_ptr(), C.POINTER(C.c_float))
+
+
+def _all_same(a, b, also=("action", "log_prob")):
+    return all(_same(a["grads"][k], b["grads"][k]) for k in KEYS) and all(_same(a[k], b[k]) for k in also)
+
+
+MEAN = dict(mode="mean")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", NAMES)
+@pytest.mark.parametrize("H", GPU_WIDTHS)
+def test_exact_network_on_the_device(kind, H):
+    import torch
+
+    n_env = 417
+    env = _env(kind, n_env)
+    for n in GPU_COUNTS:
+        x = exact_inputs(kind, n)
+        net = edge_network(kind, H, x)
+        d_mu, d_ls = exact_upstream(net, x)
+        ref, _ = assert_exact(net, x, d_mu, d_ls)
+        actor = DeviceActor(net, env)
+        rows = _rows(kind, x)
+        got = env.actor_parameter_gradients(actor, sample=MEAN, rows=rows, d_mu=_dev(d_mu), d_log_std=_dev(d_ls), records=("log_std",))
+        torch.cuda.synchronize()
+        assert bits_equal(got["log_std"].cpu().numpy(), np.clip(forward_f64(net, x)[3], -20.0, 2.0)), (kind, H, n)
+        for key in KEYS:
+            assert bits_equal(got["grads"][key].cpu().numpy(), ref[key]), (kind, H, n, key)
+        if n == n_env:  # the bound buffers
+            for key in env.ROW_KEYS:
+                env.buf[key].copy_(rows[key])
+            bound = env.actor_parameter_gradients(actor, sample=MEAN, d_mu=_dev(d_mu), d_log_std=_dev(d_ls))
+            torch.cuda.synchronize()
+            assert _all_same(bound, got), (kind, H)
+        actor.close()
+    env.close()
+
+
+def _upstream(n, tag):
+    rng = np.random.default_rng([n, tag])
+    return (rng.normal(size=(n, 6)) / n).astype(np.float32), (rng.normal(size=n) / n).astype(np.float32)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ("dyn", "ori"))
+@pytest.mark.parametrize("mode", ("gaussian", "mean"))
+def test_sample_form_on_the_checkpoints(name, mode):
+    import torch
+
+    n, seed, draw = 417, 0xC0FFEE, (1 << 63) | 5
+    w, x = weights(name), trace_rows(name)[:417]
+    env = _env(name, 8)
+    actor = DeviceActor(w, env)
+    rows, how = _rows(name, x), dict(mode=mode, seed=seed, first_draw=draw)
+    da, dlp = _upstream(n, 41)
+    res = env.actor_parameter_gradients(actor, sample=how, rows=rows, d_action=_dev(da), d_log_prob=_dev(dlp), records=env.ACTOR_GRADIENT_RECORDS)
+    action, log_prob = env.policy_actions(actor, sample=how, rows=rows)
+    torch.cuda.synchronize()
+    assert _same(res["action"], action) and _same(res["log_prob"], log_prob)  # bitwise urgym_actor_sample_rows'
+    rec = {k: res[k].cpu().numpy() for k in ("action", "log_prob") + env.ACTOR_GRADIENT_RECORDS}
+    assert all(np.isfinite(v).all() for v in rec.values())
+    # noise and log_std as tests/test_policy_sampling.py compares them: within 4 x numpy float32's own deviation from float64
+    if mode == "mean":
+        assert not rec["noise"].any()
+    else:
+        n32, n64 = (policy_noise(seed, draw, np.arange(n), "gaussian", dtype=t) for t in (np.float32, np.float64))
+        assert np.abs(rec["noise"] - n64).max() <= 4.0 * np.abs(n32 - n64).max()
+    ls64 = np.clip(forward_f64(w, x)[3], -20.0, 2.0)
+    ls32 = StochasticActor(w).heads(*split(name, x))[1]
+    assert np.abs(rec["log_std"] - ls64).max() <= 4.0 * np.abs(ls32 - ls64).max()
+    # the head arithmetic, from the call's own records
+    # (exp(log_std) is the forward pass's own value, the device's expf, which the `std` record hands out: numpy's float32 exp is another
+    # function that differs from it in the last bit on some values -- counted and printed, and immaterial in MEAN mode, where e = 0)
+    differing = lambda got: [int((rec[k].view(np.uint32) != v.view(np.uint32)).sum()) for k, v in zip(("d_mu", "d_log_std"), got)]  # noqa: E731
+    numpy_exp = differing(sample_head_gradients(rec["action"], rec["log_std"], rec["noise"], da, dlp))
+    off = differing(sample_head_gradients(rec["action"], rec["log_std"], rec["noise"], da, dlp, std=rec["std"]))
+    exp64 = np.exp(rec["log_std"].astype(np.float64))
+    ulps = float((np.abs(rec["std"] - exp64) / np.spacing(exp64.astype(np.float32))).max())
+    print(f"{name} {mode}: head gradients differing from the numpy restatement in {off} of {6 * n} floats each with the call's std record, "
+          f"in {numpy_exp} with numpy's exp ({int((rec['std'] != np.exp(rec['log_std'])).sum())} of the exp values differ; std is within {ulps:.2f} ulp of float64)")
+    assert off == [0, 0], (name, mode, off)
+    assert numpy_exp[0] == 0 and (mode == "gaussian" or numpy_exp[1] == 0), (name, mode, numpy_exp)
+    assert ulps <= 3.0  # OpenCL's bound for single-precision exp
+    # the HEADS form on those two records writes the same eight tensors
+    heads = env.actor_parameter_gradients(actor, sample=how, rows=rows, d_mu=res["d_mu"], d_log_std=res["d_log_std"])
+    # d_log_prob NULL is a zero tensor
+    null = env.actor_parameter_gradients(actor, sample=how, rows=rows, d_action=_dev(da), records=("d_mu", "d_log_std"))
+    zero = env.actor_parameter_gradients(actor, sample=how, rows=rows, d_action=_dev(da), d_log_prob=torch.zeros(n, device="cuda:0"), records=("d_mu", "d_log_std"))
+    torch.cuda.synchronize()
+    assert _all_same(heads, res)
+    assert _all_same(null, zero, also=("action", "log_prob", "d_mu", "d_log_std")) and not _all_same(null, res)
+    actor.close()
+    env.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", NAMES)
+def test_checkpoints_on_the_device(name):
+    import torch
+
+    case = checkpoint_case(name)
+    M = len(case["x"])
+    assert SPLIT < M <= 1680  # two splits: the partial sums and the third launch
+    env = _env(name, 8)
+    actor = DeviceActor(case["w"], env)
+    got = env.actor_parameter_gradients(actor, sample=MEAN, rows=_rows(name, case["x"]), d_mu=_dev(case["d_mu"]), d_log_std=_dev(case["d_ls"]))
+    torch.cuda.synchronize()
+    for k in KEYS:
+        dev = float(np.abs(got["grads"][k].cpu().numpy().astype(np.float64) - case["g64"][k]).max())
+        dev32 = case["dev32"][k]
+        print(f"{name} {k}: kernels vs float64 {dev:.3e}, numpy float32 vs float64 {dev32:.3e} (bound {4 * dev32:.3e}) on {M} rows")
+        assert dev <= 4.0 * dev32, (name, k, dev, dev32)
+    actor.close()
+    env.close()
+
+
+@pytest.fixture(scope="module")
+def dyn():
+    """The dyn checkpoint on its kept trace rows (two splits) in the SAMPLE form: env, actor, rows, upstream and one call's result."""
+    case = checkpoint_case("dyn")
+    M = len(case["x"])
+    env = _env("dyn", 8)
+    actor = DeviceActor(case["w"], env)
+    rows, how = _rows("dyn", case["x"]), dict(mode="gaussian", seed=17, first_draw=2)
+    da, dlp = (_dev(v) for v in _upstream(M, 43))
+    whole = env.actor_parameter_gradients(actor, sample=how, rows=rows, d_action=da, d_log_prob=dlp)
+    yield dict(env=env, actor=actor, w=case["w"], rows=rows, how=how, da=da, dlp=dlp, whole=whole, M=M)
+    actor.close()
+    env.close()
+
+
+@pytest.mark.gpu
+def test_two_calls_agree_and_nothing_depends_on_old_contents(dyn):
+    import torch
+
+    env, actor, rows, how, da, dlp, whole, M = (dyn[k] for k in ("env", "actor", "rows", "how", "da", "dlp", "whole", "M"))
+    assert _all_same(env.actor_parameter_gradients(actor, sample=how, rows=rows, d_action=da, d_log_prob=dlp), whole)
+    results = []
+    for fill in (float("nan"), 0.0):
+        ws = env.actor_gradient_workspace(actor, M)
+        ws.fill_(fill)
+        out = {k: torch.full_like(v, fill) for k, v in whole["grads"].items()}
+        results.append(env.actor_parameter_gradients(actor, sample=how, rows=rows, d_action=da, d_log_prob=dlp, out=out, workspace=ws))
+        assert results[-1]["grads"] is out
+    torch.cuda.synchronize()
+    assert _all_same(results[0], results[1]) and _all_same(results[0], whole)
+    assert all(bool(torch.isfinite(results[0]["grads"][k]).all()) for k in KEYS)
+    # a batch within one split (two launches) as well
+    m = 300
+    part = {k: v[:m] for k, v in rows.items()}
+    a = env.actor_parameter_gradients(actor, sample=how, rows=part, d_action=da[:m], d_log_prob=dlp[:m])
+    ws = env.actor_gradient_workspace(actor, m)
+    ws.fill_(float("nan"))
+    b = env.actor_parameter_gradients(actor, sample=how, rows=part, d_action=da[:m], d_log_prob=dlp[:m], workspace=ws)
+    torch.cuda.synchronize()
+    assert _all_same(a, b)
+
+
+RECORD_SIZES = dict(action=6, log_prob=1, noise=6, log_std=6, d_mu=6, d_log_std=6, std=6)
+
+
+def _raw(env, actor, rows, m, pad=64, fill=-12345.0):
+    """The arguments of a call through the C interface with guard words round every output, every record and the workspace."""
+    import torch
+
+    n, H = actor.in_features, actor.hidden_width
+    sizes = dict(zip(_abi.ACTOR_GRAD_ARRAYS, (H * n, H, H * H, H, 6 * H, 6, 6 * H, 6)))
+    sizes.update({k: m * s for k, s in RECORD_SIZES.items()})
+    big = {k: torch.full((s + 2 * pad,), fill, dtype=torch.float32, device="cuda:0") for k, s in sizes.items()}
+    need = C.c_uint64()
+    assert env.lib.urgym_actor_parameter_gradients_workspace(env._h, actor._a, m, C.byref(need)) == 0 and need.value % 16 == 0
+    ws = torch.full((need.value // 4 + 2 * pad,), fill, dtype=torch.float32, device="cuda:0")
+    cr = _abi.CriticRows(_fp(rows["observation"]), _fp(rows["achieved_goal"]), _fp(rows["desired_goal"]), None)
+    out = _abi.ActorParamGrads(*[_fp(big[k][pad:]) for k in _abi.ACTOR_GRAD_ARRAYS + _abi.ACTOR_GRAD_RECORDS])
+    return dict(sizes=sizes, big=big, ws=ws, need=need.value, cr=cr, out=out, pad=pad, fill=fill)
+
+
+def _untouched(r):
+    return all(bool((t == r["fill"]).all()) for t in list(r["big"].values()) + [r["ws"]])
+
+
+@pytest.mark.gpu
+def test_no_stray_writes():
+    import torch
+
+    kind, H, m = "dyn", 160, 129
+    env = _env(kind, 8)
+    x = exact_inputs(kind, m)
+    net = edge_network(kind, H, x)
+    actor = DeviceActor(net, env)
+    rows = _rows(kind, x)
+    da, dlp = (_dev(v) for v in _upstream(m, 47))
+    how = dict(mode="gaussian", seed=3, first_draw=9)
+    r = _raw(env, actor, rows, m)
+    pad, fill = r["pad"], r["fill"]
+    up = _abi.ActorUpstream(_fp(da), _fp(dlp), None, None)
+    rc = env.lib.urgym_actor_parameter_gradients(env._h, actor._a, C.byref(env._sampling(how)), C.byref(r["cr"]), m, C.byref(up), C.byref(r["out"]),
+                                                 C.c_void_p(r["ws"][pad:].data_ptr()), r["need"], env._stream())
+    assert rc == 0, env.lib.urgym_last_error(env._h)
+    want = env.actor_parameter_gradients(actor, sample=how, rows=rows, d_action=da, d_log_prob=dlp, records=env.ACTOR_GRADIENT_RECORDS)
+    torch.cuda.synchronize()
+    assert bool((r["ws"][:pad] == fill).all()) and bool((r["ws"][pad + r["need"] // 4:] == fill).all())
+    assert not bool((r["ws"][pad:pad + r["need"] // 4] == fill).any())  # every workspace float is written
+    flat = dict(zip(_abi.ACTOR_GRAD_ARRAYS, (want["grads"][k] for k in KEYS)))
+    flat.update({k: want[k] for k in _abi.ACTOR_GRAD_RECORDS})
+    for k, size in r["sizes"].items():
+        t = r["big"][k]
+        assert bool((t[:pad] == fill).all()) and bool((t[pad + size:] == fill).all()), k
+        assert _same(t[pad:pad + size], flat[k].reshape(-1)), k
+    actor.close()
+    env.close()
+
+
+@pytest.mark.gpu
+def test_reload_without_synchronisation(dyn):
+    import torch
+
+    env, w, rows, how, da, dlp, whole = (dyn[k] for k in ("env", "w", "rows", "how", "da", "dlp", "whole"))
+    call = lambda a: env.actor_parameter_gradients(a, sample=how, rows=rows, d_action=da, d_log_prob=dlp)  # noqa: E731
+    other_w = dict(w, mu_weight=w["log_std_weight"], log_std_weight=w["mu_weight"])
+    swapped = DeviceActor(other_w, env)
+    other = call(swapped)
+    again = DeviceActor(w, env)
+    tensors = {k: _dev(np.asarray(other_w[k], dtype=np.float32)) for k in KEYS}
+    first = call(again)
+    again.load_parameters(tensors)
+    reloaded = call(again)
+    torch.cuda.synchronize()
+    assert _all_same(first, whole) and _all_same(reloaded, other) and not _all_same(reloaded, whole)
+    swapped.close()
+    again.close()
+
+
+@pytest.mark.gpu
+def test_refusals_launch_nothing(dyn):
+    import torch
+
+    env, actor, rows, how, da, dlp, whole, w = (dyn[k] for k in ("env", "actor", "rows", "how", "da", "dlp", "whole", "w"))
+    m = 129
+    r = _raw(env, actor, rows, m)
+    lib, h, s = env.lib, env._h, env._stream()
+    cr, out, ws, need = r["cr"], r["out"], C.c_void_p(r["ws"][r["pad"]:].data_ptr()), r["need"]
+    g = C.byref(env._sampling(how))
+    up = _abi.ActorUpstream(_fp(da), _fp(dlp), None, None)
+    u = C.byref(up)
+    pg = lib.urgym_actor_parameter_gradients
+    wide = [DeviceActor(edge_network("dyn", H, exact_inputs("dyn", 8)), env) for H in REFUSED_WIDTHS]
+    headless = DeviceActor({k: w[k] for k in ACTOR_ARRAYS}, env)
+    size = C.c_uint64(7)
+    fields = [getattr(out, k) for k, _ in _abi.ActorParamGrads._fields_]
+    no_w1 = _abi.ActorParamGrads(*[None if i == 2 else f for i, f in enumerate(fields)])
+    no_bls = _abi.ActorParamGrads(*[None if i == 7 else f for i, f in enumerate(fields)])
+    ups = [_abi.ActorUpstream(_fp(da), _fp(dlp), _fp(da), _fp(da)), _abi.ActorUpstream(None, None, None, None), _abi.ActorUpstream(None, _fp(dlp), None, None),
+           _abi.ActorUpstream(None, None, _fp(da), None), _abi.ActorUpstream(None, None, None, _fp(da)), _abi.ActorUpstream(_fp(da), None, _fp(da), _fp(da)),
+           _abi.ActorUpstream(None, _fp(dlp), _fp(da), _fp(da))]
+    calls = [pg(h, None, g, C.byref(cr), m, u, C.byref(out), ws, need, s), pg(h, C.c_void_p(1), g, C.byref(cr), m, u, C.byref(out), ws, need, s),
+             pg(h, actor._a, None, C.byref(cr), m, u, C.byref(out), ws, need, s),
+             pg(h, actor._a, C.byref(env._sampling(dict(mode="uniform"))), C.byref(cr), m, u, C.byref(out), ws, need, s),
+             pg(h, actor._a, C.byref(_abi.Sampling(7, 0, 0, 0)), C.byref(cr), m, u, C.byref(out), ws, need, s),
+             pg(h, actor._a, C.byref(_abi.Sampling(1, 1, 0, 0)), C.byref(cr), m, u, C.byref(out), ws, need, s),
+             pg(h, actor._a, g, None, m, u, C.byref(out), ws, need, s), pg(h, actor._a, g, C.byref(cr), 0, u, C.byref(out), ws, need, s),
+             pg(h, actor._a, g, C.byref(_abi.CriticRows(None, None, None, None)), m, u, C.byref(out), ws, need, s),  # bound: count == N
+             pg(h, actor._a, g, C.byref(_abi.CriticRows(cr.observation, None, cr.desired_goal, None)), m, u, C.byref(out), ws, need, s),
+             pg(h, actor._a, g, C.byref(cr), m, None, C.byref(out), ws, need, s),
+             pg(h, actor._a, g, C.byref(cr), m, u, None, ws, need, s), pg(h, actor._a, g, C.byref(cr), m, u, C.byref(no_w1), ws, need, s),
+             pg(h, actor._a, g, C.byref(cr), m, u, C.byref(no_bls), ws, need, s),
+             pg(h, actor._a, g, C.byref(cr), m, u, C.byref(out), None, need, s),  # no workspace
+             pg(h, actor._a, g, C.byref(cr), m, u, C.byref(out), C.c_void_p(ws.value + 4), need, s),  # a misaligned one
+             pg(h, actor._a, g, C.byref(cr), m, u, C.byref(out), ws, need - 4, s),  # a short one
+             pg(h, actor._a, g, C.byref(cr), _abi.ACTOR_GRADIENTS_MAX_COUNT + 1, u, C.byref(out), ws, 1 << 40, s),
+             pg(h, headless._a, g, C.byref(cr), m, u, C.byref(out), ws, 1 << 40, s),
+             lib.urgym_actor_parameter_gradients_workspace(h, actor._a, _abi.ACTOR_GRADIENTS_MAX_COUNT + 1, C.byref(size)),
+             lib.urgym_actor_parameter_gradients_workspace(h, actor._a, 0, C.byref(size)),
+             lib.urgym_actor_parameter_gradients_workspace(h, headless._a, m, C.byref(size)),
+             lib.urgym_actor_parameter_gradients_workspace(h, actor._a, m, None)]
+    calls += [pg(h, actor._a, g, C.byref(cr), m, C.byref(bad), C.byref(out), ws, need, s) for bad in ups]
+    calls += [pg(h, a._a, g, C.byref(cr), m, u, C.byref(out), ws, 1 << 40, s) for a in wide]
+    calls += [lib.urgym_actor_parameter_gradients_workspace(h, a._a, m, C.byref(size)) for a in wide]
+    for i, rc in enumerate(calls):
+        assert rc == _abi.ERR_ARG, i
+    assert size.value == 7 and "256" in lib.urgym_last_error(h).decode()
+    torch.cuda.synchronize()
+    assert _untouched(r)  # nothing was launched
+    assert lib.urgym_actor_parameter_gradients_workspace(h, actor._a, _abi.ACTOR_GRADIENTS_MAX_COUNT, C.byref(size)) == 0 and size.value == 304942080
+    assert _all_same(env.actor_parameter_gradients(actor, sample=how, rows=rows, d_action=da, d_log_prob=dlp), whole)  # the handle is as usable as before
+    for a in wide + [headless]:
+        a.close()
+
+
+@pytest.mark.gpu
+def test_learner_actor_gradients():
+    """Learners from one seed on the same ring and (seed, draw): the actor gradients of the first update with all three options against
+    float64 autograd on the device's own noise, and with the option off the same losses as without it, bit for bit."""
+    import torch
+
+    from ur_gym_amd.evaluation import DeviceReplay
+    from ur_gym_amd.training import SAC_DEFAULTS, SACLearner, TorchActor, _features
+
+    assert SAC_DEFAULTS["device_actor_gradient"] is False
+    env = _env("dyn", 161, seed=3, auto_reset=True)
+    replay = DeviceReplay(env, 4)
+    kw = dict(seed=5, hidden_width=32, batch_size=64)
+    with pytest.raises(ValueError, match="device_action_gradient"):
+        SACLearner(env, device_actor_gradient=True, **kw)
+    ln = SACLearner(env, device_action_gradient=True, device_critic_gradient=True, device_actor_gradient=True, **kw)
+    ln.collect(replay, 4)
+    M, seed, draw = 64, 9, 2
+    gamma = float(ln.hp["gamma"])
+    batch = replay.sample_targets(ln.device_actor, ln.target, M, seed, draw, gamma, 0.0)
+    how = dict(mode="gaussian", seed=seed, first_draw=draw | 1 << 63)
+    rows = batch["observations"]
+    probe = env.actor_parameter_gradients(ln.device_actor, sample=how, rows=rows, d_action=torch.zeros((M, 6), device="cuda:0"), records=("noise",))
+    eps, action_pi = probe["noise"].clone(), probe["action"].clone()
+    alpha = ln.log_ent_coef.detach().exp().clone()
+    copies = {}
+    for label, dtype in (("float64", torch.float64), ("float32", torch.float32)):
+        copies[label] = TorchActor(ln.actor.latent_pi[0].in_features, 32).to("cuda:0").to(dtype)
+        copies[label].load_state_dict({k: v.to(dtype) for k, v in ln.actor.state_dict().items()})
+    grads_before = dict(ln.actor_grads)
+    with pytest.raises(ValueError, match="2\\*\\*63"):
+        ln.update(replay, seed, 1 << 63)
+    state = ln.noise.get_state().clone()
+    losses = ln.update(replay, seed, draw)
+    assert bool(torch.equal(ln.noise.get_state(), state))  # torch's generator is not drawn from
+    g = env.critic_action_gradient(ln.online, action_pi, rows=rows)["dqmin_da"]  # the online critic after its step, as update used it
+    print(f"largest |action| of the batch {float(action_pi.abs().max()):.6f} (fresh networks keep |pre| small: tanh does not saturate)")
+    x = _features(rows)
+    for label, actor in copies.items():
+        dtype = next(actor.parameters()).dtype
+        action, log_prob = actor.sample(x.to(dtype), eps.to(dtype))
+        (alpha.to(dtype) * log_prob - (action * g.to(dtype)).sum(1)).mean().backward()
+    ref = {k: p.grad.double() for k, p in copies["float64"].tensors().items()}
+    dev_default = {k: float((p.grad.double() - ref[k]).abs().max()) for k, p in copies["float32"].tensors().items()}
+    dev_device = {k: float((p.grad.double() - ref[k]).abs().max()) for k, p in ln.actor.tensors().items()}
+    for k in KEYS:
+        top = float(ref[k].abs().max())
+        ulp = float(np.spacing(np.float32(top)))
+        print(f"{k}: device route {dev_device[k]:.3e}, torch float32 route {dev_default[k]:.3e}, largest gradient {top:.3e}, ulp {ulp:.3e}")
+        assert top > 0.0 and dev_device[k] <= 4.0 * dev_default[k] + ulp, k
+    ln.update(replay, seed + 1, draw + 1)
+    torch.cuda.synchronize()
+    assert all(p.grad is grads_before[k] and ln.actor_grads[k] is grads_before[k] for k, p in ln.actor.tensors().items())  # over two updates
+    assert all(bool(torch.isfinite(v).all()) for v in losses.values())
+    # the option off is the option absent
+    plain = {"absent": SACLearner(env, **kw), "off": SACLearner(env, device_actor_gradient=False, **kw)}
+    out = {label: [l.update(replay, 9 + j, 2 + j) for j in range(2)] for label, l in plain.items()}
+    torch.cuda.synchronize()
+    for a, b in zip(out["absent"], out["off"]):
+        assert all(_same(a[k].reshape(1), b[k].reshape(1)) for k in a)
+    assert plain["off"].actor_grads is None and plain["off"].actor_workspace is None
+    for l in [ln] + list(plain.values()):
+        l.close()
+    env.close()

@@ -45,6 +45,11 @@ M = --num-envs rows: alternating windows of (1) the call (its two or three launc
 and (2) torch float32 for the same quantities: critic forward, loss, backward().  Bar: the call is not slower than torch at either M
 beyond the spread of the windows.  Also one SACLearner.update at batch 256: default, device_action_gradient, both options.
     python tools/bench_policy_rollout.py --critic-gradient --windows 6 --launches 100 --out profiles/policy_rollout/dyn65536_critic_gradient.json
+--actor-gradient measures urgym_actor_parameter_gradients in the SAMPLE form on the checkpoint's actor (H = 256) at
+M = 256 and M = num_envs rows, preallocated outputs and workspace, against the torch float32 route for the same quantities
+(TorchActor.sample on the call's own noise, then backward() of (action * d_action).sum() + (log_prob * d_log_prob).sum()), and one
+SACLearner.update at batch 256 four ways: the default route, device_action_gradient, that with device_critic_gradient, and all three.
+    python tools/bench_policy_rollout.py --actor-gradient --windows 6 --launches 100 --out profiles/policy_rollout/dyn65536_actor_gradient.json
 
 With --refresh: what it costs to hand new weights to a device actor / critic, at hidden width 256 and 512.
 `actor_load`, `critic_load_tau1` and `critic_load_polyak` (tau = 0.005) are load_parameters from device tensors, one launch each;
@@ -615,6 +620,105 @@ def critic_gradient_mode(args):
             f.write(line + "\n")
 
 
+def actor_gradient_mode(args):
+    import torch
+
+    from ur_gym_amd import make_vec
+    from ur_gym_amd.evaluation import ACTOR_ARRAYS, LOG_STD_ARRAYS, DeviceActor, DeviceReplay
+    from ur_gym_amd.training import SACLearner, TorchActor
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_policy_rollout.py measures on a GPU; none is visible")
+    dev, n, kind = "cuda:0", args.num_envs, ACTOR_NPZ[args.env]
+    golden = os.path.join(ROOT, "tests", "golden", "actors")
+    env = make_vec(args.env, num_envs=n, device=dev, seed=0, auto_reset=True)
+    env.reset(seed=0)
+    w = dict(np.load(os.path.join(golden, f"actor_{kind}.npz")))
+    w.update(np.load(os.path.join(golden, f"log_std_{kind}.npz")))
+    actor = DeviceActor(w, env)
+    keys = ACTOR_ARRAYS + LOG_STD_ARRAYS
+    ta = TorchActor(actor.in_features, actor.hidden_width).to(dev)
+    for k, p in ta.tensors().items():
+        p.data.copy_(torch.from_numpy(np.ascontiguousarray(w[k], dtype=np.float32)))
+    for _ in range(20):
+        env.step(torch.rand((n, 6), device=dev) * 2.0 - 1.0)
+    sync = lambda: torch.cuda.synchronize(env.device)  # noqa: E731
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def window(fn, count):
+        sync()
+        e0.record()
+        for _ in range(count):
+            fn()
+        e1.record()
+        sync()
+        return e0.elapsed_time(e1) * 1e3 / count
+
+    sizes = {}
+    how = dict(mode="gaussian", seed=1, first_draw=1 << 63)
+    for m in sorted({256, n}):
+        rows = {k: env.buf[k][:m].clone() for k in env.ROW_KEYS}
+        d_action = torch.randn((m, 6), device=dev) / m
+        d_log_prob = torch.full((m,), 1.0 / m, device=dev)
+        x = torch.cat([rows["achieved_goal"], rows["desired_goal"], rows["observation"]], dim=1)
+        out = {k: torch.empty_like(p) for k, p in ta.tensors().items()}
+        ws = env.actor_gradient_workspace(actor, m)
+        eps = env.actor_parameter_gradients(actor, sample=how, rows=rows, d_action=d_action, d_log_prob=d_log_prob, records=("noise",))["noise"]
+
+        def torch_route():  # TorchActor.sample forward on given eps, loss, backward(): the same quantities in torch float32
+            for p in ta.parameters():
+                p.grad = None
+            action, log_prob = ta.sample(x, eps)
+            ((action * d_action).sum() + (log_prob * d_log_prob).sum()).backward()
+
+        kinds = {"gradients": lambda: env.actor_parameter_gradients(actor, sample=how, rows=rows, d_action=d_action, d_log_prob=d_log_prob, out=out, workspace=ws),
+                 "torch": torch_route}
+        for fn in kinds.values():
+            for _ in range(5):
+                fn()
+        sync()
+        agree = {k: {"max_abs_difference_from_torch": float((out[k] - p.grad).abs().max()), "g_abs_max": float(p.grad.abs().max())} for k, p in ta.tensors().items()}
+        windows = {k: [] for k in kinds}
+        for _ in range(args.windows):
+            for name, fn in kinds.items():
+                windows[name].append(window(fn, args.launches))
+        med = {k: float(np.median(v)) for k, v in windows.items()}
+        spread = float(max(windows["torch"]) - min(windows["torch"]))
+        sizes[str(m)] = {"us_median": med, "us_windows": {k: [round(v, 3) for v in vs] for k, vs in windows.items()}, "torch_us_spread": spread,
+                         "launches_per_call": 2 if m <= 1024 else 3, "workspace_bytes": int(ws.numel()) * 4,
+                         "not_slower_than_torch": med["gradients"] <= med["torch"] + spread, "speedup_over_torch": med["torch"] / med["gradients"],
+                         "tensors": agree}
+    actor.close()
+    updates = {}
+    for label, options in (("parent_route", {}), ("device_action_gradient", dict(device_action_gradient=True)),
+                           ("action_and_critic", dict(device_action_gradient=True, device_critic_gradient=True)),
+                           ("all_three_options", dict(device_action_gradient=True, device_critic_gradient=True, device_actor_gradient=True))):
+        learner = SACLearner(env, seed=0, batch_size=256, hidden_width=256, **options)
+        replay = DeviceReplay(env, 4)
+        learner.collect(replay, 4)
+        draw = [0]
+
+        def one_update():
+            draw[0] += 1
+            learner.update(replay, 1, draw[0])
+
+        for _ in range(5):
+            one_update()
+        wdw = [window(one_update, 20) for _ in range(args.windows)]
+        updates[label] = {"us_median": float(np.median(wdw)), "us_windows": [round(v, 2) for v in wdw]}
+        learner.close()
+    result = {"tool": "bench_policy_rollout --actor-gradient", "env": args.env, "hidden_width": int(w["mu_weight"].shape[1]), "windows": args.windows,
+              "launches_per_window": args.launches, "device": torch.cuda.get_device_name(0), "rows": sizes,
+              "not_slower_than_torch": all(v["not_slower_than_torch"] for v in sizes.values()), "learner_update_batch256": updates}
+    env.close()
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--env", default="UR5DynReach-v1", choices=sorted(ACTOR_NPZ))
@@ -637,8 +741,11 @@ def main():
     ap.add_argument("--refresh", action="store_true", help="measure reloading actor / critic weights from device tensors against the host route and a copy (see above)")
     ap.add_argument("--action-gradient", action="store_true", help="measure the critics' action gradient launch against critic_kernel and torch autograd (see above)")
     ap.add_argument("--critic-gradient", action="store_true", help="measure the critics' parameter gradients (two or three launches) against torch autograd (see above)")
+    ap.add_argument("--actor-gradient", action="store_true", help="measure the actor's parameter gradients (two or three launches) against torch autograd (see above)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.actor_gradient:
+        return actor_gradient_mode(args)
     if args.action_gradient:
         return action_gradient_mode(args)
     if args.critic_gradient:

@@ -33,6 +33,9 @@ def main():
                     help="take the actor loss's d min Q / da from the HIP gradient kernel instead of a second torch critic pass (hidden width <= 256)")
     ap.add_argument("--device-critic-gradient", action="store_true",
                     help="take the critic loss's parameter gradients from the HIP kernels instead of torch autograd (hidden width <= 256)")
+    ap.add_argument("--device-actor-gradient", action="store_true",
+                    help="take the actor loss's parameter gradients from the HIP kernels instead of torch autograd: with the two options "
+                         "above, which it needs, no forward or backward pass of an update runs in torch (hidden width <= 256)")
     args = ap.parse_args()
 
     import torch
@@ -47,7 +50,8 @@ def main():
     env.reset(seed=args.seed)
     test_env = make_vec(args.env, num_envs=args.eval_envs, seed=args.seed + 1, auto_reset=False)
     learner = SACLearner(env, seed=args.seed, hidden_width=args.hidden_width, batch_size=args.batch_size,
-                         device_action_gradient=args.device_action_gradient, device_critic_gradient=args.device_critic_gradient)
+                         device_action_gradient=args.device_action_gradient, device_critic_gradient=args.device_critic_gradient,
+                         device_actor_gradient=args.device_actor_gradient)
     eval_actor = DeviceActor(host_arrays(learner.actor.tensors()), test_env)  # actors belong to the environment they were made for
     replay = DeviceReplay(env, args.capacity)
     updates, t0 = 0, time.perf_counter()

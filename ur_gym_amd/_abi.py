@@ -206,6 +206,22 @@ class CriticParamGrads(C.Structure):
 
 CRITIC_GRADIENTS_MAX_COUNT = 65536  # URGYM_CRITIC_GRADIENTS_MAX_COUNT
 
+ACTOR_GRAD_ARRAYS = ("w0", "b0", "w1", "b1", "w_mu", "b_mu", "w_log_std", "b_log_std")  # urgym_actor_params_dev's eight, all required
+ACTOR_GRAD_RECORDS = ("action", "log_prob", "noise", "log_std", "d_mu", "d_log_std", "std")  # optional per-row outputs, each may be NULL
+
+
+class ActorUpstream(C.Structure):
+    """urgym_actor_upstream: the SAMPLE form (d_action, d_log_prob or NULL) or the HEADS form (d_mu and d_log_std); DEVICE pointers."""
+    _fields_ = [(name, C.POINTER(C.c_float)) for name in ("d_action", "d_log_prob", "d_mu", "d_log_std")]
+
+
+class ActorParamGrads(C.Structure):
+    """urgym_actor_param_grads: where urgym_actor_parameter_gradients writes: eight tensors, then the optional per-row outputs."""
+    _fields_ = [(name, C.POINTER(C.c_float)) for name in ACTOR_GRAD_ARRAYS + ACTOR_GRAD_RECORDS]
+
+
+ACTOR_GRADIENTS_MAX_COUNT = 65536  # URGYM_ACTOR_GRADIENTS_MAX_COUNT
+
 REPLAY_TAG = 0x52504C00  # word 3 of the Philox counter of urgym_replay_sample's index draw
 
 # urgym_replay_ring after capacity_steps / reserved0: name -> (ctype of element, shape given (C, N, obs_dim, goal_dim), required)
@@ -276,6 +292,8 @@ EXPORTED_SYMBOLS = [
     "urgym_critic_action_gradient",
     "urgym_critic_parameter_gradients_workspace",
     "urgym_critic_parameter_gradients",
+    "urgym_actor_parameter_gradients_workspace",
+    "urgym_actor_parameter_gradients",
     "urgym_actor_sample_rows",
     "urgym_rollout_collect",
     "urgym_replay_sample",

@@ -74,6 +74,9 @@ def lib():
     L.urgym_critic_parameter_gradients_workspace.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]
     L.urgym_critic_parameter_gradients.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.CriticRows), C.c_int, C.c_void_p, C.c_void_p, C.c_float,
                                                    C.POINTER(_abi.CriticParamGrads), C.c_void_p, C.c_uint64, C.c_void_p]
+    L.urgym_actor_parameter_gradients_workspace.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]
+    L.urgym_actor_parameter_gradients.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.Sampling), C.POINTER(_abi.CriticRows), C.c_int,
+                                                  C.POINTER(_abi.ActorUpstream), C.POINTER(_abi.ActorParamGrads), C.c_void_p, C.c_uint64, C.c_void_p]
     L.urgym_actor_sample_rows.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.Sampling), C.POINTER(_abi.CriticRows), C.c_int, C.c_void_p,
                                           C.c_void_p, C.c_void_p]
     L.urgym_rollout_collect.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.Sampling), C.c_int, C.POINTER(_abi.ReplayRing), C.c_int, C.c_void_p]

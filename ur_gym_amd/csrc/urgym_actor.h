@@ -64,4 +64,28 @@ void actor_mark_log_std(Actor* a);  // a reload has filled the log_std head
 // actor_launch with sampled actions (actions != nullptr).  UNIFORM runs no forward pass; MEAN and GAUSSIAN need the log_std head.
 void actor_launch_sampled(Actor* a, const ActorEnv& env, float* actions, const ActorPass* pass, const ActorSample& how, hipStream_t s);
 
+// The parameter gradients of the actor summed over M rows (urgym_actor_backward.hip; include/urgym.h, urgym_actor_parameter_gradients):
+// the rows, how the pass samples (MEAN or GAUSSIAN; the noise counter's env word is the row index), the upstream gradient in one of
+// its two forms (d_action, with d_log_prob or null; or d_mu and d_log_std), the eight output tensors in the order of
+// urgym_actor_params_dev, the optional per-row outputs and the workspace.
+struct ActorBackwardCall {
+  const float *observation, *achieved_goal, *desired_goal;
+  int M, obs_dim, goal_dim;
+  int mode;  // URGYM_SAMPLE_MEAN or _GAUSSIAN
+  uint64_t seed, draw;
+  const float *d_action, *d_log_prob;  // the SAMPLE form: d_action != null
+  const float *d_mu, *d_log_std;       // the HEADS form: both != null
+  float* grad[8];
+  float *action, *log_prob, *noise, *log_std, *out_d_mu, *out_d_log_std, *std;  // each may be null
+  float* workspace;  // actor_backward_workspace_bytes(a, M), 16-byte aligned
+};
+// the widths the per-row kernel is built for (hidden_width <= 256)
+bool actor_backward_supported(Actor* a);
+uint64_t actor_backward_workspace_bytes(Actor* a, int count);
+// the launches of one call: 2 up to 1024 rows, 3 above
+int actor_backward_launches(int count);
+// on `s`; the caller has validated `call`, actor_backward_supported(a) and the log_std head
+void actor_backward_launch(Actor* a, const ActorBackwardCall& call, hipStream_t s);
+constexpr int ACTOR_BACKWARD_MAX_COUNT = 65536;  // urgym_actor_backward_map.h asserts it
+
 }  // namespace urgym

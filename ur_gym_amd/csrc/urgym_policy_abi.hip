@@ -1,5 +1,5 @@
 // urgym_policy_abi.hip — the learner's half of the C-ABI of include/urgym.h: actors (create / forward / sample / rollouts), the replay
-// ring, the weight reloads, the twin critic and its two gradients.  Host code only: every check is made here, before the first launch,
+// ring, the weight reloads, the twin critic and its two gradients, the actor's parameter gradients.  Host code only: every check is made here, before the first launch,
 // and every launch goes through urgym_actor.h, urgym_critic.h, urgym_replay.h and urgym_weights.h, or through do_step of urgym_hip.hip
 // (urgym_handle.h).  No kernel lives in this unit, so adding a check here leaves the step kernels' object file alone.
 #include <hip/hip_runtime.h>
@@ -239,6 +239,18 @@ int backward_critic(Handle* h, void* critic, int count, const char* who, Critic*
   if (int rc = enter_critic(h, critic, who, out, critic_backward_supported, "the gradient kernels are built for hidden widths up to 256")) return rc;
   if (count <= 0) return fail_in(h, URGYM_ERR_ARG, who, "count must be positive");
   if (count > CRITIC_BACKWARD_MAX_COUNT) return fail_in(h, URGYM_ERR_ARG, who, "count is above URGYM_CRITIC_GRADIENTS_MAX_COUNT (65536)");
+  return URGYM_OK;
+}
+
+// the checks urgym_actor_parameter_gradients and its workspace query share: an actor of this handle that takes this env kind's features,
+// has a log_std head and a width the kernels are built for, and count within [1, URGYM_ACTOR_GRADIENTS_MAX_COUNT]
+int backward_actor(Handle* h, void* actor, int count, const char* who, Actor** out) {
+  static_assert(URGYM_ACTOR_GRADIENTS_MAX_COUNT == ACTOR_BACKWARD_MAX_COUNT, "include/urgym.h");
+  if (int rc = enter_actor(h, actor, who, out, "the actor does not take this env kind's features")) return rc;
+  if (!actor_has_log_std(*out)) return fail_in(h, URGYM_ERR_ARG, who, "the actor has no log_std head (urgym_actor_set_log_std)");
+  if (!actor_backward_supported(*out)) return fail_in(h, URGYM_ERR_ARG, who, "the gradient kernels are built for hidden widths up to 256");
+  if (count <= 0) return fail_in(h, URGYM_ERR_ARG, who, "count must be positive");
+  if (count > ACTOR_BACKWARD_MAX_COUNT) return fail_in(h, URGYM_ERR_ARG, who, "count is above URGYM_ACTOR_GRADIENTS_MAX_COUNT (65536)");
   return URGYM_OK;
 }
 
@@ -535,6 +547,52 @@ int urgym_critic_parameter_gradients(void* handle, void* critic, const urgym_cri
   call.dq = dq, call.target = target, call.scale = target ? scale : 0.0f;
   call.q = out->q, call.workspace = (float*)workspace;
   critic_backward_launch(c, call, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_actor_parameter_gradients_workspace(void* handle, void* actor, int count, uint64_t* bytes) {
+  const char* who = "urgym_actor_parameter_gradients_workspace";
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (!bytes) return fail(h, URGYM_ERR_ARG, "urgym_actor_parameter_gradients_workspace: null bytes");
+  Actor* a = nullptr;
+  if (int rc = backward_actor(h, actor, count, who, &a)) return rc;
+  *bytes = actor_backward_workspace_bytes(a, count);
+  return URGYM_OK;
+}
+
+int urgym_actor_parameter_gradients(void* handle, void* actor, const urgym_sampling* how, const urgym_critic_rows* rows, int count, const urgym_actor_upstream* upstream, const urgym_actor_param_grads* out, void* workspace, uint64_t workspace_bytes, void* stream) {
+  const char* who = "urgym_actor_parameter_gradients";
+  Handle* h = (Handle*)handle;
+  Actor* a = nullptr;
+  if (int rc = backward_actor(h, actor, count, who, &a)) return rc;
+  if (int rc = check_sampling(h, a, how, true, who)) return rc;
+  if (how->mode == URGYM_SAMPLE_UNIFORM) return fail_in(h, URGYM_ERR_ARG, who, "mode must be URGYM_SAMPLE_GAUSSIAN or URGYM_SAMPLE_MEAN (UNIFORM runs no network)");
+  ActorBackwardCall call;
+  memset(&call, 0, sizeof(call));
+  if (int rc = resolve_rows(h, rows, count, who, &call.observation, &call.achieved_goal, &call.desired_goal)) return rc;
+  if (!upstream) return fail_in(h, URGYM_ERR_ARG, who, "null upstream");
+  const bool sample = upstream->d_action || upstream->d_log_prob, heads = upstream->d_mu || upstream->d_log_std;
+  if (sample == heads) return fail_in(h, URGYM_ERR_ARG, who, "exactly one upstream form must be given: d_action (with d_log_prob or NULL), or d_mu and d_log_std");
+  if (sample && !upstream->d_action) return fail_in(h, URGYM_ERR_ARG, who, "d_log_prob is given without d_action");
+  if (heads && (!upstream->d_mu || !upstream->d_log_std)) return fail_in(h, URGYM_ERR_ARG, who, "the HEADS form needs both d_mu and d_log_std");
+  if (!out) return fail_in(h, URGYM_ERR_ARG, who, "null out");
+  float* const tensors[8] = {out->w0, out->b0, out->w1, out->b1, out->w_mu, out->b_mu, out->w_log_std, out->b_log_std};
+  for (int i = 0; i < 8; i++) {
+    if (!tensors[i]) return fail_in(h, URGYM_ERR_ARG, who, "a gradient pointer is null (all eight are required)");
+    call.grad[i] = tensors[i];
+  }
+  if (!workspace) return fail_in(h, URGYM_ERR_ARG, who, "null workspace");
+  if ((uintptr_t)workspace % 16 != 0) return fail_in(h, URGYM_ERR_ARG, who, "the workspace must be 16-byte aligned");
+  if (workspace_bytes < actor_backward_workspace_bytes(a, count))
+    return fail_in(h, URGYM_ERR_ARG, who, "the workspace is smaller than urgym_actor_parameter_gradients_workspace reports");
+  call.M = count, call.obs_dim = h->obs_dim, call.goal_dim = h->goal_dim;
+  call.mode = how->mode, call.seed = how->seed, call.draw = how->first_draw;
+  call.d_action = upstream->d_action, call.d_log_prob = upstream->d_log_prob, call.d_mu = upstream->d_mu, call.d_log_std = upstream->d_log_std;
+  call.action = out->action, call.log_prob = out->log_prob, call.noise = out->noise, call.log_std = out->log_std;
+  call.out_d_mu = out->d_mu, call.out_d_log_std = out->d_log_std, call.std = out->std;
+  call.workspace = (float*)workspace;
+  actor_backward_launch(a, call, (hipStream_t)stream);
   return launched(h);
 }
 

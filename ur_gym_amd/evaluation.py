@@ -175,6 +175,63 @@ class StochasticActor(DeterministicActor):
         squash = np.log(np.float32(1.0) - action * action + np.float32(1e-6)).sum(axis=1)
         return action, (self.gaussian_log_prob(eps, log_std) - squash).astype(np.float32)
 
+    def parameter_gradients(self, achieved_goal, desired_goal, observation, eps=None, d_action=None, d_log_prob=None, d_mu=None, d_log_std=None):
+        """(grads, records) in float32 as include/urgym.h states urgym_actor_parameter_gradients: `grads` keyed by ACTOR_ARRAYS +
+        LOG_STD_ARRAYS, the gradients of a loss summed over the rows; `records` a dict with ``action``, ``log_prob``, ``noise``,
+        ``log_std`` (clamped), ``std`` = exp(log_std), ``d_mu`` and ``d_log_std`` (before the clamp derivative).  `eps`: the noise [N, 6] (None = zeros, the
+        mean).  The upstream gradient is either the SAMPLE form (`d_action` [N, 6], `d_log_prob` [N] or None = 0: the gradient with
+        respect to this call's action and log_prob, the noise a constant; ``sample_head_gradients`` states its arithmetic) or the
+        HEADS form (`d_mu` and `d_log_std` [N, 6], used as they are).  A pre-activation of exactly 0 has derivative 0; the clamp
+        passes the gradient where -20 <= r <= 2.  (The order of the sums is numpy's, not the kernel's.)"""
+        sample_form, heads_form = d_action is not None or d_log_prob is not None, d_mu is not None or d_log_std is not None
+        if sample_form == heads_form or (sample_form and d_action is None) or (heads_form and (d_mu is None or d_log_std is None)):
+            raise ValueError("exactly one upstream form must be given: d_action (with d_log_prob or None), or both d_mu and d_log_std")
+        f, zero = np.float32, np.float32(0.0)
+        w = self.w
+        x = np.concatenate([achieved_goal, desired_goal, observation], axis=1).astype(f)
+        assert x.shape[1] == self.in_features, (x.shape, self.in_features)
+        eps = np.zeros((len(x), 6), f) if eps is None else np.asarray(eps, dtype=f)
+        z1 = x @ w["latent_pi_0_weight"].T + w["latent_pi_0_bias"]
+        h1 = np.maximum(z1, zero)
+        z2 = h1 @ w["latent_pi_2_weight"].T + w["latent_pi_2_bias"]
+        h2 = np.maximum(z2, zero)
+        mu = (h2 @ w["mu_weight"].T + w["mu_bias"]).astype(f)
+        r = (h2 @ w["log_std_weight"].T + w["log_std_bias"]).astype(f)
+        log_std = np.clip(r, f(LOG_STD_MIN), f(LOG_STD_MAX)).astype(f)
+        std = np.exp(log_std).astype(f)
+        action = np.tanh(mu + std * eps).astype(f)
+        squash = np.log(f(1.0) - action * action + f(1e-6)).sum(axis=1)
+        log_prob = (self.gaussian_log_prob(eps, log_std) - squash).astype(f)
+        if sample_form:
+            d_mu, d_log_std = sample_head_gradients(action, log_std, eps, d_action, d_log_prob, std=std)
+        d_mu, d_log_std = np.asarray(d_mu, dtype=f), np.asarray(d_log_std, dtype=f)
+        dr = np.where((r >= f(LOG_STD_MIN)) & (r <= f(LOG_STD_MAX)), d_log_std, zero).astype(f)
+        d2 = np.where(z2 > 0.0, d_mu @ w["mu_weight"] + dr @ w["log_std_weight"], zero).astype(f)
+        d1 = np.where(z1 > 0.0, d2 @ w["latent_pi_2_weight"], zero).astype(f)
+        g = (d1.T @ x, d1.sum(axis=0), d2.T @ h1, d2.sum(axis=0), d_mu.T @ h2, d_mu.sum(axis=0), dr.T @ h2, dr.sum(axis=0))
+        grads = {k: np.asarray(v, dtype=f) for k, v in zip(ACTOR_ARRAYS + LOG_STD_ARRAYS, g)}
+        return grads, dict(action=action, log_prob=log_prob, noise=eps, log_std=log_std, std=std, d_mu=d_mu, d_log_std=d_log_std)
+
+
+def sample_head_gradients(action, log_std, noise, d_action, d_log_prob=None, std=None):
+    """(d_mu, d_log_std), float32 [N, 6] each: the head arithmetic of urgym_actor_parameter_gradients' SAMPLE form as include/urgym.h
+    states it, from the call's own records, every line one float32 operation rounded on its own:
+        p = a * a;  t = 1 - p;  c = (2 a) / (t + 1e-6);  A = d_action + (d_log_prob * c);  d_pre = A * t;  d_mu = d_pre;
+        e = exp(log_std) * noise;  d_log_std = (d_pre * e) - d_log_prob.
+    `d_log_prob` None means 0.  `std`: exp(log_std) as the forward pass formed it, where the caller has it bit for bit (the call's ``std`` record: the
+    kernel's expf and numpy's float32 exp are both good to an ulp and differ in the last bit on more than a third of the values); None = numpy's."""
+    f = np.float32
+    a, ls, eps, da = (np.asarray(v, dtype=f) for v in (action, log_std, noise, d_action))
+    dlp = np.zeros(len(a), f) if d_log_prob is None else np.asarray(d_log_prob, dtype=f)
+    dlp = dlp[:, None]
+    p = (a * a).astype(f)
+    t = (f(1.0) - p).astype(f)
+    c = ((f(2.0) * a).astype(f) / (t + f(1e-6)).astype(f)).astype(f)
+    big_a = (da + (dlp * c).astype(f)).astype(f)
+    d_pre = (big_a * t).astype(f)
+    e = ((np.exp(ls).astype(f) if std is None else np.asarray(std, dtype=f)) * eps).astype(f)
+    return d_pre, ((d_pre * e).astype(f) - dlp).astype(f)
+
 
 def goal_grid(low, high, step=0.05, repeats=5):
     """utils/generate.py:29-43, 63-80: every grid node of the goal range, `repeats` times (float arithmetic as there)."""

@@ -17,7 +17,13 @@ minibatch gather on the HIP kernels, and gradients and optimisers in torch autog
     option above) holds the torch critic's parameters when ``update`` starts, ``env.critic_parameter_gradients(target=y, scale=1/M)``
     writes d loss / d parameters into preallocated tensors that ARE the parameters' ``.grad``, the loss value is formed from the
     returned q, Adam steps, and the online critic is reloaded.
-    Neither synchronises with the host.  There is no logging, no callback and no checkpoint format here; tools/train_sac.py runs it.
+    With ``device_actor_gradient=True`` (it needs ``device_action_gradient=True``) the torch actor does not run at all: the DeviceActor
+    draws action_pi and log_prob on the batch rows (``policy_actions(sample=, rows=)`` with draw | 2^63, apart from the draw
+    ``sample_targets`` takes for a' on the same row indices), and after the critic step ONE ``env.actor_parameter_gradients`` call in
+    the SAMPLE form, d_action = -g / M and d_log_prob = ent_coef / M, writes d loss / d parameters into preallocated tensors that ARE
+    the actor parameters' ``.grad``.  No ``torch.Generator`` is drawn from, and nothing of ``update`` goes through torch autograd but
+    the entropy coefficient's scalar loss.
+    None of them synchronises with the host.  There is no logging, no callback and no checkpoint format here; tools/train_sac.py runs it.
 """
 import numpy as np
 import torch
@@ -27,7 +33,8 @@ from .evaluation import ACTOR_ARRAYS, CRITIC_ARRAYS, LOG_STD_ARRAYS, LOG_STD_MAX
 
 # SB3's SAC defaults where train.py does not set them (tests/golden/critics/sac_hyperparameters.json has the checkpoints' gamma, tau)
 SAC_DEFAULTS = dict(gamma=0.95, tau=0.005, learning_rate=1e-4, batch_size=256, learning_starts=100, hidden_width=256, target_entropy=-6.0,
-                    ent_coef_init=1.0, device_action_gradient=False, device_critic_gradient=False)
+                    ent_coef_init=1.0, device_action_gradient=False, device_critic_gradient=False,
+                    device_actor_gradient=False)
 
 
 def _mlp(n_in, hidden, n_out=None):
@@ -120,6 +127,18 @@ class SACLearner:
                 for k, p in w.items():
                     p.grad = g[k]
             self.critic_workspace = env.critic_gradient_workspace(self.online, int(hp["batch_size"]))
+        # with device_actor_gradient the actor parameters' .grad are tensors of the learner's as well, and so are the upstream gradients
+        self.actor_grads = self.actor_workspace = self.actor_d_action = self.actor_d_log_prob = None
+        if hp["device_actor_gradient"]:
+            if not hp["device_action_gradient"]:
+                raise ValueError("device_actor_gradient needs device_action_gradient=True (the upstream gradient is the critics' d min Q / da)")
+            M = int(hp["batch_size"])
+            self.actor_grads = {k: torch.zeros_like(p) for k, p in self.actor.tensors().items()}
+            for k, p in self.actor.tensors().items():
+                p.grad = self.actor_grads[k]
+            self.actor_workspace = env.actor_gradient_workspace(self.device_actor, M)
+            self.actor_d_action = torch.zeros((M, 6), dtype=torch.float32, device=dev)
+            self.actor_d_log_prob = torch.zeros((M,), dtype=torch.float32, device=dev)
         self.env_steps = 0  # per env; decides between the warm-up and the policy
         self.draw = 0       # draw index of the next collection pass
 
@@ -136,6 +155,8 @@ class SACLearner:
         tensors (not synchronised)."""
         hp = self.hp
         gamma = float(hp["gamma"])
+        if self.actor_grads is not None and not 0 <= int(draw) < 2 ** 63:
+            raise ValueError("with device_actor_gradient the draw must be below 2**63 (its top bit marks the policy's own draw)")
         batch = replay.sample_targets(self.device_actor, self.target, hp["batch_size"], seed, draw, gamma, 0.0)
         x = _features(batch["observations"])
         with torch.no_grad():
@@ -143,8 +164,13 @@ class SACLearner:
             discount = gamma * (~batch["terminated"]).to(torch.float32)
             y = batch["target"] - discount * ent_coef * batch["next_log_prob"]
 
-        eps = torch.randn((x.shape[0], 6), device=x.device, generator=self.noise)
-        action_pi, log_prob = self.actor.sample(x, eps)
+        if self.actor_grads is None:
+            eps = torch.randn((x.shape[0], 6), device=x.device, generator=self.noise)
+            action_pi, log_prob = self.actor.sample(x, eps)
+        else:
+            # the DeviceActor holds the torch actor's parameters here (loaded at construction and at the end of every update)
+            how = dict(mode="gaussian", seed=seed, first_draw=int(draw) | 1 << 63)
+            action_pi, log_prob = self.env.policy_actions(self.device_actor, sample=how, rows=batch["observations"])
 
         ent_loss = -(self.log_ent_coef * (log_prob.detach() + hp["target_entropy"])).mean()
         self.ent_opt.zero_grad(set_to_none=True)
@@ -164,6 +190,21 @@ class SACLearner:
             critic_loss = 0.5 * (((got["q"][0] - y) ** 2).mean() + ((got["q"][1] - y) ** 2).mean())
             self.critic_opt.step()  # on the .grad tensors the launches wrote
             self.online.load_parameters(self.critic.tensors(), tau=1.0)
+
+        if self.actor_grads is not None:
+            M = x.shape[0]
+            if self.critic_grads is None:
+                self.online.load_parameters(self.critic.tensors(), tau=1.0)
+            grad = self.env.critic_action_gradient(self.online, action_pi, rows=batch["observations"])
+            torch.mul(grad["dqmin_da"], -1.0 / M, out=self.actor_d_action)
+            self.actor_d_log_prob.copy_((ent_coef / M).expand(M))
+            self.env.actor_parameter_gradients(self.device_actor, sample=how, rows=batch["observations"], d_action=self.actor_d_action,
+                                               d_log_prob=self.actor_d_log_prob, out=self.actor_grads, workspace=self.actor_workspace)
+            actor_loss = (ent_coef * log_prob - grad["q_min"]).mean()
+            self.actor_opt.step()  # on the .grad tensors the launches wrote
+            self.device_actor.load_parameters(self.actor.tensors())
+            self.target.load_parameters(self.critic.tensors(), tau=hp["tau"])
+            return {"critic_loss": critic_loss.detach(), "actor_loss": actor_loss.detach(), "ent_coef_loss": ent_loss.detach()}
 
         self.actor_opt.zero_grad(set_to_none=True)
         if not hp["device_action_gradient"]:

@@ -356,6 +356,74 @@ class UR5ReachVectorEnv:
                                                                 C.c_void_p(workspace.data_ptr()), workspace.numel() * 4, self._stream()), self._h)
         return {"grads": out, "q": q}
 
+    def actor_gradient_workspace(self, actor, count):
+        """A fresh workspace for ``actor_parameter_gradients`` on `count` rows: a float32 device tensor of the size the library reports."""
+        size = C.c_uint64()
+        _native.check(self.lib.urgym_actor_parameter_gradients_workspace(self._h, self._actor_ptr(actor), int(count), C.byref(size)), self._h)
+        return torch.empty(((size.value + 3) // 4,), dtype=torch.float32, device=self.device)
+
+    ACTOR_GRADIENT_RECORDS = _abi.ACTOR_GRAD_RECORDS[2:]  # besides action and log_prob, which are always returned
+
+    def actor_parameter_gradients(self, actor, *, sample, rows=None, d_action=None, d_log_prob=None, d_mu=None, d_log_std=None, out=None,
+                                  workspace=None, records=()):
+        """The gradients of a loss on `actor` (a DeviceActor with its log_std head) with respect to its parameters, summed over the rows
+        (urgym_actor_parameter_gradients: two launches up to 1024 rows, three above).  `sample` as in ``policy_actions`` (mode
+        "gaussian" or "mean"); `rows` as in ``critic_values`` (None = the live buffers).  The upstream gradient is either `d_action`
+        [..., 6] with `d_log_prob` [...] or None (= 0) -- the gradient with respect to the call's own action and log_prob, the noise a
+        constant -- or `d_mu` and `d_log_std` [..., 6] each, the gradient at the heads, used as it is.  Returns a dict: ``grads``, keyed
+        by ACTOR_ARRAYS + LOG_STD_ARRAYS and shaped like the parameters (a parameter's ``.grad`` can be handed in through `out`, such
+        a dict); ``action`` [..., 6] and ``log_prob`` [...], bitwise ``policy_actions(..., sample=, rows=)``'s; and those of
+        ACTOR_GRADIENT_RECORDS that `records` names (``noise``, ``log_std`` after the clamp, ``d_mu``, ``d_log_std`` before the clamp
+        derivative, ``std`` = exp(log_std) as the forward pass formed it).  `workspace`: from ``actor_gradient_workspace`` (allocated where not given).  Nothing is synchronised, and the
+        sums have a fixed order: two calls give the same bits."""
+        from .evaluation import ACTOR_ARRAYS, LOG_STD_ARRAYS
+
+        a = self._actor_ptr(actor)
+        keys = ACTOR_ARRAYS + LOG_STD_ARRAYS
+        sample_form, heads_form = d_action is not None or d_log_prob is not None, d_mu is not None or d_log_std is not None
+        if sample_form == heads_form or (sample_form and d_action is None) or (heads_form and (d_mu is None or d_log_std is None)):
+            raise ValueError("exactly one upstream form must be given: d_action (with d_log_prob or None), or both d_mu and d_log_std")
+        unknown = [k for k in records if k not in self.ACTOR_GRADIENT_RECORDS]
+        if unknown:
+            raise ValueError(f"unknown records {unknown}; available: {self.ACTOR_GRADIENT_RECORDS}")
+        cr, lead, keep = self._rows(rows)
+        count = int(np.prod(lead))
+        up = _abi.ActorUpstream()
+        for name, t, shape in (("d_action", d_action, lead + (6,)), ("d_log_prob", d_log_prob, lead), ("d_mu", d_mu, lead + (6,)), ("d_log_std", d_log_std, lead + (6,))):
+            if t is None:
+                continue
+            t = torch.as_tensor(t, device=self.device)
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                t = t.to(torch.float32).contiguous()
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
+            keep.append(t)
+            setattr(up, name, C.cast(t.data_ptr(), C.POINTER(C.c_float)))
+        n, H = actor.in_features, actor.hidden_width
+        shapes = dict(zip(keys, ((H, n), (H,), (H, H), (H,), (6, H), (6,), (6, H), (6,))))
+        if out is None:
+            out = {k: torch.empty(sh, dtype=torch.float32, device=self.device) for k, sh in shapes.items()}
+        grads = _abi.ActorParamGrads()
+        for field, k in zip(_abi.ACTOR_GRAD_ARRAYS, keys):
+            t = out[k]
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != torch.device(self.device) or tuple(t.shape) != shapes[k]:
+                raise ValueError(f"out[{k!r}] must be a contiguous float32 tensor of shape {shapes[k]} on {self.device}")
+            setattr(grads, field, C.cast(t.data_ptr(), C.POINTER(C.c_float)))
+        res = {"grads": out, "action": torch.empty(lead + (6,), dtype=torch.float32, device=self.device),
+               "log_prob": torch.empty(lead, dtype=torch.float32, device=self.device)}
+        for k in records:
+            res[k] = torch.empty(lead + (6,), dtype=torch.float32, device=self.device)
+        for k in ("action", "log_prob") + tuple(records):
+            setattr(grads, k, C.cast(res[k].data_ptr(), C.POINTER(C.c_float)))
+        if workspace is None:
+            workspace = self.actor_gradient_workspace(actor, count)
+        if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.float32 or not workspace.is_contiguous() or workspace.device != torch.device(self.device):
+            raise ValueError(f"workspace must be a contiguous float32 tensor on {self.device} (actor_gradient_workspace)")
+        how = self._sampling(sample)
+        _native.check(self.lib.urgym_actor_parameter_gradients(self._h, a, C.byref(how), C.byref(cr), count, C.byref(up), C.byref(grads),
+                                                               C.c_void_p(workspace.data_ptr()), workspace.numel() * 4, self._stream()), self._h)
+        return res
+
     def policy_actions(self, actor, out=None, sample=None, rows=None):
         """model.predict(obs, deterministic=True) (model_test.py:41) for all envs, by the HIP actor kernel, from the live
         observation buffers: float32 [N, 6] on the device.
