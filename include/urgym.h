@@ -689,6 +689,105 @@ int urgym_actor_parameter_gradients_workspace(void* handle, void* actor, int cou
  * below the queried size. */
 int urgym_actor_parameter_gradients(void* handle, void* actor, const urgym_sampling* how, const urgym_critic_rows* rows, int count, const urgym_actor_upstream* upstream, const urgym_actor_param_grads* out, void* workspace, uint64_t workspace_bytes, void* stream);
 
+/* ---- Adam on the device (train.py's SAC keeps SB3's optimiser: torch.optim.Adam with betas (0.9, 0.999), eps 1e-8, no weight decay,
+ * no amsgrad).  After the gradient calls above have written a network's gradients, ONE launch steps its parameters in place and
+ * writes the packed buffer the kernels read from the stepped values: what a learner otherwise does with optimizer.step() followed by
+ * urgym_actor_load / urgym_critic_load.  Added WITHIN ABI version 4: no struct above changed, URGYM_ABI_VERSION did not move, the new
+ * symbols (urgym_adam_coefficients, urgym_actor_adam_step, urgym_critic_adam_step) are found by lookup.
+ *
+ * The library keeps NO optimiser state: the caller owns the moment tensors and counts the steps.
+ *
+ * Per element, with the seven float32 coefficients of urgym_adam_coefficients, everything float32 and every line ONE operation rounded
+ * on its own (no fused multiply-add; sqrt and / correctly rounded; subnormals kept):
+ *   m' = (b1 * m) + (omb1 * g)
+ *   gg = g * g          v' = (b2 * v) + (omb2 * gg)
+ *   s  = sqrt(v')       d  = (s / bc2_sqrt) + eps
+ *   u  = m' / d         p' = p - (step_size * u)
+ * ur_gym_amd.evaluation.adam_step restates it.  (torch.optim.Adam computes the same quantities in another association -- lerp for m,
+ * addcmul for v, addcdiv for p -- and agrees to rounding, not bitwise.) */
+
+typedef struct urgym_adam_hyper {
+  double lr;         /* finite, >= 0 */
+  double beta1;      /* in [0, 1) */
+  double beta2;      /* in [0, 1) */
+  double eps;        /* finite, > 0 */
+  int64_t step;      /* the 1-based index of THIS step, counted by the caller */
+  int32_t reserved0; /* must be 0 */
+} urgym_adam_hyper;
+
+/* Host only, launches nothing: out = { b1, omb1, b2, omb2, step_size, bc2_sqrt, eps }, each computed in double and rounded to float32
+ * once.  With corr1 = 1 - beta1^step and corr2 = 1 - beta2^step:
+ *   b1 = beta1    omb1 = 1 - beta1    b2 = beta2    omb2 = 1 - beta2    step_size = lr / corr1    bc2_sqrt = sqrt(corr2)    eps = eps
+ * The step calls below take their numbers from this function, so a restatement that calls it uses bit-identical coefficients whatever
+ * pow the host's libm has.  Refused (URGYM_ERR_ARG): NULL hp or out, and what the step calls refuse about hp. */
+int urgym_adam_coefficients(const urgym_adam_hyper* hp, float out[7]);
+
+/* The eight tensors of an actor (urgym_actor_params_dev's) as DEVICE pointers that are written, and as ones that are only read. */
+typedef struct urgym_actor_tensors {
+  float* w0;        /* [hidden_width][in_features] */
+  float* b0;        /* [hidden_width] */
+  float* w1;        /* [hidden_width][hidden_width] */
+  float* b1;        /* [hidden_width] */
+  float* w_mu;      /* [6][hidden_width] */
+  float* b_mu;      /* [6] */
+  float* w_log_std; /* [6][hidden_width] */
+  float* b_log_std; /* [6] */
+} urgym_actor_tensors;
+
+typedef struct urgym_actor_tensors_const {
+  const float* w0;
+  const float* b0;
+  const float* w1;
+  const float* b1;
+  const float* w_mu;
+  const float* b_mu;
+  const float* w_log_std;
+  const float* b_log_std;
+} urgym_actor_tensors_const;
+
+/* All 32 pointers are required (the learner's actor always has the log_std head): DEVICE, float32, torch's [out][in] layout, 4-byte
+ * aligned.  The 32 tensors must not overlap one another: that is the caller's duty, nothing checks it. */
+typedef struct urgym_actor_adam {
+  int32_t in_features;  /* must be the actor's */
+  int32_t hidden_width; /* must be the actor's */
+  int32_t reserved0;    /* must be 0 */
+  urgym_actor_tensors param;       /* read and written: p -> p' */
+  urgym_actor_tensors_const grad;  /* read */
+  urgym_actor_tensors exp_avg;     /* read and written: m -> m' */
+  urgym_actor_tensors exp_avg_sq;  /* read and written: v -> v' */
+} urgym_actor_adam;
+
+/* The same for both Q-networks: 4 x 12 pointers, all required, none overlapping another. */
+typedef struct urgym_critic_adam {
+  int32_t in_features;  /* must be the critic's */
+  int32_t hidden_width; /* must be the critic's */
+  int32_t reserved0;    /* must be 0 */
+  urgym_q_network_grad param[2];      /* read and written */
+  urgym_q_network_dev grad[2];        /* read */
+  urgym_q_network_grad exp_avg[2];    /* read and written */
+  urgym_q_network_grad exp_avg_sq[2]; /* read and written */
+} urgym_critic_adam;
+
+/* Both calls: ONE launch on `stream`; no allocation, no host synchronisation, everything validated before the launch.  The tensors are
+ * read and written when the launch RUNS: the caller keeps them alive until then and orders whatever writes the gradients before the
+ * call on `stream`.  Launches enqueued earlier on the stream see the old weights, later ones the new.  Every parameter element is
+ * stepped exactly once per call.  There is no width cap beyond what the objects accept (hidden_width up to 512).
+ *
+ * Refused by both (URGYM_ERR_ARG, nothing is launched, the objects stay usable): NULL handle / object / struct / hp; an object of
+ * another handle; any NULL tensor pointer; in_features or hidden_width other than the object's; reserved0 != 0 (the struct's or hp's);
+ * lr not finite or negative; beta1 or beta2 outside [0, 1); eps not finite or <= 0; step < 1. */
+
+/* Steps the eight tensors of the actor in place (p', m', v') and writes every float of the actor's packed buffer from p': padding as
+ * +0.0f, the log_std head included.  From this launch on the actor has a head, as with urgym_actor_load given both head pointers. */
+int urgym_actor_adam_step(void* handle, void* actor, const urgym_actor_adam* t, const urgym_adam_hyper* hp, void* stream);
+
+/* Steps the twelve tensors of both Q-networks in place and writes every float of `online`'s packed buffer from p'.  With target !=
+ * NULL the same launch blends `target`'s packed buffer exactly as urgym_critic_load does: packed = (packed * omt) + (tau * p') with omt
+ * = 1.0f - tau, three float32 operations each rounded on its own; at tau == 1 the old value is not read; padding stays +0.  `tau` is
+ * ignored when target is NULL.  Refused besides the above: target == online; a target whose in_features or hidden_width differ from
+ * online's; with a target, tau outside (0, 1] or not finite. */
+int urgym_critic_adam_step(void* handle, void* online, void* target_or_NULL, const urgym_critic_adam* t, const urgym_adam_hyper* hp, float tau, void* stream);
+
 /* Verification aid, not a hot path: synchronises the device, then copies the object's packed buffer (the kernel's own layout,
  * ur_gym_amd/csrc/urgym_pack_map.h) to host_out and stores its length in floats in *count.  host_out == NULL only reports *count;
  * otherwise capacity (in floats) must be at least that.  Refused: NULL handle / object / count, an object of another handle,

@@ -50,6 +50,13 @@ M = 256 and M = num_envs rows, preallocated outputs and workspace, against the t
 (TorchActor.sample on the call's own noise, then backward() of (action * d_action).sum() + (log_prob * d_log_prob).sum()), and one
 SACLearner.update at batch 256 four ways: the default route, device_action_gradient, that with device_critic_gradient, and all three.
     python tools/bench_policy_rollout.py --actor-gradient --windows 6 --launches 100 --out profiles/policy_rollout/dyn65536_actor_gradient.json
+--optimizer measures the Adam step kernels at hidden width 256 and 512 on freshly initialised networks with
+seeded gradients: one critic_adam_step with a target (tau = 0.005) against torch.optim.Adam.step on the twelve .grad tensors followed by
+online.load_parameters(tau=1) and target.load_parameters(tau); one actor_adam_step against Adam.step followed by
+device_actor.load_parameters; torch's fused=True Adam in both comparisons as a second line (not the bar).  Each route steps parameters of
+its own.  Alternating windows in one process, medians.  Bar: each call is not slower than the torch route beyond the spread of torch's
+windows.  Then one SACLearner.update at batch 256 with the three gradient options and with device_optimizer as well, alternating.
+    python tools/bench_policy_rollout.py --optimizer --windows 6 --launches 100 --out profiles/policy_rollout/dyn65536_optimizer.json
 
 With --refresh: what it costs to hand new weights to a device actor / critic, at hidden width 256 and 512.
 `actor_load`, `critic_load_tau1` and `critic_load_polyak` (tau = 0.005) are load_parameters from device tensors, one launch each;
@@ -719,6 +726,140 @@ def actor_gradient_mode(args):
             f.write(line + "\n")
 
 
+def optimizer_mode(args):
+    """--optimizer: one critic_adam_step (with a target) and one actor_adam_step against the torch route the learner uses today
+    (Adam.step on the .grad tensors, then the reloads), at H = 256 and 512, alternating windows in one process, medians; torch's
+    fused=True Adam as a second line; and SACLearner.update at batch 256 with three options and with four."""
+    import torch
+
+    from ur_gym_amd import make_vec
+    from ur_gym_amd.evaluation import DeviceActor, DeviceCritic, DeviceReplay
+    from ur_gym_amd.training import SACLearner, TorchActor, TorchTwinCritic, host_arrays
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_policy_rollout.py measures on a GPU; none is visible")
+    dev, n = "cuda:0", min(args.num_envs, 4096)  # the step calls do not depend on the number of envs
+    env = make_vec(args.env, num_envs=n, device=dev, seed=0, auto_reset=True)
+    env.reset(seed=0)
+    n_in = env.obs_dim + 2 * env.goal_dim
+    sync = lambda: torch.cuda.synchronize(env.device)  # noqa: E731
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def window(fn, count):
+        sync()
+        e0.record()
+        for _ in range(count):
+            fn()
+        e1.record()
+        sync()
+        return e0.elapsed_time(e1) * 1e3 / count
+
+    def measure(kinds):
+        for fn in kinds.values():
+            for _ in range(5):
+                fn()
+        windows = {k: [] for k in kinds}
+        for _ in range(args.windows):
+            for name, fn in kinds.items():
+                windows[name].append(window(fn, args.launches))
+        med = {k: float(np.median(v)) for k, v in windows.items()}
+        spread = float(max(windows["torch"]) - min(windows["torch"]))
+        return {"us_median": med, "us_windows": {k: [round(v, 3) for v in vs] for k, vs in windows.items()}, "torch_us_spread": spread,
+                "not_slower_than_torch": med["device"] <= med["torch"] + spread, "speedup_over_torch": med["torch"] / med["device"],
+                "speedup_over_torch_fused": med["torch_fused"] / med["device"]}
+
+    widths = {}
+    for H in (256, 512):
+        torch.manual_seed(H)
+        res = {}
+        # each route steps parameters of its own, so that none sees another's moments; the gradients are shared and only read
+        critics = [TorchTwinCritic(n_in + 6, H).to(dev) for _ in range(3)]
+        grads = [{k: torch.randn_like(p) * 1e-3 for k, p in w.items()} for w in critics[0].tensors()]
+        for c in critics[1:]:
+            for w, g in zip(c.tensors(), grads):
+                for k, p in w.items():
+                    p.grad = g[k]
+        online, target = DeviceCritic(host_arrays(critics[0].tensors()), env), DeviceCritic(host_arrays(critics[0].tensors()), env)
+        online_t, target_t = DeviceCritic(host_arrays(critics[0].tensors()), env), DeviceCritic(host_arrays(critics[0].tensors()), env)
+        m = [{k: torch.zeros_like(p) for k, p in w.items()} for w in critics[0].tensors()]
+        v = [{k: torch.zeros_like(p) for k, p in w.items()} for w in critics[0].tensors()]
+        opt = torch.optim.Adam(critics[1].parameters(), lr=1e-4)
+        opt_fused = torch.optim.Adam(critics[2].parameters(), lr=1e-4, fused=True)
+        step = [0]
+
+        def device_critic():
+            step[0] += 1
+            env.critic_adam_step(online, critics[0].tensors(), grads, m, v, lr=1e-4, step=step[0], target=target, tau=0.005)
+
+        def torch_critic(o=opt, c=critics[1]):
+            o.step()
+            online_t.load_parameters(c.tensors(), tau=1.0)
+            target_t.load_parameters(c.tensors(), tau=0.005)
+
+        res["critic"] = measure({"device": device_critic, "torch": torch_critic, "torch_fused": lambda: torch_critic(opt_fused, critics[2])})
+        for c in (online, target, online_t, target_t):
+            c.close()
+
+        actors = [TorchActor(n_in, H).to(dev) for _ in range(3)]
+        agrads = {k: torch.randn_like(p) * 1e-3 for k, p in actors[0].tensors().items()}
+        for a in actors[1:]:
+            for k, p in a.tensors().items():
+                p.grad = agrads[k]
+        da, da_t = DeviceActor(host_arrays(actors[0].tensors()), env), DeviceActor(host_arrays(actors[0].tensors()), env)
+        am, av = ({k: torch.zeros_like(p) for k, p in actors[0].tensors().items()} for _ in range(2))
+        aopt = torch.optim.Adam(actors[1].parameters(), lr=1e-4)
+        aopt_fused = torch.optim.Adam(actors[2].parameters(), lr=1e-4, fused=True)
+        astep = [0]
+
+        def device_actor():
+            astep[0] += 1
+            env.actor_adam_step(da, actors[0].tensors(), agrads, am, av, lr=1e-4, step=astep[0])
+
+        def torch_actor(o=aopt, a=actors[1]):
+            o.step()
+            da_t.load_parameters(a.tensors())
+
+        res["actor"] = measure({"device": device_actor, "torch": torch_actor, "torch_fused": lambda: torch_actor(aopt_fused, actors[2])})
+        da.close()
+        da_t.close()
+        widths[str(H)] = res
+
+    three = dict(device_action_gradient=True, device_critic_gradient=True, device_actor_gradient=True)
+    learners = {}
+    for label, options in (("three_options", three), ("four_options", dict(three, device_optimizer=True))):
+        learner = SACLearner(env, seed=0, batch_size=256, hidden_width=256, **options)
+        replay = DeviceReplay(env, 4)
+        learner.collect(replay, 4)
+        learners[label] = (learner, replay, [0])
+
+    def one_update(label):
+        learner, replay, draw = learners[label]
+        draw[0] += 1
+        learner.update(replay, 1, draw[0])
+
+    for label in learners:
+        for _ in range(5):
+            one_update(label)
+    wdw = {label: [] for label in learners}
+    for _ in range(args.windows):
+        for label in learners:
+            wdw[label].append(window(lambda: one_update(label), 20))
+    updates = {label: {"us_median": float(np.median(v)), "us_windows": [round(x, 2) for x in v]} for label, v in wdw.items()}
+    for learner, _, _ in learners.values():
+        learner.close()
+    result = {"tool": "bench_policy_rollout --optimizer", "env": args.env, "windows": args.windows, "launches_per_window": args.launches,
+              "device": torch.cuda.get_device_name(0), "hidden_width": widths,
+              "not_slower_than_torch": all(r["not_slower_than_torch"] for w in widths.values() for r in w.values()),
+              "learner_update_batch256": updates}
+    env.close()
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--env", default="UR5DynReach-v1", choices=sorted(ACTOR_NPZ))
@@ -742,8 +883,11 @@ def main():
     ap.add_argument("--action-gradient", action="store_true", help="measure the critics' action gradient launch against critic_kernel and torch autograd (see above)")
     ap.add_argument("--critic-gradient", action="store_true", help="measure the critics' parameter gradients (two or three launches) against torch autograd (see above)")
     ap.add_argument("--actor-gradient", action="store_true", help="measure the actor's parameter gradients (two or three launches) against torch autograd (see above)")
+    ap.add_argument("--optimizer", action="store_true", help="measure the Adam step kernels (one launch each) against torch's Adam.step followed by the reloads, and the learner's update with and without them")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.optimizer:
+        return optimizer_mode(args)
     if args.actor_gradient:
         return actor_gradient_mode(args)
     if args.action_gradient:

@@ -36,6 +36,10 @@ def main():
     ap.add_argument("--device-actor-gradient", action="store_true",
                     help="take the actor loss's parameter gradients from the HIP kernels instead of torch autograd: with the two options "
                          "above, which it needs, no forward or backward pass of an update runs in torch (hidden width <= 256)")
+    ap.add_argument("--device-optimizer", action="store_true",
+                    help="step the actor's and the critics' parameters with the HIP Adam kernels, which also reload the device networks and "
+                         "blend the target: one launch each instead of torch's optimisers and three reloads (needs --device-critic-gradient "
+                         "and --device-actor-gradient)")
     args = ap.parse_args()
 
     import torch
@@ -51,7 +55,7 @@ def main():
     test_env = make_vec(args.env, num_envs=args.eval_envs, seed=args.seed + 1, auto_reset=False)
     learner = SACLearner(env, seed=args.seed, hidden_width=args.hidden_width, batch_size=args.batch_size,
                          device_action_gradient=args.device_action_gradient, device_critic_gradient=args.device_critic_gradient,
-                         device_actor_gradient=args.device_actor_gradient)
+                         device_actor_gradient=args.device_actor_gradient, device_optimizer=args.device_optimizer)
     eval_actor = DeviceActor(host_arrays(learner.actor.tensors()), test_env)  # actors belong to the environment they were made for
     replay = DeviceReplay(env, args.capacity)
     updates, t0 = 0, time.perf_counter()

@@ -268,6 +268,30 @@ class CriticParamsDev(C.Structure):
     _fields_ = [("in_features", C.c_int32), ("hidden_width", C.c_int32), ("reserved0", C.c_int32), ("qf", QNetworkDev * 2)]
 
 
+class AdamHyper(C.Structure):
+    """urgym_adam_hyper: Adam's hyperparameters and the 1-based index of this step (the caller counts; the library keeps no state)."""
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("step", C.c_int64), ("reserved0", C.c_int32)]
+
+
+ADAM_COEFFICIENTS = ("b1", "omb1", "b2", "omb2", "step_size", "bc2_sqrt", "eps")  # the float[7] of urgym_adam_coefficients, in order
+ADAM_SETS = ("param", "grad", "exp_avg", "exp_avg_sq")  # the four tensor sets of urgym_actor_adam / urgym_critic_adam, in order
+
+
+class ActorTensors(C.Structure):
+    """urgym_actor_tensors / urgym_actor_tensors_const: eight DEVICE pointers named like urgym_actor_params_dev's."""
+    _fields_ = [(name, C.POINTER(C.c_float)) for name in ACTOR_DEV_ARRAYS]
+
+
+class ActorAdam(C.Structure):
+    """urgym_actor_adam: the shape for checking + 4 x 8 DEVICE pointers, all required."""
+    _fields_ = [("in_features", C.c_int32), ("hidden_width", C.c_int32), ("reserved0", C.c_int32)] + [(name, ActorTensors) for name in ADAM_SETS]
+
+
+class CriticAdam(C.Structure):
+    """urgym_critic_adam: the shape for checking + 4 x 2 x 6 DEVICE pointers, all required."""
+    _fields_ = [("in_features", C.c_int32), ("hidden_width", C.c_int32), ("reserved0", C.c_int32)] + [(name, QNetworkDev * 2) for name in ADAM_SETS]
+
+
 # Every symbol include/urgym.h declares (tests check that the built library exports each of them).
 EXPORTED_SYMBOLS = [
     "urgym_abi_version",
@@ -299,6 +323,9 @@ EXPORTED_SYMBOLS = [
     "urgym_replay_sample",
     "urgym_actor_load",
     "urgym_critic_load",
+    "urgym_adam_coefficients",
+    "urgym_actor_adam_step",
+    "urgym_critic_adam_step",
     "urgym_actor_read_packed",
     "urgym_critic_read_packed",
     "urgym_refresh",

@@ -1,0 +1,75 @@
+// urgym_adam.h — the Adam step that also repacks: the per-element arithmetic and the coefficients, stated once
+// as functions the kernels of urgym_adam.hip, the entry points of urgym_policy_abi.hip and tests/adam_harness.cpp (a host program,
+// built without HIP) all compile; and, for HIP units only, the seam between urgym_adam.hip and urgym_policy_abi.hip.  Nothing here is
+// exported.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+
+#include "urgym_pack_map.h"
+
+namespace urgym {
+
+// include/urgym.h, urgym_adam_coefficients: seven float32 numbers, each computed in double and rounded once
+struct AdamCoef {
+  float b1, omb1, b2, omb2, step_size, bc2_sqrt, eps;
+};
+
+inline AdamCoef adam_coefficients(double lr, double beta1, double beta2, double eps, int64_t step) {
+  const double corr1 = 1.0 - pow(beta1, (double)step), corr2 = 1.0 - pow(beta2, (double)step);
+  AdamCoef c;
+  c.b1 = (float)beta1, c.omb1 = (float)(1.0 - beta1);
+  c.b2 = (float)beta2, c.omb2 = (float)(1.0 - beta2);
+  c.step_size = (float)(lr / corr1), c.bc2_sqrt = (float)sqrt(corr2), c.eps = (float)eps;
+  return c;
+}
+
+// One element.  Every line is ONE float32 operation rounded on its own: the units that compile this are built with -ffp-contract=off
+// (no fused multiply-add), sqrt and / are IEEE (correctly rounded), subnormals are kept.  ur_gym_amd.evaluation.adam_step restates it.
+URGYM_HD inline void adam_element(const AdamCoef& c, float g, float& p, float& m, float& v) {
+  const float m_old = c.b1 * m;
+  const float m_new = c.omb1 * g;
+  m = m_old + m_new;
+  const float gg = g * g;
+  const float v_old = c.b2 * v;
+  const float v_new = c.omb2 * gg;
+  v = v_old + v_new;
+  const float s = sqrtf(v);
+  const float r = s / c.bc2_sqrt;
+  const float d = r + c.eps;
+  const float u = m / d;
+  const float w = c.step_size * u;
+  p = p - w;
+}
+
+}  // namespace urgym
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+
+#include "urgym_actor.h"
+#include "urgym_critic.h"
+
+namespace urgym {
+
+// the four tensor sets of a step, each in the order of urgym_pack_map.h (PACK_*; the critic: 6 net + PACK_*): DEVICE pointers,
+// float32, torch's [out][in] layout, 4-byte aligned, none overlapping another
+template <int N>
+struct AdamTensors {
+  float* param[N];
+  const float* grad[N];
+  float* exp_avg[N];
+  float* exp_avg_sq[N];
+};
+
+// Steps all eight tensors of the actor in place and writes every float of its packed buffer (the log_std head included, padding as
+// +0.0f) from the stepped parameters, in ONE launch on `s`.  The caller has validated everything.
+void actor_adam_launch(const ActorPacked& a, const AdamTensors<PACK_ACTOR_TENSORS>& t, const AdamCoef& c, hipStream_t s);
+
+// The same for the twelve tensors of both Q-networks and `online`'s packed buffer; with target != nullptr its packed buffer is blended
+// as critic_pack_launch blends: tau == 1 replaces (the old value is not read), otherwise (packed * (1.0f - tau)) + (tau * p').
+void critic_adam_launch(const CriticPacked& online, const CriticPacked* target, const AdamTensors<2 * PACK_CRITIC_TENSORS>& t, const AdamCoef& c,
+                        float tau, hipStream_t s);
+
+}  // namespace urgym
+#endif

@@ -1,6 +1,6 @@
 // urgym_policy_abi.hip — the learner's half of the C-ABI of include/urgym.h: actors (create / forward / sample / rollouts), the replay
-// ring, the weight reloads, the twin critic and its two gradients, the actor's parameter gradients.  Host code only: every check is made here, before the first launch,
-// and every launch goes through urgym_actor.h, urgym_critic.h, urgym_replay.h and urgym_weights.h, or through do_step of urgym_hip.hip
+// ring, the weight reloads, the twin critic and its two gradients, the actor's parameter gradients, the Adam steps.  Host code only: every check is made here, before the first launch,
+// and every launch goes through urgym_actor.h, urgym_critic.h, urgym_replay.h, urgym_weights.h and urgym_adam.h, or through do_step of urgym_hip.hip
 // (urgym_handle.h).  No kernel lives in this unit, so adding a check here leaves the step kernels' object file alone.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -16,6 +16,7 @@
 #include "urgym_pack_map.h"
 #include "urgym_weights.h"
 #include "urgym_replay.h"
+#include "urgym_adam.h"
 
 using namespace urgym;
 
@@ -267,9 +268,104 @@ int read_packed(Handle* h, const char* who, const float* dev, size_t floats, flo
   return URGYM_OK;
 }
 
+// ---- Adam (urgym_adam.h): what urgym_adam_coefficients and both step calls refuse about the hyperparameters; null = accepted
+const char* adam_hyper_refusal(const urgym_adam_hyper* hp) {
+  if (!hp) return "null hyperparameters";
+  if (hp->reserved0 != 0) return "urgym_adam_hyper.reserved0 must be 0";
+  if (!(hp->lr >= 0.0 && hp->lr < (double)INFINITY)) return "lr must be finite and not negative";  // refuses NaN too
+  if (!(hp->beta1 >= 0.0 && hp->beta1 < 1.0) || !(hp->beta2 >= 0.0 && hp->beta2 < 1.0)) return "beta1 and beta2 must be in [0, 1)";
+  if (!(hp->eps > 0.0 && hp->eps < (double)INFINITY)) return "eps must be finite and positive";
+  if (hp->step < 1) return "step is the 1-based index of this step: it must be at least 1";
+  return nullptr;
+}
+
+AdamCoef adam_coef(const urgym_adam_hyper& hp) { return adam_coefficients(hp.lr, hp.beta1, hp.beta2, hp.eps, hp.step); }
+
 }  // namespace
 
 extern "C" {
+
+// ---- Adam on the device (urgym_adam.hip): everything is checked here, before the launch
+int urgym_adam_coefficients(const urgym_adam_hyper* hp, float out[7]) {
+  if (const char* what = adam_hyper_refusal(hp)) return fail_in(nullptr, URGYM_ERR_ARG, "urgym_adam_coefficients", what);
+  if (!out) return fail(nullptr, URGYM_ERR_ARG, "urgym_adam_coefficients: null out");
+  const AdamCoef c = adam_coef(*hp);
+  out[0] = c.b1, out[1] = c.omb1, out[2] = c.b2, out[3] = c.omb2, out[4] = c.step_size, out[5] = c.bc2_sqrt, out[6] = c.eps;
+  return URGYM_OK;
+}
+
+int urgym_actor_adam_step(void* handle, void* actor, const urgym_actor_adam* t, const urgym_adam_hyper* hp, void* stream) {
+  const char* who = "urgym_actor_adam_step";
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  Actor* a = member(h->actors, actor);
+  if (!a) return fail_in(h, URGYM_ERR_ARG, who, "not an actor of this handle (actors belong to the handle they were created with)");
+  if (!t) return fail_in(h, URGYM_ERR_ARG, who, "null tensors");
+  if (t->reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "urgym_actor_adam.reserved0 must be 0");
+  const ActorPacked buf = actor_packed(a);
+  if (t->in_features != buf.in_features || t->hidden_width != buf.hidden)
+    return failf(h, URGYM_ERR_ARG, "%s: tensors are %d -> %d, the actor is %d -> %d", who, t->in_features, t->hidden_width, buf.in_features, buf.hidden);
+  AdamTensors<PACK_ACTOR_TENSORS> T;
+  {
+    const urgym_actor_tensors &p = t->param, &m = t->exp_avg, &v = t->exp_avg_sq;
+    const urgym_actor_tensors_const& g = t->grad;
+    float* const ps[PACK_ACTOR_TENSORS] = {p.w0, p.b0, p.w1, p.b1, p.w_mu, p.b_mu, p.w_log_std, p.b_log_std};
+    const float* const gs[PACK_ACTOR_TENSORS] = {g.w0, g.b0, g.w1, g.b1, g.w_mu, g.b_mu, g.w_log_std, g.b_log_std};
+    float* const ms[PACK_ACTOR_TENSORS] = {m.w0, m.b0, m.w1, m.b1, m.w_mu, m.b_mu, m.w_log_std, m.b_log_std};
+    float* const vs[PACK_ACTOR_TENSORS] = {v.w0, v.b0, v.w1, v.b1, v.w_mu, v.b_mu, v.w_log_std, v.b_log_std};
+    for (int i = 0; i < PACK_ACTOR_TENSORS; i++) {
+      if (!ps[i] || !gs[i] || !ms[i] || !vs[i]) return fail_in(h, URGYM_ERR_ARG, who, "a tensor pointer is null (all 32 are required)");
+      T.param[i] = ps[i], T.grad[i] = gs[i], T.exp_avg[i] = ms[i], T.exp_avg_sq[i] = vs[i];
+    }
+  }
+  if (const char* what = adam_hyper_refusal(hp)) return fail_in(h, URGYM_ERR_ARG, who, what);
+  HIP_TRY(h, hipSetDevice(h->device));
+  actor_adam_launch(buf, T, adam_coef(*hp), (hipStream_t)stream);
+  HIP_TRY(h, hipGetLastError());
+  actor_mark_log_std(a);  // as urgym_actor_load with both head pointers
+  return URGYM_OK;
+}
+
+int urgym_critic_adam_step(void* handle, void* online, void* target_or_NULL, const urgym_critic_adam* t, const urgym_adam_hyper* hp, float tau, void* stream) {
+  const char* who = "urgym_critic_adam_step";
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  Critic* c = member(h->critics, online);
+  if (!c) return fail_in(h, URGYM_ERR_ARG, who, "not a critic of this handle (critics belong to the handle they were created with)");
+  const CriticPacked buf = critic_packed(c);
+  CriticPacked target_buf;
+  if (target_or_NULL) {
+    if (target_or_NULL == online) return fail_in(h, URGYM_ERR_ARG, who, "the target is the online critic itself");
+    Critic* tc = member(h->critics, target_or_NULL);
+    if (!tc) return fail_in(h, URGYM_ERR_ARG, who, "the target is not a critic of this handle");
+    target_buf = critic_packed(tc);
+    if (target_buf.in_features != buf.in_features || target_buf.hidden != buf.hidden || target_buf.floats != buf.floats)
+      return failf(h, URGYM_ERR_ARG, "%s: the target is %d -> %d, the online critic is %d -> %d", who, target_buf.in_features, target_buf.hidden, buf.in_features, buf.hidden);
+    if (!(tau > 0.0f && tau <= 1.0f)) return fail_in(h, URGYM_ERR_ARG, who, "tau must be in (0, 1]");  // refuses NaN too
+  }
+  if (!t) return fail_in(h, URGYM_ERR_ARG, who, "null tensors");
+  if (t->reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "urgym_critic_adam.reserved0 must be 0");
+  if (t->in_features != buf.in_features || t->hidden_width != buf.hidden)
+    return failf(h, URGYM_ERR_ARG, "%s: tensors are %d -> %d, the critic is %d -> %d", who, t->in_features, t->hidden_width, buf.in_features, buf.hidden);
+  AdamTensors<2 * PACK_CRITIC_TENSORS> T;
+  for (int net = 0; net < 2; net++) {
+    const urgym_q_network_grad &p = t->param[net], &m = t->exp_avg[net], &v = t->exp_avg_sq[net];
+    const urgym_q_network_dev& g = t->grad[net];
+    float* const ps[PACK_CRITIC_TENSORS] = {p.w0, p.b0, p.w1, p.b1, p.w_q, p.b_q};
+    const float* const gs[PACK_CRITIC_TENSORS] = {g.w0, g.b0, g.w1, g.b1, g.w_q, g.b_q};
+    float* const ms[PACK_CRITIC_TENSORS] = {m.w0, m.b0, m.w1, m.b1, m.w_q, m.b_q};
+    float* const vs[PACK_CRITIC_TENSORS] = {v.w0, v.b0, v.w1, v.b1, v.w_q, v.b_q};
+    for (int i = 0; i < PACK_CRITIC_TENSORS; i++) {
+      if (!ps[i] || !gs[i] || !ms[i] || !vs[i]) return fail_in(h, URGYM_ERR_ARG, who, "a tensor pointer is null (all 48 are required)");
+      const int k = PACK_CRITIC_TENSORS * net + i;
+      T.param[k] = ps[i], T.grad[k] = gs[i], T.exp_avg[k] = ms[i], T.exp_avg_sq[k] = vs[i];
+    }
+  }
+  if (const char* what = adam_hyper_refusal(hp)) return fail_in(h, URGYM_ERR_ARG, who, what);
+  HIP_TRY(h, hipSetDevice(h->device));
+  critic_adam_launch(buf, target_or_NULL ? &target_buf : nullptr, T, adam_coef(*hp), tau, (hipStream_t)stream);
+  return launched(h);
+}
 
 // ---- weights from the device (urgym_weights.hip): everything is checked here, before the launch
 int urgym_actor_load(void* handle, void* actor, const urgym_actor_params_dev* p, void* stream) {

@@ -112,6 +112,60 @@ def polyak(old, src, tau):
     return ((old * omt).astype(f) + (tau * src).astype(f)).astype(f)
 
 
+def adam_coefficients(env, lr, betas=(0.9, 0.999), eps=1e-8, step=1):
+    """The seven float32 coefficients of one Adam step as the LIBRARY forms them (urgym_adam_coefficients: host only, no launch), a
+    float32 array in the order of ``_abi.ADAM_COEFFICIENTS``: b1, omb1, b2, omb2, step_size = lr / (1 - beta1^step), bc2_sqrt =
+    sqrt(1 - beta2^step), eps.  The step kernels use these very numbers, so ``adam_step`` with them is bitwise the device's step
+    whatever ``pow`` the host has.  `env`: an environment (its library is used) or None (the library is loaded); `step` is 1-based.
+    Raises ``NativeError`` for what the library refuses (lr, betas, eps, step out of range)."""
+    import ctypes as C
+
+    from . import _abi, _native
+
+    lib = env.lib if env is not None else _native.lib()
+    hp = _abi.AdamHyper(float(lr), float(betas[0]), float(betas[1]), float(eps), int(step), 0)
+    out = (C.c_float * 7)()
+    _native.check(lib.urgym_adam_coefficients(C.byref(hp), out), None)
+    return np.array(out[:], dtype=np.float32)
+
+
+def adam_step(p, g, m, v, coef):
+    """The per-element arithmetic of urgym_actor_adam_step / urgym_critic_adam_step, restated from include/urgym.h in numpy float32:
+    returns (p', m', v').  `coef`: the seven numbers of ``adam_coefficients``.  Every line is one operation rounded to float32 on its
+    own (numpy's float32 sqrt and division are the correctly rounded ones, and subnormals are kept)::
+
+        m' = (b1 * m) + (omb1 * g)
+        gg = g * g          v' = (b2 * v) + (omb2 * gg)
+        s  = sqrt(v')       d  = (s / bc2_sqrt) + eps
+        u  = m' / d         p' = p - (step_size * u)
+    """
+    f = np.float32
+    coef = np.asarray(coef)
+    if coef.dtype != f or coef.shape != (7,):
+        raise ValueError(f"coef must be the float32 [7] of adam_coefficients, got {coef.dtype} {coef.shape}")
+    b1, omb1, b2, omb2, step_size, bc2_sqrt, eps = coef
+    p, g, m, v = (np.asarray(x, dtype=f) for x in (p, g, m, v))
+    if not (p.shape == g.shape == m.shape == v.shape):
+        raise ValueError(f"p, g, m, v must have one shape, got {p.shape}, {g.shape}, {m.shape}, {v.shape}")
+    with np.errstate(all="ignore"):  # underflow of g * g, overflow and NaN are inputs the step is defined on
+        m_old = b1 * m
+        m_in = omb1 * g
+        m_new = m_old + m_in
+        gg = g * g
+        v_old = b2 * v
+        v_in = omb2 * gg
+        v_new = v_old + v_in
+        s = np.sqrt(v_new)
+        r = s / bc2_sqrt
+        d = r + eps
+        u = m_new / d
+        w = step_size * u
+        p_new = p - w
+    for x in (m_old, m_in, m_new, gg, v_old, v_in, v_new, s, r, d, u, w, p_new):
+        assert x.dtype == f, x.dtype  # no intermediate was promoted
+    return p_new, m_new, v_new
+
+
 def _check_device_tensors(tensors, wanted, device, who):
     """`wanted`: name -> shape.  Raises ValueError unless every one is a contiguous float32 torch tensor of that shape on `device`."""
     import torch

@@ -23,6 +23,14 @@ minibatch gather on the HIP kernels, and gradients and optimisers in torch autog
     the SAMPLE form, d_action = -g / M and d_log_prob = ent_coef / M, writes d loss / d parameters into preallocated tensors that ARE
     the actor parameters' ``.grad``.  No ``torch.Generator`` is drawn from, and nothing of ``update`` goes through torch autograd but
     the entropy coefficient's scalar loss.
+    With ``device_optimizer=True`` (it needs ``device_critic_gradient=True`` and ``device_actor_gradient=True``, so that every
+    ``.grad`` is a tensor the kernels wrote) the two Adam steps and the three reloads are two launches: ``critic_opt.step()``,
+    ``online.load_parameters`` and the final ``target.load_parameters`` become one ``env.critic_adam_step(target=self.target, tau=)``,
+    ``actor_opt.step()`` and ``device_actor.load_parameters`` one ``env.actor_adam_step``.  ``exp_avg`` and ``exp_avg_sq`` are zero
+    tensors of the learner's, a Python int counts the steps, and the torch optimisers of the actor and the critic are not stepped (the
+    entropy coefficient's stays in torch).  The Polyak blend of the target thereby moves from the end of ``update`` to the critic's
+    step; in stream order that is equivalent, because nothing between the two places reads the target: it is read only by the NEXT
+    update's ``sample_targets``.
     None of them synchronises with the host.  There is no logging, no callback and no checkpoint format here; tools/train_sac.py runs it.
 """
 import numpy as np
@@ -34,7 +42,7 @@ from .evaluation import ACTOR_ARRAYS, CRITIC_ARRAYS, LOG_STD_ARRAYS, LOG_STD_MAX
 # SB3's SAC defaults where train.py does not set them (tests/golden/critics/sac_hyperparameters.json has the checkpoints' gamma, tau)
 SAC_DEFAULTS = dict(gamma=0.95, tau=0.005, learning_rate=1e-4, batch_size=256, learning_starts=100, hidden_width=256, target_entropy=-6.0,
                     ent_coef_init=1.0, device_action_gradient=False, device_critic_gradient=False,
-                    device_actor_gradient=False)
+                    device_actor_gradient=False, device_optimizer=False)
 
 
 def _mlp(n_in, hidden, n_out=None):
@@ -139,6 +147,15 @@ class SACLearner:
             self.actor_workspace = env.actor_gradient_workspace(self.device_actor, M)
             self.actor_d_action = torch.zeros((M, 6), dtype=torch.float32, device=dev)
             self.actor_d_log_prob = torch.zeros((M,), dtype=torch.float32, device=dev)
+        # with device_optimizer Adam's moments are tensors of the learner's too, and the step kernels take the place of the torch optimisers
+        self.adam_state = None
+        if hp["device_optimizer"]:
+            if not (hp["device_critic_gradient"] and hp["device_actor_gradient"]):
+                raise ValueError("device_optimizer needs device_critic_gradient=True and device_actor_gradient=True (the step kernels read the .grad tensors the gradient kernels write)")
+            zeros = lambda w: {k: torch.zeros_like(p) for k, p in w.items()}  # noqa: E731
+            self.adam_state = dict(step=0, betas=(0.9, 0.999), eps=1e-8,  # torch.optim.Adam's defaults, as the optimisers above
+                                   actor=(zeros(self.actor.tensors()), zeros(self.actor.tensors())),
+                                   critic=([zeros(w) for w in self.critic.tensors()], [zeros(w) for w in self.critic.tensors()]))
         self.env_steps = 0  # per env; decides between the warm-up and the policy
         self.draw = 0       # draw index of the next collection pass
 
@@ -188,8 +205,14 @@ class SACLearner:
             got = self.env.critic_parameter_gradients(self.online, batch["actions"], target=y, scale=1.0 / x.shape[0], rows=batch["observations"],
                                                       out=self.critic_grads, workspace=self.critic_workspace)
             critic_loss = 0.5 * (((got["q"][0] - y) ** 2).mean() + ((got["q"][1] - y) ** 2).mean())
-            self.critic_opt.step()  # on the .grad tensors the launches wrote
-            self.online.load_parameters(self.critic.tensors(), tau=1.0)
+            if self.adam_state is None:
+                self.critic_opt.step()  # on the .grad tensors the launches wrote
+                self.online.load_parameters(self.critic.tensors(), tau=1.0)
+            else:  # the step, the reload of the online critic and the target's Polyak update (read next by the next update) in one launch
+                st = self.adam_state
+                st["step"] += 1
+                self.env.critic_adam_step(self.online, self.critic.tensors(), self.critic_grads, *st["critic"], lr=hp["learning_rate"],
+                                          betas=st["betas"], eps=st["eps"], step=st["step"], target=self.target, tau=hp["tau"])
 
         if self.actor_grads is not None:
             M = x.shape[0]
@@ -201,6 +224,11 @@ class SACLearner:
             self.env.actor_parameter_gradients(self.device_actor, sample=how, rows=batch["observations"], d_action=self.actor_d_action,
                                                d_log_prob=self.actor_d_log_prob, out=self.actor_grads, workspace=self.actor_workspace)
             actor_loss = (ent_coef * log_prob - grad["q_min"]).mean()
+            if self.adam_state is not None:
+                st = self.adam_state
+                self.env.actor_adam_step(self.device_actor, self.actor.tensors(), self.actor_grads, *st["actor"], lr=hp["learning_rate"],
+                                         betas=st["betas"], eps=st["eps"], step=st["step"])
+                return {"critic_loss": critic_loss.detach(), "actor_loss": actor_loss.detach(), "ent_coef_loss": ent_loss.detach()}
             self.actor_opt.step()  # on the .grad tensors the launches wrote
             self.device_actor.load_parameters(self.actor.tensors())
             self.target.load_parameters(self.critic.tensors(), tau=hp["tau"])

@@ -424,6 +424,66 @@ class UR5ReachVectorEnv:
                                                                C.c_void_p(workspace.data_ptr()), workspace.numel() * 4, self._stream()), self._h)
         return res
 
+    @staticmethod
+    def _adam_hyper(lr, betas, eps, step):
+        betas = tuple(betas)
+        if len(betas) != 2:
+            raise ValueError(f"betas must be a pair, got {betas}")
+        return _abi.AdamHyper(float(lr), float(betas[0]), float(betas[1]), float(eps), int(step), 0)
+
+    def actor_adam_step(self, actor, params, grads, exp_avg, exp_avg_sq, *, lr, betas=(0.9, 0.999), eps=1e-8, step):
+        """One Adam step of `actor`'s parameters on the device, and the reload, in ONE launch (urgym_actor_adam_step): `params`,
+        `exp_avg` and `exp_avg_sq` are updated in place from `grads`, and the DeviceActor's packed buffer is rewritten from the stepped
+        parameters, the log_std head included -- ``torch.optim.Adam.step()`` followed by ``actor.load_parameters(params)``.  The four
+        are dicts under ACTOR_ARRAYS + LOG_STD_ARRAYS (all eight tensors) as ``DeviceActor.check_parameters`` takes them; no two of
+        the 32 tensors may overlap (not checked).  `step` is the 1-based index of this step: the caller counts, the library keeps no
+        optimiser state.  The arithmetic is ``evaluation.adam_step`` with ``evaluation.adam_coefficients``, bitwise.  On torch's
+        current stream, nothing is synchronised; stream order as for ``DeviceActor.load_parameters``."""
+        from .evaluation import ACTOR_ARRAYS, LOG_STD_ARRAYS, DeviceActor
+
+        a = self._actor_ptr(actor)
+        keys = ACTOR_ARRAYS + LOG_STD_ARRAYS
+        t = _abi.ActorAdam(actor.in_features, actor.hidden_width, 0)
+        for name, tensors in zip(_abi.ADAM_SETS, (params, grads, exp_avg, exp_avg_sq)):
+            tensors = dict(tensors)
+            if not DeviceActor.check_parameters(tensors, actor.in_features, actor.hidden_width, self.device):
+                raise ValueError(f"actor_adam_step: {name} needs the log_std head too ({LOG_STD_ARRAYS})")
+            setattr(t, name, _abi.ActorTensors(*[C.cast(tensors[k].data_ptr(), C.POINTER(C.c_float)) for k in keys]))
+        hp = self._adam_hyper(lr, betas, eps, step)
+        _native.check(self.lib.urgym_actor_adam_step(self._h, a, C.byref(t), C.byref(hp), self._stream()), self._h)
+        actor.has_log_std = True
+
+    def critic_adam_step(self, online, params, grads, exp_avg, exp_avg_sq, *, lr, betas=(0.9, 0.999), eps=1e-8, step, target=None, tau=None):
+        """One Adam step of both Q-networks on the device, the reload of `online` and, with `target`, its Polyak update, in ONE launch
+        (urgym_critic_adam_step): ``torch.optim.Adam.step()`` followed by ``online.load_parameters(params, tau=1)`` and
+        ``target.load_parameters(params, tau)``.  The four are lists of two dicts under CRITIC_ARRAYS as
+        ``DeviceCritic.check_parameters`` takes them; no two of the 48 tensors may overlap (not checked).  `target`: another
+        DeviceCritic of this environment with `online`'s shape, blended as ``evaluation.polyak`` states with `tau` in (0, 1].
+        `step`, the arithmetic, the stream and the ordering as in ``actor_adam_step``."""
+        from .evaluation import CRITIC_ARRAYS, DeviceCritic
+
+        for who, c in (("online", online), ("target", target)):
+            if c is None and who == "target":
+                continue
+            if getattr(c, "env", None) is not self or not getattr(c, "_c", None):
+                raise ValueError(f"{who} must be a live DeviceCritic loaded for this environment (DeviceCritic.load(paths, env))")
+        if target is not None:
+            if tau is None:
+                raise ValueError("a target needs tau (tests/golden/critics/sac_hyperparameters.json has the checkpoints': 0.005)")
+            tau = float(tau)
+            if not (np.isfinite(tau) and 0.0 < tau <= 1.0):
+                raise ValueError(f"tau must be in (0, 1], got {tau}")
+        t = _abi.CriticAdam(online.in_features, online.hidden_width, 0)
+        for name, tensors in zip(_abi.ADAM_SETS, (params, grads, exp_avg, exp_avg_sq)):
+            tensors = [dict(w) for w in tensors]
+            DeviceCritic.check_parameters(tensors, online.in_features, online.hidden_width, self.device)
+            nets = getattr(t, name)
+            for i, w in enumerate(tensors):
+                nets[i] = _abi.QNetworkDev(*[C.cast(w[k].data_ptr(), C.POINTER(C.c_float)) for k in CRITIC_ARRAYS])
+        hp = self._adam_hyper(lr, betas, eps, step)
+        _native.check(self.lib.urgym_critic_adam_step(self._h, online._c, target._c if target is not None else None, C.byref(t), C.byref(hp),
+                                                      float(tau) if target is not None else 1.0, self._stream()), self._h)
+
     def policy_actions(self, actor, out=None, sample=None, rows=None):
         """model.predict(obs, deterministic=True) (model_test.py:41) for all envs, by the HIP actor kernel, from the live
         observation buffers: float32 [N, 6] on the device.
