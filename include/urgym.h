@@ -788,6 +788,100 @@ int urgym_actor_adam_step(void* handle, void* actor, const urgym_actor_adam* t, 
  * online's; with a target, tau outside (0, 1] or not finite. */
 int urgym_critic_adam_step(void* handle, void* online, void* target_or_NULL, const urgym_critic_adam* t, const urgym_adam_hyper* hp, float tau, void* stream);
 
+/* ---- SAC's entropy coefficient on the device (SB3's ent_coef = "auto": log_ent_coef is a learned scalar, stepped by its own Adam,
+ * and alpha = exp(log_ent_coef) of the value BEFORE the step is the coefficient of the whole update).  Two calls carry everything of a
+ * SAC update that is neither a network pass nor a network's Adam step: alpha, the entropy term of the target, the temperature's loss
+ * and step, the upstream gradients of urgym_actor_parameter_gradients, and the three loss values.  Added WITHIN ABI version 4: no
+ * struct above changed, URGYM_ABI_VERSION did not move, the new symbols (urgym_sac_entropy_step, urgym_sac_policy_terms) are found by
+ * lookup.  The library keeps NO state: the caller owns log_ent_coef and its two moments and counts the steps.
+ *
+ * Each call is ONE launch of ONE workgroup of 1024 lanes on `stream`: no allocation, no host synchronisation, everything validated
+ * before the launch.  Every lane reads the scalar state before anything is written; lane t handles rows t, t + 1024, ..., reading a
+ * row before it writes it.  count is at most URGYM_SAC_TERMS_MAX_COUNT (64 rows per lane).
+ *
+ * THE ORDERED SUM of `count` float32 terms, used by every reduction here, is carried in float64:
+ *   lane t (0 <= t < 1024) starts at +0.0 and adds terms t, t + 1024, t + 2048, ... in ascending order;
+ *   the 1024 partials are folded with partial[t] += partial[t + s] for s = 512, 256, ..., 1 (t < s);
+ *   the result is S = partial[0].  A mean is (float)(S / (double)count), rounded once.
+ * The order depends on nothing but count: two calls on the same inputs give the same bits.  There are no floating-point atomics.
+ *
+ * Everything else is float32 and every line below is ONE operation rounded on its own (no fused multiply-add; subnormals kept).
+ * ur_gym_amd.evaluation.ordered_sum / entropy_step / policy_terms restate all of it. */
+#define URGYM_SAC_TERMS_MAX_COUNT 65536
+
+/* All pointers are DEVICE pointers, 4-byte aligned where float.  The state (log_ent_coef, exp_avg, exp_avg_sq) is stepped in place.
+ * Two optional groups, each given whole or not at all:
+ *   the TARGET group    target_in, next_log_prob, y_out (all three non-NULL), gamma, and terminated or NULL (= no row is terminal);
+ *                       y_out == target_in is allowed
+ *   the UPSTREAM group  d_log_prob_out (non-NULL) and scale */
+typedef struct urgym_sac_entropy_args {
+  int32_t count;         /* rows, in [1, URGYM_SAC_TERMS_MAX_COUNT] */
+  int32_t reserved0;     /* must be 0 */
+  float target_entropy;  /* finite */
+  float gamma;           /* target group; finite */
+  float scale;           /* upstream group; finite */
+  const float* log_prob; /* [count], the policy's log-probability on the batch rows */
+  float* log_ent_coef;   /* [1], read and written: l -> l' */
+  float* exp_avg;        /* [1], read and written: m -> m' */
+  float* exp_avg_sq;     /* [1], read and written: v -> v' */
+  float* ent_coef_out;   /* [1], written: alpha */
+  float* loss_out;       /* [1], written; or NULL */
+  const float* target_in;      /* [count] */
+  const float* next_log_prob;  /* [count] */
+  const uint8_t* terminated;   /* [count], or NULL */
+  float* y_out;                /* [count] */
+  float* d_log_prob_out;       /* [count] */
+} urgym_sac_entropy_args;
+
+/* SB3's ent_coef_optimizer step plus every per-row use of alpha that is ready at that point of the update:
+ *   l      = log_ent_coef[0]                      read before anything is written
+ *   alpha  = expf(l)                              the device's expf (1 ulp); ent_coef_out[0] = alpha
+ *   nd     = terminated && terminated[m] ? 0 : 1
+ *   d      = gamma * nd      t = d * alpha      e = t * next_log_prob[m]      y_out[m] = target_in[m] - e
+ *   d_log_prob_out[m] = alpha * scale
+ *   s[m]   = log_prob[m] + target_entropy
+ *   mean   = ordered mean of s                    float64 sum, rounded once
+ *   g      = -mean                                d loss / d l
+ *   loss   = -(l * mean)                          loss_out[0]
+ *   (l', m', v') = the Adam element of the section above on (g, l, m, v) with urgym_adam_coefficients(hp)
+ * alpha is the coefficient of the OLD l.  A NaN in one next_log_prob row reaches that row of y_out only; a NaN in log_prob reaches
+ * l', m', v' and the loss, and no per-row output.  What the outputs held before the call does not matter.
+ *
+ * Refused (URGYM_ERR_ARG, nothing is launched, nothing is written): NULL handle or args; NULL log_prob, log_ent_coef, exp_avg,
+ * exp_avg_sq or ent_coef_out; count outside [1, URGYM_SAC_TERMS_MAX_COUNT]; reserved0 != 0; target_entropy not finite; a half-given
+ * target group (some but not all of target_in, next_log_prob, y_out; or terminated without them); gamma or scale not finite (also
+ * where its group is absent: leave it 0); and what urgym_actor_adam_step refuses about hp. */
+int urgym_sac_entropy_step(void* handle, const urgym_sac_entropy_args* args, const urgym_adam_hyper* hp, void* stream);
+
+/* Three optional groups, each given whole (all three pointers) or not at all, at least one given:
+ *   UPSTREAM     dqmin_da, d_action_out, scale     d_action_out may be dqmin_da itself
+ *   CRITIC LOSS  q, y, critic_loss_out
+ *   ACTOR LOSS   log_prob, q_min, actor_loss_out */
+typedef struct urgym_sac_policy_args {
+  int32_t count;     /* rows, in [1, URGYM_SAC_TERMS_MAX_COUNT] */
+  int32_t reserved0; /* must be 0 */
+  float scale;       /* upstream group; finite (a learner passes -1 / count) */
+  const float* ent_coef;   /* [1], required: what urgym_sac_entropy_step wrote to ent_coef_out */
+  const float* dqmin_da;   /* [count][6] */
+  float* d_action_out;     /* [count][6] */
+  const float* q;          /* [2][count] */
+  const float* y;          /* [count] */
+  float* critic_loss_out;  /* [1] */
+  const float* log_prob;   /* [count] */
+  const float* q_min;      /* [count] */
+  float* actor_loss_out;   /* [1] */
+} urgym_sac_policy_args;
+
+/* What can only be formed after the critic's step and the action gradient:
+ *   d_action_out[m][k] = dqmin_da[m][k] * scale
+ *   e = q[i][m] - y[m]      sq = e * e      mean_i = ordered mean of sq      critic_loss_out[0] = 0.5f * (mean_0 + mean_1)
+ *   alpha = ent_coef[0]     a = alpha * log_prob[m]      b = a - q_min[m]    actor_loss_out[0] = ordered mean of b
+ *
+ * Refused (URGYM_ERR_ARG, nothing is launched, nothing is written): NULL handle, args or ent_coef; count outside
+ * [1, URGYM_SAC_TERMS_MAX_COUNT]; reserved0 != 0; a half-given group; no group at all; scale not finite (also where the upstream
+ * group is absent: leave it 0). */
+int urgym_sac_policy_terms(void* handle, const urgym_sac_policy_args* args, void* stream);
+
 /* Verification aid, not a hot path: synchronises the device, then copies the object's packed buffer (the kernel's own layout,
  * ur_gym_amd/csrc/urgym_pack_map.h) to host_out and stores its length in floats in *count.  host_out == NULL only reports *count;
  * otherwise capacity (in floats) must be at least that.  Refused: NULL handle / object / count, an object of another handle,

@@ -57,6 +57,12 @@ device_actor.load_parameters; torch's fused=True Adam in both comparisons as a s
 its own.  Alternating windows in one process, medians.  Bar: each call is not slower than the torch route beyond the spread of torch's
 windows.  Then one SACLearner.update at batch 256 with the three gradient options and with device_optimizer as well, alternating.
     python tools/bench_policy_rollout.py --optimizer --windows 6 --launches 100 --out profiles/policy_rollout/dyn65536_optimizer.json
+--entropy measures one SACLearner.update at batch 256, H = 256 (and 512, which the gradient kernels the
+options need refuse: recorded as refused), two ways: device_optimizer with the
+three gradient options (the route before device_entropy) and the same plus device_entropy.  Alternating windows of --launches updates in one
+process, each ending in a device synchronise; wall time per update, medians.  Bar: the new route is not slower than the old beyond the
+spread of the old route's windows.  The ratio is reported whatever it is.
+    python tools/bench_policy_rollout.py --entropy --windows 8 --launches 200 --out profiles/policy_rollout/dyn65536_entropy.json
 
 With --refresh: what it costs to hand new weights to a device actor / critic, at hidden width 256 and 512.
 `actor_load`, `critic_load_tau1` and `critic_load_polyak` (tau = 0.005) are load_parameters from device tensors, one launch each;
@@ -860,6 +866,77 @@ def optimizer_mode(args):
             f.write(line + "\n")
 
 
+def entropy_mode(args):
+    """--entropy: SACLearner.update at batch 256 with device_optimizer only against the same plus device_entropy, at H = 256 and 512,
+    alternating windows in one process, medians of wall time per update (each window ends in a synchronise)."""
+    import torch
+
+    from ur_gym_amd import make_vec
+    from ur_gym_amd._native import NativeError
+    from ur_gym_amd.evaluation import DeviceReplay
+    from ur_gym_amd.training import SACLearner
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_policy_rollout.py measures on a GPU; none is visible")
+    dev, n, per_window = "cuda:0", min(args.num_envs, 4096), args.launches  # an update does not depend on the number of envs
+    env = make_vec(args.env, num_envs=n, device=dev, seed=0, auto_reset=True)
+    env.reset(seed=0)
+    sync = lambda: torch.cuda.synchronize(env.device)  # noqa: E731
+    four = dict(device_action_gradient=True, device_critic_gradient=True, device_actor_gradient=True, device_optimizer=True)
+    widths = {}
+    for H in (256, 512):
+        learners = {}
+        try:
+            for label, options in (("device_optimizer", four), ("device_entropy", dict(four, device_entropy=True))):
+                learner = SACLearner(env, seed=0, batch_size=256, hidden_width=H, **options)
+                replay = DeviceReplay(env, 4)
+                learners[label] = (learner, replay, [0])
+                learner.collect(replay, 4)
+        except NativeError as e:  # the gradient kernels the options need are built for hidden widths up to 256
+            for learner, _, _ in learners.values():
+                learner.close()
+            widths[str(H)] = {"refused": str(e)}
+            continue
+
+        def one_update(label):
+            learner, replay, draw = learners[label]
+            draw[0] += 1
+            learner.update(replay, 1, draw[0])
+
+        def window(label):
+            sync()
+            t0 = time.perf_counter()
+            for _ in range(per_window):
+                one_update(label)
+            sync()
+            return (time.perf_counter() - t0) * 1e6 / per_window
+
+        for label in learners:
+            for _ in range(10):
+                one_update(label)
+        wdw = {label: [] for label in learners}
+        for _ in range(args.windows):
+            for label in learners:
+                wdw[label].append(window(label))
+        med = {k: float(np.median(v)) for k, v in wdw.items()}
+        spread = float(max(wdw["device_optimizer"]) - min(wdw["device_optimizer"]))
+        widths[str(H)] = {"us_median": med, "us_windows": {k: [round(x, 2) for x in v] for k, v in wdw.items()},
+                          "device_optimizer_us_spread": spread, "ratio_entropy_over_optimizer": med["device_entropy"] / med["device_optimizer"],
+                          "not_slower": med["device_entropy"] <= med["device_optimizer"] + spread}
+        for learner, _, _ in learners.values():
+            learner.close()
+    result = {"tool": "bench_policy_rollout --entropy", "env": args.env, "windows": args.windows, "updates_per_window": per_window,
+              "batch": 256, "device": torch.cuda.get_device_name(0), "hidden_width": widths,
+              "not_slower": all(w.get("not_slower", True) for w in widths.values())}
+    env.close()
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--env", default="UR5DynReach-v1", choices=sorted(ACTOR_NPZ))
@@ -884,8 +961,11 @@ def main():
     ap.add_argument("--critic-gradient", action="store_true", help="measure the critics' parameter gradients (two or three launches) against torch autograd (see above)")
     ap.add_argument("--actor-gradient", action="store_true", help="measure the actor's parameter gradients (two or three launches) against torch autograd (see above)")
     ap.add_argument("--optimizer", action="store_true", help="measure the Adam step kernels (one launch each) against torch's Adam.step followed by the reloads, and the learner's update with and without them")
+    ap.add_argument("--entropy", action="store_true", help="measure the learner's update with device_optimizer only against the same plus device_entropy (see above)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.entropy:
+        return entropy_mode(args)
     if args.optimizer:
         return optimizer_mode(args)
     if args.actor_gradient:

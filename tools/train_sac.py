@@ -40,6 +40,9 @@ def main():
                     help="step the actor's and the critics' parameters with the HIP Adam kernels, which also reload the device networks and "
                          "blend the target: one launch each instead of torch's optimisers and three reloads (needs --device-critic-gradient "
                          "and --device-actor-gradient)")
+    ap.add_argument("--device-entropy", action="store_true",
+                    help="step the entropy coefficient and form its uses and the three loss values with two HIP launches: no torch operation "
+                         "is left in an update but allocations and views (needs --device-optimizer)")
     args = ap.parse_args()
 
     import torch
@@ -55,7 +58,8 @@ def main():
     test_env = make_vec(args.env, num_envs=args.eval_envs, seed=args.seed + 1, auto_reset=False)
     learner = SACLearner(env, seed=args.seed, hidden_width=args.hidden_width, batch_size=args.batch_size,
                          device_action_gradient=args.device_action_gradient, device_critic_gradient=args.device_critic_gradient,
-                         device_actor_gradient=args.device_actor_gradient, device_optimizer=args.device_optimizer)
+                         device_actor_gradient=args.device_actor_gradient, device_optimizer=args.device_optimizer,
+                         device_entropy=args.device_entropy)
     eval_actor = DeviceActor(host_arrays(learner.actor.tensors()), test_env)  # actors belong to the environment they were made for
     replay = DeviceReplay(env, args.capacity)
     updates, t0 = 0, time.perf_counter()

@@ -292,6 +292,27 @@ class CriticAdam(C.Structure):
     _fields_ = [("in_features", C.c_int32), ("hidden_width", C.c_int32), ("reserved0", C.c_int32)] + [(name, QNetworkDev * 2) for name in ADAM_SETS]
 
 
+SAC_TERMS_MAX_COUNT = 65536  # URGYM_SAC_TERMS_MAX_COUNT: the row cap of urgym_sac_entropy_step / urgym_sac_policy_terms
+SAC_TERMS_LANES = 1024       # the lanes of their one workgroup: the stride of the ordered sum
+
+
+class SacEntropyArgs(C.Structure):
+    """urgym_sac_entropy_args: the rows, the state (stepped in place), alpha and the loss, the optional target and upstream groups."""
+    _fields_ = [("count", C.c_int32), ("reserved0", C.c_int32), ("target_entropy", C.c_float), ("gamma", C.c_float), ("scale", C.c_float),
+                ("log_prob", C.POINTER(C.c_float)), ("log_ent_coef", C.POINTER(C.c_float)), ("exp_avg", C.POINTER(C.c_float)),
+                ("exp_avg_sq", C.POINTER(C.c_float)), ("ent_coef_out", C.POINTER(C.c_float)), ("loss_out", C.POINTER(C.c_float)),
+                ("target_in", C.POINTER(C.c_float)), ("next_log_prob", C.POINTER(C.c_float)), ("terminated", C.POINTER(C.c_uint8)),
+                ("y_out", C.POINTER(C.c_float)), ("d_log_prob_out", C.POINTER(C.c_float))]
+
+
+class SacPolicyArgs(C.Structure):
+    """urgym_sac_policy_args: alpha and the three optional groups (upstream, critic loss, actor loss)."""
+    _fields_ = [("count", C.c_int32), ("reserved0", C.c_int32), ("scale", C.c_float), ("ent_coef", C.POINTER(C.c_float)),
+                ("dqmin_da", C.POINTER(C.c_float)), ("d_action_out", C.POINTER(C.c_float)),
+                ("q", C.POINTER(C.c_float)), ("y", C.POINTER(C.c_float)), ("critic_loss_out", C.POINTER(C.c_float)),
+                ("log_prob", C.POINTER(C.c_float)), ("q_min", C.POINTER(C.c_float)), ("actor_loss_out", C.POINTER(C.c_float))]
+
+
 # Every symbol include/urgym.h declares (tests check that the built library exports each of them).
 EXPORTED_SYMBOLS = [
     "urgym_abi_version",
@@ -326,6 +347,8 @@ EXPORTED_SYMBOLS = [
     "urgym_adam_coefficients",
     "urgym_actor_adam_step",
     "urgym_critic_adam_step",
+    "urgym_sac_entropy_step",
+    "urgym_sac_policy_terms",
     "urgym_actor_read_packed",
     "urgym_critic_read_packed",
     "urgym_refresh",

@@ -1,6 +1,6 @@
 // urgym_policy_abi.hip — the learner's half of the C-ABI of include/urgym.h: actors (create / forward / sample / rollouts), the replay
-// ring, the weight reloads, the twin critic and its two gradients, the actor's parameter gradients, the Adam steps.  Host code only: every check is made here, before the first launch,
-// and every launch goes through urgym_actor.h, urgym_critic.h, urgym_replay.h, urgym_weights.h and urgym_adam.h, or through do_step of urgym_hip.hip
+// ring, the weight reloads, the twin critic and its two gradients, the actor's parameter gradients, the Adam steps, SAC's entropy step and loss terms.  Host code only: every check is made here, before the first launch,
+// and every launch goes through urgym_actor.h, urgym_critic.h, urgym_replay.h, urgym_weights.h, urgym_adam.h and urgym_sac_terms.h, or through do_step of urgym_hip.hip
 // (urgym_handle.h).  No kernel lives in this unit, so adding a check here leaves the step kernels' object file alone.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -17,6 +17,7 @@
 #include "urgym_weights.h"
 #include "urgym_replay.h"
 #include "urgym_adam.h"
+#include "urgym_sac_terms.h"
 
 using namespace urgym;
 
@@ -364,6 +365,64 @@ int urgym_critic_adam_step(void* handle, void* online, void* target_or_NULL, con
   if (const char* what = adam_hyper_refusal(hp)) return fail_in(h, URGYM_ERR_ARG, who, what);
   HIP_TRY(h, hipSetDevice(h->device));
   critic_adam_launch(buf, target_or_NULL ? &target_buf : nullptr, T, adam_coef(*hp), tau, (hipStream_t)stream);
+  return launched(h);
+}
+
+// ---- SAC's entropy coefficient on the device (urgym_sac_terms.hip): everything is checked here, before the launch
+int urgym_sac_entropy_step(void* handle, const urgym_sac_entropy_args* args, const urgym_adam_hyper* hp, void* stream) {
+  static_assert(URGYM_SAC_TERMS_MAX_COUNT == SAC_TERMS_MAX_COUNT, "include/urgym.h");
+  const char* who = "urgym_sac_entropy_step";
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (!args) return fail_in(h, URGYM_ERR_ARG, who, "null args");
+  const urgym_sac_entropy_args& a = *args;
+  if (a.reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_entropy_args.reserved0 must be 0");
+  if (a.count < 1 || a.count > SAC_TERMS_MAX_COUNT) return fail_in(h, URGYM_ERR_ARG, who, "count must be in [1, URGYM_SAC_TERMS_MAX_COUNT] (65536)");
+  if (!a.log_prob || !a.log_ent_coef || !a.exp_avg || !a.exp_avg_sq || !a.ent_coef_out)
+    return fail_in(h, URGYM_ERR_ARG, who, "a required pointer is null (log_prob, log_ent_coef, exp_avg, exp_avg_sq, ent_coef_out)");
+  if (!(fabsf(a.target_entropy) < INFINITY)) return fail_in(h, URGYM_ERR_ARG, who, "target_entropy must be finite");  // refuses NaN too
+  if (!(fabsf(a.gamma) < INFINITY)) return fail_in(h, URGYM_ERR_ARG, who, "gamma must be finite");
+  if (!(fabsf(a.scale) < INFINITY)) return fail_in(h, URGYM_ERR_ARG, who, "scale must be finite");
+  const int given = (a.target_in != nullptr) + (a.next_log_prob != nullptr) + (a.y_out != nullptr);
+  if ((given != 0 && given != 3) || (given == 0 && a.terminated))
+    return fail_in(h, URGYM_ERR_ARG, who, "the target group is half given: target_in, next_log_prob and y_out go together (terminated only with them)");
+  if (const char* what = adam_hyper_refusal(hp)) return fail_in(h, URGYM_ERR_ARG, who, what);
+  SacEntropyCall c;
+  c.count = a.count, c.target_entropy = a.target_entropy, c.gamma = a.gamma, c.scale = a.scale;
+  c.log_prob = a.log_prob, c.log_ent_coef = a.log_ent_coef, c.exp_avg = a.exp_avg, c.exp_avg_sq = a.exp_avg_sq;
+  c.ent_coef_out = a.ent_coef_out, c.loss_out = a.loss_out;
+  c.target_in = a.target_in, c.next_log_prob = a.next_log_prob, c.terminated = a.terminated, c.y_out = a.y_out;
+  c.d_log_prob_out = a.d_log_prob_out;
+  c.c = adam_coef(*hp);
+  HIP_TRY(h, hipSetDevice(h->device));
+  sac_entropy_launch(c, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_sac_policy_terms(void* handle, const urgym_sac_policy_args* args, void* stream) {
+  const char* who = "urgym_sac_policy_terms";
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (!args) return fail_in(h, URGYM_ERR_ARG, who, "null args");
+  const urgym_sac_policy_args& a = *args;
+  if (a.reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_policy_args.reserved0 must be 0");
+  if (a.count < 1 || a.count > SAC_TERMS_MAX_COUNT) return fail_in(h, URGYM_ERR_ARG, who, "count must be in [1, URGYM_SAC_TERMS_MAX_COUNT] (65536)");
+  if (!a.ent_coef) return fail_in(h, URGYM_ERR_ARG, who, "null ent_coef");
+  if (!(fabsf(a.scale) < INFINITY)) return fail_in(h, URGYM_ERR_ARG, who, "scale must be finite");  // refuses NaN too
+  const int upstream = (a.dqmin_da != nullptr) + (a.d_action_out != nullptr);
+  const int critic = (a.q != nullptr) + (a.y != nullptr) + (a.critic_loss_out != nullptr);
+  const int actor = (a.log_prob != nullptr) + (a.q_min != nullptr) + (a.actor_loss_out != nullptr);
+  if (upstream == 1) return fail_in(h, URGYM_ERR_ARG, who, "the upstream group is half given: dqmin_da and d_action_out go together");
+  if (critic != 0 && critic != 3) return fail_in(h, URGYM_ERR_ARG, who, "the critic-loss group is half given: q, y and critic_loss_out go together");
+  if (actor != 0 && actor != 3) return fail_in(h, URGYM_ERR_ARG, who, "the actor-loss group is half given: log_prob, q_min and actor_loss_out go together");
+  if (!upstream && !critic && !actor) return fail_in(h, URGYM_ERR_ARG, who, "no group is given (upstream, critic loss, actor loss)");
+  SacPolicyCall c;
+  c.count = a.count, c.scale = a.scale, c.ent_coef = a.ent_coef;
+  c.dqmin_da = a.dqmin_da, c.d_action_out = a.d_action_out;
+  c.q = a.q, c.y = a.y, c.critic_loss_out = a.critic_loss_out;
+  c.log_prob = a.log_prob, c.q_min = a.q_min, c.actor_loss_out = a.actor_loss_out;
+  HIP_TRY(h, hipSetDevice(h->device));
+  sac_policy_launch(c, (hipStream_t)stream);
   return launched(h);
 }
 

@@ -166,6 +166,125 @@ def adam_step(p, g, m, v, coef):
     return p_new, m_new, v_new
 
 
+def ordered_sum(terms):
+    """THE ORDERED SUM of include/urgym.h ("SAC's entropy coefficient on the device") in numpy: `terms` is a float32 [count] array;
+    lane t of 1024 starts at +0.0 and adds terms t, t + 1024, ... in ascending order in float64, then the partials are folded with
+    ``partial[t] += partial[t + s]`` for s = 512, ..., 1.  Returns the float64 sum; the order depends on nothing but count."""
+    from ._abi import SAC_TERMS_LANES as L
+
+    terms = np.asarray(terms)
+    if terms.dtype != np.float32 or terms.ndim != 1:
+        raise ValueError(f"terms must be a float32 [count] array, got {terms.dtype} {terms.shape}")
+    partial = np.zeros(L, np.float64)
+    with np.errstate(all="ignore"):
+        for first in range(0, terms.size, L):  # every lane's next term, ascending
+            row = terms[first:first + L]
+            partial[:row.size] += row.astype(np.float64)
+        s = L // 2
+        while s >= 1:
+            partial[:s] += partial[s:2 * s]
+            s //= 2
+    return np.float64(partial[0])
+
+
+def _ordered_mean(terms):
+    assert terms.dtype == np.float32, terms.dtype
+    with np.errstate(all="ignore"):
+        return np.float32(ordered_sum(terms) / np.float64(terms.size))  # rounded once
+
+
+def _rows32(name, x, shape):
+    x = np.asarray(x)
+    if x.dtype != np.float32 or x.shape != shape:
+        raise ValueError(f"{name} must be a float32 array of shape {shape}, got {x.dtype} {x.shape}")
+    return x
+
+
+def entropy_step(alpha, log_prob, target_entropy, l, m, v, coef, *, target=None, next_log_prob=None, terminated=None, gamma=None, scale=None):
+    """urgym_sac_entropy_step restated from include/urgym.h in numpy: float32 with one operation per line, the mean by
+    ``ordered_sum``, the step by ``adam_step`` with `coef` = ``adam_coefficients(...)``.  `alpha` is an INPUT -- the float32 the launch
+    wrote to ``ent_coef_out`` -- because the device's expf and numpy's exp are different functions.  `l`, `m`, `v`: the state before
+    the step (float32, one element each).  Returns a dict: ``l``, ``m``, ``v`` (float32 [1] each, after the step), ``loss``, ``mean``
+    (float32), and ``y`` [count] where the target group (`target`, `next_log_prob`, `gamma`; `terminated` or None) is given,
+    ``d_log_prob`` [count] where `scale` is."""
+    f = np.float32
+    alpha, te = f(alpha), f(target_entropy)
+    log_prob = np.asarray(log_prob)
+    if log_prob.dtype != f or log_prob.ndim != 1 or not 1 <= log_prob.size:
+        raise ValueError(f"log_prob must be a float32 [count] array, got {log_prob.dtype} {log_prob.shape}")
+    count = log_prob.size
+    l, m, v = (np.asarray(x, dtype=f).reshape(1) for x in (l, m, v))
+    group = [x is not None for x in (target, next_log_prob, gamma)]
+    if any(group) != all(group) or (terminated is not None and not all(group)):
+        raise ValueError("the target group is half given: target, next_log_prob and gamma go together (terminated only with them)")
+    out, checked = {}, []
+    with np.errstate(all="ignore"):  # NaN and overflow are inputs the step is defined on
+        if all(group):
+            target, next_log_prob = _rows32("target", target, (count,)), _rows32("next_log_prob", next_log_prob, (count,))
+            nd = np.ones(count, f) if terminated is None else np.where(np.asarray(terminated).reshape(count).astype(bool), f(0), f(1))
+            d = f(gamma) * nd
+            t = d * alpha
+            e = t * next_log_prob
+            out["y"] = target - e
+            checked += [nd, d, t, e, out["y"]]
+        if scale is not None:
+            up = alpha * f(scale)
+            out["d_log_prob"] = np.full(count, up, f)
+            checked += [up, out["d_log_prob"]]
+        s = log_prob + te
+        mean = _ordered_mean(s)
+        g = -mean
+        lm = l * mean
+        loss = -lm
+        checked += [s, mean, g, lm, loss]
+    for x in checked:
+        assert x.dtype == f, x.dtype  # no intermediate was promoted
+    out["l"], out["m"], out["v"] = adam_step(l, np.full(1, g, f), m, v, coef)
+    out["loss"], out["mean"] = loss[0], mean
+    return out
+
+
+def policy_terms(alpha, *, dqmin_da=None, scale=None, q=None, y=None, log_prob=None, q_min=None):
+    """urgym_sac_policy_terms restated from include/urgym.h in numpy float32, the means by ``ordered_sum``; `alpha` as in
+    ``entropy_step``.  Groups, each whole or absent: (`dqmin_da` [count, 6], `scale`) gives ``d_action``; (`q` [2, count], `y`
+    [count]) gives ``critic_loss`` and ``critic_terms`` [2, count]; (`log_prob`, `q_min` [count] each) gives ``actor_loss`` and
+    ``actor_terms`` [count].  Returns a dict."""
+    f = np.float32
+    alpha = f(alpha)
+    if (dqmin_da is None) != (scale is None) or (q is None) != (y is None) or (log_prob is None) != (q_min is None):
+        raise ValueError("a group is half given: (dqmin_da, scale), (q, y), (log_prob, q_min)")
+    if dqmin_da is None and q is None and log_prob is None:
+        raise ValueError("no group is given")
+    out, checked = {}, []
+    with np.errstate(all="ignore"):
+        if dqmin_da is not None:
+            dqmin_da = np.asarray(dqmin_da)
+            dqmin_da = _rows32("dqmin_da", dqmin_da, (dqmin_da.shape[0], 6))
+            out["d_action"] = dqmin_da * f(scale)
+            checked.append(out["d_action"])
+        if q is not None:
+            y = np.asarray(y)
+            y = _rows32("y", y, (y.size,))
+            q = _rows32("q", q, (2, y.size))
+            e = q - y[None, :]
+            sq = e * e
+            mean0, mean1 = _ordered_mean(sq[0]), _ordered_mean(sq[1])
+            both = mean0 + mean1
+            out["critic_loss"], out["critic_terms"] = f(0.5) * both, sq
+            checked += [e, sq, mean0, mean1, both, out["critic_loss"]]
+        if log_prob is not None:
+            log_prob = np.asarray(log_prob)
+            log_prob = _rows32("log_prob", log_prob, (log_prob.size,))
+            q_min = _rows32("q_min", q_min, log_prob.shape)
+            a = alpha * log_prob
+            b = a - q_min
+            out["actor_loss"], out["actor_terms"] = _ordered_mean(b), b
+            checked += [a, b, out["actor_loss"]]
+    for x in checked:
+        assert x.dtype == f, x.dtype  # no intermediate was promoted
+    return out
+
+
 def _check_device_tensors(tensors, wanted, device, who):
     """`wanted`: name -> shape.  Raises ValueError unless every one is a contiguous float32 torch tensor of that shape on `device`."""
     import torch

@@ -1,6 +1,6 @@
 """A small SAC learner on the device pieces: the call pattern of the reference's ``train.py:40-60`` (stable-baselines3
 ``SAC("MultiInputPolicy", env, gamma=0.95, batch_size=256).learn``) with collection, a' ~ pi(.|s'), the bootstrapped target and the
-minibatch gather on the HIP kernels, and gradients and optimisers in torch autograd.
+minibatch gather on the HIP kernels, and gradients and optimisers in torch autograd unless the options below move them to the device too.
 
     collect   replay.collect with the DeviceActor: uniform actions before ``learning_starts`` env steps, the sampled policy after.
     update    1. replay.sample_targets with the DeviceActor and the TARGET DeviceCritic: the batch, a', log pi(a'|s') and the
@@ -31,6 +31,16 @@ minibatch gather on the HIP kernels, and gradients and optimisers in torch autog
     entropy coefficient's stays in torch).  The Polyak blend of the target thereby moves from the end of ``update`` to the critic's
     step; in stream order that is equivalent, because nothing between the two places reads the target: it is read only by the NEXT
     update's ``sample_targets``.
+    With ``device_entropy=True`` (it needs ``device_optimizer=True``) no torch operation is left in ``update`` but allocations and
+    views: ``env.entropy_step`` (one launch) forms alpha = exp(log_ent_coef), y = target - gamma (1 - terminated) alpha log pi(a'|s')
+    into a preallocated tensor, d_log_prob = alpha / M, the temperature loss, and steps ``log_ent_coef`` -- the same (1,) tensor,
+    written by the kernel -- with Adam moments of the learner's; ``env.policy_terms`` (one launch, after the action gradient) forms
+    d_action = -g / M and the critic's and the actor's loss values.  ``update`` is then thirteen launches: ``sample_targets`` (3),
+    ``policy_actions``, ``entropy_step``, ``critic_parameter_gradients(target=y)`` (2), ``critic_adam_step``,
+    ``critic_action_gradient``, ``policy_terms``, ``actor_parameter_gradients`` (2), ``actor_adam_step``.  ``ent_opt`` is not stepped,
+    nothing goes through autograd, the losses are 0-dim views of preallocated tensors, and ``self.last_update`` keeps references
+    (no copies) to the ``log_prob``, ``y``, ``q``, ``q_min`` and ``dqmin_da`` the update used.  Every float of it is stated in
+    include/urgym.h.
     None of them synchronises with the host.  There is no logging, no callback and no checkpoint format here; tools/train_sac.py runs it.
 """
 import numpy as np
@@ -42,7 +52,7 @@ from .evaluation import ACTOR_ARRAYS, CRITIC_ARRAYS, LOG_STD_ARRAYS, LOG_STD_MAX
 # SB3's SAC defaults where train.py does not set them (tests/golden/critics/sac_hyperparameters.json has the checkpoints' gamma, tau)
 SAC_DEFAULTS = dict(gamma=0.95, tau=0.005, learning_rate=1e-4, batch_size=256, learning_starts=100, hidden_width=256, target_entropy=-6.0,
                     ent_coef_init=1.0, device_action_gradient=False, device_critic_gradient=False,
-                    device_actor_gradient=False, device_optimizer=False)
+                    device_actor_gradient=False, device_optimizer=False, device_entropy=False)
 
 
 def _mlp(n_in, hidden, n_out=None):
@@ -156,6 +166,17 @@ class SACLearner:
             self.adam_state = dict(step=0, betas=(0.9, 0.999), eps=1e-8,  # torch.optim.Adam's defaults, as the optimisers above
                                    actor=(zeros(self.actor.tensors()), zeros(self.actor.tensors())),
                                    critic=([zeros(w) for w in self.critic.tensors()], [zeros(w) for w in self.critic.tensors()]))
+        # with device_entropy the entropy coefficient's step, its uses and the loss values are two launches: the moments of log_ent_coef,
+        # alpha, y and the three losses are tensors of the learner's
+        self.entropy_state = self.last_update = None
+        if hp["device_entropy"]:
+            if not hp["device_optimizer"]:
+                raise ValueError("device_entropy needs device_optimizer=True (the entropy step shares its step count, and nothing else of update is left in torch)")
+            scalar = lambda: torch.zeros((1,), dtype=torch.float32, device=dev)  # noqa: E731
+            es = dict(exp_avg=scalar(), exp_avg_sq=scalar(), ent_coef=scalar(), y=torch.zeros((int(hp["batch_size"]),), dtype=torch.float32, device=dev),
+                      critic_loss=scalar(), actor_loss=scalar(), ent_coef_loss=scalar())
+            es["losses"] = {k: es[k][0] for k in ("critic_loss", "actor_loss", "ent_coef_loss")}  # 0-dim views, made once
+            self.entropy_state = es
         self.env_steps = 0  # per env; decides between the warm-up and the policy
         self.draw = 0       # draw index of the next collection pass
 
@@ -170,6 +191,8 @@ class SACLearner:
     def update(self, replay, seed, draw):
         """One gradient step on a minibatch drawn with (seed, draw), then the two reloads.  Returns the three losses as device
         tensors (not synchronised)."""
+        if self.entropy_state is not None:
+            return self._update_on_device(replay, seed, draw)
         hp = self.hp
         gamma = float(hp["gamma"])
         if self.actor_grads is not None and not 0 <= int(draw) < 2 ** 63:
@@ -250,6 +273,35 @@ class SACLearner:
         self.device_actor.load_parameters(self.actor.tensors())
         self.target.load_parameters(self.critic.tensors(), tau=hp["tau"])
         return {"critic_loss": critic_loss.detach(), "actor_loss": actor_loss.detach(), "ent_coef_loss": ent_loss.detach()}
+
+    def _update_on_device(self, replay, seed, draw):
+        """``update`` with ``device_entropy``: thirteen launches of the library's and no torch operation but allocations and views."""
+        hp, env, st, es = self.hp, self.env, self.adam_state, self.entropy_state
+        if not 0 <= int(draw) < 2 ** 63:
+            raise ValueError("with device_actor_gradient the draw must be below 2**63 (its top bit marks the policy's own draw)")
+        M, gamma = int(hp["batch_size"]), float(hp["gamma"])
+        batch = replay.sample_targets(self.device_actor, self.target, M, seed, draw, gamma, 0.0)
+        rows = batch["observations"]
+        how = dict(mode="gaussian", seed=seed, first_draw=int(draw) | 1 << 63)
+        action_pi, log_prob = env.policy_actions(self.device_actor, sample=how, rows=rows)
+        st["step"] += 1
+        adam = dict(lr=hp["learning_rate"], betas=st["betas"], eps=st["eps"], step=st["step"])
+        # alpha of the old log_ent_coef, y, d_log_prob = alpha / M, the temperature loss and its Adam step
+        env.entropy_step((self.log_ent_coef, es["exp_avg"], es["exp_avg_sq"]), log_prob, hp["target_entropy"], ent_coef_out=es["ent_coef"],
+                         loss_out=es["ent_coef_loss"], target=batch["target"], next_log_prob=batch["next_log_prob"], terminated=batch["terminated"],
+                         gamma=gamma, y_out=es["y"], d_log_prob_out=self.actor_d_log_prob, scale=1.0 / M, **adam)
+        got = env.critic_parameter_gradients(self.online, batch["actions"], target=es["y"], scale=1.0 / M, rows=rows, out=self.critic_grads,
+                                             workspace=self.critic_workspace)
+        env.critic_adam_step(self.online, self.critic.tensors(), self.critic_grads, *st["critic"], target=self.target, tau=hp["tau"], **adam)
+        grad = env.critic_action_gradient(self.online, action_pi, rows=rows)
+        # d_action = -g / M and the critic's and the actor's loss values
+        env.policy_terms(es["ent_coef"], M, dqmin_da=grad["dqmin_da"], scale=-1.0 / M, d_action_out=self.actor_d_action, q=got["q"], y=es["y"],
+                         critic_loss_out=es["critic_loss"], log_prob=log_prob, q_min=grad["q_min"], actor_loss_out=es["actor_loss"])
+        env.actor_parameter_gradients(self.device_actor, sample=how, rows=rows, d_action=self.actor_d_action, d_log_prob=self.actor_d_log_prob,
+                                      out=self.actor_grads, workspace=self.actor_workspace)
+        env.actor_adam_step(self.device_actor, self.actor.tensors(), self.actor_grads, *st["actor"], **adam)
+        self.last_update = dict(log_prob=log_prob, y=es["y"], q=got["q"], q_min=grad["q_min"], dqmin_da=grad["dqmin_da"])
+        return dict(es["losses"])
 
     def close(self):
         self.device_actor.close()

@@ -484,6 +484,104 @@ class UR5ReachVectorEnv:
         _native.check(self.lib.urgym_critic_adam_step(self._h, online._c, target._c if target is not None else None, C.byref(t), C.byref(hp),
                                                       float(tau) if target is not None else 1.0, self._stream()), self._h)
 
+    def _float_ptr(self, who, name, t, shape, dtype=torch.float32, ctype=C.c_float):
+        """The DEVICE pointer of `t` for a call that reads or writes it in place: a contiguous `dtype` tensor of `shape` on this
+        device (a bool tensor counts as uint8), or ValueError.  Nothing is converted or copied."""
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{who}: {name} must be a torch tensor on {self.device}, got {type(t).__name__}")
+        have = torch.uint8 if t.dtype == torch.bool and dtype == torch.uint8 else t.dtype
+        if have != dtype or not t.is_contiguous() or t.device != torch.device(self.device) or tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{who}: {name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on {self.device}, "
+                             f"got {t.dtype} {tuple(t.shape)} on {t.device}{'' if t.is_contiguous() else ', not contiguous'}")
+        return C.cast(t.data_ptr(), C.POINTER(ctype))
+
+    @staticmethod
+    def _finite32(x):
+        with np.errstate(over="ignore"):
+            return bool(np.isfinite(np.float32(x)))
+
+    def entropy_step(self, state, log_prob, target_entropy, *, lr, betas=(0.9, 0.999), eps=1e-8, step, ent_coef_out, loss_out=None,
+                     target=None, next_log_prob=None, terminated=None, gamma=None, y_out=None, d_log_prob_out=None, scale=None):
+        """SB3's ``ent_coef_optimizer`` step on the device plus every per-row use of alpha that is ready then, in ONE launch
+        (urgym_sac_entropy_step).  `state`: the three float32 [1] tensors (log_ent_coef, exp_avg, exp_avg_sq), as a tuple or a dict
+        under those names, stepped in place on the mean of ``log_prob + target_entropy`` over `log_prob` [count]; `step` is the 1-based
+        index of this step (the caller counts).  ``ent_coef_out`` [1] receives alpha = exp(log_ent_coef) of the value BEFORE the
+        step, ``loss_out`` [1] the temperature loss.  The target group, whole or absent: `target`, `next_log_prob`, `y_out` [count],
+        `gamma`, and `terminated` (bool or uint8 [count]) or None: ``y_out = target - ((gamma (1 - terminated)) alpha)
+        next_log_prob``; `y_out` may be `target` itself.  The upstream group: ``d_log_prob_out`` [count] = alpha * `scale`.  Every
+        tensor is checked (float32, contiguous, this device, its shape), none is converted.  The arithmetic is
+        ``evaluation.entropy_step``, bitwise.  On torch's current stream, nothing is synchronised."""
+        who = "entropy_step"
+        names = ("log_ent_coef", "exp_avg", "exp_avg_sq")
+        state = tuple(state[k] for k in names) if isinstance(state, dict) else tuple(state)
+        if len(state) != 3:
+            raise ValueError(f"{who}: state must be the three tensors {names}")
+        if not isinstance(log_prob, torch.Tensor) or log_prob.dim() != 1:
+            raise ValueError(f"{who}: log_prob must be a float32 [count] tensor")
+        count = int(log_prob.shape[0])
+        if not 1 <= count <= _abi.SAC_TERMS_MAX_COUNT:
+            raise ValueError(f"{who}: count must be in [1, {_abi.SAC_TERMS_MAX_COUNT}], got {count}")
+        group = (target is not None, next_log_prob is not None, y_out is not None, gamma is not None)
+        if any(group) != all(group) or (terminated is not None and not all(group)):
+            raise ValueError(f"{who}: the target group is half given: target, next_log_prob, y_out and gamma go together (terminated only with them)")
+        if (d_log_prob_out is None) != (scale is None):
+            raise ValueError(f"{who}: the upstream group is half given: d_log_prob_out and scale go together")
+        for name, x in (("target_entropy", target_entropy), ("gamma", gamma), ("scale", scale)):
+            if x is not None and not self._finite32(x):
+                raise ValueError(f"{who}: {name} must be finite in float32, got {x}")
+        a = _abi.SacEntropyArgs(count, 0, float(target_entropy), float(gamma or 0.0), float(scale or 0.0))
+        a.log_prob = self._float_ptr(who, "log_prob", log_prob, (count,))
+        for name, t in zip(names, state):
+            setattr(a, name, self._float_ptr(who, name, t, (1,)))
+        a.ent_coef_out = self._float_ptr(who, "ent_coef_out", ent_coef_out, (1,))
+        if loss_out is not None:
+            a.loss_out = self._float_ptr(who, "loss_out", loss_out, (1,))
+        if all(group):
+            a.target_in = self._float_ptr(who, "target", target, (count,))
+            a.next_log_prob = self._float_ptr(who, "next_log_prob", next_log_prob, (count,))
+            a.y_out = self._float_ptr(who, "y_out", y_out, (count,))
+            if terminated is not None:
+                a.terminated = self._float_ptr(who, "terminated", terminated, (count,), torch.uint8, C.c_uint8)
+        if d_log_prob_out is not None:
+            a.d_log_prob_out = self._float_ptr(who, "d_log_prob_out", d_log_prob_out, (count,))
+        hp = self._adam_hyper(lr, betas, eps, step)
+        _native.check(self.lib.urgym_sac_entropy_step(self._h, C.byref(a), C.byref(hp), self._stream()), self._h)
+
+    def policy_terms(self, ent_coef, count, *, dqmin_da=None, scale=None, d_action_out=None, q=None, y=None, critic_loss_out=None,
+                     log_prob=None, q_min=None, actor_loss_out=None):
+        """What a SAC update forms after the critic's step and the action gradient, in ONE launch (urgym_sac_policy_terms).
+        `ent_coef` [1]: what ``entropy_step`` wrote to ``ent_coef_out``.  Three groups, each whole or absent, at least one:
+        (`dqmin_da`, `d_action_out` [count, 6], `scale`) writes ``d_action_out = dqmin_da * scale``; (`q` [2, count], `y` [count],
+        `critic_loss_out` [1]) the critic loss ``0.5 (mean (q0 - y)^2 + mean (q1 - y)^2)``; (`log_prob`, `q_min` [count],
+        `actor_loss_out` [1]) the actor loss ``mean(ent_coef log_prob - q_min)``.  Tensors are checked as in ``entropy_step``; the
+        arithmetic is ``evaluation.policy_terms``, bitwise.  On torch's current stream, nothing is synchronised."""
+        who = "policy_terms"
+        count = int(count)
+        if not 1 <= count <= _abi.SAC_TERMS_MAX_COUNT:
+            raise ValueError(f"{who}: count must be in [1, {_abi.SAC_TERMS_MAX_COUNT}], got {count}")
+        groups = {"upstream": (dqmin_da, d_action_out, scale), "critic loss": (q, y, critic_loss_out), "actor loss": (log_prob, q_min, actor_loss_out)}
+        for name, g in groups.items():
+            if any(x is not None for x in g) != all(x is not None for x in g):
+                raise ValueError(f"{who}: the {name} group is half given")
+        if all(g[0] is None for g in groups.values()):
+            raise ValueError(f"{who}: no group is given (upstream, critic loss, actor loss)")
+        if scale is not None and not self._finite32(scale):
+            raise ValueError(f"{who}: scale must be finite in float32, got {scale}")
+        a = _abi.SacPolicyArgs(count, 0, float(scale or 0.0))
+        a.ent_coef = self._float_ptr(who, "ent_coef", ent_coef, (1,))
+        if dqmin_da is not None:
+            a.dqmin_da = self._float_ptr(who, "dqmin_da", dqmin_da, (count, 6))
+            a.d_action_out = self._float_ptr(who, "d_action_out", d_action_out, (count, 6))
+        if q is not None:
+            a.q = self._float_ptr(who, "q", q, (2, count))
+            a.y = self._float_ptr(who, "y", y, (count,))
+            a.critic_loss_out = self._float_ptr(who, "critic_loss_out", critic_loss_out, (1,))
+        if log_prob is not None:
+            a.log_prob = self._float_ptr(who, "log_prob", log_prob, (count,))
+            a.q_min = self._float_ptr(who, "q_min", q_min, (count,))
+            a.actor_loss_out = self._float_ptr(who, "actor_loss_out", actor_loss_out, (1,))
+        _native.check(self.lib.urgym_sac_policy_terms(self._h, C.byref(a), self._stream()), self._h)
+
     def policy_actions(self, actor, out=None, sample=None, rows=None):
         """model.predict(obs, deterministic=True) (model_test.py:41) for all envs, by the HIP actor kernel, from the live
         observation buffers: float32 [N, 6] on the device.
