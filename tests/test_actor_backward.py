@@ -22,7 +22,7 @@ Where the checks come from (no number is taken from what the kernels give):
     bitwise ``sample_head_gradients`` on the call's own records (its ``std`` record among them: exp(log_std) is the device's expf); the HEADS form on those reproduces the eight tensors bitwise.
   * the learner: the device route's actor gradients may deviate from float64 autograd by 4 x the torch float32 route's deviation on
     the same noise plus one float32 ulp of the tensor's largest gradient.
-  * tests/actor_backward_harness.cpp enumerates the kernels' index arithmetic on the host under the address and undefined-behaviour
+  * tests/backward_harness.cpp enumerates the kernels' index arithmetic on the host under the address and undefined-behaviour
     sanitizers: bounds, the bijection between stage 1's writes and stage 2's reads, every output element written once.
 """
 import ctypes as C
@@ -47,7 +47,7 @@ KEYS = ACTOR_ARRAYS + LOG_STD_ARRAYS
 UP_UNIT = 2.0 ** -4
 GPU_WIDTHS = (32, 128, 160, 256)
 REFUSED_WIDTHS = (288, 512)
-SPLIT = 1024  # rows per split of stage 2 (urgym_actor_backward_map.h: AB_SPLIT_ROWS)
+SPLIT = 1024  # rows per split of stage 2 (urgym_backward_map.h: BW_SPLIT_ROWS)
 # one lane, a second wave, a full workgroup, a second workgroup with one row, ragged; stage 2's split boundary and its neighbours
 GPU_COUNTS = (1, 33, 128, 129, 417, SPLIT - 1, SPLIT, SPLIT + 1)
 SYMBOLS = ("urgym_actor_parameter_gradients", "urgym_actor_parameter_gradients_workspace")
@@ -263,11 +263,11 @@ def test_checkpoints_float32_against_float64(name):
 def test_index_arithmetic_on_the_host_under_sanitizers():
     exe = os.path.join(HERE, "_build", "actor_backward_harness")
     os.makedirs(os.path.dirname(exe), exist_ok=True)
-    src = os.path.join(HERE, "actor_backward_harness.cpp")
-    deps = [src, os.path.join(CSRC, "urgym_actor_backward_map.h")]
+    src = os.path.join(HERE, "backward_harness.cpp")
+    deps = [src, os.path.join(CSRC, "urgym_backward_map.h")]
     if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe, src])
-    run = subprocess.run([exe], capture_output=True, text=True)
+    run = subprocess.run([exe, "actor"], capture_output=True, text=True)
     out = run.stdout
     assert run.returncode == 0 and "FAIL" not in out and "runtime error" not in run.stderr, (out[-2000:], run.stderr[-2000:])
     lines = out.splitlines()

@@ -262,7 +262,7 @@ def test_index_arithmetic_on_the_host_under_sanitizers():
     deps = [src, os.path.join(CSRC, "urgym_backward_map.h")]
     if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe, src])
-    run = subprocess.run([exe], capture_output=True, text=True)
+    run = subprocess.run([exe, "critic"], capture_output=True, text=True)
     out = run.stdout
     assert run.returncode == 0 and "FAIL" not in out and "runtime error" not in run.stderr, (out[-2000:], run.stderr[-2000:])
     lines = out.splitlines()

@@ -86,6 +86,6 @@ uint64_t actor_backward_workspace_bytes(Actor* a, int count);
 int actor_backward_launches(int count);
 // on `s`; the caller has validated `call`, actor_backward_supported(a) and the log_std head
 void actor_backward_launch(Actor* a, const ActorBackwardCall& call, hipStream_t s);
-constexpr int ACTOR_BACKWARD_MAX_COUNT = 65536;  // urgym_actor_backward_map.h asserts it
+constexpr int ACTOR_BACKWARD_MAX_COUNT = 65536;  // urgym_actor_backward.hip asserts it against urgym_backward_map.h
 
 }  // namespace urgym

@@ -39,7 +39,7 @@
 
 #include "urgym_actor.h"
 #include "urgym_pack_host.h"
-#include "urgym_philox.h"
+#include "urgym_policy_noise.h"
 
 namespace urgym {
 
@@ -67,27 +67,8 @@ struct ActorSParams : ActorKParams {  // the sampling instances and uniform_kern
   ActorSample how;
 };
 
-constexpr uint32_t NOISE_TAG = 0x504F4C00u;  // counter word 3 of the policy noise is NOISE_TAG | block (include/urgym.h)
-constexpr float TWO_M24 = 1.0f / 16777216.0f;
-constexpr float HALF_LOG_2PI = 0.918938533204672742f;
+// NOISE_TAG, TWO_M24, HALF_LOG_2PI, noise_words, store6: urgym_policy_noise.h, shared with the backward pass
 constexpr float SIX_LOG_2 = 4.15888308335967186f;
-
-// the six words of (seed, draw, env) as their 24-bit integers m(w) = w >> 8, exact in float32
-__device__ __forceinline__ void noise_words(const ActorSample& S, uint32_t env, float m[6]) {
-  uint32_t a[4], b[4];
-  const uint32_t k0 = (uint32_t)S.seed, k1 = (uint32_t)(S.seed >> 32), d0 = (uint32_t)S.draw, d1 = (uint32_t)(S.draw >> 32);
-  philox4x32_10(k0, k1, env, d0, d1, NOISE_TAG | 0u, a);
-  philox4x32_10(k0, k1, env, d0, d1, NOISE_TAG | 1u, b);
-  m[0] = (float)(a[0] >> 8), m[1] = (float)(a[1] >> 8), m[2] = (float)(a[2] >> 8), m[3] = (float)(a[3] >> 8);
-  m[4] = (float)(b[0] >> 8), m[5] = (float)(b[1] >> 8);
-}
-
-__device__ __forceinline__ void store6(float* rows, size_t env, const float v[6]) {
-  float2* out = reinterpret_cast<float2*>(rows + env * 6);
-  out[0] = make_float2(v[0], v[1]);
-  out[1] = make_float2(v[2], v[3]);
-  out[2] = make_float2(v[4], v[5]);
-}
 
 __device__ __forceinline__ float feature(const ActorEnv& E, size_t e, int k) {
   const int gd = E.goal_dim;
@@ -332,7 +313,7 @@ actor_kernel(const std::conditional_t<SAMPLE, ActorSParams, ActorKParams> P) {
     float eps[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     if (gauss) {
       float m[6];
-      noise_words(S, (uint32_t)env, m);
+      noise_words(S.seed, S.draw, (uint32_t)env, m);
 #pragma unroll
       for (int p = 0; p < 3; p++) {  // Box-Muller: u1 in (0, 1], u2 in [0, 1), both exact
         const float r = sqrtf(-2.0f * logf((m[2 * p] + 1.0f) * TWO_M24));
@@ -377,7 +358,7 @@ __global__ void __launch_bounds__(ACTOR_THREADS) uniform_kernel(const ActorSPara
   if (!P.actions || tid >= ACTOR_ENVS || env >= N) return;
   const ActorSample& S = P.how;
   float u[6], act[6];
-  noise_words(S, (uint32_t)env, u);
+  noise_words(S.seed, S.draw, (uint32_t)env, u);
 #pragma unroll
   for (int o = 0; o < 6; o++) {
     u[o] *= TWO_M24;             // exact

@@ -1,7 +1,8 @@
 // urgym_actor_backward.hip — the gradient of a loss on the SAC actor with respect to its PARAMETERS: the backward pass of SAC's policy
 // loss as HIP kernels for MI355X (gfx950) (include/urgym.h, urgym_actor_parameter_gradients).  The mirror of
 // urgym_critic_backward.hip on the actor's packed buffer, whose layer 2 has the critic's layout (urgym_pack_map.h): two stages and a
-// workspace (urgym_actor_backward_map.h states every offset once, for host and device).
+// workspace (urgym_backward_map.h states every offset once, for host and device, as ActorBackwardMap; urgym_mlp_grad.h holds the blocks
+// of all three stages that the critic's gradient units share).
 //
 //   stage 1   per row, actor_kernel<HT, true>'s forward pass operation for operation (action and log_prob are bitwise
 //             urgym_actor_sample_rows'), the ReLU masks kept as bits; the head arithmetic of the SAMPLE form, or the given head
@@ -12,8 +13,8 @@
 //   stage 2   g_W1 = d2^T h1 and g_W0 = d1^T x as v_mfma_f32_32x32x2_f32 GEMMs with the row index as K, one wave per 64 x 64 block; the
 //             bias sums g_b1, g_b0 on the VALU from the A operands; g_Wmu and g_Wls as twelve fma chains per neuron against h2 in waves
 //             of their own (a 32-wide MFMA block would carry 12 useful columns of 32); g_bmu and g_bls are float64 sums rounded once
-//             per split.  Up to AB_SPLIT_ROWS rows it stores the results itself.
-//   stage 3   only above AB_SPLIT_ROWS rows: adds the partial results of the splits in ascending order, in float64, and rounds once.
+//             per split.  Up to BW_SPLIT_ROWS rows it stores the results itself.
+//   stage 3   only above BW_SPLIT_ROWS rows: adds the partial results of the splits in ascending order, in float64, and rounds once.
 //
 // The order of every sum is fixed by the geometry alone: per output element rows ascend within a split (row group by row group; within
 // a group of 32 rows the MFMA step (q, c), q = 0 .. 3, c = 0 .. 3, adds rows 8 q + c and 8 q + 4 + c; a head chain adds rows
@@ -24,55 +25,34 @@
 #include <type_traits>
 
 #include "urgym_actor.h"
-#include "urgym_actor_backward_map.h"
+#include "urgym_backward_map.h"
+#include "urgym_mlp_grad.h"
 #include "urgym_pack_map.h"
-#include "urgym_philox.h"
+#include "urgym_policy_noise.h"
 
 namespace urgym {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace mlp_grad;
+typedef ActorBackwardMap Map;
+enum { AB_G_WMU = BW_G_HEAD, AB_G_BMU, AB_G_WLS, AB_G_BLS };  // the head tensors of the policy
 
 // actor_kernel's geometry
 constexpr int ACTOR_THREADS = 256;  // 4 waves
 constexpr int ACTOR_ROWS = 128;     // rows per workgroup (32 per wave)
 constexpr int IN_PAD = 48;          // layer-1 K, padded with zero weights (in_features <= 47)
-static_assert(ACTOR_ROWS == AB_S1_ROWS && IN_PAD == AB_X && IN_PAD == 8 * PACK_ACTOR_STEPS4 && AB_MAX_COUNT == ACTOR_BACKWARD_MAX_COUNT, "urgym_actor_backward_map.h");
+static_assert(ACTOR_ROWS == BW_S1_ROWS && IN_PAD == Map::X && IN_PAD == 8 * PACK_ACTOR_STEPS4 && BW_MAX_COUNT == ACTOR_BACKWARD_MAX_COUNT, "urgym_backward_map.h");
 constexpr int L1_STEPS4 = IN_PAD / 8;
 constexpr int L1_TILE4 = L1_STEPS4 * 64;
 constexpr int L1_CHUNK4 = 4 * L1_TILE4;
-constexpr int L2_ROW4 = 66;  // float4 per read row of a staged layer-2 tile (urgym_critic_grad.hip: the transposed A operand)
-
-constexpr uint32_t NOISE_TAG = 0x504F4C00u;  // counter word 3 of the policy noise is NOISE_TAG | block (include/urgym.h)
-constexpr float TWO_M24 = 1.0f / 16777216.0f;
-constexpr float HALF_LOG_2PI = 0.918938533204672742f;
-
 struct BackwardKParams {
   const float4* p1;     // layer 1, packed [HT][L1_STEPS4][64 lanes] float4
   const float4* p2;     // layer 2, packed [HT][HT * 4][64 lanes] float4
   const float4* small;  // b0[HP] | b1[HP] | w_mu as [HP / 4][6][4] | b_mu[8] | w_log_std as [HP / 4][6][4] | b_log_std[8]
-  AbDims d;
+  BwDims d;
   ActorBackwardCall call;
 };
-
-// the six words of (seed, draw, env) as their 24-bit integers m(w) = w >> 8, exact in float32 (urgym_actor.hip: noise_words)
-__device__ __forceinline__ void noise_words(uint64_t seed, uint64_t draw, uint32_t env, float m[6]) {
-  uint32_t a[4], b[4];
-  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), d0 = (uint32_t)draw, d1 = (uint32_t)(draw >> 32);
-  philox4x32_10(k0, k1, env, d0, d1, NOISE_TAG | 0u, a);
-  philox4x32_10(k0, k1, env, d0, d1, NOISE_TAG | 1u, b);
-  m[0] = (float)(a[0] >> 8), m[1] = (float)(a[1] >> 8), m[2] = (float)(a[2] >> 8), m[3] = (float)(a[3] >> 8);
-  m[4] = (float)(b[0] >> 8), m[5] = (float)(b[1] >> 8);
-}
-
-__device__ __forceinline__ void store6(float* rows, size_t row, const float v[6]) {
-  float2* out = reinterpret_cast<float2*>(rows + row * 6);
-  out[0] = make_float2(v[0], v[1]);
-  out[1] = make_float2(v[2], v[3]);
-  out[2] = make_float2(v[4], v[5]);
-}
 
 __device__ __forceinline__ float row_feature(const ActorBackwardCall& C, size_t m, int k) {
   const int gd = C.goal_dim;
@@ -80,34 +60,6 @@ __device__ __forceinline__ float row_feature(const ActorBackwardCall& C, size_t 
   if (k < 2 * gd) return C.desired_goal[m * gd + (k - gd)];
   k -= 2 * gd;
   return k < C.obs_dim ? C.observation[m * C.obs_dim + k] : 0.0f;
-}
-
-// where float4 (read row sq, lane l) of a packed layer-2 tile lies in its staged image
-__device__ __forceinline__ int l2_slot(int sq, int l) { return sq * L2_ROW4 + l + (l >> 5); }
-
-// bit v = acc[v] > 0: a pre-activation of exactly 0 has derivative 0 (torch's relu), and so has NaN
-__device__ __forceinline__ uint32_t relu_bits(const f32x16 acc) {
-  uint32_t bits = 0;
-#pragma unroll
-  for (int v = 0; v < 16; v++) bits |= (acc[v] > 0.0f ? 1u : 0u) << v;
-  return bits;
-}
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>());
-    static_for<I + 1, N>(f);
-  }
-}
-
-// makes a value opaque to the optimiser where it is complete (urgym_critic_grad.hip: formed)
-__device__ __forceinline__ void formed(uint32_t& word) { word = (uint32_t)__builtin_amdgcn_mov_dpp((int)word, 0xE4, 0xF, 0xF, true); }
-
-// a result that must be rounded before it is used (urgym_critic.hip: rounded)
-__device__ __forceinline__ float rounded(float x) {
-  asm volatile("" : "+v"(x));
-  return x;
 }
 
 // ------------------------------------------------------------------------------------------------ stage 1
@@ -129,7 +81,7 @@ __global__ void __launch_bounds__(ACTOR_THREADS, 1) actor_backward_rows_kernel(c
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const ActorBackwardCall& C = P.call;
-  const AbDims& D = P.d;
+  const BwDims& D = P.d;
   const int M = C.M;
 
   for (int i = tid; i < SMALL4; i += ACTOR_THREADS) small4[i] = P.small[i];
@@ -137,26 +89,27 @@ __global__ void __launch_bounds__(ACTOR_THREADS, 1) actor_backward_rows_kernel(c
   for (int i = 0; i < PF1; i++) wbuf[0][tid + ACTOR_THREADS * i] = P.p1[tid + ACTOR_THREADS * i];
 
   const int h = lane >> 5;
-  const size_t row = ab_s1_row(blockIdx.x, wave, lane);
+  const size_t row = Map::s1_row(blockIdx.x, wave, lane);
   const bool live = row < (size_t)M;
-  const bool stores = ab_s1_stores(D, row);     // the same for the whole wave: its row group exists
+  const bool stores = Map::s1_stores(D, row);     // the same for the whole wave: its row group exists
   const size_t m = live ? row : (size_t)M - 1;  // lanes past the end compute on the last row and store +0
   // the wave's row group, in scalar registers, and this lane's place in a group's [neuron][32 rows]: the neurons of lane half 1 are 4 on
-  const size_t group = ab_s1_group(blockIdx.x, __builtin_amdgcn_readfirstlane(wave));
-  const uint32_t lane_off = ab_s1_lane_offset(lane, 4);
-  // this lane as an A lane of the backward pass (urgym_critic_grad.hip)
+  const size_t group = Map::s1_group(blockIdx.x, __builtin_amdgcn_readfirstlane(wave));
+  const uint32_t lane_off = Map::s1_lane_offset(lane, 4);
+  // this lane in the staged images (urgym_mlp_grad.h: Lane)
   const int ai = lane & 31, jj = 8 * (ai >> 3) + 2 * (ai & 3) + ((ai >> 2) & 1);
   const int abase = (jj >> 1) * L2_ROW4 + (jj & 1) * 33 + 4 * h;
   const int sbase = l2_slot(tid >> 6, tid & 63);
+  const Lane L = {tid, lane, h, abase, sbase};
 
   const float* small = reinterpret_cast<const float*>(small4);
   int buf = 0;  // the half of wbuf that holds the chunk in use
 
   // this lane's float of (array, neuron 0); neuron n is 32 n floats on (a wave-uniform base and one 32-bit lane offset)
-  float* const ws_h1 = C.workspace + ab_group_offset(D, AB_H1, group) + lane_off;
-  float* const ws_h2 = C.workspace + ab_group_offset(D, AB_H2, group) + lane_off;
-  float* const ws_d2 = C.workspace + ab_group_offset(D, AB_D2, group) + lane_off;
-  float* const ws_d1 = C.workspace + ab_group_offset(D, AB_D1, group) + lane_off;
+  float* const ws_h1 = C.workspace + Map::group_offset(D, 0, BW_H1, group) + lane_off;
+  float* const ws_h2 = C.workspace + Map::group_offset(D, 0, BW_H2, group) + lane_off;
+  float* const ws_d2 = C.workspace + Map::group_offset(D, 0, BW_D2, group) + lane_off;
+  float* const ws_d1 = C.workspace + Map::group_offset(D, 0, BW_D1, group) + lane_off;
 
   // this lane's B operands of layer 1: features 2 s + h of its row
   float xb[IN_PAD / 2];
@@ -164,7 +117,7 @@ __global__ void __launch_bounds__(ACTOR_THREADS, 1) actor_backward_rows_kernel(c
   for (int s = 0; s < IN_PAD / 2; s++) xb[s] = row_feature(C, m, 2 * s + h);
   if (stores) {
 #pragma unroll
-    for (int s = 0; s < IN_PAD / 2; s++) (C.workspace + ab_x_group_offset(D, group))[32 * (2 * s) + ab_s1_lane_offset(lane, 1)] = live ? xb[s] : 0.0f;
+    for (int s = 0; s < IN_PAD / 2; s++) (C.workspace + Map::x_group_offset(D, group))[32 * (2 * s) + Map::s1_lane_offset(lane, 1)] = live ? xb[s] : 0.0f;
   }
   __syncthreads();  // small4, the first chunk
 
@@ -174,48 +127,14 @@ __global__ void __launch_bounds__(ACTOR_THREADS, 1) actor_backward_rows_kernel(c
 
   // ---- layer 1 forward (actor_kernel's); h1 lives until layer 2 has run forward, its mask beyond
   float h1[HT * 16];
-  // the chunk after the one in use travels in four parts (urgym_critic_grad.hip: staged)
-  auto staged = [&](const float4* next, auto npf, auto next_is_tile, auto&& quarter) __attribute__((always_inline)) {
-    constexpr int NPF = decltype(npf)::value, CH = (NPF + 3) / 4;
-    constexpr bool TILE = decltype(next_is_tile)::value;
-    float4* wn = wbuf[buf ^ 1];
-    static_for<0, 4>([&](auto sg) __attribute__((always_inline)) {
-      constexpr int S = decltype(sg)::value, I0 = S * CH, N = I0 + CH <= NPF ? CH : (NPF > I0 ? NPF - I0 : 0);
-      f32x4 pf[N > 0 ? N : 1];  // (a native vector: copies of a float4 struct that a rounded() stands between stayed in scratch)
-      static_for<0, N>([&](auto i) __attribute__((always_inline)) { pf[i] = *reinterpret_cast<const f32x4*>(next + ACTOR_THREADS * (I0 + i)); });
-      quarter(sg);
-      static_for<0, N>([&](auto i) __attribute__((always_inline)) {
-        *reinterpret_cast<f32x4*>(wn + (TILE ? sbase + 4 * L2_ROW4 * (I0 + i) : tid + ACTOR_THREADS * (I0 + i))) = pf[i];
-      });
-    });
-    __syncthreads();  // everyone has left this chunk (its buffer is the one after next) and the next chunk is in place
-    buf ^= 1;
-  };
+  // chunk c of four tiles; meanwhile the next chunk travels: another of layer 1 or, after the last, layer-2 tile 0
   auto chunk1 = [&](auto cc) __attribute__((always_inline)) {
     constexpr int c = decltype(cc)::value;
     constexpr bool LAST = c + 1 == L1_CHUNKS;
-    constexpr int NPF = LAST ? PF2 : PF1;
     const float4* wb = wbuf[buf];
-    staged((LAST ? P.p2 : P.p1 + (c + 1) * L1_CHUNK4) + tid, std::integral_constant<int, NPF>(), std::integral_constant<bool, LAST>(), [&](auto sg) __attribute__((always_inline)) {
-      constexpr int tt = decltype(sg)::value, t = 4 * c + tt;
-      f32x16 acc;
-#pragma unroll
-      for (int g = 0; g < 4; g++) {
-        const float4 b = small4[(32 * t + 8 * g + 4 * h) / 4];
-        acc[4 * g + 0] = b.x, acc[4 * g + 1] = b.y, acc[4 * g + 2] = b.z, acc[4 * g + 3] = b.w;
-      }
-#pragma unroll
-      for (int sq = 0; sq < L1_STEPS4; sq++) {
-        const float4 a = wb[(tt * L1_STEPS4 + sq) * 64 + lane];
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, xb[4 * sq + 0], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, xb[4 * sq + 1], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, xb[4 * sq + 2], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, xb[4 * sq + 3], acc, 0, 0, 0);
-      }
-#pragma unroll
-      for (int v = 0; v < 16; v++) h1[t * 16 + v] = fmaxf(acc[v], 0.0f);
-      m1[t >> 1] |= relu_bits(acc) << (16 * (t & 1));
-      if constexpr (tt & 1) formed(m1[t >> 1]);
+    staged<ACTOR_THREADS, (LAST ? PF2 : PF1), LAST>(wbuf, buf, L, (LAST ? P.p2 : P.p1 + (c + 1) * L1_CHUNK4) + tid, [&](auto sg) __attribute__((always_inline)) {
+      constexpr int tt = decltype(sg)::value;
+      layer1_tile<L1_STEPS4, tt, 4 * c + tt, HT>(wb, small4, L, xb, h1, m1);
     });
   };
   chunk1(std::integral_constant<int, 0>());
@@ -226,7 +145,7 @@ __global__ void __launch_bounds__(ACTOR_THREADS, 1) actor_backward_rows_kernel(c
 #pragma unroll
     for (int t = 0; t < HT; t++)
 #pragma unroll
-      for (int v = 0; v < 16; v++) ws_h1[32 * ab_fwd_neuron(t, v, 0)] = live ? h1[t * 16 + v] : 0.0f;
+      for (int v = 0; v < 16; v++) ws_h1[32 * Map::fwd_neuron(t, v, 0)] = live ? h1[t * 16 + v] : 0.0f;
   }
 
   // ---- layer 2 forward tile by tile, each tile straight into both heads of layer 3 (actor_kernel<HT, true>'s fma order per output:
@@ -241,16 +160,8 @@ __global__ void __launch_bounds__(ACTOR_THREADS, 1) actor_backward_rows_kernel(c
       const float4 b = small4[(HP + 32 * t + 8 * g + 4 * h) / 4];
       acc[4 * g + 0] = b.x, acc[4 * g + 1] = b.y, acc[4 * g + 2] = b.z, acc[4 * g + 3] = b.w;
     }
-    staged(next, std::integral_constant<int, PF2>(), std::true_type(), [&](auto sg) __attribute__((always_inline)) {
-      constexpr int S = decltype(sg)::value;
-#pragma unroll
-      for (int sq = S * HT; sq < (S + 1) * HT; sq++) {  // sq = 4 u + g: registers 4 g .. 4 g + 3 of layer-1 tile u
-        const float4 a = wb[sq * L2_ROW4];
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, h1[4 * sq + 0], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, h1[4 * sq + 1], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, h1[4 * sq + 2], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, h1[4 * sq + 3], acc, 0, 0, 0);
-      }
+    staged<ACTOR_THREADS, PF2, true>(wbuf, buf, L, next, [&](auto sg) __attribute__((always_inline)) {
+      layer2_forward_quarter<HT, decltype(sg)::value>(wb, h1, acc);
     });
     f32x16 r;
 #pragma unroll
@@ -280,7 +191,7 @@ __global__ void __launch_bounds__(ACTOR_THREADS, 1) actor_backward_rows_kernel(c
     }
     if (stores) {
 #pragma unroll
-      for (int v = 0; v < 16; v++) ws_h2[32 * ab_fwd_neuron(t, v, 0)] = live ? r[v] : 0.0f;
+      for (int v = 0; v < 16; v++) ws_h2[32 * Map::fwd_neuron(t, v, 0)] = live ? r[v] : 0.0f;
     }
     uint32_t bits = relu_bits(acc) << (16 * (t & 1));
     formed(bits);
@@ -344,7 +255,7 @@ __global__ void __launch_bounds__(ACTOR_THREADS, 1) actor_backward_rows_kernel(c
   }
   if (h == 0) {
     if (stores) {
-      float* ws_heads = C.workspace + ab_heads_group_offset(D, group) + (lane & 31);
+      float* ws_heads = C.workspace + Map::heads_group_offset(D, 0, group) + (lane & 31);
 #pragma unroll
       for (int o = 0; o < 6; o++) ws_heads[32 * o] = dmu[o], ws_heads[32 * (6 + o)] = dr[o];
     }
@@ -386,7 +297,7 @@ __global__ void __launch_bounds__(ACTOR_THREADS, 1) actor_backward_rows_kernel(c
       for (int g = 0; g < 4; g++) {
         const f32x4 d = head_back(t, g);
 #pragma unroll
-        for (int c = 0; c < 4; c++) ws_d2[32 * ab_fwd_neuron(t, 4 * g + c, 0)] = (live && ((bits >> (4 * g + c)) & 1u)) ? d[c] : 0.0f;
+        for (int c = 0; c < 4; c++) ws_d2[32 * Map::fwd_neuron(t, 4 * g + c, 0)] = (live && ((bits >> (4 * g + c)) & 1u)) ? d[c] : 0.0f;
       }
     }
   }
@@ -398,26 +309,12 @@ __global__ void __launch_bounds__(ACTOR_THREADS, 1) actor_backward_rows_kernel(c
 #pragma unroll
     for (int v = 0; v < 16; v++) dacc[u][v] = 0.0f;
   auto back2 = [&](int t, const float4* next, auto npf) __attribute__((always_inline)) {
-    uint32_t word = 0;
-#pragma unroll
-    for (int i = 0; i < MW; i++) word = (t >> 1) == i ? m2[i] : word;
-    const uint32_t bits = word >> (16 * (t & 1));
+    const uint32_t bits = mask_tile(m2, t);
     const float4* wb = wbuf[buf] + abase;
-    staged(next, npf, std::true_type(), [&](auto sg) __attribute__((always_inline)) {
+    staged<ACTOR_THREADS, decltype(npf)::value, true>(wbuf, buf, L, next, [&](auto sg) __attribute__((always_inline)) {
       constexpr int g = decltype(sg)::value;
       const f32x4 d = head_back(t, g);
-#pragma unroll
-      for (int r = 0; r < 4; r++) {  // one MFMA step: k = h is neuron 32 t + 8 g + 4 h + r of layer 2
-        const float b = (bits >> (4 * g + r)) & 1u ? d[r] : 0.0f;
-#pragma unroll
-        for (int U = 0; U < HT / 4; U++) {
-          const float4 a = wb[16 * U * L2_ROW4 + 8 * g + r];  // W1[32 t + 8 g + 4 h + r][128 U + 4 jj + c], c = 0 .. 3
-          dacc[4 * U + 0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b, dacc[4 * U + 0], 0, 0, 0);
-          dacc[4 * U + 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b, dacc[4 * U + 1], 0, 0, 0);
-          dacc[4 * U + 2] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b, dacc[4 * U + 2], 0, 0, 0);
-          dacc[4 * U + 3] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b, dacc[4 * U + 3], 0, 0, 0);
-        }
-      }
+      layer2_backward_quarter<HT, g>(wb, [&](int r) __attribute__((always_inline)) { return (bits >> (4 * g + r)) & 1u ? d[r] : 0.0f; }, dacc);
     });
   };
 #pragma unroll 1
@@ -433,7 +330,7 @@ __global__ void __launch_bounds__(ACTOR_THREADS, 1) actor_backward_rows_kernel(c
         const int u = 4 * U + (v >> 2);
         const uint32_t bits = m1[u >> 1] >> (16 * (u & 1) + 4 * (v & 3));
 #pragma unroll
-        for (int c = 0; c < 4; c++) ws_d1[32 * ab_back_neuron(4 * U + c, v, 0)] = (live && ((bits >> c) & 1u)) ? dacc[4 * U + c][v] : 0.0f;
+        for (int c = 0; c < 4; c++) ws_d1[32 * Map::back_neuron(4 * U + c, v, 0)] = (live && ((bits >> c) & 1u)) ? dacc[4 * U + c][v] : 0.0f;
       }
   }
 }
@@ -442,72 +339,65 @@ __global__ void __launch_bounds__(ACTOR_THREADS, 1) actor_backward_rows_kernel(c
 struct ReduceKParams {
   const float* ws;
   float* partial;  // the workspace again, for the partial sums (S > 1)
-  AbDims d;
-  float* grad[AB_TENSORS];
+  BwDims d;
+  float* grad[Map::NETS][Map::TENSORS];
 };
 
-// Four consecutive rows of neuron n of an array: one float4.  n < limit, or the operand is +0 (the columns of x past 48).
-__device__ __forceinline__ float4 operand4(const float* base, int n, int limit) {
-  if (n >= limit) return make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  return *reinterpret_cast<const float4*>(base + 32 * (size_t)n);
-}
-
 __global__ void __launch_bounds__(256) actor_backward_reduce_kernel(const ReduceKParams P) {
-  const AbDims& D = P.d;
+  const BwDims& D = P.d;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, i = lane & 31;
-  int split, job0;
-  ab_s2_block(D, blockIdx.x, &split, &job0);
-  const AbJob job = ab_job(D, job0 + wave);
-  if (job.kind == AB_JOB_NONE) return;
+  int split, net, job0;  // net = 0
+  Map::s2_block(D, blockIdx.x, &split, &net, &job0);
+  const BwJob job = Map::job(D, job0 + wave);
+  if (job.kind == BW_JOB_NONE) return;
   int R0, R1;
-  ab_split_groups(D, split, &R0, &R1);
-  float* dst[AB_TENSORS];
+  Map::split_groups(D, split, &R0, &R1);
+  float* dst[Map::TENSORS];
 #pragma unroll
-  for (int t = 0; t < AB_TENSORS; t++) dst[t] = D.S > 1 ? P.partial + ab_partial_offset(D, split) + ab_tensor_offset(D, t) : P.grad[t];
+  for (int t = 0; t < Map::TENSORS; t++) dst[t] = D.S > 1 ? P.partial + Map::partial_offset(D, split, 0) + Map::tensor_offset(D, t) : P.grad[0][t];
 
-  if (job.kind == AB_JOB_HEAD) {
+  if (job.kind == BW_JOB_HEAD) {
     const int n = 32 * job.ab + i;
-    float acc[AB_HEADS];
+    float acc[Map::HEADS];
 #pragma unroll
-    for (int j = 0; j < AB_HEADS; j++) acc[j] = 0.0f;
+    for (int j = 0; j < Map::HEADS; j++) acc[j] = 0.0f;
     for (int R = R0; R < R1; R++)
 #pragma unroll
       for (int q = 0; q < 4; q++) {
-        const size_t row = ab_s2_row(R, q, h);
-        const float4 a = *reinterpret_cast<const float4*>(P.ws + ab_offset(D, AB_H2, row, n));
+        const size_t row = Map::s2_row(R, q, h);
+        const float4 a = *reinterpret_cast<const float4*>(P.ws + Map::offset(D, 0, BW_H2, row, n));
 #pragma unroll
-        for (int j = 0; j < AB_HEADS; j++) {
-          const float4 d = *reinterpret_cast<const float4*>(P.ws + ab_heads_offset(D, row, j));
+        for (int j = 0; j < Map::HEADS; j++) {
+          const float4 d = *reinterpret_cast<const float4*>(P.ws + Map::heads_offset(D, 0, row, j));
           acc[j] = fmaf(a.x, d.x, acc[j]), acc[j] = fmaf(a.y, d.y, acc[j]), acc[j] = fmaf(a.z, d.z, acc[j]), acc[j] = fmaf(a.w, d.w, acc[j]);
         }
       }
 #pragma unroll
-    for (int j = 0; j < AB_HEADS; j++) {
+    for (int j = 0; j < Map::HEADS; j++) {
       const float g = acc[j] + __shfl_xor(acc[j], 32);
-      if (h == 0 && n < D.H) dst[ab_head_tensor(j)][ab_head_element(D, j, n)] = g;
+      if (h == 0 && n < D.H) dst[Map::head_tensor(j)][Map::head_element(D, j, n)] = g;
     }
     if (job.ab != 0) return;
     // g_bmu and g_bls of the split: twelve scalars out of up to 1024 terms each, possibly of one sign, so the sums are kept in float64
     // and rounded once.  Lane (h, i) adds row i of every second row group from R0 + h on, ascending; then the 64 lanes are added in
-    // a fixed butterfly.
-    double dsum[AB_HEADS];
+    // a fixed butterfly (lane_sum).
+    double dsum[Map::HEADS];
 #pragma unroll
-    for (int j = 0; j < AB_HEADS; j++) dsum[j] = 0.0;
+    for (int j = 0; j < Map::HEADS; j++) dsum[j] = 0.0;
     for (int R = R0 + h; R < R1; R += 2)
 #pragma unroll
-      for (int j = 0; j < AB_HEADS; j++) dsum[j] += (double)P.ws[ab_heads_offset(D, ab_s2_bias_row(R, i), j)];
+      for (int j = 0; j < Map::HEADS; j++) dsum[j] += (double)P.ws[Map::heads_offset(D, 0, Map::s2_bias_row(R, i), j)];
 #pragma unroll
-    for (int j = 0; j < AB_HEADS; j++) {
-#pragma unroll
-      for (int step = 32; step >= 1; step >>= 1) dsum[j] += __shfl_xor(dsum[j], step);
+    for (int j = 0; j < Map::HEADS; j++) {
+      dsum[j] = lane_sum(dsum[j]);
       if (lane == 0) dst[j < 6 ? AB_G_BMU : AB_G_BLS][j % 6] = (float)dsum[j];
     }
     return;
   }
 
   // a 64 x 64 block: A = d2 (g_W1) or d1 (g_W0), neurons 64 ab + 32 ia + i; B = h1, or x with 48 columns
-  const bool w1 = job.kind == AB_JOB_W1;
-  const int a_array = w1 ? AB_D2 : AB_D1, b_limit = w1 ? D.HP : AB_X;
+  const bool w1 = job.kind == BW_JOB_W1;
+  const int a_array = w1 ? BW_D2 : BW_D1, b_limit = w1 ? D.HP : Map::X;
   f32x16 acc[2][2];
 #pragma unroll
   for (int ia = 0; ia < 2; ia++)
@@ -520,71 +410,38 @@ __global__ void __launch_bounds__(256) actor_backward_reduce_kernel(const Reduce
   for (int R = R0; R < R1; R++)
 #pragma unroll
     for (int q = 0; q < 4; q++) {
-      const size_t row = ab_s2_row(R, q, h);
-      const float* abase = P.ws + ab_offset(D, a_array, row, 0);
-      const float* bbase = w1 ? P.ws + ab_offset(D, AB_H1, row, 0) : P.ws + ab_x_offset(D, row, 0);
+      const size_t row = Map::s2_row(R, q, h);
+      const float* abase = P.ws + Map::offset(D, 0, a_array, row, 0);
+      const float* bbase = w1 ? P.ws + Map::offset(D, 0, BW_H1, row, 0) : P.ws + Map::x_offset(D, row, 0);
       float4 a[2], b[2];
       a[0] = operand4(abase, an, D.HP), a[1] = operand4(abase, an + 32, D.HP);
       b[0] = operand4(bbase, bn, b_limit), b[1] = operand4(bbase, bn + 32, b_limit);
-#pragma unroll
-      for (int ia = 0; ia < 2; ia++) {
-#pragma unroll
-        for (int jb = 0; jb < 2; jb++) {
-          acc[ia][jb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[ia].x, b[jb].x, acc[ia][jb], 0, 0, 0);
-          acc[ia][jb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[ia].y, b[jb].y, acc[ia][jb], 0, 0, 0);
-          acc[ia][jb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[ia].z, b[jb].z, acc[ia][jb], 0, 0, 0);
-          acc[ia][jb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[ia].w, b[jb].w, acc[ia][jb], 0, 0, 0);
-        }
-        bsum[ia] = (((bsum[ia] + a[ia].x) + a[ia].y) + a[ia].z) + a[ia].w;
-      }
+      gemm_step(acc, bsum, a, b);
     }
-  const int columns = w1 ? D.H : D.in;
-  float* gw = dst[w1 ? AB_G_W1 : AB_G_W0];
-#pragma unroll
-  for (int ia = 0; ia < 2; ia++) {
-#pragma unroll
-    for (int jb = 0; jb < 2; jb++) {
-      const int j = ab_s2_column(job, jb, lane);
-#pragma unroll
-      for (int v = 0; v < 16; v++) {
-        const int n = ab_s2_neuron(job, ia, v, lane);
-        if (n < D.H && j < columns) gw[(size_t)n * columns + j] = acc[ia][jb][v];  // padded rows and columns are never stored
-      }
-    }
-    const float gb = bsum[ia] + __shfl_xor(bsum[ia], 32);
-    const int n = an + 32 * ia;
-    if (job.bb == 0 && h == 0 && n < D.H) dst[w1 ? AB_G_B1 : AB_G_B0][n] = gb;
-  }
+  gemm_store<Map>(D, job, lane, w1 ? D.H : D.in, dst[w1 ? BW_G_W1 : BW_G_W0], dst[w1 ? BW_G_B1 : BW_G_B0], acc, bsum);
 }
 
 // ------------------------------------------------------------------------------------------------ stage 3
 __global__ void __launch_bounds__(256) actor_backward_combine_kernel(const ReduceKParams P) {
-  const AbDims& D = P.d;
-  const size_t r = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (r >= D.P) return;
-  double sum = (double)P.partial[ab_partial_offset(D, 0) + r];  // at most 64 float32 terms: float64 adds them without an error of its own
-  for (int s = 1; s < D.S; s++) sum += (double)P.partial[ab_partial_offset(D, s) + r];
-  size_t at;
-  const int t = ab_tensor_of(D, r, &at);
-  P.grad[t][at] = (float)sum;
+  combine_element<Map>(P.partial, P.d, P.grad, (size_t)blockIdx.x * 256 + threadIdx.x);
 }
 
 template <int HT>
 void launch_rows(const BackwardKParams& P, hipStream_t s) {
-  hipLaunchKernelGGL((actor_backward_rows_kernel<HT>), dim3(ab_s1_grid(P.d)), dim3(ACTOR_THREADS), 0, s, P);
+  hipLaunchKernelGGL((actor_backward_rows_kernel<HT>), dim3(Map::s1_grid(P.d)), dim3(ACTOR_THREADS), 0, s, P);
 }
 
 }  // namespace
 
 // Instances HT = 4 and 8, like the critic's gradients and for their reason: the 16 HT accumulators of the pass back through layer 2.
-bool actor_backward_supported(Actor* a) { return actor_packed(a).hidden <= AB_MAX_HIDDEN; }
+bool actor_backward_supported(Actor* a) { return actor_packed(a).hidden <= BW_MAX_HIDDEN; }
 
 uint64_t actor_backward_workspace_bytes(Actor* a, int count) {
   const ActorPacked buf = actor_packed(a);
-  return (uint64_t)ab_dims(buf.in_features, buf.hidden, count).floats * sizeof(float);
+  return (uint64_t)Map::dims(buf.in_features, buf.hidden, count).floats * sizeof(float);
 }
 
-int actor_backward_launches(int count) { return count > AB_SPLIT_ROWS ? 3 : 2; }
+int actor_backward_launches(int count) { return count > BW_SPLIT_ROWS ? 3 : 2; }
 
 void actor_backward_launch(Actor* a, const ActorBackwardCall& call, hipStream_t s) {
   const ActorPacked buf = actor_packed(a);
@@ -593,14 +450,14 @@ void actor_backward_launch(Actor* a, const ActorBackwardCall& call, hipStream_t 
   P.p1 = reinterpret_cast<const float4*>(buf.weights);
   P.p2 = reinterpret_cast<const float4*>(buf.weights + pd.n1);
   P.small = reinterpret_cast<const float4*>(buf.weights + pd.n1 + pd.n2);
-  P.d = ab_dims(buf.in_features, buf.hidden, call.M);
+  P.d = Map::dims(buf.in_features, buf.hidden, call.M);
   P.call = call;
   if (pd.HT == 4) launch_rows<4>(P, s);
   else launch_rows<8>(P, s);
   ReduceKParams Q;
   Q.ws = call.workspace, Q.partial = call.workspace, Q.d = P.d;
-  for (int t = 0; t < AB_TENSORS; t++) Q.grad[t] = call.grad[t];
-  hipLaunchKernelGGL(actor_backward_reduce_kernel, dim3(ab_s2_grid(P.d)), dim3(256), 0, s, Q);
+  for (int t = 0; t < Map::TENSORS; t++) Q.grad[0][t] = call.grad[t];
+  hipLaunchKernelGGL(actor_backward_reduce_kernel, dim3(Map::s2_grid(P.d)), dim3(256), 0, s, Q);
   if (P.d.S > 1) hipLaunchKernelGGL(actor_backward_combine_kernel, dim3((unsigned)((P.d.P + 255) / 256)), dim3(256), 0, s, Q);
 }
 

@@ -18,15 +18,8 @@
 //              workgroup and network into LDS [6][HP]: da[c] = sum_j W0[j][c] (mask1[j] ? dh1[j] : 0), 6 * 16 HT fma per lane and one
 //              cross-lane add.
 //
-// The transposed A operand.  A packed layer-2 tile holds W1[32 t + n][j] in float (j & 3) of the float4 of read row sq = j >> 3 and
-// lane 32 ((j >> 2) & 1) + n: four CONSECUTIVE j of one neuron n are one float4.  So one ds_read_b128 feeds FOUR MFMAs if the output
-// rows are dealt out accordingly: accumulator 4 U + c, register v, lane half h holds dh1 of neuron j = 128 U + 8 v + 4 h + c -- which
-// is exactly where the forward pass left the mask bit of that neuron (tile 4 U + (v >> 2), register 4 (v & 3) + c, the same lane), so
-// the masks need no lane movement either.  In the forward layout [sq][64 lanes] the 16 lanes of a ds_read_b128 group would then sit
-// 128 floats apart on the same four banks; the staged tile is therefore laid out with rows of 66 float4 and lane l at l + (l >> 5):
-// the float4 slot (address mod 16) of A-lane i becomes jj(i) mod 16 + const, jj(i) = 8 (i >> 3) + 2 (i & 3) + ((i >> 2) & 1), which
-// is distinct over each of the four lane groups of ds_read_b128, and the forward read (slot = lane + (lane >> 5) + const) stays
-// conflict-free as well.  Only the LDS image is padded; the packed buffer in memory is untouched.
+// The staged double buffer, the forward and backward MFMA blocks, the mask words and the transposed A operand with its padded LDS image are
+// urgym_mlp_grad.h's, shared with the two parameter-gradient units; what is written out here is what this kernel alone does.
 //
 // This unit may contract a * b + c to fma, like urgym_critic.hip.
 #include <hip/hip_runtime.h>
@@ -34,12 +27,13 @@
 #include <type_traits>
 
 #include "urgym_critic.h"
+#include "urgym_mlp_grad.h"
 
 namespace urgym {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using namespace mlp_grad;
 
 // critic_kernel's geometry: urgym_critic.h states it once and both units assert it
 constexpr int CRITIC_THREADS = CRITIC_GEOMETRY_THREADS;  // 4 waves
@@ -48,7 +42,6 @@ constexpr int CIN_PAD = CRITIC_GEOMETRY_CIN_PAD;         // layer-1 K, padded wi
 constexpr int C1_STEPS4 = CIN_PAD / 8;
 constexpr int C1_TILE4 = C1_STEPS4 * 64;
 constexpr int C1_CHUNK4 = 4 * C1_TILE4;
-constexpr int L2_ROW4 = 66;  // float4 per read row of a staged layer-2 tile: 64 lanes, one slot between the halves, one of padding
 
 struct CriticGradKParams {
   const float4* w;      // the critic's packed layers (CriticKParams of urgym_critic.hip)
@@ -66,30 +59,6 @@ __device__ __forceinline__ float grad_feature(const CriticGradCall& C, size_t m,
   k -= C.obs_dim;
   return k < 6 ? C.action[m * 6 + k] : 0.0f;
 }
-
-// where float4 (read row sq, lane l) of a packed layer-2 tile lies in its staged image
-__device__ __forceinline__ int l2_slot(int sq, int l) { return sq * L2_ROW4 + l + (l >> 5); }
-
-// bit v = acc[v] > 0: a pre-activation of exactly 0 has derivative 0 (torch's relu), and so has NaN
-__device__ __forceinline__ uint32_t relu_bits(const f32x16 acc) {
-  uint32_t bits = 0;
-#pragma unroll
-  for (int v = 0; v < 16; v++) bits |= (acc[v] > 0.0f ? 1u : 0u) << v;
-  return bits;
-}
-
-// f(0), ..., f(N - 1) with the index a constant from the start: a prefetch array indexed so is registers in every pass
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>());
-    static_for<I + 1, N>(f);
-  }
-}
-
-// Makes a value opaque to the optimiser where it is complete (an identity quad permutation, one v_mov_dpp).  The mask words need it:
-// left to itself the compiler keeps the 16 floats of a tile alive and compares where a bit is used, a pass later, and spills them.
-__device__ __forceinline__ void formed(uint32_t& word) { word = (uint32_t)__builtin_amdgcn_mov_dpp((int)word, 0xE4, 0xF, 0xF, true); }
 
 template <int HT>
 __global__ void __launch_bounds__(CRITIC_THREADS, (HT <= 4 ? 2 : 1)) critic_grad_kernel(const CriticGradKParams P) {
@@ -119,11 +88,11 @@ __global__ void __launch_bounds__(CRITIC_THREADS, (HT <= 4 ? 2 : 1)) critic_grad
   const size_t row = row0 + wave * 32 + (lane & 31);
   const bool live = row < (size_t)M;
   const size_t m = live ? row : (size_t)M - 1;  // lanes past the end compute on the last row and store nothing
-  // this lane as an A lane of the backward pass: output row i = lane & 31 is input neuron 4 jj + c of its group of 128, k = h
+  // this lane in the staged images (urgym_mlp_grad.h: Lane)
   const int ai = lane & 31, jj = 8 * (ai >> 3) + 2 * (ai & 3) + ((ai >> 2) & 1);
   const int abase = (jj >> 1) * L2_ROW4 + (jj & 1) * 33 + 4 * h;
-  // the staging slot of float4 tid + 256 i of a layer-2 tile: read row (tid >> 6) + 4 i, lane tid & 63
   const int sbase = l2_slot(tid >> 6, tid & 63);
+  const Lane L = {tid, lane, h, abase, sbase};
 
   const float* small = reinterpret_cast<const float*>(small4);
   float* wact = reinterpret_cast<float*>(wact4);
@@ -165,49 +134,15 @@ __global__ void __launch_bounds__(CRITIC_THREADS, (HT <= 4 ? 2 : 1)) critic_grad
 
     // ---- layer 1 forward (critic_kernel's); h1 lives until layer 2 has run forward, its mask beyond
     float h1[HT * 16];
-    // The chunk after the one in use (NPF float4 per thread at `next`, a layer-2 tile for its padded image or a layer-1 chunk as it is)
-    // travels in FOUR parts, each loaded before and stored after a quarter of the work on the chunk in use: a quarter of the prefetch
-    // registers.  Nobody reads the other half of wbuf before the barrier that ends the work.
-    auto staged = [&](const float4* next, auto npf, auto next_is_tile, auto&& quarter) __attribute__((always_inline)) {
-      constexpr int NPF = decltype(npf)::value, CH = (NPF + 3) / 4;
-      constexpr bool TILE = decltype(next_is_tile)::value;
-      float4* wn = wbuf[buf ^ 1];
-      static_for<0, 4>([&](auto sg) {
-        constexpr int S = decltype(sg)::value, I0 = S * CH, N = I0 + CH <= NPF ? CH : (NPF > I0 ? NPF - I0 : 0);
-        float4 pf[N > 0 ? N : 1];
-        static_for<0, N>([&](auto i) { pf[i] = next[CRITIC_THREADS * (I0 + i)]; });
-        quarter(sg);
-        static_for<0, N>([&](auto i) { wn[TILE ? sbase + 4 * L2_ROW4 * (I0 + i) : tid + CRITIC_THREADS * (I0 + i)] = pf[i]; });
-      });
-      __syncthreads();  // everyone has left this chunk (its buffer is the one after next) and the next chunk is in place
-      buf ^= 1;
-    };
     // chunk c of four tiles; meanwhile the next chunk travels: another of layer 1 or, after the last, layer-2 tile 0
     auto chunk1 = [&](auto cc) __attribute__((always_inline)) {
       constexpr int c = decltype(cc)::value;
       constexpr bool LAST = c + 1 == L1_CHUNKS;
       constexpr int NPF = LAST ? PF2 : PF1;
       const float4* wb = wbuf[buf];
-      staged((LAST ? p2 : p1 + (c + 1) * C1_CHUNK4) + tid, std::integral_constant<int, NPF>(), std::integral_constant<bool, LAST>(), [&](auto sg) {
-        constexpr int tt = decltype(sg)::value, t = 4 * c + tt;
-        f32x16 acc;
-#pragma unroll
-        for (int g = 0; g < 4; g++) {
-          const float4 b = sm4[(32 * t + 8 * g + 4 * h) / 4];
-          acc[4 * g + 0] = b.x, acc[4 * g + 1] = b.y, acc[4 * g + 2] = b.z, acc[4 * g + 3] = b.w;
-        }
-#pragma unroll
-        for (int sq = 0; sq < C1_STEPS4; sq++) {
-          const float4 a = wb[(tt * C1_STEPS4 + sq) * 64 + lane];
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, xb[4 * sq + 0], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, xb[4 * sq + 1], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, xb[4 * sq + 2], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, xb[4 * sq + 3], acc, 0, 0, 0);
-        }
-#pragma unroll
-        for (int v = 0; v < 16; v++) h1[t * 16 + v] = fmaxf(acc[v], 0.0f);
-        m1[t >> 1] |= relu_bits(acc) << (16 * (t & 1));
-        if constexpr (tt & 1) formed(m1[t >> 1]);
+      staged<CRITIC_THREADS, NPF, LAST, float4>(wbuf, buf, L, (LAST ? p2 : p1 + (c + 1) * C1_CHUNK4) + tid, [&](auto sg) __attribute__((always_inline)) {
+        constexpr int tt = decltype(sg)::value;
+        layer1_tile<C1_STEPS4, tt, 4 * c + tt, HT>(wb, sm4, L, xb, h1, m1);
       });
     };
     chunk1(std::integral_constant<int, 0>());
@@ -225,16 +160,8 @@ __global__ void __launch_bounds__(CRITIC_THREADS, (HT <= 4 ? 2 : 1)) critic_grad
         const float4 b = sm4[(HP + 32 * t + 8 * g + 4 * h) / 4];
         acc[4 * g + 0] = b.x, acc[4 * g + 1] = b.y, acc[4 * g + 2] = b.z, acc[4 * g + 3] = b.w;
       }
-      staged(next, std::integral_constant<int, PF2>(), std::true_type(), [&](auto sg) {
-        constexpr int S = decltype(sg)::value;
-#pragma unroll
-        for (int sq = S * HT; sq < (S + 1) * HT; sq++) {  // sq = 4 u + g: registers 4 g .. 4 g + 3 of layer-1 tile u
-          const float4 a = wb[sq * L2_ROW4];
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, h1[4 * sq + 0], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, h1[4 * sq + 1], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, h1[4 * sq + 2], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, h1[4 * sq + 3], acc, 0, 0, 0);
-        }
+      staged<CRITIC_THREADS, PF2, true, float4>(wbuf, buf, L, next, [&](auto sg) __attribute__((always_inline)) {
+        layer2_forward_quarter<HT, decltype(sg)::value>(wb, h1, acc);
       });
 #pragma unroll
       for (int g = 0; g < 4; g++) {
@@ -263,27 +190,13 @@ __global__ void __launch_bounds__(CRITIC_THREADS, (HT <= 4 ? 2 : 1)) critic_grad
 #pragma unroll
       for (int v = 0; v < 16; v++) dacc[u][v] = 0.0f;
     auto back2 = [&](int t, const float4* next, auto npf, auto next_is_tile) __attribute__((always_inline)) {
-      uint32_t word = 0;
-#pragma unroll
-      for (int i = 0; i < MW; i++) word = (t >> 1) == i ? m2[i] : word;
-      const uint32_t bits = word >> (16 * (t & 1));
+      const uint32_t bits = mask_tile(m2, t);
       const float4* wb = wbuf[buf] + abase;
-      staged(next, npf, next_is_tile, [&](auto sg) {
+      staged<CRITIC_THREADS, decltype(npf)::value, decltype(next_is_tile)::value, float4>(wbuf, buf, L, next, [&](auto sg) __attribute__((always_inline)) {
         constexpr int g = decltype(sg)::value;
         const float4 wq = sm4[(2 * HP + 32 * t + 8 * g + 4 * h) / 4];
         const float wqr[4] = {wq.x, wq.y, wq.z, wq.w};
-#pragma unroll
-        for (int r = 0; r < 4; r++) {  // one MFMA step: k = h is neuron 32 t + 8 g + 4 h + r of layer 2
-          const float b = (bits >> (4 * g + r)) & 1u ? wqr[r] : 0.0f;
-#pragma unroll
-          for (int U = 0; U < HT / 4; U++) {
-            const float4 a = wb[16 * U * L2_ROW4 + 8 * g + r];  // W1[32 t + 8 g + 4 h + r][128 U + 4 jj + c], c = 0 .. 3
-            dacc[4 * U + 0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b, dacc[4 * U + 0], 0, 0, 0);
-            dacc[4 * U + 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b, dacc[4 * U + 1], 0, 0, 0);
-            dacc[4 * U + 2] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b, dacc[4 * U + 2], 0, 0, 0);
-            dacc[4 * U + 3] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b, dacc[4 * U + 3], 0, 0, 0);
-          }
-        }
+        layer2_backward_quarter<HT, g>(wb, [&](int r) __attribute__((always_inline)) { return (bits >> (4 * g + r)) & 1u ? wqr[r] : 0.0f; }, dacc);
       });
     };
 #pragma unroll 1
