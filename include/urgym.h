@@ -882,6 +882,121 @@ typedef struct urgym_sac_policy_args {
  * group is absent: leave it 0). */
 int urgym_sac_policy_terms(void* handle, const urgym_sac_policy_args* args, void* stream);
 
+/* ---- the SAC training loop in ONE call (train.py:40-60: model.learn(total_timesteps) alternates collection and gradient steps and
+ * does not return to the caller in between).  urgym_sac_train enqueues num_iterations x (one collection, G updates) of the calls
+ * above on `stream`: no new kernel, no new arithmetic, only the host side of the existing launches, checked once.  Added WITHIN ABI
+ * version 4: no struct above changed, URGYM_ABI_VERSION did not move, urgym_sac_train is found by lookup.  The library keeps NO state:
+ * the ring's cursor and fill level, the draw counters and the Adam step count are the caller's, handed in through the schedule. */
+
+/* Where a call starts and how long it runs.  Iteration i (0 <= i < num_iterations), with K = steps_per_iteration, G =
+ * updates_per_iteration and C = capacity_steps, as ur_gym_amd/csrc/urgym_sac_schedule.h derives it and
+ * ur_gym_amd.evaluation.training_schedule restates it:
+ *   collection   K steps from slot (first_slot + i K) % C with draws collect_first_draw + i K + k, k < K;
+ *                mode URGYM_SAMPLE_UNIFORM for i < uniform_iterations, URGYM_SAMPLE_GAUSSIAN after; none where K == 0
+ *   ring view    of its updates, after its collection: cursor = (first_slot + (i + 1) K) % C, filled = min(C, filled_steps + (i + 1) K),
+ *                oldest_slot = (cursor - filled) mod C
+ *   updates      none for i < idle_iterations, G otherwise; update u, counted over the whole call across the iterations that are not
+ *                idle: gather draw = update_first_draw + u (urgym_replay_sample and a' ~ pi(.|s')), policy draw = the same | 2^63,
+ *                Adam step = first_step + u, loss slot = u
+ *   afterwards   the caller's cursor is (first_slot + num_iterations K) % C and its fill level min(C, filled_steps + num_iterations K)
+ * Refused: num_iterations < 1; a negative count (K, G, uniform_iterations, idle_iterations); K and G both 0; capacity_steps <= 0 or
+ * other than the ring's; first_slot outside [0, C); filled_steps outside [0, C] (0 is allowed: nothing collected yet); an update that
+ * would see an empty ring (filled_steps == 0 with K == 0); first_step < 1, or first_step + the number of updates beyond int64;
+ * update_first_draw + the number of updates > 2^63. */
+typedef struct urgym_sac_schedule {
+  int32_t first_slot;           /* the ring's cursor */
+  int32_t filled_steps;         /* valid slots before the call */
+  int32_t capacity_steps;       /* C, the ring's */
+  int32_t num_iterations;       /* >= 1 */
+  int32_t steps_per_iteration;  /* K >= 0 */
+  int32_t updates_per_iteration; /* G >= 0 */
+  int32_t uniform_iterations;   /* U: the first U iterations collect with URGYM_SAMPLE_UNIFORM */
+  int32_t idle_iterations;      /* I: the first I iterations run no update */
+  uint64_t collect_first_draw;  /* draw of the first collection pass */
+  uint64_t update_first_draw;   /* draw of the first update */
+  int64_t first_step;           /* 1-based Adam step of the first update */
+} urgym_sac_schedule;
+
+/* Everything the thirteen launches of an update and the collection take.  All pointers are DEVICE pointers owned by the caller (the
+ * three objects excepted), float32 where float, `count` = M rows; all are required except batch.truncated, batch.is_success and
+ * batch.index (and the three loss arrays of a call without an update).  The scratch is reused by every update of the call; no two tensors may overlap (not checked). */
+typedef struct urgym_sac_learner {
+  void* actor;   /* urgym_actor_create's, with its log_std head */
+  void* online;  /* urgym_critic_create's: the critic that is stepped */
+  void* target;  /* another critic of online's shape: bootstraps, follows by Polyak averaging */
+  urgym_actor_adam actor_adam;    /* its grad tensors are the ones urgym_actor_parameter_gradients writes */
+  urgym_critic_adam critic_adam;  /* its grad tensors are the ones urgym_critic_parameter_gradients writes */
+  void* actor_workspace;          /* urgym_actor_parameter_gradients_workspace(actor, count) bytes at least, 16-byte aligned */
+  uint64_t actor_workspace_bytes;
+  void* critic_workspace;         /* urgym_critic_parameter_gradients_workspace(online, count) bytes at least, 16-byte aligned */
+  uint64_t critic_workspace_bytes;
+  float* log_ent_coef;            /* [1] the temperature's state, stepped in place */
+  float* exp_avg;                 /* [1] */
+  float* exp_avg_sq;              /* [1] */
+  urgym_replay_ring ring;
+  urgym_replay_batch batch;       /* [count] rows each: the minibatch */
+  float* next_actions;            /* [count][6]  a' ~ pi(.|s') */
+  float* next_log_prob;           /* [count] */
+  float* target_value;            /* [count]     urgym_critic_evaluate's target of `target`, without the entropy term */
+  float* y;                       /* [count]     urgym_sac_entropy_step's y_out */
+  float* action_pi;               /* [count][6]  the policy's action on the batch rows */
+  float* log_prob;                /* [count] */
+  float* q;                       /* [2][count]  urgym_critic_parameter_gradients' q */
+  float* q_min;                   /* [count]     urgym_critic_action_gradient's, at action_pi */
+  float* dqmin_da;                /* [count][6] */
+  float* d_action;                /* [count][6]  urgym_sac_policy_terms' d_action_out */
+  float* d_log_prob;              /* [count]     urgym_sac_entropy_step's d_log_prob_out */
+  float* ent_coef;                /* [1]         alpha of the running update */
+  float* critic_loss;             /* [number of updates of the call]: update u writes slot u */
+  float* actor_loss;              /* the same */
+  float* ent_coef_loss;           /* the same */
+  int32_t count;                  /* M, the batch size: in [1, 65536] */
+  int32_t reserved0;              /* must be 0 */
+  uint64_t seed;                  /* of the policy noise during collection */
+  uint64_t update_seed;           /* of the gather and the two policy draws of an update */
+  float gamma;                    /* finite */
+  float tau;                      /* in (0, 1] */
+  float target_entropy;           /* finite */
+  double lr;                      /* urgym_adam_hyper without step: one set for the actor, the critics and the temperature */
+  double beta1;
+  double beta2;
+  double eps;
+} urgym_sac_learner;
+
+/* Afterwards the bound buffers, the ring, every parameter, moment and packed buffer, the temperature state, the scratch and the loss
+ * slots hold BIT FOR BIT what this sequence of the calls above would have left, per iteration:
+ *   urgym_rollout_collect(actor, {mode, seed, draw}, K, ring, slot)                                       skipped where K == 0
+ *   and for each update, in this order (the order of SACLearner._update_on_device), M = count:
+ *     urgym_replay_sample(ring, oldest_slot, filled_steps, update_seed, gather draw, M, batch)
+ *     urgym_actor_sample_rows(actor, {GAUSSIAN, update_seed, gather draw}, batch.next_*, M, next_actions, next_log_prob)
+ *     urgym_critic_evaluate(target, batch.next_* with next_actions, M, {batch.reward, batch.terminated, next_log_prob, gamma,
+ *                           ent_coef = 0}, {target = target_value})
+ *     urgym_actor_sample_rows(actor, {GAUSSIAN, update_seed, policy draw}, the batch rows, M, action_pi, log_prob)
+ *     urgym_sac_entropy_step({log_prob, the state, ent_coef, ent_coef_loss + u, target_value, next_log_prob, batch.terminated, y,
+ *                            d_log_prob, scale = (float)(1.0 / M)}, hp)
+ *     urgym_critic_parameter_gradients(online, the batch rows with batch.action, M, target = y, scale = (float)(1.0 / M),
+ *                                      {critic_adam.grad, q}, critic_workspace)
+ *     urgym_critic_adam_step(online, target, critic_adam, hp, tau)
+ *     urgym_critic_action_gradient(online, the batch rows with action_pi, M, {dqmin_da, q_min})
+ *     urgym_sac_policy_terms({ent_coef, dqmin_da, d_action, scale = (float)(-1.0 / M), q, y, critic_loss + u, log_prob, q_min,
+ *                            actor_loss + u})
+ *     urgym_actor_parameter_gradients(actor, {GAUSSIAN, update_seed, policy draw}, the batch rows, M, {d_action, d_log_prob},
+ *                                     {actor_adam.grad}, actor_workspace)
+ *     urgym_actor_adam_step(actor, actor_adam, hp)
+ *   with hp = {lr, beta1, beta2, eps, step = the update's Adam step}; its coefficients are urgym_adam_coefficients'.
+ * 3 K + 1 launches per collection and 13 per update (15 above 1024 rows), the launches of those calls and no other.
+ *
+ * EVERYTHING is validated before the first launch: the schedule's refusals above, every refusal of every call of the sequence, and
+ * the call's own -- NULL handle, learner or schedule; a NULL required pointer; reserved0 != 0; online == target;
+ * schedule->capacity_steps other than ring.capacity_steps.  The caps of the gradient kernels apply (hidden_width at most 256, count at
+ * most 65536).  After a refusal (URGYM_ERR_ARG; URGYM_ERR_STATE before urgym_bind, or before the first reset where K > 0) nothing has
+ * been launched and nothing written.  A call whose schedule holds no update (G == 0, or every iteration idle) composes no update call:
+ * only the required pointers, the schedule and what its collections take are checked.
+ * The call never allocates and never synchronises with the host.  It returns when everything is enqueued; where the stream's queue
+ * is full the runtime may block the caller until launches drain.  If a launch fails midway (URGYM_ERR_HIP) the call has the semantics
+ * of urgym_rollout_collect: launches already enqueued stay enqueued, and urgym_last_error names the iteration and the stage. */
+int urgym_sac_train(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, void* stream);
+
 /* Verification aid, not a hot path: synchronises the device, then copies the object's packed buffer (the kernel's own layout,
  * ur_gym_amd/csrc/urgym_pack_map.h) to host_out and stores its length in floats in *count.  host_out == NULL only reports *count;
  * otherwise capacity (in floats) must be at least that.  Refused: NULL handle / object / count, an object of another handle,

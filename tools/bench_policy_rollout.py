@@ -64,6 +64,14 @@ process, each ending in a device synchronise; wall time per update, medians.  Ba
 spread of the old route's windows.  The ratio is reported whatever it is.
     python tools/bench_policy_rollout.py --entropy --windows 8 --launches 200 --out profiles/policy_rollout/dyn65536_entropy.json
 
+--native measures the same update (batch 256, H = 256, device_entropy) two ways: the thirteen-call
+SACLearner.update, and SACLearner.train(steps_per_iteration=0, updates_per_iteration=--launches), one native call per window.
+Alternating windows in one process, each ending in a device synchronise; median, min and max of the wall time per update.  Bar: the
+native route's median is not above the thirteen-call route's by more than the spread (max - min) of that route's own windows.  A second
+pair, `loop`, runs one collection step per 4 updates on both routes (--launches / 4 iterations per window).  With --native-only the
+tool runs --launches native updates --windows times and nothing else: the program of a kernel-trace run.
+    python tools/bench_policy_rollout.py --native --windows 8 --launches 200 --out profiles/policy_rollout/dyn65536_native.json
+
 With --refresh: what it costs to hand new weights to a device actor / critic, at hidden width 256 and 512.
 `actor_load`, `critic_load_tau1` and `critic_load_polyak` (tau = 0.005) are load_parameters from device tensors, one launch each;
 `*_host_route` is the only route there was before: every tensor .cpu().numpy(), destroy and create the object (the actor's head by
@@ -937,6 +945,97 @@ def entropy_mode(args):
             f.write(line + "\n")
 
 
+def native_mode(args):
+    """--native: the thirteen-call SACLearner.update against SACLearner.train, one native call per window (see above)."""
+    import torch
+
+    from ur_gym_amd import make_vec
+    from ur_gym_amd.evaluation import DeviceReplay
+    from ur_gym_amd.training import SACLearner
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_policy_rollout.py measures on a GPU; none is visible")
+    dev, n, per_window = "cuda:0", min(args.num_envs, 4096), args.launches  # an update does not depend on the number of envs
+    env = make_vec(args.env, num_envs=n, device=dev, seed=0, auto_reset=True)
+    env.reset(seed=0)
+    sync = lambda: torch.cuda.synchronize(env.device)  # noqa: E731
+    options = dict(device_action_gradient=True, device_critic_gradient=True, device_actor_gradient=True, device_optimizer=True, device_entropy=True)
+    learners = {}
+    for label in ("thirteen_calls", "native"):
+        learner = SACLearner(env, seed=0, batch_size=256, hidden_width=256, learning_starts=0, **options)
+        replay = DeviceReplay(env, 64)
+        learner.collect(replay, 4)
+        learners[label] = (learner, replay, [0])
+
+    def updates(label, count):
+        learner, replay, draw = learners[label]
+        if label == "native":
+            learner.train(replay, 1, 0, count, seed=1, first_draw=draw[0] + 1)
+            draw[0] += count
+        else:
+            for _ in range(count):
+                draw[0] += 1
+                learner.update(replay, 1, draw[0])
+
+    def loop(label, iterations, per_step=4):
+        learner, replay, draw = learners[label]
+        if label == "native":
+            learner.train(replay, iterations, 1, per_step, seed=1, first_draw=draw[0] + 1)
+            draw[0] += iterations * per_step
+        else:
+            for _ in range(iterations):
+                learner.collect(replay, 1)
+                for _ in range(per_step):
+                    draw[0] += 1
+                    learner.update(replay, 1, draw[0])
+
+    def window(fn, label, count, per_update):
+        sync()
+        t0 = time.perf_counter()
+        fn(label, count)
+        sync()
+        return (time.perf_counter() - t0) * 1e6 / per_update
+
+    if args.native_only:
+        for _ in range(args.windows):
+            updates("native", per_window)
+        sync()
+        print(json.dumps({"tool": "bench_policy_rollout --native --native-only", "updates": args.windows * per_window}))
+        for learner, _, _ in learners.values():
+            learner.close()
+        env.close()
+        return
+    pairs = {}
+    for pair, fn, count in (("updates", updates, per_window), ("loop", loop, max(1, per_window // 4))):
+        per_update = count if pair == "updates" else count * 4
+        for label in learners:
+            fn(label, 10 if pair == "updates" else 3)
+        wdw = {label: [] for label in learners}
+        for _ in range(args.windows):
+            for label in learners:
+                wdw[label].append(window(fn, label, count, per_update))
+        med = {k: float(np.median(v)) for k, v in wdw.items()}
+        spread = float(max(wdw["thirteen_calls"]) - min(wdw["thirteen_calls"]))
+        pairs[pair] = {"us_per_update_median": med, "us_per_update_min": {k: float(min(v)) for k, v in wdw.items()},
+                       "us_per_update_max": {k: float(max(v)) for k, v in wdw.items()},
+                       "us_per_update_windows": {k: [round(x, 2) for x in v] for k, v in wdw.items()}, "thirteen_calls_us_spread": spread,
+                       "ratio_native_over_thirteen_calls": med["native"] / med["thirteen_calls"],
+                       "not_slower": med["native"] <= med["thirteen_calls"] + spread}
+    pairs["loop"]["collection_steps_per_window"] = max(1, per_window // 4)
+    pairs["loop"]["updates_per_collection_step"] = 4
+    result = {"tool": "bench_policy_rollout --native", "env": args.env, "num_envs": n, "windows": args.windows, "updates_per_window": per_window,
+              "batch": 256, "hidden_width": 256, "device": torch.cuda.get_device_name(0), **pairs, "not_slower_overall": pairs["updates"]["not_slower"]}
+    for learner, _, _ in learners.values():
+        learner.close()
+    env.close()
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--env", default="UR5DynReach-v1", choices=sorted(ACTOR_NPZ))
@@ -962,8 +1061,12 @@ def main():
     ap.add_argument("--actor-gradient", action="store_true", help="measure the actor's parameter gradients (two or three launches) against torch autograd (see above)")
     ap.add_argument("--optimizer", action="store_true", help="measure the Adam step kernels (one launch each) against torch's Adam.step followed by the reloads, and the learner's update with and without them")
     ap.add_argument("--entropy", action="store_true", help="measure the learner's update with device_optimizer only against the same plus device_entropy (see above)")
+    ap.add_argument("--native", action="store_true", help="measure the thirteen-call update against SACLearner.train, one native call per window (see above)")
+    ap.add_argument("--native-only", action="store_true", help="--native: run only the native updates, --windows x --launches of them (for a kernel trace)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.native:
+        return native_mode(args)
     if args.entropy:
         return entropy_mode(args)
     if args.optimizer:

@@ -5,7 +5,8 @@ environment, as model_test.py evaluates) every so many updates.
     python tools/train_sac.py --env UR5OriReach-v1 --num-envs 1024 --steps 2000 --updates-per-step 4 --eval-every 200
 
 One loop trip = one env step of all N envs into the ring, then `--updates-per-step` gradient steps.  Prints one JSON line per
-evaluation.  No checkpoint is written.
+evaluation.  No checkpoint is written.  With --native (and --device-entropy and the options it needs) the trips between two
+evaluations are ONE native call, SACLearner.train: the same launches, bit for bit, with no Python between them.
 """
 import argparse
 import json
@@ -43,6 +44,9 @@ def main():
     ap.add_argument("--device-entropy", action="store_true",
                     help="step the entropy coefficient and form its uses and the three loss values with two HIP launches: no torch operation "
                          "is left in an update but allocations and views (needs --device-optimizer)")
+    ap.add_argument("--native", action="store_true",
+                    help="run the loop between two evaluations as ONE native call (SACLearner.train): no Python between the launches "
+                         "(needs --device-entropy)")
     args = ap.parse_args()
 
     import torch
@@ -63,7 +67,29 @@ def main():
     eval_actor = DeviceActor(host_arrays(learner.actor.tensors()), test_env)  # actors belong to the environment they were made for
     replay = DeviceReplay(env, args.capacity)
     updates, t0 = 0, time.perf_counter()
-    for step in range(args.steps):
+
+    def evaluate():
+        eval_actor.load_parameters(learner.actor.tensors())
+        test_env.reset(seed=args.seed + 1)
+        res = run_closed_loop_device(test_env, eval_actor)
+        print(json.dumps({"updates": updates, "env_steps": learner.env_steps * env.num_envs, "seconds": round(time.perf_counter() - t0, 1),
+                          "mean_episode_return": res["mean_episode_reward"], "success_rate_percent": res["success_rate_percent"]}), flush=True)
+
+    step = 0
+    while args.native and step < args.steps:
+        # as many loop trips as reach the next evaluation, in one call (warm-up trips run no update, so a call may fall short of it and
+        # the next one goes on); an evaluation falls at the end of the trip that passes a multiple of --eval-every
+        per_trip = max(1, args.updates_per_step)
+        trips = min(args.steps - step, -(-(args.eval_every - updates % args.eval_every) // per_trip))
+        before = learner.adam_state["step"]
+        learner.train(replay, trips, 1, args.updates_per_step, seed=args.seed, first_draw=updates)
+        step += trips
+        done = learner.adam_state["step"] - before
+        passed = (updates + done) // args.eval_every > updates // args.eval_every
+        updates += done
+        if passed:
+            evaluate()
+    for step in range(step, args.steps):  # the Python loop (every trip of it where --native is off)
         learner.collect(replay, 1)
         if learner.env_steps * env.num_envs < learner.hp["learning_starts"]:
             continue
@@ -71,11 +97,7 @@ def main():
             learner.update(replay, args.seed, updates)
             updates += 1
             if updates % args.eval_every == 0:
-                eval_actor.load_parameters(learner.actor.tensors())
-                test_env.reset(seed=args.seed + 1)
-                res = run_closed_loop_device(test_env, eval_actor)
-                print(json.dumps({"updates": updates, "env_steps": learner.env_steps * env.num_envs, "seconds": round(time.perf_counter() - t0, 1),
-                                  "mean_episode_return": res["mean_episode_reward"], "success_rate_percent": res["success_rate_percent"]}), flush=True)
+                evaluate()
     eval_actor.close()
     learner.close()
     test_env.close()

@@ -313,6 +313,38 @@ class SacPolicyArgs(C.Structure):
                 ("log_prob", C.POINTER(C.c_float)), ("q_min", C.POINTER(C.c_float)), ("actor_loss_out", C.POINTER(C.c_float))]
 
 
+class SacSchedule(C.Structure):
+    """urgym_sac_schedule: where a urgym_sac_train call starts and how long it runs (ur_gym_amd/csrc/urgym_sac_schedule.h)."""
+    _fields_ = [(name, C.c_int32) for name in ("first_slot", "filled_steps", "capacity_steps", "num_iterations", "steps_per_iteration",
+                                                "updates_per_iteration", "uniform_iterations", "idle_iterations")] + \
+               [("collect_first_draw", C.c_uint64), ("update_first_draw", C.c_uint64), ("first_step", C.c_int64)]
+
+
+# urgym_sac_learner's scratch after the batch: name -> shape given the batch size M; float32, all required, reused by every update
+SAC_LEARNER_SCRATCH = [
+    ("next_actions", lambda M: (M, 6)), ("next_log_prob", lambda M: (M,)), ("target_value", lambda M: (M,)), ("y", lambda M: (M,)),
+    ("action_pi", lambda M: (M, 6)), ("log_prob", lambda M: (M,)), ("q", lambda M: (2, M)), ("q_min", lambda M: (M,)),
+    ("dqmin_da", lambda M: (M, 6)), ("d_action", lambda M: (M, 6)), ("d_log_prob", lambda M: (M,)), ("ent_coef", lambda M: (1,)),
+]
+SAC_LEARNER_STATE = ("log_ent_coef", "exp_avg", "exp_avg_sq")         # the temperature's three [1] tensors
+SAC_LEARNER_LOSSES = ("critic_loss", "actor_loss", "ent_coef_loss")  # one float per update of the call each
+SAC_LEARNER_OPTIONAL = ("batch.truncated", "batch.is_success", "batch.index")  # the only pointers of the struct that may be NULL
+SAC_TRAIN_MAX_COUNT = 65536  # the row cap of the gradient kernels and of the SAC terms
+
+
+class SacLearner(C.Structure):
+    """urgym_sac_learner: everything the launches of a collection and an update take (objects, Adam tensors, workspaces, the
+    temperature's state, the ring, the batch and its scratch, the loss slots, the numbers)."""
+    _fields_ = [("actor", C.c_void_p), ("online", C.c_void_p), ("target", C.c_void_p), ("actor_adam", ActorAdam), ("critic_adam", CriticAdam),
+                ("actor_workspace", C.c_void_p), ("actor_workspace_bytes", C.c_uint64), ("critic_workspace", C.c_void_p),
+                ("critic_workspace_bytes", C.c_uint64)] + \
+               [(name, C.POINTER(C.c_float)) for name in SAC_LEARNER_STATE] + [("ring", ReplayRing), ("batch", ReplayBatch)] + \
+               [(name, C.POINTER(C.c_float)) for name, _ in SAC_LEARNER_SCRATCH] + [(name, C.POINTER(C.c_float)) for name in SAC_LEARNER_LOSSES] + \
+               [("count", C.c_int32), ("reserved0", C.c_int32), ("seed", C.c_uint64), ("update_seed", C.c_uint64), ("gamma", C.c_float),
+                ("tau", C.c_float), ("target_entropy", C.c_float), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
+                ("eps", C.c_double)]
+
+
 # Every symbol include/urgym.h declares (tests check that the built library exports each of them).
 EXPORTED_SYMBOLS = [
     "urgym_abi_version",
@@ -349,6 +381,7 @@ EXPORTED_SYMBOLS = [
     "urgym_critic_adam_step",
     "urgym_sac_entropy_step",
     "urgym_sac_policy_terms",
+    "urgym_sac_train",
     "urgym_actor_read_packed",
     "urgym_critic_read_packed",
     "urgym_refresh",

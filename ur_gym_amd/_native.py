@@ -89,6 +89,7 @@ def lib():
     L.urgym_critic_adam_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(_abi.CriticAdam), C.POINTER(_abi.AdamHyper), C.c_float, C.c_void_p]
     L.urgym_sac_entropy_step.argtypes = [C.c_void_p, C.POINTER(_abi.SacEntropyArgs), C.POINTER(_abi.AdamHyper), C.c_void_p]
     L.urgym_sac_policy_terms.argtypes = [C.c_void_p, C.POINTER(_abi.SacPolicyArgs), C.c_void_p]
+    L.urgym_sac_train.argtypes = [C.c_void_p, C.POINTER(_abi.SacLearner), C.POINTER(_abi.SacSchedule), C.c_void_p]
     L.urgym_actor_read_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.urgym_critic_read_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.urgym_refresh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]

@@ -1,5 +1,5 @@
 // urgym_policy_abi.hip — the learner's half of the C-ABI of include/urgym.h: actors (create / forward / sample / rollouts), the replay
-// ring, the weight reloads, the twin critic and its two gradients, the actor's parameter gradients, the Adam steps, SAC's entropy step and loss terms.  Host code only: every check is made here, before the first launch,
+// ring, the weight reloads, the twin critic and its two gradients, the actor's parameter gradients, the Adam steps, SAC's entropy step and loss terms, and the training loop that composes them in one call (urgym_sac_train; its index arithmetic is urgym_sac_schedule.h).  Host code only: every check is made here, before the first launch,
 // and every launch goes through urgym_actor.h, urgym_critic.h, urgym_replay.h, urgym_weights.h, urgym_adam.h and urgym_sac_terms.h, or through do_step of urgym_hip.hip
 // (urgym_handle.h).  No kernel lives in this unit, so adding a check here leaves the step kernels' object file alone.
 #include <hip/hip_runtime.h>
@@ -18,6 +18,7 @@
 #include "urgym_replay.h"
 #include "urgym_adam.h"
 #include "urgym_sac_terms.h"
+#include "urgym_sac_schedule.h"
 
 using namespace urgym;
 
@@ -282,23 +283,31 @@ const char* adam_hyper_refusal(const urgym_adam_hyper* hp) {
 
 AdamCoef adam_coef(const urgym_adam_hyper& hp) { return adam_coefficients(hp.lr, hp.beta1, hp.beta2, hp.eps, hp.step); }
 
-}  // namespace
+// ---- the checking half of every entry point urgym_sac_train composes.  Each makes ALL the checks of its entry point, in its order and
+// with its refusal texts (`who` names the entry point), launches nothing, and leaves what the launching half needs: the launch struct of
+// the kernel unit's seam header, filled.  The entry points below are check + launch; urgym_sac_train runs every check first.
 
-extern "C" {
+// what urgym_actor_sample_rows launches
+struct SampleRows {
+  Actor* a;
+  ActorEnv env;
+  float* actions;
+  ActorSample smp;
+};
+// what the two Adam steps launch, but for the coefficients
+struct ActorAdamStep {
+  Actor* a;
+  ActorPacked buf;
+  AdamTensors<PACK_ACTOR_TENSORS> T;
+};
+struct CriticAdamStep {
+  CriticPacked buf, target_buf;
+  bool has_target;
+  float tau;
+  AdamTensors<2 * PACK_CRITIC_TENSORS> T;
+};
 
-// ---- Adam on the device (urgym_adam.hip): everything is checked here, before the launch
-int urgym_adam_coefficients(const urgym_adam_hyper* hp, float out[7]) {
-  if (const char* what = adam_hyper_refusal(hp)) return fail_in(nullptr, URGYM_ERR_ARG, "urgym_adam_coefficients", what);
-  if (!out) return fail(nullptr, URGYM_ERR_ARG, "urgym_adam_coefficients: null out");
-  const AdamCoef c = adam_coef(*hp);
-  out[0] = c.b1, out[1] = c.omb1, out[2] = c.b2, out[3] = c.omb2, out[4] = c.step_size, out[5] = c.bc2_sqrt, out[6] = c.eps;
-  return URGYM_OK;
-}
-
-int urgym_actor_adam_step(void* handle, void* actor, const urgym_actor_adam* t, const urgym_adam_hyper* hp, void* stream) {
-  const char* who = "urgym_actor_adam_step";
-  Handle* h = (Handle*)handle;
-  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+int check_actor_adam(Handle* h, void* actor, const urgym_actor_adam* t, const urgym_adam_hyper* hp, const char* who, ActorAdamStep* out) {
   Actor* a = member(h->actors, actor);
   if (!a) return fail_in(h, URGYM_ERR_ARG, who, "not an actor of this handle (actors belong to the handle they were created with)");
   if (!t) return fail_in(h, URGYM_ERR_ARG, who, "null tensors");
@@ -306,7 +315,7 @@ int urgym_actor_adam_step(void* handle, void* actor, const urgym_actor_adam* t, 
   const ActorPacked buf = actor_packed(a);
   if (t->in_features != buf.in_features || t->hidden_width != buf.hidden)
     return failf(h, URGYM_ERR_ARG, "%s: tensors are %d -> %d, the actor is %d -> %d", who, t->in_features, t->hidden_width, buf.in_features, buf.hidden);
-  AdamTensors<PACK_ACTOR_TENSORS> T;
+  AdamTensors<PACK_ACTOR_TENSORS>& T = out->T;
   {
     const urgym_actor_tensors &p = t->param, &m = t->exp_avg, &v = t->exp_avg_sq;
     const urgym_actor_tensors_const& g = t->grad;
@@ -320,21 +329,16 @@ int urgym_actor_adam_step(void* handle, void* actor, const urgym_actor_adam* t, 
     }
   }
   if (const char* what = adam_hyper_refusal(hp)) return fail_in(h, URGYM_ERR_ARG, who, what);
-  HIP_TRY(h, hipSetDevice(h->device));
-  actor_adam_launch(buf, T, adam_coef(*hp), (hipStream_t)stream);
-  HIP_TRY(h, hipGetLastError());
-  actor_mark_log_std(a);  // as urgym_actor_load with both head pointers
+  out->a = a, out->buf = buf;
   return URGYM_OK;
 }
 
-int urgym_critic_adam_step(void* handle, void* online, void* target_or_NULL, const urgym_critic_adam* t, const urgym_adam_hyper* hp, float tau, void* stream) {
-  const char* who = "urgym_critic_adam_step";
-  Handle* h = (Handle*)handle;
-  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+int check_critic_adam(Handle* h, void* online, void* target_or_NULL, const urgym_critic_adam* t, const urgym_adam_hyper* hp, float tau, const char* who,
+                      CriticAdamStep* out) {
   Critic* c = member(h->critics, online);
   if (!c) return fail_in(h, URGYM_ERR_ARG, who, "not a critic of this handle (critics belong to the handle they were created with)");
   const CriticPacked buf = critic_packed(c);
-  CriticPacked target_buf;
+  CriticPacked& target_buf = out->target_buf;
   if (target_or_NULL) {
     if (target_or_NULL == online) return fail_in(h, URGYM_ERR_ARG, who, "the target is the online critic itself");
     Critic* tc = member(h->critics, target_or_NULL);
@@ -348,7 +352,7 @@ int urgym_critic_adam_step(void* handle, void* online, void* target_or_NULL, con
   if (t->reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "urgym_critic_adam.reserved0 must be 0");
   if (t->in_features != buf.in_features || t->hidden_width != buf.hidden)
     return failf(h, URGYM_ERR_ARG, "%s: tensors are %d -> %d, the critic is %d -> %d", who, t->in_features, t->hidden_width, buf.in_features, buf.hidden);
-  AdamTensors<2 * PACK_CRITIC_TENSORS> T;
+  AdamTensors<2 * PACK_CRITIC_TENSORS>& T = out->T;
   for (int net = 0; net < 2; net++) {
     const urgym_q_network_grad &p = t->param[net], &m = t->exp_avg[net], &v = t->exp_avg_sq[net];
     const urgym_q_network_dev& g = t->grad[net];
@@ -363,17 +367,12 @@ int urgym_critic_adam_step(void* handle, void* online, void* target_or_NULL, con
     }
   }
   if (const char* what = adam_hyper_refusal(hp)) return fail_in(h, URGYM_ERR_ARG, who, what);
-  HIP_TRY(h, hipSetDevice(h->device));
-  critic_adam_launch(buf, target_or_NULL ? &target_buf : nullptr, T, adam_coef(*hp), tau, (hipStream_t)stream);
-  return launched(h);
+  out->buf = buf, out->has_target = target_or_NULL != nullptr, out->tau = tau;
+  return URGYM_OK;
 }
 
-// ---- SAC's entropy coefficient on the device (urgym_sac_terms.hip): everything is checked here, before the launch
-int urgym_sac_entropy_step(void* handle, const urgym_sac_entropy_args* args, const urgym_adam_hyper* hp, void* stream) {
+int check_entropy_step(Handle* h, const urgym_sac_entropy_args* args, const urgym_adam_hyper* hp, const char* who, SacEntropyCall* out) {
   static_assert(URGYM_SAC_TERMS_MAX_COUNT == SAC_TERMS_MAX_COUNT, "include/urgym.h");
-  const char* who = "urgym_sac_entropy_step";
-  Handle* h = (Handle*)handle;
-  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
   if (!args) return fail_in(h, URGYM_ERR_ARG, who, "null args");
   const urgym_sac_entropy_args& a = *args;
   if (a.reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_entropy_args.reserved0 must be 0");
@@ -387,22 +386,17 @@ int urgym_sac_entropy_step(void* handle, const urgym_sac_entropy_args* args, con
   if ((given != 0 && given != 3) || (given == 0 && a.terminated))
     return fail_in(h, URGYM_ERR_ARG, who, "the target group is half given: target_in, next_log_prob and y_out go together (terminated only with them)");
   if (const char* what = adam_hyper_refusal(hp)) return fail_in(h, URGYM_ERR_ARG, who, what);
-  SacEntropyCall c;
+  SacEntropyCall& c = *out;
   c.count = a.count, c.target_entropy = a.target_entropy, c.gamma = a.gamma, c.scale = a.scale;
   c.log_prob = a.log_prob, c.log_ent_coef = a.log_ent_coef, c.exp_avg = a.exp_avg, c.exp_avg_sq = a.exp_avg_sq;
   c.ent_coef_out = a.ent_coef_out, c.loss_out = a.loss_out;
   c.target_in = a.target_in, c.next_log_prob = a.next_log_prob, c.terminated = a.terminated, c.y_out = a.y_out;
   c.d_log_prob_out = a.d_log_prob_out;
   c.c = adam_coef(*hp);
-  HIP_TRY(h, hipSetDevice(h->device));
-  sac_entropy_launch(c, (hipStream_t)stream);
-  return launched(h);
+  return URGYM_OK;
 }
 
-int urgym_sac_policy_terms(void* handle, const urgym_sac_policy_args* args, void* stream) {
-  const char* who = "urgym_sac_policy_terms";
-  Handle* h = (Handle*)handle;
-  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+int check_policy_terms(Handle* h, const urgym_sac_policy_args* args, const char* who, SacPolicyCall* out) {
   if (!args) return fail_in(h, URGYM_ERR_ARG, who, "null args");
   const urgym_sac_policy_args& a = *args;
   if (a.reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_policy_args.reserved0 must be 0");
@@ -416,11 +410,210 @@ int urgym_sac_policy_terms(void* handle, const urgym_sac_policy_args* args, void
   if (critic != 0 && critic != 3) return fail_in(h, URGYM_ERR_ARG, who, "the critic-loss group is half given: q, y and critic_loss_out go together");
   if (actor != 0 && actor != 3) return fail_in(h, URGYM_ERR_ARG, who, "the actor-loss group is half given: log_prob, q_min and actor_loss_out go together");
   if (!upstream && !critic && !actor) return fail_in(h, URGYM_ERR_ARG, who, "no group is given (upstream, critic loss, actor loss)");
-  SacPolicyCall c;
+  SacPolicyCall& c = *out;
   c.count = a.count, c.scale = a.scale, c.ent_coef = a.ent_coef;
   c.dqmin_da = a.dqmin_da, c.d_action_out = a.d_action_out;
   c.q = a.q, c.y = a.y, c.critic_loss_out = a.critic_loss_out;
   c.log_prob = a.log_prob, c.q_min = a.q_min, c.actor_loss_out = a.actor_loss_out;
+  return URGYM_OK;
+}
+
+int check_sample_rows(Handle* h, void* actor, const urgym_sampling* how, const urgym_critic_rows* rows, int count, float* actions_dev, float* log_prob_dev,
+                      const char* who, SampleRows* out) {
+  Actor* a = nullptr;
+  if (int rc = enter_actor(h, actor, who, &a, "the actor does not take this env kind's features")) return rc;
+  if (int rc = check_sampling(h, a, how, log_prob_dev != nullptr, who)) return rc;
+  if (!actions_dev) return fail_in(h, URGYM_ERR_ARG, who, "null actions");
+  ActorEnv& env = out->env;
+  memset(&env, 0, sizeof(env));  // no records ride in this launch: the step outputs are not read
+  if (int rc = resolve_rows(h, rows, count, who, &env.observation, &env.achieved_goal, &env.desired_goal)) return rc;
+  env.N = count, env.obs_dim = h->obs_dim, env.goal_dim = h->goal_dim;
+  out->a = a, out->actions = actions_dev;
+  out->smp = ActorSample{how->mode, how->seed, how->first_draw, log_prob_dev, nullptr, nullptr, nullptr};
+  return URGYM_OK;
+}
+
+int check_collect(Handle* h, void* actor, const urgym_sampling* how, int num_steps, const urgym_replay_ring* ring, int first_slot, const char* who, Actor** out) {
+  Actor* a = nullptr;
+  if (int rc = enter_actor(h, actor, who, &a)) return rc;
+  if (int rc = check_sampling(h, a, how, false, who)) return rc;
+  if (int rc = check_ring(h, ring, who)) return rc;
+  if (first_slot < 0 || first_slot >= ring->capacity_steps) return fail_in(h, URGYM_ERR_ARG, who, "first_slot outside [0, capacity_steps)");
+  if (num_steps <= 0) return fail_in(h, URGYM_ERR_ARG, who, "num_steps must be positive");
+  *out = a;
+  return URGYM_OK;
+}
+
+int check_replay_sample(Handle* h, const urgym_replay_ring* ring, int oldest_slot, int filled_steps, uint64_t seed, uint64_t draw, int count,
+                        const urgym_replay_batch* batch, const char* who, ReplayGather* out) {
+  if (int rc = check_ring(h, ring, who)) return rc;
+  if (filled_steps < 1 || filled_steps > ring->capacity_steps) return fail_in(h, URGYM_ERR_ARG, who, "filled_steps outside [1, capacity_steps]");
+  if (oldest_slot < 0 || oldest_slot >= ring->capacity_steps) return fail_in(h, URGYM_ERR_ARG, who, "oldest_slot outside [0, capacity_steps)");
+  if (count <= 0) return fail_in(h, URGYM_ERR_ARG, who, "count must be positive");
+  if (!batch) return fail_in(h, URGYM_ERR_ARG, who, "null batch");
+  const urgym_replay_batch& b = *batch;
+  if (!b.observation && !b.achieved_goal && !b.desired_goal && !b.action && !b.reward && !b.next_observation && !b.next_achieved_goal &&
+      !b.next_desired_goal && !b.terminated && !b.truncated && !b.is_success && !b.index)
+    return fail_in(h, URGYM_ERR_ARG, who, "no output requested (every batch pointer is null)");
+  if ((b.truncated && !ring->truncated) || (b.is_success && !ring->is_success))
+    return fail_in(h, URGYM_ERR_ARG, who, "truncated / is_success asked from a ring that does not keep it");
+  ReplayGather& g = *out;
+  g.N = h->cfg.num_envs, g.obs_dim = h->obs_dim, g.goal_dim = h->goal_dim, g.capacity = ring->capacity_steps;
+  g.oldest_slot = oldest_slot, g.count = count;
+  g.size = (uint64_t)filled_steps * (uint64_t)h->cfg.num_envs;
+  g.seed = seed, g.draw = draw;
+  g.ring = *ring, g.batch = b;
+  return URGYM_OK;
+}
+
+int check_critic_evaluate(Handle* h, void* critic, const urgym_critic_rows* rows, int count, const urgym_critic_terms* terms, const urgym_critic_out* out,
+                          const char* who, Critic** critic_out, CriticCall* call_out) {
+  if (int rc = enter_bound(h)) return rc;
+  Critic* c = nullptr;
+  if (int rc = enter_critic(h, critic, who, &c)) return rc;
+  CriticCall& call = *call_out;
+  if (int rc = critic_rows(h, rows, count, who, &call)) return rc;
+  if (!out) return fail_in(h, URGYM_ERR_ARG, who, "null out");
+  if (!out->q && !out->q_min && !out->target) return fail_in(h, URGYM_ERR_ARG, who, "no output requested (q, q_min and target are all null)");
+  if (out->target && (!terms || !terms->reward)) return fail_in(h, URGYM_ERR_ARG, who, "target requested without terms->reward");
+  if (terms && out->target) {
+    call.reward = terms->reward, call.terminated = terms->terminated, call.log_prob = terms->log_prob;
+    call.gamma = terms->gamma, call.ent_coef = terms->ent_coef;
+  }
+  call.q = out->q, call.q_min = out->q_min, call.target = out->target;
+  *critic_out = c;
+  return URGYM_OK;
+}
+
+int check_critic_action_gradient(Handle* h, void* critic, const urgym_critic_rows* rows, int count, const urgym_critic_grad_out* out, const char* who,
+                                 Critic** critic_out, CriticGradCall* call_out) {
+  if (int rc = enter_bound(h)) return rc;
+  Critic* c = nullptr;
+  if (int rc = enter_critic(h, critic, who, &c, critic_grad_supported, "the gradient kernel is built for hidden widths up to 256")) return rc;
+  CriticGradCall& call = *call_out;
+  if (int rc = critic_rows(h, rows, count, who, &call)) return rc;
+  if (!out) return fail_in(h, URGYM_ERR_ARG, who, "null out");
+  if (!out->dq_da && !out->dqmin_da) return fail_in(h, URGYM_ERR_ARG, who, "no gradient requested (dq_da and dqmin_da are both null)");
+  call.dq_da = out->dq_da, call.dqmin_da = out->dqmin_da, call.q = out->q, call.q_min = out->q_min;
+  *critic_out = c;
+  return URGYM_OK;
+}
+
+int check_critic_parameter_gradients(Handle* h, void* critic, const urgym_critic_rows* rows, int count, const float* dq, const float* target, float scale,
+                                     const urgym_critic_param_grads* out, void* workspace, uint64_t workspace_bytes, const char* who, Critic** critic_out,
+                                     CriticBackwardCall* call_out) {
+  if (int rc = enter_bound(h)) return rc;
+  Critic* c = nullptr;
+  CriticBackwardCall& call = *call_out;
+  if (int rc = backward_critic(h, critic, count, who, &c)) return rc;
+  if (int rc = critic_rows(h, rows, count, who, &call)) return rc;
+  if ((dq != nullptr) == (target != nullptr)) return fail_in(h, URGYM_ERR_ARG, who, "exactly one of dq and target must be given");
+  if (target && !(fabsf(scale) < INFINITY)) return fail_in(h, URGYM_ERR_ARG, who, "scale must be finite");
+  if (!out) return fail_in(h, URGYM_ERR_ARG, who, "null out");
+  for (int net = 0; net < 2; net++) {
+    const urgym_q_network_grad& g = out->qf[net];
+    float* one[6] = {g.w0, g.b0, g.w1, g.b1, g.w_q, g.b_q};
+    for (int i = 0; i < 6; i++) {
+      if (!one[i]) return fail_in(h, URGYM_ERR_ARG, who, "a gradient pointer is null (all twelve are required)");
+      call.grad[net][i] = one[i];
+    }
+  }
+  if (!workspace) return fail_in(h, URGYM_ERR_ARG, who, "null workspace");
+  if ((uintptr_t)workspace % 16 != 0) return fail_in(h, URGYM_ERR_ARG, who, "the workspace must be 16-byte aligned");
+  if (workspace_bytes < critic_backward_workspace_bytes(c, count))
+    return fail_in(h, URGYM_ERR_ARG, who, "the workspace is smaller than urgym_critic_parameter_gradients_workspace reports");
+  call.dq = dq, call.target = target, call.scale = target ? scale : 0.0f;
+  call.q = out->q, call.workspace = (float*)workspace;
+  *critic_out = c;
+  return URGYM_OK;
+}
+
+int check_actor_parameter_gradients(Handle* h, void* actor, const urgym_sampling* how, const urgym_critic_rows* rows, int count, const urgym_actor_upstream* upstream,
+                                    const urgym_actor_param_grads* out, void* workspace, uint64_t workspace_bytes, const char* who, Actor** actor_out,
+                                    ActorBackwardCall* call_out) {
+  Actor* a = nullptr;
+  if (int rc = backward_actor(h, actor, count, who, &a)) return rc;
+  if (int rc = check_sampling(h, a, how, true, who)) return rc;
+  if (how->mode == URGYM_SAMPLE_UNIFORM) return fail_in(h, URGYM_ERR_ARG, who, "mode must be URGYM_SAMPLE_GAUSSIAN or URGYM_SAMPLE_MEAN (UNIFORM runs no network)");
+  ActorBackwardCall& call = *call_out;
+  memset(&call, 0, sizeof(call));
+  if (int rc = resolve_rows(h, rows, count, who, &call.observation, &call.achieved_goal, &call.desired_goal)) return rc;
+  if (!upstream) return fail_in(h, URGYM_ERR_ARG, who, "null upstream");
+  const bool sample = upstream->d_action || upstream->d_log_prob, heads = upstream->d_mu || upstream->d_log_std;
+  if (sample == heads) return fail_in(h, URGYM_ERR_ARG, who, "exactly one upstream form must be given: d_action (with d_log_prob or NULL), or d_mu and d_log_std");
+  if (sample && !upstream->d_action) return fail_in(h, URGYM_ERR_ARG, who, "d_log_prob is given without d_action");
+  if (heads && (!upstream->d_mu || !upstream->d_log_std)) return fail_in(h, URGYM_ERR_ARG, who, "the HEADS form needs both d_mu and d_log_std");
+  if (!out) return fail_in(h, URGYM_ERR_ARG, who, "null out");
+  float* const tensors[8] = {out->w0, out->b0, out->w1, out->b1, out->w_mu, out->b_mu, out->w_log_std, out->b_log_std};
+  for (int i = 0; i < 8; i++) {
+    if (!tensors[i]) return fail_in(h, URGYM_ERR_ARG, who, "a gradient pointer is null (all eight are required)");
+    call.grad[i] = tensors[i];
+  }
+  if (!workspace) return fail_in(h, URGYM_ERR_ARG, who, "null workspace");
+  if ((uintptr_t)workspace % 16 != 0) return fail_in(h, URGYM_ERR_ARG, who, "the workspace must be 16-byte aligned");
+  if (workspace_bytes < actor_backward_workspace_bytes(a, count))
+    return fail_in(h, URGYM_ERR_ARG, who, "the workspace is smaller than urgym_actor_parameter_gradients_workspace reports");
+  call.M = count, call.obs_dim = h->obs_dim, call.goal_dim = h->goal_dim;
+  call.mode = how->mode, call.seed = how->seed, call.draw = how->first_draw;
+  call.d_action = upstream->d_action, call.d_log_prob = upstream->d_log_prob, call.d_mu = upstream->d_mu, call.d_log_std = upstream->d_log_std;
+  call.action = out->action, call.log_prob = out->log_prob, call.noise = out->noise, call.log_std = out->log_std;
+  call.out_d_mu = out->d_mu, call.out_d_log_std = out->d_log_std, call.std = out->std;
+  call.workspace = (float*)workspace;
+  *actor_out = a;
+  return URGYM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- Adam on the device (urgym_adam.hip): everything is checked here, before the launch
+int urgym_adam_coefficients(const urgym_adam_hyper* hp, float out[7]) {
+  if (const char* what = adam_hyper_refusal(hp)) return fail_in(nullptr, URGYM_ERR_ARG, "urgym_adam_coefficients", what);
+  if (!out) return fail(nullptr, URGYM_ERR_ARG, "urgym_adam_coefficients: null out");
+  const AdamCoef c = adam_coef(*hp);
+  out[0] = c.b1, out[1] = c.omb1, out[2] = c.b2, out[3] = c.omb2, out[4] = c.step_size, out[5] = c.bc2_sqrt, out[6] = c.eps;
+  return URGYM_OK;
+}
+
+int urgym_actor_adam_step(void* handle, void* actor, const urgym_actor_adam* t, const urgym_adam_hyper* hp, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  ActorAdamStep step;
+  if (int rc = check_actor_adam(h, actor, t, hp, "urgym_actor_adam_step", &step)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  actor_adam_launch(step.buf, step.T, adam_coef(*hp), (hipStream_t)stream);
+  HIP_TRY(h, hipGetLastError());
+  actor_mark_log_std(step.a);  // as urgym_actor_load with both head pointers
+  return URGYM_OK;
+}
+
+int urgym_critic_adam_step(void* handle, void* online, void* target_or_NULL, const urgym_critic_adam* t, const urgym_adam_hyper* hp, float tau, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  CriticAdamStep step;
+  if (int rc = check_critic_adam(h, online, target_or_NULL, t, hp, tau, "urgym_critic_adam_step", &step)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  critic_adam_launch(step.buf, step.has_target ? &step.target_buf : nullptr, step.T, adam_coef(*hp), tau, (hipStream_t)stream);
+  return launched(h);
+}
+
+// ---- SAC's entropy coefficient on the device (urgym_sac_terms.hip): everything is checked here, before the launch
+int urgym_sac_entropy_step(void* handle, const urgym_sac_entropy_args* args, const urgym_adam_hyper* hp, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  SacEntropyCall c;
+  if (int rc = check_entropy_step(h, args, hp, "urgym_sac_entropy_step", &c)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  sac_entropy_launch(c, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_sac_policy_terms(void* handle, const urgym_sac_policy_args* args, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  SacPolicyCall c;
+  if (int rc = check_policy_terms(h, args, "urgym_sac_policy_terms", &c)) return rc;
   HIP_TRY(h, hipSetDevice(h->device));
   sac_policy_launch(c, (hipStream_t)stream);
   return launched(h);
@@ -558,56 +751,27 @@ int urgym_rollout_sampled(void* handle, void* actor, const urgym_sampling* how, 
 }
 
 int urgym_actor_sample_rows(void* handle, void* actor, const urgym_sampling* how, const urgym_critic_rows* rows, int count, float* actions_dev, float* log_prob_dev, void* stream) {
-  const char* who = "urgym_actor_sample_rows";
   Handle* h = (Handle*)handle;
-  Actor* a = nullptr;
-  if (int rc = enter_actor(h, actor, who, &a, "the actor does not take this env kind's features")) return rc;
-  if (int rc = check_sampling(h, a, how, log_prob_dev != nullptr, who)) return rc;
-  if (!actions_dev) return fail(h, URGYM_ERR_ARG, "urgym_actor_sample_rows: null actions");
-  ActorEnv env;
-  memset(&env, 0, sizeof(env));  // no records ride in this launch: the step outputs are not read
-  if (int rc = resolve_rows(h, rows, count, who, &env.observation, &env.achieved_goal, &env.desired_goal)) return rc;
-  env.N = count, env.obs_dim = h->obs_dim, env.goal_dim = h->goal_dim;
-  policy_launch(a, env, actions_dev, nullptr, ActorSample{how->mode, how->seed, how->first_draw, log_prob_dev, nullptr, nullptr, nullptr},
-                (hipStream_t)stream);
+  SampleRows r;
+  if (int rc = check_sample_rows(h, actor, how, rows, count, actions_dev, log_prob_dev, "urgym_actor_sample_rows", &r)) return rc;
+  policy_launch(r.a, r.env, r.actions, nullptr, r.smp, (hipStream_t)stream);
   return launched(h);
 }
 
 // The launches of urgym_rollout_sampled without records, a store pass before each actor and one after the last step.
 int urgym_rollout_collect(void* handle, void* actor, const urgym_sampling* how, int num_steps, const urgym_replay_ring* ring, int first_slot, void* stream) {
-  const char* who = "urgym_rollout_collect";
   Handle* h = (Handle*)handle;
   Actor* a = nullptr;
-  if (int rc = enter_actor(h, actor, who, &a)) return rc;
-  if (int rc = check_sampling(h, a, how, false, who)) return rc;
-  if (int rc = check_ring(h, ring, who)) return rc;
-  if (first_slot < 0 || first_slot >= ring->capacity_steps) return fail(h, URGYM_ERR_ARG, "urgym_rollout_collect: first_slot outside [0, capacity_steps)");
-  if (num_steps <= 0) return fail(h, URGYM_ERR_ARG, "urgym_rollout_collect: num_steps must be positive");
+  if (int rc = check_collect(h, actor, how, num_steps, ring, first_slot, "urgym_rollout_collect", &a)) return rc;
   return rollout(h, a, how, num_steps, RolloutSinks{nullptr, nullptr, ring, first_slot}, (hipStream_t)stream);
 }
 
 int urgym_replay_sample(void* handle, const urgym_replay_ring* ring, int oldest_slot, int filled_steps, uint64_t seed, uint64_t draw, int count, const urgym_replay_batch* batch, void* stream) {
-  const char* who = "urgym_replay_sample";
   Handle* h = (Handle*)handle;
   if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
-  if (int rc = check_ring(h, ring, who)) return rc;
-  if (filled_steps < 1 || filled_steps > ring->capacity_steps) return fail(h, URGYM_ERR_ARG, "urgym_replay_sample: filled_steps outside [1, capacity_steps]");
-  if (oldest_slot < 0 || oldest_slot >= ring->capacity_steps) return fail(h, URGYM_ERR_ARG, "urgym_replay_sample: oldest_slot outside [0, capacity_steps)");
-  if (count <= 0) return fail(h, URGYM_ERR_ARG, "urgym_replay_sample: count must be positive");
-  if (!batch) return fail(h, URGYM_ERR_ARG, "urgym_replay_sample: null batch");
-  const urgym_replay_batch& b = *batch;
-  if (!b.observation && !b.achieved_goal && !b.desired_goal && !b.action && !b.reward && !b.next_observation && !b.next_achieved_goal &&
-      !b.next_desired_goal && !b.terminated && !b.truncated && !b.is_success && !b.index)
-    return fail(h, URGYM_ERR_ARG, "urgym_replay_sample: no output requested (every batch pointer is null)");
-  if ((b.truncated && !ring->truncated) || (b.is_success && !ring->is_success))
-    return fail(h, URGYM_ERR_ARG, "urgym_replay_sample: truncated / is_success asked from a ring that does not keep it");
-  HIP_TRY(h, hipSetDevice(h->device));
   ReplayGather g;
-  g.N = h->cfg.num_envs, g.obs_dim = h->obs_dim, g.goal_dim = h->goal_dim, g.capacity = ring->capacity_steps;
-  g.oldest_slot = oldest_slot, g.count = count;
-  g.size = (uint64_t)filled_steps * (uint64_t)h->cfg.num_envs;
-  g.seed = seed, g.draw = draw;
-  g.ring = *ring, g.batch = b;
+  if (int rc = check_replay_sample(h, ring, oldest_slot, filled_steps, seed, draw, count, batch, "urgym_replay_sample", &g)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
   replay_gather_launch(g, (hipStream_t)stream);
   return launched(h);
 }
@@ -631,36 +795,19 @@ int urgym_critic_destroy(void* handle, void* critic) {
 }
 
 int urgym_critic_evaluate(void* handle, void* critic, const urgym_critic_rows* rows, int count, const urgym_critic_terms* terms, const urgym_critic_out* out, void* stream) {
-  const char* who = "urgym_critic_evaluate";
   Handle* h = (Handle*)handle;
-  if (int rc = enter_bound(h)) return rc;
   Critic* c = nullptr;
-  if (int rc = enter_critic(h, critic, who, &c)) return rc;
   CriticCall call;
-  if (int rc = critic_rows(h, rows, count, who, &call)) return rc;
-  if (!out) return fail(h, URGYM_ERR_ARG, "urgym_critic_evaluate: null out");
-  if (!out->q && !out->q_min && !out->target) return fail(h, URGYM_ERR_ARG, "urgym_critic_evaluate: no output requested (q, q_min and target are all null)");
-  if (out->target && (!terms || !terms->reward)) return fail(h, URGYM_ERR_ARG, "urgym_critic_evaluate: target requested without terms->reward");
-  if (terms && out->target) {
-    call.reward = terms->reward, call.terminated = terms->terminated, call.log_prob = terms->log_prob;
-    call.gamma = terms->gamma, call.ent_coef = terms->ent_coef;
-  }
-  call.q = out->q, call.q_min = out->q_min, call.target = out->target;
+  if (int rc = check_critic_evaluate(h, critic, rows, count, terms, out, "urgym_critic_evaluate", &c, &call)) return rc;
   critic_launch(c, call, (hipStream_t)stream);
   return launched(h);
 }
 
 int urgym_critic_action_gradient(void* handle, void* critic, const urgym_critic_rows* rows, int count, const urgym_critic_grad_out* out, void* stream) {
-  const char* who = "urgym_critic_action_gradient";
   Handle* h = (Handle*)handle;
-  if (int rc = enter_bound(h)) return rc;
   Critic* c = nullptr;
-  if (int rc = enter_critic(h, critic, who, &c, critic_grad_supported, "the gradient kernel is built for hidden widths up to 256")) return rc;
   CriticGradCall call;
-  if (int rc = critic_rows(h, rows, count, who, &call)) return rc;
-  if (!out) return fail(h, URGYM_ERR_ARG, "urgym_critic_action_gradient: null out");
-  if (!out->dq_da && !out->dqmin_da) return fail(h, URGYM_ERR_ARG, "urgym_critic_action_gradient: no gradient requested (dq_da and dqmin_da are both null)");
-  call.dq_da = out->dq_da, call.dqmin_da = out->dqmin_da, call.q = out->q, call.q_min = out->q_min;
+  if (int rc = check_critic_action_gradient(h, critic, rows, count, out, "urgym_critic_action_gradient", &c, &call)) return rc;
   critic_grad_launch(c, call, (hipStream_t)stream);
   return launched(h);
 }
@@ -677,30 +824,10 @@ int urgym_critic_parameter_gradients_workspace(void* handle, void* critic, int c
 }
 
 int urgym_critic_parameter_gradients(void* handle, void* critic, const urgym_critic_rows* rows, int count, const float* dq, const float* target, float scale, const urgym_critic_param_grads* out, void* workspace, uint64_t workspace_bytes, void* stream) {
-  const char* who = "urgym_critic_parameter_gradients";
   Handle* h = (Handle*)handle;
-  if (int rc = enter_bound(h)) return rc;
   Critic* c = nullptr;
   CriticBackwardCall call;
-  if (int rc = backward_critic(h, critic, count, who, &c)) return rc;
-  if (int rc = critic_rows(h, rows, count, who, &call)) return rc;
-  if ((dq != nullptr) == (target != nullptr)) return fail(h, URGYM_ERR_ARG, "urgym_critic_parameter_gradients: exactly one of dq and target must be given");
-  if (target && !(fabsf(scale) < INFINITY)) return fail(h, URGYM_ERR_ARG, "urgym_critic_parameter_gradients: scale must be finite");
-  if (!out) return fail(h, URGYM_ERR_ARG, "urgym_critic_parameter_gradients: null out");
-  for (int net = 0; net < 2; net++) {
-    const urgym_q_network_grad& g = out->qf[net];
-    float* one[6] = {g.w0, g.b0, g.w1, g.b1, g.w_q, g.b_q};
-    for (int i = 0; i < 6; i++) {
-      if (!one[i]) return fail(h, URGYM_ERR_ARG, "urgym_critic_parameter_gradients: a gradient pointer is null (all twelve are required)");
-      call.grad[net][i] = one[i];
-    }
-  }
-  if (!workspace) return fail(h, URGYM_ERR_ARG, "urgym_critic_parameter_gradients: null workspace");
-  if ((uintptr_t)workspace % 16 != 0) return fail(h, URGYM_ERR_ARG, "urgym_critic_parameter_gradients: the workspace must be 16-byte aligned");
-  if (workspace_bytes < critic_backward_workspace_bytes(c, count))
-    return fail(h, URGYM_ERR_ARG, "urgym_critic_parameter_gradients: the workspace is smaller than urgym_critic_parameter_gradients_workspace reports");
-  call.dq = dq, call.target = target, call.scale = target ? scale : 0.0f;
-  call.q = out->q, call.workspace = (float*)workspace;
+  if (int rc = check_critic_parameter_gradients(h, critic, rows, count, dq, target, scale, out, workspace, workspace_bytes, "urgym_critic_parameter_gradients", &c, &call)) return rc;
   critic_backward_launch(c, call, (hipStream_t)stream);
   return launched(h);
 }
@@ -717,38 +844,199 @@ int urgym_actor_parameter_gradients_workspace(void* handle, void* actor, int cou
 }
 
 int urgym_actor_parameter_gradients(void* handle, void* actor, const urgym_sampling* how, const urgym_critic_rows* rows, int count, const urgym_actor_upstream* upstream, const urgym_actor_param_grads* out, void* workspace, uint64_t workspace_bytes, void* stream) {
-  const char* who = "urgym_actor_parameter_gradients";
   Handle* h = (Handle*)handle;
   Actor* a = nullptr;
-  if (int rc = backward_actor(h, actor, count, who, &a)) return rc;
-  if (int rc = check_sampling(h, a, how, true, who)) return rc;
-  if (how->mode == URGYM_SAMPLE_UNIFORM) return fail_in(h, URGYM_ERR_ARG, who, "mode must be URGYM_SAMPLE_GAUSSIAN or URGYM_SAMPLE_MEAN (UNIFORM runs no network)");
   ActorBackwardCall call;
-  memset(&call, 0, sizeof(call));
-  if (int rc = resolve_rows(h, rows, count, who, &call.observation, &call.achieved_goal, &call.desired_goal)) return rc;
-  if (!upstream) return fail_in(h, URGYM_ERR_ARG, who, "null upstream");
-  const bool sample = upstream->d_action || upstream->d_log_prob, heads = upstream->d_mu || upstream->d_log_std;
-  if (sample == heads) return fail_in(h, URGYM_ERR_ARG, who, "exactly one upstream form must be given: d_action (with d_log_prob or NULL), or d_mu and d_log_std");
-  if (sample && !upstream->d_action) return fail_in(h, URGYM_ERR_ARG, who, "d_log_prob is given without d_action");
-  if (heads && (!upstream->d_mu || !upstream->d_log_std)) return fail_in(h, URGYM_ERR_ARG, who, "the HEADS form needs both d_mu and d_log_std");
-  if (!out) return fail_in(h, URGYM_ERR_ARG, who, "null out");
-  float* const tensors[8] = {out->w0, out->b0, out->w1, out->b1, out->w_mu, out->b_mu, out->w_log_std, out->b_log_std};
-  for (int i = 0; i < 8; i++) {
-    if (!tensors[i]) return fail_in(h, URGYM_ERR_ARG, who, "a gradient pointer is null (all eight are required)");
-    call.grad[i] = tensors[i];
-  }
-  if (!workspace) return fail_in(h, URGYM_ERR_ARG, who, "null workspace");
-  if ((uintptr_t)workspace % 16 != 0) return fail_in(h, URGYM_ERR_ARG, who, "the workspace must be 16-byte aligned");
-  if (workspace_bytes < actor_backward_workspace_bytes(a, count))
-    return fail_in(h, URGYM_ERR_ARG, who, "the workspace is smaller than urgym_actor_parameter_gradients_workspace reports");
-  call.M = count, call.obs_dim = h->obs_dim, call.goal_dim = h->goal_dim;
-  call.mode = how->mode, call.seed = how->seed, call.draw = how->first_draw;
-  call.d_action = upstream->d_action, call.d_log_prob = upstream->d_log_prob, call.d_mu = upstream->d_mu, call.d_log_std = upstream->d_log_std;
-  call.action = out->action, call.log_prob = out->log_prob, call.noise = out->noise, call.log_std = out->log_std;
-  call.out_d_mu = out->d_mu, call.out_d_log_std = out->d_log_std, call.std = out->std;
-  call.workspace = (float*)workspace;
+  if (int rc = check_actor_parameter_gradients(h, actor, how, rows, count, upstream, out, workspace, workspace_bytes, "urgym_actor_parameter_gradients", &a, &call)) return rc;
   actor_backward_launch(a, call, (hipStream_t)stream);
   return launched(h);
+}
+
+// ---- the training loop in one call (include/urgym.h, urgym_sac_train): every check above first, then nothing
+// but launches.  The launch structs are filled once; an update rewrites the few numbers that move (draws, the ring view, Adam's
+// coefficients, the loss slots).
+
+namespace {
+
+// the required pointers of urgym_sac_learner that no composed check would name: the walk of the NULL refusals
+struct LearnerPointer {
+  const char* name;
+  const void* p;
+};
+
+// after the launches of one stage: urgym_last_error names the iteration and the stage
+int train_stage(Handle* h, int iteration, const char* stage) {
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return URGYM_OK;
+  return failf(h, URGYM_ERR_HIP, "urgym_sac_train: iteration %d, %s: %s", iteration, stage, hipGetErrorString(e));
+}
+
+}  // namespace
+
+int urgym_sac_train(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, void* stream) {
+  const char* who = "urgym_sac_train";
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (!learner) return fail_in(h, URGYM_ERR_ARG, who, "null learner");
+  if (!schedule) return fail_in(h, URGYM_ERR_ARG, who, "null schedule");
+  const urgym_sac_learner& L = *learner;
+  const urgym_sac_schedule& S = *schedule;
+  if (L.reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_learner.reserved0 must be 0");
+  const LearnerPointer required[] = {
+      {"actor", L.actor}, {"online", L.online}, {"target", L.target}, {"actor_workspace", L.actor_workspace},
+      {"critic_workspace", L.critic_workspace}, {"log_ent_coef", L.log_ent_coef}, {"exp_avg", L.exp_avg}, {"exp_avg_sq", L.exp_avg_sq},
+      {"batch.observation", L.batch.observation}, {"batch.achieved_goal", L.batch.achieved_goal}, {"batch.desired_goal", L.batch.desired_goal},
+      {"batch.action", L.batch.action}, {"batch.reward", L.batch.reward}, {"batch.next_observation", L.batch.next_observation},
+      {"batch.next_achieved_goal", L.batch.next_achieved_goal}, {"batch.next_desired_goal", L.batch.next_desired_goal},
+      {"batch.terminated", L.batch.terminated}, {"next_actions", L.next_actions}, {"next_log_prob", L.next_log_prob},
+      {"target_value", L.target_value}, {"y", L.y}, {"action_pi", L.action_pi}, {"log_prob", L.log_prob}, {"q", L.q}, {"q_min", L.q_min},
+      {"dqmin_da", L.dqmin_da}, {"d_action", L.d_action}, {"d_log_prob", L.d_log_prob}, {"ent_coef", L.ent_coef}};
+  const LearnerPointer losses[] = {{"critic_loss", L.critic_loss}, {"actor_loss", L.actor_loss}, {"ent_coef_loss", L.ent_coef_loss}};
+  for (const LearnerPointer& r : required)
+    if (!r.p) return failf(h, URGYM_ERR_ARG, "%s: urgym_sac_learner.%s is null", who, r.name);
+  if (L.online == L.target) return fail_in(h, URGYM_ERR_ARG, who, "the target is the online critic itself");
+  if (const char* what = sac_schedule_refusal(S)) return fail_in(h, URGYM_ERR_ARG, who, what);
+  if (S.capacity_steps != L.ring.capacity_steps) return fail_in(h, URGYM_ERR_ARG, who, "schedule->capacity_steps is not ring.capacity_steps");
+  for (const LearnerPointer& r : losses)  // zero slots need no array
+    if (!r.p && sac_schedule_updates(S) > 0) return failf(h, URGYM_ERR_ARG, "%s: urgym_sac_learner.%s is null", who, r.name);
+
+  // ---- the checking halves, with the numbers of the first collection and the first update
+  const int M = L.count, K = S.steps_per_iteration, G = S.updates_per_iteration;
+  const int64_t updates = sac_schedule_updates(S);
+  const float scale = (float)(1.0 / (double)M), neg_scale = (float)(-1.0 / (double)M);  // as SACLearner._update_on_device hands them over
+  Actor* collector = nullptr;
+  if (K > 0) {
+    for (int mode : {URGYM_SAMPLE_UNIFORM, URGYM_SAMPLE_GAUSSIAN}) {  // each mode the call collects with
+      if (mode == URGYM_SAMPLE_UNIFORM ? S.uniform_iterations == 0 : S.uniform_iterations >= S.num_iterations) continue;
+      const urgym_sampling how{mode, 0, L.seed, S.collect_first_draw};
+      if (int rc = check_collect(h, L.actor, &how, K, &L.ring, S.first_slot, who, &collector)) return rc;
+    }
+  }
+  const hipStream_t s = (hipStream_t)stream;
+  // the collection of iteration i: the launches of urgym_rollout_collect
+  auto collect = [&](int i, const SacIteration& it) {
+    const urgym_sampling how{it.collect_mode, 0, L.seed, it.collect_first_draw};
+    const int rc = rollout(h, collector, &how, K, RolloutSinks{nullptr, nullptr, &L.ring, it.collect_first_slot}, s);
+    if (!rc) return rc;
+    char was[160];
+    snprintf(was, sizeof(was), "%s", h->err);
+    return failf(h, rc, "urgym_sac_train: iteration %d, collect: %s", i, was);
+  };
+  if (updates == 0) {  // the sequence holds no update call: nothing more to check
+    for (int i = 0; i < S.num_iterations; i++)
+      if (int rc = collect(i, sac_schedule_iteration(S, i))) return rc;
+    return URGYM_OK;
+  }
+  const SacIteration view = sac_schedule_iteration(S, S.idle_iterations);  // what the first update sees
+  const SacUpdate first = sac_schedule_update(S, 0);
+  urgym_adam_hyper hp{L.lr, L.beta1, L.beta2, L.eps, first.adam_step, 0};
+
+  ReplayGather gather;
+  if (int rc = check_replay_sample(h, &L.ring, view.oldest_slot, view.filled_steps, L.update_seed, first.gather_draw, M, &L.batch, who, &gather)) return rc;
+  const urgym_critic_rows next_rows{L.batch.next_observation, L.batch.next_achieved_goal, L.batch.next_desired_goal, L.next_actions};
+  const urgym_critic_rows batch_rows{L.batch.observation, L.batch.achieved_goal, L.batch.desired_goal, L.batch.action};
+  const urgym_critic_rows policy_rows{L.batch.observation, L.batch.achieved_goal, L.batch.desired_goal, L.action_pi};
+  urgym_sampling how{URGYM_SAMPLE_GAUSSIAN, 0, L.update_seed, first.gather_draw};
+  SampleRows next_sample, policy_sample;
+  if (int rc = check_sample_rows(h, L.actor, &how, &next_rows, M, L.next_actions, L.next_log_prob, who, &next_sample)) return rc;
+  const urgym_critic_terms terms{L.batch.reward, L.batch.terminated, L.next_log_prob, L.gamma, 0.0f};
+  const urgym_critic_out target_out{nullptr, nullptr, L.target_value};
+  Critic *target = nullptr, *online = nullptr, *online_grad = nullptr;
+  CriticCall bootstrap;
+  if (int rc = check_critic_evaluate(h, L.target, &next_rows, M, &terms, &target_out, who, &target, &bootstrap)) return rc;
+  how.first_draw = first.policy_draw;
+  if (int rc = check_sample_rows(h, L.actor, &how, &batch_rows, M, L.action_pi, L.log_prob, who, &policy_sample)) return rc;
+  urgym_sac_entropy_args ea;
+  memset(&ea, 0, sizeof(ea));
+  ea.count = M, ea.target_entropy = L.target_entropy, ea.gamma = L.gamma, ea.scale = scale;
+  ea.log_prob = L.log_prob, ea.log_ent_coef = L.log_ent_coef, ea.exp_avg = L.exp_avg, ea.exp_avg_sq = L.exp_avg_sq;
+  ea.ent_coef_out = L.ent_coef, ea.loss_out = L.ent_coef_loss;
+  ea.target_in = L.target_value, ea.next_log_prob = L.next_log_prob, ea.terminated = L.batch.terminated, ea.y_out = L.y;
+  ea.d_log_prob_out = L.d_log_prob;
+  SacEntropyCall entropy;
+  if (int rc = check_entropy_step(h, &ea, &hp, who, &entropy)) return rc;
+  urgym_critic_param_grads cg;
+  for (int net = 0; net < 2; net++) {
+    const urgym_q_network_dev& g = L.critic_adam.grad[net];  // the tensors the step reads are the ones the gradient call writes
+    cg.qf[net] = urgym_q_network_grad{(float*)g.w0, (float*)g.b0, (float*)g.w1, (float*)g.b1, (float*)g.w_q, (float*)g.b_q};
+  }
+  cg.q = L.q;
+  CriticBackwardCall critic_backward;
+  if (int rc = check_critic_parameter_gradients(h, L.online, &batch_rows, M, nullptr, L.y, scale, &cg, L.critic_workspace, L.critic_workspace_bytes, who, &online,
+                                                &critic_backward))
+    return rc;
+  CriticAdamStep critic_step;
+  if (int rc = check_critic_adam(h, L.online, L.target, &L.critic_adam, &hp, L.tau, who, &critic_step)) return rc;
+  const urgym_critic_grad_out go{nullptr, L.dqmin_da, nullptr, L.q_min};
+  CriticGradCall action_gradient;
+  if (int rc = check_critic_action_gradient(h, L.online, &policy_rows, M, &go, who, &online_grad, &action_gradient)) return rc;
+  urgym_sac_policy_args pa;
+  memset(&pa, 0, sizeof(pa));
+  pa.count = M, pa.scale = neg_scale, pa.ent_coef = L.ent_coef;
+  pa.dqmin_da = L.dqmin_da, pa.d_action_out = L.d_action;
+  pa.q = L.q, pa.y = L.y, pa.critic_loss_out = L.critic_loss;
+  pa.log_prob = L.log_prob, pa.q_min = L.q_min, pa.actor_loss_out = L.actor_loss;
+  SacPolicyCall terms_call;
+  if (int rc = check_policy_terms(h, &pa, who, &terms_call)) return rc;
+  const urgym_actor_upstream upstream{L.d_action, L.d_log_prob, nullptr, nullptr};
+  urgym_actor_param_grads ag;
+  memset(&ag, 0, sizeof(ag));
+  {
+    const urgym_actor_tensors_const& g = L.actor_adam.grad;
+    ag.w0 = (float*)g.w0, ag.b0 = (float*)g.b0, ag.w1 = (float*)g.w1, ag.b1 = (float*)g.b1;
+    ag.w_mu = (float*)g.w_mu, ag.b_mu = (float*)g.b_mu, ag.w_log_std = (float*)g.w_log_std, ag.b_log_std = (float*)g.b_log_std;
+  }
+  Actor* actor = nullptr;
+  ActorBackwardCall actor_backward;
+  if (int rc = check_actor_parameter_gradients(h, L.actor, &how, &batch_rows, M, &upstream, &ag, L.actor_workspace, L.actor_workspace_bytes, who, &actor,
+                                               &actor_backward))
+    return rc;
+  ActorAdamStep actor_step;
+  if (int rc = check_actor_adam(h, L.actor, &L.actor_adam, &hp, who, &actor_step)) return rc;
+
+  // ---- the launching halves: nothing below refuses
+  int64_t u = 0;
+  for (int i = 0; i < S.num_iterations; i++) {
+    const SacIteration it = sac_schedule_iteration(S, i);
+    if (K > 0)
+      if (int rc = collect(i, it)) return rc;
+    if (it.idle) continue;
+    gather.oldest_slot = it.oldest_slot, gather.size = (uint64_t)it.filled_steps * (uint64_t)h->cfg.num_envs;
+    for (int g = 0; g < G; g++, u++) {
+      const SacUpdate up = sac_schedule_update(S, u);
+      const AdamCoef coef = adam_coefficients(L.lr, L.beta1, L.beta2, L.eps, up.adam_step);  // urgym_adam_coefficients' own function
+      gather.draw = up.gather_draw;
+      replay_gather_launch(gather, s);
+      if (int rc = train_stage(h, i, "replay_sample")) return rc;
+      next_sample.smp.draw = up.gather_draw;
+      policy_launch(next_sample.a, next_sample.env, next_sample.actions, nullptr, next_sample.smp, s);
+      if (int rc = train_stage(h, i, "actor_sample_rows (next rows)")) return rc;
+      critic_launch(target, bootstrap, s);
+      if (int rc = train_stage(h, i, "critic_evaluate")) return rc;
+      policy_sample.smp.draw = up.policy_draw;
+      policy_launch(policy_sample.a, policy_sample.env, policy_sample.actions, nullptr, policy_sample.smp, s);
+      if (int rc = train_stage(h, i, "actor_sample_rows (batch rows)")) return rc;
+      entropy.c = coef, entropy.loss_out = L.ent_coef_loss + up.loss_slot;
+      sac_entropy_launch(entropy, s);
+      if (int rc = train_stage(h, i, "sac_entropy_step")) return rc;
+      critic_backward_launch(online, critic_backward, s);
+      if (int rc = train_stage(h, i, "critic_parameter_gradients")) return rc;
+      critic_adam_launch(critic_step.buf, &critic_step.target_buf, critic_step.T, coef, critic_step.tau, s);
+      if (int rc = train_stage(h, i, "critic_adam_step")) return rc;
+      critic_grad_launch(online_grad, action_gradient, s);
+      if (int rc = train_stage(h, i, "critic_action_gradient")) return rc;
+      terms_call.critic_loss_out = L.critic_loss + up.loss_slot, terms_call.actor_loss_out = L.actor_loss + up.loss_slot;
+      sac_policy_launch(terms_call, s);
+      if (int rc = train_stage(h, i, "sac_policy_terms")) return rc;
+      actor_backward.draw = up.policy_draw;
+      actor_backward_launch(actor, actor_backward, s);
+      if (int rc = train_stage(h, i, "actor_parameter_gradients")) return rc;
+      actor_adam_launch(actor_step.buf, actor_step.T, coef, s);
+      if (int rc = train_stage(h, i, "actor_adam_step")) return rc;
+      actor_mark_log_std(actor_step.a);  // as urgym_actor_adam_step; the checks above have required the head already
+    }
+  }
+  return URGYM_OK;
 }
 
 }  // extern "C"

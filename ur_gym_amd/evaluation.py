@@ -94,6 +94,93 @@ def replay_indices(seed, draw, count, size):
     return np.array([((int(hi) << 32 | int(lo)) * size) >> 64 for hi, lo in zip(w[0], w[1])], dtype=np.int64).reshape(count)
 
 
+def training_schedule(*, first_slot, filled_steps, capacity_steps, num_iterations, steps_per_iteration=1, updates_per_iteration=1,
+                      uniform_iterations=0, idle_iterations=0, collect_first_draw=0, update_first_draw=0, first_step=1):
+    """The index arithmetic of one urgym_sac_train call, restated from include/urgym.h (``urgym_sac_schedule``) and
+    ur_gym_amd/csrc/urgym_sac_schedule.h in Python integers.  Returns a dict: ``iterations``, one dict per iteration
+    (``collect_first_slot``, ``collect_first_draw``, ``collect_mode`` as the URGYM_SAMPLE_* number, ``idle``, and the ring view of its
+    updates after its collection, ``oldest_slot`` and ``filled_steps``, and ``first_update``); ``updates``, one dict per update of the
+    whole call (``gather_draw``, ``policy_draw`` = the same | 2^63, ``adam_step``, ``loss_slot``, and the ``iteration`` it runs in);
+    ``num_updates``; and ``cursor`` and ``filled``, the ring afterwards.  Draws are taken modulo 2^64 like the uint64 they are.
+    Raises ValueError for what the header's validation refuses.  Needs no GPU."""
+    from . import _abi
+
+    names = ("first_slot", "filled_steps", "capacity_steps", "num_iterations", "steps_per_iteration", "updates_per_iteration",
+             "uniform_iterations", "idle_iterations", "collect_first_draw", "update_first_draw", "first_step")
+    given = (first_slot, filled_steps, capacity_steps, num_iterations, steps_per_iteration, updates_per_iteration, uniform_iterations,
+             idle_iterations, collect_first_draw, update_first_draw, first_step)
+    for name, v in zip(names, given):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"{name} must be an integer, got {v!r}")
+    slot, filled, C, n, K, G, U, I, cdraw, udraw, step = (int(v) for v in given)
+    for name, v in zip(names[:8], (slot, filled, C, n, K, G, U, I)):
+        if not -(1 << 31) <= v < 1 << 31:
+            raise ValueError(f"{name} must fit int32, got {v}")
+    if not (0 <= cdraw < 1 << 64 and 0 <= udraw < 1 << 64 and -(1 << 63) <= step < 1 << 63):
+        raise ValueError("collect_first_draw and update_first_draw must fit uint64, first_step int64")
+    active = max(0, n - I)
+    num_updates = active * G
+    if C <= 0:
+        raise ValueError("capacity_steps must be positive")
+    if n < 1:
+        raise ValueError("num_iterations must be at least 1")
+    if K < 0 or G < 0 or U < 0 or I < 0:
+        raise ValueError("a count of the schedule is negative (steps_per_iteration, updates_per_iteration, uniform_iterations, idle_iterations)")
+    if K == 0 and G == 0:
+        raise ValueError("steps_per_iteration and updates_per_iteration are both 0")
+    if not 0 <= slot < C:
+        raise ValueError(f"first_slot must be in [0, {C}), got {slot}")
+    if not 0 <= filled <= C:
+        raise ValueError(f"filled_steps must be in [0, {C}], got {filled}")
+    if num_updates > 0 and filled == 0 and K == 0:
+        raise ValueError("an update would see an empty ring (filled_steps and steps_per_iteration are both 0)")
+    if step < 1:
+        raise ValueError(f"first_step is the 1-based index of the first Adam step, got {step}")
+    if udraw + num_updates > 1 << 63:
+        raise ValueError("update_first_draw + the number of updates is above 2^63 (the top bit marks the policy's own draw)")
+    if step + num_updates > (1 << 63) - 1:
+        raise ValueError("first_step + the number of updates does not fit int64")
+
+    def ring(iterations):
+        cursor, have = (slot + iterations * K) % C, min(C, filled + iterations * K)
+        return cursor, have, (cursor - have) % C
+
+    iterations, updates = [], []
+    for i in range(n):
+        _, have, oldest = ring(i + 1)
+        iterations.append(dict(collect_first_slot=ring(i)[0], collect_first_draw=(cdraw + i * K) % (1 << 64),
+                               collect_mode=_abi.SAMPLE_UNIFORM if i < U else _abi.SAMPLE_GAUSSIAN, idle=int(i < I), oldest_slot=oldest,
+                               filled_steps=have, first_update=max(0, i - I) * G))
+        if i >= I:
+            for _ in range(G):
+                u = len(updates)
+                updates.append(dict(gather_draw=udraw + u, policy_draw=(udraw + u) | 1 << 63, adam_step=step + u, loss_slot=u, iteration=i))
+    cursor, have, _ = ring(n)
+    return dict(iterations=iterations, updates=updates, num_updates=num_updates, cursor=cursor, filled=have)
+
+
+def warmup_iterations(env_steps, num_envs, learning_starts, iterations, steps_per_iteration):
+    """(U, I) of ``training_schedule`` as SAC's warm-up decides them: iteration i starts at ``env_steps + i K`` steps per env;
+    it collects with uniform actions while ``steps * num_envs < learning_starts`` at its start (``SACLearner.collect``'s rule) and
+    runs no update while that still holds after its collection (the loop of tools/train_sac.py).  Both are prefixes of the call, so
+    each is a count; I <= U where K > 0."""
+    e, N, n, K = int(env_steps), int(num_envs), int(iterations), int(steps_per_iteration)
+
+    def leading(offset):  # the iterations i < n, counted from 0, with (e + (i + offset) K) N < learning_starts
+        if not (e + offset * K) * N < learning_starts:
+            return 0
+        if K == 0:
+            return n
+        i = min(n, max(0, int((learning_starts / N - e) // K) - offset - 1))  # a first guess from below, then the rule itself
+        while i > 0 and not (e + (i - 1 + offset) * K) * N < learning_starts:
+            i -= 1
+        while i < n and (e + (i + offset) * K) * N < learning_starts:
+            i += 1
+        return i
+
+    return leading(0), leading(1)
+
+
 def polyak(old, src, tau):
     """The blend of urgym_critic_load, restated from include/urgym.h in numpy float32: ``src`` at tau == 1 (the old value is not
     read), otherwise ``(old * omt) + (tau * src)`` with ``omt = float32(1) - float32(tau)``, three operations each rounded to

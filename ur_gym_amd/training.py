@@ -177,6 +177,7 @@ class SACLearner:
                       critic_loss=scalar(), actor_loss=scalar(), ent_coef_loss=scalar())
             es["losses"] = {k: es[k][0] for k in ("critic_loss", "actor_loss", "ent_coef_loss")}  # 0-dim views, made once
             self.entropy_state = es
+        self._train = None  # the scratch and the checked struct of train(), per replay
         self.env_steps = 0  # per env; decides between the warm-up and the policy
         self.draw = 0       # draw index of the next collection pass
 
@@ -303,7 +304,66 @@ class SACLearner:
         self.last_update = dict(log_prob=log_prob, y=es["y"], q=got["q"], q_min=grad["q_min"], dqmin_da=grad["dqmin_da"])
         return dict(es["losses"])
 
+    def _train_binding(self, replay):
+        """The scratch of ``train`` and the checked struct of the native call, made once per (learner, replay) pair."""
+        if self._train is not None and self._train["replay"] is replay:
+            return self._train
+        from . import _abi
+        from .vector_env import _TORCH_DTYPE
+
+        hp, env, st, es = self.hp, self.env, self.adam_state, self.entropy_state
+        M, dev = int(hp["batch_size"]), env.device
+        batch = {name: torch.empty((M,) + tuple(shape(1, 1, env.obs_dim, env.goal_dim)[2:]), dtype=_TORCH_DTYPE[ct], device=dev)
+                 for name, ct, shape, _ in _abi.REPLAY_RING_FIELDS}
+        batch["index"] = torch.empty((M,), dtype=torch.int64, device=dev)
+        scratch = {name: torch.zeros(shape(M), dtype=torch.float32, device=dev) for name, shape in _abi.SAC_LEARNER_SCRATCH}
+        # the tensors update() already owns stay the ones both routes write
+        scratch.update(y=es["y"], ent_coef=es["ent_coef"], d_action=self.actor_d_action, d_log_prob=self.actor_d_log_prob)
+        binding = env.sac_learner(
+            actor=self.device_actor, online=self.online, target=self.target, actor_params=self.actor.tensors(), actor_grads=self.actor_grads,
+            actor_exp_avg=st["actor"][0], actor_exp_avg_sq=st["actor"][1], critic_params=self.critic.tensors(), critic_grads=self.critic_grads,
+            critic_exp_avg=st["critic"][0], critic_exp_avg_sq=st["critic"][1], actor_workspace=self.actor_workspace,
+            critic_workspace=self.critic_workspace, log_ent_coef=self.log_ent_coef, exp_avg=es["exp_avg"], exp_avg_sq=es["exp_avg_sq"], replay=replay,
+            batch=batch, scratch=scratch, count=M, seed=self.seed, update_seed=0, gamma=hp["gamma"], tau=hp["tau"],
+            target_entropy=hp["target_entropy"], lr=hp["learning_rate"], betas=st["betas"], eps=st["eps"])
+        self._train = dict(replay=replay, binding=binding, scratch=scratch)
+        return self._train
+
+    def train(self, replay, iterations, steps_per_iteration=1, updates_per_iteration=1, *, seed, first_draw):
+        """`iterations` x (``collect(replay, steps_per_iteration)``, `updates_per_iteration` x ``update(replay, seed, draw)`` with draw =
+        `first_draw`, `first_draw` + 1, ...) in ONE native call (``env.sac_train``, urgym_sac_train), bit for bit: the loop of
+        tools/train_sac.py without Python between the launches.  Needs ``device_entropy``.  The warm-up is the loop's: an iteration
+        collects with uniform actions while ``env_steps * N < learning_starts`` when it starts, and runs no update while that still
+        holds after its collection (``evaluation.warmup_iterations``).  Advances ``env_steps``, ``draw``, ``adam_state["step"]``,
+        ``replay.cursor`` and ``replay.filled``; ``last_update`` refers to the scratch the last update used.  Returns the three
+        losses as device tensors of one entry per update (not synchronised).  ``steps_per_iteration=0, iterations=1`` is
+        `updates_per_iteration` updates in one call."""
+        from .evaluation import warmup_iterations
+
+        if self.entropy_state is None:
+            raise ValueError("train needs device_entropy=True (the native loop is the thirteen launches of the update on the device)")
+        hp, env, st = self.hp, self.env, self.adam_state
+        n, K, G = int(iterations), int(steps_per_iteration), int(updates_per_iteration)
+        tr = self._train_binding(replay)
+        uniform, idle = warmup_iterations(self.env_steps, env.num_envs, hp["learning_starts"], n, K)
+        updates = max(0, n - idle) * max(0, G)
+        losses = torch.empty((3, updates), dtype=torch.float32, device=env.device)
+        tr["binding"].struct.update_seed = int(seed)
+        env.sac_train(tr["binding"], losses[0], losses[1], losses[2], first_slot=replay.cursor, filled_steps=replay.filled, num_iterations=n,
+                      steps_per_iteration=K, updates_per_iteration=G, uniform_iterations=uniform, idle_iterations=idle,
+                      collect_first_draw=self.draw, update_first_draw=int(first_draw), first_step=st["step"] + 1)
+        self.env_steps += n * K
+        self.draw += n * K
+        st["step"] += updates
+        replay.cursor = (replay.cursor + n * K) % replay.capacity
+        replay.filled = min(replay.capacity, replay.filled + n * K)
+        if updates:
+            sc = tr["scratch"]
+            self.last_update = dict(log_prob=sc["log_prob"], y=sc["y"], q=sc["q"], q_min=sc["q_min"], dqmin_da=sc["dqmin_da"])
+        return {"critic_loss": losses[0], "actor_loss": losses[1], "ent_coef_loss": losses[2]}
+
     def close(self):
+        self._train = None
         self.device_actor.close()
         self.target.close()
         if self.online is not None:

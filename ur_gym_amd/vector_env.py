@@ -582,6 +582,135 @@ class UR5ReachVectorEnv:
             a.actor_loss_out = self._float_ptr(who, "actor_loss_out", actor_loss_out, (1,))
         _native.check(self.lib.urgym_sac_policy_terms(self._h, C.byref(a), self._stream()), self._h)
 
+    def sac_learner(self, *, actor, online, target, actor_params, actor_grads, actor_exp_avg, actor_exp_avg_sq, critic_params, critic_grads,
+                    critic_exp_avg, critic_exp_avg_sq, actor_workspace, critic_workspace, log_ent_coef, exp_avg, exp_avg_sq, replay, batch, scratch,
+                    count, seed, update_seed, gamma, tau, target_entropy, lr, betas=(0.9, 0.999), eps=1e-8):
+        """The ``urgym_sac_learner`` of ``sac_train``, built and checked ONCE: a ``SacLearnerBinding`` that holds the struct and keeps
+        every tensor it points to alive.  `actor`, `online`, `target`: the DeviceActor and the two DeviceCritics of this environment;
+        the four actor sets as ``actor_adam_step`` takes them, the four critic sets as ``critic_adam_step`` does (the grads are the
+        tensors the gradient launches write); the two workspaces from ``actor_gradient_workspace`` / ``critic_gradient_workspace``
+        for `count` rows; `log_ent_coef`, `exp_avg`, `exp_avg_sq`: the temperature's [1] tensors; `replay`: a DeviceReplay of this
+        environment; `batch`: a dict under the ring's field names (``truncated``, ``is_success`` and ``index`` optional) of [count, ...]
+        tensors as ``DeviceReplay.sample_into`` takes them; `scratch`: a dict under the names of ``_abi.SAC_LEARNER_SCRATCH``.  Every
+        tensor is checked (dtype, contiguity, device, shape) and none is converted; ValueError otherwise."""
+        from .evaluation import ACTOR_ARRAYS, CRITIC_ARRAYS, LOG_STD_ARRAYS, DeviceActor, DeviceCritic
+
+        who = "sac_learner"
+        a = self._actor_ptr(actor)
+        for name, c in (("online", online), ("target", target)):
+            if getattr(c, "env", None) is not self or not getattr(c, "_c", None):
+                raise ValueError(f"{who}: {name} must be a live DeviceCritic loaded for this environment (DeviceCritic.load(paths, env))")
+        if online is target:
+            raise ValueError(f"{who}: the target is the online critic itself")
+        if getattr(replay, "env", None) is not self or not hasattr(replay, "_ring"):
+            raise ValueError(f"{who}: replay must be a DeviceReplay allocated for this environment (DeviceReplay(env, capacity_steps))")
+        M = int(count)
+        if not 1 <= M <= _abi.SAC_TRAIN_MAX_COUNT:
+            raise ValueError(f"{who}: count must be in [1, {_abi.SAC_TRAIN_MAX_COUNT}], got {count}")
+        for name, x in (("gamma", gamma), ("tau", tau), ("target_entropy", target_entropy)):
+            if not self._finite32(x):
+                raise ValueError(f"{who}: {name} must be finite in float32, got {x}")
+        if not 0.0 < float(tau) <= 1.0:
+            raise ValueError(f"{who}: tau must be in (0, 1], got {tau}")
+        hyper = self._adam_hyper(lr, betas, eps, 1)
+        L = _abi.SacLearner()
+        keep = []
+        L.actor, L.online, L.target = a, online._c, target._c
+        L.actor_adam = _abi.ActorAdam(actor.in_features, actor.hidden_width, 0)
+        for name, tensors in zip(_abi.ADAM_SETS, (actor_params, actor_grads, actor_exp_avg, actor_exp_avg_sq)):
+            tensors = dict(tensors)
+            if not DeviceActor.check_parameters(tensors, actor.in_features, actor.hidden_width, self.device):
+                raise ValueError(f"{who}: the actor's {name} needs the log_std head too ({LOG_STD_ARRAYS})")
+            setattr(L.actor_adam, name, _abi.ActorTensors(*[C.cast(tensors[k].data_ptr(), C.POINTER(C.c_float)) for k in ACTOR_ARRAYS + LOG_STD_ARRAYS]))
+            keep.append(tensors)
+        L.critic_adam = _abi.CriticAdam(online.in_features, online.hidden_width, 0)
+        for name, tensors in zip(_abi.ADAM_SETS, (critic_params, critic_grads, critic_exp_avg, critic_exp_avg_sq)):
+            tensors = [dict(w) for w in tensors]
+            DeviceCritic.check_parameters(tensors, online.in_features, online.hidden_width, self.device)
+            nets = getattr(L.critic_adam, name)
+            for i, w in enumerate(tensors):
+                nets[i] = _abi.QNetworkDev(*[C.cast(w[k].data_ptr(), C.POINTER(C.c_float)) for k in CRITIC_ARRAYS])
+            keep.append(tensors)
+        for name, w in (("actor_workspace", actor_workspace), ("critic_workspace", critic_workspace)):
+            if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or not w.is_contiguous() or w.device != torch.device(self.device) or w.dim() != 1:
+                raise ValueError(f"{who}: {name} must be a contiguous float32 [n] tensor on {self.device} (actor_gradient_workspace / critic_gradient_workspace)")
+            setattr(L, name, w.data_ptr())
+            setattr(L, name + "_bytes", w.numel() * 4)
+            keep.append(w)
+        for name, t in zip(_abi.SAC_LEARNER_STATE, (log_ent_coef, exp_avg, exp_avg_sq)):
+            setattr(L, name, self._float_ptr(who, name, t, (1,)))
+            keep.append(t)
+        L.ring = replay._ring
+        keep.append(replay)
+        kinds = {name: (ct, shape(1, 1, self.obs_dim, self.goal_dim)[2:], required) for name, ct, shape, required in _abi.REPLAY_RING_FIELDS}
+        kinds["index"] = (C.c_int64, (), False)
+        batch = dict(batch)
+        unknown = [k for k in batch if k not in kinds]
+        if unknown:
+            raise ValueError(f"{who}: unknown batch fields {unknown}; available: {sorted(kinds)}")
+        for name, (ct, tail, required) in kinds.items():
+            if name not in batch or batch[name] is None:
+                if required:
+                    raise ValueError(f"{who}: batch[{name!r}] is required (only truncated, is_success and index are optional)")
+                continue
+            dtype = torch.int64 if ct is C.c_int64 else _TORCH_DTYPE[ct]
+            setattr(L.batch, name, self._float_ptr(who, f"batch[{name!r}]", batch[name], (M,) + tuple(tail), dtype, ct))
+        keep.append(batch)
+        scratch = dict(scratch)
+        unknown = [k for k in scratch if k not in dict(_abi.SAC_LEARNER_SCRATCH)]
+        if unknown:
+            raise ValueError(f"{who}: unknown scratch tensors {unknown}; expected {[n for n, _ in _abi.SAC_LEARNER_SCRATCH]}")
+        for name, shape in _abi.SAC_LEARNER_SCRATCH:
+            if name not in scratch:
+                raise ValueError(f"{who}: scratch[{name!r}] is missing")
+            setattr(L, name, self._float_ptr(who, f"scratch[{name!r}]", scratch[name], shape(M)))
+        keep.append(scratch)
+        L.count, L.reserved0, L.seed, L.update_seed = M, 0, int(seed), int(update_seed)
+        L.gamma, L.tau, L.target_entropy = float(gamma), float(tau), float(target_entropy)
+        L.lr, L.beta1, L.beta2, L.eps = hyper.lr, hyper.beta1, hyper.beta2, hyper.eps
+        return SacLearnerBinding(self, L, keep, actor)
+
+    def sac_train(self, learner, critic_loss, actor_loss, ent_coef_loss, *, first_slot, filled_steps, num_iterations, steps_per_iteration=1,
+                  updates_per_iteration=1, uniform_iterations=0, idle_iterations=0, collect_first_draw=0, update_first_draw=0, first_step=1):
+        """``num_iterations`` x (a collection of ``steps_per_iteration`` steps, ``updates_per_iteration`` SAC updates) in ONE native
+        call (urgym_sac_train): the launches of ``collect`` and of the thirteen calls of an update, bit for bit, without returning to
+        Python in between.  `learner`: what ``sac_learner`` returned, or a dict of its keyword arguments (then built and checked here).
+        `critic_loss`, `actor_loss`, `ent_coef_loss`: float32 tensors of one entry per update of the call, update u writes entry u.
+        The schedule as ``evaluation.training_schedule`` takes it (``capacity_steps`` is the replay's); the caller owns the ring's
+        cursor and fill level, the draw counters and the step count, and advances them.  On torch's current stream; nothing is
+        synchronised, nothing is converted.  Returns the number of updates."""
+        from .evaluation import training_schedule
+
+        who = "sac_train"
+        if isinstance(learner, dict):
+            learner = self.sac_learner(**learner)
+        if not isinstance(learner, SacLearnerBinding) or learner.env is not self:
+            raise ValueError(f"{who}: learner must come from this environment's sac_learner")
+        sched = dict(first_slot=first_slot, filled_steps=filled_steps, capacity_steps=int(learner.struct.ring.capacity_steps), num_iterations=num_iterations,
+                     steps_per_iteration=steps_per_iteration, updates_per_iteration=updates_per_iteration, uniform_iterations=uniform_iterations,
+                     idle_iterations=idle_iterations, collect_first_draw=collect_first_draw, update_first_draw=update_first_draw, first_step=first_step)
+        for name, v in sched.items():
+            if isinstance(v, bool) or int(v) != v:
+                raise ValueError(f"{who}: {name} must be an integer, got {v!r}")
+        sched = {k: int(v) for k, v in sched.items()}
+        ints = [k for k in sched if k not in ("collect_first_draw", "update_first_draw", "first_step")]
+        if any(not -(1 << 31) <= sched[k] < 1 << 31 for k in ints) or not all(0 <= sched[k] < 1 << 64 for k in ("collect_first_draw", "update_first_draw")) \
+                or not -(1 << 63) <= sched["first_step"] < 1 << 63:
+            raise ValueError(f"{who}: a number of the schedule does not fit its field (int32 counts, uint64 draws, int64 first_step)")
+        active = max(0, sched["num_iterations"] - max(0, sched["idle_iterations"]))
+        updates = active * max(0, sched["updates_per_iteration"])
+        L = learner.struct
+        for name, t in zip(_abi.SAC_LEARNER_LOSSES, (critic_loss, actor_loss, ent_coef_loss)):
+            setattr(L, name, self._float_ptr(who, name, t, (updates,)))
+        S = _abi.SacSchedule(*[sched[name] for name, _ in _abi.SacSchedule._fields_])
+        try:
+            _native.check(self.lib.urgym_sac_train(self._h, C.byref(L), C.byref(S), self._stream()), self._h)
+        finally:
+            for name in _abi.SAC_LEARNER_LOSSES:  # the loss slots belong to this call alone
+                setattr(L, name, None)
+        learner.actor.has_log_std = True
+        return updates
+
     def policy_actions(self, actor, out=None, sample=None, rows=None):
         """model.predict(obs, deterministic=True) (model_test.py:41) for all envs, by the HIP actor kernel, from the live
         observation buffers: float32 [N, 6] on the device.
@@ -799,6 +928,14 @@ class UR5ReachVectorEnv:
         _native.check(self.lib.urgym_query_refill_timing(self._h, C.byref(r)), self._h)
         self.last_refill_us = r.value  # overlapped refill of prefetched episode records (0 when that path is off)
         return a.value, b.value, n.value
+
+
+class SacLearnerBinding:
+    """What ``UR5ReachVectorEnv.sac_learner`` returns: the checked ``urgym_sac_learner`` (``struct``) and references to every tensor
+    and object it points to, so that none is freed while a call that reads it may still be queued."""
+
+    def __init__(self, env, struct, keep, actor):
+        self.env, self.struct, self.keep, self.actor = env, struct, keep, actor
 
 
 class _LazyInfo(dict):
