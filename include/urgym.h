@@ -997,6 +997,137 @@ typedef struct urgym_sac_learner {
  * of urgym_rollout_collect: launches already enqueued stay enqueued, and urgym_last_error names the iteration and the stage. */
 int urgym_sac_train(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, void* stream);
 
+/* ---- evaluation inside the training call (train.py:55-60 hands model.learn an EvalCallback, utils/callbackFunctions.py:429-518: at each
+ * evaluation it plays the deterministic policy for whole episodes, reduces them to the mean and the standard deviation of the reward,
+ * the mean episode length and the success rate, and saves best_model where the mean reward is STRICTLY above the best seen so far).
+ * Here the statistics are reduced on the device in a fixed order, the decision is taken on the device, and the best actor's tensors are
+ * copied on the device under that decision: a training call with evaluations never returns to the host.  Added WITHIN ABI version 4: no
+ * struct above changed, URGYM_ABI_VERSION did not move, the five symbols below are found by lookup.
+ *
+ * THE STATISTICS of N episodes with returns r[n] (float64: urgym_trajectory.episode_return), last[n] (int32: episode_last_step) and
+ * succ[n] (uint8: episode_success), every line ONE float64 operation rounded on its own (ur_gym_amd/csrc/urgym_eval.h states them,
+ * ur_gym_amd.evaluation.evaluation_stats restates them):
+ *   sum_r        = THE ORDERED SUM (above, "SAC's entropy coefficient on the device") of r[n]: lane t of 1024 starts at +0.0 and adds
+ *                  r[t], r[t + 1024], ... in ascending order, then partial[t] += partial[t + s] for s = 512, ..., 1
+ *   mean         = sum_r / (double)N
+ *   d            = r[n] - mean;  term = d * d                   (the second pass, as np.std takes it; NOT E[r^2] - mean^2)
+ *   sum_d2       = the ordered sum of the terms
+ *   var          = sum_d2 / (double)N                           (the POPULATION variance: callbackFunctions.py:479 uses np.std's default)
+ *   len_sum      = sum of (int64)last[n] + 1                    (exact; an episode's length is its step count, as SB3's evaluate_policy
+ *                                                                counts it)
+ *   mean_length  = (double)len_sum / (double)N
+ *   successes    = the number of succ[n] != 0                   (int32)
+ *   success_rate = (double)successes / (double)N
+ *   improved     = mean > best_mean                             (strict, callbackFunctions.py:504; false for a NaN mean)
+ *   where improved:  best_mean = mean, best_index = eval_index
+ * The standard deviation is NOT computed on the device: a reader takes sqrt(var_return) on the host. */
+typedef struct urgym_eval_record { /* one evaluation */
+  double mean_return;
+  double var_return;
+  double mean_length;
+  double success_rate;
+  double best_mean_after; /* best_mean after the decision */
+  int64_t eval_index;
+  int64_t length_sum;
+  int32_t successes;
+  int32_t count;          /* N */
+  int32_t improved;       /* 0 | 1: the flag urgym_actor_snapshot reads */
+  int32_t reserved0;      /* written as 0 */
+} urgym_eval_record;
+
+/* DEVICE pointers, all required.  The best state starts where the caller puts it (-inf and -1 for "nothing seen yet"). */
+typedef struct urgym_eval_stats_args {
+  int32_t count;                    /* N in [1, URGYM_SAC_TERMS_MAX_COUNT] */
+  int32_t reserved0;                /* must be 0 */
+  int64_t eval_index;               /* >= 0 */
+  const double* episode_return;     /* [N] */
+  const int32_t* episode_last_step; /* [N] */
+  const uint8_t* episode_success;   /* [N] */
+  double* best_mean;                /* [1] read and written */
+  int64_t* best_index;              /* [1] read and written */
+  urgym_eval_record* record;        /* [1] written, 8-byte aligned */
+} urgym_eval_stats_args;
+
+/* ONE launch of ONE workgroup on `stream`: the record and the best state as stated above.  Needs no bound environment.  No allocation,
+ * no host synchronisation, everything validated before the launch.  Refused (URGYM_ERR_ARG, nothing launched, nothing written): NULL
+ * handle or args, a NULL pointer (named), reserved0 != 0, count outside [1, 65536], a negative eval_index. */
+int urgym_eval_stats(void* handle, const urgym_eval_stats_args* args, void* stream);
+
+typedef struct urgym_actor_snapshot_args {
+  int32_t in_features;                /* of both sets of tensors: positive */
+  int32_t hidden_width;               /* positive, at most 512 */
+  urgym_actor_tensors_const source;   /* read; all eight required */
+  urgym_actor_tensors destination;    /* written; all eight required; no tensor may overlap another (not checked) */
+  const int32_t* when;                /* [1] DEVICE flag, or NULL = copy always */
+  int32_t reserved0;                  /* must be 0 */
+} urgym_actor_snapshot_args;
+
+/* ONE launch on `stream`: destination = source, element for element, for all eight tensors -- or, where `when` is given and holds 0
+ * when the launch RUNS, nothing at all.  Refused (URGYM_ERR_ARG): NULL handle or args, a NULL tensor pointer (all sixteen are
+ * required), reserved0 != 0, in_features < 1, hidden_width outside [1, 512]. */
+int urgym_actor_snapshot(void* handle, const urgym_actor_snapshot_args* args, void* stream);
+
+/* One evaluation of `source` on an evaluation environment of its own.  All pointers but eval_actor are DEVICE pointers owned by the
+ * caller, all required; N = the evaluation handle's num_envs. */
+typedef struct urgym_policy_evaluation {
+  void* eval_actor;                 /* urgym_actor_create's, of the EVALUATION handle, of the source's shape */
+  int32_t in_features;              /* of the source and the best tensors */
+  int32_t hidden_width;
+  urgym_actor_tensors_const source; /* the parameters to evaluate, the log_std head included */
+  urgym_actor_tensors best;         /* receives the source where the evaluation improved */
+  double* episode_return;           /* [N] scratch: the rollout's episode summary */
+  int32_t* episode_last_step;       /* [N] */
+  uint8_t* episode_success;         /* [N] */
+  uint8_t* episode_done;            /* [N] */
+  urgym_eval_record* records;       /* [record_capacity] */
+  double* best_mean;                /* [1] */
+  int64_t* best_index;              /* [1] */
+  uint64_t reset_seed;              /* every evaluation starts the SAME episodes: env.reset(seed=reset_seed) */
+  int32_t record_capacity;          /* >= 1 */
+  int32_t num_steps;                /* K >= 1 steps per evaluation */
+  int32_t reserved0;                /* must be 0 */
+} urgym_policy_evaluation;
+
+/* Bit for bit this sequence on `stream`:
+ *   1. urgym_actor_load(eval_handle, eval_actor, the source tensors with the head)
+ *   2. env.reset(seed = reset_seed) on an environment that looks fresh: the bound episode_id and the bound observation zeroed by
+ *      asynchronous memsets, then urgym_reset(eval_handle, NULL, reset_seed).  (urgym_reset leaves the velocity slot of the
+ *      UR5DynReach-v1 observation as it finds it -- the reference's stale ReachDyn.velocity, reach.py:657 -- so a reset depends on
+ *      the observation before it; zeroing it makes EVERY evaluation start from the observations the first one of a new handle sees, and
+ *      two evaluations of the same parameters give the same record.  The other env kinds' resets overwrite the whole row.)
+ *   3. urgym_rollout_actor(eval_handle, eval_actor, num_steps, {episode_return, episode_last_step, episode_success, episode_done})
+ *   4. urgym_eval_stats({N, eval_index, the summary, the best state, &records[record_slot]})
+ *   5. urgym_actor_snapshot({source -> best, when = &records[record_slot].improved})
+ * Everything is validated before the first launch; no allocation, no host synchronisation.  Refused (URGYM_ERR_ARG; URGYM_ERR_STATE for
+ * an evaluation handle without urgym_bind): every refusal of the five calls; a NULL handle, struct or pointer (named); reserved0 != 0;
+ * num_steps < 1; an evaluation handle with auto_reset on (the summary is that of whole first episodes) or with more than 65536 envs; an
+ * eval_actor of another handle, or of another shape than in_features -> hidden_width; record_slot outside [0, record_capacity); a
+ * negative eval_index. */
+int urgym_policy_evaluate(void* eval_handle, const urgym_policy_evaluation* evaluation, int64_t eval_index, int32_t record_slot, void* stream);
+
+typedef struct urgym_sac_evaluation {
+  void* eval_handle;                  /* a second handle on the training handle's device, NOT the training handle */
+  urgym_policy_evaluation evaluation; /* its source tensors must be learner->actor_adam.param */
+  int32_t every;                      /* E >= 1, in updates */
+  int32_t first_record_slot;          /* the j-th evaluation of the call writes records[first_record_slot + j] ... */
+  int64_t first_eval_index;           /* ... with eval_index = first_eval_index + j */
+} urgym_sac_evaluation;
+
+/* The launches of urgym_sac_train with evaluations between iterations.  With G = updates_per_iteration let
+ *   s_i = first_step - 1 + G * (the number of iterations among 0..i that are not idle),   s_{-1} = first_step - 1
+ * -- the Adam steps taken when iteration i ends.  An evaluation follows iteration i exactly where floor(s_i / E) > floor(s_{i-1} / E)
+ * (ur_gym_amd/csrc/urgym_eval_schedule.h; ur_gym_amd.evaluation.evaluation_points restates it): the rule of a loop that evaluates
+ * whenever the update count passes a multiple of E.  The result is bit for bit that of urgym_sac_train on the segments between the
+ * evaluations plus urgym_policy_evaluate at each point; the training side is bit for bit that of urgym_sac_train alone, because an
+ * evaluation writes nothing the training reads.
+ * The reference hands EvalCallback the TRAINING env (train.py:55), so that each evaluation resets the env the collection runs on.  That
+ * quirk is deliberately NOT reproduced: eval_handle == handle is refused.
+ * EVERYTHING is validated before the first launch.  Refused, besides every refusal of urgym_sac_train and urgym_policy_evaluate: a NULL
+ * evaluation or eval_handle; eval_handle == handle; the two handles on different devices; source tensors other than
+ * learner->actor_adam.param; every < 1; a negative first_eval_index or first_record_slot; first_record_slot + the evaluations of the
+ * call beyond record_capacity.  No allocation, no host synchronisation; a launch failure midway as in urgym_sac_train. */
+int urgym_sac_train_evaluated(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_evaluation* evaluation, void* stream);
+
 /* Verification aid, not a hot path: synchronises the device, then copies the object's packed buffer (the kernel's own layout,
  * ur_gym_amd/csrc/urgym_pack_map.h) to host_out and stores its length in floats in *count.  host_out == NULL only reports *count;
  * otherwise capacity (in floats) must be at least that.  Refused: NULL handle / object / count, an object of another handle,

@@ -72,6 +72,14 @@ pair, `loop`, runs one collection step per 4 updates on both routes (--launches 
 tool runs --launches native updates --windows times and nothing else: the program of a kernel-trace run.
     python tools/bench_policy_rollout.py --native --windows 8 --launches 200 --out profiles/policy_rollout/dyn65536_native.json
 
+--evaluate measures the evaluation inside the training call, 1024 evaluation envs x 100 steps, H = 256.
+`one_evaluation`: DeviceEvaluation.evaluate + results() against the route before it, load_parameters + reset(seed) +
+run_closed_loop_device; one evaluation per window, ending in a synchronise and reading its result.  `training_run`: --launches
+updates as --launches / 4 x (1 step, 4 updates) with an evaluation every 40 updates, as ONE SACLearner.train(..., evaluation=,
+eval_every=40) call against one train call per interval plus the Python evaluation.  Alternating windows in one process; median,
+min and max of the wall time in ms; the bar of --native on `one_evaluation`, the ratio reported whatever it is.
+    python tools/bench_policy_rollout.py --evaluate --windows 8 --launches 200 --out profiles/policy_rollout/dyn_evaluation.json
+
 With --refresh: what it costs to hand new weights to a device actor / critic, at hidden width 256 and 512.
 `actor_load`, `critic_load_tau1` and `critic_load_polyak` (tau = 0.005) are load_parameters from device tensors, one launch each;
 `*_host_route` is the only route there was before: every tensor .cpu().numpy(), destroy and create the object (the actor's head by
@@ -1036,6 +1044,106 @@ def native_mode(args):
             f.write(line + "\n")
 
 
+def evaluate_mode(args):
+    """--evaluate: the evaluation inside the training call.  (1) ONE evaluation of 1024 envs x 100 steps ending in
+    a synchronise: DeviceEvaluation.evaluate + results against the route before it, load_parameters + reset(seed) +
+    run_closed_loop_device, in alternating windows.  (2) a training run with an evaluation every E updates: ONE
+    SACLearner.train(..., evaluation=, eval_every=E) call against one train call per interval plus the Python evaluation."""
+    import torch
+
+    from ur_gym_amd import make_vec
+    from ur_gym_amd.evaluation import DeviceActor, DeviceEvaluation, DeviceReplay, run_closed_loop_device
+    from ur_gym_amd.training import SACLearner, host_arrays
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_policy_rollout.py measures on a GPU; none is visible")
+    dev, n, eval_n, K, E, per_step = "cuda:0", min(args.num_envs, 4096), 1024, 100, 40, 4
+    iterations = max(1, args.launches // per_step)  # --launches updates per window, as --native counts them
+    env = make_vec(args.env, num_envs=n, device=dev, seed=0, auto_reset=True)
+    env.reset(seed=0)
+    sync = lambda: torch.cuda.synchronize(env.device)  # noqa: E731
+    options = dict(device_action_gradient=True, device_critic_gradient=True, device_actor_gradient=True, device_optimizer=True, device_entropy=True)
+    sides = {}
+    for label in ("python_evaluate", "native"):
+        learner = SACLearner(env, seed=0, batch_size=256, hidden_width=256, learning_starts=0, **options)
+        replay = DeviceReplay(env, 64)
+        learner.collect(replay, 4)
+        test_env = make_vec(args.env, num_envs=eval_n, device=dev, seed=1, auto_reset=False)
+        side = dict(learner=learner, replay=replay, test_env=test_env, draw=0)
+        if label == "native":
+            side["ev"] = DeviceEvaluation(test_env, learner.actor.tensors(), num_steps=K, seed=1, capacity=max(8, iterations * per_step // E + 2))
+        else:
+            side["actor"] = DeviceActor(host_arrays(learner.actor.tensors()), test_env)
+        sides[label] = side
+
+    def evaluate(label):
+        sd = sides[label]
+        if label == "native":
+            sd["ev"].count = 0
+            sd["ev"].evaluate(sd["learner"].actor.tensors())
+            return sd["ev"].results()[0]["mean_return"]  # synchronises, reads the record
+        sd["actor"].load_parameters(sd["learner"].actor.tensors())  # tools/train_sac.py's evaluate() before this call existed
+        sd["test_env"].reset(seed=1)
+        return run_closed_loop_device(sd["test_env"], sd["actor"], K)["mean_episode_reward"]
+
+    def run(label):
+        sd = sides[label]
+        learner, replay = sd["learner"], sd["replay"]
+        if label == "native":
+            sd["ev"].count = 0
+            learner.train(replay, iterations, 1, per_step, seed=1, first_draw=sd["draw"] + 1, evaluation=sd["ev"], eval_every=E)
+            sd["draw"] += iterations * per_step
+            return [r["mean_return"] for r in sd["ev"].results()]
+        out, left = [], iterations
+        while left > 0:  # one native call per interval, then the Python evaluation: tools/train_sac.py --native before this call existed
+            step = learner.adam_state["step"]
+            trips = min(left, -(-(E - step % E) // per_step))
+            learner.train(replay, trips, 1, per_step, seed=1, first_draw=sd["draw"] + 1)
+            sd["draw"] += trips * per_step
+            left -= trips
+            if learner.adam_state["step"] // E > step // E:
+                out.append(evaluate(label))
+        sync()
+        return out
+
+    def window(fn, label):
+        sync()
+        t0 = time.perf_counter()
+        got = fn(label)
+        sync()
+        return (time.perf_counter() - t0) * 1e3, got
+
+    result = {"tool": "bench_policy_rollout --evaluate", "env": args.env, "num_envs": n, "eval_envs": eval_n, "eval_steps": K, "windows": args.windows,
+              "batch": 256, "hidden_width": 256, "device": torch.cuda.get_device_name(0)}
+    for name, fn in (("one_evaluation", evaluate), ("training_run", run)):
+        for label in sides:
+            fn(label), fn(label)
+        wdw, evaluations = {label: [] for label in sides}, {}
+        for _ in range(args.windows):
+            for label in sides:
+                ms, got = window(fn, label)
+                wdw[label].append(ms)
+                evaluations[label] = len(got) if isinstance(got, list) else 1
+        med = {k: float(np.median(v)) for k, v in wdw.items()}
+        spread = float(max(wdw["python_evaluate"]) - min(wdw["python_evaluate"]))
+        result[name] = {"ms_median": med, "ms_min": {k: float(min(v)) for k, v in wdw.items()}, "ms_max": {k: float(max(v)) for k, v in wdw.items()},
+                        "ms_windows": {k: [round(x, 3) for x in v] for k, v in wdw.items()}, "python_evaluate_ms_spread": spread,
+                        "ratio_native_over_python_evaluate": med["native"] / med["python_evaluate"], "evaluations_per_window": evaluations,
+                        "not_slower": med["native"] <= med["python_evaluate"] + spread}
+    result["training_run"].update(iterations_per_window=iterations, updates_per_iteration=per_step, eval_every=E)
+    for sd in sides.values():
+        (sd.get("ev") or sd.get("actor")).close()
+        sd["learner"].close()
+        sd["test_env"].close()
+    env.close()
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--env", default="UR5DynReach-v1", choices=sorted(ACTOR_NPZ))
@@ -1063,8 +1171,11 @@ def main():
     ap.add_argument("--entropy", action="store_true", help="measure the learner's update with device_optimizer only against the same plus device_entropy (see above)")
     ap.add_argument("--native", action="store_true", help="measure the thirteen-call update against SACLearner.train, one native call per window (see above)")
     ap.add_argument("--native-only", action="store_true", help="--native: run only the native updates, --windows x --launches of them (for a kernel trace)")
+    ap.add_argument("--evaluate", action="store_true", help="measure one evaluation (DeviceEvaluation.evaluate) against load_parameters + reset + run_closed_loop_device, and a training run with evaluations as one call against one call per interval plus the Python evaluation")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.evaluate:
+        return evaluate_mode(args)
     if args.native:
         return native_mode(args)
     if args.entropy:

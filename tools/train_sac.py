@@ -5,8 +5,11 @@ environment, as model_test.py evaluates) every so many updates.
     python tools/train_sac.py --env UR5OriReach-v1 --num-envs 1024 --steps 2000 --updates-per-step 4 --eval-every 200
 
 One loop trip = one env step of all N envs into the ring, then `--updates-per-step` gradient steps.  Prints one JSON line per
-evaluation.  No checkpoint is written.  With --native (and --device-entropy and the options it needs) the trips between two
-evaluations are ONE native call, SACLearner.train: the same launches, bit for bit, with no Python between them.
+evaluation.  With --native (and --device-entropy and the options it needs) the WHOLE run is ONE native call,
+SACLearner.train(..., evaluation=, eval_every=): the same launches, bit for bit, with no Python between them; the evaluations run
+inside the call (evaluation.DeviceEvaluation: statistics, the improvement decision and the copy of the best actor on the device), and
+their records are printed after one synchronise at the end (each evaluation there starts from a zeroed observation buffer, which
+matters on UR5DynReach-v1 alone: its reset keeps the velocity slot it finds).  --save-best PATH writes the best actor as an .npz DeviceActor.load reads.
 """
 import argparse
 import json
@@ -45,14 +48,16 @@ def main():
                     help="step the entropy coefficient and form its uses and the three loss values with two HIP launches: no torch operation "
                          "is left in an update but allocations and views (needs --device-optimizer)")
     ap.add_argument("--native", action="store_true",
-                    help="run the loop between two evaluations as ONE native call (SACLearner.train): no Python between the launches "
+                    help="run the whole loop, evaluations included, as ONE native call (SACLearner.train): no Python between the launches "
                          "(needs --device-entropy)")
+    ap.add_argument("--save-best", metavar="PATH", default=None,
+                    help="write the actor of the best evaluation (mean episode return strictly above every earlier one) as an .npz")
     args = ap.parse_args()
 
     import torch
 
     from ur_gym_amd import make_vec
-    from ur_gym_amd.evaluation import DeviceActor, DeviceReplay, run_closed_loop_device
+    from ur_gym_amd.evaluation import DeviceActor, DeviceEvaluation, DeviceReplay, evaluation_points, run_closed_loop_device, save_actor, warmup_iterations
     from ur_gym_amd.training import SACLearner, host_arrays
 
     if not torch.cuda.is_available():
@@ -67,28 +72,37 @@ def main():
     eval_actor = DeviceActor(host_arrays(learner.actor.tensors()), test_env)  # actors belong to the environment they were made for
     replay = DeviceReplay(env, args.capacity)
     updates, t0 = 0, time.perf_counter()
+    best = dict(mean=-float("inf"), tensors=None)  # the Python route's own best_model
 
     def evaluate():
         eval_actor.load_parameters(learner.actor.tensors())
         test_env.reset(seed=args.seed + 1)
         res = run_closed_loop_device(test_env, eval_actor)
+        if args.save_best and res["mean_episode_reward"] > best["mean"]:  # strictly above, as the reference's EvalCallback decides
+            best.update(mean=res["mean_episode_reward"], tensors=host_arrays(learner.actor.tensors()))
         print(json.dumps({"updates": updates, "env_steps": learner.env_steps * env.num_envs, "seconds": round(time.perf_counter() - t0, 1),
                           "mean_episode_return": res["mean_episode_reward"], "success_rate_percent": res["success_rate_percent"]}), flush=True)
 
     step = 0
-    while args.native and step < args.steps:
-        # as many loop trips as reach the next evaluation, in one call (warm-up trips run no update, so a call may fall short of it and
-        # the next one goes on); an evaluation falls at the end of the trip that passes a multiple of --eval-every
-        per_trip = max(1, args.updates_per_step)
-        trips = min(args.steps - step, -(-(args.eval_every - updates % args.eval_every) // per_trip))
-        before = learner.adam_state["step"]
-        learner.train(replay, trips, 1, args.updates_per_step, seed=args.seed, first_draw=updates)
-        step += trips
-        done = learner.adam_state["step"] - before
-        passed = (updates + done) // args.eval_every > updates // args.eval_every
-        updates += done
-        if passed:
-            evaluate()
+    if args.native:
+        # one call for the whole run: an evaluation falls at the end of every trip in which the update count passes a multiple of
+        # --eval-every (evaluation.evaluation_points); warm-up trips run no update
+        _, idle = warmup_iterations(learner.env_steps, env.num_envs, learner.hp["learning_starts"], args.steps, 1)
+        points = evaluation_points(1, args.steps, args.updates_per_step, idle, args.eval_every) if args.steps > 0 else []
+        ev = DeviceEvaluation(test_env, learner.actor.tensors(), seed=args.seed + 1, capacity=max(1, len(points)))
+        if args.steps > 0:
+            learner.train(replay, args.steps, 1, args.updates_per_step, seed=args.seed, first_draw=0, evaluation=ev, eval_every=args.eval_every)
+        seconds = None
+        for trip, rec in zip(points, ev.results()):  # results() synchronises, once
+            seconds = round(time.perf_counter() - t0, 1) if seconds is None else seconds
+            done = max(0, trip + 1 - idle) * args.updates_per_step
+            print(json.dumps({"updates": done, "env_steps": (trip + 1) * env.num_envs, "seconds": seconds, "mean_episode_return": rec["mean_return"],
+                              "success_rate_percent": 100.0 * rec["success_rate"], "std_episode_return": rec["std_return"],
+                              "mean_episode_length": rec["mean_length"], "improved": bool(rec["improved"])}), flush=True)
+        if args.save_best and ev.best_state()[1] >= 0:
+            ev.save_best(args.save_best)
+        ev.close()
+        step = args.steps
     for step in range(step, args.steps):  # the Python loop (every trip of it where --native is off)
         learner.collect(replay, 1)
         if learner.env_steps * env.num_envs < learner.hp["learning_starts"]:
@@ -98,6 +112,8 @@ def main():
             updates += 1
             if updates % args.eval_every == 0:
                 evaluate()
+    if args.save_best and best["tensors"] is not None:
+        save_actor(args.save_best, best["tensors"])
     eval_actor.close()
     learner.close()
     test_env.close()

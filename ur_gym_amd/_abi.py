@@ -345,6 +345,45 @@ class SacLearner(C.Structure):
                 ("eps", C.c_double)]
 
 
+class EvalRecord(C.Structure):
+    """urgym_eval_record: one evaluation as the device reduced it (include/urgym.h states every float); 72 bytes, 8-byte aligned."""
+    _fields_ = [(name, C.c_double) for name in ("mean_return", "var_return", "mean_length", "success_rate", "best_mean_after")] + \
+               [("eval_index", C.c_int64), ("length_sum", C.c_int64)] + \
+               [(name, C.c_int32) for name in ("successes", "count", "improved", "reserved0")]
+
+
+EVAL_RECORD_WORDS = 9  # an EvalRecord as int64 words: how a torch tensor holds an array of them
+EVAL_MAX_COUNT = SAC_TERMS_MAX_COUNT  # the cap on the evaluation envs: one workgroup reduces them
+
+
+class EvalStatsArgs(C.Structure):
+    """urgym_eval_stats_args: the three episode arrays, the best state (read and written) and the record to write; DEVICE pointers."""
+    _fields_ = [("count", C.c_int32), ("reserved0", C.c_int32), ("eval_index", C.c_int64), ("episode_return", C.POINTER(C.c_double)),
+                ("episode_last_step", C.POINTER(C.c_int32)), ("episode_success", C.POINTER(C.c_uint8)), ("best_mean", C.POINTER(C.c_double)),
+                ("best_index", C.POINTER(C.c_int64)), ("record", C.POINTER(EvalRecord))]
+
+
+class ActorSnapshotArgs(C.Structure):
+    """urgym_actor_snapshot_args: source -> destination, all sixteen tensors, under the DEVICE flag `when` (NULL = always)."""
+    _fields_ = [("in_features", C.c_int32), ("hidden_width", C.c_int32), ("source", ActorTensors), ("destination", ActorTensors),
+                ("when", C.POINTER(C.c_int32)), ("reserved0", C.c_int32)]
+
+
+class PolicyEvaluation(C.Structure):
+    """urgym_policy_evaluation: the eval actor, the source and the best tensors, the [N] scratch, the records and the best state."""
+    _fields_ = [("eval_actor", C.c_void_p), ("in_features", C.c_int32), ("hidden_width", C.c_int32), ("source", ActorTensors), ("best", ActorTensors),
+                ("episode_return", C.POINTER(C.c_double)), ("episode_last_step", C.POINTER(C.c_int32)), ("episode_success", C.POINTER(C.c_uint8)),
+                ("episode_done", C.POINTER(C.c_uint8)), ("records", C.POINTER(EvalRecord)), ("best_mean", C.POINTER(C.c_double)),
+                ("best_index", C.POINTER(C.c_int64)), ("reset_seed", C.c_uint64), ("record_capacity", C.c_int32), ("num_steps", C.c_int32),
+                ("reserved0", C.c_int32)]
+
+
+class SacEvaluation(C.Structure):
+    """urgym_sac_evaluation: the evaluation handle, the evaluation, the interval in updates and where the call's records start."""
+    _fields_ = [("eval_handle", C.c_void_p), ("evaluation", PolicyEvaluation), ("every", C.c_int32), ("first_record_slot", C.c_int32),
+                ("first_eval_index", C.c_int64)]
+
+
 # Every symbol include/urgym.h declares (tests check that the built library exports each of them).
 EXPORTED_SYMBOLS = [
     "urgym_abi_version",
@@ -382,6 +421,10 @@ EXPORTED_SYMBOLS = [
     "urgym_sac_entropy_step",
     "urgym_sac_policy_terms",
     "urgym_sac_train",
+    "urgym_eval_stats",
+    "urgym_actor_snapshot",
+    "urgym_policy_evaluate",
+    "urgym_sac_train_evaluated",
     "urgym_actor_read_packed",
     "urgym_critic_read_packed",
     "urgym_refresh",

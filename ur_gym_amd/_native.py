@@ -90,6 +90,10 @@ def lib():
     L.urgym_sac_entropy_step.argtypes = [C.c_void_p, C.POINTER(_abi.SacEntropyArgs), C.POINTER(_abi.AdamHyper), C.c_void_p]
     L.urgym_sac_policy_terms.argtypes = [C.c_void_p, C.POINTER(_abi.SacPolicyArgs), C.c_void_p]
     L.urgym_sac_train.argtypes = [C.c_void_p, C.POINTER(_abi.SacLearner), C.POINTER(_abi.SacSchedule), C.c_void_p]
+    L.urgym_eval_stats.argtypes = [C.c_void_p, C.POINTER(_abi.EvalStatsArgs), C.c_void_p]
+    L.urgym_actor_snapshot.argtypes = [C.c_void_p, C.POINTER(_abi.ActorSnapshotArgs), C.c_void_p]
+    L.urgym_policy_evaluate.argtypes = [C.c_void_p, C.POINTER(_abi.PolicyEvaluation), C.c_int64, C.c_int32, C.c_void_p]
+    L.urgym_sac_train_evaluated.argtypes = [C.c_void_p, C.POINTER(_abi.SacLearner), C.POINTER(_abi.SacSchedule), C.POINTER(_abi.SacEvaluation), C.c_void_p]
     L.urgym_actor_read_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.urgym_critic_read_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.urgym_refresh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]

@@ -1,6 +1,6 @@
 // urgym_policy_abi.hip — the learner's half of the C-ABI of include/urgym.h: actors (create / forward / sample / rollouts), the replay
-// ring, the weight reloads, the twin critic and its two gradients, the actor's parameter gradients, the Adam steps, SAC's entropy step and loss terms, and the training loop that composes them in one call (urgym_sac_train; its index arithmetic is urgym_sac_schedule.h).  Host code only: every check is made here, before the first launch,
-// and every launch goes through urgym_actor.h, urgym_critic.h, urgym_replay.h, urgym_weights.h, urgym_adam.h and urgym_sac_terms.h, or through do_step of urgym_hip.hip
+// ring, the weight reloads, the twin critic and its two gradients, the actor's parameter gradients, the Adam steps, SAC's entropy step and loss terms, the training loop that composes them in one call (urgym_sac_train; its index arithmetic is urgym_sac_schedule.h), and the evaluation inside that call (urgym_eval_stats, urgym_actor_snapshot, urgym_policy_evaluate, urgym_sac_train_evaluated; urgym_eval.h, urgym_eval_schedule.h).  Host code only: every check is made here, before the first launch,
+// and every launch goes through urgym_actor.h, urgym_critic.h, urgym_replay.h, urgym_weights.h, urgym_adam.h, urgym_sac_terms.h and urgym_eval.h, or through do_step of urgym_hip.hip
 // (urgym_handle.h).  No kernel lives in this unit, so adding a check here leaves the step kernels' object file alone.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -19,6 +19,8 @@
 #include "urgym_adam.h"
 #include "urgym_sac_terms.h"
 #include "urgym_sac_schedule.h"
+#include "urgym_eval.h"
+#include "urgym_eval_schedule.h"
 
 using namespace urgym;
 
@@ -865,16 +867,34 @@ struct LearnerPointer {
 };
 
 // after the launches of one stage: urgym_last_error names the iteration and the stage
-int train_stage(Handle* h, int iteration, const char* stage) {
+int train_stage(Handle* h, const char* who, int iteration, const char* stage) {
   const hipError_t e = hipGetLastError();
   if (e == hipSuccess) return URGYM_OK;
-  return failf(h, URGYM_ERR_HIP, "urgym_sac_train: iteration %d, %s: %s", iteration, stage, hipGetErrorString(e));
+  return failf(h, URGYM_ERR_HIP, "%s: iteration %d, %s: %s", who, iteration, stage, hipGetErrorString(e));
 }
+
+// What urgym_sac_train_evaluated hangs into the body of urgym_sac_train; urgym_sac_train itself passes none (null).  before_launch runs
+// after every check of the body and before its first launch: the check-only half of the body ends there, and a refusal of the hook
+// leaves nothing launched.  after_iteration runs after the launches of iteration i.
+struct TrainHooks {
+  int (*before_launch)(void* ctx);
+  int (*after_iteration)(void* ctx, int i);
+  void* ctx;
+};
+
+int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, void* stream, const TrainHooks* hooks);
 
 }  // namespace
 
 int urgym_sac_train(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, void* stream) {
-  const char* who = "urgym_sac_train";
+  return sac_train_body("urgym_sac_train", handle, learner, schedule, stream, nullptr);
+}
+
+}  // extern "C"
+
+namespace {
+
+int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, void* stream, const TrainHooks* hooks) {
   Handle* h = (Handle*)handle;
   if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
   if (!learner) return fail_in(h, URGYM_ERR_ARG, who, "null learner");
@@ -920,11 +940,16 @@ int urgym_sac_train(void* handle, const urgym_sac_learner* learner, const urgym_
     if (!rc) return rc;
     char was[160];
     snprintf(was, sizeof(was), "%s", h->err);
-    return failf(h, rc, "urgym_sac_train: iteration %d, collect: %s", i, was);
+    return failf(h, rc, "%s: iteration %d, collect: %s", who, i, was);
   };
   if (updates == 0) {  // the sequence holds no update call: nothing more to check
-    for (int i = 0; i < S.num_iterations; i++)
+    if (hooks)
+      if (int rc = hooks->before_launch(hooks->ctx)) return rc;
+    for (int i = 0; i < S.num_iterations; i++) {
       if (int rc = collect(i, sac_schedule_iteration(S, i))) return rc;
+      if (hooks)
+        if (int rc = hooks->after_iteration(hooks->ctx, i)) return rc;
+    }
     return URGYM_OK;
   }
   const SacIteration view = sac_schedule_iteration(S, S.idle_iterations);  // what the first update sees
@@ -994,49 +1019,281 @@ int urgym_sac_train(void* handle, const urgym_sac_learner* learner, const urgym_
   ActorAdamStep actor_step;
   if (int rc = check_actor_adam(h, L.actor, &L.actor_adam, &hp, who, &actor_step)) return rc;
 
+  if (hooks)
+    if (int rc = hooks->before_launch(hooks->ctx)) return rc;
+
   // ---- the launching halves: nothing below refuses
   int64_t u = 0;
   for (int i = 0; i < S.num_iterations; i++) {
     const SacIteration it = sac_schedule_iteration(S, i);
     if (K > 0)
       if (int rc = collect(i, it)) return rc;
-    if (it.idle) continue;
+    if (it.idle) {
+      if (hooks)
+        if (int rc = hooks->after_iteration(hooks->ctx, i)) return rc;
+      continue;
+    }
     gather.oldest_slot = it.oldest_slot, gather.size = (uint64_t)it.filled_steps * (uint64_t)h->cfg.num_envs;
     for (int g = 0; g < G; g++, u++) {
       const SacUpdate up = sac_schedule_update(S, u);
       const AdamCoef coef = adam_coefficients(L.lr, L.beta1, L.beta2, L.eps, up.adam_step);  // urgym_adam_coefficients' own function
       gather.draw = up.gather_draw;
       replay_gather_launch(gather, s);
-      if (int rc = train_stage(h, i, "replay_sample")) return rc;
+      if (int rc = train_stage(h, who, i, "replay_sample")) return rc;
       next_sample.smp.draw = up.gather_draw;
       policy_launch(next_sample.a, next_sample.env, next_sample.actions, nullptr, next_sample.smp, s);
-      if (int rc = train_stage(h, i, "actor_sample_rows (next rows)")) return rc;
+      if (int rc = train_stage(h, who, i, "actor_sample_rows (next rows)")) return rc;
       critic_launch(target, bootstrap, s);
-      if (int rc = train_stage(h, i, "critic_evaluate")) return rc;
+      if (int rc = train_stage(h, who, i, "critic_evaluate")) return rc;
       policy_sample.smp.draw = up.policy_draw;
       policy_launch(policy_sample.a, policy_sample.env, policy_sample.actions, nullptr, policy_sample.smp, s);
-      if (int rc = train_stage(h, i, "actor_sample_rows (batch rows)")) return rc;
+      if (int rc = train_stage(h, who, i, "actor_sample_rows (batch rows)")) return rc;
       entropy.c = coef, entropy.loss_out = L.ent_coef_loss + up.loss_slot;
       sac_entropy_launch(entropy, s);
-      if (int rc = train_stage(h, i, "sac_entropy_step")) return rc;
+      if (int rc = train_stage(h, who, i, "sac_entropy_step")) return rc;
       critic_backward_launch(online, critic_backward, s);
-      if (int rc = train_stage(h, i, "critic_parameter_gradients")) return rc;
+      if (int rc = train_stage(h, who, i, "critic_parameter_gradients")) return rc;
       critic_adam_launch(critic_step.buf, &critic_step.target_buf, critic_step.T, coef, critic_step.tau, s);
-      if (int rc = train_stage(h, i, "critic_adam_step")) return rc;
+      if (int rc = train_stage(h, who, i, "critic_adam_step")) return rc;
       critic_grad_launch(online_grad, action_gradient, s);
-      if (int rc = train_stage(h, i, "critic_action_gradient")) return rc;
+      if (int rc = train_stage(h, who, i, "critic_action_gradient")) return rc;
       terms_call.critic_loss_out = L.critic_loss + up.loss_slot, terms_call.actor_loss_out = L.actor_loss + up.loss_slot;
       sac_policy_launch(terms_call, s);
-      if (int rc = train_stage(h, i, "sac_policy_terms")) return rc;
+      if (int rc = train_stage(h, who, i, "sac_policy_terms")) return rc;
       actor_backward.draw = up.policy_draw;
       actor_backward_launch(actor, actor_backward, s);
-      if (int rc = train_stage(h, i, "actor_parameter_gradients")) return rc;
+      if (int rc = train_stage(h, who, i, "actor_parameter_gradients")) return rc;
       actor_adam_launch(actor_step.buf, actor_step.T, coef, s);
-      if (int rc = train_stage(h, i, "actor_adam_step")) return rc;
+      if (int rc = train_stage(h, who, i, "actor_adam_step")) return rc;
       actor_mark_log_std(actor_step.a);  // as urgym_actor_adam_step; the checks above have required the head already
     }
+    if (hooks)
+      if (int rc = hooks->after_iteration(hooks->ctx, i)) return rc;
   }
   return URGYM_OK;
+}
+
+// ---- evaluation inside the training call (include/urgym.h, urgym_eval_stats ... urgym_sac_train_evaluated).
+// As above each entry point is a checking half, which launches nothing and fills the launch struct of urgym_eval.h, and a launching
+// half, which refuses nothing.
+
+int check_eval_stats(Handle* h, const urgym_eval_stats_args* args, const char* who, EvalStatsCall* out) {
+  static_assert(sizeof(urgym_eval_record) == 72 && alignof(urgym_eval_record) == 8, "include/urgym.h");
+  if (!args) return fail_in(h, URGYM_ERR_ARG, who, "null args");
+  const urgym_eval_stats_args& a = *args;
+  if (a.reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "urgym_eval_stats_args.reserved0 must be 0");
+  if (a.count < 1 || a.count > SAC_TERMS_MAX_COUNT) return fail_in(h, URGYM_ERR_ARG, who, "count must be in [1, URGYM_SAC_TERMS_MAX_COUNT] (65536)");
+  if (a.eval_index < 0) return fail_in(h, URGYM_ERR_ARG, who, "eval_index is negative");
+  const LearnerPointer required[] = {{"episode_return", a.episode_return}, {"episode_last_step", a.episode_last_step}, {"episode_success", a.episode_success},
+                                     {"best_mean", a.best_mean},           {"best_index", a.best_index},               {"record", a.record}};
+  for (const LearnerPointer& r : required)
+    if (!r.p) return failf(h, URGYM_ERR_ARG, "%s: urgym_eval_stats_args.%s is null", who, r.name);
+  if ((uintptr_t)a.record % 8 != 0 || (uintptr_t)a.best_mean % 8 != 0 || (uintptr_t)a.best_index % 8 != 0 || (uintptr_t)a.episode_return % 8 != 0)
+    return fail_in(h, URGYM_ERR_ARG, who, "record, best_mean, best_index and episode_return must be 8-byte aligned");
+  *out = EvalStatsCall{a.count, a.eval_index, a.episode_return, a.episode_last_step, a.episode_success, a.best_mean, a.best_index, a.record};
+  return URGYM_OK;
+}
+
+int check_actor_snapshot(Handle* h, const urgym_actor_snapshot_args* args, const char* who, ActorSnapshotCall* out) {
+  if (!args) return fail_in(h, URGYM_ERR_ARG, who, "null args");
+  const urgym_actor_snapshot_args& a = *args;
+  if (a.reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "urgym_actor_snapshot_args.reserved0 must be 0");
+  if (a.in_features < 1) return fail_in(h, URGYM_ERR_ARG, who, "in_features must be positive");
+  if (a.hidden_width < 1 || a.hidden_width > 512) return fail_in(h, URGYM_ERR_ARG, who, "hidden_width must be in [1, 512]");
+  const urgym_actor_tensors_const& f = a.source;
+  const urgym_actor_tensors& t = a.destination;
+  const float* const src[ACTOR_SNAPSHOT_TENSORS] = {f.w0, f.b0, f.w1, f.b1, f.w_mu, f.b_mu, f.w_log_std, f.b_log_std};
+  float* const dst[ACTOR_SNAPSHOT_TENSORS] = {t.w0, t.b0, t.w1, t.b1, t.w_mu, t.b_mu, t.w_log_std, t.b_log_std};
+  for (int i = 0; i < ACTOR_SNAPSHOT_TENSORS; i++) {
+    if (!src[i] || !dst[i]) return fail_in(h, URGYM_ERR_ARG, who, "a tensor pointer is null (all sixteen are required)");
+    out->src[i] = src[i], out->dst[i] = dst[i];
+  }
+  actor_snapshot_offsets(a.in_features, a.hidden_width, out->first);
+  out->when = a.when;
+  return URGYM_OK;
+}
+
+// what urgym_policy_evaluate launches: the five calls of its sequence, checked
+struct PolicyEvaluation {
+  Handle* eh;
+  Actor* actor;
+  ActorPacked buf;
+  const float* src[PACK_ACTOR_TENSORS];
+  urgym_trajectory traj;
+  int num_steps;
+  uint64_t reset_seed;
+  urgym_eval_record* records;
+  EvalStatsCall stats;       // record and eval_index move per evaluation
+  ActorSnapshotCall snapshot;  // when moves per evaluation
+};
+
+// Every check of urgym_policy_evaluate but those of eval_index and record_slot (check_evaluation_slot).  Messages go to `report` -- the
+// evaluation handle itself, or the training handle of urgym_sac_train_evaluated.
+int check_policy_evaluation(Handle* report, Handle* eh, const urgym_policy_evaluation* evaluation, const char* who, PolicyEvaluation* out) {
+  static_assert(PACK_ACTOR_TENSORS == ACTOR_SNAPSHOT_TENSORS, "urgym_actor_tensors' eight");
+  if (!eh) return fail_in(report, URGYM_ERR_ARG, who, "null evaluation handle");
+  if (!eh->bound) return fail_in(report, URGYM_ERR_STATE, who, "urgym_bind() has not been called on the evaluation handle");
+  if (!evaluation) return fail_in(report, URGYM_ERR_ARG, who, "null evaluation");
+  const urgym_policy_evaluation& e = *evaluation;
+  if (e.reserved0 != 0) return fail_in(report, URGYM_ERR_ARG, who, "urgym_policy_evaluation.reserved0 must be 0");
+  if (eh->cfg.auto_reset) return fail_in(report, URGYM_ERR_ARG, who, "the evaluation handle has auto_reset on (the episode summary is that of whole first episodes)");
+  if (eh->cfg.num_envs > SAC_TERMS_MAX_COUNT) return fail_in(report, URGYM_ERR_ARG, who, "the evaluation handle has more than 65536 envs (URGYM_SAC_TERMS_MAX_COUNT)");
+  if (e.num_steps < 1) return fail_in(report, URGYM_ERR_ARG, who, "num_steps must be at least 1");
+  if (e.record_capacity < 1) return fail_in(report, URGYM_ERR_ARG, who, "record_capacity must be at least 1");
+  if (!e.eval_actor) return fail_in(report, URGYM_ERR_ARG, who, "urgym_policy_evaluation.eval_actor is null");
+  Actor* a = member(eh->actors, e.eval_actor);
+  if (!a) return fail_in(report, URGYM_ERR_ARG, who, "eval_actor is not an actor of the evaluation handle (actors belong to the handle they were created with)");
+  if (actor_in_features(a) != actor_features(eh))
+    return failf(report, URGYM_ERR_ARG, "%s: the eval actor takes %d features, the evaluation env kind offers %d", who, actor_in_features(a), actor_features(eh));
+  const ActorPacked buf = actor_packed(a);
+  if (e.in_features != buf.in_features || e.hidden_width != buf.hidden)
+    return failf(report, URGYM_ERR_ARG, "%s: the source is %d -> %d, the eval actor is %d -> %d", who, e.in_features, e.hidden_width, buf.in_features, buf.hidden);
+  const LearnerPointer required[] = {{"episode_return", e.episode_return}, {"episode_last_step", e.episode_last_step}, {"episode_success", e.episode_success},
+                                     {"episode_done", e.episode_done},     {"records", e.records},                     {"best_mean", e.best_mean},
+                                     {"best_index", e.best_index}};
+  for (const LearnerPointer& r : required)
+    if (!r.p) return failf(report, URGYM_ERR_ARG, "%s: urgym_policy_evaluation.%s is null", who, r.name);
+  PolicyEvaluation& c = *out;
+  memset(&c, 0, sizeof(c));
+  // the snapshot's checks: all sixteen tensors, the shape
+  urgym_actor_snapshot_args sa;
+  memset(&sa, 0, sizeof(sa));
+  sa.in_features = e.in_features, sa.hidden_width = e.hidden_width, sa.source = e.source, sa.destination = e.best;
+  if (int rc = check_actor_snapshot(report, &sa, who, &c.snapshot)) return rc;
+  // the statistics' checks, on slot 0 (every slot has its alignment: the record is a multiple of 8 bytes)
+  urgym_eval_stats_args ea;
+  memset(&ea, 0, sizeof(ea));
+  ea.count = eh->cfg.num_envs, ea.episode_return = e.episode_return, ea.episode_last_step = e.episode_last_step, ea.episode_success = e.episode_success;
+  ea.best_mean = e.best_mean, ea.best_index = e.best_index, ea.record = e.records;
+  if (int rc = check_eval_stats(report, &ea, who, &c.stats)) return rc;
+  c.eh = eh, c.actor = a, c.buf = buf;
+  for (int i = 0; i < PACK_ACTOR_TENSORS; i++) c.src[i] = c.snapshot.src[i];  // urgym_actor_load's order is urgym_actor_tensors'
+  c.traj.episode_return = e.episode_return, c.traj.episode_last_step = e.episode_last_step;
+  c.traj.episode_success = e.episode_success, c.traj.episode_done = e.episode_done;
+  c.num_steps = e.num_steps, c.reset_seed = e.reset_seed, c.records = e.records;
+  return URGYM_OK;
+}
+
+int check_evaluation_slot(Handle* report, const urgym_policy_evaluation& e, int64_t eval_index, int32_t record_slot, const char* who) {
+  if (eval_index < 0) return fail_in(report, URGYM_ERR_ARG, who, "eval_index is negative");
+  if (record_slot < 0 || record_slot >= e.record_capacity) return fail_in(report, URGYM_ERR_ARG, who, "record_slot outside [0, record_capacity)");
+  return URGYM_OK;
+}
+
+// the launching half: the five calls on `s`.  A failure leaves its message in the evaluation handle.
+int launch_policy_evaluation(PolicyEvaluation& c, int64_t eval_index, int32_t record_slot, hipStream_t s) {
+  Handle* eh = c.eh;
+  HIP_TRY(eh, hipSetDevice(eh->device));
+  actor_pack_launch(c.buf, c.src, s);  // urgym_actor_load with both head pointers
+  HIP_TRY(eh, hipGetLastError());
+  actor_mark_log_std(c.actor);
+  // env.reset(seed=): a seeded reset of every env rewinds the episode counters, so that it starts the same episodes every time
+  HIP_TRY(eh, hipMemsetAsync(eh->buf.episode_id, 0, sizeof(int32_t) * (size_t)eh->cfg.num_envs, s));
+  // ... and on an environment that looks fresh: RESET leaves the velocity slot of the UR5DynReach-v1 observation as it finds it (the
+  // reference's stale ReachDyn.velocity, reach.py:657), so without this the first evaluation of a handle would see zeros there and every
+  // later one the twist of the previous evaluation's last step -- other first observations, other returns, no fair comparison
+  HIP_TRY(eh, hipMemsetAsync(eh->buf.observation, 0, sizeof(float) * (size_t)eh->cfg.num_envs * (size_t)eh->obs_dim, s));
+  if (int rc = urgym_reset(eh, nullptr, c.reset_seed, s)) return rc;
+  if (int rc = rollout(eh, c.actor, nullptr, c.num_steps, RolloutSinks{&c.traj, nullptr, nullptr, 0}, s)) return rc;
+  urgym_eval_record* record = c.records + record_slot;
+  c.stats.eval_index = eval_index, c.stats.record = record;
+  eval_stats_launch(c.stats, s);
+  HIP_TRY(eh, hipGetLastError());
+  c.snapshot.when = &record->improved;
+  actor_snapshot_launch(c.snapshot, s);
+  return launched(eh);
+}
+
+// urgym_sac_train_evaluated's hooks into sac_train_body
+struct TrainEvaluation {
+  Handle* h;
+  const urgym_sac_learner* learner;
+  const urgym_sac_schedule* schedule;
+  const urgym_sac_evaluation* evaluation;
+  hipStream_t s;
+  PolicyEvaluation call;
+  int64_t done;  // evaluations launched so far
+};
+
+const char* const TRAIN_EVALUATED = "urgym_sac_train_evaluated";
+
+// runs after every check of the training body (so the learner and the schedule are sound) and before its first launch
+int train_evaluation_check(void* ctx) {
+  TrainEvaluation& t = *(TrainEvaluation*)ctx;
+  const char* who = TRAIN_EVALUATED;
+  Handle* h = t.h;
+  const urgym_sac_evaluation& E = *t.evaluation;
+  Handle* eh = (Handle*)E.eval_handle;
+  if (!eh) return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_evaluation.eval_handle is null");
+  if (eh == h) return fail_in(h, URGYM_ERR_ARG, who, "eval_handle is the training handle (an evaluation would reset the training env; evaluation on it is not supported)");
+  if (eh->device != h->device) return fail_in(h, URGYM_ERR_ARG, who, "the training handle and the evaluation handle are on different devices");
+  if (int rc = check_policy_evaluation(h, eh, &E.evaluation, who, &t.call)) return rc;
+  const urgym_actor_tensors& p = t.learner->actor_adam.param;
+  const float* const params[PACK_ACTOR_TENSORS] = {p.w0, p.b0, p.w1, p.b1, p.w_mu, p.b_mu, p.w_log_std, p.b_log_std};
+  for (int i = 0; i < PACK_ACTOR_TENSORS; i++)
+    if (t.call.src[i] != params[i]) return fail_in(h, URGYM_ERR_ARG, who, "the evaluation's source tensors are not learner->actor_adam.param");
+  if (t.learner->actor_adam.in_features != E.evaluation.in_features || t.learner->actor_adam.hidden_width != E.evaluation.hidden_width)
+    return fail_in(h, URGYM_ERR_ARG, who, "the evaluation's shape is not learner->actor_adam's");
+  if (const char* what = eval_schedule_refusal(*t.schedule, E.every, E.first_eval_index, E.first_record_slot, E.evaluation.record_capacity))
+    return fail_in(h, URGYM_ERR_ARG, who, what);
+  return URGYM_OK;
+}
+
+int train_evaluation_after(void* ctx, int i) {
+  TrainEvaluation& t = *(TrainEvaluation*)ctx;
+  const urgym_sac_evaluation& E = *t.evaluation;
+  if (!eval_follows(*t.schedule, E.every, i)) return URGYM_OK;
+  const int rc = launch_policy_evaluation(t.call, E.first_eval_index + t.done, (int32_t)(E.first_record_slot + t.done), t.s);
+  t.done++;
+  if (!rc) {
+    HIP_TRY(t.h, hipSetDevice(t.h->device));  // the same device: what the launches of the next iteration expect to be current
+    return rc;
+  }
+  return failf(t.h, rc, "%s: iteration %d, evaluation: %.150s", TRAIN_EVALUATED, i, t.call.eh->err);
+}
+
+}  // namespace
+
+extern "C" {
+
+int urgym_eval_stats(void* handle, const urgym_eval_stats_args* args, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  EvalStatsCall c;
+  if (int rc = check_eval_stats(h, args, "urgym_eval_stats", &c)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  eval_stats_launch(c, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_actor_snapshot(void* handle, const urgym_actor_snapshot_args* args, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  ActorSnapshotCall c;
+  if (int rc = check_actor_snapshot(h, args, "urgym_actor_snapshot", &c)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  actor_snapshot_launch(c, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_policy_evaluate(void* eval_handle, const urgym_policy_evaluation* evaluation, int64_t eval_index, int32_t record_slot, void* stream) {
+  const char* who = "urgym_policy_evaluate";
+  Handle* eh = (Handle*)eval_handle;
+  if (!eh) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  PolicyEvaluation c;
+  if (int rc = check_policy_evaluation(eh, eh, evaluation, who, &c)) return rc;
+  if (int rc = check_evaluation_slot(eh, *evaluation, eval_index, record_slot, who)) return rc;
+  return launch_policy_evaluation(c, eval_index, record_slot, (hipStream_t)stream);
+}
+
+int urgym_sac_train_evaluated(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_evaluation* evaluation, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (!evaluation) return fail_in(h, URGYM_ERR_ARG, TRAIN_EVALUATED, "null evaluation");
+  TrainEvaluation t;
+  t.h = h, t.learner = learner, t.schedule = schedule, t.evaluation = evaluation, t.s = (hipStream_t)stream, t.done = 0;
+  const TrainHooks hooks{train_evaluation_check, train_evaluation_after, &t};
+  return sac_train_body(TRAIN_EVALUATED, handle, learner, schedule, stream, &hooks);
 }
 
 }  // extern "C"

@@ -253,15 +253,16 @@ def adam_step(p, g, m, v, coef):
     return p_new, m_new, v_new
 
 
-def ordered_sum(terms):
+def ordered_sum(terms, dtype=np.float32):
     """THE ORDERED SUM of include/urgym.h ("SAC's entropy coefficient on the device") in numpy: `terms` is a float32 [count] array;
     lane t of 1024 starts at +0.0 and adds terms t, t + 1024, ... in ascending order in float64, then the partials are folded with
-    ``partial[t] += partial[t + s]`` for s = 512, ..., 1.  Returns the float64 sum; the order depends on nothing but count."""
+    ``partial[t] += partial[t + s]`` for s = 512, ..., 1.  Returns the float64 sum; the order depends on nothing but count.
+    ``dtype=np.float64`` takes float64 terms instead (the evaluation statistics' returns): the same lanes, the same order."""
     from ._abi import SAC_TERMS_LANES as L
 
     terms = np.asarray(terms)
-    if terms.dtype != np.float32 or terms.ndim != 1:
-        raise ValueError(f"terms must be a float32 [count] array, got {terms.dtype} {terms.shape}")
+    if terms.dtype != np.dtype(dtype) or np.dtype(dtype) not in (np.dtype(np.float32), np.dtype(np.float64)) or terms.ndim != 1:
+        raise ValueError(f"terms must be a {np.dtype(dtype)} [count] array, got {terms.dtype} {terms.shape}")
     partial = np.zeros(L, np.float64)
     with np.errstate(all="ignore"):
         for first in range(0, terms.size, L):  # every lane's next term, ascending
@@ -1017,3 +1018,186 @@ def run_closed_loop_device(env, actor, max_steps=100):
     last = rec["episode_last_step"].cpu().numpy().astype(np.float64)
     return {"success_rate_percent": 100.0 * success.mean(), "mean_episode_reward": float(reward.mean()),
             "mean_last_step_index": float(last.mean()), "success": success, "reward": reward, "last_step": last}
+
+
+# ------------------------------------------------------------------------------------------------ evaluation inside the training call
+def evaluation_stats(returns, last_step, success, best_mean, best_index, eval_index):
+    """THE STATISTICS of include/urgym.h ("evaluation inside the training call") in numpy, bitwise what urgym_eval_stats writes:
+    `returns` float64 [N], `last_step` int32 [N], `success` uint8 or bool [N]; every line one float64 operation.  Returns a dict with
+    the fields of ``urgym_eval_record`` (and ``std_return = sqrt(var_return)``, which the device does not compute) and the best state
+    afterwards under ``best_mean`` and ``best_index``."""
+    r, last, succ = np.asarray(returns), np.asarray(last_step), np.asarray(success)
+    if r.dtype != np.float64 or r.ndim != 1 or r.size < 1:
+        raise ValueError(f"returns must be a float64 [N] array with N >= 1, got {r.dtype} {r.shape}")
+    if last.dtype != np.int32 or last.shape != r.shape:
+        raise ValueError(f"last_step must be an int32 {r.shape} array, got {last.dtype} {last.shape}")
+    if succ.dtype not in (np.dtype(np.uint8), np.dtype(bool)) or succ.shape != r.shape:
+        raise ValueError(f"success must be a uint8 or bool {r.shape} array, got {succ.dtype} {succ.shape}")
+    n = np.float64(r.size)
+    with np.errstate(all="ignore"):
+        mean = ordered_sum(r, np.float64) / n
+        d = r - mean
+        var = ordered_sum(d * d, np.float64) / n
+        length_sum = int(last.astype(np.int64).sum()) + r.size
+        successes = int(np.count_nonzero(succ))
+        mean_length = np.float64(length_sum) / n
+        success_rate = np.float64(successes) / n
+        improved = bool(mean > np.float64(best_mean))  # strict; False for a NaN mean
+        std = np.sqrt(var)
+    best_mean, best_index = (mean, int(eval_index)) if improved else (np.float64(best_mean), int(best_index))
+    return dict(mean_return=mean, var_return=var, mean_length=mean_length, success_rate=success_rate, best_mean_after=best_mean,
+                eval_index=int(eval_index), length_sum=length_sum, successes=successes, count=int(r.size), improved=int(improved), reserved0=0,
+                std_return=std, best_mean=best_mean, best_index=best_index)
+
+
+def evaluation_points(first_step, iterations, updates_per_iteration, idle_iterations, every):
+    """The iterations of a ``SACLearner.train(..., evaluation=, eval_every=every)`` call that are followed by an evaluation
+    (ur_gym_amd/csrc/urgym_eval_schedule.h): with s_i = first_step - 1 + G (the iterations among 0..i that are not idle), iteration i
+    where ``s_i // every > s_{i-1} // every`` -- the update count passes a multiple of `every` in it.  `first_step`: the 1-based Adam
+    step of the call's first update."""
+    first, n, G, idle, E = int(first_step), int(iterations), int(updates_per_iteration), int(idle_iterations), int(every)
+    if first < 1 or n < 1 or G < 0 or idle < 0 or E < 1:
+        raise ValueError(f"evaluation_points: first_step >= 1, iterations >= 1, updates_per_iteration >= 0, idle_iterations >= 0 and every >= 1, got "
+                         f"{(first_step, iterations, updates_per_iteration, idle_iterations, every)}")
+    after = lambda i: first - 1 + G * max(0, i + 1 - idle)  # noqa: E731
+    return [i for i in range(n) if after(i) // E > after(i - 1) // E]
+
+
+class DeviceEvaluation:
+    """The EvalCallback of the reference's train.py:55-60 on the device: an evaluation environment (`test_env`, auto_reset off, at most
+    65536 envs), a DeviceActor on it, the episode scratch, `capacity` evaluation records, the best actor's tensors and the best state
+    (mean ``-inf``, index ``-1`` until an evaluation improves).  `actor_tensors_like`: a dict under ACTOR_ARRAYS + LOG_STD_ARRAYS (torch
+    tensors or arrays) that gives the shape and the eval actor's first weights.  Every evaluation zeroes `test_env`'s observation
+    buffer and resets it with `seed` -- ``reset(seed=)`` as a fresh environment answers it: on UR5DynReach-v1 a reset keeps the
+    velocity slot of the observation it finds -- so that all of them play the same episodes, and runs `num_steps` steps (default: the
+    env's max_episode_steps)."""
+
+    def __init__(self, test_env, actor_tensors_like, num_steps=None, seed=0, capacity=64):
+        import torch
+
+        from . import _abi
+
+        if test_env.cfg.auto_reset:
+            raise ValueError("DeviceEvaluation: test_env must be made with auto_reset=False (whole first episodes are summarised)")
+        if test_env.num_envs > _abi.EVAL_MAX_COUNT:
+            raise ValueError(f"DeviceEvaluation: at most {_abi.EVAL_MAX_COUNT} evaluation envs, got {test_env.num_envs}")
+        like = {k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)) for k, v in dict(actor_tensors_like).items()}
+        missing = [k for k in ACTOR_ARRAYS + LOG_STD_ARRAYS if k not in like]
+        if missing:
+            raise ValueError(f"DeviceEvaluation: actor_tensors_like needs all of {ACTOR_ARRAYS + LOG_STD_ARRAYS}; missing {missing}")
+        self.env, self.seed = test_env, int(seed)
+        self.num_steps = int(test_env.cfg.max_episode_steps if num_steps is None else num_steps)
+        self.capacity = int(capacity)
+        if self.num_steps < 1 or self.capacity < 1:
+            raise ValueError("DeviceEvaluation: num_steps and capacity must be at least 1")
+        self.actor = DeviceActor({k: like[k].astype(np.float32) for k in ACTOR_ARRAYS + LOG_STD_ARRAYS}, test_env)
+        dev, N = test_env.device, test_env.num_envs
+        self.scratch = dict(episode_return=torch.zeros(N, dtype=torch.float64, device=dev), episode_last_step=torch.zeros(N, dtype=torch.int32, device=dev),
+                            episode_success=torch.zeros(N, dtype=torch.uint8, device=dev), episode_done=torch.zeros(N, dtype=torch.uint8, device=dev))
+        self.records = torch.zeros((self.capacity, _abi.EVAL_RECORD_WORDS), dtype=torch.int64, device=dev)  # [capacity] urgym_eval_record
+        self.best = {k: torch.zeros(like[k].shape, dtype=torch.float32, device=dev) for k in ACTOR_ARRAYS + LOG_STD_ARRAYS}
+        self.best_mean = torch.full((1,), -np.inf, dtype=torch.float64, device=dev)
+        self.best_index = torch.full((1,), -1, dtype=torch.int64, device=dev)
+        self.count = 0   # evaluations made: the next one's eval_index and record slot
+        self._struct = self._source = None
+
+    def struct(self, tensors):
+        """The checked ``urgym_policy_evaluation`` for the source `tensors` (a dict of device tensors as ``DeviceActor.check_parameters``
+        takes them, with the log_std head); rebuilt only when another set of tensors is handed in."""
+        import ctypes as C
+
+        from . import _abi
+
+        keys = ACTOR_ARRAYS + LOG_STD_ARRAYS
+        ptrs = tuple(tensors[k].data_ptr() for k in keys) if all(k in tensors for k in keys) else None
+        if self._struct is not None and ptrs is not None and ptrs == self._source:
+            return self._struct
+        a, env = self.actor, self.env
+        if not DeviceActor.check_parameters(dict(tensors), a.in_features, a.hidden_width, env.device):
+            raise ValueError(f"DeviceEvaluation: the source needs the log_std head too ({LOG_STD_ARRAYS})")
+        fp = lambda t: C.cast(t.data_ptr(), C.POINTER(C.c_float))  # noqa: E731
+        E = _abi.PolicyEvaluation()
+        E.eval_actor, E.in_features, E.hidden_width = a._a, a.in_features, a.hidden_width
+        E.source = _abi.ActorTensors(*[fp(tensors[k]) for k in keys])
+        E.best = _abi.ActorTensors(*[fp(self.best[k]) for k in keys])
+        sc = self.scratch
+        E.episode_return = C.cast(sc["episode_return"].data_ptr(), C.POINTER(C.c_double))
+        E.episode_last_step = C.cast(sc["episode_last_step"].data_ptr(), C.POINTER(C.c_int32))
+        E.episode_success = C.cast(sc["episode_success"].data_ptr(), C.POINTER(C.c_uint8))
+        E.episode_done = C.cast(sc["episode_done"].data_ptr(), C.POINTER(C.c_uint8))
+        E.records = C.cast(self.records.data_ptr(), C.POINTER(_abi.EvalRecord))
+        E.best_mean = C.cast(self.best_mean.data_ptr(), C.POINTER(C.c_double))
+        E.best_index = C.cast(self.best_index.data_ptr(), C.POINTER(C.c_int64))
+        E.reset_seed, E.record_capacity, E.num_steps, E.reserved0 = self.seed, self.capacity, self.num_steps, 0
+        self._struct, self._source, self._keep = E, ptrs, dict(tensors)
+        return E
+
+    def advance(self, evaluations):
+        """What a native call that made `evaluations` evaluations leaves behind on the host side: the counters, and the environment's
+        own bookkeeping of ``reset(seed=)``."""
+        if evaluations:
+            self.count += int(evaluations)
+            self.actor.has_log_std = True
+            self.env._seed, self.env._needs_reset = self.seed, False
+
+    def evaluate(self, tensors):
+        """One evaluation of the actor whose parameters are `tensors` (urgym_policy_evaluate): reload, ``reset(seed=)``, `num_steps`
+        steps of the deterministic policy, the statistics into the next record, and the copy into the best tensors where the mean
+        return is strictly above the best so far.  On torch's current stream; NOT synchronised.  Returns the record's index."""
+        import ctypes as C
+
+        from . import _native
+
+        if self.count >= self.capacity:
+            raise ValueError(f"DeviceEvaluation: all {self.capacity} records are used")
+        env, slot = self.env, self.count
+        _native.check(env.lib.urgym_policy_evaluate(env._h, C.byref(self.struct(tensors)), slot, slot, env._stream()), env._h)
+        self.advance(1)
+        return slot
+
+    def results(self):
+        """Synchronises; one dict per evaluation made, with the record's fields and ``std_return = sqrt(var_return)``."""
+        import ctypes as C
+
+        import torch
+
+        from . import _abi
+
+        torch.cuda.synchronize(self.env.device)
+        raw = self.records[:self.count].cpu().numpy().tobytes()
+        out = []
+        for i in range(self.count):
+            rec = _abi.EvalRecord.from_buffer_copy(raw, i * C.sizeof(_abi.EvalRecord))
+            d = {name: getattr(rec, name) for name, _ in _abi.EvalRecord._fields_}
+            with np.errstate(all="ignore"):
+                d["std_return"] = float(np.sqrt(np.float64(d["var_return"])))
+            out.append(d)
+        return out
+
+    def best_state(self):
+        """(best mean return, index of the evaluation that reached it); synchronises."""
+        return float(self.best_mean.cpu()[0]), int(self.best_index.cpu()[0])
+
+    def best_parameters(self):
+        """The best actor's tensors (device tensors under ACTOR_ARRAYS + LOG_STD_ARRAYS): zeros until an evaluation has improved."""
+        return self.best
+
+    def save_best(self, path):
+        """Writes the best actor as an ``.npz`` under ACTOR_ARRAYS + LOG_STD_ARRAYS: what ``DeviceActor.load`` and
+        ``DeterministicActor.load`` read.  Synchronises."""
+        save_actor(path, self.best)
+
+    def close(self):
+        self._struct = self._source = None
+        self.actor.close()
+
+
+def save_actor(path, tensors):
+    """An actor's ten arrays (device tensors or arrays under ACTOR_ARRAYS + LOG_STD_ARRAYS) as an ``.npz`` ``DeviceActor.load`` and
+    ``DeterministicActor.load`` read back bitwise."""
+    arrays = {}
+    for k in ACTOR_ARRAYS + LOG_STD_ARRAYS:
+        v = tensors[k]
+        arrays[k] = np.ascontiguousarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float32)
+    with open(path, "wb") as f:  # a file object: np.savez appends no suffix of its own
+        np.savez(f, **arrays)

@@ -41,7 +41,10 @@ minibatch gather on the HIP kernels, and gradients and optimisers in torch autog
     nothing goes through autograd, the losses are 0-dim views of preallocated tensors, and ``self.last_update`` keeps references
     (no copies) to the ``log_prob``, ``y``, ``q``, ``q_min`` and ``dqmin_da`` the update used.  Every float of it is stated in
     include/urgym.h.
-    None of them synchronises with the host.  There is no logging, no callback and no checkpoint format here; tools/train_sac.py runs it.
+    None of them synchronises with the host.  ``train`` runs the whole loop in one native call and, given an
+    ``evaluation.DeviceEvaluation``, the reference's EvalCallback inside it: evaluations of the deterministic policy at a fixed interval of
+    updates, their statistics as records on the device, and the best actor's tensors, which ``DeviceEvaluation.save_best`` writes as an
+    ``.npz`` ``DeviceActor.load`` reads.  There is no logging here, and the checkpoint holds the actor alone; tools/train_sac.py runs it.
 """
 import numpy as np
 import torch
@@ -329,7 +332,7 @@ class SACLearner:
         self._train = dict(replay=replay, binding=binding, scratch=scratch)
         return self._train
 
-    def train(self, replay, iterations, steps_per_iteration=1, updates_per_iteration=1, *, seed, first_draw):
+    def train(self, replay, iterations, steps_per_iteration=1, updates_per_iteration=1, *, seed, first_draw, evaluation=None, eval_every=None):
         """`iterations` x (``collect(replay, steps_per_iteration)``, `updates_per_iteration` x ``update(replay, seed, draw)`` with draw =
         `first_draw`, `first_draw` + 1, ...) in ONE native call (``env.sac_train``, urgym_sac_train), bit for bit: the loop of
         tools/train_sac.py without Python between the launches.  Needs ``device_entropy``.  The warm-up is the loop's: an iteration
@@ -337,9 +340,16 @@ class SACLearner:
         holds after its collection (``evaluation.warmup_iterations``).  Advances ``env_steps``, ``draw``, ``adam_state["step"]``,
         ``replay.cursor`` and ``replay.filled``; ``last_update`` refers to the scratch the last update used.  Returns the three
         losses as device tensors of one entry per update (not synchronised).  ``steps_per_iteration=0, iterations=1`` is
-        `updates_per_iteration` updates in one call."""
+        `updates_per_iteration` updates in one call.
+
+        With `evaluation` (an ``evaluation.DeviceEvaluation`` on a second environment) and `eval_every` the ONE native call is
+        urgym_sac_train_evaluated: after every iteration in which the update count (``adam_state["step"]``) passes a multiple of
+        `eval_every`, the actor as it then stands is evaluated (``evaluation.evaluate`` of ``self.actor.tensors()``, bit for bit)
+        without leaving the call; `evaluation`'s counters advance.  Both or neither: one alone raises ValueError."""
         from .evaluation import warmup_iterations
 
+        if (evaluation is None) != (eval_every is None):
+            raise ValueError("train: evaluation and eval_every go together (an interval needs something to evaluate with, and the reverse)")
         if self.entropy_state is None:
             raise ValueError("train needs device_entropy=True (the native loop is the thirteen launches of the update on the device)")
         hp, env, st = self.hp, self.env, self.adam_state
@@ -351,7 +361,8 @@ class SACLearner:
         tr["binding"].struct.update_seed = int(seed)
         env.sac_train(tr["binding"], losses[0], losses[1], losses[2], first_slot=replay.cursor, filled_steps=replay.filled, num_iterations=n,
                       steps_per_iteration=K, updates_per_iteration=G, uniform_iterations=uniform, idle_iterations=idle,
-                      collect_first_draw=self.draw, update_first_draw=int(first_draw), first_step=st["step"] + 1)
+                      collect_first_draw=self.draw, update_first_draw=int(first_draw), first_step=st["step"] + 1,
+                      **({} if evaluation is None else dict(evaluation=evaluation, eval_every=eval_every)))
         self.env_steps += n * K
         self.draw += n * K
         st["step"] += updates

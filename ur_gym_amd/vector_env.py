@@ -582,6 +582,49 @@ class UR5ReachVectorEnv:
             a.actor_loss_out = self._float_ptr(who, "actor_loss_out", actor_loss_out, (1,))
         _native.check(self.lib.urgym_sac_policy_terms(self._h, C.byref(a), self._stream()), self._h)
 
+    def evaluation_stats(self, returns, last_step, success, best_mean, best_index, record, eval_index):
+        """The statistics of N evaluation episodes, the improvement decision and the best state, in ONE launch of one workgroup
+        (urgym_eval_stats): `returns` float64 [N], `last_step` int32 [N], `success` uint8 or bool [N] (the episode summary of
+        ``rollout_policy``), N in [1, 65536]; `best_mean` float64 [1] and `best_index` int64 [1] are read and written; `record`, an
+        int64 [9] tensor, receives the ``urgym_eval_record`` (``_abi.EvalRecord``).  Needs no environment of N envs.  Every tensor is
+        checked, none is converted; the arithmetic is ``evaluation.evaluation_stats``, bitwise.  On torch's current stream, nothing is
+        synchronised."""
+        who = "evaluation_stats"
+        if not isinstance(returns, torch.Tensor) or returns.dim() != 1:
+            raise ValueError(f"{who}: returns must be a float64 [N] tensor")
+        n = int(returns.shape[0])
+        if not 1 <= n <= _abi.EVAL_MAX_COUNT:
+            raise ValueError(f"{who}: N must be in [1, {_abi.EVAL_MAX_COUNT}], got {n}")
+        if isinstance(eval_index, bool) or int(eval_index) != eval_index or not 0 <= int(eval_index) < 1 << 63:
+            raise ValueError(f"{who}: eval_index must be an integer in [0, 2^63), got {eval_index!r}")
+        a = _abi.EvalStatsArgs(n, 0, int(eval_index))
+        a.episode_return = self._float_ptr(who, "returns", returns, (n,), torch.float64, C.c_double)
+        a.episode_last_step = self._float_ptr(who, "last_step", last_step, (n,), torch.int32, C.c_int32)
+        a.episode_success = self._float_ptr(who, "success", success, (n,), torch.uint8, C.c_uint8)
+        a.best_mean = self._float_ptr(who, "best_mean", best_mean, (1,), torch.float64, C.c_double)
+        a.best_index = self._float_ptr(who, "best_index", best_index, (1,), torch.int64, C.c_int64)
+        a.record = C.cast(self._float_ptr(who, "record", record, (_abi.EVAL_RECORD_WORDS,), torch.int64, C.c_int64), C.POINTER(_abi.EvalRecord))
+        _native.check(self.lib.urgym_eval_stats(self._h, C.byref(a), self._stream()), self._h)
+
+    def actor_snapshot(self, source, destination, in_features, hidden_width, when=None):
+        """``destination = source`` for an actor's eight tensors (dicts under ACTOR_ARRAYS + LOG_STD_ARRAYS of float32 device tensors
+        shaped for ``in_features -> hidden_width -> hidden_width -> 6``), in ONE launch (urgym_actor_snapshot) -- or nothing at all
+        where `when`, an int32 [1] device tensor, holds 0 when the launch runs.  ``when=None`` copies always.  Every tensor is
+        checked, none is converted.  On torch's current stream, nothing is synchronised."""
+        from .evaluation import ACTOR_ARRAYS, LOG_STD_ARRAYS, DeviceActor
+
+        who = "actor_snapshot"
+        keys = ACTOR_ARRAYS + LOG_STD_ARRAYS
+        a = _abi.ActorSnapshotArgs(int(in_features), int(hidden_width))
+        for name, tensors in (("source", source), ("destination", destination)):
+            tensors = dict(tensors)
+            if not DeviceActor.check_parameters(tensors, in_features, hidden_width, self.device):
+                raise ValueError(f"{who}: {name} needs the log_std head too ({LOG_STD_ARRAYS})")
+            setattr(a, name, _abi.ActorTensors(*[C.cast(tensors[k].data_ptr(), C.POINTER(C.c_float)) for k in keys]))
+        if when is not None:
+            a.when = self._float_ptr(who, "when", when, (1,), torch.int32, C.c_int32)
+        _native.check(self.lib.urgym_actor_snapshot(self._h, C.byref(a), self._stream()), self._h)
+
     def sac_learner(self, *, actor, online, target, actor_params, actor_grads, actor_exp_avg, actor_exp_avg_sq, critic_params, critic_grads,
                     critic_exp_avg, critic_exp_avg_sq, actor_workspace, critic_workspace, log_ent_coef, exp_avg, exp_avg_sq, replay, batch, scratch,
                     count, seed, update_seed, gamma, tau, target_entropy, lr, betas=(0.9, 0.999), eps=1e-8):
@@ -668,18 +711,24 @@ class UR5ReachVectorEnv:
         L.count, L.reserved0, L.seed, L.update_seed = M, 0, int(seed), int(update_seed)
         L.gamma, L.tau, L.target_entropy = float(gamma), float(tau), float(target_entropy)
         L.lr, L.beta1, L.beta2, L.eps = hyper.lr, hyper.beta1, hyper.beta2, hyper.eps
-        return SacLearnerBinding(self, L, keep, actor)
+        return SacLearnerBinding(self, L, keep, actor, dict(actor_params))
 
     def sac_train(self, learner, critic_loss, actor_loss, ent_coef_loss, *, first_slot, filled_steps, num_iterations, steps_per_iteration=1,
-                  updates_per_iteration=1, uniform_iterations=0, idle_iterations=0, collect_first_draw=0, update_first_draw=0, first_step=1):
+                  updates_per_iteration=1, uniform_iterations=0, idle_iterations=0, collect_first_draw=0, update_first_draw=0, first_step=1,
+                  evaluation=None, eval_every=None):
         """``num_iterations`` x (a collection of ``steps_per_iteration`` steps, ``updates_per_iteration`` SAC updates) in ONE native
         call (urgym_sac_train): the launches of ``collect`` and of the thirteen calls of an update, bit for bit, without returning to
         Python in between.  `learner`: what ``sac_learner`` returned, or a dict of its keyword arguments (then built and checked here).
         `critic_loss`, `actor_loss`, `ent_coef_loss`: float32 tensors of one entry per update of the call, update u writes entry u.
         The schedule as ``evaluation.training_schedule`` takes it (``capacity_steps`` is the replay's); the caller owns the ring's
         cursor and fill level, the draw counters and the step count, and advances them.  On torch's current stream; nothing is
-        synchronised, nothing is converted.  Returns the number of updates."""
-        from .evaluation import training_schedule
+        synchronised, nothing is converted.  Returns the number of updates.
+
+        With `evaluation` (an ``evaluation.DeviceEvaluation`` on a SECOND environment of this device) and `eval_every` (updates between
+        evaluations) the call is urgym_sac_train_evaluated: the same launches with an evaluation of the learner's actor parameters
+        after every iteration in which the update count passes a multiple of `eval_every` (``evaluation.evaluation_points``), into
+        `evaluation`'s next records; its counters are advanced.  Without them nothing changes."""
+        from .evaluation import DeviceEvaluation, evaluation_points, training_schedule
 
         who = "sac_train"
         if isinstance(learner, dict):
@@ -697,6 +746,19 @@ class UR5ReachVectorEnv:
         if any(not -(1 << 31) <= sched[k] < 1 << 31 for k in ints) or not all(0 <= sched[k] < 1 << 64 for k in ("collect_first_draw", "update_first_draw")) \
                 or not -(1 << 63) <= sched["first_step"] < 1 << 63:
             raise ValueError(f"{who}: a number of the schedule does not fit its field (int32 counts, uint64 draws, int64 first_step)")
+        if (evaluation is None) != (eval_every is None):
+            raise ValueError(f"{who}: evaluation and eval_every go together")
+        points = []
+        if evaluation is not None:
+            if not isinstance(evaluation, DeviceEvaluation):
+                raise ValueError(f"{who}: evaluation must be a DeviceEvaluation")
+            if evaluation.env is self:
+                raise ValueError(f"{who}: the evaluation needs an environment of its own (an evaluation resets it); evaluation on the training env is not supported")
+            if isinstance(eval_every, bool) or int(eval_every) != eval_every or not 1 <= int(eval_every) < 1 << 31:
+                raise ValueError(f"{who}: eval_every must be an integer in [1, 2^31), got {eval_every!r}")
+            E_ = _abi.SacEvaluation(evaluation.env._h, evaluation.struct(learner.actor_params), int(eval_every), evaluation.count, evaluation.count)
+            if sched["first_step"] >= 1 and sched["num_iterations"] >= 1 and min(sched["updates_per_iteration"], sched["idle_iterations"]) >= 0:
+                points = evaluation_points(sched["first_step"], sched["num_iterations"], sched["updates_per_iteration"], sched["idle_iterations"], eval_every)
         active = max(0, sched["num_iterations"] - max(0, sched["idle_iterations"]))
         updates = active * max(0, sched["updates_per_iteration"])
         L = learner.struct
@@ -704,7 +766,11 @@ class UR5ReachVectorEnv:
             setattr(L, name, self._float_ptr(who, name, t, (updates,)))
         S = _abi.SacSchedule(*[sched[name] for name, _ in _abi.SacSchedule._fields_])
         try:
-            _native.check(self.lib.urgym_sac_train(self._h, C.byref(L), C.byref(S), self._stream()), self._h)
+            if evaluation is None:
+                _native.check(self.lib.urgym_sac_train(self._h, C.byref(L), C.byref(S), self._stream()), self._h)
+            else:
+                _native.check(self.lib.urgym_sac_train_evaluated(self._h, C.byref(L), C.byref(S), C.byref(E_), self._stream()), self._h)
+                evaluation.advance(len(points))
         finally:
             for name in _abi.SAC_LEARNER_LOSSES:  # the loss slots belong to this call alone
                 setattr(L, name, None)
@@ -934,8 +1000,8 @@ class SacLearnerBinding:
     """What ``UR5ReachVectorEnv.sac_learner`` returns: the checked ``urgym_sac_learner`` (``struct``) and references to every tensor
     and object it points to, so that none is freed while a call that reads it may still be queued."""
 
-    def __init__(self, env, struct, keep, actor):
-        self.env, self.struct, self.keep, self.actor = env, struct, keep, actor
+    def __init__(self, env, struct, keep, actor, actor_params=None):
+        self.env, self.struct, self.keep, self.actor, self.actor_params = env, struct, keep, actor, actor_params
 
 
 class _LazyInfo(dict):
