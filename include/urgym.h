@@ -1128,6 +1128,97 @@ typedef struct urgym_sac_evaluation {
  * call beyond record_capacity.  No allocation, no host synchronisation; a launch failure midway as in urgym_sac_train. */
 int urgym_sac_train_evaluated(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_evaluation* evaluation, void* stream);
 
+/* ---- training-episode statistics on the device (train.py:52 wraps the training env in Monitor(env, log_dir), and SB3 logs
+ * rollout/ep_rew_mean, rollout/ep_len_mean and rollout/success_rate from it: the return, the length and info["is_success"] of the
+ * episodes THE COLLECTING POLICY ITSELF finishes).  Every quantity is in the replay ring the collection has just written -- reward,
+ * terminated, truncated, is_success -- so one launch follows the episodes of all N envs through the K slots of a collection, and one
+ * launch of one workgroup reduces the finished episodes to a record; neither returns to the host.  Added WITHIN ABI version 4: no struct
+ * above changed, URGYM_ABI_VERSION did not move, the three symbols below are found by lookup.  SB3 averages a window of the last 100
+ * episodes; here a record covers the episodes finished since the last clear, whose number the record states.
+ *
+ * THE STATE: DEVICE pointers owned by the caller, [N] each, N = the handle's num_envs.  All zero is the valid initial state; the library
+ * keeps none of it. */
+typedef struct urgym_monitor_state {
+  double* running_return;  /* [N] the episode in progress: its rewards so far */
+  int32_t* running_length; /* [N] the episode in progress: its steps so far */
+  double* sum_return;      /* [N] the episodes env n finished since the last clear: the sum of their returns */
+  int64_t* sum_length;     /* [N] ... the sum of their lengths */
+  int32_t* episodes;       /* [N] ... their number */
+  int32_t* successes;      /* [N] ... those that ended with is_success != 0 */
+} urgym_monitor_state;
+
+/* THE FOLD of K = num_steps steps, per env n with the steps read IN ORDER, k = 0 .. K - 1, from slot (first_slot + k) % C of the ring --
+ * the slots a urgym_rollout_collect with the same arguments has just filled.  Each line is ONE operation, in float64 where a float is
+ * involved (ur_gym_amd/csrc/urgym_monitor.h states them, ur_gym_amd.evaluation.monitor_fold restates them):
+ *   running_return += (double)reward
+ *   running_length += 1
+ *   where terminated | truncated is non-zero:
+ *     sum_return += running_return;  sum_length += running_length;  episodes += 1;  successes += (is_success != 0)
+ *     running_return = +0.0;  running_length = 0
+ * An episode may span any number of calls: folding K steps in one call or in pieces leaves identical bits.
+ * ONE launch on `stream`, one lane per env; no atomics, no allocation, no host synchronisation; everything validated before the launch.
+ * Refused (URGYM_ERR_ARG, nothing launched, nothing written): NULL handle or state, a NULL state pointer (named), running_return /
+ * sum_return / sum_length not 8-byte aligned; the ring refusals of urgym_rollout_collect (ring == NULL, a NULL required pointer,
+ * capacity_steps <= 0, reserved0 != 0, first_slot outside [0, C)); a ring without truncated or without is_success; num_steps <= 0;
+ * num_steps > C (the ring no longer holds the earlier steps); a handle with auto_reset off (its episodes do not restart). */
+int urgym_monitor_fold(void* handle, const urgym_monitor_state* state, const urgym_replay_ring* ring, int first_slot, int num_steps, void* stream);
+
+/* One record: the episodes finished since the last clear, over all N envs. */
+typedef struct urgym_monitor_record {
+  double mean_return;   /* rollout/ep_rew_mean */
+  double mean_length;   /* rollout/ep_len_mean */
+  double success_rate;  /* rollout/success_rate */
+  double sum_return;    /* sum_r below */
+  int64_t episodes;
+  int64_t length_sum;
+  int64_t successes;
+  int64_t iteration;    /* the caller's tag */
+  int64_t reserved0;    /* written as 0 */
+} urgym_monitor_record;
+
+/* THE RECORD, every line ONE operation (urgym_monitor.h states them, ur_gym_amd.evaluation.monitor_stats restates them):
+ *   episodes, length_sum, successes = the exact int64 sums of episodes[n], sum_length[n], successes[n] over the N envs
+ *   sum_r        = THE ORDERED SUM (above, "SAC's entropy coefficient on the device") of sum_return[0..N): lane t of 1024 starts at +0.0
+ *                  and adds sum_return[t], sum_return[t + 1024], ... in ascending order -- ceil(N / 1024) terms per lane at the most,
+ *                  whatever N the handle has -- then partial[t] += partial[t + s] for s = 512, ..., 1
+ *   mean_return  = sum_r / (double)episodes
+ *   mean_length  = (double)length_sum / (double)episodes
+ *   success_rate = (double)successes / (double)episodes
+ *   with episodes == 0 the three quotients are +0.0: no division produces a NaN, and a reader checks `episodes`.  (A NaN reward does
+ *   reach sum_r and mean_return, for the interval its episode ends in.)
+ * With clear != 0 each lane then zeroes the four interval entries (sum_return, sum_length, episodes, successes) it has read; an entry
+ * belongs to exactly one lane.  The episode in progress (running_*) is untouched.
+ * ONE launch of ONE workgroup on `stream`; no atomics, no allocation, no host synchronisation.  Refused (URGYM_ERR_ARG, nothing
+ * launched, nothing written): NULL handle, state or record, a NULL state pointer (named), record / running_return / sum_return /
+ * sum_length not 8-byte aligned. */
+int urgym_monitor_stats(void* handle, const urgym_monitor_state* state, urgym_monitor_record* record, int64_t iteration, int clear, void* stream);
+
+typedef struct urgym_sac_monitoring {
+  urgym_monitor_state state;
+  urgym_monitor_record* records; /* [record_capacity] */
+  int32_t record_capacity;       /* >= 0 */
+  int32_t first_record;          /* the j-th record of the call is records[first_record + j] */
+  int32_t log_every;             /* E >= 1, in iterations */
+  int32_t clear;                 /* urgym_monitor_stats' clear, for every record of the call */
+  int64_t first_iteration;       /* >= 0: the caller's count of iterations before this call */
+  int64_t reserved0;             /* must be 0 */
+} urgym_sac_monitoring;
+
+/* The launches of urgym_sac_train (evaluation == NULL) or of urgym_sac_train_evaluated (evaluation given), and added to them, with
+ * K = steps_per_iteration:
+ *   after the launches of each iteration i with K > 0 -- idle (warm-up) iterations like the others -- ONE urgym_monitor_fold of that
+ *   iteration's K slots, first_slot = (schedule->first_slot + i K) % C;
+ *   then, where (first_iteration + i + 1) % log_every == 0, ONE urgym_monitor_stats into the next record with
+ *   iteration = first_iteration + i + 1 (ur_gym_amd/csrc/urgym_monitor.h; ur_gym_amd.evaluation.monitor_points restates the rule);
+ *   then the evaluation that follows iteration i, if any.
+ * Split calls that hand the iteration count on place records where one call would.  The training side and the evaluation are bit for bit
+ * those of the call without monitoring: the two launches write the state and the records and nothing else.
+ * EVERYTHING is validated before the first launch.  Refused, besides every refusal of the call without monitoring and of the two calls
+ * above: NULL monitoring; K > C; more record points than record_capacity - first_record; a negative first_record; log_every < 1;
+ * first_iteration < 0, or first_iteration + num_iterations beyond int64; reserved0 != 0.  After a refusal nothing has been launched or
+ * written.  No allocation, no host synchronisation; a launch failure midway as in urgym_sac_train. */
+int urgym_sac_train_monitored(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring, void* stream);
+
 /* Verification aid, not a hot path: synchronises the device, then copies the object's packed buffer (the kernel's own layout,
  * ur_gym_amd/csrc/urgym_pack_map.h) to host_out and stores its length in floats in *count.  host_out == NULL only reports *count;
  * otherwise capacity (in floats) must be at least that.  Refused: NULL handle / object / count, an object of another handle,

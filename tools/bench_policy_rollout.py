@@ -80,6 +80,14 @@ eval_every=40) call against one train call per interval plus the Python evaluati
 min and max of the wall time in ms; the bar of --native on `one_evaluation`, the ratio reported whatever it is.
     python tools/bench_policy_rollout.py --evaluate --windows 8 --launches 200 --out profiles/policy_rollout/dyn_evaluation.json
 
+--monitor measures the training-episode statistics inside the training call, 4096 envs, batch 256, H = 256:
+--launches updates as --launches / 4 x (1 step, 4 updates) in ONE SACLearner.train call as it was, against the same call with
+monitor=, log_every=10 (a fold launch per iteration, a stats launch per ten).  Alternating windows in one process, each ending in a
+synchronise; median, min and max of the wall time in ms.  Bar: the monitored median is not above the plain one by more than the spread
+(max - min) of the plain route's own windows; the excess per iteration is reported whatever it is.  --monitored-only runs the monitored
+call alone: the program of a kernel-trace run.
+    python tools/bench_policy_rollout.py --monitor --windows 8 --launches 200 --out profiles/policy_rollout/dyn_monitor.json
+
 With --refresh: what it costs to hand new weights to a device actor / critic, at hidden width 256 and 512.
 `actor_load`, `critic_load_tau1` and `critic_load_polyak` (tau = 0.005) are load_parameters from device tensors, one launch each;
 `*_host_route` is the only route there was before: every tensor .cpu().numpy(), destroy and create the object (the actor's head by
@@ -1144,6 +1152,75 @@ def evaluate_mode(args):
             f.write(line + "\n")
 
 
+def monitor_mode(args):
+    """--monitor: what the training-episode statistics cost inside the training call.  --launches updates as
+    --launches / 4 x (1 step, 4 updates) in ONE SACLearner.train call, without a monitor and with ``monitor=, log_every=10`` (one fold
+    launch per iteration, one stats launch per ten), in alternating windows of one process, each ending in a synchronise."""
+    import torch
+
+    from ur_gym_amd import make_vec
+    from ur_gym_amd.evaluation import DeviceMonitor, DeviceReplay
+    from ur_gym_amd.training import SACLearner
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_policy_rollout.py measures on a GPU; none is visible")
+    dev, n, E, per_step = "cuda:0", min(args.num_envs, 4096), 10, 4
+    iterations = max(1, args.launches // per_step)  # --launches updates per window, as --native counts them
+    env = make_vec(args.env, num_envs=n, device=dev, seed=0, auto_reset=True)
+    env.reset(seed=0)
+    sync = lambda: torch.cuda.synchronize(env.device)  # noqa: E731
+    options = dict(device_action_gradient=True, device_critic_gradient=True, device_actor_gradient=True, device_optimizer=True, device_entropy=True)
+    sides = {}
+    for label in ("plain", "monitored")[1 if args.monitored_only else 0:]:
+        learner = SACLearner(env, seed=0, batch_size=256, hidden_width=256, learning_starts=0, **options)
+        replay = DeviceReplay(env, 64)
+        learner.collect(replay, 4)
+        sides[label] = dict(learner=learner, replay=replay, draw=0, mon=DeviceMonitor(env, capacity=iterations // E + 1) if label == "monitored" else None)
+
+    def run(label):
+        sd = sides[label]
+        extra = {}
+        if sd["mon"] is not None:
+            sd["mon"].count = 0
+            extra = dict(monitor=sd["mon"], log_every=E)
+        sd["learner"].train(sd["replay"], iterations, 1, per_step, seed=1, first_draw=sd["draw"] + 1, **extra)
+        sd["draw"] += iterations * per_step
+
+    def window(label):
+        sync()
+        t0 = time.perf_counter()
+        run(label)
+        sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    for label in sides:
+        run(label), run(label)
+    wdw = {label: [] for label in sides}
+    for _ in range(args.windows):
+        for label in sides:
+            wdw[label].append(window(label))
+    result = {"tool": "bench_policy_rollout --monitor", "env": args.env, "num_envs": n, "windows": args.windows, "batch": 256, "hidden_width": 256,
+              "iterations_per_window": iterations, "updates_per_iteration": per_step, "log_every": E, "device": torch.cuda.get_device_name(0),
+              "ms_median": {k: float(np.median(v)) for k, v in wdw.items()}, "ms_min": {k: float(min(v)) for k, v in wdw.items()},
+              "ms_max": {k: float(max(v)) for k, v in wdw.items()}, "ms_windows": {k: [round(x, 3) for x in v] for k, v in wdw.items()}}
+    if not args.monitored_only:
+        med, spread = result["ms_median"], float(max(wdw["plain"]) - min(wdw["plain"]))
+        excess = med["monitored"] - med["plain"]
+        result.update(plain_ms_spread=spread, excess_ms=excess, excess_us_per_iteration=excess * 1e3 / iterations,
+                      ratio_monitored_over_plain=med["monitored"] / med["plain"], not_slower=med["monitored"] <= med["plain"] + spread)
+        last = sides["monitored"]["mon"].results()
+        result["last_window_records"] = [{k: r[k] for k in ("iteration", "episodes", "mean_return", "mean_length", "success_rate")} for r in last]
+    for sd in sides.values():
+        sd["learner"].close()
+    env.close()
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--env", default="UR5DynReach-v1", choices=sorted(ACTOR_NPZ))
@@ -1172,8 +1249,12 @@ def main():
     ap.add_argument("--native", action="store_true", help="measure the thirteen-call update against SACLearner.train, one native call per window (see above)")
     ap.add_argument("--native-only", action="store_true", help="--native: run only the native updates, --windows x --launches of them (for a kernel trace)")
     ap.add_argument("--evaluate", action="store_true", help="measure one evaluation (DeviceEvaluation.evaluate) against load_parameters + reset + run_closed_loop_device, and a training run with evaluations as one call against one call per interval plus the Python evaluation")
+    ap.add_argument("--monitor", action="store_true", help="measure SACLearner.train with monitor=, log_every=10 against the same call without a monitor (see above)")
+    ap.add_argument("--monitored-only", action="store_true", help="--monitor: run only the monitored call, --windows times (for a kernel trace)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.monitor:
+        return monitor_mode(args)
     if args.evaluate:
         return evaluate_mode(args)
     if args.native:

@@ -10,6 +10,10 @@ SACLearner.train(..., evaluation=, eval_every=): the same launches, bit for bit,
 inside the call (evaluation.DeviceEvaluation: statistics, the improvement decision and the copy of the best actor on the device), and
 their records are printed after one synchronise at the end (each evaluation there starts from a zeroed observation buffer, which
 matters on UR5DynReach-v1 alone: its reset keeps the velocity slot it finds).  --save-best PATH writes the best actor as an .npz DeviceActor.load reads.
+With --monitor the training curve is printed as well, on both routes: every --log-every trips one line with the number, the mean return,
+the mean length and the success rate of the episodes the COLLECTING policy finished since the line before (evaluation.DeviceMonitor: the
+reference's Monitor and SB3's rollout/ep_rew_mean, ep_len_mean and success_rate, reduced on the device).  With --native those records,
+too, are written inside the one call and read after its one synchronise.
 """
 import argparse
 import json
@@ -50,6 +54,9 @@ def main():
     ap.add_argument("--native", action="store_true",
                     help="run the whole loop, evaluations included, as ONE native call (SACLearner.train): no Python between the launches "
                          "(needs --device-entropy)")
+    ap.add_argument("--monitor", action="store_true",
+                    help="print the training curve: the episodes the collecting policy finishes, reduced on the device (DeviceMonitor)")
+    ap.add_argument("--log-every", type=int, default=100, help="loop trips between two lines of the training curve (--monitor)")
     ap.add_argument("--save-best", metavar="PATH", default=None,
                     help="write the actor of the best evaluation (mean episode return strictly above every earlier one) as an .npz")
     args = ap.parse_args()
@@ -57,7 +64,7 @@ def main():
     import torch
 
     from ur_gym_amd import make_vec
-    from ur_gym_amd.evaluation import DeviceActor, DeviceEvaluation, DeviceReplay, evaluation_points, run_closed_loop_device, save_actor, warmup_iterations
+    from ur_gym_amd.evaluation import DeviceActor, DeviceEvaluation, DeviceMonitor, DeviceReplay, evaluation_points, run_closed_loop_device, save_actor, warmup_iterations
     from ur_gym_amd.training import SACLearner, host_arrays
 
     if not torch.cuda.is_available():
@@ -73,6 +80,15 @@ def main():
     replay = DeviceReplay(env, args.capacity)
     updates, t0 = 0, time.perf_counter()
     best = dict(mean=-float("inf"), tensors=None)  # the Python route's own best_model
+    if args.monitor and args.log_every < 1:
+        raise SystemExit("--log-every must be at least 1")
+    mon = DeviceMonitor(env, capacity=max(1, args.steps // args.log_every)) if args.monitor else None
+
+    def print_curve(seconds):
+        for rec in mon.results():  # synchronises
+            print(json.dumps({"trips": rec["iteration"], "env_steps": rec["iteration"] * env.num_envs, "seconds": seconds, "train_episodes": rec["episodes"],
+                              "train_mean_return": rec["mean_return"], "train_mean_length": rec["mean_length"],
+                              "train_success_rate_percent": 100.0 * rec["success_rate"]}), flush=True)
 
     def evaluate():
         eval_actor.load_parameters(learner.actor.tensors())
@@ -91,7 +107,8 @@ def main():
         points = evaluation_points(1, args.steps, args.updates_per_step, idle, args.eval_every) if args.steps > 0 else []
         ev = DeviceEvaluation(test_env, learner.actor.tensors(), seed=args.seed + 1, capacity=max(1, len(points)))
         if args.steps > 0:
-            learner.train(replay, args.steps, 1, args.updates_per_step, seed=args.seed, first_draw=0, evaluation=ev, eval_every=args.eval_every)
+            learner.train(replay, args.steps, 1, args.updates_per_step, seed=args.seed, first_draw=0, evaluation=ev, eval_every=args.eval_every,
+                          **(dict(monitor=mon, log_every=args.log_every) if mon is not None else {}))
         seconds = None
         for trip, rec in zip(points, ev.results()):  # results() synchronises, once
             seconds = round(time.perf_counter() - t0, 1) if seconds is None else seconds
@@ -99,12 +116,16 @@ def main():
             print(json.dumps({"updates": done, "env_steps": (trip + 1) * env.num_envs, "seconds": seconds, "mean_episode_return": rec["mean_return"],
                               "success_rate_percent": 100.0 * rec["success_rate"], "std_episode_return": rec["std_return"],
                               "mean_episode_length": rec["mean_length"], "improved": bool(rec["improved"])}), flush=True)
+        if mon is not None:
+            print_curve(round(time.perf_counter() - t0, 1) if seconds is None else seconds)
         if args.save_best and ev.best_state()[1] >= 0:
             ev.save_best(args.save_best)
         ev.close()
         step = args.steps
     for step in range(step, args.steps):  # the Python loop (every trip of it where --native is off)
-        learner.collect(replay, 1)
+        learner.collect(replay, 1, monitor=mon)
+        if mon is not None and (step + 1) % args.log_every == 0:
+            mon.record(step + 1)
         if learner.env_steps * env.num_envs < learner.hp["learning_starts"]:
             continue
         for _ in range(args.updates_per_step):
@@ -112,6 +133,8 @@ def main():
             updates += 1
             if updates % args.eval_every == 0:
                 evaluate()
+    if mon is not None and not args.native:
+        print_curve(round(time.perf_counter() - t0, 1))
     if args.save_best and best["tensors"] is not None:
         save_actor(args.save_best, best["tensors"])
     eval_actor.close()

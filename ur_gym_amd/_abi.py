@@ -384,6 +384,31 @@ class SacEvaluation(C.Structure):
                 ("first_eval_index", C.c_int64)]
 
 
+# urgym_monitor_state: name -> ctype of the six [N] DEVICE arrays, in the struct's order
+MONITOR_STATE_FIELDS = [("running_return", C.c_double), ("running_length", C.c_int32), ("sum_return", C.c_double), ("sum_length", C.c_int64),
+                        ("episodes", C.c_int32), ("successes", C.c_int32)]
+
+
+class MonitorState(C.Structure):
+    """urgym_monitor_state: per env the episode in progress and the episodes finished since the last clear; all zero is the start."""
+    _fields_ = [(name, C.POINTER(ct)) for name, ct in MONITOR_STATE_FIELDS]
+
+
+class MonitorRecord(C.Structure):
+    """urgym_monitor_record: the training episodes finished since the last clear as the device reduced them; 72 bytes, 8-byte aligned."""
+    _fields_ = [(name, C.c_double) for name in ("mean_return", "mean_length", "success_rate", "sum_return")] + \
+               [(name, C.c_int64) for name in ("episodes", "length_sum", "successes", "iteration", "reserved0")]
+
+
+MONITOR_RECORD_WORDS = 9  # a MonitorRecord as int64 words: how a torch tensor holds an array of them
+
+
+class SacMonitoring(C.Structure):
+    """urgym_sac_monitoring: the state, the records, where the call's records start, the interval in iterations and the caller's count."""
+    _fields_ = [("state", MonitorState), ("records", C.POINTER(MonitorRecord)), ("record_capacity", C.c_int32), ("first_record", C.c_int32),
+                ("log_every", C.c_int32), ("clear", C.c_int32), ("first_iteration", C.c_int64), ("reserved0", C.c_int64)]
+
+
 # Every symbol include/urgym.h declares (tests check that the built library exports each of them).
 EXPORTED_SYMBOLS = [
     "urgym_abi_version",
@@ -425,6 +450,9 @@ EXPORTED_SYMBOLS = [
     "urgym_actor_snapshot",
     "urgym_policy_evaluate",
     "urgym_sac_train_evaluated",
+    "urgym_monitor_fold",
+    "urgym_monitor_stats",
+    "urgym_sac_train_monitored",
     "urgym_actor_read_packed",
     "urgym_critic_read_packed",
     "urgym_refresh",

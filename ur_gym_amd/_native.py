@@ -94,6 +94,10 @@ def lib():
     L.urgym_actor_snapshot.argtypes = [C.c_void_p, C.POINTER(_abi.ActorSnapshotArgs), C.c_void_p]
     L.urgym_policy_evaluate.argtypes = [C.c_void_p, C.POINTER(_abi.PolicyEvaluation), C.c_int64, C.c_int32, C.c_void_p]
     L.urgym_sac_train_evaluated.argtypes = [C.c_void_p, C.POINTER(_abi.SacLearner), C.POINTER(_abi.SacSchedule), C.POINTER(_abi.SacEvaluation), C.c_void_p]
+    L.urgym_monitor_fold.argtypes = [C.c_void_p, C.POINTER(_abi.MonitorState), C.POINTER(_abi.ReplayRing), C.c_int, C.c_int, C.c_void_p]
+    L.urgym_monitor_stats.argtypes = [C.c_void_p, C.POINTER(_abi.MonitorState), C.POINTER(_abi.MonitorRecord), C.c_int64, C.c_int, C.c_void_p]
+    L.urgym_sac_train_monitored.argtypes = [C.c_void_p, C.POINTER(_abi.SacLearner), C.POINTER(_abi.SacSchedule), C.POINTER(_abi.SacEvaluation),
+                                            C.POINTER(_abi.SacMonitoring), C.c_void_p]
     L.urgym_actor_read_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.urgym_critic_read_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.urgym_refresh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]

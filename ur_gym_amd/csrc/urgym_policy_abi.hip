@@ -1,6 +1,6 @@
 // urgym_policy_abi.hip — the learner's half of the C-ABI of include/urgym.h: actors (create / forward / sample / rollouts), the replay
-// ring, the weight reloads, the twin critic and its two gradients, the actor's parameter gradients, the Adam steps, SAC's entropy step and loss terms, the training loop that composes them in one call (urgym_sac_train; its index arithmetic is urgym_sac_schedule.h), and the evaluation inside that call (urgym_eval_stats, urgym_actor_snapshot, urgym_policy_evaluate, urgym_sac_train_evaluated; urgym_eval.h, urgym_eval_schedule.h).  Host code only: every check is made here, before the first launch,
-// and every launch goes through urgym_actor.h, urgym_critic.h, urgym_replay.h, urgym_weights.h, urgym_adam.h, urgym_sac_terms.h and urgym_eval.h, or through do_step of urgym_hip.hip
+// ring, the weight reloads, the twin critic and its two gradients, the actor's parameter gradients, the Adam steps, SAC's entropy step and loss terms, the training loop that composes them in one call (urgym_sac_train; its index arithmetic is urgym_sac_schedule.h), the evaluation inside that call (urgym_eval_stats, urgym_actor_snapshot, urgym_policy_evaluate, urgym_sac_train_evaluated; urgym_eval.h, urgym_eval_schedule.h), and the training-episode statistics inside it (urgym_monitor_fold, urgym_monitor_stats, urgym_sac_train_monitored; urgym_monitor.h).  Host code only: every check is made here, before the first launch,
+// and every launch goes through urgym_actor.h, urgym_critic.h, urgym_replay.h, urgym_weights.h, urgym_adam.h, urgym_sac_terms.h, urgym_eval.h and urgym_monitor.h, or through do_step of urgym_hip.hip
 // (urgym_handle.h).  No kernel lives in this unit, so adding a check here leaves the step kernels' object file alone.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -21,6 +21,7 @@
 #include "urgym_sac_schedule.h"
 #include "urgym_eval.h"
 #include "urgym_eval_schedule.h"
+#include "urgym_monitor.h"
 
 using namespace urgym;
 
@@ -1213,6 +1214,7 @@ struct TrainEvaluation {
   hipStream_t s;
   PolicyEvaluation call;
   int64_t done;  // evaluations launched so far
+  const char* who;  // the entry point that runs them: urgym_sac_train_evaluated, or urgym_sac_train_monitored
 };
 
 const char* const TRAIN_EVALUATED = "urgym_sac_train_evaluated";
@@ -1220,7 +1222,7 @@ const char* const TRAIN_EVALUATED = "urgym_sac_train_evaluated";
 // runs after every check of the training body (so the learner and the schedule are sound) and before its first launch
 int train_evaluation_check(void* ctx) {
   TrainEvaluation& t = *(TrainEvaluation*)ctx;
-  const char* who = TRAIN_EVALUATED;
+  const char* who = t.who;
   Handle* h = t.h;
   const urgym_sac_evaluation& E = *t.evaluation;
   Handle* eh = (Handle*)E.eval_handle;
@@ -1249,7 +1251,101 @@ int train_evaluation_after(void* ctx, int i) {
     HIP_TRY(t.h, hipSetDevice(t.h->device));  // the same device: what the launches of the next iteration expect to be current
     return rc;
   }
-  return failf(t.h, rc, "%s: iteration %d, evaluation: %.150s", TRAIN_EVALUATED, i, t.call.eh->err);
+  return failf(t.h, rc, "%s: iteration %d, evaluation: %.150s", t.who, i, t.call.eh->err);
+}
+
+// ---- training-episode statistics (include/urgym.h, urgym_monitor_fold ... urgym_sac_train_monitored).  As above
+// each entry point is a checking half, which launches nothing and fills the launch struct of urgym_monitor.h, and a launching half,
+// which refuses nothing.
+
+// the six state pointers: all given, the 8-byte ones aligned
+int check_monitor_state(Handle* h, const urgym_monitor_state* state, const char* who) {
+  if (!state) return fail_in(h, URGYM_ERR_ARG, who, "null monitor state");
+  const urgym_monitor_state& m = *state;
+  const LearnerPointer required[] = {{"running_return", m.running_return}, {"running_length", m.running_length}, {"sum_return", m.sum_return},
+                                     {"sum_length", m.sum_length},         {"episodes", m.episodes},             {"successes", m.successes}};
+  for (const LearnerPointer& r : required)
+    if (!r.p) return failf(h, URGYM_ERR_ARG, "%s: urgym_monitor_state.%s is null", who, r.name);
+  if ((uintptr_t)m.running_return % 8 != 0 || (uintptr_t)m.sum_return % 8 != 0 || (uintptr_t)m.sum_length % 8 != 0)
+    return fail_in(h, URGYM_ERR_ARG, who, "running_return, sum_return and sum_length must be 8-byte aligned");
+  return URGYM_OK;
+}
+
+int check_monitor_fold(Handle* h, const urgym_monitor_state* state, const urgym_replay_ring* ring, int first_slot, int num_steps, const char* who, MonitorFoldCall* out) {
+  if (int rc = check_monitor_state(h, state, who)) return rc;
+  if (int rc = check_ring(h, ring, who)) return rc;
+  if (first_slot < 0 || first_slot >= ring->capacity_steps) return fail_in(h, URGYM_ERR_ARG, who, "first_slot outside [0, capacity_steps)");
+  if (!ring->truncated || !ring->is_success) return fail_in(h, URGYM_ERR_ARG, who, "the ring keeps no truncated or no is_success (an episode's end and its success are read from them)");
+  if (num_steps <= 0) return fail_in(h, URGYM_ERR_ARG, who, "num_steps must be positive");
+  if (num_steps > ring->capacity_steps) return fail_in(h, URGYM_ERR_ARG, who, "num_steps is above capacity_steps (the ring no longer holds the earlier steps)");
+  if (!h->cfg.auto_reset) return fail_in(h, URGYM_ERR_ARG, who, "the handle has auto_reset off (its episodes do not restart)");
+  *out = MonitorFoldCall{h->cfg.num_envs, ring->capacity_steps, first_slot, num_steps, *state, ring->reward, ring->terminated, ring->truncated, ring->is_success};
+  return URGYM_OK;
+}
+
+int check_monitor_stats(Handle* h, const urgym_monitor_state* state, urgym_monitor_record* record, int64_t iteration, int clear, const char* who, MonitorStatsCall* out) {
+  static_assert(sizeof(urgym_monitor_record) == 72 && alignof(urgym_monitor_record) == 8, "include/urgym.h");
+  if (int rc = check_monitor_state(h, state, who)) return rc;
+  if (!record) return fail_in(h, URGYM_ERR_ARG, who, "null record");
+  if ((uintptr_t)record % 8 != 0) return fail_in(h, URGYM_ERR_ARG, who, "record must be 8-byte aligned");
+  *out = MonitorStatsCall{h->cfg.num_envs, clear, iteration, *state, record};
+  return URGYM_OK;
+}
+
+// urgym_sac_train_monitored's hooks into sac_train_body: the monitor's half first, then the evaluation's existing half where one is given
+struct TrainMonitoring {
+  Handle* h;
+  const urgym_sac_learner* learner;
+  const urgym_sac_schedule* schedule;
+  const urgym_sac_monitoring* monitoring;
+  hipStream_t s;
+  MonitorFoldCall fold;    // first_slot moves per iteration
+  MonitorStatsCall stats;  // record and iteration move per record
+  int64_t done;            // records launched so far
+  TrainEvaluation* evaluation;  // null = none
+};
+
+const char* const TRAIN_MONITORED = "urgym_sac_train_monitored";
+
+// runs after every check of the training body (so the learner and the schedule are sound) and before its first launch
+int train_monitoring_check(void* ctx) {
+  TrainMonitoring& t = *(TrainMonitoring*)ctx;
+  const char* who = TRAIN_MONITORED;
+  Handle* h = t.h;
+  const urgym_sac_monitoring& M = *t.monitoring;
+  const urgym_sac_schedule& S = *t.schedule;
+  if (M.reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_monitoring.reserved0 must be 0");
+  if (const char* what = monitor_schedule_refusal(S, M.log_every, M.first_iteration, M.first_record, M.record_capacity)) return fail_in(h, URGYM_ERR_ARG, who, what);
+  // the fold's checks with the first iteration's slots (a call that collects nothing folds nothing: its state is still checked below)
+  if (S.steps_per_iteration > 0)
+    if (int rc = check_monitor_fold(h, &M.state, &t.learner->ring, S.first_slot, S.steps_per_iteration, who, &t.fold)) return rc;
+  // the statistics' checks, on the first record (every record has its alignment: it is a multiple of 8 bytes); without a record point
+  // the pointer may be anything
+  const bool records = monitor_record_count(M.first_iteration, M.log_every, S.num_iterations) > 0;
+  urgym_monitor_record unused;
+  if (int rc = check_monitor_stats(h, &M.state, records ? M.records : &unused, 0, M.clear, who, &t.stats)) return rc;
+  if (t.evaluation) return train_evaluation_check(t.evaluation);
+  return URGYM_OK;
+}
+
+int train_monitoring_after(void* ctx, int i) {
+  TrainMonitoring& t = *(TrainMonitoring*)ctx;
+  const urgym_sac_monitoring& M = *t.monitoring;
+  const urgym_sac_schedule& S = *t.schedule;
+  if (S.steps_per_iteration > 0) {
+    t.fold.first_slot = sac_schedule_iteration(S, i).collect_first_slot;
+    monitor_fold_launch(t.fold, t.s);
+    if (int rc = train_stage(t.h, TRAIN_MONITORED, i, "monitor_fold")) return rc;
+  }
+  if (monitor_record_follows(M.first_iteration, M.log_every, i)) {
+    t.stats.record = M.records + M.first_record + t.done;
+    t.stats.iteration = M.first_iteration + i + 1;
+    t.done++;
+    monitor_stats_launch(t.stats, t.s);
+    if (int rc = train_stage(t.h, TRAIN_MONITORED, i, "monitor_stats")) return rc;
+  }
+  if (t.evaluation) return train_evaluation_after(t.evaluation, i);
+  return URGYM_OK;
 }
 
 }  // namespace
@@ -1291,9 +1387,42 @@ int urgym_sac_train_evaluated(void* handle, const urgym_sac_learner* learner, co
   if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
   if (!evaluation) return fail_in(h, URGYM_ERR_ARG, TRAIN_EVALUATED, "null evaluation");
   TrainEvaluation t;
-  t.h = h, t.learner = learner, t.schedule = schedule, t.evaluation = evaluation, t.s = (hipStream_t)stream, t.done = 0;
+  t.h = h, t.learner = learner, t.schedule = schedule, t.evaluation = evaluation, t.s = (hipStream_t)stream, t.done = 0, t.who = TRAIN_EVALUATED;
   const TrainHooks hooks{train_evaluation_check, train_evaluation_after, &t};
   return sac_train_body(TRAIN_EVALUATED, handle, learner, schedule, stream, &hooks);
+}
+
+int urgym_monitor_fold(void* handle, const urgym_monitor_state* state, const urgym_replay_ring* ring, int first_slot, int num_steps, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  MonitorFoldCall c;
+  if (int rc = check_monitor_fold(h, state, ring, first_slot, num_steps, "urgym_monitor_fold", &c)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  monitor_fold_launch(c, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_monitor_stats(void* handle, const urgym_monitor_state* state, urgym_monitor_record* record, int64_t iteration, int clear, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  MonitorStatsCall c;
+  if (int rc = check_monitor_stats(h, state, record, iteration, clear, "urgym_monitor_stats", &c)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  monitor_stats_launch(c, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_sac_train_monitored(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (!monitoring) return fail_in(h, URGYM_ERR_ARG, TRAIN_MONITORED, "null monitoring");
+  TrainEvaluation e;
+  e.h = h, e.learner = learner, e.schedule = schedule, e.evaluation = evaluation_or_NULL, e.s = (hipStream_t)stream, e.done = 0, e.who = TRAIN_MONITORED;
+  TrainMonitoring t;
+  t.h = h, t.learner = learner, t.schedule = schedule, t.monitoring = monitoring, t.s = (hipStream_t)stream, t.done = 0;
+  t.evaluation = evaluation_or_NULL ? &e : nullptr;
+  const TrainHooks hooks{train_monitoring_check, train_monitoring_after, &t};
+  return sac_train_body(TRAIN_MONITORED, handle, learner, schedule, stream, &hooks);
 }
 
 }  // extern "C"

@@ -1201,3 +1201,170 @@ def save_actor(path, tensors):
         arrays[k] = np.ascontiguousarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float32)
     with open(path, "wb") as f:  # a file object: np.savez appends no suffix of its own
         np.savez(f, **arrays)
+
+
+# ------------------------------------------------------------------------------------------------ training-episode statistics (the Monitor)
+def _monitor_arrays(state):
+    """A copy of `state` (a dict under ``_abi.MONITOR_STATE_FIELDS`` of [N] arrays) with every dtype and shape checked."""
+    from . import _abi
+
+    names = [name for name, _ in _abi.MONITOR_STATE_FIELDS]
+    if not isinstance(state, dict) or sorted(state) != sorted(names):
+        raise ValueError(f"state must be a dict under {names}")
+    out, n = {}, None
+    for name, ct in _abi.MONITOR_STATE_FIELDS:
+        a, want = np.asarray(state[name]), np.dtype(ct)
+        n = a.shape if n is None else n
+        if a.dtype != want or a.ndim != 1 or a.shape != n:
+            raise ValueError(f"state[{name!r}] must be a {want} [N] array, got {a.dtype} {a.shape}")
+        out[name] = a.copy()
+    return out
+
+
+def monitor_fold(state, reward, terminated, truncated, is_success, first_slot, num_steps):
+    """THE FOLD of include/urgym.h ("training-episode statistics on the device") in numpy, bitwise what urgym_monitor_fold leaves:
+    `state` a dict under ``_abi.MONITOR_STATE_FIELDS`` of [N] arrays; `reward` float32 [C, N] and the three flags uint8 or bool [C, N],
+    the ring's tensors; the steps k = 0 .. num_steps - 1 are read in order from slot (first_slot + k) % C.  Every line is one operation,
+    in float64 where a float is involved.  Returns the new state (the argument is not written)."""
+    from . import _abi
+
+    st = _monitor_arrays(state)
+    r = np.asarray(reward)
+    flags = [np.asarray(x) for x in (terminated, truncated, is_success)]
+    n = st["running_return"].shape[0]
+    if r.dtype != np.float32 or r.ndim != 2 or r.shape[1] != n:
+        raise ValueError(f"reward must be a float32 [C, {n}] array, got {r.dtype} {r.shape}")
+    for name, x in zip(("terminated", "truncated", "is_success"), flags):
+        if x.dtype not in (np.dtype(np.uint8), np.dtype(bool)) or x.shape != r.shape:
+            raise ValueError(f"{name} must be a uint8 or bool {r.shape} array, got {x.dtype} {x.shape}")
+    cap, first, K = r.shape[0], int(first_slot), int(num_steps)
+    if not 0 <= first < cap or not 1 <= K <= cap:
+        raise ValueError(f"first_slot must be in [0, {cap}) and num_steps in [1, {cap}], got {first_slot} and {num_steps}")
+    term, trunc, succ = (x.view(np.uint8) if x.dtype == bool else x for x in flags)
+    with np.errstate(all="ignore"):
+        for k in range(K):
+            s = (first + k) % cap
+            running = st["running_return"] + r[s].astype(np.float64)
+            length = st["running_length"] + np.int32(1)
+            done = (term[s] | trunc[s]) != 0
+            st["sum_return"] = np.where(done, st["sum_return"] + running, st["sum_return"])
+            st["sum_length"] = np.where(done, st["sum_length"] + length.astype(np.int64), st["sum_length"])
+            st["episodes"] = np.where(done, st["episodes"] + np.int32(1), st["episodes"])
+            st["successes"] = np.where(done, st["successes"] + (succ[s] != 0).astype(np.int32), st["successes"])
+            st["running_return"] = np.where(done, np.float64(0.0), running)
+            st["running_length"] = np.where(done, np.int32(0), length)
+    for name, ct in _abi.MONITOR_STATE_FIELDS:
+        assert st[name].dtype == np.dtype(ct), (name, st[name].dtype)  # no intermediate was promoted
+    return st
+
+
+def monitor_stats(state, iteration, clear=True):
+    """THE RECORD of include/urgym.h ("training-episode statistics on the device") in numpy, bitwise what urgym_monitor_stats writes:
+    the exact integer sums, the ordered sum of ``sum_return`` in float64, the three quotients (one division each; ``+0.0`` where no
+    episode finished).  Returns ``(record, state)``: a dict with the fields of ``urgym_monitor_record``, and the state afterwards -- with
+    `clear` its four interval arrays zeroed, the episode in progress untouched (the argument is not written)."""
+    st = _monitor_arrays(state)
+    episodes = int(st["episodes"].astype(np.int64).sum())
+    length_sum = int(st["sum_length"].sum())
+    successes = int(st["successes"].astype(np.int64).sum())
+    with np.errstate(all="ignore"):
+        sum_r = ordered_sum(st["sum_return"], np.float64)
+        zero = np.float64(0.0)
+        e = np.float64(episodes)
+        mean_return = sum_r / e if episodes else zero
+        mean_length = np.float64(length_sum) / e if episodes else zero
+        success_rate = np.float64(successes) / e if episodes else zero
+    if clear:
+        for name in ("sum_return", "sum_length", "episodes", "successes"):
+            st[name] = np.zeros_like(st[name])
+    rec = dict(mean_return=mean_return, mean_length=mean_length, success_rate=success_rate, sum_return=sum_r, episodes=episodes, length_sum=length_sum,
+               successes=successes, iteration=int(iteration), reserved0=0)
+    return rec, st
+
+
+def monitor_points(first_iteration, iterations, log_every):
+    """The iterations i of a ``SACLearner.train(..., monitor=, log_every=)`` call of `iterations` iterations that are followed by a record
+    (ur_gym_amd/csrc/urgym_monitor.h): those where ``(first_iteration + i + 1) % log_every == 0`` -- the monitor's count of iterations,
+    that one included, reaches a multiple of `log_every`.  `first_iteration`: the count before the call."""
+    first, n, E = int(first_iteration), int(iterations), int(log_every)
+    if first < 0 or n < 0 or E < 1:
+        raise ValueError(f"monitor_points: first_iteration >= 0, iterations >= 0 and log_every >= 1, got {(first_iteration, iterations, log_every)}")
+    return [i for i in range(n) if (first + i + 1) % E == 0]
+
+
+class DeviceMonitor:
+    """The ``Monitor(env, log_dir)`` of the reference's train.py:52 on the device: per env the return and the length of the episode the
+    COLLECTING policy is playing and the episodes it finished since the last record, read from the replay ring the collection has just
+    written; and `capacity` records of them (SB3's rollout/ep_rew_mean, rollout/ep_len_mean, rollout/success_rate), each over the
+    episodes finished since the record before it (``clear=False``: since the start).  `env`: a UR5ReachVectorEnv with auto_reset.
+    ``iterations`` (training iterations seen) and ``count`` (records written) live on the host: ``SACLearner.train`` advances them, so
+    that split calls place records where one call would."""
+
+    def __init__(self, env, capacity=64, clear=True):
+        import ctypes as C
+
+        import torch
+
+        from . import _abi
+        from .vector_env import _TORCH_DTYPE
+
+        if not env.cfg.auto_reset:
+            raise ValueError("DeviceMonitor: env must be made with auto_reset=True (the episodes of an env that is not reset do not restart)")
+        self.env, self.capacity, self.clear = env, int(capacity), bool(clear)
+        if self.capacity < 1:
+            raise ValueError("DeviceMonitor: capacity must be at least 1")
+        self.state = {name: torch.zeros(env.num_envs, dtype=torch.int64 if ct is C.c_int64 else _TORCH_DTYPE[ct], device=env.device)
+                      for name, ct in _abi.MONITOR_STATE_FIELDS}
+        self.records = torch.zeros((self.capacity, _abi.MONITOR_RECORD_WORDS), dtype=torch.int64, device=env.device)  # [capacity] urgym_monitor_record
+        self.count = 0       # records written: the next one's slot
+        self.iterations = 0  # training iterations train() has run with this monitor
+        self._struct = None
+
+    def struct(self, log_every):
+        """The ``urgym_sac_monitoring`` of the next ``env.sac_train`` call: the state, the records from the cursor on, the count so far."""
+        import ctypes as C
+
+        from . import _abi
+
+        if self._struct is None:
+            M = _abi.SacMonitoring()
+            M.state = self.env._monitor_state("DeviceMonitor", self.state)
+            M.records = C.cast(self.records.data_ptr(), C.POINTER(_abi.MonitorRecord))
+            M.record_capacity, M.reserved0 = self.capacity, 0
+            self._struct = M
+        M = self._struct
+        M.first_record, M.log_every, M.clear, M.first_iteration = self.count, int(log_every), int(self.clear), self.iterations
+        return M
+
+    def advance(self, iterations, records):
+        """What a native call of `iterations` iterations that wrote `records` records leaves behind on the host side."""
+        self.iterations += int(iterations)
+        self.count += int(records)
+
+    def fold(self, replay, first_slot, num_steps):
+        """The `num_steps` steps `replay` holds from `first_slot` on, folded into the state (``env.monitor_fold``): call it behind the
+        ``collect`` that wrote them, with its arguments.  One launch; NOT synchronised."""
+        self.env.monitor_fold(self.state, replay, first_slot, num_steps)
+
+    def record(self, iteration, clear=None):
+        """The episodes finished since the last clear into the next record, tagged `iteration` (``env.monitor_stats``); `clear`
+        defaults to the monitor's.  One launch; NOT synchronised.  Returns the record's index."""
+        if self.count >= self.capacity:
+            raise ValueError(f"DeviceMonitor: all {self.capacity} records are used")
+        slot = self.count
+        self.env.monitor_stats(self.state, self.records[slot], iteration, self.clear if clear is None else clear)
+        self.count += 1
+        return slot
+
+    def results(self):
+        """Synchronises; one dict per record written, with the record's fields."""
+        import ctypes as C
+
+        import torch
+
+        from . import _abi
+
+        torch.cuda.synchronize(self.env.device)
+        raw = self.records[:self.count].cpu().numpy().tobytes()
+        recs = [_abi.MonitorRecord.from_buffer_copy(raw, i * C.sizeof(_abi.MonitorRecord)) for i in range(self.count)]
+        return [{name: getattr(r, name) for name, _ in _abi.MonitorRecord._fields_} for r in recs]

@@ -44,7 +44,10 @@ minibatch gather on the HIP kernels, and gradients and optimisers in torch autog
     None of them synchronises with the host.  ``train`` runs the whole loop in one native call and, given an
     ``evaluation.DeviceEvaluation``, the reference's EvalCallback inside it: evaluations of the deterministic policy at a fixed interval of
     updates, their statistics as records on the device, and the best actor's tensors, which ``DeviceEvaluation.save_best`` writes as an
-    ``.npz`` ``DeviceActor.load`` reads.  There is no logging here, and the checkpoint holds the actor alone; tools/train_sac.py runs it.
+    ``.npz`` ``DeviceActor.load`` reads.  Given an ``evaluation.DeviceMonitor``, ``collect`` and ``train`` also keep the reference's
+    ``Monitor`` (train.py:52) on the device: the return, the length and the success of the episodes the collecting policy finishes, as
+    records of the training curve (SB3's rollout/ep_rew_mean, ep_len_mean and success_rate); nothing else is logged, and the checkpoint
+    holds the actor alone; tools/train_sac.py runs it.
 """
 import numpy as np
 import torch
@@ -184,11 +187,15 @@ class SACLearner:
         self.env_steps = 0  # per env; decides between the warm-up and the policy
         self.draw = 0       # draw index of the next collection pass
 
-    def collect(self, replay, num_steps):
+    def collect(self, replay, num_steps, monitor=None):
         """`num_steps` env steps of all N envs into `replay`, with uniform actions before ``learning_starts`` env steps and the sampled
-        policy afterwards (a call is one or the other: the mode is decided when it starts)."""
+        policy afterwards (a call is one or the other: the mode is decided when it starts).  With `monitor` (an
+        ``evaluation.DeviceMonitor``) the steps just collected are folded into its state: one more launch."""
         mode = "uniform" if self.env_steps * self.env.num_envs < self.hp["learning_starts"] else "gaussian"
+        first = replay.cursor
         replay.collect(self.device_actor, num_steps, sample=dict(mode=mode, seed=self.seed, first_draw=self.draw))
+        if monitor is not None:
+            monitor.fold(replay, first, num_steps)
         self.env_steps += int(num_steps)
         self.draw += int(num_steps)
 
@@ -332,7 +339,8 @@ class SACLearner:
         self._train = dict(replay=replay, binding=binding, scratch=scratch)
         return self._train
 
-    def train(self, replay, iterations, steps_per_iteration=1, updates_per_iteration=1, *, seed, first_draw, evaluation=None, eval_every=None):
+    def train(self, replay, iterations, steps_per_iteration=1, updates_per_iteration=1, *, seed, first_draw, evaluation=None, eval_every=None,
+              monitor=None, log_every=None):
         """`iterations` x (``collect(replay, steps_per_iteration)``, `updates_per_iteration` x ``update(replay, seed, draw)`` with draw =
         `first_draw`, `first_draw` + 1, ...) in ONE native call (``env.sac_train``, urgym_sac_train), bit for bit: the loop of
         tools/train_sac.py without Python between the launches.  Needs ``device_entropy``.  The warm-up is the loop's: an iteration
@@ -345,11 +353,20 @@ class SACLearner:
         With `evaluation` (an ``evaluation.DeviceEvaluation`` on a second environment) and `eval_every` the ONE native call is
         urgym_sac_train_evaluated: after every iteration in which the update count (``adam_state["step"]``) passes a multiple of
         `eval_every`, the actor as it then stands is evaluated (``evaluation.evaluate`` of ``self.actor.tensors()``, bit for bit)
-        without leaving the call; `evaluation`'s counters advance.  Both or neither: one alone raises ValueError."""
+        without leaving the call; `evaluation`'s counters advance.  Both or neither: one alone raises ValueError.
+
+        With `monitor` (an ``evaluation.DeviceMonitor`` of the training environment) and `log_every` the ONE native call is
+        urgym_sac_train_monitored, with the evaluations if those are given too: every iteration's collection is folded into the
+        monitor (``collect(..., monitor=)``, bit for bit, warm-up iterations included), and after every iteration at which
+        ``monitor.iterations`` reaches a multiple of `log_every` the finished episodes go to the monitor's next record
+        (``monitor.record(monitor.iterations)``).  ``monitor.iterations`` and ``monitor.count`` advance, so that split calls place
+        records where one call would.  Both or neither: one alone raises ValueError."""
         from .evaluation import warmup_iterations
 
         if (evaluation is None) != (eval_every is None):
             raise ValueError("train: evaluation and eval_every go together (an interval needs something to evaluate with, and the reverse)")
+        if (monitor is None) != (log_every is None):
+            raise ValueError("train: monitor and log_every go together (an interval needs something to record with, and the reverse)")
         if self.entropy_state is None:
             raise ValueError("train needs device_entropy=True (the native loop is the thirteen launches of the update on the device)")
         hp, env, st = self.hp, self.env, self.adam_state
@@ -362,7 +379,8 @@ class SACLearner:
         env.sac_train(tr["binding"], losses[0], losses[1], losses[2], first_slot=replay.cursor, filled_steps=replay.filled, num_iterations=n,
                       steps_per_iteration=K, updates_per_iteration=G, uniform_iterations=uniform, idle_iterations=idle,
                       collect_first_draw=self.draw, update_first_draw=int(first_draw), first_step=st["step"] + 1,
-                      **({} if evaluation is None else dict(evaluation=evaluation, eval_every=eval_every)))
+                      **({} if evaluation is None else dict(evaluation=evaluation, eval_every=eval_every)),
+                      **({} if monitor is None else dict(monitor=monitor, log_every=log_every)))
         self.env_steps += n * K
         self.draw += n * K
         st["step"] += updates

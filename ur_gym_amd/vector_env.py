@@ -625,6 +625,46 @@ class UR5ReachVectorEnv:
             a.when = self._float_ptr(who, "when", when, (1,), torch.int32, C.c_int32)
         _native.check(self.lib.urgym_actor_snapshot(self._h, C.byref(a), self._stream()), self._h)
 
+    def _monitor_state(self, who, state):
+        """The checked ``urgym_monitor_state`` of `state`: a dict under the names of ``_abi.MONITOR_STATE_FIELDS`` of [N] device tensors."""
+        if not isinstance(state, dict) or sorted(state) != sorted(name for name, _ in _abi.MONITOR_STATE_FIELDS):
+            raise ValueError(f"{who}: state must be a dict under {[name for name, _ in _abi.MONITOR_STATE_FIELDS]}")
+        m = _abi.MonitorState()
+        for name, ct in _abi.MONITOR_STATE_FIELDS:
+            dtype = torch.int64 if ct is C.c_int64 else _TORCH_DTYPE[ct]
+            setattr(m, name, self._float_ptr(who, f"state[{name!r}]", state[name], (self.num_envs,), dtype, ct))
+        return m
+
+    def monitor_fold(self, state, replay, first_slot, num_steps):
+        """Follows the episodes of all N envs through `num_steps` steps of `replay` (an ``evaluation.DeviceReplay`` of this environment)
+        from slot `first_slot` on -- the slots a ``collect`` with the same arguments has just filled -- in ONE launch, one lane per env
+        (urgym_monitor_fold).  `state`: a dict under ``_abi.MONITOR_STATE_FIELDS`` of [N] device tensors (float64 ``running_return``
+        and ``sum_return``, int64 ``sum_length``, int32 the others), read and written; all zero is the start.  Every tensor is
+        checked, none is converted; the arithmetic is ``evaluation.monitor_fold``, bitwise.  At most the ring's capacity in steps, and
+        only with auto_reset.  On torch's current stream, nothing is synchronised."""
+        who = "monitor_fold"
+        if getattr(replay, "env", None) is not self or not hasattr(replay, "_ring"):
+            raise ValueError(f"{who}: replay must be a DeviceReplay allocated for this environment (DeviceReplay(env, capacity_steps))")
+        if not self.cfg.auto_reset:
+            raise ValueError(f"{who}: the environment has auto_reset off (its episodes do not restart)")
+        replay.check_args(replay.capacity, num_steps=num_steps, first_slot=first_slot)
+        if int(num_steps) > replay.capacity:
+            raise ValueError(f"{who}: num_steps must be at most the ring's {replay.capacity} slots (it no longer holds the earlier steps), got {num_steps}")
+        m = self._monitor_state(who, state)
+        _native.check(self.lib.urgym_monitor_fold(self._h, C.byref(m), C.byref(replay._ring), int(first_slot), int(num_steps), self._stream()), self._h)
+
+    def monitor_stats(self, state, record, iteration, clear=True):
+        """The episodes finished since the last clear, over all N envs, reduced to one ``urgym_monitor_record`` (``_abi.MonitorRecord``)
+        in `record`, an int64 [9] tensor, in ONE launch of one workgroup (urgym_monitor_stats); `iteration` is the caller's tag.  With
+        `clear` the interval entries of `state` are zeroed, the episodes in progress stay.  The arithmetic is
+        ``evaluation.monitor_stats``, bitwise.  On torch's current stream, nothing is synchronised."""
+        who = "monitor_stats"
+        if isinstance(iteration, bool) or int(iteration) != iteration or not -(1 << 63) <= int(iteration) < 1 << 63:
+            raise ValueError(f"{who}: iteration must be an integer that fits int64, got {iteration!r}")
+        m = self._monitor_state(who, state)
+        rec = C.cast(self._float_ptr(who, "record", record, (_abi.MONITOR_RECORD_WORDS,), torch.int64, C.c_int64), C.POINTER(_abi.MonitorRecord))
+        _native.check(self.lib.urgym_monitor_stats(self._h, C.byref(m), rec, int(iteration), int(bool(clear)), self._stream()), self._h)
+
     def sac_learner(self, *, actor, online, target, actor_params, actor_grads, actor_exp_avg, actor_exp_avg_sq, critic_params, critic_grads,
                     critic_exp_avg, critic_exp_avg_sq, actor_workspace, critic_workspace, log_ent_coef, exp_avg, exp_avg_sq, replay, batch, scratch,
                     count, seed, update_seed, gamma, tau, target_entropy, lr, betas=(0.9, 0.999), eps=1e-8):
@@ -715,7 +755,7 @@ class UR5ReachVectorEnv:
 
     def sac_train(self, learner, critic_loss, actor_loss, ent_coef_loss, *, first_slot, filled_steps, num_iterations, steps_per_iteration=1,
                   updates_per_iteration=1, uniform_iterations=0, idle_iterations=0, collect_first_draw=0, update_first_draw=0, first_step=1,
-                  evaluation=None, eval_every=None):
+                  evaluation=None, eval_every=None, monitor=None, log_every=None):
         """``num_iterations`` x (a collection of ``steps_per_iteration`` steps, ``updates_per_iteration`` SAC updates) in ONE native
         call (urgym_sac_train): the launches of ``collect`` and of the thirteen calls of an update, bit for bit, without returning to
         Python in between.  `learner`: what ``sac_learner`` returned, or a dict of its keyword arguments (then built and checked here).
@@ -727,8 +767,14 @@ class UR5ReachVectorEnv:
         With `evaluation` (an ``evaluation.DeviceEvaluation`` on a SECOND environment of this device) and `eval_every` (updates between
         evaluations) the call is urgym_sac_train_evaluated: the same launches with an evaluation of the learner's actor parameters
         after every iteration in which the update count passes a multiple of `eval_every` (``evaluation.evaluation_points``), into
-        `evaluation`'s next records; its counters are advanced.  Without them nothing changes."""
-        from .evaluation import DeviceEvaluation, evaluation_points, training_schedule
+        `evaluation`'s next records; its counters are advanced.  Without them nothing changes.
+
+        With `monitor` (an ``evaluation.DeviceMonitor`` of this environment) and `log_every` (iterations between records) the call is
+        urgym_sac_train_monitored: the same launches -- with the evaluations, if those are given too -- and after every iteration that
+        collects one ``monitor.fold`` of its slots, and after every iteration at which the monitor's iteration count reaches a multiple
+        of `log_every` one ``monitor.record`` (``evaluation.monitor_points``); the monitor's count and record cursor are advanced.
+        Without them nothing changes."""
+        from .evaluation import DeviceEvaluation, DeviceMonitor, evaluation_points, monitor_points, training_schedule
 
         who = "sac_train"
         if isinstance(learner, dict):
@@ -759,6 +805,15 @@ class UR5ReachVectorEnv:
             E_ = _abi.SacEvaluation(evaluation.env._h, evaluation.struct(learner.actor_params), int(eval_every), evaluation.count, evaluation.count)
             if sched["first_step"] >= 1 and sched["num_iterations"] >= 1 and min(sched["updates_per_iteration"], sched["idle_iterations"]) >= 0:
                 points = evaluation_points(sched["first_step"], sched["num_iterations"], sched["updates_per_iteration"], sched["idle_iterations"], eval_every)
+        if (monitor is None) != (log_every is None):
+            raise ValueError(f"{who}: monitor and log_every go together")
+        if monitor is not None:
+            if not isinstance(monitor, DeviceMonitor) or monitor.env is not self:
+                raise ValueError(f"{who}: monitor must be a DeviceMonitor of this environment")
+            if isinstance(log_every, bool) or int(log_every) != log_every or not 1 <= int(log_every) < 1 << 31:
+                raise ValueError(f"{who}: log_every must be an integer in [1, 2^31), got {log_every!r}")
+            M_ = monitor.struct(int(log_every))
+            logged = monitor_points(monitor.iterations, max(0, sched["num_iterations"]), int(log_every))
         active = max(0, sched["num_iterations"] - max(0, sched["idle_iterations"]))
         updates = active * max(0, sched["updates_per_iteration"])
         L = learner.struct
@@ -766,7 +821,13 @@ class UR5ReachVectorEnv:
             setattr(L, name, self._float_ptr(who, name, t, (updates,)))
         S = _abi.SacSchedule(*[sched[name] for name, _ in _abi.SacSchedule._fields_])
         try:
-            if evaluation is None:
+            if monitor is not None:
+                _native.check(self.lib.urgym_sac_train_monitored(self._h, C.byref(L), C.byref(S), C.byref(E_) if evaluation is not None else None,
+                                                                 C.byref(M_), self._stream()), self._h)
+                monitor.advance(sched["num_iterations"], len(logged))
+                if evaluation is not None:
+                    evaluation.advance(len(points))
+            elif evaluation is None:
                 _native.check(self.lib.urgym_sac_train(self._h, C.byref(L), C.byref(S), self._stream()), self._h)
             else:
                 _native.check(self.lib.urgym_sac_train_evaluated(self._h, C.byref(L), C.byref(S), C.byref(E_), self._stream()), self._h)
