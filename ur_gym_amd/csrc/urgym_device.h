@@ -404,14 +404,26 @@ __device__ __forceinline__ void gjk_finish(GjkRun& r, bool check_simplex, bool s
   if (separated) r.info |= GJK_SEPARATED;
   r.core = sqrt(l2);
 }
+// A caller that defers gjk_finish (gjk_advance below) may park the exit code of the search in r.info above the GJK_* flags until it
+// runs it: the code is never 0 for an ended search (bit 0 is set), so the parked bits also say "ended, not finished yet".
+constexpr int GJK_FIN_SHIFT = 4, GJK_FIN_MASK = 7 << GJK_FIN_SHIFT;
+// what gjk_finish(r, !(fin & 2), ...) will decide about GJK_PENETRATING, without its square root: for a caller that has to know at
+// once whether an ended search needs a penetration depth
+__device__ __forceinline__ bool gjk_ends_penetrating(const GjkRun& r, int fin) {
+  return !(r.info & GJK_ITERCAP) && ((fin & 2) || len2(r.v) < 1.0e-12);
+}
 // one iteration of btGjkPairDetector's loop.  max_d: Bullet's early-out distance of this query (handed in per call rather than
 // kept in the run: callers derive it from the query's kind, which costs less than two VGPRs across the loop)
 // verdict_d (0 = off): for a query that only asks "are the cores closer than verdict_d?".  |v| is the distance of a point of A - B from
 // the origin, i.e. an UPPER bound of the core distance: once it is <= verdict_d the answer is yes whatever the search would still
 // find, and the search stops there (Bullet converges first and compares then -- same verdict).  The matching lower bound is the
 // early-out above: such a caller hands in max_d = verdict_d.
-__device__ __forceinline__ void gjk_iterate(GjkRun& r, const HullMap& g, const ShapeDesc& A, XRef T, const ShapeDesc& B, double max_d,
-                                            double verdict_d = 0.0) {
+// gjk_advance is the iteration WITHOUT the bookkeeping of an ended search: it returns the exit code fin (0: the search goes on) and
+// leaves r.done, r.core and the GJK_PENETRATING / GJK_SEPARATED flags to the caller's gjk_finish(r, !(fin & 2), (fin & 4) != 0),
+// which may run whenever the result is wanted: nothing the finish reads (r.v, GJK_ITERCAP) changes once the search has ended.
+// gjk_iterate below is the two in one.
+__device__ __forceinline__ int gjk_advance(GjkRun& r, const HullMap& g, const ShapeDesc& A, XRef T, const ShapeDesc& B, double max_d,
+                                           double verdict_d = 0.0) {
   const double REL_ERROR2 = 1.0e-12;
   const double EPS = 2.220446049250313e-16;
   // the (up to three) vertices already in the simplex, requested together with the pose: their LDS round trip runs under the support
@@ -437,7 +449,8 @@ __device__ __forceinline__ void gjk_iterate(GjkRun& r, const HullMap& g, const S
   }
   // Every exit of the iteration only RECORDS that and how the search ends (fin: bit 0 = ends, bit 1 = without the simplex check, i.e.
   // overlapping cores / iteration cap, bit 2 = on a separating axis); the bookkeeping of an ended search -- a square root among it --
-  // runs once, at the bottom, for all lanes that end in this trip, instead of once per exit that some lane happens to take.
+  // runs once, in gjk_finish, for all lanes that end in this trip (gjk_iterate) or whenever the caller files the result (gjk_advance),
+  // instead of once per exit that some lane happens to take.
   int fin = 0;
   const double delta = dot(r.v, w);
   if (delta > 0.0 && delta * delta > r.sq * (max_d * max_d)) fin = 1 | 4;
@@ -557,6 +570,11 @@ __device__ __forceinline__ void gjk_iterate(GjkRun& r, const HullMap& g, const S
       }
     }
   }  // (fin == 0: the simplex step)
+  return fin;
+}
+__device__ __forceinline__ void gjk_iterate(GjkRun& r, const HullMap& g, const ShapeDesc& A, XRef T, const ShapeDesc& B, double max_d,
+                                            double verdict_d = 0.0) {
+  const int fin = gjk_advance(r, g, A, T, B, max_d, verdict_d);
   if (fin) gjk_finish(r, !(fin & 2), (fin & 4) != 0);
 }
 

@@ -17,7 +17,7 @@
 //        pyb_setup.py:439-456; 15 E with URGYM_LINK_DIST_WORKBENCH: table and track too) + the set bits of the pair masks
 //        (boolean "closer than the margin?" queries, which stop as soon as the upper or the lower bound of the running search
 //        decides the verdict).  Every lane advances ITS query by one GJK iteration per loop trip through one inlined, resumable
-//        GJK body (gjk_begin / gjk_iterate); idle lanes draw the next item together.
+//        GJK body (gjk_begin / gjk_advance); idle lanes file what their search found and draw the next item together.
 //   EPA  the (rare) obstacle queries whose cores overlap and whose distance is consumed: penetration depth by an expanding
 //        polytope, one wave per query, faces spread over the lanes (pyb_setup.py:452 stores a negative contact distance);
 //        served by waves that have left the pool while the others still iterate.
@@ -896,16 +896,52 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
     };
 
     GjkRun run;
+    run.info = 0;  // (no ended search waits to be filed)
     bool busy = false;
     if (MODE == MODE_STEP) p1_ok = __hip_atomic_load(&s_p1done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) >= G;
     if (tid < n_tickets) {
       busy = setup(ticket_item(tid), std::false_type{});
       if (busy) gjk_begin(run, v0);
     }
-    // One loop trip of a lane: its query advances by one GJK iteration and, when that ends it, files its result.  The body is inlined
-    // twice, into the steady loop and into the drain loop below; neither holds anything else.
+    // FILING the result of an ended search: gjk_finish (a float64 square root among it), the distance or the verdict, the status bits
+    // and EPA marks.  Nothing reads any of that before P4, behind the pool's barrier, so it does not run in the trip, for the handful
+    // of lanes that end in it, but where the wave is out of the loops anyway: in the draw step, before set-up overwrites the lane's
+    // kind / lb / e / exact, and once behind the drain loop.  Until then an idle lane carries the exit code of its search in run.info
+    // (GJK_FIN_MASK), beside the flags the search itself set; run.v, which the finish reads, does not change while the lane is idle.
+    auto file_distance = [&](double dist) {
+      if (workbench) atomicMin(reinterpret_cast<long long*>(dist_cell(lb - 2, e)), sortable(dist));
+      else *dist_cell(lb - 2, e) = dist;
+    };
+    // an exact query that ended with overlapping cores (GJK_PENETRATING): the status bit, the EPA mark where the depth is consumed, and
+    // the provisional distance (exact only when the cores just touch), which the EPA phase below replaces where it is consumed
+    auto file_overlap = [&]() {
+      const double msum = margin_sum();
+      const int body = (kind == 3) ? 0 : (kind == Q_TABLE ? 1 : 2);
+      atomicOr(&s_flags[e], URGYM_STATUS_PENETRATION | (need_epa ? (1 << (EPA_SHIFT + 5 * body + (lb - 2))) : 0));
+      file_distance(-msum);
+    };
+    auto file = [&]() {
+      if (!busy && (run.info & GJK_FIN_MASK)) {
+        const int fin = run.info >> GJK_FIN_SHIFT;
+        run.info &= ~GJK_FIN_MASK;
+        gjk_finish(run, !(fin & 2), (fin & 4) != 0);
+        const double msum = margin_sum();
+        if (kind == 3 || exact) {
+          if (run.info & GJK_ITERCAP) atomicOr(&s_flags[e], URGYM_STATUS_GJK_ITER);
+          if (run.info & GJK_PENETRATING) file_overlap();
+          else file_distance(run.core - msum);
+        } else {
+          const bool hit = (run.info & (GJK_PENETRATING | GJK_CLOSE)) || (!(run.info & GJK_SEPARATED) && (run.core - msum) <= cfg.collision_margin);
+          if (hit) atomicOr(&s_flags[e], COLL_BIT);
+        }
+        run.info = 0;
+      }
+    };
+    // One loop trip of a lane: its query advances by one GJK iteration; when that ends the search, the lane notes how and goes idle.
+    // The body is inlined twice, into the steady loop and into the drain loop below; neither holds anything else.
     auto trip = [&]() __attribute__((always_inline)) {
       if (busy) {
+        int fin;
         // exact queries (link distances): Bullet's early-out distance of getClosestPoints(distance = 5.0).  Boolean queries ("closer
         // than the contact margin?", check_collision): both bounds of the search are compared with the margin itself -- the search
         // stops as soon as either decides, with the verdict Bullet reaches after converging (pyb_setup.py:402-422)
@@ -915,37 +951,32 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
           sb.type = (kind == 3) ? SH_CYLZ : ((kind == Q_SELF) ? SH_HULL : SH_BOX);
           sb.hull = lb - 1;
           sb.hx = row[0]; sb.hy = row[1]; sb.hz = row[2];
-          gjk_iterate(run, P.graph, shape_a(), pose_slot, sb, row[3], row[4]);
+          fin = gjk_advance(run, P.graph, shape_a(), pose_slot, sb, row[3], row[4]);
         } else {
           const bool wants_distance = (kind == 3 || exact);
           const double verdict_d = wants_distance ? 0.0 : margin_sum() + cfg.collision_margin;
-          gjk_iterate(run, P.graph, shape_a(), pose_slot, shape_b(), wants_distance ? margin_sum() + 0.02 + 5.0 : verdict_d, verdict_d);
+          fin = gjk_advance(run, P.graph, shape_a(), pose_slot, shape_b(), wants_distance ? margin_sum() + 0.02 + 5.0 : verdict_d, verdict_d);
         }
-        if (run.done) {
-          const double msum = margin_sum();
-          if (kind == 3 || exact) {
-            double dist = run.core - msum;
-            if (run.info & GJK_PENETRATING) {
-              // provisional value (exact only when the cores just touch); the EPA phase below replaces it where it is consumed
-              dist = -msum;
-              const int body = (kind == 3) ? 0 : (kind == Q_TABLE ? 1 : 2);
-              atomicOr(&s_flags[e], URGYM_STATUS_PENETRATION | (need_epa ? (1 << (EPA_SHIFT + 5 * body + (lb - 2))) : 0));
-            }
-            if (run.info & GJK_ITERCAP) atomicOr(&s_flags[e], URGYM_STATUS_GJK_ITER);
-            if (workbench) atomicMin(reinterpret_cast<long long*>(dist_cell(lb - 2, e)), sortable(dist));
-            else *dist_cell(lb - 2, e) = dist;
-          } else {
-            const bool hit = (run.info & (GJK_PENETRATING | GJK_CLOSE)) || (!(run.info & GJK_SEPARATED) && (run.core - msum) <= cfg.collision_margin);
-            if (hit) atomicOr(&s_flags[e], COLL_BIT);
-          }
+        if (fin) {
+          run.info |= fin << GJK_FIN_SHIFT;
           busy = false;
+          // Kernels with the EPA phase: an exact query that ends with overlapping cores, and whose depth is consumed, is filed at once,
+          // so that its mark is up while the other waves still iterate -- an EPA takes 70-250 us, and the service waves below hide it
+          // only if it starts early.  That end needs no finish: the core distance is 0 (gjk_finish), the iteration cap excludes it.
+          // Rare; the instances without the phase (the Dyn / Sta step with collision checks) carry no such test.
+          if (HAS_OBST && WITH_EPA) {
+            if (need_epa && (kind == 3 || exact) && gjk_ends_penetrating(run, fin)) {
+              file_overlap();
+              run.info = 0;
+            }
+          }
         }
       }
     };
     // Three loop shapes.  The STEADY loop runs trips and nothing else while fewer than REFILL_MIN lanes are idle: drawing an item
     // costs the whole wave a set-up (FK + operands), so idle lanes draw together, and until enough of them wait the pool is not
     // even looked at.  (A wave without a query runs its one trip with every lane masked off and falls through.)  The DRAW step
-    // polls the pool and draws -- in a STEP launch only once the per-env phase has published: a draw is then loads from its set-up
+    // polls the pool, files what the idle lanes' searches found and draws -- in a STEP launch only once the per-env phase has published: a draw is then loads from its set-up
     // cache, and until then idle lanes stay idle, as they do while the pool is empty.  Once it has seen the pool dry for good -- tickets only count up, and s_pending only falls once
     // the pair masks are published -- the wave finishes what its lanes hold in the DRAIN loop and leaves.  While the pool is empty
     // but the pair masks are not published yet, the wave comes back to the draw step after every trip.
@@ -963,6 +994,7 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
       const bool more_pairs = pool.y > 0;
       if (MODE == MODE_STEP) p1_ok = p1_published;
       if (!busy && p1_ok) {  // (at least REFILL_MIN lanes are here; STEP: before P1 has published they stay idle)
+        file();  // what the lane's last search found, while the lane still knows which query that was
         uint32_t item = NO_ITEM;
         if (more_tickets) {
           const int t = atomicAdd(&s_ticket, 1);
@@ -991,6 +1023,7 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
         }
       }
     }
+    file();  // every lane's last result, before the wave counts itself out (s_left) and before the barrier P4 waits behind
     // ---- EPA: penetration depth of the marked queries, one wave per query (urgym_device.h epa_wave).  A wave that has left
     //      the pool turns into a service wave: it keeps looking for marks and serves them while the other waves still iterate
     //      (overlapping cores are found within a few GJK iterations, an EPA takes 70-250 us: starting it at once instead of
