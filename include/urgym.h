@@ -1219,10 +1219,65 @@ typedef struct urgym_sac_monitoring {
  * written.  No allocation, no host synchronisation; a launch failure midway as in urgym_sac_train. */
 int urgym_sac_train_monitored(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring, void* stream);
 
+/* ---- weights back to the device tensors (a checkpoint: the reference's train.py:31-36 continues a saved run, and the TARGET critic
+ * exists only as a packed buffer, blended in place by urgym_critic_load(tau < 1) and urgym_critic_adam_step(target)).  The packing
+ * map of ur_gym_amd/csrc/urgym_pack_map.h run the other way, on the device: every element of every destination tensor -- DEVICE
+ * pointers, float32, torch's [out][in] row-major layout, 4-byte aligned and nothing more -- is written from the one packed float that
+ * holds it; padding has no destination.  Copies only: every bit pattern goes through unchanged, NaN payloads and -0.0f included.
+ * Added WITHIN ABI version 4: no struct above changed, URGYM_ABI_VERSION did not move, the new symbols (urgym_actor_unpack,
+ * urgym_critic_unpack) are found by lookup.
+ *
+ * Each unpack is ONE launch on `stream`: no allocation, no host synchronisation, everything validated before the launch.  The
+ * destinations are written when the launch RUNS, not during the call.  Stream order holds against the loads, the Adam steps and the
+ * urgym_sac_train* calls: an unpack sees what those enqueued before it on the same stream left in the buffer, and nothing of those
+ * enqueued after it.  Every hidden width the objects accept is covered (32 to 512).
+ * ROUND TRIP: urgym_*_unpack followed by urgym_*_load (tau == 1) of the same tensors leaves the packed buffer bit for bit as it was. */
+
+/* urgym_actor_params_dev with pointers that are written. */
+typedef struct urgym_actor_params_out {
+  int32_t in_features;    /* must be the actor's */
+  int32_t hidden_width;   /* must be the actor's */
+  int32_t reserved0;      /* must be 0 */
+  float* w0;        /* latent_pi.0.weight [hidden_width][in_features] */
+  float* b0;        /* latent_pi.0.bias   [hidden_width] */
+  float* w1;        /* latent_pi.2.weight [hidden_width][hidden_width] */
+  float* b1;        /* latent_pi.2.bias   [hidden_width] */
+  float* w_mu;      /* mu.weight [6][hidden_width] */
+  float* b_mu;      /* mu.bias   [6] */
+  float* w_log_std; /* log_std.weight [6][hidden_width], or NULL together with b_log_std: the head is skipped */
+  float* b_log_std; /* log_std.bias   [6], or NULL together with w_log_std */
+} urgym_actor_params_out;
+
+/* urgym_q_network_dev with pointers that are written. */
+typedef struct urgym_q_network_out {
+  float* w0;  /* qf{i}.0.weight [hidden_width][in_features] */
+  float* b0;  /* qf{i}.0.bias   [hidden_width] */
+  float* w1;  /* qf{i}.2.weight [hidden_width][hidden_width] */
+  float* b1;  /* qf{i}.2.bias   [hidden_width] */
+  float* w_q; /* qf{i}.4.weight [1][hidden_width] */
+  float* b_q; /* qf{i}.4.bias   [1] */
+} urgym_q_network_out;
+
+typedef struct urgym_critic_params_out {
+  int32_t in_features;  /* must be the critic's */
+  int32_t hidden_width; /* must be the critic's */
+  int32_t reserved0;    /* must be 0 */
+  urgym_q_network_out qf[2];
+} urgym_critic_params_out;
+
+/* Writes an actor's tensors.  Refused (URGYM_ERR_ARG; handle and actor stay usable, nothing is launched, nothing is written): NULL
+ * handle / actor / out, an actor of another handle, a NULL required pointer (the message names it), only one of the two log_std
+ * pointers, log_std pointers for an actor that has no head, in_features or hidden_width other than the actor's, reserved0 != 0. */
+int urgym_actor_unpack(void* handle, void* actor, const urgym_actor_params_out* out, void* stream);
+
+/* Writes both Q-networks of a critic.  Refused: as urgym_actor_unpack (every pointer of both networks is required). */
+int urgym_critic_unpack(void* handle, void* critic, const urgym_critic_params_out* out, void* stream);
+
 /* Verification aid, not a hot path: synchronises the device, then copies the object's packed buffer (the kernel's own layout,
  * ur_gym_amd/csrc/urgym_pack_map.h) to host_out and stores its length in floats in *count.  host_out == NULL only reports *count;
  * otherwise capacity (in floats) must be at least that.  Refused: NULL handle / object / count, an object of another handle,
- * capacity too small. */
+ * capacity too small.  The parameters themselves, in torch's layout and without a synchronisation, are urgym_actor_unpack /
+ * urgym_critic_unpack: nothing that is kept should hold this layout. */
 int urgym_actor_read_packed(void* handle, void* actor, float* host_out, uint64_t capacity, uint64_t* count);
 int urgym_critic_read_packed(void* handle, void* critic, float* host_out, uint64_t capacity, uint64_t* count);
 

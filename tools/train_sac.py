@@ -14,6 +14,12 @@ With --monitor the training curve is printed as well, on both routes: every --lo
 the mean length and the success rate of the episodes the COLLECTING policy finished since the line before (evaluation.DeviceMonitor: the
 reference's Monitor and SB3's rollout/ep_rew_mean, ep_len_mean and success_rate, reduced on the device).  With --native those records,
 too, are written inside the one call and read after its one synchronise.
+--save PATH writes the WHOLE run as a checkpoint when it ends and every --save-every updates (SACLearner.save: the parameters, the target
+critic, every Adam moment, the entropy coefficient, the ring, the environment, the monitor, with --native the evaluation, and this loop's
+own counters); --resume PATH continues it with the same arguments up to --steps trips in all -- the reference's train.py:31-36 -- and
+prints the evaluation and monitor lines from the resume point on as the uninterrupted run prints them (on the device routes every number
+in them is the same; without --native the evaluations are this script's own and its best actor so far is kept only as its mean).
+--init-from ACTOR.npz CRITIC0.npz CRITIC1.npz starts a run from plain parameter files instead (SACLearner.load_parameters).
 """
 import argparse
 import json
@@ -59,7 +65,23 @@ def main():
     ap.add_argument("--log-every", type=int, default=100, help="loop trips between two lines of the training curve (--monitor)")
     ap.add_argument("--save-best", metavar="PATH", default=None,
                     help="write the actor of the best evaluation (mean episode return strictly above every earlier one) as an .npz")
+    ap.add_argument("--save", metavar="PATH", default=None,
+                    help="write the whole run as a checkpoint (SACLearner.save: learner, target critic, moments, ring, environment, monitor, "
+                         "evaluation, counters) when it ends, and every --save-every updates; written to a temporary name and renamed")
+    ap.add_argument("--save-every", type=int, default=0, metavar="UPDATES", help="updates between two checkpoints (0: only at the end); needs --save")
+    ap.add_argument("--resume", metavar="PATH", default=None,
+                    help="continue the run a checkpoint holds, with the same arguments, up to --steps trips in all: bit for bit the "
+                         "uninterrupted run on the device routes, and the same evaluation and monitor lines from the resume point on")
+    ap.add_argument("--init-from", nargs=3, metavar=("ACTOR.npz", "CRITIC0.npz", "CRITIC1.npz"), default=None,
+                    help="warm start from plain parameter files (the reference's SAC.load then learn, train.py:31-36): the actor's eight "
+                         "arrays as --save-best writes them, one file per Q-network; moments and step count start at zero")
     args = ap.parse_args()
+    if args.save_every and not args.save:
+        raise SystemExit("--save-every needs --save")
+    if args.save_every < 0:
+        raise SystemExit("--save-every must not be negative")
+    if args.resume and args.init_from:
+        raise SystemExit("--resume continues a run, --init-from starts one: give one of them")
 
     import torch
 
@@ -84,12 +106,6 @@ def main():
         raise SystemExit("--log-every must be at least 1")
     mon = DeviceMonitor(env, capacity=max(1, args.steps // args.log_every)) if args.monitor else None
 
-    def print_curve(seconds):
-        for rec in mon.results():  # synchronises
-            print(json.dumps({"trips": rec["iteration"], "env_steps": rec["iteration"] * env.num_envs, "seconds": seconds, "train_episodes": rec["episodes"],
-                              "train_mean_return": rec["mean_return"], "train_mean_length": rec["mean_length"],
-                              "train_success_rate_percent": 100.0 * rec["success_rate"]}), flush=True)
-
     def evaluate():
         eval_actor.load_parameters(learner.actor.tensors())
         test_env.reset(seed=args.seed + 1)
@@ -99,18 +115,49 @@ def main():
         print(json.dumps({"updates": updates, "env_steps": learner.env_steps * env.num_envs, "seconds": round(time.perf_counter() - t0, 1),
                           "mean_episode_return": res["mean_episode_reward"], "success_rate_percent": res["success_rate_percent"]}), flush=True)
 
-    step = 0
+    if args.init_from:
+        import numpy as np
+
+        actor = dict(np.load(args.init_from[0]))
+        learner.load_parameters(actor=actor, critics=[dict(np.load(p)) for p in args.init_from[1:]])
+
+    # the whole run's schedule, counted from its first trip whether this process starts there or resumes: an evaluation falls at the
+    # end of every trip in which the update count passes a multiple of --eval-every (evaluation.evaluation_points); warm-up trips run
+    # no update
+    _, idle = warmup_iterations(0, env.num_envs, learner.hp["learning_starts"], args.steps, 1)
+    points = evaluation_points(1, args.steps, args.updates_per_step, idle, args.eval_every) if args.steps > 0 else []
+    ev = DeviceEvaluation(test_env, learner.actor.tensors(), seed=args.seed + 1, capacity=max(1, len(points))) if args.native else None
+    parts = dict(replay=replay, monitor=mon, evaluation=ev)
+    step = shown_evals = shown_curve = 0
+    if args.resume:
+        extra = learner.load(args.resume, **parts)  # refuses another env, width, option set or hyperparameter, naming it
+        step, updates, best["mean"] = int(extra["trips"]), int(extra["updates"]), float(extra["best_mean"])
+        shown_evals, shown_curve = (ev.count if ev is not None else 0), (mon.count if mon is not None else 0)
+        if step > args.steps:
+            raise SystemExit(f"--resume: the checkpoint is {step} trips into the run, --steps asks for {args.steps} in all")
+
+    def save(trips):
+        learner.save(args.save, **parts, extra=dict(trips=trips, updates=updates, best_mean=best["mean"]))
+
+    def print_curve(seconds):
+        for rec in mon.results()[shown_curve:]:  # synchronises
+            print(json.dumps({"trips": rec["iteration"], "env_steps": rec["iteration"] * env.num_envs, "seconds": seconds, "train_episodes": rec["episodes"],
+                              "train_mean_return": rec["mean_return"], "train_mean_length": rec["mean_length"],
+                              "train_success_rate_percent": 100.0 * rec["success_rate"]}), flush=True)
+
     if args.native:
-        # one call for the whole run: an evaluation falls at the end of every trip in which the update count passes a multiple of
-        # --eval-every (evaluation.evaluation_points); warm-up trips run no update
-        _, idle = warmup_iterations(learner.env_steps, env.num_envs, learner.hp["learning_starts"], args.steps, 1)
-        points = evaluation_points(1, args.steps, args.updates_per_step, idle, args.eval_every) if args.steps > 0 else []
-        ev = DeviceEvaluation(test_env, learner.actor.tensors(), seed=args.seed + 1, capacity=max(1, len(points)))
-        if args.steps > 0:
-            learner.train(replay, args.steps, 1, args.updates_per_step, seed=args.seed, first_draw=0, evaluation=ev, eval_every=args.eval_every,
+        # one call for the whole run -- or, with --save-every, one per stretch between two checkpoints: split calls are bit for bit the
+        # single one (the schedule's counters are handed on), so the checkpoints cost the launches nothing but their own copies
+        stretch = max(1, -(-args.save_every // max(1, args.updates_per_step))) if args.save_every else max(1, args.steps)
+        while step < args.steps:
+            n = min(stretch, args.steps - step)
+            learner.train(replay, n, 1, args.updates_per_step, seed=args.seed, first_draw=updates, evaluation=ev, eval_every=args.eval_every,
                           **(dict(monitor=mon, log_every=args.log_every) if mon is not None else {}))
+            step, updates = step + n, learner.adam_state["step"]
+            if args.save and (args.save_every or step == args.steps):
+                save(step)
         seconds = None
-        for trip, rec in zip(points, ev.results()):  # results() synchronises, once
+        for trip, rec in list(zip(points, ev.results()))[shown_evals:]:  # results() synchronises, once
             seconds = round(time.perf_counter() - t0, 1) if seconds is None else seconds
             done = max(0, trip + 1 - idle) * args.updates_per_step
             print(json.dumps({"updates": done, "env_steps": (trip + 1) * env.num_envs, "seconds": seconds, "mean_episode_return": rec["mean_return"],
@@ -120,8 +167,6 @@ def main():
             print_curve(round(time.perf_counter() - t0, 1) if seconds is None else seconds)
         if args.save_best and ev.best_state()[1] >= 0:
             ev.save_best(args.save_best)
-        ev.close()
-        step = args.steps
     for step in range(step, args.steps):  # the Python loop (every trip of it where --native is off)
         learner.collect(replay, 1, monitor=mon)
         if mon is not None and (step + 1) % args.log_every == 0:
@@ -133,8 +178,15 @@ def main():
             updates += 1
             if updates % args.eval_every == 0:
                 evaluate()
-    if mon is not None and not args.native:
-        print_curve(round(time.perf_counter() - t0, 1))
+        if args.save_every and updates // args.save_every > (updates - args.updates_per_step) // args.save_every:
+            save(step + 1)  # this trip is done
+    if not args.native:
+        if mon is not None:
+            print_curve(round(time.perf_counter() - t0, 1))
+        if args.save:
+            save(args.steps)
+    if ev is not None:
+        ev.close()
     if args.save_best and best["tensors"] is not None:
         save_actor(args.save_best, best["tensors"])
     eval_actor.close()

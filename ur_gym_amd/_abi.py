@@ -268,6 +268,21 @@ class CriticParamsDev(C.Structure):
     _fields_ = [("in_features", C.c_int32), ("hidden_width", C.c_int32), ("reserved0", C.c_int32), ("qf", QNetworkDev * 2)]
 
 
+class ActorParamsOut(C.Structure):
+    """urgym_actor_params_out: ActorParamsDev with pointers that are written (urgym_actor_unpack)."""
+    _fields_ = list(ActorParamsDev._fields_)
+
+
+class QNetworkOut(C.Structure):
+    """urgym_q_network_out: QNetworkDev with pointers that are written."""
+    _fields_ = list(QNetworkDev._fields_)
+
+
+class CriticParamsOut(C.Structure):
+    """urgym_critic_params_out: the shape for checking + the two Q-networks that are written (urgym_critic_unpack)."""
+    _fields_ = [("in_features", C.c_int32), ("hidden_width", C.c_int32), ("reserved0", C.c_int32), ("qf", QNetworkOut * 2)]
+
+
 class AdamHyper(C.Structure):
     """urgym_adam_hyper: Adam's hyperparameters and the 1-based index of this step (the caller counts; the library keeps no state)."""
     _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("step", C.c_int64), ("reserved0", C.c_int32)]
@@ -440,6 +455,8 @@ EXPORTED_SYMBOLS = [
     "urgym_replay_sample",
     "urgym_actor_load",
     "urgym_critic_load",
+    "urgym_actor_unpack",
+    "urgym_critic_unpack",
     "urgym_adam_coefficients",
     "urgym_actor_adam_step",
     "urgym_critic_adam_step",

@@ -84,7 +84,9 @@ def lib():
                                       C.POINTER(_abi.ReplayBatch), C.c_void_p]
     L.urgym_actor_load.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.ActorParamsDev), C.c_void_p]
     L.urgym_critic_load.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.CriticParamsDev), C.c_float, C.c_void_p]
-    L.urgym_adam_coefficients.argtypes = [C.POINTER(_abi.AdamHyper), C.POINTER(C.c_float)]
+    L.urgym_actor_unpack.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.ActorParamsOut), C.c_void_p]
+    L.urgym_critic_unpack.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.CriticParamsOut), C.c_void_p]
+    L.urgym_adam_coefficients.argtypes =[C.POINTER(_abi.AdamHyper), C.POINTER(C.c_float)]
     L.urgym_actor_adam_step.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.ActorAdam), C.POINTER(_abi.AdamHyper), C.c_void_p]
     L.urgym_critic_adam_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(_abi.CriticAdam), C.POINTER(_abi.AdamHyper), C.c_float, C.c_void_p]
     L.urgym_sac_entropy_step.argtypes = [C.c_void_p, C.POINTER(_abi.SacEntropyArgs), C.POINTER(_abi.AdamHyper), C.c_void_p]

@@ -1,5 +1,5 @@
 // urgym_policy_abi.hip — the learner's half of the C-ABI of include/urgym.h: actors (create / forward / sample / rollouts), the replay
-// ring, the weight reloads, the twin critic and its two gradients, the actor's parameter gradients, the Adam steps, SAC's entropy step and loss terms, the training loop that composes them in one call (urgym_sac_train; its index arithmetic is urgym_sac_schedule.h), the evaluation inside that call (urgym_eval_stats, urgym_actor_snapshot, urgym_policy_evaluate, urgym_sac_train_evaluated; urgym_eval.h, urgym_eval_schedule.h), and the training-episode statistics inside it (urgym_monitor_fold, urgym_monitor_stats, urgym_sac_train_monitored; urgym_monitor.h).  Host code only: every check is made here, before the first launch,
+// ring, the weight reloads and their inverse (urgym_actor_unpack, urgym_critic_unpack), the twin critic and its two gradients, the actor's parameter gradients, the Adam steps, SAC's entropy step and loss terms, the training loop that composes them in one call (urgym_sac_train; its index arithmetic is urgym_sac_schedule.h), the evaluation inside that call (urgym_eval_stats, urgym_actor_snapshot, urgym_policy_evaluate, urgym_sac_train_evaluated; urgym_eval.h, urgym_eval_schedule.h), and the training-episode statistics inside it (urgym_monitor_fold, urgym_monitor_stats, urgym_sac_train_monitored; urgym_monitor.h).  Host code only: every check is made here, before the first launch,
 // and every launch goes through urgym_actor.h, urgym_critic.h, urgym_replay.h, urgym_weights.h, urgym_adam.h, urgym_sac_terms.h, urgym_eval.h and urgym_monitor.h, or through do_step of urgym_hip.hip
 // (urgym_handle.h).  No kernel lives in this unit, so adding a check here leaves the step kernels' object file alone.
 #include <hip/hip_runtime.h>
@@ -663,6 +663,79 @@ int urgym_critic_load(void* handle, void* critic, const urgym_critic_params_dev*
   }
   HIP_TRY(h, hipSetDevice(h->device));
   critic_pack_launch(buf, src, tau, (hipStream_t)stream);
+  return launched(h);
+}
+
+// ---- weights back to device tensors (the unpack kernels of urgym_weights.hip): a checking half that launches nothing and leaves what
+// the launching half needs, like the entry points urgym_sac_train composes
+namespace {
+
+struct ActorUnpack {
+  ActorPacked buf;
+  float* dst[PACK_ACTOR_TENSORS];
+};
+struct CriticUnpack {
+  CriticPacked buf;
+  float* dst[2 * PACK_CRITIC_TENSORS];
+};
+
+int check_actor_unpack(Handle* h, void* actor, const urgym_actor_params_out* p, const char* who, ActorUnpack* call) {
+  Actor* a = member(h->actors, actor);
+  if (!a) return fail_in(h, URGYM_ERR_ARG, who, "not an actor of this handle (actors belong to the handle they were created with)");
+  if (!p) return fail_in(h, URGYM_ERR_ARG, who, "null out");
+  if (p->reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "reserved0 must be 0");
+  call->buf = actor_packed(a);
+  if (p->in_features != call->buf.in_features || p->hidden_width != call->buf.hidden)
+    return failf(h, URGYM_ERR_ARG, "%s: out is %d -> %d, the actor is %d -> %d", who, p->in_features, p->hidden_width, call->buf.in_features, call->buf.hidden);
+  float* const dst[PACK_ACTOR_TENSORS] = {p->w0, p->b0, p->w1, p->b1, p->w_mu, p->b_mu, p->w_log_std, p->b_log_std};
+  static const char* const names[PACK_ACTOR_TENSORS] = {"w0", "b0", "w1", "b1", "w_mu", "b_mu", "w_log_std", "b_log_std"};
+  for (int i = 0; i <= PACK_B_OUT; i++)
+    if (!dst[i]) return failf(h, URGYM_ERR_ARG, "%s: out->%s is null", who, names[i]);
+  if (!p->w_log_std != !p->b_log_std) return fail_in(h, URGYM_ERR_ARG, who, "the log_std head needs both w_log_std and b_log_std, or neither");
+  if (p->w_log_std && !actor_has_log_std(a)) return fail_in(h, URGYM_ERR_ARG, who, "the actor has no log_std head (urgym_actor_set_log_std): w_log_std and b_log_std must be null");
+  for (int i = 0; i < PACK_ACTOR_TENSORS; i++) call->dst[i] = dst[i];
+  return URGYM_OK;
+}
+
+int check_critic_unpack(Handle* h, void* critic, const urgym_critic_params_out* p, const char* who, CriticUnpack* call) {
+  Critic* c = member(h->critics, critic);
+  if (!c) return fail_in(h, URGYM_ERR_ARG, who, "not a critic of this handle (critics belong to the handle they were created with)");
+  if (!p) return fail_in(h, URGYM_ERR_ARG, who, "null out");
+  if (p->reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "reserved0 must be 0");
+  call->buf = critic_packed(c);
+  if (p->in_features != call->buf.in_features || p->hidden_width != call->buf.hidden)
+    return failf(h, URGYM_ERR_ARG, "%s: out is %d -> %d, the critic is %d -> %d", who, p->in_features, p->hidden_width, call->buf.in_features, call->buf.hidden);
+  static const char* const names[PACK_CRITIC_TENSORS] = {"w0", "b0", "w1", "b1", "w_q", "b_q"};
+  for (int net = 0; net < 2; net++) {
+    const urgym_q_network_out& q = p->qf[net];
+    float* const one[PACK_CRITIC_TENSORS] = {q.w0, q.b0, q.w1, q.b1, q.w_q, q.b_q};
+    for (int i = 0; i < PACK_CRITIC_TENSORS; i++) {
+      if (!one[i]) return failf(h, URGYM_ERR_ARG, "%s: out->qf[%d].%s is null", who, net, names[i]);
+      call->dst[PACK_CRITIC_TENSORS * net + i] = one[i];
+    }
+  }
+  return URGYM_OK;
+}
+
+}  // namespace
+
+int urgym_actor_unpack(void* handle, void* actor, const urgym_actor_params_out* out, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  ActorUnpack call;
+  if (int rc = check_actor_unpack(h, actor, out, "urgym_actor_unpack", &call)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  actor_unpack_launch(call.buf, call.dst, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_critic_unpack(void* handle, void* critic, const urgym_critic_params_out* out, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  CriticUnpack call;
+  if (int rc = check_critic_unpack(h, critic, out, "urgym_critic_unpack", &call)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  critic_unpack_launch(call.buf, call.dst, (hipStream_t)stream);
   return launched(h);
 }
 

@@ -655,6 +655,31 @@ class DeviceActor:
         _native.check(env.lib.urgym_actor_load(env._h, self._a, C.byref(p), env._stream()), env._h)
         self.has_log_std = self.has_log_std or head
 
+    def parameters(self, out=None):
+        """The actor's tensors as the packed buffer holds them (urgym_actor_unpack): a dict of device tensors under ACTOR_ARRAYS, and
+        LOG_STD_ARRAYS too when the actor has the head.  `out`: the tensors to write, checked as ``check_parameters`` checks sources
+        (without the head tensors the head is skipped); None = fresh ones.  ONE launch on torch's current stream, nothing is
+        synchronised: it sees the loads and Adam steps enqueued before it, and the tensors hold the result once it has run."""
+        import ctypes as C
+
+        import torch
+
+        from . import _abi, _native
+
+        env, n, H = self.env, self.in_features, self.hidden_width
+        if out is None:
+            shapes = dict(zip(ACTOR_ARRAYS + LOG_STD_ARRAYS, ((H, n), (H,), (H, H), (H,), (6, H), (6,), (6, H), (6,))))
+            keys = ACTOR_ARRAYS + (LOG_STD_ARRAYS if self.has_log_std else ())
+            out = {k: torch.empty(shapes[k], dtype=torch.float32, device=env.device) for k in keys}
+        head = self.check_parameters(out, n, H, env.device)
+        if head and not self.has_log_std:
+            raise ValueError(f"parameters: the actor has no log_std head, out must not hold {LOG_STD_ARRAYS}")
+        p = _abi.ActorParamsOut(n, H, 0)
+        for field, key in zip(_abi.ACTOR_DEV_ARRAYS, ACTOR_ARRAYS + (LOG_STD_ARRAYS if head else ())):
+            setattr(p, field, C.cast(out[key].data_ptr(), C.POINTER(C.c_float)))
+        _native.check(env.lib.urgym_actor_unpack(env._h, self._a, C.byref(p), env._stream()), env._h)
+        return out
+
     def packed(self):
         """The packed weight buffer as the kernel reads it (float32 numpy array; urgym_actor_read_packed).  A verification aid:
         synchronises the device."""
@@ -854,6 +879,29 @@ class DeviceCritic:
             p.qf[i] = _abi.QNetworkDev(*[C.cast(w[k].data_ptr(), C.POINTER(C.c_float)) for k in CRITIC_ARRAYS])
         _native.check(env.lib.urgym_critic_load(env._h, self._c, C.byref(p), tau, env._stream()), env._h)
 
+    def parameters(self, out=None):
+        """Both Q-networks' tensors as the packed buffer holds them (urgym_critic_unpack): a list of two dicts of device tensors
+        under CRITIC_ARRAYS -- for a target critic, the Polyak average itself, which no torch tensor holds otherwise.  `out`: the
+        tensors to write, checked as ``check_parameters`` checks sources; None = fresh ones.  ONE launch on torch's current
+        stream, nothing is synchronised; stream order as for ``DeviceActor.parameters``."""
+        import ctypes as C
+
+        import torch
+
+        from . import _abi, _native
+
+        env, n, H = self.env, self.in_features, self.hidden_width
+        if out is None:
+            shapes = dict(zip(CRITIC_ARRAYS, ((H, n), (H,), (H, H), (H,), (1, H), (1,))))
+            out = [{k: torch.empty(sh, dtype=torch.float32, device=env.device) for k, sh in shapes.items()} for _ in range(2)]
+        out = [dict(w) for w in out]
+        self.check_parameters(out, n, H, env.device)
+        p = _abi.CriticParamsOut(n, H, 0)
+        for i, w in enumerate(out):
+            p.qf[i] = _abi.QNetworkOut(*[C.cast(w[k].data_ptr(), C.POINTER(C.c_float)) for k in CRITIC_ARRAYS])
+        _native.check(env.lib.urgym_critic_unpack(env._h, self._c, C.byref(p), env._stream()), env._h)
+        return out
+
     def packed(self):
         """The packed weight buffer of both networks as the kernel reads it (float32 numpy array; urgym_critic_read_packed).  A
         verification aid: synchronises the device."""
@@ -926,6 +974,61 @@ class DeviceReplay:
 
     def __len__(self):
         return self.filled * self.env.num_envs
+
+    def _geometry(self):
+        env = self.env
+        return dict(capacity=self.capacity, num_envs=env.num_envs, obs_dim=env.obs_dim, goal_dim=env.goal_dim)
+
+    def state_dict(self, include_data=True):
+        """The ring for a checkpoint: ``cursor``, ``filled``, the geometry, and under ``ring`` every tensor of
+        ``_abi.REPLAY_RING_FIELDS`` as a host array of the ``filled`` valid slots, oldest first.  ``include_data=False`` leaves the
+        tensors out: such a state loads as an empty ring.  Synchronises (device-to-host copies)."""
+        import torch
+
+        from . import _abi
+
+        out = dict(self._geometry(), cursor=self.cursor, filled=self.filled, include_data=bool(include_data))
+        if include_data:
+            slots = torch.as_tensor([(self.oldest_slot + i) % self.capacity for i in range(self.filled)], dtype=torch.int64, device=self.env.device)
+            whole = self.filled == self.capacity and self.oldest_slot == 0
+            out["ring"] = {name: (self.ring[name] if whole else self.ring[name].index_select(0, slots)).cpu().numpy()
+                           for name, _, _, _ in _abi.REPLAY_RING_FIELDS}
+        return out
+
+    def check_state_dict(self, state):
+        """Raises ValueError unless `state` is a ``state_dict`` of a ring of this capacity and env shape.  Writes nothing."""
+        from . import _abi
+
+        for k, v in self._geometry().items():
+            if int(state[k]) != v:
+                raise ValueError(f"DeviceReplay.load_state_dict: {k} is {state[k]} in the state, {v} here")
+        cursor, filled = int(state["cursor"]), int(state["filled"])
+        if not (0 <= cursor < self.capacity and 0 <= filled <= self.capacity):
+            raise ValueError(f"DeviceReplay.load_state_dict: cursor {cursor} or filled {filled} outside a ring of {self.capacity}")
+        if state["include_data"]:
+            env = self.env
+            for name, ct, shape, _ in _abi.REPLAY_RING_FIELDS:
+                a, want = np.asarray(state["ring"][name]), (filled,) + tuple(shape(1, env.num_envs, env.obs_dim, env.goal_dim)[1:])
+                if a.dtype != np.dtype(ct) or a.shape != want:
+                    raise ValueError(f"DeviceReplay.load_state_dict: ring[{name!r}] must be {np.dtype(ct)} {want}, got {a.dtype} {a.shape}")
+
+    def load_state_dict(self, state):
+        """Restores what ``state_dict`` saved, every tensor to the slots it came from, so that ``oldest_slot`` and the index draw see
+        the same ring.  A state without data leaves an empty ring (``filled == 0``) at the saved cursor.  A capacity or env-shape
+        mismatch raises ValueError before anything is written."""
+        import torch
+
+        self.check_state_dict(state)
+        cursor, filled = int(state["cursor"]), int(state["filled"])
+        if not state["include_data"]:
+            self.cursor, self.filled = cursor, 0
+            return
+        oldest = (cursor - filled) % self.capacity
+        slots = torch.as_tensor([(oldest + i) % self.capacity for i in range(filled)], dtype=torch.int64, device=self.env.device)
+        for name, t in self.ring.items():
+            if filled:
+                t.index_copy_(0, slots, torch.from_numpy(np.ascontiguousarray(state["ring"][name])).to(self.env.device))
+        self.cursor, self.filled = cursor, filled
 
     def collect(self, actor, num_steps, sample=None):
         """`num_steps` x (store pass, actor, step) from slot ``cursor`` on, without returning to Python; `sample` as in
@@ -1187,6 +1290,43 @@ class DeviceEvaluation:
         ``DeterministicActor.load`` read.  Synchronises."""
         save_actor(path, self.best)
 
+    def state_dict(self):
+        """The evaluation for a checkpoint: the records written so far, the best actor's tensors, ``best_mean``, ``best_index`` and
+        ``count``; ``seed`` and ``num_steps``, which a load checks; and the evaluation environment's ``checkpoint_state`` (its sticky
+        status words are the only thing of it that an evaluation does not rewrite).  Synchronises."""
+        return dict(seed=self.seed, num_steps=self.num_steps, count=self.count, records=self.records[:self.count].cpu().numpy(),
+                    best={k: v.cpu().numpy() for k, v in self.best.items()}, best_mean=self.best_mean.cpu().numpy(),
+                    best_index=self.best_index.cpu().numpy(), env=self.env.checkpoint_state())
+
+    def load_state_dict(self, state):
+        """Restores what ``state_dict`` saved, in place (a ``struct`` made earlier stays valid).  Raises ValueError, before anything
+        is written, for another seed, episode length, actor shape or environment, or more records than this evaluation's capacity."""
+        import torch
+
+        from . import _abi
+
+        count, records = int(state["count"]), np.asarray(state["records"])
+        if int(state["seed"]) != self.seed or int(state["num_steps"]) != self.num_steps:
+            raise ValueError(f"DeviceEvaluation.load_state_dict: the state evaluates with seed {state['seed']} for {state['num_steps']} steps, "
+                             f"this evaluation with seed {self.seed} for {self.num_steps}")
+        if not 0 <= count <= self.capacity or records.shape != (count, _abi.EVAL_RECORD_WORDS) or records.dtype != np.int64:
+            raise ValueError(f"DeviceEvaluation.load_state_dict: {count} records ({records.dtype} {records.shape}) do not fit a capacity of {self.capacity}")
+        best = {k: np.asarray(state["best"][k]) for k in ACTOR_ARRAYS + LOG_STD_ARRAYS}
+        for k, v in best.items():
+            if v.dtype != np.float32 or v.shape != tuple(self.best[k].shape):
+                raise ValueError(f"DeviceEvaluation.load_state_dict: best[{k!r}] must be float32 {tuple(self.best[k].shape)}, got {v.dtype} {v.shape}")
+        self.env.check_checkpoint(state["env"])
+        for k, v in best.items():
+            self.best[k].copy_(torch.from_numpy(v))
+        self.best_mean.copy_(torch.from_numpy(np.asarray(state["best_mean"], dtype=np.float64).reshape(1)))
+        self.best_index.copy_(torch.from_numpy(np.asarray(state["best_index"], dtype=np.int64).reshape(1)))
+        self.records.zero_()
+        self.records[:count].copy_(torch.from_numpy(np.ascontiguousarray(records)))
+        self.env.restore_checkpoint(state["env"])
+        self.count = count
+        if count:
+            self.actor.has_log_std = True
+
     def close(self):
         self._struct = self._source = None
         self.actor.close()
@@ -1340,6 +1480,34 @@ class DeviceMonitor:
         """What a native call of `iterations` iterations that wrote `records` records leaves behind on the host side."""
         self.iterations += int(iterations)
         self.count += int(records)
+
+    def state_dict(self):
+        """The monitor for a checkpoint: the per-env running state, the records written so far, ``iterations`` and ``count`` (and
+        ``num_envs`` and ``clear``, which a load checks).  Synchronises."""
+        return dict(num_envs=self.env.num_envs, clear=self.clear, iterations=self.iterations, count=self.count,
+                    state={k: v.cpu().numpy() for k, v in self.state.items()}, records=self.records[:self.count].cpu().numpy())
+
+    def load_state_dict(self, state):
+        """Restores what ``state_dict`` saved, in place (a ``struct`` made earlier stays valid).  Raises ValueError, before anything
+        is written, for another env count or ``clear``, or more records than this monitor's capacity."""
+        import torch
+
+        from . import _abi
+
+        count, records = int(state["count"]), np.asarray(state["records"])
+        if int(state["num_envs"]) != self.env.num_envs or bool(state["clear"]) != self.clear:
+            raise ValueError(f"DeviceMonitor.load_state_dict: the state is of {state['num_envs']} envs with clear={state['clear']}, "
+                             f"this monitor of {self.env.num_envs} with clear={self.clear}")
+        if not 0 <= count <= self.capacity or records.shape != (count, _abi.MONITOR_RECORD_WORDS) or records.dtype != np.int64:
+            raise ValueError(f"DeviceMonitor.load_state_dict: {count} records ({records.dtype} {records.shape}) do not fit a capacity of {self.capacity}")
+        arrays = _monitor_arrays({k: np.asarray(v) for k, v in dict(state["state"]).items()})
+        if arrays["running_return"].shape != (self.env.num_envs,):
+            raise ValueError(f"DeviceMonitor.load_state_dict: the state arrays must be [{self.env.num_envs}]")
+        for k, v in arrays.items():
+            self.state[k].copy_(torch.from_numpy(v))
+        self.records.zero_()
+        self.records[:count].copy_(torch.from_numpy(np.ascontiguousarray(records)))
+        self.iterations, self.count = int(state["iterations"]), count
 
     def fold(self, replay, first_slot, num_steps):
         """The `num_steps` steps `replay` holds from `first_slot` on, folded into the state (``env.monitor_fold``): call it behind the

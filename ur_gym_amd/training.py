@@ -46,8 +46,12 @@ minibatch gather on the HIP kernels, and gradients and optimisers in torch autog
     updates, their statistics as records on the device, and the best actor's tensors, which ``DeviceEvaluation.save_best`` writes as an
     ``.npz`` ``DeviceActor.load`` reads.  Given an ``evaluation.DeviceMonitor``, ``collect`` and ``train`` also keep the reference's
     ``Monitor`` (train.py:52) on the device: the return, the length and the success of the episodes the collecting policy finishes, as
-    records of the training curve (SB3's rollout/ep_rew_mean, ep_len_mean and success_rate); nothing else is logged, and the checkpoint
-    holds the actor alone; tools/train_sac.py runs it.
+    records of the training curve (SB3's rollout/ep_rew_mean, ep_len_mean and success_rate); nothing else is logged.
+    ``save`` / ``load`` write and read the WHOLE run -- the parameters, the target critic (through the unpack kernel: it exists only
+    packed), every Adam moment, the entropy coefficient, the counters and, handed in, the replay ring, the environment, the monitor and
+    the evaluation -- so that a run rebuilt in fresh objects continues bit for bit; ``load_parameters`` is the
+    reference's ``SAC.load`` then ``learn`` (train.py:31-36) from plain parameter files.  ``DeviceEvaluation.save_best`` still writes the
+    best actor alone; tools/train_sac.py runs all of it.
 """
 import numpy as np
 import torch
@@ -115,6 +119,24 @@ def host_arrays(tensors):
     if isinstance(tensors, dict):
         return {k: v.detach().cpu().numpy().copy() for k, v in tensors.items()}
     return [host_arrays(t) for t in tensors]
+
+
+def _optimizer_to_host(sd):
+    """A ``torch.optim`` state dict as a checkpoint tree: tensors as numpy arrays, the parameter indices as strings."""
+    state = {str(i): {k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in s.items()} for i, s in sd["state"].items()}
+    return dict(state=state, param_groups=[{k: (list(v) if isinstance(v, tuple) else v) for k, v in g.items()} for g in sd["param_groups"]])
+
+
+def _optimizer_from_host(tree, opt, device):
+    """The inverse of ``_optimizer_to_host`` for ``opt.load_state_dict``: every tensor goes where `opt` keeps its like (the step
+    count on the host, the moments on `device`).  The hyperparameters of the parameter groups stay `opt`'s own, learning rate included."""
+    here = opt.state_dict()
+    if [len(g["params"]) for g in tree["param_groups"]] != [len(g["params"]) for g in here["param_groups"]]:
+        raise ValueError("load_state_dict: the optimiser state is of other parameter groups")
+    state = {}
+    for i, s in tree["state"].items():
+        state[int(i)] = {k: (torch.from_numpy(np.array(v)).to("cpu" if k == "step" else device) if isinstance(v, np.ndarray) else v) for k, v in s.items()}
+    return dict(state=state, param_groups=here["param_groups"])
 
 
 class SACLearner:
@@ -390,6 +412,212 @@ class SACLearner:
             sc = tr["scratch"]
             self.last_update = dict(log_prob=sc["log_prob"], y=sc["y"], q=sc["q"], q_min=sc["q_min"], dqmin_da=sc["dqmin_da"])
         return {"critic_loss": losses[0], "actor_loss": losses[1], "ent_coef_loss": losses[2]}
+
+    # ------------------------------------------------------------------------------------------------ checkpoints
+    OVERRIDABLE = ("learning_rate", "learning_starts")  # what a resumed run may set anew; everything else must be the checkpoint's
+
+    def _optimizers(self):
+        return dict(actor_opt=self.actor_opt, critic_opt=self.critic_opt, ent_opt=self.ent_opt)
+
+    def state_dict(self):
+        """Everything the learner is, as host arrays and scalars: the actor's eight and the critics' twelve parameter tensors, the
+        TARGET critic's twelve in the same layout (``DeviceCritic.parameters``: the unpack kernel; the Polyak average lives nowhere
+        else), ``log_ent_coef``, ``adam_state`` and ``entropy_state``'s two moments where the learner has them, the three
+        ``torch.optim`` state dicts and the ``torch.Generator`` state (empty and unused on the device routes), ``env_steps``, ``draw``,
+        ``seed``, the hyperparameters, the env id and env count.  One launch, then ONE synchronisation, then copies."""
+        target = self.target.parameters()
+        torch.cuda.synchronize(self.env.device)
+        host = lambda w: {k: v.detach().cpu().numpy() for k, v in w.items()}  # noqa: E731
+        out = dict(env_id=self.env.env_id, num_envs=self.env.num_envs, hp=dict(self.hp), seed=self.seed, env_steps=self.env_steps, draw=self.draw,
+                   actor=host(self.actor.tensors()), critic=[host(w) for w in self.critic.tensors()], target=[host(w) for w in target],
+                   log_ent_coef=self.log_ent_coef.detach().cpu().numpy(), adam_state=None, entropy_state=None)
+        st, es = self.adam_state, self.entropy_state
+        if st is not None:
+            out["adam_state"] = dict(step=st["step"], betas=list(st["betas"]), eps=st["eps"], actor=[host(w) for w in st["actor"]],
+                                     critic=[[host(w) for w in pair] for pair in st["critic"]])
+        if es is not None:
+            out["entropy_state"] = dict(exp_avg=es["exp_avg"].cpu().numpy(), exp_avg_sq=es["exp_avg_sq"].cpu().numpy())
+        out["torch"] = dict({name: _optimizer_to_host(opt.state_dict()) for name, opt in self._optimizers().items()},
+                            generator=self.noise.get_state().cpu().numpy())
+        return out
+
+    def _tensor_plan(self, state):
+        """[(destination tensor, source array, name)] for every tensor ``load_state_dict`` writes in place, shapes and dtypes checked."""
+        plan = []
+
+        def add(dst, src, name):
+            a = np.asarray(src)
+            if a.dtype != np.float32 or a.shape != tuple(dst.shape):
+                raise ValueError(f"load_state_dict: {name} must be float32 {tuple(dst.shape)}, got {a.dtype} {a.shape}")
+            plan.append((dst, a, name))
+
+        def add_set(dst, src, name):
+            if sorted(dst) != sorted(src):
+                raise ValueError(f"load_state_dict: {name} holds {sorted(src)}, expected {sorted(dst)}")
+            for k in dst:
+                add(dst[k], src[k], f"{name}.{k}")
+
+        add_set(self.actor.tensors(), state["actor"], "actor")
+        for i, w in enumerate(self.critic.tensors()):
+            add_set(w, state["critic"][i], f"critic.qf{i}")
+        add(self.log_ent_coef, state["log_ent_coef"], "log_ent_coef")
+        st, es = self.adam_state, self.entropy_state
+        if st is not None:
+            for j, moment in enumerate(("exp_avg", "exp_avg_sq")):
+                add_set(st["actor"][j], state["adam_state"]["actor"][j], f"adam_state.actor.{moment}")
+                for i in range(2):
+                    add_set(st["critic"][j][i], state["adam_state"]["critic"][j][i], f"adam_state.critic.{moment}.qf{i}")
+        if es is not None:
+            for k in ("exp_avg", "exp_avg_sq"):
+                add(es[k], state["entropy_state"][k], f"entropy_state.{k}")
+        return plan
+
+    def check_state_dict(self, state, override=()):
+        """Raises ValueError naming the first difference unless `state` is a ``state_dict`` of a learner like this one: the same env id
+        and env count, the same hyperparameters -- widths and the ``device_*`` option set among them -- but those named in `override`
+        (of ``OVERRIDABLE``), and tensors of this learner's shapes.  Writes nothing.  Returns what ``load_state_dict`` needs."""
+        unknown = [k for k in override if k not in self.OVERRIDABLE]
+        if unknown:
+            raise ValueError(f"load_state_dict: only {self.OVERRIDABLE} may be overridden, got {unknown}")
+        if state["env_id"] != self.env.env_id:
+            raise ValueError(f"load_state_dict: env_id is {state['env_id']!r} in the checkpoint, {self.env.env_id!r} here")
+        if int(state["num_envs"]) != self.env.num_envs:
+            raise ValueError(f"load_state_dict: num_envs is {state['num_envs']} in the checkpoint, {self.env.num_envs} here")
+        for k in SAC_DEFAULTS:
+            if k in override:
+                continue
+            if k not in state["hp"] or state["hp"][k] != self.hp[k]:
+                raise ValueError(f"load_state_dict: {k} is {state['hp'].get(k)!r} in the checkpoint, {self.hp[k]!r} here")
+        for name, mine in (("adam_state", self.adam_state), ("entropy_state", self.entropy_state)):
+            if (state[name] is None) != (mine is None):
+                raise ValueError(f"load_state_dict: {name} is {'absent' if state[name] is None else 'present'} in the checkpoint and the reverse here")
+        if self.adam_state is not None:
+            st, saved = self.adam_state, state["adam_state"]
+            if list(saved["betas"]) != list(st["betas"]) or saved["eps"] != st["eps"]:
+                raise ValueError(f"load_state_dict: adam_state has betas {saved['betas']} and eps {saved['eps']} in the checkpoint, {list(st['betas'])} and {st['eps']} here")
+        plan = self._tensor_plan(state)
+        n, H = self.target.in_features, self.target.hidden_width
+        shapes = dict(zip(CRITIC_ARRAYS, ((H, n), (H,), (H, H), (H,), (1, H), (1,))))
+        target = []
+        for i in range(2):
+            w = {k: np.asarray(state["target"][i][k]) for k in CRITIC_ARRAYS}
+            for k, a in w.items():
+                if a.dtype != np.float32 or a.shape != shapes[k]:
+                    raise ValueError(f"load_state_dict: target.qf{i}.{k} must be float32 {shapes[k]}, got {a.dtype} {a.shape}")
+            target.append(w)
+        return plan, target
+
+    def load_state_dict(self, state, override=()):
+        """Puts a ``state_dict`` back.  Refuses (ValueError, nothing written) what ``check_state_dict`` refuses; `override` names the
+        hyperparameters of ``OVERRIDABLE`` for which this learner's own value stays.  Every tensor is written IN PLACE, so the
+        ``.grad`` aliases, the workspaces and a ``train`` binding made earlier stay valid; then the three packed buffers are rebuilt by
+        the launches that always build them: ``device_actor.load_parameters``, ``online.load_parameters(tau=1)`` and
+        ``target.load_parameters(the saved target tensors, tau=1)``.  Not synchronised beyond the host-to-device copies."""
+        plan, target = self.check_state_dict(state, override)
+        dev = self.env.device
+        with torch.no_grad():
+            for dst, a, _ in plan:
+                dst.copy_(torch.from_numpy(np.ascontiguousarray(a)))
+        if self.adam_state is not None:
+            self.adam_state["step"] = int(state["adam_state"]["step"])
+        for name, opt in self._optimizers().items():
+            opt.load_state_dict(_optimizer_from_host(state["torch"][name], opt, dev))
+        self.noise.set_state(torch.from_numpy(np.ascontiguousarray(state["torch"]["generator"])))
+        self.seed, self.env_steps, self.draw = int(state["seed"]), int(state["env_steps"]), int(state["draw"])
+        if self._train is not None:
+            self._train["binding"].struct.seed = self.seed  # the collection's seed of a binding made before the load
+        self._repack([{k: torch.from_numpy(np.ascontiguousarray(a)).to(dev) for k, a in w.items()} for w in target])
+
+    def _repack(self, target_tensors):
+        """The three packed buffers from the torch parameters as they stand, and the target from `target_tensors`."""
+        self.device_actor.load_parameters(self.actor.tensors())
+        if self.online is not None:
+            self.online.load_parameters(self.critic.tensors(), tau=1.0)
+        self.target.load_parameters(target_tensors, tau=1.0)
+
+    def load_parameters(self, actor, critics, target=None, log_ent_coef=None):
+        """A warm start from plain parameter files, the reference's ``SAC.load(...)`` followed by ``learn`` (train.py:31-36): `actor` a
+        dict of arrays under ACTOR_ARRAYS + LOG_STD_ARRAYS, `critics` (and `target`, default `critics`) two dicts under
+        CRITIC_ARRAYS, as tests/golden/actors and tests/golden/critics hold them.  Sets the parameters in place, zeroes every Adam
+        moment and the step count, and rebuilds the packed buffers; `log_ent_coef` (a float) is set where given.  ``env_steps`` and
+        ``draw`` stay.  ValueError for shapes that are not this learner's, before anything is written."""
+        def host(w, keys):
+            w = dict(w)
+            return {k: np.asarray(w[k], dtype=np.float32) for k in keys if k in w}
+
+        actor = host(actor, ACTOR_ARRAYS + LOG_STD_ARRAYS)
+        missing = [k for k in ACTOR_ARRAYS + LOG_STD_ARRAYS if k not in actor]
+        if missing:
+            raise ValueError(f"load_parameters: actor arrays missing: {missing}")
+        critics = [host(w, CRITIC_ARRAYS) for w in critics]
+        target = critics if target is None else [host(w, CRITIC_ARRAYS) for w in target]
+        if len(critics) != 2 or len(target) != 2:
+            raise ValueError("load_parameters: a twin critic has two Q-networks")
+        mine = self.critic.tensors()
+        checked = [("actor", self.actor.tensors(), actor)] + [(f"critics[{i}]", mine[i], critics[i]) for i in range(2)] + \
+                  [(f"target[{i}]", mine[i], target[i]) for i in range(2)]  # the target has the critics' shapes and no tensor of its own
+        for name, dst, src in checked:
+            for k, t in dst.items():
+                if k not in src or src[k].shape != tuple(t.shape):
+                    raise ValueError(f"load_parameters: {name}.{k} must have shape {tuple(t.shape)}, got {src[k].shape if k in src else 'nothing'}")
+        plan = [(t, src[k]) for _, dst, src in checked[:3] for k, t in dst.items()]
+        if log_ent_coef is not None and not np.isfinite(float(log_ent_coef)):
+            raise ValueError(f"load_parameters: log_ent_coef must be finite, got {log_ent_coef}")
+        dev = self.env.device
+        with torch.no_grad():
+            for t, a in plan:
+                t.copy_(torch.from_numpy(np.ascontiguousarray(a)))
+            if log_ent_coef is not None:
+                self.log_ent_coef.fill_(float(log_ent_coef))
+            if self.adam_state is not None:
+                st = self.adam_state
+                st["step"] = 0
+                for w in list(st["actor"]) + [w for pair in st["critic"] for w in pair]:
+                    for t in w.values():
+                        t.zero_()
+            if self.entropy_state is not None:
+                self.entropy_state["exp_avg"].zero_()
+                self.entropy_state["exp_avg_sq"].zero_()
+        for opt in self._optimizers().values():
+            opt.state.clear()  # torch's Adam starts again: zero moments, step 0
+        self._repack([{k: torch.from_numpy(np.ascontiguousarray(a)).to(dev) for k, a in w.items()} for w in target])
+
+    def save(self, path, replay=None, monitor=None, evaluation=None, env_state=True, extra=None):
+        """One ``.npz`` (``ur_gym_amd.checkpoint``: plain arrays and one JSON string, readable with ``allow_pickle=False``) holding
+        ``state_dict()`` and, where given, the ``state_dict`` of `replay`, `monitor` and `evaluation`, the training environment's
+        ``checkpoint_state`` (`env_state`) and `extra`, the caller's own counters as JSON scalars (tools/train_sac.py keeps its update
+        draw there).  Written to a temporary name and renamed: a job killed mid-save leaves the previous file whole."""
+        from . import checkpoint
+
+        state = dict(learner=self.state_dict(), extra=extra,
+                     replay=None if replay is None else replay.state_dict(), monitor=None if monitor is None else monitor.state_dict(),
+                     evaluation=None if evaluation is None else evaluation.state_dict(), env=self.env.checkpoint_state() if env_state else None)
+        checkpoint.write(path, state)
+
+    def load(self, path, replay=None, monitor=None, evaluation=None, env_state=True, override=()):
+        """Reads what ``save`` wrote into this learner and the same objects; returns `extra`.  A part that was saved but has no object
+        handed in, or the reverse, raises ValueError, and so does everything ``load_state_dict`` and the parts' own loads refuse -- the
+        learner's, the ring's and the environment's checks are all made before anything is written."""
+        from . import checkpoint
+
+        state = checkpoint.read(path)
+        given = dict(replay=replay, monitor=monitor, evaluation=evaluation, env=self.env if env_state else None)
+        for name, obj in given.items():
+            if (state[name] is None) != (obj is None):
+                raise ValueError(f"load: {name} is {'absent from' if state[name] is None else 'present in'} the checkpoint, "
+                                 f"and the call has {'no' if obj is None else 'an'} object for it")
+        self.check_state_dict(state["learner"], override)
+        if replay is not None:
+            replay.check_state_dict(state["replay"])
+        if env_state:
+            self.env.check_checkpoint(state["env"])
+        self.load_state_dict(state["learner"], override)
+        if env_state:
+            self.env.restore_checkpoint(state["env"])
+        for name in ("replay", "monitor", "evaluation"):
+            if given[name] is not None:
+                given[name].load_state_dict(state[name])
+        return state["extra"]
 
     def close(self):
         self._train = None

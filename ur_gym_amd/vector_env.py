@@ -1016,6 +1016,59 @@ class UR5ReachVectorEnv:
             self._refresh(None)
         self._needs_reset = False
 
+    def _config_dict(self):
+        """The configuration as JSON scalars and lists, in the struct's order: what a checkpoint compares."""
+        out = {}
+        for name, _ in _abi.Config._fields_:
+            v = getattr(self.cfg, name)
+            out[name] = v if isinstance(v, (int, float)) else [float(x) for x in v]
+        return out
+
+    def checkpoint_state(self):
+        """Everything a run needs to continue bit for bit in another environment object: EVERY bound buffer of
+        ``_abi.BUFFER_FIELDS`` on the host -- the outputs and the observation as well as ``STATE_KEYS``: a reset of UR5DynReach-v1 reads
+        the observation it finds, and the status words are sticky -- with ``_seed``, ``_needs_reset``, the env id, the env count and the
+        configuration.  Synchronises."""
+        return dict(env_id=self.env_id, num_envs=self.num_envs, config=self._config_dict(), seed=self._seed, needs_reset=bool(self._needs_reset),
+                    buffers={name: self.buf[name].detach().cpu().numpy() for name, _, _ in _abi.BUFFER_FIELDS})
+
+    def check_checkpoint(self, state):
+        """Raises ValueError unless `state` is a ``checkpoint_state`` of an environment of this id, env count and configuration, naming
+        the first difference.  Writes nothing."""
+        if state["env_id"] != self.env_id or int(state["num_envs"]) != self.num_envs:
+            raise ValueError(f"restore_checkpoint: the state is of {state['env_id']} x {state['num_envs']}, this environment is {self.env_id} x {self.num_envs}")
+        mine = self._config_dict()
+        for name, v in mine.items():
+            if name not in state["config"] or state["config"][name] != v:
+                raise ValueError(f"restore_checkpoint: config.{name} is {state['config'].get(name)!r} in the state, {v!r} here")
+        for name, ct, _ in _abi.BUFFER_FIELDS:
+            a = np.asarray(state["buffers"][name])
+            if a.dtype != np.dtype(ct) or a.shape != tuple(self.buf[name].shape):
+                raise ValueError(f"restore_checkpoint: buffers[{name!r}] must be {np.dtype(ct)} {tuple(self.buf[name].shape)}, got {a.dtype} {a.shape}")
+
+    def restore_checkpoint(self, state):
+        """Puts a ``checkpoint_state`` back into this environment (same id, env count and configuration; ValueError otherwise, before
+        anything is written).  The sampler is re-keyed with the saved seed by a full urgym_reset -- made with every env's episode id
+        set ONE BELOW the saved one, so that the episode records the library prefetches behind a reset (keyed by seed, env and episode
+        id) are those of the saved ids: the restored environment resets its finished envs inline from valid records, exactly as the
+        one the state was taken from does, and never takes the kernel fallback, whose work list is itself a bound buffer.  Then every
+        bound buffer is copied back over what that reset wrote.  The steps that follow are bit for bit those of the environment the
+        state was taken from, in every bound buffer.  (A state that holds an episode id of 0 on an environment that has been reset
+        -- ``set_state`` can make one -- has no id below it: its records are invalidated instead, urgym_invalidate_records, and it
+        continues through the fallback with the same results but for the two work-list buffers.)  ``get_state`` / ``set_state`` are
+        the teacher-forcing pair and stay as they are."""
+        self.check_checkpoint(state)
+        seed, fresh = int(state["seed"]), bool(state["needs_reset"])
+        ids = np.asarray(state["buffers"]["episode_id"])
+        if not fresh:
+            self.buf["episode_id"].copy_(torch.from_numpy(np.maximum(ids - 1, 0).astype(ids.dtype)))
+            _native.check(self.lib.urgym_reset(self._h, None, C.c_uint64(seed), self._stream()), self._h)
+        for name, _, _ in _abi.BUFFER_FIELDS:
+            self.buf[name].copy_(torch.from_numpy(np.ascontiguousarray(state["buffers"][name])))
+        if not fresh and (ids < 1).any():
+            _native.check(self.lib.urgym_invalidate_records(self._h), self._h)
+        self._seed, self._needs_reset = seed, fresh
+
     def probe_closest(self, type_a, par_a, pose_a, type_b, par_b, pose_b, threshold=5.0):
         """Unit probe of the device closest-distance routine (urgym_probe_closest): arrays of queries -> (dist, info)."""
         dev = self.device
