@@ -1219,6 +1219,96 @@ typedef struct urgym_sac_monitoring {
  * written.  No allocation, no host synchronisation; a launch failure midway as in urgym_sac_train. */
 int urgym_sac_train_monitored(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring, void* stream);
 
+/* ---- multi-step (n-step) returns (stable-baselines3 offers them for SAC as n_steps=; one collection step writes N transitions that are
+ * all one env step old, and a one-step target moves reward back through the ring one update per step).  The ring is [C][N][...]: an
+ * env's consecutive steps sit N entries apart, and the ring keeps `truncated` and the terminal next_* rows a correct walk needs.
+ * Added WITHIN ABI version 4: no struct above changed, URGYM_ABI_VERSION did not move, the new symbols (urgym_replay_sample_nstep,
+ * urgym_sac_entropy_step_nstep, urgym_sac_train_nstep) are found by lookup.  n_steps = 1 is the calls above. */
+
+#define URGYM_REPLAY_NSTEP_MAX 32
+
+typedef struct urgym_replay_nstep {
+  int32_t n_steps;     /* in [1, URGYM_REPLAY_NSTEP_MAX] */
+  int32_t reserved0;   /* must be 0 */
+  float gamma;         /* finite */
+  float reserved1;     /* must be 0 */
+  float* discount;     /* [count] required: gamma^m by repeated float32 products */
+  int32_t* steps;      /* [count] or NULL: m */
+  int64_t* last_index; /* [count] or NULL: the ring entry that next_* and the flags came from */
+} urgym_replay_nstep;
+
+/* urgym_replay_sample whose rows span up to n_steps consecutive steps of one env, in ONE gather launch on `stream`; no allocation, no
+ * host synchronisation, everything validated before the launch.  The draw is urgym_replay_sample's, word for word: the same Philox
+ * counter, the same e, and `index` bitwise the same.  For row i, with N the env count and C = capacity_steps:
+ *   p = e / N (the age of the drawn slot, 0 = the oldest), env = e % N;
+ *   L = min(n_steps, filled_steps - p): the window never runs past the newest valid slot;
+ *   entry_k = ((oldest_slot + p + k) % C) * N + env for k < L;
+ *   m = the smallest k + 1 with terminated[entry_k] | truncated[entry_k] non-zero, else L: the window never crosses an episode's end
+ *   (with auto_reset the env's next slot belongs to another episode).
+ * The return, in float32, each operation rounded on its own (ur_gym_amd/csrc/urgym_nstep.h; no product is fused into a sum):
+ *   R = reward[entry_0], g = gamma;  for k = 1 .. m - 1:  t = g * reward[entry_k];  R = R + t;  g = g * gamma;
+ *   batch.reward[i] = R, discount[i] = g (= gamma^m), steps[i] = m.
+ * observation, achieved_goal, desired_goal, action and index come from entry_0; the three next_* rows, terminated, truncated,
+ * is_success and last_index from entry_{m-1}.  At a truncation the next_* rows are therefore the ring's final_* rows and terminated
+ * is the env's own flag, 0: the target bootstraps through, as the one-step ring does.  No entry at or past age filled_steps is read.
+ * With n_steps == 1 every batch output is bitwise urgym_replay_sample's and discount[i] == gamma exactly.  A NaN reward reaches that
+ * row's R and nothing else.  A row depends on (seed, draw, i) and the ring only: not on count, not on the launch geometry.
+ * ur_gym_amd.evaluation.nstep_batch restates it.
+ * Refused (URGYM_ERR_ARG, nothing launched, nothing written): everything urgym_replay_sample refuses; nstep == NULL; n_steps outside
+ * [1, URGYM_REPLAY_NSTEP_MAX]; a non-zero reserved field; gamma not finite; discount == NULL; n_steps > 1 on a ring with
+ * truncated == NULL (an episode's end at the time limit could not be seen). */
+int urgym_replay_sample_nstep(void* handle, const urgym_replay_ring* ring, int oldest_slot, int filled_steps, uint64_t seed, uint64_t draw, int count, const urgym_replay_batch* batch, const urgym_replay_nstep* nstep, void* stream);
+
+/* urgym_sac_entropy_args with the target group of a per-row discount: reward, q_min_next, discount, next_log_prob and y_out go
+ * together (terminated only with them); everything else as in urgym_sac_entropy_args. */
+typedef struct urgym_sac_entropy_nstep_args {
+  int32_t count;              /* in [1, URGYM_SAC_TERMS_MAX_COUNT] */
+  int32_t reserved0;          /* must be 0 */
+  float target_entropy;       /* finite */
+  float scale;                /* finite; the upstream group's factor */
+  const float* log_prob;      /* [count] required */
+  float* log_ent_coef;        /* [1] required, stepped in place */
+  float* exp_avg;             /* [1] required */
+  float* exp_avg_sq;          /* [1] required */
+  float* ent_coef_out;        /* [1] required: alpha of the OLD log_ent_coef */
+  float* loss_out;            /* [1] or NULL */
+  const float* reward;        /* [count]: the multi-step return R */
+  const float* q_min_next;    /* [count]: min_i Q_i'(s', a') on the rows of entry_{m-1} */
+  const float* discount;      /* [count]: gamma^m */
+  const float* next_log_prob; /* [count] */
+  const uint8_t* terminated;  /* [count] or NULL (= none terminal) */
+  float* y_out;               /* [count]; may be reward itself */
+  float* d_log_prob_out;      /* [count] or NULL: alpha * scale */
+} urgym_sac_entropy_nstep_args;
+
+/* urgym_sac_entropy_step with another target group.  Per row m, float32, one operation per line (urgym_sac_terms.h,
+ * sac_target_row_nstep):
+ *   nd = terminated[m] ? 0 : 1;  d = discount[m] * nd;  a = d * q_min_next[m];  tv = reward[m] + a;  t = d * alpha;
+ *   e = t * next_log_prob[m];  y_out[m] = tv - e.
+ * Everything else is urgym_sac_entropy_step's: alpha = expf of the old log_ent_coef, THE ORDERED SUM in float64, the loss, the Adam
+ * element, d_log_prob_out, ONE launch of one workgroup of 1024 lanes.  With discount[m] == gamma on every row, y_out is bitwise what
+ * urgym_critic_evaluate(target, ent_coef = 0) followed by urgym_sac_entropy_step leave.  A non-finite next_log_prob[m] reaches y_out[m]
+ * alone.  ur_gym_amd.evaluation.entropy_step_nstep restates it.  Refused: what urgym_sac_entropy_step refuses, with the new group given
+ * whole or not at all. */
+int urgym_sac_entropy_step_nstep(void* handle, const urgym_sac_entropy_nstep_args* args, const urgym_adam_hyper* hp, void* stream);
+
+typedef struct urgym_sac_nstep {
+  int32_t n_steps;   /* in [2, URGYM_REPLAY_NSTEP_MAX] */
+  int32_t reserved0; /* must be 0 */
+  float* discount;   /* [count] scratch */
+  float* q_min_next; /* [count] scratch */
+} urgym_sac_nstep;
+
+/* The launches of urgym_sac_train_monitored, urgym_sac_train_evaluated or urgym_sac_train, according to which of the two arguments are
+ * NULL, with two differences in each update: the gather is urgym_replay_sample_nstep(..., {n_steps, gamma = learner->gamma, discount})
+ * and the third call is urgym_critic_evaluate(target, next rows) writing out.q_min = q_min_next with no terms, after which the entropy
+ * step is urgym_sac_entropy_step_nstep(reward = batch.reward, q_min_next, discount, next_log_prob, terminated = batch.terminated, y).
+ * Still 13 launches per update (15 above 1024 rows); learner->target_value is not written.  The schedule, the draws, the step numbers
+ * and the loss slots are those of urgym_sac_train (ur_gym_amd/csrc/urgym_sac_schedule.h).  EVERYTHING is validated before the first
+ * launch.  Refused besides what those calls refuse: nstep == NULL, n_steps outside [2, URGYM_REPLAY_NSTEP_MAX] (n_steps == 1 is the
+ * calls above), reserved0 != 0, a NULL scratch pointer, a ring without truncated -- these also where the call holds no update. */
+int urgym_sac_train_nstep(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_nstep* nstep, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream);
+
 /* ---- weights back to the device tensors (a checkpoint: the reference's train.py:31-36 continues a saved run, and the TARGET critic
  * exists only as a packed buffer, blended in place by urgym_critic_load(tau < 1) and urgym_critic_adam_step(target)).  The packing
  * map of ur_gym_amd/csrc/urgym_pack_map.h run the other way, on the device: every element of every destination tensor -- DEVICE

@@ -1052,6 +1052,169 @@ def native_mode(args):
             f.write(line + "\n")
 
 
+def nstep_mode(args):
+    """--nstep: the gather of multi-step returns (urgym_replay_sample_nstep) on a filled ring, in alternating windows in one process:
+    at n_steps = 1 against the one-step gather (urgym_replay_sample: the same work but one store per row), at n_steps = 3 and 5 against
+    a torch composition of the same batch (index arithmetic, flag gathers, index_select per field); then SACLearner.update and
+    SACLearner.train at batch 256, H = 256, with n_steps = 1 and 3."""
+    import torch
+
+    from ur_gym_amd import make_vec
+    from ur_gym_amd.evaluation import DeviceActor, DeviceReplay
+    from ur_gym_amd.training import SACLearner
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_policy_rollout.py measures on a GPU; none is visible")
+    dev, n, cap, kind, gamma = "cuda:0", args.num_envs, args.capacity, ACTOR_NPZ[args.env], 0.95
+    w = dict(np.load(os.path.join(ROOT, "tests", "golden", "actors", f"actor_{kind}.npz")))
+    w.update(np.load(os.path.join(ROOT, "tests", "golden", "actors", f"log_std_{kind}.npz")))
+    env = make_vec(args.env, num_envs=n, device=dev, seed=0, auto_reset=True)
+    env.reset(seed=0)
+    actor = DeviceActor(w, env)
+    replay = DeviceReplay(env, cap)
+    sync = lambda: torch.cuda.synchronize(env.device)  # noqa: E731
+    done = 0
+    while replay.filled < cap:  # a filled ring, from the sampled policy
+        steps = min(64, cap - replay.filled)
+        replay.collect(actor, steps, sample=dict(mode="gaussian", seed=1, first_draw=done))
+        done += steps
+    sync()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def window(fn, reps):
+        sync()
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        sync()
+        return e0.elapsed_time(e1) * 1e3 / reps
+
+    def alternate(kinds):
+        for fn in kinds.values():
+            for _ in range(10):
+                fn()
+        wins = {k: [] for k in kinds}
+        for _ in range(args.windows):
+            for name, fn in kinds.items():
+                wins[name].append(window(fn, args.launches))
+        return wins, {k: float(np.median(v)) for k, v in wins.items()}
+
+    size, oldest, filled = replay.filled * n, replay.oldest_slot, replay.filled
+    flat = {name: t.reshape((cap * n,) + tuple(t.shape[2:])) for name, t in replay.ring.items()}
+    first_fields = ("observation", "achieved_goal", "desired_goal", "action")
+    last_fields = ("next_observation", "next_achieved_goal", "next_desired_goal", "terminated", "truncated", "is_success")
+    gather = {}
+    for B in (256, 65536):
+        out = {name: torch.empty((B,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev) for name, t in flat.items()}
+        one = dict(out, index=torch.empty((B,), dtype=torch.int64, device=dev))
+        multi = dict(one, discount=torch.empty((B,), dtype=torch.float32, device=dev), steps=torch.empty((B,), dtype=torch.int32, device=dev),
+                     last_index=torch.empty((B,), dtype=torch.int64, device=dev))
+        tick = [0]
+
+        def one_step():
+            tick[0] += 1
+            replay.sample_into(one, 3, tick[0])
+
+        def nstep(steps, into=multi):
+            def fn():
+                tick[0] += 1
+                replay.sample_into(into, 3, tick[0], n_steps=steps, gamma=gamma)
+            return fn
+
+        def torch_nstep(steps):
+            k = torch.arange(steps, device=dev)
+            powers = torch.tensor([gamma ** i for i in range(steps + 1)], dtype=torch.float32, device=dev)
+
+            def fn():
+                e = torch.randint(0, size, (B,), device=dev)
+                p, envi = e // n, e % n
+                L = torch.clamp(filled - p, max=steps)
+                entries = ((oldest + p[:, None] + k[None, :]) % cap) * n + envi[:, None]
+                valid = k[None, :] < L[:, None]
+                entries = torch.where(valid, entries, entries[:, :1])
+                ends = ((flat["terminated"][entries] | flat["truncated"][entries]) != 0) & valid
+                m = torch.minimum(torch.where(ends.any(1), ends.int().argmax(1) + 1, L), L)
+                taken = k[None, :] < m[:, None]
+                torch.sum(torch.where(taken, flat["reward"][entries], 0.0) * powers[None, :steps], 1, out=out["reward"])
+                multi["discount"].copy_(powers[m])
+                multi["steps"].copy_(m)
+                last = entries.gather(1, (m - 1)[:, None])[:, 0]
+                multi["index"].copy_(entries[:, 0])
+                multi["last_index"].copy_(last)
+                for name in first_fields:
+                    torch.index_select(flat[name], 0, entries[:, 0], out=out[name])
+                for name in last_fields:
+                    torch.index_select(flat[name], 0, last, out=out[name])
+            return fn
+
+        # the same outputs plus the one required array, discount: the same work plus one store per row
+        wins, med = alternate({"one_step_gather": one_step, "nstep_gather_1": nstep(1, dict(one, discount=multi["discount"]))})
+        spread = float(max(wins["one_step_gather"]) - min(wins["one_step_gather"]))
+        entry = {"n_steps_1": {"us_windows": {k: [round(x, 3) for x in v] for k, v in wins.items()}, "us_median": med, "one_step_us_spread": spread,
+                               "difference_us": med["nstep_gather_1"] - med["one_step_gather"],
+                               "within_the_one_step_spread": med["nstep_gather_1"] <= med["one_step_gather"] + spread}}
+        for steps in (3, 5):
+            wins, med = alternate({"device": nstep(steps), "torch": torch_nstep(steps)})
+            entry[f"n_steps_{steps}"] = {"us_windows": {k: [round(x, 3) for x in v] for k, v in wins.items()}, "us_median": med,
+                                         "not_slower_than_torch": med["device"] <= med["torch"], "speedup_over_torch": med["torch"] / med["device"]}
+        gather[str(B)] = entry
+        del out, one, multi
+    actor.close()
+
+    # the learner: one update and one train window at batch 256, H = 256
+    options = dict(device_action_gradient=True, device_critic_gradient=True, device_actor_gradient=True, device_optimizer=True, device_entropy=True)
+    learners = {}
+    for label, steps in (("n_steps_1", 1), ("n_steps_3", 3)):
+        learners[label] = (SACLearner(env, seed=0, batch_size=256, hidden_width=256, learning_starts=0, n_steps=steps, **options), [0])
+
+    def updates(label, native):
+        learner, draw = learners[label]
+
+        def fn():
+            if native:
+                learner.train(replay, 1, 0, args.launches, seed=1, first_draw=draw[0] + 1)
+                draw[0] += args.launches
+            else:
+                for _ in range(args.launches):
+                    draw[0] += 1
+                    learner.update(replay, 1, draw[0])
+        return fn
+
+    def host_window(fn):
+        sync()
+        t0 = time.perf_counter()
+        fn()
+        sync()
+        return (time.perf_counter() - t0) * 1e6 / args.launches
+
+    learner_result = {}
+    for route, native in (("update", False), ("train", True)):
+        fns = {label: updates(label, native) for label in learners}
+        for fn in fns.values():
+            fn()
+        wins = {label: [] for label in fns}
+        for _ in range(args.windows):
+            for label, fn in fns.items():
+                wins[label].append(host_window(fn))
+        med = {k: float(np.median(v)) for k, v in wins.items()}
+        learner_result[route] = {"us_per_update_windows": {k: [round(x, 2) for x in v] for k, v in wins.items()}, "us_per_update_median": med,
+                                 "n_steps_1_us_spread": float(max(wins["n_steps_1"]) - min(wins["n_steps_1"])),
+                                 "n_steps_3_minus_n_steps_1_us": med["n_steps_3"] - med["n_steps_1"]}
+    for learner, _ in learners.values():
+        learner.close()
+    result = {"tool": "bench_policy_rollout --nstep", "env": args.env, "num_envs": n, "capacity_steps": cap, "windows": args.windows,
+              "launches_per_window": args.launches, "gamma": gamma, "device": torch.cuda.get_device_name(0), "gather": gather,
+              "learner": dict(learner_result, batch=256, hidden_width=256)}
+    env.close()
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
 def evaluate_mode(args):
     """--evaluate: the evaluation inside the training call.  (1) ONE evaluation of 1024 envs x 100 steps ending in
     a synchronise: DeviceEvaluation.evaluate + results against the route before it, load_parameters + reset(seed) +
@@ -1251,8 +1414,11 @@ def main():
     ap.add_argument("--evaluate", action="store_true", help="measure one evaluation (DeviceEvaluation.evaluate) against load_parameters + reset + run_closed_loop_device, and a training run with evaluations as one call against one call per interval plus the Python evaluation")
     ap.add_argument("--monitor", action="store_true", help="measure SACLearner.train with monitor=, log_every=10 against the same call without a monitor (see above)")
     ap.add_argument("--monitored-only", action="store_true", help="--monitor: run only the monitored call, --windows times (for a kernel trace)")
+    ap.add_argument("--nstep", action="store_true", help="measure the gather of multi-step returns against the one-step gather and a torch composition, and the learner at n_steps 1 and 3")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.nstep:
+        return nstep_mode(args)
     if args.monitor:
         return monitor_mode(args)
     if args.evaluate:

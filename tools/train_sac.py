@@ -57,6 +57,9 @@ def main():
     ap.add_argument("--device-entropy", action="store_true",
                     help="step the entropy coefficient and form its uses and the three loss values with two HIP launches: no torch operation "
                          "is left in an update but allocations and views (needs --device-optimizer)")
+    ap.add_argument("--n-steps", type=int, default=1,
+                    help="multi-step returns: a target spans up to this many consecutive steps of an env and stops at an episode's end "
+                         "(SB3's n_steps; above 1 needs --device-entropy)")
     ap.add_argument("--native", action="store_true",
                     help="run the whole loop, evaluations included, as ONE native call (SACLearner.train): no Python between the launches "
                          "(needs --device-entropy)")
@@ -97,7 +100,7 @@ def main():
     learner = SACLearner(env, seed=args.seed, hidden_width=args.hidden_width, batch_size=args.batch_size,
                          device_action_gradient=args.device_action_gradient, device_critic_gradient=args.device_critic_gradient,
                          device_actor_gradient=args.device_actor_gradient, device_optimizer=args.device_optimizer,
-                         device_entropy=args.device_entropy)
+                         device_entropy=args.device_entropy, n_steps=args.n_steps)
     eval_actor = DeviceActor(host_arrays(learner.actor.tensors()), test_env)  # actors belong to the environment they were made for
     replay = DeviceReplay(env, args.capacity)
     updates, t0 = 0, time.perf_counter()

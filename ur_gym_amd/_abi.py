@@ -424,6 +424,30 @@ class SacMonitoring(C.Structure):
                 ("log_every", C.c_int32), ("clear", C.c_int32), ("first_iteration", C.c_int64), ("reserved0", C.c_int64)]
 
 
+REPLAY_NSTEP_MAX = 32  # URGYM_REPLAY_NSTEP_MAX: the longest window of urgym_replay_sample_nstep
+
+
+class ReplayNstep(C.Structure):
+    """urgym_replay_nstep: the window and gamma of urgym_replay_sample_nstep and its three extra outputs (discount required)."""
+    _fields_ = [("n_steps", C.c_int32), ("reserved0", C.c_int32), ("gamma", C.c_float), ("reserved1", C.c_float),
+                ("discount", C.POINTER(C.c_float)), ("steps", C.POINTER(C.c_int32)), ("last_index", C.POINTER(C.c_int64))]
+
+
+class SacEntropyNstepArgs(C.Structure):
+    """urgym_sac_entropy_nstep_args: SacEntropyArgs with the target group of a per-row discount (reward, q_min_next, discount)."""
+    _fields_ = [("count", C.c_int32), ("reserved0", C.c_int32), ("target_entropy", C.c_float), ("scale", C.c_float),
+                ("log_prob", C.POINTER(C.c_float)), ("log_ent_coef", C.POINTER(C.c_float)), ("exp_avg", C.POINTER(C.c_float)),
+                ("exp_avg_sq", C.POINTER(C.c_float)), ("ent_coef_out", C.POINTER(C.c_float)), ("loss_out", C.POINTER(C.c_float)),
+                ("reward", C.POINTER(C.c_float)), ("q_min_next", C.POINTER(C.c_float)), ("discount", C.POINTER(C.c_float)),
+                ("next_log_prob", C.POINTER(C.c_float)), ("terminated", C.POINTER(C.c_uint8)), ("y_out", C.POINTER(C.c_float)),
+                ("d_log_prob_out", C.POINTER(C.c_float))]
+
+
+class SacNstep(C.Structure):
+    """urgym_sac_nstep: the window of urgym_sac_train_nstep and its two [count] scratch arrays."""
+    _fields_ = [("n_steps", C.c_int32), ("reserved0", C.c_int32), ("discount", C.POINTER(C.c_float)), ("q_min_next", C.POINTER(C.c_float))]
+
+
 # Every symbol include/urgym.h declares (tests check that the built library exports each of them).
 EXPORTED_SYMBOLS = [
     "urgym_abi_version",
@@ -470,6 +494,9 @@ EXPORTED_SYMBOLS = [
     "urgym_monitor_fold",
     "urgym_monitor_stats",
     "urgym_sac_train_monitored",
+    "urgym_replay_sample_nstep",
+    "urgym_sac_entropy_step_nstep",
+    "urgym_sac_train_nstep",
     "urgym_actor_read_packed",
     "urgym_critic_read_packed",
     "urgym_refresh",

@@ -1,5 +1,5 @@
 // urgym_policy_abi.hip — the learner's half of the C-ABI of include/urgym.h: actors (create / forward / sample / rollouts), the replay
-// ring, the weight reloads and their inverse (urgym_actor_unpack, urgym_critic_unpack), the twin critic and its two gradients, the actor's parameter gradients, the Adam steps, SAC's entropy step and loss terms, the training loop that composes them in one call (urgym_sac_train; its index arithmetic is urgym_sac_schedule.h), the evaluation inside that call (urgym_eval_stats, urgym_actor_snapshot, urgym_policy_evaluate, urgym_sac_train_evaluated; urgym_eval.h, urgym_eval_schedule.h), and the training-episode statistics inside it (urgym_monitor_fold, urgym_monitor_stats, urgym_sac_train_monitored; urgym_monitor.h).  Host code only: every check is made here, before the first launch,
+// ring, the weight reloads and their inverse (urgym_actor_unpack, urgym_critic_unpack), the twin critic and its two gradients, the actor's parameter gradients, the Adam steps, SAC's entropy step and loss terms, the training loop that composes them in one call (urgym_sac_train; its index arithmetic is urgym_sac_schedule.h), the evaluation inside that call (urgym_eval_stats, urgym_actor_snapshot, urgym_policy_evaluate, urgym_sac_train_evaluated; urgym_eval.h, urgym_eval_schedule.h), and the training-episode statistics inside it (urgym_monitor_fold, urgym_monitor_stats, urgym_sac_train_monitored; urgym_monitor.h), and the multi-step returns (urgym_replay_sample_nstep, urgym_sac_entropy_step_nstep, urgym_sac_train_nstep; urgym_nstep.h).  Host code only: every check is made here, before the first launch,
 // and every launch goes through urgym_actor.h, urgym_critic.h, urgym_replay.h, urgym_weights.h, urgym_adam.h, urgym_sac_terms.h, urgym_eval.h and urgym_monitor.h, or through do_step of urgym_hip.hip
 // (urgym_handle.h).  No kernel lives in this unit, so adding a check here leaves the step kernels' object file alone.
 #include <hip/hip_runtime.h>
@@ -16,6 +16,7 @@
 #include "urgym_pack_map.h"
 #include "urgym_weights.h"
 #include "urgym_replay.h"
+#include "urgym_nstep.h"
 #include "urgym_adam.h"
 #include "urgym_sac_terms.h"
 #include "urgym_sac_schedule.h"
@@ -469,6 +470,49 @@ int check_replay_sample(Handle* h, const urgym_replay_ring* ring, int oldest_slo
   return URGYM_OK;
 }
 
+// urgym_replay_sample_nstep: check_replay_sample's refusals first, then the window's
+int check_replay_sample_nstep(Handle* h, const urgym_replay_ring* ring, int oldest_slot, int filled_steps, uint64_t seed, uint64_t draw, int count,
+                              const urgym_replay_batch* batch, const urgym_replay_nstep* nstep, const char* who, ReplayGatherNstep* out) {
+  static_assert(URGYM_REPLAY_NSTEP_MAX == NSTEP_MAX, "include/urgym.h");
+  if (int rc = check_replay_sample(h, ring, oldest_slot, filled_steps, seed, draw, count, batch, who, &out->g)) return rc;
+  if (!nstep) return fail_in(h, URGYM_ERR_ARG, who, "null nstep");
+  const urgym_replay_nstep& n = *nstep;
+  if (n.n_steps < 1 || n.n_steps > NSTEP_MAX) return fail_in(h, URGYM_ERR_ARG, who, "n_steps must be in [1, URGYM_REPLAY_NSTEP_MAX] (32)");
+  if (n.reserved0 != 0 || n.reserved1 != 0.0f) return fail_in(h, URGYM_ERR_ARG, who, "urgym_replay_nstep.reserved0 and reserved1 must be 0");
+  if (!(fabsf(n.gamma) < INFINITY)) return fail_in(h, URGYM_ERR_ARG, who, "gamma must be finite");  // refuses NaN too
+  if (!n.discount) return fail_in(h, URGYM_ERR_ARG, who, "null discount");
+  if (n.n_steps > 1 && !ring->truncated)
+    return fail_in(h, URGYM_ERR_ARG, who, "n_steps > 1 on a ring that keeps no truncated (an episode's end at the time limit could not be seen)");
+  out->n_steps = n.n_steps, out->filled_steps = filled_steps, out->gamma = n.gamma;
+  out->discount = n.discount, out->steps = n.steps, out->last_index = n.last_index;
+  return URGYM_OK;
+}
+
+// urgym_sac_entropy_step_nstep: check_entropy_step's refusals on the other target group
+int check_entropy_step_nstep(Handle* h, const urgym_sac_entropy_nstep_args* args, const urgym_adam_hyper* hp, const char* who, SacEntropyNstepCall* out) {
+  if (!args) return fail_in(h, URGYM_ERR_ARG, who, "null args");
+  const urgym_sac_entropy_nstep_args& a = *args;
+  if (a.reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_entropy_nstep_args.reserved0 must be 0");
+  if (a.count < 1 || a.count > SAC_TERMS_MAX_COUNT) return fail_in(h, URGYM_ERR_ARG, who, "count must be in [1, URGYM_SAC_TERMS_MAX_COUNT] (65536)");
+  if (!a.log_prob || !a.log_ent_coef || !a.exp_avg || !a.exp_avg_sq || !a.ent_coef_out)
+    return fail_in(h, URGYM_ERR_ARG, who, "a required pointer is null (log_prob, log_ent_coef, exp_avg, exp_avg_sq, ent_coef_out)");
+  if (!(fabsf(a.target_entropy) < INFINITY)) return fail_in(h, URGYM_ERR_ARG, who, "target_entropy must be finite");  // refuses NaN too
+  if (!(fabsf(a.scale) < INFINITY)) return fail_in(h, URGYM_ERR_ARG, who, "scale must be finite");
+  const int given = (a.reward != nullptr) + (a.q_min_next != nullptr) + (a.discount != nullptr) + (a.next_log_prob != nullptr) + (a.y_out != nullptr);
+  if ((given != 0 && given != 5) || (given == 0 && a.terminated))
+    return fail_in(h, URGYM_ERR_ARG, who,
+                   "the target group is half given: reward, q_min_next, discount, next_log_prob and y_out go together (terminated only with them)");
+  if (const char* what = adam_hyper_refusal(hp)) return fail_in(h, URGYM_ERR_ARG, who, what);
+  SacEntropyNstepCall& c = *out;
+  c.count = a.count, c.target_entropy = a.target_entropy, c.scale = a.scale;
+  c.log_prob = a.log_prob, c.log_ent_coef = a.log_ent_coef, c.exp_avg = a.exp_avg, c.exp_avg_sq = a.exp_avg_sq;
+  c.ent_coef_out = a.ent_coef_out, c.loss_out = a.loss_out;
+  c.reward = a.reward, c.q_min_next = a.q_min_next, c.discount = a.discount, c.next_log_prob = a.next_log_prob;
+  c.terminated = a.terminated, c.y_out = a.y_out, c.d_log_prob_out = a.d_log_prob_out;
+  c.c = adam_coef(*hp);
+  return URGYM_OK;
+}
+
 int check_critic_evaluate(Handle* h, void* critic, const urgym_critic_rows* rows, int count, const urgym_critic_terms* terms, const urgym_critic_out* out,
                           const char* who, Critic** critic_out, CriticCall* call_out) {
   if (int rc = enter_bound(h)) return rc;
@@ -609,6 +653,16 @@ int urgym_sac_entropy_step(void* handle, const urgym_sac_entropy_args* args, con
   if (int rc = check_entropy_step(h, args, hp, "urgym_sac_entropy_step", &c)) return rc;
   HIP_TRY(h, hipSetDevice(h->device));
   sac_entropy_launch(c, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_sac_entropy_step_nstep(void* handle, const urgym_sac_entropy_nstep_args* args, const urgym_adam_hyper* hp, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  SacEntropyNstepCall c;
+  if (int rc = check_entropy_step_nstep(h, args, hp, "urgym_sac_entropy_step_nstep", &c)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  sac_entropy_nstep_launch(c, (hipStream_t)stream);
   return launched(h);
 }
 
@@ -852,6 +906,16 @@ int urgym_replay_sample(void* handle, const urgym_replay_ring* ring, int oldest_
   return launched(h);
 }
 
+int urgym_replay_sample_nstep(void* handle, const urgym_replay_ring* ring, int oldest_slot, int filled_steps, uint64_t seed, uint64_t draw, int count, const urgym_replay_batch* batch, const urgym_replay_nstep* nstep, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  ReplayGatherNstep g;
+  if (int rc = check_replay_sample_nstep(h, ring, oldest_slot, filled_steps, seed, draw, count, batch, nstep, "urgym_replay_sample_nstep", &g)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  replay_gather_nstep_launch(g, (hipStream_t)stream);
+  return launched(h);
+}
+
 int urgym_critic_create(void* handle, const urgym_critic_desc* desc, void** critic) {
   Handle* h = (Handle*)handle;
   if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
@@ -956,7 +1020,9 @@ struct TrainHooks {
   void* ctx;
 };
 
-int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, void* stream, const TrainHooks* hooks);
+// `nstep`: null = the one-step update; given (urgym_sac_train_nstep) = the update whose gather, third call and entropy step are the
+// multi-step ones
+int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, void* stream, const TrainHooks* hooks, const urgym_sac_nstep* nstep = nullptr);
 
 }  // namespace
 
@@ -968,7 +1034,7 @@ int urgym_sac_train(void* handle, const urgym_sac_learner* learner, const urgym_
 
 namespace {
 
-int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, void* stream, const TrainHooks* hooks) {
+int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, void* stream, const TrainHooks* hooks, const urgym_sac_nstep* nstep) {
   Handle* h = (Handle*)handle;
   if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
   if (!learner) return fail_in(h, URGYM_ERR_ARG, who, "null learner");
@@ -993,6 +1059,13 @@ int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learn
   if (S.capacity_steps != L.ring.capacity_steps) return fail_in(h, URGYM_ERR_ARG, who, "schedule->capacity_steps is not ring.capacity_steps");
   for (const LearnerPointer& r : losses)  // zero slots need no array
     if (!r.p && sac_schedule_updates(S) > 0) return failf(h, URGYM_ERR_ARG, "%s: urgym_sac_learner.%s is null", who, r.name);
+  if (nstep) {  // the window's own refusals, whether or not the call holds an update
+    if (nstep->n_steps < 2 || nstep->n_steps > NSTEP_MAX)
+      return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_nstep.n_steps must be in [2, URGYM_REPLAY_NSTEP_MAX] (n_steps == 1 is urgym_sac_train and its kin)");
+    if (nstep->reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_nstep.reserved0 must be 0");
+    if (!nstep->discount || !nstep->q_min_next) return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_nstep.discount or q_min_next is null");
+    if (!L.ring.truncated) return fail_in(h, URGYM_ERR_ARG, who, "the ring keeps no truncated (an episode's end at the time limit could not be seen)");
+  }
 
   // ---- the checking halves, with the numbers of the first collection and the first update
   const int M = L.count, K = S.steps_per_iteration, G = S.updates_per_iteration;
@@ -1030,8 +1103,15 @@ int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learn
   const SacUpdate first = sac_schedule_update(S, 0);
   urgym_adam_hyper hp{L.lr, L.beta1, L.beta2, L.eps, first.adam_step, 0};
 
-  ReplayGather gather;
-  if (int rc = check_replay_sample(h, &L.ring, view.oldest_slot, view.filled_steps, L.update_seed, first.gather_draw, M, &L.batch, who, &gather)) return rc;
+  ReplayGatherNstep gather_nstep;
+  ReplayGather& gather = gather_nstep.g;
+  if (nstep) {
+    const urgym_replay_nstep window{nstep->n_steps, 0, L.gamma, 0.0f, nstep->discount, nullptr, nullptr};
+    if (int rc = check_replay_sample_nstep(h, &L.ring, view.oldest_slot, view.filled_steps, L.update_seed, first.gather_draw, M, &L.batch, &window, who, &gather_nstep))
+      return rc;
+  } else if (int rc = check_replay_sample(h, &L.ring, view.oldest_slot, view.filled_steps, L.update_seed, first.gather_draw, M, &L.batch, who, &gather)) {
+    return rc;
+  }
   const urgym_critic_rows next_rows{L.batch.next_observation, L.batch.next_achieved_goal, L.batch.next_desired_goal, L.next_actions};
   const urgym_critic_rows batch_rows{L.batch.observation, L.batch.achieved_goal, L.batch.desired_goal, L.batch.action};
   const urgym_critic_rows policy_rows{L.batch.observation, L.batch.achieved_goal, L.batch.desired_goal, L.action_pi};
@@ -1039,10 +1119,10 @@ int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learn
   SampleRows next_sample, policy_sample;
   if (int rc = check_sample_rows(h, L.actor, &how, &next_rows, M, L.next_actions, L.next_log_prob, who, &next_sample)) return rc;
   const urgym_critic_terms terms{L.batch.reward, L.batch.terminated, L.next_log_prob, L.gamma, 0.0f};
-  const urgym_critic_out target_out{nullptr, nullptr, L.target_value};
+  const urgym_critic_out target_out{nullptr, nstep ? nstep->q_min_next : nullptr, nstep ? nullptr : L.target_value};
   Critic *target = nullptr, *online = nullptr, *online_grad = nullptr;
   CriticCall bootstrap;
-  if (int rc = check_critic_evaluate(h, L.target, &next_rows, M, &terms, &target_out, who, &target, &bootstrap)) return rc;
+  if (int rc = check_critic_evaluate(h, L.target, &next_rows, M, nstep ? nullptr : &terms, &target_out, who, &target, &bootstrap)) return rc;
   how.first_draw = first.policy_draw;
   if (int rc = check_sample_rows(h, L.actor, &how, &batch_rows, M, L.action_pi, L.log_prob, who, &policy_sample)) return rc;
   urgym_sac_entropy_args ea;
@@ -1053,7 +1133,19 @@ int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learn
   ea.target_in = L.target_value, ea.next_log_prob = L.next_log_prob, ea.terminated = L.batch.terminated, ea.y_out = L.y;
   ea.d_log_prob_out = L.d_log_prob;
   SacEntropyCall entropy;
-  if (int rc = check_entropy_step(h, &ea, &hp, who, &entropy)) return rc;
+  SacEntropyNstepCall entropy_nstep;
+  if (nstep) {
+    urgym_sac_entropy_nstep_args na;
+    memset(&na, 0, sizeof(na));
+    na.count = M, na.target_entropy = L.target_entropy, na.scale = scale;
+    na.log_prob = L.log_prob, na.log_ent_coef = L.log_ent_coef, na.exp_avg = L.exp_avg, na.exp_avg_sq = L.exp_avg_sq;
+    na.ent_coef_out = L.ent_coef, na.loss_out = L.ent_coef_loss;
+    na.reward = L.batch.reward, na.q_min_next = nstep->q_min_next, na.discount = nstep->discount, na.next_log_prob = L.next_log_prob;
+    na.terminated = L.batch.terminated, na.y_out = L.y, na.d_log_prob_out = L.d_log_prob;
+    if (int rc = check_entropy_step_nstep(h, &na, &hp, who, &entropy_nstep)) return rc;
+  } else if (int rc = check_entropy_step(h, &ea, &hp, who, &entropy)) {
+    return rc;
+  }
   urgym_critic_param_grads cg;
   for (int net = 0; net < 2; net++) {
     const urgym_q_network_dev& g = L.critic_adam.grad[net];  // the tensors the step reads are the ones the gradient call writes
@@ -1108,11 +1200,15 @@ int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learn
       continue;
     }
     gather.oldest_slot = it.oldest_slot, gather.size = (uint64_t)it.filled_steps * (uint64_t)h->cfg.num_envs;
+    gather_nstep.filled_steps = it.filled_steps;
     for (int g = 0; g < G; g++, u++) {
       const SacUpdate up = sac_schedule_update(S, u);
       const AdamCoef coef = adam_coefficients(L.lr, L.beta1, L.beta2, L.eps, up.adam_step);  // urgym_adam_coefficients' own function
       gather.draw = up.gather_draw;
-      replay_gather_launch(gather, s);
+      if (nstep)
+        replay_gather_nstep_launch(gather_nstep, s);
+      else
+        replay_gather_launch(gather, s);
       if (int rc = train_stage(h, who, i, "replay_sample")) return rc;
       next_sample.smp.draw = up.gather_draw;
       policy_launch(next_sample.a, next_sample.env, next_sample.actions, nullptr, next_sample.smp, s);
@@ -1122,8 +1218,13 @@ int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learn
       policy_sample.smp.draw = up.policy_draw;
       policy_launch(policy_sample.a, policy_sample.env, policy_sample.actions, nullptr, policy_sample.smp, s);
       if (int rc = train_stage(h, who, i, "actor_sample_rows (batch rows)")) return rc;
-      entropy.c = coef, entropy.loss_out = L.ent_coef_loss + up.loss_slot;
-      sac_entropy_launch(entropy, s);
+      if (nstep) {
+        entropy_nstep.c = coef, entropy_nstep.loss_out = L.ent_coef_loss + up.loss_slot;
+        sac_entropy_nstep_launch(entropy_nstep, s);
+      } else {
+        entropy.c = coef, entropy.loss_out = L.ent_coef_loss + up.loss_slot;
+        sac_entropy_launch(entropy, s);
+      }
       if (int rc = train_stage(h, who, i, "sac_entropy_step")) return rc;
       critic_backward_launch(online, critic_backward, s);
       if (int rc = train_stage(h, who, i, "critic_parameter_gradients")) return rc;
@@ -1376,6 +1477,7 @@ struct TrainMonitoring {
   MonitorStatsCall stats;  // record and iteration move per record
   int64_t done;            // records launched so far
   TrainEvaluation* evaluation;  // null = none
+  const char* who;  // the entry point that runs them: urgym_sac_train_monitored, or urgym_sac_train_nstep
 };
 
 const char* const TRAIN_MONITORED = "urgym_sac_train_monitored";
@@ -1383,7 +1485,7 @@ const char* const TRAIN_MONITORED = "urgym_sac_train_monitored";
 // runs after every check of the training body (so the learner and the schedule are sound) and before its first launch
 int train_monitoring_check(void* ctx) {
   TrainMonitoring& t = *(TrainMonitoring*)ctx;
-  const char* who = TRAIN_MONITORED;
+  const char* who = t.who;
   Handle* h = t.h;
   const urgym_sac_monitoring& M = *t.monitoring;
   const urgym_sac_schedule& S = *t.schedule;
@@ -1408,14 +1510,14 @@ int train_monitoring_after(void* ctx, int i) {
   if (S.steps_per_iteration > 0) {
     t.fold.first_slot = sac_schedule_iteration(S, i).collect_first_slot;
     monitor_fold_launch(t.fold, t.s);
-    if (int rc = train_stage(t.h, TRAIN_MONITORED, i, "monitor_fold")) return rc;
+    if (int rc = train_stage(t.h, t.who, i, "monitor_fold")) return rc;
   }
   if (monitor_record_follows(M.first_iteration, M.log_every, i)) {
     t.stats.record = M.records + M.first_record + t.done;
     t.stats.iteration = M.first_iteration + i + 1;
     t.done++;
     monitor_stats_launch(t.stats, t.s);
-    if (int rc = train_stage(t.h, TRAIN_MONITORED, i, "monitor_stats")) return rc;
+    if (int rc = train_stage(t.h, t.who, i, "monitor_stats")) return rc;
   }
   if (t.evaluation) return train_evaluation_after(t.evaluation, i);
   return URGYM_OK;
@@ -1493,9 +1595,30 @@ int urgym_sac_train_monitored(void* handle, const urgym_sac_learner* learner, co
   e.h = h, e.learner = learner, e.schedule = schedule, e.evaluation = evaluation_or_NULL, e.s = (hipStream_t)stream, e.done = 0, e.who = TRAIN_MONITORED;
   TrainMonitoring t;
   t.h = h, t.learner = learner, t.schedule = schedule, t.monitoring = monitoring, t.s = (hipStream_t)stream, t.done = 0;
-  t.evaluation = evaluation_or_NULL ? &e : nullptr;
+  t.evaluation = evaluation_or_NULL ? &e : nullptr, t.who = TRAIN_MONITORED;
   const TrainHooks hooks{train_monitoring_check, train_monitoring_after, &t};
   return sac_train_body(TRAIN_MONITORED, handle, learner, schedule, stream, &hooks);
+}
+
+int urgym_sac_train_nstep(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_nstep* nstep, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream) {
+  const char* who = "urgym_sac_train_nstep";
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (!nstep) return fail_in(h, URGYM_ERR_ARG, who, "null nstep");
+  TrainEvaluation e;
+  e.h = h, e.learner = learner, e.schedule = schedule, e.evaluation = evaluation_or_NULL, e.s = (hipStream_t)stream, e.done = 0, e.who = who;
+  TrainMonitoring t;
+  t.h = h, t.learner = learner, t.schedule = schedule, t.monitoring = monitoring_or_NULL, t.s = (hipStream_t)stream, t.done = 0;
+  t.evaluation = evaluation_or_NULL ? &e : nullptr, t.who = who;
+  if (monitoring_or_NULL) {
+    const TrainHooks hooks{train_monitoring_check, train_monitoring_after, &t};
+    return sac_train_body(who, handle, learner, schedule, stream, &hooks, nstep);
+  }
+  if (evaluation_or_NULL) {
+    const TrainHooks hooks{train_evaluation_check, train_evaluation_after, &e};
+    return sac_train_body(who, handle, learner, schedule, stream, &hooks, nstep);
+  }
+  return sac_train_body(who, handle, learner, schedule, stream, nullptr, nstep);
 }
 
 }  // extern "C"

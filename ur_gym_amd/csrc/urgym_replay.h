@@ -38,4 +38,17 @@ struct ReplayGather {
 // ONE launch on `s`
 void replay_gather_launch(const ReplayGather& p, hipStream_t s);
 
+// One minibatch of multi-step returns (urgym_replay_sample_nstep): the gather above plus the window of urgym_nstep.h, validated
+struct ReplayGatherNstep {
+  ReplayGather g;
+  int n_steps, filled_steps;  // g.size = filled_steps * g.N
+  float gamma;
+  float* discount;      // [count]
+  int32_t* steps;       // [count] or null
+  int64_t* last_index;  // [count] or null
+};
+
+// ONE launch on `s`
+void replay_gather_nstep_launch(const ReplayGatherNstep& p, hipStream_t s);
+
 }  // namespace urgym

@@ -24,6 +24,19 @@ URGYM_HD inline float sac_target_row(float target, float next_log_prob, bool ter
   return target - e;
 }
 
+// The same y from a per-row discount (urgym_sac_entropy_step_nstep: discount = gamma^m of a multi-step return) and the bootstrap
+// value itself: y = (reward + (discount * nd) * q_min_next) - ((discount * nd) * alpha) * next_log_prob.  With discount == gamma this is
+// urgym_critic_evaluate's target at ent_coef = 0 followed by sac_target_row, operation for operation.
+URGYM_HD inline float sac_target_row_nstep(float reward, float q_min_next, float discount, float next_log_prob, bool terminal, float alpha) {
+  const float nd = terminal ? 0.0f : 1.0f;
+  const float d = discount * nd;
+  const float a = d * q_min_next;
+  const float tv = reward + a;
+  const float t = d * alpha;
+  const float e = t * next_log_prob;
+  return tv - e;
+}
+
 // the term of the temperature loss: s = log_prob + target_entropy
 URGYM_HD inline float sac_entropy_term(float log_prob, float target_entropy) { return log_prob + target_entropy; }
 
@@ -100,6 +113,20 @@ struct SacEntropyCall {
   AdamCoef c;
 };
 
+// include/urgym.h, urgym_sac_entropy_nstep_args, validated: SacEntropyCall with the target group of a per-row discount
+struct SacEntropyNstepCall {
+  int count;
+  float target_entropy, scale;
+  const float* log_prob;
+  float *log_ent_coef, *exp_avg, *exp_avg_sq;
+  float *ent_coef_out, *loss_out;  // loss_out may be null
+  const float *reward, *q_min_next, *discount, *next_log_prob;
+  const uint8_t* terminated;  // may be null with the group given
+  float* y_out;               // null = no target group
+  float* d_log_prob_out;      // null = no upstream group
+  AdamCoef c;
+};
+
 // include/urgym.h, urgym_sac_policy_args, validated
 struct SacPolicyCall {
   int count;
@@ -115,6 +142,7 @@ struct SacPolicyCall {
 
 // ONE launch of ONE workgroup of SAC_TERMS_LANES lanes on `s` each.  The caller has validated everything.
 void sac_entropy_launch(const SacEntropyCall& call, hipStream_t s);
+void sac_entropy_nstep_launch(const SacEntropyNstepCall& call, hipStream_t s);
 void sac_policy_launch(const SacPolicyCall& call, hipStream_t s);
 
 }  // namespace urgym

@@ -55,6 +55,35 @@ __global__ void __launch_bounds__(SAC_TERMS_LANES) sac_entropy_kernel(const SacE
   P.log_ent_coef[0] = l, P.exp_avg[0] = m, P.exp_avg_sq[0] = v;
 }
 
+// sac_entropy_kernel with the target group of urgym_sac_entropy_step_nstep: a row's y comes from its own discount and the bootstrap
+// value (sac_target_row_nstep); a lane reads the row before it writes it, so y_out == reward is allowed.  Everything else is the
+// kernel above, line for line.
+__global__ void __launch_bounds__(SAC_TERMS_LANES) sac_entropy_nstep_kernel(const SacEntropyNstepCall P) {
+  __shared__ double partial[SAC_TERMS_LANES];
+  const int t = threadIdx.x;
+  float l = P.log_ent_coef[0], m = P.exp_avg[0], v = P.exp_avg_sq[0];
+  const float alpha = expf(l);
+  const float up = alpha * P.scale;
+  double s = 0.0;
+  for (int r = t; r < P.count; r += SAC_TERMS_LANES) {
+    s += (double)sac_entropy_term(P.log_prob[r], P.target_entropy);
+    if (P.y_out) {
+      const bool terminal = P.terminated && P.terminated[r];
+      P.y_out[r] = sac_target_row_nstep(P.reward[r], P.q_min_next[r], P.discount[r], P.next_log_prob[r], terminal, alpha);
+    }
+    if (P.d_log_prob_out) P.d_log_prob_out[r] = up;
+  }
+  partial[t] = s;
+  fold(partial, t);
+  if (t != 0) return;
+  const float mean = ordered_mean(partial[0], P.count);
+  float loss;
+  sac_entropy_tail(P.c, mean, l, m, v, loss);
+  P.ent_coef_out[0] = alpha;
+  if (P.loss_out) P.loss_out[0] = loss;
+  P.log_ent_coef[0] = l, P.exp_avg[0] = m, P.exp_avg_sq[0] = v;
+}
+
 __global__ void __launch_bounds__(SAC_TERMS_LANES) sac_policy_kernel(const SacPolicyCall P) {
   __shared__ double partial[3][SAC_TERMS_LANES];  // q0's, q1's and the actor's terms
   const int t = threadIdx.x;
@@ -91,6 +120,10 @@ __global__ void __launch_bounds__(SAC_TERMS_LANES) sac_policy_kernel(const SacPo
 
 void sac_entropy_launch(const SacEntropyCall& call, hipStream_t s) {
   hipLaunchKernelGGL(sac_entropy_kernel, dim3(1), dim3(SAC_TERMS_LANES), 0, s, call);
+}
+
+void sac_entropy_nstep_launch(const SacEntropyNstepCall& call, hipStream_t s) {
+  hipLaunchKernelGGL(sac_entropy_nstep_kernel, dim3(1), dim3(SAC_TERMS_LANES), 0, s, call);
 }
 
 void sac_policy_launch(const SacPolicyCall& call, hipStream_t s) {

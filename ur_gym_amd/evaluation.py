@@ -332,6 +332,94 @@ def entropy_step(alpha, log_prob, target_entropy, l, m, v, coef, *, target=None,
     return out
 
 
+def entropy_step_nstep(alpha, log_prob, target_entropy, l, m, v, coef, *, reward=None, q_min_next=None, discount=None, next_log_prob=None,
+                       terminated=None, scale=None):
+    """urgym_sac_entropy_step_nstep restated from include/urgym.h in numpy: ``entropy_step`` with the target group of a per-row
+    discount -- `reward` (the multi-step return), `q_min_next`, `discount`, `next_log_prob`, float32 [count] each and given
+    together; `terminated` or None.  ``y = (reward + (discount nd) q_min_next) - ((discount nd) alpha) next_log_prob``, float32 with
+    one operation per line.  Everything else, and the returned dict, as ``entropy_step``."""
+    f = np.float32
+    out = entropy_step(alpha, log_prob, target_entropy, l, m, v, coef, scale=scale)
+    group = [x is not None for x in (reward, q_min_next, discount, next_log_prob)]
+    if any(group) != all(group) or (terminated is not None and not all(group)):
+        raise ValueError("the target group is half given: reward, q_min_next, discount and next_log_prob go together (terminated only with them)")
+    if all(group):
+        count, alpha = np.asarray(log_prob).size, f(alpha)
+        reward, q_min_next, discount, next_log_prob = (_rows32(name, x, (count,)) for name, x in (
+            ("reward", reward), ("q_min_next", q_min_next), ("discount", discount), ("next_log_prob", next_log_prob)))
+        with np.errstate(all="ignore"):  # NaN and overflow are inputs the step is defined on
+            nd = np.ones(count, f) if terminated is None else np.where(np.asarray(terminated).reshape(count).astype(bool), f(0), f(1))
+            d = discount * nd
+            a = d * q_min_next
+            tv = reward + a
+            t = d * alpha
+            e = t * next_log_prob
+            out["y"] = tv - e
+        for x in (nd, d, a, tv, t, e, out["y"]):
+            assert x.dtype == f, x.dtype  # no intermediate was promoted
+    return out
+
+
+def nstep_batch(ring_arrays, oldest_slot, filled, seed, draw, count, n_steps, gamma):
+    """urgym_replay_sample_nstep restated from include/urgym.h in numpy float32, on ``replay_indices``.  `ring_arrays`: the ring's
+    fields as host arrays [C, N, ...] (``truncated`` and ``is_success`` may be absent; ``truncated`` is needed for `n_steps` > 1);
+    `filled` valid slots from `oldest_slot` on.  For row i with e = replay_indices(...)[i]: p = e // N, env = e % N, L = min(n_steps,
+    filled - p), entry_k = ((oldest_slot + p + k) % C) N + env, m = the first k + 1 at which terminated | truncated, else L; R =
+    reward[entry_0], g = gamma, then for k = 1 .. m - 1: t = g reward[entry_k], R = R + t, g = g gamma, each rounded to float32.
+    Returns a dict: every ring field present [count, ...] -- ``reward`` = R; the s rows and ``action`` from entry_0; the ``next_*``
+    rows and the flags from entry_{m-1} -- and ``index`` (entry_0), ``last_index`` (entry_{m-1}), both int64, ``steps`` (m, int32) and
+    ``discount`` (g = gamma^m, float32)."""
+    f = np.float32
+    n_steps, oldest_slot, filled, count = int(n_steps), int(oldest_slot), int(filled), int(count)
+    from . import _abi
+
+    if not 1 <= n_steps <= _abi.REPLAY_NSTEP_MAX:
+        raise ValueError(f"n_steps must be in [1, {_abi.REPLAY_NSTEP_MAX}], got {n_steps}")
+    if not np.isfinite(f(gamma)):
+        raise ValueError(f"gamma must be finite in float32, got {gamma}")
+    reward = np.asarray(ring_arrays["reward"])
+    if reward.dtype != f or reward.ndim != 2:
+        raise ValueError(f"ring_arrays['reward'] must be float32 [C, N], got {reward.dtype} {reward.shape}")
+    cap, N = reward.shape
+    if not (1 <= filled <= cap and 0 <= oldest_slot < cap):
+        raise ValueError(f"filled must be in [1, {cap}] and oldest_slot in [0, {cap}), got {filled}, {oldest_slot}")
+    truncated = ring_arrays.get("truncated")
+    if truncated is None and n_steps > 1:
+        raise ValueError("n_steps > 1 needs the ring's truncated (an episode's end at the time limit could not be seen)")
+    flat = lambda a: np.asarray(a).reshape(cap * N, *np.asarray(a).shape[2:])  # noqa: E731
+    ends = flat(ring_arrays["terminated"]) != 0
+    if truncated is not None:
+        ends = ends | (flat(truncated) != 0)
+    e = replay_indices(seed, draw, count, filled * N)
+    p, env = e // N, e % N
+    L = np.minimum(n_steps, filled - p)
+    gamma = f(gamma)
+    R, g = np.zeros(count, f), np.full(count, gamma, f)
+    m, first, last, running = np.zeros(count, np.int32), np.zeros(count, np.int64), np.zeros(count, np.int64), np.ones(count, bool)
+    with np.errstate(all="ignore"):  # NaN and overflow are values a reward may hold
+        for k in range(n_steps):
+            take = running & (k < L)
+            entry = np.where(take, ((oldest_slot + p + k) % cap) * N + env, 0)  # rows that take no step k read nothing of it
+            r = flat(reward)[entry]
+            if k == 0:
+                R, first = r.copy(), entry.copy()
+            else:
+                t = g * r
+                R_next = R + t
+                g_next = g * gamma
+                assert t.dtype == f and R_next.dtype == f and g_next.dtype == f  # no intermediate was promoted
+                R, g = np.where(take, R_next, R), np.where(take, g_next, g)
+            m, last = np.where(take, np.int32(k + 1), m), np.where(take, entry, last)
+            running = running & ~(take & ends[entry])
+    out = {"reward": R, "discount": g, "steps": m, "index": first, "last_index": last}
+    for name in ("observation", "achieved_goal", "desired_goal", "action"):
+        out[name] = flat(ring_arrays[name])[first]
+    for name in ("next_observation", "next_achieved_goal", "next_desired_goal", "terminated", "truncated", "is_success"):
+        if ring_arrays.get(name) is not None:
+            out[name] = flat(ring_arrays[name])[last]
+    return out
+
+
 def policy_terms(alpha, *, dqmin_da=None, scale=None, q=None, y=None, log_prob=None, q_min=None):
     """urgym_sac_policy_terms restated from include/urgym.h in numpy float32, the means by ``ordered_sum``; `alpha` as in
     ``entropy_step``.  Groups, each whole or absent: (`dqmin_da` [count, 6], `scale`) gives ``d_action``; (`q` [2, count], `y`
@@ -1038,9 +1126,12 @@ class DeviceReplay:
         self.cursor = (self.cursor + K) % self.capacity
         self.filled = min(self.capacity, self.filled + K)
 
-    def sample_into(self, out, seed, draw):
+    def sample_into(self, out, seed, draw, n_steps=None, gamma=None):
         """The gather itself: `out` maps ring field names (and ``index``, int64) to contiguous device tensors with one leading
-        length, the batch size; only those are written.  The rows are ``replay_indices(seed, draw, count, len(self))``."""
+        length, the batch size; only those are written.  The rows are ``replay_indices(seed, draw, count, len(self))``.
+
+        With `n_steps` and `gamma` (both or neither) the launch is urgym_replay_sample_nstep: a row spans up to `n_steps` steps of
+        its env (``nstep_batch``), `out` must hold ``discount`` (float32) and may hold ``steps`` (int32) and ``last_index`` (int64)."""
         import ctypes as C
 
         import torch
@@ -1051,12 +1142,17 @@ class DeviceReplay:
         env = self.env
         kinds = {name: (ct, shape(1, 1, env.obs_dim, env.goal_dim)[2:]) for name, ct, shape, _ in _abi.REPLAY_RING_FIELDS}
         kinds["index"] = (C.c_int64, ())
-        batch, count = _abi.ReplayBatch(), None
+        if (n_steps is None) != (gamma is None):
+            raise ValueError("n_steps and gamma go together")
+        extra = {"discount": (C.c_float, ()), "steps": (C.c_int32, ()), "last_index": (C.c_int64, ())} if n_steps is not None else {}
+        kinds.update(extra)
+        dtypes = {C.c_int64: torch.int64, C.c_int32: torch.int32}
+        batch, nstep, count = _abi.ReplayBatch(), _abi.ReplayNstep(), None
         for name, t in out.items():
             if name not in kinds:
                 raise ValueError(f"unknown batch field {name!r}; available: {sorted(kinds)}")
             ct, tail = kinds[name]
-            want = torch.int64 if ct is C.c_int64 else _TORCH_DTYPE[ct]
+            want = dtypes[ct] if ct in dtypes else _TORCH_DTYPE[ct]
             t = t.view(torch.uint8) if t.dtype == torch.bool else t
             if t.dtype != want or not t.is_contiguous() or t.device != env.device or t.dim() != 1 + len(tail) or tuple(t.shape[1:]) != tail:
                 raise ValueError(f"{name} must be a contiguous {want} [count{''.join(f', {d}' for d in tail)}] tensor on {env.device}")
@@ -1064,18 +1160,33 @@ class DeviceReplay:
                 count = int(t.shape[0])
             elif int(t.shape[0]) != count:
                 raise ValueError(f"{name} has {int(t.shape[0])} rows, the others {count}")
-            setattr(batch, name, C.cast(t.data_ptr(), C.POINTER(ct)))
+            setattr(nstep if name in extra else batch, name, C.cast(t.data_ptr(), C.POINTER(ct)))
         if count is None:
             raise ValueError("no output requested")
         self.check_args(self.capacity, filled_steps=self.filled, oldest_slot=self.oldest_slot, batch_size=count)
+        if n_steps is not None:
+            if isinstance(n_steps, bool) or int(n_steps) != n_steps or not 1 <= int(n_steps) <= _abi.REPLAY_NSTEP_MAX:
+                raise ValueError(f"n_steps must be an integer in [1, {_abi.REPLAY_NSTEP_MAX}], got {n_steps!r}")
+            if not abs(float(gamma)) < 3.4028235677973366e38:  # the first double that rounds to an infinite float32; refuses NaN too
+                raise ValueError(f"gamma must be finite in float32, got {gamma}")
+            if "discount" not in out:
+                raise ValueError("with n_steps the batch needs discount")
+            nstep.n_steps, nstep.gamma = int(n_steps), float(gamma)
+            _native.check(env.lib.urgym_replay_sample_nstep(env._h, C.byref(self._ring), self.oldest_slot, self.filled, int(seed), int(draw), count,
+                                                            C.byref(batch), C.byref(nstep), env._stream()), env._h)
+            return
         _native.check(env.lib.urgym_replay_sample(env._h, C.byref(self._ring), self.oldest_slot, self.filled, int(seed), int(draw), count,
                                                   C.byref(batch), env._stream()), env._h)
 
-    def sample(self, batch_size, seed, draw):
+    def sample(self, batch_size, seed, draw, n_steps=None, gamma=None):
         """A minibatch of `batch_size` transitions drawn uniformly with replacement, one launch: a dict of fresh device tensors --
         ``observations`` and ``next_observations`` (each {observation, achieved_goal, desired_goal}: the `rows` of
         ``env.policy_actions`` / ``env.critic_values``), ``actions``, ``rewards``, ``terminated``, ``truncated``, ``is_success``
-        (bool views) and ``index`` (int64: the flat ring entry slot * N + env of each row).  Nothing is synchronised."""
+        (bool views) and ``index`` (int64: the flat ring entry slot * N + env of each row).  Nothing is synchronised.
+
+        With `n_steps` and `gamma` the rows are multi-step transitions (``sample_into``): ``rewards`` is the discounted return over
+        the m steps taken, ``next_observations`` and the flags are those of the last of them, and the dict also holds ``discount``
+        (gamma^m, float32), ``steps`` (m, int32) and ``last_index`` (int64)."""
         import ctypes as C
 
         import torch
@@ -1088,21 +1199,32 @@ class DeviceReplay:
         flat = {name: torch.empty((B,) + tuple(shape(1, 1, env.obs_dim, env.goal_dim)[2:]), dtype=_TORCH_DTYPE[ct], device=env.device)
                 for name, ct, shape, _ in _abi.REPLAY_RING_FIELDS}
         flat["index"] = torch.empty((B,), dtype=torch.int64, device=env.device)
-        self.sample_into(flat, seed, draw)
+        if n_steps is not None:
+            flat.update(discount=torch.empty((B,), dtype=torch.float32, device=env.device), steps=torch.empty((B,), dtype=torch.int32, device=env.device),
+                        last_index=torch.empty((B,), dtype=torch.int64, device=env.device))
+        self.sample_into(flat, seed, draw, n_steps=n_steps, gamma=gamma)
         rows = ("observation", "achieved_goal", "desired_goal")
-        return {"observations": {k: flat[k] for k in rows}, "next_observations": {k: flat["next_" + k] for k in rows},
+        more = {k: flat[k] for k in ("discount", "steps", "last_index")} if n_steps is not None else {}
+        return {**more, "observations": {k: flat[k] for k in rows}, "next_observations": {k: flat["next_" + k] for k in rows},
                 "actions": flat["action"], "rewards": flat["reward"], "terminated": flat["terminated"].view(torch.bool),
                 "truncated": flat["truncated"].view(torch.bool), "is_success": flat["is_success"].view(torch.bool), "index": flat["index"]}
 
-    def sample_targets(self, actor, critic, batch_size, seed, draw, gamma, ent_coef, sample=None):
+    def sample_targets(self, actor, critic, batch_size, seed, draw, gamma, ent_coef, sample=None, n_steps=None):
         """``sample``, then a' ~ pi(.|s') on the gathered next observations (``env.policy_actions(rows=)``), then SAC's target
         y = r + gamma (1 - terminated) (min_i Q_i(s', a') - ent_coef log pi(a'|s')) (``env.critic_values``): three launches.
         `sample` = how a' is drawn (default: gaussian with this call's seed and draw).  Returns the batch with ``next_actions``,
-        ``next_log_prob`` and ``target`` added."""
-        batch = self.sample(batch_size, seed, draw)
+        ``next_log_prob`` and ``target`` added.
+
+        With `n_steps` the batch is ``sample(..., n_steps=, gamma=)`` and the third launch writes the bootstrap value alone: the
+        batch gets ``q_min_next`` = min_i Q_i(s', a') beside its ``discount`` instead of ``target`` (``env.entropy_step_nstep`` forms
+        y from them); `ent_coef` is not used."""
+        batch = self.sample(batch_size, seed, draw, n_steps=n_steps, gamma=None if n_steps is None else gamma)
         how = dict(mode="gaussian", seed=seed, first_draw=draw) if sample is None else sample
         nxt = batch["next_observations"]
         batch["next_actions"], batch["next_log_prob"] = self.env.policy_actions(actor, sample=how, rows=nxt)
+        if n_steps is not None:
+            batch["q_min_next"] = self.env.critic_values(critic, batch["next_actions"], rows=nxt)["q_min"]
+            return batch
         batch["target"] = self.env.critic_values(critic, batch["next_actions"], rows=nxt, reward=batch["rewards"], terminated=batch["terminated"],
                                                  log_prob=batch["next_log_prob"], gamma=gamma, ent_coef=ent_coef)["target"]
         return batch

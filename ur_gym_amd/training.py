@@ -41,6 +41,11 @@ minibatch gather on the HIP kernels, and gradients and optimisers in torch autog
     nothing goes through autograd, the losses are 0-dim views of preallocated tensors, and ``self.last_update`` keeps references
     (no copies) to the ``log_prob``, ``y``, ``q``, ``q_min`` and ``dqmin_da`` the update used.  Every float of it is stated in
     include/urgym.h.
+    With ``n_steps`` > 1 (it needs ``device_entropy=True``; SB3's ``n_steps=``) the target is a multi-step return: the gather walks up
+    to ``n_steps`` consecutive steps of the drawn env and stops at an episode's end (``DeviceReplay.sample_targets(n_steps=)``,
+    urgym_replay_sample_nstep), the third launch writes min_i Q_i'(s', a') alone, and ``env.entropy_step_nstep`` forms
+    y = R + gamma^m (1 - terminated) (min Q' - alpha log pi(a'|s')) from the row's own discount: still thirteen launches.
+    ``n_steps`` = 1, the default, makes exactly the calls above.
     None of them synchronises with the host.  ``train`` runs the whole loop in one native call and, given an
     ``evaluation.DeviceEvaluation``, the reference's EvalCallback inside it: evaluations of the deterministic policy at a fixed interval of
     updates, their statistics as records on the device, and the best actor's tensors, which ``DeviceEvaluation.save_best`` writes as an
@@ -62,7 +67,7 @@ from .evaluation import ACTOR_ARRAYS, CRITIC_ARRAYS, LOG_STD_ARRAYS, LOG_STD_MAX
 # SB3's SAC defaults where train.py does not set them (tests/golden/critics/sac_hyperparameters.json has the checkpoints' gamma, tau)
 SAC_DEFAULTS = dict(gamma=0.95, tau=0.005, learning_rate=1e-4, batch_size=256, learning_starts=100, hidden_width=256, target_entropy=-6.0,
                     ent_coef_init=1.0, device_action_gradient=False, device_critic_gradient=False,
-                    device_actor_gradient=False, device_optimizer=False, device_entropy=False)
+                    device_actor_gradient=False, device_optimizer=False, device_entropy=False, n_steps=1)
 
 
 def _mlp(n_in, hidden, n_out=None):
@@ -149,6 +154,11 @@ class SACLearner:
         if unknown:
             raise TypeError(f"unknown hyperparameters {unknown}; available: {sorted(SAC_DEFAULTS)}")
         hp = dict(SAC_DEFAULTS, **overrides)
+        n_steps = hp["n_steps"]
+        if isinstance(n_steps, bool) or int(n_steps) != n_steps or not 1 <= int(n_steps) <= 32:
+            raise ValueError(f"n_steps must be an integer in [1, 32], got {n_steps!r}")
+        if int(n_steps) > 1 and not hp["device_entropy"]:
+            raise ValueError("n_steps > 1 needs device_entropy=True (the multi-step target is formed by the device's entropy step)")
         self.env, self.hp, self.seed = env, hp, int(seed)
         n_in, H, dev = env.obs_dim + 2 * env.goal_dim, int(hp["hidden_width"]), env.device
         torch.manual_seed(self.seed)
@@ -312,17 +322,23 @@ class SACLearner:
         hp, env, st, es = self.hp, self.env, self.adam_state, self.entropy_state
         if not 0 <= int(draw) < 2 ** 63:
             raise ValueError("with device_actor_gradient the draw must be below 2**63 (its top bit marks the policy's own draw)")
-        M, gamma = int(hp["batch_size"]), float(hp["gamma"])
-        batch = replay.sample_targets(self.device_actor, self.target, M, seed, draw, gamma, 0.0)
+        M, gamma, n_steps = int(hp["batch_size"]), float(hp["gamma"]), int(hp["n_steps"])
+        batch = replay.sample_targets(self.device_actor, self.target, M, seed, draw, gamma, 0.0, **({} if n_steps == 1 else dict(n_steps=n_steps)))
         rows = batch["observations"]
         how = dict(mode="gaussian", seed=seed, first_draw=int(draw) | 1 << 63)
         action_pi, log_prob = env.policy_actions(self.device_actor, sample=how, rows=rows)
         st["step"] += 1
         adam = dict(lr=hp["learning_rate"], betas=st["betas"], eps=st["eps"], step=st["step"])
         # alpha of the old log_ent_coef, y, d_log_prob = alpha / M, the temperature loss and its Adam step
-        env.entropy_step((self.log_ent_coef, es["exp_avg"], es["exp_avg_sq"]), log_prob, hp["target_entropy"], ent_coef_out=es["ent_coef"],
-                         loss_out=es["ent_coef_loss"], target=batch["target"], next_log_prob=batch["next_log_prob"], terminated=batch["terminated"],
-                         gamma=gamma, y_out=es["y"], d_log_prob_out=self.actor_d_log_prob, scale=1.0 / M, **adam)
+        if n_steps == 1:
+            env.entropy_step((self.log_ent_coef, es["exp_avg"], es["exp_avg_sq"]), log_prob, hp["target_entropy"], ent_coef_out=es["ent_coef"],
+                             loss_out=es["ent_coef_loss"], target=batch["target"], next_log_prob=batch["next_log_prob"], terminated=batch["terminated"],
+                             gamma=gamma, y_out=es["y"], d_log_prob_out=self.actor_d_log_prob, scale=1.0 / M, **adam)
+        else:
+            env.entropy_step_nstep((self.log_ent_coef, es["exp_avg"], es["exp_avg_sq"]), log_prob, hp["target_entropy"], ent_coef_out=es["ent_coef"],
+                                   loss_out=es["ent_coef_loss"], reward=batch["rewards"], q_min_next=batch["q_min_next"], discount=batch["discount"],
+                                   next_log_prob=batch["next_log_prob"], terminated=batch["terminated"], y_out=es["y"],
+                                   d_log_prob_out=self.actor_d_log_prob, scale=1.0 / M, **adam)
         got = env.critic_parameter_gradients(self.online, batch["actions"], target=es["y"], scale=1.0 / M, rows=rows, out=self.critic_grads,
                                              workspace=self.critic_workspace)
         env.critic_adam_step(self.online, self.critic.tensors(), self.critic_grads, *st["critic"], target=self.target, tau=hp["tau"], **adam)
@@ -358,7 +374,10 @@ class SACLearner:
             critic_workspace=self.critic_workspace, log_ent_coef=self.log_ent_coef, exp_avg=es["exp_avg"], exp_avg_sq=es["exp_avg_sq"], replay=replay,
             batch=batch, scratch=scratch, count=M, seed=self.seed, update_seed=0, gamma=hp["gamma"], tau=hp["tau"],
             target_entropy=hp["target_entropy"], lr=hp["learning_rate"], betas=st["betas"], eps=st["eps"])
-        self._train = dict(replay=replay, binding=binding, scratch=scratch)
+        self._train = dict(replay=replay, binding=binding, scratch=scratch, nstep=None)
+        if int(hp["n_steps"]) > 1:  # the two scratch tensors of urgym_sac_train_nstep; like the batch scratch, never saved
+            self._train["nstep"] = dict(n_steps=int(hp["n_steps"]), discount=torch.zeros((M,), dtype=torch.float32, device=dev),
+                                        q_min_next=torch.zeros((M,), dtype=torch.float32, device=dev))
         return self._train
 
     def train(self, replay, iterations, steps_per_iteration=1, updates_per_iteration=1, *, seed, first_draw, evaluation=None, eval_every=None,
@@ -382,7 +401,9 @@ class SACLearner:
         monitor (``collect(..., monitor=)``, bit for bit, warm-up iterations included), and after every iteration at which
         ``monitor.iterations`` reaches a multiple of `log_every` the finished episodes go to the monitor's next record
         (``monitor.record(monitor.iterations)``).  ``monitor.iterations`` and ``monitor.count`` advance, so that split calls place
-        records where one call would.  Both or neither: one alone raises ValueError."""
+        records where one call would.  Both or neither: one alone raises ValueError.
+
+        With ``n_steps`` > 1 the ONE native call is urgym_sac_train_nstep, with the evaluations and the monitor where given."""
         from .evaluation import warmup_iterations
 
         if (evaluation is None) != (eval_every is None):
@@ -402,7 +423,8 @@ class SACLearner:
                       steps_per_iteration=K, updates_per_iteration=G, uniform_iterations=uniform, idle_iterations=idle,
                       collect_first_draw=self.draw, update_first_draw=int(first_draw), first_step=st["step"] + 1,
                       **({} if evaluation is None else dict(evaluation=evaluation, eval_every=eval_every)),
-                      **({} if monitor is None else dict(monitor=monitor, log_every=log_every)))
+                      **({} if monitor is None else dict(monitor=monitor, log_every=log_every)),
+                      **({} if tr["nstep"] is None else dict(nstep=tr["nstep"])))
         self.env_steps += n * K
         self.draw += n * K
         st["step"] += updates
@@ -419,6 +441,11 @@ class SACLearner:
     def _optimizers(self):
         return dict(actor_opt=self.actor_opt, critic_opt=self.critic_opt, ent_opt=self.ent_opt)
 
+    def _saved_hp(self):
+        """The hyperparameters as a checkpoint holds them: ``n_steps`` only where it is not 1, so that the file of a one-step run is
+        what it was before the option existed (``check_state_dict`` reads an absent ``n_steps`` as 1)."""
+        return {k: v for k, v in self.hp.items() if k != "n_steps" or int(v) != 1}
+
     def state_dict(self):
         """Everything the learner is, as host arrays and scalars: the actor's eight and the critics' twelve parameter tensors, the
         TARGET critic's twelve in the same layout (``DeviceCritic.parameters``: the unpack kernel; the Polyak average lives nowhere
@@ -428,7 +455,7 @@ class SACLearner:
         target = self.target.parameters()
         torch.cuda.synchronize(self.env.device)
         host = lambda w: {k: v.detach().cpu().numpy() for k, v in w.items()}  # noqa: E731
-        out = dict(env_id=self.env.env_id, num_envs=self.env.num_envs, hp=dict(self.hp), seed=self.seed, env_steps=self.env_steps, draw=self.draw,
+        out = dict(env_id=self.env.env_id, num_envs=self.env.num_envs, hp=self._saved_hp(), seed=self.seed, env_steps=self.env_steps, draw=self.draw,
                    actor=host(self.actor.tensors()), critic=[host(w) for w in self.critic.tensors()], target=[host(w) for w in target],
                    log_ent_coef=self.log_ent_coef.detach().cpu().numpy(), adam_state=None, entropy_state=None)
         st, es = self.adam_state, self.entropy_state
@@ -486,8 +513,9 @@ class SACLearner:
         for k in SAC_DEFAULTS:
             if k in override:
                 continue
-            if k not in state["hp"] or state["hp"][k] != self.hp[k]:
-                raise ValueError(f"load_state_dict: {k} is {state['hp'].get(k)!r} in the checkpoint, {self.hp[k]!r} here")
+            saved = dict(n_steps=1, **state["hp"]) if "n_steps" not in state["hp"] else state["hp"]  # a one-step run's file holds no n_steps
+            if k not in saved or saved[k] != self.hp[k]:
+                raise ValueError(f"load_state_dict: {k} is {saved.get(k)!r} in the checkpoint, {self.hp[k]!r} here")
         for name, mine in (("adam_state", self.adam_state), ("entropy_state", self.entropy_state)):
             if (state[name] is None) != (mine is None):
                 raise ValueError(f"load_state_dict: {name} is {'absent' if state[name] is None else 'present'} in the checkpoint and the reverse here")

@@ -547,6 +547,50 @@ class UR5ReachVectorEnv:
         hp = self._adam_hyper(lr, betas, eps, step)
         _native.check(self.lib.urgym_sac_entropy_step(self._h, C.byref(a), C.byref(hp), self._stream()), self._h)
 
+    def entropy_step_nstep(self, state, log_prob, target_entropy, *, lr, betas=(0.9, 0.999), eps=1e-8, step, ent_coef_out, loss_out=None,
+                           reward=None, q_min_next=None, discount=None, next_log_prob=None, terminated=None, y_out=None,
+                           d_log_prob_out=None, scale=None):
+        """``entropy_step`` with the target group of a multi-step return, in ONE launch (urgym_sac_entropy_step_nstep): `reward`
+        (the return R), `q_min_next` (min_i Q_i'(s', a')), `discount` (gamma^m), `next_log_prob` and `y_out`, [count] each and given
+        together, and `terminated` or None: ``y_out = (reward + (discount (1 - terminated)) q_min_next) - ((discount (1 -
+        terminated)) alpha) next_log_prob``; `y_out` may be `reward` itself.  Everything else as in ``entropy_step``.  The arithmetic
+        is ``evaluation.entropy_step_nstep``, bitwise.  On torch's current stream, nothing is synchronised."""
+        who = "entropy_step_nstep"
+        names = ("log_ent_coef", "exp_avg", "exp_avg_sq")
+        state = tuple(state[k] for k in names) if isinstance(state, dict) else tuple(state)
+        if len(state) != 3:
+            raise ValueError(f"{who}: state must be the three tensors {names}")
+        if not isinstance(log_prob, torch.Tensor) or log_prob.dim() != 1:
+            raise ValueError(f"{who}: log_prob must be a float32 [count] tensor")
+        count = int(log_prob.shape[0])
+        if not 1 <= count <= _abi.SAC_TERMS_MAX_COUNT:
+            raise ValueError(f"{who}: count must be in [1, {_abi.SAC_TERMS_MAX_COUNT}], got {count}")
+        group = {"reward": reward, "q_min_next": q_min_next, "discount": discount, "next_log_prob": next_log_prob, "y_out": y_out}
+        given = [x is not None for x in group.values()]
+        if any(given) != all(given) or (terminated is not None and not all(given)):
+            raise ValueError(f"{who}: the target group is half given: {', '.join(group)} go together (terminated only with them)")
+        if (d_log_prob_out is None) != (scale is None):
+            raise ValueError(f"{who}: the upstream group is half given: d_log_prob_out and scale go together")
+        for name, x in (("target_entropy", target_entropy), ("scale", scale)):
+            if x is not None and not self._finite32(x):
+                raise ValueError(f"{who}: {name} must be finite in float32, got {x}")
+        a = _abi.SacEntropyNstepArgs(count, 0, float(target_entropy), float(scale or 0.0))
+        a.log_prob = self._float_ptr(who, "log_prob", log_prob, (count,))
+        for name, t in zip(names, state):
+            setattr(a, name, self._float_ptr(who, name, t, (1,)))
+        a.ent_coef_out = self._float_ptr(who, "ent_coef_out", ent_coef_out, (1,))
+        if loss_out is not None:
+            a.loss_out = self._float_ptr(who, "loss_out", loss_out, (1,))
+        if all(given):
+            for name, t in group.items():
+                setattr(a, name, self._float_ptr(who, name, t, (count,)))
+            if terminated is not None:
+                a.terminated = self._float_ptr(who, "terminated", terminated, (count,), torch.uint8, C.c_uint8)
+        if d_log_prob_out is not None:
+            a.d_log_prob_out = self._float_ptr(who, "d_log_prob_out", d_log_prob_out, (count,))
+        hp = self._adam_hyper(lr, betas, eps, step)
+        _native.check(self.lib.urgym_sac_entropy_step_nstep(self._h, C.byref(a), C.byref(hp), self._stream()), self._h)
+
     def policy_terms(self, ent_coef, count, *, dqmin_da=None, scale=None, d_action_out=None, q=None, y=None, critic_loss_out=None,
                      log_prob=None, q_min=None, actor_loss_out=None):
         """What a SAC update forms after the critic's step and the action gradient, in ONE launch (urgym_sac_policy_terms).
@@ -755,7 +799,7 @@ class UR5ReachVectorEnv:
 
     def sac_train(self, learner, critic_loss, actor_loss, ent_coef_loss, *, first_slot, filled_steps, num_iterations, steps_per_iteration=1,
                   updates_per_iteration=1, uniform_iterations=0, idle_iterations=0, collect_first_draw=0, update_first_draw=0, first_step=1,
-                  evaluation=None, eval_every=None, monitor=None, log_every=None):
+                  evaluation=None, eval_every=None, monitor=None, log_every=None, nstep=None):
         """``num_iterations`` x (a collection of ``steps_per_iteration`` steps, ``updates_per_iteration`` SAC updates) in ONE native
         call (urgym_sac_train): the launches of ``collect`` and of the thirteen calls of an update, bit for bit, without returning to
         Python in between.  `learner`: what ``sac_learner`` returned, or a dict of its keyword arguments (then built and checked here).
@@ -773,7 +817,11 @@ class UR5ReachVectorEnv:
         urgym_sac_train_monitored: the same launches -- with the evaluations, if those are given too -- and after every iteration that
         collects one ``monitor.fold`` of its slots, and after every iteration at which the monitor's iteration count reaches a multiple
         of `log_every` one ``monitor.record`` (``evaluation.monitor_points``); the monitor's count and record cursor are advanced.
-        Without them nothing changes."""
+        Without them nothing changes.
+
+        With `nstep` (a dict: ``n_steps`` in [2, 32] and the float32 [count] scratch tensors ``discount`` and ``q_min_next``) the call
+        is urgym_sac_train_nstep, with the evaluations and the monitor if those are given: every update gathers multi-step returns
+        (``DeviceReplay.sample_targets(n_steps=)``) and forms y by ``entropy_step_nstep``.  Without it nothing changes."""
         from .evaluation import DeviceEvaluation, DeviceMonitor, evaluation_points, monitor_points, training_schedule
 
         who = "sac_train"
@@ -817,11 +865,25 @@ class UR5ReachVectorEnv:
         active = max(0, sched["num_iterations"] - max(0, sched["idle_iterations"]))
         updates = active * max(0, sched["updates_per_iteration"])
         L = learner.struct
+        if nstep is not None:
+            n_steps = nstep["n_steps"]
+            if isinstance(n_steps, bool) or int(n_steps) != n_steps or not 2 <= int(n_steps) <= _abi.REPLAY_NSTEP_MAX:
+                raise ValueError(f"{who}: nstep['n_steps'] must be an integer in [2, {_abi.REPLAY_NSTEP_MAX}], got {n_steps!r}")
+            count = int(L.count)
+            N_ = _abi.SacNstep(int(n_steps), 0, self._float_ptr(who, "nstep['discount']", nstep["discount"], (count,)),
+                               self._float_ptr(who, "nstep['q_min_next']", nstep["q_min_next"], (count,)))
         for name, t in zip(_abi.SAC_LEARNER_LOSSES, (critic_loss, actor_loss, ent_coef_loss)):
             setattr(L, name, self._float_ptr(who, name, t, (updates,)))
         S = _abi.SacSchedule(*[sched[name] for name, _ in _abi.SacSchedule._fields_])
         try:
-            if monitor is not None:
+            if nstep is not None:
+                _native.check(self.lib.urgym_sac_train_nstep(self._h, C.byref(L), C.byref(S), C.byref(N_), C.byref(E_) if evaluation is not None else None,
+                                                             C.byref(M_) if monitor is not None else None, self._stream()), self._h)
+                if monitor is not None:
+                    monitor.advance(sched["num_iterations"], len(logged))
+                if evaluation is not None:
+                    evaluation.advance(len(points))
+            elif monitor is not None:
                 _native.check(self.lib.urgym_sac_train_monitored(self._h, C.byref(L), C.byref(S), C.byref(E_) if evaluation is not None else None,
                                                                  C.byref(M_), self._stream()), self._h)
                 monitor.advance(sched["num_iterations"], len(logged))
