@@ -1309,6 +1309,142 @@ typedef struct urgym_sac_nstep {
  * calls above), reserved0 != 0, a NULL scratch pointer, a ring without truncated -- these also where the call holds no update. */
 int urgym_sac_train_nstep(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_nstep* nstep, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream);
 
+/* ---- prioritized replay (Schaul et al., 2016, the proportional variant: one collection step writes N near-identical mid-episode
+ * transitions, and the terminal rows that move the value function are a fraction of a percent of the ring).  A priority structure over
+ * the ring's entries, the draw through it, the importance weights and the write-back of the new priorities, all on the device and all
+ * deterministic: no floating-point atomics, every sum in a stated order (ur_gym_amd/csrc/urgym_per.h states every index and every
+ * float operation; ur_gym_amd.evaluation.per_sums / per_descent / per_terms restate it).  Added WITHIN ABI version 4: no struct above
+ * changed, URGYM_ABI_VERSION did not move, the new symbols (urgym_per_sums_count, urgym_per_rebuild, urgym_per_fill,
+ * urgym_replay_sample_prioritized, urgym_per_terms, urgym_sac_train_prioritized) are found by lookup.  The library allocates nothing and keeps no state; everything
+ * is validated before the first launch; no host synchronisation.  Whether prioritized replay learns a task faster is asserted nowhere.
+ *
+ * leaf[C N], float32, indexed by the flat ring entry slot * N + env (urgym_replay_batch.index): the priority ALREADY raised to alpha,
+ * 0 = never drawn; an all-zero array is a valid empty structure.  sums: float64, fan-out URGYM_PER_FANOUT.  Entry b of level 1 is the
+ * sum of leaves 256 b .. 256 b + 255 (those below C N; blocks straddle slots when N is no multiple of 256), ONE float64 addition per
+ * leaf in ascending order starting from +0.0; level k + 1 is the same over level k; levels are added until one has at most 256
+ * entries, and the TOTAL is the ascending sum of that level.  sums holds level 1, level 2, ..., then the total: urgym_per_sums_count
+ * doubles.  max_leaf[1]: what a new transition gets; the caller sets it to 1.0f once. */
+
+#define URGYM_PER_FANOUT 256
+#define URGYM_PER_TERMS_MAX_COUNT 65536
+
+typedef struct urgym_per_priorities {
+  int32_t capacity_steps; /* C of the ring the leaves belong to */
+  int32_t reserved0;      /* must be 0 */
+  float* leaf;            /* [C][N] */
+  double* sums;           /* [urgym_per_sums_count] */
+  float* max_leaf;        /* [1] */
+} urgym_per_priorities;
+
+/* The length of `sums` for a ring of capacity_steps slots of this handle's N.  Refused: NULL handle / doubles, capacity_steps <= 0,
+ * more than 2^31 - 1 level-1 entries. */
+int urgym_per_sums_count(void* handle, int capacity_steps, uint64_t* doubles);
+
+/* Forms every level and the total from the leaves as they lie.  TWO launches on `stream` (level 1: one workgroup per entry; every
+ * level above and the total: one workgroup).  Refused: NULL handle / pri or one of its three pointers, capacity_steps <= 0,
+ * reserved0 != 0. */
+int urgym_per_rebuild(void* handle, const urgym_per_priorities* pri, void* stream);
+
+/* The leaves of slots (first_slot + k) % C, k < num_steps, become max_leaf[0] (num_steps >= C: every leaf), and the sums are
+ * repaired -- the level-1 entries that overlap those slots, then every level above -- to bitwise what urgym_per_rebuild would leave.
+ * TWO launches (the first writes the leaves and forms the level-1 entries).  Refused beyond urgym_per_rebuild's: first_slot outside
+ * [0, C), num_steps <= 0. */
+int urgym_per_fill(void* handle, const urgym_per_priorities* pri, int first_slot, int num_steps, void* stream);
+
+/* urgym_replay_sample with the entry of row i drawn in proportion to its leaf, in ONE launch (the descent, then the same gather):
+ *   w = (w0 << 32) | w1 of Philox4x32-10 with urgym_replay_sample's key and the counter (i, draw lo, draw hi, 0x50455200) -- the last
+ *   word meets none of the others (0x504F4C00 | block, 0x52504C00, the reset sampler's 0..4);
+ *   u = (double)(w >> 11) * 2^-53;  t = u * total;  then from the top level down, over the children of the chosen node in ascending
+ *   order with s = +0.0:  s2 = s + v[k];  if t < s2 take k and t = t - s, else s = s2;  v[k] = (double)leaf at the last level.
+ *   If rounding lets no child be taken: the last child with v > 0, else the first (an all-zero structure yields entry 0).
+ * A leaf of 0 is never drawn while any leaf is positive, so unfilled slots need no oldest_slot.  index[i] = the entry (batch->index
+ * is REQUIRED here), leaf_out[i] = leaf[entry] (float32, [count]), total_out[0] = the total (float64); the other batch fields as
+ * urgym_replay_sample gathers them.  A row depends on (seed, draw, i) and the structure only: not on count, not on the launch
+ * geometry.  Refused: the ring refusals of urgym_replay_sample, count <= 0, batch == NULL, batch->index == NULL, truncated /
+ * is_success asked from a ring that does not keep it, the refusals of urgym_per_rebuild about pri, pri->capacity_steps other than
+ * the ring's, leaf_out or total_out NULL. */
+int urgym_replay_sample_prioritized(void* handle, const urgym_replay_ring* ring, const urgym_per_priorities* pri, uint64_t seed, uint64_t draw, int count, const urgym_replay_batch* batch, float* leaf_out, double* total_out, void* stream);
+
+/* DEVICE pointers.  The write-back group -- index, new_leaf and the three pointers of `priorities` -- is given whole or not at all. */
+typedef struct urgym_per_terms_args {
+  int32_t count;          /* in [1, URGYM_PER_TERMS_MAX_COUNT] */
+  int32_t reserved0;      /* must be 0 */
+  float size;             /* filled_steps * N as float32; positive and finite */
+  float beta;             /* in [0, 1] */
+  float alpha;            /* in [0, 1] */
+  float eps;              /* positive and finite */
+  float scale;            /* finite; 1 / count gives SB3's critic loss */
+  float reserved1;        /* must be 0 */
+  const float* leaf_in;   /* [count] leaf_out of the draw */
+  const double* total;    /* [1] total_out of the draw */
+  const float* q;         /* [2][count] urgym_critic_evaluate's q of the batch rows */
+  const float* y;         /* [count] the target */
+  float* w_raw;           /* [count] */
+  float* w;               /* [count] */
+  float* dq;              /* [2][count] urgym_critic_parameter_gradients' dq */
+  const int64_t* index;   /* [count] batch.index, or NULL */
+  float* new_leaf;        /* [count], or NULL */
+  urgym_per_priorities priorities; /* all three pointers NULL without the group */
+} urgym_per_terms_args;
+
+/* The importance weights, the weighted upstream gradient of the critics and the new priorities.  The per-row part is ONE launch of ONE
+ * workgroup of 1024 lanes (the shape of urgym_sac_entropy_step).  Per row m, each line ONE float32 operation rounded on its own
+ * unless marked:
+ *   prob = (float)((double)leaf_in[m] / total[0])          (one float64 division, rounded to float32 once)
+ *   x = size * prob
+ *   w_raw[m] = powf(x, -beta)
+ *   wmax = the maximum of 0 and every w_raw (fmaxf: order-independent; a NaN is passed over)
+ *   w[m] = w_raw[m] / wmax
+ *   e_i = q[i][m] - y[m];   g_i = e_i * scale;   dq[i][m] = g_i * w[m]
+ *   td = fmaxf(|e_0|, |e_1|);   p = td + eps;   new_leaf[m] = powf(p, alpha)
+ * A new_leaf that is not finite (a NaN q or y in the row) is replaced by max_leaf[0] as it stood before the call.  With w == 1 on
+ * every row (beta = 0) dq is bitwise what urgym_critic_parameter_gradients forms from target = y and the same scale.  powf is the
+ * device library's (OpenCL's table allows 16 ulp): w_raw and new_leaf are outputs, and a restatement takes them as inputs.
+ * With the write-back group: leaf[index[m]] = new_leaf[m]; an entry drawn by several rows ends at the LARGEST of their values (the
+ * entry is set to +0, then an integer maximum on the bit patterns of the non-negative floats: order-independent); an index outside
+ * [0, C N) is passed over; max_leaf[0] = fmaxf(max_leaf[0], max_m new_leaf[m]); then the sums are repaired in TWO more launches (the
+ * level-1 entries of the touched leaves -- every level-1 entry where count is at least their number --, then every level above) to
+ * bitwise what urgym_per_rebuild would leave.  Without the group: one launch, nothing but w_raw, w and dq is written.
+ * The critic loss urgym_sac_policy_terms reports stays the unweighted one.
+ * Refused (URGYM_ERR_ARG, nothing launched, nothing written): NULL handle / args; count outside [1, URGYM_PER_TERMS_MAX_COUNT];
+ * reserved0 or reserved1 != 0; a NULL required pointer; alpha or beta outside [0, 1] (NaN included); eps not positive and finite; size
+ * not positive and finite; scale not finite; a half-given write-back group; with the group, priorities.capacity_steps <= 0 or its
+ * reserved0 != 0. */
+int urgym_per_terms(void* handle, const urgym_per_terms_args* args, void* stream);
+
+/* The structure, the exponents, the beta schedule and the [count] scratch of urgym_sac_train_prioritized. */
+typedef struct urgym_sac_prioritized {
+  urgym_per_priorities priorities; /* of learner->ring: the same capacity_steps */
+  double beta0;       /* in [0, 1] */
+  int64_t beta_steps; /* >= 1 */
+  float alpha;        /* in [0, 1] */
+  float eps;          /* positive and finite */
+  float* leaf;        /* [count] scratch: leaf_out of the draw */
+  double* total;      /* [1] scratch: total_out of the draw */
+  float* q;           /* [2][count] scratch: the online critics' q on the batch rows */
+  float* w_raw;       /* [count] scratch */
+  float* w;           /* [count] scratch */
+  float* dq;          /* [2][count] scratch */
+  float* new_leaf;    /* [count] scratch */
+  int64_t reserved0;  /* must be 0 */
+} urgym_sac_prioritized;
+
+/* The launches of urgym_sac_train_monitored, urgym_sac_train_evaluated or urgym_sac_train, according to which of the two arguments are
+ * NULL, with these differences.  After the collection of every iteration with steps_per_iteration > 0 (idle iterations too): ONE
+ * urgym_per_fill on the slots just written.  In each update: the gather is urgym_replay_sample_prioritized (batch.index is required);
+ * after the entropy step come urgym_critic_evaluate(online, the batch rows with batch.action) -> q and urgym_per_terms(leaf, total, q,
+ * y, size = filled_steps * N of the iteration, beta, alpha, eps, scale = 1 / count, the write-back group); and
+ * urgym_critic_parameter_gradients takes dq = instead of target =, its own q output bitwise the evaluate's.  beta of the update at Adam
+ * step t is beta0 + (1 - beta0) min(1, t / beta_steps), formed in float64 and rounded to float32 once (per_beta of
+ * ur_gym_amd/csrc/urgym_per.h; ur_gym_amd.evaluation.per_beta restates it).  17 launches per update (19 above 1024 rows) and 2 per
+ * collection.  urgym_sac_policy_terms is unchanged: the critic loss reported is the UNWEIGHTED one.  The schedule, the draws, the
+ * step numbers and the loss slots are those of urgym_sac_train.  Bit for bit that sequence of single calls.  EVERYTHING is validated
+ * before the first launch.  Refused besides what those calls and the single calls refuse: prioritized == NULL, reserved0 != 0, a NULL
+ * scratch pointer, beta0 outside [0, 1], beta_steps < 1, priorities.capacity_steps other than the ring's, batch.index == NULL --
+ * these also where the call holds no update.  Multi-step returns together with priorities are out of scope (the multi-step gather
+ * draws its own indices): there is no such call. */
+int urgym_sac_train_prioritized(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_prioritized* prioritized, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream);
+
 /* ---- weights back to the device tensors (a checkpoint: the reference's train.py:31-36 continues a saved run, and the TARGET critic
  * exists only as a packed buffer, blended in place by urgym_critic_load(tau < 1) and urgym_critic_adam_step(target)).  The packing
  * map of ur_gym_amd/csrc/urgym_pack_map.h run the other way, on the device: every element of every destination tensor -- DEVICE

@@ -1215,6 +1215,112 @@ def nstep_mode(args):
             f.write(line + "\n")
 
 
+def prioritized_mode(args):
+    """--prioritized: the prioritized update against the uniform one, both as SACLearner.train on the same filled
+    ring (a DevicePrioritizedReplay serves both: the uniform learner goes through exactly the calls it always made), H = 256, batch
+    65,536 and 4,096, in alternating windows of --launches updates in one native call each, timed on the host around a
+    synchronisation.  Then the pieces on their own, timed with events: the uniform gather against the prioritized one (the descent's
+    cost per row), and urgym_per_terms with its write-back (one workgroup, then the two repair launches)."""
+    import torch
+
+    from ur_gym_amd import make_vec
+    from ur_gym_amd.evaluation import DevicePrioritizedReplay
+    from ur_gym_amd.training import SACLearner
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_policy_rollout.py measures on a GPU; none is visible")
+    dev, n, cap = "cuda:0", args.num_envs, args.capacity
+    env = make_vec(args.env, num_envs=n, device=dev, seed=0, auto_reset=True)
+    env.reset(seed=0)
+    sync = lambda: torch.cuda.synchronize(env.device)  # noqa: E731
+    options = dict(device_action_gradient=True, device_critic_gradient=True, device_actor_gradient=True, device_optimizer=True, device_entropy=True)
+    replay = DevicePrioritizedReplay(env, cap)
+    filler = SACLearner(env, seed=0, batch_size=256, hidden_width=256, learning_starts=0, **options)
+    while replay.filled < cap:  # a filled ring, from the sampled policy; every leaf at max_leaf
+        filler.collect(replay, min(64, cap - replay.filled))
+    filler.close()
+    sync()
+    batches = (65536,) if args.prioritized_only else (65536, 4096)
+    result = {}
+    for M in batches:
+        learners = {} if args.prioritized_only else {"uniform": (SACLearner(env, seed=0, batch_size=M, hidden_width=256, learning_starts=0, **options), [0])}
+        learners["prioritized"] = (SACLearner(env, seed=0, batch_size=M, hidden_width=256, learning_starts=0, prioritized=True, per_beta_steps=1000, **options), [0])
+
+        def updates(label):
+            learner, draw = learners[label]
+
+            def fn():
+                learner.train(replay, 1, 0, args.launches, seed=1, first_draw=draw[0] + 1)
+                draw[0] += args.launches
+            return fn
+
+        def host_window(fn):
+            sync()
+            t0 = time.perf_counter()
+            fn()
+            sync()
+            return (time.perf_counter() - t0) * 1e6 / args.launches
+
+        fns = {label: updates(label) for label in learners}
+        for fn in fns.values():
+            fn()
+        wins = {label: [] for label in fns}
+        for _ in range(args.windows):
+            for label, fn in fns.items():
+                wins[label].append(host_window(fn))
+        med = {k: float(np.median(v)) for k, v in wins.items()}
+        entry = {"us_per_update_windows": {k: [round(x, 2) for x in v] for k, v in wins.items()}, "us_per_update_median": med}
+        if not args.prioritized_only:
+            entry["prioritized_minus_uniform_us"] = med["prioritized"] - med["uniform"]
+            entry["uniform_us_spread"] = float(max(wins["uniform"]) - min(wins["uniform"]))
+            # the pieces, with events
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+            def window(fn, reps=args.launches):
+                for _ in range(5):
+                    fn()
+                sync()
+                e0.record()
+                for _ in range(reps):
+                    fn()
+                e1.record()
+                sync()
+                return e0.elapsed_time(e1) * 1e3 / reps
+
+            tick = [0]
+
+            def uniform_gather():
+                tick[0] += 1
+                replay.sample(M, 3, tick[0])
+
+            def prioritized_gather():
+                tick[0] += 1
+                replay.sample_prioritized(M, 3, tick[0])
+
+            batch = replay.sample_prioritized(M, 3, 1)
+            q, y = torch.randn((2, M), device=dev), torch.randn((M,), device=dev)
+            out = {}
+            pieces = {"uniform_gather_us": [window(uniform_gather) for _ in range(args.windows)],
+                      "prioritized_gather_us": [window(prioritized_gather) for _ in range(args.windows)],
+                      "per_terms_three_launches_us": [window(lambda: replay.terms(batch, q, y, 0.7, 1.0 / M, out=out)) for _ in range(args.windows)],
+                      "per_terms_one_launch_us": [window(lambda: replay.terms(batch, q, y, 0.7, 1.0 / M, write_back=False, out=out)) for _ in range(args.windows)],
+                      "fill_one_slot_us": [window(lambda: replay.fill(3, 1)) for _ in range(args.windows)]}
+            entry["pieces_us_median"] = {k: float(np.median(v)) for k, v in pieces.items()}
+            entry["descent_ns_per_row"] = (entry["pieces_us_median"]["prioritized_gather_us"] - entry["pieces_us_median"]["uniform_gather_us"]) * 1e3 / M
+        result[str(M)] = entry
+        for learner, _ in learners.values():
+            learner.close()
+    out = {"tool": "bench_policy_rollout --prioritized", "env": args.env, "num_envs": n, "capacity_steps": cap, "windows": args.windows,
+           "launches_per_window": args.launches, "hidden_width": 256, "device": torch.cuda.get_device_name(0), "batch": result}
+    env.close()
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
 def evaluate_mode(args):
     """--evaluate: the evaluation inside the training call.  (1) ONE evaluation of 1024 envs x 100 steps ending in
     a synchronise: DeviceEvaluation.evaluate + results against the route before it, load_parameters + reset(seed) +
@@ -1415,8 +1521,12 @@ def main():
     ap.add_argument("--monitor", action="store_true", help="measure SACLearner.train with monitor=, log_every=10 against the same call without a monitor (see above)")
     ap.add_argument("--monitored-only", action="store_true", help="--monitor: run only the monitored call, --windows times (for a kernel trace)")
     ap.add_argument("--nstep", action="store_true", help="measure the gather of multi-step returns against the one-step gather and a torch composition, and the learner at n_steps 1 and 3")
+    ap.add_argument("--prioritized", action="store_true", help="measure the prioritized update against the uniform one (SACLearner.train, batch 65,536 and 4,096, H = 256), and the prioritized gather and urgym_per_terms on their own")
+    ap.add_argument("--prioritized-only", action="store_true", help="--prioritized: run only the prioritized native updates at batch 65,536, --windows x --launches of them (for a kernel trace)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.prioritized or args.prioritized_only:
+        return prioritized_mode(args)
     if args.nstep:
         return nstep_mode(args)
     if args.monitor:

@@ -60,6 +60,12 @@ def main():
     ap.add_argument("--n-steps", type=int, default=1,
                     help="multi-step returns: a target spans up to this many consecutive steps of an env and stops at an episode's end "
                          "(SB3's n_steps; above 1 needs --device-entropy)")
+    ap.add_argument("--prioritized", action="store_true",
+                    help="proportional prioritized replay on the device: draw each minibatch row in proportion to |TD error| ** alpha and "
+                         "weight the critics' gradient by the importance weights (needs --device-entropy; not with --n-steps above 1)")
+    ap.add_argument("--per-alpha", type=float, default=0.6, help="--prioritized: the priority exponent, in [0, 1]")
+    ap.add_argument("--per-beta", type=float, default=0.4, help="--prioritized: the importance exponent at the first update, in [0, 1]")
+    ap.add_argument("--per-beta-steps", type=int, default=100000, help="--prioritized: updates over which beta rises linearly to 1")
     ap.add_argument("--native", action="store_true",
                     help="run the whole loop, evaluations included, as ONE native call (SACLearner.train): no Python between the launches "
                          "(needs --device-entropy)")
@@ -89,7 +95,7 @@ def main():
     import torch
 
     from ur_gym_amd import make_vec
-    from ur_gym_amd.evaluation import DeviceActor, DeviceEvaluation, DeviceMonitor, DeviceReplay, evaluation_points, run_closed_loop_device, save_actor, warmup_iterations
+    from ur_gym_amd.evaluation import DeviceActor, DeviceEvaluation, DeviceMonitor, DevicePrioritizedReplay, DeviceReplay, evaluation_points, run_closed_loop_device, save_actor, warmup_iterations
     from ur_gym_amd.training import SACLearner, host_arrays
 
     if not torch.cuda.is_available():
@@ -100,9 +106,10 @@ def main():
     learner = SACLearner(env, seed=args.seed, hidden_width=args.hidden_width, batch_size=args.batch_size,
                          device_action_gradient=args.device_action_gradient, device_critic_gradient=args.device_critic_gradient,
                          device_actor_gradient=args.device_actor_gradient, device_optimizer=args.device_optimizer,
-                         device_entropy=args.device_entropy, n_steps=args.n_steps)
+                         device_entropy=args.device_entropy, n_steps=args.n_steps,
+                         **(dict(prioritized=True, per_beta=args.per_beta, per_beta_steps=args.per_beta_steps) if args.prioritized else {}))
     eval_actor = DeviceActor(host_arrays(learner.actor.tensors()), test_env)  # actors belong to the environment they were made for
-    replay = DeviceReplay(env, args.capacity)
+    replay = DevicePrioritizedReplay(env, args.capacity, alpha=args.per_alpha) if args.prioritized else DeviceReplay(env, args.capacity)
     updates, t0 = 0, time.perf_counter()
     best = dict(mean=-float("inf"), tensors=None)  # the Python route's own best_model
     if args.monitor and args.log_every < 1:

@@ -448,6 +448,39 @@ class SacNstep(C.Structure):
     _fields_ = [("n_steps", C.c_int32), ("reserved0", C.c_int32), ("discount", C.POINTER(C.c_float)), ("q_min_next", C.POINTER(C.c_float))]
 
 
+PER_FANOUT = 256  # URGYM_PER_FANOUT: the fan-out of the priority sums
+PER_TERMS_MAX_COUNT = 65536  # URGYM_PER_TERMS_MAX_COUNT
+PER_TAG = 0x50455200  # word 3 of the Philox counter of urgym_replay_sample_prioritized's draw
+
+
+class PerPriorities(C.Structure):
+    """urgym_per_priorities: the leaves [C][N] (priority ** alpha, 0 = never drawn), the float64 sum levels and the total, max_leaf[1]."""
+    _fields_ = [("capacity_steps", C.c_int32), ("reserved0", C.c_int32), ("leaf", C.POINTER(C.c_float)), ("sums", C.POINTER(C.c_double)),
+                ("max_leaf", C.POINTER(C.c_float))]
+
+
+class PerTermsArgs(C.Structure):
+    """urgym_per_terms_args: the drawn leaves and the total, q and y, the outputs w_raw, w, dq, and the write-back group (index,
+    new_leaf, priorities) given whole or not at all."""
+    _fields_ = [("count", C.c_int32), ("reserved0", C.c_int32), ("size", C.c_float), ("beta", C.c_float), ("alpha", C.c_float),
+                ("eps", C.c_float), ("scale", C.c_float), ("reserved1", C.c_float), ("leaf_in", C.POINTER(C.c_float)),
+                ("total", C.POINTER(C.c_double)), ("q", C.POINTER(C.c_float)), ("y", C.POINTER(C.c_float)), ("w_raw", C.POINTER(C.c_float)),
+                ("w", C.POINTER(C.c_float)), ("dq", C.POINTER(C.c_float)), ("index", C.POINTER(C.c_int64)), ("new_leaf", C.POINTER(C.c_float)),
+                ("priorities", PerPriorities)]
+
+
+class SacPrioritized(C.Structure):
+    """urgym_sac_prioritized: the structure, the beta schedule, the exponents and the [count] scratch of urgym_sac_train_prioritized."""
+    _fields_ = [("priorities", PerPriorities), ("beta0", C.c_double), ("beta_steps", C.c_int64), ("alpha", C.c_float), ("eps", C.c_float),
+                ("leaf", C.POINTER(C.c_float)), ("total", C.POINTER(C.c_double)), ("q", C.POINTER(C.c_float)), ("w_raw", C.POINTER(C.c_float)),
+                ("w", C.POINTER(C.c_float)), ("dq", C.POINTER(C.c_float)), ("new_leaf", C.POINTER(C.c_float)), ("reserved0", C.c_int64)]
+
+
+# urgym_sac_prioritized: name -> shape(count) of the float32 scratch (total is float64 [1])
+SAC_PRIORITIZED_SCRATCH = [("leaf", lambda M: (M,)), ("q", lambda M: (2, M)), ("w_raw", lambda M: (M,)), ("w", lambda M: (M,)), ("dq", lambda M: (2, M)),
+                           ("new_leaf", lambda M: (M,))]
+
+
 # Every symbol include/urgym.h declares (tests check that the built library exports each of them).
 EXPORTED_SYMBOLS = [
     "urgym_abi_version",
@@ -497,6 +530,12 @@ EXPORTED_SYMBOLS = [
     "urgym_replay_sample_nstep",
     "urgym_sac_entropy_step_nstep",
     "urgym_sac_train_nstep",
+    "urgym_per_sums_count",
+    "urgym_per_rebuild",
+    "urgym_per_fill",
+    "urgym_replay_sample_prioritized",
+    "urgym_per_terms",
+    "urgym_sac_train_prioritized",
     "urgym_actor_read_packed",
     "urgym_critic_read_packed",
     "urgym_refresh",

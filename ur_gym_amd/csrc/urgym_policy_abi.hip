@@ -1,6 +1,6 @@
 // urgym_policy_abi.hip — the learner's half of the C-ABI of include/urgym.h: actors (create / forward / sample / rollouts), the replay
-// ring, the weight reloads and their inverse (urgym_actor_unpack, urgym_critic_unpack), the twin critic and its two gradients, the actor's parameter gradients, the Adam steps, SAC's entropy step and loss terms, the training loop that composes them in one call (urgym_sac_train; its index arithmetic is urgym_sac_schedule.h), the evaluation inside that call (urgym_eval_stats, urgym_actor_snapshot, urgym_policy_evaluate, urgym_sac_train_evaluated; urgym_eval.h, urgym_eval_schedule.h), and the training-episode statistics inside it (urgym_monitor_fold, urgym_monitor_stats, urgym_sac_train_monitored; urgym_monitor.h), and the multi-step returns (urgym_replay_sample_nstep, urgym_sac_entropy_step_nstep, urgym_sac_train_nstep; urgym_nstep.h).  Host code only: every check is made here, before the first launch,
-// and every launch goes through urgym_actor.h, urgym_critic.h, urgym_replay.h, urgym_weights.h, urgym_adam.h, urgym_sac_terms.h, urgym_eval.h and urgym_monitor.h, or through do_step of urgym_hip.hip
+// ring, the weight reloads and their inverse (urgym_actor_unpack, urgym_critic_unpack), the twin critic and its two gradients, the actor's parameter gradients, the Adam steps, SAC's entropy step and loss terms, the training loop that composes them in one call (urgym_sac_train; its index arithmetic is urgym_sac_schedule.h), the evaluation inside that call (urgym_eval_stats, urgym_actor_snapshot, urgym_policy_evaluate, urgym_sac_train_evaluated; urgym_eval.h, urgym_eval_schedule.h), and the training-episode statistics inside it (urgym_monitor_fold, urgym_monitor_stats, urgym_sac_train_monitored; urgym_monitor.h), and the multi-step returns (urgym_replay_sample_nstep, urgym_sac_entropy_step_nstep, urgym_sac_train_nstep; urgym_nstep.h), and prioritized replay (urgym_per_sums_count, urgym_per_rebuild, urgym_per_fill, urgym_replay_sample_prioritized, urgym_per_terms; urgym_per.h).  Host code only: every check is made here, before the first launch,
+// and every launch goes through urgym_actor.h, urgym_critic.h, urgym_replay.h, urgym_weights.h, urgym_adam.h, urgym_sac_terms.h, urgym_eval.h, urgym_monitor.h and urgym_per.h, or through do_step of urgym_hip.hip
 // (urgym_handle.h).  No kernel lives in this unit, so adding a check here leaves the step kernels' object file alone.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -23,6 +23,7 @@
 #include "urgym_eval.h"
 #include "urgym_eval_schedule.h"
 #include "urgym_monitor.h"
+#include "urgym_per.h"
 
 using namespace urgym;
 
@@ -916,6 +917,137 @@ int urgym_replay_sample_nstep(void* handle, const urgym_replay_ring* ring, int o
   return launched(h);
 }
 
+}  // extern "C"
+
+// ---- prioritized replay (urgym_per.hip; urgym_per.h states the arithmetic): everything is checked here, before the first launch
+namespace {
+
+int check_priorities(Handle* h, const urgym_per_priorities* pri, const char* who, PerTree* out) {
+  static_assert(URGYM_PER_FANOUT == PER_FANOUT && URGYM_PER_TERMS_MAX_COUNT == PER_TERMS_MAX_COUNT, "include/urgym.h");
+  if (!pri) return fail_in(h, URGYM_ERR_ARG, who, "null priorities");
+  if (pri->capacity_steps <= 0) return fail_in(h, URGYM_ERR_ARG, who, "priorities: capacity_steps must be positive");
+  if (pri->reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "urgym_per_priorities.reserved0 must be 0");
+  if (!pri->leaf || !pri->sums || !pri->max_leaf) return fail_in(h, URGYM_ERR_ARG, who, "a priorities pointer is null (leaf, sums, max_leaf)");
+  const int64_t leaves = (int64_t)pri->capacity_steps * (int64_t)h->cfg.num_envs;
+  if ((leaves + PER_FANOUT - 1) / PER_FANOUT > (int64_t)INT32_MAX) return fail_in(h, URGYM_ERR_ARG, who, "more than 2^31 - 1 level-1 entries");
+  *out = PerTree{leaves, h->cfg.num_envs, pri->capacity_steps, pri->leaf, pri->sums, pri->max_leaf};
+  return URGYM_OK;
+}
+
+// the leaves of `num_steps` slots from first_slot on as at most two runs, and the level-1 entries that overlap each
+void per_fill_ranges(PerFill& f, int first_slot, int64_t num_steps) {
+  const int64_t N = f.tree.N, C = f.tree.capacity;
+  f.lo0 = f.hi0 = f.lo1 = f.hi1 = 0;
+  if (num_steps >= C) {
+    f.hi0 = f.tree.leaves;
+  } else if (first_slot + num_steps <= C) {
+    f.lo0 = first_slot * N, f.hi0 = (first_slot + num_steps) * N;
+  } else {
+    f.lo0 = first_slot * N, f.hi0 = f.tree.leaves;
+    f.hi1 = (first_slot + num_steps - C) * N;
+  }
+  f.block0 = f.lo0 / PER_FANOUT, f.blocks0 = f.hi0 > f.lo0 ? (f.hi0 - 1) / PER_FANOUT - f.block0 + 1 : 0;
+  f.block1 = f.lo1 / PER_FANOUT, f.blocks1 = f.hi1 > f.lo1 ? (f.hi1 - 1) / PER_FANOUT - f.block1 + 1 : 0;
+}
+
+int check_per_terms(Handle* h, const urgym_per_terms_args* args, const char* who, PerTermsCall* out) {
+  if (!args) return fail_in(h, URGYM_ERR_ARG, who, "null args");
+  const urgym_per_terms_args& a = *args;
+  if (a.reserved0 != 0 || a.reserved1 != 0.0f) return fail_in(h, URGYM_ERR_ARG, who, "urgym_per_terms_args.reserved0 and reserved1 must be 0");
+  if (a.count < 1 || a.count > PER_TERMS_MAX_COUNT) return fail_in(h, URGYM_ERR_ARG, who, "count must be in [1, URGYM_PER_TERMS_MAX_COUNT] (65536)");
+  if (!a.leaf_in || !a.total || !a.q || !a.y || !a.w_raw || !a.w || !a.dq)
+    return fail_in(h, URGYM_ERR_ARG, who, "a required pointer is null (leaf_in, total, q, y, w_raw, w, dq)");
+  if (!(a.alpha >= 0.0f && a.alpha <= 1.0f)) return fail_in(h, URGYM_ERR_ARG, who, "alpha must be in [0, 1]");  // refuses NaN too
+  if (!(a.beta >= 0.0f && a.beta <= 1.0f)) return fail_in(h, URGYM_ERR_ARG, who, "beta must be in [0, 1]");
+  if (!(a.eps > 0.0f && a.eps < INFINITY)) return fail_in(h, URGYM_ERR_ARG, who, "eps must be positive and finite");
+  if (!(a.size > 0.0f && a.size < INFINITY)) return fail_in(h, URGYM_ERR_ARG, who, "size must be positive and finite");
+  if (!(fabsf(a.scale) < INFINITY)) return fail_in(h, URGYM_ERR_ARG, who, "scale must be finite");
+  const urgym_per_priorities& p = a.priorities;
+  const int given = (a.index != nullptr) + (a.new_leaf != nullptr) + (p.leaf != nullptr) + (p.sums != nullptr) + (p.max_leaf != nullptr);
+  if (given != 0 && given != 5)
+    return fail_in(h, URGYM_ERR_ARG, who, "the write-back group is half given: index, new_leaf and the three pointers of priorities go together");
+  PerTermsCall& c = *out;
+  memset(&c, 0, sizeof(c));
+  if (given)
+    if (int rc = check_priorities(h, &p, who, &c.tree)) return rc;
+  c.count = a.count, c.size = a.size, c.beta = a.beta, c.alpha = a.alpha, c.eps = a.eps, c.scale = a.scale;
+  c.leaf_in = a.leaf_in, c.total = a.total, c.q = a.q, c.y = a.y, c.w_raw = a.w_raw, c.w = a.w, c.dq = a.dq;
+  c.index = a.index, c.new_leaf = a.new_leaf;
+  return URGYM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int urgym_per_sums_count(void* handle, int capacity_steps, uint64_t* doubles) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  const char* who = "urgym_per_sums_count";
+  if (!doubles) return fail_in(h, URGYM_ERR_ARG, who, "null doubles");
+  if (capacity_steps <= 0) return fail_in(h, URGYM_ERR_ARG, who, "capacity_steps must be positive");
+  const int64_t leaves = (int64_t)capacity_steps * (int64_t)h->cfg.num_envs;
+  if ((leaves + PER_FANOUT - 1) / PER_FANOUT > (int64_t)INT32_MAX) return fail_in(h, URGYM_ERR_ARG, who, "more than 2^31 - 1 level-1 entries");
+  *doubles = (uint64_t)per_shape<PER_FANOUT>(leaves).doubles;
+  return URGYM_OK;
+}
+
+int urgym_per_rebuild(void* handle, const urgym_per_priorities* pri, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  PerFill f;
+  memset(&f, 0, sizeof(f));
+  if (int rc = check_priorities(h, pri, "urgym_per_rebuild", &f.tree)) return rc;
+  f.blocks0 = per_shape<PER_FANOUT>(f.tree.leaves).count[1];  // every level-1 entry, no leaf written
+  HIP_TRY(h, hipSetDevice(h->device));
+  per_fill_launch(f, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_per_fill(void* handle, const urgym_per_priorities* pri, int first_slot, int num_steps, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  const char* who = "urgym_per_fill";
+  PerFill f;
+  memset(&f, 0, sizeof(f));
+  if (int rc = check_priorities(h, pri, who, &f.tree)) return rc;
+  if (first_slot < 0 || first_slot >= pri->capacity_steps) return fail_in(h, URGYM_ERR_ARG, who, "first_slot outside [0, capacity_steps)");
+  if (num_steps <= 0) return fail_in(h, URGYM_ERR_ARG, who, "num_steps must be positive");
+  per_fill_ranges(f, first_slot, num_steps);
+  HIP_TRY(h, hipSetDevice(h->device));
+  per_fill_launch(f, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_replay_sample_prioritized(void* handle, const urgym_replay_ring* ring, const urgym_per_priorities* pri, uint64_t seed, uint64_t draw, int count, const urgym_replay_batch* batch, float* leaf_out, double* total_out, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  const char* who = "urgym_replay_sample_prioritized";
+  PerGather g;
+  memset(&g, 0, sizeof(g));
+  // filled_steps = C and oldest_slot = 0: the leaves, not a window of slots, say which entries can be drawn
+  if (int rc = check_ring(h, ring, who)) return rc;
+  if (int rc = check_replay_sample(h, ring, 0, ring->capacity_steps, seed, draw, count, batch, who, &g.g)) return rc;
+  if (!batch->index) return fail_in(h, URGYM_ERR_ARG, who, "batch->index is required");
+  if (int rc = check_priorities(h, pri, who, &g.tree)) return rc;
+  if (pri->capacity_steps != ring->capacity_steps) return fail_in(h, URGYM_ERR_ARG, who, "priorities->capacity_steps is not the ring's");
+  if (!leaf_out || !total_out) return fail_in(h, URGYM_ERR_ARG, who, "leaf_out or total_out is null");
+  g.leaf_out = leaf_out, g.total_out = total_out;
+  HIP_TRY(h, hipSetDevice(h->device));
+  per_gather_launch(g, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_per_terms(void* handle, const urgym_per_terms_args* args, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  PerTermsCall c;
+  if (int rc = check_per_terms(h, args, "urgym_per_terms", &c)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  per_terms_launch(c, (hipStream_t)stream);
+  return launched(h);
+}
+
 int urgym_critic_create(void* handle, const urgym_critic_desc* desc, void** critic) {
   Handle* h = (Handle*)handle;
   if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
@@ -1022,7 +1154,8 @@ struct TrainHooks {
 
 // `nstep`: null = the one-step update; given (urgym_sac_train_nstep) = the update whose gather, third call and entropy step are the
 // multi-step ones
-int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, void* stream, const TrainHooks* hooks, const urgym_sac_nstep* nstep = nullptr);
+int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, void* stream, const TrainHooks* hooks, const urgym_sac_nstep* nstep = nullptr,
+                   const urgym_sac_prioritized* per = nullptr);
 
 }  // namespace
 
@@ -1034,7 +1167,8 @@ int urgym_sac_train(void* handle, const urgym_sac_learner* learner, const urgym_
 
 namespace {
 
-int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, void* stream, const TrainHooks* hooks, const urgym_sac_nstep* nstep) {
+int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, void* stream, const TrainHooks* hooks, const urgym_sac_nstep* nstep,
+                   const urgym_sac_prioritized* per) {
   Handle* h = (Handle*)handle;
   if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
   if (!learner) return fail_in(h, URGYM_ERR_ARG, who, "null learner");
@@ -1066,6 +1200,20 @@ int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learn
     if (!nstep->discount || !nstep->q_min_next) return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_nstep.discount or q_min_next is null");
     if (!L.ring.truncated) return fail_in(h, URGYM_ERR_ARG, who, "the ring keeps no truncated (an episode's end at the time limit could not be seen)");
   }
+  PerFill per_fill;
+  memset(&per_fill, 0, sizeof(per_fill));
+  if (per) {  // the structure's own refusals, whether or not the call holds an update
+    if (nstep) return fail_in(h, URGYM_ERR_ARG, who, "priorities with n_steps > 1 are out of scope (the multi-step gather draws its own indices)");
+    if (per->reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_prioritized.reserved0 must be 0");
+    if (int rc = check_priorities(h, &per->priorities, who, &per_fill.tree)) return rc;
+    if (per->priorities.capacity_steps != L.ring.capacity_steps) return fail_in(h, URGYM_ERR_ARG, who, "priorities.capacity_steps is not ring.capacity_steps");
+    if (!(per->beta0 >= 0.0 && per->beta0 <= 1.0)) return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_prioritized.beta0 must be in [0, 1]");
+    if (per->beta_steps < 1) return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_prioritized.beta_steps must be positive");
+    if (!(per->alpha >= 0.0f && per->alpha <= 1.0f)) return fail_in(h, URGYM_ERR_ARG, who, "alpha must be in [0, 1]");
+    if (!(per->eps > 0.0f && per->eps < INFINITY)) return fail_in(h, URGYM_ERR_ARG, who, "eps must be positive and finite");
+    if (!per->leaf || !per->total || !per->q || !per->w_raw || !per->w || !per->dq || !per->new_leaf)
+      return fail_in(h, URGYM_ERR_ARG, who, "a scratch pointer of urgym_sac_prioritized is null (leaf, total, q, w_raw, w, dq, new_leaf)");
+  }
 
   // ---- the checking halves, with the numbers of the first collection and the first update
   const int M = L.count, K = S.steps_per_iteration, G = S.updates_per_iteration;
@@ -1084,6 +1232,11 @@ int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learn
   auto collect = [&](int i, const SacIteration& it) {
     const urgym_sampling how{it.collect_mode, 0, L.seed, it.collect_first_draw};
     const int rc = rollout(h, collector, &how, K, RolloutSinks{nullptr, nullptr, &L.ring, it.collect_first_slot}, s);
+    if (!rc && per) {  // urgym_per_fill on the slots just written
+      per_fill_ranges(per_fill, it.collect_first_slot, K);
+      per_fill_launch(per_fill, s);
+      return train_stage(h, who, i, "per_fill");
+    }
     if (!rc) return rc;
     char was[160];
     snprintf(was, sizeof(was), "%s", h->err);
@@ -1111,6 +1264,13 @@ int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learn
       return rc;
   } else if (int rc = check_replay_sample(h, &L.ring, view.oldest_slot, view.filled_steps, L.update_seed, first.gather_draw, M, &L.batch, who, &gather)) {
     return rc;
+  }
+  PerGather per_gather;
+  memset(&per_gather, 0, sizeof(per_gather));
+  if (per) {  // urgym_replay_sample_prioritized
+    if (int rc = check_replay_sample(h, &L.ring, 0, L.ring.capacity_steps, L.update_seed, first.gather_draw, M, &L.batch, who, &per_gather.g)) return rc;
+    if (!L.batch.index) return fail_in(h, URGYM_ERR_ARG, who, "batch.index is required with priorities");
+    per_gather.tree = per_fill.tree, per_gather.leaf_out = per->leaf, per_gather.total_out = per->total;
   }
   const urgym_critic_rows next_rows{L.batch.next_observation, L.batch.next_achieved_goal, L.batch.next_desired_goal, L.next_actions};
   const urgym_critic_rows batch_rows{L.batch.observation, L.batch.achieved_goal, L.batch.desired_goal, L.batch.action};
@@ -1152,9 +1312,24 @@ int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learn
     cg.qf[net] = urgym_q_network_grad{(float*)g.w0, (float*)g.b0, (float*)g.w1, (float*)g.b1, (float*)g.w_q, (float*)g.b_q};
   }
   cg.q = L.q;
+  // with priorities: the online critics' q on the batch rows, then urgym_per_terms, and the gradients take its dq
+  Critic* online_q = nullptr;
+  CriticCall evaluate_q;
+  PerTermsCall per_terms;
+  if (per) {
+    const urgym_critic_out q_out{per->q, nullptr, nullptr};
+    if (int rc = check_critic_evaluate(h, L.online, &batch_rows, M, nullptr, &q_out, who, &online_q, &evaluate_q)) return rc;
+    urgym_per_terms_args ta;
+    memset(&ta, 0, sizeof(ta));
+    ta.count = M, ta.size = (float)((uint64_t)view.filled_steps * (uint64_t)h->cfg.num_envs), ta.beta = per_beta(per->beta0, first.adam_step, per->beta_steps);
+    ta.alpha = per->alpha, ta.eps = per->eps, ta.scale = scale;
+    ta.leaf_in = per->leaf, ta.total = per->total, ta.q = per->q, ta.y = L.y, ta.w_raw = per->w_raw, ta.w = per->w, ta.dq = per->dq;
+    ta.index = L.batch.index, ta.new_leaf = per->new_leaf, ta.priorities = per->priorities;
+    if (int rc = check_per_terms(h, &ta, who, &per_terms)) return rc;
+  }
   CriticBackwardCall critic_backward;
-  if (int rc = check_critic_parameter_gradients(h, L.online, &batch_rows, M, nullptr, L.y, scale, &cg, L.critic_workspace, L.critic_workspace_bytes, who, &online,
-                                                &critic_backward))
+  if (int rc = check_critic_parameter_gradients(h, L.online, &batch_rows, M, per ? per->dq : nullptr, per ? nullptr : L.y, scale, &cg, L.critic_workspace,
+                                                L.critic_workspace_bytes, who, &online, &critic_backward))
     return rc;
   CriticAdamStep critic_step;
   if (int rc = check_critic_adam(h, L.online, L.target, &L.critic_adam, &hp, L.tau, who, &critic_step)) return rc;
@@ -1205,7 +1380,10 @@ int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learn
       const SacUpdate up = sac_schedule_update(S, u);
       const AdamCoef coef = adam_coefficients(L.lr, L.beta1, L.beta2, L.eps, up.adam_step);  // urgym_adam_coefficients' own function
       gather.draw = up.gather_draw;
-      if (nstep)
+      per_gather.g.draw = up.gather_draw;
+      if (per)
+        per_gather_launch(per_gather, s);
+      else if (nstep)
         replay_gather_nstep_launch(gather_nstep, s);
       else
         replay_gather_launch(gather, s);
@@ -1226,6 +1404,14 @@ int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learn
         sac_entropy_launch(entropy, s);
       }
       if (int rc = train_stage(h, who, i, "sac_entropy_step")) return rc;
+      if (per) {
+        critic_launch(online_q, evaluate_q, s);
+        if (int rc = train_stage(h, who, i, "critic_evaluate (batch rows)")) return rc;
+        per_terms.size = (float)((uint64_t)it.filled_steps * (uint64_t)h->cfg.num_envs);
+        per_terms.beta = per_beta(per->beta0, up.adam_step, per->beta_steps);
+        per_terms_launch(per_terms, s);
+        if (int rc = train_stage(h, who, i, "per_terms")) return rc;
+      }
       critic_backward_launch(online, critic_backward, s);
       if (int rc = train_stage(h, who, i, "critic_parameter_gradients")) return rc;
       critic_adam_launch(critic_step.buf, &critic_step.target_buf, critic_step.T, coef, critic_step.tau, s);
@@ -1619,6 +1805,27 @@ int urgym_sac_train_nstep(void* handle, const urgym_sac_learner* learner, const 
     return sac_train_body(who, handle, learner, schedule, stream, &hooks, nstep);
   }
   return sac_train_body(who, handle, learner, schedule, stream, nullptr, nstep);
+}
+
+int urgym_sac_train_prioritized(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_prioritized* prioritized, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream) {
+  const char* who = "urgym_sac_train_prioritized";
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (!prioritized) return fail_in(h, URGYM_ERR_ARG, who, "null prioritized");
+  TrainEvaluation e;
+  e.h = h, e.learner = learner, e.schedule = schedule, e.evaluation = evaluation_or_NULL, e.s = (hipStream_t)stream, e.done = 0, e.who = who;
+  TrainMonitoring t;
+  t.h = h, t.learner = learner, t.schedule = schedule, t.monitoring = monitoring_or_NULL, t.s = (hipStream_t)stream, t.done = 0;
+  t.evaluation = evaluation_or_NULL ? &e : nullptr, t.who = who;
+  if (monitoring_or_NULL) {
+    const TrainHooks hooks{train_monitoring_check, train_monitoring_after, &t};
+    return sac_train_body(who, handle, learner, schedule, stream, &hooks, nullptr, prioritized);
+  }
+  if (evaluation_or_NULL) {
+    const TrainHooks hooks{train_evaluation_check, train_evaluation_after, &e};
+    return sac_train_body(who, handle, learner, schedule, stream, &hooks, nullptr, prioritized);
+  }
+  return sac_train_body(who, handle, learner, schedule, stream, nullptr, nullptr, prioritized);
 }
 
 }  // extern "C"

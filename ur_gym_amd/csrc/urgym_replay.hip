@@ -9,6 +9,7 @@
 #include "urgym_replay.h"
 
 #include "urgym_nstep.h"
+#include "urgym_replay_gather.h"
 #include "urgym_philox.h"
 
 namespace urgym {
@@ -55,24 +56,11 @@ __global__ void __launch_bounds__(STORE_THREADS) replay_store_kernel(const Repla
   store_rows(P.desired_goal, P.final_desired_goal, P.des, P.next_des, done, P.goal_dim, env0, cnt, tid);
 }
 
-// The gather: one wave takes 64 samples.  Lane l computes the ring entry of sample l (once per sample; it also moves that sample's
-// scalars: index, reward, flags -- written coalesced), then the wave works through its samples four at a time, a group of 16 lanes
-// per sample with the lanes along the row's floats.  16 lanes are one 64-byte run: a row is a few such runs (35 floats = 3 trips,
-// a goal or an action 1), and the four groups of a wave write four neighbouring output rows, i.e. one contiguous stretch.
-constexpr int GATHER_THREADS = 64;
-constexpr int GATHER_GROUP = 16;
-constexpr int GATHER_ROUNDS = GATHER_THREADS / (GATHER_THREADS / GATHER_GROUP);  // 16 rounds of 4 samples
-
-__device__ __forceinline__ void gather_row(float* __restrict__ dst, const float* __restrict__ src, int dim, size_t sample, size_t entry, int l) {
-  if (!dst) return;
-  for (int i = l; i < dim; i += GATHER_GROUP) dst[sample * dim + i] = src[entry * dim + i];
-}
-
+// The gather (urgym_replay_gather.h states the geometry and holds the body the prioritized draw of urgym_per.hip shares): lane l
+// computes the ring entry of sample l, then the wave copies its samples' rows.
 __global__ void __launch_bounds__(GATHER_THREADS) replay_gather_kernel(const ReplayGather P) {
   const int lane = threadIdx.x;
   const int base = blockIdx.x * GATHER_THREADS;  // count is an int: so is every sample number
-  const urgym_replay_ring& R = P.ring;
-  const urgym_replay_batch& B = P.batch;
   int64_t entry = 0;
   if (base + lane < P.count) {
     const int i = base + lane;
@@ -83,28 +71,9 @@ __global__ void __launch_bounds__(GATHER_THREADS) replay_gather_kernel(const Rep
     uint64_t slot = (uint64_t)P.oldest_slot + step;  // < 2 C
     if (slot >= (uint64_t)P.capacity) slot -= (uint64_t)P.capacity;
     entry = (int64_t)(slot * (uint64_t)P.N + env);
-    if (B.index) B.index[i] = entry;
-    if (B.reward) B.reward[i] = R.reward[entry];
-    if (B.terminated) B.terminated[i] = R.terminated[entry];
-    if (B.truncated) B.truncated[i] = R.truncated[entry];
-    if (B.is_success) B.is_success[i] = R.is_success[entry];
+    gather_scalars(P.ring, P.batch, i, entry);
   }
-  const int group = lane / GATHER_GROUP, l = lane % GATHER_GROUP;
-  const int lo = (int)(uint32_t)entry, hi = (int)(uint32_t)((uint64_t)entry >> 32);
-  for (int r = 0; r < GATHER_ROUNDS; r++) {
-    const int from = r * (GATHER_THREADS / GATHER_GROUP) + group;  // the lane that holds this group's sample
-    const uint32_t e_lo = (uint32_t)__shfl(lo, from), e_hi = (uint32_t)__shfl(hi, from);  // every lane takes part
-    const int sample = base + from;
-    if (sample >= P.count) continue;
-    const size_t e = (size_t)(((uint64_t)e_hi << 32) | e_lo), s = (size_t)sample;
-    gather_row(B.observation, R.observation, P.obs_dim, s, e, l);
-    gather_row(B.achieved_goal, R.achieved_goal, P.goal_dim, s, e, l);
-    gather_row(B.desired_goal, R.desired_goal, P.goal_dim, s, e, l);
-    gather_row(B.action, R.action, 6, s, e, l);
-    gather_row(B.next_observation, R.next_observation, P.obs_dim, s, e, l);
-    gather_row(B.next_achieved_goal, R.next_achieved_goal, P.goal_dim, s, e, l);
-    gather_row(B.next_desired_goal, R.next_desired_goal, P.goal_dim, s, e, l);
-  }
+  gather_rows(P, base, lane, entry);
 }
 
 // The gather of multi-step returns (urgym_replay_sample_nstep): replay_gather_kernel's geometry and draw, word for word.  The sample's

@@ -420,6 +420,121 @@ def nstep_batch(ring_arrays, oldest_slot, filled, seed, draw, count, n_steps, ga
     return out
 
 
+def per_sums(leaf, fanout=None):
+    """The sum levels of the prioritized replay restated from ur_gym_amd/csrc/urgym_per.h in numpy float64.  `leaf`: float32, any
+    shape (taken flat: the ring's entry order).  Level 0 is the leaves; entry b of level k + 1 is the ascending float64 sum, from +0.0,
+    of entries fanout b .. fanout b + fanout - 1 of level k (``np.cumsum`` in float64 is that sum); levels are added until one has at
+    most `fanout` entries; the total is the ascending sum of that level.  Returns ``levels`` (a list of float64 arrays, level 1
+    first), ``total`` (np.float64) and ``flat`` (the levels and the total as the device lays them out)."""
+    from . import _abi
+
+    F = int(_abi.PER_FANOUT if fanout is None else fanout)
+    leaf = np.asarray(leaf)
+    if leaf.dtype != np.float32 or F < 2:
+        raise ValueError(f"leaf must be float32 and fanout at least 2, got {leaf.dtype}, {F}")
+    v, levels = leaf.reshape(-1).astype(np.float64), []
+    while True:
+        blocks = -(-v.size // F)
+        padded = np.zeros(blocks * F, np.float64)  # an absent entry adds +0.0: no change
+        padded[:v.size] = v
+        v = np.cumsum(padded.reshape(blocks, F), axis=1)[:, -1] + 0.0  # + 0.0: the sum starts from +0.0 (a block of one -0.0)
+        levels.append(v)
+        if blocks <= F:
+            break
+    padded = np.zeros(F, np.float64)
+    padded[:v.size] = v
+    total = np.float64(np.cumsum(padded)[-1] + 0.0)
+    return dict(levels=levels, total=total, flat=np.concatenate(levels + [np.array([total])]))
+
+
+def per_words(seed, draw, count):
+    """The 64-bit words of urgym_replay_sample_prioritized's draw: (w0 << 32) | w1 of Philox4x32-10 at the counter
+    (i, draw lo, draw hi, PER_TAG), uint64 [count]."""
+    from . import _abi
+
+    seed, draw = int(seed), int(draw)
+    key = (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
+    w = philox4x32_10(key, (np.arange(int(count), dtype=np.uint64), np.uint64(draw & 0xFFFFFFFF), np.uint64((draw >> 32) & 0xFFFFFFFF),
+                            np.uint64(_abi.PER_TAG)))
+    return (w[0].astype(np.uint64) << np.uint64(32)) | w[1].astype(np.uint64)
+
+
+def per_descent(leaf, words, fanout=None, sums=None):
+    """The descent of urgym_per.h restated in numpy float64: for each 64-bit word (``per_words``) the leaf it draws.  u = (w >> 11)
+    2^-53, t = u total, then from the top level down over the children of the chosen node in ascending order with s = +0.0:
+    s2 = s + v[k]; t < s2 takes k and t = t - s; else s = s2.  If no child is taken: the last child with v > 0, else the first, and t
+    stays.  `sums`: a ``per_sums`` result of the same leaves (formed here if None).  Returns int64 [len(words)]."""
+    from . import _abi
+
+    F = int(_abi.PER_FANOUT if fanout is None else fanout)
+    leaf = np.asarray(leaf).reshape(-1)
+    sums = per_sums(leaf, F) if sums is None else sums
+    below = [leaf.astype(np.float64)] + list(sums["levels"])  # below[k]: level k
+    prefix = []
+    for v in below:  # the running s2 of every block, once: np.cumsum is the chain s2 = s + v[k] from s = +0.0
+        blocks = -(-v.size // F)
+        padded = np.zeros(blocks * F, np.float64)
+        padded[:v.size] = v
+        prefix.append(np.cumsum(padded.reshape(blocks, F), axis=1) + 0.0)
+    total, out = sums["total"], np.zeros(len(words), np.int64)
+    for i, w in enumerate(np.asarray(words, dtype=np.uint64)):
+        t = np.float64(int(w) >> 11) * np.float64(2.0 ** -53) * total
+        node = 0
+        for k in range(len(below) - 1, -1, -1):  # the top level has one block
+            v, span = below[k], min(F, below[k].size - node * F)
+            s2 = prefix[k][node]
+            j = int(np.searchsorted(s2[:span], t, side="right"))  # the first k with t < s2[k]: s2 never decreases
+            if j < span:
+                t = t - (s2[j - 1] if j else np.float64(0.0))
+            else:
+                positive = np.nonzero(v[node * F:node * F + span] > 0)[0]
+                j = int(positive[-1]) if positive.size else 0
+            node = node * F + j
+        out[i] = node
+    return out
+
+
+def per_beta(beta0, step, beta_steps):
+    """beta of the update at Adam step `step` (1, 2, ...): beta0 + (1 - beta0) min(1, step / beta_steps) in float64, rounded to
+    float32 once (per_beta of urgym_per.h)."""
+    f = float(int(step)) / float(int(beta_steps))
+    return np.float32(float(beta0) + (1.0 - float(beta0)) * (f if f < 1.0 else 1.0))
+
+
+def per_terms(leaf_in, total, size, beta, q, y, scale, eps, alpha, w_raw, new_leaf=None, index=None, leaf=None, max_leaf=None):
+    """urgym_per_terms restated from include/urgym.h in numpy, one float32 operation per line.  `w_raw` [count] and `new_leaf` [count]
+    are INPUTS, as alpha is to ``entropy_step``: the device's powf and numpy's are different functions.  Returns a dict with ``x``
+    (powf's argument of w_raw) and ``p`` (that of new_leaf), ``wmax``, ``w``, ``dq`` [2, count], ``replaced`` (the rows whose powf
+    cannot be finite: their new_leaf must be the old max_leaf) and, with the write-back group (`new_leaf`, `index`, `leaf` flat or
+    [C, N], `max_leaf`), ``leaf`` (a copy: every drawn entry at the largest new_leaf of its rows) and ``max_leaf``."""
+    f = np.float32
+    q, y, w_raw = np.asarray(q), np.asarray(y), np.asarray(w_raw)
+    leaf_in = np.asarray(leaf_in)
+    if any(a.dtype != f for a in (q, y, w_raw, leaf_in)) or q.shape != (2, y.size):
+        raise ValueError("leaf_in, q [2, count], y and w_raw must be float32")
+    size, beta, scale, eps, alpha = f(size), f(beta), f(scale), f(eps), f(alpha)
+    with np.errstate(all="ignore"):
+        prob = (leaf_in.astype(np.float64) / np.float64(total)).astype(f)
+        x = size * prob
+        wmax = np.fmax.reduce(w_raw, initial=f(0))
+        w = w_raw / wmax
+        e = q - y[None, :]
+        g = e * scale
+        dq = g * w[None, :]
+        td = np.fmax(np.abs(e[0]), np.abs(e[1]))
+        p = td + eps
+    assert all(a.dtype == f for a in (x, w, dq, p))  # no intermediate was promoted
+    out = dict(x=x, p=p, wmax=wmax, w=w, dq=dq, replaced=~np.isfinite(p) & (alpha > 0))
+    if new_leaf is not None:
+        new_leaf, after = np.asarray(new_leaf), np.array(leaf, dtype=f).reshape(-1)
+        index = np.asarray(index, dtype=np.int64)
+        after[index] = 0
+        np.maximum.at(after, index, new_leaf)
+        out["leaf"] = after.reshape(np.shape(leaf))
+        out["max_leaf"] = np.fmax(f(max_leaf), np.fmax.reduce(new_leaf, initial=f(0)))
+    return out
+
+
 def policy_terms(alpha, *, dqmin_da=None, scale=None, q=None, y=None, log_prob=None, q_min=None):
     """urgym_sac_policy_terms restated from include/urgym.h in numpy float32, the means by ``ordered_sum``; `alpha` as in
     ``entropy_step``.  Groups, each whole or absent: (`dqmin_da` [count, 6], `scale`) gives ``d_action``; (`q` [2, count], `y`
@@ -1228,6 +1343,173 @@ class DeviceReplay:
         batch["target"] = self.env.critic_values(critic, batch["next_actions"], rows=nxt, reward=batch["rewards"], terminated=batch["terminated"],
                                                  log_prob=batch["next_log_prob"], gamma=gamma, ent_coef=ent_coef)["target"]
         return batch
+
+
+class DevicePrioritizedReplay(DeviceReplay):
+    """``DeviceReplay`` with proportional priorities on the device (include/urgym.h, "prioritized replay"; urgym_per.h).  ``leaf``
+    [C, N] float32 holds priority ** alpha per ring entry (0 = never drawn: unfilled slots are never sampled), ``sums`` the float64
+    sum levels and the total (``per_sums(...)["flat"]``), ``max_leaf`` [1] what a new transition gets (1 at the start).  ``collect``
+    also fills the slots it wrote; ``sample_prioritized`` draws through the sums (``per_descent``); ``terms`` forms the importance
+    weights and the critics' weighted upstream gradient and writes the new priorities back (``per_terms``).  The sums are never
+    saved: ``load_state_dict`` rebuilds them, bitwise what they were."""
+
+    def __init__(self, env, capacity_steps, alpha=0.6, eps=1e-6):
+        import ctypes as C
+
+        import torch
+
+        from . import _native
+
+        super().__init__(env, capacity_steps)
+        self.alpha, self.eps = self.check_per_args(alpha, eps)
+        doubles = C.c_uint64(0)
+        _native.check(env.lib.urgym_per_sums_count(env._h, self.capacity, C.byref(doubles)), env._h)
+        self.leaf = torch.zeros((self.capacity, env.num_envs), dtype=torch.float32, device=env.device)
+        self.sums = torch.zeros((int(doubles.value),), dtype=torch.float64, device=env.device)
+        self.max_leaf = torch.ones((1,), dtype=torch.float32, device=env.device)
+        self._pri = self.priorities_struct()
+
+    def priorities_struct(self):
+        import ctypes as C
+
+        from . import _abi
+
+        return _abi.PerPriorities(self.capacity, 0, C.cast(self.leaf.data_ptr(), C.POINTER(C.c_float)),
+                                  C.cast(self.sums.data_ptr(), C.POINTER(C.c_double)), C.cast(self.max_leaf.data_ptr(), C.POINTER(C.c_float)))
+
+    @staticmethod
+    def check_per_args(alpha, eps):
+        """Raises ValueError for what urgym_per_terms refuses about alpha (outside [0, 1]) and eps (not positive and finite in float32).
+        Returns both as floats.  Needs no GPU."""
+        a, e = np.float32(alpha), np.float32(eps)
+        if not 0.0 <= a <= 1.0:
+            raise ValueError(f"alpha must be in [0, 1], got {alpha}")
+        if not (e > 0 and np.isfinite(e)):
+            raise ValueError(f"eps must be positive and finite in float32, got {eps}")
+        return float(alpha), float(eps)
+
+    def state_dict(self, include_data=True):
+        """``DeviceReplay.state_dict`` plus, under ``priorities``: alpha, eps, max_leaf and (with data) the leaves [C, N] as they lie.
+        The sums are not saved."""
+        out = super().state_dict(include_data)
+        out["priorities"] = dict(alpha=self.alpha, eps=self.eps, max_leaf=self.max_leaf.cpu().numpy())
+        if include_data:
+            out["priorities"]["leaf"] = self.leaf.cpu().numpy()
+        return out
+
+    def check_state_dict(self, state):
+        super().check_state_dict(state)
+        pri = state.get("priorities")
+        if pri is None:
+            raise ValueError("DevicePrioritizedReplay.load_state_dict: the state holds no priorities (a uniform ring's?)")
+        for k in ("alpha", "eps"):
+            if float(pri[k]) != getattr(self, k):
+                raise ValueError(f"DevicePrioritizedReplay.load_state_dict: {k} is {pri[k]} in the state, {getattr(self, k)} here")
+        m = np.asarray(pri["max_leaf"])
+        if m.dtype != np.float32 or m.shape != (1,):
+            raise ValueError(f"DevicePrioritizedReplay.load_state_dict: max_leaf must be float32 [1], got {m.dtype} {m.shape}")
+        if state["include_data"]:
+            a = np.asarray(pri["leaf"])
+            if a.dtype != np.float32 or a.shape != tuple(self.leaf.shape):
+                raise ValueError(f"DevicePrioritizedReplay.load_state_dict: leaf must be float32 {tuple(self.leaf.shape)}, got {a.dtype} {a.shape}")
+
+    def load_state_dict(self, state):
+        """``DeviceReplay.load_state_dict``, then the leaves and max_leaf, then ``rebuild``: the sums are bitwise what they were.  A
+        state without data leaves an empty structure (every leaf 0)."""
+        import torch
+
+        super().load_state_dict(state)
+        pri = state["priorities"]
+        self.max_leaf.copy_(torch.from_numpy(np.ascontiguousarray(pri["max_leaf"])))
+        if state["include_data"]:
+            self.leaf.copy_(torch.from_numpy(np.ascontiguousarray(pri["leaf"])))
+        else:
+            self.leaf.zero_()
+        self.rebuild()
+
+    def rebuild(self):
+        """Every sum level and the total from the leaves as they lie (urgym_per_rebuild: two launches)."""
+        import ctypes as C
+
+        from . import _native
+
+        env = self.env
+        _native.check(env.lib.urgym_per_rebuild(env._h, C.byref(self._pri), env._stream()), env._h)
+
+    def fill(self, first_slot, num_steps):
+        """The leaves of `num_steps` slots from `first_slot` on become ``max_leaf`` and the sums are repaired (urgym_per_fill: two
+        launches)."""
+        import ctypes as C
+
+        from . import _native
+
+        env = self.env
+        self.check_args(self.capacity, num_steps=num_steps, first_slot=first_slot)
+        _native.check(env.lib.urgym_per_fill(env._h, C.byref(self._pri), int(first_slot), int(num_steps), env._stream()), env._h)
+
+    def collect(self, actor, num_steps, sample=None):
+        """``DeviceReplay.collect``, then ``fill`` on the slots just written: a new transition is drawn at the largest priority seen."""
+        first = self.cursor
+        super().collect(actor, num_steps, sample=sample)
+        self.fill(first, num_steps)
+
+    def sample_prioritized(self, batch_size, seed, draw):
+        """``sample`` with each row drawn in proportion to its leaf, one launch (urgym_replay_sample_prioritized): the dict of
+        ``sample`` plus ``leaf`` (float32 [B]: the leaf each row was drawn at) and ``total`` (float64 [1]).  The rows are
+        ``per_descent(leaf, per_words(seed, draw, B))``.  Nothing is synchronised."""
+        import ctypes as C
+
+        import torch
+
+        from . import _abi, _native
+        from .vector_env import _TORCH_DTYPE
+
+        self.check_args(self.capacity, batch_size=batch_size)
+        env, B = self.env, int(batch_size)
+        flat = {name: torch.empty((B,) + tuple(shape(1, 1, env.obs_dim, env.goal_dim)[2:]), dtype=_TORCH_DTYPE[ct], device=env.device)
+                for name, ct, shape, _ in _abi.REPLAY_RING_FIELDS}
+        batch = _abi.ReplayBatch()
+        for name, ct, _, _ in _abi.REPLAY_RING_FIELDS:
+            setattr(batch, name, C.cast(flat[name].data_ptr(), C.POINTER(ct)))
+        index = torch.empty((B,), dtype=torch.int64, device=env.device)
+        batch.index = C.cast(index.data_ptr(), C.POINTER(C.c_int64))
+        leaf, total = torch.empty((B,), dtype=torch.float32, device=env.device), torch.empty((1,), dtype=torch.float64, device=env.device)
+        _native.check(env.lib.urgym_replay_sample_prioritized(env._h, C.byref(self._ring), C.byref(self._pri), int(seed), int(draw), B, C.byref(batch),
+                                                              leaf.data_ptr(), total.data_ptr(), env._stream()), env._h)
+        rows = ("observation", "achieved_goal", "desired_goal")
+        return {"observations": {k: flat[k] for k in rows}, "next_observations": {k: flat["next_" + k] for k in rows}, "actions": flat["action"],
+                "rewards": flat["reward"], "terminated": flat["terminated"].view(torch.bool), "truncated": flat["truncated"].view(torch.bool),
+                "is_success": flat["is_success"].view(torch.bool), "index": index, "leaf": leaf, "total": total}
+
+    def terms(self, batch, q, y, beta, scale, write_back=True, out=None):
+        """urgym_per_terms on a ``sample_prioritized`` batch: `q` float32 [2, B] (``env.critic_values`` of the batch rows), `y`
+        float32 [B] (the target), `beta` and `scale` floats.  Returns (or fills `out`) ``w_raw``, ``w`` [B], ``dq`` [2, B] and, with
+        `write_back`, ``new_leaf`` [B]; then the leaves of ``batch["index"]``, ``max_leaf`` and the sums are updated (three launches;
+        one without `write_back`).  ``per_terms`` restates it."""
+        import ctypes as C
+
+        import torch
+
+        from . import _abi, _native
+
+        env, B = self.env, int(batch["index"].shape[0])
+        fp = lambda t: C.cast(t.data_ptr(), C.POINTER(C.c_float))  # noqa: E731
+        want = {"q": (q, (2, B)), "y": (y, (B,)), "leaf": (batch["leaf"], (B,))}
+        for name, (t, shape) in want.items():
+            if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != env.device:
+                raise ValueError(f"{name} must be a contiguous float32 {shape} tensor on {env.device}")
+        out = {} if out is None else out
+        for name, shape in (("w_raw", (B,)), ("w", (B,)), ("dq", (2, B))) + ((("new_leaf", (B,)),) if write_back else ()):
+            if name not in out:
+                out[name] = torch.empty(shape, dtype=torch.float32, device=env.device)
+        a = _abi.PerTermsArgs(count=B, size=float(np.float32(self.filled * env.num_envs)), beta=float(beta), alpha=self.alpha, eps=self.eps,
+                              scale=float(scale), leaf_in=fp(batch["leaf"]), total=C.cast(batch["total"].data_ptr(), C.POINTER(C.c_double)),
+                              q=fp(q), y=fp(y), w_raw=fp(out["w_raw"]), w=fp(out["w"]), dq=fp(out["dq"]))
+        if write_back:
+            a.index, a.new_leaf = C.cast(batch["index"].data_ptr(), C.POINTER(C.c_int64)), fp(out["new_leaf"])
+            a.priorities = self._pri
+        _native.check(env.lib.urgym_per_terms(env._h, C.byref(a), env._stream()), env._h)
+        return out
 
 
 def run_closed_loop_device(env, actor, max_steps=100):

@@ -68,6 +68,9 @@ from .evaluation import ACTOR_ARRAYS, CRITIC_ARRAYS, LOG_STD_ARRAYS, LOG_STD_MAX
 SAC_DEFAULTS = dict(gamma=0.95, tau=0.005, learning_rate=1e-4, batch_size=256, learning_starts=100, hidden_width=256, target_entropy=-6.0,
                     ent_coef_init=1.0, device_action_gradient=False, device_critic_gradient=False,
                     device_actor_gradient=False, device_optimizer=False, device_entropy=False, n_steps=1)
+# Prioritized replay: the options of SACLearner(prioritized=True).  Kept apart from SAC_DEFAULTS: a run without
+# priorities holds none of them in its checkpoint.  beta of the update at Adam step t is evaluation.per_beta(per_beta, t, per_beta_steps).
+PER_DEFAULTS = dict(prioritized=False, per_beta=0.4, per_beta_steps=100000)
 
 
 def _mlp(n_in, hidden, n_out=None):
@@ -147,13 +150,28 @@ def _optimizer_from_host(tree, opt, device):
 class SACLearner:
     """Torch modules for the actor and the twin critic with Adam on each and on ``log_ent_coef``; a DeviceActor that follows the
     torch actor and a target DeviceCritic that follows the torch critic by Polyak averaging.  `env`: a UR5ReachVectorEnv with
-    auto_reset.  Keyword arguments override SAC_DEFAULTS."""
+    auto_reset.  Keyword arguments override SAC_DEFAULTS and PER_DEFAULTS: ``prioritized=True`` (with ``per_beta``, ``per_beta_steps``; needs
+    all five ``device_*`` options and a ``DevicePrioritizedReplay``) draws each minibatch in proportion to the transitions' priorities and
+    weights the critics' gradient by the importance weights; not together with ``n_steps`` > 1."""
 
     def __init__(self, env, seed=0, **overrides):
-        unknown = [k for k in overrides if k not in SAC_DEFAULTS]
+        unknown = [k for k in overrides if k not in SAC_DEFAULTS and k not in PER_DEFAULTS]
         if unknown:
-            raise TypeError(f"unknown hyperparameters {unknown}; available: {sorted(SAC_DEFAULTS)}")
-        hp = dict(SAC_DEFAULTS, **overrides)
+            raise TypeError(f"unknown hyperparameters {unknown}; available: {sorted(SAC_DEFAULTS) + sorted(PER_DEFAULTS)}")
+        hp = dict(SAC_DEFAULTS, **PER_DEFAULTS)
+        hp.update(overrides)
+        if not isinstance(hp["prioritized"], bool):
+            raise ValueError(f"prioritized must be True or False, got {hp['prioritized']!r}")
+        if hp["prioritized"]:
+            if not hp["device_entropy"]:
+                raise ValueError("prioritized=True needs all five device_* options (the weights and the new priorities are formed between the device's launches)")
+            if int(hp["n_steps"]) != 1:
+                raise ValueError("prioritized=True with n_steps > 1 is out of scope: the multi-step gather draws its own indices")
+            if not 0.0 <= float(hp["per_beta"]) <= 1.0:
+                raise ValueError(f"per_beta must be in [0, 1], got {hp['per_beta']!r}")
+            steps = hp["per_beta_steps"]
+            if isinstance(steps, bool) or int(steps) != steps or int(steps) < 1:
+                raise ValueError(f"per_beta_steps must be a positive integer, got {steps!r}")
         n_steps = hp["n_steps"]
         if isinstance(n_steps, bool) or int(n_steps) != n_steps or not 1 <= int(n_steps) <= 32:
             raise ValueError(f"n_steps must be an integer in [1, 32], got {n_steps!r}")
@@ -323,6 +341,8 @@ class SACLearner:
         if not 0 <= int(draw) < 2 ** 63:
             raise ValueError("with device_actor_gradient the draw must be below 2**63 (its top bit marks the policy's own draw)")
         M, gamma, n_steps = int(hp["batch_size"]), float(hp["gamma"]), int(hp["n_steps"])
+        if hp.get("prioritized"):
+            return self._update_prioritized(replay, seed, draw)
         batch = replay.sample_targets(self.device_actor, self.target, M, seed, draw, gamma, 0.0, **({} if n_steps == 1 else dict(n_steps=n_steps)))
         rows = batch["observations"]
         how = dict(mode="gaussian", seed=seed, first_draw=int(draw) | 1 << 63)
@@ -352,6 +372,43 @@ class SACLearner:
         self.last_update = dict(log_prob=log_prob, y=es["y"], q=got["q"], q_min=grad["q_min"], dqmin_da=grad["dqmin_da"])
         return dict(es["losses"])
 
+    def _update_prioritized(self, replay, seed, draw):
+        """``_update_on_device`` on a ``DevicePrioritizedReplay``: the draw goes through the priority sums, and between the entropy step
+        and the critics' gradients come the online critics' q on the batch rows (urgym_critic_evaluate) and urgym_per_terms -- the
+        importance weights at ``per_beta`` of this Adam step, the weighted upstream gradient dq, the new priorities written back and
+        the sums repaired.  Seventeen launches (nineteen above 1024 rows).  The critic loss reported stays the unweighted one."""
+        from .evaluation import DevicePrioritizedReplay, per_beta
+
+        if not isinstance(replay, DevicePrioritizedReplay):
+            raise ValueError("prioritized=True needs a DevicePrioritizedReplay")
+        hp, env, st, es = self.hp, self.env, self.adam_state, self.entropy_state
+        M, gamma = int(hp["batch_size"]), float(hp["gamma"])
+        batch = replay.sample_prioritized(M, seed, draw)
+        rows, nxt = batch["observations"], batch["next_observations"]
+        next_actions, next_log_prob = env.policy_actions(self.device_actor, sample=dict(mode="gaussian", seed=seed, first_draw=draw), rows=nxt)
+        target = env.critic_values(self.target, next_actions, rows=nxt, reward=batch["rewards"], terminated=batch["terminated"], log_prob=next_log_prob,
+                                   gamma=gamma, ent_coef=0.0)["target"]
+        how = dict(mode="gaussian", seed=seed, first_draw=int(draw) | 1 << 63)
+        action_pi, log_prob = env.policy_actions(self.device_actor, sample=how, rows=rows)
+        st["step"] += 1
+        adam = dict(lr=hp["learning_rate"], betas=st["betas"], eps=st["eps"], step=st["step"])
+        env.entropy_step((self.log_ent_coef, es["exp_avg"], es["exp_avg_sq"]), log_prob, hp["target_entropy"], ent_coef_out=es["ent_coef"],
+                         loss_out=es["ent_coef_loss"], target=target, next_log_prob=next_log_prob, terminated=batch["terminated"],
+                         gamma=gamma, y_out=es["y"], d_log_prob_out=self.actor_d_log_prob, scale=1.0 / M, **adam)
+        q = env.critic_values(self.online, batch["actions"], rows=rows)["q"]
+        per = replay.terms(batch, q, es["y"], per_beta(hp["per_beta"], st["step"], hp["per_beta_steps"]), 1.0 / M)
+        got = env.critic_parameter_gradients(self.online, batch["actions"], dq=per["dq"], rows=rows, out=self.critic_grads, workspace=self.critic_workspace)
+        env.critic_adam_step(self.online, self.critic.tensors(), self.critic_grads, *st["critic"], target=self.target, tau=hp["tau"], **adam)
+        grad = env.critic_action_gradient(self.online, action_pi, rows=rows)
+        env.policy_terms(es["ent_coef"], M, dqmin_da=grad["dqmin_da"], scale=-1.0 / M, d_action_out=self.actor_d_action, q=got["q"], y=es["y"],
+                         critic_loss_out=es["critic_loss"], log_prob=log_prob, q_min=grad["q_min"], actor_loss_out=es["actor_loss"])
+        env.actor_parameter_gradients(self.device_actor, sample=how, rows=rows, d_action=self.actor_d_action, d_log_prob=self.actor_d_log_prob,
+                                      out=self.actor_grads, workspace=self.actor_workspace)
+        env.actor_adam_step(self.device_actor, self.actor.tensors(), self.actor_grads, *st["actor"], **adam)
+        self.last_update = dict(log_prob=log_prob, y=es["y"], q=got["q"], q_min=grad["q_min"], dqmin_da=grad["dqmin_da"], q_evaluated=q, index=batch["index"],
+                                leaf=batch["leaf"], total=batch["total"], **per)
+        return dict(es["losses"])
+
     def _train_binding(self, replay):
         """The scratch of ``train`` and the checked struct of the native call, made once per (learner, replay) pair."""
         if self._train is not None and self._train["replay"] is replay:
@@ -374,7 +431,11 @@ class SACLearner:
             critic_workspace=self.critic_workspace, log_ent_coef=self.log_ent_coef, exp_avg=es["exp_avg"], exp_avg_sq=es["exp_avg_sq"], replay=replay,
             batch=batch, scratch=scratch, count=M, seed=self.seed, update_seed=0, gamma=hp["gamma"], tau=hp["tau"],
             target_entropy=hp["target_entropy"], lr=hp["learning_rate"], betas=st["betas"], eps=st["eps"])
-        self._train = dict(replay=replay, binding=binding, scratch=scratch, nstep=None)
+        self._train = dict(replay=replay, binding=binding, scratch=scratch, batch=batch, nstep=None, prioritized=None)
+        if hp.get("prioritized"):  # the scratch of urgym_sac_train_prioritized; like the batch scratch, never saved
+            per = {name: torch.zeros(shape(M), dtype=torch.float32, device=dev) for name, shape in _abi.SAC_PRIORITIZED_SCRATCH}
+            per.update(total=torch.zeros((1,), dtype=torch.float64, device=dev), replay=replay, beta0=float(hp["per_beta"]), beta_steps=int(hp["per_beta_steps"]))
+            self._train["prioritized"] = per
         if int(hp["n_steps"]) > 1:  # the two scratch tensors of urgym_sac_train_nstep; like the batch scratch, never saved
             self._train["nstep"] = dict(n_steps=int(hp["n_steps"]), discount=torch.zeros((M,), dtype=torch.float32, device=dev),
                                         q_min_next=torch.zeros((M,), dtype=torch.float32, device=dev))
@@ -403,7 +464,9 @@ class SACLearner:
         (``monitor.record(monitor.iterations)``).  ``monitor.iterations`` and ``monitor.count`` advance, so that split calls place
         records where one call would.  Both or neither: one alone raises ValueError.
 
-        With ``n_steps`` > 1 the ONE native call is urgym_sac_train_nstep, with the evaluations and the monitor where given."""
+        With ``n_steps`` > 1 the ONE native call is urgym_sac_train_nstep, with the evaluations and the monitor where given.  With
+        ``prioritized`` it is urgym_sac_train_prioritized on a ``DevicePrioritizedReplay``, the same way: every collection is followed
+        by the fill of its slots, every update is ``update``'s seventeen launches."""
         from .evaluation import warmup_iterations
 
         if (evaluation is None) != (eval_every is None):
@@ -412,6 +475,8 @@ class SACLearner:
             raise ValueError("train: monitor and log_every go together (an interval needs something to record with, and the reverse)")
         if self.entropy_state is None:
             raise ValueError("train needs device_entropy=True (the native loop is the thirteen launches of the update on the device)")
+        if self.hp.get("prioritized") and not hasattr(replay, "priorities_struct"):
+            raise ValueError("prioritized=True needs a DevicePrioritizedReplay")
         hp, env, st = self.hp, self.env, self.adam_state
         n, K, G = int(iterations), int(steps_per_iteration), int(updates_per_iteration)
         tr = self._train_binding(replay)
@@ -424,7 +489,8 @@ class SACLearner:
                       collect_first_draw=self.draw, update_first_draw=int(first_draw), first_step=st["step"] + 1,
                       **({} if evaluation is None else dict(evaluation=evaluation, eval_every=eval_every)),
                       **({} if monitor is None else dict(monitor=monitor, log_every=log_every)),
-                      **({} if tr["nstep"] is None else dict(nstep=tr["nstep"])))
+                      **({} if tr["nstep"] is None else dict(nstep=tr["nstep"])),
+                      **({} if tr["prioritized"] is None else dict(prioritized=tr["prioritized"])))
         self.env_steps += n * K
         self.draw += n * K
         st["step"] += updates
@@ -433,6 +499,10 @@ class SACLearner:
         if updates:
             sc = tr["scratch"]
             self.last_update = dict(log_prob=sc["log_prob"], y=sc["y"], q=sc["q"], q_min=sc["q_min"], dqmin_da=sc["dqmin_da"])
+            if tr["prioritized"] is not None:
+                per = tr["prioritized"]
+                self.last_update.update(q_evaluated=per["q"], index=tr["batch"]["index"], leaf=per["leaf"], total=per["total"],
+                                        **{k: per[k] for k in ("w_raw", "w", "dq", "new_leaf")})
         return {"critic_loss": losses[0], "actor_loss": losses[1], "ent_coef_loss": losses[2]}
 
     # ------------------------------------------------------------------------------------------------ checkpoints
@@ -444,7 +514,7 @@ class SACLearner:
     def _saved_hp(self):
         """The hyperparameters as a checkpoint holds them: ``n_steps`` only where it is not 1, so that the file of a one-step run is
         what it was before the option existed (``check_state_dict`` reads an absent ``n_steps`` as 1)."""
-        return {k: v for k, v in self.hp.items() if k != "n_steps" or int(v) != 1}
+        return {k: v for k, v in self.hp.items() if (k != "n_steps" or int(v) != 1) and (k not in PER_DEFAULTS or self.hp.get("prioritized"))}
 
     def state_dict(self):
         """Everything the learner is, as host arrays and scalars: the actor's eight and the critics' twelve parameter tensors, the
@@ -516,6 +586,11 @@ class SACLearner:
             saved = dict(n_steps=1, **state["hp"]) if "n_steps" not in state["hp"] else state["hp"]  # a one-step run's file holds no n_steps
             if k not in saved or saved[k] != self.hp[k]:
                 raise ValueError(f"load_state_dict: {k} is {saved.get(k)!r} in the checkpoint, {self.hp[k]!r} here")
+        for k, default in PER_DEFAULTS.items():  # a file without priorities holds none of the three
+            if k != "prioritized" and not self.hp.get("prioritized") and not state["hp"].get("prioritized"):
+                continue
+            if state["hp"].get(k, default) != self.hp.get(k, default):
+                raise ValueError(f"load_state_dict: {k} is {state['hp'].get(k, default)!r} in the checkpoint, {self.hp.get(k, default)!r} here")
         for name, mine in (("adam_state", self.adam_state), ("entropy_state", self.entropy_state)):
             if (state[name] is None) != (mine is None):
                 raise ValueError(f"load_state_dict: {name} is {'absent' if state[name] is None else 'present'} in the checkpoint and the reverse here")

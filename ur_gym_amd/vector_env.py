@@ -799,7 +799,7 @@ class UR5ReachVectorEnv:
 
     def sac_train(self, learner, critic_loss, actor_loss, ent_coef_loss, *, first_slot, filled_steps, num_iterations, steps_per_iteration=1,
                   updates_per_iteration=1, uniform_iterations=0, idle_iterations=0, collect_first_draw=0, update_first_draw=0, first_step=1,
-                  evaluation=None, eval_every=None, monitor=None, log_every=None, nstep=None):
+                  evaluation=None, eval_every=None, monitor=None, log_every=None, nstep=None, prioritized=None):
         """``num_iterations`` x (a collection of ``steps_per_iteration`` steps, ``updates_per_iteration`` SAC updates) in ONE native
         call (urgym_sac_train): the launches of ``collect`` and of the thirteen calls of an update, bit for bit, without returning to
         Python in between.  `learner`: what ``sac_learner`` returned, or a dict of its keyword arguments (then built and checked here).
@@ -821,7 +821,12 @@ class UR5ReachVectorEnv:
 
         With `nstep` (a dict: ``n_steps`` in [2, 32] and the float32 [count] scratch tensors ``discount`` and ``q_min_next``) the call
         is urgym_sac_train_nstep, with the evaluations and the monitor if those are given: every update gathers multi-step returns
-        (``DeviceReplay.sample_targets(n_steps=)``) and forms y by ``entropy_step_nstep``.  Without it nothing changes."""
+        (``DeviceReplay.sample_targets(n_steps=)``) and forms y by ``entropy_step_nstep``.  Without it nothing changes.
+
+        With `prioritized` (a dict: ``replay``, the ``DevicePrioritizedReplay`` the learner's ring belongs to, ``beta0``,
+        ``beta_steps``, and the scratch tensors of ``_abi.SAC_PRIORITIZED_SCRATCH`` and ``total``, float64 [1]) the call is
+        urgym_sac_train_prioritized, with the evaluations and the monitor if those are given: every collection is followed by the
+        fill of its slots and every update draws through the priorities and writes the new ones back.  Not together with `nstep`."""
         from .evaluation import DeviceEvaluation, DeviceMonitor, evaluation_points, monitor_points, training_schedule
 
         who = "sac_train"
@@ -872,11 +877,29 @@ class UR5ReachVectorEnv:
             count = int(L.count)
             N_ = _abi.SacNstep(int(n_steps), 0, self._float_ptr(who, "nstep['discount']", nstep["discount"], (count,)),
                                self._float_ptr(who, "nstep['q_min_next']", nstep["q_min_next"], (count,)))
+        if prioritized is not None:
+            if nstep is not None:
+                raise ValueError(f"{who}: priorities together with multi-step returns are out of scope (the multi-step gather draws its own indices)")
+            rp, count = prioritized["replay"], int(L.count)
+            total = prioritized["total"]
+            if total.dtype != torch.float64 or tuple(total.shape) != (1,) or total.device != torch.device(self.device):
+                raise ValueError(f"{who}: prioritized['total'] must be a float64 [1] tensor on {self.device}")
+            P_ = _abi.SacPrioritized(priorities=rp.priorities_struct(), beta0=float(prioritized["beta0"]), beta_steps=int(prioritized["beta_steps"]),
+                                     alpha=rp.alpha, eps=rp.eps, total=C.cast(total.data_ptr(), C.POINTER(C.c_double)))
+            for name, shape in _abi.SAC_PRIORITIZED_SCRATCH:
+                setattr(P_, name, self._float_ptr(who, f"prioritized[{name!r}]", prioritized[name], shape(count)))
         for name, t in zip(_abi.SAC_LEARNER_LOSSES, (critic_loss, actor_loss, ent_coef_loss)):
             setattr(L, name, self._float_ptr(who, name, t, (updates,)))
         S = _abi.SacSchedule(*[sched[name] for name, _ in _abi.SacSchedule._fields_])
         try:
-            if nstep is not None:
+            if prioritized is not None:
+                _native.check(self.lib.urgym_sac_train_prioritized(self._h, C.byref(L), C.byref(S), C.byref(P_), C.byref(E_) if evaluation is not None else None,
+                                                                   C.byref(M_) if monitor is not None else None, self._stream()), self._h)
+                if monitor is not None:
+                    monitor.advance(sched["num_iterations"], len(logged))
+                if evaluation is not None:
+                    evaluation.advance(len(points))
+            elif nstep is not None:
                 _native.check(self.lib.urgym_sac_train_nstep(self._h, C.byref(L), C.byref(S), C.byref(N_), C.byref(E_) if evaluation is not None else None,
                                                              C.byref(M_) if monitor is not None else None, self._stream()), self._h)
                 if monitor is not None:
