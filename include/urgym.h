@@ -1445,6 +1445,78 @@ typedef struct urgym_sac_prioritized {
  * draws its own indices): there is no such call. */
 int urgym_sac_train_prioritized(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_prioritized* prioritized, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream);
 
+/* ---- hindsight experience replay (SB3's HerReplayBuffer): a drawn transition gets, as its goal, a pose its own
+ * episode reached at the same or a later step, and is re-scored against it.  The ring holds everything this needs (next_achieved_goal,
+ * next_desired_goal, the three flags; consecutive steps of an env lie N entries apart), so nothing is collected differently and
+ * nothing joins the ring or a checkpoint.  Added WITHIN ABI version 4: no struct above changed, URGYM_ABI_VERSION did not move, the
+ * new symbols (urgym_replay_sample_hindsight, urgym_sac_train_hindsight) are found by lookup.  The rule, as
+ * ur_gym_amd/csrc/urgym_her.h states it and ur_gym_amd.evaluation.hindsight_pick / hindsight_batch restate it, for row i:
+ *
+ * Draw.  The Philox word of urgym_replay_sample unchanged (same key, same counter, last word 0x52504C00): w[0], w[1] give e,
+ * p = e / N, env and index exactly as there, batch.index is bitwise what urgym_replay_sample writes.  HER spends w[2] and w[3], which
+ * that call leaves unused, and only them.
+ * Relabel decision.  Relabel iff (uint64)w[2] < relabel_threshold, in [0, 2^32]; the host forms it with integers as
+ * (n_sampled_goal << 32) / (n_sampled_goal + 1) (SB3's n_sampled_goal = 4: a ratio of 0.8).  A row that is not relabelled is bitwise
+ * the row urgym_replay_sample gathers, in every output.
+ * Episode window.  H = min(horizon, filled_steps - p), entry_k = ((oldest_slot + p + k) % C) N + env, F = the smallest k + 1 <= H with
+ * terminated[entry_k] | truncated[entry_k] non-zero, else H.  No entry at or past age filled_steps is read.  An episode still in
+ * progress ends, for this purpose, at the newest slot (SB3 samples finished episodes only; the multi-step window does the same as here).
+ * Goal entry g = entry_j.  URGYM_HER_GOAL_FUTURE: j = ((uint64)w[3] F) >> 32 (SB3's `future`, own step included).
+ * URGYM_HER_GOAL_FINAL: j = F - 1.  URGYM_HER_GOAL_OWN (a diagnostic): no entry; the "new" goal is next_desired_goal[e], so the whole
+ * re-scoring path runs with the goal the row already had.  Otherwise the new goal is next_achieved_goal[g], goal_dim float32 words
+ * copied bitwise.
+ * Rows of a relabelled sample.  desired_goal and next_desired_goal become the new goal; observation and next_observation are the
+ * ring's rows with floats [12, 12 + goal_dim) replaced by it (the goal lies there in all four env kinds); achieved_goal,
+ * next_achieved_goal, action, truncated and index come from e unchanged; goal_index holds g, or -1 where the row was not relabelled or
+ * the strategy is OWN.
+ * Re-scoring, in float64 with every operation rounded on its own, the weights and thresholds being the handle's urgym_config:
+ *   coll = terminated[e] && !is_success[e]; succ0 = is_success[e] (the stored flag); a = next_achieved_goal[e], g1 the new goal,
+ *   g0 = next_desired_goal[e], each widened to double; d = distance(a, g1), th = angular_distance(a + 3, g1 + 3) for goal_dim == 6,
+ *   else 0 (the step kernel's own functions); d0, th0 the same against g0; succ = d < distance_threshold, and for goal_dim == 6 also
+ *   th < ori_threshold.
+ *   Ori and Obs: G(s, d, th) = (((s ? w_success : 0) + (coll ? w_collision : 0)) + w_distance d) + w_orientation th, and
+ *     r' = ((double)r - G(succ0, d0, th0)) + G(succ, d, th).
+ *   Dyn and Sta: coll: r' = w_collision; else succ: r' = w_success; else r' = (w_distance d + w_orientation th) + S with
+ *     S = ((double)r - w_distance d0) - w_orientation th0 if !succ0, else 0.
+ *   batch.reward = (float)r', terminated' = succ || coll, is_success' = terminated' && !coll.
+ * The bracketed remainder is the part of the stored reward that does not depend on the goal (the link-distance shaping; for Ori the
+ * rounding residue of the float64 goal).  A NaN in a goal reaches that row's reward and nothing else.  pose_terms[i] = {d, th, d0,
+ * th0} (zeros where the row was not relabelled): sincos and acos of the device library are restated bitwise by no host, so the
+ * restatement takes them as inputs. */
+#define URGYM_HER_HORIZON_MAX 256
+#define URGYM_HER_GOAL_FUTURE 0
+#define URGYM_HER_GOAL_FINAL 1
+#define URGYM_HER_GOAL_OWN 2
+
+typedef struct urgym_replay_hindsight {
+  uint64_t relabel_threshold; /* in [0, 2^32]: 0 relabels no row, 2^32 every row */
+  int32_t strategy;           /* URGYM_HER_GOAL_* */
+  int32_t horizon;            /* in [1, URGYM_HER_HORIZON_MAX]: the env's max_episode_steps */
+  int64_t* goal_index;        /* [count] or NULL */
+  double* pose_terms;         /* [count][4] or NULL */
+  int64_t reserved0;          /* must be 0 */
+} urgym_replay_hindsight;
+
+/* urgym_replay_sample with the rule above, in ONE launch on `stream`: no allocation, no host synchronisation.  Refused
+ * (URGYM_ERR_ARG, nothing launched, nothing written): everything urgym_replay_sample refuses; hindsight == NULL; relabel_threshold >
+ * 2^32; strategy outside 0..2; horizon outside [1, URGYM_HER_HORIZON_MAX]; a non-zero reserved field; a ring without truncated or
+ * without is_success. */
+int urgym_replay_sample_hindsight(void* handle, const urgym_replay_ring* ring, int oldest_slot, int filled_steps, uint64_t seed, uint64_t draw, int count, const urgym_replay_batch* batch, const urgym_replay_hindsight* hindsight, void* stream);
+
+typedef struct urgym_sac_hindsight {
+  uint64_t relabel_threshold; /* as urgym_replay_hindsight */
+  int32_t strategy;           /* URGYM_HER_GOAL_FUTURE or URGYM_HER_GOAL_FINAL */
+  int32_t horizon;
+  int64_t reserved0;          /* must be 0 */
+} urgym_sac_hindsight;
+
+/* urgym_sac_train, urgym_sac_train_evaluated or urgym_sac_train_monitored -- by which of evaluation_or_NULL and monitoring_or_NULL is
+ * given -- with the gather of each update replaced by urgym_replay_sample_hindsight(..., {relabel_threshold, strategy, horizon}):
+ * still 13 launches per update (15 above 1024 rows), the same schedule, draws, step numbers and loss slots.  Everything is validated
+ * before the first launch, also where the call holds no update.  Refused besides what those calls and the gather refuse: hindsight ==
+ * NULL, URGYM_HER_GOAL_OWN (a diagnostic of the gather, not a way to train). */
+int urgym_sac_train_hindsight(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_hindsight* hindsight, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream);
+
 /* ---- weights back to the device tensors (a checkpoint: the reference's train.py:31-36 continues a saved run, and the TARGET critic
  * exists only as a packed buffer, blended in place by urgym_critic_load(tau < 1) and urgym_critic_adam_step(target)).  The packing
  * map of ur_gym_amd/csrc/urgym_pack_map.h run the other way, on the device: every element of every destination tensor -- DEVICE

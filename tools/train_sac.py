@@ -66,6 +66,11 @@ def main():
     ap.add_argument("--per-alpha", type=float, default=0.6, help="--prioritized: the priority exponent, in [0, 1]")
     ap.add_argument("--per-beta", type=float, default=0.4, help="--prioritized: the importance exponent at the first update, in [0, 1]")
     ap.add_argument("--per-beta-steps", type=int, default=100000, help="--prioritized: updates over which beta rises linearly to 1")
+    ap.add_argument("--hindsight", action="store_true",
+                    help="hindsight experience replay on the device (SB3's HerReplayBuffer): the gather gives a share of each minibatch's rows "
+                         "a goal their own episode reached later and re-scores them (needs --device-entropy; not with --n-steps above 1 or --prioritized)")
+    ap.add_argument("--her-n-sampled-goal", type=int, default=4, help="--hindsight: relabelled rows per kept row (4: a share of 0.8)")
+    ap.add_argument("--her-strategy", default="future", choices=("future", "final"), help="--hindsight: which later pose of the episode becomes the goal")
     ap.add_argument("--native", action="store_true",
                     help="run the whole loop, evaluations included, as ONE native call (SACLearner.train): no Python between the launches "
                          "(needs --device-entropy)")
@@ -107,7 +112,8 @@ def main():
                          device_action_gradient=args.device_action_gradient, device_critic_gradient=args.device_critic_gradient,
                          device_actor_gradient=args.device_actor_gradient, device_optimizer=args.device_optimizer,
                          device_entropy=args.device_entropy, n_steps=args.n_steps,
-                         **(dict(prioritized=True, per_beta=args.per_beta, per_beta_steps=args.per_beta_steps) if args.prioritized else {}))
+                         **(dict(prioritized=True, per_beta=args.per_beta, per_beta_steps=args.per_beta_steps) if args.prioritized else {}),
+                         **(dict(hindsight=True, her_n_sampled_goal=args.her_n_sampled_goal, her_strategy=args.her_strategy) if args.hindsight else {}))
     eval_actor = DeviceActor(host_arrays(learner.actor.tensors()), test_env)  # actors belong to the environment they were made for
     replay = DevicePrioritizedReplay(env, args.capacity, alpha=args.per_alpha) if args.prioritized else DeviceReplay(env, args.capacity)
     updates, t0 = 0, time.perf_counter()

@@ -448,6 +448,24 @@ class SacNstep(C.Structure):
     _fields_ = [("n_steps", C.c_int32), ("reserved0", C.c_int32), ("discount", C.POINTER(C.c_float)), ("q_min_next", C.POINTER(C.c_float))]
 
 
+HER_HORIZON_MAX = 256  # URGYM_HER_HORIZON_MAX: the longest episode window of urgym_replay_sample_hindsight
+HER_GOAL_FUTURE, HER_GOAL_FINAL, HER_GOAL_OWN = 0, 1, 2  # URGYM_HER_GOAL_*
+HER_STRATEGIES = {"future": HER_GOAL_FUTURE, "final": HER_GOAL_FINAL, "own": HER_GOAL_OWN}
+HER_GOAL_OFFSET = 12  # the goal lies at floats [12, 12 + goal_dim) of an observation row in all four env kinds
+
+
+class ReplayHindsight(C.Structure):
+    """urgym_replay_hindsight: the relabel threshold, the strategy and the horizon of urgym_replay_sample_hindsight and its two
+    optional outputs."""
+    _fields_ = [("relabel_threshold", C.c_uint64), ("strategy", C.c_int32), ("horizon", C.c_int32), ("goal_index", C.POINTER(C.c_int64)),
+                ("pose_terms", C.POINTER(C.c_double)), ("reserved0", C.c_int64)]
+
+
+class SacHindsight(C.Structure):
+    """urgym_sac_hindsight: the rule of urgym_sac_train_hindsight's gathers."""
+    _fields_ = [("relabel_threshold", C.c_uint64), ("strategy", C.c_int32), ("horizon", C.c_int32), ("reserved0", C.c_int64)]
+
+
 PER_FANOUT = 256  # URGYM_PER_FANOUT: the fan-out of the priority sums
 PER_TERMS_MAX_COUNT = 65536  # URGYM_PER_TERMS_MAX_COUNT
 PER_TAG = 0x50455200  # word 3 of the Philox counter of urgym_replay_sample_prioritized's draw
@@ -536,6 +554,8 @@ EXPORTED_SYMBOLS = [
     "urgym_replay_sample_prioritized",
     "urgym_per_terms",
     "urgym_sac_train_prioritized",
+    "urgym_replay_sample_hindsight",
+    "urgym_sac_train_hindsight",
     "urgym_actor_read_packed",
     "urgym_critic_read_packed",
     "urgym_refresh",

@@ -113,6 +113,10 @@ def lib():
     L.urgym_per_terms.argtypes = [C.c_void_p, C.POINTER(_abi.PerTermsArgs), C.c_void_p]
     L.urgym_sac_train_prioritized.argtypes = [C.c_void_p, C.POINTER(_abi.SacLearner), C.POINTER(_abi.SacSchedule), C.POINTER(_abi.SacPrioritized),
                                               C.POINTER(_abi.SacEvaluation), C.POINTER(_abi.SacMonitoring), C.c_void_p]
+    L.urgym_replay_sample_hindsight.argtypes = [C.c_void_p, C.POINTER(_abi.ReplayRing), C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_int,
+                                                C.POINTER(_abi.ReplayBatch), C.POINTER(_abi.ReplayHindsight), C.c_void_p]
+    L.urgym_sac_train_hindsight.argtypes = [C.c_void_p, C.POINTER(_abi.SacLearner), C.POINTER(_abi.SacSchedule), C.POINTER(_abi.SacHindsight),
+                                            C.POINTER(_abi.SacEvaluation), C.POINTER(_abi.SacMonitoring), C.c_void_p]
     L.urgym_actor_read_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.urgym_critic_read_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.urgym_refresh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]

@@ -1,5 +1,5 @@
 // urgym_policy_abi.hip — the learner's half of the C-ABI of include/urgym.h: actors (create / forward / sample / rollouts), the replay
-// ring, the weight reloads and their inverse (urgym_actor_unpack, urgym_critic_unpack), the twin critic and its two gradients, the actor's parameter gradients, the Adam steps, SAC's entropy step and loss terms, the training loop that composes them in one call (urgym_sac_train; its index arithmetic is urgym_sac_schedule.h), the evaluation inside that call (urgym_eval_stats, urgym_actor_snapshot, urgym_policy_evaluate, urgym_sac_train_evaluated; urgym_eval.h, urgym_eval_schedule.h), and the training-episode statistics inside it (urgym_monitor_fold, urgym_monitor_stats, urgym_sac_train_monitored; urgym_monitor.h), and the multi-step returns (urgym_replay_sample_nstep, urgym_sac_entropy_step_nstep, urgym_sac_train_nstep; urgym_nstep.h), and prioritized replay (urgym_per_sums_count, urgym_per_rebuild, urgym_per_fill, urgym_replay_sample_prioritized, urgym_per_terms; urgym_per.h).  Host code only: every check is made here, before the first launch,
+// ring, the weight reloads and their inverse (urgym_actor_unpack, urgym_critic_unpack), the twin critic and its two gradients, the actor's parameter gradients, the Adam steps, SAC's entropy step and loss terms, the training loop that composes them in one call (urgym_sac_train; its index arithmetic is urgym_sac_schedule.h), the evaluation inside that call (urgym_eval_stats, urgym_actor_snapshot, urgym_policy_evaluate, urgym_sac_train_evaluated; urgym_eval.h, urgym_eval_schedule.h), and the training-episode statistics inside it (urgym_monitor_fold, urgym_monitor_stats, urgym_sac_train_monitored; urgym_monitor.h), and the multi-step returns (urgym_replay_sample_nstep, urgym_sac_entropy_step_nstep, urgym_sac_train_nstep; urgym_nstep.h), and prioritized replay (urgym_per_sums_count, urgym_per_rebuild, urgym_per_fill, urgym_replay_sample_prioritized, urgym_per_terms; urgym_per.h), and hindsight experience replay (urgym_replay_sample_hindsight, urgym_sac_train_hindsight; urgym_her.h).  Host code only: every check is made here, before the first launch,
 // and every launch goes through urgym_actor.h, urgym_critic.h, urgym_replay.h, urgym_weights.h, urgym_adam.h, urgym_sac_terms.h, urgym_eval.h, urgym_monitor.h and urgym_per.h, or through do_step of urgym_hip.hip
 // (urgym_handle.h).  No kernel lives in this unit, so adding a check here leaves the step kernels' object file alone.
 #include <hip/hip_runtime.h>
@@ -17,6 +17,7 @@
 #include "urgym_weights.h"
 #include "urgym_replay.h"
 #include "urgym_nstep.h"
+#include "urgym_her.h"
 #include "urgym_adam.h"
 #include "urgym_sac_terms.h"
 #include "urgym_sac_schedule.h"
@@ -489,6 +490,32 @@ int check_replay_sample_nstep(Handle* h, const urgym_replay_ring* ring, int olde
   return URGYM_OK;
 }
 
+// urgym_replay_sample_hindsight: check_replay_sample's refusals first, then the rule's
+int check_replay_sample_hindsight(Handle* h, const urgym_replay_ring* ring, int oldest_slot, int filled_steps, uint64_t seed, uint64_t draw, int count,
+                                  const urgym_replay_batch* batch, const urgym_replay_hindsight* hindsight, const char* who, ReplayGatherHindsight* out) {
+  static_assert(URGYM_HER_HORIZON_MAX == HER_HORIZON_MAX && URGYM_HER_GOAL_FUTURE == HER_GOAL_FUTURE && URGYM_HER_GOAL_FINAL == HER_GOAL_FINAL &&
+                    URGYM_HER_GOAL_OWN == HER_GOAL_OWN,
+                "include/urgym.h");
+  if (int rc = check_replay_sample(h, ring, oldest_slot, filled_steps, seed, draw, count, batch, who, &out->g)) return rc;
+  if (!hindsight) return fail_in(h, URGYM_ERR_ARG, who, "null hindsight");
+  const urgym_replay_hindsight& q = *hindsight;
+  if (q.relabel_threshold > (uint64_t)1 << 32) return fail_in(h, URGYM_ERR_ARG, who, "relabel_threshold must be in [0, 2^32]");
+  if (q.strategy < HER_GOAL_FUTURE || q.strategy > HER_GOAL_OWN) return fail_in(h, URGYM_ERR_ARG, who, "strategy must be URGYM_HER_GOAL_FUTURE, _FINAL or _OWN");
+  if (q.horizon < 1 || q.horizon > HER_HORIZON_MAX) return fail_in(h, URGYM_ERR_ARG, who, "horizon must be in [1, URGYM_HER_HORIZON_MAX] (256)");
+  if (q.reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "urgym_replay_hindsight.reserved0 must be 0");
+  if (!ring->truncated || !ring->is_success)
+    return fail_in(h, URGYM_ERR_ARG, who, "the ring keeps no truncated or no is_success (an episode's end and a collision could not be seen)");
+  if (h->obs_dim < HER_GOAL_OFFSET + h->goal_dim || (h->goal_dim != 3 && h->goal_dim != 6))
+    return fail_in(h, URGYM_ERR_ARG, who, "the observation row holds no goal at floats [12, 12 + goal_dim)");
+  const urgym_config& c = h->cfg;
+  out->filled_steps = filled_steps, out->strategy = q.strategy, out->horizon = q.horizon, out->relabel_threshold = q.relabel_threshold;
+  out->distance_threshold = c.distance_threshold, out->ori_threshold = c.ori_threshold, out->w_collision = c.w_collision;
+  out->w_success = c.w_success, out->w_distance = c.w_distance, out->w_orientation = c.w_orientation;
+  out->additive = c.env_kind == URGYM_ENV_ORI || c.env_kind == URGYM_ENV_OBS;
+  out->goal_index = q.goal_index, out->pose_terms = q.pose_terms;
+  return URGYM_OK;
+}
+
 // urgym_sac_entropy_step_nstep: check_entropy_step's refusals on the other target group
 int check_entropy_step_nstep(Handle* h, const urgym_sac_entropy_nstep_args* args, const urgym_adam_hyper* hp, const char* who, SacEntropyNstepCall* out) {
   if (!args) return fail_in(h, URGYM_ERR_ARG, who, "null args");
@@ -917,6 +944,16 @@ int urgym_replay_sample_nstep(void* handle, const urgym_replay_ring* ring, int o
   return launched(h);
 }
 
+int urgym_replay_sample_hindsight(void* handle, const urgym_replay_ring* ring, int oldest_slot, int filled_steps, uint64_t seed, uint64_t draw, int count, const urgym_replay_batch* batch, const urgym_replay_hindsight* hindsight, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  ReplayGatherHindsight g;
+  if (int rc = check_replay_sample_hindsight(h, ring, oldest_slot, filled_steps, seed, draw, count, batch, hindsight, "urgym_replay_sample_hindsight", &g)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  replay_gather_hindsight_launch(g, (hipStream_t)stream);
+  return launched(h);
+}
+
 }  // extern "C"
 
 // ---- prioritized replay (urgym_per.hip; urgym_per.h states the arithmetic): everything is checked here, before the first launch
@@ -1153,9 +1190,9 @@ struct TrainHooks {
 };
 
 // `nstep`: null = the one-step update; given (urgym_sac_train_nstep) = the update whose gather, third call and entropy step are the
-// multi-step ones
+// multi-step ones.  `her`: given (urgym_sac_train_hindsight) = the update whose gather is urgym_replay_sample_hindsight
 int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, void* stream, const TrainHooks* hooks, const urgym_sac_nstep* nstep = nullptr,
-                   const urgym_sac_prioritized* per = nullptr);
+                   const urgym_sac_prioritized* per = nullptr, const urgym_sac_hindsight* her = nullptr);
 
 }  // namespace
 
@@ -1168,7 +1205,7 @@ int urgym_sac_train(void* handle, const urgym_sac_learner* learner, const urgym_
 namespace {
 
 int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, void* stream, const TrainHooks* hooks, const urgym_sac_nstep* nstep,
-                   const urgym_sac_prioritized* per) {
+                   const urgym_sac_prioritized* per, const urgym_sac_hindsight* her) {
   Handle* h = (Handle*)handle;
   if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
   if (!learner) return fail_in(h, URGYM_ERR_ARG, who, "null learner");
@@ -1199,6 +1236,17 @@ int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learn
     if (nstep->reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_nstep.reserved0 must be 0");
     if (!nstep->discount || !nstep->q_min_next) return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_nstep.discount or q_min_next is null");
     if (!L.ring.truncated) return fail_in(h, URGYM_ERR_ARG, who, "the ring keeps no truncated (an episode's end at the time limit could not be seen)");
+  }
+  ReplayGatherHindsight gather_her;
+  urgym_replay_hindsight her_rule;
+  memset(&her_rule, 0, sizeof(her_rule));
+  if (her) {  // the rule's own refusals, whether or not the call holds an update: the gather's checks on the ring as it stands
+    if (nstep || per) return fail_in(h, URGYM_ERR_ARG, who, "hindsight with multi-step returns or priorities is out of scope");
+    if (her->strategy == HER_GOAL_OWN) return fail_in(h, URGYM_ERR_ARG, who, "URGYM_HER_GOAL_OWN is a diagnostic of the gather, not a way to train");
+    if (her->reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_hindsight.reserved0 must be 0");
+    her_rule.relabel_threshold = her->relabel_threshold, her_rule.strategy = her->strategy, her_rule.horizon = her->horizon;
+    if (L.count <= 0) return fail_in(h, URGYM_ERR_ARG, who, "count must be positive");
+    if (int rc = check_replay_sample_hindsight(h, &L.ring, 0, 1, L.update_seed, 0, L.count, &L.batch, &her_rule, who, &gather_her)) return rc;
   }
   PerFill per_fill;
   memset(&per_fill, 0, sizeof(per_fill));
@@ -1265,6 +1313,9 @@ int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learn
   } else if (int rc = check_replay_sample(h, &L.ring, view.oldest_slot, view.filled_steps, L.update_seed, first.gather_draw, M, &L.batch, who, &gather)) {
     return rc;
   }
+  if (her)
+    if (int rc = check_replay_sample_hindsight(h, &L.ring, view.oldest_slot, view.filled_steps, L.update_seed, first.gather_draw, M, &L.batch, &her_rule, who, &gather_her))
+      return rc;
   PerGather per_gather;
   memset(&per_gather, 0, sizeof(per_gather));
   if (per) {  // urgym_replay_sample_prioritized
@@ -1376,12 +1427,16 @@ int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learn
     }
     gather.oldest_slot = it.oldest_slot, gather.size = (uint64_t)it.filled_steps * (uint64_t)h->cfg.num_envs;
     gather_nstep.filled_steps = it.filled_steps;
+    if (her) gather_her.g.oldest_slot = gather.oldest_slot, gather_her.g.size = gather.size, gather_her.filled_steps = it.filled_steps;
     for (int g = 0; g < G; g++, u++) {
       const SacUpdate up = sac_schedule_update(S, u);
       const AdamCoef coef = adam_coefficients(L.lr, L.beta1, L.beta2, L.eps, up.adam_step);  // urgym_adam_coefficients' own function
       gather.draw = up.gather_draw;
       per_gather.g.draw = up.gather_draw;
-      if (per)
+      gather_her.g.draw = up.gather_draw;
+      if (her)
+        replay_gather_hindsight_launch(gather_her, s);
+      else if (per)
         per_gather_launch(per_gather, s);
       else if (nstep)
         replay_gather_nstep_launch(gather_nstep, s);
@@ -1826,6 +1881,27 @@ int urgym_sac_train_prioritized(void* handle, const urgym_sac_learner* learner, 
     return sac_train_body(who, handle, learner, schedule, stream, &hooks, nullptr, prioritized);
   }
   return sac_train_body(who, handle, learner, schedule, stream, nullptr, nullptr, prioritized);
+}
+
+int urgym_sac_train_hindsight(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_hindsight* hindsight, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream) {
+  const char* who = "urgym_sac_train_hindsight";
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (!hindsight) return fail_in(h, URGYM_ERR_ARG, who, "null hindsight");
+  TrainEvaluation e;
+  e.h = h, e.learner = learner, e.schedule = schedule, e.evaluation = evaluation_or_NULL, e.s = (hipStream_t)stream, e.done = 0, e.who = who;
+  TrainMonitoring t;
+  t.h = h, t.learner = learner, t.schedule = schedule, t.monitoring = monitoring_or_NULL, t.s = (hipStream_t)stream, t.done = 0;
+  t.evaluation = evaluation_or_NULL ? &e : nullptr, t.who = who;
+  if (monitoring_or_NULL) {
+    const TrainHooks hooks{train_monitoring_check, train_monitoring_after, &t};
+    return sac_train_body(who, handle, learner, schedule, stream, &hooks, nullptr, nullptr, hindsight);
+  }
+  if (evaluation_or_NULL) {
+    const TrainHooks hooks{train_evaluation_check, train_evaluation_after, &e};
+    return sac_train_body(who, handle, learner, schedule, stream, &hooks, nullptr, nullptr, hindsight);
+  }
+  return sac_train_body(who, handle, learner, schedule, stream, nullptr, nullptr, nullptr, hindsight);
 }
 
 }  // extern "C"

@@ -51,4 +51,21 @@ struct ReplayGatherNstep {
 // ONE launch on `s`
 void replay_gather_nstep_launch(const ReplayGatherNstep& p, hipStream_t s);
 
+// One minibatch with relabelled goals (urgym_replay_sample_hindsight; urgym_her.hip, a unit of its own): the one-step gather's draw
+// and geometry plus the rule of urgym_her.h, validated
+struct ReplayGatherHindsight {
+  ReplayGather g;
+  int filled_steps;  // g.size = filled_steps * g.N
+  int strategy, horizon;
+  uint64_t relabel_threshold;
+  // the re-scoring rule's numbers, from the handle's urgym_config (HerRule of urgym_her.h)
+  double distance_threshold, ori_threshold, w_collision, w_success, w_distance, w_orientation;
+  int additive;
+  int64_t* goal_index;  // [count] or null
+  double* pose_terms;   // [count][4] or null
+};
+
+// ONE launch on `s`
+void replay_gather_hindsight_launch(const ReplayGatherHindsight& p, hipStream_t s);
+
 }  // namespace urgym

@@ -420,6 +420,164 @@ def nstep_batch(ring_arrays, oldest_slot, filled, seed, draw, count, n_steps, ga
     return out
 
 
+def relabel_threshold(n_sampled_goal):
+    """The relabel threshold of urgym_replay_sample_hindsight for SB3's ``n_sampled_goal``, formed with integers:
+    (n_sampled_goal << 32) // (n_sampled_goal + 1), i.e. a share n / (n + 1) of the rows (4 -> 0.8).  0 relabels nothing."""
+    n = n_sampled_goal
+    if isinstance(n, bool) or int(n) != n or not 0 <= int(n) < 1 << 31:
+        raise ValueError(f"n_sampled_goal must be a non-negative integer, got {n_sampled_goal!r}")
+    return (int(n) << 32) // (int(n) + 1)
+
+
+def _her_arguments(threshold, strategy, horizon):
+    from . import _abi
+
+    strategy = _abi.HER_STRATEGIES.get(strategy, strategy)
+    if isinstance(threshold, bool) or int(threshold) != threshold or not 0 <= int(threshold) <= 1 << 32:
+        raise ValueError(f"the relabel threshold must be an integer in [0, 2^32], got {threshold!r}")
+    if isinstance(strategy, bool) or strategy not in (_abi.HER_GOAL_FUTURE, _abi.HER_GOAL_FINAL, _abi.HER_GOAL_OWN):
+        raise ValueError(f"strategy must be one of {sorted(_abi.HER_STRATEGIES)} (or URGYM_HER_GOAL_*), got {strategy!r}; SB3's 'episode' is out of scope")
+    if isinstance(horizon, bool) or int(horizon) != horizon or not 1 <= int(horizon) <= _abi.HER_HORIZON_MAX:
+        raise ValueError(f"horizon must be an integer in [1, {_abi.HER_HORIZON_MAX}], got {horizon!r}")
+    return int(threshold), int(strategy), int(horizon)
+
+
+def hindsight_pick(ring_flags, oldest_slot, filled, seed, draw, count, threshold, strategy, horizon, num_envs):
+    """The integer half of urgym_replay_sample_hindsight restated from include/urgym.h: pure integers, no float.  `ring_flags`: the
+    ring's ``terminated`` and ``truncated`` as host arrays [C, N]; `threshold` in [0, 2^32]; `strategy` "future", "final", "own" or
+    the URGYM_HER_GOAL_* number.  For row i, with the Philox word w of ``replay_indices`` (same key, same counter): e as there, p = e //
+    N, env = e % N, index = ((oldest_slot + p) % C) N + env; relabel = w[2] < threshold; H = min(horizon, filled - p), entry_k =
+    ((oldest_slot + p + k) % C) N + env, F = the smallest k + 1 <= H with terminated | truncated at entry_k, else H; j = (w[3] F) >> 32
+    for "future", F - 1 otherwise; g = entry_j.  Returns a dict of [count] arrays: ``e``, ``index``, ``g`` (int64), ``relabel``
+    (bool), ``F``, ``j`` (int32) -- F, j and g for every row, relabelled or not -- and ``goal_index`` (int64): g where the row is
+    relabelled and the strategy is not "own", else -1."""
+    from . import _abi
+
+    threshold, strategy, horizon = _her_arguments(threshold, strategy, horizon)
+    oldest_slot, filled, count, N = int(oldest_slot), int(filled), int(count), int(num_envs)
+    term, trunc = np.asarray(ring_flags["terminated"]), np.asarray(ring_flags["truncated"])
+    if term.ndim != 2 or term.shape != trunc.shape or term.shape[1] != N:
+        raise ValueError(f"terminated and truncated must be [C, {N}] arrays, got {term.shape} and {trunc.shape}")
+    cap = term.shape[0]
+    if not (1 <= filled <= cap and 0 <= oldest_slot < cap):
+        raise ValueError(f"filled must be in [1, {cap}] and oldest_slot in [0, {cap}), got {filled}, {oldest_slot}")
+    seed, draw = int(seed), int(draw)
+    key = (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
+    w = philox4x32_10(key, (np.arange(count, dtype=np.uint64), np.uint64(draw & 0xFFFFFFFF), np.uint64((draw >> 32) & 0xFFFFFFFF),
+                            np.uint64(_abi.REPLAY_TAG)))
+    size = filled * N
+    e = np.array([((int(hi) << 32 | int(lo)) * size) >> 64 for hi, lo in zip(w[0], w[1])], dtype=np.int64).reshape(count)
+    p, env = e // N, e % N
+    relabel = w[2].astype(np.uint64) < np.uint64(threshold) if threshold < 1 << 32 else np.ones(count, bool)
+    ends = ((term != 0) | (trunc != 0)).reshape(cap * N)
+    H = np.minimum(horizon, filled - p)
+    F, running = np.zeros(count, np.int64), np.ones(count, bool)
+    for k in range(int(H.max()) if count else 0):
+        take = running & (k < H)
+        entry = np.where(take, ((oldest_slot + p + k) % cap) * N + env, 0)  # rows that take no step k read nothing of it
+        F = np.where(take, k + 1, F)
+        running = running & ~(take & ends[entry])
+    j = (w[3].astype(np.uint64) * F.astype(np.uint64)) >> np.uint64(32) if strategy == _abi.HER_GOAL_FUTURE else F - 1  # w3 F < 2^41
+    j = j.astype(np.int64)
+    g = ((oldest_slot + p + j) % cap) * N + env
+    index = ((oldest_slot + p) % cap) * N + env
+    goal_index = np.where(relabel & (strategy != _abi.HER_GOAL_OWN), g, -1).astype(np.int64)
+    return dict(e=e, index=index.astype(np.int64), relabel=relabel, F=F.astype(np.int32), j=j.astype(np.int32), g=g.astype(np.int64), goal_index=goal_index)
+
+
+HER_CONFIG_FIELDS = ("env_kind", "distance_threshold", "ori_threshold", "w_collision", "w_success", "w_distance", "w_orientation")
+
+
+def _her_config(config):
+    get = (lambda k: config[k]) if isinstance(config, dict) else (lambda k: getattr(config, k))
+    c = {k: get(k) for k in HER_CONFIG_FIELDS}
+    return int(c.pop("env_kind")), {k: np.float64(v) for k, v in c.items()}
+
+
+def hindsight_rescore(config, goal_dim, reward, terminated, is_success, pose_terms):
+    """The re-scoring of urgym_her.h restated in numpy float64, one operation per line and in the header's order.  `reward` float32,
+    `terminated`, `is_success` the stored flags, `pose_terms` [rows, 4] float64 = d, th, d0, th0.  Returns (reward' float32,
+    terminated' uint8, is_success' uint8)."""
+    from . import _abi
+
+    kind, c = _her_config(config)
+    t4 = np.asarray(pose_terms, dtype=np.float64)
+    d, th, d0, th0 = t4[:, 0], t4[:, 1], t4[:, 2], t4[:, 3]
+    r = np.asarray(reward, dtype=np.float32).astype(np.float64)
+    term, succ0 = np.asarray(terminated) != 0, np.asarray(is_success) != 0
+    coll = term & ~succ0
+    with np.errstate(all="ignore"):  # a NaN goal is a value
+        succ = d < c["distance_threshold"]
+        if goal_dim == 6:
+            succ = succ & (th < c["ori_threshold"])
+
+        def goal_terms(s, dist, ang):
+            g = np.where(s, c["w_success"], np.float64(0))
+            k = np.where(coll, c["w_collision"], np.float64(0))
+            g = g + k
+            t = c["w_distance"] * dist
+            g = g + t
+            u = c["w_orientation"] * ang
+            g = g + u
+            return g
+
+        if kind in (_abi.ENV_ORI, _abi.ENV_OBS):
+            g0 = goal_terms(succ0, d0, th0)
+            g1 = goal_terms(succ, d, th)
+            out = r - g0
+            out = out + g1
+        else:
+            t0 = c["w_distance"] * d0
+            S = r - t0
+            u0 = c["w_orientation"] * th0
+            S = S - u0
+            S = np.where(succ0, np.float64(0), S)
+            t = c["w_distance"] * d
+            u = c["w_orientation"] * th
+            shaped = t + u
+            shaped = shaped + S
+            out = np.where(coll, c["w_collision"], np.where(succ, c["w_success"], shaped))
+        assert out.dtype == np.float64
+        new_term = succ | coll
+        return out.astype(np.float32), new_term.astype(np.uint8), (new_term & ~coll).astype(np.uint8)
+
+
+def hindsight_batch(ring_arrays, oldest_slot, filled, seed, draw, count, threshold, strategy, horizon, config, pose_terms):
+    """urgym_replay_sample_hindsight restated from include/urgym.h, every output, given the pose terms.  `ring_arrays`: the ring's
+    eleven fields as host arrays [C, N, ...]; `config`: the env's urgym_config (``_abi.Config``, or a dict of ``HER_CONFIG_FIELDS``);
+    `pose_terms`: [count, 4] float64 = d, th, d0, th0 per row (the library's own output, or a harness's: sincos and acos are restated
+    bitwise by no host; rows that are not relabelled ignore theirs).  Returns a dict: ``index``, ``goal_index`` (int64), ``relabel``
+    (bool), the seven row outputs, ``reward`` (float32) and the three flags (uint8).  A row that is not relabelled is plain indexing."""
+    from . import _abi
+
+    obs = np.asarray(ring_arrays["observation"])
+    cap, N, obs_dim = obs.shape
+    goal_dim = int(np.asarray(ring_arrays["desired_goal"]).shape[2])
+    if goal_dim not in (3, 6) or obs_dim < _abi.HER_GOAL_OFFSET + goal_dim:
+        raise ValueError(f"the observation row ({obs_dim} floats) holds no goal of {goal_dim} floats at [{_abi.HER_GOAL_OFFSET}, {_abi.HER_GOAL_OFFSET + goal_dim})")
+    for k in ("truncated", "is_success"):
+        if ring_arrays.get(k) is None:
+            raise ValueError(f"hindsight needs the ring's {k}")
+    pick = hindsight_pick(ring_arrays, oldest_slot, filled, seed, draw, count, threshold, strategy, horizon, N)
+    _, strategy, _ = _her_arguments(threshold, strategy, horizon)
+    t4 = np.asarray(pose_terms)
+    if t4.dtype != np.float64 or t4.shape != (int(count), 4):
+        raise ValueError(f"pose_terms must be float64 [{int(count)}, 4], got {t4.dtype} {t4.shape}")
+    flat = lambda a: np.asarray(a).reshape(cap * N, *np.asarray(a).shape[2:])  # noqa: E731
+    e, rel = pick["index"], pick["relabel"]
+    out = {name: flat(ring_arrays[name])[e].copy() for name, _, _, _ in _abi.REPLAY_RING_FIELDS}
+    goal = flat(ring_arrays["next_desired_goal"])[e] if strategy == _abi.HER_GOAL_OWN else flat(ring_arrays["next_achieved_goal"])[pick["g"]]
+    lo = _abi.HER_GOAL_OFFSET
+    for name, at in (("desired_goal", 0), ("next_desired_goal", 0), ("observation", lo), ("next_observation", lo)):
+        out[name][rel, at:at + goal_dim] = goal[rel]  # float32 words, copied bitwise
+    reward, term, succ = hindsight_rescore(config, goal_dim, out["reward"], out["terminated"], out["is_success"], t4)
+    out["reward"] = np.where(rel, reward, out["reward"])
+    out["terminated"] = np.where(rel, term, out["terminated"]).astype(np.uint8)
+    out["is_success"] = np.where(rel, succ, out["is_success"]).astype(np.uint8)
+    out.update(index=e, goal_index=pick["goal_index"], relabel=rel)
+    return out
+
+
 def per_sums(leaf, fanout=None):
     """The sum levels of the prioritized replay restated from ur_gym_amd/csrc/urgym_per.h in numpy float64.  `leaf`: float32, any
     shape (taken flat: the ring's entry order).  Level 0 is the leaves; entry b of level k + 1 is the ascending float64 sum, from +0.0,
@@ -1241,12 +1399,15 @@ class DeviceReplay:
         self.cursor = (self.cursor + K) % self.capacity
         self.filled = min(self.capacity, self.filled + K)
 
-    def sample_into(self, out, seed, draw, n_steps=None, gamma=None):
+    def sample_into(self, out, seed, draw, n_steps=None, gamma=None, hindsight=None):
         """The gather itself: `out` maps ring field names (and ``index``, int64) to contiguous device tensors with one leading
         length, the batch size; only those are written.  The rows are ``replay_indices(seed, draw, count, len(self))``.
 
         With `n_steps` and `gamma` (both or neither) the launch is urgym_replay_sample_nstep: a row spans up to `n_steps` steps of
-        its env (``nstep_batch``), `out` must hold ``discount`` (float32) and may hold ``steps`` (int32) and ``last_index`` (int64)."""
+        its env (``nstep_batch``), `out` must hold ``discount`` (float32) and may hold ``steps`` (int32) and ``last_index`` (int64).
+
+        With `hindsight` (a dict: ``threshold`` in [0, 2^32], ``strategy``, ``horizon``; not together with `n_steps`) the launch is
+        urgym_replay_sample_hindsight (``hindsight_batch``): `out` may hold ``goal_index`` (int64) and ``pose_terms`` (float64 [count, 4])."""
         import ctypes as C
 
         import torch
@@ -1260,8 +1421,14 @@ class DeviceReplay:
         if (n_steps is None) != (gamma is None):
             raise ValueError("n_steps and gamma go together")
         extra = {"discount": (C.c_float, ()), "steps": (C.c_int32, ()), "last_index": (C.c_int64, ())} if n_steps is not None else {}
+        her = _abi.ReplayHindsight()
+        if hindsight is not None:
+            if n_steps is not None:
+                raise ValueError("hindsight together with multi-step returns is out of scope")
+            extra = {"goal_index": (C.c_int64, ()), "pose_terms": (C.c_double, (4,))}
+            her.relabel_threshold, her.strategy, her.horizon = _her_arguments(hindsight["threshold"], hindsight["strategy"], hindsight["horizon"])
         kinds.update(extra)
-        dtypes = {C.c_int64: torch.int64, C.c_int32: torch.int32}
+        dtypes = {C.c_int64: torch.int64, C.c_int32: torch.int32, C.c_double: torch.float64}
         batch, nstep, count = _abi.ReplayBatch(), _abi.ReplayNstep(), None
         for name, t in out.items():
             if name not in kinds:
@@ -1275,7 +1442,7 @@ class DeviceReplay:
                 count = int(t.shape[0])
             elif int(t.shape[0]) != count:
                 raise ValueError(f"{name} has {int(t.shape[0])} rows, the others {count}")
-            setattr(nstep if name in extra else batch, name, C.cast(t.data_ptr(), C.POINTER(ct)))
+            setattr((nstep if hindsight is None else her) if name in extra else batch, name, C.cast(t.data_ptr(), C.POINTER(ct)))
         if count is None:
             raise ValueError("no output requested")
         self.check_args(self.capacity, filled_steps=self.filled, oldest_slot=self.oldest_slot, batch_size=count)
@@ -1289,6 +1456,10 @@ class DeviceReplay:
             nstep.n_steps, nstep.gamma = int(n_steps), float(gamma)
             _native.check(env.lib.urgym_replay_sample_nstep(env._h, C.byref(self._ring), self.oldest_slot, self.filled, int(seed), int(draw), count,
                                                             C.byref(batch), C.byref(nstep), env._stream()), env._h)
+            return
+        if hindsight is not None:
+            _native.check(env.lib.urgym_replay_sample_hindsight(env._h, C.byref(self._ring), self.oldest_slot, self.filled, int(seed), int(draw), count,
+                                                                C.byref(batch), C.byref(her), env._stream()), env._h)
             return
         _native.check(env.lib.urgym_replay_sample(env._h, C.byref(self._ring), self.oldest_slot, self.filled, int(seed), int(draw), count,
                                                   C.byref(batch), env._stream()), env._h)
@@ -1324,7 +1495,35 @@ class DeviceReplay:
                 "actions": flat["action"], "rewards": flat["reward"], "terminated": flat["terminated"].view(torch.bool),
                 "truncated": flat["truncated"].view(torch.bool), "is_success": flat["is_success"].view(torch.bool), "index": flat["index"]}
 
-    def sample_targets(self, actor, critic, batch_size, seed, draw, gamma, ent_coef, sample=None, n_steps=None):
+    def sample_hindsight(self, batch_size, seed, draw, n_sampled_goal=4, strategy="future", pose_terms=False):
+        """``sample`` with hindsight experience replay (SB3's HerReplayBuffer; urgym_replay_sample_hindsight, ``hindsight_batch``), one
+        launch: a share n_sampled_goal / (n_sampled_goal + 1) of the rows gets, as its goal, a pose its own episode reached at the
+        same or a later step (`strategy` "future": uniform over them; "final": the episode's last; "own": the row's own goal, a
+        diagnostic), and is re-scored against it with the task's reward.  The horizon is the env's ``max_episode_steps``.  The dict
+        of ``sample`` plus ``goal_index`` (int64: the ring entry the goal came from, -1 = not relabelled) and, with `pose_terms`,
+        ``pose_terms`` (float64 [batch_size, 4]: d, th, d0, th0).  Nothing is synchronised."""
+        import torch
+
+        from . import _abi
+        from .vector_env import _TORCH_DTYPE
+
+        self.check_args(self.capacity, batch_size=batch_size)
+        env, B = self.env, int(batch_size)
+        how = dict(threshold=relabel_threshold(n_sampled_goal), strategy=strategy, horizon=int(env.cfg.max_episode_steps))
+        flat = {name: torch.empty((B,) + tuple(shape(1, 1, env.obs_dim, env.goal_dim)[2:]), dtype=_TORCH_DTYPE[ct], device=env.device)
+                for name, ct, shape, _ in _abi.REPLAY_RING_FIELDS}
+        flat["index"] = torch.empty((B,), dtype=torch.int64, device=env.device)
+        flat["goal_index"] = torch.empty((B,), dtype=torch.int64, device=env.device)
+        if pose_terms:
+            flat["pose_terms"] = torch.empty((B, 4), dtype=torch.float64, device=env.device)
+        self.sample_into(flat, seed, draw, hindsight=how)
+        rows = ("observation", "achieved_goal", "desired_goal")
+        more = {k: flat[k] for k in ("goal_index", "pose_terms") if k in flat}
+        return {**more, "observations": {k: flat[k] for k in rows}, "next_observations": {k: flat["next_" + k] for k in rows},
+                "actions": flat["action"], "rewards": flat["reward"], "terminated": flat["terminated"].view(torch.bool),
+                "truncated": flat["truncated"].view(torch.bool), "is_success": flat["is_success"].view(torch.bool), "index": flat["index"]}
+
+    def sample_targets(self, actor, critic, batch_size, seed, draw, gamma, ent_coef, sample=None, n_steps=None, hindsight=None):
         """``sample``, then a' ~ pi(.|s') on the gathered next observations (``env.policy_actions(rows=)``), then SAC's target
         y = r + gamma (1 - terminated) (min_i Q_i(s', a') - ent_coef log pi(a'|s')) (``env.critic_values``): three launches.
         `sample` = how a' is drawn (default: gaussian with this call's seed and draw).  Returns the batch with ``next_actions``,
@@ -1333,7 +1532,12 @@ class DeviceReplay:
         With `n_steps` the batch is ``sample(..., n_steps=, gamma=)`` and the third launch writes the bootstrap value alone: the
         batch gets ``q_min_next`` = min_i Q_i(s', a') beside its ``discount`` instead of ``target`` (``env.entropy_step_nstep`` forms
         y from them); `ent_coef` is not used."""
-        batch = self.sample(batch_size, seed, draw, n_steps=n_steps, gamma=None if n_steps is None else gamma)
+        if hindsight is not None:  # dict(n_sampled_goal=, strategy=): the batch is ``sample_hindsight``'s, the rest as below
+            if n_steps is not None:
+                raise ValueError("hindsight together with multi-step returns is out of scope")
+            batch = self.sample_hindsight(batch_size, seed, draw, **hindsight)
+        else:
+            batch = self.sample(batch_size, seed, draw, n_steps=n_steps, gamma=None if n_steps is None else gamma)
         how = dict(mode="gaussian", seed=seed, first_draw=draw) if sample is None else sample
         nxt = batch["next_observations"]
         batch["next_actions"], batch["next_log_prob"] = self.env.policy_actions(actor, sample=how, rows=nxt)

@@ -71,6 +71,9 @@ SAC_DEFAULTS = dict(gamma=0.95, tau=0.005, learning_rate=1e-4, batch_size=256, l
 # Prioritized replay: the options of SACLearner(prioritized=True).  Kept apart from SAC_DEFAULTS: a run without
 # priorities holds none of them in its checkpoint.  beta of the update at Adam step t is evaluation.per_beta(per_beta, t, per_beta_steps).
 PER_DEFAULTS = dict(prioritized=False, per_beta=0.4, per_beta_steps=100000)
+# Hindsight experience replay: the options of SACLearner(hindsight=True), SB3's HerReplayBuffer arguments.  Kept
+# apart like PER_DEFAULTS: a run without hindsight saves none of them, so its checkpoint is what it was before the option existed.
+HER_DEFAULTS = dict(hindsight=False, her_n_sampled_goal=4, her_strategy="future")
 
 
 def _mlp(n_in, hidden, n_out=None):
@@ -152,14 +155,31 @@ class SACLearner:
     torch actor and a target DeviceCritic that follows the torch critic by Polyak averaging.  `env`: a UR5ReachVectorEnv with
     auto_reset.  Keyword arguments override SAC_DEFAULTS and PER_DEFAULTS: ``prioritized=True`` (with ``per_beta``, ``per_beta_steps``; needs
     all five ``device_*`` options and a ``DevicePrioritizedReplay``) draws each minibatch in proportion to the transitions' priorities and
-    weights the critics' gradient by the importance weights; not together with ``n_steps`` > 1."""
+    weights the critics' gradient by the importance weights; not together with ``n_steps`` > 1.  ``hindsight=True``
+    (HER_DEFAULTS: ``her_n_sampled_goal``, ``her_strategy`` "future" or "final"; needs ``device_entropy=True``) relabels the goals of each
+    minibatch in the gather (``DeviceReplay.sample_hindsight``); not together with ``n_steps`` > 1 or ``prioritized``."""
 
     def __init__(self, env, seed=0, **overrides):
-        unknown = [k for k in overrides if k not in SAC_DEFAULTS and k not in PER_DEFAULTS]
+        unknown = [k for k in overrides if k not in SAC_DEFAULTS and k not in PER_DEFAULTS and k not in HER_DEFAULTS]
         if unknown:
-            raise TypeError(f"unknown hyperparameters {unknown}; available: {sorted(SAC_DEFAULTS) + sorted(PER_DEFAULTS)}")
-        hp = dict(SAC_DEFAULTS, **PER_DEFAULTS)
+            raise TypeError(f"unknown hyperparameters {unknown}; available: {sorted(SAC_DEFAULTS) + sorted(PER_DEFAULTS) + sorted(HER_DEFAULTS)}")
+        hp = dict(SAC_DEFAULTS, **PER_DEFAULTS, **HER_DEFAULTS)
         hp.update(overrides)
+        if not isinstance(hp["hindsight"], bool):
+            raise ValueError(f"hindsight must be True or False, got {hp['hindsight']!r}")
+        if hp["hindsight"]:
+            from .evaluation import relabel_threshold
+
+            if not hp["device_entropy"]:
+                raise ValueError("hindsight=True needs device_entropy=True (the relabelled minibatch is gathered and used by the device's launches)")
+            if hp["prioritized"] is True or (not isinstance(hp["n_steps"], bool) and hp["n_steps"] != 1):
+                raise ValueError("hindsight=True with n_steps > 1 or prioritized=True is out of scope: each of the three has a gather of its own")
+            if hp["her_strategy"] not in ("future", "final"):
+                raise ValueError(f"her_strategy must be 'future' or 'final', got {hp['her_strategy']!r} ('own' is a diagnostic of the gather, SB3's 'episode' is out of scope)")
+            if relabel_threshold(hp["her_n_sampled_goal"]) == 0:
+                raise ValueError("her_n_sampled_goal must be a positive integer")
+            if env is not None and int(env.cfg.max_episode_steps) > 256:
+                raise ValueError(f"hindsight=True needs max_episode_steps <= 256 (the episode window's horizon), got {int(env.cfg.max_episode_steps)}")
         if not isinstance(hp["prioritized"], bool):
             raise ValueError(f"prioritized must be True or False, got {hp['prioritized']!r}")
         if hp["prioritized"]:
@@ -343,7 +363,8 @@ class SACLearner:
         M, gamma, n_steps = int(hp["batch_size"]), float(hp["gamma"]), int(hp["n_steps"])
         if hp.get("prioritized"):
             return self._update_prioritized(replay, seed, draw)
-        batch = replay.sample_targets(self.device_actor, self.target, M, seed, draw, gamma, 0.0, **({} if n_steps == 1 else dict(n_steps=n_steps)))
+        her = dict(hindsight=dict(n_sampled_goal=hp["her_n_sampled_goal"], strategy=hp["her_strategy"])) if hp.get("hindsight") else {}
+        batch = replay.sample_targets(self.device_actor, self.target, M, seed, draw, gamma, 0.0, **({} if n_steps == 1 else dict(n_steps=n_steps)), **her)
         rows = batch["observations"]
         how = dict(mode="gaussian", seed=seed, first_draw=int(draw) | 1 << 63)
         action_pi, log_prob = env.policy_actions(self.device_actor, sample=how, rows=rows)
@@ -431,7 +452,9 @@ class SACLearner:
             critic_workspace=self.critic_workspace, log_ent_coef=self.log_ent_coef, exp_avg=es["exp_avg"], exp_avg_sq=es["exp_avg_sq"], replay=replay,
             batch=batch, scratch=scratch, count=M, seed=self.seed, update_seed=0, gamma=hp["gamma"], tau=hp["tau"],
             target_entropy=hp["target_entropy"], lr=hp["learning_rate"], betas=st["betas"], eps=st["eps"])
-        self._train = dict(replay=replay, binding=binding, scratch=scratch, batch=batch, nstep=None, prioritized=None)
+        self._train = dict(replay=replay, binding=binding, scratch=scratch, batch=batch, nstep=None, prioritized=None, hindsight=None)
+        if hp.get("hindsight"):  # the rule of urgym_sac_train_hindsight's gathers: numbers only, no scratch
+            self._train["hindsight"] = dict(n_sampled_goal=hp["her_n_sampled_goal"], strategy=hp["her_strategy"], horizon=int(env.cfg.max_episode_steps))
         if hp.get("prioritized"):  # the scratch of urgym_sac_train_prioritized; like the batch scratch, never saved
             per = {name: torch.zeros(shape(M), dtype=torch.float32, device=dev) for name, shape in _abi.SAC_PRIORITIZED_SCRATCH}
             per.update(total=torch.zeros((1,), dtype=torch.float64, device=dev), replay=replay, beta0=float(hp["per_beta"]), beta_steps=int(hp["per_beta_steps"]))
@@ -466,7 +489,8 @@ class SACLearner:
 
         With ``n_steps`` > 1 the ONE native call is urgym_sac_train_nstep, with the evaluations and the monitor where given.  With
         ``prioritized`` it is urgym_sac_train_prioritized on a ``DevicePrioritizedReplay``, the same way: every collection is followed
-        by the fill of its slots, every update is ``update``'s seventeen launches."""
+        by the fill of its slots, every update is ``update``'s seventeen launches.  With ``hindsight`` it is urgym_sac_train_hindsight:
+        the thirteen launches with the gather of ``DeviceReplay.sample_hindsight``."""
         from .evaluation import warmup_iterations
 
         if (evaluation is None) != (eval_every is None):
@@ -490,7 +514,8 @@ class SACLearner:
                       **({} if evaluation is None else dict(evaluation=evaluation, eval_every=eval_every)),
                       **({} if monitor is None else dict(monitor=monitor, log_every=log_every)),
                       **({} if tr["nstep"] is None else dict(nstep=tr["nstep"])),
-                      **({} if tr["prioritized"] is None else dict(prioritized=tr["prioritized"])))
+                      **({} if tr["prioritized"] is None else dict(prioritized=tr["prioritized"])),
+                      **({} if tr["hindsight"] is None else dict(hindsight=tr["hindsight"])))
         self.env_steps += n * K
         self.draw += n * K
         st["step"] += updates
@@ -514,7 +539,8 @@ class SACLearner:
     def _saved_hp(self):
         """The hyperparameters as a checkpoint holds them: ``n_steps`` only where it is not 1, so that the file of a one-step run is
         what it was before the option existed (``check_state_dict`` reads an absent ``n_steps`` as 1)."""
-        return {k: v for k, v in self.hp.items() if (k != "n_steps" or int(v) != 1) and (k not in PER_DEFAULTS or self.hp.get("prioritized"))}
+        return {k: v for k, v in self.hp.items() if (k != "n_steps" or int(v) != 1) and (k not in PER_DEFAULTS or self.hp.get("prioritized"))
+                and (k not in HER_DEFAULTS or self.hp.get("hindsight"))}
 
     def state_dict(self):
         """Everything the learner is, as host arrays and scalars: the actor's eight and the critics' twelve parameter tensors, the
@@ -588,6 +614,11 @@ class SACLearner:
                 raise ValueError(f"load_state_dict: {k} is {saved.get(k)!r} in the checkpoint, {self.hp[k]!r} here")
         for k, default in PER_DEFAULTS.items():  # a file without priorities holds none of the three
             if k != "prioritized" and not self.hp.get("prioritized") and not state["hp"].get("prioritized"):
+                continue
+            if state["hp"].get(k, default) != self.hp.get(k, default):
+                raise ValueError(f"load_state_dict: {k} is {state['hp'].get(k, default)!r} in the checkpoint, {self.hp.get(k, default)!r} here")
+        for k, default in HER_DEFAULTS.items():  # a file without hindsight holds none of the three
+            if k != "hindsight" and not self.hp.get("hindsight") and not state["hp"].get("hindsight"):
                 continue
             if state["hp"].get(k, default) != self.hp.get(k, default):
                 raise ValueError(f"load_state_dict: {k} is {state['hp'].get(k, default)!r} in the checkpoint, {self.hp.get(k, default)!r} here")

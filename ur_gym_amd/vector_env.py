@@ -799,7 +799,7 @@ class UR5ReachVectorEnv:
 
     def sac_train(self, learner, critic_loss, actor_loss, ent_coef_loss, *, first_slot, filled_steps, num_iterations, steps_per_iteration=1,
                   updates_per_iteration=1, uniform_iterations=0, idle_iterations=0, collect_first_draw=0, update_first_draw=0, first_step=1,
-                  evaluation=None, eval_every=None, monitor=None, log_every=None, nstep=None, prioritized=None):
+                  evaluation=None, eval_every=None, monitor=None, log_every=None, nstep=None, prioritized=None, hindsight=None):
         """``num_iterations`` x (a collection of ``steps_per_iteration`` steps, ``updates_per_iteration`` SAC updates) in ONE native
         call (urgym_sac_train): the launches of ``collect`` and of the thirteen calls of an update, bit for bit, without returning to
         Python in between.  `learner`: what ``sac_learner`` returned, or a dict of its keyword arguments (then built and checked here).
@@ -826,8 +826,12 @@ class UR5ReachVectorEnv:
         With `prioritized` (a dict: ``replay``, the ``DevicePrioritizedReplay`` the learner's ring belongs to, ``beta0``,
         ``beta_steps``, and the scratch tensors of ``_abi.SAC_PRIORITIZED_SCRATCH`` and ``total``, float64 [1]) the call is
         urgym_sac_train_prioritized, with the evaluations and the monitor if those are given: every collection is followed by the
-        fill of its slots and every update draws through the priorities and writes the new ones back.  Not together with `nstep`."""
-        from .evaluation import DeviceEvaluation, DeviceMonitor, evaluation_points, monitor_points, training_schedule
+        fill of its slots and every update draws through the priorities and writes the new ones back.  Not together with `nstep`.
+
+        With `hindsight` (a dict: ``n_sampled_goal``, ``strategy`` "future" or "final", ``horizon``) the call is
+        urgym_sac_train_hindsight, with the evaluations and the monitor if those are given: every update's gather is the one of
+        ``DeviceReplay.sample_hindsight``.  Not together with `nstep` or `prioritized`."""
+        from .evaluation import DeviceEvaluation, DeviceMonitor, _her_arguments, evaluation_points, monitor_points, relabel_threshold, training_schedule
 
         who = "sac_train"
         if isinstance(learner, dict):
@@ -888,11 +892,24 @@ class UR5ReachVectorEnv:
                                      alpha=rp.alpha, eps=rp.eps, total=C.cast(total.data_ptr(), C.POINTER(C.c_double)))
             for name, shape in _abi.SAC_PRIORITIZED_SCRATCH:
                 setattr(P_, name, self._float_ptr(who, f"prioritized[{name!r}]", prioritized[name], shape(count)))
+        if hindsight is not None:
+            if nstep is not None or prioritized is not None:
+                raise ValueError(f"{who}: hindsight together with multi-step returns or priorities is out of scope")
+            if hindsight["strategy"] not in ("future", "final"):
+                raise ValueError(f"{who}: hindsight['strategy'] must be 'future' or 'final', got {hindsight['strategy']!r}")
+            H_ = _abi.SacHindsight(*_her_arguments(relabel_threshold(hindsight["n_sampled_goal"]), hindsight["strategy"], hindsight["horizon"]), 0)
         for name, t in zip(_abi.SAC_LEARNER_LOSSES, (critic_loss, actor_loss, ent_coef_loss)):
             setattr(L, name, self._float_ptr(who, name, t, (updates,)))
         S = _abi.SacSchedule(*[sched[name] for name, _ in _abi.SacSchedule._fields_])
         try:
-            if prioritized is not None:
+            if hindsight is not None:
+                _native.check(self.lib.urgym_sac_train_hindsight(self._h, C.byref(L), C.byref(S), C.byref(H_), C.byref(E_) if evaluation is not None else None,
+                                                                 C.byref(M_) if monitor is not None else None, self._stream()), self._h)
+                if monitor is not None:
+                    monitor.advance(sched["num_iterations"], len(logged))
+                if evaluation is not None:
+                    evaluation.advance(len(points))
+            elif prioritized is not None:
                 _native.check(self.lib.urgym_sac_train_prioritized(self._h, C.byref(L), C.byref(S), C.byref(P_), C.byref(E_) if evaluation is not None else None,
                                                                    C.byref(M_) if monitor is not None else None, self._stream()), self._h)
                 if monitor is not None:
