@@ -37,6 +37,7 @@ struct Handle {
   Kernels k;
   double* d_ld_scratch = nullptr;  // [5][N] link distances of the running step
   double* d_sc_scratch = nullptr;  // [SC_ROWS][N] set-up cache of the running step
+  double* d_lf_scratch = nullptr;  // [3][12][N] frames of links 4, 5, 6 of the running step (sized by this handle's N)
   CandRec* d_recs = nullptr;          // support map: candidate records ...
   unsigned short* d_cell = nullptr;   // ... and the cube map of directions that points into them
   uint64_t seed = 0;

@@ -52,11 +52,18 @@ namespace {
 constexpr int WAVES = 4;  // waves per workgroup
 constexpr int THREADS = GROUP * WAVES;
 constexpr uint32_t NO_ITEM = 0xFFFFFFFFu;
-constexpr int REFILL_MIN = 16;
+// idle lanes a wave waits for before it draws (the STEADY loop below).  Compile-time only, like URGYM_DIRMAP_G: -DURGYM_REFILL_MIN=<n>
+// builds a variant to measure (8, 12, 16, 24).
+#ifndef URGYM_REFILL_MIN
+#define URGYM_REFILL_MIN 16
+#endif
+constexpr int REFILL_MIN = URGYM_REFILL_MIN;
+static_assert(REFILL_MIN >= 1 && REFILL_MIN <= 64, "a wave has 64 lanes");
 // Resident STEP / PREFETCH workgroups per CU the kernels are compiled for (launch bounds -> VGPR budget 168) and the cap of the
 // step grid's residency (plan_handle)
 constexpr int RESIDENT = 3;
 constexpr int SC_ROWS = 19;  // rows of KParams::sc_scratch
+constexpr int LF_FIRST = 4, LF_LINKS = 3, LF_ROWS = 12 * LF_LINKS;  // KParams::lf_scratch: the frames of links 4, 5, 6, twelve rows each
 // bits of the per-env culling mask: table vs links 2..6, track vs links 2..6, the nine self pairs
 constexpr int PAIR_TABLE = 0, PAIR_TRACK = 5, PAIR_SELF = 10;
 __host__ __device__ constexpr int self_pair_bit(int la, int lb) {  // (1,3)(1,4)(1,5)(1,6)(2,4)(2,5)(2,6)(3,5)(3,6)
@@ -117,7 +124,12 @@ struct KParams {
                        // quaternion after this step's motion (the six float64 sincos of a full forward-kinematics pass were three
                        // quarters of a set-up).  Caching the link frames of P1's culling pass as well (72 more rows) was measured
                        // at +1 % env-steps/s for +61 MB of L2 <-> fabric traffic per launch (N = 65536 Dyn: 186.3 M without the
-                       // cache, 195.4 M with these rows, 197.7 M with the frames; profiles/r2/exp_setup_cache_levels.txt), and dropped.
+                       // cache, 195.4 M with these rows, 197.7 M with the frames; profiles/r2/exp_setup_cache_levels.txt), and dropped then;
+                       // the frames of the three links a draw can ask for came back in lf_scratch below.
+  double* lf_scratch;  // [LF_LINKS][12][N]: the frames of links 4, 5, 6 of the running step (row-major rotation, then translation), stored by
+                       // the env's P1 lane out of its culling pass and published with sc_scratch; a draw inside the pool loads its link's
+                       // frame from here instead of repeating 4-6 chain products.  Owned by the handle,
+                       // indexed by global env.  A STEP launch without the culling pass (check_collision = 0) stores and reads nothing.
   int* rzero;       // a list counter this launch arms (sets to 0) for a later launch, or null
   int* rzero2;      // a second one
   int fallback_on;  // STEP with prefetch: 1 = the RESET / PREFETCH fallback launches follow this step (records may be stale)
@@ -629,6 +641,13 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
     s_flags[tid] = 0;
     s_pairs[tid] = 0;
   }
+  // STEP: the P1 lanes leave the frames of links 4, 5, 6 for the draws of this workgroup (KParams::lf_scratch) where its pool holds more
+  // tickets than the lanes own -- then tickets are drawn inside the pool, 4-6 chain products each -- and the launch runs the culling
+  // pass that forms the frames.  A workgroup whose tickets are all the lanes' own (5 E <= 256; UR5OriReach-v1 has none) would pay
+  // the stores in front of its pair queries for the few pair items they could serve: it keeps the parent's P1 and the chain.  So do
+  // the instances with the EPA phase (UR5ObsReach-v1; check_collision = 0 stores no frame anyway): with the frame path compiled in,
+  // the loops of env_step_fused<1, true> came out two instructions longer and Obs N = 16384, which draws no ticket, measured -0.5 %.
+  const bool frames_on = (MODE == MODE_STEP) && HAS_OBST && !WITH_EPA && cfg.check_collision && (workbench ? 15 : 5) * E > THREADS;
   __syncthreads();
   // ---- P1 (waves 0..G-1, one lane per env slot): which env, joint update, obstacle motion, and the conservative
   //      bounding-capsule culling of the table / track / self pairs of check_collision (pyb_setup.py:407-427) -> LDS
@@ -712,13 +731,24 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
       const double lim = cfg.collision_margin + M_HULL + 1e-6;
       X3 T = identity_x3();
       D3 a0[3], a1[3];
+      double sn45[2] = {0, 0}, cs45[2] = {0, 0};  // frames_on: sin / cos of the last two joints, read before the first frame is stored
 #pragma unroll
       for (int k = 0; k < 6; k++) {
         double sn, cs;
-        if (use_cache) { sn = SOA(P.sc_scratch, 2 * k, n, N); cs = SOA(P.sc_scratch, 2 * k + 1, n, N); }  // (this lane stored them above)
+        if (frames_on && k >= LF_FIRST) { sn = sn45[k - LF_FIRST]; cs = cs45[k - LF_FIRST]; }
+        else if (use_cache) { sn = SOA(P.sc_scratch, 2 * k, n, N); cs = SOA(P.sc_scratch, 2 * k + 1, n, N); }  // (this lane stored them above)
         else sincos(q[k], &sn, &cs);
         fk_joint(T, k, sn, cs);
         const int link = k + 1;
+        // The frames a draw can ask for (KParams::lf_scratch): stores only, published with the set-up cache by s_p1done below.  The
+        // loads this loop still needs are issued first: a load behind the stores is waited for together with them (one counter).
+        if (frames_on && link == LF_FIRST)
+          for (int j = 0; j < 2; j++) { sn45[j] = SOA(P.sc_scratch, 2 * (LF_FIRST + j), n, N); cs45[j] = SOA(P.sc_scratch, 2 * (LF_FIRST + j) + 1, n, N); }
+        if (frames_on && link >= LF_FIRST) {
+          const int row = 12 * (link - LF_FIRST);
+          for (int i = 0; i < 9; i++) SOA(P.lf_scratch, row + i, n, N) = T.r[i];
+          SOA(P.lf_scratch, row + 9, n, N) = T.t.x; SOA(P.lf_scratch, row + 10, n, N) = T.t.y; SOA(P.lf_scratch, row + 11, n, N) = T.t.z;
+        }
         const double* c = c_tab.capsule[k];
         const D3 b0 = apply(T, d3(c[0], c[1], c[2])), b1 = apply(T, d3(c[3], c[4], c[5]));
         const double rb = c[6];
@@ -822,8 +852,21 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
         if (!finite) return false;
       }
       X3 T = identity_x3(), TA = identity_x3();
+      // A draw inside the pool finds the frames of links 4, 5, 6 where the env's P1 lane left them (KParams::lf_scratch): the output of
+      // the very chain below on the very sin / cos values it would read back, so the same bits, for twelve loads instead of lb dependent
+      // rounds.  Only where that lane stored them (frames_on; a live env, which n >= 0 says after P1) and only
+      // for an item that needs nothing from inside the chain: a self pair takes TA there, links 2 and 3 have no frame.  The lanes' own
+      // first tickets (std::false_type) may run ahead of P1 and keep the chain.  (e, lb are in range: the decoder's check above.)
+      // The loads stand directly in front of their use in each branch below, not here: a load still in flight on some path through
+      // the branches that follow would put waits for it into the loops behind the draw step.
+      const bool framed = decltype(after_p1)::value && frames_on && lb >= LF_FIRST && kind != Q_SELF;
+      auto load_frame = [&]() {
+        const int row = 12 * (lb - LF_FIRST);
+        for (int i = 0; i < 9; i++) T.r[i] = SOA(P.lf_scratch, row + i, n, N);
+        T.t = d3(SOA(P.lf_scratch, row + 9, n, N), SOA(P.lf_scratch, row + 10, n, N), SOA(P.lf_scratch, row + 11, n, N));
+      };
 #pragma unroll 1
-      for (int k = 0; k < lb; k++) {
+      for (int k = 0; k < (framed ? 0 : lb); k++) {
         double sn, cs;
         if (cached) { sn = SOA(P.sc_scratch, 2 * k, n, N); cs = SOA(P.sc_scratch, 2 * k + 1, n, N); }
         else sincos(LDS_Q ? s_q[k][e] : joint_of_step<MODE>(P, actions, n, k), &sn, &cs);
@@ -845,12 +888,14 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
           quat_to_rot(oqs, To.r);
           To.t = d3(op[0], op[1], op[2]);
         }
+        if (framed) load_frame();
         store(pose_slot, rel(To, T));
         v0 = rotT(To, guided ? guided_axis(capsule_mid(lb, T), To.t) : d3(0, 1, 0));  // Bullet: the world +Y axis
       } else if (kind == Q_SELF) {
         store(pose_slot, rel(T, TA));
         v0 = rotT(T, guided ? guided_axis(capsule_mid(la, TA), capsule_mid(lb, T)) : d3(0, 1, 0));
       } else {
+        if (framed) load_frame();
         const bool tbl = (kind == Q_TABLE);
         const D3 centre = d3(tbl ? TABLE_CX : TRACK_CX, tbl ? TABLE_CY : TRACK_CY, tbl ? TABLE_CZ : TRACK_CZ);
         v0 = guided ? guided_axis(capsule_mid(lb, T), centre) : d3(0, 1, 0);
@@ -1661,6 +1706,7 @@ KParams make_params(Handle* h, int copy_final) {
   P.rec_i = h->d_reci;
   P.ld_scratch = h->d_ld_scratch;
   P.sc_scratch = h->d_sc_scratch;
+  P.lf_scratch = h->d_lf_scratch;
   P.fallback_on = 1;
   P.inline_ori = h->plan.inline_ori ? 1 : 0;
   for (int i = 0; i < 6; i++) P.neutral_ach[i] = h->neutral_ach[i];
@@ -1713,7 +1759,7 @@ void time_end(Handle* h, int slot, hipStream_t s) {
 
 // every failure path of urgym_create and urgym_destroy: frees whatever the handle holds
 void release(Handle* h) {
-  for (void* p : {(void*)h->d_ld_scratch, (void*)h->d_sc_scratch, (void*)h->d_recs, (void*)h->d_cell, (void*)h->d_rec,
+  for (void* p : {(void*)h->d_ld_scratch, (void*)h->d_sc_scratch, (void*)h->d_lf_scratch, (void*)h->d_recs, (void*)h->d_cell, (void*)h->d_rec,
                   (void*)h->d_reci, (void*)h->d_rl[0], (void*)h->d_rl[1], (void*)h->d_rl[2], (void*)h->d_rl[3], (void*)h->d_rcount})
     if (p) hipFree(p);
   for (auto e : h->ev) hipEventDestroy(e);
@@ -1821,11 +1867,12 @@ int upload_tables(Handle* h) {
   return URGYM_OK;
 }
 
-// the library's own scratch: link distances and set-up cache of the running step; episode records and refill lists
+// the library's own scratch: link distances, set-up cache and link frames of the running step; episode records and refill lists
 int allocate_scratch(Handle* h) {
   const size_t n = (size_t)h->cfg.num_envs;
   HIP_TRY(h, hipMalloc((void**)&h->d_ld_scratch, sizeof(double) * 5 * n));
   HIP_TRY(h, hipMalloc((void**)&h->d_sc_scratch, sizeof(double) * SC_ROWS * n));
+  HIP_TRY(h, hipMalloc((void**)&h->d_lf_scratch, sizeof(double) * LF_ROWS * n));
   if (!h->plan.prefetch) return URGYM_OK;
   HIP_TRY(h, hipMalloc((void**)&h->d_rec, sizeof(double) * 2 * REC_FIELDS * n));
   HIP_TRY(h, hipMalloc((void**)&h->d_reci, sizeof(int32_t) * 4 * n));
