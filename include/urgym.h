@@ -1517,6 +1517,73 @@ typedef struct urgym_sac_hindsight {
  * NULL, URGYM_HER_GOAL_OWN (a diagnostic of the gather, not a way to train). */
 int urgym_sac_train_hindsight(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_hindsight* hindsight, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream);
 
+/* ---- gradient-norm clipping on the device (torch.nn.utils.clip_grad_norm_, the usual torch idiom; SB3's SAC does NOT clip, so this
+ * is an option the reference does not have).  The global norm of a network's gradient tensors is reduced on the device in a stated
+ * order, the clip coefficient stays on the device, and the Adam steps apply it while they step.  Added WITHIN ABI version 4: no struct
+ * above changed, URGYM_ABI_VERSION did not move, the new symbols (urgym_actor_grad_norm, urgym_critic_grad_norm,
+ * urgym_actor_adam_step_scaled, urgym_critic_adam_step_scaled, urgym_sac_train_clipped) are found by lookup.
+ *
+ * A group is the gradient tensors of one optimiser in a FIXED order: the actor's 8 in the order of urgym_actor_tensors; or the 2 x 6
+ * of both Q-networks, network 0 then network 1, each w0, b0, w1, b1, w_q, b_q (both networks are ONE group).  For tensor k:
+ *   s_k    = THE ORDERED SUM (above, "SAC's entropy coefficient on the device": 1024 lanes, lane t adds elements t, t + 1024, ... in
+ *            ascending order, fold 512 .. 1) over the tensor's flat elements of (double)g * (double)g -- exact in float64
+ *   total  = ((s_0 + s_1) + s_2) + ...                    float64, tensor order
+ *   norm64 = sqrt(total)                                  float64, correctly rounded
+ *   c64    = (double)max_norm / (norm64 + 1e-6)           torch's formula
+ *   scale  = c64 < 1.0 ? (float)c64 : 1.0f
+ *   norm   = (float)norm64                                for the record only
+ * The order depends on the tensors' shapes alone; there are no atomics.  ur_gym_amd.evaluation.grad_norm restates all of it, the
+ * square root included (the device's is held bitwise to the host's correctly rounded one by the GPU tests).
+ * UNLIKE torch the gradient tensors are NOT written: the scaled steps multiply each element as they read it, gs = g * scale, ONE
+ * float32 multiply rounded on its own, and the element of urgym_actor_adam_step runs on gs unchanged.
+ * Non-finite elements: a NaN makes c64 NaN, the comparison false and scale 1.0f -- the step is then what it is without clipping.  An
+ * infinity (and no NaN) makes norm64 = +inf and scale = +0.0f: finite elements step with gs = +-0, the infinite ones with gs = NaN. */
+typedef struct urgym_grad_norm {
+  float max_norm;          /* finite, > 0 */
+  int32_t reserved0;       /* must be 0 */
+  float* norm_out;         /* [1] DEVICE */
+  float* scale_out;        /* [1] DEVICE */
+  double* tensor_sums_out; /* [8] (actor) or [12] (critics) DEVICE, 8-byte aligned; or NULL */
+} urgym_grad_norm;
+
+/* Both calls: ONE launch of ONE workgroup of 1024 lanes on `stream`; no allocation, no host synchronisation, everything validated
+ * before the launch.  The gradient tensors (shapes: the object's) are read when the launch RUNS and are not written.  Refused
+ * (URGYM_ERR_ARG, nothing launched, nothing written): NULL handle / object / grad / args; an object of another handle; a NULL tensor
+ * pointer; a NULL norm_out or scale_out; tensor_sums_out not 8-byte aligned; reserved0 != 0; max_norm not finite or <= 0. */
+int urgym_actor_grad_norm(void* handle, void* actor, const urgym_actor_tensors_const* grad, const urgym_grad_norm* args, void* stream);
+int urgym_critic_grad_norm(void* handle, void* critic, const urgym_q_network_dev grad[2], const urgym_grad_norm* args, void* stream);
+
+/* urgym_actor_adam_step / urgym_critic_adam_step with every gradient element multiplied by *scale_dev as it is read (see above): ONE
+ * launch each, kernels of their own.  scale_dev is a DEVICE scalar read when the launch runs -- what a urgym_*_grad_norm call earlier
+ * on `stream` wrote to scale_out.  With *scale_dev == 1.0f every output is bit for bit the unscaled call's.  Refused: everything the
+ * unscaled step refuses, and a NULL scale_dev. */
+int urgym_actor_adam_step_scaled(void* handle, void* actor, const urgym_actor_adam* t, const urgym_adam_hyper* hp, const float* scale_dev, void* stream);
+int urgym_critic_adam_step_scaled(void* handle, void* online, void* target_or_NULL, const urgym_critic_adam* t, const urgym_adam_hyper* hp, float tau, const float* scale_dev, void* stream);
+
+typedef struct urgym_sac_clipping {
+  float max_grad_norm;     /* finite, > 0: of the critics' group and of the actor's group alike */
+  int32_t reserved0;       /* must be 0 */
+  float* scale;            /* [2] DEVICE scratch: the critics' coefficient, then the actor's, of the running update */
+  float* critic_grad_norm; /* [number of updates of the call] DEVICE: update u writes slot u, like the losses */
+  float* actor_grad_norm;  /* the same */
+} urgym_sac_clipping;
+
+/* urgym_sac_train -- or urgym_sac_train_evaluated / _monitored / _nstep / _prioritized / _hindsight, by which of the five optional
+ * arguments are given -- with two more launches per update and the two steps replaced by their scaled forms.  Afterwards everything
+ * is BIT FOR BIT what that call's sequence would have left with these substitutions, u = the update's slot:
+ *     urgym_critic_parameter_gradients(...)                                                        as before
+ *     urgym_critic_grad_norm(online, critic_adam.grad, {max_grad_norm, critic_grad_norm + u, scale + 0, NULL})
+ *     urgym_critic_adam_step_scaled(online, target, critic_adam, hp, tau, scale + 0)               in place of urgym_critic_adam_step
+ *     ...
+ *     urgym_actor_parameter_gradients(...)                                                         as before
+ *     urgym_actor_grad_norm(actor, actor_adam.grad, {max_grad_norm, actor_grad_norm + u, scale + 1, NULL})
+ *     urgym_actor_adam_step_scaled(actor, actor_adam, hp, scale + 1)                               in place of urgym_actor_adam_step
+ * 15 launches per update (17 above 1024 rows; the prioritized route's count plus two).  The temperature's scalar step is not clipped.
+ * Everything is validated before the first launch.  Refused besides what the composed call refuses: clipping == NULL; reserved0 != 0;
+ * max_grad_norm not finite or <= 0; a NULL scale; a NULL critic_grad_norm or actor_grad_norm in a call that holds an update; more
+ * than one of nstep, prioritized and hindsight (the pairings those calls already refuse). */
+int urgym_sac_train_clipped(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_clipping* clipping, const urgym_sac_nstep* nstep_or_NULL, const urgym_sac_prioritized* prioritized_or_NULL, const urgym_sac_hindsight* hindsight_or_NULL, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream);
+
 /* ---- weights back to the device tensors (a checkpoint: the reference's train.py:31-36 continues a saved run, and the TARGET critic
  * exists only as a packed buffer, blended in place by urgym_critic_load(tau < 1) and urgym_critic_adam_step(target)).  The packing
  * map of ur_gym_amd/csrc/urgym_pack_map.h run the other way, on the device: every element of every destination tensor -- DEVICE

@@ -64,6 +64,15 @@ process, each ending in a device synchronise; wall time per update, medians.  Ba
 spread of the old route's windows.  The ratio is reported whatever it is.
     python tools/bench_policy_rollout.py --entropy --windows 8 --launches 200 --out profiles/policy_rollout/dyn65536_entropy.json
 
+--clip measures gradient-norm clipping on the same update (4096 envs, batch 256, H = 256, device_entropy):
+`device_entropy`, the learner without max_grad_norm (the thirteen calls it always made), against `clipped`, the learner with
+max_grad_norm (fifteen: two norm launches, two scaled steps); and the same pair as ONE SACLearner.train call per window
+(urgym_sac_train against urgym_sac_train_clipped).  Alternating windows of --launches updates in one process, each ending in a device
+synchronise; median, min and max of the wall time per update, and the extra time per update of the clipped route.  No bar on the
+clipped route; the unclipped one is compared with the parent commit's --entropy figure by whoever runs both.  --clip-only runs the
+clipped native updates alone: the program of a kernel-trace run.
+    python tools/bench_policy_rollout.py --clip --windows 8 --launches 200 --out profiles/policy_rollout/dyn65536_clip.json
+
 --native measures the same update (batch 256, H = 256, device_entropy) two ways: the thirteen-call
 SACLearner.update, and SACLearner.train(steps_per_iteration=0, updates_per_iteration=--launches), one native call per window.
 Alternating windows in one process, each ending in a device synchronise; median, min and max of the wall time per update.  Bar: the
@@ -961,6 +970,83 @@ def entropy_mode(args):
             f.write(line + "\n")
 
 
+def clip_mode(args):
+    """--clip: the update without and with max_grad_norm, as update() calls and as one native call per window (see above)."""
+    import torch
+
+    from ur_gym_amd import make_vec
+    from ur_gym_amd.evaluation import DeviceReplay
+    from ur_gym_amd.training import SACLearner
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_policy_rollout.py measures on a GPU; none is visible")
+    dev, n, per_window = "cuda:0", min(args.num_envs, 4096), args.launches  # an update does not depend on the number of envs
+    env = make_vec(args.env, num_envs=n, device=dev, seed=0, auto_reset=True)
+    env.reset(seed=0)
+    sync = lambda: torch.cuda.synchronize(env.device)  # noqa: E731
+    options = dict(device_action_gradient=True, device_critic_gradient=True, device_actor_gradient=True, device_optimizer=True, device_entropy=True)
+    routes = {"device_entropy": (False, {}), "clipped": (False, dict(max_grad_norm=args.max_grad_norm)),
+              "native": (True, {}), "native_clipped": (True, dict(max_grad_norm=args.max_grad_norm))}
+    if args.clip_only:
+        routes = {"native_clipped": routes["native_clipped"]}
+    learners = {}
+    for label, (native, extra) in routes.items():
+        learner = SACLearner(env, seed=0, batch_size=256, hidden_width=256, learning_starts=0, **options, **extra)
+        replay = DeviceReplay(env, 64)
+        learner.collect(replay, 4)
+        learners[label] = (learner, replay, [0], native)
+
+    def updates(label, count):
+        learner, replay, draw, native = learners[label]
+        if native:
+            learner.train(replay, 1, 0, count, seed=1, first_draw=draw[0] + 1)
+            draw[0] += count
+        else:
+            for _ in range(count):
+                draw[0] += 1
+                learner.update(replay, 1, draw[0])
+
+    def window(label):
+        sync()
+        t0 = time.perf_counter()
+        updates(label, per_window)
+        sync()
+        return (time.perf_counter() - t0) * 1e6 / per_window
+
+    for label in learners:
+        updates(label, 10)
+    if args.clip_only:
+        for _ in range(args.windows):
+            updates("native_clipped", per_window)
+        sync()
+        print(json.dumps({"tool": "bench_policy_rollout --clip --clip-only", "updates": args.windows * per_window}))
+    else:
+        wdw = {label: [] for label in learners}
+        for _ in range(args.windows):
+            for label in learners:
+                wdw[label].append(window(label))
+        med = {k: float(np.median(v)) for k, v in wdw.items()}
+        last = learners["clipped"][0].last_update
+        result = {"tool": "bench_policy_rollout --clip", "env": args.env, "num_envs": n, "windows": args.windows, "updates_per_window": per_window,
+                  "batch": 256, "hidden_width": 256, "max_grad_norm": args.max_grad_norm, "device": torch.cuda.get_device_name(0),
+                  "us_per_update_median": med, "us_per_update_min": {k: float(min(v)) for k, v in wdw.items()},
+                  "us_per_update_max": {k: float(max(v)) for k, v in wdw.items()},
+                  "us_per_update_windows": {k: [round(x, 2) for x in v] for k, v in wdw.items()},
+                  "device_entropy_us_spread": float(max(wdw["device_entropy"]) - min(wdw["device_entropy"])),
+                  "clipped_minus_device_entropy_us": med["clipped"] - med["device_entropy"],
+                  "native_clipped_minus_native_us": med["native_clipped"] - med["native"],
+                  "last_update": {k: float(last[k][0]) for k in ("critic_grad_norm", "actor_grad_norm", "critic_scale", "actor_scale")}}
+        line = json.dumps(result)
+        print(line)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+    for learner, _, _, _ in learners.values():
+        learner.close()
+    env.close()
+
+
 def native_mode(args):
     """--native: the thirteen-call SACLearner.update against SACLearner.train, one native call per window (see above)."""
     import torch
@@ -1620,6 +1706,9 @@ def main():
     ap.add_argument("--actor-gradient", action="store_true", help="measure the actor's parameter gradients (two or three launches) against torch autograd (see above)")
     ap.add_argument("--optimizer", action="store_true", help="measure the Adam step kernels (one launch each) against torch's Adam.step followed by the reloads, and the learner's update with and without them")
     ap.add_argument("--entropy", action="store_true", help="measure the learner's update with device_optimizer only against the same plus device_entropy (see above)")
+    ap.add_argument("--clip", action="store_true", help="measure the update with max_grad_norm against the update without it, as update() calls and as one native call per window (see above)")
+    ap.add_argument("--clip-only", action="store_true", help="--clip: run only the clipped native updates, --windows x --launches of them (for a kernel trace)")
+    ap.add_argument("--max-grad-norm", type=float, default=1.0, help="--clip: the bound of the clipped learners")
     ap.add_argument("--native", action="store_true", help="measure the thirteen-call update against SACLearner.train, one native call per window (see above)")
     ap.add_argument("--native-only", action="store_true", help="--native: run only the native updates, --windows x --launches of them (for a kernel trace)")
     ap.add_argument("--evaluate", action="store_true", help="measure one evaluation (DeviceEvaluation.evaluate) against load_parameters + reset + run_closed_loop_device, and a training run with evaluations as one call against one call per interval plus the Python evaluation")
@@ -1642,6 +1731,8 @@ def main():
         return monitor_mode(args)
     if args.evaluate:
         return evaluate_mode(args)
+    if args.clip or args.clip_only:
+        return clip_mode(args)
     if args.native:
         return native_mode(args)
     if args.entropy:

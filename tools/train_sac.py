@@ -20,6 +20,9 @@ own counters); --resume PATH continues it with the same arguments up to --steps 
 prints the evaluation and monitor lines from the resume point on as the uninterrupted run prints them (on the device routes every number
 in them is the same; without --native the evaluations are this script's own and its best actor so far is kept only as its mean).
 --init-from ACTOR.npz CRITIC0.npz CRITIC1.npz starts a run from plain parameter files instead (SACLearner.load_parameters).
+--max-grad-norm X clips the critics' and the actor's gradients by their global norm on the device (SACLearner(max_grad_norm=X), needs
+--device-entropy; SB3's SAC does not clip) and adds to every evaluation line the three losses and the two gradient norms, before
+clipping, of the latest update.
 """
 import argparse
 import json
@@ -71,6 +74,9 @@ def main():
                          "a goal their own episode reached later and re-scores them (needs --device-entropy; not with --n-steps above 1 or --prioritized)")
     ap.add_argument("--her-n-sampled-goal", type=int, default=4, help="--hindsight: relabelled rows per kept row (4: a share of 0.8)")
     ap.add_argument("--her-strategy", default="future", choices=("future", "final"), help="--hindsight: which later pose of the episode becomes the goal")
+    ap.add_argument("--max-grad-norm", type=float, default=None, metavar="X",
+                    help="clip the critics' and the actor's gradients by their global norm on the device (torch's clip_grad_norm_ idiom; SB3's SAC "
+                         "does not clip) and print the losses and the norms with every evaluation (needs --device-entropy)")
     ap.add_argument("--native", action="store_true",
                     help="run the whole loop, evaluations included, as ONE native call (SACLearner.train): no Python between the launches "
                          "(needs --device-entropy)")
@@ -113,7 +119,8 @@ def main():
                          device_actor_gradient=args.device_actor_gradient, device_optimizer=args.device_optimizer,
                          device_entropy=args.device_entropy, n_steps=args.n_steps,
                          **(dict(prioritized=True, per_beta=args.per_beta, per_beta_steps=args.per_beta_steps) if args.prioritized else {}),
-                         **(dict(hindsight=True, her_n_sampled_goal=args.her_n_sampled_goal, her_strategy=args.her_strategy) if args.hindsight else {}))
+                         **(dict(hindsight=True, her_n_sampled_goal=args.her_n_sampled_goal, her_strategy=args.her_strategy) if args.hindsight else {}),
+                         **(dict(max_grad_norm=args.max_grad_norm) if args.max_grad_norm is not None else {}))
     eval_actor = DeviceActor(host_arrays(learner.actor.tensors()), test_env)  # actors belong to the environment they were made for
     replay = DevicePrioritizedReplay(env, args.capacity, alpha=args.per_alpha) if args.prioritized else DeviceReplay(env, args.capacity)
     updates, t0 = 0, time.perf_counter()
@@ -122,14 +129,20 @@ def main():
         raise SystemExit("--log-every must be at least 1")
     mon = DeviceMonitor(env, capacity=max(1, args.steps // args.log_every)) if args.monitor else None
 
+    latest = {}  # --max-grad-norm on the Python route: the losses the latest update returned (device tensors)
+
     def evaluate():
         eval_actor.load_parameters(learner.actor.tensors())
         test_env.reset(seed=args.seed + 1)
         res = run_closed_loop_device(test_env, eval_actor)
+        norms = {}
+        if args.max_grad_norm is not None:  # the run is synchronised here anyway
+            norms = {k: float(v) for k, v in latest.items()}
+            norms.update({k: float(learner.last_update[k][0]) for k in ("critic_grad_norm", "actor_grad_norm")})
         if args.save_best and res["mean_episode_reward"] > best["mean"]:  # strictly above, as the reference's EvalCallback decides
             best.update(mean=res["mean_episode_reward"], tensors=host_arrays(learner.actor.tensors()))
         print(json.dumps({"updates": updates, "env_steps": learner.env_steps * env.num_envs, "seconds": round(time.perf_counter() - t0, 1),
-                          "mean_episode_return": res["mean_episode_reward"], "success_rate_percent": res["success_rate_percent"]}), flush=True)
+                          "mean_episode_return": res["mean_episode_reward"], "success_rate_percent": res["success_rate_percent"], **norms}), flush=True)
 
     if args.init_from:
         import numpy as np
@@ -165,20 +178,25 @@ def main():
         # one call for the whole run -- or, with --save-every, one per stretch between two checkpoints: split calls are bit for bit the
         # single one (the schedule's counters are handed on), so the checkpoints cost the launches nothing but their own copies
         stretch = max(1, -(-args.save_every // max(1, args.updates_per_step))) if args.save_every else max(1, args.steps)
+        first_update, curves = updates, []  # --max-grad-norm: the losses and norms of every update of this process, one entry per call
         while step < args.steps:
             n = min(stretch, args.steps - step)
-            learner.train(replay, n, 1, args.updates_per_step, seed=args.seed, first_draw=updates, evaluation=ev, eval_every=args.eval_every,
-                          **(dict(monitor=mon, log_every=args.log_every) if mon is not None else {}))
+            got = learner.train(replay, n, 1, args.updates_per_step, seed=args.seed, first_draw=updates, evaluation=ev, eval_every=args.eval_every,
+                                **(dict(monitor=mon, log_every=args.log_every) if mon is not None else {}))
+            if args.max_grad_norm is not None:
+                curves.append(got)
             step, updates = step + n, learner.adam_state["step"]
             if args.save and (args.save_every or step == args.steps):
                 save(step)
         seconds = None
+        curve = {k: torch.cat([c[k] for c in curves]).cpu().numpy() for k in curves[0]} if curves else {}  # after the run: synchronises
         for trip, rec in list(zip(points, ev.results()))[shown_evals:]:  # results() synchronises, once
             seconds = round(time.perf_counter() - t0, 1) if seconds is None else seconds
             done = max(0, trip + 1 - idle) * args.updates_per_step
+            norms = {k: float(v[done - 1 - first_update]) for k, v in curve.items()} if curve and done - 1 >= first_update else {}
             print(json.dumps({"updates": done, "env_steps": (trip + 1) * env.num_envs, "seconds": seconds, "mean_episode_return": rec["mean_return"],
                               "success_rate_percent": 100.0 * rec["success_rate"], "std_episode_return": rec["std_return"],
-                              "mean_episode_length": rec["mean_length"], "improved": bool(rec["improved"])}), flush=True)
+                              "mean_episode_length": rec["mean_length"], "improved": bool(rec["improved"]), **norms}), flush=True)
         if mon is not None:
             print_curve(round(time.perf_counter() - t0, 1) if seconds is None else seconds)
         if args.save_best and ev.best_state()[1] >= 0:
@@ -190,7 +208,7 @@ def main():
         if learner.env_steps * env.num_envs < learner.hp["learning_starts"]:
             continue
         for _ in range(args.updates_per_step):
-            learner.update(replay, args.seed, updates)
+            latest = learner.update(replay, args.seed, updates)
             updates += 1
             if updates % args.eval_every == 0:
                 evaluate()

@@ -466,6 +466,22 @@ class SacHindsight(C.Structure):
     _fields_ = [("relabel_threshold", C.c_uint64), ("strategy", C.c_int32), ("horizon", C.c_int32), ("reserved0", C.c_int64)]
 
 
+GRAD_NORM_ACTOR_TENSORS, GRAD_NORM_CRITIC_TENSORS = 8, 12  # the tensors of the two groups of urgym_*_grad_norm, in their fixed order
+GRAD_NORM_EPS = 1e-6  # torch.nn.utils.clip_grad_norm_'s: c64 = max_norm / (norm64 + GRAD_NORM_EPS)
+
+
+class GradNorm(C.Structure):
+    """urgym_grad_norm: the bound and the three outputs of urgym_actor_grad_norm / urgym_critic_grad_norm (tensor_sums_out may be NULL)."""
+    _fields_ = [("max_norm", C.c_float), ("reserved0", C.c_int32), ("norm_out", C.POINTER(C.c_float)), ("scale_out", C.POINTER(C.c_float)),
+                ("tensor_sums_out", C.POINTER(C.c_double))]
+
+
+class SacClipping(C.Structure):
+    """urgym_sac_clipping: the bound, the [2] scratch of the two coefficients and the two norm slots per update of urgym_sac_train_clipped."""
+    _fields_ = [("max_grad_norm", C.c_float), ("reserved0", C.c_int32), ("scale", C.POINTER(C.c_float)), ("critic_grad_norm", C.POINTER(C.c_float)),
+                ("actor_grad_norm", C.POINTER(C.c_float))]
+
+
 PER_FANOUT = 256  # URGYM_PER_FANOUT: the fan-out of the priority sums
 PER_TERMS_MAX_COUNT = 65536  # URGYM_PER_TERMS_MAX_COUNT
 PER_TAG = 0x50455200  # word 3 of the Philox counter of urgym_replay_sample_prioritized's draw
@@ -556,6 +572,11 @@ EXPORTED_SYMBOLS = [
     "urgym_sac_train_prioritized",
     "urgym_replay_sample_hindsight",
     "urgym_sac_train_hindsight",
+    "urgym_actor_grad_norm",
+    "urgym_critic_grad_norm",
+    "urgym_actor_adam_step_scaled",
+    "urgym_critic_adam_step_scaled",
+    "urgym_sac_train_clipped",
     "urgym_actor_read_packed",
     "urgym_critic_read_packed",
     "urgym_refresh",

@@ -117,6 +117,14 @@ def lib():
                                                 C.POINTER(_abi.ReplayBatch), C.POINTER(_abi.ReplayHindsight), C.c_void_p]
     L.urgym_sac_train_hindsight.argtypes = [C.c_void_p, C.POINTER(_abi.SacLearner), C.POINTER(_abi.SacSchedule), C.POINTER(_abi.SacHindsight),
                                             C.POINTER(_abi.SacEvaluation), C.POINTER(_abi.SacMonitoring), C.c_void_p]
+    L.urgym_actor_grad_norm.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.ActorTensors), C.POINTER(_abi.GradNorm), C.c_void_p]
+    L.urgym_critic_grad_norm.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.QNetworkDev), C.POINTER(_abi.GradNorm), C.c_void_p]
+    L.urgym_actor_adam_step_scaled.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.ActorAdam), C.POINTER(_abi.AdamHyper), C.c_void_p, C.c_void_p]
+    L.urgym_critic_adam_step_scaled.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(_abi.CriticAdam), C.POINTER(_abi.AdamHyper), C.c_float,
+                                                C.c_void_p, C.c_void_p]
+    L.urgym_sac_train_clipped.argtypes = [C.c_void_p, C.POINTER(_abi.SacLearner), C.POINTER(_abi.SacSchedule), C.POINTER(_abi.SacClipping),
+                                          C.POINTER(_abi.SacNstep), C.POINTER(_abi.SacPrioritized), C.POINTER(_abi.SacHindsight),
+                                          C.POINTER(_abi.SacEvaluation), C.POINTER(_abi.SacMonitoring), C.c_void_p]
     L.urgym_actor_read_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.urgym_critic_read_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.urgym_refresh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]

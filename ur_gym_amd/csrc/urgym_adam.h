@@ -71,5 +71,11 @@ void actor_adam_launch(const ActorPacked& a, const AdamTensors<PACK_ACTOR_TENSOR
 void critic_adam_launch(const CriticPacked& online, const CriticPacked* target, const AdamTensors<2 * PACK_CRITIC_TENSORS>& t, const AdamCoef& c,
                         float tau, hipStream_t s);
 
+// The two launches above with the clipped element of urgym_grad_clip.h: `scale` is a DEVICE scalar (what urgym_*_grad_norm wrote
+// earlier on `s`), read when the launch runs; every gradient element is multiplied by it as it is read.  Kernels of their own.
+void actor_adam_scaled_launch(const ActorPacked& a, const AdamTensors<PACK_ACTOR_TENSORS>& t, const AdamCoef& c, const float* scale, hipStream_t s);
+void critic_adam_scaled_launch(const CriticPacked& online, const CriticPacked* target, const AdamTensors<2 * PACK_CRITIC_TENSORS>& t, const AdamCoef& c,
+                               float tau, const float* scale, hipStream_t s);
+
 }  // namespace urgym
 #endif

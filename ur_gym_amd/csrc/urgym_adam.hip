@@ -14,9 +14,13 @@
 // This unit is built with -ffp-contract=off: every line of adam_element and of the blend is one operation rounded on its own, with no
 // device to keep the compiler from fusing them.  Division and square root are the correctly rounded ones (hipcc's default), and the
 // unit's float32 denormal mode keeps subnormals.
+//
+// The clipped steps (actor_adam_scaled_kernel, critic_adam_scaled_kernel) are the same two bodies with the
+// element of urgym_grad_clip.h: separate kernels, so that the device code of the two unclipped ones is what it was without them.
 #include <hip/hip_runtime.h>
 
 #include "urgym_adam.h"
+#include "urgym_grad_clip.h"
 #include "urgym_pack_map.h"
 
 namespace urgym {
@@ -53,9 +57,10 @@ __device__ __forceinline__ T* pick(T* const (&src)[N], int t) {
   return p;
 }
 
-// steps the four elements quad `m` names and returns the quad of the packed buffer: p' where an offset is given, +0.0f where not
-template <int N>
-__device__ __forceinline__ float4 step_quad(const AdamTensors<N>& t, const PackQuad& m, const AdamCoef& c) {
+// steps the four elements quad `m` names and returns the quad of the packed buffer: p' where an offset is given, +0.0f where not.
+// SCALED: the element of urgym_grad_clip.h, gs = g * scale first (the clipped steps); otherwise `scale` is not looked at.
+template <int N, bool SCALED = false>
+__device__ __forceinline__ float4 step_quad(const AdamTensors<N>& t, const PackQuad& m, const AdamCoef& c, float scale = 1.0f) {
   float* const p = pick(t.param, m.tensor);
   const float* const g = pick(t.grad, m.tensor);
   float* const ea = pick(t.exp_avg, m.tensor);
@@ -67,7 +72,10 @@ __device__ __forceinline__ float4 step_quad(const AdamTensors<N>& t, const PackQ
     const int o = m.off[k];
     if (o >= 0) {
       float pv = p[o], mv = ea[o], vv = es[o];
-      adam_element(c, g[o], pv, mv, vv);
+      if (SCALED)
+        adam_element_scaled(c, g[o], scale, pv, mv, vv);
+      else
+        adam_element(c, g[o], pv, mv, vv);
       p[o] = pv, ea[o] = mv, es[o] = vv;
       out[k] = pv;
     }
@@ -108,6 +116,49 @@ __global__ void __launch_bounds__(ADAM_THREADS) critic_adam_kernel(const CriticA
   P.target[q] = v;
 }
 
+// The clipped steps (include/urgym.h, urgym_actor_adam_step_scaled / urgym_critic_adam_step_scaled): the two kernels above, line for
+// line, with the clip coefficient -- a DEVICE scalar a urgym_*_grad_norm launch earlier on the stream wrote -- read once per lane and
+// every gradient element multiplied by it as it is read.  Kernels of their own: the two above are not touched by their existence.
+struct ActorAdamScaledParams {
+  ActorAdamParams p;
+  const float* scale;
+};
+
+struct CriticAdamScaledParams {
+  CriticAdamParams p;
+  const float* scale;
+};
+
+__global__ void __launch_bounds__(ADAM_THREADS) actor_adam_scaled_kernel(const ActorAdamScaledParams S) {
+  const ActorAdamParams& P = S.p;
+  const uint32_t q = blockIdx.x * ADAM_THREADS + threadIdx.x;
+  if (q >= P.quads) return;
+  const float scale = S.scale[0];
+  PackQuad m;
+  pack_quad_actor(P.d, q, m);
+  P.packed[q] = step_quad<PACK_ACTOR_TENSORS, true>(P.t, m, P.c, scale);
+}
+
+__global__ void __launch_bounds__(ADAM_THREADS) critic_adam_scaled_kernel(const CriticAdamScaledParams S) {
+  const CriticAdamParams& P = S.p;
+  const uint32_t q = blockIdx.x * ADAM_THREADS + threadIdx.x;
+  if (q >= P.quads) return;
+  const float scale = S.scale[0];
+  PackQuad m;
+  pack_quad_critic(P.d, q, m);
+  float4 v = step_quad<2 * PACK_CRITIC_TENSORS, true>(P.t, m, P.c, scale);
+  P.online[q] = v;
+  if (!P.target) return;
+  if (P.blend) {  // tau == 1 never reads the old value
+    const float4 o = P.target[q];
+    v.x = polyak(o.x, v.x, P.tau, P.omt);
+    v.y = polyak(o.y, v.y, P.tau, P.omt);
+    v.z = polyak(o.z, v.z, P.tau, P.omt);
+    v.w = polyak(o.w, v.w, P.tau, P.omt);
+  }
+  P.target[q] = v;
+}
+
 }  // namespace
 
 void actor_adam_launch(const ActorPacked& a, const AdamTensors<PACK_ACTOR_TENSORS>& t, const AdamCoef& c, hipStream_t s) {
@@ -132,6 +183,34 @@ void critic_adam_launch(const CriticPacked& online, const CriticPacked* target, 
   P.tau = target ? tau : 1.0f, P.omt = 1.0f - P.tau;
   P.c = c;
   hipLaunchKernelGGL(critic_adam_kernel, dim3((P.quads + ADAM_THREADS - 1) / ADAM_THREADS), dim3(ADAM_THREADS), 0, s, P);
+}
+
+void actor_adam_scaled_launch(const ActorPacked& a, const AdamTensors<PACK_ACTOR_TENSORS>& t, const AdamCoef& c, const float* scale, hipStream_t s) {
+  ActorAdamScaledParams S;
+  ActorAdamParams& P = S.p;
+  P.packed = reinterpret_cast<float4*>(a.weights);
+  P.t = t;
+  P.d = pack_dims_actor(a.in_features, a.hidden);
+  P.quads = (uint32_t)(pack_actor_floats(P.d) / 4);
+  P.c = c;
+  S.scale = scale;
+  hipLaunchKernelGGL(actor_adam_scaled_kernel, dim3((P.quads + ADAM_THREADS - 1) / ADAM_THREADS), dim3(ADAM_THREADS), 0, s, S);
+}
+
+void critic_adam_scaled_launch(const CriticPacked& online, const CriticPacked* target, const AdamTensors<2 * PACK_CRITIC_TENSORS>& t, const AdamCoef& c,
+                               float tau, const float* scale, hipStream_t s) {
+  CriticAdamScaledParams S;
+  CriticAdamParams& P = S.p;
+  P.online = reinterpret_cast<float4*>(online.weights);
+  P.target = target ? reinterpret_cast<float4*>(target->weights) : nullptr;
+  P.t = t;
+  P.d = pack_dims_critic(online.in_features, online.hidden);
+  P.quads = (uint32_t)(pack_critic_floats(P.d) / 4);
+  P.blend = target && tau != 1.0f;
+  P.tau = target ? tau : 1.0f, P.omt = 1.0f - P.tau;
+  P.c = c;
+  S.scale = scale;
+  hipLaunchKernelGGL(critic_adam_scaled_kernel, dim3((P.quads + ADAM_THREADS - 1) / ADAM_THREADS), dim3(ADAM_THREADS), 0, s, S);
 }
 
 }  // namespace urgym

@@ -1,5 +1,5 @@
 // urgym_policy_abi.hip — the learner's half of the C-ABI of include/urgym.h: actors (create / forward / sample / rollouts), the replay
-// ring, the weight reloads and their inverse (urgym_actor_unpack, urgym_critic_unpack), the twin critic and its two gradients, the actor's parameter gradients, the Adam steps, SAC's entropy step and loss terms, the training loop that composes them in one call (urgym_sac_train; its index arithmetic is urgym_sac_schedule.h), the evaluation inside that call (urgym_eval_stats, urgym_actor_snapshot, urgym_policy_evaluate, urgym_sac_train_evaluated; urgym_eval.h, urgym_eval_schedule.h), and the training-episode statistics inside it (urgym_monitor_fold, urgym_monitor_stats, urgym_sac_train_monitored; urgym_monitor.h), and the multi-step returns (urgym_replay_sample_nstep, urgym_sac_entropy_step_nstep, urgym_sac_train_nstep; urgym_nstep.h), and prioritized replay (urgym_per_sums_count, urgym_per_rebuild, urgym_per_fill, urgym_replay_sample_prioritized, urgym_per_terms; urgym_per.h), and hindsight experience replay (urgym_replay_sample_hindsight, urgym_sac_train_hindsight; urgym_her.h).  Host code only: every check is made here, before the first launch,
+// ring, the weight reloads and their inverse (urgym_actor_unpack, urgym_critic_unpack), the twin critic and its two gradients, the actor's parameter gradients, the Adam steps, SAC's entropy step and loss terms, the training loop that composes them in one call (urgym_sac_train; its index arithmetic is urgym_sac_schedule.h), the evaluation inside that call (urgym_eval_stats, urgym_actor_snapshot, urgym_policy_evaluate, urgym_sac_train_evaluated; urgym_eval.h, urgym_eval_schedule.h), and the training-episode statistics inside it (urgym_monitor_fold, urgym_monitor_stats, urgym_sac_train_monitored; urgym_monitor.h), and the multi-step returns (urgym_replay_sample_nstep, urgym_sac_entropy_step_nstep, urgym_sac_train_nstep; urgym_nstep.h), and prioritized replay (urgym_per_sums_count, urgym_per_rebuild, urgym_per_fill, urgym_replay_sample_prioritized, urgym_per_terms; urgym_per.h), and hindsight experience replay (urgym_replay_sample_hindsight, urgym_sac_train_hindsight; urgym_her.h), and gradient-norm clipping (urgym_actor_grad_norm, urgym_critic_grad_norm, the two scaled Adam steps, urgym_sac_train_clipped; urgym_grad_clip.h).  Host code only: every check is made here, before the first launch,
 // and every launch goes through urgym_actor.h, urgym_critic.h, urgym_replay.h, urgym_weights.h, urgym_adam.h, urgym_sac_terms.h, urgym_eval.h, urgym_monitor.h and urgym_per.h, or through do_step of urgym_hip.hip
 // (urgym_handle.h).  No kernel lives in this unit, so adding a check here leaves the step kernels' object file alone.
 #include <hip/hip_runtime.h>
@@ -25,6 +25,7 @@
 #include "urgym_eval_schedule.h"
 #include "urgym_monitor.h"
 #include "urgym_per.h"
+#include "urgym_grad_clip.h"
 
 using namespace urgym;
 
@@ -377,6 +378,57 @@ int check_critic_adam(Handle* h, void* online, void* target_or_NULL, const urgym
   return URGYM_OK;
 }
 
+// ---- gradient-norm clipping (include/urgym.h, urgym_actor_grad_norm ... urgym_sac_train_clipped)
+
+// what both norm calls refuse about their args
+int check_grad_norm_args(Handle* h, const urgym_grad_norm* args, const char* who, GradNormCall* out) {
+  if (!args) return fail_in(h, URGYM_ERR_ARG, who, "null args");
+  if (args->reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "urgym_grad_norm.reserved0 must be 0");
+  if (!(args->max_norm > 0.0f && args->max_norm < INFINITY)) return fail_in(h, URGYM_ERR_ARG, who, "max_norm must be finite and positive");  // refuses NaN too
+  if (!args->norm_out || !args->scale_out) return fail_in(h, URGYM_ERR_ARG, who, "norm_out or scale_out is null");
+  if ((uintptr_t)args->tensor_sums_out % 8 != 0) return fail_in(h, URGYM_ERR_ARG, who, "tensor_sums_out must be 8-byte aligned");
+  out->max_norm = args->max_norm, out->norm_out = args->norm_out, out->scale_out = args->scale_out, out->tensor_sums_out = args->tensor_sums_out;
+  return URGYM_OK;
+}
+
+int check_actor_grad_norm(Handle* h, void* actor, const urgym_actor_tensors_const* grad, const urgym_grad_norm* args, const char* who, GradNormCall* out) {
+  static_assert(GRAD_NORM_ACTOR_TENSORS == 8 && GRAD_NORM_CRITIC_TENSORS == 12, "include/urgym.h");
+  Actor* a = member(h->actors, actor);
+  if (!a) return fail_in(h, URGYM_ERR_ARG, who, "not an actor of this handle (actors belong to the handle they were created with)");
+  if (!grad) return fail_in(h, URGYM_ERR_ARG, who, "null grad");
+  const ActorPacked buf = actor_packed(a);
+  const int n = buf.in_features, H = buf.hidden;
+  const float* const gs[GRAD_NORM_ACTOR_TENSORS] = {grad->w0, grad->b0, grad->w1, grad->b1, grad->w_mu, grad->b_mu, grad->w_log_std, grad->b_log_std};
+  const int counts[GRAD_NORM_ACTOR_TENSORS] = {H * n, H, H * H, H, 6 * H, 6, 6 * H, 6};
+  memset(out, 0, sizeof(*out));
+  out->tensors = GRAD_NORM_ACTOR_TENSORS;
+  for (int i = 0; i < GRAD_NORM_ACTOR_TENSORS; i++) {
+    if (!gs[i]) return fail_in(h, URGYM_ERR_ARG, who, "a tensor pointer is null (all 8 are required)");
+    out->grad[i] = gs[i], out->count[i] = counts[i];
+  }
+  return check_grad_norm_args(h, args, who, out);
+}
+
+int check_critic_grad_norm(Handle* h, void* critic, const urgym_q_network_dev* grad, const urgym_grad_norm* args, const char* who, GradNormCall* out) {
+  Critic* c = member(h->critics, critic);
+  if (!c) return fail_in(h, URGYM_ERR_ARG, who, "not a critic of this handle (critics belong to the handle they were created with)");
+  if (!grad) return fail_in(h, URGYM_ERR_ARG, who, "null grad");
+  const CriticPacked buf = critic_packed(c);
+  const int n = buf.in_features, H = buf.hidden;
+  const int counts[PACK_CRITIC_TENSORS] = {H * n, H, H * H, H, H, 1};
+  memset(out, 0, sizeof(*out));
+  out->tensors = GRAD_NORM_CRITIC_TENSORS;
+  for (int net = 0; net < 2; net++) {
+    const urgym_q_network_dev& g = grad[net];
+    const float* const gs[PACK_CRITIC_TENSORS] = {g.w0, g.b0, g.w1, g.b1, g.w_q, g.b_q};
+    for (int i = 0; i < PACK_CRITIC_TENSORS; i++) {
+      if (!gs[i]) return fail_in(h, URGYM_ERR_ARG, who, "a tensor pointer is null (all 12 are required)");
+      out->grad[PACK_CRITIC_TENSORS * net + i] = gs[i], out->count[PACK_CRITIC_TENSORS * net + i] = counts[i];
+    }
+  }
+  return check_grad_norm_args(h, args, who, out);
+}
+
 int check_entropy_step(Handle* h, const urgym_sac_entropy_args* args, const urgym_adam_hyper* hp, const char* who, SacEntropyCall* out) {
   static_assert(URGYM_SAC_TERMS_MAX_COUNT == SAC_TERMS_MAX_COUNT, "include/urgym.h");
   if (!args) return fail_in(h, URGYM_ERR_ARG, who, "null args");
@@ -670,6 +722,53 @@ int urgym_critic_adam_step(void* handle, void* online, void* target_or_NULL, con
   if (int rc = check_critic_adam(h, online, target_or_NULL, t, hp, tau, "urgym_critic_adam_step", &step)) return rc;
   HIP_TRY(h, hipSetDevice(h->device));
   critic_adam_launch(step.buf, step.has_target ? &step.target_buf : nullptr, step.T, adam_coef(*hp), tau, (hipStream_t)stream);
+  return launched(h);
+}
+
+// ---- gradient-norm clipping (urgym_grad_clip.hip, the scaled kernels of urgym_adam.hip): everything is checked here, before the launch
+int urgym_actor_grad_norm(void* handle, void* actor, const urgym_actor_tensors_const* grad, const urgym_grad_norm* args, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  GradNormCall c;
+  if (int rc = check_actor_grad_norm(h, actor, grad, args, "urgym_actor_grad_norm", &c)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  grad_norm_launch(c, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_critic_grad_norm(void* handle, void* critic, const urgym_q_network_dev grad[2], const urgym_grad_norm* args, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  GradNormCall c;
+  if (int rc = check_critic_grad_norm(h, critic, grad, args, "urgym_critic_grad_norm", &c)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  grad_norm_launch(c, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_actor_adam_step_scaled(void* handle, void* actor, const urgym_actor_adam* t, const urgym_adam_hyper* hp, const float* scale_dev, void* stream) {
+  const char* who = "urgym_actor_adam_step_scaled";
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  ActorAdamStep step;
+  if (int rc = check_actor_adam(h, actor, t, hp, who, &step)) return rc;
+  if (!scale_dev) return fail_in(h, URGYM_ERR_ARG, who, "null scale_dev");
+  HIP_TRY(h, hipSetDevice(h->device));
+  actor_adam_scaled_launch(step.buf, step.T, adam_coef(*hp), scale_dev, (hipStream_t)stream);
+  HIP_TRY(h, hipGetLastError());
+  actor_mark_log_std(step.a);  // as urgym_actor_adam_step
+  return URGYM_OK;
+}
+
+int urgym_critic_adam_step_scaled(void* handle, void* online, void* target_or_NULL, const urgym_critic_adam* t, const urgym_adam_hyper* hp, float tau, const float* scale_dev, void* stream) {
+  const char* who = "urgym_critic_adam_step_scaled";
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  CriticAdamStep step;
+  if (int rc = check_critic_adam(h, online, target_or_NULL, t, hp, tau, who, &step)) return rc;
+  if (!scale_dev) return fail_in(h, URGYM_ERR_ARG, who, "null scale_dev");
+  HIP_TRY(h, hipSetDevice(h->device));
+  critic_adam_scaled_launch(step.buf, step.has_target ? &step.target_buf : nullptr, step.T, adam_coef(*hp), tau, scale_dev, (hipStream_t)stream);
   return launched(h);
 }
 
@@ -1190,9 +1289,10 @@ struct TrainHooks {
 };
 
 // `nstep`: null = the one-step update; given (urgym_sac_train_nstep) = the update whose gather, third call and entropy step are the
-// multi-step ones.  `her`: given (urgym_sac_train_hindsight) = the update whose gather is urgym_replay_sample_hindsight
+// multi-step ones.  `her`: given (urgym_sac_train_hindsight) = the update whose gather is urgym_replay_sample_hindsight.  `clip`: given
+// (urgym_sac_train_clipped) = the update with the two norm launches and the scaled steps
 int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, void* stream, const TrainHooks* hooks, const urgym_sac_nstep* nstep = nullptr,
-                   const urgym_sac_prioritized* per = nullptr, const urgym_sac_hindsight* her = nullptr);
+                   const urgym_sac_prioritized* per = nullptr, const urgym_sac_hindsight* her = nullptr, const urgym_sac_clipping* clip = nullptr);
 
 }  // namespace
 
@@ -1205,7 +1305,7 @@ int urgym_sac_train(void* handle, const urgym_sac_learner* learner, const urgym_
 namespace {
 
 int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, void* stream, const TrainHooks* hooks, const urgym_sac_nstep* nstep,
-                   const urgym_sac_prioritized* per, const urgym_sac_hindsight* her) {
+                   const urgym_sac_prioritized* per, const urgym_sac_hindsight* her, const urgym_sac_clipping* clip) {
   Handle* h = (Handle*)handle;
   if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
   if (!learner) return fail_in(h, URGYM_ERR_ARG, who, "null learner");
@@ -1261,6 +1361,13 @@ int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learn
     if (!(per->eps > 0.0f && per->eps < INFINITY)) return fail_in(h, URGYM_ERR_ARG, who, "eps must be positive and finite");
     if (!per->leaf || !per->total || !per->q || !per->w_raw || !per->w || !per->dq || !per->new_leaf)
       return fail_in(h, URGYM_ERR_ARG, who, "a scratch pointer of urgym_sac_prioritized is null (leaf, total, q, w_raw, w, dq, new_leaf)");
+  }
+  if (clip) {  // the option's own refusals, whether or not the call holds an update
+    if (clip->reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_clipping.reserved0 must be 0");
+    if (!(clip->max_grad_norm > 0.0f && clip->max_grad_norm < INFINITY)) return fail_in(h, URGYM_ERR_ARG, who, "max_grad_norm must be finite and positive");
+    if (!clip->scale) return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_clipping.scale is null");
+    if ((!clip->critic_grad_norm || !clip->actor_grad_norm) && sac_schedule_updates(S) > 0)  // zero slots need no array
+      return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_clipping.critic_grad_norm or actor_grad_norm is null");
   }
 
   // ---- the checking halves, with the numbers of the first collection and the first update
@@ -1384,6 +1491,11 @@ int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learn
     return rc;
   CriticAdamStep critic_step;
   if (int rc = check_critic_adam(h, L.online, L.target, &L.critic_adam, &hp, L.tau, who, &critic_step)) return rc;
+  GradNormCall critic_norm, actor_norm;
+  if (clip) {
+    const urgym_grad_norm na{clip->max_grad_norm, 0, clip->critic_grad_norm, clip->scale, nullptr};
+    if (int rc = check_critic_grad_norm(h, L.online, L.critic_adam.grad, &na, who, &critic_norm)) return rc;
+  }
   const urgym_critic_grad_out go{nullptr, L.dqmin_da, nullptr, L.q_min};
   CriticGradCall action_gradient;
   if (int rc = check_critic_action_gradient(h, L.online, &policy_rows, M, &go, who, &online_grad, &action_gradient)) return rc;
@@ -1410,6 +1522,10 @@ int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learn
     return rc;
   ActorAdamStep actor_step;
   if (int rc = check_actor_adam(h, L.actor, &L.actor_adam, &hp, who, &actor_step)) return rc;
+  if (clip) {
+    const urgym_grad_norm na{clip->max_grad_norm, 0, clip->actor_grad_norm, clip->scale + 1, nullptr};
+    if (int rc = check_actor_grad_norm(h, L.actor, &L.actor_adam.grad, &na, who, &actor_norm)) return rc;
+  }
 
   if (hooks)
     if (int rc = hooks->before_launch(hooks->ctx)) return rc;
@@ -1469,7 +1585,14 @@ int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learn
       }
       critic_backward_launch(online, critic_backward, s);
       if (int rc = train_stage(h, who, i, "critic_parameter_gradients")) return rc;
-      critic_adam_launch(critic_step.buf, &critic_step.target_buf, critic_step.T, coef, critic_step.tau, s);
+      if (clip) {
+        critic_norm.norm_out = clip->critic_grad_norm + up.loss_slot;
+        grad_norm_launch(critic_norm, s);
+        if (int rc = train_stage(h, who, i, "critic_grad_norm")) return rc;
+        critic_adam_scaled_launch(critic_step.buf, &critic_step.target_buf, critic_step.T, coef, critic_step.tau, clip->scale, s);
+      } else {
+        critic_adam_launch(critic_step.buf, &critic_step.target_buf, critic_step.T, coef, critic_step.tau, s);
+      }
       if (int rc = train_stage(h, who, i, "critic_adam_step")) return rc;
       critic_grad_launch(online_grad, action_gradient, s);
       if (int rc = train_stage(h, who, i, "critic_action_gradient")) return rc;
@@ -1479,7 +1602,14 @@ int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learn
       actor_backward.draw = up.policy_draw;
       actor_backward_launch(actor, actor_backward, s);
       if (int rc = train_stage(h, who, i, "actor_parameter_gradients")) return rc;
-      actor_adam_launch(actor_step.buf, actor_step.T, coef, s);
+      if (clip) {
+        actor_norm.norm_out = clip->actor_grad_norm + up.loss_slot;
+        grad_norm_launch(actor_norm, s);
+        if (int rc = train_stage(h, who, i, "actor_grad_norm")) return rc;
+        actor_adam_scaled_launch(actor_step.buf, actor_step.T, coef, clip->scale + 1, s);
+      } else {
+        actor_adam_launch(actor_step.buf, actor_step.T, coef, s);
+      }
       if (int rc = train_stage(h, who, i, "actor_adam_step")) return rc;
       actor_mark_log_std(actor_step.a);  // as urgym_actor_adam_step; the checks above have required the head already
     }
@@ -1902,6 +2032,29 @@ int urgym_sac_train_hindsight(void* handle, const urgym_sac_learner* learner, co
     return sac_train_body(who, handle, learner, schedule, stream, &hooks, nullptr, nullptr, hindsight);
   }
   return sac_train_body(who, handle, learner, schedule, stream, nullptr, nullptr, nullptr, hindsight);
+}
+
+int urgym_sac_train_clipped(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_clipping* clipping, const urgym_sac_nstep* nstep_or_NULL, const urgym_sac_prioritized* prioritized_or_NULL, const urgym_sac_hindsight* hindsight_or_NULL, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream) {
+  const char* who = "urgym_sac_train_clipped";
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (!clipping) return fail_in(h, URGYM_ERR_ARG, who, "null clipping");
+  if ((nstep_or_NULL != nullptr) + (prioritized_or_NULL != nullptr) + (hindsight_or_NULL != nullptr) > 1)
+    return fail_in(h, URGYM_ERR_ARG, who, "at most one of nstep, prioritized and hindsight may be given (each has a gather of its own)");
+  TrainEvaluation e;
+  e.h = h, e.learner = learner, e.schedule = schedule, e.evaluation = evaluation_or_NULL, e.s = (hipStream_t)stream, e.done = 0, e.who = who;
+  TrainMonitoring t;
+  t.h = h, t.learner = learner, t.schedule = schedule, t.monitoring = monitoring_or_NULL, t.s = (hipStream_t)stream, t.done = 0;
+  t.evaluation = evaluation_or_NULL ? &e : nullptr, t.who = who;
+  if (monitoring_or_NULL) {
+    const TrainHooks hooks{train_monitoring_check, train_monitoring_after, &t};
+    return sac_train_body(who, handle, learner, schedule, stream, &hooks, nstep_or_NULL, prioritized_or_NULL, hindsight_or_NULL, clipping);
+  }
+  if (evaluation_or_NULL) {
+    const TrainHooks hooks{train_evaluation_check, train_evaluation_after, &e};
+    return sac_train_body(who, handle, learner, schedule, stream, &hooks, nstep_or_NULL, prioritized_or_NULL, hindsight_or_NULL, clipping);
+  }
+  return sac_train_body(who, handle, learner, schedule, stream, nullptr, nstep_or_NULL, prioritized_or_NULL, hindsight_or_NULL, clipping);
 }
 
 }  // extern "C"

@@ -216,7 +216,7 @@ def adam_coefficients(env, lr, betas=(0.9, 0.999), eps=1e-8, step=1):
     return np.array(out[:], dtype=np.float32)
 
 
-def adam_step(p, g, m, v, coef):
+def adam_step(p, g, m, v, coef, scale=None):
     """The per-element arithmetic of urgym_actor_adam_step / urgym_critic_adam_step, restated from include/urgym.h in numpy float32:
     returns (p', m', v').  `coef`: the seven numbers of ``adam_coefficients``.  Every line is one operation rounded to float32 on its
     own (numpy's float32 sqrt and division are the correctly rounded ones, and subnormals are kept)::
@@ -225,6 +225,9 @@ def adam_step(p, g, m, v, coef):
         gg = g * g          v' = (b2 * v) + (omb2 * gg)
         s  = sqrt(v')       d  = (s / bc2_sqrt) + eps
         u  = m' / d         p' = p - (step_size * u)
+
+    With `scale` (a float32 scalar: ``grad_norm(...)["scale"]``) it is the element of urgym_*_adam_step_scaled: ``gs = g * scale``
+    first, one float32 multiply rounded on its own, then the lines above on gs.  ``None`` is exactly the step without it.
     """
     f = np.float32
     coef = np.asarray(coef)
@@ -234,6 +237,13 @@ def adam_step(p, g, m, v, coef):
     p, g, m, v = (np.asarray(x, dtype=f) for x in (p, g, m, v))
     if not (p.shape == g.shape == m.shape == v.shape):
         raise ValueError(f"p, g, m, v must have one shape, got {p.shape}, {g.shape}, {m.shape}, {v.shape}")
+    if scale is not None:
+        scale = np.asarray(scale)
+        if scale.dtype != f or scale.size != 1:
+            raise ValueError(f"scale must be one float32 (grad_norm's), got {scale.dtype} {scale.shape}")
+        with np.errstate(all="ignore"):
+            g = g * scale.reshape(())
+        assert g.dtype == f, g.dtype
     with np.errstate(all="ignore"):  # underflow of g * g, overflow and NaN are inputs the step is defined on
         m_old = b1 * m
         m_in = omb1 * g
@@ -273,6 +283,52 @@ def ordered_sum(terms, dtype=np.float32):
             partial[:s] += partial[s:2 * s]
             s //= 2
     return np.float64(partial[0])
+
+
+def grad_group(tensors):
+    """The gradient tensors of one optimiser as the flat float32 arrays of urgym_*_grad_norm's group, in its FIXED order: a dict under
+    ACTOR_ARRAYS + LOG_STD_ARRAYS (the actor's eight), a list of two dicts under CRITIC_ARRAYS (both Q-networks, network 0 first: one
+    group), or a sequence of arrays taken in the order given.  torch tensors are copied to the host."""
+    def host(x):
+        x = x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+        if x.dtype != np.float32:
+            raise ValueError(f"gradient tensors must be float32, got {x.dtype}")
+        return np.ascontiguousarray(x).reshape(-1)
+
+    if isinstance(tensors, dict):
+        return [host(tensors[k]) for k in ACTOR_ARRAYS + LOG_STD_ARRAYS]
+    tensors = list(tensors)
+    if tensors and all(isinstance(w, dict) for w in tensors):
+        if len(tensors) != 2:
+            raise ValueError(f"the critics' group is two networks, got {len(tensors)}")
+        return [host(w[k]) for w in tensors for k in CRITIC_ARRAYS]
+    return [host(x) for x in tensors]
+
+
+def grad_norm(tensors, max_norm):
+    """urgym_actor_grad_norm / urgym_critic_grad_norm restated from include/urgym.h in numpy.  `tensors`: what ``grad_group`` takes.
+    Returns a dict: ``tensor_sums`` (float64 [k]: per tensor THE ORDERED SUM, ``ordered_sum(..., dtype=np.float64)``, of the exact
+    float64 squares of its flat elements), ``total`` (float64: ((s_0 + s_1) + s_2) + ..., tensor order), ``norm64`` =
+    sqrt(total) (numpy's float64 sqrt is the correctly rounded one), ``scale`` (float32: c64 = max_norm / (norm64 + 1e-6) rounded to
+    float32 where c64 < 1, else 1 -- so a NaN norm gives 1) and ``norm`` (float32 of norm64, for the record).  `max_norm` is taken as
+    the float32 the library is handed."""
+    from ._abi import GRAD_NORM_EPS
+
+    group = grad_group(tensors)
+    with np.errstate(over="ignore"):
+        max32 = np.float32(max_norm)
+    if not (np.isfinite(max32) and max32 > 0):
+        raise ValueError(f"max_norm must be finite and positive in float32, got {max_norm!r}")
+    with np.errstate(all="ignore"):
+        sums = np.array([ordered_sum(g.astype(np.float64) * g.astype(np.float64), dtype=np.float64) for g in group], dtype=np.float64)
+        total = np.float64(sums[0])
+        for s_k in sums[1:]:
+            total = np.float64(total + s_k)
+        norm64 = np.sqrt(total)
+        c64 = np.float64(max32) / np.float64(norm64 + np.float64(GRAD_NORM_EPS))
+        scale = np.float32(c64) if c64 < 1.0 else np.float32(1.0)
+        norm = np.float32(norm64)
+    return dict(tensor_sums=sums, total=total, norm64=norm64, norm=norm, scale=scale)
 
 
 def _ordered_mean(terms):

@@ -46,6 +46,11 @@ minibatch gather on the HIP kernels, and gradients and optimisers in torch autog
     urgym_replay_sample_nstep), the third launch writes min_i Q_i'(s', a') alone, and ``env.entropy_step_nstep`` forms
     y = R + gamma^m (1 - terminated) (min Q' - alpha log pi(a'|s')) from the row's own discount: still thirteen launches.
     ``n_steps`` = 1, the default, makes exactly the calls above.
+    With ``max_grad_norm=X`` (it needs ``device_entropy=True``) each of the two Adam steps is preceded by ONE launch that reduces the
+    global norm of its gradients on the device and leaves the clip coefficient there (``env.critic_gradient_norm``,
+    ``env.actor_gradient_norm``), and the step multiplies each gradient element by it as it reads it (``scale=``): fifteen launches.
+    The ``.grad`` tensors are not written, the temperature's scalar step is not clipped.  ``None``, the default, makes exactly the
+    calls above.
     None of them synchronises with the host.  ``train`` runs the whole loop in one native call and, given an
     ``evaluation.DeviceEvaluation``, the reference's EvalCallback inside it: evaluations of the deterministic policy at a fixed interval of
     updates, their statistics as records on the device, and the best actor's tensors, which ``DeviceEvaluation.save_best`` writes as an
@@ -74,6 +79,10 @@ PER_DEFAULTS = dict(prioritized=False, per_beta=0.4, per_beta_steps=100000)
 # Hindsight experience replay: the options of SACLearner(hindsight=True), SB3's HerReplayBuffer arguments.  Kept
 # apart like PER_DEFAULTS: a run without hindsight saves none of them, so its checkpoint is what it was before the option existed.
 HER_DEFAULTS = dict(hindsight=False, her_n_sampled_goal=4, her_strategy="future")
+# Gradient-norm clipping: SACLearner(max_grad_norm=X) clips the critics' and the actor's gradients by their global
+# norm, torch.nn.utils.clip_grad_norm_'s idiom on the device.  SB3's SAC does not clip; None, the default, is the learner as it was.  Kept
+# apart like the two above: a run without it saves no new key.
+CLIP_DEFAULTS = dict(max_grad_norm=None)
 
 
 def _mlp(n_in, hidden, n_out=None):
@@ -157,14 +166,26 @@ class SACLearner:
     all five ``device_*`` options and a ``DevicePrioritizedReplay``) draws each minibatch in proportion to the transitions' priorities and
     weights the critics' gradient by the importance weights; not together with ``n_steps`` > 1.  ``hindsight=True``
     (HER_DEFAULTS: ``her_n_sampled_goal``, ``her_strategy`` "future" or "final"; needs ``device_entropy=True``) relabels the goals of each
-    minibatch in the gather (``DeviceReplay.sample_hindsight``); not together with ``n_steps`` > 1 or ``prioritized``."""
+    minibatch in the gather (``DeviceReplay.sample_hindsight``); not together with ``n_steps`` > 1 or ``prioritized``.
+    ``max_grad_norm=X`` (CLIP_DEFAULTS; needs ``device_entropy=True``) clips the critics' and the actor's gradients by their global norm on
+    the device, inside the Adam steps; with any of the options above."""
 
     def __init__(self, env, seed=0, **overrides):
-        unknown = [k for k in overrides if k not in SAC_DEFAULTS and k not in PER_DEFAULTS and k not in HER_DEFAULTS]
+        unknown = [k for k in overrides if k not in SAC_DEFAULTS and k not in PER_DEFAULTS and k not in HER_DEFAULTS and k not in CLIP_DEFAULTS]
         if unknown:
-            raise TypeError(f"unknown hyperparameters {unknown}; available: {sorted(SAC_DEFAULTS) + sorted(PER_DEFAULTS) + sorted(HER_DEFAULTS)}")
-        hp = dict(SAC_DEFAULTS, **PER_DEFAULTS, **HER_DEFAULTS)
+            raise TypeError(f"unknown hyperparameters {unknown}; available: {sorted(SAC_DEFAULTS) + sorted(PER_DEFAULTS) + sorted(HER_DEFAULTS) + sorted(CLIP_DEFAULTS)}")
+        hp = dict(SAC_DEFAULTS, **PER_DEFAULTS, **HER_DEFAULTS, **CLIP_DEFAULTS)
         hp.update(overrides)
+        if hp["max_grad_norm"] is not None:
+            with np.errstate(over="ignore"):
+                bound = hp["max_grad_norm"]
+                ok = not isinstance(bound, bool) and isinstance(bound, (int, float, np.integer, np.floating)) and bool(np.isfinite(np.float32(bound))) and float(np.float32(bound)) > 0.0
+            if not ok:
+                raise ValueError(f"max_grad_norm must be None or a positive number that is finite in float32, got {hp['max_grad_norm']!r}")
+            if not hp["device_entropy"]:
+                raise ValueError("max_grad_norm needs device_entropy=True (the norm is reduced and the clip coefficient applied between the device's launches; "
+                                 "clipping the .grad tensors from torch would bring host-visible norms back into the update)")
+            hp["max_grad_norm"] = float(bound)
         if not isinstance(hp["hindsight"], bool):
             raise ValueError(f"hindsight must be True or False, got {hp['hindsight']!r}")
         if hp["hindsight"]:
@@ -253,6 +274,12 @@ class SACLearner:
                       critic_loss=scalar(), actor_loss=scalar(), ent_coef_loss=scalar())
             es["losses"] = {k: es[k][0] for k in ("critic_loss", "actor_loss", "ent_coef_loss")}  # 0-dim views, made once
             self.entropy_state = es
+        # with max_grad_norm the two norms and the two clip coefficients of the running update are tensors of the learner's; never saved
+        self.clip_state = None
+        if hp["max_grad_norm"] is not None:
+            scale = torch.zeros((2,), dtype=torch.float32, device=dev)  # the critics' coefficient, then the actor's
+            self.clip_state = dict(scale=scale, critic_scale=scale[0:1], actor_scale=scale[1:2], critic_grad_norm=torch.zeros((1,), dtype=torch.float32, device=dev),
+                                   actor_grad_norm=torch.zeros((1,), dtype=torch.float32, device=dev))
         self._train = None  # the scratch and the checked struct of train(), per replay
         self.env_steps = 0  # per env; decides between the warm-up and the policy
         self.draw = 0       # draw index of the next collection pass
@@ -382,16 +409,36 @@ class SACLearner:
                                    d_log_prob_out=self.actor_d_log_prob, scale=1.0 / M, **adam)
         got = env.critic_parameter_gradients(self.online, batch["actions"], target=es["y"], scale=1.0 / M, rows=rows, out=self.critic_grads,
                                              workspace=self.critic_workspace)
-        env.critic_adam_step(self.online, self.critic.tensors(), self.critic_grads, *st["critic"], target=self.target, tau=hp["tau"], **adam)
+        env.critic_adam_step(self.online, self.critic.tensors(), self.critic_grads, *st["critic"], target=self.target, tau=hp["tau"], **adam,
+                             **self._clip("critic"))
         grad = env.critic_action_gradient(self.online, action_pi, rows=rows)
         # d_action = -g / M and the critic's and the actor's loss values
         env.policy_terms(es["ent_coef"], M, dqmin_da=grad["dqmin_da"], scale=-1.0 / M, d_action_out=self.actor_d_action, q=got["q"], y=es["y"],
                          critic_loss_out=es["critic_loss"], log_prob=log_prob, q_min=grad["q_min"], actor_loss_out=es["actor_loss"])
         env.actor_parameter_gradients(self.device_actor, sample=how, rows=rows, d_action=self.actor_d_action, d_log_prob=self.actor_d_log_prob,
                                       out=self.actor_grads, workspace=self.actor_workspace)
-        env.actor_adam_step(self.device_actor, self.actor.tensors(), self.actor_grads, *st["actor"], **adam)
-        self.last_update = dict(log_prob=log_prob, y=es["y"], q=got["q"], q_min=grad["q_min"], dqmin_da=grad["dqmin_da"])
+        env.actor_adam_step(self.device_actor, self.actor.tensors(), self.actor_grads, *st["actor"], **adam, **self._clip("actor"))
+        self.last_update = dict(log_prob=log_prob, y=es["y"], q=got["q"], q_min=grad["q_min"], dqmin_da=grad["dqmin_da"], **self._clip_record())
         return dict(es["losses"])
+
+    def _clip(self, which):
+        """With ``max_grad_norm``: ONE launch reduces the global norm of the critics' (or the actor's) gradients into the learner's
+        tensors; returns the ``scale=`` keyword of the step that follows.  Without it: nothing is launched, no keyword."""
+        cs = self.clip_state
+        if cs is None:
+            return {}
+        if which == "critic":
+            self.env.critic_gradient_norm(self.online, self.critic_grads, self.hp["max_grad_norm"], norm_out=cs["critic_grad_norm"], scale_out=cs["critic_scale"],
+                                          tensor_sums_out=False)
+        else:
+            self.env.actor_gradient_norm(self.device_actor, self.actor_grads, self.hp["max_grad_norm"], norm_out=cs["actor_grad_norm"], scale_out=cs["actor_scale"],
+                                         tensor_sums_out=False)
+        return dict(scale=cs[which + "_scale"])
+
+    def _clip_record(self):
+        """What ``last_update`` gains with ``max_grad_norm``: references to the two norms and the two coefficients of the update."""
+        cs = self.clip_state
+        return {} if cs is None else {k: cs[k] for k in ("critic_grad_norm", "actor_grad_norm", "critic_scale", "actor_scale")}
 
     def _update_prioritized(self, replay, seed, draw):
         """``_update_on_device`` on a ``DevicePrioritizedReplay``: the draw goes through the priority sums, and between the entropy step
@@ -419,15 +466,16 @@ class SACLearner:
         q = env.critic_values(self.online, batch["actions"], rows=rows)["q"]
         per = replay.terms(batch, q, es["y"], per_beta(hp["per_beta"], st["step"], hp["per_beta_steps"]), 1.0 / M)
         got = env.critic_parameter_gradients(self.online, batch["actions"], dq=per["dq"], rows=rows, out=self.critic_grads, workspace=self.critic_workspace)
-        env.critic_adam_step(self.online, self.critic.tensors(), self.critic_grads, *st["critic"], target=self.target, tau=hp["tau"], **adam)
+        env.critic_adam_step(self.online, self.critic.tensors(), self.critic_grads, *st["critic"], target=self.target, tau=hp["tau"], **adam,
+                             **self._clip("critic"))
         grad = env.critic_action_gradient(self.online, action_pi, rows=rows)
         env.policy_terms(es["ent_coef"], M, dqmin_da=grad["dqmin_da"], scale=-1.0 / M, d_action_out=self.actor_d_action, q=got["q"], y=es["y"],
                          critic_loss_out=es["critic_loss"], log_prob=log_prob, q_min=grad["q_min"], actor_loss_out=es["actor_loss"])
         env.actor_parameter_gradients(self.device_actor, sample=how, rows=rows, d_action=self.actor_d_action, d_log_prob=self.actor_d_log_prob,
                                       out=self.actor_grads, workspace=self.actor_workspace)
-        env.actor_adam_step(self.device_actor, self.actor.tensors(), self.actor_grads, *st["actor"], **adam)
+        env.actor_adam_step(self.device_actor, self.actor.tensors(), self.actor_grads, *st["actor"], **adam, **self._clip("actor"))
         self.last_update = dict(log_prob=log_prob, y=es["y"], q=got["q"], q_min=grad["q_min"], dqmin_da=grad["dqmin_da"], q_evaluated=q, index=batch["index"],
-                                leaf=batch["leaf"], total=batch["total"], **per)
+                                leaf=batch["leaf"], total=batch["total"], **per, **self._clip_record())
         return dict(es["losses"])
 
     def _train_binding(self, replay):
@@ -490,7 +538,9 @@ class SACLearner:
         With ``n_steps`` > 1 the ONE native call is urgym_sac_train_nstep, with the evaluations and the monitor where given.  With
         ``prioritized`` it is urgym_sac_train_prioritized on a ``DevicePrioritizedReplay``, the same way: every collection is followed
         by the fill of its slots, every update is ``update``'s seventeen launches.  With ``hindsight`` it is urgym_sac_train_hindsight:
-        the thirteen launches with the gather of ``DeviceReplay.sample_hindsight``."""
+        the thirteen launches with the gather of ``DeviceReplay.sample_hindsight``.  With ``max_grad_norm`` it is
+        urgym_sac_train_clipped with whichever of those apply: two more launches per update, and the result also holds
+        ``critic_grad_norm`` and ``actor_grad_norm``, one entry per update like the losses."""
         from .evaluation import warmup_iterations
 
         if (evaluation is None) != (eval_every is None):
@@ -507,6 +557,10 @@ class SACLearner:
         uniform, idle = warmup_iterations(self.env_steps, env.num_envs, hp["learning_starts"], n, K)
         updates = max(0, n - idle) * max(0, G)
         losses = torch.empty((3, updates), dtype=torch.float32, device=env.device)
+        cs, clipping = self.clip_state, {}
+        if cs is not None:
+            norms = torch.empty((2, updates), dtype=torch.float32, device=env.device)
+            clipping = dict(clipping=dict(max_grad_norm=hp["max_grad_norm"], scale=cs["scale"], critic_grad_norm=norms[0], actor_grad_norm=norms[1]))
         tr["binding"].struct.update_seed = int(seed)
         env.sac_train(tr["binding"], losses[0], losses[1], losses[2], first_slot=replay.cursor, filled_steps=replay.filled, num_iterations=n,
                       steps_per_iteration=K, updates_per_iteration=G, uniform_iterations=uniform, idle_iterations=idle,
@@ -515,7 +569,7 @@ class SACLearner:
                       **({} if monitor is None else dict(monitor=monitor, log_every=log_every)),
                       **({} if tr["nstep"] is None else dict(nstep=tr["nstep"])),
                       **({} if tr["prioritized"] is None else dict(prioritized=tr["prioritized"])),
-                      **({} if tr["hindsight"] is None else dict(hindsight=tr["hindsight"])))
+                      **({} if tr["hindsight"] is None else dict(hindsight=tr["hindsight"])), **clipping)
         self.env_steps += n * K
         self.draw += n * K
         st["step"] += updates
@@ -528,6 +582,11 @@ class SACLearner:
                 per = tr["prioritized"]
                 self.last_update.update(q_evaluated=per["q"], index=tr["batch"]["index"], leaf=per["leaf"], total=per["total"],
                                         **{k: per[k] for k in ("w_raw", "w", "dq", "new_leaf")})
+            if cs is not None:  # the last update's norms, as views of the call's slots; the coefficients are the scratch's
+                self.last_update.update(critic_grad_norm=norms[0, updates - 1:], actor_grad_norm=norms[1, updates - 1:], critic_scale=cs["critic_scale"],
+                                        actor_scale=cs["actor_scale"])
+        if cs is not None:
+            return {"critic_loss": losses[0], "actor_loss": losses[1], "ent_coef_loss": losses[2], "critic_grad_norm": norms[0], "actor_grad_norm": norms[1]}
         return {"critic_loss": losses[0], "actor_loss": losses[1], "ent_coef_loss": losses[2]}
 
     # ------------------------------------------------------------------------------------------------ checkpoints
@@ -540,7 +599,7 @@ class SACLearner:
         """The hyperparameters as a checkpoint holds them: ``n_steps`` only where it is not 1, so that the file of a one-step run is
         what it was before the option existed (``check_state_dict`` reads an absent ``n_steps`` as 1)."""
         return {k: v for k, v in self.hp.items() if (k != "n_steps" or int(v) != 1) and (k not in PER_DEFAULTS or self.hp.get("prioritized"))
-                and (k not in HER_DEFAULTS or self.hp.get("hindsight"))}
+                and (k not in HER_DEFAULTS or self.hp.get("hindsight")) and (k not in CLIP_DEFAULTS or v is not None)}
 
     def state_dict(self):
         """Everything the learner is, as host arrays and scalars: the actor's eight and the critics' twelve parameter tensors, the
@@ -620,6 +679,9 @@ class SACLearner:
         for k, default in HER_DEFAULTS.items():  # a file without hindsight holds none of the three
             if k != "hindsight" and not self.hp.get("hindsight") and not state["hp"].get("hindsight"):
                 continue
+            if state["hp"].get(k, default) != self.hp.get(k, default):
+                raise ValueError(f"load_state_dict: {k} is {state['hp'].get(k, default)!r} in the checkpoint, {self.hp.get(k, default)!r} here")
+        for k, default in CLIP_DEFAULTS.items():  # a file without clipping holds no max_grad_norm
             if state["hp"].get(k, default) != self.hp.get(k, default):
                 raise ValueError(f"load_state_dict: {k} is {state['hp'].get(k, default)!r} in the checkpoint, {self.hp.get(k, default)!r} here")
         for name, mine in (("adam_state", self.adam_state), ("entropy_state", self.entropy_state)):

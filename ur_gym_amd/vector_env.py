@@ -431,14 +431,67 @@ class UR5ReachVectorEnv:
             raise ValueError(f"betas must be a pair, got {betas}")
         return _abi.AdamHyper(float(lr), float(betas[0]), float(betas[1]), float(eps), int(step), 0)
 
-    def actor_adam_step(self, actor, params, grads, exp_avg, exp_avg_sq, *, lr, betas=(0.9, 0.999), eps=1e-8, step):
+    def _grad_norm_args(self, who, max_norm, tensors, norm_out, scale_out, tensor_sums_out):
+        """The ``_abi.GradNorm`` of a norm call and the dict it returns: outputs not handed in are allocated (not synchronised);
+        ``tensor_sums_out=False`` asks for no per-tensor sums (a NULL pointer: the kernel then writes none)."""
+        max_norm = float(max_norm)
+        if not (self._finite32(max_norm) and max_norm > 0.0):
+            raise ValueError(f"{who}: max_norm must be finite and positive, got {max_norm}")
+        out = dict(norm=norm_out if norm_out is not None else torch.empty((1,), dtype=torch.float32, device=self.device),
+                   scale=scale_out if scale_out is not None else torch.empty((1,), dtype=torch.float32, device=self.device),
+                   tensor_sums=tensor_sums_out if tensor_sums_out is not None else torch.empty((tensors,), dtype=torch.float64, device=self.device))
+        sums = None
+        if tensor_sums_out is False:
+            del out["tensor_sums"]
+        else:
+            sums = self._float_ptr(who, "tensor_sums_out", out["tensor_sums"], (tensors,), torch.float64, C.c_double)
+        args = _abi.GradNorm(max_norm, 0, self._float_ptr(who, "norm_out", out["norm"], (1,)), self._float_ptr(who, "scale_out", out["scale"], (1,)), sums)
+        return args, out
+
+    def actor_gradient_norm(self, actor, grads, max_norm, *, norm_out=None, scale_out=None, tensor_sums_out=None):
+        """The global norm of the actor's eight gradient tensors and the clip coefficient, on the device in ONE launch of one workgroup
+        (urgym_actor_grad_norm): `grads` as ``actor_adam_step`` takes them, only read.  Returns ``dict(norm=, scale=, tensor_sums=)``:
+        float32 [1], float32 [1] and float64 [8] tensors, the ones handed in (`norm_out`, `scale_out`, `tensor_sums_out`) or new ones;
+        ``tensor_sums_out=False`` leaves the sums out (what the training call does).
+        ``scale`` is what ``actor_adam_step(scale=)`` takes.  The arithmetic is ``evaluation.grad_norm``, bitwise.  On torch's current
+        stream, nothing is synchronised."""
+        from .evaluation import ACTOR_ARRAYS, LOG_STD_ARRAYS, DeviceActor
+
+        who = "actor_gradient_norm"
+        a = self._actor_ptr(actor)
+        grads = dict(grads)
+        if not DeviceActor.check_parameters(grads, actor.in_features, actor.hidden_width, self.device):
+            raise ValueError(f"{who}: grads needs the log_std head too ({LOG_STD_ARRAYS})")
+        g = _abi.ActorTensors(*[C.cast(grads[k].data_ptr(), C.POINTER(C.c_float)) for k in ACTOR_ARRAYS + LOG_STD_ARRAYS])
+        args, out = self._grad_norm_args(who, max_norm, _abi.GRAD_NORM_ACTOR_TENSORS, norm_out, scale_out, tensor_sums_out)
+        _native.check(self.lib.urgym_actor_grad_norm(self._h, a, C.byref(g), C.byref(args), self._stream()), self._h)
+        return out
+
+    def critic_gradient_norm(self, critic, grads, max_norm, *, norm_out=None, scale_out=None, tensor_sums_out=None):
+        """``actor_gradient_norm`` for the twelve gradient tensors of both Q-networks, ONE group (urgym_critic_grad_norm): `grads` as
+        ``critic_adam_step`` takes them; ``tensor_sums`` is float64 [12], network 0 first."""
+        from .evaluation import CRITIC_ARRAYS, DeviceCritic
+
+        who = "critic_gradient_norm"
+        if getattr(critic, "env", None) is not self or not getattr(critic, "_c", None):
+            raise ValueError(f"{who}: critic must be a live DeviceCritic loaded for this environment (DeviceCritic.load(paths, env))")
+        grads = [dict(w) for w in grads]
+        DeviceCritic.check_parameters(grads, critic.in_features, critic.hidden_width, self.device)
+        g = (_abi.QNetworkDev * 2)(*[_abi.QNetworkDev(*[C.cast(w[k].data_ptr(), C.POINTER(C.c_float)) for k in CRITIC_ARRAYS]) for w in grads])
+        args, out = self._grad_norm_args(who, max_norm, _abi.GRAD_NORM_CRITIC_TENSORS, norm_out, scale_out, tensor_sums_out)
+        _native.check(self.lib.urgym_critic_grad_norm(self._h, critic._c, g, C.byref(args), self._stream()), self._h)
+        return out
+
+    def actor_adam_step(self, actor, params, grads, exp_avg, exp_avg_sq, *, lr, betas=(0.9, 0.999), eps=1e-8, step, scale=None):
         """One Adam step of `actor`'s parameters on the device, and the reload, in ONE launch (urgym_actor_adam_step): `params`,
         `exp_avg` and `exp_avg_sq` are updated in place from `grads`, and the DeviceActor's packed buffer is rewritten from the stepped
         parameters, the log_std head included -- ``torch.optim.Adam.step()`` followed by ``actor.load_parameters(params)``.  The four
         are dicts under ACTOR_ARRAYS + LOG_STD_ARRAYS (all eight tensors) as ``DeviceActor.check_parameters`` takes them; no two of
         the 32 tensors may overlap (not checked).  `step` is the 1-based index of this step: the caller counts, the library keeps no
         optimiser state.  The arithmetic is ``evaluation.adam_step`` with ``evaluation.adam_coefficients``, bitwise.  On torch's
-        current stream, nothing is synchronised; stream order as for ``DeviceActor.load_parameters``."""
+        current stream, nothing is synchronised; stream order as for ``DeviceActor.load_parameters``.  With `scale` (a float32 [1]
+        tensor on this device: ``actor_gradient_norm(...)["scale"]``) the call is urgym_actor_adam_step_scaled: every gradient element is
+        multiplied by it as it is read (``evaluation.adam_step(scale=)``); `grads` is not written.  ``None`` makes exactly the call above."""
         from .evaluation import ACTOR_ARRAYS, LOG_STD_ARRAYS, DeviceActor
 
         a = self._actor_ptr(actor)
@@ -450,16 +503,22 @@ class UR5ReachVectorEnv:
                 raise ValueError(f"actor_adam_step: {name} needs the log_std head too ({LOG_STD_ARRAYS})")
             setattr(t, name, _abi.ActorTensors(*[C.cast(tensors[k].data_ptr(), C.POINTER(C.c_float)) for k in keys]))
         hp = self._adam_hyper(lr, betas, eps, step)
-        _native.check(self.lib.urgym_actor_adam_step(self._h, a, C.byref(t), C.byref(hp), self._stream()), self._h)
+        if scale is None:
+            _native.check(self.lib.urgym_actor_adam_step(self._h, a, C.byref(t), C.byref(hp), self._stream()), self._h)
+        else:
+            sc = self._float_ptr("actor_adam_step", "scale", scale, (1,))
+            _native.check(self.lib.urgym_actor_adam_step_scaled(self._h, a, C.byref(t), C.byref(hp), C.cast(sc, C.c_void_p), self._stream()), self._h)
         actor.has_log_std = True
 
-    def critic_adam_step(self, online, params, grads, exp_avg, exp_avg_sq, *, lr, betas=(0.9, 0.999), eps=1e-8, step, target=None, tau=None):
+    def critic_adam_step(self, online, params, grads, exp_avg, exp_avg_sq, *, lr, betas=(0.9, 0.999), eps=1e-8, step, target=None, tau=None,
+                         scale=None):
         """One Adam step of both Q-networks on the device, the reload of `online` and, with `target`, its Polyak update, in ONE launch
         (urgym_critic_adam_step): ``torch.optim.Adam.step()`` followed by ``online.load_parameters(params, tau=1)`` and
         ``target.load_parameters(params, tau)``.  The four are lists of two dicts under CRITIC_ARRAYS as
         ``DeviceCritic.check_parameters`` takes them; no two of the 48 tensors may overlap (not checked).  `target`: another
         DeviceCritic of this environment with `online`'s shape, blended as ``evaluation.polyak`` states with `tau` in (0, 1].
-        `step`, the arithmetic, the stream and the ordering as in ``actor_adam_step``."""
+        `step`, the arithmetic, the stream and the ordering as in ``actor_adam_step``; `scale` likewise
+        (``critic_gradient_norm(...)["scale"]``: urgym_critic_adam_step_scaled), ``None`` makes exactly the call above."""
         from .evaluation import CRITIC_ARRAYS, DeviceCritic
 
         for who, c in (("online", online), ("target", target)):
@@ -481,8 +540,13 @@ class UR5ReachVectorEnv:
             for i, w in enumerate(tensors):
                 nets[i] = _abi.QNetworkDev(*[C.cast(w[k].data_ptr(), C.POINTER(C.c_float)) for k in CRITIC_ARRAYS])
         hp = self._adam_hyper(lr, betas, eps, step)
-        _native.check(self.lib.urgym_critic_adam_step(self._h, online._c, target._c if target is not None else None, C.byref(t), C.byref(hp),
-                                                      float(tau) if target is not None else 1.0, self._stream()), self._h)
+        if scale is None:
+            _native.check(self.lib.urgym_critic_adam_step(self._h, online._c, target._c if target is not None else None, C.byref(t), C.byref(hp),
+                                                          float(tau) if target is not None else 1.0, self._stream()), self._h)
+        else:
+            sc = self._float_ptr("critic_adam_step", "scale", scale, (1,))
+            _native.check(self.lib.urgym_critic_adam_step_scaled(self._h, online._c, target._c if target is not None else None, C.byref(t), C.byref(hp),
+                                                                 float(tau) if target is not None else 1.0, C.cast(sc, C.c_void_p), self._stream()), self._h)
 
     def _float_ptr(self, who, name, t, shape, dtype=torch.float32, ctype=C.c_float):
         """The DEVICE pointer of `t` for a call that reads or writes it in place: a contiguous `dtype` tensor of `shape` on this
@@ -799,7 +863,7 @@ class UR5ReachVectorEnv:
 
     def sac_train(self, learner, critic_loss, actor_loss, ent_coef_loss, *, first_slot, filled_steps, num_iterations, steps_per_iteration=1,
                   updates_per_iteration=1, uniform_iterations=0, idle_iterations=0, collect_first_draw=0, update_first_draw=0, first_step=1,
-                  evaluation=None, eval_every=None, monitor=None, log_every=None, nstep=None, prioritized=None, hindsight=None):
+                  evaluation=None, eval_every=None, monitor=None, log_every=None, nstep=None, prioritized=None, hindsight=None, clipping=None):
         """``num_iterations`` x (a collection of ``steps_per_iteration`` steps, ``updates_per_iteration`` SAC updates) in ONE native
         call (urgym_sac_train): the launches of ``collect`` and of the thirteen calls of an update, bit for bit, without returning to
         Python in between.  `learner`: what ``sac_learner`` returned, or a dict of its keyword arguments (then built and checked here).
@@ -830,7 +894,12 @@ class UR5ReachVectorEnv:
 
         With `hindsight` (a dict: ``n_sampled_goal``, ``strategy`` "future" or "final", ``horizon``) the call is
         urgym_sac_train_hindsight, with the evaluations and the monitor if those are given: every update's gather is the one of
-        ``DeviceReplay.sample_hindsight``.  Not together with `nstep` or `prioritized`."""
+        ``DeviceReplay.sample_hindsight``.  Not together with `nstep` or `prioritized`.
+
+        With `clipping` (a dict: ``max_grad_norm``, ``scale``, a float32 [2] scratch tensor, and ``critic_grad_norm`` and
+        ``actor_grad_norm``, float32 tensors of one entry per update of the call like the losses) the call is urgym_sac_train_clipped,
+        with whichever of the options above are given: every update runs ``critic_gradient_norm`` and ``actor_gradient_norm`` before
+        the two steps, which take the coefficients (``scale=``); update u writes the norms to entry u.  Without it nothing changes."""
         from .evaluation import DeviceEvaluation, DeviceMonitor, _her_arguments, evaluation_points, monitor_points, relabel_threshold, training_schedule
 
         who = "sac_train"
@@ -901,8 +970,24 @@ class UR5ReachVectorEnv:
         for name, t in zip(_abi.SAC_LEARNER_LOSSES, (critic_loss, actor_loss, ent_coef_loss)):
             setattr(L, name, self._float_ptr(who, name, t, (updates,)))
         S = _abi.SacSchedule(*[sched[name] for name, _ in _abi.SacSchedule._fields_])
+        if clipping is not None:
+            max_grad_norm = float(clipping["max_grad_norm"])
+            if not (self._finite32(max_grad_norm) and max_grad_norm > 0.0):
+                raise ValueError(f"{who}: clipping['max_grad_norm'] must be finite and positive, got {max_grad_norm}")
+            C_ = _abi.SacClipping(max_grad_norm, 0, self._float_ptr(who, "clipping['scale']", clipping["scale"], (2,)),
+                                  self._float_ptr(who, "clipping['critic_grad_norm']", clipping["critic_grad_norm"], (updates,)),
+                                  self._float_ptr(who, "clipping['actor_grad_norm']", clipping["actor_grad_norm"], (updates,)))
         try:
-            if hindsight is not None:
+            if clipping is not None:
+                _native.check(self.lib.urgym_sac_train_clipped(self._h, C.byref(L), C.byref(S), C.byref(C_), C.byref(N_) if nstep is not None else None,
+                                                               C.byref(P_) if prioritized is not None else None, C.byref(H_) if hindsight is not None else None,
+                                                               C.byref(E_) if evaluation is not None else None,
+                                                               C.byref(M_) if monitor is not None else None, self._stream()), self._h)
+                if monitor is not None:
+                    monitor.advance(sched["num_iterations"], len(logged))
+                if evaluation is not None:
+                    evaluation.advance(len(points))
+            elif hindsight is not None:
                 _native.check(self.lib.urgym_sac_train_hindsight(self._h, C.byref(L), C.byref(S), C.byref(H_), C.byref(E_) if evaluation is not None else None,
                                                                  C.byref(M_) if monitor is not None else None, self._stream()), self._h)
                 if monitor is not None:
