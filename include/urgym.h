@@ -1646,6 +1646,145 @@ int urgym_critic_unpack(void* handle, void* critic, const urgym_critic_params_ou
 int urgym_actor_read_packed(void* handle, void* actor, float* host_out, uint64_t capacity, uint64_t* count);
 int urgym_critic_read_packed(void* handle, void* critic, float* host_out, uint64_t capacity, uint64_t* count);
 
+/* ---- running observation and reward normalization on the device (stable-baselines3's VecNormalize, which the reference's
+ * utils/callbackFunctions.py names: sync_envs_normalization, get_vec_normalize_env, save_vecnormalize).  The running mean and variance
+ * of what the collecting actor saw and of the discounted return are kept in float64 on the device, folded from the replay ring a
+ * collection has just written, and applied by one launch to rows (what the actor reads) or to a learner's batch.  The ring keeps the
+ * RAW rows, as SB3's buffer does.  Added WITHIN ABI version 4: no struct above changed, URGYM_ABI_VERSION did not move, the new symbols
+ * (urgym_norm_workspace, urgym_norm_fold, urgym_norm_rows, urgym_norm_batch, urgym_norm_snapshot, urgym_rollout_collect_normalized,
+ * urgym_policy_evaluate_normalized, urgym_sac_train_normalized) are found by lookup.
+ * The library keeps none of the state.  Non-finite inputs are out of scope: nothing below is stated or tested for them.
+ *
+ * THE STATE: DEVICE pointers owned by the caller, all float64, 8-byte aligned.  Four groups -- observation [obs_dim], achieved_goal
+ * [goal_dim], desired_goal [goal_dim], ret [1] -- each mean[d], var[d] and ONE count; running_ret [N] is the discounted return of each
+ * env's running episode.  The initial state is mean = 0, var = 1, count = 1e-4, running_ret = 0 (SB3's RunningMeanStd). */
+typedef struct urgym_norm_state {
+  double* observation_mean;    /* [obs_dim] */
+  double* observation_var;     /* [obs_dim] */
+  double* observation_count;   /* [1] */
+  double* achieved_goal_mean;  /* [goal_dim] */
+  double* achieved_goal_var;   /* [goal_dim] */
+  double* achieved_goal_count; /* [1] */
+  double* desired_goal_mean;   /* [goal_dim] */
+  double* desired_goal_var;    /* [goal_dim] */
+  double* desired_goal_count;  /* [1] */
+  double* ret_mean;            /* [1] */
+  double* ret_var;             /* [1] */
+  double* ret_count;           /* [1] */
+  double* running_ret;         /* [N] */
+} urgym_norm_state;
+
+typedef struct urgym_normalization {
+  urgym_norm_state state;
+  double gamma;             /* the discount of running_ret */
+  double eps;               /* >= 0 */
+  double clip_obs;          /* > 0, +inf allowed */
+  double clip_reward;       /* > 0, +inf allowed */
+  int32_t norm_obs;         /* 0: the three observation groups are neither folded nor applied */
+  int32_t norm_reward;      /* 0: the return group is neither folded nor applied */
+  int32_t training;         /* 0: urgym_norm_fold launches nothing and leaves the state untouched */
+  float* scratch;           /* [N][obs_dim + 2 goal_dim] DEVICE: the N observation rows, then the N achieved_goal rows, then the N
+                               desired_goal rows the collecting actor reads; required by urgym_rollout_collect_normalized only */
+  void* workspace;          /* DEVICE, 8-byte aligned: the partial sums of urgym_norm_fold; required by urgym_norm_fold only */
+  uint64_t workspace_bytes; /* at least urgym_norm_workspace(num_steps) */
+  float* eval_scratch;      /* [N_eval][obs_dim + 2 goal_dim] DEVICE, laid out like scratch for the EVALUATION handle's env count;
+                               required by urgym_policy_evaluate_normalized and by an evaluation inside urgym_sac_train_normalized only */
+  const urgym_norm_state* best_state; /* where an evaluation that improved snapshots the statistics (running_ret is not copied and may
+                               be NULL); required where eval_scratch is */
+  int64_t reserved0;        /* must be 0 */
+} urgym_normalization;
+
+/* THE FOLD of one ring slot.  The inputs are the rows s of that slot -- what the actor saw, N rows per group.  Per feature j:
+ *   S1 = the float64 sum of (double)x, S2 = the float64 sum of (double)x * (double)x (each product is exact), BOTH IN THIS ORDER, a
+ *   function of N alone (ur_gym_amd/csrc/urgym_norm.h states it, ur_gym_amd.evaluation.norm_sums restates it):
+ *     slab b holds rows 128 b .. min(128 b + 127, N - 1).  Within a slab, chain q = 0..3 starts at +0.0 and adds rows 128 b + q,
+ *     128 b + q + 4, ... in ascending order (32 terms at the most);  slab = (chain0 + chain1) + (chain2 + chain3);
+ *     part c = 0..15 starts at +0.0 and adds slabs c, c + 16, c + 32, ... in ascending order;
+ *     part[c] += part[c + s] for s = 8, 4, 2, 1;  the sum is part[0].
+ *   n = (double)N;  bm = S1 / n;  bv = max(S2 / n - bm * bm, 0.0)
+ * then the merge of SB3's update_from_moments, ONE float64 operation per line in the association written:
+ *   delta = bm - mean
+ *   tot   = count + n
+ *   mean' = mean + (delta * n) / tot
+ *   M2    = (var * count + bv * n) + ((delta * delta) * count) * n / tot
+ *   var'  = M2 / tot
+ *   count' = tot
+ * The return group, per env: running_ret = running_ret * gamma + (double)reward; then the same sums and the same merge over the N
+ * values of running_ret (a group of one feature); then running_ret = +0.0 where terminated | truncated.
+ * K = num_steps slots (first_slot + k) % C are folded in slot order with one merge per slot: K steps in one call and the same steps in
+ * pieces leave identical bits.  norm_obs == 0 leaves the three observation groups alone, norm_reward == 0 the return group and
+ * running_ret; training == 0 launches nothing.
+ * TWO launches on `stream` whatever K is: many workgroups reduce slabs to partial sums in the workspace (one lane per env walks the K
+ * slots for running_ret in the same launch), ONE workgroup of 1024 lanes combines them, merges slot by slot and writes the state.  No
+ * atomics, nothing crosses between workgroups but through the launch boundary, no allocation, no host synchronisation, everything
+ * validated before the first launch.
+ * Refused (URGYM_ERR_ARG, nothing launched, nothing written): NULL handle or norm; a NULL or misaligned state pointer (named); gamma
+ * outside [0, 1]; eps < 0; a clip <= 0; reserved0 != 0; a NULL or misaligned workspace or workspace_bytes too small; and
+ * urgym_monitor_fold's ring refusals (ring == NULL, a NULL required pointer, capacity_steps <= 0, reserved0 != 0, first_slot outside
+ * [0, C), a ring without truncated or is_success, num_steps <= 0, num_steps > C, a handle with auto_reset off). */
+int urgym_norm_workspace(void* handle, int num_steps, uint64_t* bytes);
+int urgym_norm_fold(void* handle, const urgym_normalization* norm, const urgym_replay_ring* ring, int first_slot, int num_steps, void* stream);
+
+/* NORMALIZE.  Once per feature: inv_j = 1.0 / sqrt(var_j + eps), in float64 (both correctly rounded).
+ *   an observation or goal element becomes (float)min(max(((double)x - mean_j) * inv_j, -clip_obs), clip_obs)
+ *   a reward becomes (float)min(max((double)r * inv_ret, -clip_reward), clip_reward): no mean is subtracted, as in SB3
+ * The state is read when the launch RUNS: a fold earlier on `stream` is seen, a later one is not.
+ *
+ * urgym_norm_rows: ONE launch maps `count` rows of the three groups, each source pointer optional (NULL = that group is skipped,
+ * together with its destination), from source to destination; a destination may be its source.  With norm_obs == 0 the rows are
+ * copied unchanged.  Refused: NULL handle or norm, the state and option refusals of urgym_norm_fold (not the workspace's), count <= 0,
+ * no group at all, a source without its destination or the reverse. */
+typedef struct urgym_norm_rows_args {
+  const float* observation;   /* [count][obs_dim] or NULL */
+  const float* achieved_goal; /* [count][goal_dim] or NULL */
+  const float* desired_goal;  /* [count][goal_dim] or NULL */
+  float* observation_out;
+  float* achieved_goal_out;
+  float* desired_goal_out;
+} urgym_norm_rows_args;
+int urgym_norm_rows(void* handle, const urgym_normalization* norm, const urgym_norm_rows_args* rows, int count, void* stream);
+
+/* urgym_norm_batch: ONE launch normalizes a learner's batch of `count` rows IN PLACE: observation and next_observation with the
+ * observation group, achieved_goal and next_achieved_goal, desired_goal and next_desired_goal likewise (norm_obs != 0), and reward
+ * with the return group (norm_reward != 0).  Every pointer of the batch may be NULL (= left alone); action and the flags are not
+ * touched.  With both switches off nothing is launched.  Refused: as urgym_norm_rows; NULL batch. */
+int urgym_norm_batch(void* handle, const urgym_normalization* norm, const urgym_replay_batch* batch, int count, void* stream);
+
+/* urgym_rollout_collect whose actor reads NORMALIZED rows: before the policy pass of every step ONE more launch (urgym_norm_rows of
+ * the N bound rows into norm->scratch), and the actor runs on the scratch; its kernels, its noise (a function of the env index) and
+ * the step are those of urgym_rollout_collect.  The store pass files the RAW rows.  4 num_steps + 1 launches.  The statistics are
+ * NOT folded inside the call -- a step's action sees the statistics as of the start of the call, a stated deviation from SB3, which
+ * updates them every step -- : fold afterwards with urgym_norm_fold from the slots the call wrote.  With norm_obs == 0 the call is
+ * urgym_rollout_collect.  Refused: everything urgym_rollout_collect and urgym_norm_rows refuse; a NULL scratch. */
+int urgym_rollout_collect_normalized(void* handle, void* actor, const urgym_sampling* how, int num_steps, const urgym_replay_ring* ring, int first_slot, const urgym_normalization* norm, void* stream);
+
+/* THE STATE SNAPSHOT, the twin of urgym_actor_snapshot: destination = source for mean, var and count of the four groups (running_ret is
+ * not copied) in ONE launch of one workgroup -- or nothing at all where `when`, a DEVICE int32, holds 0 when the launch RUNS (NULL =
+ * always).  dims are the handle's.  Refused: NULL handle / source / destination, a NULL or misaligned pointer of the twelve. */
+int urgym_norm_snapshot(void* handle, const urgym_norm_state* source, const urgym_norm_state* destination, const int32_t* when, void* stream);
+
+/* urgym_policy_evaluate whose actor reads rows normalized with the statistics normalization->state points to -- the TRAINING state, read
+ * through its pointers when the launches run: SB3's sync_envs_normalization.  One more launch per step before the policy pass (the N_eval
+ * bound rows of the evaluation handle into normalization->eval_scratch; none with norm_obs == 0), and after urgym_actor_snapshot ONE
+ * urgym_norm_snapshot of the state into normalization->best_state under the record's `improved` flag, so that the best actor is kept
+ * with the statistics it was selected under.  Rewards are NOT normalized: the records hold raw returns.  Nothing is folded.  Refused:
+ * everything urgym_policy_evaluate and urgym_norm_rows refuse; a NULL eval_scratch or best_state; a NULL or misaligned pointer of
+ * best_state's twelve. */
+int urgym_policy_evaluate_normalized(void* eval_handle, const urgym_policy_evaluation* evaluation, const urgym_normalization* normalization, int64_t eval_index, int32_t record_slot, void* stream);
+
+/* urgym_sac_train -- or urgym_sac_train_clipped / _nstep / _prioritized / _hindsight / _monitored, by which of the optional arguments
+ * are given -- with the statistics in it.  Afterwards everything is BIT FOR BIT what that call's sequence would have left with:
+ *   every collection urgym_rollout_collect_normalized (one more launch per step);
+ *   after each iteration's collection, idle warm-up iterations included, and before the monitor's fold, ONE urgym_norm_fold of the
+ *     K slots just written (two launches; none with training == 0);
+ *   right after the gather of every update, whichever gather it is, ONE urgym_norm_batch of the learner's batch: 14 launches per
+ *     update instead of 13, 16 with clipping.  With n_steps > 1 the normalized reward is the row's ACCUMULATED multi-step return.
+ * normalization->workspace must hold steps_per_iteration steps.  Everything is validated before the first launch.  Refused besides
+ * what the composed call, urgym_norm_fold and urgym_norm_batch refuse: normalization == NULL; a NULL scratch with norm_obs != 0 in a
+ * call that collects; more than one of nstep, prioritized and hindsight.  An evaluation inside the call is
+ * urgym_policy_evaluate_normalized with this normalization (its refusals: a NULL eval_scratch or best_state). */
+int urgym_sac_train_normalized(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_normalization* normalization, const urgym_sac_clipping* clipping_or_NULL, const urgym_sac_nstep* nstep_or_NULL, const urgym_sac_prioritized* prioritized_or_NULL, const urgym_sac_hindsight* hindsight_or_NULL, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream);
+
 /* Replaces Reach*.set_goal / set_goal_and_obstacle (reach.py:202-204, 328-335, 702-713): the caller has
  * overwritten goal / obst_start / obst_end (and possibly q) for the masked envs; this recomputes obstacle pose,
  * velocity, collision, link_dist and the observation for them, leaving step_count untouched. */

@@ -73,6 +73,15 @@ clipped route; the unclipped one is compared with the parent commit's --entropy 
 clipped native updates alone: the program of a kernel-trace run.
     python tools/bench_policy_rollout.py --clip --windows 8 --launches 200 --out profiles/policy_rollout/dyn65536_clip.json
 
+--normalize measures running normalization.  The update as in --clip: `device_entropy`, the learner without the
+option (the thirteen calls it always made), against `normalized` (fourteen: one urgym_norm_batch after the gather), and the same pair as
+ONE SACLearner.train call per window.  Then, at --num-envs envs, a collection step without and with the normalize launch
+(env.collect of --collect-steps steps, alternating windows; the two collections follow different trajectories, so their difference is
+NOT the launch's cost: the kernel trace of --normalize-only is) and one fold of those steps (two launches).  Medians, mins and maxes of
+wall times between device synchronises.  No bar on the normalized routes.  --normalize-only runs the normalized collection, the fold and
+the normalized native updates alone: the program of a kernel-trace run.
+    python tools/bench_policy_rollout.py --normalize --windows 8 --launches 200 --out profiles/policy_rollout/dyn65536_norm.json
+
 --native measures the same update (batch 256, H = 256, device_entropy) two ways: the thirteen-call
 SACLearner.update, and SACLearner.train(steps_per_iteration=0, updates_per_iteration=--launches), one native call per window.
 Alternating windows in one process, each ending in a device synchronise; median, min and max of the wall time per update.  Bar: the
@@ -1047,6 +1056,116 @@ def clip_mode(args):
     env.close()
 
 
+def normalize_mode(args):
+    """--normalize: the update without and with normalize, the collection step without and with the normalize launch, the fold (see above)."""
+    import torch
+
+    from ur_gym_amd import make_vec
+    from ur_gym_amd.evaluation import DeviceNormalizer, DeviceReplay
+    from ur_gym_amd.training import SACLearner
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_policy_rollout.py measures on a GPU; none is visible")
+    dev, n, per_window = "cuda:0", min(args.num_envs, 4096), args.launches  # an update does not depend on the number of envs
+    env = make_vec(args.env, num_envs=n, device=dev, seed=0, auto_reset=True)
+    env.reset(seed=0)
+    sync = lambda: torch.cuda.synchronize(env.device)  # noqa: E731
+    options = dict(device_action_gradient=True, device_critic_gradient=True, device_actor_gradient=True, device_optimizer=True, device_entropy=True)
+    routes = {"device_entropy": (False, {}), "normalized": (False, dict(normalize=True)), "native": (True, {}), "native_normalized": (True, dict(normalize=True))}
+    if args.normalize_only:
+        routes = {"native_normalized": routes["native_normalized"]}
+    learners = {}
+    for label, (native, extra) in routes.items():
+        learner = SACLearner(env, seed=0, batch_size=256, hidden_width=256, learning_starts=0, **options, **extra)
+        replay = DeviceReplay(env, 64)
+        learner.collect(replay, 4)
+        learners[label] = (learner, replay, [0], native)
+
+    def updates(label, count):
+        learner, replay, draw, native = learners[label]
+        if native:
+            learner.train(replay, 1, 0, count, seed=1, first_draw=draw[0] + 1)
+            draw[0] += count
+        else:
+            for _ in range(count):
+                draw[0] += 1
+                learner.update(replay, 1, draw[0])
+
+    def window(label):
+        sync()
+        t0 = time.perf_counter()
+        updates(label, per_window)
+        sync()
+        return (time.perf_counter() - t0) * 1e6 / per_window
+
+    for label in learners:
+        updates(label, 10)
+    wdw = {label: [] for label in learners}
+    for _ in range(args.windows):
+        for label in learners:
+            if args.normalize_only:
+                updates(label, per_window)
+            else:
+                wdw[label].append(window(label))
+    sync()
+    # the collection and the fold at the full env count, on an environment of their own
+    K = args.collect_steps
+    big = make_vec(args.env, num_envs=args.num_envs, device=dev, seed=0, auto_reset=True)
+    big.reset(seed=0)
+    from ur_gym_amd.evaluation import DeviceActor
+    from ur_gym_amd.training import host_arrays
+
+    big_actor = DeviceActor(host_arrays(learners[next(iter(learners))][0].actor.tensors()), big)
+    ring, nz = DeviceReplay(big, K), DeviceNormalizer(big, fold_steps=K)
+    how = dict(mode="gaussian", seed=3, first_draw=0)
+
+    def timed(fn):
+        torch.cuda.synchronize(big.device)
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize(big.device)
+        return (time.perf_counter() - t0) * 1e6
+
+    plain = lambda: big.collect(big_actor, K, ring, sample=how, first_slot=0)  # noqa: E731
+    normed = lambda: big.collect(big_actor, K, ring, sample=how, first_slot=0, normalizer=nz)  # noqa: E731
+    fold = lambda: nz.fold(ring, 0, K)  # noqa: E731
+    for fn in (plain, normed, fold):
+        fn()
+    cw = {"collect": [], "collect_normalized": [], "fold": []}
+    for _ in range(args.windows):
+        if not args.normalize_only:
+            cw["collect"].append(timed(plain) / K)
+        cw["collect_normalized"].append(timed(normed) / K)
+        cw["fold"].append(timed(fold))
+    if args.normalize_only:
+        print(json.dumps({"tool": "bench_policy_rollout --normalize --normalize-only", "updates": args.windows * per_window, "collect_steps": args.windows * K}))
+    else:
+        med = {k: float(np.median(v)) for k, v in wdw.items()}
+        cmed = {k: float(np.median(v)) for k, v in cw.items()}
+        result = {"tool": "bench_policy_rollout --normalize", "env": args.env, "num_envs_update": n, "num_envs_collect": args.num_envs, "windows": args.windows,
+                  "updates_per_window": per_window, "batch": 256, "hidden_width": 256, "collect_steps": K, "device": torch.cuda.get_device_name(0),
+                  "us_per_update_median": med, "us_per_update_min": {k: float(min(v)) for k, v in wdw.items()},
+                  "us_per_update_max": {k: float(max(v)) for k, v in wdw.items()},
+                  "us_per_update_windows": {k: [round(x, 2) for x in v] for k, v in wdw.items()},
+                  "device_entropy_us_spread": float(max(wdw["device_entropy"]) - min(wdw["device_entropy"])),
+                  "normalized_minus_device_entropy_us": med["normalized"] - med["device_entropy"],
+                  "native_normalized_minus_native_us": med["native_normalized"] - med["native"],
+                  "us_per_collect_step_median": {k: cmed[k] for k in ("collect", "collect_normalized")},
+                  "us_per_collect_step_windows": {k: [round(x, 2) for x in cw[k]] for k in ("collect", "collect_normalized")},
+                  "us_per_fold_median": cmed["fold"], "us_per_fold_windows": [round(x, 2) for x in cw["fold"]], "us_per_fold_per_step": cmed["fold"] / K}
+        line = json.dumps(result)
+        print(line)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+    big_actor.close()
+    big.close()
+    for learner, _, _, _ in learners.values():
+        learner.close()
+    env.close()
+
+
 def native_mode(args):
     """--native: the thirteen-call SACLearner.update against SACLearner.train, one native call per window (see above)."""
     import torch
@@ -1707,6 +1826,9 @@ def main():
     ap.add_argument("--optimizer", action="store_true", help="measure the Adam step kernels (one launch each) against torch's Adam.step followed by the reloads, and the learner's update with and without them")
     ap.add_argument("--entropy", action="store_true", help="measure the learner's update with device_optimizer only against the same plus device_entropy (see above)")
     ap.add_argument("--clip", action="store_true", help="measure the update with max_grad_norm against the update without it, as update() calls and as one native call per window (see above)")
+    ap.add_argument("--normalize", action="store_true", help="measure the update with normalize against the update without it, the collection step without and with the normalize launch, and the fold (see above)")
+    ap.add_argument("--normalize-only", action="store_true", help="--normalize: run only the normalized collection, the fold and the normalized native updates (for a kernel trace)")
+    ap.add_argument("--collect-steps", type=int, default=8, help="--normalize: steps per collection and per fold")
     ap.add_argument("--clip-only", action="store_true", help="--clip: run only the clipped native updates, --windows x --launches of them (for a kernel trace)")
     ap.add_argument("--max-grad-norm", type=float, default=1.0, help="--clip: the bound of the clipped learners")
     ap.add_argument("--native", action="store_true", help="measure the thirteen-call update against SACLearner.train, one native call per window (see above)")
@@ -1733,6 +1855,8 @@ def main():
         return evaluate_mode(args)
     if args.clip or args.clip_only:
         return clip_mode(args)
+    if args.normalize or args.normalize_only:
+        return normalize_mode(args)
     if args.native:
         return native_mode(args)
     if args.entropy:

@@ -23,6 +23,11 @@ in them is the same; without --native the evaluations are this script's own and 
 --max-grad-norm X clips the critics' and the actor's gradients by their global norm on the device (SACLearner(max_grad_norm=X), needs
 --device-entropy; SB3's SAC does not clip) and adds to every evaluation line the three losses and the two gradient norms, before
 clipping, of the latest update.
+--normalize keeps stable-baselines3's VecNormalize on the device (SACLearner(normalize=True), needs --device-entropy): the collecting actor
+and the update read observations and rewards normalized with running statistics, the ring keeps the raw rows, and every evaluation runs
+its actor on rows normalized with the TRAINING statistics as they then stand (sync_envs_normalization) -- with --native inside the one
+call (urgym_policy_evaluate_normalized), otherwise step by step from this script -- and --save-best writes the statistics the best actor
+was selected under beside it (evaluation.load_best_normalization reads them).
 """
 import argparse
 import json
@@ -77,6 +82,13 @@ def main():
     ap.add_argument("--max-grad-norm", type=float, default=None, metavar="X",
                     help="clip the critics' and the actor's gradients by their global norm on the device (torch's clip_grad_norm_ idiom; SB3's SAC "
                          "does not clip) and print the losses and the norms with every evaluation (needs --device-entropy)")
+    ap.add_argument("--normalize", action="store_true",
+                    help="running observation and reward normalization on the device (SB3's VecNormalize; needs --device-entropy)")
+    ap.add_argument("--no-norm-obs", action="store_true", help="--normalize: leave the observations as they are")
+    ap.add_argument("--no-norm-reward", action="store_true", help="--normalize: leave the rewards as they are")
+    ap.add_argument("--clip-obs", type=float, default=10.0, help="--normalize: the bound of a normalized observation element")
+    ap.add_argument("--clip-reward", type=float, default=10.0, help="--normalize: the bound of a normalized reward")
+    ap.add_argument("--norm-epsilon", type=float, default=1e-8, help="--normalize: added to a variance before its square root")
     ap.add_argument("--native", action="store_true",
                     help="run the whole loop, evaluations included, as ONE native call (SACLearner.train): no Python between the launches "
                          "(needs --device-entropy)")
@@ -120,7 +132,10 @@ def main():
                          device_entropy=args.device_entropy, n_steps=args.n_steps,
                          **(dict(prioritized=True, per_beta=args.per_beta, per_beta_steps=args.per_beta_steps) if args.prioritized else {}),
                          **(dict(hindsight=True, her_n_sampled_goal=args.her_n_sampled_goal, her_strategy=args.her_strategy) if args.hindsight else {}),
-                         **(dict(max_grad_norm=args.max_grad_norm) if args.max_grad_norm is not None else {}))
+                         **(dict(max_grad_norm=args.max_grad_norm) if args.max_grad_norm is not None else {}),
+                         **(dict(normalize=True, norm_obs=not args.no_norm_obs, norm_reward=not args.no_norm_reward, clip_obs=args.clip_obs,
+                                 clip_reward=args.clip_reward, norm_epsilon=args.norm_epsilon) if args.normalize else {}))
+    normalizer = learner.normalizer  # None without --normalize
     eval_actor = DeviceActor(host_arrays(learner.actor.tensors()), test_env)  # actors belong to the environment they were made for
     replay = DevicePrioritizedReplay(env, args.capacity, alpha=args.per_alpha) if args.prioritized else DeviceReplay(env, args.capacity)
     updates, t0 = 0, time.perf_counter()
@@ -134,13 +149,19 @@ def main():
     def evaluate():
         eval_actor.load_parameters(learner.actor.tensors())
         test_env.reset(seed=args.seed + 1)
-        res = run_closed_loop_device(test_env, eval_actor)
+        res = run_closed_loop_device(test_env, eval_actor, **(dict(normalizer=normalizer) if normalizer is not None and not args.no_norm_obs else {}))
         norms = {}
         if args.max_grad_norm is not None:  # the run is synchronised here anyway
             norms = {k: float(v) for k, v in latest.items()}
             norms.update({k: float(learner.last_update[k][0]) for k in ("critic_grad_norm", "actor_grad_norm")})
         if args.save_best and res["mean_episode_reward"] > best["mean"]:  # strictly above, as the reference's EvalCallback decides
             best.update(mean=res["mean_episode_reward"], tensors=host_arrays(learner.actor.tensors()))
+            if normalizer is not None:  # the statistics it was selected under, as DeviceEvaluation.save_best writes them
+                import numpy as np
+
+                o = normalizer.options
+                best["norm"] = {"norm/" + k: v.cpu().numpy() for k, v in normalizer.state.items() if k != "running_ret"}
+                best["norm"]["norm/options"] = np.array([o["gamma"], o["epsilon"], o["clip_obs"], o["clip_reward"], float(o["norm_obs"]), float(o["norm_reward"])])
         print(json.dumps({"updates": updates, "env_steps": learner.env_steps * env.num_envs, "seconds": round(time.perf_counter() - t0, 1),
                           "mean_episode_return": res["mean_episode_reward"], "success_rate_percent": res["success_rate_percent"], **norms}), flush=True)
 
@@ -155,7 +176,8 @@ def main():
     # no update
     _, idle = warmup_iterations(0, env.num_envs, learner.hp["learning_starts"], args.steps, 1)
     points = evaluation_points(1, args.steps, args.updates_per_step, idle, args.eval_every) if args.steps > 0 else []
-    ev = DeviceEvaluation(test_env, learner.actor.tensors(), seed=args.seed + 1, capacity=max(1, len(points))) if args.native else None
+    ev = DeviceEvaluation(test_env, learner.actor.tensors(), seed=args.seed + 1, capacity=max(1, len(points)),
+                          **(dict(normalizer=normalizer) if normalizer is not None else {})) if args.native else None
     parts = dict(replay=replay, monitor=mon, evaluation=ev)
     step = shown_evals = shown_curve = 0
     if args.resume:
@@ -222,7 +244,7 @@ def main():
     if ev is not None:
         ev.close()
     if args.save_best and best["tensors"] is not None:
-        save_actor(args.save_best, best["tensors"])
+        save_actor(args.save_best, best["tensors"], best.get("norm"))
     eval_actor.close()
     learner.close()
     test_env.close()

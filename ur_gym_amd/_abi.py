@@ -482,6 +482,33 @@ class SacClipping(C.Structure):
                 ("actor_grad_norm", C.POINTER(C.c_float))]
 
 
+# urgym_norm_state: the thirteen float64 DEVICE arrays in the struct's order, name -> shape(num_envs, obs_dim, goal_dim)
+NORM_GROUPS = ("observation", "achieved_goal", "desired_goal", "ret")
+NORM_STATE_FIELDS = [(f"{g}_{part}", (lambda N, od, gd, g=g, part=part: (1,) if part == "count" or g == "ret" else ((od,) if g == "observation" else (gd,))))
+                     for g in NORM_GROUPS for part in ("mean", "var", "count")] + [("running_ret", lambda N, od, gd: (N,))]
+NORM_SLAB_ROWS, NORM_CHAINS, NORM_PARTS = 128, 4, 16  # the order of the sums (ur_gym_amd/csrc/urgym_norm.h)
+NORM_INITIAL_COUNT = 1e-4  # SB3's RunningMeanStd(epsilon=1e-4)
+
+
+class NormState(C.Structure):
+    """urgym_norm_state: mean, var and count of the four groups and the running discounted return of every env, all float64."""
+    _fields_ = [(name, C.POINTER(C.c_double)) for name, _ in NORM_STATE_FIELDS]
+
+
+class Normalization(C.Structure):
+    """urgym_normalization: the state, the options, the actor's scratch rows and the fold's workspace."""
+    _fields_ = [("state", NormState), ("gamma", C.c_double), ("eps", C.c_double), ("clip_obs", C.c_double), ("clip_reward", C.c_double),
+                ("norm_obs", C.c_int32), ("norm_reward", C.c_int32), ("training", C.c_int32), ("scratch", C.POINTER(C.c_float)),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_uint64), ("eval_scratch", C.POINTER(C.c_float)), ("best_state", C.POINTER(NormState)),
+                ("reserved0", C.c_int64)]
+
+
+class NormRowsArgs(C.Structure):
+    """urgym_norm_rows_args: the three optional sources and their destinations."""
+    _fields_ = [(name, C.POINTER(C.c_float)) for name in ("observation", "achieved_goal", "desired_goal", "observation_out", "achieved_goal_out",
+                                                          "desired_goal_out")]
+
+
 PER_FANOUT = 256  # URGYM_PER_FANOUT: the fan-out of the priority sums
 PER_TERMS_MAX_COUNT = 65536  # URGYM_PER_TERMS_MAX_COUNT
 PER_TAG = 0x50455200  # word 3 of the Philox counter of urgym_replay_sample_prioritized's draw
@@ -579,6 +606,14 @@ EXPORTED_SYMBOLS = [
     "urgym_sac_train_clipped",
     "urgym_actor_read_packed",
     "urgym_critic_read_packed",
+    "urgym_norm_workspace",
+    "urgym_norm_fold",
+    "urgym_norm_rows",
+    "urgym_norm_batch",
+    "urgym_norm_snapshot",
+    "urgym_rollout_collect_normalized",
+    "urgym_policy_evaluate_normalized",
+    "urgym_sac_train_normalized",
     "urgym_refresh",
     "urgym_invalidate_records",
     "urgym_derive_obstacle_motion",

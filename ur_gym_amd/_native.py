@@ -125,6 +125,17 @@ def lib():
     L.urgym_sac_train_clipped.argtypes = [C.c_void_p, C.POINTER(_abi.SacLearner), C.POINTER(_abi.SacSchedule), C.POINTER(_abi.SacClipping),
                                           C.POINTER(_abi.SacNstep), C.POINTER(_abi.SacPrioritized), C.POINTER(_abi.SacHindsight),
                                           C.POINTER(_abi.SacEvaluation), C.POINTER(_abi.SacMonitoring), C.c_void_p]
+    L.urgym_norm_workspace.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]
+    L.urgym_norm_fold.argtypes = [C.c_void_p, C.POINTER(_abi.Normalization), C.POINTER(_abi.ReplayRing), C.c_int, C.c_int, C.c_void_p]
+    L.urgym_norm_rows.argtypes = [C.c_void_p, C.POINTER(_abi.Normalization), C.POINTER(_abi.NormRowsArgs), C.c_int, C.c_void_p]
+    L.urgym_norm_batch.argtypes = [C.c_void_p, C.POINTER(_abi.Normalization), C.POINTER(_abi.ReplayBatch), C.c_int, C.c_void_p]
+    L.urgym_norm_snapshot.argtypes = [C.c_void_p, C.POINTER(_abi.NormState), C.POINTER(_abi.NormState), C.c_void_p, C.c_void_p]
+    L.urgym_policy_evaluate_normalized.argtypes = [C.c_void_p, C.POINTER(_abi.PolicyEvaluation), C.POINTER(_abi.Normalization), C.c_int64, C.c_int32, C.c_void_p]
+    L.urgym_rollout_collect_normalized.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.Sampling), C.c_int, C.POINTER(_abi.ReplayRing), C.c_int,
+                                                   C.POINTER(_abi.Normalization), C.c_void_p]
+    L.urgym_sac_train_normalized.argtypes = [C.c_void_p, C.POINTER(_abi.SacLearner), C.POINTER(_abi.SacSchedule), C.POINTER(_abi.Normalization),
+                                             C.POINTER(_abi.SacClipping), C.POINTER(_abi.SacNstep), C.POINTER(_abi.SacPrioritized),
+                                             C.POINTER(_abi.SacHindsight), C.POINTER(_abi.SacEvaluation), C.POINTER(_abi.SacMonitoring), C.c_void_p]
     L.urgym_actor_read_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.urgym_critic_read_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.urgym_refresh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]

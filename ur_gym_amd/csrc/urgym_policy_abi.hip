@@ -1,6 +1,6 @@
 // urgym_policy_abi.hip — the learner's half of the C-ABI of include/urgym.h: actors (create / forward / sample / rollouts), the replay
-// ring, the weight reloads and their inverse (urgym_actor_unpack, urgym_critic_unpack), the twin critic and its two gradients, the actor's parameter gradients, the Adam steps, SAC's entropy step and loss terms, the training loop that composes them in one call (urgym_sac_train; its index arithmetic is urgym_sac_schedule.h), the evaluation inside that call (urgym_eval_stats, urgym_actor_snapshot, urgym_policy_evaluate, urgym_sac_train_evaluated; urgym_eval.h, urgym_eval_schedule.h), and the training-episode statistics inside it (urgym_monitor_fold, urgym_monitor_stats, urgym_sac_train_monitored; urgym_monitor.h), and the multi-step returns (urgym_replay_sample_nstep, urgym_sac_entropy_step_nstep, urgym_sac_train_nstep; urgym_nstep.h), and prioritized replay (urgym_per_sums_count, urgym_per_rebuild, urgym_per_fill, urgym_replay_sample_prioritized, urgym_per_terms; urgym_per.h), and hindsight experience replay (urgym_replay_sample_hindsight, urgym_sac_train_hindsight; urgym_her.h), and gradient-norm clipping (urgym_actor_grad_norm, urgym_critic_grad_norm, the two scaled Adam steps, urgym_sac_train_clipped; urgym_grad_clip.h).  Host code only: every check is made here, before the first launch,
-// and every launch goes through urgym_actor.h, urgym_critic.h, urgym_replay.h, urgym_weights.h, urgym_adam.h, urgym_sac_terms.h, urgym_eval.h, urgym_monitor.h and urgym_per.h, or through do_step of urgym_hip.hip
+// ring, the weight reloads and their inverse (urgym_actor_unpack, urgym_critic_unpack), the twin critic and its two gradients, the actor's parameter gradients, the Adam steps, SAC's entropy step and loss terms, the training loop that composes them in one call (urgym_sac_train; its index arithmetic is urgym_sac_schedule.h), the evaluation inside that call (urgym_eval_stats, urgym_actor_snapshot, urgym_policy_evaluate, urgym_sac_train_evaluated; urgym_eval.h, urgym_eval_schedule.h), and the training-episode statistics inside it (urgym_monitor_fold, urgym_monitor_stats, urgym_sac_train_monitored; urgym_monitor.h), and the multi-step returns (urgym_replay_sample_nstep, urgym_sac_entropy_step_nstep, urgym_sac_train_nstep; urgym_nstep.h), and prioritized replay (urgym_per_sums_count, urgym_per_rebuild, urgym_per_fill, urgym_replay_sample_prioritized, urgym_per_terms; urgym_per.h), and hindsight experience replay (urgym_replay_sample_hindsight, urgym_sac_train_hindsight; urgym_her.h), and gradient-norm clipping (urgym_actor_grad_norm, urgym_critic_grad_norm, the two scaled Adam steps, urgym_sac_train_clipped; urgym_grad_clip.h), and running normalization (urgym_norm_workspace, urgym_norm_fold, urgym_norm_rows, urgym_norm_batch, urgym_norm_snapshot, urgym_rollout_collect_normalized, urgym_policy_evaluate_normalized, urgym_sac_train_normalized; urgym_norm.h).  Host code only: every check is made here, before the first launch,
+// and every launch goes through urgym_actor.h, urgym_critic.h, urgym_replay.h, urgym_weights.h, urgym_adam.h, urgym_sac_terms.h, urgym_eval.h, urgym_monitor.h, urgym_per.h and urgym_norm.h, or through do_step of urgym_hip.hip
 // (urgym_handle.h).  No kernel lives in this unit, so adding a check here leaves the step kernels' object file alone.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -26,6 +26,7 @@
 #include "urgym_monitor.h"
 #include "urgym_per.h"
 #include "urgym_grad_clip.h"
+#include "urgym_norm.h"
 
 using namespace urgym;
 
@@ -189,9 +190,12 @@ struct RolloutSinks {
 // Every launch below goes to `s`, and so does everything do_step launches (the step or fused launch, the RESET / PREFETCH fallbacks of
 // a dirty step, the timing events): stream order alone puts step k - 1 before the passes that read its outputs (the store pass files
 // its outcome, the actor's pass records it) and those before the step that reads their actions.
-int rollout(Handle* h, Actor* a, const urgym_sampling* how, int num_steps, const RolloutSinks& to, hipStream_t s) {
+// `norm`: given (urgym_rollout_collect_normalized) = one more launch before every policy pass, which maps the bound rows into the
+// scratch its destinations name, and the actor reads the scratch; the store pass and the step see the bound buffers as before.
+int rollout(Handle* h, Actor* a, const urgym_sampling* how, int num_steps, const RolloutSinks& to, hipStream_t s, const NormApplyCall* norm = nullptr) {
   if (num_steps == 0) return URGYM_OK;
-  const ActorEnv env = actor_env(h);
+  ActorEnv env = actor_env(h);
+  if (norm) env.observation = norm->seg[0].dst, env.achieved_goal = norm->seg[1].dst, env.desired_goal = norm->seg[2].dst;
   const size_t n = (size_t)h->cfg.num_envs, row = n * 6;
   auto at = [](float* p, size_t off) { return p ? p + off : p; };
   for (int k = 0; k <= num_steps; k++) {
@@ -212,6 +216,7 @@ int rollout(Handle* h, Actor* a, const urgym_sampling* how, int num_steps, const
       smp.log_prob = at(to.extra->log_prob, (size_t)k * n), smp.noise = at(to.extra->noise, (size_t)k * row);
       smp.mean_action = at(to.extra->mean_action, (size_t)k * row), smp.log_std = at(to.extra->log_std, (size_t)k * row);
     }
+    if (norm) norm_apply_launch(*norm, s);
     policy_launch(a, env, actions, to.traj ? &pass : nullptr, smp, s);
     if (int rc = do_step(h, actions, s)) return rc;
   }
@@ -1272,6 +1277,106 @@ struct LearnerPointer {
   const void* p;
 };
 
+// what a fold of num_steps slots from first_slot on refuses about the ring and the handle: urgym_monitor_fold's and urgym_norm_fold's
+static int check_fold_ring(Handle* h, const urgym_replay_ring* ring, int first_slot, int num_steps, const char* who) {
+  if (int rc = check_ring(h, ring, who)) return rc;
+  if (first_slot < 0 || first_slot >= ring->capacity_steps) return fail_in(h, URGYM_ERR_ARG, who, "first_slot outside [0, capacity_steps)");
+  if (!ring->truncated || !ring->is_success) return fail_in(h, URGYM_ERR_ARG, who, "the ring keeps no truncated or no is_success (an episode's end and its success are read from them)");
+  if (num_steps <= 0) return fail_in(h, URGYM_ERR_ARG, who, "num_steps must be positive");
+  if (num_steps > ring->capacity_steps) return fail_in(h, URGYM_ERR_ARG, who, "num_steps is above capacity_steps (the ring no longer holds the earlier steps)");
+  if (!h->cfg.auto_reset) return fail_in(h, URGYM_ERR_ARG, who, "the handle has auto_reset off (its episodes do not restart)");
+  return URGYM_OK;
+}
+
+// ---- running observation and reward normalization (include/urgym.h, urgym_norm_workspace ... urgym_rollout_collect_normalized;
+// DESIGN.md section 25).  As above each entry point is a checking half, which launches nothing and fills the launch struct of
+// urgym_norm.h, and a launching half, which refuses nothing.
+
+// (static: this stretch lies inside the extern "C" block, where an unnamed namespace alone would still export the names)
+// the state's thirteen pointers, all given and 8-byte aligned, and the options
+static int check_normalization(Handle* h, const urgym_normalization* norm, const char* who) {
+  static_assert(sizeof(urgym_norm_state) == 13 * sizeof(void*) && sizeof(urgym_normalization) == sizeof(urgym_norm_state) + 96, "include/urgym.h");
+  if (!norm) return fail_in(h, URGYM_ERR_ARG, who, "null normalization");
+  const urgym_norm_state& m = norm->state;
+  const LearnerPointer required[] = {{"observation_mean", m.observation_mean},       {"observation_var", m.observation_var},     {"observation_count", m.observation_count},
+                                     {"achieved_goal_mean", m.achieved_goal_mean},   {"achieved_goal_var", m.achieved_goal_var}, {"achieved_goal_count", m.achieved_goal_count},
+                                     {"desired_goal_mean", m.desired_goal_mean},     {"desired_goal_var", m.desired_goal_var},   {"desired_goal_count", m.desired_goal_count},
+                                     {"ret_mean", m.ret_mean},                       {"ret_var", m.ret_var},                     {"ret_count", m.ret_count},
+                                     {"running_ret", m.running_ret}};
+  for (const LearnerPointer& r : required) {
+    if (!r.p) return failf(h, URGYM_ERR_ARG, "%s: urgym_norm_state.%s is null", who, r.name);
+    if ((uintptr_t)r.p % 8 != 0) return failf(h, URGYM_ERR_ARG, "%s: urgym_norm_state.%s must be 8-byte aligned", who, r.name);
+  }
+  if (const char* what = norm_options_refusal(*norm)) return fail_in(h, URGYM_ERR_ARG, who, what);
+  if (actor_features(h) + 1 > NORM_FEATURE_LANES || h->obs_dim > 48 || h->goal_dim > 48)
+    return fail_in(h, URGYM_ERR_ARG, who, "the kernels are built for at most 63 features in all and 48 in a group");
+  return URGYM_OK;
+}
+
+static int check_norm_fold(Handle* h, const urgym_normalization* norm, const urgym_replay_ring* ring, int first_slot, int num_steps, const char* who, NormFoldCall* out) {
+  if (int rc = check_normalization(h, norm, who)) return rc;
+  if (int rc = check_fold_ring(h, ring, first_slot, num_steps, who)) return rc;  // urgym_monitor_fold's ring refusals
+  if (num_steps >= 65535) return fail_in(h, URGYM_ERR_ARG, who, "num_steps must be below 65535 (one grid row per slot)");
+  if (!norm->workspace) return fail_in(h, URGYM_ERR_ARG, who, "urgym_normalization.workspace is null");
+  if ((uintptr_t)norm->workspace % 8 != 0) return fail_in(h, URGYM_ERR_ARG, who, "urgym_normalization.workspace must be 8-byte aligned");
+  const uint64_t need = norm_workspace_doubles(h->cfg.num_envs, actor_features(h), num_steps) * sizeof(double);
+  if (norm->workspace_bytes < need)
+    return failf(h, URGYM_ERR_ARG, "%s: workspace_bytes is %llu, %d steps need %llu (urgym_norm_workspace)", who, (unsigned long long)norm->workspace_bytes, num_steps, (unsigned long long)need);
+  NormFoldCall& c = *out;
+  memset(&c, 0, sizeof(c));
+  c.num_envs = h->cfg.num_envs, c.capacity = ring->capacity_steps, c.first_slot = first_slot, c.num_steps = num_steps;
+  c.dim[0] = h->obs_dim, c.dim[1] = h->goal_dim, c.dim[2] = h->goal_dim;
+  c.norm_obs = norm->norm_obs != 0, c.norm_reward = norm->norm_reward != 0, c.gamma = norm->gamma, c.state = norm->state;
+  c.rows[0] = ring->observation, c.rows[1] = ring->achieved_goal, c.rows[2] = ring->desired_goal;
+  c.reward = ring->reward, c.terminated = ring->terminated, c.truncated = ring->truncated, c.workspace = (double*)norm->workspace;
+  return URGYM_OK;
+}
+
+// the three observation groups of `count` rows, src -> dst (each pair whole or absent), appended to the call's segments
+static const char* norm_row_segments(const Handle* h, const urgym_normalization& norm, const float* const src[3], float* const dst[3], NormApplyCall* c) {
+  const urgym_norm_state& m = norm.state;
+  const double* const mean[3] = {m.observation_mean, m.achieved_goal_mean, m.desired_goal_mean};
+  const double* const var[3] = {m.observation_var, m.achieved_goal_var, m.desired_goal_var};
+  const int dim[3] = {h->obs_dim, h->goal_dim, h->goal_dim};
+  for (int g = 0; g < 3; g++) {
+    if ((src[g] == nullptr) != (dst[g] == nullptr)) return "a source without its destination, or a destination without its source";
+    if (!src[g]) continue;
+    c->seg[c->segments++] = NormSegment{src[g], dst[g], mean[g], var[g], dim[g], norm.clip_obs};
+  }
+  return nullptr;
+}
+
+static int check_norm_rows(Handle* h, const urgym_normalization* norm, const urgym_norm_rows_args* rows, int count, const char* who, NormApplyCall* out) {
+  if (int rc = check_normalization(h, norm, who)) return rc;
+  if (!rows) return fail_in(h, URGYM_ERR_ARG, who, "null rows");
+  if (count <= 0) return fail_in(h, URGYM_ERR_ARG, who, "count must be positive");
+  memset(out, 0, sizeof(*out));
+  out->count = count, out->eps = norm->eps, out->identity = norm->norm_obs == 0;
+  const float* const src[3] = {rows->observation, rows->achieved_goal, rows->desired_goal};
+  float* const dst[3] = {rows->observation_out, rows->achieved_goal_out, rows->desired_goal_out};
+  if (const char* what = norm_row_segments(h, *norm, src, dst, out)) return fail_in(h, URGYM_ERR_ARG, who, what);
+  if (out->segments == 0) return fail_in(h, URGYM_ERR_ARG, who, "no group is given");
+  return URGYM_OK;
+}
+
+// segments == 0 afterwards: nothing to launch
+static int check_norm_batch(Handle* h, const urgym_normalization* norm, const urgym_replay_batch* batch, int count, const char* who, NormApplyCall* out) {
+  if (int rc = check_normalization(h, norm, who)) return rc;
+  if (!batch) return fail_in(h, URGYM_ERR_ARG, who, "null batch");
+  if (count <= 0) return fail_in(h, URGYM_ERR_ARG, who, "count must be positive");
+  memset(out, 0, sizeof(*out));
+  out->count = count, out->eps = norm->eps;
+  if (norm->norm_obs != 0) {
+    float* const now[3] = {batch->observation, batch->achieved_goal, batch->desired_goal};
+    float* const next[3] = {batch->next_observation, batch->next_achieved_goal, batch->next_desired_goal};
+    norm_row_segments(h, *norm, now, now, out);
+    norm_row_segments(h, *norm, next, next, out);
+  }
+  if (norm->norm_reward != 0 && batch->reward)
+    out->seg[out->segments++] = NormSegment{batch->reward, batch->reward, nullptr, norm->state.ret_var, 1, norm->clip_reward};
+  return URGYM_OK;
+}
+
 // after the launches of one stage: urgym_last_error names the iteration and the stage
 int train_stage(Handle* h, const char* who, int iteration, const char* stage) {
   const hipError_t e = hipGetLastError();
@@ -1290,9 +1395,11 @@ struct TrainHooks {
 
 // `nstep`: null = the one-step update; given (urgym_sac_train_nstep) = the update whose gather, third call and entropy step are the
 // multi-step ones.  `her`: given (urgym_sac_train_hindsight) = the update whose gather is urgym_replay_sample_hindsight.  `clip`: given
-// (urgym_sac_train_clipped) = the update with the two norm launches and the scaled steps
+// (urgym_sac_train_clipped) = the update with the two norm launches and the scaled steps.  `norm`: given (urgym_sac_train_normalized) = the
+// collection whose actor reads normalized rows, one fold of the statistics after every collection, one urgym_norm_batch after every gather
 int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, void* stream, const TrainHooks* hooks, const urgym_sac_nstep* nstep = nullptr,
-                   const urgym_sac_prioritized* per = nullptr, const urgym_sac_hindsight* her = nullptr, const urgym_sac_clipping* clip = nullptr);
+                   const urgym_sac_prioritized* per = nullptr, const urgym_sac_hindsight* her = nullptr, const urgym_sac_clipping* clip = nullptr,
+                   const urgym_normalization* norm = nullptr);
 
 }  // namespace
 
@@ -1305,7 +1412,7 @@ int urgym_sac_train(void* handle, const urgym_sac_learner* learner, const urgym_
 namespace {
 
 int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, void* stream, const TrainHooks* hooks, const urgym_sac_nstep* nstep,
-                   const urgym_sac_prioritized* per, const urgym_sac_hindsight* her, const urgym_sac_clipping* clip) {
+                   const urgym_sac_prioritized* per, const urgym_sac_hindsight* her, const urgym_sac_clipping* clip, const urgym_normalization* norm) {
   Handle* h = (Handle*)handle;
   if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
   if (!learner) return fail_in(h, URGYM_ERR_ARG, who, "null learner");
@@ -1372,6 +1479,25 @@ int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learn
 
   // ---- the checking halves, with the numbers of the first collection and the first update
   const int M = L.count, K = S.steps_per_iteration, G = S.updates_per_iteration;
+  NormFoldCall norm_fold;
+  NormApplyCall norm_collect, norm_batch;
+  memset(&norm_batch, 0, sizeof(norm_batch));
+  if (norm) {  // the option's own refusals, whether or not the call holds an update
+    if (int rc = check_normalization(h, norm, who)) return rc;
+    if (K > 0) {
+      if (int rc = check_norm_fold(h, norm, &L.ring, S.first_slot, K, who, &norm_fold)) return rc;
+      if (norm->norm_obs != 0) {
+        if (!norm->scratch) return fail_in(h, URGYM_ERR_ARG, who, "urgym_normalization.scratch is null");
+        const size_t n = (size_t)h->cfg.num_envs;
+        float* const ach = norm->scratch + n * (size_t)h->obs_dim;
+        const urgym_norm_rows_args rows{h->buf.observation, h->buf.achieved_goal, h->buf.desired_goal, norm->scratch, ach, ach + n * (size_t)h->goal_dim};
+        if (int rc = check_norm_rows(h, norm, &rows, h->cfg.num_envs, who, &norm_collect)) return rc;
+      }
+    }
+    if (M <= 0) return fail_in(h, URGYM_ERR_ARG, who, "count must be positive");
+    if (int rc = check_norm_batch(h, norm, &L.batch, M, who, &norm_batch)) return rc;
+  }
+  const bool normalized_rows = norm && K > 0 && norm->norm_obs != 0, folds = norm && K > 0 && norm->training != 0;
   const int64_t updates = sac_schedule_updates(S);
   const float scale = (float)(1.0 / (double)M), neg_scale = (float)(-1.0 / (double)M);  // as SACLearner._update_on_device hands them over
   Actor* collector = nullptr;
@@ -1386,7 +1512,12 @@ int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learn
   // the collection of iteration i: the launches of urgym_rollout_collect
   auto collect = [&](int i, const SacIteration& it) {
     const urgym_sampling how{it.collect_mode, 0, L.seed, it.collect_first_draw};
-    const int rc = rollout(h, collector, &how, K, RolloutSinks{nullptr, nullptr, &L.ring, it.collect_first_slot}, s);
+    const int rc = rollout(h, collector, &how, K, RolloutSinks{nullptr, nullptr, &L.ring, it.collect_first_slot}, s, normalized_rows ? &norm_collect : nullptr);
+    if (!rc && folds) {  // urgym_norm_fold on the slots just written
+      norm_fold.first_slot = it.collect_first_slot;
+      norm_fold_launch(norm_fold, s);
+      if (int stage = train_stage(h, who, i, "norm_fold")) return stage;
+    }
     if (!rc && per) {  // urgym_per_fill on the slots just written
       per_fill_ranges(per_fill, it.collect_first_slot, K);
       per_fill_launch(per_fill, s);
@@ -1559,6 +1690,10 @@ int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learn
       else
         replay_gather_launch(gather, s);
       if (int rc = train_stage(h, who, i, "replay_sample")) return rc;
+      if (norm_batch.segments > 0) {
+        norm_apply_launch(norm_batch, s);
+        if (int rc = train_stage(h, who, i, "norm_batch")) return rc;
+      }
       next_sample.smp.draw = up.gather_draw;
       policy_launch(next_sample.a, next_sample.env, next_sample.actions, nullptr, next_sample.smp, s);
       if (int rc = train_stage(h, who, i, "actor_sample_rows (next rows)")) return rc;
@@ -1671,7 +1806,31 @@ struct PolicyEvaluation {
   urgym_eval_record* records;
   EvalStatsCall stats;       // record and eval_index move per evaluation
   ActorSnapshotCall snapshot;  // when moves per evaluation
+  bool normalized, normalized_rows;  // urgym_policy_evaluate_normalized; ... with norm_obs on
+  NormApplyCall norm;                // the evaluation handle's bound rows into eval_scratch
+  NormSnapshotCall norm_snapshot;    // when moves per evaluation
 };
+
+static int check_normalization(Handle* h, const urgym_normalization* norm, const char* who);
+static int check_norm_rows(Handle* h, const urgym_normalization* norm, const urgym_norm_rows_args* rows, int count, const char* who, NormApplyCall* out);
+int check_norm_snapshot(Handle* h, const urgym_norm_state* source, const urgym_norm_state* destination, const int32_t* when, const char* who, NormSnapshotCall* out);
+
+// What urgym_policy_evaluate_normalized checks beyond urgym_policy_evaluate, after check_policy_evaluation has filled `out`.  The
+// dimensions are the evaluation handle's; messages go to `report`.
+int check_evaluation_normalization(Handle* report, Handle* eh, const urgym_normalization* norm, const char* who, PolicyEvaluation* out) {
+  auto relay = [&](int rc) { return report == eh ? rc : failf(report, rc, "%.200s", eh->err); };
+  if (int rc = check_normalization(eh, norm, who)) return relay(rc);
+  if (!norm->eval_scratch) return fail_in(report, URGYM_ERR_ARG, who, "urgym_normalization.eval_scratch is null");
+  if (int rc = check_norm_snapshot(eh, &norm->state, norm->best_state, nullptr, who, &out->norm_snapshot)) return relay(rc);
+  out->normalized = true, out->normalized_rows = norm->norm_obs != 0;
+  if (out->normalized_rows) {
+    const size_t n = (size_t)eh->cfg.num_envs;
+    float* const ach = norm->eval_scratch + n * (size_t)eh->obs_dim;
+    const urgym_norm_rows_args rows{eh->buf.observation, eh->buf.achieved_goal, eh->buf.desired_goal, norm->eval_scratch, ach, ach + n * (size_t)eh->goal_dim};
+    if (int rc = check_norm_rows(eh, norm, &rows, eh->cfg.num_envs, who, &out->norm)) return relay(rc);
+  }
+  return URGYM_OK;
+}
 
 // Every check of urgym_policy_evaluate but those of eval_index and record_slot (check_evaluation_slot).  Messages go to `report` -- the
 // evaluation handle itself, or the training handle of urgym_sac_train_evaluated.
@@ -1740,13 +1899,18 @@ int launch_policy_evaluation(PolicyEvaluation& c, int64_t eval_index, int32_t re
   // later one the twist of the previous evaluation's last step -- other first observations, other returns, no fair comparison
   HIP_TRY(eh, hipMemsetAsync(eh->buf.observation, 0, sizeof(float) * (size_t)eh->cfg.num_envs * (size_t)eh->obs_dim, s));
   if (int rc = urgym_reset(eh, nullptr, c.reset_seed, s)) return rc;
-  if (int rc = rollout(eh, c.actor, nullptr, c.num_steps, RolloutSinks{&c.traj, nullptr, nullptr, 0}, s)) return rc;
+  if (int rc = rollout(eh, c.actor, nullptr, c.num_steps, RolloutSinks{&c.traj, nullptr, nullptr, 0}, s, c.normalized_rows ? &c.norm : nullptr)) return rc;
   urgym_eval_record* record = c.records + record_slot;
   c.stats.eval_index = eval_index, c.stats.record = record;
   eval_stats_launch(c.stats, s);
   HIP_TRY(eh, hipGetLastError());
   c.snapshot.when = &record->improved;
   actor_snapshot_launch(c.snapshot, s);
+  if (c.normalized) {  // the statistics the actor was selected under, beside it
+    HIP_TRY(eh, hipGetLastError());
+    c.norm_snapshot.when = &record->improved;
+    norm_snapshot_launch(c.norm_snapshot, s);
+  }
   return launched(eh);
 }
 
@@ -1760,6 +1924,7 @@ struct TrainEvaluation {
   PolicyEvaluation call;
   int64_t done;  // evaluations launched so far
   const char* who;  // the entry point that runs them: urgym_sac_train_evaluated, or urgym_sac_train_monitored
+  const urgym_normalization* norm = nullptr;  // urgym_sac_train_normalized: the evaluations are urgym_policy_evaluate_normalized's
 };
 
 const char* const TRAIN_EVALUATED = "urgym_sac_train_evaluated";
@@ -1775,6 +1940,8 @@ int train_evaluation_check(void* ctx) {
   if (eh == h) return fail_in(h, URGYM_ERR_ARG, who, "eval_handle is the training handle (an evaluation would reset the training env; evaluation on it is not supported)");
   if (eh->device != h->device) return fail_in(h, URGYM_ERR_ARG, who, "the training handle and the evaluation handle are on different devices");
   if (int rc = check_policy_evaluation(h, eh, &E.evaluation, who, &t.call)) return rc;
+  if (t.norm)
+    if (int rc = check_evaluation_normalization(h, eh, t.norm, who, &t.call)) return rc;
   const urgym_actor_tensors& p = t.learner->actor_adam.param;
   const float* const params[PACK_ACTOR_TENSORS] = {p.w0, p.b0, p.w1, p.b1, p.w_mu, p.b_mu, p.w_log_std, p.b_log_std};
   for (int i = 0; i < PACK_ACTOR_TENSORS; i++)
@@ -1818,12 +1985,7 @@ int check_monitor_state(Handle* h, const urgym_monitor_state* state, const char*
 
 int check_monitor_fold(Handle* h, const urgym_monitor_state* state, const urgym_replay_ring* ring, int first_slot, int num_steps, const char* who, MonitorFoldCall* out) {
   if (int rc = check_monitor_state(h, state, who)) return rc;
-  if (int rc = check_ring(h, ring, who)) return rc;
-  if (first_slot < 0 || first_slot >= ring->capacity_steps) return fail_in(h, URGYM_ERR_ARG, who, "first_slot outside [0, capacity_steps)");
-  if (!ring->truncated || !ring->is_success) return fail_in(h, URGYM_ERR_ARG, who, "the ring keeps no truncated or no is_success (an episode's end and its success are read from them)");
-  if (num_steps <= 0) return fail_in(h, URGYM_ERR_ARG, who, "num_steps must be positive");
-  if (num_steps > ring->capacity_steps) return fail_in(h, URGYM_ERR_ARG, who, "num_steps is above capacity_steps (the ring no longer holds the earlier steps)");
-  if (!h->cfg.auto_reset) return fail_in(h, URGYM_ERR_ARG, who, "the handle has auto_reset off (its episodes do not restart)");
+  if (int rc = check_fold_ring(h, ring, first_slot, num_steps, who)) return rc;
   *out = MonitorFoldCall{h->cfg.num_envs, ring->capacity_steps, first_slot, num_steps, *state, ring->reward, ring->terminated, ring->truncated, ring->is_success};
   return URGYM_OK;
 }
@@ -2055,6 +2217,140 @@ int urgym_sac_train_clipped(void* handle, const urgym_sac_learner* learner, cons
     return sac_train_body(who, handle, learner, schedule, stream, &hooks, nstep_or_NULL, prioritized_or_NULL, hindsight_or_NULL, clipping);
   }
   return sac_train_body(who, handle, learner, schedule, stream, nullptr, nstep_or_NULL, prioritized_or_NULL, hindsight_or_NULL, clipping);
+}
+
+}  // extern "C"
+
+namespace {
+
+// the twelve pointers of a state that is read or written without its running_ret
+int check_norm_state12(Handle* h, const urgym_norm_state* st, const char* who, const char* what) {
+  if (!st) return failf(h, URGYM_ERR_ARG, "%s: null %s", who, what);
+  const void* const p[12] = {st->observation_mean,   st->observation_var,  st->observation_count,  st->achieved_goal_mean, st->achieved_goal_var, st->achieved_goal_count,
+                             st->desired_goal_mean,  st->desired_goal_var, st->desired_goal_count, st->ret_mean,           st->ret_var,           st->ret_count};
+  for (const void* q : p)
+    if (!q || (uintptr_t)q % 8 != 0) return failf(h, URGYM_ERR_ARG, "%s: a pointer of %s is null or not 8-byte aligned (mean, var and count of the four groups)", who, what);
+  return URGYM_OK;
+}
+
+int check_norm_snapshot(Handle* h, const urgym_norm_state* source, const urgym_norm_state* destination, const int32_t* when, const char* who, NormSnapshotCall* out) {
+  if (int rc = check_norm_state12(h, source, who, "source state")) return rc;
+  if (int rc = check_norm_state12(h, destination, who, "destination state")) return rc;
+  if (actor_features(h) + 1 > NORM_FEATURE_LANES) return fail_in(h, URGYM_ERR_ARG, who, "the kernels are built for at most 63 features in all");
+  memset(out, 0, sizeof(*out));
+  out->dim[0] = h->obs_dim, out->dim[1] = h->goal_dim, out->dim[2] = h->goal_dim;
+  out->src = *source, out->dst = *destination, out->when = when;
+  return URGYM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int urgym_norm_snapshot(void* handle, const urgym_norm_state* source, const urgym_norm_state* destination, const int32_t* when, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  NormSnapshotCall c;
+  if (int rc = check_norm_snapshot(h, source, destination, when, "urgym_norm_snapshot", &c)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  norm_snapshot_launch(c, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_policy_evaluate_normalized(void* eval_handle, const urgym_policy_evaluation* evaluation, const urgym_normalization* normalization, int64_t eval_index, int32_t record_slot, void* stream) {
+  const char* who = "urgym_policy_evaluate_normalized";
+  Handle* eh = (Handle*)eval_handle;
+  if (!eh) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  PolicyEvaluation c;
+  if (int rc = check_policy_evaluation(eh, eh, evaluation, who, &c)) return rc;
+  if (int rc = check_evaluation_slot(eh, *evaluation, eval_index, record_slot, who)) return rc;
+  if (int rc = check_evaluation_normalization(eh, eh, normalization, who, &c)) return rc;
+  return launch_policy_evaluation(c, eval_index, record_slot, (hipStream_t)stream);
+}
+
+int urgym_norm_workspace(void* handle, int num_steps, uint64_t* bytes) {
+  const char* who = "urgym_norm_workspace";
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (!bytes) return fail_in(h, URGYM_ERR_ARG, who, "null bytes");
+  if (num_steps <= 0) return fail_in(h, URGYM_ERR_ARG, who, "num_steps must be positive");
+  *bytes = norm_workspace_doubles(h->cfg.num_envs, actor_features(h), num_steps) * sizeof(double);
+  return URGYM_OK;
+}
+
+int urgym_norm_fold(void* handle, const urgym_normalization* norm, const urgym_replay_ring* ring, int first_slot, int num_steps, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  NormFoldCall c;
+  if (int rc = check_norm_fold(h, norm, ring, first_slot, num_steps, "urgym_norm_fold", &c)) return rc;
+  if (norm->training == 0) return URGYM_OK;
+  HIP_TRY(h, hipSetDevice(h->device));
+  norm_fold_launch(c, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_norm_rows(void* handle, const urgym_normalization* norm, const urgym_norm_rows_args* rows, int count, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  NormApplyCall c;
+  if (int rc = check_norm_rows(h, norm, rows, count, "urgym_norm_rows", &c)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  norm_apply_launch(c, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_norm_batch(void* handle, const urgym_normalization* norm, const urgym_replay_batch* batch, int count, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  NormApplyCall c;
+  if (int rc = check_norm_batch(h, norm, batch, count, "urgym_norm_batch", &c)) return rc;
+  if (c.segments == 0) return URGYM_OK;
+  HIP_TRY(h, hipSetDevice(h->device));
+  norm_apply_launch(c, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_rollout_collect_normalized(void* handle, void* actor, const urgym_sampling* how, int num_steps, const urgym_replay_ring* ring, int first_slot, const urgym_normalization* norm, void* stream) {
+  const char* who = "urgym_rollout_collect_normalized";
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  Actor* a = nullptr;
+  if (int rc = check_collect(h, actor, how, num_steps, ring, first_slot, who, &a)) return rc;
+  if (int rc = check_normalization(h, norm, who)) return rc;
+  if (norm->norm_obs == 0) return rollout(h, a, how, num_steps, RolloutSinks{nullptr, nullptr, ring, first_slot}, (hipStream_t)stream);
+  if (!norm->scratch) return fail_in(h, URGYM_ERR_ARG, who, "urgym_normalization.scratch is null");
+  const size_t n = (size_t)h->cfg.num_envs;
+  float* const obs = norm->scratch;
+  float* const ach = obs + n * (size_t)h->obs_dim;
+  float* const des = ach + n * (size_t)h->goal_dim;
+  const urgym_norm_rows_args rows{h->buf.observation, h->buf.achieved_goal, h->buf.desired_goal, obs, ach, des};
+  NormApplyCall c;
+  if (int rc = check_norm_rows(h, norm, &rows, h->cfg.num_envs, who, &c)) return rc;
+  return rollout(h, a, how, num_steps, RolloutSinks{nullptr, nullptr, ring, first_slot}, (hipStream_t)stream, &c);
+}
+
+int urgym_sac_train_normalized(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_normalization* normalization, const urgym_sac_clipping* clipping_or_NULL, const urgym_sac_nstep* nstep_or_NULL, const urgym_sac_prioritized* prioritized_or_NULL, const urgym_sac_hindsight* hindsight_or_NULL, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream) {
+  const char* who = "urgym_sac_train_normalized";
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (!normalization) return fail_in(h, URGYM_ERR_ARG, who, "null normalization");
+  if ((nstep_or_NULL != nullptr) + (prioritized_or_NULL != nullptr) + (hindsight_or_NULL != nullptr) > 1)
+    return fail_in(h, URGYM_ERR_ARG, who, "at most one of nstep, prioritized and hindsight may be given (each has a gather of its own)");
+  TrainEvaluation e;
+  e.h = h, e.learner = learner, e.schedule = schedule, e.evaluation = evaluation_or_NULL, e.s = (hipStream_t)stream, e.done = 0, e.who = who;
+  e.norm = normalization;
+  TrainMonitoring t;
+  t.h = h, t.learner = learner, t.schedule = schedule, t.monitoring = monitoring_or_NULL, t.s = (hipStream_t)stream, t.done = 0;
+  t.evaluation = evaluation_or_NULL ? &e : nullptr, t.who = who;
+  if (monitoring_or_NULL) {
+    const TrainHooks hooks{train_monitoring_check, train_monitoring_after, &t};
+    return sac_train_body(who, handle, learner, schedule, stream, &hooks, nstep_or_NULL, prioritized_or_NULL, hindsight_or_NULL, clipping_or_NULL, normalization);
+  }
+  if (evaluation_or_NULL) {
+    const TrainHooks hooks{train_evaluation_check, train_evaluation_after, &e};
+    return sac_train_body(who, handle, learner, schedule, stream, &hooks, nstep_or_NULL, prioritized_or_NULL, hindsight_or_NULL, clipping_or_NULL, normalization);
+  }
+  return sac_train_body(who, handle, learner, schedule, stream, nullptr, nstep_or_NULL, prioritized_or_NULL, hindsight_or_NULL, clipping_or_NULL, normalization);
 }
 
 }  // extern "C"

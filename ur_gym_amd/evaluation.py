@@ -1447,11 +1447,12 @@ class DeviceReplay:
                 t.index_copy_(0, slots, torch.from_numpy(np.ascontiguousarray(state["ring"][name])).to(self.env.device))
         self.cursor, self.filled = cursor, filled
 
-    def collect(self, actor, num_steps, sample=None):
+    def collect(self, actor, num_steps, sample=None, normalizer=None):
         """`num_steps` x (store pass, actor, step) from slot ``cursor`` on, without returning to Python; `sample` as in
-        ``env.rollout_policy`` (None = the deterministic policy).  Advances ``cursor`` and ``filled``."""
+        ``env.rollout_policy`` (None = the deterministic policy); `normalizer` as in ``env.collect`` (the actor reads normalized rows;
+        nothing is folded here).  Advances ``cursor`` and ``filled``."""
         K = int(num_steps)
-        self.env.collect(actor, K, self, sample=sample, first_slot=self.cursor)
+        self.env.collect(actor, K, self, sample=sample, first_slot=self.cursor, **({} if normalizer is None else dict(normalizer=normalizer)))
         self.cursor = (self.cursor + K) % self.capacity
         self.filled = min(self.capacity, self.filled + K)
 
@@ -1579,7 +1580,7 @@ class DeviceReplay:
                 "actions": flat["action"], "rewards": flat["reward"], "terminated": flat["terminated"].view(torch.bool),
                 "truncated": flat["truncated"].view(torch.bool), "is_success": flat["is_success"].view(torch.bool), "index": flat["index"]}
 
-    def sample_targets(self, actor, critic, batch_size, seed, draw, gamma, ent_coef, sample=None, n_steps=None, hindsight=None):
+    def sample_targets(self, actor, critic, batch_size, seed, draw, gamma, ent_coef, sample=None, n_steps=None, hindsight=None, normalizer=None):
         """``sample``, then a' ~ pi(.|s') on the gathered next observations (``env.policy_actions(rows=)``), then SAC's target
         y = r + gamma (1 - terminated) (min_i Q_i(s', a') - ent_coef log pi(a'|s')) (``env.critic_values``): three launches.
         `sample` = how a' is drawn (default: gaussian with this call's seed and draw).  Returns the batch with ``next_actions``,
@@ -1587,13 +1588,18 @@ class DeviceReplay:
 
         With `n_steps` the batch is ``sample(..., n_steps=, gamma=)`` and the third launch writes the bootstrap value alone: the
         batch gets ``q_min_next`` = min_i Q_i(s', a') beside its ``discount`` instead of ``target`` (``env.entropy_step_nstep`` forms
-        y from them); `ent_coef` is not used."""
+        y from them); `ent_coef` is not used.
+
+        With `normalizer` (a ``DeviceNormalizer``) the gathered batch is normalized in place right after the gather
+        (``env.norm_batch``: one more launch); with `n_steps` the normalized reward is the row's accumulated return."""
         if hindsight is not None:  # dict(n_sampled_goal=, strategy=): the batch is ``sample_hindsight``'s, the rest as below
             if n_steps is not None:
                 raise ValueError("hindsight together with multi-step returns is out of scope")
             batch = self.sample_hindsight(batch_size, seed, draw, **hindsight)
         else:
             batch = self.sample(batch_size, seed, draw, n_steps=n_steps, gamma=None if n_steps is None else gamma)
+        if normalizer is not None:
+            self.env.norm_batch(normalizer, batch)
         how = dict(mode="gaussian", seed=seed, first_draw=draw) if sample is None else sample
         nxt = batch["next_observations"]
         batch["next_actions"], batch["next_log_prob"] = self.env.policy_actions(actor, sample=how, rows=nxt)
@@ -1707,10 +1713,10 @@ class DevicePrioritizedReplay(DeviceReplay):
         self.check_args(self.capacity, num_steps=num_steps, first_slot=first_slot)
         _native.check(env.lib.urgym_per_fill(env._h, C.byref(self._pri), int(first_slot), int(num_steps), env._stream()), env._h)
 
-    def collect(self, actor, num_steps, sample=None):
+    def collect(self, actor, num_steps, sample=None, normalizer=None):
         """``DeviceReplay.collect``, then ``fill`` on the slots just written: a new transition is drawn at the largest priority seen."""
         first = self.cursor
-        super().collect(actor, num_steps, sample=sample)
+        super().collect(actor, num_steps, sample=sample, normalizer=normalizer)
         self.fill(first, num_steps)
 
     def sample_prioritized(self, batch_size, seed, draw):
@@ -1772,12 +1778,15 @@ class DevicePrioritizedReplay(DeviceReplay):
         return out
 
 
-def run_closed_loop_device(env, actor, max_steps=100):
+def run_closed_loop_device(env, actor, max_steps=100, normalizer=None):
     """``run_closed_loop`` with everything on the device: `env` is a UR5ReachVectorEnv (auto-reset off, like there), `actor` a
     DeviceActor of it.  One native call enqueues the max_steps x (actor, step) launches; the per-trial reward, success flag and
-    last step come from the episode summary the launches keep (model_test.py:38-50).  Returns the same dictionary."""
+    last step come from the episode summary the launches keep (model_test.py:38-50).  Returns the same dictionary.  With `normalizer`
+    (a ``DeviceNormalizer`` of an environment of this kind) the actor reads normalized rows, step by step from Python."""
     import torch
 
+    if normalizer is not None:
+        return _run_closed_loop_normalized(env, actor, normalizer, max_steps)
     rec = env.rollout_policy(actor, max_steps, record=("episode_return", "episode_last_step", "episode_success"))
     torch.cuda.synchronize(env.device)
     reward = rec["episode_return"].cpu().numpy()
@@ -1785,6 +1794,32 @@ def run_closed_loop_device(env, actor, max_steps=100):
     last = rec["episode_last_step"].cpu().numpy().astype(np.float64)
     return {"success_rate_percent": 100.0 * success.mean(), "mean_episode_reward": float(reward.mean()),
             "mean_last_step_index": float(last.mean()), "success": success, "reward": reward, "last_step": last}
+
+
+def _run_closed_loop_normalized(env, actor, normalizer, max_steps):
+    """``run_closed_loop_device`` whose actor reads rows normalized with `normalizer`'s statistics as they stand (a ``DeviceNormalizer``,
+    usually the TRAINING environment's: SB3's ``sync_envs_normalization``): a Python loop of ``env.norm_rows``, ``policy_actions(rows=)``
+    and ``step``, three launches a step, with the episode of every env summed in float64 on the device as the rollout's summary sums
+    it (model_test.py:42-49): rewards while the episode runs, closed at ``terminated`` or at the last step, success as that step reports."""
+    import torch
+
+    n, dev = env.num_envs, env.device
+    ret = torch.zeros(n, dtype=torch.float64, device=dev)
+    alive = torch.ones(n, dtype=torch.bool, device=dev)
+    success = torch.zeros(n, dtype=torch.bool, device=dev)
+    last = torch.full((n,), max_steps - 1, dtype=torch.int32, device=dev)
+    for k in range(max_steps):
+        rows = env.norm_rows(normalizer, {g: env.buf[g] for g in NORM_ROW_GROUPS})
+        _, rew, term, trunc, info = env.step(env.policy_actions(actor, rows=rows))
+        ret += torch.where(alive, rew.to(torch.float64), torch.zeros_like(ret))
+        done = alive & (term | (k == max_steps - 1))
+        success |= done & info["is_success"]
+        last = torch.where(done, torch.full_like(last, k), last)
+        alive &= ~done
+    torch.cuda.synchronize(dev)
+    reward, ok, last = ret.cpu().numpy(), success.cpu().numpy().astype(bool), last.cpu().numpy().astype(np.float64)
+    return {"success_rate_percent": 100.0 * ok.mean(), "mean_episode_reward": float(reward.mean()), "mean_last_step_index": float(last.mean()),
+            "success": ok, "reward": reward, "last_step": last}
 
 
 # ------------------------------------------------------------------------------------------------ evaluation inside the training call
@@ -1837,9 +1872,12 @@ class DeviceEvaluation:
     tensors or arrays) that gives the shape and the eval actor's first weights.  Every evaluation zeroes `test_env`'s observation
     buffer and resets it with `seed` -- ``reset(seed=)`` as a fresh environment answers it: on UR5DynReach-v1 a reset keeps the
     velocity slot of the observation it finds -- so that all of them play the same episodes, and runs `num_steps` steps (default: the
-    env's max_episode_steps)."""
+    env's max_episode_steps).  With `normalizer` (the TRAINING environment's ``DeviceNormalizer``, of the same env kind and device) every
+    evaluation runs its actor on rows normalized with those statistics as they stand when it runs (urgym_policy_evaluate_normalized:
+    SB3's ``sync_envs_normalization``), and an evaluation that improves also snapshots the statistics into ``best_norm``, which
+    ``save_best`` writes beside the actor under ``norm/...`` keys (``load_best_normalization`` reads them back)."""
 
-    def __init__(self, test_env, actor_tensors_like, num_steps=None, seed=0, capacity=64):
+    def __init__(self, test_env, actor_tensors_like, num_steps=None, seed=0, capacity=64, normalizer=None):
         import torch
 
         from . import _abi
@@ -1867,6 +1905,19 @@ class DeviceEvaluation:
         self.best_index = torch.full((1,), -1, dtype=torch.int64, device=dev)
         self.count = 0   # evaluations made: the next one's eval_index and record slot
         self._struct = self._source = None
+        self.normalizer = self.best_norm = self._norm_struct = None
+        if normalizer is not None:
+            import ctypes as C
+
+            other = getattr(normalizer, "env", None)
+            if not isinstance(normalizer, DeviceNormalizer) or other.env_kind != test_env.env_kind or other.device != test_env.device:
+                raise ValueError("DeviceEvaluation: normalizer must be a DeviceNormalizer of an environment of test_env's kind and device")
+            self.normalizer = normalizer
+            self.eval_scratch = torch.zeros((N * (test_env.obs_dim + 2 * test_env.goal_dim),), dtype=torch.float32, device=dev)
+            self.best_norm = {k: torch.from_numpy(a).to(dev) for k, a in norm_initial_state(1, test_env.obs_dim, test_env.goal_dim).items() if k != "running_ret"}
+            self._best_norm_struct = _abi.NormState()
+            for k, t in self.best_norm.items():
+                setattr(self._best_norm_struct, k, C.cast(t.data_ptr(), C.POINTER(C.c_double)))
 
     def struct(self, tensors):
         """The checked ``urgym_policy_evaluation`` for the source `tensors` (a dict of device tensors as ``DeviceActor.check_parameters``
@@ -1899,6 +1950,21 @@ class DeviceEvaluation:
         self._struct, self._source, self._keep = E, ptrs, dict(tensors)
         return E
 
+    def norm_struct(self):
+        """The ``urgym_normalization`` of an evaluation with this object: the normalizer's as it stands, with ``eval_scratch`` and
+        ``best_state`` set.  None without a normalizer."""
+        import ctypes as C
+
+        from . import _abi
+
+        if self.normalizer is None:
+            return None
+        Z = _abi.Normalization.from_buffer_copy(bytes(self.normalizer.struct()))
+        Z.eval_scratch = C.cast(self.eval_scratch.data_ptr(), C.POINTER(C.c_float))
+        Z.best_state = C.pointer(self._best_norm_struct)
+        self._norm_struct = Z
+        return Z
+
     def advance(self, evaluations):
         """What a native call that made `evaluations` evaluations leaves behind on the host side: the counters, and the environment's
         own bookkeeping of ``reset(seed=)``."""
@@ -1918,7 +1984,10 @@ class DeviceEvaluation:
         if self.count >= self.capacity:
             raise ValueError(f"DeviceEvaluation: all {self.capacity} records are used")
         env, slot = self.env, self.count
-        _native.check(env.lib.urgym_policy_evaluate(env._h, C.byref(self.struct(tensors)), slot, slot, env._stream()), env._h)
+        if self.normalizer is not None:
+            _native.check(env.lib.urgym_policy_evaluate_normalized(env._h, C.byref(self.struct(tensors)), C.byref(self.norm_struct()), slot, slot, env._stream()), env._h)
+        else:
+            _native.check(env.lib.urgym_policy_evaluate(env._h, C.byref(self.struct(tensors)), slot, slot, env._stream()), env._h)
         self.advance(1)
         return slot
 
@@ -1951,16 +2020,27 @@ class DeviceEvaluation:
 
     def save_best(self, path):
         """Writes the best actor as an ``.npz`` under ACTOR_ARRAYS + LOG_STD_ARRAYS: what ``DeviceActor.load`` and
-        ``DeterministicActor.load`` read.  Synchronises."""
-        save_actor(path, self.best)
+        ``DeterministicActor.load`` read.  With a normalizer the file also holds the statistics the best actor was selected under, as
+        float64 arrays under ``norm/<field>`` (the twelve of ``best_norm``) and the options under ``norm/options`` (gamma, epsilon,
+        clip_obs, clip_reward, norm_obs, norm_reward as float64): ``load_best_normalization`` reads them.  Without one the file is what it
+        always was.  Synchronises."""
+        extra, normalizer = None, getattr(self, "normalizer", None)
+        if normalizer is not None:
+            o = normalizer.options
+            extra = {"norm/" + k: v.cpu().numpy() for k, v in self.best_norm.items()}
+            extra["norm/options"] = np.array([o["gamma"], o["epsilon"], o["clip_obs"], o["clip_reward"], float(o["norm_obs"]), float(o["norm_reward"])], np.float64)
+        save_actor(path, self.best, extra)
 
     def state_dict(self):
         """The evaluation for a checkpoint: the records written so far, the best actor's tensors, ``best_mean``, ``best_index`` and
         ``count``; ``seed`` and ``num_steps``, which a load checks; and the evaluation environment's ``checkpoint_state`` (its sticky
         status words are the only thing of it that an evaluation does not rewrite).  Synchronises."""
-        return dict(seed=self.seed, num_steps=self.num_steps, count=self.count, records=self.records[:self.count].cpu().numpy(),
-                    best={k: v.cpu().numpy() for k, v in self.best.items()}, best_mean=self.best_mean.cpu().numpy(),
-                    best_index=self.best_index.cpu().numpy(), env=self.env.checkpoint_state())
+        out = dict(seed=self.seed, num_steps=self.num_steps, count=self.count, records=self.records[:self.count].cpu().numpy(),
+                   best={k: v.cpu().numpy() for k, v in self.best.items()}, best_mean=self.best_mean.cpu().numpy(),
+                   best_index=self.best_index.cpu().numpy(), env=self.env.checkpoint_state())
+        if getattr(self, "normalizer", None) is not None:  # an evaluation without a normalizer gains no key
+            out["best_norm"] = {k: v.cpu().numpy() for k, v in self.best_norm.items()}
+        return out
 
     def load_state_dict(self, state):
         """Restores what ``state_dict`` saved, in place (a ``struct`` made earlier stays valid).  Raises ValueError, before anything
@@ -1979,7 +2059,18 @@ class DeviceEvaluation:
         for k, v in best.items():
             if v.dtype != np.float32 or v.shape != tuple(self.best[k].shape):
                 raise ValueError(f"DeviceEvaluation.load_state_dict: best[{k!r}] must be float32 {tuple(self.best[k].shape)}, got {v.dtype} {v.shape}")
+        normalizer = getattr(self, "normalizer", None)
+        if (state.get("best_norm") is None) != (normalizer is None):
+            raise ValueError("DeviceEvaluation.load_state_dict: the best statistics are in the state and this evaluation has no normalizer, or the reverse")
+        best_norm = None
+        if normalizer is not None:
+            best_norm = {k: np.asarray(state["best_norm"][k]) for k in self.best_norm}
+            for k, v in best_norm.items():
+                if v.dtype != np.float64 or v.shape != tuple(self.best_norm[k].shape):
+                    raise ValueError(f"DeviceEvaluation.load_state_dict: best_norm[{k!r}] must be float64 {tuple(self.best_norm[k].shape)}, got {v.dtype} {v.shape}")
         self.env.check_checkpoint(state["env"])
+        for k, v in (best_norm or {}).items():
+            self.best_norm[k].copy_(torch.from_numpy(v))
         for k, v in best.items():
             self.best[k].copy_(torch.from_numpy(v))
         self.best_mean.copy_(torch.from_numpy(np.asarray(state["best_mean"], dtype=np.float64).reshape(1)))
@@ -1996,10 +2087,22 @@ class DeviceEvaluation:
         self.actor.close()
 
 
-def save_actor(path, tensors):
+def load_best_normalization(path):
+    """The statistics ``DeviceEvaluation.save_best`` wrote beside the best actor: ``(state, options)`` -- the twelve float64 arrays under
+    the names of ``_abi.NORM_STATE_FIELDS`` (no ``running_ret``) and a dict of the options -- or None for a file that holds none."""
+    with np.load(path, allow_pickle=False) as f:
+        keys = [k for k in f.files if k.startswith("norm/")]
+        if not keys:
+            return None
+        state = {k[len("norm/"):]: np.array(f[k]) for k in keys if k != "norm/options"}
+        o = np.array(f["norm/options"])
+    return state, dict(gamma=float(o[0]), epsilon=float(o[1]), clip_obs=float(o[2]), clip_reward=float(o[3]), norm_obs=bool(o[4]), norm_reward=bool(o[5]))
+
+
+def save_actor(path, tensors, extra=None):
     """An actor's ten arrays (device tensors or arrays under ACTOR_ARRAYS + LOG_STD_ARRAYS) as an ``.npz`` ``DeviceActor.load`` and
-    ``DeterministicActor.load`` read back bitwise."""
-    arrays = {}
+    ``DeterministicActor.load`` read back bitwise; `extra`: further arrays under names of their own."""
+    arrays = dict(extra or {})
     for k in ACTOR_ARRAYS + LOG_STD_ARRAYS:
         v = tensors[k]
         arrays[k] = np.ascontiguousarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float32)
@@ -2200,3 +2303,274 @@ class DeviceMonitor:
         raw = self.records[:self.count].cpu().numpy().tobytes()
         recs = [_abi.MonitorRecord.from_buffer_copy(raw, i * C.sizeof(_abi.MonitorRecord)) for i in range(self.count)]
         return [{name: getattr(r, name) for name, _ in _abi.MonitorRecord._fields_} for r in recs]
+
+
+# ------------------------------------------------------------------------------------------------ running normalization (VecNormalize)
+def norm_sums(terms):
+    """THE ORDER OF THE SUMS of include/urgym.h ("running observation and reward normalization on the device") in numpy: `terms`
+    float64 [N] or [N, d], summed over the rows per column, bitwise what the two fold kernels leave.  Slabs of 128 rows, four chains
+    per slab over rows q, q + 4, ..., ``(c0 + c1) + (c2 + c3)``, sixteen parts over slabs c, c + 16, ..., then ``part[c] += part[c + s]``
+    for s = 8, 4, 2, 1.  An absent term is +0.0: no partial sum is ever -0.0, so that leaves the bits a skipped term would."""
+    from . import _abi
+
+    x = np.asarray(terms)
+    if x.dtype != np.float64 or x.ndim not in (1, 2) or x.shape[0] < 1:
+        raise ValueError(f"terms must be a float64 [N] or [N, d] array, got {x.dtype} {x.shape}")
+    flat = x.ndim == 1
+    x = x.reshape(x.shape[0], -1)
+    n, d = x.shape
+    R, Q, P = _abi.NORM_SLAB_ROWS, _abi.NORM_CHAINS, _abi.NORM_PARTS
+    slabs = -(-n // R)
+    padded = np.zeros((slabs * R, d), np.float64)
+    padded[:n] = x
+    rows = padded.reshape(slabs, R // Q, Q, d)
+    with np.errstate(all="ignore"):
+        chain = np.zeros((slabs, Q, d), np.float64)
+        for i in range(R // Q):
+            chain = chain + rows[:, i]
+        slab = (chain[:, 0] + chain[:, 1]) + (chain[:, 2] + chain[:, 3])
+        rounds = -(-slabs // P)
+        held = np.zeros((rounds * P, d), np.float64)
+        held[:slabs] = slab
+        held = held.reshape(rounds, P, d)
+        part = np.zeros((P, d), np.float64)
+        for i in range(rounds):
+            part = part + held[i]
+        s = P // 2
+        while s >= 1:
+            part[:s] = part[:s] + part[s:2 * s]
+            s //= 2
+    return part[0, 0] if flat else part[0].copy()
+
+
+def norm_merge(mean, var, count, s1, s2, n):
+    """One slot's merge into one group (SB3's ``RunningMeanStd.update_from_moments``), every line ONE float64 operation in the
+    association include/urgym.h writes: `mean`, `var` float64 [d], `count` a float64, `s1` and `s2` the sums of the slot, `n` the row
+    count.  Returns ``(mean', var', count')``."""
+    mean, var = np.asarray(mean, np.float64), np.asarray(var, np.float64)
+    count, nn = np.float64(count), np.float64(n)
+    with np.errstate(all="ignore"):
+        bm = s1 / nn
+        m2 = s2 / nn
+        sq = bm * bm
+        d = m2 - sq
+        bv = np.where(d > 0.0, d, np.float64(0.0))
+        delta = bm - mean
+        tot = count + nn
+        dn = delta * nn
+        step = dn / tot
+        ma = var * count
+        mb = bv * nn
+        mab = ma + mb
+        d2 = delta * delta
+        d2c = d2 * count
+        d2cn = d2c * nn
+        cross = d2cn / tot
+        new_m2 = mab + cross
+        return mean + step, new_m2 / tot, tot
+
+
+NORM_ROW_GROUPS = ("observation", "achieved_goal", "desired_goal")
+
+
+def norm_initial_state(num_envs, obs_dim, goal_dim):
+    """SB3's ``RunningMeanStd`` at its start for the four groups, and ``running_ret`` = 0: a dict under ``_abi.NORM_STATE_FIELDS``."""
+    from . import _abi
+
+    out = {}
+    for name, shape in _abi.NORM_STATE_FIELDS:
+        fill = 1.0 if name.endswith("_var") else (_abi.NORM_INITIAL_COUNT if name.endswith("_count") else 0.0)
+        out[name] = np.full(shape(num_envs, obs_dim, goal_dim), fill, np.float64)
+    return out
+
+
+def _norm_arrays(state):
+    from . import _abi
+
+    names = [name for name, _ in _abi.NORM_STATE_FIELDS]
+    if not isinstance(state, dict) or sorted(state) != sorted(names):
+        raise ValueError(f"state must be a dict under {names}")
+    out = {}
+    for name in names:
+        a = np.asarray(state[name])
+        if a.dtype != np.float64 or a.ndim != 1:
+            raise ValueError(f"state[{name!r}] must be a float64 1-d array, got {a.dtype} {a.shape}")
+        out[name] = a.copy()
+    return out
+
+
+def norm_fold(state, ring, first_slot, num_steps, gamma, norm_obs=True, norm_reward=True):
+    """THE FOLD of include/urgym.h in numpy, bitwise what urgym_norm_fold leaves: `state` a dict under ``_abi.NORM_STATE_FIELDS``;
+    `ring` a dict of the ring's arrays ``observation`` [C, N, obs_dim], ``achieved_goal``, ``desired_goal`` [C, N, goal_dim], ``reward``
+    float32 [C, N], ``terminated`` and ``truncated`` uint8 or bool [C, N]; the slots (first_slot + k) % C are folded in order, one merge
+    per slot and group.  Returns the new state (the argument is not written)."""
+    st = _norm_arrays(state)
+    reward = np.asarray(ring["reward"])
+    cap, n = reward.shape
+    first, K = int(first_slot), int(num_steps)
+    if reward.dtype != np.float32 or not 0 <= first < cap or not 1 <= K <= cap or st["running_ret"].shape != (n,):
+        raise ValueError(f"norm_fold: reward must be float32 [C, N], first_slot in [0, C), num_steps in [1, C], running_ret [N]; got {reward.dtype} {reward.shape}, {first_slot}, {num_steps}")
+    flags = []
+    for name in ("terminated", "truncated"):
+        x = np.asarray(ring[name])
+        if x.dtype not in (np.dtype(np.uint8), np.dtype(bool)) or x.shape != reward.shape:
+            raise ValueError(f"norm_fold: {name} must be a uint8 or bool {reward.shape} array, got {x.dtype} {x.shape}")
+        flags.append(x.view(np.uint8) if x.dtype == bool else x)
+    rows = {}
+    for g in NORM_ROW_GROUPS:
+        x = np.asarray(ring[g])
+        if x.dtype != np.float32 or x.ndim != 3 or x.shape[:2] != reward.shape or x.shape[2] != st[g + "_mean"].shape[0]:
+            raise ValueError(f"norm_fold: {g} must be a float32 [C, N, {st[g + '_mean'].shape[0]}] array, got {x.dtype} {x.shape}")
+        rows[g] = x
+    g64 = np.float64(gamma)
+    with np.errstate(all="ignore"):
+        for k in range(K):
+            s = (first + k) % cap
+            if norm_obs:
+                for g in NORM_ROW_GROUPS:
+                    x = rows[g][s].astype(np.float64)
+                    m, v, c = norm_merge(st[g + "_mean"], st[g + "_var"], st[g + "_count"][0], norm_sums(x), norm_sums(x * x), n)
+                    st[g + "_mean"], st[g + "_var"], st[g + "_count"] = m, v, np.array([c], np.float64)
+            if norm_reward:
+                scaled = st["running_ret"] * g64
+                running = scaled + reward[s].astype(np.float64)
+                m, v, c = norm_merge(st["ret_mean"], st["ret_var"], st["ret_count"][0], norm_sums(running), norm_sums(running * running), n)
+                st["ret_mean"], st["ret_var"], st["ret_count"] = np.atleast_1d(m), np.atleast_1d(v), np.array([c], np.float64)
+                st["running_ret"] = np.where((flags[0][s] | flags[1][s]) != 0, np.float64(0.0), running)
+    return st
+
+
+def _norm_clip(v, clip):
+    c = np.float64(clip)
+    lo = np.where(v < -c, -c, v)
+    return np.where(lo > c, c, lo)
+
+
+def normalize_rows(x, mean, var, eps, clip):
+    """NORMALIZE of include/urgym.h in numpy, bitwise what urgym_norm_rows / urgym_norm_batch write: `x` float32 [..., d], `mean` and
+    `var` float64 [d]; ``inv = 1 / sqrt(var + eps)`` once per feature, then ``(float)min(max(((double)x - mean) * inv, -clip), clip)``."""
+    x = np.asarray(x)
+    if x.dtype != np.float32:
+        raise ValueError(f"x must be float32, got {x.dtype}")
+    with np.errstate(all="ignore"):
+        inv = np.float64(1.0) / np.sqrt(np.asarray(var, np.float64) + np.float64(eps))
+        centred = x.astype(np.float64) - np.asarray(mean, np.float64)
+        return _norm_clip(centred * inv, clip).astype(np.float32)
+
+
+def normalize_reward(r, var, eps, clip):
+    """A reward as urgym_norm_batch writes it: ``(float)min(max((double)r * inv_ret, -clip), clip)``, no mean subtracted (SB3)."""
+    r = np.asarray(r)
+    if r.dtype != np.float32:
+        raise ValueError(f"r must be float32, got {r.dtype}")
+    with np.errstate(all="ignore"):
+        inv = np.float64(1.0) / np.sqrt(np.float64(np.asarray(var).reshape(-1)[0]) + np.float64(eps))
+        return _norm_clip(r.astype(np.float64) * inv, clip).astype(np.float32)
+
+
+class DeviceNormalizer:
+    """stable-baselines3's ``VecNormalize`` on the device: the running mean and variance of the three observation groups the collecting
+    actor saw and of the discounted return, in float64 device tensors (``self.state``, under ``_abi.NORM_STATE_FIELDS``), the scratch
+    rows the collecting actor reads and the fold's workspace.  `env`: a UR5ReachVectorEnv with auto_reset.  ``fold`` follows a
+    ``collect`` with its arguments; ``training = False`` freezes the statistics (``fold`` then launches nothing).  `fold_steps`: the most
+    steps one fold (or one iteration of ``SACLearner.train``) may hold; the workspace is sized for it."""
+
+    def __init__(self, env, gamma=0.95, norm_obs=True, norm_reward=True, clip_obs=10.0, clip_reward=10.0, epsilon=1e-8, fold_steps=32):
+        import ctypes as C
+
+        import torch
+
+        from . import _abi, _native
+
+        if not env.cfg.auto_reset:
+            raise ValueError("DeviceNormalizer: env must be made with auto_reset=True (the return of an env that is not reset does not restart)")
+        self.options = self.check_options(gamma=gamma, norm_obs=norm_obs, norm_reward=norm_reward, clip_obs=clip_obs, clip_reward=clip_reward, epsilon=epsilon)
+        if isinstance(fold_steps, bool) or int(fold_steps) != fold_steps or not 1 <= int(fold_steps) < 65535:
+            raise ValueError(f"DeviceNormalizer: fold_steps must be an integer in [1, 65535), got {fold_steps!r}")
+        self.env, self.training, self.fold_steps = env, True, int(fold_steps)
+        dev = env.device
+        self.state = {name: torch.from_numpy(a).to(dev) for name, a in norm_initial_state(env.num_envs, env.obs_dim, env.goal_dim).items()}
+        self.scratch = torch.zeros((env.num_envs * (env.obs_dim + 2 * env.goal_dim),), dtype=torch.float32, device=dev)
+        need = C.c_uint64(0)
+        _native.check(env.lib.urgym_norm_workspace(env._h, self.fold_steps, C.byref(need)), env._h)
+        self.workspace = torch.zeros((need.value // 8,), dtype=torch.float64, device=dev)
+        Z = _abi.Normalization()
+        for name, _ in _abi.NORM_STATE_FIELDS:
+            setattr(Z.state, name, C.cast(self.state[name].data_ptr(), C.POINTER(C.c_double)))
+        o = self.options
+        Z.gamma, Z.eps, Z.clip_obs, Z.clip_reward = o["gamma"], o["epsilon"], o["clip_obs"], o["clip_reward"]
+        Z.norm_obs, Z.norm_reward, Z.reserved0 = int(o["norm_obs"]), int(o["norm_reward"]), 0
+        Z.scratch = C.cast(self.scratch.data_ptr(), C.POINTER(C.c_float))
+        Z.workspace, Z.workspace_bytes = self.workspace.data_ptr(), need.value
+        self._struct = Z
+
+    @staticmethod
+    def check_options(*, gamma, norm_obs, norm_reward, clip_obs, clip_reward, epsilon):
+        """Raises ValueError for what the entry points refuse about the options (include/urgym.h); returns them as plain values.
+        Needs no GPU."""
+        for name, v in (("norm_obs", norm_obs), ("norm_reward", norm_reward)):
+            if not isinstance(v, (bool, np.bool_)):
+                raise ValueError(f"{name} must be True or False, got {v!r}")
+        for name, v in (("gamma", gamma), ("clip_obs", clip_obs), ("clip_reward", clip_reward), ("epsilon", epsilon)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise ValueError(f"{name} must be a number, got {v!r}")
+        if not 0.0 <= float(gamma) <= 1.0:
+            raise ValueError(f"gamma must be in [0, 1], got {gamma!r}")
+        if not (float(epsilon) >= 0.0 and np.isfinite(float(epsilon))):
+            raise ValueError(f"epsilon must be finite and at least 0, got {epsilon!r}")
+        for name, v in (("clip_obs", clip_obs), ("clip_reward", clip_reward)):
+            if not float(v) > 0.0:
+                raise ValueError(f"{name} must be positive (+inf is allowed), got {v!r}")
+        return dict(gamma=float(gamma), norm_obs=bool(norm_obs), norm_reward=bool(norm_reward), clip_obs=float(clip_obs), clip_reward=float(clip_reward),
+                    epsilon=float(epsilon))
+
+    def struct(self):
+        """The ``urgym_normalization`` as it stands: ``training`` is read now."""
+        self._struct.training = int(bool(self.training))
+        return self._struct
+
+    def fold(self, replay, first_slot, num_steps):
+        """The `num_steps` steps `replay` holds from `first_slot` on, folded into the statistics (``env.norm_fold``): call it behind the
+        ``collect`` that wrote them, with its arguments.  Two launches, none with ``training`` False; NOT synchronised."""
+        self.env.norm_fold(self, replay, first_slot, num_steps)
+
+    def normalize(self, rows, out=None):
+        """``env.norm_rows`` with these statistics: one launch, NOT synchronised."""
+        return self.env.norm_rows(self, rows, out)
+
+    def normalize_batch(self, batch):
+        """``env.norm_batch`` with these statistics, in place: one launch, NOT synchronised."""
+        return self.env.norm_batch(self, batch)
+
+    def state_dict(self):
+        """The statistics for a checkpoint: the thirteen arrays, the options, ``training``, and the env shape a load checks.
+        Synchronises."""
+        env = self.env
+        return dict(num_envs=env.num_envs, obs_dim=env.obs_dim, goal_dim=env.goal_dim, options=dict(self.options), training=bool(self.training),
+                    state={k: v.cpu().numpy() for k, v in self.state.items()})
+
+    def check_state_dict(self, state):
+        """Raises ValueError unless `state` is a ``state_dict`` of a normalizer of this env shape and these options.  Writes nothing."""
+        from . import _abi
+
+        env = self.env
+        for k, v in dict(num_envs=env.num_envs, obs_dim=env.obs_dim, goal_dim=env.goal_dim).items():
+            if int(state[k]) != v:
+                raise ValueError(f"DeviceNormalizer.load_state_dict: {k} is {state[k]} in the state, {v} here")
+        if dict(state["options"]) != self.options:
+            raise ValueError(f"DeviceNormalizer.load_state_dict: the options are {dict(state['options'])} in the state, {self.options} here")
+        arrays = _norm_arrays({k: np.asarray(v) for k, v in dict(state["state"]).items()})
+        for name, shape in _abi.NORM_STATE_FIELDS:
+            if arrays[name].shape != tuple(shape(env.num_envs, env.obs_dim, env.goal_dim)):
+                raise ValueError(f"DeviceNormalizer.load_state_dict: state[{name!r}] must be {tuple(shape(env.num_envs, env.obs_dim, env.goal_dim))}, got {arrays[name].shape}")
+        return arrays
+
+    def load_state_dict(self, state):
+        """Restores what ``state_dict`` saved, in place (the struct stays valid).  Everything is checked before anything is written."""
+        import torch
+
+        arrays = self.check_state_dict(state)
+        for k, v in arrays.items():
+            self.state[k].copy_(torch.from_numpy(v))
+        self.training = bool(state["training"])
+

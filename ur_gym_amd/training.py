@@ -51,6 +51,11 @@ minibatch gather on the HIP kernels, and gradients and optimisers in torch autog
     ``env.actor_gradient_norm``), and the step multiplies each gradient element by it as it reads it (``scale=``): fifteen launches.
     The ``.grad`` tensors are not written, the temperature's scalar step is not clipped.  ``None``, the default, makes exactly the
     calls above.
+    With ``normalize=True`` (it needs ``device_entropy=True``; SB3's ``VecNormalize``) the learner owns an
+    ``evaluation.DeviceNormalizer`` (``self.normalizer``): ``collect`` runs the actor on rows normalized with the running statistics
+    (one more launch per step; the ring keeps the raw rows) and folds the collected slots into them afterwards (two launches), and
+    ``update`` normalizes the gathered minibatch in place right after the gather (``env.norm_batch``: fourteen launches, sixteen with
+    clipping).  ``self.normalizer.training = False`` freezes the statistics.  ``False``, the default, makes exactly the calls above.
     None of them synchronises with the host.  ``train`` runs the whole loop in one native call and, given an
     ``evaluation.DeviceEvaluation``, the reference's EvalCallback inside it: evaluations of the deterministic policy at a fixed interval of
     updates, their statistics as records on the device, and the best actor's tensors, which ``DeviceEvaluation.save_best`` writes as an
@@ -83,6 +88,9 @@ HER_DEFAULTS = dict(hindsight=False, her_n_sampled_goal=4, her_strategy="future"
 # norm, torch.nn.utils.clip_grad_norm_'s idiom on the device.  SB3's SAC does not clip; None, the default, is the learner as it was.  Kept
 # apart like the two above: a run without it saves no new key.
 CLIP_DEFAULTS = dict(max_grad_norm=None)
+# Running observation and reward normalization: SACLearner(normalize=True) is SB3's VecNormalize on the device, with
+# its defaults.  Kept apart like the three above: a run without it saves none of these, and no statistics.
+NORM_DEFAULTS = dict(normalize=False, norm_obs=True, norm_reward=True, clip_obs=10.0, clip_reward=10.0, norm_epsilon=1e-8)
 
 
 def _mlp(n_in, hidden, n_out=None):
@@ -171,11 +179,21 @@ class SACLearner:
     the device, inside the Adam steps; with any of the options above."""
 
     def __init__(self, env, seed=0, **overrides):
-        unknown = [k for k in overrides if k not in SAC_DEFAULTS and k not in PER_DEFAULTS and k not in HER_DEFAULTS and k not in CLIP_DEFAULTS]
+        unknown = [k for k in overrides if k not in SAC_DEFAULTS and k not in PER_DEFAULTS and k not in HER_DEFAULTS and k not in CLIP_DEFAULTS and k not in NORM_DEFAULTS]
         if unknown:
-            raise TypeError(f"unknown hyperparameters {unknown}; available: {sorted(SAC_DEFAULTS) + sorted(PER_DEFAULTS) + sorted(HER_DEFAULTS) + sorted(CLIP_DEFAULTS)}")
-        hp = dict(SAC_DEFAULTS, **PER_DEFAULTS, **HER_DEFAULTS, **CLIP_DEFAULTS)
+            raise TypeError(f"unknown hyperparameters {unknown}; available: "
+                            f"{sorted(SAC_DEFAULTS) + sorted(PER_DEFAULTS) + sorted(HER_DEFAULTS) + sorted(CLIP_DEFAULTS) + sorted(NORM_DEFAULTS)}")
+        hp = dict(SAC_DEFAULTS, **PER_DEFAULTS, **HER_DEFAULTS, **CLIP_DEFAULTS, **NORM_DEFAULTS)
         hp.update(overrides)
+        if not isinstance(hp["normalize"], bool):
+            raise ValueError(f"normalize must be True or False, got {hp['normalize']!r}")
+        if hp["normalize"]:
+            from .evaluation import DeviceNormalizer
+
+            if not hp["device_entropy"]:
+                raise ValueError("normalize=True needs device_entropy=True (the collecting actor and the update read the normalized rows between the device's launches)")
+            DeviceNormalizer.check_options(gamma=hp["gamma"], norm_obs=hp["norm_obs"], norm_reward=hp["norm_reward"], clip_obs=hp["clip_obs"],
+                                           clip_reward=hp["clip_reward"], epsilon=hp["norm_epsilon"])
         if hp["max_grad_norm"] is not None:
             with np.errstate(over="ignore"):
                 bound = hp["max_grad_norm"]
@@ -280,6 +298,13 @@ class SACLearner:
             scale = torch.zeros((2,), dtype=torch.float32, device=dev)  # the critics' coefficient, then the actor's
             self.clip_state = dict(scale=scale, critic_scale=scale[0:1], actor_scale=scale[1:2], critic_grad_norm=torch.zeros((1,), dtype=torch.float32, device=dev),
                                    actor_grad_norm=torch.zeros((1,), dtype=torch.float32, device=dev))
+        # with normalize the running statistics, the actor's scratch rows and the fold's workspace are the normalizer's
+        self.normalizer = None
+        if hp["normalize"]:
+            from .evaluation import DeviceNormalizer
+
+            self.normalizer = DeviceNormalizer(env, gamma=hp["gamma"], norm_obs=hp["norm_obs"], norm_reward=hp["norm_reward"], clip_obs=hp["clip_obs"],
+                                               clip_reward=hp["clip_reward"], epsilon=hp["norm_epsilon"])
         self._train = None  # the scratch and the checked struct of train(), per replay
         self.env_steps = 0  # per env; decides between the warm-up and the policy
         self.draw = 0       # draw index of the next collection pass
@@ -287,10 +312,17 @@ class SACLearner:
     def collect(self, replay, num_steps, monitor=None):
         """`num_steps` env steps of all N envs into `replay`, with uniform actions before ``learning_starts`` env steps and the sampled
         policy afterwards (a call is one or the other: the mode is decided when it starts).  With `monitor` (an
-        ``evaluation.DeviceMonitor``) the steps just collected are folded into its state: one more launch."""
+        ``evaluation.DeviceMonitor``) the steps just collected are folded into its state: one more launch.  With ``normalize`` the actor
+        reads normalized rows and the steps are folded into the statistics first (at most ``normalizer.fold_steps`` steps a call)."""
         mode = "uniform" if self.env_steps * self.env.num_envs < self.hp["learning_starts"] else "gaussian"
         first = replay.cursor
-        replay.collect(self.device_actor, num_steps, sample=dict(mode=mode, seed=self.seed, first_draw=self.draw))
+        if self.normalizer is not None:
+            if int(num_steps) > self.normalizer.fold_steps:
+                raise ValueError(f"collect: with normalize at most fold_steps = {self.normalizer.fold_steps} steps a call, got {num_steps}")
+            replay.collect(self.device_actor, num_steps, sample=dict(mode=mode, seed=self.seed, first_draw=self.draw), normalizer=self.normalizer)
+            self.normalizer.fold(replay, first, num_steps)
+        else:
+            replay.collect(self.device_actor, num_steps, sample=dict(mode=mode, seed=self.seed, first_draw=self.draw))
         if monitor is not None:
             monitor.fold(replay, first, num_steps)
         self.env_steps += int(num_steps)
@@ -391,7 +423,8 @@ class SACLearner:
         if hp.get("prioritized"):
             return self._update_prioritized(replay, seed, draw)
         her = dict(hindsight=dict(n_sampled_goal=hp["her_n_sampled_goal"], strategy=hp["her_strategy"])) if hp.get("hindsight") else {}
-        batch = replay.sample_targets(self.device_actor, self.target, M, seed, draw, gamma, 0.0, **({} if n_steps == 1 else dict(n_steps=n_steps)), **her)
+        norm = {} if self.normalizer is None else dict(normalizer=self.normalizer)
+        batch = replay.sample_targets(self.device_actor, self.target, M, seed, draw, gamma, 0.0, **({} if n_steps == 1 else dict(n_steps=n_steps)), **her, **norm)
         rows = batch["observations"]
         how = dict(mode="gaussian", seed=seed, first_draw=int(draw) | 1 << 63)
         action_pi, log_prob = env.policy_actions(self.device_actor, sample=how, rows=rows)
@@ -452,6 +485,8 @@ class SACLearner:
         hp, env, st, es = self.hp, self.env, self.adam_state, self.entropy_state
         M, gamma = int(hp["batch_size"]), float(hp["gamma"])
         batch = replay.sample_prioritized(M, seed, draw)
+        if self.normalizer is not None:
+            self.normalizer.normalize_batch(batch)
         rows, nxt = batch["observations"], batch["next_observations"]
         next_actions, next_log_prob = env.policy_actions(self.device_actor, sample=dict(mode="gaussian", seed=seed, first_draw=draw), rows=nxt)
         target = env.critic_values(self.target, next_actions, rows=nxt, reward=batch["rewards"], terminated=batch["terminated"], log_prob=next_log_prob,
@@ -540,7 +575,9 @@ class SACLearner:
         by the fill of its slots, every update is ``update``'s seventeen launches.  With ``hindsight`` it is urgym_sac_train_hindsight:
         the thirteen launches with the gather of ``DeviceReplay.sample_hindsight``.  With ``max_grad_norm`` it is
         urgym_sac_train_clipped with whichever of those apply: two more launches per update, and the result also holds
-        ``critic_grad_norm`` and ``actor_grad_norm``, one entry per update like the losses."""
+        ``critic_grad_norm`` and ``actor_grad_norm``, one entry per update like the losses.  With ``normalize`` it is
+        urgym_sac_train_normalized with whichever of those apply: the normalized collection, one fold of the statistics per iteration
+        and one ``norm_batch`` per update; not together with `evaluation` unless ``norm_obs`` is off."""
         from .evaluation import warmup_iterations
 
         if (evaluation is None) != (eval_every is None):
@@ -569,7 +606,8 @@ class SACLearner:
                       **({} if monitor is None else dict(monitor=monitor, log_every=log_every)),
                       **({} if tr["nstep"] is None else dict(nstep=tr["nstep"])),
                       **({} if tr["prioritized"] is None else dict(prioritized=tr["prioritized"])),
-                      **({} if tr["hindsight"] is None else dict(hindsight=tr["hindsight"])), **clipping)
+                      **({} if tr["hindsight"] is None else dict(hindsight=tr["hindsight"])), **clipping,
+                      **({} if self.normalizer is None else dict(normalizer=self.normalizer)))
         self.env_steps += n * K
         self.draw += n * K
         st["step"] += updates
@@ -599,7 +637,8 @@ class SACLearner:
         """The hyperparameters as a checkpoint holds them: ``n_steps`` only where it is not 1, so that the file of a one-step run is
         what it was before the option existed (``check_state_dict`` reads an absent ``n_steps`` as 1)."""
         return {k: v for k, v in self.hp.items() if (k != "n_steps" or int(v) != 1) and (k not in PER_DEFAULTS or self.hp.get("prioritized"))
-                and (k not in HER_DEFAULTS or self.hp.get("hindsight")) and (k not in CLIP_DEFAULTS or v is not None)}
+                and (k not in HER_DEFAULTS or self.hp.get("hindsight")) and (k not in CLIP_DEFAULTS or v is not None)
+                and (k not in NORM_DEFAULTS or self.hp.get("normalize"))}
 
     def state_dict(self):
         """Everything the learner is, as host arrays and scalars: the actor's eight and the critics' twelve parameter tensors, the
@@ -619,6 +658,8 @@ class SACLearner:
                                      critic=[[host(w) for w in pair] for pair in st["critic"]])
         if es is not None:
             out["entropy_state"] = dict(exp_avg=es["exp_avg"].cpu().numpy(), exp_avg_sq=es["exp_avg_sq"].cpu().numpy())
+        if self.normalizer is not None:  # a run without the option gains no key
+            out["normalizer"] = self.normalizer.state_dict()
         out["torch"] = dict({name: _optimizer_to_host(opt.state_dict()) for name, opt in self._optimizers().items()},
                             generator=self.noise.get_state().cpu().numpy())
         return out
@@ -684,6 +725,16 @@ class SACLearner:
         for k, default in CLIP_DEFAULTS.items():  # a file without clipping holds no max_grad_norm
             if state["hp"].get(k, default) != self.hp.get(k, default):
                 raise ValueError(f"load_state_dict: {k} is {state['hp'].get(k, default)!r} in the checkpoint, {self.hp.get(k, default)!r} here")
+        for k, default in NORM_DEFAULTS.items():  # a file without normalization holds none of the six, and no statistics
+            if k != "normalize" and not self.hp.get("normalize") and not state["hp"].get("normalize"):
+                continue
+            if state["hp"].get(k, default) != self.hp.get(k, default):
+                raise ValueError(f"load_state_dict: {k} is {state['hp'].get(k, default)!r} in the checkpoint, {self.hp.get(k, default)!r} here")
+        normalizer = getattr(self, "normalizer", None)
+        if (state.get("normalizer") is None) != (normalizer is None):
+            raise ValueError(f"load_state_dict: the statistics of normalize are {'absent from' if state.get('normalizer') is None else 'present in'} the checkpoint and the reverse here")
+        if normalizer is not None:
+            normalizer.check_state_dict(state["normalizer"])
         for name, mine in (("adam_state", self.adam_state), ("entropy_state", self.entropy_state)):
             if (state[name] is None) != (mine is None):
                 raise ValueError(f"load_state_dict: {name} is {'absent' if state[name] is None else 'present'} in the checkpoint and the reverse here")
@@ -720,6 +771,8 @@ class SACLearner:
             opt.load_state_dict(_optimizer_from_host(state["torch"][name], opt, dev))
         self.noise.set_state(torch.from_numpy(np.ascontiguousarray(state["torch"]["generator"])))
         self.seed, self.env_steps, self.draw = int(state["seed"]), int(state["env_steps"]), int(state["draw"])
+        if self.normalizer is not None:
+            self.normalizer.load_state_dict(state["normalizer"])
         if self._train is not None:
             self._train["binding"].struct.seed = self.seed  # the collection's seed of a binding made before the load
         self._repack([{k: torch.from_numpy(np.ascontiguousarray(a)).to(dev) for k, a in w.items()} for w in target])

@@ -863,7 +863,8 @@ class UR5ReachVectorEnv:
 
     def sac_train(self, learner, critic_loss, actor_loss, ent_coef_loss, *, first_slot, filled_steps, num_iterations, steps_per_iteration=1,
                   updates_per_iteration=1, uniform_iterations=0, idle_iterations=0, collect_first_draw=0, update_first_draw=0, first_step=1,
-                  evaluation=None, eval_every=None, monitor=None, log_every=None, nstep=None, prioritized=None, hindsight=None, clipping=None):
+                  evaluation=None, eval_every=None, monitor=None, log_every=None, nstep=None, prioritized=None, hindsight=None, clipping=None,
+                  normalizer=None):
         """``num_iterations`` x (a collection of ``steps_per_iteration`` steps, ``updates_per_iteration`` SAC updates) in ONE native
         call (urgym_sac_train): the launches of ``collect`` and of the thirteen calls of an update, bit for bit, without returning to
         Python in between.  `learner`: what ``sac_learner`` returned, or a dict of its keyword arguments (then built and checked here).
@@ -899,7 +900,13 @@ class UR5ReachVectorEnv:
         With `clipping` (a dict: ``max_grad_norm``, ``scale``, a float32 [2] scratch tensor, and ``critic_grad_norm`` and
         ``actor_grad_norm``, float32 tensors of one entry per update of the call like the losses) the call is urgym_sac_train_clipped,
         with whichever of the options above are given: every update runs ``critic_gradient_norm`` and ``actor_gradient_norm`` before
-        the two steps, which take the coefficients (``scale=``); update u writes the norms to entry u.  Without it nothing changes."""
+        the two steps, which take the coefficients (``scale=``); update u writes the norms to entry u.  Without it nothing changes.
+
+        With `normalizer` (an ``evaluation.DeviceNormalizer`` of this environment) the call is urgym_sac_train_normalized, with
+        whichever of the options above are given: every collection is ``collect(..., normalizer=)`` followed by ``norm_fold`` of its
+        slots, and every update's gather is followed by ``norm_batch``.  An `evaluation` given with it must have been made with this
+        normalizer (``DeviceEvaluation(..., normalizer=)``): its evaluations are ``evaluation.evaluate``'s, on normalized rows, with the
+        statistics snapshot beside the best actor.  Without it nothing changes."""
         from .evaluation import DeviceEvaluation, DeviceMonitor, _her_arguments, evaluation_points, monitor_points, relabel_threshold, training_schedule
 
         who = "sac_train"
@@ -977,8 +984,25 @@ class UR5ReachVectorEnv:
             C_ = _abi.SacClipping(max_grad_norm, 0, self._float_ptr(who, "clipping['scale']", clipping["scale"], (2,)),
                                   self._float_ptr(who, "clipping['critic_grad_norm']", clipping["critic_grad_norm"], (updates,)),
                                   self._float_ptr(who, "clipping['actor_grad_norm']", clipping["actor_grad_norm"], (updates,)))
+        if evaluation is not None and getattr(evaluation, "normalizer", None) is not normalizer:
+            raise ValueError(f"{who}: the evaluation and the call must share one normalizer (DeviceEvaluation(..., normalizer=)), or have none")
+        if normalizer is not None:
+            Z_ = self._normalization(who, normalizer)
+            if evaluation is not None:
+                Z_ = evaluation.norm_struct()
+            if sched["steps_per_iteration"] > normalizer.fold_steps:
+                raise ValueError(f"{who}: steps_per_iteration must be at most the normalizer's fold_steps = {normalizer.fold_steps} (its workspace)")
         try:
-            if clipping is not None:
+            if normalizer is not None:
+                _native.check(self.lib.urgym_sac_train_normalized(self._h, C.byref(L), C.byref(S), C.byref(Z_), C.byref(C_) if clipping is not None else None,
+                                                                  C.byref(N_) if nstep is not None else None, C.byref(P_) if prioritized is not None else None,
+                                                                  C.byref(H_) if hindsight is not None else None, C.byref(E_) if evaluation is not None else None,
+                                                                  C.byref(M_) if monitor is not None else None, self._stream()), self._h)
+                if monitor is not None:
+                    monitor.advance(sched["num_iterations"], len(logged))
+                if evaluation is not None:
+                    evaluation.advance(len(points))
+            elif clipping is not None:
                 _native.check(self.lib.urgym_sac_train_clipped(self._h, C.byref(L), C.byref(S), C.byref(C_), C.byref(N_) if nstep is not None else None,
                                                                C.byref(P_) if prioritized is not None else None, C.byref(H_) if hindsight is not None else None,
                                                                C.byref(E_) if evaluation is not None else None,
@@ -1112,12 +1136,100 @@ class UR5ReachVectorEnv:
         _native.check(self.lib.urgym_rollout_sampled(self._h, a, C.byref(how), K, C.byref(traj), C.byref(extra), self._stream()), self._h)
         return out
 
-    def collect(self, actor, num_steps, replay, sample=None, first_slot=None):
+    def _normalization(self, who, normalizer, same_kind=False):
+        """The ``urgym_normalization`` of `normalizer`, an ``evaluation.DeviceNormalizer`` of this environment, as it stands now.
+        `same_kind`: one of another environment of this env kind on this device will do (only its statistics are read)."""
+        other = getattr(normalizer, "env", None)
+        if not hasattr(normalizer, "struct") or (other is not self and not (same_kind and other is not None and other.env_kind == self.env_kind
+                                                                            and other.device == self.device)):
+            raise ValueError(f"{who}: normalizer must be a DeviceNormalizer of this environment (DeviceNormalizer(env, ...))")
+        return normalizer.struct()
+
+    def norm_fold(self, normalizer, replay, first_slot, num_steps):
+        """Folds what the actor saw and the rewards of `num_steps` steps of `replay` from slot `first_slot` on -- the slots a
+        ``collect`` with the same arguments has just filled -- into the running statistics of `normalizer` (an
+        ``evaluation.DeviceNormalizer`` of this environment), slot by slot, in TWO launches whatever `num_steps` is (urgym_norm_fold).
+        With ``normalizer.training`` False nothing is launched.  The arithmetic is ``evaluation.norm_fold``, bitwise.  At most
+        ``normalizer.fold_steps`` steps (the workspace's size) and the ring's capacity, and only with auto_reset.  On torch's current
+        stream, nothing is synchronised."""
+        who = "norm_fold"
+        if getattr(replay, "env", None) is not self or not hasattr(replay, "_ring"):
+            raise ValueError(f"{who}: replay must be a DeviceReplay allocated for this environment (DeviceReplay(env, capacity_steps))")
+        if not self.cfg.auto_reset:
+            raise ValueError(f"{who}: the environment has auto_reset off (its episodes do not restart)")
+        replay.check_args(replay.capacity, num_steps=num_steps, first_slot=first_slot)
+        if int(num_steps) > replay.capacity:
+            raise ValueError(f"{who}: num_steps must be at most the ring's {replay.capacity} slots (it no longer holds the earlier steps), got {num_steps}")
+        n = self._normalization(who, normalizer)
+        if int(num_steps) > normalizer.fold_steps:
+            raise ValueError(f"{who}: num_steps must be at most the normalizer's fold_steps = {normalizer.fold_steps} (its workspace), got {num_steps}")
+        _native.check(self.lib.urgym_norm_fold(self._h, C.byref(n), C.byref(replay._ring), int(first_slot), int(num_steps), self._stream()), self._h)
+
+    _NORM_ROWS = ("observation", "achieved_goal", "desired_goal")
+
+    def norm_rows(self, normalizer, rows, out=None):
+        """Normalizes rows with the statistics of `normalizer` as they stand when the launch RUNS, in ONE launch (urgym_norm_rows).
+        `rows`: a dict under some or all of ``observation`` [count, obs_dim], ``achieved_goal`` and ``desired_goal`` [count, goal_dim]
+        (float32 device tensors, any leading shape, the same for all); `out`: the destinations under the same names (default: fresh
+        tensors; `rows` itself = in place).  Returns `out`.  The arithmetic is ``evaluation.normalize_rows``, bitwise.  The normalizer
+        may belong to another environment of this env kind: an evaluation environment reads the TRAINING statistics this way (SB3's
+        ``sync_envs_normalization``)."""
+        who = "norm_rows"
+        n = self._normalization(who, normalizer, same_kind=True)
+        names = [k for k in self._NORM_ROWS if k in rows]
+        if not names or len(names) != len(rows):
+            raise ValueError(f"{who}: rows must be a dict under some of {self._NORM_ROWS}")
+        if out is None:
+            out = {k: torch.empty_like(rows[k]) for k in names}
+        if sorted(out) != sorted(names):
+            raise ValueError(f"{who}: out must hold exactly the groups of rows")
+        dims = dict(observation=self.obs_dim, achieved_goal=self.goal_dim, desired_goal=self.goal_dim)
+        lead = tuple(rows[names[0]].shape[:-1])
+        count = int(np.prod(lead)) if lead else 1
+        a = _abi.NormRowsArgs()
+        for k in names:
+            setattr(a, k, self._float_ptr(who, f"rows[{k!r}]", rows[k], lead + (dims[k],)))
+            setattr(a, k + "_out", self._float_ptr(who, f"out[{k!r}]", out[k], lead + (dims[k],)))
+        _native.check(self.lib.urgym_norm_rows(self._h, C.byref(n), C.byref(a), count, self._stream()), self._h)
+        return out
+
+    def norm_batch(self, normalizer, batch):
+        """Normalizes a minibatch IN PLACE in ONE launch (urgym_norm_batch): `batch` as ``DeviceReplay.sample`` returns it --
+        ``observations`` and ``next_observations`` with the three observation groups (``norm_obs``), ``rewards`` with the return
+        group (``norm_reward``); actions and flags are not touched.  The arithmetic is ``evaluation.normalize_rows`` /
+        ``normalize_reward``, bitwise.  Returns `batch`."""
+        who = "norm_batch"
+        n = self._normalization(who, normalizer)
+        count = int(batch["rewards"].shape[0])
+        dims = dict(observation=self.obs_dim, achieved_goal=self.goal_dim, desired_goal=self.goal_dim)
+        b = _abi.ReplayBatch()
+        for prefix, key in (("", "observations"), ("next_", "next_observations")):
+            for k in self._NORM_ROWS:
+                setattr(b, prefix + k, self._float_ptr(who, f"batch[{key!r}][{k!r}]", batch[key][k], (count, dims[k])))
+        b.reward = self._float_ptr(who, "batch['rewards']", batch["rewards"], (count,))
+        _native.check(self.lib.urgym_norm_batch(self._h, C.byref(n), C.byref(b), count, self._stream()), self._h)
+        return batch
+
+    def collect(self, actor, num_steps, replay, sample=None, first_slot=None, normalizer=None):
         """``rollout_policy`` that files every transition in `replay` (an ``evaluation.DeviceReplay`` of this environment) as it
         happens (urgym_rollout_collect): step k goes to slot (first_slot + k) % capacity, complete with the terminal observation
         and goals of envs that were auto-reset.  `sample` as in ``rollout_policy`` (None = the deterministic policy); `first_slot`
-        defaults to the ring's cursor, which this method does NOT move -- ``replay.collect`` does.  Nothing is synchronised."""
+        defaults to the ring's cursor, which this method does NOT move -- ``replay.collect`` does.  Nothing is synchronised.
+
+        With `normalizer` (an ``evaluation.DeviceNormalizer`` of this environment) the actor reads rows normalized with the
+        statistics as they stand (urgym_rollout_collect_normalized: one more launch per step); the ring still holds the RAW rows, and
+        the statistics are NOT folded here -- ``normalizer.fold`` afterwards does that."""
         a = self._actor_ptr(actor)
+        if normalizer is not None:
+            if getattr(replay, "env", None) is not self or not hasattr(replay, "_ring"):
+                raise ValueError("replay must be a DeviceReplay allocated for this environment (DeviceReplay(env, capacity_steps))")
+            n = self._normalization("collect", normalizer)
+            first = replay.cursor if first_slot is None else first_slot
+            replay.check_args(replay.capacity, num_steps=num_steps, first_slot=first)
+            how = self._sampling(sample if sample is not None else dict(mode="mean"))
+            _native.check(self.lib.urgym_rollout_collect_normalized(self._h, a, C.byref(how), int(num_steps), C.byref(replay._ring), int(first), C.byref(n),
+                                                                    self._stream()), self._h)
+            return
         if getattr(replay, "env", None) is not self or not hasattr(replay, "_ring"):
             raise ValueError("replay must be a DeviceReplay allocated for this environment (DeviceReplay(env, capacity_steps))")
         first = replay.cursor if first_slot is None else first_slot
