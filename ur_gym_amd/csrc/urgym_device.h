@@ -451,16 +451,15 @@ __device__ __forceinline__ int gjk_advance(GjkRun& r, const HullMap& g, const Sh
   // overlapping cores / iteration cap, bit 2 = on a separating axis); the bookkeeping of an ended search -- a square root among it --
   // runs once, in gjk_finish, for all lanes that end in this trip (gjk_iterate) or whenever the caller files the result (gjk_advance),
   // instead of once per exit that some lane happens to take.
-  int fin = 0;
+  // The three exits in front of the simplex step -- a separating axis, a vertex the simplex holds already, too little progress along
+  // v -- are straight-line predicates on values the lane has anyway, folded into fin in their order of priority: the simplex step below
+  // is the ONE divergent region they open.  (bitwise on purpose: independent comparisons, no short-circuit branches)
   const double delta = dot(r.v, w);
-  if (delta > 0.0 && delta * delta > r.sq * (max_d * max_d)) fin = 1 | 4;
-  if (fin == 0) {
-    // (bitwise on purpose: three independent comparisons, no short-circuit branches)
-    const bool in = (((int)(r.n > 0) & (int)(len2(W0 - w) <= 1e-12)) | ((int)(r.n > 1) & (int)(len2(W1 - w) <= 1e-12)) |
-                     ((int)(r.n > 2) & (int)(len2(W2 - w) <= 1e-12))) != 0;
-    const double f0 = r.sq - delta, f1 = r.sq * REL_ERROR2;
-    if (in || f0 <= f1) fin = 1;
-  }
+  const int sep = (int)(delta > 0.0) & (int)(delta * delta > r.sq * (max_d * max_d));
+  const int in = ((int)(r.n > 0) & (int)(len2(W0 - w) <= 1e-12)) | ((int)(r.n > 1) & (int)(len2(W1 - w) <= 1e-12)) |
+                 ((int)(r.n > 2) & (int)(len2(W2 - w) <= 1e-12));
+  const double f0 = r.sq - delta, f1 = r.sq * REL_ERROR2;
+  int fin = sep ? (1 | 4) : (in | (int)(f0 <= f1));
   if (fin == 0) {
     stw(T, r.n, w);
     int n = r.n + 1;
@@ -503,16 +502,18 @@ __device__ __forceinline__ int gjk_advance(GjkRun& r, const HullMap& g, const Sh
         io = (f == 0) ? 3 : ((f == 1) ? 1 : ((f == 2) ? 2 : 0));
       };
       int todo = 1;  // triangle: just face 0 = (w0, w1, w2)
-      bool degen = false;
+      int degen = 0;
       if (tetra) {
         // the four plane tests as straight-line code on the vertices read above: four independent chains the scheduler can
-        // interleave, instead of four dependent rounds that each start with an LDS round trip (same expressions, same bits)
+        // interleave, instead of four dependent rounds that each start with an LDS round trip (same expressions, same bits).
+        // Branch-free: a degenerate face sets degen and never its bit, as the two-armed test did.
         todo = 0;
         auto plane = [&](D3 a, D3 b, D3 c, D3 o, int bit) {
           const D3 nrm = cross(b - a, c - a);
           const double signp = -dot(a, nrm), signd = dot(o - a, nrm);
-          if (signd * signd < (1.0e-8 * 1.0e-8)) degen = true;
-          else if (signp * signd < 0.0) todo |= bit;
+          const int dg = (int)(signd * signd < (1.0e-8 * 1.0e-8));
+          degen |= dg;
+          todo |= ((dg ^ 1) & (int)(signp * signd < 0.0)) ? bit : 0;
         };
         plane(W0, W1, W2, w, 1);   // ABC | D
         plane(W0, W2, w, W1, 2);   // ACD | B
@@ -553,22 +554,30 @@ __device__ __forceinline__ int gjk_advance(GjkRun& r, const HullMap& g, const Sh
       if (n >= 1 && !(used & 1)) { n--; stw(T, 0, ldw(T, n)); }
     }
     r.n = n;
-    if (!valid) fin = 1;  // sliver tetrahedron
-    else {
-      const double nsq = len2(nv);
-      if (nsq < REL_ERROR2) { r.v = nv; fin = 1; }
-      else if (nsq <= verdict_d * verdict_d) { r.v = nv; r.info |= GJK_CLOSE; fin = 1; }
-      else {
-        const double prev = r.sq;
-        r.sq = nsq;
-        if (prev - nsq <= EPS * prev) fin = 1;  // no progress: the previous v stands
-        else {
-          r.v = nv;
-          if (r.iter++ > 1000) { r.info |= GJK_ITERCAP; fin = 3; }
-          else if (n == 4) fin = 3;  // the origin is inside the tetrahedron
-        }
-      }
-    }
+    // ---- the termination tests, ONE flat tail: every predicate is computed once, the decisions follow from them by integer logic in
+    //      Bullet's order of priority, and r.v, r.sq, r.iter take their new values through selects -- no arm assigns them, so no copy of
+    //      r.v has to travel round the loop for the arms that leave it alone.  In order:
+    //        sliver tetrahedron                      ends (1), nothing changes
+    //        touching cores, nsq < REL_ERROR2        ends (1), v = nv
+    //        the verdict, nsq <= verdict_d^2         ends (1), v = nv, GJK_CLOSE
+    //        no progress                             ends (1), sq = nsq; the previous v stands
+    //        otherwise v = nv, sq = nsq, iter + 1;   the cap: ends (3), GJK_ITERCAP;  n == 4: ends (3), the origin is inside
+    const double nsq = len2(nv);
+    const double prev = r.sq;
+    const int sliver = (int)!valid;
+    const int touch = (int)(nsq < REL_ERROR2);
+    const int close = (int)(nsq <= verdict_d * verdict_d);
+    const int stuck = (int)(prev - nsq <= EPS * prev);
+    const int cap = (int)(r.iter > 1000);
+    const int early = sliver | touch | close;      // the arms that leave r.sq and r.iter alone
+    const int on = (early | stuck) ^ 1;            // the search moved: it goes on unless the cap or a full simplex ends it
+    const bool takes_nv = (((sliver ^ 1) & (touch | close | (stuck ^ 1))) != 0);
+    r.info |= (((sliver | touch) ^ 1) & close) ? GJK_CLOSE : 0;
+    r.info |= (on & cap) ? GJK_ITERCAP : 0;
+    r.v.x = takes_nv ? nv.x : r.v.x; r.v.y = takes_nv ? nv.y : r.v.y; r.v.z = takes_nv ? nv.z : r.v.z;
+    r.sq = early ? prev : nsq;
+    r.iter += on;
+    fin = on ? ((cap | (int)(n == 4)) ? 3 : 0) : 1;
   }  // (fin == 0: the simplex step)
   return fin;
 }
