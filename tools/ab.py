@@ -7,6 +7,9 @@ library (URGYM_LIB) and environment switches; variants are interleaved over the 
         --variant res2:ur_gym_amd/csrc/build/liburgym_res2.so:URGYM_STEP_ENVS=128 \
         -- --num-envs 65536                                (arguments after -- go to bench.py)
 
+--stop-on-error ends the whole run after the first child that fails (exit status 4), as a timeout always does (3): on a GPU machine
+nothing is started after a run that faulted, aborted or hung.
+
 This process never touches the GPU itself.  One JSON line per run: variant, value (M env-steps/s), ms_per_step, kernel_us."""
 import argparse, json, os, subprocess, sys
 
@@ -16,6 +19,9 @@ ap.add_argument("--out", required=True)
 ap.add_argument("--reps", type=int, default=2)
 ap.add_argument("--variant", action="append", default=[])
 ap.add_argument("--timeout", type=int, default=300)
+ap.add_argument("--stop-on-error", action="store_true",
+                help="end with status 4 after the first child that fails (a non-zero exit status or no result line): on a GPU machine nothing is "
+                     "started after a run that faulted or aborted")
 ap.add_argument("bench_args", nargs="*")
 args = ap.parse_args()
 os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
@@ -33,7 +39,7 @@ with open(args.out, "a") as f:
             try:
                 p = subprocess.run(cmd, env=dict(os.environ, **env), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=args.timeout)
                 lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
-                if not lines:
+                if not lines or (args.stop_on_error and p.returncode != 0):
                     rec = {"variant": name, "error": (p.stderr or "")[-400:], "rc": p.returncode}
                 else:
                     d = json.loads(lines[-1])
@@ -48,3 +54,5 @@ with open(args.out, "a") as f:
             print(json.dumps(rec), flush=True)
             f.write(json.dumps(rec) + "\n")
             f.flush()
+            if args.stop_on_error and "error" in rec:
+                sys.exit(4)

@@ -63,6 +63,53 @@ __device__ __forceinline__ X3 rel(const X3& A, const X3& B) {
   return C;
 }
 
+// ---- the lower bounds of the per-env culling pass (urgym_hip.hip P1): bounding capsules against the boxes and each other.
+// squared closest distance between two segments (Ericson RTCD §5.1.9)
+__device__ __forceinline__ double segseg_dist2(D3 p1, D3 q1, D3 p2, D3 q2) {
+  D3 d1 = q1 - p1, d2 = q2 - p2, r = p1 - p2;
+  double a = dot(d1, d1), e = dot(d2, d2), f = dot(d2, r);
+  double s, t;
+  const double EPS = 1e-18;
+  if (a <= EPS && e <= EPS) return len2(r);
+  if (a <= EPS) {
+    s = 0.0;
+    t = fmin(1.0, fmax(0.0, f / e));
+  } else {
+    double c = dot(d1, r);
+    if (e <= EPS) {
+      t = 0.0;
+      s = fmin(1.0, fmax(0.0, -c / a));
+    } else {
+      double b = dot(d1, d2), den = a * e - b * b;
+      s = den > 1e-30 ? fmin(1.0, fmax(0.0, (b * f - c * e) / den)) : 0.0;
+      t = (b * s + f) / e;
+      if (t < 0.0) { t = 0.0; s = fmin(1.0, fmax(0.0, -c / a)); }
+      else if (t > 1.0) { t = 1.0; s = fmin(1.0, fmax(0.0, (b - c) / a)); }
+    }
+  }
+  D3 c1 = p1 + d1 * s, c2 = p2 + d2 * t;
+  return len2(c1 - c2);
+}
+__device__ __forceinline__ double segseg_dist(D3 p1, D3 q1, D3 p2, D3 q2) { return sqrt(segseg_dist2(p1, q1, p2, q2)); }
+// (squared) lower bound of the distance between segment (p,q) and an axis-aligned box (centre c, half h)
+__device__ __forceinline__ double seg_box_lower_bound2(D3 p, D3 q, double cx, double cy, double cz, double hx, double hy, double hz) {
+  double gx = fmax(fmax((cx - hx) - fmax(p.x, q.x), fmin(p.x, q.x) - (cx + hx)), 0.0);
+  double gy = fmax(fmax((cy - hy) - fmax(p.y, q.y), fmin(p.y, q.y) - (cy + hy)), 0.0);
+  double gz = fmax(fmax((cz - hz) - fmax(p.z, q.z), fmin(p.z, q.z) - (cz + hz)), 0.0);
+  return gx * gx + gy * gy + gz * gz;
+}
+__device__ __forceinline__ double seg_box_lower_bound(D3 p, D3 q, double cx, double cy, double cz, double hx, double hy, double hz) {
+  return sqrt(seg_box_lower_bound2(p, q, cx, cy, cz, hx, hy, hz));
+}
+// The culling test without its square root: `sqrt(d2) - radii <= lim` keeps a pair, and so does `d2 <= cull_bound2(lim + radii)`
+// for every pair the first form keeps.  The two differ by rounding only: one correctly rounded root and one or two subtractions on
+// the left, one or two additions, a square and a product here -- a few 2^-53 relative to the bound, which therefore carries a
+// relative slack of CULL_SLACK, thousands of times that.  A pair kept in addition (a capsule distance within 1e-12 of the bound, relative) is decided
+// by its exact GJK query like every other survivor, so no output depends on it.  (A negative reach -- a contact margin below minus a
+// capsule radius -- keeps nothing in the root form and is squared here: pairs kept in addition, still a superset, and no guard to pay.)
+constexpr double CULL_SLACK = 1e-12;
+__device__ __forceinline__ double cull_bound2(double reach) { return (reach * reach) * (1.0 + CULL_SLACK); }
+
 // A rigid transform parked in LDS (per-lane slot, element k at p[k * stride]: r[0..8] then t.xyz).  The GJK keeps its
 // pose operand there instead of in 24 VGPRs; it is re-read twice per iteration (18 + 12 ds_read_b64, conflict-free
 // because consecutive lanes own consecutive addresses).

@@ -58,6 +58,12 @@ constexpr uint32_t NO_ITEM = 0xFFFFFFFFu;
 #define URGYM_REFILL_MIN 16
 #endif
 constexpr int REFILL_MIN = URGYM_REFILL_MIN;
+// The head of the P1 waves, by item, compile-time only like REFILL_MIN: -DURGYM_HEAD_ITEMS=<bits> builds
+// one alone to measure.  1: with two P1 waves the first to finish waits for its sister's publication; 2: the culling pass compares
+// squared distances; 4: the culling pass evaluates the six sin / cos itself and keeps them in registers.  All three ship.
+#ifndef URGYM_HEAD_ITEMS
+#define URGYM_HEAD_ITEMS 7
+#endif
 static_assert(REFILL_MIN >= 1 && REFILL_MIN <= 64, "a wave has 64 lanes");
 // Resident STEP / PREFETCH workgroups per CU the kernels are compiled for (launch bounds -> VGPR budget 168) and the cap of the
 // step grid's residency (plan_handle)
@@ -204,39 +210,7 @@ __device__ __forceinline__ X3 identity_x3() {
   return T;
 }
 
-// closest distance between two segments (Ericson RTCD §5.1.9)
-__device__ __forceinline__ double segseg_dist(D3 p1, D3 q1, D3 p2, D3 q2) {
-  D3 d1 = q1 - p1, d2 = q2 - p2, r = p1 - p2;
-  double a = dot(d1, d1), e = dot(d2, d2), f = dot(d2, r);
-  double s, t;
-  const double EPS = 1e-18;
-  if (a <= EPS && e <= EPS) return sqrt(len2(r));
-  if (a <= EPS) {
-    s = 0.0;
-    t = fmin(1.0, fmax(0.0, f / e));
-  } else {
-    double c = dot(d1, r);
-    if (e <= EPS) {
-      t = 0.0;
-      s = fmin(1.0, fmax(0.0, -c / a));
-    } else {
-      double b = dot(d1, d2), den = a * e - b * b;
-      s = den > 1e-30 ? fmin(1.0, fmax(0.0, (b * f - c * e) / den)) : 0.0;
-      t = (b * s + f) / e;
-      if (t < 0.0) { t = 0.0; s = fmin(1.0, fmax(0.0, -c / a)); }
-      else if (t > 1.0) { t = 1.0; s = fmin(1.0, fmax(0.0, (b - c) / a)); }
-    }
-  }
-  D3 c1 = p1 + d1 * s, c2 = p2 + d2 * t;
-  return sqrt(len2(c1 - c2));
-}
-// lower bound of the distance between segment (p,q) and an axis-aligned box (centre c, half h)
-__device__ __forceinline__ double seg_box_lower_bound(D3 p, D3 q, double cx, double cy, double cz, double hx, double hy, double hz) {
-  double gx = fmax(fmax((cx - hx) - fmax(p.x, q.x), fmin(p.x, q.x) - (cx + hx)), 0.0);
-  double gy = fmax(fmax((cy - hy) - fmax(p.y, q.y), fmin(p.y, q.y) - (cy + hy)), 0.0);
-  double gz = fmax(fmax((cz - hz) - fmax(p.z, q.z), fmin(p.z, q.z) - (cz + hz)), 0.0);
-  return sqrt(gx * gx + gy * gy + gz * gz);
-}
+// (segseg_dist / seg_box_lower_bound and their squared forms, which P1 culls with: urgym_device.h)
 
 // ReachDyn.set_velocity (reach.py:728-753): v = (end-start)/T; omega = axis*angle/T of dq = nearest(q_end)*q_start^-1
 __device__ void dyn_velocity(const double start[6], const double end[6], double T, double vel[6]) {
@@ -589,6 +563,9 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
   const int first = tail_block ? P.big_blocks * P.envs + (vb - P.big_blocks) * P.envs_tail : vb * P.envs;
   const int G = (E + GROUP - 1) / GROUP;     // waves that run the per-env phases
   constexpr bool HAS_OBST = (KIND != URGYM_ENV_ORI);
+  // the head of the P1 waves of the step kernels without the penetration-depth phase
+  constexpr bool HEAD = (MODE == MODE_STEP) && !WITH_EPA;
+  constexpr bool HEAD_WAIT = HEAD && (URGYM_HEAD_ITEMS & 1), HEAD_SQ = HEAD && (URGYM_HEAD_ITEMS & 2), HEAD_REG = HEAD && (URGYM_HEAD_ITEMS & 4);
   constexpr int COLL_BIT = 1 << 30;
   constexpr int EE_BIT = 1 << 29;  // STEP: the per-env phase has already stored the end-effector pose of this step (P4 reads it back)
   // bits 8..22 of s_flags: exact queries that ended with overlapping cores and whose distance IS consumed -> penetration depth
@@ -699,13 +676,20 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
     // (the set-up cache serves the draws of closest-distance queries: a launch that runs none -- UR5OriReach-v1 with the collision checks
     //  off -- does not fill it; its six sin / cos evaluations were a third of that launch's span)
     const bool use_cache = (MODE == MODE_STEP) && (HAS_OBST || cfg.check_collision);
+    // Round 8: where the culling pass below runs in a step kernel without the penetration-depth phase, IT evaluates the six sin / cos, from
+    // the joints this lane holds in registers, stores them and goes on with them in registers.  The rolled loop here handed them to that
+    // pass through memory: six more joint updates, and twelve loads that waited behind the stores of the cache (one counter).
+    bool sincos_in_pass = false;
+    if constexpr (HEAD_REG) sincos_in_pass = live && cfg.check_collision;
     if (use_cache && live) {  // the set-up cache of this env (KParams::sc_scratch)
+      if (!sincos_in_pass) {
 #pragma unroll 1
-      for (int k = 0; k < 6; k++) {
-        double sn, cs;
-        sincos(joint_of_step<MODE>(P, actions, n, k), &sn, &cs);
-        SOA(P.sc_scratch, 2 * k, n, N) = sn;
-        SOA(P.sc_scratch, 2 * k + 1, n, N) = cs;
+        for (int k = 0; k < 6; k++) {
+          double sn, cs;
+          sincos(joint_of_step<MODE>(P, actions, n, k), &sn, &cs);
+          SOA(P.sc_scratch, 2 * k, n, N) = sn;
+          SOA(P.sc_scratch, 2 * k + 1, n, N) = cs;
+        }
       }
       if (HAS_OBST) {
         obstacle_of_step<KIND>(P, n, opos, oq);
@@ -729,20 +713,27 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
       // their margin, i.e. inside the full boxes used here), so a pair can be closer than its capsules by one hull margin (two for
       // a self pair).  Round 2 found the bound without that term: a table contact at 0.00988 m was culled (margin 0.01).
       const double lim = cfg.collision_margin + M_HULL + 1e-6;
+      // The step kernels without the penetration-depth phase compare SQUARED distances with squared bounds (cull_bound2, urgym_device.h):
+      // they keep every pair the root form keeps, and the nineteen float64 square roots leave the head of the P1 waves, which hold most of
+      // the workgroup's longest queries as their own first tickets.  The other launches keep the root form.
       X3 T = identity_x3();
       D3 a0[3], a1[3];
       double sn45[2] = {0, 0}, cs45[2] = {0, 0};  // frames_on: sin / cos of the last two joints, read before the first frame is stored
 #pragma unroll
       for (int k = 0; k < 6; k++) {
         double sn, cs;
-        if (frames_on && k >= LF_FIRST) { sn = sn45[k - LF_FIRST]; cs = cs45[k - LF_FIRST]; }
+        if constexpr (HEAD_REG) {  // (use_cache holds: the pass runs under check_collision.  joint_of_step is a pure function: q[k] is what the rolled loop passed)
+          sincos(q[k], &sn, &cs);
+          SOA(P.sc_scratch, 2 * k, n, N) = sn;
+          SOA(P.sc_scratch, 2 * k + 1, n, N) = cs;
+        } else if (frames_on && k >= LF_FIRST) { sn = sn45[k - LF_FIRST]; cs = cs45[k - LF_FIRST]; }
         else if (use_cache) { sn = SOA(P.sc_scratch, 2 * k, n, N); cs = SOA(P.sc_scratch, 2 * k + 1, n, N); }  // (this lane stored them above)
         else sincos(q[k], &sn, &cs);
         fk_joint(T, k, sn, cs);
         const int link = k + 1;
         // The frames a draw can ask for (KParams::lf_scratch): stores only, published with the set-up cache by s_p1done below.  The
         // loads this loop still needs are issued first: a load behind the stores is waited for together with them (one counter).
-        if (frames_on && link == LF_FIRST)
+        if (!HEAD_REG && frames_on && link == LF_FIRST)
           for (int j = 0; j < 2; j++) { sn45[j] = SOA(P.sc_scratch, 2 * (LF_FIRST + j), n, N); cs45[j] = SOA(P.sc_scratch, 2 * (LF_FIRST + j) + 1, n, N); }
         if (frames_on && link >= LF_FIRST) {
           const int row = 12 * (link - LF_FIRST);
@@ -754,14 +745,24 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
         const double rb = c[6];
         if (k < 3) { a0[k] = b0; a1[k] = b1; }
         if (link >= 2) {
-          if (seg_box_lower_bound(b0, b1, TABLE_CX, TABLE_CY, TABLE_CZ, TABLE_HX, TABLE_HY, TABLE_HZ) - rb <= lim) pairs |= 1u << (PAIR_TABLE + link - 2);
-          if (seg_box_lower_bound(b0, b1, TRACK_CX, TRACK_CY, TRACK_CZ, TRACK_HX, TRACK_HY, TRACK_HZ) - rb <= lim) pairs |= 1u << (PAIR_TRACK + link - 2);
+          if constexpr (HEAD_SQ) {
+            const double box2 = cull_bound2(lim + rb);
+            if (seg_box_lower_bound2(b0, b1, TABLE_CX, TABLE_CY, TABLE_CZ, TABLE_HX, TABLE_HY, TABLE_HZ) <= box2) pairs |= 1u << (PAIR_TABLE + link - 2);
+            if (seg_box_lower_bound2(b0, b1, TRACK_CX, TRACK_CY, TRACK_CZ, TRACK_HX, TRACK_HY, TRACK_HZ) <= box2) pairs |= 1u << (PAIR_TRACK + link - 2);
+          } else {
+            if (seg_box_lower_bound(b0, b1, TABLE_CX, TABLE_CY, TABLE_CZ, TABLE_HX, TABLE_HY, TABLE_HZ) - rb <= lim) pairs |= 1u << (PAIR_TABLE + link - 2);
+            if (seg_box_lower_bound(b0, b1, TRACK_CX, TRACK_CY, TRACK_CZ, TRACK_HX, TRACK_HY, TRACK_HZ) - rb <= lim) pairs |= 1u << (PAIR_TRACK + link - 2);
+          }
         }
         // self pairs (pyb_setup.py:417-427): (1,3)(1,4)(1,5)(1,6)(2,4)(2,5)(2,6)(3,5)(3,6)
 #pragma unroll
         for (int A = 1; A <= 3; A++) {
           if (A <= link - 2) {
-            if (segseg_dist(a0[A - 1], a1[A - 1], b0, b1) - c_tab.capsule[A - 1][6] - rb <= lim + M_HULL) pairs |= 1u << self_pair_bit(A, link);
+            if constexpr (HEAD_SQ) {
+              if (segseg_dist2(a0[A - 1], a1[A - 1], b0, b1) <= cull_bound2(lim + M_HULL + c_tab.capsule[A - 1][6] + rb)) pairs |= 1u << self_pair_bit(A, link);
+            } else {
+              if (segseg_dist(a0[A - 1], a1[A - 1], b0, b1) - c_tab.capsule[A - 1][6] - rb <= lim + M_HULL) pairs |= 1u << self_pair_bit(A, link);
+            }
           }
         }
       }
@@ -859,7 +860,10 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
       // first tickets (std::false_type) may run ahead of P1 and keep the chain.  (e, lb are in range: the decoder's check above.)
       // The loads stand directly in front of their use in each branch below, not here: a load still in flight on some path through
       // the branches that follow would put waits for it into the loops behind the draw step.
-      const bool framed = decltype(after_p1)::value && frames_on && lb >= LF_FIRST && kind != Q_SELF;
+      // (Round 8: so does an own first ticket whose lane has seen the publication -- a P1 wave, after its own or behind its wait.)
+      bool published = decltype(after_p1)::value;
+      if constexpr (HEAD_WAIT) published = published || p1_ok;
+      const bool framed = published && frames_on && lb >= LF_FIRST && kind != Q_SELF;
       auto load_frame = [&]() {
         const int row = 12 * (lb - LF_FIRST);
         for (int i = 0; i < 9; i++) T.r[i] = SOA(P.lf_scratch, row + i, n, N);
@@ -944,6 +948,22 @@ __device__ __forceinline__ void env_body(const KParams& P, const float* __restri
     run.info = 0;  // (no ended search waits to be filed)
     bool busy = false;
     if (MODE == MODE_STEP) p1_ok = __hip_atomic_load(&s_p1done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) >= G;
+    // Two P1 waves (E > 64): the one that counts itself in first would find s_p1done short of G and re-derive, for its own first
+    // tickets, what its sister publishes microseconds later -- the finite check, the obstacle's motion, three or four float64 sincos --
+    // and these two waves own most of the workgroup's link 3 tickets, its longest searches.  It waits for the sister instead: she runs
+    // the same straight-line phase from the same barrier, publishes unconditionally and waits for nothing, so there is no cycle; the
+    // wait sleeps between polls and gives up after P1_WAIT_POLLS of them (about a set-up's worth of time), and then the set-up below
+    // re-derives as before.  One P1 wave (G == 1) has seen its own publication above.
+    if constexpr (HEAD_WAIT) {
+      constexpr int P1_WAIT_POLLS = 32;
+      if (G > 1 && wv >= WAVES - G) {
+#pragma unroll 1
+        for (int poll = 0; poll < P1_WAIT_POLLS && !p1_ok; poll++) {
+          __builtin_amdgcn_s_sleep(2);
+          p1_ok = __builtin_amdgcn_readfirstlane(__hip_atomic_load(&s_p1done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) >= G;
+        }
+      }
+    }
     if (tid < n_tickets) {
       busy = setup(ticket_item(tid), std::false_type{});
       if (busy) gjk_begin(run, v0);
