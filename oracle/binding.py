@@ -54,6 +54,7 @@ def lib():
         L.urgym_oracle_integrate_obstacle.argtypes = [dp, dp, C.c_double]
         L.urgym_oracle_set_primitive_margin.argtypes = [C.c_double]
         L.urgym_oracle_last_epa_iterations.restype = C.c_int
+        L.urgym_oracle_last_gjk_exit.restype = C.c_int
         L.urgym_oracle_last_epa_census.argtypes = [C.POINTER(C.c_int)]
         L.urgym_oracle_last_epa_census.restype = None
         L.urgym_oracle_philox.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, dp]
@@ -240,6 +241,13 @@ def set_collision_groups(bits):
 
 def last_epa_iterations():
     return lib().urgym_oracle_last_epa_iterations()
+
+
+def last_gjk_exit():
+    """How the calling thread's last GJK search (the one of closest(); the last of several after query()) left its loop: Bullet's degenerate
+    code -- 1 duplicate vertex, 2 / 11 the relative test, 3 sliver tetrahedron, 5 / 6 touching cores, 10 separating-axis early-out,
+    12 no progress, 13 origin inside a full simplex, 0 iteration cap."""
+    return lib().urgym_oracle_last_gjk_exit()
 
 
 def last_epa_census():

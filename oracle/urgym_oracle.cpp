@@ -612,6 +612,11 @@ EpaResult epa_core_depth(const Shape& A, const Shape& B) {
   }
 }
 
+// How the calling thread's last gjk_distance left its loop (Bullet's m_degenerateSimplex; probe for tests): 1 duplicate vertex,
+// 2 / 11 the relative test (f0 <= 0 / f0 <= f1), 3 sliver tetrahedron (the previous v stands), 5 / 6 touching cores, 10 early-out
+// on a separating axis, 12 no progress, 13 full simplex (origin inside), 0 iteration cap.
+thread_local int g_last_gjk_exit = 0;
+
 struct GjkResult {
   bool has_point;     // a closest point within max_dist was produced (pybullet getClosestPoints returns a non-empty list)
   double distance;    // signed distance between the margin-inflated shapes
@@ -695,9 +700,11 @@ GjkResult gjk_distance(const Shape& A, const Shape& B, double threshold, const V
   res.iterations = iter;
   bool valid = false;
   double distance = 0;
+  g_last_gjk_exit = degenerate;
   if (check_simplex) {
     double l2 = len2(v);
     if (l2 < REL_ERROR2) degenerate = 5;
+    g_last_gjk_exit = degenerate;
     if (l2 > EPS * EPS) {
       distance = std::sqrt(l2) - margin;
       valid = true;
@@ -1443,6 +1450,7 @@ int urgym_oracle_query(const double* q, const double* obst_pose, int has_obstacl
 void urgym_oracle_set_emulation(int flags) { g_emulate = flags; }
 void urgym_oracle_set_collision_groups(int bits) { g_collision_groups = bits; }
 int urgym_oracle_last_epa_iterations(void) { return g_last_epa_iterations; }
+int urgym_oracle_last_gjk_exit(void) { return g_last_gjk_exit; }
 // out4 = {largest rim-candidate count, degenerate faces made, highest face slot written, 1 if the search ended because no face
 // slot was free} of the calling thread's last EPA
 void urgym_oracle_last_epa_census(int* out4) {
