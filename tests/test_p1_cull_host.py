@@ -28,7 +28,7 @@ MARGINS = (0.01, 0.0, 0.05)  # check_collision's contact margin (pyb_setup.py:40
 def harness():
     os.makedirs(os.path.dirname(SO), exist_ok=True)
     src = os.path.join(HERE, "p1_cull_harness.cpp")
-    deps = [src, os.path.join(ROOT, "ur_gym_amd", "csrc", "urgym_device.h"), os.path.join(ROOT, "data", "ur5e_model.h")]
+    deps = [src, os.path.join(HERE, "p1_chain.h"), os.path.join(ROOT, "ur_gym_amd", "csrc", "urgym_device.h"), os.path.join(ROOT, "data", "ur5e_model.h")]
     if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", SO, src])
     lib = C.CDLL(SO)
