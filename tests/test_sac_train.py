@@ -403,6 +403,63 @@ def test_refusals_launch_nothing_and_write_nothing():
     other.close(), hb.close()
 
 
+def test_refusals_of_the_evaluation_and_monitoring_halves_carry_the_callers_name():
+    """Each of the five entry points that take their evaluation and monitoring as options, with its own required option valid: an
+    evaluation without a handle, and a monitoring with reserved0 set, are refused under that entry point's name, with nothing launched."""
+    from ur_gym_amd.evaluation import DeviceMonitor, DeviceNormalizer, DevicePrioritizedReplay, _her_arguments, relabel_threshold
+
+    hb = HandBuilt(updates=4)
+    s, env, lib, dev = hb.side, hb.side.env, hb.side.env.lib, hb.side.env.device
+    L, M = hb.binding.struct, 64
+    fp = lambda t: C.cast(t.data_ptr(), C.POINTER(C.c_float))  # noqa: E731
+    for name, t in zip(_abi.SAC_LEARNER_LOSSES, hb.losses):
+        setattr(L, name, fp(t))
+    S = _abi.SacSchedule(first_slot=0, filled_steps=CAP, capacity_steps=CAP, num_iterations=2, steps_per_iteration=1, updates_per_iteration=2,
+                         uniform_iterations=1, idle_iterations=0, collect_first_draw=0, update_first_draw=0, first_step=1)
+    nan = lambda *shape: torch.full(shape, float("nan"), device=dev)  # noqa: E731
+    # the options' own scratch and outputs, and the learner's: NaN before every call, NaN after it
+    scratch = dict(discount=nan(M), q_min_next=nan(M), scale=nan(2), critic_grad_norm=nan(4), actor_grad_norm=nan(4))
+    scratch.update({f"per.{name}": nan(*shape(M)) for name, shape in _abi.SAC_PRIORITIZED_SCRATCH})
+    scratch.update({name: hb.g[name][1] for name, _ in _abi.SAC_LEARNER_SCRATCH})
+    scratch.update(zip(_abi.SAC_LEARNER_LOSSES, hb.losses))
+    total = torch.zeros(1, dtype=torch.float64, device=dev)
+    pri = DevicePrioritizedReplay(env, CAP)  # for its priorities alone: the ring is the learner's
+    normalizer, monitor = DeviceNormalizer(env), DeviceMonitor(env)
+    nstep = _abi.SacNstep(3, 0, fp(scratch["discount"]), fp(scratch["q_min_next"]))
+    prioritized = _abi.SacPrioritized(priorities=pri.priorities_struct(), beta0=0.4, beta_steps=7, alpha=pri.alpha, eps=pri.eps,
+                                      total=C.cast(total.data_ptr(), C.POINTER(C.c_double)),
+                                      **{name: fp(scratch[f"per.{name}"]) for name, _ in _abi.SAC_PRIORITIZED_SCRATCH})
+    hindsight = _abi.SacHindsight(*_her_arguments(relabel_threshold(4), "future", 3), 0)
+    clipping = _abi.SacClipping(1.0, 0, fp(scratch["scale"]), fp(scratch["critic_grad_norm"]), fp(scratch["actor_grad_norm"]))
+    normalization = env._normalization("test", normalizer)
+    b = C.byref
+    calls = {  # entry point -> the call with its own option given and the evaluation and monitoring passed through
+        "urgym_sac_train_nstep": lambda E, Mo: lib.urgym_sac_train_nstep(env._h, b(L), b(S), b(nstep), E, Mo, env._stream()),
+        "urgym_sac_train_prioritized": lambda E, Mo: lib.urgym_sac_train_prioritized(env._h, b(L), b(S), b(prioritized), E, Mo, env._stream()),
+        "urgym_sac_train_hindsight": lambda E, Mo: lib.urgym_sac_train_hindsight(env._h, b(L), b(S), b(hindsight), E, Mo, env._stream()),
+        "urgym_sac_train_clipped": lambda E, Mo: lib.urgym_sac_train_clipped(env._h, b(L), b(S), b(clipping), None, None, None, E, Mo, env._stream()),
+        "urgym_sac_train_normalized": lambda E, Mo: lib.urgym_sac_train_normalized(env._h, b(L), b(S), b(normalization), None, None, None, None, E, Mo, env._stream()),
+    }
+    no_handle = _abi.SacEvaluation()  # eval_handle is NULL
+    reserved = _abi.SacMonitoring.from_buffer_copy(monitor.struct(1))
+    reserved.reserved0 = 1
+    for who, call in calls.items():
+        for what, E, Mo, expect in (("evaluation", b(no_handle), None, "eval_handle is null"), ("monitoring", None, b(reserved), "urgym_sac_monitoring.reserved0")):
+            for t in scratch.values():
+                t.fill_(float("nan"))
+            torch.cuda.synchronize(dev)
+            before = hb.everything()
+            rc = call(E, Mo)
+            msg = lib.urgym_last_error(env._h).decode()
+            assert rc == _abi.ERR_ARG and msg.startswith(who + ": ") and expect in msg, (who, what, rc, msg)
+            torch.cuda.synchronize(dev)
+            assert torch.equal(hb.everything(), before), (who, what)
+            assert all(torch.isnan(t).all() for t in scratch.values()), (who, what)
+    for name in _abi.SAC_LEARNER_LOSSES:
+        setattr(L, name, None)
+    hb.close()
+
+
 # names of operations that allocate or make a view: nothing among them launches a kernel (test_sac_terms.py's list, restated)
 ALLOCATIONS_AND_VIEWS = {"aten.empty.memory_format", "aten.empty_strided.default", "aten.view.default", "aten.view.dtype", "aten._unsafe_view.default",
                          "aten.select.int", "aten.slice.Tensor", "aten.squeeze.dim", "aten.unsqueeze.default", "aten.expand.default",

@@ -1,7 +1,17 @@
-// urgym_policy_abi.hip — the learner's half of the C-ABI of include/urgym.h: actors (create / forward / sample / rollouts), the replay
-// ring, the weight reloads and their inverse (urgym_actor_unpack, urgym_critic_unpack), the twin critic and its two gradients, the actor's parameter gradients, the Adam steps, SAC's entropy step and loss terms, the training loop that composes them in one call (urgym_sac_train; its index arithmetic is urgym_sac_schedule.h), the evaluation inside that call (urgym_eval_stats, urgym_actor_snapshot, urgym_policy_evaluate, urgym_sac_train_evaluated; urgym_eval.h, urgym_eval_schedule.h), and the training-episode statistics inside it (urgym_monitor_fold, urgym_monitor_stats, urgym_sac_train_monitored; urgym_monitor.h), and the multi-step returns (urgym_replay_sample_nstep, urgym_sac_entropy_step_nstep, urgym_sac_train_nstep; urgym_nstep.h), and prioritized replay (urgym_per_sums_count, urgym_per_rebuild, urgym_per_fill, urgym_replay_sample_prioritized, urgym_per_terms; urgym_per.h), and hindsight experience replay (urgym_replay_sample_hindsight, urgym_sac_train_hindsight; urgym_her.h), and gradient-norm clipping (urgym_actor_grad_norm, urgym_critic_grad_norm, the two scaled Adam steps, urgym_sac_train_clipped; urgym_grad_clip.h), and running normalization (urgym_norm_workspace, urgym_norm_fold, urgym_norm_rows, urgym_norm_batch, urgym_norm_snapshot, urgym_rollout_collect_normalized, urgym_policy_evaluate_normalized, urgym_sac_train_normalized; urgym_norm.h).  Host code only: every check is made here, before the first launch,
-// and every launch goes through urgym_actor.h, urgym_critic.h, urgym_replay.h, urgym_weights.h, urgym_adam.h, urgym_sac_terms.h, urgym_eval.h, urgym_monitor.h, urgym_per.h and urgym_norm.h, or through do_step of urgym_hip.hip
-// (urgym_handle.h).  No kernel lives in this unit, so adding a check here leaves the step kernels' object file alone.
+// urgym_policy_abi.hip -- the learner's half of the C-ABI of include/urgym.h.  Host code only: no kernel lives in this unit, so a check
+// added here leaves every kernel's object file alone.  Every check is made here, before the first launch; every launch goes through the
+// kernel units' headers (urgym_actor.h ... urgym_norm.h) or through do_step of urgym_hip.hip (urgym_handle.h).  In file order:
+//   - actors: create / forward / sample, the rollouts, urgym_rollout_collect; the replay ring and its gathers (urgym_replay.h,
+//     urgym_nstep.h, urgym_her.h)
+//   - the twin critic, its action gradient and parameter gradients; the actor's parameter gradients
+//   - the Adam steps (urgym_adam.h) and gradient-norm clipping (urgym_grad_clip.h)
+//   - SAC's entropy step and loss terms (urgym_sac_terms.h)
+//   - the weight reloads and their inverse, urgym_actor_unpack / urgym_critic_unpack (urgym_weights.h)
+//   - prioritized replay (urgym_per.h)
+//   - running normalization (urgym_norm.h), evaluation (urgym_eval.h, urgym_eval_schedule.h) and training-episode statistics
+//     (urgym_monitor.h): the checking halves, then their entry points
+//   - the training loop in one call: TrainOptions, TrainExtras, sac_train_body, and the eight urgym_sac_train* entry points
+//     (urgym_sac_schedule.h has the index arithmetic)
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -1265,20 +1275,21 @@ int urgym_actor_parameter_gradients(void* handle, void* actor, const urgym_sampl
   return launched(h);
 }
 
-// ---- the training loop in one call (include/urgym.h, urgym_sac_train; DESIGN.md section 17): every check above first, then nothing
-// but launches.  The launch structs are filled once; an update rewrites the few numbers that move (draws, the ring view, Adam's
-// coefficients, the loss slots).
+}  // extern "C"
+
+// ---- normalization, evaluation and training-episode statistics: the checking halves first, in the order in which they build on each
+// other (the training loop below composes all of them), then the features' own entry points
 
 namespace {
 
-// the required pointers of urgym_sac_learner that no composed check would name: the walk of the NULL refusals
+// a required pointer and the name a NULL refusal gives it: urgym_sac_learner's, and those of the structs below
 struct LearnerPointer {
   const char* name;
   const void* p;
 };
 
 // what a fold of num_steps slots from first_slot on refuses about the ring and the handle: urgym_monitor_fold's and urgym_norm_fold's
-static int check_fold_ring(Handle* h, const urgym_replay_ring* ring, int first_slot, int num_steps, const char* who) {
+int check_fold_ring(Handle* h, const urgym_replay_ring* ring, int first_slot, int num_steps, const char* who) {
   if (int rc = check_ring(h, ring, who)) return rc;
   if (first_slot < 0 || first_slot >= ring->capacity_steps) return fail_in(h, URGYM_ERR_ARG, who, "first_slot outside [0, capacity_steps)");
   if (!ring->truncated || !ring->is_success) return fail_in(h, URGYM_ERR_ARG, who, "the ring keeps no truncated or no is_success (an episode's end and its success are read from them)");
@@ -1292,9 +1303,8 @@ static int check_fold_ring(Handle* h, const urgym_replay_ring* ring, int first_s
 // DESIGN.md section 25).  As above each entry point is a checking half, which launches nothing and fills the launch struct of
 // urgym_norm.h, and a launching half, which refuses nothing.
 
-// (static: this stretch lies inside the extern "C" block, where an unnamed namespace alone would still export the names)
 // the state's thirteen pointers, all given and 8-byte aligned, and the options
-static int check_normalization(Handle* h, const urgym_normalization* norm, const char* who) {
+int check_normalization(Handle* h, const urgym_normalization* norm, const char* who) {
   static_assert(sizeof(urgym_norm_state) == 13 * sizeof(void*) && sizeof(urgym_normalization) == sizeof(urgym_norm_state) + 96, "include/urgym.h");
   if (!norm) return fail_in(h, URGYM_ERR_ARG, who, "null normalization");
   const urgym_norm_state& m = norm->state;
@@ -1313,7 +1323,7 @@ static int check_normalization(Handle* h, const urgym_normalization* norm, const
   return URGYM_OK;
 }
 
-static int check_norm_fold(Handle* h, const urgym_normalization* norm, const urgym_replay_ring* ring, int first_slot, int num_steps, const char* who, NormFoldCall* out) {
+int check_norm_fold(Handle* h, const urgym_normalization* norm, const urgym_replay_ring* ring, int first_slot, int num_steps, const char* who, NormFoldCall* out) {
   if (int rc = check_normalization(h, norm, who)) return rc;
   if (int rc = check_fold_ring(h, ring, first_slot, num_steps, who)) return rc;  // urgym_monitor_fold's ring refusals
   if (num_steps >= 65535) return fail_in(h, URGYM_ERR_ARG, who, "num_steps must be below 65535 (one grid row per slot)");
@@ -1333,7 +1343,7 @@ static int check_norm_fold(Handle* h, const urgym_normalization* norm, const urg
 }
 
 // the three observation groups of `count` rows, src -> dst (each pair whole or absent), appended to the call's segments
-static const char* norm_row_segments(const Handle* h, const urgym_normalization& norm, const float* const src[3], float* const dst[3], NormApplyCall* c) {
+const char* norm_row_segments(const Handle* h, const urgym_normalization& norm, const float* const src[3], float* const dst[3], NormApplyCall* c) {
   const urgym_norm_state& m = norm.state;
   const double* const mean[3] = {m.observation_mean, m.achieved_goal_mean, m.desired_goal_mean};
   const double* const var[3] = {m.observation_var, m.achieved_goal_var, m.desired_goal_var};
@@ -1346,7 +1356,7 @@ static const char* norm_row_segments(const Handle* h, const urgym_normalization&
   return nullptr;
 }
 
-static int check_norm_rows(Handle* h, const urgym_normalization* norm, const urgym_norm_rows_args* rows, int count, const char* who, NormApplyCall* out) {
+int check_norm_rows(Handle* h, const urgym_normalization* norm, const urgym_norm_rows_args* rows, int count, const char* who, NormApplyCall* out) {
   if (int rc = check_normalization(h, norm, who)) return rc;
   if (!rows) return fail_in(h, URGYM_ERR_ARG, who, "null rows");
   if (count <= 0) return fail_in(h, URGYM_ERR_ARG, who, "count must be positive");
@@ -1360,7 +1370,7 @@ static int check_norm_rows(Handle* h, const urgym_normalization* norm, const urg
 }
 
 // segments == 0 afterwards: nothing to launch
-static int check_norm_batch(Handle* h, const urgym_normalization* norm, const urgym_replay_batch* batch, int count, const char* who, NormApplyCall* out) {
+int check_norm_batch(Handle* h, const urgym_normalization* norm, const urgym_replay_batch* batch, int count, const char* who, NormApplyCall* out) {
   if (int rc = check_normalization(h, norm, who)) return rc;
   if (!batch) return fail_in(h, URGYM_ERR_ARG, who, "null batch");
   if (count <= 0) return fail_in(h, URGYM_ERR_ARG, who, "count must be positive");
@@ -1377,6 +1387,359 @@ static int check_norm_batch(Handle* h, const urgym_normalization* norm, const ur
   return URGYM_OK;
 }
 
+// the twelve pointers of a state that is read or written without its running_ret
+int check_norm_state12(Handle* h, const urgym_norm_state* st, const char* who, const char* what) {
+  if (!st) return failf(h, URGYM_ERR_ARG, "%s: null %s", who, what);
+  const void* const p[12] = {st->observation_mean,   st->observation_var,  st->observation_count,  st->achieved_goal_mean, st->achieved_goal_var, st->achieved_goal_count,
+                             st->desired_goal_mean,  st->desired_goal_var, st->desired_goal_count, st->ret_mean,           st->ret_var,           st->ret_count};
+  for (const void* q : p)
+    if (!q || (uintptr_t)q % 8 != 0) return failf(h, URGYM_ERR_ARG, "%s: a pointer of %s is null or not 8-byte aligned (mean, var and count of the four groups)", who, what);
+  return URGYM_OK;
+}
+
+int check_norm_snapshot(Handle* h, const urgym_norm_state* source, const urgym_norm_state* destination, const int32_t* when, const char* who, NormSnapshotCall* out) {
+  if (int rc = check_norm_state12(h, source, who, "source state")) return rc;
+  if (int rc = check_norm_state12(h, destination, who, "destination state")) return rc;
+  if (actor_features(h) + 1 > NORM_FEATURE_LANES) return fail_in(h, URGYM_ERR_ARG, who, "the kernels are built for at most 63 features in all");
+  memset(out, 0, sizeof(*out));
+  out->dim[0] = h->obs_dim, out->dim[1] = h->goal_dim, out->dim[2] = h->goal_dim;
+  out->src = *source, out->dst = *destination, out->when = when;
+  return URGYM_OK;
+}
+
+// ---- evaluation inside the training call (include/urgym.h, urgym_eval_stats ... urgym_sac_train_evaluated; DESIGN.md section 18).
+// As above each entry point is a checking half, which launches nothing and fills the launch struct of urgym_eval.h, and a launching
+// half, which refuses nothing.
+
+int check_eval_stats(Handle* h, const urgym_eval_stats_args* args, const char* who, EvalStatsCall* out) {
+  static_assert(sizeof(urgym_eval_record) == 72 && alignof(urgym_eval_record) == 8, "include/urgym.h");
+  if (!args) return fail_in(h, URGYM_ERR_ARG, who, "null args");
+  const urgym_eval_stats_args& a = *args;
+  if (a.reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "urgym_eval_stats_args.reserved0 must be 0");
+  if (a.count < 1 || a.count > SAC_TERMS_MAX_COUNT) return fail_in(h, URGYM_ERR_ARG, who, "count must be in [1, URGYM_SAC_TERMS_MAX_COUNT] (65536)");
+  if (a.eval_index < 0) return fail_in(h, URGYM_ERR_ARG, who, "eval_index is negative");
+  const LearnerPointer required[] = {{"episode_return", a.episode_return}, {"episode_last_step", a.episode_last_step}, {"episode_success", a.episode_success},
+                                     {"best_mean", a.best_mean},           {"best_index", a.best_index},               {"record", a.record}};
+  for (const LearnerPointer& r : required)
+    if (!r.p) return failf(h, URGYM_ERR_ARG, "%s: urgym_eval_stats_args.%s is null", who, r.name);
+  if ((uintptr_t)a.record % 8 != 0 || (uintptr_t)a.best_mean % 8 != 0 || (uintptr_t)a.best_index % 8 != 0 || (uintptr_t)a.episode_return % 8 != 0)
+    return fail_in(h, URGYM_ERR_ARG, who, "record, best_mean, best_index and episode_return must be 8-byte aligned");
+  *out = EvalStatsCall{a.count, a.eval_index, a.episode_return, a.episode_last_step, a.episode_success, a.best_mean, a.best_index, a.record};
+  return URGYM_OK;
+}
+
+int check_actor_snapshot(Handle* h, const urgym_actor_snapshot_args* args, const char* who, ActorSnapshotCall* out) {
+  if (!args) return fail_in(h, URGYM_ERR_ARG, who, "null args");
+  const urgym_actor_snapshot_args& a = *args;
+  if (a.reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "urgym_actor_snapshot_args.reserved0 must be 0");
+  if (a.in_features < 1) return fail_in(h, URGYM_ERR_ARG, who, "in_features must be positive");
+  if (a.hidden_width < 1 || a.hidden_width > 512) return fail_in(h, URGYM_ERR_ARG, who, "hidden_width must be in [1, 512]");
+  const urgym_actor_tensors_const& f = a.source;
+  const urgym_actor_tensors& t = a.destination;
+  const float* const src[ACTOR_SNAPSHOT_TENSORS] = {f.w0, f.b0, f.w1, f.b1, f.w_mu, f.b_mu, f.w_log_std, f.b_log_std};
+  float* const dst[ACTOR_SNAPSHOT_TENSORS] = {t.w0, t.b0, t.w1, t.b1, t.w_mu, t.b_mu, t.w_log_std, t.b_log_std};
+  for (int i = 0; i < ACTOR_SNAPSHOT_TENSORS; i++) {
+    if (!src[i] || !dst[i]) return fail_in(h, URGYM_ERR_ARG, who, "a tensor pointer is null (all sixteen are required)");
+    out->src[i] = src[i], out->dst[i] = dst[i];
+  }
+  actor_snapshot_offsets(a.in_features, a.hidden_width, out->first);
+  out->when = a.when;
+  return URGYM_OK;
+}
+
+// what urgym_policy_evaluate launches: the five calls of its sequence, checked
+struct PolicyEvaluation {
+  Handle* eh;
+  Actor* actor;
+  ActorPacked buf;
+  const float* src[PACK_ACTOR_TENSORS];
+  urgym_trajectory traj;
+  int num_steps;
+  uint64_t reset_seed;
+  urgym_eval_record* records;
+  EvalStatsCall stats;       // record and eval_index move per evaluation
+  ActorSnapshotCall snapshot;  // when moves per evaluation
+  bool normalized, normalized_rows;  // urgym_policy_evaluate_normalized; ... with norm_obs on
+  NormApplyCall norm;                // the evaluation handle's bound rows into eval_scratch
+  NormSnapshotCall norm_snapshot;    // when moves per evaluation
+};
+
+// What urgym_policy_evaluate_normalized checks beyond urgym_policy_evaluate, after check_policy_evaluation has filled `out`.  The
+// dimensions are the evaluation handle's; messages go to `report`.
+int check_evaluation_normalization(Handle* report, Handle* eh, const urgym_normalization* norm, const char* who, PolicyEvaluation* out) {
+  auto relay = [&](int rc) { return report == eh ? rc : failf(report, rc, "%.200s", eh->err); };
+  if (int rc = check_normalization(eh, norm, who)) return relay(rc);
+  if (!norm->eval_scratch) return fail_in(report, URGYM_ERR_ARG, who, "urgym_normalization.eval_scratch is null");
+  if (int rc = check_norm_snapshot(eh, &norm->state, norm->best_state, nullptr, who, &out->norm_snapshot)) return relay(rc);
+  out->normalized = true, out->normalized_rows = norm->norm_obs != 0;
+  if (out->normalized_rows) {
+    const size_t n = (size_t)eh->cfg.num_envs;
+    float* const ach = norm->eval_scratch + n * (size_t)eh->obs_dim;
+    const urgym_norm_rows_args rows{eh->buf.observation, eh->buf.achieved_goal, eh->buf.desired_goal, norm->eval_scratch, ach, ach + n * (size_t)eh->goal_dim};
+    if (int rc = check_norm_rows(eh, norm, &rows, eh->cfg.num_envs, who, &out->norm)) return relay(rc);
+  }
+  return URGYM_OK;
+}
+
+// Every check of urgym_policy_evaluate but those of eval_index and record_slot (check_evaluation_slot).  Messages go to `report` -- the
+// evaluation handle itself, or the training handle of urgym_sac_train_evaluated.
+int check_policy_evaluation(Handle* report, Handle* eh, const urgym_policy_evaluation* evaluation, const char* who, PolicyEvaluation* out) {
+  static_assert(PACK_ACTOR_TENSORS == ACTOR_SNAPSHOT_TENSORS, "urgym_actor_tensors' eight");
+  if (!eh) return fail_in(report, URGYM_ERR_ARG, who, "null evaluation handle");
+  if (!eh->bound) return fail_in(report, URGYM_ERR_STATE, who, "urgym_bind() has not been called on the evaluation handle");
+  if (!evaluation) return fail_in(report, URGYM_ERR_ARG, who, "null evaluation");
+  const urgym_policy_evaluation& e = *evaluation;
+  if (e.reserved0 != 0) return fail_in(report, URGYM_ERR_ARG, who, "urgym_policy_evaluation.reserved0 must be 0");
+  if (eh->cfg.auto_reset) return fail_in(report, URGYM_ERR_ARG, who, "the evaluation handle has auto_reset on (the episode summary is that of whole first episodes)");
+  if (eh->cfg.num_envs > SAC_TERMS_MAX_COUNT) return fail_in(report, URGYM_ERR_ARG, who, "the evaluation handle has more than 65536 envs (URGYM_SAC_TERMS_MAX_COUNT)");
+  if (e.num_steps < 1) return fail_in(report, URGYM_ERR_ARG, who, "num_steps must be at least 1");
+  if (e.record_capacity < 1) return fail_in(report, URGYM_ERR_ARG, who, "record_capacity must be at least 1");
+  if (!e.eval_actor) return fail_in(report, URGYM_ERR_ARG, who, "urgym_policy_evaluation.eval_actor is null");
+  Actor* a = member(eh->actors, e.eval_actor);
+  if (!a) return fail_in(report, URGYM_ERR_ARG, who, "eval_actor is not an actor of the evaluation handle (actors belong to the handle they were created with)");
+  if (actor_in_features(a) != actor_features(eh))
+    return failf(report, URGYM_ERR_ARG, "%s: the eval actor takes %d features, the evaluation env kind offers %d", who, actor_in_features(a), actor_features(eh));
+  const ActorPacked buf = actor_packed(a);
+  if (e.in_features != buf.in_features || e.hidden_width != buf.hidden)
+    return failf(report, URGYM_ERR_ARG, "%s: the source is %d -> %d, the eval actor is %d -> %d", who, e.in_features, e.hidden_width, buf.in_features, buf.hidden);
+  const LearnerPointer required[] = {{"episode_return", e.episode_return}, {"episode_last_step", e.episode_last_step}, {"episode_success", e.episode_success},
+                                     {"episode_done", e.episode_done},     {"records", e.records},                     {"best_mean", e.best_mean},
+                                     {"best_index", e.best_index}};
+  for (const LearnerPointer& r : required)
+    if (!r.p) return failf(report, URGYM_ERR_ARG, "%s: urgym_policy_evaluation.%s is null", who, r.name);
+  PolicyEvaluation& c = *out;
+  memset(&c, 0, sizeof(c));
+  // the snapshot's checks: all sixteen tensors, the shape
+  urgym_actor_snapshot_args sa;
+  memset(&sa, 0, sizeof(sa));
+  sa.in_features = e.in_features, sa.hidden_width = e.hidden_width, sa.source = e.source, sa.destination = e.best;
+  if (int rc = check_actor_snapshot(report, &sa, who, &c.snapshot)) return rc;
+  // the statistics' checks, on slot 0 (every slot has its alignment: the record is a multiple of 8 bytes)
+  urgym_eval_stats_args ea;
+  memset(&ea, 0, sizeof(ea));
+  ea.count = eh->cfg.num_envs, ea.episode_return = e.episode_return, ea.episode_last_step = e.episode_last_step, ea.episode_success = e.episode_success;
+  ea.best_mean = e.best_mean, ea.best_index = e.best_index, ea.record = e.records;
+  if (int rc = check_eval_stats(report, &ea, who, &c.stats)) return rc;
+  c.eh = eh, c.actor = a, c.buf = buf;
+  for (int i = 0; i < PACK_ACTOR_TENSORS; i++) c.src[i] = c.snapshot.src[i];  // urgym_actor_load's order is urgym_actor_tensors'
+  c.traj.episode_return = e.episode_return, c.traj.episode_last_step = e.episode_last_step;
+  c.traj.episode_success = e.episode_success, c.traj.episode_done = e.episode_done;
+  c.num_steps = e.num_steps, c.reset_seed = e.reset_seed, c.records = e.records;
+  return URGYM_OK;
+}
+
+int check_evaluation_slot(Handle* report, const urgym_policy_evaluation& e, int64_t eval_index, int32_t record_slot, const char* who) {
+  if (eval_index < 0) return fail_in(report, URGYM_ERR_ARG, who, "eval_index is negative");
+  if (record_slot < 0 || record_slot >= e.record_capacity) return fail_in(report, URGYM_ERR_ARG, who, "record_slot outside [0, record_capacity)");
+  return URGYM_OK;
+}
+
+// the launching half: the five calls on `s`.  A failure leaves its message in the evaluation handle.
+int launch_policy_evaluation(PolicyEvaluation& c, int64_t eval_index, int32_t record_slot, hipStream_t s) {
+  Handle* eh = c.eh;
+  HIP_TRY(eh, hipSetDevice(eh->device));
+  actor_pack_launch(c.buf, c.src, s);  // urgym_actor_load with both head pointers
+  HIP_TRY(eh, hipGetLastError());
+  actor_mark_log_std(c.actor);
+  // env.reset(seed=): a seeded reset of every env rewinds the episode counters, so that it starts the same episodes every time
+  HIP_TRY(eh, hipMemsetAsync(eh->buf.episode_id, 0, sizeof(int32_t) * (size_t)eh->cfg.num_envs, s));
+  // ... and on an environment that looks fresh: RESET leaves the velocity slot of the UR5DynReach-v1 observation as it finds it (the
+  // reference's stale ReachDyn.velocity, reach.py:657), so without this the first evaluation of a handle would see zeros there and every
+  // later one the twist of the previous evaluation's last step -- other first observations, other returns, no fair comparison
+  HIP_TRY(eh, hipMemsetAsync(eh->buf.observation, 0, sizeof(float) * (size_t)eh->cfg.num_envs * (size_t)eh->obs_dim, s));
+  if (int rc = urgym_reset(eh, nullptr, c.reset_seed, s)) return rc;
+  if (int rc = rollout(eh, c.actor, nullptr, c.num_steps, RolloutSinks{&c.traj, nullptr, nullptr, 0}, s, c.normalized_rows ? &c.norm : nullptr)) return rc;
+  urgym_eval_record* record = c.records + record_slot;
+  c.stats.eval_index = eval_index, c.stats.record = record;
+  eval_stats_launch(c.stats, s);
+  HIP_TRY(eh, hipGetLastError());
+  c.snapshot.when = &record->improved;
+  actor_snapshot_launch(c.snapshot, s);
+  if (c.normalized) {  // the statistics the actor was selected under, beside it
+    HIP_TRY(eh, hipGetLastError());
+    c.norm_snapshot.when = &record->improved;
+    norm_snapshot_launch(c.norm_snapshot, s);
+  }
+  return launched(eh);
+}
+
+// ---- training-episode statistics (include/urgym.h, urgym_monitor_fold ... urgym_sac_train_monitored; DESIGN.md section 19).  As above
+// each entry point is a checking half, which launches nothing and fills the launch struct of urgym_monitor.h, and a launching half,
+// which refuses nothing.
+
+// the six state pointers: all given, the 8-byte ones aligned
+int check_monitor_state(Handle* h, const urgym_monitor_state* state, const char* who) {
+  if (!state) return fail_in(h, URGYM_ERR_ARG, who, "null monitor state");
+  const urgym_monitor_state& m = *state;
+  const LearnerPointer required[] = {{"running_return", m.running_return}, {"running_length", m.running_length}, {"sum_return", m.sum_return},
+                                     {"sum_length", m.sum_length},         {"episodes", m.episodes},             {"successes", m.successes}};
+  for (const LearnerPointer& r : required)
+    if (!r.p) return failf(h, URGYM_ERR_ARG, "%s: urgym_monitor_state.%s is null", who, r.name);
+  if ((uintptr_t)m.running_return % 8 != 0 || (uintptr_t)m.sum_return % 8 != 0 || (uintptr_t)m.sum_length % 8 != 0)
+    return fail_in(h, URGYM_ERR_ARG, who, "running_return, sum_return and sum_length must be 8-byte aligned");
+  return URGYM_OK;
+}
+
+int check_monitor_fold(Handle* h, const urgym_monitor_state* state, const urgym_replay_ring* ring, int first_slot, int num_steps, const char* who, MonitorFoldCall* out) {
+  if (int rc = check_monitor_state(h, state, who)) return rc;
+  if (int rc = check_fold_ring(h, ring, first_slot, num_steps, who)) return rc;
+  *out = MonitorFoldCall{h->cfg.num_envs, ring->capacity_steps, first_slot, num_steps, *state, ring->reward, ring->terminated, ring->truncated, ring->is_success};
+  return URGYM_OK;
+}
+
+int check_monitor_stats(Handle* h, const urgym_monitor_state* state, urgym_monitor_record* record, int64_t iteration, int clear, const char* who, MonitorStatsCall* out) {
+  static_assert(sizeof(urgym_monitor_record) == 72 && alignof(urgym_monitor_record) == 8, "include/urgym.h");
+  if (int rc = check_monitor_state(h, state, who)) return rc;
+  if (!record) return fail_in(h, URGYM_ERR_ARG, who, "null record");
+  if ((uintptr_t)record % 8 != 0) return fail_in(h, URGYM_ERR_ARG, who, "record must be 8-byte aligned");
+  *out = MonitorStatsCall{h->cfg.num_envs, clear, iteration, *state, record};
+  return URGYM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int urgym_eval_stats(void* handle, const urgym_eval_stats_args* args, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  EvalStatsCall c;
+  if (int rc = check_eval_stats(h, args, "urgym_eval_stats", &c)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  eval_stats_launch(c, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_actor_snapshot(void* handle, const urgym_actor_snapshot_args* args, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  ActorSnapshotCall c;
+  if (int rc = check_actor_snapshot(h, args, "urgym_actor_snapshot", &c)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  actor_snapshot_launch(c, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_policy_evaluate(void* eval_handle, const urgym_policy_evaluation* evaluation, int64_t eval_index, int32_t record_slot, void* stream) {
+  const char* who = "urgym_policy_evaluate";
+  Handle* eh = (Handle*)eval_handle;
+  if (!eh) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  PolicyEvaluation c;
+  if (int rc = check_policy_evaluation(eh, eh, evaluation, who, &c)) return rc;
+  if (int rc = check_evaluation_slot(eh, *evaluation, eval_index, record_slot, who)) return rc;
+  return launch_policy_evaluation(c, eval_index, record_slot, (hipStream_t)stream);
+}
+
+int urgym_monitor_fold(void* handle, const urgym_monitor_state* state, const urgym_replay_ring* ring, int first_slot, int num_steps, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  MonitorFoldCall c;
+  if (int rc = check_monitor_fold(h, state, ring, first_slot, num_steps, "urgym_monitor_fold", &c)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  monitor_fold_launch(c, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_monitor_stats(void* handle, const urgym_monitor_state* state, urgym_monitor_record* record, int64_t iteration, int clear, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  MonitorStatsCall c;
+  if (int rc = check_monitor_stats(h, state, record, iteration, clear, "urgym_monitor_stats", &c)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  monitor_stats_launch(c, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_norm_snapshot(void* handle, const urgym_norm_state* source, const urgym_norm_state* destination, const int32_t* when, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  NormSnapshotCall c;
+  if (int rc = check_norm_snapshot(h, source, destination, when, "urgym_norm_snapshot", &c)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  norm_snapshot_launch(c, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_policy_evaluate_normalized(void* eval_handle, const urgym_policy_evaluation* evaluation, const urgym_normalization* normalization, int64_t eval_index, int32_t record_slot, void* stream) {
+  const char* who = "urgym_policy_evaluate_normalized";
+  Handle* eh = (Handle*)eval_handle;
+  if (!eh) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  PolicyEvaluation c;
+  if (int rc = check_policy_evaluation(eh, eh, evaluation, who, &c)) return rc;
+  if (int rc = check_evaluation_slot(eh, *evaluation, eval_index, record_slot, who)) return rc;
+  if (int rc = check_evaluation_normalization(eh, eh, normalization, who, &c)) return rc;
+  return launch_policy_evaluation(c, eval_index, record_slot, (hipStream_t)stream);
+}
+
+int urgym_norm_workspace(void* handle, int num_steps, uint64_t* bytes) {
+  const char* who = "urgym_norm_workspace";
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (!bytes) return fail_in(h, URGYM_ERR_ARG, who, "null bytes");
+  if (num_steps <= 0) return fail_in(h, URGYM_ERR_ARG, who, "num_steps must be positive");
+  *bytes = norm_workspace_doubles(h->cfg.num_envs, actor_features(h), num_steps) * sizeof(double);
+  return URGYM_OK;
+}
+
+int urgym_norm_fold(void* handle, const urgym_normalization* norm, const urgym_replay_ring* ring, int first_slot, int num_steps, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  NormFoldCall c;
+  if (int rc = check_norm_fold(h, norm, ring, first_slot, num_steps, "urgym_norm_fold", &c)) return rc;
+  if (norm->training == 0) return URGYM_OK;
+  HIP_TRY(h, hipSetDevice(h->device));
+  norm_fold_launch(c, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_norm_rows(void* handle, const urgym_normalization* norm, const urgym_norm_rows_args* rows, int count, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  NormApplyCall c;
+  if (int rc = check_norm_rows(h, norm, rows, count, "urgym_norm_rows", &c)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  norm_apply_launch(c, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_norm_batch(void* handle, const urgym_normalization* norm, const urgym_replay_batch* batch, int count, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  NormApplyCall c;
+  if (int rc = check_norm_batch(h, norm, batch, count, "urgym_norm_batch", &c)) return rc;
+  if (c.segments == 0) return URGYM_OK;
+  HIP_TRY(h, hipSetDevice(h->device));
+  norm_apply_launch(c, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_rollout_collect_normalized(void* handle, void* actor, const urgym_sampling* how, int num_steps, const urgym_replay_ring* ring, int first_slot, const urgym_normalization* norm, void* stream) {
+  const char* who = "urgym_rollout_collect_normalized";
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  Actor* a = nullptr;
+  if (int rc = check_collect(h, actor, how, num_steps, ring, first_slot, who, &a)) return rc;
+  if (int rc = check_normalization(h, norm, who)) return rc;
+  if (norm->norm_obs == 0) return rollout(h, a, how, num_steps, RolloutSinks{nullptr, nullptr, ring, first_slot}, (hipStream_t)stream);
+  if (!norm->scratch) return fail_in(h, URGYM_ERR_ARG, who, "urgym_normalization.scratch is null");
+  const size_t n = (size_t)h->cfg.num_envs;
+  float* const obs = norm->scratch;
+  float* const ach = obs + n * (size_t)h->obs_dim;
+  float* const des = ach + n * (size_t)h->goal_dim;
+  const urgym_norm_rows_args rows{h->buf.observation, h->buf.achieved_goal, h->buf.desired_goal, obs, ach, des};
+  NormApplyCall c;
+  if (int rc = check_norm_rows(h, norm, &rows, h->cfg.num_envs, who, &c)) return rc;
+  return rollout(h, a, how, num_steps, RolloutSinks{nullptr, nullptr, ring, first_slot}, (hipStream_t)stream, &c);
+}
+
+}  // extern "C"
+
+// ---- the training loop in one call (include/urgym.h, urgym_sac_train; DESIGN.md section 17): every check above first, then nothing
+// but launches.  The launch structs are filled once; an update rewrites the few numbers that move (draws, the ring view, Adam's
+// coefficients, the loss slots).
+
+namespace {
+
 // after the launches of one stage: urgym_last_error names the iteration and the stage
 int train_stage(Handle* h, const char* who, int iteration, const char* stage) {
   const hipError_t e = hipGetLastError();
@@ -1384,39 +1747,112 @@ int train_stage(Handle* h, const char* who, int iteration, const char* stage) {
   return failf(h, URGYM_ERR_HIP, "%s: iteration %d, %s: %s", who, iteration, stage, hipGetErrorString(e));
 }
 
-// What urgym_sac_train_evaluated hangs into the body of urgym_sac_train; urgym_sac_train itself passes none (null).  before_launch runs
-// after every check of the body and before its first launch: the check-only half of the body ends there, and a refusal of the hook
-// leaves nothing launched.  after_iteration runs after the launches of iteration i.
-struct TrainHooks {
-  int (*before_launch)(void* ctx);
-  int (*after_iteration)(void* ctx, int i);
-  void* ctx;
+// What one training call takes beyond the learner and the schedule: the option structs of the entry points, null = absent.
+struct TrainOptions {
+  const urgym_sac_nstep* nstep;            // the update whose gather, third call and entropy step are the multi-step ones
+  const urgym_sac_prioritized* per;        // urgym_per_fill after every collection, the gather through the priorities, urgym_per_terms
+  const urgym_sac_hindsight* her;          // the update whose gather is urgym_replay_sample_hindsight
+  const urgym_sac_clipping* clip;          // the update with the two norm launches and the scaled steps
+  const urgym_normalization* norm;         // the actor reads normalized rows, one fold after every collection, one urgym_norm_batch after every gather
+  const urgym_sac_evaluation* evaluation;  // TrainExtras
+  const urgym_sac_monitoring* monitoring;  // TrainExtras
 };
 
-// `nstep`: null = the one-step update; given (urgym_sac_train_nstep) = the update whose gather, third call and entropy step are the
-// multi-step ones.  `her`: given (urgym_sac_train_hindsight) = the update whose gather is urgym_replay_sample_hindsight.  `clip`: given
-// (urgym_sac_train_clipped) = the update with the two norm launches and the scaled steps.  `norm`: given (urgym_sac_train_normalized) = the
-// collection whose actor reads normalized rows, one fold of the statistics after every collection, one urgym_norm_batch after every gather
-int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, void* stream, const TrainHooks* hooks, const urgym_sac_nstep* nstep = nullptr,
-                   const urgym_sac_prioritized* per = nullptr, const urgym_sac_hindsight* her = nullptr, const urgym_sac_clipping* clip = nullptr,
-                   const urgym_normalization* norm = nullptr);
+// The evaluations and the training-episode statistics of one training call: what the body runs beside its own checks and launches.
+// check() runs after every check of the body (so the learner and the schedule are sound) and before its first launch: a refusal leaves
+// nothing launched.  after(i) runs after the launches of iteration i.  The monitor's half goes first in both; with neither option given
+// both do nothing.
+struct TrainExtras {
+  const char* who;  // the entry point that runs them
+  Handle* h;
+  const urgym_sac_learner* learner;
+  const urgym_sac_schedule* schedule;
+  hipStream_t s;
+  const urgym_sac_evaluation* evaluation;
+  const urgym_sac_monitoring* monitoring;
+  const urgym_normalization* norm;  // given: the evaluations are urgym_policy_evaluate_normalized's
+  PolicyEvaluation eval_call;
+  int64_t evals_done;      // evaluations launched so far
+  MonitorFoldCall fold;    // first_slot moves per iteration
+  MonitorStatsCall stats;  // record and iteration move per record
+  int64_t records_done;    // records launched so far
 
-}  // namespace
+  int check_monitoring() {
+    const urgym_sac_monitoring& M = *monitoring;
+    const urgym_sac_schedule& S = *schedule;
+    if (M.reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_monitoring.reserved0 must be 0");
+    if (const char* what = monitor_schedule_refusal(S, M.log_every, M.first_iteration, M.first_record, M.record_capacity)) return fail_in(h, URGYM_ERR_ARG, who, what);
+    // the fold's checks with the first iteration's slots (a call that collects nothing folds nothing: its state is still checked below)
+    if (S.steps_per_iteration > 0)
+      if (int rc = check_monitor_fold(h, &M.state, &learner->ring, S.first_slot, S.steps_per_iteration, who, &fold)) return rc;
+    // the statistics' checks, on the first record (every record has its alignment: it is a multiple of 8 bytes); without a record point
+    // the pointer may be anything
+    const bool records = monitor_record_count(M.first_iteration, M.log_every, S.num_iterations) > 0;
+    urgym_monitor_record unused;
+    return check_monitor_stats(h, &M.state, records ? M.records : &unused, 0, M.clear, who, &stats);
+  }
 
-int urgym_sac_train(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, void* stream) {
-  return sac_train_body("urgym_sac_train", handle, learner, schedule, stream, nullptr);
-}
+  int check_evaluation() {
+    const urgym_sac_evaluation& E = *evaluation;
+    Handle* eh = (Handle*)E.eval_handle;
+    if (!eh) return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_evaluation.eval_handle is null");
+    if (eh == h) return fail_in(h, URGYM_ERR_ARG, who, "eval_handle is the training handle (an evaluation would reset the training env; evaluation on it is not supported)");
+    if (eh->device != h->device) return fail_in(h, URGYM_ERR_ARG, who, "the training handle and the evaluation handle are on different devices");
+    if (int rc = check_policy_evaluation(h, eh, &E.evaluation, who, &eval_call)) return rc;
+    if (norm)
+      if (int rc = check_evaluation_normalization(h, eh, norm, who, &eval_call)) return rc;
+    const urgym_actor_tensors& p = learner->actor_adam.param;
+    const float* const params[PACK_ACTOR_TENSORS] = {p.w0, p.b0, p.w1, p.b1, p.w_mu, p.b_mu, p.w_log_std, p.b_log_std};
+    for (int i = 0; i < PACK_ACTOR_TENSORS; i++)
+      if (eval_call.src[i] != params[i]) return fail_in(h, URGYM_ERR_ARG, who, "the evaluation's source tensors are not learner->actor_adam.param");
+    if (learner->actor_adam.in_features != E.evaluation.in_features || learner->actor_adam.hidden_width != E.evaluation.hidden_width)
+      return fail_in(h, URGYM_ERR_ARG, who, "the evaluation's shape is not learner->actor_adam's");
+    if (const char* what = eval_schedule_refusal(*schedule, E.every, E.first_eval_index, E.first_record_slot, E.evaluation.record_capacity))
+      return fail_in(h, URGYM_ERR_ARG, who, what);
+    return URGYM_OK;
+  }
 
-}  // extern "C"
+  int check() {
+    if (monitoring)
+      if (int rc = check_monitoring()) return rc;
+    return evaluation ? check_evaluation() : URGYM_OK;
+  }
 
-namespace {
+  int after(int i) {
+    if (monitoring) {
+      const urgym_sac_monitoring& M = *monitoring;
+      if (schedule->steps_per_iteration > 0) {
+        fold.first_slot = sac_schedule_iteration(*schedule, i).collect_first_slot;
+        monitor_fold_launch(fold, s);
+        if (int rc = train_stage(h, who, i, "monitor_fold")) return rc;
+      }
+      if (monitor_record_follows(M.first_iteration, M.log_every, i)) {
+        stats.record = M.records + M.first_record + records_done;
+        stats.iteration = M.first_iteration + i + 1;
+        records_done++;
+        monitor_stats_launch(stats, s);
+        if (int rc = train_stage(h, who, i, "monitor_stats")) return rc;
+      }
+    }
+    if (!evaluation || !eval_follows(*schedule, evaluation->every, i)) return URGYM_OK;
+    const int rc = launch_policy_evaluation(eval_call, evaluation->first_eval_index + evals_done, (int32_t)(evaluation->first_record_slot + evals_done), s);
+    evals_done++;
+    if (rc) return failf(h, rc, "%s: iteration %d, evaluation: %.150s", who, i, eval_call.eh->err);
+    HIP_TRY(h, hipSetDevice(h->device));  // the same device: what the launches of the next iteration expect to be current
+    return URGYM_OK;
+  }
+};
 
-int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, void* stream, const TrainHooks* hooks, const urgym_sac_nstep* nstep,
-                   const urgym_sac_prioritized* per, const urgym_sac_hindsight* her, const urgym_sac_clipping* clip, const urgym_normalization* norm) {
-  Handle* h = (Handle*)handle;
-  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+// The one driver of the eight urgym_sac_train* entry points: `who` is the entry point's own name in every refusal, `opt` what it was given.
+int sac_train_body(const char* who, Handle* h, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, hipStream_t s, const TrainOptions& opt) {
   if (!learner) return fail_in(h, URGYM_ERR_ARG, who, "null learner");
   if (!schedule) return fail_in(h, URGYM_ERR_ARG, who, "null schedule");
+  const urgym_sac_nstep* const nstep = opt.nstep;
+  const urgym_sac_prioritized* const per = opt.per;
+  const urgym_sac_hindsight* const her = opt.her;
+  const urgym_sac_clipping* const clip = opt.clip;
+  const urgym_normalization* const norm = opt.norm;
+  TrainExtras extras{who, h, learner, schedule, s, opt.evaluation, opt.monitoring, norm};
   const urgym_sac_learner& L = *learner;
   const urgym_sac_schedule& S = *schedule;
   if (L.reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_learner.reserved0 must be 0");
@@ -1448,7 +1884,6 @@ int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learn
   urgym_replay_hindsight her_rule;
   memset(&her_rule, 0, sizeof(her_rule));
   if (her) {  // the rule's own refusals, whether or not the call holds an update: the gather's checks on the ring as it stands
-    if (nstep || per) return fail_in(h, URGYM_ERR_ARG, who, "hindsight with multi-step returns or priorities is out of scope");
     if (her->strategy == HER_GOAL_OWN) return fail_in(h, URGYM_ERR_ARG, who, "URGYM_HER_GOAL_OWN is a diagnostic of the gather, not a way to train");
     if (her->reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_hindsight.reserved0 must be 0");
     her_rule.relabel_threshold = her->relabel_threshold, her_rule.strategy = her->strategy, her_rule.horizon = her->horizon;
@@ -1458,7 +1893,6 @@ int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learn
   PerFill per_fill;
   memset(&per_fill, 0, sizeof(per_fill));
   if (per) {  // the structure's own refusals, whether or not the call holds an update
-    if (nstep) return fail_in(h, URGYM_ERR_ARG, who, "priorities with n_steps > 1 are out of scope (the multi-step gather draws its own indices)");
     if (per->reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_prioritized.reserved0 must be 0");
     if (int rc = check_priorities(h, &per->priorities, who, &per_fill.tree)) return rc;
     if (per->priorities.capacity_steps != L.ring.capacity_steps) return fail_in(h, URGYM_ERR_ARG, who, "priorities.capacity_steps is not ring.capacity_steps");
@@ -1508,7 +1942,6 @@ int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learn
       if (int rc = check_collect(h, L.actor, &how, K, &L.ring, S.first_slot, who, &collector)) return rc;
     }
   }
-  const hipStream_t s = (hipStream_t)stream;
   // the collection of iteration i: the launches of urgym_rollout_collect
   auto collect = [&](int i, const SacIteration& it) {
     const urgym_sampling how{it.collect_mode, 0, L.seed, it.collect_first_draw};
@@ -1529,12 +1962,10 @@ int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learn
     return failf(h, rc, "%s: iteration %d, collect: %s", who, i, was);
   };
   if (updates == 0) {  // the sequence holds no update call: nothing more to check
-    if (hooks)
-      if (int rc = hooks->before_launch(hooks->ctx)) return rc;
+    if (int rc = extras.check()) return rc;
     for (int i = 0; i < S.num_iterations; i++) {
       if (int rc = collect(i, sac_schedule_iteration(S, i))) return rc;
-      if (hooks)
-        if (int rc = hooks->after_iteration(hooks->ctx, i)) return rc;
+      if (int rc = extras.after(i)) return rc;
     }
     return URGYM_OK;
   }
@@ -1658,8 +2089,7 @@ int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learn
     if (int rc = check_actor_grad_norm(h, L.actor, &L.actor_adam.grad, &na, who, &actor_norm)) return rc;
   }
 
-  if (hooks)
-    if (int rc = hooks->before_launch(hooks->ctx)) return rc;
+  if (int rc = extras.check()) return rc;
 
   // ---- the launching halves: nothing below refuses
   int64_t u = 0;
@@ -1668,8 +2098,7 @@ int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learn
     if (K > 0)
       if (int rc = collect(i, it)) return rc;
     if (it.idle) {
-      if (hooks)
-        if (int rc = hooks->after_iteration(hooks->ctx, i)) return rc;
+      if (int rc = extras.after(i)) return rc;
       continue;
     }
     gather.oldest_slot = it.oldest_slot, gather.size = (uint64_t)it.filled_steps * (uint64_t)h->cfg.num_envs;
@@ -1748,389 +2177,41 @@ int sac_train_body(const char* who, void* handle, const urgym_sac_learner* learn
       if (int rc = train_stage(h, who, i, "actor_adam_step")) return rc;
       actor_mark_log_std(actor_step.a);  // as urgym_actor_adam_step; the checks above have required the head already
     }
-    if (hooks)
-      if (int rc = hooks->after_iteration(hooks->ctx, i)) return rc;
+    if (int rc = extras.after(i)) return rc;
   }
   return URGYM_OK;
 }
 
-// ---- evaluation inside the training call (include/urgym.h, urgym_eval_stats ... urgym_sac_train_evaluated; DESIGN.md section 18).
-// As above each entry point is a checking half, which launches nothing and fills the launch struct of urgym_eval.h, and a launching
-// half, which refuses nothing.
-
-int check_eval_stats(Handle* h, const urgym_eval_stats_args* args, const char* who, EvalStatsCall* out) {
-  static_assert(sizeof(urgym_eval_record) == 72 && alignof(urgym_eval_record) == 8, "include/urgym.h");
-  if (!args) return fail_in(h, URGYM_ERR_ARG, who, "null args");
-  const urgym_eval_stats_args& a = *args;
-  if (a.reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "urgym_eval_stats_args.reserved0 must be 0");
-  if (a.count < 1 || a.count > SAC_TERMS_MAX_COUNT) return fail_in(h, URGYM_ERR_ARG, who, "count must be in [1, URGYM_SAC_TERMS_MAX_COUNT] (65536)");
-  if (a.eval_index < 0) return fail_in(h, URGYM_ERR_ARG, who, "eval_index is negative");
-  const LearnerPointer required[] = {{"episode_return", a.episode_return}, {"episode_last_step", a.episode_last_step}, {"episode_success", a.episode_success},
-                                     {"best_mean", a.best_mean},           {"best_index", a.best_index},               {"record", a.record}};
-  for (const LearnerPointer& r : required)
-    if (!r.p) return failf(h, URGYM_ERR_ARG, "%s: urgym_eval_stats_args.%s is null", who, r.name);
-  if ((uintptr_t)a.record % 8 != 0 || (uintptr_t)a.best_mean % 8 != 0 || (uintptr_t)a.best_index % 8 != 0 || (uintptr_t)a.episode_return % 8 != 0)
-    return fail_in(h, URGYM_ERR_ARG, who, "record, best_mean, best_index and episode_return must be 8-byte aligned");
-  *out = EvalStatsCall{a.count, a.eval_index, a.episode_return, a.episode_last_step, a.episode_success, a.best_mean, a.best_index, a.record};
-  return URGYM_OK;
-}
-
-int check_actor_snapshot(Handle* h, const urgym_actor_snapshot_args* args, const char* who, ActorSnapshotCall* out) {
-  if (!args) return fail_in(h, URGYM_ERR_ARG, who, "null args");
-  const urgym_actor_snapshot_args& a = *args;
-  if (a.reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "urgym_actor_snapshot_args.reserved0 must be 0");
-  if (a.in_features < 1) return fail_in(h, URGYM_ERR_ARG, who, "in_features must be positive");
-  if (a.hidden_width < 1 || a.hidden_width > 512) return fail_in(h, URGYM_ERR_ARG, who, "hidden_width must be in [1, 512]");
-  const urgym_actor_tensors_const& f = a.source;
-  const urgym_actor_tensors& t = a.destination;
-  const float* const src[ACTOR_SNAPSHOT_TENSORS] = {f.w0, f.b0, f.w1, f.b1, f.w_mu, f.b_mu, f.w_log_std, f.b_log_std};
-  float* const dst[ACTOR_SNAPSHOT_TENSORS] = {t.w0, t.b0, t.w1, t.b1, t.w_mu, t.b_mu, t.w_log_std, t.b_log_std};
-  for (int i = 0; i < ACTOR_SNAPSHOT_TENSORS; i++) {
-    if (!src[i] || !dst[i]) return fail_in(h, URGYM_ERR_ARG, who, "a tensor pointer is null (all sixteen are required)");
-    out->src[i] = src[i], out->dst[i] = dst[i];
-  }
-  actor_snapshot_offsets(a.in_features, a.hidden_width, out->first);
-  out->when = a.when;
-  return URGYM_OK;
-}
-
-// what urgym_policy_evaluate launches: the five calls of its sequence, checked
-struct PolicyEvaluation {
-  Handle* eh;
-  Actor* actor;
-  ActorPacked buf;
-  const float* src[PACK_ACTOR_TENSORS];
-  urgym_trajectory traj;
-  int num_steps;
-  uint64_t reset_seed;
-  urgym_eval_record* records;
-  EvalStatsCall stats;       // record and eval_index move per evaluation
-  ActorSnapshotCall snapshot;  // when moves per evaluation
-  bool normalized, normalized_rows;  // urgym_policy_evaluate_normalized; ... with norm_obs on
-  NormApplyCall norm;                // the evaluation handle's bound rows into eval_scratch
-  NormSnapshotCall norm_snapshot;    // when moves per evaluation
-};
-
-static int check_normalization(Handle* h, const urgym_normalization* norm, const char* who);
-static int check_norm_rows(Handle* h, const urgym_normalization* norm, const urgym_norm_rows_args* rows, int count, const char* who, NormApplyCall* out);
-int check_norm_snapshot(Handle* h, const urgym_norm_state* source, const urgym_norm_state* destination, const int32_t* when, const char* who, NormSnapshotCall* out);
-
-// What urgym_policy_evaluate_normalized checks beyond urgym_policy_evaluate, after check_policy_evaluation has filled `out`.  The
-// dimensions are the evaluation handle's; messages go to `report`.
-int check_evaluation_normalization(Handle* report, Handle* eh, const urgym_normalization* norm, const char* who, PolicyEvaluation* out) {
-  auto relay = [&](int rc) { return report == eh ? rc : failf(report, rc, "%.200s", eh->err); };
-  if (int rc = check_normalization(eh, norm, who)) return relay(rc);
-  if (!norm->eval_scratch) return fail_in(report, URGYM_ERR_ARG, who, "urgym_normalization.eval_scratch is null");
-  if (int rc = check_norm_snapshot(eh, &norm->state, norm->best_state, nullptr, who, &out->norm_snapshot)) return relay(rc);
-  out->normalized = true, out->normalized_rows = norm->norm_obs != 0;
-  if (out->normalized_rows) {
-    const size_t n = (size_t)eh->cfg.num_envs;
-    float* const ach = norm->eval_scratch + n * (size_t)eh->obs_dim;
-    const urgym_norm_rows_args rows{eh->buf.observation, eh->buf.achieved_goal, eh->buf.desired_goal, norm->eval_scratch, ach, ach + n * (size_t)eh->goal_dim};
-    if (int rc = check_norm_rows(eh, norm, &rows, eh->cfg.num_envs, who, &out->norm)) return relay(rc);
-  }
-  return URGYM_OK;
-}
-
-// Every check of urgym_policy_evaluate but those of eval_index and record_slot (check_evaluation_slot).  Messages go to `report` -- the
-// evaluation handle itself, or the training handle of urgym_sac_train_evaluated.
-int check_policy_evaluation(Handle* report, Handle* eh, const urgym_policy_evaluation* evaluation, const char* who, PolicyEvaluation* out) {
-  static_assert(PACK_ACTOR_TENSORS == ACTOR_SNAPSHOT_TENSORS, "urgym_actor_tensors' eight");
-  if (!eh) return fail_in(report, URGYM_ERR_ARG, who, "null evaluation handle");
-  if (!eh->bound) return fail_in(report, URGYM_ERR_STATE, who, "urgym_bind() has not been called on the evaluation handle");
-  if (!evaluation) return fail_in(report, URGYM_ERR_ARG, who, "null evaluation");
-  const urgym_policy_evaluation& e = *evaluation;
-  if (e.reserved0 != 0) return fail_in(report, URGYM_ERR_ARG, who, "urgym_policy_evaluation.reserved0 must be 0");
-  if (eh->cfg.auto_reset) return fail_in(report, URGYM_ERR_ARG, who, "the evaluation handle has auto_reset on (the episode summary is that of whole first episodes)");
-  if (eh->cfg.num_envs > SAC_TERMS_MAX_COUNT) return fail_in(report, URGYM_ERR_ARG, who, "the evaluation handle has more than 65536 envs (URGYM_SAC_TERMS_MAX_COUNT)");
-  if (e.num_steps < 1) return fail_in(report, URGYM_ERR_ARG, who, "num_steps must be at least 1");
-  if (e.record_capacity < 1) return fail_in(report, URGYM_ERR_ARG, who, "record_capacity must be at least 1");
-  if (!e.eval_actor) return fail_in(report, URGYM_ERR_ARG, who, "urgym_policy_evaluation.eval_actor is null");
-  Actor* a = member(eh->actors, e.eval_actor);
-  if (!a) return fail_in(report, URGYM_ERR_ARG, who, "eval_actor is not an actor of the evaluation handle (actors belong to the handle they were created with)");
-  if (actor_in_features(a) != actor_features(eh))
-    return failf(report, URGYM_ERR_ARG, "%s: the eval actor takes %d features, the evaluation env kind offers %d", who, actor_in_features(a), actor_features(eh));
-  const ActorPacked buf = actor_packed(a);
-  if (e.in_features != buf.in_features || e.hidden_width != buf.hidden)
-    return failf(report, URGYM_ERR_ARG, "%s: the source is %d -> %d, the eval actor is %d -> %d", who, e.in_features, e.hidden_width, buf.in_features, buf.hidden);
-  const LearnerPointer required[] = {{"episode_return", e.episode_return}, {"episode_last_step", e.episode_last_step}, {"episode_success", e.episode_success},
-                                     {"episode_done", e.episode_done},     {"records", e.records},                     {"best_mean", e.best_mean},
-                                     {"best_index", e.best_index}};
-  for (const LearnerPointer& r : required)
-    if (!r.p) return failf(report, URGYM_ERR_ARG, "%s: urgym_policy_evaluation.%s is null", who, r.name);
-  PolicyEvaluation& c = *out;
-  memset(&c, 0, sizeof(c));
-  // the snapshot's checks: all sixteen tensors, the shape
-  urgym_actor_snapshot_args sa;
-  memset(&sa, 0, sizeof(sa));
-  sa.in_features = e.in_features, sa.hidden_width = e.hidden_width, sa.source = e.source, sa.destination = e.best;
-  if (int rc = check_actor_snapshot(report, &sa, who, &c.snapshot)) return rc;
-  // the statistics' checks, on slot 0 (every slot has its alignment: the record is a multiple of 8 bytes)
-  urgym_eval_stats_args ea;
-  memset(&ea, 0, sizeof(ea));
-  ea.count = eh->cfg.num_envs, ea.episode_return = e.episode_return, ea.episode_last_step = e.episode_last_step, ea.episode_success = e.episode_success;
-  ea.best_mean = e.best_mean, ea.best_index = e.best_index, ea.record = e.records;
-  if (int rc = check_eval_stats(report, &ea, who, &c.stats)) return rc;
-  c.eh = eh, c.actor = a, c.buf = buf;
-  for (int i = 0; i < PACK_ACTOR_TENSORS; i++) c.src[i] = c.snapshot.src[i];  // urgym_actor_load's order is urgym_actor_tensors'
-  c.traj.episode_return = e.episode_return, c.traj.episode_last_step = e.episode_last_step;
-  c.traj.episode_success = e.episode_success, c.traj.episode_done = e.episode_done;
-  c.num_steps = e.num_steps, c.reset_seed = e.reset_seed, c.records = e.records;
-  return URGYM_OK;
-}
-
-int check_evaluation_slot(Handle* report, const urgym_policy_evaluation& e, int64_t eval_index, int32_t record_slot, const char* who) {
-  if (eval_index < 0) return fail_in(report, URGYM_ERR_ARG, who, "eval_index is negative");
-  if (record_slot < 0 || record_slot >= e.record_capacity) return fail_in(report, URGYM_ERR_ARG, who, "record_slot outside [0, record_capacity)");
-  return URGYM_OK;
-}
-
-// the launching half: the five calls on `s`.  A failure leaves its message in the evaluation handle.
-int launch_policy_evaluation(PolicyEvaluation& c, int64_t eval_index, int32_t record_slot, hipStream_t s) {
-  Handle* eh = c.eh;
-  HIP_TRY(eh, hipSetDevice(eh->device));
-  actor_pack_launch(c.buf, c.src, s);  // urgym_actor_load with both head pointers
-  HIP_TRY(eh, hipGetLastError());
-  actor_mark_log_std(c.actor);
-  // env.reset(seed=): a seeded reset of every env rewinds the episode counters, so that it starts the same episodes every time
-  HIP_TRY(eh, hipMemsetAsync(eh->buf.episode_id, 0, sizeof(int32_t) * (size_t)eh->cfg.num_envs, s));
-  // ... and on an environment that looks fresh: RESET leaves the velocity slot of the UR5DynReach-v1 observation as it finds it (the
-  // reference's stale ReachDyn.velocity, reach.py:657), so without this the first evaluation of a handle would see zeros there and every
-  // later one the twist of the previous evaluation's last step -- other first observations, other returns, no fair comparison
-  HIP_TRY(eh, hipMemsetAsync(eh->buf.observation, 0, sizeof(float) * (size_t)eh->cfg.num_envs * (size_t)eh->obs_dim, s));
-  if (int rc = urgym_reset(eh, nullptr, c.reset_seed, s)) return rc;
-  if (int rc = rollout(eh, c.actor, nullptr, c.num_steps, RolloutSinks{&c.traj, nullptr, nullptr, 0}, s, c.normalized_rows ? &c.norm : nullptr)) return rc;
-  urgym_eval_record* record = c.records + record_slot;
-  c.stats.eval_index = eval_index, c.stats.record = record;
-  eval_stats_launch(c.stats, s);
-  HIP_TRY(eh, hipGetLastError());
-  c.snapshot.when = &record->improved;
-  actor_snapshot_launch(c.snapshot, s);
-  if (c.normalized) {  // the statistics the actor was selected under, beside it
-    HIP_TRY(eh, hipGetLastError());
-    c.norm_snapshot.when = &record->improved;
-    norm_snapshot_launch(c.norm_snapshot, s);
-  }
-  return launched(eh);
-}
-
-// urgym_sac_train_evaluated's hooks into sac_train_body
-struct TrainEvaluation {
-  Handle* h;
-  const urgym_sac_learner* learner;
-  const urgym_sac_schedule* schedule;
-  const urgym_sac_evaluation* evaluation;
-  hipStream_t s;
-  PolicyEvaluation call;
-  int64_t done;  // evaluations launched so far
-  const char* who;  // the entry point that runs them: urgym_sac_train_evaluated, or urgym_sac_train_monitored
-  const urgym_normalization* norm = nullptr;  // urgym_sac_train_normalized: the evaluations are urgym_policy_evaluate_normalized's
-};
-
-const char* const TRAIN_EVALUATED = "urgym_sac_train_evaluated";
-
-// runs after every check of the training body (so the learner and the schedule are sound) and before its first launch
-int train_evaluation_check(void* ctx) {
-  TrainEvaluation& t = *(TrainEvaluation*)ctx;
-  const char* who = t.who;
-  Handle* h = t.h;
-  const urgym_sac_evaluation& E = *t.evaluation;
-  Handle* eh = (Handle*)E.eval_handle;
-  if (!eh) return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_evaluation.eval_handle is null");
-  if (eh == h) return fail_in(h, URGYM_ERR_ARG, who, "eval_handle is the training handle (an evaluation would reset the training env; evaluation on it is not supported)");
-  if (eh->device != h->device) return fail_in(h, URGYM_ERR_ARG, who, "the training handle and the evaluation handle are on different devices");
-  if (int rc = check_policy_evaluation(h, eh, &E.evaluation, who, &t.call)) return rc;
-  if (t.norm)
-    if (int rc = check_evaluation_normalization(h, eh, t.norm, who, &t.call)) return rc;
-  const urgym_actor_tensors& p = t.learner->actor_adam.param;
-  const float* const params[PACK_ACTOR_TENSORS] = {p.w0, p.b0, p.w1, p.b1, p.w_mu, p.b_mu, p.w_log_std, p.b_log_std};
-  for (int i = 0; i < PACK_ACTOR_TENSORS; i++)
-    if (t.call.src[i] != params[i]) return fail_in(h, URGYM_ERR_ARG, who, "the evaluation's source tensors are not learner->actor_adam.param");
-  if (t.learner->actor_adam.in_features != E.evaluation.in_features || t.learner->actor_adam.hidden_width != E.evaluation.hidden_width)
-    return fail_in(h, URGYM_ERR_ARG, who, "the evaluation's shape is not learner->actor_adam's");
-  if (const char* what = eval_schedule_refusal(*t.schedule, E.every, E.first_eval_index, E.first_record_slot, E.evaluation.record_capacity))
-    return fail_in(h, URGYM_ERR_ARG, who, what);
-  return URGYM_OK;
-}
-
-int train_evaluation_after(void* ctx, int i) {
-  TrainEvaluation& t = *(TrainEvaluation*)ctx;
-  const urgym_sac_evaluation& E = *t.evaluation;
-  if (!eval_follows(*t.schedule, E.every, i)) return URGYM_OK;
-  const int rc = launch_policy_evaluation(t.call, E.first_eval_index + t.done, (int32_t)(E.first_record_slot + t.done), t.s);
-  t.done++;
-  if (!rc) {
-    HIP_TRY(t.h, hipSetDevice(t.h->device));  // the same device: what the launches of the next iteration expect to be current
-    return rc;
-  }
-  return failf(t.h, rc, "%s: iteration %d, evaluation: %.150s", t.who, i, t.call.eh->err);
-}
-
-// ---- training-episode statistics (include/urgym.h, urgym_monitor_fold ... urgym_sac_train_monitored; DESIGN.md section 19).  As above
-// each entry point is a checking half, which launches nothing and fills the launch struct of urgym_monitor.h, and a launching half,
-// which refuses nothing.
-
-// the six state pointers: all given, the 8-byte ones aligned
-int check_monitor_state(Handle* h, const urgym_monitor_state* state, const char* who) {
-  if (!state) return fail_in(h, URGYM_ERR_ARG, who, "null monitor state");
-  const urgym_monitor_state& m = *state;
-  const LearnerPointer required[] = {{"running_return", m.running_return}, {"running_length", m.running_length}, {"sum_return", m.sum_return},
-                                     {"sum_length", m.sum_length},         {"episodes", m.episodes},             {"successes", m.successes}};
-  for (const LearnerPointer& r : required)
-    if (!r.p) return failf(h, URGYM_ERR_ARG, "%s: urgym_monitor_state.%s is null", who, r.name);
-  if ((uintptr_t)m.running_return % 8 != 0 || (uintptr_t)m.sum_return % 8 != 0 || (uintptr_t)m.sum_length % 8 != 0)
-    return fail_in(h, URGYM_ERR_ARG, who, "running_return, sum_return and sum_length must be 8-byte aligned");
-  return URGYM_OK;
-}
-
-int check_monitor_fold(Handle* h, const urgym_monitor_state* state, const urgym_replay_ring* ring, int first_slot, int num_steps, const char* who, MonitorFoldCall* out) {
-  if (int rc = check_monitor_state(h, state, who)) return rc;
-  if (int rc = check_fold_ring(h, ring, first_slot, num_steps, who)) return rc;
-  *out = MonitorFoldCall{h->cfg.num_envs, ring->capacity_steps, first_slot, num_steps, *state, ring->reward, ring->terminated, ring->truncated, ring->is_success};
-  return URGYM_OK;
-}
-
-int check_monitor_stats(Handle* h, const urgym_monitor_state* state, urgym_monitor_record* record, int64_t iteration, int clear, const char* who, MonitorStatsCall* out) {
-  static_assert(sizeof(urgym_monitor_record) == 72 && alignof(urgym_monitor_record) == 8, "include/urgym.h");
-  if (int rc = check_monitor_state(h, state, who)) return rc;
-  if (!record) return fail_in(h, URGYM_ERR_ARG, who, "null record");
-  if ((uintptr_t)record % 8 != 0) return fail_in(h, URGYM_ERR_ARG, who, "record must be 8-byte aligned");
-  *out = MonitorStatsCall{h->cfg.num_envs, clear, iteration, *state, record};
-  return URGYM_OK;
-}
-
-// urgym_sac_train_monitored's hooks into sac_train_body: the monitor's half first, then the evaluation's existing half where one is given
-struct TrainMonitoring {
-  Handle* h;
-  const urgym_sac_learner* learner;
-  const urgym_sac_schedule* schedule;
-  const urgym_sac_monitoring* monitoring;
-  hipStream_t s;
-  MonitorFoldCall fold;    // first_slot moves per iteration
-  MonitorStatsCall stats;  // record and iteration move per record
-  int64_t done;            // records launched so far
-  TrainEvaluation* evaluation;  // null = none
-  const char* who;  // the entry point that runs them: urgym_sac_train_monitored, or urgym_sac_train_nstep
-};
-
-const char* const TRAIN_MONITORED = "urgym_sac_train_monitored";
-
-// runs after every check of the training body (so the learner and the schedule are sound) and before its first launch
-int train_monitoring_check(void* ctx) {
-  TrainMonitoring& t = *(TrainMonitoring*)ctx;
-  const char* who = t.who;
-  Handle* h = t.h;
-  const urgym_sac_monitoring& M = *t.monitoring;
-  const urgym_sac_schedule& S = *t.schedule;
-  if (M.reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_monitoring.reserved0 must be 0");
-  if (const char* what = monitor_schedule_refusal(S, M.log_every, M.first_iteration, M.first_record, M.record_capacity)) return fail_in(h, URGYM_ERR_ARG, who, what);
-  // the fold's checks with the first iteration's slots (a call that collects nothing folds nothing: its state is still checked below)
-  if (S.steps_per_iteration > 0)
-    if (int rc = check_monitor_fold(h, &M.state, &t.learner->ring, S.first_slot, S.steps_per_iteration, who, &t.fold)) return rc;
-  // the statistics' checks, on the first record (every record has its alignment: it is a multiple of 8 bytes); without a record point
-  // the pointer may be anything
-  const bool records = monitor_record_count(M.first_iteration, M.log_every, S.num_iterations) > 0;
-  urgym_monitor_record unused;
-  if (int rc = check_monitor_stats(h, &M.state, records ? M.records : &unused, 0, M.clear, who, &t.stats)) return rc;
-  if (t.evaluation) return train_evaluation_check(t.evaluation);
-  return URGYM_OK;
-}
-
-int train_monitoring_after(void* ctx, int i) {
-  TrainMonitoring& t = *(TrainMonitoring*)ctx;
-  const urgym_sac_monitoring& M = *t.monitoring;
-  const urgym_sac_schedule& S = *t.schedule;
-  if (S.steps_per_iteration > 0) {
-    t.fold.first_slot = sac_schedule_iteration(S, i).collect_first_slot;
-    monitor_fold_launch(t.fold, t.s);
-    if (int rc = train_stage(t.h, t.who, i, "monitor_fold")) return rc;
-  }
-  if (monitor_record_follows(M.first_iteration, M.log_every, i)) {
-    t.stats.record = M.records + M.first_record + t.done;
-    t.stats.iteration = M.first_iteration + i + 1;
-    t.done++;
-    monitor_stats_launch(t.stats, t.s);
-    if (int rc = train_stage(t.h, t.who, i, "monitor_stats")) return rc;
-  }
-  if (t.evaluation) return train_evaluation_after(t.evaluation, i);
-  return URGYM_OK;
-}
+// what urgym_sac_train_clipped and urgym_sac_train_normalized refuse before the driver: the body takes the three gathers' options as given
+const char* const ONE_GATHER = "at most one of nstep, prioritized and hindsight may be given (each has a gather of its own)";
 
 }  // namespace
 
 extern "C" {
 
-int urgym_eval_stats(void* handle, const urgym_eval_stats_args* args, void* stream) {
+// Each entry point: the null handle, its own required option, then the driver with what it was given.  TrainOptions' order is
+// {nstep, per, her, clip, norm, evaluation, monitoring}.
+
+int urgym_sac_train(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, void* stream) {
   Handle* h = (Handle*)handle;
   if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
-  EvalStatsCall c;
-  if (int rc = check_eval_stats(h, args, "urgym_eval_stats", &c)) return rc;
-  HIP_TRY(h, hipSetDevice(h->device));
-  eval_stats_launch(c, (hipStream_t)stream);
-  return launched(h);
-}
-
-int urgym_actor_snapshot(void* handle, const urgym_actor_snapshot_args* args, void* stream) {
-  Handle* h = (Handle*)handle;
-  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
-  ActorSnapshotCall c;
-  if (int rc = check_actor_snapshot(h, args, "urgym_actor_snapshot", &c)) return rc;
-  HIP_TRY(h, hipSetDevice(h->device));
-  actor_snapshot_launch(c, (hipStream_t)stream);
-  return launched(h);
-}
-
-int urgym_policy_evaluate(void* eval_handle, const urgym_policy_evaluation* evaluation, int64_t eval_index, int32_t record_slot, void* stream) {
-  const char* who = "urgym_policy_evaluate";
-  Handle* eh = (Handle*)eval_handle;
-  if (!eh) return fail(nullptr, URGYM_ERR_ARG, "null handle");
-  PolicyEvaluation c;
-  if (int rc = check_policy_evaluation(eh, eh, evaluation, who, &c)) return rc;
-  if (int rc = check_evaluation_slot(eh, *evaluation, eval_index, record_slot, who)) return rc;
-  return launch_policy_evaluation(c, eval_index, record_slot, (hipStream_t)stream);
+  return sac_train_body("urgym_sac_train", h, learner, schedule, (hipStream_t)stream, TrainOptions{});
 }
 
 int urgym_sac_train_evaluated(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_evaluation* evaluation, void* stream) {
+  const char* who = "urgym_sac_train_evaluated";
   Handle* h = (Handle*)handle;
   if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
-  if (!evaluation) return fail_in(h, URGYM_ERR_ARG, TRAIN_EVALUATED, "null evaluation");
-  TrainEvaluation t;
-  t.h = h, t.learner = learner, t.schedule = schedule, t.evaluation = evaluation, t.s = (hipStream_t)stream, t.done = 0, t.who = TRAIN_EVALUATED;
-  const TrainHooks hooks{train_evaluation_check, train_evaluation_after, &t};
-  return sac_train_body(TRAIN_EVALUATED, handle, learner, schedule, stream, &hooks);
-}
-
-int urgym_monitor_fold(void* handle, const urgym_monitor_state* state, const urgym_replay_ring* ring, int first_slot, int num_steps, void* stream) {
-  Handle* h = (Handle*)handle;
-  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
-  MonitorFoldCall c;
-  if (int rc = check_monitor_fold(h, state, ring, first_slot, num_steps, "urgym_monitor_fold", &c)) return rc;
-  HIP_TRY(h, hipSetDevice(h->device));
-  monitor_fold_launch(c, (hipStream_t)stream);
-  return launched(h);
-}
-
-int urgym_monitor_stats(void* handle, const urgym_monitor_state* state, urgym_monitor_record* record, int64_t iteration, int clear, void* stream) {
-  Handle* h = (Handle*)handle;
-  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
-  MonitorStatsCall c;
-  if (int rc = check_monitor_stats(h, state, record, iteration, clear, "urgym_monitor_stats", &c)) return rc;
-  HIP_TRY(h, hipSetDevice(h->device));
-  monitor_stats_launch(c, (hipStream_t)stream);
-  return launched(h);
+  if (!evaluation) return fail_in(h, URGYM_ERR_ARG, who, "null evaluation");
+  return sac_train_body(who, h, learner, schedule, (hipStream_t)stream, TrainOptions{nullptr, nullptr, nullptr, nullptr, nullptr, evaluation, nullptr});
 }
 
 int urgym_sac_train_monitored(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring, void* stream) {
+  const char* who = "urgym_sac_train_monitored";
   Handle* h = (Handle*)handle;
   if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
-  if (!monitoring) return fail_in(h, URGYM_ERR_ARG, TRAIN_MONITORED, "null monitoring");
-  TrainEvaluation e;
-  e.h = h, e.learner = learner, e.schedule = schedule, e.evaluation = evaluation_or_NULL, e.s = (hipStream_t)stream, e.done = 0, e.who = TRAIN_MONITORED;
-  TrainMonitoring t;
-  t.h = h, t.learner = learner, t.schedule = schedule, t.monitoring = monitoring, t.s = (hipStream_t)stream, t.done = 0;
-  t.evaluation = evaluation_or_NULL ? &e : nullptr, t.who = TRAIN_MONITORED;
-  const TrainHooks hooks{train_monitoring_check, train_monitoring_after, &t};
-  return sac_train_body(TRAIN_MONITORED, handle, learner, schedule, stream, &hooks);
+  if (!monitoring) return fail_in(h, URGYM_ERR_ARG, who, "null monitoring");
+  return sac_train_body(who, h, learner, schedule, (hipStream_t)stream, TrainOptions{nullptr, nullptr, nullptr, nullptr, nullptr, evaluation_or_NULL, monitoring});
 }
 
 int urgym_sac_train_nstep(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_nstep* nstep, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream) {
@@ -2138,20 +2219,7 @@ int urgym_sac_train_nstep(void* handle, const urgym_sac_learner* learner, const 
   Handle* h = (Handle*)handle;
   if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
   if (!nstep) return fail_in(h, URGYM_ERR_ARG, who, "null nstep");
-  TrainEvaluation e;
-  e.h = h, e.learner = learner, e.schedule = schedule, e.evaluation = evaluation_or_NULL, e.s = (hipStream_t)stream, e.done = 0, e.who = who;
-  TrainMonitoring t;
-  t.h = h, t.learner = learner, t.schedule = schedule, t.monitoring = monitoring_or_NULL, t.s = (hipStream_t)stream, t.done = 0;
-  t.evaluation = evaluation_or_NULL ? &e : nullptr, t.who = who;
-  if (monitoring_or_NULL) {
-    const TrainHooks hooks{train_monitoring_check, train_monitoring_after, &t};
-    return sac_train_body(who, handle, learner, schedule, stream, &hooks, nstep);
-  }
-  if (evaluation_or_NULL) {
-    const TrainHooks hooks{train_evaluation_check, train_evaluation_after, &e};
-    return sac_train_body(who, handle, learner, schedule, stream, &hooks, nstep);
-  }
-  return sac_train_body(who, handle, learner, schedule, stream, nullptr, nstep);
+  return sac_train_body(who, h, learner, schedule, (hipStream_t)stream, TrainOptions{nstep, nullptr, nullptr, nullptr, nullptr, evaluation_or_NULL, monitoring_or_NULL});
 }
 
 int urgym_sac_train_prioritized(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_prioritized* prioritized, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream) {
@@ -2159,20 +2227,7 @@ int urgym_sac_train_prioritized(void* handle, const urgym_sac_learner* learner, 
   Handle* h = (Handle*)handle;
   if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
   if (!prioritized) return fail_in(h, URGYM_ERR_ARG, who, "null prioritized");
-  TrainEvaluation e;
-  e.h = h, e.learner = learner, e.schedule = schedule, e.evaluation = evaluation_or_NULL, e.s = (hipStream_t)stream, e.done = 0, e.who = who;
-  TrainMonitoring t;
-  t.h = h, t.learner = learner, t.schedule = schedule, t.monitoring = monitoring_or_NULL, t.s = (hipStream_t)stream, t.done = 0;
-  t.evaluation = evaluation_or_NULL ? &e : nullptr, t.who = who;
-  if (monitoring_or_NULL) {
-    const TrainHooks hooks{train_monitoring_check, train_monitoring_after, &t};
-    return sac_train_body(who, handle, learner, schedule, stream, &hooks, nullptr, prioritized);
-  }
-  if (evaluation_or_NULL) {
-    const TrainHooks hooks{train_evaluation_check, train_evaluation_after, &e};
-    return sac_train_body(who, handle, learner, schedule, stream, &hooks, nullptr, prioritized);
-  }
-  return sac_train_body(who, handle, learner, schedule, stream, nullptr, nullptr, prioritized);
+  return sac_train_body(who, h, learner, schedule, (hipStream_t)stream, TrainOptions{nullptr, prioritized, nullptr, nullptr, nullptr, evaluation_or_NULL, monitoring_or_NULL});
 }
 
 int urgym_sac_train_hindsight(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_hindsight* hindsight, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream) {
@@ -2180,20 +2235,7 @@ int urgym_sac_train_hindsight(void* handle, const urgym_sac_learner* learner, co
   Handle* h = (Handle*)handle;
   if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
   if (!hindsight) return fail_in(h, URGYM_ERR_ARG, who, "null hindsight");
-  TrainEvaluation e;
-  e.h = h, e.learner = learner, e.schedule = schedule, e.evaluation = evaluation_or_NULL, e.s = (hipStream_t)stream, e.done = 0, e.who = who;
-  TrainMonitoring t;
-  t.h = h, t.learner = learner, t.schedule = schedule, t.monitoring = monitoring_or_NULL, t.s = (hipStream_t)stream, t.done = 0;
-  t.evaluation = evaluation_or_NULL ? &e : nullptr, t.who = who;
-  if (monitoring_or_NULL) {
-    const TrainHooks hooks{train_monitoring_check, train_monitoring_after, &t};
-    return sac_train_body(who, handle, learner, schedule, stream, &hooks, nullptr, nullptr, hindsight);
-  }
-  if (evaluation_or_NULL) {
-    const TrainHooks hooks{train_evaluation_check, train_evaluation_after, &e};
-    return sac_train_body(who, handle, learner, schedule, stream, &hooks, nullptr, nullptr, hindsight);
-  }
-  return sac_train_body(who, handle, learner, schedule, stream, nullptr, nullptr, nullptr, hindsight);
+  return sac_train_body(who, h, learner, schedule, (hipStream_t)stream, TrainOptions{nullptr, nullptr, hindsight, nullptr, nullptr, evaluation_or_NULL, monitoring_or_NULL});
 }
 
 int urgym_sac_train_clipped(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_clipping* clipping, const urgym_sac_nstep* nstep_or_NULL, const urgym_sac_prioritized* prioritized_or_NULL, const urgym_sac_hindsight* hindsight_or_NULL, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream) {
@@ -2201,132 +2243,8 @@ int urgym_sac_train_clipped(void* handle, const urgym_sac_learner* learner, cons
   Handle* h = (Handle*)handle;
   if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
   if (!clipping) return fail_in(h, URGYM_ERR_ARG, who, "null clipping");
-  if ((nstep_or_NULL != nullptr) + (prioritized_or_NULL != nullptr) + (hindsight_or_NULL != nullptr) > 1)
-    return fail_in(h, URGYM_ERR_ARG, who, "at most one of nstep, prioritized and hindsight may be given (each has a gather of its own)");
-  TrainEvaluation e;
-  e.h = h, e.learner = learner, e.schedule = schedule, e.evaluation = evaluation_or_NULL, e.s = (hipStream_t)stream, e.done = 0, e.who = who;
-  TrainMonitoring t;
-  t.h = h, t.learner = learner, t.schedule = schedule, t.monitoring = monitoring_or_NULL, t.s = (hipStream_t)stream, t.done = 0;
-  t.evaluation = evaluation_or_NULL ? &e : nullptr, t.who = who;
-  if (monitoring_or_NULL) {
-    const TrainHooks hooks{train_monitoring_check, train_monitoring_after, &t};
-    return sac_train_body(who, handle, learner, schedule, stream, &hooks, nstep_or_NULL, prioritized_or_NULL, hindsight_or_NULL, clipping);
-  }
-  if (evaluation_or_NULL) {
-    const TrainHooks hooks{train_evaluation_check, train_evaluation_after, &e};
-    return sac_train_body(who, handle, learner, schedule, stream, &hooks, nstep_or_NULL, prioritized_or_NULL, hindsight_or_NULL, clipping);
-  }
-  return sac_train_body(who, handle, learner, schedule, stream, nullptr, nstep_or_NULL, prioritized_or_NULL, hindsight_or_NULL, clipping);
-}
-
-}  // extern "C"
-
-namespace {
-
-// the twelve pointers of a state that is read or written without its running_ret
-int check_norm_state12(Handle* h, const urgym_norm_state* st, const char* who, const char* what) {
-  if (!st) return failf(h, URGYM_ERR_ARG, "%s: null %s", who, what);
-  const void* const p[12] = {st->observation_mean,   st->observation_var,  st->observation_count,  st->achieved_goal_mean, st->achieved_goal_var, st->achieved_goal_count,
-                             st->desired_goal_mean,  st->desired_goal_var, st->desired_goal_count, st->ret_mean,           st->ret_var,           st->ret_count};
-  for (const void* q : p)
-    if (!q || (uintptr_t)q % 8 != 0) return failf(h, URGYM_ERR_ARG, "%s: a pointer of %s is null or not 8-byte aligned (mean, var and count of the four groups)", who, what);
-  return URGYM_OK;
-}
-
-int check_norm_snapshot(Handle* h, const urgym_norm_state* source, const urgym_norm_state* destination, const int32_t* when, const char* who, NormSnapshotCall* out) {
-  if (int rc = check_norm_state12(h, source, who, "source state")) return rc;
-  if (int rc = check_norm_state12(h, destination, who, "destination state")) return rc;
-  if (actor_features(h) + 1 > NORM_FEATURE_LANES) return fail_in(h, URGYM_ERR_ARG, who, "the kernels are built for at most 63 features in all");
-  memset(out, 0, sizeof(*out));
-  out->dim[0] = h->obs_dim, out->dim[1] = h->goal_dim, out->dim[2] = h->goal_dim;
-  out->src = *source, out->dst = *destination, out->when = when;
-  return URGYM_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int urgym_norm_snapshot(void* handle, const urgym_norm_state* source, const urgym_norm_state* destination, const int32_t* when, void* stream) {
-  Handle* h = (Handle*)handle;
-  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
-  NormSnapshotCall c;
-  if (int rc = check_norm_snapshot(h, source, destination, when, "urgym_norm_snapshot", &c)) return rc;
-  HIP_TRY(h, hipSetDevice(h->device));
-  norm_snapshot_launch(c, (hipStream_t)stream);
-  return launched(h);
-}
-
-int urgym_policy_evaluate_normalized(void* eval_handle, const urgym_policy_evaluation* evaluation, const urgym_normalization* normalization, int64_t eval_index, int32_t record_slot, void* stream) {
-  const char* who = "urgym_policy_evaluate_normalized";
-  Handle* eh = (Handle*)eval_handle;
-  if (!eh) return fail(nullptr, URGYM_ERR_ARG, "null handle");
-  PolicyEvaluation c;
-  if (int rc = check_policy_evaluation(eh, eh, evaluation, who, &c)) return rc;
-  if (int rc = check_evaluation_slot(eh, *evaluation, eval_index, record_slot, who)) return rc;
-  if (int rc = check_evaluation_normalization(eh, eh, normalization, who, &c)) return rc;
-  return launch_policy_evaluation(c, eval_index, record_slot, (hipStream_t)stream);
-}
-
-int urgym_norm_workspace(void* handle, int num_steps, uint64_t* bytes) {
-  const char* who = "urgym_norm_workspace";
-  Handle* h = (Handle*)handle;
-  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
-  if (!bytes) return fail_in(h, URGYM_ERR_ARG, who, "null bytes");
-  if (num_steps <= 0) return fail_in(h, URGYM_ERR_ARG, who, "num_steps must be positive");
-  *bytes = norm_workspace_doubles(h->cfg.num_envs, actor_features(h), num_steps) * sizeof(double);
-  return URGYM_OK;
-}
-
-int urgym_norm_fold(void* handle, const urgym_normalization* norm, const urgym_replay_ring* ring, int first_slot, int num_steps, void* stream) {
-  Handle* h = (Handle*)handle;
-  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
-  NormFoldCall c;
-  if (int rc = check_norm_fold(h, norm, ring, first_slot, num_steps, "urgym_norm_fold", &c)) return rc;
-  if (norm->training == 0) return URGYM_OK;
-  HIP_TRY(h, hipSetDevice(h->device));
-  norm_fold_launch(c, (hipStream_t)stream);
-  return launched(h);
-}
-
-int urgym_norm_rows(void* handle, const urgym_normalization* norm, const urgym_norm_rows_args* rows, int count, void* stream) {
-  Handle* h = (Handle*)handle;
-  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
-  NormApplyCall c;
-  if (int rc = check_norm_rows(h, norm, rows, count, "urgym_norm_rows", &c)) return rc;
-  HIP_TRY(h, hipSetDevice(h->device));
-  norm_apply_launch(c, (hipStream_t)stream);
-  return launched(h);
-}
-
-int urgym_norm_batch(void* handle, const urgym_normalization* norm, const urgym_replay_batch* batch, int count, void* stream) {
-  Handle* h = (Handle*)handle;
-  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
-  NormApplyCall c;
-  if (int rc = check_norm_batch(h, norm, batch, count, "urgym_norm_batch", &c)) return rc;
-  if (c.segments == 0) return URGYM_OK;
-  HIP_TRY(h, hipSetDevice(h->device));
-  norm_apply_launch(c, (hipStream_t)stream);
-  return launched(h);
-}
-
-int urgym_rollout_collect_normalized(void* handle, void* actor, const urgym_sampling* how, int num_steps, const urgym_replay_ring* ring, int first_slot, const urgym_normalization* norm, void* stream) {
-  const char* who = "urgym_rollout_collect_normalized";
-  Handle* h = (Handle*)handle;
-  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
-  Actor* a = nullptr;
-  if (int rc = check_collect(h, actor, how, num_steps, ring, first_slot, who, &a)) return rc;
-  if (int rc = check_normalization(h, norm, who)) return rc;
-  if (norm->norm_obs == 0) return rollout(h, a, how, num_steps, RolloutSinks{nullptr, nullptr, ring, first_slot}, (hipStream_t)stream);
-  if (!norm->scratch) return fail_in(h, URGYM_ERR_ARG, who, "urgym_normalization.scratch is null");
-  const size_t n = (size_t)h->cfg.num_envs;
-  float* const obs = norm->scratch;
-  float* const ach = obs + n * (size_t)h->obs_dim;
-  float* const des = ach + n * (size_t)h->goal_dim;
-  const urgym_norm_rows_args rows{h->buf.observation, h->buf.achieved_goal, h->buf.desired_goal, obs, ach, des};
-  NormApplyCall c;
-  if (int rc = check_norm_rows(h, norm, &rows, h->cfg.num_envs, who, &c)) return rc;
-  return rollout(h, a, how, num_steps, RolloutSinks{nullptr, nullptr, ring, first_slot}, (hipStream_t)stream, &c);
+  if ((nstep_or_NULL != nullptr) + (prioritized_or_NULL != nullptr) + (hindsight_or_NULL != nullptr) > 1) return fail_in(h, URGYM_ERR_ARG, who, ONE_GATHER);
+  return sac_train_body(who, h, learner, schedule, (hipStream_t)stream, TrainOptions{nstep_or_NULL, prioritized_or_NULL, hindsight_or_NULL, clipping, nullptr, evaluation_or_NULL, monitoring_or_NULL});
 }
 
 int urgym_sac_train_normalized(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_normalization* normalization, const urgym_sac_clipping* clipping_or_NULL, const urgym_sac_nstep* nstep_or_NULL, const urgym_sac_prioritized* prioritized_or_NULL, const urgym_sac_hindsight* hindsight_or_NULL, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream) {
@@ -2334,23 +2252,8 @@ int urgym_sac_train_normalized(void* handle, const urgym_sac_learner* learner, c
   Handle* h = (Handle*)handle;
   if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
   if (!normalization) return fail_in(h, URGYM_ERR_ARG, who, "null normalization");
-  if ((nstep_or_NULL != nullptr) + (prioritized_or_NULL != nullptr) + (hindsight_or_NULL != nullptr) > 1)
-    return fail_in(h, URGYM_ERR_ARG, who, "at most one of nstep, prioritized and hindsight may be given (each has a gather of its own)");
-  TrainEvaluation e;
-  e.h = h, e.learner = learner, e.schedule = schedule, e.evaluation = evaluation_or_NULL, e.s = (hipStream_t)stream, e.done = 0, e.who = who;
-  e.norm = normalization;
-  TrainMonitoring t;
-  t.h = h, t.learner = learner, t.schedule = schedule, t.monitoring = monitoring_or_NULL, t.s = (hipStream_t)stream, t.done = 0;
-  t.evaluation = evaluation_or_NULL ? &e : nullptr, t.who = who;
-  if (monitoring_or_NULL) {
-    const TrainHooks hooks{train_monitoring_check, train_monitoring_after, &t};
-    return sac_train_body(who, handle, learner, schedule, stream, &hooks, nstep_or_NULL, prioritized_or_NULL, hindsight_or_NULL, clipping_or_NULL, normalization);
-  }
-  if (evaluation_or_NULL) {
-    const TrainHooks hooks{train_evaluation_check, train_evaluation_after, &e};
-    return sac_train_body(who, handle, learner, schedule, stream, &hooks, nstep_or_NULL, prioritized_or_NULL, hindsight_or_NULL, clipping_or_NULL, normalization);
-  }
-  return sac_train_body(who, handle, learner, schedule, stream, nullptr, nstep_or_NULL, prioritized_or_NULL, hindsight_or_NULL, clipping_or_NULL, normalization);
+  if ((nstep_or_NULL != nullptr) + (prioritized_or_NULL != nullptr) + (hindsight_or_NULL != nullptr) > 1) return fail_in(h, URGYM_ERR_ARG, who, ONE_GATHER);
+  return sac_train_body(who, h, learner, schedule, (hipStream_t)stream, TrainOptions{nstep_or_NULL, prioritized_or_NULL, hindsight_or_NULL, clipping_or_NULL, normalization, evaluation_or_NULL, monitoring_or_NULL});
 }
 
 }  // extern "C"

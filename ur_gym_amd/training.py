@@ -556,28 +556,26 @@ class SACLearner:
         holds after its collection (``evaluation.warmup_iterations``).  Advances ``env_steps``, ``draw``, ``adam_state["step"]``,
         ``replay.cursor`` and ``replay.filled``; ``last_update`` refers to the scratch the last update used.  Returns the three
         losses as device tensors of one entry per update (not synchronised).  ``steps_per_iteration=0, iterations=1`` is
-        `updates_per_iteration` updates in one call.
+        `updates_per_iteration` updates in one call.  Whatever is given below, it stays ONE native call (``env.sac_train`` picks the
+        entry point).
 
-        With `evaluation` (an ``evaluation.DeviceEvaluation`` on a second environment) and `eval_every` the ONE native call is
-        urgym_sac_train_evaluated: after every iteration in which the update count (``adam_state["step"]``) passes a multiple of
-        `eval_every`, the actor as it then stands is evaluated (``evaluation.evaluate`` of ``self.actor.tensors()``, bit for bit)
-        without leaving the call; `evaluation`'s counters advance.  Both or neither: one alone raises ValueError.
+        With `evaluation` (an ``evaluation.DeviceEvaluation`` on a second environment) and `eval_every`: after every iteration in which
+        the update count (``adam_state["step"]``) passes a multiple of `eval_every`, the actor as it then stands is evaluated
+        (``evaluation.evaluate`` of ``self.actor.tensors()``, bit for bit) without leaving the call; `evaluation`'s counters advance.
+        Both or neither: one alone raises ValueError.
 
-        With `monitor` (an ``evaluation.DeviceMonitor`` of the training environment) and `log_every` the ONE native call is
-        urgym_sac_train_monitored, with the evaluations if those are given too: every iteration's collection is folded into the
-        monitor (``collect(..., monitor=)``, bit for bit, warm-up iterations included), and after every iteration at which
-        ``monitor.iterations`` reaches a multiple of `log_every` the finished episodes go to the monitor's next record
+        With `monitor` (an ``evaluation.DeviceMonitor`` of the training environment) and `log_every`: every iteration's collection is
+        folded into the monitor (``collect(..., monitor=)``, bit for bit, warm-up iterations included), and after every iteration at
+        which ``monitor.iterations`` reaches a multiple of `log_every` the finished episodes go to the monitor's next record
         (``monitor.record(monitor.iterations)``).  ``monitor.iterations`` and ``monitor.count`` advance, so that split calls place
         records where one call would.  Both or neither: one alone raises ValueError.
 
-        With ``n_steps`` > 1 the ONE native call is urgym_sac_train_nstep, with the evaluations and the monitor where given.  With
-        ``prioritized`` it is urgym_sac_train_prioritized on a ``DevicePrioritizedReplay``, the same way: every collection is followed
-        by the fill of its slots, every update is ``update``'s seventeen launches.  With ``hindsight`` it is urgym_sac_train_hindsight:
-        the thirteen launches with the gather of ``DeviceReplay.sample_hindsight``.  With ``max_grad_norm`` it is
-        urgym_sac_train_clipped with whichever of those apply: two more launches per update, and the result also holds
-        ``critic_grad_norm`` and ``actor_grad_norm``, one entry per update like the losses.  With ``normalize`` it is
-        urgym_sac_train_normalized with whichever of those apply: the normalized collection, one fold of the statistics per iteration
-        and one ``norm_batch`` per update; not together with `evaluation` unless ``norm_obs`` is off."""
+        With ``n_steps`` > 1 every update is the multi-step one.  With ``prioritized``, on a ``DevicePrioritizedReplay``, every
+        collection is followed by the fill of its slots and every update is ``update``'s seventeen launches.  With ``hindsight`` an
+        update is the thirteen launches with the gather of ``DeviceReplay.sample_hindsight``.  With ``max_grad_norm``: two more
+        launches per update, and the result also holds ``critic_grad_norm`` and ``actor_grad_norm``, one entry per update like the
+        losses.  With ``normalize``: the normalized collection, one fold of the statistics per iteration and one ``norm_batch`` per
+        update; not together with `evaluation` unless ``norm_obs`` is off."""
         from .evaluation import warmup_iterations
 
         if (evaluation is None) != (eval_every is None):

@@ -49,6 +49,27 @@ except Exception:  # pragma: no cover - exercised when gymnasium is absent
 
 _TORCH_DTYPE = {C.c_double: torch.float64, C.c_float: torch.float32, C.c_int32: torch.int32, C.c_uint8: torch.uint8}
 
+# The training call's entry points (include/urgym.h), in the order ``sac_train`` tries them: (symbol, the option that selects it, the
+# options it takes between ``learner, schedule`` and ``stream``, in the order of its signature).  The last row takes none.
+_SAC_TRAIN_ENTRIES = (
+    ("urgym_sac_train_normalized", "normalizer", ("normalizer", "clipping", "nstep", "prioritized", "hindsight", "evaluation", "monitor")),
+    ("urgym_sac_train_clipped", "clipping", ("clipping", "nstep", "prioritized", "hindsight", "evaluation", "monitor")),
+    ("urgym_sac_train_hindsight", "hindsight", ("hindsight", "evaluation", "monitor")),
+    ("urgym_sac_train_prioritized", "prioritized", ("prioritized", "evaluation", "monitor")),
+    ("urgym_sac_train_nstep", "nstep", ("nstep", "evaluation", "monitor")),
+    ("urgym_sac_train_monitored", "monitor", ("evaluation", "monitor")),
+    ("urgym_sac_train_evaluated", "evaluation", ("evaluation",)),
+    ("urgym_sac_train", None, ()),
+)
+
+
+def _sac_train_entry(present):
+    """(symbol, option names) of the entry point that serves a call with the options in `present` (any container of names out of
+    evaluation, monitor, nstep, prioritized, hindsight, clipping, normalizer): the first row of ``_SAC_TRAIN_ENTRIES`` whose option is given."""
+    for symbol, selects, options in _SAC_TRAIN_ENTRIES:
+        if selects is None or selects in present:
+            return symbol, options
+
 
 class UR5ReachVectorEnv:
     """N independent UR5{Ori,Obs,Dyn}Reach-v1 environments stepped by one fused kernel launch.
@@ -873,40 +894,37 @@ class UR5ReachVectorEnv:
         cursor and fill level, the draw counters and the step count, and advances them.  On torch's current stream; nothing is
         synchronised, nothing is converted.  Returns the number of updates.
 
+        The options combine freely but for the three gathers (`nstep`, `prioritized`, `hindsight`: at most one); an option left out
+        changes nothing.  Which urgym_sac_train_* entry point serves the call is ``_sac_train_entry``'s table.
+
         With `evaluation` (an ``evaluation.DeviceEvaluation`` on a SECOND environment of this device) and `eval_every` (updates between
-        evaluations) the call is urgym_sac_train_evaluated: the same launches with an evaluation of the learner's actor parameters
-        after every iteration in which the update count passes a multiple of `eval_every` (``evaluation.evaluation_points``), into
-        `evaluation`'s next records; its counters are advanced.  Without them nothing changes.
+        evaluations): an evaluation of the learner's actor parameters after every iteration in which the update count passes a
+        multiple of `eval_every` (``evaluation.evaluation_points``), into `evaluation`'s next records; its counters are advanced.
 
-        With `monitor` (an ``evaluation.DeviceMonitor`` of this environment) and `log_every` (iterations between records) the call is
-        urgym_sac_train_monitored: the same launches -- with the evaluations, if those are given too -- and after every iteration that
-        collects one ``monitor.fold`` of its slots, and after every iteration at which the monitor's iteration count reaches a multiple
-        of `log_every` one ``monitor.record`` (``evaluation.monitor_points``); the monitor's count and record cursor are advanced.
-        Without them nothing changes.
+        With `monitor` (an ``evaluation.DeviceMonitor`` of this environment) and `log_every` (iterations between records): after every
+        iteration that collects one ``monitor.fold`` of its slots, and after every iteration at which the monitor's iteration count
+        reaches a multiple of `log_every` one ``monitor.record`` (``evaluation.monitor_points``); the monitor's count and record cursor
+        are advanced.
 
-        With `nstep` (a dict: ``n_steps`` in [2, 32] and the float32 [count] scratch tensors ``discount`` and ``q_min_next``) the call
-        is urgym_sac_train_nstep, with the evaluations and the monitor if those are given: every update gathers multi-step returns
-        (``DeviceReplay.sample_targets(n_steps=)``) and forms y by ``entropy_step_nstep``.  Without it nothing changes.
+        With `nstep` (a dict: ``n_steps`` in [2, 32] and the float32 [count] scratch tensors ``discount`` and ``q_min_next``): every
+        update gathers multi-step returns (``DeviceReplay.sample_targets(n_steps=)``) and forms y by ``entropy_step_nstep``.
 
         With `prioritized` (a dict: ``replay``, the ``DevicePrioritizedReplay`` the learner's ring belongs to, ``beta0``,
-        ``beta_steps``, and the scratch tensors of ``_abi.SAC_PRIORITIZED_SCRATCH`` and ``total``, float64 [1]) the call is
-        urgym_sac_train_prioritized, with the evaluations and the monitor if those are given: every collection is followed by the
-        fill of its slots and every update draws through the priorities and writes the new ones back.  Not together with `nstep`.
+        ``beta_steps``, and the scratch tensors of ``_abi.SAC_PRIORITIZED_SCRATCH`` and ``total``, float64 [1]): every collection is
+        followed by the fill of its slots and every update draws through the priorities and writes the new ones back.
 
-        With `hindsight` (a dict: ``n_sampled_goal``, ``strategy`` "future" or "final", ``horizon``) the call is
-        urgym_sac_train_hindsight, with the evaluations and the monitor if those are given: every update's gather is the one of
-        ``DeviceReplay.sample_hindsight``.  Not together with `nstep` or `prioritized`.
+        With `hindsight` (a dict: ``n_sampled_goal``, ``strategy`` "future" or "final", ``horizon``): every update's gather is the one
+        of ``DeviceReplay.sample_hindsight``.
 
         With `clipping` (a dict: ``max_grad_norm``, ``scale``, a float32 [2] scratch tensor, and ``critic_grad_norm`` and
-        ``actor_grad_norm``, float32 tensors of one entry per update of the call like the losses) the call is urgym_sac_train_clipped,
-        with whichever of the options above are given: every update runs ``critic_gradient_norm`` and ``actor_gradient_norm`` before
-        the two steps, which take the coefficients (``scale=``); update u writes the norms to entry u.  Without it nothing changes.
+        ``actor_grad_norm``, float32 tensors of one entry per update of the call like the losses): every update runs
+        ``critic_gradient_norm`` and ``actor_gradient_norm`` before the two steps, which take the coefficients (``scale=``); update u
+        writes the norms to entry u.
 
-        With `normalizer` (an ``evaluation.DeviceNormalizer`` of this environment) the call is urgym_sac_train_normalized, with
-        whichever of the options above are given: every collection is ``collect(..., normalizer=)`` followed by ``norm_fold`` of its
-        slots, and every update's gather is followed by ``norm_batch``.  An `evaluation` given with it must have been made with this
-        normalizer (``DeviceEvaluation(..., normalizer=)``): its evaluations are ``evaluation.evaluate``'s, on normalized rows, with the
-        statistics snapshot beside the best actor.  Without it nothing changes."""
+        With `normalizer` (an ``evaluation.DeviceNormalizer`` of this environment): every collection is ``collect(..., normalizer=)``
+        followed by ``norm_fold`` of its slots, and every update's gather is followed by ``norm_batch``.  An `evaluation` given with it
+        must have been made with this normalizer (``DeviceEvaluation(..., normalizer=)``): its evaluations are
+        ``evaluation.evaluate``'s, on normalized rows, with the statistics snapshot beside the best actor."""
         from .evaluation import DeviceEvaluation, DeviceMonitor, _her_arguments, evaluation_points, monitor_points, relabel_threshold, training_schedule
 
         who = "sac_train"
@@ -928,6 +946,7 @@ class UR5ReachVectorEnv:
         if (evaluation is None) != (eval_every is None):
             raise ValueError(f"{who}: evaluation and eval_every go together")
         points = []
+        given = {}  # option name -> its _abi struct, for the options that are given
         if evaluation is not None:
             if not isinstance(evaluation, DeviceEvaluation):
                 raise ValueError(f"{who}: evaluation must be a DeviceEvaluation")
@@ -935,7 +954,7 @@ class UR5ReachVectorEnv:
                 raise ValueError(f"{who}: the evaluation needs an environment of its own (an evaluation resets it); evaluation on the training env is not supported")
             if isinstance(eval_every, bool) or int(eval_every) != eval_every or not 1 <= int(eval_every) < 1 << 31:
                 raise ValueError(f"{who}: eval_every must be an integer in [1, 2^31), got {eval_every!r}")
-            E_ = _abi.SacEvaluation(evaluation.env._h, evaluation.struct(learner.actor_params), int(eval_every), evaluation.count, evaluation.count)
+            given["evaluation"] = _abi.SacEvaluation(evaluation.env._h, evaluation.struct(learner.actor_params), int(eval_every), evaluation.count, evaluation.count)
             if sched["first_step"] >= 1 and sched["num_iterations"] >= 1 and min(sched["updates_per_iteration"], sched["idle_iterations"]) >= 0:
                 points = evaluation_points(sched["first_step"], sched["num_iterations"], sched["updates_per_iteration"], sched["idle_iterations"], eval_every)
         if (monitor is None) != (log_every is None):
@@ -945,7 +964,7 @@ class UR5ReachVectorEnv:
                 raise ValueError(f"{who}: monitor must be a DeviceMonitor of this environment")
             if isinstance(log_every, bool) or int(log_every) != log_every or not 1 <= int(log_every) < 1 << 31:
                 raise ValueError(f"{who}: log_every must be an integer in [1, 2^31), got {log_every!r}")
-            M_ = monitor.struct(int(log_every))
+            given["monitor"] = monitor.struct(int(log_every))
             logged = monitor_points(monitor.iterations, max(0, sched["num_iterations"]), int(log_every))
         active = max(0, sched["num_iterations"] - max(0, sched["idle_iterations"]))
         updates = active * max(0, sched["updates_per_iteration"])
@@ -955,8 +974,8 @@ class UR5ReachVectorEnv:
             if isinstance(n_steps, bool) or int(n_steps) != n_steps or not 2 <= int(n_steps) <= _abi.REPLAY_NSTEP_MAX:
                 raise ValueError(f"{who}: nstep['n_steps'] must be an integer in [2, {_abi.REPLAY_NSTEP_MAX}], got {n_steps!r}")
             count = int(L.count)
-            N_ = _abi.SacNstep(int(n_steps), 0, self._float_ptr(who, "nstep['discount']", nstep["discount"], (count,)),
-                               self._float_ptr(who, "nstep['q_min_next']", nstep["q_min_next"], (count,)))
+            given["nstep"] = _abi.SacNstep(int(n_steps), 0, self._float_ptr(who, "nstep['discount']", nstep["discount"], (count,)),
+                                           self._float_ptr(who, "nstep['q_min_next']", nstep["q_min_next"], (count,)))
         if prioritized is not None:
             if nstep is not None:
                 raise ValueError(f"{who}: priorities together with multi-step returns are out of scope (the multi-step gather draws its own indices)")
@@ -964,8 +983,8 @@ class UR5ReachVectorEnv:
             total = prioritized["total"]
             if total.dtype != torch.float64 or tuple(total.shape) != (1,) or total.device != torch.device(self.device):
                 raise ValueError(f"{who}: prioritized['total'] must be a float64 [1] tensor on {self.device}")
-            P_ = _abi.SacPrioritized(priorities=rp.priorities_struct(), beta0=float(prioritized["beta0"]), beta_steps=int(prioritized["beta_steps"]),
-                                     alpha=rp.alpha, eps=rp.eps, total=C.cast(total.data_ptr(), C.POINTER(C.c_double)))
+            P_ = given["prioritized"] = _abi.SacPrioritized(priorities=rp.priorities_struct(), beta0=float(prioritized["beta0"]), beta_steps=int(prioritized["beta_steps"]),
+                                                            alpha=rp.alpha, eps=rp.eps, total=C.cast(total.data_ptr(), C.POINTER(C.c_double)))
             for name, shape in _abi.SAC_PRIORITIZED_SCRATCH:
                 setattr(P_, name, self._float_ptr(who, f"prioritized[{name!r}]", prioritized[name], shape(count)))
         if hindsight is not None:
@@ -973,7 +992,7 @@ class UR5ReachVectorEnv:
                 raise ValueError(f"{who}: hindsight together with multi-step returns or priorities is out of scope")
             if hindsight["strategy"] not in ("future", "final"):
                 raise ValueError(f"{who}: hindsight['strategy'] must be 'future' or 'final', got {hindsight['strategy']!r}")
-            H_ = _abi.SacHindsight(*_her_arguments(relabel_threshold(hindsight["n_sampled_goal"]), hindsight["strategy"], hindsight["horizon"]), 0)
+            given["hindsight"] = _abi.SacHindsight(*_her_arguments(relabel_threshold(hindsight["n_sampled_goal"]), hindsight["strategy"], hindsight["horizon"]), 0)
         for name, t in zip(_abi.SAC_LEARNER_LOSSES, (critic_loss, actor_loss, ent_coef_loss)):
             setattr(L, name, self._float_ptr(who, name, t, (updates,)))
         S = _abi.SacSchedule(*[sched[name] for name, _ in _abi.SacSchedule._fields_])
@@ -981,67 +1000,23 @@ class UR5ReachVectorEnv:
             max_grad_norm = float(clipping["max_grad_norm"])
             if not (self._finite32(max_grad_norm) and max_grad_norm > 0.0):
                 raise ValueError(f"{who}: clipping['max_grad_norm'] must be finite and positive, got {max_grad_norm}")
-            C_ = _abi.SacClipping(max_grad_norm, 0, self._float_ptr(who, "clipping['scale']", clipping["scale"], (2,)),
-                                  self._float_ptr(who, "clipping['critic_grad_norm']", clipping["critic_grad_norm"], (updates,)),
-                                  self._float_ptr(who, "clipping['actor_grad_norm']", clipping["actor_grad_norm"], (updates,)))
+            given["clipping"] = _abi.SacClipping(max_grad_norm, 0, self._float_ptr(who, "clipping['scale']", clipping["scale"], (2,)),
+                                                 self._float_ptr(who, "clipping['critic_grad_norm']", clipping["critic_grad_norm"], (updates,)),
+                                                 self._float_ptr(who, "clipping['actor_grad_norm']", clipping["actor_grad_norm"], (updates,)))
         if evaluation is not None and getattr(evaluation, "normalizer", None) is not normalizer:
             raise ValueError(f"{who}: the evaluation and the call must share one normalizer (DeviceEvaluation(..., normalizer=)), or have none")
         if normalizer is not None:
-            Z_ = self._normalization(who, normalizer)
+            given["normalizer"] = self._normalization(who, normalizer)
             if evaluation is not None:
-                Z_ = evaluation.norm_struct()
+                given["normalizer"] = evaluation.norm_struct()
             if sched["steps_per_iteration"] > normalizer.fold_steps:
                 raise ValueError(f"{who}: steps_per_iteration must be at most the normalizer's fold_steps = {normalizer.fold_steps} (its workspace)")
+        symbol, options = _sac_train_entry(given)
         try:
-            if normalizer is not None:
-                _native.check(self.lib.urgym_sac_train_normalized(self._h, C.byref(L), C.byref(S), C.byref(Z_), C.byref(C_) if clipping is not None else None,
-                                                                  C.byref(N_) if nstep is not None else None, C.byref(P_) if prioritized is not None else None,
-                                                                  C.byref(H_) if hindsight is not None else None, C.byref(E_) if evaluation is not None else None,
-                                                                  C.byref(M_) if monitor is not None else None, self._stream()), self._h)
-                if monitor is not None:
-                    monitor.advance(sched["num_iterations"], len(logged))
-                if evaluation is not None:
-                    evaluation.advance(len(points))
-            elif clipping is not None:
-                _native.check(self.lib.urgym_sac_train_clipped(self._h, C.byref(L), C.byref(S), C.byref(C_), C.byref(N_) if nstep is not None else None,
-                                                               C.byref(P_) if prioritized is not None else None, C.byref(H_) if hindsight is not None else None,
-                                                               C.byref(E_) if evaluation is not None else None,
-                                                               C.byref(M_) if monitor is not None else None, self._stream()), self._h)
-                if monitor is not None:
-                    monitor.advance(sched["num_iterations"], len(logged))
-                if evaluation is not None:
-                    evaluation.advance(len(points))
-            elif hindsight is not None:
-                _native.check(self.lib.urgym_sac_train_hindsight(self._h, C.byref(L), C.byref(S), C.byref(H_), C.byref(E_) if evaluation is not None else None,
-                                                                 C.byref(M_) if monitor is not None else None, self._stream()), self._h)
-                if monitor is not None:
-                    monitor.advance(sched["num_iterations"], len(logged))
-                if evaluation is not None:
-                    evaluation.advance(len(points))
-            elif prioritized is not None:
-                _native.check(self.lib.urgym_sac_train_prioritized(self._h, C.byref(L), C.byref(S), C.byref(P_), C.byref(E_) if evaluation is not None else None,
-                                                                   C.byref(M_) if monitor is not None else None, self._stream()), self._h)
-                if monitor is not None:
-                    monitor.advance(sched["num_iterations"], len(logged))
-                if evaluation is not None:
-                    evaluation.advance(len(points))
-            elif nstep is not None:
-                _native.check(self.lib.urgym_sac_train_nstep(self._h, C.byref(L), C.byref(S), C.byref(N_), C.byref(E_) if evaluation is not None else None,
-                                                             C.byref(M_) if monitor is not None else None, self._stream()), self._h)
-                if monitor is not None:
-                    monitor.advance(sched["num_iterations"], len(logged))
-                if evaluation is not None:
-                    evaluation.advance(len(points))
-            elif monitor is not None:
-                _native.check(self.lib.urgym_sac_train_monitored(self._h, C.byref(L), C.byref(S), C.byref(E_) if evaluation is not None else None,
-                                                                 C.byref(M_), self._stream()), self._h)
+            _native.check(getattr(self.lib, symbol)(self._h, C.byref(L), C.byref(S), *[C.byref(given[o]) if o in given else None for o in options], self._stream()), self._h)
+            if monitor is not None:
                 monitor.advance(sched["num_iterations"], len(logged))
-                if evaluation is not None:
-                    evaluation.advance(len(points))
-            elif evaluation is None:
-                _native.check(self.lib.urgym_sac_train(self._h, C.byref(L), C.byref(S), self._stream()), self._h)
-            else:
-                _native.check(self.lib.urgym_sac_train_evaluated(self._h, C.byref(L), C.byref(S), C.byref(E_), self._stream()), self._h)
+            if evaluation is not None:
                 evaluation.advance(len(points))
         finally:
             for name in _abi.SAC_LEARNER_LOSSES:  # the loss slots belong to this call alone
