@@ -1785,6 +1785,116 @@ int urgym_policy_evaluate_normalized(void* eval_handle, const urgym_policy_evalu
  * urgym_policy_evaluate_normalized with this normalization (its refusals: a NULL eval_scratch or best_state). */
 int urgym_sac_train_normalized(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_normalization* normalization, const urgym_sac_clipping* clipping_or_NULL, const urgym_sac_nstep* nstep_or_NULL, const urgym_sac_prioritized* prioritized_or_NULL, const urgym_sac_hindsight* hindsight_or_NULL, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream);
 
+/* ---- sampling-based MPC on the device: an MPPI planner (Williams et al., 2017) that plans with the step kernel itself (DESIGN.md
+ * section 26).  Added WITHIN ABI version 4 like everything since the sampling calls: no struct above changed, the new symbols
+ * (urgym_mppi_*) are found by lookup.  No existing kernel is touched: the planner's futures are ordinary environments of a second
+ * handle, stepped by urgym_step's own launches.
+ *
+ * Notation.  E source envs ("parents"), K samples per parent in [2, URGYM_MPPI_SAMPLES_MAX], H horizon steps in
+ * [1, URGYM_MPPI_HORIZON_MAX], I refinement iterations in [1, URGYM_MPPI_ITERATIONS_MAX].  The PLANNER is a handle of the same env
+ * kind and config with num_envs == E * K and auto_reset == 0; its env n = p * K + j is sample j of parent p (p = n / K, j = n - p * K).
+ * The SOURCE handle has num_envs == E.  Every array below is a DEVICE pointer owned by the caller; the library allocates nothing.
+ *
+ * THE FAN-OUT (urgym_mppi_fanout, one launch).  For every planner env n it copies parent p's column of every state field of
+ * urgym_buffers from the source's bound buffers (SoA [f][E]) into the planner's ([f][E * K]): q, goal, obst_start, obst_end, obst_pos,
+ * obst_quat, obst_vel (all 9 rows), link_dist, step_count, episode_id; and the rows of observation, achieved_goal, desired_goal (a Dyn
+ * step may read the row it finds).  Bytes only.  The planner's status is zeroed.  The planner thus inherits the parent's step_count:
+ * a time limit that falls inside the horizon truncates the sample there.
+ *
+ * THE SAMPLE (urgym_mppi_sample, one launch) writes actions[h][n][c] and eps[h][n][c], float32 [H][E * K][6].  Sample j = 0 is the
+ * nominal sequence: eps = 0.  Otherwise eps is Box-Muller exactly as the GAUSSIAN policy noise above states it (u1, u2, r, cos, sin;
+ * pairs p = 0, 1, 2 from the words w0 .. w5) on the words of Philox4x32-10 with key = (seed & 0xFFFFFFFF, seed >> 32) and
+ *   counter = (p, (i << 24) | (h << 16) | j, (uint32)draw, URGYM_MPPI_TAG | block),  block = 0, 1,
+ * i the refinement iteration.  URGYM_MPPI_TAG = 0x4D505000 meets none of 0x504F4C00 | b (policy noise), 0x52504C00 (replay),
+ * 0x50455200 (prioritized replay) or the reset sampler's 0 .. 4.  draw >= 2^32 is refused.  The action line, float32, one operation per
+ * line:
+ *   s = sigma * eps;  a = mean[h][p][c] + s;  action = fminf(fmaxf(a, -1), 1).
+ * The noise is a function of (seed, draw, i, p, j, h, c) only -- not of E, K or the launch geometry.
+ *
+ * THE SCORE (urgym_mppi_score, one launch after planner step h, one lane per planner env n, float64, one operation per line):
+ *   at h == 0 first:  ret = 0;  g = 1;  alive = 1;  end_step = H - 1;  success = 0;  collided = 0
+ *   where alive:      t = g * (double)reward[n];  ret = ret + t;  g = g * gamma;
+ *                     if (terminated[n] | truncated[n]) { alive = 0;  end_step = h;  success = is_success[n];  collided = collision[n]; }
+ * reward .. collision being the planner's bound outputs.  A NaN reward reaches that env's ret only.
+ *
+ * THE UPDATE (urgym_mppi_update, one launch: one workgroup of 1024 lanes per parent, lane j < K, float64, no atomics).  r_j = ret[pK + j].
+ *   rmax = the fmax over the FINITE r_j (a NaN or an infinity is passed over; -inf when none is finite)
+ *   none finite:  w_0 = 1, w_j = 0 otherwise.   else:  d = r_j - rmax;  x = d / lambda;  w_j = finite(r_j) ? exp(x) : 0
+ *   Z = THE ORDERED SUM (above, "SAC's entropy coefficient on the device") of w_j over j < K, float64 terms
+ *   for each (h, c):  S = the ordered sum of w_j * (double)actions[h][pK + j][c];  m = S / Z;  new_mean[h][p][c] = (float)m
+ *   Q = the ordered sum of w_j * w_j;  zz = Z * Z;  ess[p] = zz / Q
+ *   action_out[p][c] = new_mean[0][p][c];  best_return[p] = rmax;  nominal_return[p] = r_0;  w[p][j] = w_j (w may be NULL)
+ *   then mean = new_mean; with shift != 0 instead mean[h] = new_mean[h + 1] for h < H - 1 and mean[H - 1] = new_mean[H - 1].
+ * exp is the device library's: w is an output, and a restatement takes it as an input (as powf is treated by urgym_per_terms).
+ *
+ * THE RECORD (urgym_mppi_record, one launch) is pass k of urgym_rollout_actor's records, restated for the closed loop: pass k in
+ * [0, num_steps] copies the source's observation rows into row k of the trajectory (k < num_steps), initialises the episode summary
+ * (k == 0), and for k > 0 files what source step k - 1 returned (reward .. final_observation rows k - 1, action row k - 1 =
+ * action_out) and the episode summary exactly as urgym_trajectory states it.  For k > 0 it also zeroes mean[:, p, :] where source env
+ * p has just finished (terminated | truncated), so that a new episode does not start from the old plan.  traj may be NULL (only the
+ * zeroing is left); episode_done is required when any of the three other summary arrays is given. */
+#define URGYM_MPPI_TAG 0x4D505000u
+#define URGYM_MPPI_SAMPLES_MAX 1024
+#define URGYM_MPPI_HORIZON_MAX 64
+#define URGYM_MPPI_ITERATIONS_MAX 8
+
+typedef struct urgym_mppi {
+  int32_t num_parents;   /* E */
+  int32_t samples;       /* K in [2, 1024] */
+  int32_t horizon;       /* H in [1, 64] */
+  int32_t iterations;    /* I in [1, 8] (urgym_mppi_plan / _control only) */
+  int32_t shift;         /* != 0: the update (of the LAST iteration, in a plan) leaves mean advanced by one step */
+  int32_t reserved0;     /* must be 0 */
+  float sigma;           /* finite, >= 0 */
+  int32_t reserved1;     /* must be 0 */
+  double lam;            /* lambda, the temperature: finite, > 0 */
+  double gamma;          /* finite */
+  uint64_t seed;         /* the Philox key */
+  float* mean;           /* [H][E][6] the nominal sequence: in (sample) and out (update, record) */
+  float* new_mean;       /* [H][E][6] */
+  float* actions;        /* [H][E*K][6] */
+  float* eps;            /* [H][E*K][6] */
+  double* ret;           /* [E*K] */
+  double* g;             /* [E*K] */
+  uint8_t* alive;        /* [E*K] */
+  int32_t* end_step;     /* [E*K] */
+  uint8_t* success;      /* [E*K] */
+  uint8_t* collided;     /* [E*K] */
+  float* action_out;     /* [E][6] */
+  double* best_return;   /* [E] */
+  double* nominal_return;/* [E] */
+  double* ess;           /* [E] */
+  double* w;             /* [E][K], may be NULL */
+} urgym_mppi;
+
+/* The five single launches.  Everything is validated before the launch; no allocation, no host synchronisation.  Refused by all
+ * (the message names the entry point and the argument): a NULL handle; a NULL m; a NULL pointer of m other than w; K, H or
+ * iterations out of range; num_parents < 1; sigma not finite or < 0; lam not finite or <= 0; gamma not finite; a non-zero reserved
+ * field.  urgym_mppi_sample and urgym_mppi_update need no bound environment (the handle names the device).  Refused besides:
+ *   _fanout  an unbound handle; handles on different devices; a planner with auto_reset != 0 (its episodes must not restart); planner
+ *            num_envs != E * K; source num_envs != E; any urgym_config field other than num_envs and auto_reset differing between
+ *            the two handles
+ *   _sample  draw >= 2^32; iteration outside [0, 8)
+ *   _score   an unbound planner; planner num_envs != E * K; h outside [0, H)
+ *   _record  an unbound source; source num_envs != E; num_steps < 1; k outside [0, num_steps]; a summary array without episode_done */
+int urgym_mppi_fanout(void* source_handle, void* planner_handle, const urgym_mppi* m, void* stream);
+int urgym_mppi_sample(void* handle, const urgym_mppi* m, uint64_t draw, int iteration, void* stream);
+int urgym_mppi_score(void* planner_handle, const urgym_mppi* m, int h, void* stream);
+int urgym_mppi_update(void* handle, const urgym_mppi* m, void* stream);
+int urgym_mppi_record(void* source_handle, const urgym_mppi* m, int k, int num_steps, const urgym_trajectory* traj_or_NULL, void* stream);
+
+/* ONE PLAN: I x (fanout, sample with iteration i, H x (urgym_step(planner, actions[h]), score h), update), the shift applied by the
+ * update of the last iteration only: 3 + 2 H launches per iteration besides what a step itself launches.  Bit for bit that sequence of
+ * single calls and urgym_steps.  Afterwards action_out holds the first action of the refined nominal sequence of every parent.
+ * Refused: everything urgym_mppi_fanout and urgym_mppi_sample refuse. */
+int urgym_mppi_plan(void* source_handle, void* planner_handle, const urgym_mppi* m, uint64_t draw, void* stream);
+
+/* THE CLOSED LOOP: record pass 0, then for t < num_steps: urgym_mppi_plan with draw = first_draw + t; urgym_step(source, action_out);
+ * record pass t + 1.  Bit for bit that sequence.  A source env that finishes inside the call has its mean zeroed by the record pass and,
+ * with the source's auto_reset, plans its new episode from the next step.  Refused: everything urgym_mppi_plan and urgym_mppi_record
+ * refuse; num_steps < 1; first_draw + num_steps > 2^32. */
+int urgym_mppi_control(void* source_handle, void* planner_handle, const urgym_mppi* m, uint64_t first_draw, int num_steps, const urgym_trajectory* traj_or_NULL, void* stream);
+
 /* Replaces Reach*.set_goal / set_goal_and_obstacle (reach.py:202-204, 328-335, 702-713): the caller has
  * overwritten goal / obst_start / obst_end (and possibly q) for the masked envs; this recomputes obstacle pose,
  * velocity, collision, link_dist and the observation for them, leaving step_count untouched. */

@@ -1,0 +1,161 @@
+#!/usr/bin/env python3
+"""What the simulator alone achieves on the reference's test protocol, with no training: the MPPI planner of DESIGN.md section 26
+(``ur_gym_amd.evaluation.DeviceMPPI``) in place of ``model.predict`` in model_test.py's loop, over a small grid of (K, H, sigma, lambda).
+
+Per env kind (UR5OriReach-v1, UR5DynReach-v1) and grid row: the success rate, mean episode reward and mean last step over test points
+drawn as tests/test_closed_loop.py draws them (the goal grid of utils/generate.py; Dyn: obstacle start / end with travel >= 0.3 and
+clearance >= 0.1), E = budget // K points at a time; and the time of a control step, measured with device events around
+``urgym_mppi_plan`` in steady state, next to the time of the plan's own 3 + H launches -- fan-out, sample, H scores, update -- run
+without the steps between them, which is what the four planner kernels cost.  The reference's figures for its trained actors
+(tests/golden/actors/reference_results.json) are copied into the output for comparison.  Needs an MI355X; writes one JSON file.
+
+    python tools/bench_mppi.py --env dyn --out profiles/mppi/dyn_control.json
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from ur_gym_amd import make_vec  # noqa: E402
+from ur_gym_amd.evaluation import DeviceMPPI, constrained_euler, goal_grid, run_closed_loop_mppi  # noqa: E402
+
+ENV_IDS = {"ori": "UR5OriReach-v1", "dyn": "UR5DynReach-v1"}
+LOW = {"ori": np.array([0.3, -0.5, 0.0]), "dyn": np.array([0.4, -0.5, 0.0])}   # reach.py:151-152, 584-585
+HIGH = np.array([0.75, 0.5, 0.2])
+# (K, H, sigma, lambda): a centre, steps to either side of it in each direction, and the horizons 12 and 24 (a
+# horizon whose summed step rewards outweigh w_collision makes ending the episode the best-scoring future)
+GRID = ((256, 6, 0.3, 5.0), (256, 6, 0.15, 5.0), (256, 6, 0.6, 5.0), (256, 6, 0.3, 1.0), (256, 6, 0.3, 25.0), (256, 4, 0.3, 5.0), (256, 8, 0.3, 5.0),
+        (256, 12, 0.3, 5.0), (256, 24, 0.3, 5.0), (64, 6, 0.3, 5.0), (1024, 6, 0.3, 5.0), (1024, 6, 0.3, 25.0), (256, 6, 0.6, 1.0), (256, 6, 1.0, 5.0))
+
+
+def thin(points, keep):
+    return points if keep >= len(points) else points[:: max(1, len(points) // keep)][:keep]
+
+
+def quaternion(rpy):
+    """xyzw of the fixed-axis roll, pitch, yaw `rpy` [n, 3] (pybullet's getQuaternionFromEuler)."""
+    cr, cp, cy = (np.cos(rpy[:, i] / 2) for i in range(3))
+    sr, sp, sy = (np.sin(rpy[:, i] / 2) for i in range(3))
+    return np.stack([sr * cp * cy - cr * sp * sy, cr * sp * cy + sr * cp * sy, cr * cp * sy - sr * sp * cy, cr * cp * cy + sr * sp * sy], axis=1)
+
+
+def test_points(kind, count, device):
+    """`count` test points: [n, 6] goals (Ori) or [n, 18] goal, obstacle start, obstacle end (Dyn), as tests/test_closed_loop.py draws them."""
+    import torch
+
+    rng = np.random.default_rng(0)
+    grid = thin(goal_grid(LOW[kind], HIGH), count)
+    if kind == "ori":
+        return np.concatenate([grid, constrained_euler(rng, len(grid))], axis=1)
+    gen = make_vec(ENV_IDS["dyn"], num_envs=3 * len(grid), device=device, seed=3, auto_reset=False, min_travel=0.3)
+    gen.reset(seed=3)
+    torch.cuda.synchronize()
+    st = gen.get_state()
+    goal_rpy, start, end = st["goal"][3:].T.copy(), st["obst_start"].T.copy(), st["obst_end"].T.copy()
+    cand = np.concatenate([np.repeat(grid, 3, axis=0), goal_rpy], axis=1)
+    n = len(cand)
+    d, _ = gen.probe_closest(np.full(n, 2), np.tile([0.025] * 3, (n, 1)), np.c_[cand[:, :3], quaternion(cand[:, 3:])], np.full(n, 1),
+                             np.tile([0.05, 0.4, 0.0], (n, 1)), np.c_[end[:, :3], quaternion(end[:, 3:])])
+    gen.close()
+    ok = np.asarray(d) >= 0.1
+    rows = []
+    for i in range(len(grid)):
+        choices = [k for k in range(3 * i, 3 * i + 3) if ok[k]]
+        k = choices[0] if choices else 3 * i
+        rows.append(np.r_[cand[k], start[k], end[k]])
+    return np.array(rows)
+
+
+def control_step_time(env, options, repeats):
+    """(ms of one urgym_mppi_plan, ms of the 3 + H launches of the planner's own kernels in it), device events, `repeats` of each after
+    a warm-up of three plans.  The second figure times the single calls -- fan-out, sample, H scores, update -- without the steps between
+    them; their work does not depend on what the steps computed."""
+    import ctypes as C
+
+    import torch
+
+    mppi = DeviceMPPI(env, **options)
+    lib, M, src, planner, s = env.lib, mppi.struct(), env._h, mppi.planner._h, env._stream()
+    for draw in range(3):
+        mppi.plan(draw)
+    begin, mid, end = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+    begin.record()
+    for draw in range(repeats):
+        mppi.plan(3 + draw)
+    mid.record()
+    for draw in range(repeats):
+        rc = lib.urgym_mppi_fanout(src, planner, C.byref(M), s) or lib.urgym_mppi_sample(src, C.byref(M), 3 + draw, 0, s)
+        for h in range(M.horizon):
+            rc = rc or lib.urgym_mppi_score(planner, C.byref(M), h, s)
+        rc = rc or lib.urgym_mppi_update(src, C.byref(M), s)
+        if rc:
+            raise RuntimeError(f"a planner launch failed ({rc})")
+    end.record()
+    torch.cuda.synchronize()
+    mppi.close()
+    return begin.elapsed_time(mid) / repeats, mid.elapsed_time(end) / repeats
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--env", choices=("ori", "dyn"), default="dyn")
+    ap.add_argument("--budget", type=int, default=65536, help="planner envs E * K")
+    ap.add_argument("--points", type=int, default=1024, help="test points per grid row (E = budget // K at a time)")
+    ap.add_argument("--steps", type=int, default=100, help="control steps per trial (model_test.py: 100)")
+    ap.add_argument("--repeats", type=int, default=20, help="plans per timing")
+    ap.add_argument("--rows", type=int, default=len(GRID), help="the first so many rows of the grid")
+    ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+
+    kind, env_id = args.env, ENV_IDS[args.env]
+    points = test_points(kind, args.points, args.device)
+    rows = []
+    for K, H, sigma, lam in GRID[:args.rows]:
+        E = max(1, args.budget // K)
+        options = dict(samples=K, horizon=H, sigma=sigma, lam=lam, gamma=1.0, iterations=1, shift=True, seed=0)
+        success, reward, last, wall = [], [], [], 0.0
+        for first in range(0, len(points) - E + 1, E) if len(points) >= E else [0]:
+            batch = points[first:first + E]
+            env = make_vec(env_id, num_envs=len(batch), device=args.device, seed=4, auto_reset=False)
+            env.reset(seed=4)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res = run_closed_loop_mppi(env, batch, max_steps=args.steps, first_draw=0, **options)  # ends in a device synchronise
+            wall += time.perf_counter() - t0
+            success.append(res["success"]), reward.append(res["reward"]), last.append(res["last_step"])
+            env.close()
+        success, reward, last = (np.concatenate(x) for x in (success, reward, last))
+        env = make_vec(env_id, num_envs=E, device=args.device, seed=4, auto_reset=False)
+        env.reset(seed=4)
+        plan_ms, own_ms = control_step_time(env, options, args.repeats)
+        env.close()
+        row = dict(K=K, H=H, sigma=sigma, lam=lam, E=E, planner_envs=E * K, trials=int(success.size), success_rate_percent=100.0 * float(success.mean()),
+                   mean_episode_reward=float(reward.mean()), mean_last_step_index=float(last.mean()),
+                   early_fail_percent=100.0 * float((~success & (last < args.steps - 1)).mean()), timeout_percent=100.0 * float((last >= args.steps - 1).mean()),
+                   plan_ms=plan_ms, planner_kernels_ms=own_ms, planner_kernels_share=own_ms / plan_ms,
+                   control_steps_per_second=1e3 / plan_ms, env_control_steps_per_second=E * 1e3 / plan_ms,
+                   closed_loop_wall_seconds_including_setup=wall)
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    ref = json.load(open(os.path.join(ROOT, "tests", "golden", "actors", "reference_results.json")))[kind]
+    out = dict(env_id=env_id, protocol=f"model_test.py: {args.steps} steps per trial, closed at the first terminated step", budget=args.budget,
+               timing=f"device events around {args.repeats} urgym_mppi_plan calls after 3 warm-up plans; planner_kernels_ms is the fan-out, sample, H score and update launches alone",
+               reference_trained_actor={k: ref[k] for k in ("success_rate_percent", "mean_episode_reward", "mean_last_step_index", "trials")},
+               device=torch.cuda.get_device_name(0), grid=rows)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+    print(json.dumps({k: v for k, v in out.items() if k != "grid"}))
+
+
+if __name__ == "__main__":
+    main()

@@ -542,6 +542,36 @@ SAC_PRIORITIZED_SCRATCH = [("leaf", lambda M: (M,)), ("q", lambda M: (2, M)), ("
                            ("new_leaf", lambda M: (M,))]
 
 
+MPPI_TAG = 0x4D505000  # URGYM_MPPI_TAG: word 3 of the Philox counter of the planner's noise is MPPI_TAG | block
+MPPI_SAMPLES_MAX, MPPI_HORIZON_MAX, MPPI_ITERATIONS_MAX = 1024, 64, 8  # URGYM_MPPI_*_MAX
+
+# urgym_mppi's device pointers: name -> (ctype of element, shape given (E, K, H)); w may be NULL
+MPPI_FIELDS = [
+    ("mean", C.c_float, lambda E, K, H: (H, E, 6)),
+    ("new_mean", C.c_float, lambda E, K, H: (H, E, 6)),
+    ("actions", C.c_float, lambda E, K, H: (H, E * K, 6)),
+    ("eps", C.c_float, lambda E, K, H: (H, E * K, 6)),
+    ("ret", C.c_double, lambda E, K, H: (E * K,)),
+    ("g", C.c_double, lambda E, K, H: (E * K,)),
+    ("alive", C.c_uint8, lambda E, K, H: (E * K,)),
+    ("end_step", C.c_int32, lambda E, K, H: (E * K,)),
+    ("success", C.c_uint8, lambda E, K, H: (E * K,)),
+    ("collided", C.c_uint8, lambda E, K, H: (E * K,)),
+    ("action_out", C.c_float, lambda E, K, H: (E, 6)),
+    ("best_return", C.c_double, lambda E, K, H: (E,)),
+    ("nominal_return", C.c_double, lambda E, K, H: (E,)),
+    ("ess", C.c_double, lambda E, K, H: (E,)),
+    ("w", C.c_double, lambda E, K, H: (E, K)),
+]
+
+
+class Mppi(C.Structure):
+    """urgym_mppi: the scalars of a planner and its caller-owned device arrays."""
+    _fields_ = [("num_parents", C.c_int32), ("samples", C.c_int32), ("horizon", C.c_int32), ("iterations", C.c_int32), ("shift", C.c_int32),
+                ("reserved0", C.c_int32), ("sigma", C.c_float), ("reserved1", C.c_int32), ("lam", C.c_double), ("gamma", C.c_double),
+                ("seed", C.c_uint64)] + [(name, C.POINTER(ct)) for name, ct, _ in MPPI_FIELDS]
+
+
 # Every symbol include/urgym.h declares (tests check that the built library exports each of them).
 EXPORTED_SYMBOLS = [
     "urgym_abi_version",
@@ -614,6 +644,13 @@ EXPORTED_SYMBOLS = [
     "urgym_rollout_collect_normalized",
     "urgym_policy_evaluate_normalized",
     "urgym_sac_train_normalized",
+    "urgym_mppi_fanout",
+    "urgym_mppi_sample",
+    "urgym_mppi_score",
+    "urgym_mppi_update",
+    "urgym_mppi_record",
+    "urgym_mppi_plan",
+    "urgym_mppi_control",
     "urgym_refresh",
     "urgym_invalidate_records",
     "urgym_derive_obstacle_motion",

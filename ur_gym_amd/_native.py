@@ -136,6 +136,13 @@ def lib():
     L.urgym_sac_train_normalized.argtypes = [C.c_void_p, C.POINTER(_abi.SacLearner), C.POINTER(_abi.SacSchedule), C.POINTER(_abi.Normalization),
                                              C.POINTER(_abi.SacClipping), C.POINTER(_abi.SacNstep), C.POINTER(_abi.SacPrioritized),
                                              C.POINTER(_abi.SacHindsight), C.POINTER(_abi.SacEvaluation), C.POINTER(_abi.SacMonitoring), C.c_void_p]
+    L.urgym_mppi_fanout.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.Mppi), C.c_void_p]
+    L.urgym_mppi_sample.argtypes = [C.c_void_p, C.POINTER(_abi.Mppi), C.c_uint64, C.c_int, C.c_void_p]
+    L.urgym_mppi_score.argtypes = [C.c_void_p, C.POINTER(_abi.Mppi), C.c_int, C.c_void_p]
+    L.urgym_mppi_update.argtypes = [C.c_void_p, C.POINTER(_abi.Mppi), C.c_void_p]
+    L.urgym_mppi_record.argtypes = [C.c_void_p, C.POINTER(_abi.Mppi), C.c_int, C.c_int, C.POINTER(_abi.Trajectory), C.c_void_p]
+    L.urgym_mppi_plan.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.Mppi), C.c_uint64, C.c_void_p]
+    L.urgym_mppi_control.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.Mppi), C.c_uint64, C.c_int, C.POINTER(_abi.Trajectory), C.c_void_p]
     L.urgym_actor_read_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.urgym_critic_read_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.urgym_refresh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]

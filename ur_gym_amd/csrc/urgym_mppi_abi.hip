@@ -1,0 +1,246 @@
+// urgym_mppi_abi.hip -- the planner's entry points of include/urgym.h ("sampling-based MPC on the device").  Host
+// code only, beside urgym_policy_abi.hip: every check is made here, before the first launch; every launch goes through urgym_mppi.h or
+// through do_step of urgym_hip.hip (urgym_handle.h).  As there, each entry point is a checking half, which launches nothing, and a
+// launching half, which refuses nothing.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#include "../../include/urgym.h"
+#include "urgym_handle.h"
+#include "urgym_mppi.h"
+
+using namespace urgym;
+
+namespace {
+
+constexpr uint64_t DRAW_END = (uint64_t)1 << 32;  // the counter holds 32 bits of the draw
+
+struct NamedPointer {
+  const char* name;
+  const void* p;
+};
+
+// the checks that concern the struct alone; `report` keeps the message
+int check_mppi(Handle* report, const urgym_mppi* m, const char* who) {
+  static_assert(sizeof(urgym_mppi) == 176 && alignof(urgym_mppi) == 8, "include/urgym.h");
+  if (!m) return fail_in(report, URGYM_ERR_ARG, who, "null urgym_mppi");
+  const char* what = nullptr;
+  if (m->reserved0 != 0 || m->reserved1 != 0) what = "urgym_mppi.reserved0 and reserved1 must be 0";
+  else if (m->num_parents < 1) what = "urgym_mppi.num_parents must be positive";
+  else if (m->samples < 2 || m->samples > URGYM_MPPI_SAMPLES_MAX) what = "urgym_mppi.samples must be in [2, URGYM_MPPI_SAMPLES_MAX] (1024)";
+  else if (m->horizon < 1 || m->horizon > URGYM_MPPI_HORIZON_MAX) what = "urgym_mppi.horizon must be in [1, URGYM_MPPI_HORIZON_MAX] (64)";
+  else if (m->iterations < 1 || m->iterations > URGYM_MPPI_ITERATIONS_MAX) what = "urgym_mppi.iterations must be in [1, URGYM_MPPI_ITERATIONS_MAX] (8)";
+  else if ((int64_t)m->num_parents * m->samples > INT32_MAX) what = "num_parents * samples does not fit an env count";
+  else if (!isfinite(m->sigma) || m->sigma < 0.0f) what = "urgym_mppi.sigma must be finite and not negative";
+  else if (!isfinite(m->lam) || m->lam <= 0.0) what = "urgym_mppi.lam must be finite and positive";
+  else if (!isfinite(m->gamma)) what = "urgym_mppi.gamma must be finite";
+  if (what) return fail_in(report, URGYM_ERR_ARG, who, what);
+  const NamedPointer required[] = {{"mean", m->mean},       {"new_mean", m->new_mean},       {"actions", m->actions},
+                                   {"eps", m->eps},         {"ret", m->ret},                 {"g", m->g},
+                                   {"alive", m->alive},     {"end_step", m->end_step},       {"success", m->success},
+                                   {"collided", m->collided}, {"action_out", m->action_out}, {"best_return", m->best_return},
+                                   {"nominal_return", m->nominal_return}, {"ess", m->ess}};
+  for (const NamedPointer& r : required)
+    if (!r.p) return failf(report, URGYM_ERR_ARG, "%s: urgym_mppi.%s is null", who, r.name);
+  return URGYM_OK;
+}
+
+int check_bound(Handle* report, const Handle* h, const char* who, const char* which) {
+  if (!h->bound) return failf(report, URGYM_ERR_STATE, "%s: urgym_bind() has not been called on the %s handle", who, which);
+  return URGYM_OK;
+}
+
+int check_planner(Handle* report, const Handle* ph, const urgym_mppi* m, const char* who) {
+  if (int rc = check_bound(report, ph, who, "planner")) return rc;
+  if ((int64_t)ph->cfg.num_envs != (int64_t)m->num_parents * m->samples)
+    return failf(report, URGYM_ERR_ARG, "%s: the planner has %d envs, num_parents * samples is %lld", who, ph->cfg.num_envs,
+                 (long long)m->num_parents * m->samples);
+  return URGYM_OK;
+}
+
+int check_source(Handle* report, const Handle* sh, const urgym_mppi* m, const char* who) {
+  if (int rc = check_bound(report, sh, who, "source")) return rc;
+  if (sh->cfg.num_envs != m->num_parents) return failf(report, URGYM_ERR_ARG, "%s: the source has %d envs, num_parents is %d", who, sh->cfg.num_envs, m->num_parents);
+  return URGYM_OK;
+}
+
+// the checks of a call that moves a source's state into a planner (urgym_mppi_fanout, _plan, _control); the source keeps the message
+int check_pair(Handle* sh, Handle* ph, const urgym_mppi* m, const char* who) {
+  if (!ph) return fail_in(sh, URGYM_ERR_ARG, who, "null planner handle");
+  if (int rc = check_mppi(sh, m, who)) return rc;
+  if (int rc = check_source(sh, sh, m, who)) return rc;
+  if (int rc = check_planner(sh, ph, m, who)) return rc;
+  if (sh == ph) return fail_in(sh, URGYM_ERR_ARG, who, "source and planner are the same handle");
+  if (sh->device != ph->device) return failf(sh, URGYM_ERR_ARG, "%s: the source is on device %d, the planner on device %d", who, sh->device, ph->device);
+  if (ph->cfg.auto_reset != 0) return fail_in(sh, URGYM_ERR_ARG, who, "the planner must have auto_reset == 0 (its episodes must not restart)");
+  urgym_config a = sh->cfg, b = ph->cfg;
+  a.num_envs = b.num_envs = 0, a.auto_reset = b.auto_reset = 0;
+  if (memcmp(&a, &b, sizeof(a)) != 0)
+    return fail_in(sh, URGYM_ERR_ARG, who, "source and planner differ in a urgym_config field other than num_envs and auto_reset");
+  return URGYM_OK;
+}
+
+int check_draw(Handle* report, uint64_t first_draw, int count, const char* who) {
+  if (first_draw >= DRAW_END || first_draw + (uint64_t)count > DRAW_END) return fail_in(report, URGYM_ERR_ARG, who, "draw must stay below 2^32");
+  return URGYM_OK;
+}
+
+MppiFanout fanout_of(const Handle* sh, const Handle* ph, const urgym_mppi& m) {
+  return MppiFanout{sh->buf, ph->buf, m.num_parents, m.samples, sh->obs_dim, sh->goal_dim};
+}
+
+MppiOutcome outcome_of(const Handle* ph) {
+  const urgym_buffers& b = ph->buf;
+  return MppiOutcome{b.reward, b.terminated, b.truncated, b.is_success, b.collision};
+}
+
+int check_record(Handle* sh, int k, int num_steps, const urgym_trajectory* t, const char* who) {
+  if (num_steps < 1) return fail_in(sh, URGYM_ERR_ARG, who, "num_steps must be positive");
+  if (k < 0 || k > num_steps) return fail_in(sh, URGYM_ERR_ARG, who, "k must be in [0, num_steps]");
+  if (t && (t->episode_return || t->episode_last_step || t->episode_success) && !t->episode_done)
+    return fail_in(sh, URGYM_ERR_ARG, who, "traj->episode_done is null with an episode summary asked for");
+  return URGYM_OK;
+}
+
+// pass k of the records: rows k of what the planner sees, rows k - 1 of what the step before returned (actor_pass of urgym_policy_abi.hip)
+MppiRecord record_of(const Handle* sh, const urgym_mppi& m, const urgym_trajectory* traj, int k, int num_steps) {
+  const urgym_buffers& b = sh->buf;
+  const size_t n = (size_t)sh->cfg.num_envs, od = (size_t)sh->obs_dim, gd = (size_t)sh->goal_dim;
+  const size_t pre = (size_t)k * n, post = (size_t)(k > 0 ? k - 1 : 0) * n;
+  auto at = [](auto* p, size_t off) { return p ? p + off : p; };
+  MppiRecord r;
+  memset(&r, 0, sizeof(r));
+  r.E = sh->cfg.num_envs, r.H = m.horizon, r.obs_dim = sh->obs_dim, r.goal_dim = sh->goal_dim, r.auto_reset = sh->cfg.auto_reset;
+  r.k = k, r.num_steps = num_steps;
+  r.observation = b.observation, r.achieved_goal = b.achieved_goal, r.desired_goal = b.desired_goal, r.reward = b.reward;
+  r.final_observation = b.final_observation;
+  r.terminated = b.terminated, r.truncated = b.truncated, r.is_success = b.is_success, r.collision = b.collision;
+  r.action_in = m.action_out;
+  r.mean = m.mean;
+  if (!traj) return r;
+  const urgym_trajectory& t = *traj;
+  r.obs = at(t.observation, pre * od), r.ach = at(t.achieved_goal, pre * gd), r.des = at(t.desired_goal, pre * gd);
+  r.action_row = at(t.action, post * 6);
+  r.reward_row = at(t.reward, post);
+  r.terminated_row = at(t.terminated, post), r.truncated_row = at(t.truncated, post), r.is_success_row = at(t.is_success, post);
+  r.collision_row = at(t.collision, post);
+  r.final_obs_row = at(t.final_observation, post * od);
+  r.ep_return = t.episode_return, r.ep_last = t.episode_last_step, r.ep_success = t.episode_success, r.ep_done = t.episode_done;
+  return r;
+}
+
+// the launches of one plan; everything has been checked
+int plan(Handle* sh, Handle* ph, const urgym_mppi& m, uint64_t draw, hipStream_t s) {
+  const size_t row = (size_t)ph->cfg.num_envs * 6;
+  const MppiFanout f = fanout_of(sh, ph, m);
+  const MppiOutcome o = outcome_of(ph);
+  for (int i = 0; i < m.iterations; i++) {
+    mppi_fanout_launch(f, s);
+    mppi_sample_launch(m, draw, i, s);
+    for (int h = 0; h < m.horizon; h++) {
+      if (int rc = do_step(ph, m.actions + (size_t)h * row, s)) {
+        if (ph != sh) memcpy(sh->err, ph->err, sizeof(sh->err));  // the caller asks the source
+        return rc;
+      }
+      mppi_score_launch(m, o, h, s);
+    }
+    urgym_mppi last = m;
+    if (i + 1 < m.iterations) last.shift = 0;  // the sequence advances once, after the last refinement
+    mppi_update_launch(last, s);
+  }
+  return URGYM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int urgym_mppi_fanout(void* source_handle, void* planner_handle, const urgym_mppi* m, void* stream) {
+  const char* who = "urgym_mppi_fanout";
+  Handle *sh = (Handle*)source_handle, *ph = (Handle*)planner_handle;
+  if (!sh) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (int rc = check_pair(sh, ph, m, who)) return rc;
+  HIP_TRY(sh, hipSetDevice(sh->device));
+  mppi_fanout_launch(fanout_of(sh, ph, *m), (hipStream_t)stream);
+  return launched(sh);
+}
+
+int urgym_mppi_sample(void* handle, const urgym_mppi* m, uint64_t draw, int iteration, void* stream) {
+  const char* who = "urgym_mppi_sample";
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (int rc = check_mppi(h, m, who)) return rc;
+  if (int rc = check_draw(h, draw, 1, who)) return rc;
+  if (iteration < 0 || iteration >= URGYM_MPPI_ITERATIONS_MAX) return fail_in(h, URGYM_ERR_ARG, who, "iteration must be in [0, URGYM_MPPI_ITERATIONS_MAX)");
+  HIP_TRY(h, hipSetDevice(h->device));
+  mppi_sample_launch(*m, draw, iteration, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_mppi_score(void* planner_handle, const urgym_mppi* m, int h, void* stream) {
+  const char* who = "urgym_mppi_score";
+  Handle* ph = (Handle*)planner_handle;
+  if (!ph) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (int rc = check_mppi(ph, m, who)) return rc;
+  if (int rc = check_planner(ph, ph, m, who)) return rc;
+  if (h < 0 || h >= m->horizon) return fail_in(ph, URGYM_ERR_ARG, who, "h must be in [0, horizon)");
+  HIP_TRY(ph, hipSetDevice(ph->device));
+  mppi_score_launch(*m, outcome_of(ph), h, (hipStream_t)stream);
+  return launched(ph);
+}
+
+int urgym_mppi_update(void* handle, const urgym_mppi* m, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (int rc = check_mppi(h, m, "urgym_mppi_update")) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  mppi_update_launch(*m, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_mppi_record(void* source_handle, const urgym_mppi* m, int k, int num_steps, const urgym_trajectory* traj_or_NULL, void* stream) {
+  const char* who = "urgym_mppi_record";
+  Handle* sh = (Handle*)source_handle;
+  if (!sh) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (int rc = check_mppi(sh, m, who)) return rc;
+  if (int rc = check_source(sh, sh, m, who)) return rc;
+  if (int rc = check_record(sh, k, num_steps, traj_or_NULL, who)) return rc;
+  HIP_TRY(sh, hipSetDevice(sh->device));
+  mppi_record_launch(record_of(sh, *m, traj_or_NULL, k, num_steps), (hipStream_t)stream);
+  return launched(sh);
+}
+
+int urgym_mppi_plan(void* source_handle, void* planner_handle, const urgym_mppi* m, uint64_t draw, void* stream) {
+  const char* who = "urgym_mppi_plan";
+  Handle *sh = (Handle*)source_handle, *ph = (Handle*)planner_handle;
+  if (!sh) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (int rc = check_pair(sh, ph, m, who)) return rc;
+  if (int rc = check_draw(sh, draw, 1, who)) return rc;
+  HIP_TRY(sh, hipSetDevice(sh->device));
+  if (int rc = plan(sh, ph, *m, draw, (hipStream_t)stream)) return rc;
+  return launched(sh);
+}
+
+int urgym_mppi_control(void* source_handle, void* planner_handle, const urgym_mppi* m, uint64_t first_draw, int num_steps, const urgym_trajectory* traj_or_NULL, void* stream) {
+  const char* who = "urgym_mppi_control";
+  Handle *sh = (Handle*)source_handle, *ph = (Handle*)planner_handle;
+  hipStream_t s = (hipStream_t)stream;
+  if (!sh) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (int rc = check_pair(sh, ph, m, who)) return rc;
+  if (int rc = check_record(sh, 0, num_steps, traj_or_NULL, who)) return rc;
+  if (int rc = check_draw(sh, first_draw, num_steps, who)) return rc;
+  HIP_TRY(sh, hipSetDevice(sh->device));
+  // Every launch goes to `s`: stream order alone puts a plan's update before the source step that reads action_out, and that step
+  // before the record pass that files its outcome and the fan-out that clones its state.
+  mppi_record_launch(record_of(sh, *m, traj_or_NULL, 0, num_steps), s);
+  for (int t = 0; t < num_steps; t++) {
+    if (int rc = plan(sh, ph, *m, first_draw + (uint64_t)t, s)) return rc;
+    if (int rc = do_step(sh, m->action_out, s)) return rc;
+    mppi_record_launch(record_of(sh, *m, traj_or_NULL, t + 1, num_steps), s);
+  }
+  return launched(sh);
+}
+
+}  // extern "C"

@@ -67,10 +67,20 @@ def policy_noise(seed, draw, env_ids, mode, dtype=np.float32):
     lo, hi = draw & np.uint64(0xFFFFFFFF), draw >> np.uint64(32)
     a = philox4x32_10(key, (env, lo, hi, np.uint64(_abi.NOISE_TAG | 0)))
     b = philox4x32_10(key, (env, lo, hi, np.uint64(_abi.NOISE_TAG | 1)))
-    m = np.stack([w >> np.uint32(8) for w in (a[0], a[1], a[2], a[3], b[0], b[1])], axis=-1).astype(dtype)  # 24 bits: exact
-    scale = dtype(2.0 ** -24)
+    m = _noise_integers(a, b, dtype)
     if mode == _abi.SAMPLE_UNIFORM:
-        return m * scale
+        return m * dtype(2.0 ** -24)
+    return _box_muller(m, dtype)
+
+
+def _noise_integers(a, b, dtype):
+    """The six 24-bit integers m(w) = w >> 8 of the words w0 .. w3 of block 0 (`a`) and w4, w5 of block 1 (`b`), exact in `dtype`."""
+    return np.stack([w >> np.uint32(8) for w in (a[0], a[1], a[2], a[3], b[0], b[1])], axis=-1).astype(dtype)
+
+
+def _box_muller(m, dtype):
+    """Box-Muller on the pairs of `m` (shape + (6,) integers below 2^24) as include/urgym.h states it for the GAUSSIAN policy noise."""
+    scale = dtype(2.0 ** -24)
     u1, u2 = (m[..., 0::2] + dtype(1)) * scale, m[..., 1::2] * scale  # (0, 1], [0, 1)
     r, angle = np.sqrt(dtype(-2) * np.log(u1)), dtype(2 * np.pi) * u2
     out = np.empty_like(m)
@@ -2573,4 +2583,233 @@ class DeviceNormalizer:
         for k, v in arrays.items():
             self.state[k].copy_(torch.from_numpy(v))
         self.training = bool(state["training"])
+
+
+# ------------------------------------------------------------------------------------------------ sampling-based MPC on the device (MPPI)
+def mppi_noise(seed, draw, iteration, parents, samples, steps, dtype=np.float32):
+    """The noise of the device's MPPI planner, restated from include/urgym.h ("sampling-based MPC on the device"): a pure function of
+    (seed, draw, iteration, parent p, sample j, horizon step h, component).  `parents`, `samples`, `steps` are integers or integer
+    arrays that broadcast together; returns their shape + (6,): zeros where j == 0 (the nominal sequence), else Box-Muller as
+    ``policy_noise`` states it on the words of the counter (p, (i << 24) | (h << 16) | j, draw, MPPI_TAG | block).  `dtype` is the
+    precision of ln / sqrt / cos / sin."""
+    from . import _abi
+
+    draw, i = int(draw), int(iteration)
+    if not 0 <= draw < 1 << 32 or not 0 <= i < _abi.MPPI_ITERATIONS_MAX:
+        raise ValueError(f"draw must be in [0, 2^32) and iteration in [0, {_abi.MPPI_ITERATIONS_MAX}), got {draw}, {i}")
+    p, j, h = np.broadcast_arrays(*(np.asarray(x, dtype=np.uint64) for x in (parents, samples, steps)))
+    if j.size and (int(j.max()) >= _abi.MPPI_SAMPLES_MAX or int(h.max()) >= _abi.MPPI_HORIZON_MAX):
+        raise ValueError("samples must be below 1024 and steps below 64")
+    seed = int(seed)
+    key = (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
+    mid = np.uint64(i << 24) | (h << np.uint64(16)) | j
+    a = philox4x32_10(key, (p, mid, np.uint64(draw), np.uint64(_abi.MPPI_TAG | 0)))
+    b = philox4x32_10(key, (p, mid, np.uint64(draw), np.uint64(_abi.MPPI_TAG | 1)))
+    eps = _box_muller(_noise_integers(a, b, dtype), dtype)
+    eps[j == 0] = 0
+    return eps
+
+
+def mppi_actions(mean, eps, sigma):
+    """THE SAMPLE's action line in numpy, bitwise: `mean` float32 [H, E, 6], `eps` float32 [H, E * K, 6]; planner env n = p * K + j reads
+    parent p's mean.  s = sigma * eps; a = mean + s; action = fmin(fmax(a, -1), 1), each one float32 operation."""
+    mean, eps = np.asarray(mean), np.asarray(eps)
+    if mean.dtype != np.float32 or eps.dtype != np.float32 or mean.ndim != 3 or eps.ndim != 3 or eps.shape[1] % mean.shape[1]:
+        raise ValueError(f"mean must be float32 [H, E, 6] and eps float32 [H, E * K, 6], got {mean.dtype} {mean.shape}, {eps.dtype} {eps.shape}")
+    s = np.float32(sigma) * eps
+    a = np.repeat(mean, eps.shape[1] // mean.shape[1], axis=1) + s
+    return np.fmin(np.fmax(a, np.float32(-1)), np.float32(1))
+
+
+def mppi_score(reward, terminated, truncated, is_success, collision, gamma):
+    """THE SCORE in numpy, bitwise what H urgym_mppi_score launches leave: the five arrays are [H, N], what planner step h returned.
+    Returns a dict of ret, g (float64), alive, success, collided (uint8) and end_step (int32), each [N]."""
+    reward = np.asarray(reward)
+    if reward.dtype != np.float32 or reward.ndim != 2:
+        raise ValueError(f"reward must be a float32 [H, N] array, got {reward.dtype} {reward.shape}")
+    H, n = reward.shape
+    done = (np.asarray(terminated).astype(np.uint8) | np.asarray(truncated).astype(np.uint8)) != 0
+    ret, g, alive = np.zeros(n, np.float64), np.ones(n, np.float64), np.ones(n, bool)
+    end_step, success, collided = np.full(n, H - 1, np.int32), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+    with np.errstate(all="ignore"):
+        for h in range(H):
+            t = g * reward[h].astype(np.float64)
+            ret = np.where(alive, ret + t, ret)
+            g = np.where(alive, g * np.float64(gamma), g)
+            ends = alive & done[h]
+            end_step[ends] = h
+            success[ends] = np.asarray(is_success[h]).astype(np.uint8)[ends]
+            collided[ends] = np.asarray(collision[h]).astype(np.uint8)[ends]
+            alive = alive & ~ends
+    return dict(ret=ret, g=g, alive=alive.astype(np.uint8), end_step=end_step, success=success, collided=collided)
+
+
+def mppi_weights(ret, lam, samples):
+    """THE UPDATE's weights with numpy's float64 exp in place of the device's: `ret` float64 [E * K].  Returns (w [E, K], rmax [E]).
+    A return that is not finite weighs nothing; a parent without a finite return puts everything on its sample 0."""
+    r = np.asarray(ret, dtype=np.float64).reshape(-1, int(samples))
+    finite = np.isfinite(r)
+    rmax = np.where(finite, r, -np.inf).max(axis=1)
+    with np.errstate(all="ignore"):
+        w = np.where(finite, np.exp((r - rmax[:, None]) / np.float64(lam)), 0.0)
+    none = ~finite.any(axis=1)
+    w[none] = 0.0
+    w[none, 0] = 1.0
+    return w, rmax
+
+
+def mppi_update(ret, w, actions, shift):
+    """THE UPDATE in numpy given the weights, bitwise: `ret` float64 [E * K], `w` float64 [E, K] (the device's own, or ``mppi_weights``),
+    `actions` float32 [H, E * K, 6].  Every sum is THE ORDERED SUM over the K float64 terms of a parent.  Returns a dict of new_mean and
+    mean ([H, E, 6] float32; mean is new_mean advanced by one step where `shift`), action_out [E, 6], best_return, nominal_return, ess [E]."""
+    w, actions = np.asarray(w), np.asarray(actions)
+    if w.dtype != np.float64 or w.ndim != 2 or actions.dtype != np.float32 or actions.ndim != 3 or actions.shape[1:] != (w.size, 6):
+        raise ValueError(f"w must be float64 [E, K] and actions float32 [H, E * K, 6], got {w.dtype} {w.shape}, {actions.dtype} {actions.shape}")
+    E, K = w.shape
+    H = actions.shape[0]
+    r = np.asarray(ret, dtype=np.float64).reshape(E, K)
+    new_mean, ess = np.zeros((H, E, 6), np.float32), np.zeros(E, np.float64)
+    with np.errstate(all="ignore"):
+        for p in range(E):
+            Z = ordered_sum(w[p], np.float64)
+            Q = ordered_sum(w[p] * w[p], np.float64)
+            ess[p] = (Z * Z) / Q
+            a = actions[:, p * K:(p + 1) * K].astype(np.float64)
+            for h in range(H):
+                for c in range(6):
+                    new_mean[h, p, c] = np.float32(ordered_sum(w[p] * a[h, :, c], np.float64) / Z)
+    mean = new_mean.copy()
+    if shift:
+        mean[:-1] = new_mean[1:]
+    rmax = np.where(np.isfinite(r), r, -np.inf).max(axis=1)
+    return dict(new_mean=new_mean, mean=mean, action_out=new_mean[0].copy(), best_return=rmax, nominal_return=r[:, 0].copy(), ess=ess)
+
+
+class DeviceMPPI:
+    """An MPPI planner (Williams et al., 2017) for `env`, a UR5ReachVectorEnv of E envs, that plans with the step kernel itself: it owns a
+    planner environment of E * `samples` envs (same env id, configuration and device, ``auto_reset=False``) and every buffer of
+    ``urgym_mppi``.  A plan clones each env into `samples` futures, rolls them `horizon` steps under perturbed action sequences, weighs
+    the sequences by exp((return - best) / `lam`) and keeps the weighted mean as the next nominal sequence; `iterations` repeats that
+    from the refined mean.  `sigma` is the standard deviation of the perturbation in action units ([-1, 1] per joint), `gamma` the
+    discount inside the horizon.  With `shift` the nominal sequence advances by one step after each plan (receding horizon).  The
+    defaults of `horizon`, `sigma` and `lam` are a row of the grid tools/bench_mppi.py ran on UR5DynReach-v1 and UR5OriReach-v1 (DESIGN.md
+    section 26); a horizon whose summed step rewards outweigh the collision penalty makes ending the episode the best-scoring future."""
+
+    DIAGNOSTICS = ("best_return", "nominal_return", "ess")
+
+    def __init__(self, env, samples=256, horizon=6, sigma=0.6, lam=5.0, gamma=1.0, iterations=1, shift=True, seed=0, keep_weights=False):
+        import ctypes as C
+
+        import torch
+
+        from . import _abi
+        from .vector_env import _TORCH_DTYPE, UR5ReachVectorEnv
+
+        E, K, H = env.num_envs, int(samples), int(horizon)
+        if not 2 <= K <= _abi.MPPI_SAMPLES_MAX or not 1 <= H <= _abi.MPPI_HORIZON_MAX or not 1 <= int(iterations) <= _abi.MPPI_ITERATIONS_MAX:
+            raise ValueError(f"DeviceMPPI: samples must be in [2, 1024], horizon in [1, 64], iterations in [1, 8]; got {samples}, {horizon}, {iterations}")
+        if not (np.isfinite(sigma) and sigma >= 0 and np.isfinite(lam) and lam > 0 and np.isfinite(gamma)):
+            raise ValueError(f"DeviceMPPI: sigma must be finite and >= 0, lam finite and > 0, gamma finite; got {sigma}, {lam}, {gamma}")
+        same = {name: getattr(env.cfg, name) for name, _ in _abi.Config._fields_ if name not in ("env_kind", "num_envs", "auto_reset", "check_collision")}
+        self.env = env
+        self.planner = UR5ReachVectorEnv(env.env_id, num_envs=E * K, device=env.device, auto_reset=False, check_collision=bool(env.cfg.check_collision), **same)
+        self.planner._needs_reset = False  # its state is the fan-out's
+        self.samples, self.horizon = K, H
+        self.buf = {}
+        M = _abi.Mppi()
+        M.num_parents, M.samples, M.horizon, M.iterations, M.shift = E, K, H, int(iterations), int(bool(shift))
+        M.sigma, M.lam, M.gamma, M.seed = float(sigma), float(lam), float(gamma), int(seed)
+        for name, ct, shape in _abi.MPPI_FIELDS:
+            if name == "w" and not keep_weights:
+                continue
+            self.buf[name] = torch.zeros(shape(E, K, H), dtype=_TORCH_DTYPE[ct], device=env.device)
+            setattr(M, name, C.cast(self.buf[name].data_ptr(), C.POINTER(ct)))
+        self._struct = M
+
+    def struct(self):
+        """The ``urgym_mppi`` of this planner (its pointers stay valid until ``close``)."""
+        return self._struct
+
+    def plan(self, draw=0):
+        """One ``urgym_mppi_plan`` from the environment's state as it stands.  Returns (action_out [E, 6], diagnostics): views of this
+        planner's buffers, overwritten by the next plan; diagnostics holds ``best_return``, ``nominal_return`` and ``ess`` [E].  NOT
+        synchronised."""
+        import ctypes as C
+
+        from . import _native
+
+        env = self.env
+        _native.check(env.lib.urgym_mppi_plan(env._h, self.planner._h, C.byref(self._struct), int(draw), env._stream()), env._h)
+        return self.buf["action_out"], {k: self.buf[k] for k in self.DIAGNOSTICS}
+
+    def run(self, num_steps, first_draw=0, record=("reward", "terminated", "truncated", "is_success")):
+        """`num_steps` x (plan, step the environment with the plan's first action) in ONE native call (``urgym_mppi_control``); step t
+        draws with ``first_draw + t``.  `record` names what to keep, as ``UR5ReachVectorEnv.rollout_policy`` does ("all" = every key).
+        Returns a dict of fresh device tensors (flags as bool views).  NOT synchronised."""
+        import ctypes as C
+
+        import torch
+
+        from . import _abi, _native
+        from .vector_env import _TORCH_DTYPE
+
+        env, T = self.env, int(num_steps)
+        keys = tuple(name for name, _, _ in _abi.TRAJECTORY_FIELDS)
+        names = tuple(k for k in keys if k != "final_observation" or env.cfg.auto_reset) if record == "all" else tuple(record)
+        unknown = [n for n in names if n not in keys]
+        if unknown:
+            raise ValueError(f"unknown record {unknown}; available: {keys}")
+        if "final_observation" in names and not env.cfg.auto_reset:
+            raise ValueError("final_observation exists only with auto_reset")
+        if any(n.startswith("episode_") for n in names) and "episode_done" not in names:
+            names += ("episode_done",)
+        traj, out = _abi.Trajectory(), {}
+        for name, ct, shape in _abi.TRAJECTORY_FIELDS:
+            if name in names:
+                t = torch.zeros(shape(T, env.num_envs, env.obs_dim, env.goal_dim), dtype=_TORCH_DTYPE[ct], device=env.device)
+                setattr(traj, name, C.cast(t.data_ptr(), C.POINTER(ct)))
+                out[name] = t.view(torch.bool) if ct is C.c_uint8 else t
+        _native.check(env.lib.urgym_mppi_control(env._h, self.planner._h, C.byref(self._struct), int(first_draw), T, C.byref(traj) if names else None,
+                                                 env._stream()), env._h)
+        return out
+
+    def reset_plan(self, mask=None):
+        """Zeroes the nominal sequence of every env, or of those `mask` (a bool [E] tensor or array, or env ids) selects."""
+        import torch
+
+        if mask is None:
+            self.buf["mean"].zero_()
+        else:
+            self.buf["mean"][:, torch.as_tensor(mask, device=self.env.device)] = 0.0
+
+    def close(self):
+        if getattr(self, "planner", None) is not None:
+            self.planner.close()
+            self.planner = None
+
+
+def run_closed_loop_mppi(env, points=None, max_steps=100, first_draw=0, **planner):
+    """``run_closed_loop_device`` with an MPPI planner in place of ``model.predict``: model_test.py's protocol (model_test.py:26-61) for all
+    envs of `env` at once, a UR5ReachVectorEnv with auto-reset off that has been reset.  `points`, if given, are one test point per env,
+    set with ``set_goal`` (UR5OriReach-v1) or ``set_goal_and_obstacle`` first.  `planner` are ``DeviceMPPI``'s keywords.  One native call;
+    returns the same dictionary."""
+    import torch
+
+    from . import _abi
+
+    if env.cfg.auto_reset:
+        raise ValueError("run_closed_loop_mppi: env must be made with auto_reset=False")
+    if points is not None:
+        (env.set_goal if env.env_kind == _abi.ENV_ORI else env.set_goal_and_obstacle)(np.arange(env.num_envs), points)
+    mppi = DeviceMPPI(env, **planner)
+    try:
+        rec = mppi.run(max_steps, first_draw, record=("episode_return", "episode_last_step", "episode_success"))
+        torch.cuda.synchronize(env.device)
+    finally:
+        mppi.close()
+    reward = rec["episode_return"].cpu().numpy()
+    success = rec["episode_success"].cpu().numpy().astype(bool)
+    last = rec["episode_last_step"].cpu().numpy().astype(np.float64)
+    return {"success_rate_percent": 100.0 * success.mean(), "mean_episode_reward": float(reward.mean()),
+            "mean_last_step_index": float(last.mean()), "success": success, "reward": reward, "last_step": last}
 
