@@ -1895,6 +1895,65 @@ int urgym_mppi_plan(void* source_handle, void* planner_handle, const urgym_mppi*
  * refuse; num_steps < 1; first_draw + num_steps > 2^32. */
 int urgym_mppi_control(void* source_handle, void* planner_handle, const urgym_mppi* m, uint64_t first_draw, int num_steps, const urgym_trajectory* traj_or_NULL, void* stream);
 
+/* ---- MPPI with the learner in the loop: the critic values the state a plan stops in, the actor proposes samples, and a future that
+ * ends without success costs a scalar.  Added WITHIN ABI version 4: no struct above changed, the four new
+ * symbols are found by lookup, and urgym_mppi_plan / urgym_mppi_control and the five single launches are what they were.  The actor and
+ * the critic are ordinary ones (urgym_actor_create, urgym_critic_create) of the PLANNER handle: they read its bound rows, [E * K] of
+ * them, raw -- a policy trained on normalized observations is not served.
+ *
+ * THE GUIDE (urgym_mppi_guide_actions, one launch before planner step h, one lane per (n, c), float32, one operation per line) rewrites
+ * the action rows of samples 1 .. P of every parent, planner envs n = p K + j with 1 <= j <= P:
+ *   s = policy_sigma * eps[h][n][c];  a = policy_action[n][c] + s;  actions[h][n][c] = fminf(fmaxf(a, -1), 1)
+ * eps being what the sample launch drew for (h, n, c) -- no new Philox words -- and policy_action what urgym_actor_forward wrote for
+ * the planner's bound observation before planner step h.  Sample 0 (the nominal) and samples j > P are not written.  actions then
+ * holds what every future executed, which is what the update's weighted mean reads.
+ *
+ * THE TERMINAL STEP (urgym_mppi_terminal, one launch after the score of step H - 1, one lane per planner env n, float64):
+ *   alive:                  v = terminal_value ? (double)value[n] : 0
+ *   not alive, success:     v = 0
+ *   not alive, no success:  v = -fail_cost
+ *   terminal[n] = v;   if (v != 0) { t = g * v;  ret = ret + t; }
+ * alive, success, g and ret as the score left them: g is gamma^H for a live future and gamma^(end_step + 1) for an ended one.  The
+ * choice of the case is a selection: value[n] of an ended future is not read, so a NaN there reaches nothing; a NaN value of a live
+ * future reaches that future's ret only, and the update gives a return that is not finite the weight 0.  value[n] is
+ * min(q0, q1)(s_H, actor(s_H)), urgym_critic_evaluate's q_min.  The shipped critics were trained with gamma = 0.95: a plan that credits
+ * their value should discount with it. */
+typedef struct urgym_mppi_guide {
+  void* actor;             /* an actor of the PLANNER handle, or NULL */
+  void* critic;            /* a critic of the PLANNER handle, or NULL */
+  int32_t policy_samples;  /* P in [0, K - 1]: samples 1 .. P follow the actor */
+  int32_t terminal_value;  /* != 0: a future alive after H steps is credited min Q(s_H, actor(s_H)) */
+  float policy_sigma;      /* finite, >= 0 */
+  int32_t reserved0;       /* must be 0 */
+  double fail_cost;        /* finite, >= 0 */
+  float* policy_action;    /* [E*K][6]; needed when the actor is used (P > 0 or terminal_value) */
+  float* value;            /* [E*K]; needed with terminal_value */
+  double* terminal;        /* [E*K]; needed when the terminal launch is made (terminal_value or fail_cost > 0) */
+} urgym_mppi_guide;
+
+/* The two single launches.  Everything is validated before the launch; no allocation, no host synchronisation.  Refused by both and
+ * by the two composed calls below (the message names the entry point and the argument): what urgym_mppi_score refuses about handle, m
+ * and the planner; a NULL g; a non-zero reserved0; P outside [0, K - 1]; P > 0 without an actor; terminal_value without an actor or
+ * without a critic; an actor or critic that is not the planner handle's (the source handle's in particular) or does not take its env
+ * kind's features; policy_sigma not finite or < 0; fail_cost not finite or < 0; a NULL policy_action, value or terminal that the chosen
+ * options need.  Refused besides: _guide_actions  h outside [0, H);  _terminal  neither terminal_value nor fail_cost > 0 (there is no
+ * terminal launch then).  With P == 0 no sample follows the actor and urgym_mppi_guide_actions launches nothing. */
+int urgym_mppi_guide_actions(void* planner_handle, const urgym_mppi* m, const urgym_mppi_guide* g, int h, void* stream);
+int urgym_mppi_terminal(void* planner_handle, const urgym_mppi* m, const urgym_mppi_guide* g, void* stream);
+
+/* ONE GUIDED PLAN, per iteration: fanout; sample; for each h: with P > 0 urgym_actor_forward(planner, actor, policy_action) and the
+ * guide launch h, then urgym_step(planner, actions[h]) and score h; with terminal_value urgym_actor_forward(planner, actor,
+ * policy_action) and urgym_critic_evaluate(planner, critic, the bound rows with action = policy_action, E * K, out.q_min = value); with
+ * terminal_value or fail_cost > 0 the terminal launch; update (the shift on the last iteration only).  That is up to 2 H + 3 launches
+ * per iteration more than a plain plan.  Bit for bit that sequence of single calls; with P == 0, terminal_value == 0 and fail_cost == 0
+ * it launches, and leaves, what urgym_mppi_plan does.  The actor reads the rows the fan-out and the planner's steps wrote: the planner
+ * needs no urgym_reset of its own.  Refused: everything urgym_mppi_plan and the two launches above refuse. */
+int urgym_mppi_plan_guided(void* source_handle, void* planner_handle, const urgym_mppi* m, const urgym_mppi_guide* g, uint64_t draw, void* stream);
+
+/* THE GUIDED CLOSED LOOP: urgym_mppi_control with urgym_mppi_plan_guided in place of urgym_mppi_plan, bit for bit.  Refused:
+ * everything urgym_mppi_plan_guided and urgym_mppi_control refuse. */
+int urgym_mppi_control_guided(void* source_handle, void* planner_handle, const urgym_mppi* m, const urgym_mppi_guide* g, uint64_t first_draw, int num_steps, const urgym_trajectory* traj_or_NULL, void* stream);
+
 /* Replaces Reach*.set_goal / set_goal_and_obstacle (reach.py:202-204, 328-335, 702-713): the caller has
  * overwritten goal / obst_start / obst_end (and possibly q) for the masked envs; this recomputes obstacle pose,
  * velocity, collision, link_dist and the observation for them, leaving step_count untouched. */

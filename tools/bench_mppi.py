@@ -10,6 +10,14 @@ without the steps between them, which is what the four planner kernels cost.  Th
 (tests/golden/actors/reference_results.json) are copied into the output for comparison.  Needs an MI355X; writes one JSON file.
 
     python tools/bench_mppi.py --env dyn --out profiles/mppi/dyn_control.json
+
+With the learner in the loop (--fail-cost, --terminal-value, --policy-samples with --actor and --critics) every
+grid row is run a second time with the guide and reported under "guided" beside the plain figures of the same (K, H, sigma, lambda): the
+same protocol figures, the time of a guided plan, and the time of the launches the guide adds -- actor, guide, critic, terminal -- run
+without the rest.  --grid replaces the built-in grid.
+
+    python tools/bench_mppi.py --env ori --grid 256:6:0.3:5 256:12:0.3:5 256:24:0.3:5 --terminal-value --policy-samples 64 \
+        --actor tests/golden/actors/actor_ori.npz --critics tests/golden/critics/critic_ori_qf0.npz tests/golden/critics/critic_ori_qf1.npz
 """
 import argparse
 import json
@@ -101,6 +109,80 @@ def control_step_time(env, options, repeats):
     return begin.elapsed_time(mid) / repeats, mid.elapsed_time(end) / repeats
 
 
+def guided_step_time(env, options, repeats):
+    """(ms of one urgym_mppi_plan_guided, ms of the launches the guide adds to it), measured like ``control_step_time``.  The second
+    figure times the single calls -- per horizon step the actor and the guide launch where samples follow the policy, then actor, critic
+    and the terminal launch as the options ask -- without the steps between them; the planner is reset once before them, because the
+    single call urgym_actor_forward wants a handle that has observed something."""
+    import ctypes as C
+
+    import torch
+
+    from ur_gym_amd import _abi
+
+    mppi = DeviceMPPI(env, **options)
+    lib, M, G, planner, s = env.lib, mppi.struct(), mppi.guide(), mppi.planner._h, env._stream()
+    for draw in range(3):
+        mppi.plan(draw)
+    begin, mid, end = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+    begin.record()
+    for draw in range(repeats):
+        mppi.plan(3 + draw)
+    mid.record()
+    torch.cuda.synchronize()
+    plan_ms = begin.elapsed_time(mid) / repeats
+    mppi.planner.reset(seed=0)
+    pa = C.c_void_p(mppi.buf["policy_action"].data_ptr()) if "policy_action" in mppi.buf else None
+    rows, out = _abi.CriticRows(None, None, None, G.policy_action), _abi.CriticOut(None, G.value, None)
+
+    def added():
+        rc = 0
+        for h in range(M.horizon if G.policy_samples else 0):
+            rc = rc or lib.urgym_actor_forward(planner, mppi.actor._a, pa, s) or lib.urgym_mppi_guide_actions(planner, C.byref(M), C.byref(G), h, s)
+        if G.terminal_value:
+            rc = rc or lib.urgym_actor_forward(planner, mppi.actor._a, pa, s)
+            rc = rc or lib.urgym_critic_evaluate(planner, mppi.critic._c, C.byref(rows), M.num_parents * M.samples, None, C.byref(out), s)
+        if G.terminal_value or G.fail_cost > 0:
+            rc = rc or lib.urgym_mppi_terminal(planner, C.byref(M), C.byref(G), s)
+        if rc:
+            raise RuntimeError(f"a guide launch failed ({rc})")
+
+    for _ in range(3):
+        added()
+    mid.record()
+    for _ in range(repeats):
+        added()
+    end.record()
+    torch.cuda.synchronize()
+    mppi.close()
+    return plan_ms, mid.elapsed_time(end) / repeats
+
+
+def protocol(env_id, points, E, steps, device, options):
+    """model_test.py's protocol over `points`, E at a time: (success, reward, last step, wall seconds)."""
+    import torch
+
+    success, reward, last, wall = [], [], [], 0.0
+    for first in range(0, len(points) - E + 1, E) if len(points) >= E else [0]:
+        batch = points[first:first + E]
+        env = make_vec(env_id, num_envs=len(batch), device=device, seed=4, auto_reset=False)
+        env.reset(seed=4)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = run_closed_loop_mppi(env, batch, max_steps=steps, first_draw=0, **options)  # ends in a device synchronise
+        wall += time.perf_counter() - t0
+        success.append(res["success"]), reward.append(res["reward"]), last.append(res["last_step"])
+        env.close()
+    success, reward, last = (np.concatenate(x) for x in (success, reward, last))
+    return success, reward, last, wall
+
+
+def figures(success, reward, last, steps):
+    return dict(trials=int(success.size), success_rate_percent=100.0 * float(success.mean()), mean_episode_reward=float(reward.mean()),
+                mean_last_step_index=float(last.mean()), early_fail_percent=100.0 * float((~success & (last < steps - 1)).mean()),
+                timeout_percent=100.0 * float((last >= steps - 1).mean()))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--env", choices=("ori", "dyn"), default="dyn")
@@ -111,37 +193,48 @@ def main():
     ap.add_argument("--rows", type=int, default=len(GRID), help="the first so many rows of the grid")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--grid", nargs="+", default=None, metavar="K:H:SIGMA:LAMBDA", help="rows to run in place of the built-in grid")
+    ap.add_argument("--actor", default=None, help="actor weights (.npz) for --policy-samples and --terminal-value")
+    ap.add_argument("--critics", nargs=2, default=None, metavar="NPZ", help="the two Q-networks' weights for --terminal-value")
+    ap.add_argument("--policy-samples", type=int, default=0, help="P: samples 1 .. P of every parent follow the actor")
+    ap.add_argument("--policy-sigma", type=float, default=0.1, help="the noise scale around the actor's action (with --policy-samples)")
+    ap.add_argument("--terminal-value", action="store_true", help="credit a future alive after H steps with min Q(s_H, actor(s_H))")
+    ap.add_argument("--fail-cost", type=float, default=0.0, help="the cost of a future that ends without success")
+    ap.add_argument("--guided-gamma", type=float, default=None, help="gamma of the guided rows (default 0.95 with --terminal-value, the critics' own, else 1)")
     args = ap.parse_args()
     import torch
 
     kind, env_id = args.env, ENV_IDS[args.env]
     points = test_points(kind, args.points, args.device)
+    grid = GRID[:args.rows] if args.grid is None else [(int(k), int(h), float(sg), float(lm)) for k, h, sg, lm in (r.split(":") for r in args.grid)]
+    guide = None
+    if args.policy_samples or args.terminal_value or args.fail_cost:
+        guide = dict(policy_samples=args.policy_samples, policy_sigma=args.policy_sigma if args.policy_samples else 0.0, terminal_value=args.terminal_value,
+                     fail_cost=args.fail_cost, actor=args.actor, critic=args.critics,
+                     gamma=args.guided_gamma if args.guided_gamma is not None else (0.95 if args.terminal_value else 1.0))
     rows = []
-    for K, H, sigma, lam in GRID[:args.rows]:
+    for K, H, sigma, lam in grid:
         E = max(1, args.budget // K)
         options = dict(samples=K, horizon=H, sigma=sigma, lam=lam, gamma=1.0, iterations=1, shift=True, seed=0)
-        success, reward, last, wall = [], [], [], 0.0
-        for first in range(0, len(points) - E + 1, E) if len(points) >= E else [0]:
-            batch = points[first:first + E]
-            env = make_vec(env_id, num_envs=len(batch), device=args.device, seed=4, auto_reset=False)
-            env.reset(seed=4)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            res = run_closed_loop_mppi(env, batch, max_steps=args.steps, first_draw=0, **options)  # ends in a device synchronise
-            wall += time.perf_counter() - t0
-            success.append(res["success"]), reward.append(res["reward"]), last.append(res["last_step"])
-            env.close()
-        success, reward, last = (np.concatenate(x) for x in (success, reward, last))
+        success, reward, last, wall = protocol(env_id, points, E, args.steps, args.device, options)
         env = make_vec(env_id, num_envs=E, device=args.device, seed=4, auto_reset=False)
         env.reset(seed=4)
         plan_ms, own_ms = control_step_time(env, options, args.repeats)
         env.close()
-        row = dict(K=K, H=H, sigma=sigma, lam=lam, E=E, planner_envs=E * K, trials=int(success.size), success_rate_percent=100.0 * float(success.mean()),
-                   mean_episode_reward=float(reward.mean()), mean_last_step_index=float(last.mean()),
-                   early_fail_percent=100.0 * float((~success & (last < args.steps - 1)).mean()), timeout_percent=100.0 * float((last >= args.steps - 1).mean()),
+        row = dict(K=K, H=H, sigma=sigma, lam=lam, E=E, planner_envs=E * K, **figures(success, reward, last, args.steps),
                    plan_ms=plan_ms, planner_kernels_ms=own_ms, planner_kernels_share=own_ms / plan_ms,
                    control_steps_per_second=1e3 / plan_ms, env_control_steps_per_second=E * 1e3 / plan_ms,
                    closed_loop_wall_seconds_including_setup=wall)
+        if guide:
+            guided = dict(options, **guide)
+            success, reward, last, wall = protocol(env_id, points, E, args.steps, args.device, guided)
+            env = make_vec(env_id, num_envs=E, device=args.device, seed=4, auto_reset=False)
+            env.reset(seed=4)
+            guided_ms, added_ms = guided_step_time(env, guided, args.repeats)
+            env.close()
+            row["guided"] = dict({k: v for k, v in guide.items() if k not in ("actor", "critic")}, **figures(success, reward, last, args.steps),
+                                 plan_ms=guided_ms, plan_ms_over_plain=guided_ms / plan_ms, guide_launches_ms=added_ms, guide_launches_share=added_ms / guided_ms,
+                                 closed_loop_wall_seconds_including_setup=wall)
         rows.append(row)
         print(json.dumps(row), flush=True)
     ref = json.load(open(os.path.join(ROOT, "tests", "golden", "actors", "reference_results.json")))[kind]
@@ -149,6 +242,9 @@ def main():
                timing=f"device events around {args.repeats} urgym_mppi_plan calls after 3 warm-up plans; planner_kernels_ms is the fan-out, sample, H score and update launches alone",
                reference_trained_actor={k: ref[k] for k in ("success_rate_percent", "mean_episode_reward", "mean_last_step_index", "trials")},
                device=torch.cuda.get_device_name(0), grid=rows)
+    if guide:
+        out["guide"] = dict({k: v for k, v in guide.items() if k not in ("actor", "critic")}, actor=args.actor and os.path.basename(args.actor),
+                            critics=args.critics and [os.path.basename(c) for c in args.critics])
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:

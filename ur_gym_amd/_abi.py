@@ -572,6 +572,21 @@ class Mppi(C.Structure):
                 ("seed", C.c_uint64)] + [(name, C.POINTER(ct)) for name, ct, _ in MPPI_FIELDS]
 
 
+# urgym_mppi_guide's device pointers: name -> (ctype of element, shape given (E, K)); each may be NULL where the options do not need it
+MPPI_GUIDE_FIELDS = [
+    ("policy_action", C.c_float, lambda E, K: (E * K, 6)),
+    ("value", C.c_float, lambda E, K: (E * K,)),
+    ("terminal", C.c_double, lambda E, K: (E * K,)),
+]
+
+
+class MppiGuide(C.Structure):
+    """urgym_mppi_guide: the learner in the planner's loop -- an actor and a critic of the PLANNER handle, how they are used, and the
+    caller-owned device arrays they write."""
+    _fields_ = [("actor", C.c_void_p), ("critic", C.c_void_p), ("policy_samples", C.c_int32), ("terminal_value", C.c_int32),
+                ("policy_sigma", C.c_float), ("reserved0", C.c_int32), ("fail_cost", C.c_double)] + [(name, C.POINTER(ct)) for name, ct, _ in MPPI_GUIDE_FIELDS]
+
+
 # Every symbol include/urgym.h declares (tests check that the built library exports each of them).
 EXPORTED_SYMBOLS = [
     "urgym_abi_version",
@@ -651,6 +666,10 @@ EXPORTED_SYMBOLS = [
     "urgym_mppi_record",
     "urgym_mppi_plan",
     "urgym_mppi_control",
+    "urgym_mppi_guide_actions",
+    "urgym_mppi_terminal",
+    "urgym_mppi_plan_guided",
+    "urgym_mppi_control_guided",
     "urgym_refresh",
     "urgym_invalidate_records",
     "urgym_derive_obstacle_motion",

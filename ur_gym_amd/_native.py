@@ -143,6 +143,11 @@ def lib():
     L.urgym_mppi_record.argtypes = [C.c_void_p, C.POINTER(_abi.Mppi), C.c_int, C.c_int, C.POINTER(_abi.Trajectory), C.c_void_p]
     L.urgym_mppi_plan.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.Mppi), C.c_uint64, C.c_void_p]
     L.urgym_mppi_control.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.Mppi), C.c_uint64, C.c_int, C.POINTER(_abi.Trajectory), C.c_void_p]
+    L.urgym_mppi_guide_actions.argtypes = [C.c_void_p, C.POINTER(_abi.Mppi), C.POINTER(_abi.MppiGuide), C.c_int, C.c_void_p]
+    L.urgym_mppi_terminal.argtypes = [C.c_void_p, C.POINTER(_abi.Mppi), C.POINTER(_abi.MppiGuide), C.c_void_p]
+    L.urgym_mppi_plan_guided.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.Mppi), C.POINTER(_abi.MppiGuide), C.c_uint64, C.c_void_p]
+    L.urgym_mppi_control_guided.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.Mppi), C.POINTER(_abi.MppiGuide), C.c_uint64, C.c_int,
+                                            C.POINTER(_abi.Trajectory), C.c_void_p]
     L.urgym_actor_read_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.urgym_critic_read_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.urgym_refresh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]

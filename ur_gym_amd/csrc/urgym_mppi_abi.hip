@@ -1,6 +1,7 @@
-// urgym_mppi_abi.hip -- the planner's entry points of include/urgym.h ("sampling-based MPC on the device").  Host
-// code only, beside urgym_policy_abi.hip: every check is made here, before the first launch; every launch goes through urgym_mppi.h or
-// through do_step of urgym_hip.hip (urgym_handle.h).  As there, each entry point is a checking half, which launches nothing, and a
+// urgym_mppi_abi.hip -- the planner's entry points of include/urgym.h ("sampling-based MPC on the device", "MPPI with the learner in the
+// loop"; DESIGN.md sections 26 and 27).  Host code only, beside urgym_policy_abi.hip: every check is made here, before the first launch;
+// every launch goes through urgym_mppi.h, urgym_mppi_guide.h, the actor's and the critic's own launches (urgym_actor.h, urgym_critic.h)
+// or through do_step of urgym_hip.hip (urgym_handle.h).  As there, each entry point is a checking half, which launches nothing, and a
 // launching half, which refuses nothing.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -8,8 +9,13 @@
 #include <string.h>
 
 #include "../../include/urgym.h"
+#include <algorithm>
+
+#include "urgym_actor.h"
+#include "urgym_critic.h"
 #include "urgym_handle.h"
 #include "urgym_mppi.h"
+#include "urgym_mppi_guide.h"
 
 using namespace urgym;
 
@@ -131,26 +137,133 @@ MppiRecord record_of(const Handle* sh, const urgym_mppi& m, const urgym_trajecto
   return r;
 }
 
-// the launches of one plan; everything has been checked
-int plan(Handle* sh, Handle* ph, const urgym_mppi& m, uint64_t draw, hipStream_t s) {
+// ---- the guide (urgym_mppi_guide): what a guided plan launches besides the plain one's, resolved by check_guide
+struct Guide {
+  Actor* actor = nullptr;    // launched where P > 0 or terminal_value
+  Critic* critic = nullptr;  // launched with terminal_value
+  bool terminal = false;     // the terminal launch is made: terminal_value or fail_cost > 0
+  float* policy_action = nullptr;  // what the actor writes
+  float* value = nullptr;          // what the critic writes
+  MppiGuideCall call;
+};
+
+// the checks that concern urgym_mppi_guide; m and the planner have been checked.  `report` keeps the message.
+int check_guide(Handle* report, Handle* ph, const urgym_mppi* m, const urgym_mppi_guide* g, const char* who, Guide* out) {
+  static_assert(sizeof(urgym_mppi_guide) == 64 && alignof(urgym_mppi_guide) == 8, "include/urgym.h");
+  if (!g) return fail_in(report, URGYM_ERR_ARG, who, "null urgym_mppi_guide");
+  const bool wants_value = g->terminal_value != 0;
+  const char* what = nullptr;
+  if (g->reserved0 != 0) what = "urgym_mppi_guide.reserved0 must be 0";
+  else if (g->policy_samples < 0 || g->policy_samples > m->samples - 1) what = "urgym_mppi_guide.policy_samples must be in [0, samples - 1]";
+  else if (!isfinite(g->policy_sigma) || g->policy_sigma < 0.0f) what = "urgym_mppi_guide.policy_sigma must be finite and not negative";
+  else if (!isfinite(g->fail_cost) || g->fail_cost < 0.0) what = "urgym_mppi_guide.fail_cost must be finite and not negative";
+  else if (g->policy_samples > 0 && !g->actor) what = "urgym_mppi_guide.actor is null with policy_samples > 0";
+  else if (wants_value && !g->actor) what = "urgym_mppi_guide.actor is null with terminal_value";
+  else if (wants_value && !g->critic) what = "urgym_mppi_guide.critic is null with terminal_value";
+  if (what) return fail_in(report, URGYM_ERR_ARG, who, what);
+  const int features = ph->obs_dim + 2 * ph->goal_dim;
+  Guide r;
+  if (g->actor) {
+    if (std::find(ph->actors.begin(), ph->actors.end(), (Actor*)g->actor) == ph->actors.end())
+      return fail_in(report, URGYM_ERR_ARG, who, "urgym_mppi_guide.actor is not an actor of the planner handle (actors belong to the handle they were created with)");
+    r.actor = (Actor*)g->actor;
+    if (actor_in_features(r.actor) != features)
+      return failf(report, URGYM_ERR_ARG, "%s: urgym_mppi_guide.actor takes %d features, this env kind offers %d", who, actor_in_features(r.actor), features);
+  }
+  if (g->critic) {
+    if (std::find(ph->critics.begin(), ph->critics.end(), (Critic*)g->critic) == ph->critics.end())
+      return fail_in(report, URGYM_ERR_ARG, who, "urgym_mppi_guide.critic is not a critic of the planner handle (critics belong to the handle they were created with)");
+    r.critic = (Critic*)g->critic;
+    if (critic_in_features(r.critic) != features + 6) return fail_in(report, URGYM_ERR_ARG, who, "urgym_mppi_guide.critic does not take this env kind's features");
+  }
+  r.terminal = wants_value || g->fail_cost > 0.0;
+  if ((g->policy_samples > 0 || wants_value) && !g->policy_action) what = "urgym_mppi_guide.policy_action is null";
+  else if (wants_value && !g->value) what = "urgym_mppi_guide.value is null with terminal_value";
+  else if (r.terminal && !g->terminal) what = "urgym_mppi_guide.terminal is null";
+  if (what) return fail_in(report, URGYM_ERR_ARG, who, what);
+  if (g->policy_samples == 0 && !wants_value) r.actor = nullptr;  // given, not used
+  if (!wants_value) r.critic = nullptr;
+  r.policy_action = g->policy_action, r.value = g->value;
+  r.call = MppiGuideCall{g->policy_samples, wants_value ? 1 : 0, g->policy_sigma, g->fail_cost, g->policy_action, g->value, g->terminal};
+  *out = r;
+  return URGYM_OK;
+}
+
+// urgym_actor_forward's launch on the planner's bound rows (actor_env of urgym_policy_abi.hip)
+void policy_launch(const Handle* ph, const Guide& gd, hipStream_t s) {
+  const urgym_buffers& b = ph->buf;
+  const ActorEnv env{ph->cfg.num_envs, ph->obs_dim, ph->goal_dim, ph->cfg.auto_reset, b.observation, b.achieved_goal, b.desired_goal,
+                     b.reward, b.final_observation, b.terminated, b.truncated, b.is_success, b.collision};
+  actor_launch(gd.actor, env, gd.policy_action, nullptr, s);
+}
+
+// urgym_critic_evaluate's launch on the planner's bound rows with action = policy_action, out.q_min = value and nothing else asked for
+void value_launch(const Handle* ph, const Guide& gd, hipStream_t s) {
+  CriticCall call;
+  memset(&call, 0, sizeof(call));
+  call.M = ph->cfg.num_envs, call.obs_dim = ph->obs_dim, call.goal_dim = ph->goal_dim;
+  call.observation = ph->buf.observation, call.achieved_goal = ph->buf.achieved_goal, call.desired_goal = ph->buf.desired_goal;
+  call.action = gd.policy_action;
+  call.q_min = gd.value;
+  critic_launch(gd.critic, call, s);
+}
+
+// the launches of one plan; everything has been checked.  gd == nullptr: the plain plan.
+int plan(Handle* sh, Handle* ph, const urgym_mppi& m, uint64_t draw, hipStream_t s, const Guide* gd = nullptr) {
   const size_t row = (size_t)ph->cfg.num_envs * 6;
   const MppiFanout f = fanout_of(sh, ph, m);
   const MppiOutcome o = outcome_of(ph);
+  const bool proposes = gd && gd->call.policy_samples > 0;
   for (int i = 0; i < m.iterations; i++) {
     mppi_fanout_launch(f, s);
     mppi_sample_launch(m, draw, i, s);
     for (int h = 0; h < m.horizon; h++) {
+      if (proposes) {
+        policy_launch(ph, *gd, s);
+        mppi_guide_launch(m, gd->call, h, s);
+      }
       if (int rc = do_step(ph, m.actions + (size_t)h * row, s)) {
         if (ph != sh) memcpy(sh->err, ph->err, sizeof(sh->err));  // the caller asks the source
         return rc;
       }
       mppi_score_launch(m, o, h, s);
     }
+    if (gd && gd->critic) {
+      policy_launch(ph, *gd, s);
+      value_launch(ph, *gd, s);
+    }
+    if (gd && gd->terminal) mppi_terminal_launch(m, gd->call, s);
     urgym_mppi last = m;
     if (i + 1 < m.iterations) last.shift = 0;  // the sequence advances once, after the last refinement
     mppi_update_launch(last, s);
   }
   return URGYM_OK;
+}
+
+// the launches of the closed loop; everything has been checked.  Every launch goes to `s`: stream order alone puts a plan's update
+// before the source step that reads action_out, and that step before the record pass that files its outcome and the fan-out that
+// clones its state.
+int control(Handle* sh, Handle* ph, const urgym_mppi& m, uint64_t first_draw, int num_steps, const urgym_trajectory* traj, hipStream_t s, const Guide* gd = nullptr) {
+  mppi_record_launch(record_of(sh, m, traj, 0, num_steps), s);
+  for (int t = 0; t < num_steps; t++) {
+    if (int rc = plan(sh, ph, m, first_draw + (uint64_t)t, s, gd)) return rc;
+    if (int rc = do_step(sh, m.action_out, s)) return rc;
+    mppi_record_launch(record_of(sh, m, traj, t + 1, num_steps), s);
+  }
+  return URGYM_OK;
+}
+
+// the checks of the two composed guided calls after check_pair
+int check_guided_pair(Handle* sh, Handle* ph, const urgym_mppi* m, const urgym_mppi_guide* g, const char* who, Guide* out) {
+  if (int rc = check_pair(sh, ph, m, who)) return rc;
+  return check_guide(sh, ph, m, g, who, out);
+}
+
+// the checks of the two single guided launches: the planner keeps the message
+int check_guided_planner(Handle* ph, const urgym_mppi* m, const urgym_mppi_guide* g, const char* who, Guide* out) {
+  if (int rc = check_mppi(ph, m, who)) return rc;
+  if (int rc = check_planner(ph, ph, m, who)) return rc;
+  return check_guide(ph, ph, m, g, who, out);
 }
 
 }  // namespace
@@ -232,14 +345,56 @@ int urgym_mppi_control(void* source_handle, void* planner_handle, const urgym_mp
   if (int rc = check_record(sh, 0, num_steps, traj_or_NULL, who)) return rc;
   if (int rc = check_draw(sh, first_draw, num_steps, who)) return rc;
   HIP_TRY(sh, hipSetDevice(sh->device));
-  // Every launch goes to `s`: stream order alone puts a plan's update before the source step that reads action_out, and that step
-  // before the record pass that files its outcome and the fan-out that clones its state.
-  mppi_record_launch(record_of(sh, *m, traj_or_NULL, 0, num_steps), s);
-  for (int t = 0; t < num_steps; t++) {
-    if (int rc = plan(sh, ph, *m, first_draw + (uint64_t)t, s)) return rc;
-    if (int rc = do_step(sh, m->action_out, s)) return rc;
-    mppi_record_launch(record_of(sh, *m, traj_or_NULL, t + 1, num_steps), s);
-  }
+  if (int rc = control(sh, ph, *m, first_draw, num_steps, traj_or_NULL, s)) return rc;
+  return launched(sh);
+}
+
+int urgym_mppi_guide_actions(void* planner_handle, const urgym_mppi* m, const urgym_mppi_guide* g, int h, void* stream) {
+  const char* who = "urgym_mppi_guide_actions";
+  Handle* ph = (Handle*)planner_handle;
+  Guide gd;
+  if (!ph) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (int rc = check_guided_planner(ph, m, g, who, &gd)) return rc;
+  if (h < 0 || h >= m->horizon) return fail_in(ph, URGYM_ERR_ARG, who, "h must be in [0, horizon)");
+  HIP_TRY(ph, hipSetDevice(ph->device));
+  if (gd.call.policy_samples > 0) mppi_guide_launch(*m, gd.call, h, (hipStream_t)stream);  // P == 0: no sample follows the actor
+  return launched(ph);
+}
+
+int urgym_mppi_terminal(void* planner_handle, const urgym_mppi* m, const urgym_mppi_guide* g, void* stream) {
+  const char* who = "urgym_mppi_terminal";
+  Handle* ph = (Handle*)planner_handle;
+  Guide gd;
+  if (!ph) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (int rc = check_guided_planner(ph, m, g, who, &gd)) return rc;
+  if (!gd.terminal) return fail_in(ph, URGYM_ERR_ARG, who, "neither urgym_mppi_guide.terminal_value nor fail_cost > 0: there is no terminal launch");
+  HIP_TRY(ph, hipSetDevice(ph->device));
+  mppi_terminal_launch(*m, gd.call, (hipStream_t)stream);
+  return launched(ph);
+}
+
+int urgym_mppi_plan_guided(void* source_handle, void* planner_handle, const urgym_mppi* m, const urgym_mppi_guide* g, uint64_t draw, void* stream) {
+  const char* who = "urgym_mppi_plan_guided";
+  Handle *sh = (Handle*)source_handle, *ph = (Handle*)planner_handle;
+  Guide gd;
+  if (!sh) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (int rc = check_guided_pair(sh, ph, m, g, who, &gd)) return rc;
+  if (int rc = check_draw(sh, draw, 1, who)) return rc;
+  HIP_TRY(sh, hipSetDevice(sh->device));
+  if (int rc = plan(sh, ph, *m, draw, (hipStream_t)stream, &gd)) return rc;
+  return launched(sh);
+}
+
+int urgym_mppi_control_guided(void* source_handle, void* planner_handle, const urgym_mppi* m, const urgym_mppi_guide* g, uint64_t first_draw, int num_steps, const urgym_trajectory* traj_or_NULL, void* stream) {
+  const char* who = "urgym_mppi_control_guided";
+  Handle *sh = (Handle*)source_handle, *ph = (Handle*)planner_handle;
+  Guide gd;
+  if (!sh) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (int rc = check_guided_pair(sh, ph, m, g, who, &gd)) return rc;
+  if (int rc = check_record(sh, 0, num_steps, traj_or_NULL, who)) return rc;
+  if (int rc = check_draw(sh, first_draw, num_steps, who)) return rc;
+  HIP_TRY(sh, hipSetDevice(sh->device));
+  if (int rc = control(sh, ph, *m, first_draw, num_steps, traj_or_NULL, (hipStream_t)stream, &gd)) return rc;
   return launched(sh);
 }
 

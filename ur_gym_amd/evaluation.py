@@ -2685,6 +2685,45 @@ def mppi_update(ret, w, actions, shift):
     return dict(new_mean=new_mean, mean=mean, action_out=new_mean[0].copy(), best_return=rmax, nominal_return=r[:, 0].copy(), ess=ess)
 
 
+def mppi_guided_actions(actions, policy_action, eps, policy_sigma, samples, policy_samples):
+    """THE GUIDE in numpy, bitwise (include/urgym.h, "MPPI with the learner in the loop"): `actions` and `eps` float32 [H, E * K, 6] as the
+    sample launch left them, `policy_action` float32 [H, E * K, 6] -- row h what the actor gave before planner step h -- or [E * K, 6] for
+    every step alike.  Returns a copy of `actions` in which the rows of samples 1 .. `policy_samples` of every parent are
+    s = policy_sigma * eps; a = policy_action + s; fmin(fmax(a, -1), 1), each one float32 operation; every other row is `actions`'."""
+    actions, eps, pa = np.asarray(actions), np.asarray(eps), np.asarray(policy_action)
+    K, P = int(samples), int(policy_samples)
+    if actions.dtype != np.float32 or eps.dtype != np.float32 or pa.dtype != np.float32 or actions.ndim != 3 or actions.shape != eps.shape:
+        raise ValueError(f"actions and eps must be float32 [H, E * K, 6] and policy_action float32, got {actions.dtype} {actions.shape}, {eps.dtype} {eps.shape}, {pa.dtype}")
+    if pa.shape not in (actions.shape, actions.shape[1:]) or actions.shape[1] % K or not 0 <= P <= K - 1:
+        raise ValueError(f"policy_action must be [H, E * K, 6] or [E * K, 6] and policy_samples in [0, samples - 1], got {pa.shape}, {P}, {K}")
+    j = np.arange(actions.shape[1]) % K
+    guided = (j >= 1) & (j <= P)
+    with np.errstate(all="ignore"):
+        s = np.float32(policy_sigma) * eps
+        a = np.broadcast_to(pa, actions.shape) + s
+        line = np.fmin(np.fmax(a, np.float32(-1)), np.float32(1))
+    out = actions.copy()
+    out[:, guided] = line[:, guided]
+    return out
+
+
+def mppi_terminal(score, value, terminal_value, fail_cost):
+    """THE TERMINAL STEP in numpy, bitwise: `score` is ``mppi_score``'s dict (ret, g, alive, success are read), `value` float32 [N] or None
+    where `terminal_value` is off.  v = value for a live future (0 with `terminal_value` off), 0 for one that ended in success, -fail_cost
+    for one that ended otherwise -- a selection, so a NaN value of an ended future reaches nothing; where v != 0, t = g * v and
+    ret = ret + t in float64.  Returns dict(terminal [N], ret [N])."""
+    ret, g = np.asarray(score["ret"], dtype=np.float64), np.asarray(score["g"], dtype=np.float64)
+    alive, success = np.asarray(score["alive"]) != 0, np.asarray(score["success"]) != 0
+    live = np.asarray(value, dtype=np.float32).astype(np.float64) if terminal_value else np.zeros(ret.shape, np.float64)
+    if live.shape != ret.shape:
+        raise ValueError(f"value must be [N] like ret, got {live.shape}, {ret.shape}")
+    v = np.where(alive, live, np.where(success, np.float64(0.0), -np.float64(fail_cost)))
+    with np.errstate(all="ignore"):
+        t = g * v
+        new = np.where(v != 0, ret + t, ret)
+    return dict(terminal=v, ret=new)
+
+
 class DeviceMPPI:
     """An MPPI planner (Williams et al., 2017) for `env`, a UR5ReachVectorEnv of E envs, that plans with the step kernel itself: it owns a
     planner environment of E * `samples` envs (same env id, configuration and device, ``auto_reset=False``) and every buffer of
@@ -2693,11 +2732,19 @@ class DeviceMPPI:
     from the refined mean.  `sigma` is the standard deviation of the perturbation in action units ([-1, 1] per joint), `gamma` the
     discount inside the horizon.  With `shift` the nominal sequence advances by one step after each plan (receding horizon).  The
     defaults of `horizon`, `sigma` and `lam` are a row of the grid tools/bench_mppi.py ran on UR5DynReach-v1 and UR5OriReach-v1 (DESIGN.md
-    section 26); a horizon whose summed step rewards outweigh the collision penalty makes ending the episode the best-scoring future."""
+    section 26); a horizon whose summed step rewards outweigh the collision penalty makes ending the episode the best-scoring future.
+
+    The learner in the loop, all opt-in.  `actor` and `critic` are what ``DeviceActor`` and ``DeviceCritic`` take
+    (the weights, or a path / a pair of paths to load them from); they are created on the planner environment and closed with it, and
+    see its raw rows.  `policy_samples` = P in [0, samples - 1]: samples 1 .. P of every parent execute actor(state) + `policy_sigma` *
+    noise at every horizon step.  `terminal_value`: a future still alive after the horizon is credited gamma^H min Q(s_H, actor(s_H));
+    the shipped critics were trained with gamma = 0.95, so use ``gamma=0.95`` with them.  `fail_cost`: a future that ends without success
+    is charged that much, discounted.  With all four at their defaults the plain entry points are called as before."""
 
     DIAGNOSTICS = ("best_return", "nominal_return", "ess")
 
-    def __init__(self, env, samples=256, horizon=6, sigma=0.6, lam=5.0, gamma=1.0, iterations=1, shift=True, seed=0, keep_weights=False):
+    def __init__(self, env, samples=256, horizon=6, sigma=0.6, lam=5.0, gamma=1.0, iterations=1, shift=True, seed=0, keep_weights=False,
+                 actor=None, critic=None, policy_samples=0, policy_sigma=0.0, terminal_value=False, fail_cost=0.0):
         import ctypes as C
 
         import torch
@@ -2725,10 +2772,56 @@ class DeviceMPPI:
             self.buf[name] = torch.zeros(shape(E, K, H), dtype=_TORCH_DTYPE[ct], device=env.device)
             setattr(M, name, C.cast(self.buf[name].data_ptr(), C.POINTER(ct)))
         self._struct = M
+        self.actor = self.critic = self._guide = None
+        P = int(policy_samples)
+        if P or terminal_value or fail_cost or policy_sigma:
+            try:
+                self._guide = self._make_guide(actor, critic, P, float(policy_sigma), bool(terminal_value), float(fail_cost))
+            except Exception:
+                self.close()
+                raise
+
+    def _make_guide(self, actor, critic, P, policy_sigma, terminal_value, fail_cost):
+        import ctypes as C
+        import os
+
+        import torch
+
+        from . import _abi
+        from .vector_env import _TORCH_DTYPE
+
+        E, K = self.env.num_envs, self.samples
+        if not 0 <= P <= K - 1:
+            raise ValueError(f"DeviceMPPI: policy_samples must be in [0, samples - 1], got {P}")
+        if not (np.isfinite(policy_sigma) and policy_sigma >= 0 and np.isfinite(fail_cost) and fail_cost >= 0):
+            raise ValueError(f"DeviceMPPI: policy_sigma and fail_cost must be finite and >= 0, got {policy_sigma}, {fail_cost}")
+        if (P or terminal_value) and actor is None:
+            raise ValueError("DeviceMPPI: policy_samples > 0 and terminal_value need actor=")
+        if terminal_value and critic is None:
+            raise ValueError("DeviceMPPI: terminal_value needs critic=")
+        G = _abi.MppiGuide()
+        G.policy_samples, G.terminal_value, G.policy_sigma, G.fail_cost = P, int(terminal_value), policy_sigma, fail_cost
+        if actor is not None and (P or terminal_value):
+            self.actor = DeviceActor.load(actor, self.planner) if isinstance(actor, (str, os.PathLike)) else DeviceActor(actor, self.planner)
+            G.actor = self.actor._a
+        if critic is not None and terminal_value:
+            paths = isinstance(critic, (tuple, list)) and all(isinstance(c, (str, os.PathLike)) for c in critic)
+            self.critic = DeviceCritic.load(critic, self.planner) if paths else DeviceCritic(critic, self.planner)
+            G.critic = self.critic._c
+        needed = {"policy_action": bool(P or terminal_value), "value": terminal_value, "terminal": terminal_value or fail_cost > 0}
+        for name, ct, shape in _abi.MPPI_GUIDE_FIELDS:
+            if needed[name]:
+                self.buf[name] = torch.zeros(shape(E, K), dtype=_TORCH_DTYPE[ct], device=self.env.device)
+                setattr(G, name, C.cast(self.buf[name].data_ptr(), C.POINTER(ct)))
+        return G
 
     def struct(self):
         """The ``urgym_mppi`` of this planner (its pointers stay valid until ``close``)."""
         return self._struct
+
+    def guide(self):
+        """The ``urgym_mppi_guide`` of this planner, or None where the learner is not in the loop."""
+        return self._guide
 
     def plan(self, draw=0):
         """One ``urgym_mppi_plan`` from the environment's state as it stands.  Returns (action_out [E, 6], diagnostics): views of this
@@ -2739,8 +2832,11 @@ class DeviceMPPI:
         from . import _native
 
         env = self.env
-        _native.check(env.lib.urgym_mppi_plan(env._h, self.planner._h, C.byref(self._struct), int(draw), env._stream()), env._h)
-        return self.buf["action_out"], {k: self.buf[k] for k in self.DIAGNOSTICS}
+        if self._guide is None:
+            _native.check(env.lib.urgym_mppi_plan(env._h, self.planner._h, C.byref(self._struct), int(draw), env._stream()), env._h)
+        else:
+            _native.check(env.lib.urgym_mppi_plan_guided(env._h, self.planner._h, C.byref(self._struct), C.byref(self._guide), int(draw), env._stream()), env._h)
+        return self.buf["action_out"], {k: self.buf[k] for k in self.DIAGNOSTICS + (("terminal",) if "terminal" in self.buf else ())}
 
     def run(self, num_steps, first_draw=0, record=("reward", "terminated", "truncated", "is_success")):
         """`num_steps` x (plan, step the environment with the plan's first action) in ONE native call (``urgym_mppi_control``); step t
@@ -2769,8 +2865,12 @@ class DeviceMPPI:
                 t = torch.zeros(shape(T, env.num_envs, env.obs_dim, env.goal_dim), dtype=_TORCH_DTYPE[ct], device=env.device)
                 setattr(traj, name, C.cast(t.data_ptr(), C.POINTER(ct)))
                 out[name] = t.view(torch.bool) if ct is C.c_uint8 else t
-        _native.check(env.lib.urgym_mppi_control(env._h, self.planner._h, C.byref(self._struct), int(first_draw), T, C.byref(traj) if names else None,
-                                                 env._stream()), env._h)
+        if self._guide is None:
+            _native.check(env.lib.urgym_mppi_control(env._h, self.planner._h, C.byref(self._struct), int(first_draw), T, C.byref(traj) if names else None,
+                                                     env._stream()), env._h)
+        else:
+            _native.check(env.lib.urgym_mppi_control_guided(env._h, self.planner._h, C.byref(self._struct), C.byref(self._guide), int(first_draw), T,
+                                                            C.byref(traj) if names else None, env._stream()), env._h)
         return out
 
     def reset_plan(self, mask=None):
@@ -2783,6 +2883,10 @@ class DeviceMPPI:
             self.buf["mean"][:, torch.as_tensor(mask, device=self.env.device)] = 0.0
 
     def close(self):
+        for name in ("actor", "critic"):  # they live in the planner's handle
+            if getattr(self, name, None) is not None:
+                getattr(self, name).close()
+                setattr(self, name, None)
         if getattr(self, "planner", None) is not None:
             self.planner.close()
             self.planner = None
