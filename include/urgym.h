@@ -1834,6 +1834,9 @@ int urgym_sac_train_normalized(void* handle, const urgym_sac_learner* learner, c
  * p has just finished (terminated | truncated), so that a new episode does not start from the old plan.  traj may be NULL (only the
  * zeroing is left); episode_done is required when any of the three other summary arrays is given. */
 #define URGYM_MPPI_TAG 0x4D505000u
+/* Blocks 0 and 1 under the tag are THE SAMPLE's.  Blocks 2 and 3 are the exploration noise of urgym_mppi_execute (below, "planner-
+ * collected experience"): counter = (p, 0, (uint32)draw, URGYM_MPPI_TAG | block), block = URGYM_MPPI_EXPLORE_BLOCK, + 1. */
+#define URGYM_MPPI_EXPLORE_BLOCK 2
 #define URGYM_MPPI_SAMPLES_MAX 1024
 #define URGYM_MPPI_HORIZON_MAX 64
 #define URGYM_MPPI_ITERATIONS_MAX 8
@@ -1953,6 +1956,63 @@ int urgym_mppi_plan_guided(void* source_handle, void* planner_handle, const urgy
 /* THE GUIDED CLOSED LOOP: urgym_mppi_control with urgym_mppi_plan_guided in place of urgym_mppi_plan, bit for bit.  Refused:
  * everything urgym_mppi_plan_guided and urgym_mppi_control refuse. */
 int urgym_mppi_control_guided(void* source_handle, void* planner_handle, const urgym_mppi* m, const urgym_mppi_guide* g, uint64_t first_draw, int num_steps, const urgym_trajectory* traj_or_NULL, void* stream);
+
+/* ---- planner-collected experience: MPPI files its transitions into the ring.  urgym_mppi_control(_guided)
+ * writes a urgym_trajectory, an evaluation record; urgym_rollout_collect fills the replay ring but takes an actor.  The two calls below
+ * are a collection whose policy is the planner, so that an off-policy learner can train on what the planner did.  Added WITHIN ABI
+ * version 4: no struct above changed, the two new symbols are found by lookup, and urgym_mppi_plan, urgym_mppi_control, their guided
+ * forms and urgym_rollout_collect are what they were.  The ring is filled by urgym_rollout_collect's own store pass, so every gather
+ * (one-step, multi-step, prioritized, hindsight), urgym_monitor_fold and urgym_norm_fold read the slots as they read a policy's.
+ *
+ * THE EXPLORATION NOISE.  For source env (parent) p and draw d, six normals e[p][0 .. 5]: Box-Muller exactly as THE SAMPLE above forms
+ * its own (u1, u2, r, cos, sin; pairs 0, 1, 2 from the words w0 .. w5) on the words of Philox4x32-10 with the planner's key,
+ * (m->seed & 0xFFFFFFFF, m->seed >> 32), and
+ *   counter = (p, 0, (uint32)d, URGYM_MPPI_TAG | block),  block = 2, 3
+ * (w0 .. w3 from block 2, w4 and w5 from block 3).  THE SAMPLE's counters carry block 0 or 1 in the same word, so no exploration
+ * counter meets a sample counter, whatever (i, h, j) are; the other tags are those THE SAMPLE lists.  The noise is a function of
+ * (seed, d, p, c) only -- not of E or the launch geometry.
+ *
+ * THE EXECUTE LINE (urgym_mppi_execute, one launch, one lane per (p, c), float32, one operation per line):
+ *   s = explore_sigma * e[p][c];  a = action_out[p][c] + s;  executed[p][c] = fminf(fmaxf(a, -1), 1)
+ * With explore_sigma == 0 no Philox word is drawn and executed[p][c] is the 32 bits of action_out[p][c] (a -0.0 stays -0.0).
+ * explore_eps[p][c], where given, receives e[p][c], or 0 with explore_sigma == 0.  A NaN in action_out reaches its own element only.
+ * The launch has no LDS and no atomics, one writer per output, and writes executed and explore_eps only. */
+typedef struct urgym_mppi_explore {
+  float explore_sigma;   /* finite, >= 0 */
+  int32_t reserved0;     /* must be 0 */
+  float* explore_eps;    /* [E][6] or NULL */
+} urgym_mppi_explore;
+
+/* The single launch.  Refused (the source keeps the message): a NULL handle; everything urgym_mppi_record refuses about m and the source
+ * (an unbound source, source num_envs != E); a NULL x; a non-zero reserved0; explore_sigma not finite or < 0; a NULL executed;
+ * draw >= 2^32. */
+int urgym_mppi_execute(void* source_handle, const urgym_mppi* m, const urgym_mppi_explore* x, uint64_t draw, float* executed /* [E][6] */, void* stream);
+
+/* THE COLLECTION.  With C = ring->capacity_steps and slot(t) = (first_slot + t) % C, for t < num_steps:
+ *   1. store pass t: urgym_rollout_collect's store launch, sequenced as there -- the source's live rows are at once the s of step t
+ *      (into slot(t)) and, for t > 0, the s' of step t - 1 (into slot(t - 1), with its reward and flags; the final_* rows in place of the
+ *      live ones for an env that finished under auto_reset);
+ *   2. for t > 0, record pass t with a NULL trajectory (THE RECORD above): it zeroes mean[:, p, :] of every source env p that has just
+ *      finished, as urgym_mppi_control does;
+ *   3. the plan: urgym_mppi_plan, or urgym_mppi_plan_guided where a guide is given, with draw = first_draw + t;
+ *   4. the execute launch with draw = first_draw + t and executed = the action rows of slot(t): the planner's action is written straight
+ *      into the ring, as the actor's is in urgym_rollout_collect;
+ *   5. urgym_step(source, those rows).
+ * After the loop: store pass num_steps (the outcome of the last step into slot(num_steps - 1)) and record pass num_steps.
+ * Launches: per step one store pass, one record pass (none at t == 0) and one execute launch besides the plan's and the step's own,
+ * and one store pass and one record pass after the loop: 3 num_steps + 1 in all besides num_steps plans and num_steps steps.
+ *
+ * A slot is complete when the call returns.  num_steps may exceed C (the ring wraps; later steps overwrite earlier ones of the same
+ * call).  No launch writes a slot other than those of the call's own steps.  No allocation, no host synchronisation; everything is
+ * validated before the first launch.  Afterwards the source's bound buffers hold what num_steps calls of urgym_step with those actions
+ * would have left, and mean is carried to the next call: two calls of a and b steps, the second with first_draw + a and the slot after
+ * the first's last, leave the bits of one call of a + b steps.  With explore_sigma == 0 the ring's action, reward and flags are, bit for
+ * bit, what urgym_mppi_control(_guided) with the same arguments records in its trajectory.  x->explore_eps, where given, holds the
+ * noise of the LAST step.  The planner's actor and critic read raw rows: a policy trained on normalized observations is not served.
+ * Refused, each launching and writing nothing: everything urgym_mppi_control (guide_or_NULL == NULL) or urgym_mppi_control_guided
+ * refuses about its arguments; everything urgym_rollout_collect refuses about the ring, first_slot, num_steps and a source that has
+ * observed nothing; a NULL x; a non-zero reserved0; explore_sigma not finite or < 0. */
+int urgym_mppi_collect(void* source_handle, void* planner_handle, const urgym_mppi* m, const urgym_mppi_guide* guide_or_NULL, const urgym_mppi_explore* x, uint64_t first_draw, int num_steps, const urgym_replay_ring* ring, int first_slot, void* stream);
 
 /* Replaces Reach*.set_goal / set_goal_and_obstacle (reach.py:202-204, 328-335, 702-713): the caller has
  * overwritten goal / obst_start / obst_end (and possibly q) for the masked envs; this recomputes obstacle pose,

@@ -28,6 +28,12 @@ and the update read observations and rewards normalized with running statistics,
 its actor on rows normalized with the TRAINING statistics as they then stand (sync_envs_normalization) -- with --native inside the one
 call (urgym_policy_evaluate_normalized), otherwise step by step from this script -- and --save-best writes the statistics the best actor
 was selected under beside it (evaluation.load_best_normalization reads them).
+--planner collects with an MPPI planner in place of the sampled policy (SACLearner.collect(planner=), urgym_mppi_collect; DESIGN.md section
+28): every trip plans with --planner-samples futures per env over --planner-horizon steps, optionally guided by the learner's own actor
+(--planner-policy-samples) and critic (--planner-terminal-value), executes the plan's first action plus --planner-explore-sigma times
+exploration noise, and after the trip's updates puts the planner's actor and critic on the learner's parameters (SACLearner.sync_planner).
+The Python loop only: not with --native (the native training call has no planner option yet) and not with --normalize (the planner's
+actor and critic read raw rows).  It prints what it prints without.
 """
 import argparse
 import json
@@ -107,7 +113,22 @@ def main():
     ap.add_argument("--init-from", nargs=3, metavar=("ACTOR.npz", "CRITIC0.npz", "CRITIC1.npz"), default=None,
                     help="warm start from plain parameter files (the reference's SAC.load then learn, train.py:31-36): the actor's eight "
                          "arrays as --save-best writes them, one file per Q-network; moments and step count start at zero")
+    ap.add_argument("--planner", action="store_true",
+                    help="collect with an MPPI planner on the step kernel instead of the sampled policy, from the first trip on "
+                         "(SACLearner.collect(planner=); the Python loop only: not with --native or --normalize)")
+    ap.add_argument("--planner-samples", type=int, default=64, help="--planner: futures per env, in [2, 1024]; the planner steps num-envs times as many envs")
+    ap.add_argument("--planner-horizon", type=int, default=6, help="--planner: steps of a future, in [1, 64]")
+    ap.add_argument("--planner-sigma", type=float, default=0.6, help="--planner: standard deviation of the sampled action sequences")
+    ap.add_argument("--planner-lam", type=float, default=5.0, help="--planner: the temperature of the weights")
+    ap.add_argument("--planner-policy-samples", type=int, default=0, help="--planner: futures per env that follow the learner's actor, in [0, samples - 1]")
+    ap.add_argument("--planner-policy-sigma", type=float, default=0.1, help="--planner: noise on the actions of the futures that follow the actor")
+    ap.add_argument("--planner-terminal-value", action="store_true",
+                    help="--planner: credit a future alive after the horizon with the learner's min Q of the state it stops in (the planner then discounts with the learner's gamma)")
+    ap.add_argument("--planner-fail-cost", type=float, default=0.0, help="--planner: what a future that ends without success is charged")
+    ap.add_argument("--planner-explore-sigma", type=float, default=0.0, help="--planner: standard deviation of the exploration noise on the executed action")
     args = ap.parse_args()
+    if args.planner and (args.native or args.normalize):
+        raise SystemExit("--planner runs the Python loop on raw rows: not with --native (the native training call has no planner option yet) or --normalize")
     if args.save_every and not args.save:
         raise SystemExit("--save-every needs --save")
     if args.save_every < 0:
@@ -118,7 +139,7 @@ def main():
     import torch
 
     from ur_gym_amd import make_vec
-    from ur_gym_amd.evaluation import DeviceActor, DeviceEvaluation, DeviceMonitor, DevicePrioritizedReplay, DeviceReplay, evaluation_points, run_closed_loop_device, save_actor, warmup_iterations
+    from ur_gym_amd.evaluation import DeviceActor, DeviceEvaluation, DeviceMonitor, DeviceMPPI, DevicePrioritizedReplay, DeviceReplay, evaluation_points, run_closed_loop_device, save_actor, warmup_iterations
     from ur_gym_amd.training import SACLearner, host_arrays
 
     if not torch.cuda.is_available():
@@ -138,6 +159,15 @@ def main():
     normalizer = learner.normalizer  # None without --normalize
     eval_actor = DeviceActor(host_arrays(learner.actor.tensors()), test_env)  # actors belong to the environment they were made for
     replay = DevicePrioritizedReplay(env, args.capacity, alpha=args.per_alpha) if args.prioritized else DeviceReplay(env, args.capacity)
+    planner = None
+    if args.planner:  # guided by copies of the learner's own networks, kept current by sync_planner
+        guided = args.planner_policy_samples > 0 or args.planner_terminal_value
+        planner = DeviceMPPI(env, samples=args.planner_samples, horizon=args.planner_horizon, sigma=args.planner_sigma, lam=args.planner_lam,
+                             gamma=learner.hp["gamma"] if args.planner_terminal_value else 1.0, seed=args.seed,
+                             actor=host_arrays(learner.actor.tensors()) if guided else None,
+                             critic=host_arrays(learner.critic.tensors()) if args.planner_terminal_value else None,
+                             policy_samples=args.planner_policy_samples, policy_sigma=args.planner_policy_sigma if args.planner_policy_samples else 0.0,
+                             terminal_value=args.planner_terminal_value, fail_cost=args.planner_fail_cost)
     updates, t0 = 0, time.perf_counter()
     best = dict(mean=-float("inf"), tensors=None)  # the Python route's own best_model
     if args.monitor and args.log_every < 1:
@@ -224,7 +254,7 @@ def main():
         if args.save_best and ev.best_state()[1] >= 0:
             ev.save_best(args.save_best)
     for step in range(step, args.steps):  # the Python loop (every trip of it where --native is off)
-        learner.collect(replay, 1, monitor=mon)
+        learner.collect(replay, 1, monitor=mon, **(dict(planner=planner, explore_sigma=args.planner_explore_sigma) if planner is not None else {}))
         if mon is not None and (step + 1) % args.log_every == 0:
             mon.record(step + 1)
         if learner.env_steps * env.num_envs < learner.hp["learning_starts"]:
@@ -234,6 +264,8 @@ def main():
             updates += 1
             if updates % args.eval_every == 0:
                 evaluate()
+        if planner is not None:  # the next plan uses the parameters these updates left
+            learner.sync_planner(planner)
         if args.save_every and updates // args.save_every > (updates - args.updates_per_step) // args.save_every:
             save(step + 1)  # this trip is done
     if not args.native:
@@ -246,6 +278,8 @@ def main():
     if args.save_best and best["tensors"] is not None:
         save_actor(args.save_best, best["tensors"], best.get("norm"))
     eval_actor.close()
+    if planner is not None:
+        planner.close()
     learner.close()
     test_env.close()
     env.close()

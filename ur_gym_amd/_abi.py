@@ -587,6 +587,14 @@ class MppiGuide(C.Structure):
                 ("policy_sigma", C.c_float), ("reserved0", C.c_int32), ("fail_cost", C.c_double)] + [(name, C.POINTER(ct)) for name, ct, _ in MPPI_GUIDE_FIELDS]
 
 
+MPPI_EXPLORE_BLOCK = 2  # URGYM_MPPI_EXPLORE_BLOCK: the exploration noise draws blocks 2 and 3 under MPPI_TAG (0 and 1 are the sample noise)
+
+
+class MppiExplore(C.Structure):
+    """urgym_mppi_explore: the exploration noise on the action a planner-driven collection executes; explore_eps ([E][6]) may be NULL."""
+    _fields_ = [("explore_sigma", C.c_float), ("reserved0", C.c_int32), ("explore_eps", C.POINTER(C.c_float))]
+
+
 # Every symbol include/urgym.h declares (tests check that the built library exports each of them).
 EXPORTED_SYMBOLS = [
     "urgym_abi_version",
@@ -670,6 +678,8 @@ EXPORTED_SYMBOLS = [
     "urgym_mppi_terminal",
     "urgym_mppi_plan_guided",
     "urgym_mppi_control_guided",
+    "urgym_mppi_execute",
+    "urgym_mppi_collect",
     "urgym_refresh",
     "urgym_invalidate_records",
     "urgym_derive_obstacle_motion",

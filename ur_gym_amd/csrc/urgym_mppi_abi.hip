@@ -1,7 +1,8 @@
 // urgym_mppi_abi.hip -- the planner's entry points of include/urgym.h ("sampling-based MPC on the device", "MPPI with the learner in the
-// loop"; DESIGN.md sections 26 and 27).  Host code only, beside urgym_policy_abi.hip: every check is made here, before the first launch;
-// every launch goes through urgym_mppi.h, urgym_mppi_guide.h, the actor's and the critic's own launches (urgym_actor.h, urgym_critic.h)
-// or through do_step of urgym_hip.hip (urgym_handle.h).  As there, each entry point is a checking half, which launches nothing, and a
+// loop", "planner-collected experience"; DESIGN.md sections 26 to 28).  Host code only, beside urgym_policy_abi.hip: every check is made
+// here, before the first launch; every launch goes through urgym_mppi.h, urgym_mppi_guide.h, urgym_mppi_collect.h, the actor's and the
+// critic's own launches (urgym_actor.h, urgym_critic.h), the ring's store pass (urgym_replay.h) or through do_step of urgym_hip.hip
+// (urgym_handle.h).  As there, each entry point is a checking half, which launches nothing, and a
 // launching half, which refuses nothing.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -15,7 +16,9 @@
 #include "urgym_critic.h"
 #include "urgym_handle.h"
 #include "urgym_mppi.h"
+#include "urgym_mppi_collect.h"
 #include "urgym_mppi_guide.h"
+#include "urgym_replay.h"
 
 using namespace urgym;
 
@@ -266,6 +269,81 @@ int check_guided_planner(Handle* ph, const urgym_mppi* m, const urgym_mppi_guide
   return check_guide(ph, ph, m, g, who, out);
 }
 
+// ---- planner-collected experience (urgym_mppi_execute, urgym_mppi_collect)
+
+// the checks that concern urgym_mppi_explore; `report` keeps the message
+int check_explore(Handle* report, const urgym_mppi_explore* x, const char* who) {
+  static_assert(sizeof(urgym_mppi_explore) == 16 && alignof(urgym_mppi_explore) == 8, "include/urgym.h");
+  const char* what = nullptr;
+  if (!x) what = "null urgym_mppi_explore";
+  else if (x->reserved0 != 0) what = "urgym_mppi_explore.reserved0 must be 0";
+  else if (!isfinite(x->explore_sigma) || x->explore_sigma < 0.0f) what = "urgym_mppi_explore.explore_sigma must be finite and not negative";
+  return what ? fail_in(report, URGYM_ERR_ARG, who, what) : URGYM_OK;
+}
+
+MppiExecute execute_of(const urgym_mppi& m, const urgym_mppi_explore& x, uint64_t draw, float* executed) {
+  return MppiExecute{m.num_parents, x.explore_sigma, m.seed, draw, m.action_out, executed, x.explore_eps};
+}
+
+// what urgym_rollout_collect refuses about the ring and the slots (check_ring and check_collect of urgym_policy_abi.hip, restated)
+int check_ring(Handle* h, const urgym_replay_ring* r, int first_slot, int num_steps, const char* who) {
+  const char* what = nullptr;
+  if (!r) what = "null ring";
+  else if (r->capacity_steps <= 0) what = "ring->capacity_steps must be positive";
+  else if (r->reserved0 != 0) what = "urgym_replay_ring.reserved0 must be 0";
+  else if (!r->observation || !r->achieved_goal || !r->desired_goal || !r->action || !r->reward || !r->next_observation ||
+           !r->next_achieved_goal || !r->next_desired_goal || !r->terminated)
+    what = "a required ring pointer is null (all but truncated and is_success)";
+  else if (first_slot < 0 || first_slot >= r->capacity_steps) what = "first_slot outside [0, capacity_steps)";
+  else if (num_steps <= 0) what = "num_steps must be positive";
+  return what ? fail_in(h, URGYM_ERR_ARG, who, what) : URGYM_OK;
+}
+
+// the store pass before step k of a collection that started at first_slot (replay_store of urgym_policy_abi.hip, restated): the s of
+// slot k (k < num_steps), the outcome of slot k - 1
+ReplayStore store_of(const Handle* h, const urgym_replay_ring& r, int first_slot, int k, int num_steps) {
+  const urgym_buffers& b = h->buf;
+  const size_t n = (size_t)h->cfg.num_envs, od = (size_t)h->obs_dim, gd = (size_t)h->goal_dim, C = (size_t)r.capacity_steps;
+  ReplayStore p;
+  memset(&p, 0, sizeof(p));
+  p.N = h->cfg.num_envs, p.obs_dim = h->obs_dim, p.goal_dim = h->goal_dim, p.auto_reset = h->cfg.auto_reset;
+  p.observation = b.observation, p.achieved_goal = b.achieved_goal, p.desired_goal = b.desired_goal, p.reward = b.reward;
+  p.final_observation = b.final_observation, p.final_achieved_goal = b.final_achieved_goal, p.final_desired_goal = b.final_desired_goal;
+  p.terminated = b.terminated, p.truncated = b.truncated, p.is_success = b.is_success;
+  if (k < num_steps) {
+    const size_t at = (((size_t)first_slot + (size_t)k) % C) * n;
+    p.obs = r.observation + at * od, p.ach = r.achieved_goal + at * gd, p.des = r.desired_goal + at * gd;
+  }
+  if (k > 0) {
+    const size_t at = (((size_t)first_slot + (size_t)k - 1) % C) * n;
+    p.reward_out = r.reward + at, p.terminated_out = r.terminated + at;
+    p.truncated_out = r.truncated ? r.truncated + at : nullptr, p.is_success_out = r.is_success ? r.is_success + at : nullptr;
+    p.next_obs = r.next_observation + at * od, p.next_ach = r.next_achieved_goal + at * gd, p.next_des = r.next_desired_goal + at * gd;
+  }
+  return p;
+}
+
+// The launches of a collection; everything has been checked.  Every launch goes to `s`: stream order alone puts source step t - 1
+// before the store pass that files its outcome and the record pass that zeroes the finished envs' mean, those before the plan that
+// clones the source's state and reads mean, the plan's update before the execute launch that reads action_out, and that before the
+// source step that reads the slot's action rows.
+int collect(Handle* sh, Handle* ph, const urgym_mppi& m, const Guide* gd, const urgym_mppi_explore& x, uint64_t first_draw, int num_steps,
+            const urgym_replay_ring& ring, int first_slot, hipStream_t s) {
+  const size_t row = (size_t)sh->cfg.num_envs * 6, C = (size_t)ring.capacity_steps;
+  for (int t = 0; t < num_steps; t++) {
+    replay_store_launch(store_of(sh, ring, first_slot, t, num_steps), s);
+    if (t > 0) mppi_record_launch(record_of(sh, m, nullptr, t, num_steps), s);
+    const uint64_t draw = first_draw + (uint64_t)t;
+    if (int rc = plan(sh, ph, m, draw, s, gd)) return rc;
+    float* actions = ring.action + (((size_t)first_slot + (size_t)t) % C) * row;  // the execute launch writes the slot, the step reads it
+    mppi_execute_launch(execute_of(m, x, draw, actions), s);
+    if (int rc = do_step(sh, actions, s)) return rc;
+  }
+  replay_store_launch(store_of(sh, ring, first_slot, num_steps, num_steps), s);
+  mppi_record_launch(record_of(sh, m, nullptr, num_steps, num_steps), s);
+  return URGYM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -395,6 +473,35 @@ int urgym_mppi_control_guided(void* source_handle, void* planner_handle, const u
   if (int rc = check_draw(sh, first_draw, num_steps, who)) return rc;
   HIP_TRY(sh, hipSetDevice(sh->device));
   if (int rc = control(sh, ph, *m, first_draw, num_steps, traj_or_NULL, (hipStream_t)stream, &gd)) return rc;
+  return launched(sh);
+}
+
+int urgym_mppi_execute(void* source_handle, const urgym_mppi* m, const urgym_mppi_explore* x, uint64_t draw, float* executed, void* stream) {
+  const char* who = "urgym_mppi_execute";
+  Handle* sh = (Handle*)source_handle;
+  if (!sh) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (int rc = check_mppi(sh, m, who)) return rc;
+  if (int rc = check_source(sh, sh, m, who)) return rc;
+  if (int rc = check_explore(sh, x, who)) return rc;
+  if (!executed) return fail_in(sh, URGYM_ERR_ARG, who, "executed is null");
+  if (int rc = check_draw(sh, draw, 1, who)) return rc;
+  HIP_TRY(sh, hipSetDevice(sh->device));
+  mppi_execute_launch(execute_of(*m, *x, draw, executed), (hipStream_t)stream);
+  return launched(sh);
+}
+
+int urgym_mppi_collect(void* source_handle, void* planner_handle, const urgym_mppi* m, const urgym_mppi_guide* guide_or_NULL, const urgym_mppi_explore* x, uint64_t first_draw, int num_steps, const urgym_replay_ring* ring, int first_slot, void* stream) {
+  const char* who = "urgym_mppi_collect";
+  Handle *sh = (Handle*)source_handle, *ph = (Handle*)planner_handle;
+  Guide gd;
+  if (!sh) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (int rc = guide_or_NULL ? check_guided_pair(sh, ph, m, guide_or_NULL, who, &gd) : check_pair(sh, ph, m, who)) return rc;
+  if (!sh->observed) return fail_in(sh, URGYM_ERR_STATE, who, "nothing has been observed yet: urgym_reset() or urgym_refresh() the source first");
+  if (int rc = check_explore(sh, x, who)) return rc;
+  if (int rc = check_ring(sh, ring, first_slot, num_steps, who)) return rc;
+  if (int rc = check_draw(sh, first_draw, num_steps, who)) return rc;
+  HIP_TRY(sh, hipSetDevice(sh->device));
+  if (int rc = collect(sh, ph, *m, guide_or_NULL ? &gd : nullptr, *x, first_draw, num_steps, *ring, first_slot, (hipStream_t)stream)) return rc;
   return launched(sh);
 }
 

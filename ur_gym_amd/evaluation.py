@@ -1466,6 +1466,17 @@ class DeviceReplay:
         self.cursor = (self.cursor + K) % self.capacity
         self.filled = min(self.capacity, self.filled + K)
 
+    def collect_planned(self, planner, num_steps, first_draw=0, explore_sigma=0.0):
+        """``collect`` with a planner as the policy: `num_steps` x (store pass, plan, execute, step) from slot ``cursor`` on in one native
+        call (urgym_mppi_collect), `planner` a ``DeviceMPPI`` of this ring's environment; step t plans and explores with draw
+        ``first_draw + t``, and the executed action is the plan's first action plus `explore_sigma` times the exploration noise, clamped.
+        The slots are what a policy collection writes, so every gather, the monitor's fold and the normalizer's fold serve them as they
+        are.  Advances ``cursor`` and ``filled``."""
+        K = int(num_steps)
+        planner.collect(self, K, first_draw=first_draw, explore_sigma=explore_sigma, first_slot=self.cursor)
+        self.cursor = (self.cursor + K) % self.capacity
+        self.filled = min(self.capacity, self.filled + K)
+
     def sample_into(self, out, seed, draw, n_steps=None, gamma=None, hindsight=None):
         """The gather itself: `out` maps ring field names (and ``index``, int64) to contiguous device tensors with one leading
         length, the batch size; only those are written.  The rows are ``replay_indices(seed, draw, count, len(self))``.
@@ -1727,6 +1738,12 @@ class DevicePrioritizedReplay(DeviceReplay):
         """``DeviceReplay.collect``, then ``fill`` on the slots just written: a new transition is drawn at the largest priority seen."""
         first = self.cursor
         super().collect(actor, num_steps, sample=sample, normalizer=normalizer)
+        self.fill(first, num_steps)
+
+    def collect_planned(self, planner, num_steps, first_draw=0, explore_sigma=0.0):
+        """``DeviceReplay.collect_planned``, then ``fill`` on the slots just written, as ``collect`` does."""
+        first = self.cursor
+        super().collect_planned(planner, num_steps, first_draw=first_draw, explore_sigma=explore_sigma)
         self.fill(first, num_steps)
 
     def sample_prioritized(self, batch_size, seed, draw):
@@ -2724,6 +2741,53 @@ def mppi_terminal(score, value, terminal_value, fail_cost):
     return dict(terminal=v, ret=new)
 
 
+def mppi_explore_counters(draw, parents):
+    """The two Philox counters of the exploration noise of (parent p, draw) (include/urgym.h, "planner-collected experience"): a pair of
+    4-tuples (p, 0, draw, MPPI_TAG | block) for block 2 and block 3, `parents` an integer or an integer array."""
+    from . import _abi
+
+    draw = int(draw)
+    if not 0 <= draw < 1 << 32:
+        raise ValueError(f"draw must be in [0, 2^32), got {draw}")
+    p = np.asarray(parents, dtype=np.uint64)
+    if p.size and int(p.max()) >= 1 << 31:
+        raise ValueError("parents must be env indices")
+    return tuple((p, np.uint64(0), np.uint64(draw), np.uint64(_abi.MPPI_TAG | (_abi.MPPI_EXPLORE_BLOCK + b))) for b in (0, 1))
+
+
+def mppi_explore_noise(seed, draw, parents, dtype=np.float32):
+    """The exploration noise of a planner-driven collection, restated from include/urgym.h: a pure function of (seed, draw, parent p,
+    component) -- six normals per parent, Box-Muller as ``mppi_noise`` forms the planner's on the words of the counters
+    ``mppi_explore_counters`` states (blocks 2 and 3 under the planner's tag; the planner's own noise draws blocks 0 and 1), with the
+    planner's key.  `parents` is an integer or an integer array; returns its shape + (6,).  `dtype` is the precision of ln / sqrt / cos /
+    sin."""
+    seed = int(seed)
+    key = (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
+    c2, c3 = mppi_explore_counters(draw, parents)
+    return _box_muller(_noise_integers(philox4x32_10(key, c2), philox4x32_10(key, c3), dtype), dtype)
+
+
+def mppi_execute(action_out, eps, explore_sigma):
+    """THE EXECUTE LINE in numpy, bitwise given `eps`: `action_out` and `eps` float32 [E, 6].  s = explore_sigma * eps; a = action_out + s;
+    executed = fmin(fmax(a, -1), 1), each one float32 operation.  With ``explore_sigma == 0`` the result is a copy of `action_out`'s
+    bytes (no clamp, a -0.0 stays -0.0) and `eps` is not read (it may be None)."""
+    action_out = np.asarray(action_out)
+    if action_out.dtype != np.float32 or action_out.ndim != 2 or action_out.shape[1] != 6:
+        raise ValueError(f"action_out must be float32 [E, 6], got {action_out.dtype} {action_out.shape}")
+    sigma = np.float32(explore_sigma)
+    if not (np.isfinite(sigma) and sigma >= 0):
+        raise ValueError(f"explore_sigma must be finite and >= 0, got {explore_sigma}")
+    if sigma == 0:
+        return action_out.copy()
+    eps = np.asarray(eps)
+    if eps.dtype != np.float32 or eps.shape != action_out.shape:
+        raise ValueError(f"eps must be float32 {action_out.shape}, got {eps.dtype} {eps.shape}")
+    with np.errstate(all="ignore"):
+        s = sigma * eps
+        a = action_out + s
+        return np.fmin(np.fmax(a, np.float32(-1)), np.float32(1))
+
+
 class DeviceMPPI:
     """An MPPI planner (Williams et al., 2017) for `env`, a UR5ReachVectorEnv of E envs, that plans with the step kernel itself: it owns a
     planner environment of E * `samples` envs (same env id, configuration and device, ``auto_reset=False``) and every buffer of
@@ -2763,6 +2827,7 @@ class DeviceMPPI:
         self.planner._needs_reset = False  # its state is the fan-out's
         self.samples, self.horizon = K, H
         self.buf = {}
+        self.explore = {}  # executed and explore_eps of ``execute``, allocated at its first call
         M = _abi.Mppi()
         M.num_parents, M.samples, M.horizon, M.iterations, M.shift = E, K, H, int(iterations), int(bool(shift))
         M.sigma, M.lam, M.gamma, M.seed = float(sigma), float(lam), float(gamma), int(seed)
@@ -2872,6 +2937,54 @@ class DeviceMPPI:
             _native.check(env.lib.urgym_mppi_control_guided(env._h, self.planner._h, C.byref(self._struct), C.byref(self._guide), int(first_draw), T,
                                                             C.byref(traj) if names else None, env._stream()), env._h)
         return out
+
+    @staticmethod
+    def check_explore(explore_sigma):
+        """Raises ValueError for what urgym_mppi_execute / urgym_mppi_collect refuse about explore_sigma.  Returns it as a float.  Needs no GPU."""
+        with np.errstate(over="ignore"):
+            ok = not isinstance(explore_sigma, bool) and bool(np.isfinite(np.float32(explore_sigma))) and float(explore_sigma) >= 0.0
+        if not ok:
+            raise ValueError(f"explore_sigma must be finite (in float32) and >= 0, got {explore_sigma!r}")
+        return float(explore_sigma)
+
+    def execute(self, draw=0, explore_sigma=0.0):
+        """The action the environment should execute after a ``plan``: ``action_out`` plus `explore_sigma` times the exploration noise of
+        `draw`, clamped to [-1, 1] (urgym_mppi_execute: one launch; ``mppi_execute`` on ``mppi_explore_noise`` restates it).  With
+        ``explore_sigma == 0`` it is a copy of ``action_out``.  Returns (executed [E, 6], explore_eps [E, 6]): tensors of this planner's,
+        allocated at the first call and overwritten by the next.  NOT synchronised."""
+        import ctypes as C
+
+        import torch
+
+        from . import _abi, _native
+
+        env = self.env
+        x = _abi.MppiExplore(self.check_explore(explore_sigma), 0, None)
+        if not self.explore:
+            for name in ("executed", "explore_eps"):
+                self.explore[name] = torch.zeros((env.num_envs, 6), dtype=torch.float32, device=env.device)
+        x.explore_eps = C.cast(self.explore["explore_eps"].data_ptr(), C.POINTER(C.c_float))
+        _native.check(env.lib.urgym_mppi_execute(env._h, C.byref(self._struct), C.byref(x), int(draw), C.c_void_p(self.explore["executed"].data_ptr()),
+                                                 env._stream()), env._h)
+        return self.explore["executed"], self.explore["explore_eps"]
+
+    def collect(self, replay, num_steps, first_draw=0, explore_sigma=0.0, first_slot=None):
+        """`num_steps` x (store pass, plan, execute, step the environment) in ONE native call (urgym_mppi_collect) that files every
+        transition in `replay` (an ``evaluation.DeviceReplay`` of this planner's environment) as it happens: step t goes to slot
+        (first_slot + t) % capacity and draws with ``first_draw + t``.  `first_slot` defaults to the ring's cursor, which this method does
+        NOT move -- ``replay.collect_planned`` does.  NOT synchronised."""
+        import ctypes as C
+
+        from . import _abi, _native
+
+        env = self.env
+        if getattr(replay, "env", None) is not env or not hasattr(replay, "_ring"):
+            raise ValueError("replay must be a DeviceReplay allocated for this planner's environment (DeviceReplay(env, capacity_steps))")
+        first = replay.cursor if first_slot is None else first_slot
+        replay.check_args(replay.capacity, num_steps=num_steps, first_slot=first)
+        x = _abi.MppiExplore(self.check_explore(explore_sigma), 0, None)
+        _native.check(env.lib.urgym_mppi_collect(env._h, self.planner._h, C.byref(self._struct), None if self._guide is None else C.byref(self._guide),
+                                                 C.byref(x), int(first_draw), int(num_steps), C.byref(replay._ring), int(first), env._stream()), env._h)
 
     def reset_plan(self, mask=None):
         """Zeroes the nominal sequence of every env, or of those `mask` (a bool [E] tensor or array, or env ids) selects."""

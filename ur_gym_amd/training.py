@@ -56,6 +56,11 @@ minibatch gather on the HIP kernels, and gradients and optimisers in torch autog
     (one more launch per step; the ring keeps the raw rows) and folds the collected slots into them afterwards (two launches), and
     ``update`` normalizes the gathered minibatch in place right after the gather (``env.norm_batch``: fourteen launches, sixteen with
     clipping).  ``self.normalizer.training = False`` freezes the statistics.  ``False``, the default, makes exactly the calls above.
+    With ``collect(planner=)`` (an ``evaluation.DeviceMPPI`` on the learner's env) the collecting policy is the MPPI
+    planner instead of the sampled actor: every step is planned (urgym_mppi_collect), the executed action is the plan's first action plus
+    ``explore_sigma`` times exploration noise, and the transitions land in the same ring slots, so ``update`` trains on them as they stand
+    (SAC is off-policy); ``sync_planner`` puts the planner's actor and critic on the learner's current parameters.  Not with ``normalize``;
+    ``train`` has no planner option yet.
     None of them synchronises with the host.  ``train`` runs the whole loop in one native call and, given an
     ``evaluation.DeviceEvaluation``, the reference's EvalCallback inside it: evaluations of the deterministic policy at a fixed interval of
     updates, their statistics as records on the device, and the best actor's tensors, which ``DeviceEvaluation.save_best`` writes as an
@@ -309,11 +314,31 @@ class SACLearner:
         self.env_steps = 0  # per env; decides between the warm-up and the policy
         self.draw = 0       # draw index of the next collection pass
 
-    def collect(self, replay, num_steps, monitor=None):
+    def collect(self, replay, num_steps, monitor=None, planner=None, explore_sigma=0.0):
         """`num_steps` env steps of all N envs into `replay`, with uniform actions before ``learning_starts`` env steps and the sampled
         policy afterwards (a call is one or the other: the mode is decided when it starts).  With `monitor` (an
         ``evaluation.DeviceMonitor``) the steps just collected are folded into its state: one more launch.  With ``normalize`` the actor
-        reads normalized rows and the steps are folded into the statistics first (at most ``normalizer.fold_steps`` steps a call)."""
+        reads normalized rows and the steps are folded into the statistics first (at most ``normalizer.fold_steps`` steps a call).
+
+        With `planner` (an ``evaluation.DeviceMPPI`` on this learner's env) every step is planned instead
+        (``replay.collect_planned``): ``learning_starts`` is not consulted, the planner's draw is ``self.draw``, and
+        the executed action is the plan's plus `explore_sigma` times the exploration noise.  SAC is off-policy and trains on these
+        transitions as they stand; ``sync_planner`` keeps the planner's actor and critic on this learner's parameters.  Not together
+        with ``normalize``: the planner's actor and critic read raw rows.  Without `planner` the calls are those above."""
+        if planner is not None:
+            if self.normalizer is not None:
+                raise ValueError("collect: planner= together with normalize=True is out of scope (the planner's actor and critic read raw rows, not normalized ones)")
+            if getattr(planner, "env", None) is not self.env:
+                raise ValueError("collect: the planner's source env is not this learner's env (DeviceMPPI(learner.env, ...))")
+            first = replay.cursor
+            replay.collect_planned(planner, num_steps, first_draw=self.draw, explore_sigma=explore_sigma)
+            if monitor is not None:
+                monitor.fold(replay, first, num_steps)
+            self.env_steps += int(num_steps)
+            self.draw += int(num_steps)
+            return
+        if explore_sigma:
+            raise ValueError("collect: explore_sigma is the planner's exploration noise and needs planner=")
         mode = "uniform" if self.env_steps * self.env.num_envs < self.hp["learning_starts"] else "gaussian"
         first = replay.cursor
         if self.normalizer is not None:
@@ -327,6 +352,15 @@ class SACLearner:
             monitor.fold(replay, first, num_steps)
         self.env_steps += int(num_steps)
         self.draw += int(num_steps)
+
+    def sync_planner(self, planner):
+        """Puts `planner`'s actor and critic (an ``evaluation.DeviceMPPI`` made with ``actor=`` / ``critic=``) on this learner's current
+        parameters: the actor from the torch actor's tensors (urgym_actor_load), the critic from the ONLINE critics with tau = 1
+        (urgym_critic_load), one launch each on the planner's handle, nothing synchronised.  A part the planner does not have is skipped."""
+        if planner.actor is not None:
+            planner.actor.load_parameters(self.actor.tensors())
+        if planner.critic is not None:
+            planner.critic.load_parameters(self.critic.tensors(), tau=1.0)
 
     def update(self, replay, seed, draw):
         """One gradient step on a minibatch drawn with (seed, draw), then the two reloads.  Returns the three losses as device
