@@ -2014,6 +2014,76 @@ int urgym_mppi_execute(void* source_handle, const urgym_mppi* m, const urgym_mpp
  * observed nothing; a NULL x; a non-zero reserved0; explore_sigma not finite or < 0. */
 int urgym_mppi_collect(void* source_handle, void* planner_handle, const urgym_mppi* m, const urgym_mppi_guide* guide_or_NULL, const urgym_mppi_explore* x, uint64_t first_draw, int num_steps, const urgym_replay_ring* ring, int first_slot, void* stream);
 
+/* ---- elite samples and an adaptive std: the update TD-MPC's planner runs.  THE UPDATE above weighs every
+ * finite sample under one temperature, and every refinement iteration samples with the one scalar sigma.  The calls below rank the K
+ * returns of a parent, keep the M best as elites, weigh those as THE UPDATE does, and form, beside the mean, a standard deviation per
+ * (horizon step, joint) with which the next iteration of the same plan samples.  Opt-in and WITHIN ABI version 4: no struct above
+ * changed, the five new symbols are found by lookup, and every call above launches and leaves what it did.
+ *
+ * THE RANK of sample j of parent p (float64's own comparisons, so -0.0 == 0.0):
+ *   key_j  = finite(r_j) ? r_j : -inf                          (the term of rmax; no key is a NaN)
+ *   rank_j = #{ i < K : key_i > key_j, or key_i == key_j and i < j }      a permutation of 0 .. K - 1 whatever the returns are
+ *   elite_j = rank_j < M && finite(r_j)
+ *   elite_count[p] = the number of elites = min(M, the number of finite returns)
+ *   threshold[p]   = r_j of the elite with rank elite_count[p] - 1, the smallest elite return; -inf with no elite
+ *
+ * THE ELITE WEIGHT.  rmax as in THE UPDATE (the best finite return has rank 0 and is an elite).
+ *   none finite:  w_0 = 1, w_j = 0 otherwise.   else:  d = r_j - rmax;  x = d / lambda;  w_j = elite_j ? exp(x) : 0
+ * With M == K elite_j is finite(r_j): the weight is THE UPDATE's.
+ *
+ * Z, S, new_mean, Q, ess, action_out, best_return, nominal_return, w and the shift of mean are THE UPDATE's lines over all j < K, in its
+ * order; a sample that is no elite contributes a zero term.  With M == K each of them is, bit for bit, what urgym_mppi_update writes.
+ *
+ * THE STD, for each (h, c), float64, one operation per line, after S and Z of THE UPDATE:
+ *   m = S / Z                                                   (the mean before it is rounded to float32)
+ *   per j:  a = (double)actions[h][pK + j][c];  d = a - m;  dd = d * d;  t = w_j * dd
+ *   V = the ordered sum of t;  v = V / Z;  sd = sqrt(v)          (the correctly rounded square root)
+ *   lo = fmax(sd, (double)std_min);  hi = fmin(lo, (double)std_max);  new_std[h][p][c] = (float)hi
+ * A NaN v (a NaN action, even one that weighs nothing) ends at std_min, by fmax.  new_std is not shifted, and it is not carried from one
+ * plan to the next: every plan starts at sigma.
+ *
+ * THE ADAPTIVE SAMPLE (urgym_mppi_sample_adaptive, one launch, THE SAMPLE's geometry).  Counters, words, Box-Muller and eps are THE
+ * SAMPLE's, bit for bit; sample 0 is the nominal with eps = 0.  The action line reads its width per element:
+ *   s = std[h][p][c] * eps;  a = mean[h][p][c] + s;  action = fminf(fmaxf(a, -1), 1).
+ * With every element of std equal to sigma, actions and eps are bitwise urgym_mppi_sample's.
+ *
+ * THE ELITE UPDATE (urgym_mppi_update_elite, one launch: one workgroup of 1024 lanes per parent, lane j < K, no atomics, one writer per
+ * output).  It writes what THE UPDATE writes and new_std, rank, elite (each may be NULL), elite_count and threshold.  It does not
+ * write std. */
+typedef struct urgym_mppi_adapt {
+  int32_t elites;        /* M in [1, K] */
+  int32_t adapt_std;     /* != 0: iterations >= 1 of a plan sample with new_std of the iteration before */
+  float std_min, std_max;/* finite, 0 <= std_min <= std_max */
+  float* std;            /* [H][E][6] what urgym_mppi_sample_adaptive reads */
+  float* new_std;        /* [H][E][6] what the elite update writes */
+  int32_t* rank;         /* [E][K], may be NULL */
+  uint8_t* elite;        /* [E][K], may be NULL */
+  int32_t* elite_count;  /* [E] */
+  double* threshold;     /* [E] */
+} urgym_mppi_adapt;
+
+/* The two single launches.  Like urgym_mppi_sample and urgym_mppi_update they need no bound environment.  Refused, each launching and
+ * writing nothing (the message names the entry point and the argument): everything urgym_mppi_sample (_sample_adaptive) or
+ * urgym_mppi_update (_update_elite) refuses; a NULL a; elites outside [1, K]; std_min or std_max not finite or negative;
+ * std_min > std_max; a NULL std, new_std, elite_count or threshold. */
+int urgym_mppi_sample_adaptive(void* handle, const urgym_mppi* m, const urgym_mppi_adapt* a, uint64_t draw, int iteration, void* stream);
+int urgym_mppi_update_elite(void* handle, const urgym_mppi* m, const urgym_mppi_adapt* a, void* stream);
+
+/* ONE ADAPTIVE PLAN.  Per iteration i it runs what urgym_mppi_plan runs, or urgym_mppi_plan_guided where a guide is given, with the
+ * elite update in place of the update.  Iteration 0 samples with urgym_mppi_sample and m->sigma.  With adapt_std, an iteration i >= 1
+ * first copies new_std (of iteration i - 1) into std, device to device on the stream, and samples with urgym_mppi_sample_adaptive;
+ * without adapt_std every iteration samples with urgym_mppi_sample.  The launches are a plain plan's and at most that copy per
+ * iteration.  Bit for bit that sequence of single calls and urgym_steps.  With M == K and adapt_std == 0 it leaves every buffer of
+ * urgym_mppi and of the planner as urgym_mppi_plan(_guided) leaves it.  Refused: everything urgym_mppi_plan (guide_or_NULL == NULL) or
+ * urgym_mppi_plan_guided refuses, and what the two launches above refuse about a. */
+int urgym_mppi_plan_adaptive(void* source_handle, void* planner_handle, const urgym_mppi* m, const urgym_mppi_adapt* a, const urgym_mppi_guide* guide_or_NULL, uint64_t draw, void* stream);
+
+/* THE CLOSED LOOP and THE COLLECTION with the adaptive plan inside: urgym_mppi_control(_guided) and urgym_mppi_collect with
+ * urgym_mppi_plan_adaptive in place of the plan, bit for bit.  Refused: everything those calls refuse, and what the two launches above
+ * refuse about a. */
+int urgym_mppi_control_adaptive(void* source_handle, void* planner_handle, const urgym_mppi* m, const urgym_mppi_adapt* a, const urgym_mppi_guide* guide_or_NULL, uint64_t first_draw, int num_steps, const urgym_trajectory* traj_or_NULL, void* stream);
+int urgym_mppi_collect_adaptive(void* source_handle, void* planner_handle, const urgym_mppi* m, const urgym_mppi_adapt* a, const urgym_mppi_guide* guide_or_NULL, const urgym_mppi_explore* x, uint64_t first_draw, int num_steps, const urgym_replay_ring* ring, int first_slot, void* stream);
+
 /* Replaces Reach*.set_goal / set_goal_and_obstacle (reach.py:202-204, 328-335, 702-713): the caller has
  * overwritten goal / obst_start / obst_end (and possibly q) for the masked envs; this recomputes obstacle pose,
  * velocity, collision, link_dist and the observation for them, leaving step_count untouched. */

@@ -16,6 +16,12 @@ grid row is run a second time with the guide and reported under "guided" beside 
 same protocol figures, the time of a guided plan, and the time of the launches the guide adds -- actor, guide, critic, terminal -- run
 without the rest.  --grid replaces the built-in grid.
 
+With elite samples and the adaptive std (--elites M [M ...], --adapt-std, --std-min, --std-max) and --iterations
+I [I ...]: every grid row is run once per I, plain first, and then under "adaptive" once per (M, adapt_std off / on where --adapt-std
+is given) with the same protocol figures and the time of an adaptive plan beside the plain figures of the same row and I.
+
+    python tools/bench_mppi.py --env dyn --grid 256:6:0.6:5 --iterations 1 2 4 --elites 256 64 16 --adapt-std --out profiles/mppi/dyn_elites_grid.json
+
     python tools/bench_mppi.py --env ori --grid 256:6:0.3:5 256:12:0.3:5 256:24:0.3:5 --terminal-value --policy-samples 64 \
         --actor tests/golden/actors/actor_ori.npz --critics tests/golden/critics/critic_ori_qf0.npz tests/golden/critics/critic_ori_qf1.npz
 """
@@ -96,8 +102,8 @@ def control_step_time(env, options, repeats):
     for draw in range(repeats):
         mppi.plan(3 + draw)
     mid.record()
-    for draw in range(repeats):
-        rc = lib.urgym_mppi_fanout(src, planner, C.byref(M), s) or lib.urgym_mppi_sample(src, C.byref(M), 3 + draw, 0, s)
+    for draw, i in ((d, i) for d in range(repeats) for i in range(M.iterations)):
+        rc = lib.urgym_mppi_fanout(src, planner, C.byref(M), s) or lib.urgym_mppi_sample(src, C.byref(M), 3 + draw, i, s)
         for h in range(M.horizon):
             rc = rc or lib.urgym_mppi_score(planner, C.byref(M), h, s)
         rc = rc or lib.urgym_mppi_update(src, C.byref(M), s)
@@ -201,6 +207,11 @@ def main():
     ap.add_argument("--terminal-value", action="store_true", help="credit a future alive after H steps with min Q(s_H, actor(s_H))")
     ap.add_argument("--fail-cost", type=float, default=0.0, help="the cost of a future that ends without success")
     ap.add_argument("--guided-gamma", type=float, default=None, help="gamma of the guided rows (default 0.95 with --terminal-value, the critics' own, else 1)")
+    ap.add_argument("--iterations", type=int, nargs="+", default=[1], metavar="I", help="refinement iterations of a plan; every row is run once per value")
+    ap.add_argument("--elites", type=int, nargs="+", default=None, metavar="M", help="run every row again with only the M best samples weighing in, once per value")
+    ap.add_argument("--adapt-std", action="store_true", help="... and once more per M with the std adapted across the iterations of a plan")
+    ap.add_argument("--std-min", type=float, default=0.05, help="--adapt-std: the floor of the adaptive std")
+    ap.add_argument("--std-max", type=float, default=None, help="--adapt-std: its ceiling (default: the row's sigma)")
     args = ap.parse_args()
     import torch
 
@@ -212,16 +223,18 @@ def main():
         guide = dict(policy_samples=args.policy_samples, policy_sigma=args.policy_sigma if args.policy_samples else 0.0, terminal_value=args.terminal_value,
                      fail_cost=args.fail_cost, actor=args.actor, critic=args.critics,
                      gamma=args.guided_gamma if args.guided_gamma is not None else (0.95 if args.terminal_value else 1.0))
+    if args.adapt_std and args.elites is None:
+        raise SystemExit("--adapt-std runs beside --elites M (M = K keeps every finite sample)")
     rows = []
-    for K, H, sigma, lam in grid:
+    for K, H, sigma, lam, iterations in [(*row, i) for row in grid for i in args.iterations]:
         E = max(1, args.budget // K)
-        options = dict(samples=K, horizon=H, sigma=sigma, lam=lam, gamma=1.0, iterations=1, shift=True, seed=0)
+        options = dict(samples=K, horizon=H, sigma=sigma, lam=lam, gamma=1.0, iterations=iterations, shift=True, seed=0)
         success, reward, last, wall = protocol(env_id, points, E, args.steps, args.device, options)
         env = make_vec(env_id, num_envs=E, device=args.device, seed=4, auto_reset=False)
         env.reset(seed=4)
         plan_ms, own_ms = control_step_time(env, options, args.repeats)
         env.close()
-        row = dict(K=K, H=H, sigma=sigma, lam=lam, E=E, planner_envs=E * K, **figures(success, reward, last, args.steps),
+        row = dict(K=K, H=H, sigma=sigma, lam=lam, iterations=iterations, E=E, planner_envs=E * K, **figures(success, reward, last, args.steps),
                    plan_ms=plan_ms, planner_kernels_ms=own_ms, planner_kernels_share=own_ms / plan_ms,
                    control_steps_per_second=1e3 / plan_ms, env_control_steps_per_second=E * 1e3 / plan_ms,
                    closed_loop_wall_seconds_including_setup=wall)
@@ -235,6 +248,16 @@ def main():
             row["guided"] = dict({k: v for k, v in guide.items() if k not in ("actor", "critic")}, **figures(success, reward, last, args.steps),
                                  plan_ms=guided_ms, plan_ms_over_plain=guided_ms / plan_ms, guide_launches_ms=added_ms, guide_launches_share=added_ms / guided_ms,
                                  closed_loop_wall_seconds_including_setup=wall)
+        for M, adapt_std in [(m, a) for m in args.elites or () for a in ((False, True) if args.adapt_std else (False,))]:
+            adaptive = dict(options, elites=M, adapt_std=adapt_std, std_min=args.std_min, std_max=args.std_max)
+            success, reward, last, wall = protocol(env_id, points, E, args.steps, args.device, adaptive)
+            env = make_vec(env_id, num_envs=E, device=args.device, seed=4, auto_reset=False)
+            env.reset(seed=4)
+            adaptive_ms, _ = control_step_time(env, adaptive, args.repeats)  # the second figure times the plain launches: not reported here
+            env.close()
+            row.setdefault("adaptive", []).append(dict(elites=M, adapt_std=adapt_std, std_min=args.std_min, std_max=sigma if args.std_max is None else args.std_max,
+                                                       **figures(success, reward, last, args.steps), plan_ms=adaptive_ms, plan_ms_over_plain=adaptive_ms / plan_ms,
+                                                       closed_loop_wall_seconds_including_setup=wall))
         rows.append(row)
         print(json.dumps(row), flush=True)
     ref = json.load(open(os.path.join(ROOT, "tests", "golden", "actors", "reference_results.json")))[kind]

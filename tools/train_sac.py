@@ -31,7 +31,8 @@ was selected under beside it (evaluation.load_best_normalization reads them).
 --planner collects with an MPPI planner in place of the sampled policy (SACLearner.collect(planner=), urgym_mppi_collect; DESIGN.md section
 28): every trip plans with --planner-samples futures per env over --planner-horizon steps, optionally guided by the learner's own actor
 (--planner-policy-samples) and critic (--planner-terminal-value), executes the plan's first action plus --planner-explore-sigma times
-exploration noise, and after the trip's updates puts the planner's actor and critic on the learner's parameters (SACLearner.sync_planner).
+exploration noise (--planner-iterations, --planner-elites, --planner-adapt-std, --planner-std-min, --planner-std-max: refinement with
+elite samples and an adaptive std), and after the trip's updates puts the planner's actor and critic on the learner's parameters (SACLearner.sync_planner).
 The Python loop only: not with --native (the native training call has no planner option yet) and not with --normalize (the planner's
 actor and critic read raw rows).  It prints what it prints without.
 """
@@ -126,6 +127,13 @@ def main():
                     help="--planner: credit a future alive after the horizon with the learner's min Q of the state it stops in (the planner then discounts with the learner's gamma)")
     ap.add_argument("--planner-fail-cost", type=float, default=0.0, help="--planner: what a future that ends without success is charged")
     ap.add_argument("--planner-explore-sigma", type=float, default=0.0, help="--planner: standard deviation of the exploration noise on the executed action")
+    ap.add_argument("--planner-iterations", "--iterations", type=int, default=1, help="--planner: refinement iterations of a plan, in [1, 8]")
+    ap.add_argument("--planner-elites", "--elites", type=int, default=None, metavar="M",
+                    help="--planner: only the M best-scoring futures of an env weigh in, M in [1, samples] (DESIGN.md section 29; default: every finite one)")
+    ap.add_argument("--planner-adapt-std", "--adapt-std", action="store_true",
+                    help="--planner: iterations after the first sample with a std per (step, joint) formed from the elites of the one before (needs --planner-iterations > 1 to act)")
+    ap.add_argument("--planner-std-min", "--std-min", type=float, default=0.05, help="--planner-adapt-std: the floor of the adaptive std")
+    ap.add_argument("--planner-std-max", "--std-max", type=float, default=None, help="--planner-adapt-std: its ceiling (default: --planner-sigma)")
     args = ap.parse_args()
     if args.planner and (args.native or args.normalize):
         raise SystemExit("--planner runs the Python loop on raw rows: not with --native (the native training call has no planner option yet) or --normalize")
@@ -167,7 +175,8 @@ def main():
                              actor=host_arrays(learner.actor.tensors()) if guided else None,
                              critic=host_arrays(learner.critic.tensors()) if args.planner_terminal_value else None,
                              policy_samples=args.planner_policy_samples, policy_sigma=args.planner_policy_sigma if args.planner_policy_samples else 0.0,
-                             terminal_value=args.planner_terminal_value, fail_cost=args.planner_fail_cost)
+                             terminal_value=args.planner_terminal_value, fail_cost=args.planner_fail_cost, iterations=args.planner_iterations,
+                             elites=args.planner_elites, adapt_std=args.planner_adapt_std, std_min=args.planner_std_min, std_max=args.planner_std_max)
     updates, t0 = 0, time.perf_counter()
     best = dict(mean=-float("inf"), tensors=None)  # the Python route's own best_model
     if args.monitor and args.log_every < 1:

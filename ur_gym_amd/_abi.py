@@ -595,6 +595,23 @@ class MppiExplore(C.Structure):
     _fields_ = [("explore_sigma", C.c_float), ("reserved0", C.c_int32), ("explore_eps", C.POINTER(C.c_float))]
 
 
+# urgym_mppi_adapt's device pointers: name -> (ctype of element, shape given (E, K, H)); rank and elite may be NULL
+MPPI_ADAPT_FIELDS = [
+    ("std", C.c_float, lambda E, K, H: (H, E, 6)),
+    ("new_std", C.c_float, lambda E, K, H: (H, E, 6)),
+    ("rank", C.c_int32, lambda E, K, H: (E, K)),
+    ("elite", C.c_uint8, lambda E, K, H: (E, K)),
+    ("elite_count", C.c_int32, lambda E, K, H: (E,)),
+    ("threshold", C.c_double, lambda E, K, H: (E,)),
+]
+
+
+class MppiAdapt(C.Structure):
+    """urgym_mppi_adapt: elite selection and the per-(step, joint) std of a planner, and the caller-owned device arrays they write."""
+    _fields_ = [("elites", C.c_int32), ("adapt_std", C.c_int32), ("std_min", C.c_float), ("std_max", C.c_float)] + [
+        (name, C.POINTER(ct)) for name, ct, _ in MPPI_ADAPT_FIELDS]
+
+
 # Every symbol include/urgym.h declares (tests check that the built library exports each of them).
 EXPORTED_SYMBOLS = [
     "urgym_abi_version",
@@ -680,6 +697,11 @@ EXPORTED_SYMBOLS = [
     "urgym_mppi_control_guided",
     "urgym_mppi_execute",
     "urgym_mppi_collect",
+    "urgym_mppi_sample_adaptive",
+    "urgym_mppi_update_elite",
+    "urgym_mppi_plan_adaptive",
+    "urgym_mppi_control_adaptive",
+    "urgym_mppi_collect_adaptive",
     "urgym_refresh",
     "urgym_invalidate_records",
     "urgym_derive_obstacle_motion",

@@ -151,6 +151,14 @@ def lib():
     L.urgym_mppi_execute.argtypes = [C.c_void_p, C.POINTER(_abi.Mppi), C.POINTER(_abi.MppiExplore), C.c_uint64, C.c_void_p, C.c_void_p]
     L.urgym_mppi_collect.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.Mppi), C.POINTER(_abi.MppiGuide), C.POINTER(_abi.MppiExplore), C.c_uint64,
                                      C.c_int, C.POINTER(_abi.ReplayRing), C.c_int, C.c_void_p]
+    L.urgym_mppi_sample_adaptive.argtypes = [C.c_void_p, C.POINTER(_abi.Mppi), C.POINTER(_abi.MppiAdapt), C.c_uint64, C.c_int, C.c_void_p]
+    L.urgym_mppi_update_elite.argtypes = [C.c_void_p, C.POINTER(_abi.Mppi), C.POINTER(_abi.MppiAdapt), C.c_void_p]
+    L.urgym_mppi_plan_adaptive.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.Mppi), C.POINTER(_abi.MppiAdapt), C.POINTER(_abi.MppiGuide), C.c_uint64,
+                                           C.c_void_p]
+    L.urgym_mppi_control_adaptive.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.Mppi), C.POINTER(_abi.MppiAdapt), C.POINTER(_abi.MppiGuide), C.c_uint64,
+                                              C.c_int, C.POINTER(_abi.Trajectory), C.c_void_p]
+    L.urgym_mppi_collect_adaptive.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.Mppi), C.POINTER(_abi.MppiAdapt), C.POINTER(_abi.MppiGuide),
+                                              C.POINTER(_abi.MppiExplore), C.c_uint64, C.c_int, C.POINTER(_abi.ReplayRing), C.c_int, C.c_void_p]
     L.urgym_actor_read_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.urgym_critic_read_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.urgym_refresh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]

@@ -1,8 +1,9 @@
 // urgym_mppi_abi.hip -- the planner's entry points of include/urgym.h ("sampling-based MPC on the device", "MPPI with the learner in the
-// loop", "planner-collected experience"; DESIGN.md sections 26 to 28).  Host code only, beside urgym_policy_abi.hip: every check is made
-// here, before the first launch; every launch goes through urgym_mppi.h, urgym_mppi_guide.h, urgym_mppi_collect.h, the actor's and the
-// critic's own launches (urgym_actor.h, urgym_critic.h), the ring's store pass (urgym_replay.h) or through do_step of urgym_hip.hip
-// (urgym_handle.h).  As there, each entry point is a checking half, which launches nothing, and a
+// loop", "planner-collected experience", "elite samples and an adaptive std"; DESIGN.md sections 26 to 29).  Host code only, beside
+// urgym_policy_abi.hip: every check is made here, before the first launch; every launch goes through urgym_mppi.h, urgym_mppi_guide.h,
+// urgym_mppi_collect.h, urgym_mppi_elite.h, the actor's and the critic's own launches (urgym_actor.h, urgym_critic.h), the ring's store
+// pass (urgym_replay.h) or through do_step of urgym_hip.hip (urgym_handle.h); the one exception is the device-to-device copy of new_std
+// into std between two iterations of an adaptive plan.  As there, each entry point is a checking half, which launches nothing, and a
 // launching half, which refuses nothing.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -17,6 +18,7 @@
 #include "urgym_handle.h"
 #include "urgym_mppi.h"
 #include "urgym_mppi_collect.h"
+#include "urgym_mppi_elite.h"
 #include "urgym_mppi_guide.h"
 #include "urgym_replay.h"
 
@@ -211,15 +213,50 @@ void value_launch(const Handle* ph, const Guide& gd, hipStream_t s) {
   critic_launch(gd.critic, call, s);
 }
 
-// the launches of one plan; everything has been checked.  gd == nullptr: the plain plan.
-int plan(Handle* sh, Handle* ph, const urgym_mppi& m, uint64_t draw, hipStream_t s, const Guide* gd = nullptr) {
+// ---- elite samples and the adaptive std (urgym_mppi_adapt), resolved by check_adapt
+struct Adapt {
+  bool adapt_std = false;
+  float* std = nullptr;  // what the copy between two iterations writes
+  MppiElite call;
+};
+
+// the checks that concern urgym_mppi_adapt; m has been checked.  `report` keeps the message.
+int check_adapt(Handle* report, const urgym_mppi* m, const urgym_mppi_adapt* a, const char* who, Adapt* out) {
+  static_assert(sizeof(urgym_mppi_adapt) == 64 && alignof(urgym_mppi_adapt) == 8, "include/urgym.h");
+  if (!a) return fail_in(report, URGYM_ERR_ARG, who, "null urgym_mppi_adapt");
+  const char* what = nullptr;
+  if (a->elites < 1 || a->elites > m->samples) what = "urgym_mppi_adapt.elites must be in [1, samples]";
+  else if (!isfinite(a->std_min) || a->std_min < 0.0f) what = "urgym_mppi_adapt.std_min must be finite and not negative";
+  else if (!isfinite(a->std_max) || a->std_max < 0.0f) what = "urgym_mppi_adapt.std_max must be finite and not negative";
+  else if (a->std_min > a->std_max) what = "urgym_mppi_adapt.std_min must not exceed std_max";
+  if (what) return fail_in(report, URGYM_ERR_ARG, who, what);
+  const NamedPointer required[] = {{"std", a->std}, {"new_std", a->new_std}, {"elite_count", a->elite_count}, {"threshold", a->threshold}};
+  for (const NamedPointer& r : required)
+    if (!r.p) return failf(report, URGYM_ERR_ARG, "%s: urgym_mppi_adapt.%s is null", who, r.name);
+  Adapt r;
+  r.adapt_std = a->adapt_std != 0;
+  r.std = a->std;
+  r.call = MppiElite{a->elites, a->std_min, a->std_max, a->std, a->new_std, a->rank, a->elite, a->elite_count, a->threshold};
+  *out = r;
+  return URGYM_OK;
+}
+
+// the launches of one plan; everything has been checked.  gd == nullptr: the plain plan.  ad == nullptr: the plain update and sample;
+// else the elite update stands in place of the update and, with adapt_std, iterations >= 1 sample with new_std of the iteration before.
+int plan(Handle* sh, Handle* ph, const urgym_mppi& m, uint64_t draw, hipStream_t s, const Guide* gd = nullptr, const Adapt* ad = nullptr) {
   const size_t row = (size_t)ph->cfg.num_envs * 6;
   const MppiFanout f = fanout_of(sh, ph, m);
   const MppiOutcome o = outcome_of(ph);
   const bool proposes = gd && gd->call.policy_samples > 0;
   for (int i = 0; i < m.iterations; i++) {
     mppi_fanout_launch(f, s);
-    mppi_sample_launch(m, draw, i, s);
+    if (ad && ad->adapt_std && i >= 1) {
+      const size_t bytes = (size_t)m.horizon * (size_t)m.num_parents * 6 * sizeof(float);
+      HIP_TRY(sh, hipMemcpyAsync(ad->std, ad->call.new_std, bytes, hipMemcpyDeviceToDevice, s));
+      mppi_sample_adaptive_launch(m, ad->call, draw, i, s);
+    } else {
+      mppi_sample_launch(m, draw, i, s);
+    }
     for (int h = 0; h < m.horizon; h++) {
       if (proposes) {
         policy_launch(ph, *gd, s);
@@ -238,7 +275,8 @@ int plan(Handle* sh, Handle* ph, const urgym_mppi& m, uint64_t draw, hipStream_t
     if (gd && gd->terminal) mppi_terminal_launch(m, gd->call, s);
     urgym_mppi last = m;
     if (i + 1 < m.iterations) last.shift = 0;  // the sequence advances once, after the last refinement
-    mppi_update_launch(last, s);
+    if (ad) mppi_elite_update_launch(last, ad->call, s);
+    else mppi_update_launch(last, s);
   }
   return URGYM_OK;
 }
@@ -246,10 +284,11 @@ int plan(Handle* sh, Handle* ph, const urgym_mppi& m, uint64_t draw, hipStream_t
 // the launches of the closed loop; everything has been checked.  Every launch goes to `s`: stream order alone puts a plan's update
 // before the source step that reads action_out, and that step before the record pass that files its outcome and the fan-out that
 // clones its state.
-int control(Handle* sh, Handle* ph, const urgym_mppi& m, uint64_t first_draw, int num_steps, const urgym_trajectory* traj, hipStream_t s, const Guide* gd = nullptr) {
+int control(Handle* sh, Handle* ph, const urgym_mppi& m, uint64_t first_draw, int num_steps, const urgym_trajectory* traj, hipStream_t s, const Guide* gd = nullptr,
+            const Adapt* ad = nullptr) {
   mppi_record_launch(record_of(sh, m, traj, 0, num_steps), s);
   for (int t = 0; t < num_steps; t++) {
-    if (int rc = plan(sh, ph, m, first_draw + (uint64_t)t, s, gd)) return rc;
+    if (int rc = plan(sh, ph, m, first_draw + (uint64_t)t, s, gd, ad)) return rc;
     if (int rc = do_step(sh, m.action_out, s)) return rc;
     mppi_record_launch(record_of(sh, m, traj, t + 1, num_steps), s);
   }
@@ -328,13 +367,13 @@ ReplayStore store_of(const Handle* h, const urgym_replay_ring& r, int first_slot
 // clones the source's state and reads mean, the plan's update before the execute launch that reads action_out, and that before the
 // source step that reads the slot's action rows.
 int collect(Handle* sh, Handle* ph, const urgym_mppi& m, const Guide* gd, const urgym_mppi_explore& x, uint64_t first_draw, int num_steps,
-            const urgym_replay_ring& ring, int first_slot, hipStream_t s) {
+            const urgym_replay_ring& ring, int first_slot, hipStream_t s, const Adapt* ad = nullptr) {
   const size_t row = (size_t)sh->cfg.num_envs * 6, C = (size_t)ring.capacity_steps;
   for (int t = 0; t < num_steps; t++) {
     replay_store_launch(store_of(sh, ring, first_slot, t, num_steps), s);
     if (t > 0) mppi_record_launch(record_of(sh, m, nullptr, t, num_steps), s);
     const uint64_t draw = first_draw + (uint64_t)t;
-    if (int rc = plan(sh, ph, m, draw, s, gd)) return rc;
+    if (int rc = plan(sh, ph, m, draw, s, gd, ad)) return rc;
     float* actions = ring.action + (((size_t)first_slot + (size_t)t) % C) * row;  // the execute launch writes the slot, the step reads it
     mppi_execute_launch(execute_of(m, x, draw, actions), s);
     if (int rc = do_step(sh, actions, s)) return rc;
@@ -502,6 +541,78 @@ int urgym_mppi_collect(void* source_handle, void* planner_handle, const urgym_mp
   if (int rc = check_draw(sh, first_draw, num_steps, who)) return rc;
   HIP_TRY(sh, hipSetDevice(sh->device));
   if (int rc = collect(sh, ph, *m, guide_or_NULL ? &gd : nullptr, *x, first_draw, num_steps, *ring, first_slot, (hipStream_t)stream)) return rc;
+  return launched(sh);
+}
+
+int urgym_mppi_sample_adaptive(void* handle, const urgym_mppi* m, const urgym_mppi_adapt* a, uint64_t draw, int iteration, void* stream) {
+  const char* who = "urgym_mppi_sample_adaptive";
+  Handle* h = (Handle*)handle;
+  Adapt ad;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (int rc = check_mppi(h, m, who)) return rc;
+  if (int rc = check_adapt(h, m, a, who, &ad)) return rc;
+  if (int rc = check_draw(h, draw, 1, who)) return rc;
+  if (iteration < 0 || iteration >= URGYM_MPPI_ITERATIONS_MAX) return fail_in(h, URGYM_ERR_ARG, who, "iteration must be in [0, URGYM_MPPI_ITERATIONS_MAX)");
+  HIP_TRY(h, hipSetDevice(h->device));
+  mppi_sample_adaptive_launch(*m, ad.call, draw, iteration, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_mppi_update_elite(void* handle, const urgym_mppi* m, const urgym_mppi_adapt* a, void* stream) {
+  const char* who = "urgym_mppi_update_elite";
+  Handle* h = (Handle*)handle;
+  Adapt ad;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (int rc = check_mppi(h, m, who)) return rc;
+  if (int rc = check_adapt(h, m, a, who, &ad)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  mppi_elite_update_launch(*m, ad.call, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_mppi_plan_adaptive(void* source_handle, void* planner_handle, const urgym_mppi* m, const urgym_mppi_adapt* a, const urgym_mppi_guide* guide_or_NULL, uint64_t draw, void* stream) {
+  const char* who = "urgym_mppi_plan_adaptive";
+  Handle *sh = (Handle*)source_handle, *ph = (Handle*)planner_handle;
+  Guide gd;
+  Adapt ad;
+  if (!sh) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (int rc = guide_or_NULL ? check_guided_pair(sh, ph, m, guide_or_NULL, who, &gd) : check_pair(sh, ph, m, who)) return rc;
+  if (int rc = check_adapt(sh, m, a, who, &ad)) return rc;
+  if (int rc = check_draw(sh, draw, 1, who)) return rc;
+  HIP_TRY(sh, hipSetDevice(sh->device));
+  if (int rc = plan(sh, ph, *m, draw, (hipStream_t)stream, guide_or_NULL ? &gd : nullptr, &ad)) return rc;
+  return launched(sh);
+}
+
+int urgym_mppi_control_adaptive(void* source_handle, void* planner_handle, const urgym_mppi* m, const urgym_mppi_adapt* a, const urgym_mppi_guide* guide_or_NULL, uint64_t first_draw, int num_steps, const urgym_trajectory* traj_or_NULL, void* stream) {
+  const char* who = "urgym_mppi_control_adaptive";
+  Handle *sh = (Handle*)source_handle, *ph = (Handle*)planner_handle;
+  Guide gd;
+  Adapt ad;
+  if (!sh) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (int rc = guide_or_NULL ? check_guided_pair(sh, ph, m, guide_or_NULL, who, &gd) : check_pair(sh, ph, m, who)) return rc;
+  if (int rc = check_adapt(sh, m, a, who, &ad)) return rc;
+  if (int rc = check_record(sh, 0, num_steps, traj_or_NULL, who)) return rc;
+  if (int rc = check_draw(sh, first_draw, num_steps, who)) return rc;
+  HIP_TRY(sh, hipSetDevice(sh->device));
+  if (int rc = control(sh, ph, *m, first_draw, num_steps, traj_or_NULL, (hipStream_t)stream, guide_or_NULL ? &gd : nullptr, &ad)) return rc;
+  return launched(sh);
+}
+
+int urgym_mppi_collect_adaptive(void* source_handle, void* planner_handle, const urgym_mppi* m, const urgym_mppi_adapt* a, const urgym_mppi_guide* guide_or_NULL, const urgym_mppi_explore* x, uint64_t first_draw, int num_steps, const urgym_replay_ring* ring, int first_slot, void* stream) {
+  const char* who = "urgym_mppi_collect_adaptive";
+  Handle *sh = (Handle*)source_handle, *ph = (Handle*)planner_handle;
+  Guide gd;
+  Adapt ad;
+  if (!sh) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (int rc = guide_or_NULL ? check_guided_pair(sh, ph, m, guide_or_NULL, who, &gd) : check_pair(sh, ph, m, who)) return rc;
+  if (int rc = check_adapt(sh, m, a, who, &ad)) return rc;
+  if (!sh->observed) return fail_in(sh, URGYM_ERR_STATE, who, "nothing has been observed yet: urgym_reset() or urgym_refresh() the source first");
+  if (int rc = check_explore(sh, x, who)) return rc;
+  if (int rc = check_ring(sh, ring, first_slot, num_steps, who)) return rc;
+  if (int rc = check_draw(sh, first_draw, num_steps, who)) return rc;
+  HIP_TRY(sh, hipSetDevice(sh->device));
+  if (int rc = collect(sh, ph, *m, guide_or_NULL ? &gd : nullptr, *x, first_draw, num_steps, *ring, first_slot, (hipStream_t)stream, &ad)) return rc;
   return launched(sh);
 }
 

@@ -2629,12 +2629,21 @@ def mppi_noise(seed, draw, iteration, parents, samples, steps, dtype=np.float32)
 
 def mppi_actions(mean, eps, sigma):
     """THE SAMPLE's action line in numpy, bitwise: `mean` float32 [H, E, 6], `eps` float32 [H, E * K, 6]; planner env n = p * K + j reads
-    parent p's mean.  s = sigma * eps; a = mean + s; action = fmin(fmax(a, -1), 1), each one float32 operation."""
+    parent p's mean.  s = sigma * eps; a = mean + s; action = fmin(fmax(a, -1), 1), each one float32 operation.  `sigma` is a number, or
+    -- THE ADAPTIVE SAMPLE -- a float32 [H, E, 6] array of one width per element, read as the mean is."""
     mean, eps = np.asarray(mean), np.asarray(eps)
     if mean.dtype != np.float32 or eps.dtype != np.float32 or mean.ndim != 3 or eps.ndim != 3 or eps.shape[1] % mean.shape[1]:
         raise ValueError(f"mean must be float32 [H, E, 6] and eps float32 [H, E * K, 6], got {mean.dtype} {mean.shape}, {eps.dtype} {eps.shape}")
-    s = np.float32(sigma) * eps
-    a = np.repeat(mean, eps.shape[1] // mean.shape[1], axis=1) + s
+    K = eps.shape[1] // mean.shape[1]
+    if np.ndim(sigma) == 0:
+        width = np.float32(sigma)
+    else:
+        width = np.asarray(sigma)
+        if width.dtype != np.float32 or width.shape != mean.shape:
+            raise ValueError(f"an array sigma must be float32 {mean.shape} like mean, got {width.dtype} {width.shape}")
+        width = np.repeat(width, K, axis=1)
+    s = width * eps
+    a = np.repeat(mean, K, axis=1) + s
     return np.fmin(np.fmax(a, np.float32(-1)), np.float32(1))
 
 
@@ -2700,6 +2709,63 @@ def mppi_update(ret, w, actions, shift):
         mean[:-1] = new_mean[1:]
     rmax = np.where(np.isfinite(r), r, -np.inf).max(axis=1)
     return dict(new_mean=new_mean, mean=mean, action_out=new_mean[0].copy(), best_return=rmax, nominal_return=r[:, 0].copy(), ess=ess)
+
+
+def mppi_elite_rank(ret, samples, elites):
+    """THE RANK in numpy (include/urgym.h, "elite samples and an adaptive std"): `ret` float64 [E * K].  key = the return, or -inf where it
+    is not finite; rank_j counts the samples of the same parent with a larger key, or an equal key (-0.0 == 0.0) and a lower index.
+    Returns a dict of rank (int32 [E, K], a permutation per parent), elite (uint8 [E, K]: rank < `elites` and finite), elite_count (int32
+    [E]) and threshold (float64 [E]: the smallest elite return, its bits kept; -inf with no elite)."""
+    K, M = int(samples), int(elites)
+    if not 1 <= M <= K:
+        raise ValueError(f"elites must be in [1, samples], got {M}, {K}")
+    r = np.asarray(ret, dtype=np.float64).reshape(-1, K)
+    finite = np.isfinite(r)
+    key = np.where(finite, r, -np.inf)
+    index = np.arange(K)
+    before = (key[:, :, None] > key[:, None, :]) | ((key[:, :, None] == key[:, None, :]) & (index[:, None] < index[None, :]))  # [p, i, j]
+    rank = before.sum(axis=1).astype(np.int32)
+    elite = (rank < M) & finite
+    count = elite.sum(axis=1).astype(np.int32)
+    threshold = np.full(r.shape[0], -np.inf, np.float64)
+    for p in np.nonzero(count)[0]:
+        threshold[p] = r[p, rank[p] == count[p] - 1][0]
+    return dict(rank=rank, elite=elite.astype(np.uint8), elite_count=count, threshold=threshold)
+
+
+def mppi_elite_weights(ret, lam, samples, elites):
+    """THE ELITE WEIGHT with numpy's float64 exp in place of the device's: ``mppi_weights`` with every sample that is no elite weighing
+    nothing.  Returns (w [E, K], rmax [E]); with ``elites == samples`` they are ``mppi_weights``'."""
+    w, rmax = mppi_weights(ret, lam, samples)
+    elite = mppi_elite_rank(ret, samples, elites)["elite"] != 0
+    none = ~np.isfinite(np.asarray(ret, dtype=np.float64).reshape(-1, int(samples))).any(axis=1)
+    w = np.where(elite | none[:, None], w, 0.0)
+    return w, rmax
+
+
+def mppi_elite_update(ret, w, actions, shift, std_min, std_max):
+    """THE ELITE UPDATE in numpy given the weights, bitwise: ``mppi_update``'s dict (the same lines on the same `w`, zero for a sample that
+    is no elite) and new_std, float32 [H, E, 6] -- THE STD: m = S / Z unrounded; per sample d = a - m, dd = d * d, t = w * dd; V their
+    ordered sum; v = V / Z; sd = sqrt(v); fmin(fmax(sd, std_min), std_max), rounded to float32 once.  A NaN v ends at std_min."""
+    out = mppi_update(ret, w, actions, shift)
+    w, actions = np.asarray(w), np.asarray(actions)
+    E, K = w.shape
+    H = actions.shape[0]
+    lo, hi = np.float64(np.float32(std_min)), np.float64(np.float32(std_max))
+    new_std = np.zeros((H, E, 6), np.float32)
+    with np.errstate(all="ignore"):
+        for p in range(E):
+            Z = ordered_sum(w[p], np.float64)
+            a = actions[:, p * K:(p + 1) * K].astype(np.float64)
+            for h in range(H):
+                for c in range(6):
+                    m = ordered_sum(w[p] * a[h, :, c], np.float64) / Z
+                    d = a[h, :, c] - m
+                    dd = d * d
+                    v = ordered_sum(w[p] * dd, np.float64) / Z
+                    new_std[h, p, c] = np.float32(np.fmin(np.fmax(np.sqrt(v), lo), hi))
+    out["new_std"] = new_std
+    return out
 
 
 def mppi_guided_actions(actions, policy_action, eps, policy_sigma, samples, policy_samples):
@@ -2803,12 +2869,20 @@ class DeviceMPPI:
     see its raw rows.  `policy_samples` = P in [0, samples - 1]: samples 1 .. P of every parent execute actor(state) + `policy_sigma` *
     noise at every horizon step.  `terminal_value`: a future still alive after the horizon is credited gamma^H min Q(s_H, actor(s_H));
     the shipped critics were trained with gamma = 0.95, so use ``gamma=0.95`` with them.  `fail_cost`: a future that ends without success
-    is charged that much, discounted.  With all four at their defaults the plain entry points are called as before."""
+    is charged that much, discounted.  With all four at their defaults the plain entry points are called as before.
+
+    Elite samples and the adaptive std, opt-in.  `elites` = M in [1, samples]: only the M best-scoring samples of
+    a parent weigh in (``None``: every finite one, as before).  `adapt_std`: the update also forms a standard deviation per (horizon step,
+    joint) from the elites, clamped to [`std_min`, `std_max`] (`std_max` defaults to `sigma`), and iterations >= 1 of the same plan sample
+    with it; every plan starts at `sigma` again.  With either given the ``urgym_mppi_*_adaptive`` entry points are called, ``adapt()`` is
+    the struct, and ``DIAGNOSTICS`` gains ``elite_count`` and ``threshold``; with ``elites=None`` and ``adapt_std=False`` the planner
+    makes exactly the calls it made before."""
 
     DIAGNOSTICS = ("best_return", "nominal_return", "ess")
 
     def __init__(self, env, samples=256, horizon=6, sigma=0.6, lam=5.0, gamma=1.0, iterations=1, shift=True, seed=0, keep_weights=False,
-                 actor=None, critic=None, policy_samples=0, policy_sigma=0.0, terminal_value=False, fail_cost=0.0):
+                 actor=None, critic=None, policy_samples=0, policy_sigma=0.0, terminal_value=False, fail_cost=0.0, elites=None, adapt_std=False,
+                 std_min=0.05, std_max=None):
         import ctypes as C
 
         import torch
@@ -2821,6 +2895,7 @@ class DeviceMPPI:
             raise ValueError(f"DeviceMPPI: samples must be in [2, 1024], horizon in [1, 64], iterations in [1, 8]; got {samples}, {horizon}, {iterations}")
         if not (np.isfinite(sigma) and sigma >= 0 and np.isfinite(lam) and lam > 0 and np.isfinite(gamma)):
             raise ValueError(f"DeviceMPPI: sigma must be finite and >= 0, lam finite and > 0, gamma finite; got {sigma}, {lam}, {gamma}")
+        adapt = self.check_adapt(K, sigma, elites, adapt_std, std_min, std_max)
         same = {name: getattr(env.cfg, name) for name, _ in _abi.Config._fields_ if name not in ("env_kind", "num_envs", "auto_reset", "check_collision")}
         self.env = env
         self.planner = UR5ReachVectorEnv(env.env_id, num_envs=E * K, device=env.device, auto_reset=False, check_collision=bool(env.cfg.check_collision), **same)
@@ -2837,6 +2912,15 @@ class DeviceMPPI:
             self.buf[name] = torch.zeros(shape(E, K, H), dtype=_TORCH_DTYPE[ct], device=env.device)
             setattr(M, name, C.cast(self.buf[name].data_ptr(), C.POINTER(ct)))
         self._struct = M
+        self._adapt = None
+        if adapt is not None:
+            A = _abi.MppiAdapt()
+            A.elites, A.adapt_std, A.std_min, A.std_max = adapt
+            for name, ct, shape in _abi.MPPI_ADAPT_FIELDS:
+                self.buf[name] = torch.zeros(shape(E, K, H), dtype=_TORCH_DTYPE[ct], device=env.device)
+                setattr(A, name, C.cast(self.buf[name].data_ptr(), C.POINTER(ct)))
+            self._adapt = A
+            self.DIAGNOSTICS = DeviceMPPI.DIAGNOSTICS + ("elite_count", "threshold")
         self.actor = self.critic = self._guide = None
         P = int(policy_samples)
         if P or terminal_value or fail_cost or policy_sigma:
@@ -2880,9 +2964,29 @@ class DeviceMPPI:
                 setattr(G, name, C.cast(self.buf[name].data_ptr(), C.POINTER(ct)))
         return G
 
+    @staticmethod
+    def check_adapt(samples, sigma, elites=None, adapt_std=False, std_min=0.05, std_max=None):
+        """Raises ValueError for what the adaptive entry points refuse about urgym_mppi_adapt's scalars.  Returns None where neither option
+        is asked for, else (elites, adapt_std, std_min, std_max) as the struct takes them.  Needs no GPU."""
+        if elites is None and not adapt_std:
+            return None
+        M = int(samples) if elites is None else int(elites)
+        if isinstance(elites, bool) or not 1 <= M <= int(samples):
+            raise ValueError(f"DeviceMPPI: elites must be in [1, samples], got {elites!r}")
+        lo, hi = float(std_min), float(sigma) if std_max is None else float(std_max)
+        with np.errstate(over="ignore"):
+            ok = bool(np.isfinite(np.float32(lo))) and bool(np.isfinite(np.float32(hi))) and 0.0 <= lo and np.float32(lo) <= np.float32(hi)
+        if not ok:
+            raise ValueError(f"DeviceMPPI: std_min and std_max must be finite (in float32) with 0 <= std_min <= std_max, got {std_min!r}, {std_max!r}")
+        return M, int(bool(adapt_std)), lo, hi
+
     def struct(self):
         """The ``urgym_mppi`` of this planner (its pointers stay valid until ``close``)."""
         return self._struct
+
+    def adapt(self):
+        """The ``urgym_mppi_adapt`` of this planner, or None where neither `elites` nor `adapt_std` was given."""
+        return self._adapt
 
     def guide(self):
         """The ``urgym_mppi_guide`` of this planner, or None where the learner is not in the loop."""
@@ -2890,14 +2994,17 @@ class DeviceMPPI:
 
     def plan(self, draw=0):
         """One ``urgym_mppi_plan`` from the environment's state as it stands.  Returns (action_out [E, 6], diagnostics): views of this
-        planner's buffers, overwritten by the next plan; diagnostics holds ``best_return``, ``nominal_return`` and ``ess`` [E].  NOT
-        synchronised."""
+        planner's buffers, overwritten by the next plan; diagnostics holds ``best_return``, ``nominal_return`` and ``ess`` [E], and with
+        elites or the adaptive std ``elite_count`` and ``threshold`` [E].  NOT synchronised."""
         import ctypes as C
 
         from . import _native
 
         env = self.env
-        if self._guide is None:
+        guide = None if self._guide is None else C.byref(self._guide)
+        if self._adapt is not None:
+            _native.check(env.lib.urgym_mppi_plan_adaptive(env._h, self.planner._h, C.byref(self._struct), C.byref(self._adapt), guide, int(draw), env._stream()), env._h)
+        elif self._guide is None:
             _native.check(env.lib.urgym_mppi_plan(env._h, self.planner._h, C.byref(self._struct), int(draw), env._stream()), env._h)
         else:
             _native.check(env.lib.urgym_mppi_plan_guided(env._h, self.planner._h, C.byref(self._struct), C.byref(self._guide), int(draw), env._stream()), env._h)
@@ -2930,7 +3037,11 @@ class DeviceMPPI:
                 t = torch.zeros(shape(T, env.num_envs, env.obs_dim, env.goal_dim), dtype=_TORCH_DTYPE[ct], device=env.device)
                 setattr(traj, name, C.cast(t.data_ptr(), C.POINTER(ct)))
                 out[name] = t.view(torch.bool) if ct is C.c_uint8 else t
-        if self._guide is None:
+        if self._adapt is not None:
+            _native.check(env.lib.urgym_mppi_control_adaptive(env._h, self.planner._h, C.byref(self._struct), C.byref(self._adapt),
+                                                              None if self._guide is None else C.byref(self._guide), int(first_draw), T,
+                                                              C.byref(traj) if names else None, env._stream()), env._h)
+        elif self._guide is None:
             _native.check(env.lib.urgym_mppi_control(env._h, self.planner._h, C.byref(self._struct), int(first_draw), T, C.byref(traj) if names else None,
                                                      env._stream()), env._h)
         else:
@@ -2983,7 +3094,12 @@ class DeviceMPPI:
         first = replay.cursor if first_slot is None else first_slot
         replay.check_args(replay.capacity, num_steps=num_steps, first_slot=first)
         x = _abi.MppiExplore(self.check_explore(explore_sigma), 0, None)
-        _native.check(env.lib.urgym_mppi_collect(env._h, self.planner._h, C.byref(self._struct), None if self._guide is None else C.byref(self._guide),
+        guide = None if self._guide is None else C.byref(self._guide)
+        if self._adapt is not None:
+            _native.check(env.lib.urgym_mppi_collect_adaptive(env._h, self.planner._h, C.byref(self._struct), C.byref(self._adapt), guide, C.byref(x),
+                                                              int(first_draw), int(num_steps), C.byref(replay._ring), int(first), env._stream()), env._h)
+            return
+        _native.check(env.lib.urgym_mppi_collect(env._h, self.planner._h, C.byref(self._struct), guide,
                                                  C.byref(x), int(first_draw), int(num_steps), C.byref(replay._ring), int(first), env._stream()), env._h)
 
     def reset_plan(self, mask=None):
