@@ -2084,6 +2084,95 @@ int urgym_mppi_plan_adaptive(void* source_handle, void* planner_handle, const ur
 int urgym_mppi_control_adaptive(void* source_handle, void* planner_handle, const urgym_mppi* m, const urgym_mppi_adapt* a, const urgym_mppi_guide* guide_or_NULL, uint64_t first_draw, int num_steps, const urgym_trajectory* traj_or_NULL, void* stream);
 int urgym_mppi_collect_adaptive(void* source_handle, void* planner_handle, const urgym_mppi* m, const urgym_mppi_adapt* a, const urgym_mppi_guide* guide_or_NULL, const urgym_mppi_explore* x, uint64_t first_draw, int num_steps, const urgym_replay_ring* ring, int first_slot, void* stream);
 
+/* ---- the planner inside the training call, with plan statistics.  urgym_mppi_collect(_adaptive) is a collection
+ * whose policy is the planner, but a run that trains on it went back to the host between every collection, its updates and the reload
+ * of the planner's actor and critic.  urgym_sac_train_planned is urgym_sac_train and its kin with that collection inside, and
+ * urgym_mppi_stats reduces what a plan left in best_return, nominal_return, ess (and elite_count, threshold) to one record on the device,
+ * at the points where the call writes the monitor's records.  Added WITHIN ABI version 4: no struct above changed, the two new symbols
+ * are found by lookup, and every call above launches and leaves what it did.
+ *
+ * THE PLAN STATISTICS (urgym_mppi_stats: ONE launch of ONE workgroup of 1024 lanes, float64, no atomics, one writer per output; it
+ * reads the [E] diagnostics and writes the record, nothing else).  "finite" is r - r == 0 (false for a NaN and either infinity).  Every
+ * sum is THE ORDERED SUM ("SAC's entropy coefficient on the device") over ALL parents p < E: a parent that is passed over contributes
+ * the term +0.0, so the order depends on E alone.  Every mean is one float64 division of the sum by (double)count, and +0.0 where the
+ * count is 0.
+ *   planned          = #{p : best_return[p] finite}      (the update writes -inf where no sample's return was finite)
+ *   mean_best_return = (the sum of best_return[p] over those p) / planned
+ *   nominal_finite   = #{p : nominal_return[p] finite};  mean_nominal_return likewise
+ *   gain_count       = #{p : both finite};  mean_gain = (the sum of best_return[p] - nominal_return[p], one subtraction, over those p) / gain_count
+ *   mean_ess         = (the sum of ess[p] over all p) / E: a NaN in one parent's ess reaches mean_ess of that record, and nothing else
+ *   min_ess          = fmin over all p, with what fmin leaves open fixed: f(a, b) = a is NaN ? b : b is NaN ? a : b < a ? b : a.  Lane t
+ *                      starts at NaN and takes p = t, t + 1024, ... ascending as m = f(m, ess[p]); the 1024 results are folded by THE
+ *                      ORDERED SUM's levels, level[t] = f(level[t], level[t + s]), s = 512 .. 1.  NaN only where every ess is NaN.
+ *   with a:  mean_elite_count = (the sum of (double)elite_count[p] over all p) / E;  threshold_count = #{p : threshold[p] finite},
+ *            mean_threshold = (the sum of threshold[p] over those p) / threshold_count.  Without a the three fields are 0.
+ * The record is 88 bytes, 8-byte aligned; an array of records is contiguous. */
+typedef struct urgym_mppi_stats_record {
+  double mean_best_return;
+  double mean_nominal_return;
+  double mean_gain;
+  double mean_ess;
+  double min_ess;
+  double mean_elite_count;      /* 0 without urgym_mppi_adapt */
+  double mean_threshold;        /* 0 without urgym_mppi_adapt */
+  int64_t iteration;            /* the caller's tag */
+  int32_t num_parents;          /* E */
+  int32_t planned;
+  int32_t nominal_finite;
+  int32_t gain_count;
+  int32_t threshold_count;      /* 0 without urgym_mppi_adapt */
+  int32_t reserved0;            /* written as 0 */
+} urgym_mppi_stats_record;
+
+/* What urgym_sac_train_planned takes beyond the learner, the schedule and the options of urgym_sac_train_clipped: the planner that
+ * collects.  The training handle is the planner's source. */
+typedef struct urgym_sac_planning {
+  void* planner_handle;
+  const urgym_mppi* mppi;
+  const urgym_mppi_adapt* adapt_or_NULL;
+  const urgym_mppi_guide* guide_or_NULL;
+  urgym_mppi_explore explore;
+  int32_t sync;                       /* != 0: after the updates of every non-idle iteration the guide's actor and critic are reloaded */
+  int32_t record_capacity;            /* >= 0 */
+  urgym_mppi_stats_record* records;   /* [record_capacity] or NULL: no plan statistics */
+  int64_t reserved0;                  /* must be 0 */
+} urgym_sac_planning;
+
+/* The single launch; it needs no bound environment.  record_dev is a DEVICE pointer.  Refused, launching and writing nothing: a NULL
+ * handle, m or record_dev; num_parents < 1 or above 65,536; a NULL best_return, nominal_return or ess; with a, a NULL elite_count or
+ * threshold; a record_dev that is not 8-byte aligned. */
+int urgym_mppi_stats(void* handle, const urgym_mppi* m, const urgym_mppi_adapt* a_or_NULL, urgym_mppi_stats_record* record_dev, int64_t iteration, void* stream);
+
+/* THE PLANNED TRAINING CALL.  With K = steps_per_iteration and G = updates_per_iteration, iteration i enqueues
+ *   1. the launches of urgym_mppi_collect, or of urgym_mppi_collect_adaptive where adapt_or_NULL is given, with the planning's mppi,
+ *      guide and explore, first_draw = the iteration's collect_first_draw (the field the sampled collection draws with), num_steps = K and
+ *      first_slot = the iteration's collect_first_slot; with priorities, urgym_per_fill on those slots.  Every step is planned:
+ *      schedule->uniform_iterations has no meaning and must be 0;
+ *   2. for an iteration that is not idle, the G updates exactly as urgym_sac_train_clipped with the same options launches them
+ *      (clipping_or_NULL == NULL: as urgym_sac_train_nstep, _prioritized, _hindsight or urgym_sac_train do);
+ *   3. where sync != 0, the iteration is not idle and G > 0: the launch of urgym_actor_load on the planner handle, guide->actor from
+ *      learner->actor_adam.param, then the launch of urgym_critic_load on the planner handle, guide->critic from
+ *      learner->critic_adam.param (the ONLINE critics) with tau = 1.  One launch each on the call's stream; a part the guide does not
+ *      use is skipped (an actor given with policy_samples == 0 and no terminal_value, a critic given without terminal_value); without a
+ *      guide nothing is launched;
+ *   4. what urgym_sac_train_monitored runs after an iteration (the monitor's fold, its record, the evaluation), and, where
+ *      planning->records is given, directly after every urgym_monitor_stats launch that writes monitor record r one urgym_mppi_stats
+ *      launch into planning->records[r], with iteration = monitoring->first_iteration + i + 1: the index is the monitor's own
+ *      (first_record + the records of the call so far).  The record describes the LAST plan of iteration i: neither the updates nor the
+ *      reload touch the buffers it reads.
+ * Bit for bit that sequence of single calls.  Two calls of a and b iterations whose counters are handed on leave the bits of one call
+ * of a + b iterations; mean is carried between calls.  There is no normalization argument: the planner's actor and critic read raw
+ * rows.  No allocation, no host synchronisation; everything is validated before the first launch.
+ * Refused, each launching and writing nothing (the message names urgym_sac_train_planned): a NULL handle; everything
+ * urgym_sac_train_clipped refuses about the learner, the schedule and the options given; a NULL planning, planner_handle or mppi; a
+ * non-zero reserved0; steps_per_iteration == 0 (there is nothing to plan); uniform_iterations != 0; everything
+ * urgym_mppi_collect(_adaptive) refuses about the two handles, mppi, adapt, guide, explore, the ring and the draws
+ * (collect_first_draw + num_iterations * K > 2^32); planner_handle equal to the training handle or to the evaluation's eval_handle;
+ * with sync != 0, a guide's actor whose in_features / hidden_width are not learner->actor_adam's, or a guide's critic whose shape is
+ * not learner->critic_adam's; a negative record_capacity; records without monitoring; records with fewer than monitoring->first_record
+ * + the record points of the call entries; records not 8-byte aligned. */
+int urgym_sac_train_planned(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_planning* planning, const urgym_sac_clipping* clipping_or_NULL, const urgym_sac_nstep* nstep_or_NULL, const urgym_sac_prioritized* prioritized_or_NULL, const urgym_sac_hindsight* hindsight_or_NULL, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream);
+
 /* Replaces Reach*.set_goal / set_goal_and_obstacle (reach.py:202-204, 328-335, 702-713): the caller has
  * overwritten goal / obst_start / obst_end (and possibly q) for the masked envs; this recomputes obstacle pose,
  * velocity, collision, link_dist and the observation for them, leaving step_count untouched. */

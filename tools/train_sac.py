@@ -33,8 +33,11 @@ was selected under beside it (evaluation.load_best_normalization reads them).
 (--planner-policy-samples) and critic (--planner-terminal-value), executes the plan's first action plus --planner-explore-sigma times
 exploration noise (--planner-iterations, --planner-elites, --planner-adapt-std, --planner-std-min, --planner-std-max: refinement with
 elite samples and an adaptive std), and after the trip's updates puts the planner's actor and critic on the learner's parameters (SACLearner.sync_planner).
-The Python loop only: not with --native (the native training call has no planner option yet) and not with --normalize (the planner's
-actor and critic read raw rows).  It prints what it prints without.
+With --native the planned collection, the updates and the reload are inside the one call as well (SACLearner.train(planner=),
+urgym_sac_train_planned), and with --monitor every line of the training curve is followed by a line of plan
+statistics over the envs' last plans (evaluation.mppi_plan_stats: the mean best and nominal return, their mean difference, the mean and
+the lowest effective sample size, how many envs had a finite plan, and with elites their mean count and threshold).  Not with
+--normalize (the planner's actor and critic read raw rows).  Otherwise it prints what it prints without.
 """
 import argparse
 import json
@@ -116,7 +119,7 @@ def main():
                          "arrays as --save-best writes them, one file per Q-network; moments and step count start at zero")
     ap.add_argument("--planner", action="store_true",
                     help="collect with an MPPI planner on the step kernel instead of the sampled policy, from the first trip on "
-                         "(SACLearner.collect(planner=); the Python loop only: not with --native or --normalize)")
+                         "(SACLearner.collect(planner=), with --native SACLearner.train(planner=); not with --normalize)")
     ap.add_argument("--planner-samples", type=int, default=64, help="--planner: futures per env, in [2, 1024]; the planner steps num-envs times as many envs")
     ap.add_argument("--planner-horizon", type=int, default=6, help="--planner: steps of a future, in [1, 64]")
     ap.add_argument("--planner-sigma", type=float, default=0.6, help="--planner: standard deviation of the sampled action sequences")
@@ -135,8 +138,8 @@ def main():
     ap.add_argument("--planner-std-min", "--std-min", type=float, default=0.05, help="--planner-adapt-std: the floor of the adaptive std")
     ap.add_argument("--planner-std-max", "--std-max", type=float, default=None, help="--planner-adapt-std: its ceiling (default: --planner-sigma)")
     args = ap.parse_args()
-    if args.planner and (args.native or args.normalize):
-        raise SystemExit("--planner runs the Python loop on raw rows: not with --native (the native training call has no planner option yet) or --normalize")
+    if args.planner and args.normalize:
+        raise SystemExit("--planner plans on raw rows: not with --normalize (the planner's actor and critic read raw rows)")
     if args.save_every and not args.save:
         raise SystemExit("--save-every needs --save")
     if args.save_every < 0:
@@ -235,6 +238,14 @@ def main():
                               "train_mean_return": rec["mean_return"], "train_mean_length": rec["mean_length"],
                               "train_success_rate_percent": 100.0 * rec["success_rate"]}), flush=True)
 
+    def print_plan_stats(seconds):
+        for rec in planner.plan_stats(shown_curve, mon.count - shown_curve):  # beside the monitor's records, at their indices
+            print(json.dumps({"trips": rec["iteration"], "seconds": seconds, "plan_envs": rec["num_parents"], "plan_planned": rec["planned"],
+                              "plan_mean_best_return": rec["mean_best_return"], "plan_mean_nominal_return": rec["mean_nominal_return"],
+                              "plan_mean_gain": rec["mean_gain"], "plan_mean_ess": rec["mean_ess"], "plan_min_ess": rec["min_ess"],
+                              **(dict(plan_mean_elite_count=rec["mean_elite_count"], plan_mean_threshold=rec["mean_threshold"])
+                                 if planner.adapt() is not None else {})}), flush=True)
+
     if args.native:
         # one call for the whole run -- or, with --save-every, one per stretch between two checkpoints: split calls are bit for bit the
         # single one (the schedule's counters are handed on), so the checkpoints cost the launches nothing but their own copies
@@ -243,7 +254,8 @@ def main():
         while step < args.steps:
             n = min(stretch, args.steps - step)
             got = learner.train(replay, n, 1, args.updates_per_step, seed=args.seed, first_draw=updates, evaluation=ev, eval_every=args.eval_every,
-                                **(dict(monitor=mon, log_every=args.log_every) if mon is not None else {}))
+                                **(dict(monitor=mon, log_every=args.log_every) if mon is not None else {}),
+                                **(dict(planner=planner, explore_sigma=args.planner_explore_sigma, plan_stats=mon is not None) if planner is not None else {}))
             if args.max_grad_norm is not None:
                 curves.append(got)
             step, updates = step + n, learner.adam_state["step"]
@@ -260,6 +272,8 @@ def main():
                               "mean_episode_length": rec["mean_length"], "improved": bool(rec["improved"]), **norms}), flush=True)
         if mon is not None:
             print_curve(round(time.perf_counter() - t0, 1) if seconds is None else seconds)
+            if planner is not None:
+                print_plan_stats(round(time.perf_counter() - t0, 1) if seconds is None else seconds)
         if args.save_best and ev.best_state()[1] >= 0:
             ev.save_best(args.save_best)
     for step in range(step, args.steps):  # the Python loop (every trip of it where --native is off)

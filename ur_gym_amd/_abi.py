@@ -612,6 +612,26 @@ class MppiAdapt(C.Structure):
         (name, C.POINTER(ct)) for name, ct, _ in MPPI_ADAPT_FIELDS]
 
 
+class MppiStatsRecord(C.Structure):
+    """urgym_mppi_stats_record: one record of plan statistics over the E parents of a planner (urgym_mppi_stats)."""
+    _fields_ = [("mean_best_return", C.c_double), ("mean_nominal_return", C.c_double), ("mean_gain", C.c_double), ("mean_ess", C.c_double),
+                ("min_ess", C.c_double), ("mean_elite_count", C.c_double), ("mean_threshold", C.c_double), ("iteration", C.c_int64),
+                ("num_parents", C.c_int32), ("planned", C.c_int32), ("nominal_finite", C.c_int32), ("gain_count", C.c_int32),
+                ("threshold_count", C.c_int32), ("reserved0", C.c_int32)]
+
+
+MPPI_STATS_RECORD_WORDS = 11  # sizeof(urgym_mppi_stats_record) / 8: a record as a row of an int64 tensor
+MPPI_STATS_MAX_PARENTS = 65536  # SAC_TERMS_MAX_COUNT: one workgroup reduces them
+
+
+class SacPlanning(C.Structure):
+    """urgym_sac_planning: the planner that collects inside urgym_sac_train_planned, whether its actor and critic follow the learner, and
+    the plan-statistics records."""
+    _fields_ = [("planner_handle", C.c_void_p), ("mppi", C.POINTER(Mppi)), ("adapt_or_NULL", C.POINTER(MppiAdapt)), ("guide_or_NULL", C.POINTER(MppiGuide)),
+                ("explore", MppiExplore), ("sync", C.c_int32), ("record_capacity", C.c_int32), ("records", C.POINTER(MppiStatsRecord)),
+                ("reserved0", C.c_int64)]
+
+
 # Every symbol include/urgym.h declares (tests check that the built library exports each of them).
 EXPORTED_SYMBOLS = [
     "urgym_abi_version",
@@ -702,6 +722,8 @@ EXPORTED_SYMBOLS = [
     "urgym_mppi_plan_adaptive",
     "urgym_mppi_control_adaptive",
     "urgym_mppi_collect_adaptive",
+    "urgym_mppi_stats",
+    "urgym_sac_train_planned",
     "urgym_refresh",
     "urgym_invalidate_records",
     "urgym_derive_obstacle_motion",

@@ -1,5 +1,6 @@
 // urgym_mppi_abi.hip -- the planner's entry points of include/urgym.h ("sampling-based MPC on the device", "MPPI with the learner in the
-// loop", "planner-collected experience", "elite samples and an adaptive std"; DESIGN.md sections 26 to 29).  Host code only, beside
+// loop", "planner-collected experience", "elite samples and an adaptive std", "the planner inside the training call"; DESIGN.md
+// sections 26 to 30).  Host code only, beside
 // urgym_policy_abi.hip: every check is made here, before the first launch; every launch goes through urgym_mppi.h, urgym_mppi_guide.h,
 // urgym_mppi_collect.h, urgym_mppi_elite.h, the actor's and the critic's own launches (urgym_actor.h, urgym_critic.h), the ring's store
 // pass (urgym_replay.h) or through do_step of urgym_hip.hip (urgym_handle.h); the one exception is the device-to-device copy of new_std
@@ -20,6 +21,8 @@
 #include "urgym_mppi_collect.h"
 #include "urgym_mppi_elite.h"
 #include "urgym_mppi_guide.h"
+#include "urgym_mppi_stats.h"
+#include "urgym_mppi_train.h"
 #include "urgym_replay.h"
 
 using namespace urgym;
@@ -383,7 +386,84 @@ int collect(Handle* sh, Handle* ph, const urgym_mppi& m, const Guide* gd, const 
   return URGYM_OK;
 }
 
+// ---- plan statistics (urgym_mppi_stats)
+
+// the checks of urgym_mppi_stats but the null handle; `report` keeps the message
+int check_stats(Handle* report, const urgym_mppi* m, const urgym_mppi_adapt* a, urgym_mppi_stats_record* record, int64_t iteration, const char* who, MppiStatsCall* out) {
+  static_assert(sizeof(urgym_mppi_stats_record) == 88 && alignof(urgym_mppi_stats_record) == 8, "include/urgym.h");
+  const char* what = nullptr;
+  if (!m) what = "null urgym_mppi";
+  else if (!record) what = "null record_dev";
+  else if (m->num_parents < 1 || m->num_parents > SAC_TERMS_MAX_COUNT) what = "urgym_mppi.num_parents must be in [1, 65536]";
+  else if (!m->best_return || !m->nominal_return || !m->ess) what = "urgym_mppi.best_return, nominal_return or ess is null";
+  else if (a && (!a->elite_count || !a->threshold)) what = "urgym_mppi_adapt.elite_count or threshold is null";
+  else if ((uintptr_t)record % 8 != 0) what = "record_dev must be 8-byte aligned";
+  if (what) return fail_in(report, URGYM_ERR_ARG, who, what);
+  *out = MppiStatsCall{m->num_parents, iteration, m->best_return, m->nominal_return, m->ess, a ? a->elite_count : nullptr, a ? a->threshold : nullptr, record};
+  return URGYM_OK;
+}
+
 }  // namespace
+
+// ---- the planner inside the training call (urgym_mppi_train.h)
+namespace urgym {
+
+int planned_check(const char* who, Handle* h, const urgym_sac_planning* planning, const urgym_replay_ring* ring, const urgym_sac_schedule& S, PlannedCall* out) {
+  static_assert(sizeof(urgym_sac_planning) == 72 && alignof(urgym_sac_planning) == 8, "include/urgym.h");
+  if (!planning) return fail_in(h, URGYM_ERR_ARG, who, "null planning");
+  const urgym_sac_planning& P = *planning;
+  const char* what = nullptr;
+  if (!P.planner_handle) what = "urgym_sac_planning.planner_handle is null";
+  else if (!P.mppi) what = "urgym_sac_planning.mppi is null";
+  else if (P.reserved0 != 0) what = "urgym_sac_planning.reserved0 must be 0";
+  else if (P.record_capacity < 0) what = "urgym_sac_planning.record_capacity is negative";
+  else if (S.steps_per_iteration == 0) what = "steps_per_iteration is 0: there is nothing to plan";
+  else if (S.uniform_iterations != 0) what = "schedule->uniform_iterations must be 0 (the planner plans from the first step)";
+  if (what) return fail_in(h, URGYM_ERR_ARG, who, what);
+  Handle* ph = (Handle*)P.planner_handle;
+  if (ph == h) return fail_in(h, URGYM_ERR_ARG, who, "planner_handle is the training handle (source and planner are the same handle)");
+  const int K = S.steps_per_iteration;
+  PlannedCall c;
+  memset(&c, 0, sizeof(c));
+  Guide gd;
+  Adapt ad;
+  if (int rc = P.guide_or_NULL ? check_guided_pair(h, ph, P.mppi, P.guide_or_NULL, who, &gd) : check_pair(h, ph, P.mppi, who)) return rc;
+  if (P.adapt_or_NULL)
+    if (int rc = check_adapt(h, P.mppi, P.adapt_or_NULL, who, &ad)) return rc;
+  if (!h->observed) return fail_in(h, URGYM_ERR_STATE, who, "nothing has been observed yet: urgym_reset() or urgym_refresh() the source first");
+  if (int rc = check_explore(h, &P.explore, who)) return rc;
+  if (int rc = check_ring(h, ring, S.first_slot, K, who)) return rc;
+  if (S.collect_first_draw >= DRAW_END || S.collect_first_draw + (uint64_t)S.num_iterations * (uint64_t)K > DRAW_END)
+    return fail_in(h, URGYM_ERR_ARG, who, "draw must stay below 2^32 (collect_first_draw + num_iterations * steps_per_iteration)");
+  if (P.records)
+    if (int rc = check_stats(h, P.mppi, P.adapt_or_NULL, P.records, 0, who, &c.stats)) return rc;
+  c.source = h, c.planner = ph, c.m = *P.mppi, c.explore = P.explore, c.ring = *ring, c.records = P.records, c.record_capacity = P.record_capacity;
+  c.guided = P.guide_or_NULL != nullptr, c.adaptive = P.adapt_or_NULL != nullptr;
+  if (c.guided) c.guide = *P.guide_or_NULL, c.sync_actor = gd.actor, c.sync_critic = gd.critic;
+  if (c.adaptive) c.adapt = *P.adapt_or_NULL;
+  *out = c;
+  return URGYM_OK;
+}
+
+// planned_check has accepted the guide and the adapt struct: resolving them again refuses nothing
+int planned_collect(const PlannedCall& c, uint64_t first_draw, int num_steps, int first_slot, hipStream_t s) {
+  const char* who = "planned_collect";
+  Guide gd;
+  Adapt ad;
+  if (c.guided)
+    if (int rc = check_guide(c.source, c.planner, &c.m, &c.guide, who, &gd)) return rc;
+  if (c.adaptive)
+    if (int rc = check_adapt(c.source, &c.m, &c.adapt, who, &ad)) return rc;
+  return collect(c.source, c.planner, c.m, c.guided ? &gd : nullptr, c.explore, first_draw, num_steps, c.ring, first_slot, s, c.adaptive ? &ad : nullptr);
+}
+
+void planned_stats(const PlannedCall& c, urgym_mppi_stats_record* record, int64_t iteration, hipStream_t s) {
+  MppiStatsCall call = c.stats;
+  call.record = record, call.iteration = iteration;
+  mppi_stats_launch(call, s);
+}
+
+}  // namespace urgym
 
 extern "C" {
 
@@ -614,6 +694,16 @@ int urgym_mppi_collect_adaptive(void* source_handle, void* planner_handle, const
   HIP_TRY(sh, hipSetDevice(sh->device));
   if (int rc = collect(sh, ph, *m, guide_or_NULL ? &gd : nullptr, *x, first_draw, num_steps, *ring, first_slot, (hipStream_t)stream, &ad)) return rc;
   return launched(sh);
+}
+
+int urgym_mppi_stats(void* handle, const urgym_mppi* m, const urgym_mppi_adapt* a_or_NULL, urgym_mppi_stats_record* record_dev, int64_t iteration, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  MppiStatsCall c;
+  if (int rc = check_stats(h, m, a_or_NULL, record_dev, iteration, "urgym_mppi_stats", &c)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  mppi_stats_launch(c, (hipStream_t)stream);
+  return launched(h);
 }
 
 }  // extern "C"

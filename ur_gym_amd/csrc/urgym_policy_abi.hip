@@ -10,8 +10,9 @@
 //   - prioritized replay (urgym_per.h)
 //   - running normalization (urgym_norm.h), evaluation (urgym_eval.h, urgym_eval_schedule.h) and training-episode statistics
 //     (urgym_monitor.h): the checking halves, then their entry points
-//   - the training loop in one call: TrainOptions, TrainExtras, sac_train_body, and the eight urgym_sac_train* entry points
-//     (urgym_sac_schedule.h has the index arithmetic)
+//   - the training loop in one call: TrainOptions, TrainExtras, sac_train_body, and the nine urgym_sac_train* entry points
+//     (urgym_sac_schedule.h has the index arithmetic).  With a planner the collection and the plan statistics
+//     are urgym_mppi_abi.hip's, reached through urgym_mppi_train.h
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -37,6 +38,7 @@
 #include "urgym_per.h"
 #include "urgym_grad_clip.h"
 #include "urgym_norm.h"
+#include "urgym_mppi_train.h"
 
 using namespace urgym;
 
@@ -1756,6 +1758,7 @@ struct TrainOptions {
   const urgym_normalization* norm;         // the actor reads normalized rows, one fold after every collection, one urgym_norm_batch after every gather
   const urgym_sac_evaluation* evaluation;  // TrainExtras
   const urgym_sac_monitoring* monitoring;  // TrainExtras
+  const urgym_sac_planning* planning;      // the collection is the planner's (urgym_mppi_train.h), planner_sync after the updates, TrainExtras
 };
 
 // The evaluations and the training-episode statistics of one training call: what the body runs beside its own checks and launches.
@@ -1771,6 +1774,7 @@ struct TrainExtras {
   const urgym_sac_evaluation* evaluation;
   const urgym_sac_monitoring* monitoring;
   const urgym_normalization* norm;  // given: the evaluations are urgym_policy_evaluate_normalized's
+  const PlannedCall* planned;       // given: the collection is the planner's; with records, a plan-statistics record beside every monitor record
   PolicyEvaluation eval_call;
   int64_t evals_done;      // evaluations launched so far
   MonitorFoldCall fold;    // first_slot moves per iteration
@@ -1812,7 +1816,21 @@ struct TrainExtras {
     return URGYM_OK;
   }
 
+  // what urgym_sac_train_planned refuses about the planning beside the two options
+  int check_planning() {
+    if (evaluation && evaluation->eval_handle == (void*)planned->planner) return fail_in(h, URGYM_ERR_ARG, who, "planner_handle is the evaluation's eval_handle");
+    if (!planned->records) return URGYM_OK;
+    if (!monitoring) return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_planning.records is given without monitoring (a plan-statistics record goes beside a monitor record)");
+    const urgym_sac_monitoring& M = *monitoring;
+    if (M.log_every < 1 || M.first_iteration < 0 || M.first_record < 0) return URGYM_OK;  // check_monitoring refuses it
+    if (monitor_record_count(M.first_iteration, M.log_every, schedule->num_iterations) > (int64_t)planned->record_capacity - M.first_record)
+      return fail_in(h, URGYM_ERR_ARG, who, "first_record + the records of the call is beyond urgym_sac_planning.record_capacity");
+    return URGYM_OK;
+  }
+
   int check() {
+    if (planned)
+      if (int rc = check_planning()) return rc;
     if (monitoring)
       if (int rc = check_monitoring()) return rc;
     return evaluation ? check_evaluation() : URGYM_OK;
@@ -1832,6 +1850,10 @@ struct TrainExtras {
         records_done++;
         monitor_stats_launch(stats, s);
         if (int rc = train_stage(h, who, i, "monitor_stats")) return rc;
+        if (planned && planned->records) {  // planner record r beside monitor record r
+          planned_stats(*planned, planned->records + M.first_record + (records_done - 1), stats.iteration, s);
+          if (int rc = train_stage(h, who, i, "mppi_stats")) return rc;
+        }
       }
     }
     if (!evaluation || !eval_follows(*schedule, evaluation->every, i)) return URGYM_OK;
@@ -1843,7 +1865,7 @@ struct TrainExtras {
   }
 };
 
-// The one driver of the eight urgym_sac_train* entry points: `who` is the entry point's own name in every refusal, `opt` what it was given.
+// The one driver of the nine urgym_sac_train* entry points: `who` is the entry point's own name in every refusal, `opt` what it was given.
 int sac_train_body(const char* who, Handle* h, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, hipStream_t s, const TrainOptions& opt) {
   if (!learner) return fail_in(h, URGYM_ERR_ARG, who, "null learner");
   if (!schedule) return fail_in(h, URGYM_ERR_ARG, who, "null schedule");
@@ -1852,7 +1874,9 @@ int sac_train_body(const char* who, Handle* h, const urgym_sac_learner* learner,
   const urgym_sac_hindsight* const her = opt.her;
   const urgym_sac_clipping* const clip = opt.clip;
   const urgym_normalization* const norm = opt.norm;
-  TrainExtras extras{who, h, learner, schedule, s, opt.evaluation, opt.monitoring, norm};
+  const urgym_sac_planning* const planning = opt.planning;
+  PlannedCall planned;
+  TrainExtras extras{who, h, learner, schedule, s, opt.evaluation, opt.monitoring, norm, planning ? &planned : nullptr};
   const urgym_sac_learner& L = *learner;
   const urgym_sac_schedule& S = *schedule;
   if (L.reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_learner.reserved0 must be 0");
@@ -1910,6 +1934,23 @@ int sac_train_body(const char* who, Handle* h, const urgym_sac_learner* learner,
     if ((!clip->critic_grad_norm || !clip->actor_grad_norm) && sac_schedule_updates(S) > 0)  // zero slots need no array
       return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_clipping.critic_grad_norm or actor_grad_norm is null");
   }
+  if (planning) {  // the planner's own refusals and the collection's, whether or not the call holds an update
+    if (int rc = planned_check(who, h, planning, &L.ring, S, &planned)) return rc;
+    if (planning->sync != 0) {  // planner_sync reloads the guide's actor and critic from the learner's tensors
+      if (planned.sync_actor) {
+        const ActorPacked buf = actor_packed(planned.sync_actor);
+        if (buf.in_features != L.actor_adam.in_features || buf.hidden != L.actor_adam.hidden_width)
+          return failf(h, URGYM_ERR_ARG, "%s: sync: learner->actor_adam is %d -> %d, the guide's actor is %d -> %d", who, L.actor_adam.in_features,
+                       L.actor_adam.hidden_width, buf.in_features, buf.hidden);
+      }
+      if (planned.sync_critic) {
+        const CriticPacked buf = critic_packed(planned.sync_critic);
+        if (buf.in_features != L.critic_adam.in_features || buf.hidden != L.critic_adam.hidden_width)
+          return failf(h, URGYM_ERR_ARG, "%s: sync: learner->critic_adam is %d -> %d, the guide's critic is %d -> %d", who, L.critic_adam.in_features,
+                       L.critic_adam.hidden_width, buf.in_features, buf.hidden);
+      }
+    }
+  }
 
   // ---- the checking halves, with the numbers of the first collection and the first update
   const int M = L.count, K = S.steps_per_iteration, G = S.updates_per_iteration;
@@ -1935,17 +1976,18 @@ int sac_train_body(const char* who, Handle* h, const urgym_sac_learner* learner,
   const int64_t updates = sac_schedule_updates(S);
   const float scale = (float)(1.0 / (double)M), neg_scale = (float)(-1.0 / (double)M);  // as SACLearner._update_on_device hands them over
   Actor* collector = nullptr;
-  if (K > 0) {
+  if (K > 0 && !planning) {
     for (int mode : {URGYM_SAMPLE_UNIFORM, URGYM_SAMPLE_GAUSSIAN}) {  // each mode the call collects with
       if (mode == URGYM_SAMPLE_UNIFORM ? S.uniform_iterations == 0 : S.uniform_iterations >= S.num_iterations) continue;
       const urgym_sampling how{mode, 0, L.seed, S.collect_first_draw};
       if (int rc = check_collect(h, L.actor, &how, K, &L.ring, S.first_slot, who, &collector)) return rc;
     }
   }
-  // the collection of iteration i: the launches of urgym_rollout_collect
+  // the collection of iteration i: the launches of urgym_rollout_collect, or with a planner those of urgym_mppi_collect(_adaptive)
   auto collect = [&](int i, const SacIteration& it) {
     const urgym_sampling how{it.collect_mode, 0, L.seed, it.collect_first_draw};
-    const int rc = rollout(h, collector, &how, K, RolloutSinks{nullptr, nullptr, &L.ring, it.collect_first_slot}, s, normalized_rows ? &norm_collect : nullptr);
+    const int rc = planning ? planned_collect(planned, it.collect_first_draw, K, it.collect_first_slot, s)
+                            : rollout(h, collector, &how, K, RolloutSinks{nullptr, nullptr, &L.ring, it.collect_first_slot}, s, normalized_rows ? &norm_collect : nullptr);
     if (!rc && folds) {  // urgym_norm_fold on the slots just written
       norm_fold.first_slot = it.collect_first_slot;
       norm_fold_launch(norm_fold, s);
@@ -2177,6 +2219,25 @@ int sac_train_body(const char* who, Handle* h, const urgym_sac_learner* learner,
       if (int rc = train_stage(h, who, i, "actor_adam_step")) return rc;
       actor_mark_log_std(actor_step.a);  // as urgym_actor_adam_step; the checks above have required the head already
     }
+    if (planning && planning->sync != 0 && G > 0) {  // planner_sync: the launches of urgym_actor_load and urgym_critic_load (tau = 1) on the planner handle
+      if (planned.sync_actor) {
+        const urgym_actor_tensors& p = L.actor_adam.param;
+        const float* src[PACK_ACTOR_TENSORS] = {p.w0, p.b0, p.w1, p.b1, p.w_mu, p.b_mu, p.w_log_std, p.b_log_std};
+        actor_pack_launch(actor_packed(planned.sync_actor), src, s);
+        if (int rc = train_stage(h, who, i, "planner_sync (actor)")) return rc;
+        if (p.w_log_std) actor_mark_log_std(planned.sync_actor);
+      }
+      if (planned.sync_critic) {
+        const float* src[2 * PACK_CRITIC_TENSORS];
+        for (int net = 0; net < 2; net++) {
+          const auto& q = L.critic_adam.param[net];
+          const float* one[PACK_CRITIC_TENSORS] = {q.w0, q.b0, q.w1, q.b1, q.w_q, q.b_q};
+          for (int k = 0; k < PACK_CRITIC_TENSORS; k++) src[PACK_CRITIC_TENSORS * net + k] = one[k];
+        }
+        critic_pack_launch(critic_packed(planned.sync_critic), src, 1.0f, s);
+        if (int rc = train_stage(h, who, i, "planner_sync (critic)")) return rc;
+      }
+    }
     if (int rc = extras.after(i)) return rc;
   }
   return URGYM_OK;
@@ -2190,7 +2251,7 @@ const char* const ONE_GATHER = "at most one of nstep, prioritized and hindsight 
 extern "C" {
 
 // Each entry point: the null handle, its own required option, then the driver with what it was given.  TrainOptions' order is
-// {nstep, per, her, clip, norm, evaluation, monitoring}.
+// {nstep, per, her, clip, norm, evaluation, monitoring, planning}.
 
 int urgym_sac_train(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, void* stream) {
   Handle* h = (Handle*)handle;
@@ -2254,6 +2315,15 @@ int urgym_sac_train_normalized(void* handle, const urgym_sac_learner* learner, c
   if (!normalization) return fail_in(h, URGYM_ERR_ARG, who, "null normalization");
   if ((nstep_or_NULL != nullptr) + (prioritized_or_NULL != nullptr) + (hindsight_or_NULL != nullptr) > 1) return fail_in(h, URGYM_ERR_ARG, who, ONE_GATHER);
   return sac_train_body(who, h, learner, schedule, (hipStream_t)stream, TrainOptions{nstep_or_NULL, prioritized_or_NULL, hindsight_or_NULL, clipping_or_NULL, normalization, evaluation_or_NULL, monitoring_or_NULL});
+}
+
+int urgym_sac_train_planned(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_planning* planning, const urgym_sac_clipping* clipping_or_NULL, const urgym_sac_nstep* nstep_or_NULL, const urgym_sac_prioritized* prioritized_or_NULL, const urgym_sac_hindsight* hindsight_or_NULL, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream) {
+  const char* who = "urgym_sac_train_planned";
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (!planning) return fail_in(h, URGYM_ERR_ARG, who, "null planning");
+  if ((nstep_or_NULL != nullptr) + (prioritized_or_NULL != nullptr) + (hindsight_or_NULL != nullptr) > 1) return fail_in(h, URGYM_ERR_ARG, who, ONE_GATHER);
+  return sac_train_body(who, h, learner, schedule, (hipStream_t)stream, TrainOptions{nstep_or_NULL, prioritized_or_NULL, hindsight_or_NULL, clipping_or_NULL, nullptr, evaluation_or_NULL, monitoring_or_NULL, planning});
 }
 
 }  // extern "C"

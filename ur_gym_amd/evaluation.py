@@ -2854,6 +2854,75 @@ def mppi_execute(action_out, eps, explore_sigma):
         return np.fmin(np.fmax(a, np.float32(-1)), np.float32(1))
 
 
+def _stats_fmin(a, b):
+    """urgym_mppi_stats.h's mppi_stats_fmin, elementwise: a NaN operand gives the other one, equal operands give `a`."""
+    return np.where(np.isnan(a), b, np.where(np.isnan(b), a, np.where(b < a, b, a)))
+
+
+def mppi_plan_stats(best_return, nominal_return, ess, elite_count=None, threshold=None, iteration=0):
+    """THE PLAN STATISTICS of include/urgym.h ("the planner inside the training call") in numpy, bitwise what urgym_mppi_stats writes:
+    `best_return`, `nominal_return`, `ess` float64 [E] as a plan leaves them; `elite_count` (int32 [E]) and `threshold` (float64 [E]) both
+    given (a planner with elites or the adaptive std) or neither.  Every sum is ``ordered_sum(..., np.float64)`` over all E parents with
+    +0.0 for a parent that does not count; every mean is one float64 division, +0.0 where nothing counted; the minimum runs the ordered
+    sum's lanes and levels with ``mppi_stats_fmin``.  Returns a dict with the fields of ``urgym_mppi_stats_record``."""
+    from ._abi import MPPI_STATS_MAX_PARENTS
+    from ._abi import SAC_TERMS_LANES as L
+
+    best, nominal, ess = (np.asarray(x) for x in (best_return, nominal_return, ess))
+    for name, x in (("best_return", best), ("nominal_return", nominal), ("ess", ess)):
+        if x.dtype != np.float64 or x.ndim != 1 or x.shape != best.shape:
+            raise ValueError(f"{name} must be a float64 [E] array, got {x.dtype} {x.shape}")
+    E = best.shape[0]
+    if not 1 <= E <= MPPI_STATS_MAX_PARENTS:
+        raise ValueError(f"E must be in [1, {MPPI_STATS_MAX_PARENTS}], got {E}")
+    if (elite_count is None) != (threshold is None):
+        raise ValueError("elite_count and threshold go together")
+    adaptive = elite_count is not None
+    if adaptive:
+        elite_count, threshold = np.asarray(elite_count), np.asarray(threshold)
+        if elite_count.dtype != np.int32 or elite_count.shape != (E,) or threshold.dtype != np.float64 or threshold.shape != (E,):
+            raise ValueError(f"elite_count must be int32 [{E}] and threshold float64 [{E}]")
+    zero = np.float64(0.0)
+
+    def mean(total, count):
+        return total / np.float64(count) if count else zero
+
+    def counted(mask, x):
+        return ordered_sum(np.where(mask, x, zero), np.float64), int(mask.sum())
+
+    with np.errstate(all="ignore"):
+        fin_b, fin_n = (best - best) == 0.0, (nominal - nominal) == 0.0  # false for a NaN and for either infinity
+        both = fin_b & fin_n
+        sum_b, planned = counted(fin_b, best)
+        sum_n, nominal_finite = counted(fin_n, nominal)
+        sum_g, gain_count = counted(both, best - nominal)
+        sum_e = ordered_sum(ess, np.float64)
+        low = np.full(L, np.nan)
+        for first in range(0, E, L):  # every lane's next parent, ascending
+            row = ess[first:first + L]
+            low[:row.size] = _stats_fmin(low[:row.size], row)
+        s = L // 2
+        while s >= 1:
+            low[:s] = _stats_fmin(low[:s], low[s:2 * s])
+            s //= 2
+        rec = dict(mean_best_return=mean(sum_b, planned), mean_nominal_return=mean(sum_n, nominal_finite), mean_gain=mean(sum_g, gain_count),
+                   mean_ess=mean(sum_e, E), min_ess=np.float64(low[0]), mean_elite_count=zero, mean_threshold=zero, iteration=int(iteration), num_parents=E,
+                   planned=planned, nominal_finite=nominal_finite, gain_count=gain_count, threshold_count=0, reserved0=0)
+        if adaptive:
+            fin_t = (threshold - threshold) == 0.0
+            sum_t, threshold_count = counted(fin_t, threshold)
+            rec.update(mean_elite_count=mean(ordered_sum(elite_count.astype(np.float64), np.float64), E), mean_threshold=mean(sum_t, threshold_count),
+                       threshold_count=threshold_count)
+    return rec
+
+
+def mppi_stats_record_bytes(rec):
+    """A dict of ``mppi_plan_stats`` as the 88 bytes of ``urgym_mppi_stats_record``."""
+    from . import _abi
+
+    return bytes(_abi.MppiStatsRecord(*[rec[name] for name, _ in _abi.MppiStatsRecord._fields_]))
+
+
 class DeviceMPPI:
     """An MPPI planner (Williams et al., 2017) for `env`, a UR5ReachVectorEnv of E envs, that plans with the step kernel itself: it owns a
     planner environment of E * `samples` envs (same env id, configuration and device, ``auto_reset=False``) and every buffer of
@@ -2876,7 +2945,12 @@ class DeviceMPPI:
     joint) from the elites, clamped to [`std_min`, `std_max`] (`std_max` defaults to `sigma`), and iterations >= 1 of the same plan sample
     with it; every plan starts at `sigma` again.  With either given the ``urgym_mppi_*_adaptive`` entry points are called, ``adapt()`` is
     the struct, and ``DIAGNOSTICS`` gains ``elite_count`` and ``threshold``; with ``elites=None`` and ``adapt_std=False`` the planner
-    makes exactly the calls it made before."""
+    makes exactly the calls it made before.
+
+    Plan statistics.  ``stats()`` reduces the diagnostics of the last plan to one ``urgym_mppi_stats_record`` on
+    the device; ``records`` is this planner's array of them (int64 [capacity, 11], grown by ``reserve_records``), which
+    ``SACLearner.train(planner=, plan_stats=True)`` fills beside the monitor's records; ``planning()`` is the ``urgym_sac_planning`` of such
+    a call."""
 
     DIAGNOSTICS = ("best_return", "nominal_return", "ess")
 
@@ -2921,6 +2995,7 @@ class DeviceMPPI:
                 setattr(A, name, C.cast(self.buf[name].data_ptr(), C.POINTER(ct)))
             self._adapt = A
             self.DIAGNOSTICS = DeviceMPPI.DIAGNOSTICS + ("elite_count", "threshold")
+        self.records = torch.zeros((64, _abi.MPPI_STATS_RECORD_WORDS), dtype=torch.int64, device=env.device)  # [capacity] urgym_mppi_stats_record
         self.actor = self.critic = self._guide = None
         P = int(policy_samples)
         if P or terminal_value or fail_cost or policy_sigma:
@@ -3101,6 +3176,88 @@ class DeviceMPPI:
             return
         _native.check(env.lib.urgym_mppi_collect(env._h, self.planner._h, C.byref(self._struct), guide,
                                                  C.byref(x), int(first_draw), int(num_steps), C.byref(replay._ring), int(first), env._stream()), env._h)
+
+    def stats(self, iteration=0, out=None):
+        """The diagnostics the last plan left, reduced over the E parents to one ``urgym_mppi_stats_record`` (urgym_mppi_stats: ONE launch
+        of one workgroup; ``mppi_plan_stats`` restates it bitwise).  `out`: an int64 [11] device tensor to write, a row of ``records`` for
+        instance; a fresh one by default.  Returns a dict of 0-dim device views of that record under the struct's field names, and the
+        row itself under ``"record"``.  NOT synchronised."""
+        import ctypes as C
+
+        import torch
+
+        from . import _abi, _native
+
+        env = self.env
+        if isinstance(iteration, bool) or int(iteration) != iteration or not -(1 << 63) <= int(iteration) < 1 << 63:
+            raise ValueError(f"stats: iteration must be an integer that fits int64, got {iteration!r}")
+        if out is None:
+            out = torch.zeros((_abi.MPPI_STATS_RECORD_WORDS,), dtype=torch.int64, device=env.device)
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or tuple(out.shape) != (_abi.MPPI_STATS_RECORD_WORDS,) or not out.is_contiguous() \
+                or out.device != torch.device(env.device):
+            raise ValueError(f"stats: out must be a contiguous int64 [{_abi.MPPI_STATS_RECORD_WORDS}] tensor on {env.device}")
+        _native.check(env.lib.urgym_mppi_stats(env._h, C.byref(self._struct), None if self._adapt is None else C.byref(self._adapt),
+                                               C.cast(out.data_ptr(), C.POINTER(_abi.MppiStatsRecord)), int(iteration), env._stream()), env._h)
+        return self._record_views(out)
+
+    @staticmethod
+    def _record_views(row):
+        """The fields of one record row (int64 [11]) as 0-dim views: the doubles and the int64 by word, the int32 by half word."""
+        import torch
+
+        from . import _abi
+
+        f64, i32 = row.view(torch.float64), row.view(torch.int32)
+        rec, offset = {"record": row}, 0
+        for name, ct in _abi.MppiStatsRecord._fields_:
+            size = 8 if ct in (_abi.C.c_double, _abi.C.c_int64) else 4
+            rec[name] = f64[offset // 8] if ct is _abi.C.c_double else row[offset // 8] if ct is _abi.C.c_int64 else i32[offset // 4]
+            offset += size
+        return rec
+
+    def reserve_records(self, count):
+        """Grows ``records`` to hold at least `count` records; what is there is kept.  Nothing happens where they already fit."""
+        import torch
+
+        if int(count) <= self.records.shape[0]:
+            return
+        grown = torch.zeros((max(int(count), 2 * self.records.shape[0]), self.records.shape[1]), dtype=torch.int64, device=self.records.device)
+        grown[:self.records.shape[0]].copy_(self.records)
+        self.records = grown
+
+    def plan_stats(self, first, count):
+        """Synchronises; records `first` .. `first` + `count` - 1 of ``records`` as dicts under the struct's field names."""
+        import ctypes as C
+
+        import torch
+
+        from . import _abi
+
+        torch.cuda.synchronize(self.env.device)
+        raw = self.records[int(first):int(first) + int(count)].cpu().numpy().tobytes()
+        recs = [_abi.MppiStatsRecord.from_buffer_copy(raw, i * C.sizeof(_abi.MppiStatsRecord)) for i in range(int(count))]
+        return [{name: getattr(r, name) for name, _ in _abi.MppiStatsRecord._fields_} for r in recs]
+
+    def planning(self, explore_sigma=0.0, sync=True, records=False):
+        """The ``urgym_sac_planning`` of an ``env.sac_train(planner=)`` call: this planner's handle and structs, the exploration noise,
+        whether the actor and the critic follow the learner, and, with `records`, ``records`` as it stands (``reserve_records`` first)."""
+        import ctypes as C
+
+        from . import _abi
+
+        P = _abi.SacPlanning()
+        P.planner_handle = self.planner._h
+        P.mppi = C.pointer(self._struct)
+        if self._adapt is not None:
+            P.adapt_or_NULL = C.pointer(self._adapt)
+        if self._guide is not None:
+            P.guide_or_NULL = C.pointer(self._guide)
+        P.explore = _abi.MppiExplore(self.check_explore(explore_sigma), 0, None)
+        P.sync = int(bool(sync))
+        if records:
+            P.record_capacity = int(self.records.shape[0])
+            P.records = C.cast(self.records.data_ptr(), C.POINTER(_abi.MppiStatsRecord))
+        return P
 
     def reset_plan(self, mask=None):
         """Zeroes the nominal sequence of every env, or of those `mask` (a bool [E] tensor or array, or env ids) selects."""

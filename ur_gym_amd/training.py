@@ -59,8 +59,10 @@ minibatch gather on the HIP kernels, and gradients and optimisers in torch autog
     With ``collect(planner=)`` (an ``evaluation.DeviceMPPI`` on the learner's env) the collecting policy is the MPPI
     planner instead of the sampled actor: every step is planned (urgym_mppi_collect), the executed action is the plan's first action plus
     ``explore_sigma`` times exploration noise, and the transitions land in the same ring slots, so ``update`` trains on them as they stand
-    (SAC is off-policy); ``sync_planner`` puts the planner's actor and critic on the learner's current parameters.  Not with ``normalize``;
-    ``train`` has no planner option yet.
+    (SAC is off-policy); ``sync_planner`` puts the planner's actor and critic on the learner's current parameters.  Not with ``normalize``.
+    ``train(planner=)`` runs that loop -- the planned collection, the updates, ``sync_planner`` -- inside the one native call
+    (urgym_sac_train_planned), and with ``plan_stats=True`` keeps a record of how the plans went beside every
+    record of the monitor.
     None of them synchronises with the host.  ``train`` runs the whole loop in one native call and, given an
     ``evaluation.DeviceEvaluation``, the reference's EvalCallback inside it: evaluations of the deterministic policy at a fixed interval of
     updates, their statistics as records on the device, and the best actor's tensors, which ``DeviceEvaluation.save_best`` writes as an
@@ -582,7 +584,7 @@ class SACLearner:
         return self._train
 
     def train(self, replay, iterations, steps_per_iteration=1, updates_per_iteration=1, *, seed, first_draw, evaluation=None, eval_every=None,
-              monitor=None, log_every=None):
+              monitor=None, log_every=None, planner=None, explore_sigma=0.0, sync_planner=True, plan_stats=False):
         """`iterations` x (``collect(replay, steps_per_iteration)``, `updates_per_iteration` x ``update(replay, seed, draw)`` with draw =
         `first_draw`, `first_draw` + 1, ...) in ONE native call (``env.sac_train``, urgym_sac_train), bit for bit: the loop of
         tools/train_sac.py without Python between the launches.  Needs ``device_entropy``.  The warm-up is the loop's: an iteration
@@ -609,7 +611,17 @@ class SACLearner:
         update is the thirteen launches with the gather of ``DeviceReplay.sample_hindsight``.  With ``max_grad_norm``: two more
         launches per update, and the result also holds ``critic_grad_norm`` and ``actor_grad_norm``, one entry per update like the
         losses.  With ``normalize``: the normalized collection, one fold of the statistics per iteration and one ``norm_batch`` per
-        update; not together with `evaluation` unless ``norm_obs`` is off."""
+        update; not together with `evaluation` unless ``norm_obs`` is off.
+
+        With `planner` (an ``evaluation.DeviceMPPI`` on this learner's env) every iteration is
+        ``collect(replay, steps_per_iteration, monitor=, planner=, explore_sigma=)``, then -- unless the warm-up still holds after it --
+        the updates and, with `sync_planner`, ``sync_planner(planner)``, bit for bit and still ONE native call
+        (urgym_sac_train_planned).  Every step is planned: ``learning_starts`` only decides which iterations run no update.  With
+        ``plan_stats=True`` (it needs `monitor`) every record of the monitor has a ``planner.stats`` record of the iteration's last plan
+        beside it, in ``planner.records`` at the monitor's index, and the result holds the records of this call (rows of
+        ``planner.records``, not synchronised) under ``"plan_stats"``.  Raises ValueError, before anything runs, for ``normalize=True``,
+        for a planner on another env, for `explore_sigma` without `planner` and for `plan_stats` without `monitor` (or without
+        `planner`).  Without `planner` the call is exactly the one above."""
         from .evaluation import warmup_iterations
 
         if (evaluation is None) != (eval_every is None):
@@ -620,10 +632,28 @@ class SACLearner:
             raise ValueError("train needs device_entropy=True (the native loop is the thirteen launches of the update on the device)")
         if self.hp.get("prioritized") and not hasattr(replay, "priorities_struct"):
             raise ValueError("prioritized=True needs a DevicePrioritizedReplay")
+        planning = {}
+        if planner is None:
+            if explore_sigma:
+                raise ValueError("train: explore_sigma is the planner's exploration noise and needs planner=")
+            if plan_stats:
+                raise ValueError("train: plan_stats needs planner= (the statistics are the planner's)")
+        else:
+            if self.normalizer is not None:
+                raise ValueError("train: planner= together with normalize=True is out of scope (the planner's actor and critic read raw rows, not normalized ones)")
+            if getattr(planner, "env", None) is not self.env:
+                raise ValueError("train: the planner's source env is not this learner's env (DeviceMPPI(learner.env, ...))")
+            if plan_stats and monitor is None:
+                raise ValueError("train: plan_stats=True needs monitor= and log_every= (a plan-statistics record goes beside a monitor record)")
+            planner.check_explore(explore_sigma)
+            planning = dict(planner=dict(planner=planner, explore_sigma=explore_sigma, sync=bool(sync_planner), records=bool(plan_stats)))
         hp, env, st = self.hp, self.env, self.adam_state
         n, K, G = int(iterations), int(steps_per_iteration), int(updates_per_iteration)
         tr = self._train_binding(replay)
         uniform, idle = warmup_iterations(self.env_steps, env.num_envs, hp["learning_starts"], n, K)
+        if planner is not None:
+            uniform = 0  # every step is planned; the warm-up only keeps the idle iterations without updates
+        first_record = None if monitor is None else monitor.count
         updates = max(0, n - idle) * max(0, G)
         losses = torch.empty((3, updates), dtype=torch.float32, device=env.device)
         cs, clipping = self.clip_state, {}
@@ -639,7 +669,7 @@ class SACLearner:
                       **({} if tr["nstep"] is None else dict(nstep=tr["nstep"])),
                       **({} if tr["prioritized"] is None else dict(prioritized=tr["prioritized"])),
                       **({} if tr["hindsight"] is None else dict(hindsight=tr["hindsight"])), **clipping,
-                      **({} if self.normalizer is None else dict(normalizer=self.normalizer)))
+                      **({} if self.normalizer is None else dict(normalizer=self.normalizer)), **planning)
         self.env_steps += n * K
         self.draw += n * K
         st["step"] += updates
@@ -655,9 +685,10 @@ class SACLearner:
             if cs is not None:  # the last update's norms, as views of the call's slots; the coefficients are the scratch's
                 self.last_update.update(critic_grad_norm=norms[0, updates - 1:], actor_grad_norm=norms[1, updates - 1:], critic_scale=cs["critic_scale"],
                                         actor_scale=cs["actor_scale"])
+        extra = {"plan_stats": planner.records[first_record:monitor.count]} if plan_stats else {}
         if cs is not None:
-            return {"critic_loss": losses[0], "actor_loss": losses[1], "ent_coef_loss": losses[2], "critic_grad_norm": norms[0], "actor_grad_norm": norms[1]}
-        return {"critic_loss": losses[0], "actor_loss": losses[1], "ent_coef_loss": losses[2]}
+            return {"critic_loss": losses[0], "actor_loss": losses[1], "ent_coef_loss": losses[2], "critic_grad_norm": norms[0], "actor_grad_norm": norms[1], **extra}
+        return {"critic_loss": losses[0], "actor_loss": losses[1], "ent_coef_loss": losses[2], **extra}
 
     # ------------------------------------------------------------------------------------------------ checkpoints
     OVERRIDABLE = ("learning_rate", "learning_starts")  # what a resumed run may set anew; everything else must be the checkpoint's

@@ -52,6 +52,7 @@ _TORCH_DTYPE = {C.c_double: torch.float64, C.c_float: torch.float32, C.c_int32: 
 # The training call's entry points (include/urgym.h), in the order ``sac_train`` tries them: (symbol, the option that selects it, the
 # options it takes between ``learner, schedule`` and ``stream``, in the order of its signature).  The last row takes none.
 _SAC_TRAIN_ENTRIES = (
+    ("urgym_sac_train_planned", "planner", ("planner", "clipping", "nstep", "prioritized", "hindsight", "evaluation", "monitor")),
     ("urgym_sac_train_normalized", "normalizer", ("normalizer", "clipping", "nstep", "prioritized", "hindsight", "evaluation", "monitor")),
     ("urgym_sac_train_clipped", "clipping", ("clipping", "nstep", "prioritized", "hindsight", "evaluation", "monitor")),
     ("urgym_sac_train_hindsight", "hindsight", ("hindsight", "evaluation", "monitor")),
@@ -65,7 +66,7 @@ _SAC_TRAIN_ENTRIES = (
 
 def _sac_train_entry(present):
     """(symbol, option names) of the entry point that serves a call with the options in `present` (any container of names out of
-    evaluation, monitor, nstep, prioritized, hindsight, clipping, normalizer): the first row of ``_SAC_TRAIN_ENTRIES`` whose option is given."""
+    evaluation, monitor, nstep, prioritized, hindsight, clipping, normalizer, planner): the first row of ``_SAC_TRAIN_ENTRIES`` whose option is given."""
     for symbol, selects, options in _SAC_TRAIN_ENTRIES:
         if selects is None or selects in present:
             return symbol, options
@@ -885,7 +886,7 @@ class UR5ReachVectorEnv:
     def sac_train(self, learner, critic_loss, actor_loss, ent_coef_loss, *, first_slot, filled_steps, num_iterations, steps_per_iteration=1,
                   updates_per_iteration=1, uniform_iterations=0, idle_iterations=0, collect_first_draw=0, update_first_draw=0, first_step=1,
                   evaluation=None, eval_every=None, monitor=None, log_every=None, nstep=None, prioritized=None, hindsight=None, clipping=None,
-                  normalizer=None):
+                  normalizer=None, planner=None):
         """``num_iterations`` x (a collection of ``steps_per_iteration`` steps, ``updates_per_iteration`` SAC updates) in ONE native
         call (urgym_sac_train): the launches of ``collect`` and of the thirteen calls of an update, bit for bit, without returning to
         Python in between.  `learner`: what ``sac_learner`` returned, or a dict of its keyword arguments (then built and checked here).
@@ -924,8 +925,15 @@ class UR5ReachVectorEnv:
         With `normalizer` (an ``evaluation.DeviceNormalizer`` of this environment): every collection is ``collect(..., normalizer=)``
         followed by ``norm_fold`` of its slots, and every update's gather is followed by ``norm_batch``.  An `evaluation` given with it
         must have been made with this normalizer (``DeviceEvaluation(..., normalizer=)``): its evaluations are
-        ``evaluation.evaluate``'s, on normalized rows, with the statistics snapshot beside the best actor."""
-        from .evaluation import DeviceEvaluation, DeviceMonitor, _her_arguments, evaluation_points, monitor_points, relabel_threshold, training_schedule
+        ``evaluation.evaluate``'s, on normalized rows, with the statistics snapshot beside the best actor.
+
+        With `planner` (a dict: ``planner``, an ``evaluation.DeviceMPPI`` whose source is this environment, and optionally
+        ``explore_sigma`` (0), ``sync`` (True) and ``records`` (False)): every collection is the planner's
+        (``DeviceMPPI.collect(..., first_draw=collect_first_draw + i K, explore_sigma=)``, urgym_sac_train_planned); with ``sync`` the
+        planner's actor and critic are reloaded from the learner's parameters after the updates of every iteration that has any; with
+        ``records`` (it needs `monitor`) one ``DeviceMPPI.stats`` record is written beside every monitor record, into
+        ``planner.records`` at the monitor's own index.  ``uniform_iterations`` must be 0; not together with `normalizer`."""
+        from .evaluation import DeviceEvaluation, DeviceMonitor, DeviceMPPI, _her_arguments, evaluation_points, monitor_points, relabel_threshold, training_schedule
 
         who = "sac_train"
         if isinstance(learner, dict):
@@ -1011,6 +1019,20 @@ class UR5ReachVectorEnv:
                 given["normalizer"] = evaluation.norm_struct()
             if sched["steps_per_iteration"] > normalizer.fold_steps:
                 raise ValueError(f"{who}: steps_per_iteration must be at most the normalizer's fold_steps = {normalizer.fold_steps} (its workspace)")
+        if planner is not None:
+            mppi = planner.get("planner") if isinstance(planner, dict) else None
+            if not isinstance(mppi, DeviceMPPI) or mppi.env is not self:
+                raise ValueError(f"{who}: planner must be a dict whose 'planner' is a DeviceMPPI of this environment (DeviceMPPI(env, ...))")
+            unknown = [k for k in planner if k not in ("planner", "explore_sigma", "sync", "records")]
+            if unknown:
+                raise ValueError(f"{who}: unknown planner options {unknown}; available: planner, explore_sigma, sync, records")
+            if normalizer is not None:
+                raise ValueError(f"{who}: planner together with normalizer is out of scope (the planner's actor and critic read raw rows)")
+            if planner.get("records", False) and monitor is None:
+                raise ValueError(f"{who}: the planner's records need monitor (a plan-statistics record goes beside a monitor record)")
+            if planner.get("records", False):
+                mppi.reserve_records(monitor.count + len(logged))
+            given["planner"] = mppi.planning(planner.get("explore_sigma", 0.0), planner.get("sync", True), planner.get("records", False))
         symbol, options = _sac_train_entry(given)
         try:
             _native.check(getattr(self.lib, symbol)(self._h, C.byref(L), C.byref(S), *[C.byref(given[o]) if o in given else None for o in options], self._stream()), self._h)
