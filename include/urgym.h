@@ -2173,6 +2173,73 @@ int urgym_mppi_stats(void* handle, const urgym_mppi* m, const urgym_mppi_adapt* 
  * + the record points of the call entries; records not 8-byte aligned. */
 int urgym_sac_train_planned(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_planning* planning, const urgym_sac_clipping* clipping_or_NULL, const urgym_sac_nstep* nstep_or_NULL, const urgym_sac_prioritized* prioritized_or_NULL, const urgym_sac_hindsight* hindsight_or_NULL, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream);
 
+/* ---- the temperature from a target effective sample size.  urgym_mppi.lam is one scalar for a whole run and
+ * every env, while the scale of the returns moves by orders of magnitude with the critic's terminal value, with the distance to the
+ * goal and with fail_cost: a fixed lambda leaves the weights of many parents on a single sample.  The tempered update solves the
+ * temperature per parent, at every update, so that the weights have a chosen effective sample size (the temperature of REPS; TD-MPC
+ * and MPPI-Generic normalise their scores to the same end).  Added WITHIN ABI version 4: no struct above changed, URGYM_ABI_VERSION did
+ * not move, no kernel of the calls above changed, the five symbols below are found by lookup.  A planner that does not use them makes
+ * the calls it made and leaves the bits it left.
+ *
+ * THE EXPONENTIAL.  The weights of THE UPDATE and THE ELITE UPDATE come from the device library's exp, which no host restates bitwise;
+ * that is why w is an output a host restatement is given.  A search that compares an effective sample size with a target cannot be
+ * handed its exponentials, so the tempered update has its own, texp, float64, for x <= 0, one rounding per operation:
+ *     x < -708.0 gives +0.0; otherwise
+ *     y = x * LOG2E (1.4426950408889634);  kf = rint(y), to nearest, ties to even;
+ *     hi = kf * LN2_HI;  r1 = x - hi;  lo = kf * LN2_LO;  r = r1 - lo     (fdlibm's split: LN2_HI = 6.93147180369123816490e-01,
+ *                                                                            LN2_LO = 1.90821492927058770002e-10; hi is exact)
+ *     p = c13;  then for n = 12 .. 0:  t = p * r;  p = t + cn             (Horner; cn = 1 / n!, the correctly rounded float64)
+ *     scale = the double whose bits are (1023 + (int64) kf) << 52;  texp = p * scale.
+ * texp(0) = texp(-0.0) = 1 exactly; kf >= -1021 on the accepted range, so scale and the result are normal.  Within 2 ulp of exp.
+ *
+ * THE ESS AT A TEMPERATURE.  For parent p, rmax is THE UPDATE's.  sample j is COUNTED where its return is finite, and, with adapt, where
+ * it is an elite of THE RANK.  At a temperature lam:  d = r_j - rmax;  x = d / lam;  w_j = texp(x) where j is counted, else +0.0;
+ * Z = THE ORDERED SUM of w_j;  Q = THE ORDERED SUM of w_j * w_j;  ess(lam) = (Z * Z) / Q.  The best counted sample weighs 1, so Z >= 1
+ * and Q >= 1.
+ *
+ * THE SEARCH, per parent, with T = ess_target and S = steps:
+ *   1. no return is finite: lam = m->lam and w_0 = 1, every other 0, as THE UPDATE puts it; saturated = URGYM_MPPI_TEMPER_NO_RETURN;
+ *   2. else if ess(lam_max) < T: lam = lam_max, the target cannot be met; saturated = URGYM_MPPI_TEMPER_AT_MAX;
+ *   3. else if ess(lam_min) >= T: lam = lam_min; saturated = URGYM_MPPI_TEMPER_AT_MIN;
+ *   4. else lo = lam_min, hi = lam_max, and S times:  q = lo * hi;  mid = sqrt(q), correctly rounded;  e = ess(mid);  e >= T ? hi = mid
+ *      : lo = mid.  Then lam = hi; saturated = URGYM_MPPI_TEMPER_SOLVED.  S is fixed and there is no early exit.
+ * The weights are w_j at lam.  Everything after them is THE UPDATE's lines, or with adapt THE ELITE UPDATE's, unchanged, on those
+ * weights: Z, Q, ess, new_mean, action_out, best_return, nominal_return, w, the shift, and with adapt rank, elite, elite_count,
+ * threshold and new_std.  ess[p] is the value the search last accepted.  Without adapt none of urgym_mppi_adapt's arrays is touched. */
+#define URGYM_MPPI_TEMPER_SOLVED 0
+#define URGYM_MPPI_TEMPER_AT_MAX 1
+#define URGYM_MPPI_TEMPER_AT_MIN 2
+#define URGYM_MPPI_TEMPER_NO_RETURN 3
+#define URGYM_MPPI_TEMPER_STEPS_MAX 64
+
+typedef struct urgym_mppi_temper {
+  double ess_target;     /* T, finite, in [1, M] (M = adapt->elites; samples without adapt) */
+  double lam_min, lam_max; /* finite, 1e-100 <= lam_min <= lam_max <= 1e100 */
+  int32_t steps;         /* S in [1, URGYM_MPPI_TEMPER_STEPS_MAX] */
+  int32_t reserved0;     /* must be 0 */
+  double* lam_out;       /* [E] the temperature of the last update */
+  uint8_t* saturated;    /* [E] URGYM_MPPI_TEMPER_*, may be NULL */
+} urgym_mppi_temper;
+
+/* The single launch: ONE workgroup of 1024 lanes per parent; it needs no bound environment.  Refused, launching and writing nothing (the
+ * message names the entry point and the argument): everything urgym_mppi_update refuses, and with adapt_or_NULL everything
+ * urgym_mppi_update_elite refuses; a NULL temper or lam_out; an ess_target that is not finite or outside [1, M]; bounds that are not
+ * finite, outside [1e-100, 1e100] or out of order; steps outside [1, 64]; a non-zero reserved0. */
+int urgym_mppi_update_tempered(void* handle, const urgym_mppi* m, const urgym_mppi_temper* temper, const urgym_mppi_adapt* adapt_or_NULL, void* stream);
+
+/* urgym_mppi_plan_adaptive, urgym_mppi_control_adaptive and urgym_mppi_collect_adaptive with the tempered update in place of the update
+ * (adapt_or_NULL == NULL: urgym_mppi_plan(_guided), _control(_guided) and urgym_mppi_collect with it): bit for bit the sequence of single
+ * launches.  lam_out and saturated hold what the last update of the call left.  Refused: what the untempered call refuses, and what
+ * urgym_mppi_update_tempered refuses about temper. */
+int urgym_mppi_plan_tempered(void* source_handle, void* planner_handle, const urgym_mppi* m, const urgym_mppi_temper* temper, const urgym_mppi_adapt* adapt_or_NULL, const urgym_mppi_guide* guide_or_NULL, uint64_t draw, void* stream);
+int urgym_mppi_control_tempered(void* source_handle, void* planner_handle, const urgym_mppi* m, const urgym_mppi_temper* temper, const urgym_mppi_adapt* adapt_or_NULL, const urgym_mppi_guide* guide_or_NULL, uint64_t first_draw, int num_steps, const urgym_trajectory* traj_or_NULL, void* stream);
+int urgym_mppi_collect_tempered(void* source_handle, void* planner_handle, const urgym_mppi* m, const urgym_mppi_temper* temper, const urgym_mppi_adapt* adapt_or_NULL, const urgym_mppi_guide* guide_or_NULL, const urgym_mppi_explore* x, uint64_t first_draw, int num_steps, const urgym_replay_ring* ring, int first_slot, void* stream);
+
+/* THE PLANNED TRAINING CALL with step 1 the launches of urgym_mppi_collect_tempered; everything else as urgym_sac_train_planned states
+ * it, urgym_sac_planning and urgym_mppi_stats_record unchanged.  Refused: what urgym_sac_train_planned refuses (the message names
+ * urgym_sac_train_tempered), and what urgym_mppi_update_tempered refuses about temper. */
+int urgym_sac_train_tempered(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_planning* planning, const urgym_mppi_temper* temper, const urgym_sac_clipping* clipping_or_NULL, const urgym_sac_nstep* nstep_or_NULL, const urgym_sac_prioritized* prioritized_or_NULL, const urgym_sac_hindsight* hindsight_or_NULL, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream);
+
 /* Replaces Reach*.set_goal / set_goal_and_obstacle (reach.py:202-204, 328-335, 702-713): the caller has
  * overwritten goal / obst_start / obst_end (and possibly q) for the masked envs; this recomputes obstacle pose,
  * velocity, collision, link_dist and the observation for them, leaving step_count untouched. */

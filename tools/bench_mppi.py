@@ -22,6 +22,12 @@ is given) with the same protocol figures and the time of an adaptive plan beside
 
     python tools/bench_mppi.py --env dyn --grid 256:6:0.6:5 --iterations 1 2 4 --elites 256 64 16 --adapt-std --out profiles/mppi/dyn_elites_grid.json
 
+With the temperature solved from a target effective sample size (--ess-target T [T ...], --lam-min, --lam-max):
+every grid row is run again once per T and reported under "tempered" -- the same protocol figures, the time of a tempered plan, and the
+mean temperature and the envs at a bound of the last timed plan -- beside the plain figures of the same row, whose lambda is fixed.
+
+    python tools/bench_mppi.py --env dyn --grid 256:6:0.6:5 --ess-target 8 32 128 --out profiles/mppi/dyn_temper.json
+
     python tools/bench_mppi.py --env ori --grid 256:6:0.3:5 256:12:0.3:5 256:24:0.3:5 --terminal-value --policy-samples 64 \
         --actor tests/golden/actors/actor_ori.npz --critics tests/golden/critics/critic_ori_qf0.npz tests/golden/critics/critic_ori_qf1.npz
 """
@@ -85,7 +91,7 @@ def test_points(kind, count, device):
     return np.array(rows)
 
 
-def control_step_time(env, options, repeats):
+def control_step_time(env, options, repeats, left=None):
     """(ms of one urgym_mppi_plan, ms of the 3 + H launches of the planner's own kernels in it), device events, `repeats` of each after
     a warm-up of three plans.  The second figure times the single calls -- fan-out, sample, H scores, update -- without the steps between
     them; their work does not depend on what the steps computed."""
@@ -102,6 +108,10 @@ def control_step_time(env, options, repeats):
     for draw in range(repeats):
         mppi.plan(3 + draw)
     mid.record()
+    if left is not None and mppi.temper() is not None:  # what the last timed plan's search left
+        lam, how = mppi.buf["lam_out"].cpu().numpy(), mppi.buf["saturated"].cpu().numpy()
+        left.update(mean_lam=float(lam.mean()), min_lam=float(lam.min()), max_lam=float(lam.max()), at_lam_max=int((how == 1).sum()), at_lam_min=int((how == 2).sum()),
+                    mean_ess=float(mppi.buf["ess"].cpu().numpy().mean()))
     for draw, i in ((d, i) for d in range(repeats) for i in range(M.iterations)):
         rc = lib.urgym_mppi_fanout(src, planner, C.byref(M), s) or lib.urgym_mppi_sample(src, C.byref(M), 3 + draw, i, s)
         for h in range(M.horizon):
@@ -212,6 +222,10 @@ def main():
     ap.add_argument("--adapt-std", action="store_true", help="... and once more per M with the std adapted across the iterations of a plan")
     ap.add_argument("--std-min", type=float, default=0.05, help="--adapt-std: the floor of the adaptive std")
     ap.add_argument("--std-max", type=float, default=None, help="--adapt-std: its ceiling (default: the row's sigma)")
+    ap.add_argument("--ess-target", type=float, nargs="+", default=None, metavar="T",
+                    help="run every row again with the temperature solved per env and update for an effective sample size of T, once per value")
+    ap.add_argument("--lam-min", type=float, default=1e-3, help="--ess-target: the lowest temperature of the search")
+    ap.add_argument("--lam-max", type=float, default=1e6, help="--ess-target: the highest temperature of the search")
     args = ap.parse_args()
     import torch
 
@@ -257,6 +271,17 @@ def main():
             env.close()
             row.setdefault("adaptive", []).append(dict(elites=M, adapt_std=adapt_std, std_min=args.std_min, std_max=sigma if args.std_max is None else args.std_max,
                                                        **figures(success, reward, last, args.steps), plan_ms=adaptive_ms, plan_ms_over_plain=adaptive_ms / plan_ms,
+                                                       closed_loop_wall_seconds_including_setup=wall))
+        for target in args.ess_target or ():
+            tempered = dict(options, ess_target=target, lam_min=args.lam_min, lam_max=args.lam_max)
+            success, reward, last, wall = protocol(env_id, points, E, args.steps, args.device, tempered)
+            env = make_vec(env_id, num_envs=E, device=args.device, seed=4, auto_reset=False)
+            env.reset(seed=4)
+            left = {}
+            tempered_ms, _ = control_step_time(env, tempered, args.repeats, left)  # the second figure times the plain launches: not reported here
+            env.close()
+            row.setdefault("tempered", []).append(dict(ess_target=target, lam_min=args.lam_min, lam_max=args.lam_max, **figures(success, reward, last, args.steps),
+                                                       plan_ms=tempered_ms, plan_ms_over_plain=tempered_ms / plan_ms, last_plan=left,
                                                        closed_loop_wall_seconds_including_setup=wall))
         rows.append(row)
         print(json.dumps(row), flush=True)

@@ -38,6 +38,10 @@ urgym_sac_train_planned), and with --monitor every line of
 statistics over the envs' last plans (evaluation.mppi_plan_stats: the mean best and nominal return, their mean difference, the mean and
 the lowest effective sample size, how many envs had a finite plan, and with elites their mean count and threshold).  Not with
 --normalize (the planner's actor and critic read raw rows).  Otherwise it prints what it prints without.
+--planner-ess-target T solves the planner's temperature per env at every update so that the weights have an effective sample size of T
+(DeviceMPPI(ess_target=), urgym_mppi_*_tempered and with --native urgym_sac_train_tempered); --planner-lam is then
+used only by an env without a finite return.  With --monitor the last line of plan statistics of a native call also carries the mean of
+the temperatures its last plan left and how many envs ended at a bound, read on the host after the call's synchronise.
 """
 import argparse
 import json
@@ -137,6 +141,9 @@ def main():
                     help="--planner: iterations after the first sample with a std per (step, joint) formed from the elites of the one before (needs --planner-iterations > 1 to act)")
     ap.add_argument("--planner-std-min", "--std-min", type=float, default=0.05, help="--planner-adapt-std: the floor of the adaptive std")
     ap.add_argument("--planner-std-max", "--std-max", type=float, default=None, help="--planner-adapt-std: its ceiling (default: --planner-sigma)")
+    ap.add_argument("--planner-ess-target", type=float, default=None, metavar="T",
+                    help="--planner: solve the temperature per env and update for an effective sample size of T, in [1, M] (M = --planner-elites, else "
+                         "--planner-samples; DESIGN.md section 31; default: the fixed --planner-lam)")
     args = ap.parse_args()
     if args.planner and args.normalize:
         raise SystemExit("--planner plans on raw rows: not with --normalize (the planner's actor and critic read raw rows)")
@@ -179,7 +186,8 @@ def main():
                              critic=host_arrays(learner.critic.tensors()) if args.planner_terminal_value else None,
                              policy_samples=args.planner_policy_samples, policy_sigma=args.planner_policy_sigma if args.planner_policy_samples else 0.0,
                              terminal_value=args.planner_terminal_value, fail_cost=args.planner_fail_cost, iterations=args.planner_iterations,
-                             elites=args.planner_elites, adapt_std=args.planner_adapt_std, std_min=args.planner_std_min, std_max=args.planner_std_max)
+                             elites=args.planner_elites, adapt_std=args.planner_adapt_std, std_min=args.planner_std_min, std_max=args.planner_std_max,
+                             ess_target=args.planner_ess_target)
     updates, t0 = 0, time.perf_counter()
     best = dict(mean=-float("inf"), tensors=None)  # the Python route's own best_model
     if args.monitor and args.log_every < 1:
@@ -239,12 +247,17 @@ def main():
                               "train_success_rate_percent": 100.0 * rec["success_rate"]}), flush=True)
 
     def print_plan_stats(seconds):
-        for rec in planner.plan_stats(shown_curve, mon.count - shown_curve):  # beside the monitor's records, at their indices
+        recs = planner.plan_stats(shown_curve, mon.count - shown_curve)  # beside the monitor's records, at their indices; synchronises
+        for i, rec in enumerate(recs):
+            last = {}
+            if planner.temper() is not None and i == len(recs) - 1 and rec["iteration"] == step:  # the buffers hold the last plan of the call
+                lam, how = planner.buf["lam_out"].cpu().numpy(), planner.buf["saturated"].cpu().numpy()
+                last = dict(plan_mean_lam=float(lam.mean()), plan_at_lam_max=int((how == 1).sum()), plan_at_lam_min=int((how == 2).sum()))
             print(json.dumps({"trips": rec["iteration"], "seconds": seconds, "plan_envs": rec["num_parents"], "plan_planned": rec["planned"],
                               "plan_mean_best_return": rec["mean_best_return"], "plan_mean_nominal_return": rec["mean_nominal_return"],
                               "plan_mean_gain": rec["mean_gain"], "plan_mean_ess": rec["mean_ess"], "plan_min_ess": rec["min_ess"],
                               **(dict(plan_mean_elite_count=rec["mean_elite_count"], plan_mean_threshold=rec["mean_threshold"])
-                                 if planner.adapt() is not None else {})}), flush=True)
+                                 if planner.adapt() is not None else {}), **last}), flush=True)
 
     if args.native:
         # one call for the whole run -- or, with --save-every, one per stretch between two checkpoints: split calls are bit for bit the

@@ -632,6 +632,24 @@ class SacPlanning(C.Structure):
                 ("reserved0", C.c_int64)]
 
 
+MPPI_TEMPER_SOLVED, MPPI_TEMPER_AT_MAX, MPPI_TEMPER_AT_MIN, MPPI_TEMPER_NO_RETURN = 0, 1, 2, 3  # URGYM_MPPI_TEMPER_*: what `saturated` holds
+MPPI_TEMPER_STEPS_MAX = 64  # URGYM_MPPI_TEMPER_STEPS_MAX
+MPPI_TEMPER_LAM_RANGE = (1e-100, 1e100)  # the bounds lam_min and lam_max must lie in
+
+# urgym_mppi_temper's device pointers: name -> (ctype of element, shape given (E, K, H)); saturated may be NULL
+MPPI_TEMPER_FIELDS = [
+    ("lam_out", C.c_double, lambda E, K, H: (E,)),
+    ("saturated", C.c_uint8, lambda E, K, H: (E,)),
+]
+
+
+class MppiTemper(C.Structure):
+    """urgym_mppi_temper: the target effective sample size of the tempered update, the bracket and the steps of its search, and the
+    caller-owned device arrays it writes."""
+    _fields_ = [("ess_target", C.c_double), ("lam_min", C.c_double), ("lam_max", C.c_double), ("steps", C.c_int32), ("reserved0", C.c_int32)] + [
+        (name, C.POINTER(ct)) for name, ct, _ in MPPI_TEMPER_FIELDS]
+
+
 # Every symbol include/urgym.h declares (tests check that the built library exports each of them).
 EXPORTED_SYMBOLS = [
     "urgym_abi_version",
@@ -724,6 +742,11 @@ EXPORTED_SYMBOLS = [
     "urgym_mppi_collect_adaptive",
     "urgym_mppi_stats",
     "urgym_sac_train_planned",
+    "urgym_mppi_update_tempered",
+    "urgym_mppi_plan_tempered",
+    "urgym_mppi_control_tempered",
+    "urgym_mppi_collect_tempered",
+    "urgym_sac_train_tempered",
     "urgym_refresh",
     "urgym_invalidate_records",
     "urgym_derive_obstacle_motion",

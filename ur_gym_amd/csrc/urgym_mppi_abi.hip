@@ -1,8 +1,8 @@
 // urgym_mppi_abi.hip -- the planner's entry points of include/urgym.h ("sampling-based MPC on the device", "MPPI with the learner in the
-// loop", "planner-collected experience", "elite samples and an adaptive std", "the planner inside the training call"; DESIGN.md
-// sections 26 to 30).  Host code only, beside
+// loop", "planner-collected experience", "elite samples and an adaptive std", "the planner inside the training call", "the temperature from a
+// target effective sample size"; DESIGN.md sections 26 to 31).  Host code only, beside
 // urgym_policy_abi.hip: every check is made here, before the first launch; every launch goes through urgym_mppi.h, urgym_mppi_guide.h,
-// urgym_mppi_collect.h, urgym_mppi_elite.h, the actor's and the critic's own launches (urgym_actor.h, urgym_critic.h), the ring's store
+// urgym_mppi_collect.h, urgym_mppi_elite.h, urgym_mppi_temper.h, the actor's and the critic's own launches (urgym_actor.h, urgym_critic.h), the ring's store
 // pass (urgym_replay.h) or through do_step of urgym_hip.hip (urgym_handle.h); the one exception is the device-to-device copy of new_std
 // into std between two iterations of an adaptive plan.  As there, each entry point is a checking half, which launches nothing, and a
 // launching half, which refuses nothing.
@@ -22,6 +22,7 @@
 #include "urgym_mppi_elite.h"
 #include "urgym_mppi_guide.h"
 #include "urgym_mppi_stats.h"
+#include "urgym_mppi_temper.h"
 #include "urgym_mppi_train.h"
 #include "urgym_replay.h"
 
@@ -244,9 +245,30 @@ int check_adapt(Handle* report, const urgym_mppi* m, const urgym_mppi_adapt* a, 
   return URGYM_OK;
 }
 
+// ---- the temperature from a target effective sample size (urgym_mppi_temper), resolved by check_temper
+
+// the checks that concern urgym_mppi_temper; m and, where given, the adapt struct have been checked.  `report` keeps the message.
+int check_temper(Handle* report, const urgym_mppi* m, const urgym_mppi_temper* t, const urgym_mppi_adapt* a, const char* who, MppiTemper* out) {
+  static_assert(sizeof(urgym_mppi_temper) == 48 && alignof(urgym_mppi_temper) == 8, "include/urgym.h");
+  if (!t) return fail_in(report, URGYM_ERR_ARG, who, "null urgym_mppi_temper");
+  const double most = (double)(a ? a->elites : m->samples);
+  const char* what = nullptr;
+  if (t->reserved0 != 0) what = "urgym_mppi_temper.reserved0 must be 0";
+  else if (!isfinite(t->ess_target) || t->ess_target < 1.0 || t->ess_target > most) what = "urgym_mppi_temper.ess_target must be finite and in [1, M] (M = elites; samples without adapt)";
+  else if (!isfinite(t->lam_min) || !isfinite(t->lam_max)) what = "urgym_mppi_temper.lam_min and lam_max must be finite";
+  else if (t->lam_min < 1e-100 || t->lam_max > 1e100) what = "urgym_mppi_temper.lam_min and lam_max must lie in [1e-100, 1e100]";
+  else if (t->lam_min > t->lam_max) what = "urgym_mppi_temper.lam_min must not exceed lam_max";
+  else if (t->steps < 1 || t->steps > URGYM_MPPI_TEMPER_STEPS_MAX) what = "urgym_mppi_temper.steps must be in [1, URGYM_MPPI_TEMPER_STEPS_MAX] (64)";
+  else if (!t->lam_out) what = "urgym_mppi_temper.lam_out is null";
+  if (what) return fail_in(report, URGYM_ERR_ARG, who, what);
+  *out = MppiTemper{t->ess_target, t->lam_min, t->lam_max, t->steps, t->lam_out, t->saturated};
+  return URGYM_OK;
+}
+
 // the launches of one plan; everything has been checked.  gd == nullptr: the plain plan.  ad == nullptr: the plain update and sample;
 // else the elite update stands in place of the update and, with adapt_std, iterations >= 1 sample with new_std of the iteration before.
-int plan(Handle* sh, Handle* ph, const urgym_mppi& m, uint64_t draw, hipStream_t s, const Guide* gd = nullptr, const Adapt* ad = nullptr) {
+// tp != nullptr: the tempered update stands in place of either update.
+int plan(Handle* sh, Handle* ph, const urgym_mppi& m, uint64_t draw, hipStream_t s, const Guide* gd = nullptr, const Adapt* ad = nullptr, const MppiTemper* tp = nullptr) {
   const size_t row = (size_t)ph->cfg.num_envs * 6;
   const MppiFanout f = fanout_of(sh, ph, m);
   const MppiOutcome o = outcome_of(ph);
@@ -278,7 +300,8 @@ int plan(Handle* sh, Handle* ph, const urgym_mppi& m, uint64_t draw, hipStream_t
     if (gd && gd->terminal) mppi_terminal_launch(m, gd->call, s);
     urgym_mppi last = m;
     if (i + 1 < m.iterations) last.shift = 0;  // the sequence advances once, after the last refinement
-    if (ad) mppi_elite_update_launch(last, ad->call, s);
+    if (tp) mppi_tempered_update_launch(last, *tp, ad ? &ad->call : nullptr, s);
+    else if (ad) mppi_elite_update_launch(last, ad->call, s);
     else mppi_update_launch(last, s);
   }
   return URGYM_OK;
@@ -288,10 +311,10 @@ int plan(Handle* sh, Handle* ph, const urgym_mppi& m, uint64_t draw, hipStream_t
 // before the source step that reads action_out, and that step before the record pass that files its outcome and the fan-out that
 // clones its state.
 int control(Handle* sh, Handle* ph, const urgym_mppi& m, uint64_t first_draw, int num_steps, const urgym_trajectory* traj, hipStream_t s, const Guide* gd = nullptr,
-            const Adapt* ad = nullptr) {
+            const Adapt* ad = nullptr, const MppiTemper* tp = nullptr) {
   mppi_record_launch(record_of(sh, m, traj, 0, num_steps), s);
   for (int t = 0; t < num_steps; t++) {
-    if (int rc = plan(sh, ph, m, first_draw + (uint64_t)t, s, gd, ad)) return rc;
+    if (int rc = plan(sh, ph, m, first_draw + (uint64_t)t, s, gd, ad, tp)) return rc;
     if (int rc = do_step(sh, m.action_out, s)) return rc;
     mppi_record_launch(record_of(sh, m, traj, t + 1, num_steps), s);
   }
@@ -370,13 +393,13 @@ ReplayStore store_of(const Handle* h, const urgym_replay_ring& r, int first_slot
 // clones the source's state and reads mean, the plan's update before the execute launch that reads action_out, and that before the
 // source step that reads the slot's action rows.
 int collect(Handle* sh, Handle* ph, const urgym_mppi& m, const Guide* gd, const urgym_mppi_explore& x, uint64_t first_draw, int num_steps,
-            const urgym_replay_ring& ring, int first_slot, hipStream_t s, const Adapt* ad = nullptr) {
+            const urgym_replay_ring& ring, int first_slot, hipStream_t s, const Adapt* ad = nullptr, const MppiTemper* tp = nullptr) {
   const size_t row = (size_t)sh->cfg.num_envs * 6, C = (size_t)ring.capacity_steps;
   for (int t = 0; t < num_steps; t++) {
     replay_store_launch(store_of(sh, ring, first_slot, t, num_steps), s);
     if (t > 0) mppi_record_launch(record_of(sh, m, nullptr, t, num_steps), s);
     const uint64_t draw = first_draw + (uint64_t)t;
-    if (int rc = plan(sh, ph, m, draw, s, gd, ad)) return rc;
+    if (int rc = plan(sh, ph, m, draw, s, gd, ad, tp)) return rc;
     float* actions = ring.action + (((size_t)first_slot + (size_t)t) % C) * row;  // the execute launch writes the slot, the step reads it
     mppi_execute_launch(execute_of(m, x, draw, actions), s);
     if (int rc = do_step(sh, actions, s)) return rc;
@@ -408,7 +431,8 @@ int check_stats(Handle* report, const urgym_mppi* m, const urgym_mppi_adapt* a, 
 // ---- the planner inside the training call (urgym_mppi_train.h)
 namespace urgym {
 
-int planned_check(const char* who, Handle* h, const urgym_sac_planning* planning, const urgym_replay_ring* ring, const urgym_sac_schedule& S, PlannedCall* out) {
+int planned_check(const char* who, Handle* h, const urgym_sac_planning* planning, const urgym_replay_ring* ring, const urgym_sac_schedule& S, PlannedCall* out,
+                  const urgym_mppi_temper* temper_or_NULL) {
   static_assert(sizeof(urgym_sac_planning) == 72 && alignof(urgym_sac_planning) == 8, "include/urgym.h");
   if (!planning) return fail_in(h, URGYM_ERR_ARG, who, "null planning");
   const urgym_sac_planning& P = *planning;
@@ -430,6 +454,9 @@ int planned_check(const char* who, Handle* h, const urgym_sac_planning* planning
   if (int rc = P.guide_or_NULL ? check_guided_pair(h, ph, P.mppi, P.guide_or_NULL, who, &gd) : check_pair(h, ph, P.mppi, who)) return rc;
   if (P.adapt_or_NULL)
     if (int rc = check_adapt(h, P.mppi, P.adapt_or_NULL, who, &ad)) return rc;
+  MppiTemper tp;
+  if (temper_or_NULL)
+    if (int rc = check_temper(h, P.mppi, temper_or_NULL, P.adapt_or_NULL, who, &tp)) return rc;
   if (!h->observed) return fail_in(h, URGYM_ERR_STATE, who, "nothing has been observed yet: urgym_reset() or urgym_refresh() the source first");
   if (int rc = check_explore(h, &P.explore, who)) return rc;
   if (int rc = check_ring(h, ring, S.first_slot, K, who)) return rc;
@@ -441,11 +468,13 @@ int planned_check(const char* who, Handle* h, const urgym_sac_planning* planning
   c.guided = P.guide_or_NULL != nullptr, c.adaptive = P.adapt_or_NULL != nullptr;
   if (c.guided) c.guide = *P.guide_or_NULL, c.sync_actor = gd.actor, c.sync_critic = gd.critic;
   if (c.adaptive) c.adapt = *P.adapt_or_NULL;
+  c.tempered = temper_or_NULL != nullptr;
+  if (c.tempered) c.temper = *temper_or_NULL;
   *out = c;
   return URGYM_OK;
 }
 
-// planned_check has accepted the guide and the adapt struct: resolving them again refuses nothing
+// planned_check has accepted the guide, the adapt and the temper struct: resolving them again refuses nothing
 int planned_collect(const PlannedCall& c, uint64_t first_draw, int num_steps, int first_slot, hipStream_t s) {
   const char* who = "planned_collect";
   Guide gd;
@@ -454,7 +483,11 @@ int planned_collect(const PlannedCall& c, uint64_t first_draw, int num_steps, in
     if (int rc = check_guide(c.source, c.planner, &c.m, &c.guide, who, &gd)) return rc;
   if (c.adaptive)
     if (int rc = check_adapt(c.source, &c.m, &c.adapt, who, &ad)) return rc;
-  return collect(c.source, c.planner, c.m, c.guided ? &gd : nullptr, c.explore, first_draw, num_steps, c.ring, first_slot, s, c.adaptive ? &ad : nullptr);
+  MppiTemper tp;
+  if (c.tempered)
+    if (int rc = check_temper(c.source, &c.m, &c.temper, c.adaptive ? &c.adapt : nullptr, who, &tp)) return rc;
+  return collect(c.source, c.planner, c.m, c.guided ? &gd : nullptr, c.explore, first_draw, num_steps, c.ring, first_slot, s, c.adaptive ? &ad : nullptr,
+                 c.tempered ? &tp : nullptr);
 }
 
 void planned_stats(const PlannedCall& c, urgym_mppi_stats_record* record, int64_t iteration, hipStream_t s) {
@@ -693,6 +726,76 @@ int urgym_mppi_collect_adaptive(void* source_handle, void* planner_handle, const
   if (int rc = check_draw(sh, first_draw, num_steps, who)) return rc;
   HIP_TRY(sh, hipSetDevice(sh->device));
   if (int rc = collect(sh, ph, *m, guide_or_NULL ? &gd : nullptr, *x, first_draw, num_steps, *ring, first_slot, (hipStream_t)stream, &ad)) return rc;
+  return launched(sh);
+}
+
+int urgym_mppi_update_tempered(void* handle, const urgym_mppi* m, const urgym_mppi_temper* temper, const urgym_mppi_adapt* adapt_or_NULL, void* stream) {
+  const char* who = "urgym_mppi_update_tempered";
+  Handle* h = (Handle*)handle;
+  Adapt ad;
+  MppiTemper tp;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (int rc = check_mppi(h, m, who)) return rc;
+  if (adapt_or_NULL)
+    if (int rc = check_adapt(h, m, adapt_or_NULL, who, &ad)) return rc;
+  if (int rc = check_temper(h, m, temper, adapt_or_NULL, who, &tp)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  mppi_tempered_update_launch(*m, tp, adapt_or_NULL ? &ad.call : nullptr, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_mppi_plan_tempered(void* source_handle, void* planner_handle, const urgym_mppi* m, const urgym_mppi_temper* temper, const urgym_mppi_adapt* adapt_or_NULL, const urgym_mppi_guide* guide_or_NULL, uint64_t draw, void* stream) {
+  const char* who = "urgym_mppi_plan_tempered";
+  Handle *sh = (Handle*)source_handle, *ph = (Handle*)planner_handle;
+  Guide gd;
+  Adapt ad;
+  MppiTemper tp;
+  if (!sh) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (int rc = guide_or_NULL ? check_guided_pair(sh, ph, m, guide_or_NULL, who, &gd) : check_pair(sh, ph, m, who)) return rc;
+  if (adapt_or_NULL)
+    if (int rc = check_adapt(sh, m, adapt_or_NULL, who, &ad)) return rc;
+  if (int rc = check_temper(sh, m, temper, adapt_or_NULL, who, &tp)) return rc;
+  if (int rc = check_draw(sh, draw, 1, who)) return rc;
+  HIP_TRY(sh, hipSetDevice(sh->device));
+  if (int rc = plan(sh, ph, *m, draw, (hipStream_t)stream, guide_or_NULL ? &gd : nullptr, adapt_or_NULL ? &ad : nullptr, &tp)) return rc;
+  return launched(sh);
+}
+
+int urgym_mppi_control_tempered(void* source_handle, void* planner_handle, const urgym_mppi* m, const urgym_mppi_temper* temper, const urgym_mppi_adapt* adapt_or_NULL, const urgym_mppi_guide* guide_or_NULL, uint64_t first_draw, int num_steps, const urgym_trajectory* traj_or_NULL, void* stream) {
+  const char* who = "urgym_mppi_control_tempered";
+  Handle *sh = (Handle*)source_handle, *ph = (Handle*)planner_handle;
+  Guide gd;
+  Adapt ad;
+  MppiTemper tp;
+  if (!sh) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (int rc = guide_or_NULL ? check_guided_pair(sh, ph, m, guide_or_NULL, who, &gd) : check_pair(sh, ph, m, who)) return rc;
+  if (adapt_or_NULL)
+    if (int rc = check_adapt(sh, m, adapt_or_NULL, who, &ad)) return rc;
+  if (int rc = check_temper(sh, m, temper, adapt_or_NULL, who, &tp)) return rc;
+  if (int rc = check_record(sh, 0, num_steps, traj_or_NULL, who)) return rc;
+  if (int rc = check_draw(sh, first_draw, num_steps, who)) return rc;
+  HIP_TRY(sh, hipSetDevice(sh->device));
+  if (int rc = control(sh, ph, *m, first_draw, num_steps, traj_or_NULL, (hipStream_t)stream, guide_or_NULL ? &gd : nullptr, adapt_or_NULL ? &ad : nullptr, &tp)) return rc;
+  return launched(sh);
+}
+
+int urgym_mppi_collect_tempered(void* source_handle, void* planner_handle, const urgym_mppi* m, const urgym_mppi_temper* temper, const urgym_mppi_adapt* adapt_or_NULL, const urgym_mppi_guide* guide_or_NULL, const urgym_mppi_explore* x, uint64_t first_draw, int num_steps, const urgym_replay_ring* ring, int first_slot, void* stream) {
+  const char* who = "urgym_mppi_collect_tempered";
+  Handle *sh = (Handle*)source_handle, *ph = (Handle*)planner_handle;
+  Guide gd;
+  Adapt ad;
+  MppiTemper tp;
+  if (!sh) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (int rc = guide_or_NULL ? check_guided_pair(sh, ph, m, guide_or_NULL, who, &gd) : check_pair(sh, ph, m, who)) return rc;
+  if (adapt_or_NULL)
+    if (int rc = check_adapt(sh, m, adapt_or_NULL, who, &ad)) return rc;
+  if (int rc = check_temper(sh, m, temper, adapt_or_NULL, who, &tp)) return rc;
+  if (!sh->observed) return fail_in(sh, URGYM_ERR_STATE, who, "nothing has been observed yet: urgym_reset() or urgym_refresh() the source first");
+  if (int rc = check_explore(sh, x, who)) return rc;
+  if (int rc = check_ring(sh, ring, first_slot, num_steps, who)) return rc;
+  if (int rc = check_draw(sh, first_draw, num_steps, who)) return rc;
+  HIP_TRY(sh, hipSetDevice(sh->device));
+  if (int rc = collect(sh, ph, *m, guide_or_NULL ? &gd : nullptr, *x, first_draw, num_steps, *ring, first_slot, (hipStream_t)stream, adapt_or_NULL ? &ad : nullptr, &tp)) return rc;
   return launched(sh);
 }
 

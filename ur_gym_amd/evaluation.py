@@ -2768,6 +2768,89 @@ def mppi_elite_update(ret, w, actions, shift, std_min, std_max):
     return out
 
 
+_TEMPER_LOG2E, _TEMPER_LN2_HI, _TEMPER_LN2_LO = np.float64(1.4426950408889634), np.float64(6.93147180369123816490e-01), np.float64(1.90821492927058770002e-10)
+# 1 / n! for n = 0 .. 13, each the correctly rounded float64 (urgym_mppi_temper.h writes the same literals)
+_TEMPER_COEF = (1.0, 1.0, 0.5, 0.16666666666666666, 0.041666666666666664, 0.008333333333333333, 0.001388888888888889, 0.0001984126984126984,
+                2.48015873015873e-05, 2.7557319223985893e-06, 2.755731922398589e-07, 2.505210838544172e-08, 2.08767569878681e-09, 1.6059043836821613e-10)
+
+
+def mppi_temper_exp(x):
+    """THE EXPONENTIAL of include/urgym.h ("the temperature from a target effective sample size") in numpy, bitwise, elementwise: `x`
+    float64, not positive and no NaN.  x < -708 gives +0.0; otherwise y = x * LOG2E; kf = rint(y); hi = kf * LN2_HI; r1 = x - hi;
+    lo = kf * LN2_LO; r = r1 - lo; Horner over 1 / n!, n = 13 .. 0, as t = p * r; p = t + c; the result is p times the power of two whose
+    exponent field is 1023 + kf.  Every operation is one float64 rounding.  Within 2 ulp of exp; exactly 1 at 0 and -0.0."""
+    x = np.asarray(x, dtype=np.float64)
+    if np.isnan(x).any() or (x > 0).any():
+        raise ValueError("mppi_temper_exp takes arguments that are not positive and no NaN")
+    below = x < -708.0
+    xs = np.where(below, 0.0, x)  # the lanes that return early take no part in what follows
+    kf = np.rint(xs * _TEMPER_LOG2E)
+    r = xs - kf * _TEMPER_LN2_HI
+    r = r - kf * _TEMPER_LN2_LO
+    p = np.full_like(r, _TEMPER_COEF[13])
+    for c in _TEMPER_COEF[12::-1]:
+        t = p * r
+        p = t + np.float64(c)
+    scale = ((np.int64(1023) + kf.astype(np.int64)) << np.int64(52)).view(np.float64)
+    return np.where(below, 0.0, p * scale)
+
+
+def mppi_temper_solve(ret, samples, ess_target, lam_min, lam_max, steps, lam=5.0, elites=None):
+    """THE SEARCH of include/urgym.h ("the temperature from a target effective sample size") and the weights it ends with, in numpy,
+    bitwise: `ret` float64 [E * K].  A sample is counted where its return is finite and, with `elites`, where it is an elite of
+    ``mppi_elite_rank``.  ess(lam) = (Z * Z) / Q with Z and Q THE ORDERED SUMs of w_j = ``mppi_temper_exp((r_j - rmax) / lam)`` (0 where
+    j is not counted) and of w_j * w_j.  Per parent: no finite return keeps `lam` (urgym_mppi.lam) and puts everything on sample 0
+    (saturated 3); ess(lam_max) < T ends at lam_max (1); ess(lam_min) >= T at lam_min (2); otherwise `steps` bisections of
+    mid = sqrt(lo * hi) -- ess(mid) >= T moves hi, else lo -- end at hi (0).  Returns a dict of lam [E], saturated (uint8 [E]), w
+    ([E, K], what ``mppi_update`` / ``mppi_elite_update`` take), ess [E] (the value the search last accepted: that of w), rmax [E], and
+    lam_below [E]: the lo the bisection ended with (ess there is below T; lam itself where there was no bisection)."""
+    from . import _abi
+
+    K, S, T = int(samples), int(steps), np.float64(ess_target)
+    r = np.asarray(ret, dtype=np.float64).reshape(-1, K)
+    E = r.shape[0]
+    finite = np.isfinite(r)
+    counted = finite if elites is None else mppi_elite_rank(ret, K, elites)["elite"] != 0
+    rmax = np.where(finite, r, -np.inf).max(axis=1)
+    out = dict(lam=np.zeros(E, np.float64), saturated=np.zeros(E, np.uint8), w=np.zeros((E, K), np.float64), ess=np.zeros(E, np.float64), rmax=rmax,
+               lam_below=np.zeros(E, np.float64))
+
+    def weights(p, at):
+        with np.errstate(all="ignore"):
+            d = np.where(counted[p], r[p] - rmax[p], 0.0)
+            return np.where(counted[p], mppi_temper_exp(d / np.float64(at)), 0.0)
+
+    def ess(p, at):
+        w = weights(p, at)
+        Z, Q = ordered_sum(w, np.float64), ordered_sum(w * w, np.float64)
+        return (Z * Z) / Q
+
+    for p in range(E):
+        if not finite[p].any():
+            at, below, how = np.float64(lam), np.float64(lam), _abi.MPPI_TEMPER_NO_RETURN
+            w = np.zeros(K, np.float64)
+            w[0] = 1.0
+        else:
+            lo, hi = np.float64(lam_min), np.float64(lam_max)
+            if ess(p, hi) < T:
+                at, below, how = hi, hi, _abi.MPPI_TEMPER_AT_MAX
+            elif ess(p, lo) >= T:
+                at, below, how = lo, lo, _abi.MPPI_TEMPER_AT_MIN
+            else:
+                for _ in range(S):
+                    q = lo * hi
+                    mid = np.sqrt(q)
+                    if ess(p, mid) >= T:
+                        hi = mid
+                    else:
+                        lo = mid
+                at, below, how = hi, lo, _abi.MPPI_TEMPER_SOLVED
+            w = weights(p, at)
+        Z, Q = ordered_sum(w, np.float64), ordered_sum(w * w, np.float64)
+        out["lam"][p], out["lam_below"][p], out["saturated"][p], out["w"][p], out["ess"][p] = at, below, how, w, (Z * Z) / Q
+    return out
+
+
 def mppi_guided_actions(actions, policy_action, eps, policy_sigma, samples, policy_samples):
     """THE GUIDE in numpy, bitwise (include/urgym.h, "MPPI with the learner in the loop"): `actions` and `eps` float32 [H, E * K, 6] as the
     sample launch left them, `policy_action` float32 [H, E * K, 6] -- row h what the actor gave before planner step h -- or [E * K, 6] for
@@ -2947,6 +3030,13 @@ class DeviceMPPI:
     the struct, and ``DIAGNOSTICS`` gains ``elite_count`` and ``threshold``; with ``elites=None`` and ``adapt_std=False`` the planner
     makes exactly the calls it made before.
 
+    The temperature from a target effective sample size, opt-in.  `ess_target` = T in [1, M] (M = `elites`, or
+    `samples` without them): every update solves its own temperature per env, within [`lam_min`, `lam_max`] by `temper_steps` bisections,
+    so that the weights have an effective sample size of T (``mppi_temper_solve`` restates it); `lam` is then used only for an env
+    without a finite return.  The ``urgym_mppi_*_tempered`` entry points are called, ``temper()`` is the struct, and ``DIAGNOSTICS``
+    gains ``lam`` (the temperature of the last update) and ``saturated`` (``_abi.MPPI_TEMPER_*``: 0 solved, 1 at `lam_max`, the target
+    cannot be met, 2 at `lam_min`, 3 no finite return) [E]; with ``ess_target=None`` the planner makes exactly the calls it made before.
+
     Plan statistics.  ``stats()`` reduces the diagnostics of the last plan to one ``urgym_mppi_stats_record`` on
     the device; ``records`` is this planner's array of them (int64 [capacity, 11], grown by ``reserve_records``), which
     ``SACLearner.train(planner=, plan_stats=True)`` fills beside the monitor's records; ``planning()`` is the ``urgym_sac_planning`` of such
@@ -2956,7 +3046,7 @@ class DeviceMPPI:
 
     def __init__(self, env, samples=256, horizon=6, sigma=0.6, lam=5.0, gamma=1.0, iterations=1, shift=True, seed=0, keep_weights=False,
                  actor=None, critic=None, policy_samples=0, policy_sigma=0.0, terminal_value=False, fail_cost=0.0, elites=None, adapt_std=False,
-                 std_min=0.05, std_max=None):
+                 std_min=0.05, std_max=None, ess_target=None, lam_min=1e-3, lam_max=1e6, temper_steps=32):
         import ctypes as C
 
         import torch
@@ -2970,6 +3060,7 @@ class DeviceMPPI:
         if not (np.isfinite(sigma) and sigma >= 0 and np.isfinite(lam) and lam > 0 and np.isfinite(gamma)):
             raise ValueError(f"DeviceMPPI: sigma must be finite and >= 0, lam finite and > 0, gamma finite; got {sigma}, {lam}, {gamma}")
         adapt = self.check_adapt(K, sigma, elites, adapt_std, std_min, std_max)
+        temper = self.check_temper(K if adapt is None else adapt[0], ess_target, lam_min, lam_max, temper_steps)
         same = {name: getattr(env.cfg, name) for name, _ in _abi.Config._fields_ if name not in ("env_kind", "num_envs", "auto_reset", "check_collision")}
         self.env = env
         self.planner = UR5ReachVectorEnv(env.env_id, num_envs=E * K, device=env.device, auto_reset=False, check_collision=bool(env.cfg.check_collision), **same)
@@ -2995,6 +3086,15 @@ class DeviceMPPI:
                 setattr(A, name, C.cast(self.buf[name].data_ptr(), C.POINTER(ct)))
             self._adapt = A
             self.DIAGNOSTICS = DeviceMPPI.DIAGNOSTICS + ("elite_count", "threshold")
+        self._temper = None
+        if temper is not None:
+            T = _abi.MppiTemper()
+            T.ess_target, T.lam_min, T.lam_max, T.steps = temper
+            for name, ct, shape in _abi.MPPI_TEMPER_FIELDS:
+                self.buf[name] = torch.zeros(shape(E, K, H), dtype=_TORCH_DTYPE[ct], device=env.device)
+                setattr(T, name, C.cast(self.buf[name].data_ptr(), C.POINTER(ct)))
+            self._temper = T
+            self.DIAGNOSTICS = self.DIAGNOSTICS + ("lam", "saturated")
         self.records = torch.zeros((64, _abi.MPPI_STATS_RECORD_WORDS), dtype=torch.int64, device=env.device)  # [capacity] urgym_mppi_stats_record
         self.actor = self.critic = self._guide = None
         P = int(policy_samples)
@@ -3055,9 +3155,47 @@ class DeviceMPPI:
             raise ValueError(f"DeviceMPPI: std_min and std_max must be finite (in float32) with 0 <= std_min <= std_max, got {std_min!r}, {std_max!r}")
         return M, int(bool(adapt_std)), lo, hi
 
+    @staticmethod
+    def check_temper(most, ess_target=None, lam_min=1e-3, lam_max=1e6, temper_steps=32):
+        """Raises ValueError for what the tempered entry points refuse about urgym_mppi_temper's scalars; `most` is M, the elites, or the
+        samples without them.  Returns None where `ess_target` is None (nothing else is looked at), else (ess_target, lam_min, lam_max,
+        steps) as the struct takes them.  Needs no GPU."""
+        from . import _abi
+
+        if ess_target is None:
+            return None
+        low, high = _abi.MPPI_TEMPER_LAM_RANGE
+        if isinstance(ess_target, bool) or not (np.isfinite(ess_target) and 1.0 <= float(ess_target) <= float(most)):
+            raise ValueError(f"DeviceMPPI: ess_target must be finite and in [1, M] (M = {int(most)}: elites, or samples without them), got {ess_target!r}")
+        if not (np.isfinite(lam_min) and np.isfinite(lam_max) and low <= float(lam_min) <= float(lam_max) <= high):
+            raise ValueError(f"DeviceMPPI: lam_min and lam_max must be finite with 1e-100 <= lam_min <= lam_max <= 1e100, got {lam_min!r}, {lam_max!r}")
+        if isinstance(temper_steps, bool) or int(temper_steps) != temper_steps or not 1 <= int(temper_steps) <= _abi.MPPI_TEMPER_STEPS_MAX:
+            raise ValueError(f"DeviceMPPI: temper_steps must be an integer in [1, {_abi.MPPI_TEMPER_STEPS_MAX}], got {temper_steps!r}")
+        return float(ess_target), float(lam_min), float(lam_max), int(temper_steps)
+
     def struct(self):
         """The ``urgym_mppi`` of this planner (its pointers stay valid until ``close``)."""
         return self._struct
+
+    def temper(self):
+        """The ``urgym_mppi_temper`` of this planner, or None where `ess_target` was not given."""
+        return self._temper
+
+    def update(self):
+        """The single update launch on the returns as they stand: ``urgym_mppi_update_tempered`` with `ess_target`, else
+        ``urgym_mppi_update_elite`` with elites or the adaptive std, else ``urgym_mppi_update``.  NOT synchronised."""
+        import ctypes as C
+
+        from . import _native
+
+        env = self.env
+        adapt = None if self._adapt is None else C.byref(self._adapt)
+        if self._temper is not None:
+            _native.check(env.lib.urgym_mppi_update_tempered(env._h, C.byref(self._struct), C.byref(self._temper), adapt, env._stream()), env._h)
+        elif self._adapt is not None:
+            _native.check(env.lib.urgym_mppi_update_elite(env._h, C.byref(self._struct), adapt, env._stream()), env._h)
+        else:
+            _native.check(env.lib.urgym_mppi_update(env._h, C.byref(self._struct), env._stream()), env._h)
 
     def adapt(self):
         """The ``urgym_mppi_adapt`` of this planner, or None where neither `elites` nor `adapt_std` was given."""
@@ -3069,21 +3207,25 @@ class DeviceMPPI:
 
     def plan(self, draw=0):
         """One ``urgym_mppi_plan`` from the environment's state as it stands.  Returns (action_out [E, 6], diagnostics): views of this
-        planner's buffers, overwritten by the next plan; diagnostics holds ``best_return``, ``nominal_return`` and ``ess`` [E], and with
-        elites or the adaptive std ``elite_count`` and ``threshold`` [E].  NOT synchronised."""
+        planner's buffers, overwritten by the next plan; diagnostics holds ``best_return``, ``nominal_return`` and ``ess`` [E], with
+        elites or the adaptive std ``elite_count`` and ``threshold`` [E], and with `ess_target` ``lam`` and ``saturated`` [E].  NOT
+        synchronised."""
         import ctypes as C
 
         from . import _native
 
         env = self.env
         guide = None if self._guide is None else C.byref(self._guide)
-        if self._adapt is not None:
+        if self._temper is not None:
+            _native.check(env.lib.urgym_mppi_plan_tempered(env._h, self.planner._h, C.byref(self._struct), C.byref(self._temper),
+                                                           None if self._adapt is None else C.byref(self._adapt), guide, int(draw), env._stream()), env._h)
+        elif self._adapt is not None:
             _native.check(env.lib.urgym_mppi_plan_adaptive(env._h, self.planner._h, C.byref(self._struct), C.byref(self._adapt), guide, int(draw), env._stream()), env._h)
         elif self._guide is None:
             _native.check(env.lib.urgym_mppi_plan(env._h, self.planner._h, C.byref(self._struct), int(draw), env._stream()), env._h)
         else:
             _native.check(env.lib.urgym_mppi_plan_guided(env._h, self.planner._h, C.byref(self._struct), C.byref(self._guide), int(draw), env._stream()), env._h)
-        return self.buf["action_out"], {k: self.buf[k] for k in self.DIAGNOSTICS + (("terminal",) if "terminal" in self.buf else ())}
+        return self.buf["action_out"], {k: self.buf["lam_out" if k == "lam" else k] for k in self.DIAGNOSTICS + (("terminal",) if "terminal" in self.buf else ())}
 
     def run(self, num_steps, first_draw=0, record=("reward", "terminated", "truncated", "is_success")):
         """`num_steps` x (plan, step the environment with the plan's first action) in ONE native call (``urgym_mppi_control``); step t
@@ -3112,7 +3254,12 @@ class DeviceMPPI:
                 t = torch.zeros(shape(T, env.num_envs, env.obs_dim, env.goal_dim), dtype=_TORCH_DTYPE[ct], device=env.device)
                 setattr(traj, name, C.cast(t.data_ptr(), C.POINTER(ct)))
                 out[name] = t.view(torch.bool) if ct is C.c_uint8 else t
-        if self._adapt is not None:
+        if self._temper is not None:
+            _native.check(env.lib.urgym_mppi_control_tempered(env._h, self.planner._h, C.byref(self._struct), C.byref(self._temper),
+                                                              None if self._adapt is None else C.byref(self._adapt),
+                                                              None if self._guide is None else C.byref(self._guide), int(first_draw), T,
+                                                              C.byref(traj) if names else None, env._stream()), env._h)
+        elif self._adapt is not None:
             _native.check(env.lib.urgym_mppi_control_adaptive(env._h, self.planner._h, C.byref(self._struct), C.byref(self._adapt),
                                                               None if self._guide is None else C.byref(self._guide), int(first_draw), T,
                                                               C.byref(traj) if names else None, env._stream()), env._h)
@@ -3170,6 +3317,11 @@ class DeviceMPPI:
         replay.check_args(replay.capacity, num_steps=num_steps, first_slot=first)
         x = _abi.MppiExplore(self.check_explore(explore_sigma), 0, None)
         guide = None if self._guide is None else C.byref(self._guide)
+        if self._temper is not None:
+            _native.check(env.lib.urgym_mppi_collect_tempered(env._h, self.planner._h, C.byref(self._struct), C.byref(self._temper),
+                                                              None if self._adapt is None else C.byref(self._adapt), guide, C.byref(x),
+                                                              int(first_draw), int(num_steps), C.byref(replay._ring), int(first), env._stream()), env._h)
+            return
         if self._adapt is not None:
             _native.check(env.lib.urgym_mppi_collect_adaptive(env._h, self.planner._h, C.byref(self._struct), C.byref(self._adapt), guide, C.byref(x),
                                                               int(first_draw), int(num_steps), C.byref(replay._ring), int(first), env._stream()), env._h)

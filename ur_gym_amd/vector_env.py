@@ -52,6 +52,7 @@ _TORCH_DTYPE = {C.c_double: torch.float64, C.c_float: torch.float32, C.c_int32: 
 # The training call's entry points (include/urgym.h), in the order ``sac_train`` tries them: (symbol, the option that selects it, the
 # options it takes between ``learner, schedule`` and ``stream``, in the order of its signature).  The last row takes none.
 _SAC_TRAIN_ENTRIES = (
+    ("urgym_sac_train_tempered", "temper", ("planner", "temper", "clipping", "nstep", "prioritized", "hindsight", "evaluation", "monitor")),
     ("urgym_sac_train_planned", "planner", ("planner", "clipping", "nstep", "prioritized", "hindsight", "evaluation", "monitor")),
     ("urgym_sac_train_normalized", "normalizer", ("normalizer", "clipping", "nstep", "prioritized", "hindsight", "evaluation", "monitor")),
     ("urgym_sac_train_clipped", "clipping", ("clipping", "nstep", "prioritized", "hindsight", "evaluation", "monitor")),
@@ -66,7 +67,8 @@ _SAC_TRAIN_ENTRIES = (
 
 def _sac_train_entry(present):
     """(symbol, option names) of the entry point that serves a call with the options in `present` (any container of names out of
-    evaluation, monitor, nstep, prioritized, hindsight, clipping, normalizer, planner): the first row of ``_SAC_TRAIN_ENTRIES`` whose option is given."""
+    evaluation, monitor, nstep, prioritized, hindsight, clipping, normalizer, planner, temper -- the planner's temper struct, given where
+    the planner has an ess_target): the first row of ``_SAC_TRAIN_ENTRIES`` whose option is given."""
     for symbol, selects, options in _SAC_TRAIN_ENTRIES:
         if selects is None or selects in present:
             return symbol, options
@@ -1033,6 +1035,8 @@ class UR5ReachVectorEnv:
             if planner.get("records", False):
                 mppi.reserve_records(monitor.count + len(logged))
             given["planner"] = mppi.planning(planner.get("explore_sigma", 0.0), planner.get("sync", True), planner.get("records", False))
+            if mppi.temper() is not None:
+                given["temper"] = mppi.temper()
         symbol, options = _sac_train_entry(given)
         try:
             _native.check(getattr(self.lib, symbol)(self._h, C.byref(L), C.byref(S), *[C.byref(given[o]) if o in given else None for o in options], self._stream()), self._h)
