@@ -2240,6 +2240,52 @@ int urgym_mppi_collect_tempered(void* source_handle, void* planner_handle, const
  * urgym_sac_train_tempered), and what urgym_mppi_update_tempered refuses about temper. */
 int urgym_sac_train_tempered(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_planning* planning, const urgym_mppi_temper* temper, const urgym_sac_clipping* clipping_or_NULL, const urgym_sac_nstep* nstep_or_NULL, const urgym_sac_prioritized* prioritized_or_NULL, const urgym_sac_hindsight* hindsight_or_NULL, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream);
 
+/* ---- temporally correlated sampling noise.  THE SAMPLE draws every (horizon step, sample, joint) independently:
+ * a sample's net displacement over H steps grows like sigma * sqrt(H), and most of a sequence's energy is step-to-step jitter that the
+ * weighted mean cancels.  The coloured sample runs a first-order autoregressive recurrence along the horizon on top of the same draws
+ * (the change iCEM makes to CEM; smoothed MPPI and Ornstein-Uhlenbeck exploration do the same in their places).  Added WITHIN ABI
+ * version 4: no struct above changed, URGYM_ABI_VERSION did not move, no kernel of the calls above changed, the five symbols below are
+ * found by lookup.  A planner that does not use them makes the calls it made and leaves the bits it left.
+ *
+ * THE COLOURED SAMPLE (urgym_mppi_sample_colored, one launch).  xi[h][n][c] is THE SAMPLE's eps exactly as stated above: the same
+ * counters (p, (i << 24) | (h << 16) | j, (uint32)draw, URGYM_MPPI_TAG | block) with blocks 0 and 1, the same words, the same Box-Muller
+ * lines, and zero for sample j = 0.  No other Philox block is used.
+ *   on the host, once per call, float64:  b = (double)beta;  bb = b * b;  d = 1.0 - bb;  r = sqrt(d), correctly rounded;
+ *                                         scale = (float)r.        The kernel is handed beta and scale; the device never forms scale.
+ *   the recurrence, float32, one rounding per line:
+ *       eps[0][n][c] = xi[0][n][c]
+ *       for h >= 1:  a = beta * eps[h - 1][n][c];  b = scale * xi[h][n][c];  eps[h][n][c] = a + b
+ *   the action line is THE SAMPLE's:  s = width * eps[h][n][c];  a = mean[h][p][c] + s;  action = fminf(fmaxf(a, -1), 1),
+ *       width = m->sigma, or, where an adapt struct is given, std[h][p][c], read as THE ADAPTIVE SAMPLE reads it.
+ * Every step has unit marginal variance and lag-1 correlation beta.  Sample 0 stays the nominal sequence: every eps is +0.0.  beta = 0
+ * gives eps = xi by value (a -0.0 of xi becomes +0.0 from step 1 on), beta = 1 gives scale = 0 and every step the value of step 0.
+ * Both eps -- the coloured values -- and actions are written to urgym_mppi's arrays: THE GUIDE, which executes actor(state) +
+ * policy_sigma * eps, gets correlated policy samples with no change, and THE ELITE UPDATE's std, formed from actions, is unchanged too.
+ * The result is a function of (seed, draw, i, p, j, h, c, beta) only -- not of E, K or the launch geometry. */
+typedef struct urgym_mppi_noise {
+  float beta;        /* finite, in [0, 1] */
+  int32_t reserved0; /* must be 0 */
+} urgym_mppi_noise;
+
+/* The single launch; like urgym_mppi_sample it needs no bound environment.  Refused, launching and writing nothing (the message names
+ * the entry point and the argument): everything urgym_mppi_sample refuses, and with adapt_or_NULL everything urgym_mppi_sample_adaptive
+ * refuses; a NULL noise; a beta that is not finite or outside [0, 1]; a non-zero reserved0. */
+int urgym_mppi_sample_colored(void* handle, const urgym_mppi* m, const urgym_mppi_noise* noise, const urgym_mppi_adapt* adapt_or_NULL, uint64_t draw, int iteration, void* stream);
+
+/* urgym_mppi_plan_tempered, urgym_mppi_control_tempered and urgym_mppi_collect_tempered with the coloured sample as the sample launch of
+ * every iteration (temper_or_NULL == NULL: urgym_mppi_plan_adaptive, _control_adaptive and _collect_adaptive with it; adapt_or_NULL ==
+ * NULL as well: the plain or guided calls with it).  Where adapt_std is set and i >= 1 that launch follows the same copy of new_std into
+ * std and runs with the adapt struct; otherwise it runs with m->sigma.  Everything else is the untouched call: bit for bit the sequence
+ * of single launches.  Refused: what the call without noise refuses, and what urgym_mppi_sample_colored refuses about noise. */
+int urgym_mppi_plan_colored(void* source_handle, void* planner_handle, const urgym_mppi* m, const urgym_mppi_noise* noise, const urgym_mppi_temper* temper_or_NULL, const urgym_mppi_adapt* adapt_or_NULL, const urgym_mppi_guide* guide_or_NULL, uint64_t draw, void* stream);
+int urgym_mppi_control_colored(void* source_handle, void* planner_handle, const urgym_mppi* m, const urgym_mppi_noise* noise, const urgym_mppi_temper* temper_or_NULL, const urgym_mppi_adapt* adapt_or_NULL, const urgym_mppi_guide* guide_or_NULL, uint64_t first_draw, int num_steps, const urgym_trajectory* traj_or_NULL, void* stream);
+int urgym_mppi_collect_colored(void* source_handle, void* planner_handle, const urgym_mppi* m, const urgym_mppi_noise* noise, const urgym_mppi_temper* temper_or_NULL, const urgym_mppi_adapt* adapt_or_NULL, const urgym_mppi_guide* guide_or_NULL, const urgym_mppi_explore* x, uint64_t first_draw, int num_steps, const urgym_replay_ring* ring, int first_slot, void* stream);
+
+/* THE PLANNED TRAINING CALL with step 1 the launches of urgym_mppi_collect_colored; everything else as urgym_sac_train_planned (with
+ * temper_or_NULL: urgym_sac_train_tempered) states it.  Refused: what that call refuses (the message names urgym_sac_train_colored), and
+ * what urgym_mppi_sample_colored refuses about noise. */
+int urgym_sac_train_colored(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_planning* planning, const urgym_mppi_noise* noise, const urgym_mppi_temper* temper_or_NULL, const urgym_sac_clipping* clipping_or_NULL, const urgym_sac_nstep* nstep_or_NULL, const urgym_sac_prioritized* prioritized_or_NULL, const urgym_sac_hindsight* hindsight_or_NULL, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream);
+
 /* Replaces Reach*.set_goal / set_goal_and_obstacle (reach.py:202-204, 328-335, 702-713): the caller has
  * overwritten goal / obst_start / obst_end (and possibly q) for the masked envs; this recomputes obstacle pose,
  * velocity, collision, link_dist and the observation for them, leaving step_count untouched. */

@@ -28,6 +28,12 @@ mean temperature and the envs at a bound of the last timed plan -- beside the pl
 
     python tools/bench_mppi.py --env dyn --grid 256:6:0.6:5 --ess-target 8 32 128 --out profiles/mppi/dyn_temper.json
 
+With temporally correlated sampling noise (--noise-beta B [B ...]): every grid row is run again once per B and
+reported under "colored" -- the same protocol figures and the time of a coloured plan -- beside the figures of the same row with white
+noise; with a guide (--fail-cost, --terminal-value, --policy-samples) the coloured rows carry the guide too and stand beside "guided".
+
+    python tools/bench_mppi.py --env dyn --grid 256:6:0.6:5 --noise-beta 0 0.5 0.8 0.95 --out profiles/mppi/dyn_noise.json
+
     python tools/bench_mppi.py --env ori --grid 256:6:0.3:5 256:12:0.3:5 256:24:0.3:5 --terminal-value --policy-samples 64 \
         --actor tests/golden/actors/actor_ori.npz --critics tests/golden/critics/critic_ori_qf0.npz tests/golden/critics/critic_ori_qf1.npz
 """
@@ -123,6 +129,24 @@ def control_step_time(env, options, repeats, left=None):
     torch.cuda.synchronize()
     mppi.close()
     return begin.elapsed_time(mid) / repeats, mid.elapsed_time(end) / repeats
+
+
+def plan_time(env, options, repeats):
+    """ms of one plan of a DeviceMPPI with `options`, whichever entry point they select: device events around `repeats` plans after a
+    warm-up of three."""
+    import torch
+
+    mppi = DeviceMPPI(env, **options)
+    for draw in range(3):
+        mppi.plan(draw)
+    begin, end = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+    begin.record()
+    for draw in range(repeats):
+        mppi.plan(3 + draw)
+    end.record()
+    torch.cuda.synchronize()
+    mppi.close()
+    return begin.elapsed_time(end) / repeats
 
 
 def guided_step_time(env, options, repeats):
@@ -226,6 +250,8 @@ def main():
                     help="run every row again with the temperature solved per env and update for an effective sample size of T, once per value")
     ap.add_argument("--lam-min", type=float, default=1e-3, help="--ess-target: the lowest temperature of the search")
     ap.add_argument("--lam-max", type=float, default=1e6, help="--ess-target: the highest temperature of the search")
+    ap.add_argument("--noise-beta", type=float, nargs="+", default=None, metavar="B",
+                    help="run every row again with sampling noise of lag-1 correlation B along the horizon, once per value (0: white noise through the coloured calls)")
     args = ap.parse_args()
     import torch
 
@@ -283,6 +309,15 @@ def main():
             row.setdefault("tempered", []).append(dict(ess_target=target, lam_min=args.lam_min, lam_max=args.lam_max, **figures(success, reward, last, args.steps),
                                                        plan_ms=tempered_ms, plan_ms_over_plain=tempered_ms / plan_ms, last_plan=left,
                                                        closed_loop_wall_seconds_including_setup=wall))
+        for beta in args.noise_beta or ():
+            colored = dict(options, **(guide or {}), noise_beta=beta)
+            success, reward, last, wall = protocol(env_id, points, E, args.steps, args.device, colored)
+            env = make_vec(env_id, num_envs=E, device=args.device, seed=4, auto_reset=False)
+            env.reset(seed=4)
+            colored_ms = plan_time(env, colored, args.repeats)
+            env.close()
+            row.setdefault("colored", []).append(dict(noise_beta=beta, guided=bool(guide), **figures(success, reward, last, args.steps), plan_ms=colored_ms,
+                                                      plan_ms_over_plain=colored_ms / plan_ms, closed_loop_wall_seconds_including_setup=wall))
         rows.append(row)
         print(json.dumps(row), flush=True)
     ref = json.load(open(os.path.join(ROOT, "tests", "golden", "actors", "reference_results.json")))[kind]

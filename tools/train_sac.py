@@ -42,6 +42,8 @@ the lowest effective sample size, how many envs had a finite plan, and with elit
 (DeviceMPPI(ess_target=), urgym_mppi_*_tempered and with --native urgym_sac_train_tempered); --planner-lam is then
 used only by an env without a finite return.  With --monitor the last line of plan statistics of a native call also carries the mean of
 the temperatures its last plan left and how many envs ended at a bound, read on the host after the call's synchronise.
+--planner-noise-beta B gives the planner's sampling noise a lag-1 correlation of B along the horizon (DeviceMPPI(noise_beta=),
+urgym_mppi_*_colored and with --native urgym_sac_train_colored); 0 is white noise through the same calls.
 """
 import argparse
 import json
@@ -144,6 +146,8 @@ def main():
     ap.add_argument("--planner-ess-target", type=float, default=None, metavar="T",
                     help="--planner: solve the temperature per env and update for an effective sample size of T, in [1, M] (M = --planner-elites, else "
                          "--planner-samples; DESIGN.md section 31; default: the fixed --planner-lam)")
+    ap.add_argument("--planner-noise-beta", type=float, default=None, metavar="B",
+                    help="--planner: sampling noise with lag-1 correlation B in [0, 1] along the horizon (DESIGN.md section 32; default: white noise, the calls of before)")
     args = ap.parse_args()
     if args.planner and args.normalize:
         raise SystemExit("--planner plans on raw rows: not with --normalize (the planner's actor and critic read raw rows)")
@@ -187,7 +191,7 @@ def main():
                              policy_samples=args.planner_policy_samples, policy_sigma=args.planner_policy_sigma if args.planner_policy_samples else 0.0,
                              terminal_value=args.planner_terminal_value, fail_cost=args.planner_fail_cost, iterations=args.planner_iterations,
                              elites=args.planner_elites, adapt_std=args.planner_adapt_std, std_min=args.planner_std_min, std_max=args.planner_std_max,
-                             ess_target=args.planner_ess_target)
+                             ess_target=args.planner_ess_target, noise_beta=args.planner_noise_beta)
     updates, t0 = 0, time.perf_counter()
     best = dict(mean=-float("inf"), tensors=None)  # the Python route's own best_model
     if args.monitor and args.log_every < 1:

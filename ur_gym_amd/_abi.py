@@ -650,6 +650,11 @@ class MppiTemper(C.Structure):
         (name, C.POINTER(ct)) for name, ct, _ in MPPI_TEMPER_FIELDS]
 
 
+class MppiNoise(C.Structure):
+    """urgym_mppi_noise: the lag-1 correlation of the planner's sampling noise along the horizon.  It owns no array."""
+    _fields_ = [("beta", C.c_float), ("reserved0", C.c_int32)]
+
+
 # Every symbol include/urgym.h declares (tests check that the built library exports each of them).
 EXPORTED_SYMBOLS = [
     "urgym_abi_version",
@@ -747,6 +752,11 @@ EXPORTED_SYMBOLS = [
     "urgym_mppi_control_tempered",
     "urgym_mppi_collect_tempered",
     "urgym_sac_train_tempered",
+    "urgym_mppi_sample_colored",
+    "urgym_mppi_plan_colored",
+    "urgym_mppi_control_colored",
+    "urgym_mppi_collect_colored",
+    "urgym_sac_train_colored",
     "urgym_refresh",
     "urgym_invalidate_records",
     "urgym_derive_obstacle_motion",

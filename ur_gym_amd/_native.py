@@ -174,7 +174,19 @@ def lib():
     L.urgym_sac_train_tempered.argtypes = [C.c_void_p, C.POINTER(_abi.SacLearner), C.POINTER(_abi.SacSchedule), C.POINTER(_abi.SacPlanning),
                                            C.POINTER(_abi.MppiTemper), C.POINTER(_abi.SacClipping), C.POINTER(_abi.SacNstep), C.POINTER(_abi.SacPrioritized),
                                            C.POINTER(_abi.SacHindsight), C.POINTER(_abi.SacEvaluation), C.POINTER(_abi.SacMonitoring), C.c_void_p]
-    L.urgym_actor_read_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.urgym_mppi_sample_colored.argtypes = [C.c_void_p, C.POINTER(_abi.Mppi), C.POINTER(_abi.MppiNoise), C.POINTER(_abi.MppiAdapt), C.c_uint64, C.c_int, C.c_void_p]
+    L.urgym_mppi_plan_colored.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.Mppi), C.POINTER(_abi.MppiNoise), C.POINTER(_abi.MppiTemper),
+                                          C.POINTER(_abi.MppiAdapt), C.POINTER(_abi.MppiGuide), C.c_uint64, C.c_void_p]
+    L.urgym_mppi_control_colored.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.Mppi), C.POINTER(_abi.MppiNoise), C.POINTER(_abi.MppiTemper),
+                                             C.POINTER(_abi.MppiAdapt), C.POINTER(_abi.MppiGuide), C.c_uint64, C.c_int, C.POINTER(_abi.Trajectory), C.c_void_p]
+    L.urgym_mppi_collect_colored.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_abi.Mppi), C.POINTER(_abi.MppiNoise), C.POINTER(_abi.MppiTemper),
+                                             C.POINTER(_abi.MppiAdapt), C.POINTER(_abi.MppiGuide), C.POINTER(_abi.MppiExplore), C.c_uint64, C.c_int,
+                                             C.POINTER(_abi.ReplayRing), C.c_int, C.c_void_p]
+    L.urgym_sac_train_colored.argtypes = [C.c_void_p, C.POINTER(_abi.SacLearner), C.POINTER(_abi.SacSchedule), C.POINTER(_abi.SacPlanning),
+                                          C.POINTER(_abi.MppiNoise), C.POINTER(_abi.MppiTemper), C.POINTER(_abi.SacClipping), C.POINTER(_abi.SacNstep),
+                                          C.POINTER(_abi.SacPrioritized), C.POINTER(_abi.SacHindsight), C.POINTER(_abi.SacEvaluation),
+                                          C.POINTER(_abi.SacMonitoring), C.c_void_p]
+    L.urgym_actor_read_packed.argtypes =[C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.urgym_critic_read_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.urgym_refresh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.urgym_invalidate_records.argtypes = [C.c_void_p]

@@ -1,8 +1,8 @@
 // urgym_mppi_abi.hip -- the planner's entry points of include/urgym.h ("sampling-based MPC on the device", "MPPI with the learner in the
 // loop", "planner-collected experience", "elite samples and an adaptive std", "the planner inside the training call", "the temperature from a
-// target effective sample size"; DESIGN.md sections 26 to 31).  Host code only, beside
+// target effective sample size", "temporally correlated sampling noise"; DESIGN.md sections 26 to 32).  Host code only, beside
 // urgym_policy_abi.hip: every check is made here, before the first launch; every launch goes through urgym_mppi.h, urgym_mppi_guide.h,
-// urgym_mppi_collect.h, urgym_mppi_elite.h, urgym_mppi_temper.h, the actor's and the critic's own launches (urgym_actor.h, urgym_critic.h), the ring's store
+// urgym_mppi_collect.h, urgym_mppi_elite.h, urgym_mppi_temper.h, urgym_mppi_noise.h, the actor's and the critic's own launches (urgym_actor.h, urgym_critic.h), the ring's store
 // pass (urgym_replay.h) or through do_step of urgym_hip.hip (urgym_handle.h); the one exception is the device-to-device copy of new_std
 // into std between two iterations of an adaptive plan.  As there, each entry point is a checking half, which launches nothing, and a
 // launching half, which refuses nothing.
@@ -21,6 +21,7 @@
 #include "urgym_mppi_collect.h"
 #include "urgym_mppi_elite.h"
 #include "urgym_mppi_guide.h"
+#include "urgym_mppi_noise.h"
 #include "urgym_mppi_stats.h"
 #include "urgym_mppi_temper.h"
 #include "urgym_mppi_train.h"
@@ -265,10 +266,25 @@ int check_temper(Handle* report, const urgym_mppi* m, const urgym_mppi_temper* t
   return URGYM_OK;
 }
 
+// ---- temporally correlated sampling noise (urgym_mppi_noise), resolved by check_noise
+
+// the checks that concern urgym_mppi_noise.  `report` keeps the message.  The scale is formed here, on the host, once per call; std is
+// left null: plan() and the single launch put the adapt struct's there where the width is per element.
+int check_noise(Handle* report, const urgym_mppi_noise* z, const char* who, MppiNoise* out) {
+  static_assert(sizeof(urgym_mppi_noise) == 8 && alignof(urgym_mppi_noise) == 4, "include/urgym.h");
+  if (!z) return fail_in(report, URGYM_ERR_ARG, who, "null urgym_mppi_noise");
+  if (z->reserved0 != 0) return fail_in(report, URGYM_ERR_ARG, who, "urgym_mppi_noise.reserved0 must be 0");
+  if (!isfinite(z->beta) || z->beta < 0.0f || z->beta > 1.0f) return fail_in(report, URGYM_ERR_ARG, who, "urgym_mppi_noise.beta must be finite and in [0, 1]");
+  *out = MppiNoise{z->beta, mppi_noise_scale(z->beta), nullptr};
+  return URGYM_OK;
+}
+
 // the launches of one plan; everything has been checked.  gd == nullptr: the plain plan.  ad == nullptr: the plain update and sample;
 // else the elite update stands in place of the update and, with adapt_std, iterations >= 1 sample with new_std of the iteration before.
-// tp != nullptr: the tempered update stands in place of either update.
-int plan(Handle* sh, Handle* ph, const urgym_mppi& m, uint64_t draw, hipStream_t s, const Guide* gd = nullptr, const Adapt* ad = nullptr, const MppiTemper* tp = nullptr) {
+// tp != nullptr: the tempered update stands in place of either update.  nz != nullptr: the coloured sample stands in place of either
+// sample, after the same copy and with the std where the adaptive sample would have read it.
+int plan(Handle* sh, Handle* ph, const urgym_mppi& m, uint64_t draw, hipStream_t s, const Guide* gd = nullptr, const Adapt* ad = nullptr, const MppiTemper* tp = nullptr,
+         const MppiNoise* nz = nullptr) {
   const size_t row = (size_t)ph->cfg.num_envs * 6;
   const MppiFanout f = fanout_of(sh, ph, m);
   const MppiOutcome o = outcome_of(ph);
@@ -278,7 +294,10 @@ int plan(Handle* sh, Handle* ph, const urgym_mppi& m, uint64_t draw, hipStream_t
     if (ad && ad->adapt_std && i >= 1) {
       const size_t bytes = (size_t)m.horizon * (size_t)m.num_parents * 6 * sizeof(float);
       HIP_TRY(sh, hipMemcpyAsync(ad->std, ad->call.new_std, bytes, hipMemcpyDeviceToDevice, s));
-      mppi_sample_adaptive_launch(m, ad->call, draw, i, s);
+      if (nz) mppi_sample_colored_launch(m, MppiNoise{nz->beta, nz->scale, ad->call.std}, draw, i, s);
+      else mppi_sample_adaptive_launch(m, ad->call, draw, i, s);
+    } else if (nz) {
+      mppi_sample_colored_launch(m, *nz, draw, i, s);
     } else {
       mppi_sample_launch(m, draw, i, s);
     }
@@ -311,10 +330,10 @@ int plan(Handle* sh, Handle* ph, const urgym_mppi& m, uint64_t draw, hipStream_t
 // before the source step that reads action_out, and that step before the record pass that files its outcome and the fan-out that
 // clones its state.
 int control(Handle* sh, Handle* ph, const urgym_mppi& m, uint64_t first_draw, int num_steps, const urgym_trajectory* traj, hipStream_t s, const Guide* gd = nullptr,
-            const Adapt* ad = nullptr, const MppiTemper* tp = nullptr) {
+            const Adapt* ad = nullptr, const MppiTemper* tp = nullptr, const MppiNoise* nz = nullptr) {
   mppi_record_launch(record_of(sh, m, traj, 0, num_steps), s);
   for (int t = 0; t < num_steps; t++) {
-    if (int rc = plan(sh, ph, m, first_draw + (uint64_t)t, s, gd, ad, tp)) return rc;
+    if (int rc = plan(sh, ph, m, first_draw + (uint64_t)t, s, gd, ad, tp, nz)) return rc;
     if (int rc = do_step(sh, m.action_out, s)) return rc;
     mppi_record_launch(record_of(sh, m, traj, t + 1, num_steps), s);
   }
@@ -325,6 +344,30 @@ int control(Handle* sh, Handle* ph, const urgym_mppi& m, uint64_t first_draw, in
 int check_guided_pair(Handle* sh, Handle* ph, const urgym_mppi* m, const urgym_mppi_guide* g, const char* who, Guide* out) {
   if (int rc = check_pair(sh, ph, m, who)) return rc;
   return check_guide(sh, ph, m, g, who, out);
+}
+
+// what the three composed coloured calls resolve before their own checks: the pair, then the optional structs in the order of their
+// tempered kin, then the noise.  gd, ad and tp point into the struct where the option was given, else they are null.
+struct Colored {
+  Guide guide;
+  Adapt adapt;
+  MppiTemper temper;
+  MppiNoise nz;
+  const Guide* gd = nullptr;
+  const Adapt* ad = nullptr;
+  const MppiTemper* tp = nullptr;
+};
+
+int check_colored(Handle* sh, Handle* ph, const urgym_mppi* m, const urgym_mppi_noise* noise, const urgym_mppi_temper* temper, const urgym_mppi_adapt* adapt,
+                  const urgym_mppi_guide* guide, const char* who, Colored* c) {
+  if (int rc = guide ? check_guided_pair(sh, ph, m, guide, who, &c->guide) : check_pair(sh, ph, m, who)) return rc;
+  if (adapt)
+    if (int rc = check_adapt(sh, m, adapt, who, &c->adapt)) return rc;
+  if (temper)
+    if (int rc = check_temper(sh, m, temper, adapt, who, &c->temper)) return rc;
+  if (int rc = check_noise(sh, noise, who, &c->nz)) return rc;
+  c->gd = guide ? &c->guide : nullptr, c->ad = adapt ? &c->adapt : nullptr, c->tp = temper ? &c->temper : nullptr;
+  return URGYM_OK;
 }
 
 // the checks of the two single guided launches: the planner keeps the message
@@ -393,13 +436,14 @@ ReplayStore store_of(const Handle* h, const urgym_replay_ring& r, int first_slot
 // clones the source's state and reads mean, the plan's update before the execute launch that reads action_out, and that before the
 // source step that reads the slot's action rows.
 int collect(Handle* sh, Handle* ph, const urgym_mppi& m, const Guide* gd, const urgym_mppi_explore& x, uint64_t first_draw, int num_steps,
-            const urgym_replay_ring& ring, int first_slot, hipStream_t s, const Adapt* ad = nullptr, const MppiTemper* tp = nullptr) {
+            const urgym_replay_ring& ring, int first_slot, hipStream_t s, const Adapt* ad = nullptr, const MppiTemper* tp = nullptr,
+            const MppiNoise* nz = nullptr) {
   const size_t row = (size_t)sh->cfg.num_envs * 6, C = (size_t)ring.capacity_steps;
   for (int t = 0; t < num_steps; t++) {
     replay_store_launch(store_of(sh, ring, first_slot, t, num_steps), s);
     if (t > 0) mppi_record_launch(record_of(sh, m, nullptr, t, num_steps), s);
     const uint64_t draw = first_draw + (uint64_t)t;
-    if (int rc = plan(sh, ph, m, draw, s, gd, ad, tp)) return rc;
+    if (int rc = plan(sh, ph, m, draw, s, gd, ad, tp, nz)) return rc;
     float* actions = ring.action + (((size_t)first_slot + (size_t)t) % C) * row;  // the execute launch writes the slot, the step reads it
     mppi_execute_launch(execute_of(m, x, draw, actions), s);
     if (int rc = do_step(sh, actions, s)) return rc;
@@ -432,7 +476,7 @@ int check_stats(Handle* report, const urgym_mppi* m, const urgym_mppi_adapt* a, 
 namespace urgym {
 
 int planned_check(const char* who, Handle* h, const urgym_sac_planning* planning, const urgym_replay_ring* ring, const urgym_sac_schedule& S, PlannedCall* out,
-                  const urgym_mppi_temper* temper_or_NULL) {
+                  const urgym_mppi_temper* temper_or_NULL, const urgym_mppi_noise* noise_or_NULL) {
   static_assert(sizeof(urgym_sac_planning) == 72 && alignof(urgym_sac_planning) == 8, "include/urgym.h");
   if (!planning) return fail_in(h, URGYM_ERR_ARG, who, "null planning");
   const urgym_sac_planning& P = *planning;
@@ -457,6 +501,9 @@ int planned_check(const char* who, Handle* h, const urgym_sac_planning* planning
   MppiTemper tp;
   if (temper_or_NULL)
     if (int rc = check_temper(h, P.mppi, temper_or_NULL, P.adapt_or_NULL, who, &tp)) return rc;
+  MppiNoise nz;
+  if (noise_or_NULL)
+    if (int rc = check_noise(h, noise_or_NULL, who, &nz)) return rc;
   if (!h->observed) return fail_in(h, URGYM_ERR_STATE, who, "nothing has been observed yet: urgym_reset() or urgym_refresh() the source first");
   if (int rc = check_explore(h, &P.explore, who)) return rc;
   if (int rc = check_ring(h, ring, S.first_slot, K, who)) return rc;
@@ -470,11 +517,13 @@ int planned_check(const char* who, Handle* h, const urgym_sac_planning* planning
   if (c.adaptive) c.adapt = *P.adapt_or_NULL;
   c.tempered = temper_or_NULL != nullptr;
   if (c.tempered) c.temper = *temper_or_NULL;
+  c.colored = noise_or_NULL != nullptr;
+  if (c.colored) c.noise = *noise_or_NULL;
   *out = c;
   return URGYM_OK;
 }
 
-// planned_check has accepted the guide, the adapt and the temper struct: resolving them again refuses nothing
+// planned_check has accepted the guide, the adapt, the temper and the noise struct: resolving them again refuses nothing
 int planned_collect(const PlannedCall& c, uint64_t first_draw, int num_steps, int first_slot, hipStream_t s) {
   const char* who = "planned_collect";
   Guide gd;
@@ -486,8 +535,11 @@ int planned_collect(const PlannedCall& c, uint64_t first_draw, int num_steps, in
   MppiTemper tp;
   if (c.tempered)
     if (int rc = check_temper(c.source, &c.m, &c.temper, c.adaptive ? &c.adapt : nullptr, who, &tp)) return rc;
+  MppiNoise nz;
+  if (c.colored)
+    if (int rc = check_noise(c.source, &c.noise, who, &nz)) return rc;
   return collect(c.source, c.planner, c.m, c.guided ? &gd : nullptr, c.explore, first_draw, num_steps, c.ring, first_slot, s, c.adaptive ? &ad : nullptr,
-                 c.tempered ? &tp : nullptr);
+                 c.tempered ? &tp : nullptr, c.colored ? &nz : nullptr);
 }
 
 void planned_stats(const PlannedCall& c, urgym_mppi_stats_record* record, int64_t iteration, hipStream_t s) {
@@ -796,6 +848,64 @@ int urgym_mppi_collect_tempered(void* source_handle, void* planner_handle, const
   if (int rc = check_draw(sh, first_draw, num_steps, who)) return rc;
   HIP_TRY(sh, hipSetDevice(sh->device));
   if (int rc = collect(sh, ph, *m, guide_or_NULL ? &gd : nullptr, *x, first_draw, num_steps, *ring, first_slot, (hipStream_t)stream, adapt_or_NULL ? &ad : nullptr, &tp)) return rc;
+  return launched(sh);
+}
+
+int urgym_mppi_sample_colored(void* handle, const urgym_mppi* m, const urgym_mppi_noise* noise, const urgym_mppi_adapt* adapt_or_NULL, uint64_t draw, int iteration, void* stream) {
+  const char* who = "urgym_mppi_sample_colored";
+  Handle* h = (Handle*)handle;
+  Adapt ad;
+  MppiNoise nz;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (int rc = check_mppi(h, m, who)) return rc;
+  if (adapt_or_NULL)
+    if (int rc = check_adapt(h, m, adapt_or_NULL, who, &ad)) return rc;
+  if (int rc = check_noise(h, noise, who, &nz)) return rc;
+  if (int rc = check_draw(h, draw, 1, who)) return rc;
+  if (iteration < 0 || iteration >= URGYM_MPPI_ITERATIONS_MAX) return fail_in(h, URGYM_ERR_ARG, who, "iteration must be in [0, URGYM_MPPI_ITERATIONS_MAX)");
+  if (adapt_or_NULL) nz.std = ad.call.std;
+  HIP_TRY(h, hipSetDevice(h->device));
+  mppi_sample_colored_launch(*m, nz, draw, iteration, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_mppi_plan_colored(void* source_handle, void* planner_handle, const urgym_mppi* m, const urgym_mppi_noise* noise, const urgym_mppi_temper* temper_or_NULL, const urgym_mppi_adapt* adapt_or_NULL, const urgym_mppi_guide* guide_or_NULL, uint64_t draw, void* stream) {
+  const char* who = "urgym_mppi_plan_colored";
+  Handle *sh = (Handle*)source_handle, *ph = (Handle*)planner_handle;
+  Colored c;
+  if (!sh) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (int rc = check_colored(sh, ph, m, noise, temper_or_NULL, adapt_or_NULL, guide_or_NULL, who, &c)) return rc;
+  if (int rc = check_draw(sh, draw, 1, who)) return rc;
+  HIP_TRY(sh, hipSetDevice(sh->device));
+  if (int rc = plan(sh, ph, *m, draw, (hipStream_t)stream, c.gd, c.ad, c.tp, &c.nz)) return rc;
+  return launched(sh);
+}
+
+int urgym_mppi_control_colored(void* source_handle, void* planner_handle, const urgym_mppi* m, const urgym_mppi_noise* noise, const urgym_mppi_temper* temper_or_NULL, const urgym_mppi_adapt* adapt_or_NULL, const urgym_mppi_guide* guide_or_NULL, uint64_t first_draw, int num_steps, const urgym_trajectory* traj_or_NULL, void* stream) {
+  const char* who = "urgym_mppi_control_colored";
+  Handle *sh = (Handle*)source_handle, *ph = (Handle*)planner_handle;
+  Colored c;
+  if (!sh) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (int rc = check_colored(sh, ph, m, noise, temper_or_NULL, adapt_or_NULL, guide_or_NULL, who, &c)) return rc;
+  if (int rc = check_record(sh, 0, num_steps, traj_or_NULL, who)) return rc;
+  if (int rc = check_draw(sh, first_draw, num_steps, who)) return rc;
+  HIP_TRY(sh, hipSetDevice(sh->device));
+  if (int rc = control(sh, ph, *m, first_draw, num_steps, traj_or_NULL, (hipStream_t)stream, c.gd, c.ad, c.tp, &c.nz)) return rc;
+  return launched(sh);
+}
+
+int urgym_mppi_collect_colored(void* source_handle, void* planner_handle, const urgym_mppi* m, const urgym_mppi_noise* noise, const urgym_mppi_temper* temper_or_NULL, const urgym_mppi_adapt* adapt_or_NULL, const urgym_mppi_guide* guide_or_NULL, const urgym_mppi_explore* x, uint64_t first_draw, int num_steps, const urgym_replay_ring* ring, int first_slot, void* stream) {
+  const char* who = "urgym_mppi_collect_colored";
+  Handle *sh = (Handle*)source_handle, *ph = (Handle*)planner_handle;
+  Colored c;
+  if (!sh) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (int rc = check_colored(sh, ph, m, noise, temper_or_NULL, adapt_or_NULL, guide_or_NULL, who, &c)) return rc;
+  if (!sh->observed) return fail_in(sh, URGYM_ERR_STATE, who, "nothing has been observed yet: urgym_reset() or urgym_refresh() the source first");
+  if (int rc = check_explore(sh, x, who)) return rc;
+  if (int rc = check_ring(sh, ring, first_slot, num_steps, who)) return rc;
+  if (int rc = check_draw(sh, first_draw, num_steps, who)) return rc;
+  HIP_TRY(sh, hipSetDevice(sh->device));
+  if (int rc = collect(sh, ph, *m, c.gd, *x, first_draw, num_steps, *ring, first_slot, (hipStream_t)stream, c.ad, c.tp, &c.nz)) return rc;
   return launched(sh);
 }
 

@@ -19,7 +19,8 @@ struct PlannedCall {
   urgym_mppi_guide guide;  // with `guided`
   urgym_mppi_adapt adapt;  // with `adaptive`
   urgym_mppi_temper temper;  // with `tempered` (urgym_sac_train_tempered)
-  bool guided, adaptive, tempered;
+  urgym_mppi_noise noise;    // with `colored` (urgym_sac_train_colored)
+  bool guided, adaptive, tempered, colored;
   urgym_mppi_explore explore;
   urgym_replay_ring ring;
   Actor* sync_actor;    // the guide's actor where a plan launches it, else null: what planner_sync reloads
@@ -31,10 +32,11 @@ struct PlannedCall {
 
 // What urgym_sac_train_planned refuses about `planning` alone and what urgym_mppi_collect(_adaptive) refuses about the handles, mppi,
 // adapt, guide, explore, the ring and the draws of the whole call, and with temper_or_NULL what urgym_mppi_update_tempered refuses about
-// it; the schedule has been accepted.  `h` keeps the message.
+// it, and with noise_or_NULL what urgym_mppi_sample_colored refuses about it; the schedule has been accepted.  `h` keeps the message.
 int planned_check(const char* who, Handle* h, const urgym_sac_planning* planning, const urgym_replay_ring* ring, const urgym_sac_schedule& schedule, PlannedCall* out,
-                  const urgym_mppi_temper* temper_or_NULL = nullptr);
-// the launches of urgym_mppi_collect(_adaptive), or with a temper struct of urgym_mppi_collect_tempered
+                  const urgym_mppi_temper* temper_or_NULL = nullptr, const urgym_mppi_noise* noise_or_NULL = nullptr);
+// the launches of urgym_mppi_collect(_adaptive), with a temper struct of urgym_mppi_collect_tempered, with a noise struct of
+// urgym_mppi_collect_colored
 int planned_collect(const PlannedCall& call, uint64_t first_draw, int num_steps, int first_slot, hipStream_t s);
 // the launch of urgym_mppi_stats into `record`
 void planned_stats(const PlannedCall& call, urgym_mppi_stats_record* record, int64_t iteration, hipStream_t s);

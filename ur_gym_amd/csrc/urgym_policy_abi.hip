@@ -1760,6 +1760,7 @@ struct TrainOptions {
   const urgym_sac_monitoring* monitoring;  // TrainExtras
   const urgym_sac_planning* planning;      // the collection is the planner's (urgym_mppi_train.h), planner_sync after the updates, TrainExtras
   const urgym_mppi_temper* temper;         // with planning: the planner's update is the tempered one (urgym_sac_train_tempered)
+  const urgym_mppi_noise* noise;           // with planning: the planner's sample is the coloured one (urgym_sac_train_colored)
 };
 
 // The evaluations and the training-episode statistics of one training call: what the body runs beside its own checks and launches.
@@ -1936,7 +1937,7 @@ int sac_train_body(const char* who, Handle* h, const urgym_sac_learner* learner,
       return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_clipping.critic_grad_norm or actor_grad_norm is null");
   }
   if (planning) {  // the planner's own refusals and the collection's, whether or not the call holds an update
-    if (int rc = planned_check(who, h, planning, &L.ring, S, &planned, opt.temper)) return rc;
+    if (int rc = planned_check(who, h, planning, &L.ring, S, &planned, opt.temper, opt.noise)) return rc;
     if (planning->sync != 0) {  // planner_sync reloads the guide's actor and critic from the learner's tensors
       if (planned.sync_actor) {
         const ActorPacked buf = actor_packed(planned.sync_actor);
@@ -2252,7 +2253,7 @@ const char* const ONE_GATHER = "at most one of nstep, prioritized and hindsight 
 extern "C" {
 
 // Each entry point: the null handle, its own required option, then the driver with what it was given.  TrainOptions' order is
-// {nstep, per, her, clip, norm, evaluation, monitoring, planning, temper}.
+// {nstep, per, her, clip, norm, evaluation, monitoring, planning, temper, noise}.
 
 int urgym_sac_train(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, void* stream) {
   Handle* h = (Handle*)handle;
@@ -2335,6 +2336,16 @@ int urgym_sac_train_tempered(void* handle, const urgym_sac_learner* learner, con
   if (!temper) return fail_in(h, URGYM_ERR_ARG, who, "null urgym_mppi_temper");
   if ((nstep_or_NULL != nullptr) + (prioritized_or_NULL != nullptr) + (hindsight_or_NULL != nullptr) > 1) return fail_in(h, URGYM_ERR_ARG, who, ONE_GATHER);
   return sac_train_body(who, h, learner, schedule, (hipStream_t)stream, TrainOptions{nstep_or_NULL, prioritized_or_NULL, hindsight_or_NULL, clipping_or_NULL, nullptr, evaluation_or_NULL, monitoring_or_NULL, planning, temper});
+}
+
+int urgym_sac_train_colored(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_planning* planning, const urgym_mppi_noise* noise, const urgym_mppi_temper* temper_or_NULL, const urgym_sac_clipping* clipping_or_NULL, const urgym_sac_nstep* nstep_or_NULL, const urgym_sac_prioritized* prioritized_or_NULL, const urgym_sac_hindsight* hindsight_or_NULL, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream) {
+  const char* who = "urgym_sac_train_colored";
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (!planning) return fail_in(h, URGYM_ERR_ARG, who, "null planning");
+  if (!noise) return fail_in(h, URGYM_ERR_ARG, who, "null urgym_mppi_noise");
+  if ((nstep_or_NULL != nullptr) + (prioritized_or_NULL != nullptr) + (hindsight_or_NULL != nullptr) > 1) return fail_in(h, URGYM_ERR_ARG, who, ONE_GATHER);
+  return sac_train_body(who, h, learner, schedule, (hipStream_t)stream, TrainOptions{nstep_or_NULL, prioritized_or_NULL, hindsight_or_NULL, clipping_or_NULL, nullptr, evaluation_or_NULL, monitoring_or_NULL, planning, temper_or_NULL, noise});
 }
 
 }  // extern "C"

@@ -2627,6 +2627,33 @@ def mppi_noise(seed, draw, iteration, parents, samples, steps, dtype=np.float32)
     return eps
 
 
+def mppi_colored_noise(xi, beta):
+    """THE COLOURED SAMPLE's recurrence in numpy, bitwise (include/urgym.h, "temporally correlated sampling noise"): `xi` float32
+    [H, ...], THE SAMPLE's eps (``mppi_noise``), `beta` in [0, 1].  scale = float32(sqrt(1 - beta * beta)) with beta taken as float32
+    and everything up to the square root in float64; eps[0] = xi[0]; for h >= 1: a = beta * eps[h - 1]; b = scale * xi[h];
+    eps[h] = a + b, each one float32 operation.  Every step has unit variance and lag-1 correlation beta; the nominal sample's zeros
+    stay +0.0."""
+    xi = np.asarray(xi)
+    if xi.dtype != np.float32 or xi.ndim < 1:
+        raise ValueError(f"xi must be float32 [H, ...], got {xi.dtype} {xi.shape}")
+    with np.errstate(over="ignore"):
+        beta = np.float32(beta)
+    if not (np.isfinite(beta) and 0.0 <= beta <= 1.0):
+        raise ValueError(f"beta must be finite and in [0, 1], got {beta!r}")
+    b = np.float64(beta)
+    bb = b * b
+    d = np.float64(1.0) - bb
+    scale = np.float32(np.sqrt(d))
+    eps = np.empty_like(xi)
+    if xi.shape[0]:
+        eps[0] = xi[0]
+    for h in range(1, xi.shape[0]):
+        a = beta * eps[h - 1]
+        b = scale * xi[h]
+        eps[h] = a + b
+    return eps
+
+
 def mppi_actions(mean, eps, sigma):
     """THE SAMPLE's action line in numpy, bitwise: `mean` float32 [H, E, 6], `eps` float32 [H, E * K, 6]; planner env n = p * K + j reads
     parent p's mean.  s = sigma * eps; a = mean + s; action = fmin(fmax(a, -1), 1), each one float32 operation.  `sigma` is a number, or
@@ -3037,6 +3064,12 @@ class DeviceMPPI:
     gains ``lam`` (the temperature of the last update) and ``saturated`` (``_abi.MPPI_TEMPER_*``: 0 solved, 1 at `lam_max`, the target
     cannot be met, 2 at `lam_min`, 3 no finite return) [E]; with ``ess_target=None`` the planner makes exactly the calls it made before.
 
+    Temporally correlated sampling noise, opt-in.  `noise_beta` = beta in [0, 1]: the noise of every sample is a
+    first-order autoregressive sequence along the horizon on top of the same draws -- unit variance at every step, lag-1 correlation
+    beta (``mppi_colored_noise`` restates it) -- with whichever of the options above is set; ``eps`` holds the coloured values, so the
+    policy samples of a guide are correlated too.  The ``urgym_mppi_*_colored`` entry points are called and ``noise()`` is the struct;
+    ``noise_beta=0.0`` is a set option and goes through them; with ``noise_beta=None`` the planner makes exactly the calls it made before.
+
     Plan statistics.  ``stats()`` reduces the diagnostics of the last plan to one ``urgym_mppi_stats_record`` on
     the device; ``records`` is this planner's array of them (int64 [capacity, 11], grown by ``reserve_records``), which
     ``SACLearner.train(planner=, plan_stats=True)`` fills beside the monitor's records; ``planning()`` is the ``urgym_sac_planning`` of such
@@ -3046,7 +3079,7 @@ class DeviceMPPI:
 
     def __init__(self, env, samples=256, horizon=6, sigma=0.6, lam=5.0, gamma=1.0, iterations=1, shift=True, seed=0, keep_weights=False,
                  actor=None, critic=None, policy_samples=0, policy_sigma=0.0, terminal_value=False, fail_cost=0.0, elites=None, adapt_std=False,
-                 std_min=0.05, std_max=None, ess_target=None, lam_min=1e-3, lam_max=1e6, temper_steps=32):
+                 std_min=0.05, std_max=None, ess_target=None, lam_min=1e-3, lam_max=1e6, temper_steps=32, noise_beta=None):
         import ctypes as C
 
         import torch
@@ -3061,6 +3094,7 @@ class DeviceMPPI:
             raise ValueError(f"DeviceMPPI: sigma must be finite and >= 0, lam finite and > 0, gamma finite; got {sigma}, {lam}, {gamma}")
         adapt = self.check_adapt(K, sigma, elites, adapt_std, std_min, std_max)
         temper = self.check_temper(K if adapt is None else adapt[0], ess_target, lam_min, lam_max, temper_steps)
+        beta = self.check_noise(noise_beta)
         same = {name: getattr(env.cfg, name) for name, _ in _abi.Config._fields_ if name not in ("env_kind", "num_envs", "auto_reset", "check_collision")}
         self.env = env
         self.planner = UR5ReachVectorEnv(env.env_id, num_envs=E * K, device=env.device, auto_reset=False, check_collision=bool(env.cfg.check_collision), **same)
@@ -3095,6 +3129,7 @@ class DeviceMPPI:
                 setattr(T, name, C.cast(self.buf[name].data_ptr(), C.POINTER(ct)))
             self._temper = T
             self.DIAGNOSTICS = self.DIAGNOSTICS + ("lam", "saturated")
+        self._noise = None if beta is None else _abi.MppiNoise(beta, 0)
         self.records = torch.zeros((64, _abi.MPPI_STATS_RECORD_WORDS), dtype=torch.int64, device=env.device)  # [capacity] urgym_mppi_stats_record
         self.actor = self.critic = self._guide = None
         P = int(policy_samples)
@@ -3173,9 +3208,44 @@ class DeviceMPPI:
             raise ValueError(f"DeviceMPPI: temper_steps must be an integer in [1, {_abi.MPPI_TEMPER_STEPS_MAX}], got {temper_steps!r}")
         return float(ess_target), float(lam_min), float(lam_max), int(temper_steps)
 
+    @staticmethod
+    def check_noise(noise_beta=None):
+        """Raises ValueError for what the coloured entry points refuse about urgym_mppi_noise.beta.  Returns None where `noise_beta` is
+        None, else beta as the struct takes it (0.0 is a set option).  Needs no GPU."""
+        if noise_beta is None:
+            return None
+        with np.errstate(over="ignore"):
+            ok = not isinstance(noise_beta, bool) and bool(np.isfinite(np.float32(noise_beta))) and 0.0 <= float(np.float32(noise_beta)) <= 1.0
+        if not ok:
+            raise ValueError(f"DeviceMPPI: noise_beta must be finite and in [0, 1] (in float32), got {noise_beta!r}")
+        return float(noise_beta)
+
     def struct(self):
         """The ``urgym_mppi`` of this planner (its pointers stay valid until ``close``)."""
         return self._struct
+
+    def noise(self):
+        """The ``urgym_mppi_noise`` of this planner, or None where `noise_beta` was not given."""
+        return self._noise
+
+    def sample(self, draw=0, iteration=0, adaptive=False):
+        """The single sample launch into ``eps`` and ``actions`` from the mean as it stands: ``urgym_mppi_sample_colored`` with
+        `noise_beta` (with `adaptive`, the width is ``std``), else ``urgym_mppi_sample_adaptive`` with `adaptive`, else
+        ``urgym_mppi_sample``.  NOT synchronised."""
+        import ctypes as C
+
+        from . import _native
+
+        env = self.env
+        if adaptive and self._adapt is None:
+            raise ValueError("sample(adaptive=True) needs a planner made with elites or adapt_std")
+        adapt = C.byref(self._adapt) if adaptive else None
+        if self._noise is not None:
+            _native.check(env.lib.urgym_mppi_sample_colored(env._h, C.byref(self._struct), C.byref(self._noise), adapt, int(draw), int(iteration), env._stream()), env._h)
+        elif adaptive:
+            _native.check(env.lib.urgym_mppi_sample_adaptive(env._h, C.byref(self._struct), adapt, int(draw), int(iteration), env._stream()), env._h)
+        else:
+            _native.check(env.lib.urgym_mppi_sample(env._h, C.byref(self._struct), int(draw), int(iteration), env._stream()), env._h)
 
     def temper(self):
         """The ``urgym_mppi_temper`` of this planner, or None where `ess_target` was not given."""
@@ -3206,7 +3276,7 @@ class DeviceMPPI:
         return self._guide
 
     def plan(self, draw=0):
-        """One ``urgym_mppi_plan`` from the environment's state as it stands.  Returns (action_out [E, 6], diagnostics): views of this
+        """One ``urgym_mppi_plan`` (or its guided, adaptive, tempered or coloured kin, as the options ask) from the environment's state as it stands.  Returns (action_out [E, 6], diagnostics): views of this
         planner's buffers, overwritten by the next plan; diagnostics holds ``best_return``, ``nominal_return`` and ``ess`` [E], with
         elites or the adaptive std ``elite_count`` and ``threshold`` [E], and with `ess_target` ``lam`` and ``saturated`` [E].  NOT
         synchronised."""
@@ -3216,7 +3286,11 @@ class DeviceMPPI:
 
         env = self.env
         guide = None if self._guide is None else C.byref(self._guide)
-        if self._temper is not None:
+        if self._noise is not None:
+            _native.check(env.lib.urgym_mppi_plan_colored(env._h, self.planner._h, C.byref(self._struct), C.byref(self._noise),
+                                                          None if self._temper is None else C.byref(self._temper),
+                                                          None if self._adapt is None else C.byref(self._adapt), guide, int(draw), env._stream()), env._h)
+        elif self._temper is not None:
             _native.check(env.lib.urgym_mppi_plan_tempered(env._h, self.planner._h, C.byref(self._struct), C.byref(self._temper),
                                                            None if self._adapt is None else C.byref(self._adapt), guide, int(draw), env._stream()), env._h)
         elif self._adapt is not None:
@@ -3254,7 +3328,13 @@ class DeviceMPPI:
                 t = torch.zeros(shape(T, env.num_envs, env.obs_dim, env.goal_dim), dtype=_TORCH_DTYPE[ct], device=env.device)
                 setattr(traj, name, C.cast(t.data_ptr(), C.POINTER(ct)))
                 out[name] = t.view(torch.bool) if ct is C.c_uint8 else t
-        if self._temper is not None:
+        if self._noise is not None:
+            _native.check(env.lib.urgym_mppi_control_colored(env._h, self.planner._h, C.byref(self._struct), C.byref(self._noise),
+                                                             None if self._temper is None else C.byref(self._temper),
+                                                             None if self._adapt is None else C.byref(self._adapt),
+                                                             None if self._guide is None else C.byref(self._guide), int(first_draw), T,
+                                                             C.byref(traj) if names else None, env._stream()), env._h)
+        elif self._temper is not None:
             _native.check(env.lib.urgym_mppi_control_tempered(env._h, self.planner._h, C.byref(self._struct), C.byref(self._temper),
                                                               None if self._adapt is None else C.byref(self._adapt),
                                                               None if self._guide is None else C.byref(self._guide), int(first_draw), T,
@@ -3317,6 +3397,12 @@ class DeviceMPPI:
         replay.check_args(replay.capacity, num_steps=num_steps, first_slot=first)
         x = _abi.MppiExplore(self.check_explore(explore_sigma), 0, None)
         guide = None if self._guide is None else C.byref(self._guide)
+        if self._noise is not None:
+            _native.check(env.lib.urgym_mppi_collect_colored(env._h, self.planner._h, C.byref(self._struct), C.byref(self._noise),
+                                                             None if self._temper is None else C.byref(self._temper),
+                                                             None if self._adapt is None else C.byref(self._adapt), guide, C.byref(x),
+                                                             int(first_draw), int(num_steps), C.byref(replay._ring), int(first), env._stream()), env._h)
+            return
         if self._temper is not None:
             _native.check(env.lib.urgym_mppi_collect_tempered(env._h, self.planner._h, C.byref(self._struct), C.byref(self._temper),
                                                               None if self._adapt is None else C.byref(self._adapt), guide, C.byref(x),

@@ -61,7 +61,8 @@ minibatch gather on the HIP kernels, and gradients and optimisers in torch autog
     ``explore_sigma`` times exploration noise, and the transitions land in the same ring slots, so ``update`` trains on them as they stand
     (SAC is off-policy); ``sync_planner`` puts the planner's actor and critic on the learner's current parameters.  Not with ``normalize``.
     ``train(planner=)`` runs that loop -- the planned collection, the updates, ``sync_planner`` -- inside the one native call
-    (urgym_sac_train_planned, or urgym_sac_train_tempered for a planner made with ``ess_target=``; DESIGN.md sections 30 and 31), and with
+    (urgym_sac_train_planned, urgym_sac_train_tempered for a planner made with ``ess_target=``, urgym_sac_train_colored for one made with
+    ``noise_beta=``; DESIGN.md sections 30 to 32), and with
     ``plan_stats=True`` keeps a record of how the plans went beside every
     record of the monitor.
     None of them synchronises with the host.  ``train`` runs the whole loop in one native call and, given an

@@ -64,12 +64,19 @@ _SAC_TRAIN_ENTRIES = (
     ("urgym_sac_train", None, ()),
 )
 
+# The entry points ``sac_train`` tries ahead of that table, in the same form: a planner with coloured sampling noise
+# goes to urgym_sac_train_colored whatever else is given; its temper struct, like every option after it, may be absent.
+_SAC_TRAIN_ENTRIES_AHEAD = (
+    ("urgym_sac_train_colored", "noise", ("planner", "noise", "temper", "clipping", "nstep", "prioritized", "hindsight", "evaluation", "monitor")),
+)
+
 
 def _sac_train_entry(present):
     """(symbol, option names) of the entry point that serves a call with the options in `present` (any container of names out of
     evaluation, monitor, nstep, prioritized, hindsight, clipping, normalizer, planner, temper -- the planner's temper struct, given where
-    the planner has an ess_target): the first row of ``_SAC_TRAIN_ENTRIES`` whose option is given."""
-    for symbol, selects, options in _SAC_TRAIN_ENTRIES:
+    the planner has an ess_target -- and noise, its noise struct, given where it has a noise_beta): the first row of
+    ``_SAC_TRAIN_ENTRIES_AHEAD``, then of ``_SAC_TRAIN_ENTRIES``, whose option is given."""
+    for symbol, selects, options in _SAC_TRAIN_ENTRIES_AHEAD + _SAC_TRAIN_ENTRIES:
         if selects is None or selects in present:
             return symbol, options
 
@@ -1037,6 +1044,8 @@ class UR5ReachVectorEnv:
             given["planner"] = mppi.planning(planner.get("explore_sigma", 0.0), planner.get("sync", True), planner.get("records", False))
             if mppi.temper() is not None:
                 given["temper"] = mppi.temper()
+            if mppi.noise() is not None:
+                given["noise"] = mppi.noise()
         symbol, options = _sac_train_entry(given)
         try:
             _native.check(getattr(self.lib, symbol)(self._h, C.byref(L), C.byref(S), *[C.byref(given[o]) if o in given else None for o in options], self._stream()), self._h)
