@@ -882,6 +882,51 @@ typedef struct urgym_sac_policy_args {
  * group is absent: leave it 0). */
 int urgym_sac_policy_terms(void* handle, const urgym_sac_policy_args* args, void* stream);
 
+/* ---- behaviour cloning in the policy loss, with a Q-filter.  SAC's policy loss, alpha log pi - min Q, sees the
+ * actions of the replay ring only through the critic; a learner fed by a planner or by demonstrations also wants a pull of the policy's
+ * action towards the action the ring holds (TD3+BC, Fujimoto & Gu 2021; the Q-filter of Nair et al. 2018).  urgym_sac_policy_terms_cloned
+ * is urgym_sac_policy_terms with that pull added to d_action_out: still ONE launch of ONE workgroup of 1024 lanes, in its place.  Added
+ * WITHIN ABI version 4: no struct above changed, URGYM_ABI_VERSION did not move, the new symbols (urgym_sac_policy_terms_cloned,
+ * urgym_sac_train_cloned) are found by lookup.  All pointers are DEVICE pointers, all required. */
+typedef struct urgym_sac_clone_args {
+  const float* action_pi;    /* [count][6], the policy's sampled, squashed action on the batch rows */
+  const float* action_data;  /* [count][6], the action the replay ring holds for the row: the one that was executed */
+  float weight;              /* finite, >= 0 */
+  float bc_scale;            /* finite (a learner passes 1 / count) */
+  int32_t scale_by_q;        /* 0 or 1 */
+  int32_t q_filter;          /* 0 or 1 */
+  float* bc_loss_out;        /* [1] */
+  float* bc_weight_out;      /* [1] */
+  int32_t* bc_rows_out;      /* [1] */
+  int32_t reserved0;         /* must be 0 */
+} urgym_sac_clone_args;
+
+/* With q = args->q (the ONLINE critics at the REPLAYED action, [2][count]) and q_min = args->q_min (at the policy's action):
+ *   phase 1, per row m (lane t takes rows t, t + 1024, ...):
+ *     qd        = q[1][m] < q[0][m] ? q[1][m] : q[0][m]
+ *     cloned[m] = q_filter ? (qd > q_min[m]) : true            a NaN on either side, or a tie, gives not cloned
+ *     for k = 0..5 ascending:  d_k = action_pi[m][k] - action_data[m][k];  p = d_k * d_k;  s = s + p      (s starts at +0.0f)
+ *     h[m]      = 0.5f * s where the row is cloned, +0.0f where it is not
+ *     absq[m]   = fabsf(q_min[m])                              over ALL rows
+ *     mean_abs  = ordered mean of absq      bc_loss = ordered mean of h over all count rows      rows = the number of cloned rows
+ *     the three sums of urgym_sac_policy_terms are formed as there
+ *   scalar:  w = scale_by_q ? weight * mean_abs : weight       one float32 product; mean_abs is a constant of the step (TD3+BC's
+ *            normalisation written as a weight on the cloning term instead of 1 / lambda on Q: no division)
+ *   phase 2, per element:
+ *     g = dqmin_da[m][k] * scale                               urgym_sac_policy_terms' line
+ *     not cloned:  d_action_out[m][k] = g                      bitwise what urgym_sac_policy_terms writes
+ *     cloned:      t = d_k * w;  u = t * bc_scale;  d_action_out[m][k] = g + u
+ *   The two actions are read again in phase 2; nothing per row is stored between the phases.  d_action_out may be dqmin_da itself.
+ *   critic_loss_out and actor_loss_out are bitwise urgym_sac_policy_terms'; bc_loss_out[0] = bc_loss, bc_weight_out[0] = w,
+ *   bc_rows_out[0] = rows.  With weight = 0 a cloned element is g + (+-0): equal to g, though a -0.0 g may become +0.0.
+ * A NaN in action_pi or action_data of a cloned row reaches that row of d_action_out and bc_loss_out; a NaN in q_min reaches w only with
+ * scale_by_q, and through w every cloned row; a row that is not cloned is touched by neither.
+ *
+ * Refused (URGYM_ERR_ARG, nothing is launched, nothing is written): everything urgym_sac_policy_terms refuses; any of its three groups
+ * absent (this call needs all three); NULL clone args or any NULL pointer in them; weight not finite or < 0; bc_scale not finite;
+ * scale_by_q or q_filter other than 0 or 1; reserved0 != 0; d_action_out equal to action_pi or action_data. */
+int urgym_sac_policy_terms_cloned(void* handle, const urgym_sac_policy_args* args, const urgym_sac_clone_args* clone, void* stream);
+
 /* ---- the SAC training loop in ONE call (train.py:40-60: model.learn(total_timesteps) alternates collection and gradient steps and
  * does not return to the caller in between).  urgym_sac_train enqueues num_iterations x (one collection, G updates) of the calls
  * above on `stream`: no new kernel, no new arithmetic, only the host side of the existing launches, checked once.  Added WITHIN ABI
@@ -2285,6 +2330,28 @@ int urgym_mppi_collect_colored(void* source_handle, void* planner_handle, const 
  * temper_or_NULL: urgym_sac_train_tempered) states it.  Refused: what that call refuses (the message names urgym_sac_train_colored), and
  * what urgym_mppi_sample_colored refuses about noise. */
 int urgym_sac_train_colored(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_planning* planning, const urgym_mppi_noise* noise, const urgym_mppi_temper* temper_or_NULL, const urgym_sac_clipping* clipping_or_NULL, const urgym_sac_nstep* nstep_or_NULL, const urgym_sac_prioritized* prioritized_or_NULL, const urgym_sac_hindsight* hindsight_or_NULL, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream);
+
+/* ---- the training call with behaviour cloning: in every update the launch of urgym_sac_policy_terms is the one
+ * of urgym_sac_policy_terms_cloned, with action_pi = learner->action_pi, action_data = learner->batch.action (the ring's action: the
+ * executed one, under every gather), bc_scale = (float)(1.0 / M), and weight, scale_by_q and q_filter as given here.  Update u of the call
+ * writes slot u of bc_loss, bc_weight and bc_rows.  Nothing else in the sequence moves: an update stays thirteen launches (more with
+ * the other options, as they state), and the actor's backward pass, Adam, the ring and the planner are unchanged. */
+typedef struct urgym_sac_cloning {
+  float weight;        /* finite, >= 0 */
+  int32_t scale_by_q;  /* 0 or 1 */
+  int32_t q_filter;    /* 0 or 1 */
+  int32_t reserved0;   /* must be 0 */
+  float* bc_loss;      /* [updates of the call] */
+  float* bc_weight;    /* the same */
+  int32_t* bc_rows;    /* the same */
+} urgym_sac_cloning;
+
+/* Every option after `cloning` may be NULL and is then as in the call without it: planning (with temper and noise, which need it),
+ * normalization, clipping, at most one of nstep, prioritized and hindsight, evaluation, monitoring.  Refused, nothing launched (the
+ * message names urgym_sac_train_cloned): NULL cloning; what urgym_sac_policy_terms_cloned refuses about weight, the two flags and
+ * reserved0; a NULL bc_loss, bc_weight or bc_rows where the call holds an update; temper or noise without planning; normalization
+ * together with planning; and what the call with the same options and no cloning refuses. */
+int urgym_sac_train_cloned(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_cloning* cloning, const urgym_sac_planning* planning_or_NULL, const urgym_mppi_temper* temper_or_NULL, const urgym_mppi_noise* noise_or_NULL, const urgym_normalization* normalization_or_NULL, const urgym_sac_clipping* clipping_or_NULL, const urgym_sac_nstep* nstep_or_NULL, const urgym_sac_prioritized* prioritized_or_NULL, const urgym_sac_hindsight* hindsight_or_NULL, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream);
 
 /* Replaces Reach*.set_goal / set_goal_and_obstacle (reach.py:202-204, 328-335, 702-713): the caller has
  * overwritten goal / obst_start / obst_end (and possibly q) for the masked envs; this recomputes obstacle pose,

@@ -73,6 +73,13 @@ clipped route; the unclipped one is compared with the parent commit's --entropy 
 clipped native updates alone: the program of a kernel-trace run.
     python tools/bench_policy_rollout.py --clip --windows 8 --launches 200 --out profiles/policy_rollout/dyn65536_clip.json
 
+--clone measures behaviour cloning in the policy terms.  First the launch alone: urgym_sac_policy_terms against
+urgym_sac_policy_terms_cloned (weight 1, scale_by_q and q_filter on) on the same seeded device tensors at M = 256 and M = 65536, --launches
+back-to-back launches per window between two device events and a synchronise, the two alternating, median of --windows; both and the
+difference are reported, no bound is fixed.  Then the update as in --clip: the learner without the option against the one with
+bc_weight=1, bc_scale_by_q, bc_q_filter, as update() calls and as one native call per window, alternating; both and the differences.
+    python tools/bench_policy_rollout.py --clone --windows 10 --launches 200 --out profiles/policy_rollout/bc_time.json
+
 --normalize measures running normalization.  The update as in --clip: `device_entropy`, the learner without the
 option (the thirteen calls it always made), against `normalized` (fourteen: one urgym_norm_batch after the gather), and the same pair as
 ONE SACLearner.train call per window.  Then, at --num-envs envs, a collection step without and with the normalize launch
@@ -1056,6 +1063,113 @@ def clip_mode(args):
     env.close()
 
 
+def clone_mode(args):
+    """--clone: urgym_sac_policy_terms against urgym_sac_policy_terms_cloned at two batch sizes, and the update without and with the option
+    (see above)."""
+    import torch
+
+    from ur_gym_amd import make_vec
+    from ur_gym_amd.evaluation import DeviceReplay
+    from ur_gym_amd.training import SACLearner
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_policy_rollout.py measures on a GPU; none is visible")
+    dev, n, per_window = "cuda:0", min(args.num_envs, 4096), args.launches
+    env = make_vec(args.env, num_envs=n, device=dev, seed=0, auto_reset=True)
+    env.reset(seed=0)
+    sync = lambda: torch.cuda.synchronize(env.device)  # noqa: E731
+    launch = {}
+    for M in (256, 65536):
+        rng = np.random.default_rng(M)
+        t = {k: torch.from_numpy(rng.standard_normal(shape).astype(np.float32)).to(dev)
+             for k, shape in dict(dqmin_da=(M, 6), q=(2, M), y=(M,), log_prob=(M,), q_min=(M,), action_pi=(M, 6), action_data=(M, 6)).items()}
+        t["action_pi"], t["action_data"] = torch.tanh(t["action_pi"]), torch.tanh(t["action_data"])
+        out = {k: torch.zeros(shape, dtype=torch.float32, device=dev) for k, shape in dict(d_action=(M, 6), critic_loss=(1,), actor_loss=(1,), bc_loss=(1,), bc_weight=(1,)).items()}
+        out["bc_rows"], ent_coef = torch.zeros((1,), dtype=torch.int32, device=dev), torch.full((1,), 0.2, dtype=torch.float32, device=dev)
+        common = dict(dqmin_da=t["dqmin_da"], scale=-1.0 / M, d_action_out=out["d_action"], q=t["q"], y=t["y"], critic_loss_out=out["critic_loss"],
+                      log_prob=t["log_prob"], q_min=t["q_min"], actor_loss_out=out["actor_loss"])
+        calls = {"policy_terms": lambda: env.policy_terms(ent_coef, M, **common),
+                 "policy_terms_cloned": lambda: env.policy_terms_cloned(ent_coef, M, **common, action_pi=t["action_pi"], action_data=t["action_data"], weight=1.0,
+                                                                       bc_scale=1.0 / M, scale_by_q=True, q_filter=True, bc_loss_out=out["bc_loss"],
+                                                                       bc_weight_out=out["bc_weight"], bc_rows_out=out["bc_rows"])}
+
+        def window(call):
+            first, last = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            sync()
+            t0 = time.perf_counter()
+            first.record()
+            for _ in range(per_window):
+                call()
+            last.record()
+            sync()
+            return first.elapsed_time(last) * 1e3 / per_window, (time.perf_counter() - t0) * 1e6 / per_window
+
+        for call in calls.values():
+            for _ in range(20):
+                call()
+        wdw = {k: [] for k in calls}
+        for _ in range(args.windows):
+            for k, call in calls.items():
+                wdw[k].append(window(call))
+        sync()
+        med = {k: float(np.median([w[0] for w in v])) for k, v in wdw.items()}
+        launch[str(M)] = {"us_per_launch_device_events_median": med, "us_per_launch_wall_median": {k: float(np.median([w[1] for w in v])) for k, v in wdw.items()},
+                          "us_per_launch_device_events_min": {k: float(min(w[0] for w in v)) for k, v in wdw.items()},
+                          "us_per_launch_device_events_max": {k: float(max(w[0] for w in v)) for k, v in wdw.items()},
+                          "cloned_minus_plain_us": med["policy_terms_cloned"] - med["policy_terms"], "cloned_rows": int(out["bc_rows"].item())}
+
+    options = dict(device_action_gradient=True, device_critic_gradient=True, device_actor_gradient=True, device_optimizer=True, device_entropy=True)
+    bc = dict(bc_weight=1.0, bc_scale_by_q=True, bc_q_filter=True)
+    routes = {"device_entropy": (False, {}), "cloned": (False, bc), "native": (True, {}), "native_cloned": (True, bc)}
+    learners = {}
+    for label, (native, extra) in routes.items():
+        learner = SACLearner(env, seed=0, batch_size=256, hidden_width=256, learning_starts=0, **options, **extra)
+        replay = DeviceReplay(env, 64)
+        learner.collect(replay, 4)
+        learners[label] = (learner, replay, [0], native)
+
+    def updates(label, count):
+        learner, replay, draw, native = learners[label]
+        if native:
+            learner.train(replay, 1, 0, count, seed=1, first_draw=draw[0] + 1)
+            draw[0] += count
+        else:
+            for _ in range(count):
+                draw[0] += 1
+                learner.update(replay, 1, draw[0])
+
+    def update_window(label):
+        sync()
+        t0 = time.perf_counter()
+        updates(label, per_window)
+        sync()
+        return (time.perf_counter() - t0) * 1e6 / per_window
+
+    for label in learners:
+        updates(label, 10)
+    wdw = {label: [] for label in learners}
+    for _ in range(args.windows):
+        for label in learners:
+            wdw[label].append(update_window(label))
+    med = {k: float(np.median(v)) for k, v in wdw.items()}
+    last = learners["cloned"][0].last_update
+    result = {"tool": "bench_policy_rollout --clone", "env": args.env, "num_envs": n, "windows": args.windows, "launches_per_window": per_window,
+              "device": torch.cuda.get_device_name(0), "launch": launch, "update": {
+                  "batch": 256, "hidden_width": 256, "options": bc, "us_per_update_median": med, "us_per_update_min": {k: float(min(v)) for k, v in wdw.items()},
+                  "us_per_update_max": {k: float(max(v)) for k, v in wdw.items()}, "us_per_update_windows": {k: [round(x, 2) for x in v] for k, v in wdw.items()},
+                  "cloned_minus_device_entropy_us": med["cloned"] - med["device_entropy"], "native_cloned_minus_native_us": med["native_cloned"] - med["native"],
+                  "last_update": {"bc_loss": float(last["bc_loss"][0]), "bc_weight": float(last["bc_weight"][0]), "bc_rows": int(last["bc_rows"][0])}}}
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    for learner, _, _, _ in learners.values():
+        learner.close()
+    env.close()
+
+
 def normalize_mode(args):
     """--normalize: the update without and with normalize, the collection step without and with the normalize launch, the fold (see above)."""
     import torch
@@ -1826,6 +1940,7 @@ def main():
     ap.add_argument("--optimizer", action="store_true", help="measure the Adam step kernels (one launch each) against torch's Adam.step followed by the reloads, and the learner's update with and without them")
     ap.add_argument("--entropy", action="store_true", help="measure the learner's update with device_optimizer only against the same plus device_entropy (see above)")
     ap.add_argument("--clip", action="store_true", help="measure the update with max_grad_norm against the update without it, as update() calls and as one native call per window (see above)")
+    ap.add_argument("--clone", action="store_true", help="measure urgym_sac_policy_terms_cloned against urgym_sac_policy_terms at M = 256 and 65536, and the update with and without bc_weight (see above)")
     ap.add_argument("--normalize", action="store_true", help="measure the update with normalize against the update without it, the collection step without and with the normalize launch, and the fold (see above)")
     ap.add_argument("--normalize-only", action="store_true", help="--normalize: run only the normalized collection, the fold and the normalized native updates (for a kernel trace)")
     ap.add_argument("--collect-steps", type=int, default=8, help="--normalize: steps per collection and per fold")
@@ -1853,6 +1968,8 @@ def main():
         return monitor_mode(args)
     if args.evaluate:
         return evaluate_mode(args)
+    if args.clone:
+        return clone_mode(args)
     if args.clip or args.clip_only:
         return clip_mode(args)
     if args.normalize or args.normalize_only:

@@ -44,6 +44,11 @@ used only by an env without a finite return.  With --monitor the last line of pl
 the temperatures its last plan left and how many envs ended at a bound, read on the host after the call's synchronise.
 --planner-noise-beta B gives the planner's sampling noise a lag-1 correlation of B along the horizon (DeviceMPPI(noise_beta=),
 urgym_mppi_*_colored and with --native urgym_sac_train_colored); 0 is white noise through the same calls.
+--bc-weight X adds behaviour cloning to the policy loss (SACLearner(bc_weight=X), needs --device-entropy): the
+policy's action is pulled towards the action the ring holds -- the planner's, with --planner -- with weight X, or with --bc-scale-by-q X
+times the batch's mean |min Q| (TD3+BC's normalisation), on every row or with --bc-q-filter on the rows where the critics rate the ring's
+action above the policy's own; with --native urgym_sac_train_cloned.  Every evaluation line then also carries the three losses, bc_loss,
+bc_weight and the cloned share of the batch of the latest update.
 """
 import argparse
 import json
@@ -98,6 +103,11 @@ def main():
     ap.add_argument("--max-grad-norm", type=float, default=None, metavar="X",
                     help="clip the critics' and the actor's gradients by their global norm on the device (torch's clip_grad_norm_ idiom; SB3's SAC "
                          "does not clip) and print the losses and the norms with every evaluation (needs --device-entropy)")
+    ap.add_argument("--bc-weight", type=float, default=None, metavar="X",
+                    help="behaviour cloning in the policy loss: pull the policy's action towards the ring's with weight X >= 0 and print bc_loss and the "
+                         "cloned share with the losses (needs --device-entropy; DESIGN.md section 33)")
+    ap.add_argument("--bc-scale-by-q", action="store_true", help="--bc-weight: multiply the weight by the batch's mean |min Q| (TD3+BC's normalisation)")
+    ap.add_argument("--bc-q-filter", action="store_true", help="--bc-weight: clone only the rows where the critics rate the ring's action above the policy's own")
     ap.add_argument("--normalize", action="store_true",
                     help="running observation and reward normalization on the device (SB3's VecNormalize; needs --device-entropy)")
     ap.add_argument("--no-norm-obs", action="store_true", help="--normalize: leave the observations as they are")
@@ -151,6 +161,8 @@ def main():
     args = ap.parse_args()
     if args.planner and args.normalize:
         raise SystemExit("--planner plans on raw rows: not with --normalize (the planner's actor and critic read raw rows)")
+    if (args.bc_scale_by_q or args.bc_q_filter) and args.bc_weight is None:
+        raise SystemExit("--bc-scale-by-q and --bc-q-filter qualify --bc-weight and need it")
     if args.save_every and not args.save:
         raise SystemExit("--save-every needs --save")
     if args.save_every < 0:
@@ -176,6 +188,7 @@ def main():
                          **(dict(prioritized=True, per_beta=args.per_beta, per_beta_steps=args.per_beta_steps) if args.prioritized else {}),
                          **(dict(hindsight=True, her_n_sampled_goal=args.her_n_sampled_goal, her_strategy=args.her_strategy) if args.hindsight else {}),
                          **(dict(max_grad_norm=args.max_grad_norm) if args.max_grad_norm is not None else {}),
+                         **(dict(bc_weight=args.bc_weight, bc_scale_by_q=args.bc_scale_by_q, bc_q_filter=args.bc_q_filter) if args.bc_weight is not None else {}),
                          **(dict(normalize=True, norm_obs=not args.no_norm_obs, norm_reward=not args.no_norm_reward, clip_obs=args.clip_obs,
                                  clip_reward=args.clip_reward, norm_epsilon=args.norm_epsilon) if args.normalize else {}))
     normalizer = learner.normalizer  # None without --normalize
@@ -198,16 +211,25 @@ def main():
         raise SystemExit("--log-every must be at least 1")
     mon = DeviceMonitor(env, capacity=max(1, args.steps // args.log_every)) if args.monitor else None
 
-    latest = {}  # --max-grad-norm on the Python route: the losses the latest update returned (device tensors)
+    latest = {}  # --max-grad-norm, --bc-weight on the Python route: the losses the latest update returned (device tensors)
+    with_losses = args.max_grad_norm is not None or args.bc_weight is not None  # the evaluation lines carry the latest update's values
+
+    def cloned_share(values):
+        """bc_rows of a line becomes the share of the batch that was cloned."""
+        if "bc_rows" in values:
+            values["bc_cloned_share"] = values.pop("bc_rows") / args.batch_size
+        return values
 
     def evaluate():
         eval_actor.load_parameters(learner.actor.tensors())
         test_env.reset(seed=args.seed + 1)
         res = run_closed_loop_device(test_env, eval_actor, **(dict(normalizer=normalizer) if normalizer is not None and not args.no_norm_obs else {}))
         norms = {}
-        if args.max_grad_norm is not None:  # the run is synchronised here anyway
+        if with_losses:  # the run is synchronised here anyway
             norms = {k: float(v) for k, v in latest.items()}
-            norms.update({k: float(learner.last_update[k][0]) for k in ("critic_grad_norm", "actor_grad_norm")})
+            keys = (("critic_grad_norm", "actor_grad_norm") if args.max_grad_norm is not None else ()) + (("bc_loss", "bc_weight", "bc_rows") if args.bc_weight is not None else ())
+            norms.update({k: float(learner.last_update[k][0]) for k in keys})
+            cloned_share(norms)
         if args.save_best and res["mean_episode_reward"] > best["mean"]:  # strictly above, as the reference's EvalCallback decides
             best.update(mean=res["mean_episode_reward"], tensors=host_arrays(learner.actor.tensors()))
             if normalizer is not None:  # the statistics it was selected under, as DeviceEvaluation.save_best writes them
@@ -267,14 +289,14 @@ def main():
         # one call for the whole run -- or, with --save-every, one per stretch between two checkpoints: split calls are bit for bit the
         # single one (the schedule's counters are handed on), so the checkpoints cost the launches nothing but their own copies
         stretch = max(1, -(-args.save_every // max(1, args.updates_per_step))) if args.save_every else max(1, args.steps)
-        first_update, curves = updates, []  # --max-grad-norm: the losses and norms of every update of this process, one entry per call
+        first_update, curves = updates, []  # --max-grad-norm, --bc-weight: the losses, norms and cloning values of every update of this process, one entry per call
         while step < args.steps:
             n = min(stretch, args.steps - step)
             got = learner.train(replay, n, 1, args.updates_per_step, seed=args.seed, first_draw=updates, evaluation=ev, eval_every=args.eval_every,
                                 **(dict(monitor=mon, log_every=args.log_every) if mon is not None else {}),
                                 **(dict(planner=planner, explore_sigma=args.planner_explore_sigma, plan_stats=mon is not None) if planner is not None else {}))
-            if args.max_grad_norm is not None:
-                curves.append(got)
+            if with_losses:
+                curves.append({k: v for k, v in got.items() if k != "plan_stats"})
             step, updates = step + n, learner.adam_state["step"]
             if args.save and (args.save_every or step == args.steps):
                 save(step)
@@ -283,7 +305,7 @@ def main():
         for trip, rec in list(zip(points, ev.results()))[shown_evals:]:  # results() synchronises, once
             seconds = round(time.perf_counter() - t0, 1) if seconds is None else seconds
             done = max(0, trip + 1 - idle) * args.updates_per_step
-            norms = {k: float(v[done - 1 - first_update]) for k, v in curve.items()} if curve and done - 1 >= first_update else {}
+            norms = cloned_share({k: float(v[done - 1 - first_update]) for k, v in curve.items()}) if curve and done - 1 >= first_update else {}
             print(json.dumps({"updates": done, "env_steps": (trip + 1) * env.num_envs, "seconds": seconds, "mean_episode_return": rec["mean_return"],
                               "success_rate_percent": 100.0 * rec["success_rate"], "std_episode_return": rec["std_return"],
                               "mean_episode_length": rec["mean_length"], "improved": bool(rec["improved"]), **norms}), flush=True)

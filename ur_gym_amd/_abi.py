@@ -655,6 +655,21 @@ class MppiNoise(C.Structure):
     _fields_ = [("beta", C.c_float), ("reserved0", C.c_int32)]
 
 
+class SacCloneArgs(C.Structure):
+    """urgym_sac_clone_args: what urgym_sac_policy_terms_cloned takes beside urgym_sac_policy_args -- the two actions, the weight and its
+    two flags, the three [1] outputs.  All pointers required."""
+    _fields_ = [("action_pi", C.POINTER(C.c_float)), ("action_data", C.POINTER(C.c_float)), ("weight", C.c_float), ("bc_scale", C.c_float),
+                ("scale_by_q", C.c_int32), ("q_filter", C.c_int32), ("bc_loss_out", C.POINTER(C.c_float)), ("bc_weight_out", C.POINTER(C.c_float)),
+                ("bc_rows_out", C.POINTER(C.c_int32)), ("reserved0", C.c_int32)]
+
+
+class SacCloning(C.Structure):
+    """urgym_sac_cloning: the option of urgym_sac_train_cloned -- the weight, its two flags and one slot per update of the call each for
+    the cloning loss, the weight used and the number of cloned rows."""
+    _fields_ = [("weight", C.c_float), ("scale_by_q", C.c_int32), ("q_filter", C.c_int32), ("reserved0", C.c_int32),
+                ("bc_loss", C.POINTER(C.c_float)), ("bc_weight", C.POINTER(C.c_float)), ("bc_rows", C.POINTER(C.c_int32))]
+
+
 # Every symbol include/urgym.h declares (tests check that the built library exports each of them).
 EXPORTED_SYMBOLS = [
     "urgym_abi_version",
@@ -757,6 +772,8 @@ EXPORTED_SYMBOLS = [
     "urgym_mppi_control_colored",
     "urgym_mppi_collect_colored",
     "urgym_sac_train_colored",
+    "urgym_sac_policy_terms_cloned",
+    "urgym_sac_train_cloned",
     "urgym_refresh",
     "urgym_invalidate_records",
     "urgym_derive_obstacle_motion",

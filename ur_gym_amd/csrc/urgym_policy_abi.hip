@@ -30,6 +30,7 @@
 #include "urgym_nstep.h"
 #include "urgym_her.h"
 #include "urgym_adam.h"
+#include "urgym_sac_bc.h"
 #include "urgym_sac_terms.h"
 #include "urgym_sac_schedule.h"
 #include "urgym_eval.h"
@@ -493,6 +494,30 @@ int check_policy_terms(Handle* h, const urgym_sac_policy_args* args, const char*
   return URGYM_OK;
 }
 
+// what urgym_sac_policy_terms_cloned and urgym_sac_train_cloned refuse about the option's numbers, or null
+const char* clone_option_refusal(float weight, int32_t scale_by_q, int32_t q_filter, int32_t reserved0) {
+  if (reserved0 != 0) return "reserved0 of the cloning struct must be 0";
+  if (!(weight >= 0.0f && weight < INFINITY)) return "the cloning weight must be finite and >= 0";  // refuses NaN too
+  if ((scale_by_q != 0 && scale_by_q != 1) || (q_filter != 0 && q_filter != 1)) return "scale_by_q and q_filter must be 0 or 1";
+  return nullptr;
+}
+
+// urgym_sac_policy_terms_cloned: `call` is check_policy_terms' result for the same args
+int check_policy_terms_cloned(Handle* h, const SacPolicyCall& call, const urgym_sac_clone_args* clone, const char* who, SacCloneCall* out) {
+  if (!call.d_action_out || !call.critic_loss_out || !call.actor_loss_out)
+    return fail_in(h, URGYM_ERR_ARG, who, "the cloned call needs all three groups (upstream, critic loss, actor loss)");
+  if (!clone) return fail_in(h, URGYM_ERR_ARG, who, "null clone args");
+  const urgym_sac_clone_args& b = *clone;
+  if (!b.action_pi || !b.action_data || !b.bc_loss_out || !b.bc_weight_out || !b.bc_rows_out)
+    return fail_in(h, URGYM_ERR_ARG, who, "a pointer of urgym_sac_clone_args is null (action_pi, action_data, bc_loss_out, bc_weight_out, bc_rows_out)");
+  if (const char* what = clone_option_refusal(b.weight, b.scale_by_q, b.q_filter, b.reserved0)) return fail_in(h, URGYM_ERR_ARG, who, what);
+  if (!(fabsf(b.bc_scale) < INFINITY)) return fail_in(h, URGYM_ERR_ARG, who, "bc_scale must be finite");
+  if (call.d_action_out == b.action_pi || call.d_action_out == b.action_data)
+    return fail_in(h, URGYM_ERR_ARG, who, "d_action_out is action_pi or action_data (the actions are read again after d_action_out is written)");
+  *out = SacCloneCall{b.action_pi, b.action_data, b.weight, b.bc_scale, b.scale_by_q, b.q_filter, b.bc_loss_out, b.bc_weight_out, b.bc_rows_out};
+  return URGYM_OK;
+}
+
 int check_sample_rows(Handle* h, void* actor, const urgym_sampling* how, const urgym_critic_rows* rows, int count, float* actions_dev, float* log_prob_dev,
                       const char* who, SampleRows* out) {
   Actor* a = nullptr;
@@ -817,6 +842,20 @@ int urgym_sac_policy_terms(void* handle, const urgym_sac_policy_args* args, void
   if (int rc = check_policy_terms(h, args, "urgym_sac_policy_terms", &c)) return rc;
   HIP_TRY(h, hipSetDevice(h->device));
   sac_policy_launch(c, (hipStream_t)stream);
+  return launched(h);
+}
+
+// the policy terms with behaviour cloning (urgym_sac_bc.hip)
+int urgym_sac_policy_terms_cloned(void* handle, const urgym_sac_policy_args* args, const urgym_sac_clone_args* clone, void* stream) {
+  const char* who = "urgym_sac_policy_terms_cloned";
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  SacPolicyCall c;
+  SacCloneCall b;
+  if (int rc = check_policy_terms(h, args, who, &c)) return rc;
+  if (int rc = check_policy_terms_cloned(h, c, clone, who, &b)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  sac_policy_bc_launch(c, b, (hipStream_t)stream);
   return launched(h);
 }
 
@@ -1761,6 +1800,7 @@ struct TrainOptions {
   const urgym_sac_planning* planning;      // the collection is the planner's (urgym_mppi_train.h), planner_sync after the updates, TrainExtras
   const urgym_mppi_temper* temper;         // with planning: the planner's update is the tempered one (urgym_sac_train_tempered)
   const urgym_mppi_noise* noise;           // with planning: the planner's sample is the coloured one (urgym_sac_train_colored)
+  const urgym_sac_cloning* cloning;        // the update whose policy terms are urgym_sac_policy_terms_cloned's (urgym_sac_train_cloned)
 };
 
 // The evaluations and the training-episode statistics of one training call: what the body runs beside its own checks and launches.
@@ -1867,7 +1907,7 @@ struct TrainExtras {
   }
 };
 
-// The one driver of the nine urgym_sac_train* entry points: `who` is the entry point's own name in every refusal, `opt` what it was given.
+// The one driver of the twelve urgym_sac_train* entry points: `who` is the entry point's own name in every refusal, `opt` what it was given.
 int sac_train_body(const char* who, Handle* h, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, hipStream_t s, const TrainOptions& opt) {
   if (!learner) return fail_in(h, URGYM_ERR_ARG, who, "null learner");
   if (!schedule) return fail_in(h, URGYM_ERR_ARG, who, "null schedule");
@@ -1877,6 +1917,7 @@ int sac_train_body(const char* who, Handle* h, const urgym_sac_learner* learner,
   const urgym_sac_clipping* const clip = opt.clip;
   const urgym_normalization* const norm = opt.norm;
   const urgym_sac_planning* const planning = opt.planning;
+  const urgym_sac_cloning* const cloning = opt.cloning;
   PlannedCall planned;
   TrainExtras extras{who, h, learner, schedule, s, opt.evaluation, opt.monitoring, norm, planning ? &planned : nullptr};
   const urgym_sac_learner& L = *learner;
@@ -1935,6 +1976,11 @@ int sac_train_body(const char* who, Handle* h, const urgym_sac_learner* learner,
     if (!clip->scale) return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_clipping.scale is null");
     if ((!clip->critic_grad_norm || !clip->actor_grad_norm) && sac_schedule_updates(S) > 0)  // zero slots need no array
       return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_clipping.critic_grad_norm or actor_grad_norm is null");
+  }
+  if (cloning) {  // the option's own refusals, whether or not the call holds an update
+    if (const char* what = clone_option_refusal(cloning->weight, cloning->scale_by_q, cloning->q_filter, cloning->reserved0)) return fail_in(h, URGYM_ERR_ARG, who, what);
+    if ((!cloning->bc_loss || !cloning->bc_weight || !cloning->bc_rows) && sac_schedule_updates(S) > 0)  // zero slots need no array
+      return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_cloning.bc_loss, bc_weight or bc_rows is null");
   }
   if (planning) {  // the planner's own refusals and the collection's, whether or not the call holds an update
     if (int rc = planned_check(who, h, planning, &L.ring, S, &planned, opt.temper, opt.noise)) return rc;
@@ -2113,6 +2159,15 @@ int sac_train_body(const char* who, Handle* h, const urgym_sac_learner* learner,
   pa.log_prob = L.log_prob, pa.q_min = L.q_min, pa.actor_loss_out = L.actor_loss;
   SacPolicyCall terms_call;
   if (int rc = check_policy_terms(h, &pa, who, &terms_call)) return rc;
+  SacCloneCall clone_call;
+  if (cloning) {
+    urgym_sac_clone_args ca;
+    memset(&ca, 0, sizeof(ca));
+    ca.action_pi = L.action_pi, ca.action_data = L.batch.action, ca.weight = cloning->weight, ca.bc_scale = scale;
+    ca.scale_by_q = cloning->scale_by_q, ca.q_filter = cloning->q_filter;
+    ca.bc_loss_out = cloning->bc_loss, ca.bc_weight_out = cloning->bc_weight, ca.bc_rows_out = cloning->bc_rows;
+    if (int rc = check_policy_terms_cloned(h, terms_call, &ca, who, &clone_call)) return rc;
+  }
   const urgym_actor_upstream upstream{L.d_action, L.d_log_prob, nullptr, nullptr};
   urgym_actor_param_grads ag;
   memset(&ag, 0, sizeof(ag));
@@ -2205,7 +2260,13 @@ int sac_train_body(const char* who, Handle* h, const urgym_sac_learner* learner,
       critic_grad_launch(online_grad, action_gradient, s);
       if (int rc = train_stage(h, who, i, "critic_action_gradient")) return rc;
       terms_call.critic_loss_out = L.critic_loss + up.loss_slot, terms_call.actor_loss_out = L.actor_loss + up.loss_slot;
-      sac_policy_launch(terms_call, s);
+      if (cloning) {
+        clone_call.bc_loss_out = cloning->bc_loss + up.loss_slot, clone_call.bc_weight_out = cloning->bc_weight + up.loss_slot;
+        clone_call.bc_rows_out = cloning->bc_rows + up.loss_slot;
+        sac_policy_bc_launch(terms_call, clone_call, s);
+      } else {
+        sac_policy_launch(terms_call, s);
+      }
       if (int rc = train_stage(h, who, i, "sac_policy_terms")) return rc;
       actor_backward.draw = up.policy_draw;
       actor_backward_launch(actor, actor_backward, s);
@@ -2253,7 +2314,7 @@ const char* const ONE_GATHER = "at most one of nstep, prioritized and hindsight 
 extern "C" {
 
 // Each entry point: the null handle, its own required option, then the driver with what it was given.  TrainOptions' order is
-// {nstep, per, her, clip, norm, evaluation, monitoring, planning, temper, noise}.
+// {nstep, per, her, clip, norm, evaluation, monitoring, planning, temper, noise, cloning}.
 
 int urgym_sac_train(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, void* stream) {
   Handle* h = (Handle*)handle;
@@ -2346,6 +2407,17 @@ int urgym_sac_train_colored(void* handle, const urgym_sac_learner* learner, cons
   if (!noise) return fail_in(h, URGYM_ERR_ARG, who, "null urgym_mppi_noise");
   if ((nstep_or_NULL != nullptr) + (prioritized_or_NULL != nullptr) + (hindsight_or_NULL != nullptr) > 1) return fail_in(h, URGYM_ERR_ARG, who, ONE_GATHER);
   return sac_train_body(who, h, learner, schedule, (hipStream_t)stream, TrainOptions{nstep_or_NULL, prioritized_or_NULL, hindsight_or_NULL, clipping_or_NULL, nullptr, evaluation_or_NULL, monitoring_or_NULL, planning, temper_or_NULL, noise});
+}
+
+int urgym_sac_train_cloned(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_cloning* cloning, const urgym_sac_planning* planning_or_NULL, const urgym_mppi_temper* temper_or_NULL, const urgym_mppi_noise* noise_or_NULL, const urgym_normalization* normalization_or_NULL, const urgym_sac_clipping* clipping_or_NULL, const urgym_sac_nstep* nstep_or_NULL, const urgym_sac_prioritized* prioritized_or_NULL, const urgym_sac_hindsight* hindsight_or_NULL, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream) {
+  const char* who = "urgym_sac_train_cloned";
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (!cloning) return fail_in(h, URGYM_ERR_ARG, who, "null cloning");
+  if (!planning_or_NULL && (temper_or_NULL || noise_or_NULL)) return fail_in(h, URGYM_ERR_ARG, who, "temper and noise are the planner's and need planning");
+  if (planning_or_NULL && normalization_or_NULL) return fail_in(h, URGYM_ERR_ARG, who, "normalization together with planning is out of scope (the planner's actor and critic read raw rows)");
+  if ((nstep_or_NULL != nullptr) + (prioritized_or_NULL != nullptr) + (hindsight_or_NULL != nullptr) > 1) return fail_in(h, URGYM_ERR_ARG, who, ONE_GATHER);
+  return sac_train_body(who, h, learner, schedule, (hipStream_t)stream, TrainOptions{nstep_or_NULL, prioritized_or_NULL, hindsight_or_NULL, clipping_or_NULL, normalization_or_NULL, evaluation_or_NULL, monitoring_or_NULL, planning_or_NULL, temper_or_NULL, noise_or_NULL, cloning});
 }
 
 }  // extern "C"

@@ -1,0 +1,67 @@
+// urgym_sac_bc.h — behaviour cloning in SAC's policy loss on the device, with a Q-filter: the per-row arithmetic
+// and the scalar weight of urgym_sac_policy_terms_cloned, stated once as functions the kernel of urgym_sac_bc.hip and
+// tests/sac_bc_harness.cpp (a host program, built without HIP) both compile; and, for HIP units only, the seam between urgym_sac_bc.hip
+// and urgym_policy_abi.hip.  The sums, the means and the three loss terms are urgym_sac_terms.h's, used as they are.  Nothing here is
+// exported.
+#pragma once
+#include <stdint.h>
+
+#include "urgym_sac_terms.h"
+
+namespace urgym {
+
+// Every function below is float32 with ONE operation per line, rounded on its own: the units that compile this are built with
+// -ffp-contract=off.  ur_gym_amd.evaluation.policy_terms_cloned restates them.
+
+// the smaller of the two online critics at the replayed action; a NaN q1 gives q0
+URGYM_HD inline float sac_bc_q_data(float q0, float q1) { return q1 < q0 ? q1 : q0; }
+
+// THE Q-FILTER (Nair et al. 2018): a row is cloned only where the critic rates the replayed action above the policy's own.  A NaN on
+// either side, or a tie, gives not cloned.  Without the filter every row is cloned.
+URGYM_HD inline bool sac_bc_cloned(bool q_filter, float q_data, float q_min) { return q_filter ? (q_data > q_min) : true; }
+
+// one difference of the two actions
+URGYM_HD inline float sac_bc_difference(float action_pi, float action_data) { return action_pi - action_data; }
+
+// the term of the cloning loss of one row: half the squared distance of the six components, added in ascending order from +0.0f
+URGYM_HD inline float sac_bc_term(const float* action_pi, const float* action_data) {
+  float s = 0.0f;
+  for (int k = 0; k < 6; k++) {
+    const float d = sac_bc_difference(action_pi[k], action_data[k]);
+    const float p = d * d;
+    s = s + p;
+  }
+  return 0.5f * s;
+}
+
+// the weight of the cloning term: TD3+BC's normalisation by the mean |Q|, written as a weight on the cloning term (no division)
+URGYM_HD inline float sac_bc_weight(bool scale_by_q, float weight, float mean_abs) { return scale_by_q ? weight * mean_abs : weight; }
+
+// one element of the upstream gradient of a cloned row: g is dqmin_da * scale, the line of urgym_sac_policy_terms
+URGYM_HD inline float sac_bc_upstream(float g, float d, float w, float bc_scale) {
+  const float t = d * w;
+  const float u = t * bc_scale;
+  return g + u;
+}
+
+}  // namespace urgym
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+
+namespace urgym {
+
+// include/urgym.h, urgym_sac_clone_args, validated: DEVICE pointers, none null
+struct SacCloneCall {
+  const float *action_pi, *action_data;
+  float weight, bc_scale;
+  int scale_by_q, q_filter;
+  float *bc_loss_out, *bc_weight_out;
+  int32_t* bc_rows_out;
+};
+
+// ONE launch of ONE workgroup of SAC_TERMS_LANES lanes on `s`.  The caller has validated everything: all three groups of `call` given.
+void sac_policy_bc_launch(const SacPolicyCall& call, const SacCloneCall& clone, hipStream_t s);
+
+}  // namespace urgym
+#endif

@@ -800,6 +800,46 @@ def policy_terms(alpha, *, dqmin_da=None, scale=None, q=None, y=None, log_prob=N
     return out
 
 
+def policy_terms_cloned(alpha, *, dqmin_da, scale, q, y, log_prob, q_min, action_pi, action_data, weight, bc_scale, scale_by_q=False, q_filter=False,
+                        w_mean_abs=None):
+    """urgym_sac_policy_terms_cloned restated from include/urgym.h in numpy float32, line by line, the means by ``ordered_sum``.  The
+    arguments of ``policy_terms`` (all three groups, `q` the online critics at the replayed action) and `action_pi`, `action_data`
+    [count, 6], `weight`, `bc_scale`, the two flags.  `w_mean_abs`: None, or the float32 to take for the mean of ``|q_min|`` in the
+    weight instead of this function's own (a test that feeds another reduction's value).  Returns a dict: ``d_action`` [count, 6],
+    ``critic_loss``, ``actor_loss``, ``bc_loss``, ``bc_weight`` (float32 scalars), ``bc_rows`` (int32), ``cloned`` (bool [count]),
+    ``mean_abs`` (float32) and ``bc_terms`` (h, float32 [count])."""
+    f = np.float32
+    out = policy_terms(alpha, dqmin_da=dqmin_da, scale=scale, q=q, y=y, log_prob=log_prob, q_min=q_min)
+    g = out.pop("d_action")
+    count = g.shape[0]
+    q, q_min = np.asarray(q), np.asarray(q_min)
+    action_pi, action_data = _rows32("action_pi", action_pi, (count, 6)), _rows32("action_data", action_data, (count, 6))
+    with np.errstate(all="ignore"):
+        weight, bc_scale = f(weight), f(bc_scale)
+        if not (np.isfinite(weight) and weight >= 0 and np.isfinite(bc_scale)):
+            raise ValueError(f"weight must be finite and >= 0 and bc_scale finite in float32, got {weight!r}, {bc_scale!r}")
+        qd = np.where(q[1] < q[0], q[1], q[0])
+        cloned = (qd > q_min) if q_filter else np.ones(count, dtype=bool)
+        d = action_pi - action_data
+        s = np.zeros(count, dtype=f)
+        for k in range(6):
+            p = d[:, k] * d[:, k]
+            s = s + p
+        h = np.where(cloned, f(0.5) * s, f(0.0))
+        absq = np.abs(q_min)
+        mean_abs = _ordered_mean(absq)
+        bc_loss = _ordered_mean(h)
+        used = mean_abs if w_mean_abs is None else f(w_mean_abs)
+        w = weight * used if scale_by_q else weight
+        t = d * w
+        u = t * bc_scale
+        d_action = np.where(cloned[:, None], g + u, g)
+    for x in (qd, d, s, h, absq, mean_abs, bc_loss, w, t, u, d_action):
+        assert x.dtype == f, x.dtype  # no intermediate was promoted
+    out.update(d_action=d_action, bc_loss=bc_loss, bc_weight=w, bc_rows=np.int32(np.count_nonzero(cloned)), cloned=cloned, mean_abs=mean_abs, bc_terms=h)
+    return out
+
+
 def _check_device_tensors(tensors, wanted, device, who):
     """`wanted`: name -> shape.  Raises ValueError unless every one is a contiguous float32 torch tensor of that shape on `device`."""
     import torch

@@ -65,6 +65,11 @@ minibatch gather on the HIP kernels, and gradients and optimisers in torch autog
     ``noise_beta=``; DESIGN.md sections 30 to 32), and with
     ``plan_stats=True`` keeps a record of how the plans went beside every
     record of the monitor.
+    With ``bc_weight=X`` (it needs ``device_entropy=True``) the policy loss also imitates the action the ring holds:
+    ``env.policy_terms`` becomes ``env.policy_terms_cloned`` on ``batch["actions"]`` -- ONE launch in its place, so the counts above
+    stand -- which adds ``X' (action_pi - action) / M`` to d_action on the rows it clones, X' = X or, with ``bc_scale_by_q``, X times the
+    mean |min Q| (TD3+BC's normalisation), the rows being all of them or, with ``bc_q_filter``, those where the critics rate the ring's
+    action above the policy's own.  ``None``, the default, makes exactly the calls above.
     None of them synchronises with the host.  ``train`` runs the whole loop in one native call and, given an
     ``evaluation.DeviceEvaluation``, the reference's EvalCallback inside it: evaluations of the deterministic policy at a fixed interval of
     updates, their statistics as records on the device, and the best actor's tensors, which ``DeviceEvaluation.save_best`` writes as an
@@ -100,6 +105,10 @@ CLIP_DEFAULTS = dict(max_grad_norm=None)
 # Running observation and reward normalization: SACLearner(normalize=True) is SB3's VecNormalize on the device, with
 # its defaults.  Kept apart like the three above: a run without it saves none of these, and no statistics.
 NORM_DEFAULTS = dict(normalize=False, norm_obs=True, norm_reward=True, clip_obs=10.0, clip_reward=10.0, norm_epsilon=1e-8)
+# Behaviour cloning in the policy loss: SACLearner(bc_weight=X) pulls the policy's action towards the ring's, with
+# TD3+BC's normalisation by the mean |Q| (bc_scale_by_q) and the Q-filter (bc_q_filter).  None, the default, is the learner as it was.
+# Kept apart like the four above: a run without it saves none of the three.
+BC_DEFAULTS = dict(bc_weight=None, bc_scale_by_q=False, bc_q_filter=False)
 
 
 def _mlp(n_in, hidden, n_out=None):
@@ -188,12 +197,28 @@ class SACLearner:
     the device, inside the Adam steps; with any of the options above."""
 
     def __init__(self, env, seed=0, **overrides):
-        unknown = [k for k in overrides if k not in SAC_DEFAULTS and k not in PER_DEFAULTS and k not in HER_DEFAULTS and k not in CLIP_DEFAULTS and k not in NORM_DEFAULTS]
+        unknown = [k for k in overrides if k not in SAC_DEFAULTS and k not in PER_DEFAULTS and k not in HER_DEFAULTS and k not in CLIP_DEFAULTS and k not in NORM_DEFAULTS
+                   and k not in BC_DEFAULTS]
         if unknown:
             raise TypeError(f"unknown hyperparameters {unknown}; available: "
-                            f"{sorted(SAC_DEFAULTS) + sorted(PER_DEFAULTS) + sorted(HER_DEFAULTS) + sorted(CLIP_DEFAULTS) + sorted(NORM_DEFAULTS)}")
-        hp = dict(SAC_DEFAULTS, **PER_DEFAULTS, **HER_DEFAULTS, **CLIP_DEFAULTS, **NORM_DEFAULTS)
+                            f"{sorted(SAC_DEFAULTS) + sorted(PER_DEFAULTS) + sorted(HER_DEFAULTS) + sorted(CLIP_DEFAULTS) + sorted(NORM_DEFAULTS) + sorted(BC_DEFAULTS)}")
+        hp = dict(SAC_DEFAULTS, **PER_DEFAULTS, **HER_DEFAULTS, **CLIP_DEFAULTS, **NORM_DEFAULTS, **BC_DEFAULTS)
         hp.update(overrides)
+        for k in ("bc_scale_by_q", "bc_q_filter"):
+            if not isinstance(hp[k], bool):
+                raise ValueError(f"{k} must be True or False, got {hp[k]!r}")
+        if hp["bc_weight"] is None:
+            if hp["bc_scale_by_q"] or hp["bc_q_filter"]:
+                raise ValueError("bc_scale_by_q and bc_q_filter qualify bc_weight and need it")
+        else:
+            with np.errstate(over="ignore"):
+                weight = hp["bc_weight"]
+                ok = not isinstance(weight, bool) and isinstance(weight, (int, float, np.integer, np.floating)) and bool(np.isfinite(np.float32(weight))) and float(np.float32(weight)) >= 0.0
+            if not ok:
+                raise ValueError(f"bc_weight must be None or a number that is finite in float32 and >= 0, got {hp['bc_weight']!r}")
+            if not hp["device_entropy"]:
+                raise ValueError("bc_weight needs device_entropy=True (the cloning term is added to the policy's upstream gradient by the device's policy terms)")
+            hp["bc_weight"] = float(weight)
         if not isinstance(hp["normalize"], bool):
             raise ValueError(f"normalize must be True or False, got {hp['normalize']!r}")
         if hp["normalize"]:
@@ -307,6 +332,11 @@ class SACLearner:
             scale = torch.zeros((2,), dtype=torch.float32, device=dev)  # the critics' coefficient, then the actor's
             self.clip_state = dict(scale=scale, critic_scale=scale[0:1], actor_scale=scale[1:2], critic_grad_norm=torch.zeros((1,), dtype=torch.float32, device=dev),
                                    actor_grad_norm=torch.zeros((1,), dtype=torch.float32, device=dev))
+        # with bc_weight the cloning loss, the weight used and the number of cloned rows of the running update are tensors of the learner's; never saved
+        self.bc_state = None
+        if hp["bc_weight"] is not None:
+            self.bc_state = dict(bc_loss=torch.zeros((1,), dtype=torch.float32, device=dev), bc_weight=torch.zeros((1,), dtype=torch.float32, device=dev),
+                                 bc_rows=torch.zeros((1,), dtype=torch.int32, device=dev))
         # with normalize the running statistics, the actor's scratch rows and the fold's workspace are the normalizer's
         self.normalizer = None
         if hp["normalize"]:
@@ -484,13 +514,30 @@ class SACLearner:
                              **self._clip("critic"))
         grad = env.critic_action_gradient(self.online, action_pi, rows=rows)
         # d_action = -g / M and the critic's and the actor's loss values
-        env.policy_terms(es["ent_coef"], M, dqmin_da=grad["dqmin_da"], scale=-1.0 / M, d_action_out=self.actor_d_action, q=got["q"], y=es["y"],
-                         critic_loss_out=es["critic_loss"], log_prob=log_prob, q_min=grad["q_min"], actor_loss_out=es["actor_loss"])
+        self._policy_terms(M, grad, got, log_prob, action_pi, batch["actions"])
         env.actor_parameter_gradients(self.device_actor, sample=how, rows=rows, d_action=self.actor_d_action, d_log_prob=self.actor_d_log_prob,
                                       out=self.actor_grads, workspace=self.actor_workspace)
         env.actor_adam_step(self.device_actor, self.actor.tensors(), self.actor_grads, *st["actor"], **adam, **self._clip("actor"))
-        self.last_update = dict(log_prob=log_prob, y=es["y"], q=got["q"], q_min=grad["q_min"], dqmin_da=grad["dqmin_da"], **self._clip_record())
+        self.last_update = dict(log_prob=log_prob, y=es["y"], q=got["q"], q_min=grad["q_min"], dqmin_da=grad["dqmin_da"], **self._clip_record(), **self._bc_record(action_pi, batch["actions"]))
         return dict(es["losses"])
+
+    def _policy_terms(self, M, grad, got, log_prob, action_pi, actions):
+        """d_action = -g / M and the critic's and the actor's loss values: ``env.policy_terms``, or with ``bc_weight`` the ONE launch of
+        ``env.policy_terms_cloned`` in its place, which adds the cloning term on the rows it clones (`actions`: the ring's)."""
+        hp, es, bc = self.hp, self.entropy_state, self.bc_state
+        common = dict(dqmin_da=grad["dqmin_da"], scale=-1.0 / M, d_action_out=self.actor_d_action, q=got["q"], y=es["y"], critic_loss_out=es["critic_loss"],
+                      log_prob=log_prob, q_min=grad["q_min"], actor_loss_out=es["actor_loss"])
+        if bc is None:
+            self.env.policy_terms(es["ent_coef"], M, **common)
+        else:
+            self.env.policy_terms_cloned(es["ent_coef"], M, **common, action_pi=action_pi, action_data=actions, weight=hp["bc_weight"], bc_scale=1.0 / M,
+                                         scale_by_q=hp["bc_scale_by_q"], q_filter=hp["bc_q_filter"], bc_loss_out=bc["bc_loss"], bc_weight_out=bc["bc_weight"],
+                                         bc_rows_out=bc["bc_rows"])
+
+    def _bc_record(self, action_pi, actions):
+        """What ``last_update`` gains with ``bc_weight``: references to the cloning loss, the weight used and the number of cloned rows, and
+        to the two actions the cloning term was formed from."""
+        return {} if self.bc_state is None else dict(self.bc_state, action_pi=action_pi, action_data=actions)
 
     def _clip(self, which):
         """With ``max_grad_norm``: ONE launch reduces the global norm of the critics' (or the actor's) gradients into the learner's
@@ -542,13 +589,12 @@ class SACLearner:
         env.critic_adam_step(self.online, self.critic.tensors(), self.critic_grads, *st["critic"], target=self.target, tau=hp["tau"], **adam,
                              **self._clip("critic"))
         grad = env.critic_action_gradient(self.online, action_pi, rows=rows)
-        env.policy_terms(es["ent_coef"], M, dqmin_da=grad["dqmin_da"], scale=-1.0 / M, d_action_out=self.actor_d_action, q=got["q"], y=es["y"],
-                         critic_loss_out=es["critic_loss"], log_prob=log_prob, q_min=grad["q_min"], actor_loss_out=es["actor_loss"])
+        self._policy_terms(M, grad, got, log_prob, action_pi, batch["actions"])
         env.actor_parameter_gradients(self.device_actor, sample=how, rows=rows, d_action=self.actor_d_action, d_log_prob=self.actor_d_log_prob,
                                       out=self.actor_grads, workspace=self.actor_workspace)
         env.actor_adam_step(self.device_actor, self.actor.tensors(), self.actor_grads, *st["actor"], **adam, **self._clip("actor"))
         self.last_update = dict(log_prob=log_prob, y=es["y"], q=got["q"], q_min=grad["q_min"], dqmin_da=grad["dqmin_da"], q_evaluated=q, index=batch["index"],
-                                leaf=batch["leaf"], total=batch["total"], **per, **self._clip_record())
+                                leaf=batch["leaf"], total=batch["total"], **per, **self._clip_record(), **self._bc_record(action_pi, batch["actions"]))
         return dict(es["losses"])
 
     def _train_binding(self, replay):
@@ -662,6 +708,11 @@ class SACLearner:
         if cs is not None:
             norms = torch.empty((2, updates), dtype=torch.float32, device=env.device)
             clipping = dict(clipping=dict(max_grad_norm=hp["max_grad_norm"], scale=cs["scale"], critic_grad_norm=norms[0], actor_grad_norm=norms[1]))
+        cloning, bc_out = {}, {}
+        if self.bc_state is not None:
+            bc_out = dict(bc_loss=torch.empty((updates,), dtype=torch.float32, device=env.device), bc_weight=torch.empty((updates,), dtype=torch.float32, device=env.device),
+                          bc_rows=torch.empty((updates,), dtype=torch.int32, device=env.device))
+            cloning = dict(cloning=dict(weight=hp["bc_weight"], scale_by_q=hp["bc_scale_by_q"], q_filter=hp["bc_q_filter"], **bc_out))
         tr["binding"].struct.update_seed = int(seed)
         env.sac_train(tr["binding"], losses[0], losses[1], losses[2], first_slot=replay.cursor, filled_steps=replay.filled, num_iterations=n,
                       steps_per_iteration=K, updates_per_iteration=G, uniform_iterations=uniform, idle_iterations=idle,
@@ -671,7 +722,7 @@ class SACLearner:
                       **({} if tr["nstep"] is None else dict(nstep=tr["nstep"])),
                       **({} if tr["prioritized"] is None else dict(prioritized=tr["prioritized"])),
                       **({} if tr["hindsight"] is None else dict(hindsight=tr["hindsight"])), **clipping,
-                      **({} if self.normalizer is None else dict(normalizer=self.normalizer)), **planning)
+                      **({} if self.normalizer is None else dict(normalizer=self.normalizer)), **planning, **cloning)
         self.env_steps += n * K
         self.draw += n * K
         st["step"] += updates
@@ -687,7 +738,10 @@ class SACLearner:
             if cs is not None:  # the last update's norms, as views of the call's slots; the coefficients are the scratch's
                 self.last_update.update(critic_grad_norm=norms[0, updates - 1:], actor_grad_norm=norms[1, updates - 1:], critic_scale=cs["critic_scale"],
                                         actor_scale=cs["actor_scale"])
+            if bc_out:  # the last update's three, as views of the call's slots
+                self.last_update.update({k: v[updates - 1:] for k, v in bc_out.items()}, action_pi=sc["action_pi"], action_data=tr["batch"]["action"])
         extra = {"plan_stats": planner.records[first_record:monitor.count]} if plan_stats else {}
+        extra.update(bc_out)
         if cs is not None:
             return {"critic_loss": losses[0], "actor_loss": losses[1], "ent_coef_loss": losses[2], "critic_grad_norm": norms[0], "actor_grad_norm": norms[1], **extra}
         return {"critic_loss": losses[0], "actor_loss": losses[1], "ent_coef_loss": losses[2], **extra}
@@ -703,7 +757,7 @@ class SACLearner:
         what it was before the option existed (``check_state_dict`` reads an absent ``n_steps`` as 1)."""
         return {k: v for k, v in self.hp.items() if (k != "n_steps" or int(v) != 1) and (k not in PER_DEFAULTS or self.hp.get("prioritized"))
                 and (k not in HER_DEFAULTS or self.hp.get("hindsight")) and (k not in CLIP_DEFAULTS or v is not None)
-                and (k not in NORM_DEFAULTS or self.hp.get("normalize"))}
+                and (k not in NORM_DEFAULTS or self.hp.get("normalize")) and (k not in BC_DEFAULTS or self.hp.get("bc_weight") is not None)}
 
     def state_dict(self):
         """Everything the learner is, as host arrays and scalars: the actor's eight and the critics' twelve parameter tensors, the
@@ -788,6 +842,9 @@ class SACLearner:
             if state["hp"].get(k, default) != self.hp.get(k, default):
                 raise ValueError(f"load_state_dict: {k} is {state['hp'].get(k, default)!r} in the checkpoint, {self.hp.get(k, default)!r} here")
         for k, default in CLIP_DEFAULTS.items():  # a file without clipping holds no max_grad_norm
+            if state["hp"].get(k, default) != self.hp.get(k, default):
+                raise ValueError(f"load_state_dict: {k} is {state['hp'].get(k, default)!r} in the checkpoint, {self.hp.get(k, default)!r} here")
+        for k, default in BC_DEFAULTS.items():  # a file without cloning holds none of the three
             if state["hp"].get(k, default) != self.hp.get(k, default):
                 raise ValueError(f"load_state_dict: {k} is {state['hp'].get(k, default)!r} in the checkpoint, {self.hp.get(k, default)!r} here")
         for k, default in NORM_DEFAULTS.items():  # a file without normalization holds none of the six, and no statistics

@@ -65,8 +65,10 @@ _SAC_TRAIN_ENTRIES = (
 )
 
 # The entry points ``sac_train`` tries ahead of that table, in the same form: a planner with coloured sampling noise
-# goes to urgym_sac_train_colored whatever else is given; its temper struct, like every option after it, may be absent.
+# goes to urgym_sac_train_colored whatever else is given; its temper struct, like every option after it, may be absent.  Ahead of that,
+# behaviour cloning goes to urgym_sac_train_cloned, which takes every other option, each of which may be absent.
 _SAC_TRAIN_ENTRIES_AHEAD = (
+    ("urgym_sac_train_cloned", "cloning", ("cloning", "planner", "temper", "noise", "normalizer", "clipping", "nstep", "prioritized", "hindsight", "evaluation", "monitor")),
     ("urgym_sac_train_colored", "noise", ("planner", "noise", "temper", "clipping", "nstep", "prioritized", "hindsight", "evaluation", "monitor")),
 )
 
@@ -74,7 +76,7 @@ _SAC_TRAIN_ENTRIES_AHEAD = (
 def _sac_train_entry(present):
     """(symbol, option names) of the entry point that serves a call with the options in `present` (any container of names out of
     evaluation, monitor, nstep, prioritized, hindsight, clipping, normalizer, planner, temper -- the planner's temper struct, given where
-    the planner has an ess_target -- and noise, its noise struct, given where it has a noise_beta): the first row of
+    the planner has an ess_target -- noise, its noise struct, given where it has a noise_beta, and cloning): the first row of
     ``_SAC_TRAIN_ENTRIES_AHEAD``, then of ``_SAC_TRAIN_ENTRIES``, whose option is given."""
     for symbol, selects, options in _SAC_TRAIN_ENTRIES_AHEAD + _SAC_TRAIN_ENTRIES:
         if selects is None or selects in present:
@@ -721,6 +723,48 @@ class UR5ReachVectorEnv:
             a.actor_loss_out = self._float_ptr(who, "actor_loss_out", actor_loss_out, (1,))
         _native.check(self.lib.urgym_sac_policy_terms(self._h, C.byref(a), self._stream()), self._h)
 
+    def policy_terms_cloned(self, ent_coef, count, *, dqmin_da, scale, d_action_out, q, y, critic_loss_out, log_prob, q_min, actor_loss_out,
+                            action_pi, action_data, weight, bc_scale, scale_by_q=False, q_filter=False, bc_loss_out, bc_weight_out, bc_rows_out):
+        """``policy_terms`` with behaviour cloning, in ONE launch in its place (urgym_sac_policy_terms_cloned): all
+        three groups of ``policy_terms`` are required, `q` being the online critics at the REPLAYED action.  `action_pi`, `action_data`
+        [count, 6]: the policy's action and the ring's on the batch rows.  A row is cloned where `q_filter` is off or ``min(q[0], q[1])
+        > q_min``; a cloned row gets ``d_action_out = dqmin_da * scale + ((action_pi - action_data) * w) * bc_scale`` with ``w = weight``
+        or, with `scale_by_q`, ``weight * mean |q_min|``; any other row what ``policy_terms`` writes.  ``bc_loss_out`` [1] receives the
+        mean over all rows of half the squared distance of the cloned rows, ``bc_weight_out`` [1] w, ``bc_rows_out`` (int32 [1]) the
+        number of cloned rows.  Tensors are checked as in ``policy_terms``; the arithmetic is ``evaluation.policy_terms_cloned``,
+        bitwise.  On torch's current stream, nothing is synchronised."""
+        who = "policy_terms_cloned"
+        count = int(count)
+        if not 1 <= count <= _abi.SAC_TERMS_MAX_COUNT:
+            raise ValueError(f"{who}: count must be in [1, {_abi.SAC_TERMS_MAX_COUNT}], got {count}")
+        for name, x in (("scale", scale), ("bc_scale", bc_scale), ("weight", weight)):
+            if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not self._finite32(x):
+                raise ValueError(f"{who}: {name} must be a number that is finite in float32, got {x!r}")
+        if float(np.float32(weight)) < 0.0:
+            raise ValueError(f"{who}: weight must be >= 0, got {weight}")
+        for name, x in (("scale_by_q", scale_by_q), ("q_filter", q_filter)):
+            if not isinstance(x, (bool, np.bool_)):
+                raise ValueError(f"{who}: {name} must be True or False, got {x!r}")
+        a = _abi.SacPolicyArgs(count, 0, float(scale))
+        a.ent_coef = self._float_ptr(who, "ent_coef", ent_coef, (1,))
+        a.dqmin_da = self._float_ptr(who, "dqmin_da", dqmin_da, (count, 6))
+        a.d_action_out = self._float_ptr(who, "d_action_out", d_action_out, (count, 6))
+        a.q = self._float_ptr(who, "q", q, (2, count))
+        a.y = self._float_ptr(who, "y", y, (count,))
+        a.critic_loss_out = self._float_ptr(who, "critic_loss_out", critic_loss_out, (1,))
+        a.log_prob = self._float_ptr(who, "log_prob", log_prob, (count,))
+        a.q_min = self._float_ptr(who, "q_min", q_min, (count,))
+        a.actor_loss_out = self._float_ptr(who, "actor_loss_out", actor_loss_out, (1,))
+        b = _abi.SacCloneArgs(weight=float(weight), bc_scale=float(bc_scale), scale_by_q=int(bool(scale_by_q)), q_filter=int(bool(q_filter)), reserved0=0)
+        b.action_pi = self._float_ptr(who, "action_pi", action_pi, (count, 6))
+        b.action_data = self._float_ptr(who, "action_data", action_data, (count, 6))
+        b.bc_loss_out = self._float_ptr(who, "bc_loss_out", bc_loss_out, (1,))
+        b.bc_weight_out = self._float_ptr(who, "bc_weight_out", bc_weight_out, (1,))
+        b.bc_rows_out = self._float_ptr(who, "bc_rows_out", bc_rows_out, (1,), torch.int32, C.c_int32)
+        if d_action_out.data_ptr() in (action_pi.data_ptr(), action_data.data_ptr()):
+            raise ValueError(f"{who}: d_action_out must not be action_pi or action_data (the actions are read again after it is written)")
+        _native.check(self.lib.urgym_sac_policy_terms_cloned(self._h, C.byref(a), C.byref(b), self._stream()), self._h)
+
     def evaluation_stats(self, returns, last_step, success, best_mean, best_index, record, eval_index):
         """The statistics of N evaluation episodes, the improvement decision and the best state, in ONE launch of one workgroup
         (urgym_eval_stats): `returns` float64 [N], `last_step` int32 [N], `success` uint8 or bool [N] (the episode summary of
@@ -895,7 +939,7 @@ class UR5ReachVectorEnv:
     def sac_train(self, learner, critic_loss, actor_loss, ent_coef_loss, *, first_slot, filled_steps, num_iterations, steps_per_iteration=1,
                   updates_per_iteration=1, uniform_iterations=0, idle_iterations=0, collect_first_draw=0, update_first_draw=0, first_step=1,
                   evaluation=None, eval_every=None, monitor=None, log_every=None, nstep=None, prioritized=None, hindsight=None, clipping=None,
-                  normalizer=None, planner=None):
+                  normalizer=None, planner=None, cloning=None):
         """``num_iterations`` x (a collection of ``steps_per_iteration`` steps, ``updates_per_iteration`` SAC updates) in ONE native
         call (urgym_sac_train): the launches of ``collect`` and of the thirteen calls of an update, bit for bit, without returning to
         Python in between.  `learner`: what ``sac_learner`` returned, or a dict of its keyword arguments (then built and checked here).
@@ -941,7 +985,12 @@ class UR5ReachVectorEnv:
         (``DeviceMPPI.collect(..., first_draw=collect_first_draw + i K, explore_sigma=)``, urgym_sac_train_planned); with ``sync`` the
         planner's actor and critic are reloaded from the learner's parameters after the updates of every iteration that has any; with
         ``records`` (it needs `monitor`) one ``DeviceMPPI.stats`` record is written beside every monitor record, into
-        ``planner.records`` at the monitor's own index.  ``uniform_iterations`` must be 0; not together with `normalizer`."""
+        ``planner.records`` at the monitor's own index.  ``uniform_iterations`` must be 0; not together with `normalizer`.
+
+        With `cloning` (a dict: ``weight``, optionally ``scale_by_q`` and ``q_filter`` (False), and ``bc_loss``, ``bc_weight`` (float32)
+        and ``bc_rows`` (int32), tensors of one entry per update of the call like the losses): every update's ``policy_terms`` is
+        ``policy_terms_cloned`` on the policy's action and the batch's (urgym_sac_train_cloned), ``bc_scale`` = 1 / count; update u
+        writes entry u of the three.  With any of the options above."""
         from .evaluation import DeviceEvaluation, DeviceMonitor, DeviceMPPI, _her_arguments, evaluation_points, monitor_points, relabel_threshold, training_schedule
 
         who = "sac_train"
@@ -1046,6 +1095,19 @@ class UR5ReachVectorEnv:
                 given["temper"] = mppi.temper()
             if mppi.noise() is not None:
                 given["noise"] = mppi.noise()
+        if cloning is not None:
+            unknown = [k for k in cloning if k not in ("weight", "scale_by_q", "q_filter", "bc_loss", "bc_weight", "bc_rows")]
+            if unknown:
+                raise ValueError(f"{who}: unknown cloning options {unknown}; available: weight, scale_by_q, q_filter, bc_loss, bc_weight, bc_rows")
+            weight = cloning["weight"]
+            if isinstance(weight, bool) or not isinstance(weight, (int, float, np.integer, np.floating)) or not self._finite32(weight) or float(np.float32(weight)) < 0.0:
+                raise ValueError(f"{who}: cloning['weight'] must be a number that is finite in float32 and >= 0, got {weight!r}")
+            flags = [cloning.get(k, False) for k in ("scale_by_q", "q_filter")]
+            if not all(isinstance(x, (bool, np.bool_)) for x in flags):
+                raise ValueError(f"{who}: cloning['scale_by_q'] and cloning['q_filter'] must be True or False")
+            given["cloning"] = _abi.SacCloning(float(weight), int(flags[0]), int(flags[1]), 0, self._float_ptr(who, "cloning['bc_loss']", cloning["bc_loss"], (updates,)),
+                                               self._float_ptr(who, "cloning['bc_weight']", cloning["bc_weight"], (updates,)),
+                                               self._float_ptr(who, "cloning['bc_rows']", cloning["bc_rows"], (updates,), torch.int32, C.c_int32))
         symbol, options = _sac_train_entry(given)
         try:
             _native.check(getattr(self.lib, symbol)(self._h, C.byref(L), C.byref(S), *[C.byref(given[o]) if o in given else None for o in options], self._stream()), self._h)
