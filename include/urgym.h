@@ -2353,6 +2353,72 @@ typedef struct urgym_sac_cloning {
  * together with planning; and what the call with the same options and no cloning refuses. */
 int urgym_sac_train_cloned(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_cloning* cloning, const urgym_sac_planning* planning_or_NULL, const urgym_mppi_temper* temper_or_NULL, const urgym_mppi_noise* noise_or_NULL, const urgym_normalization* normalization_or_NULL, const urgym_sac_clipping* clipping_or_NULL, const urgym_sac_nstep* nstep_or_NULL, const urgym_sac_prioritized* prioritized_or_NULL, const urgym_sac_hindsight* hindsight_or_NULL, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream);
 
+/* ---- the demonstration ring: a second replay ring that collection never overwrites, a fixed part of every
+ * minibatch drawn from it, and cloning on those rows only (Nair et al. 2018 keep such a buffer and clone its rows; RLPD, Ball et al. 2023,
+ * draws half of every batch from offline data; with the whole batch from it, TD3+BC).  Opt-in and added WITHIN ABI version 4: no struct
+ * above changed, no symbol above changed, URGYM_ABI_VERSION did not move, the three symbols below (urgym_replay_sample_mixed,
+ * urgym_sac_policy_terms_cloned_masked, urgym_sac_train_demonstrated) are found by lookup.  The library keeps no state: the
+ * demonstration ring, its cursor and its fill level are the caller's, like the learner's own. */
+
+/* The last counter word of a draw from the demonstrations.  It meets none of the tags in use: 0x504F4C00 | block (policy noise),
+ * 0x52504C00 (replay), 0x50455200 (prioritized replay), 0x4D505000 | block (the planner), the reset sampler's blocks 0..4. */
+#define URGYM_DEMO_TAG 0x44454D00u   /* "DEM\0" */
+
+typedef struct urgym_replay_demonstrations {
+  urgym_replay_ring ring;  /* a ring of the SAME env kind, every array [C_d][N_d][...]; truncated / is_success may be NULL */
+  int32_t num_envs;        /* N_d >= 1; need not be the handle's N */
+  int32_t oldest_slot;     /* in [0, C_d) */
+  int32_t filled_steps;    /* in [1, C_d] */
+  int32_t count;           /* D in [0, count]: rows 0 .. D-1 of the minibatch come from here */
+} urgym_replay_demonstrations;
+
+/* urgym_replay_sample whose first D = demo->count rows come from the demonstrations, in ONE gather launch on `stream`.
+ * Rows i >= D are exactly urgym_replay_sample's row i: the same Philox call, counter (i, draw lo, draw hi, 0x52504C00), the same
+ *   e = (w * size) >> 64 and the same slot and env arithmetic, so they are bitwise the rows that call gathers at the same (seed, draw) and
+ *   position; with D == 0 every output is bitwise that call's.
+ * Rows i < D draw from the demonstrations: the same key, counter (i, draw lo, draw hi, URGYM_DEMO_TAG);  w = (w0 << 32) | w1;
+ *   size_d = filled_d * N_d;  e = (w * size_d) >> 64;  slot = (oldest_d + e / N_d) % C_d;  env = e % N_d;  index = slot * N_d + env,
+ *   an entry of the DEMONSTRATION ring (batch->index[i] holds it).
+ * The result is a function of (seed, draw, i, size, size_d) alone: not of count, not of the launch geometry.  source_out[i] is 1 for a
+ * demonstration row and 0 otherwise.  The geometry is urgym_replay_sample's (64 samples per wave, 16 lanes per row, four rows per
+ * round); in a wave whose samples straddle D each group of 16 lanes reads the ring of ITS sample.
+ * ur_gym_amd.evaluation.mixed_indices restates the draw.
+ * Refused (URGYM_ERR_ARG, nothing is launched, nothing is written): everything urgym_replay_sample refuses; demo == NULL; a NULL
+ * required pointer in demo->ring or capacity_steps <= 0 there; reserved0 != 0 in demo->ring; num_envs < 1; oldest_slot outside [0, C_d);
+ * filled_steps outside [1, C_d]; demo->count outside [0, count]; filled_steps * num_envs not below 2^63; truncated or is_success asked for
+ * while either ring does not keep it. */
+int urgym_replay_sample_mixed(void* handle, const urgym_replay_ring* ring, int oldest_slot, int filled_steps, uint64_t seed, uint64_t draw, int count, const urgym_replay_batch* batch, const urgym_replay_demonstrations* demo, uint8_t* source_out /* [count] or NULL */, void* stream);
+
+/* urgym_sac_policy_terms_cloned with ONE change to the verdict of a row:
+ *     cloned[m] = row_mask[m] != 0 && (q_filter ? qd > q_min[m] : true)
+ * Everything else is that call's, line by line: absq and mean_abs stay over ALL rows; bc_loss stays the ordered mean over all count rows
+ * with +0.0f for a row that is not cloned; rows counts the cloned rows; a row that is not cloned gets d_action_out bitwise
+ * urgym_sac_policy_terms'.  ONE launch of ONE workgroup of 1024 lanes, like the kernel it stands in for.  A mask of all ones gives
+ * urgym_sac_policy_terms_cloned's bits; a mask of all zeros gives urgym_sac_policy_terms' bits, bc_loss = +0.0, rows = 0, and bc_weight
+ * still written.  action_pi and action_data of a row the mask excludes reach no output.  d_action_out may be dqmin_da itself.
+ * Refused (URGYM_ERR_ARG, nothing is launched, nothing is written): what urgym_sac_policy_terms_cloned refuses, and a NULL row_mask. */
+int urgym_sac_policy_terms_cloned_masked(void* handle, const urgym_sac_policy_args* args, const urgym_sac_clone_args* clone, const uint8_t* row_mask /* [count], required */, void* stream);
+
+/* The training call with demonstrations.  In every update the gather launch is urgym_replay_sample_mixed's, at the (seed, draw) the plain
+ * call would use, with source_out = source; and, with cloning and clone_demonstrations_only, the policy-terms launch is
+ * urgym_sac_policy_terms_cloned_masked's with row_mask = source.  Nothing else in the sequence moves: an update stays thirteen launches
+ * (more with the other options, as they state).  bc_scale stays (float)(1.0 / M), so a weight means the same at every demonstration
+ * share.  urgym_norm_batch normalizes the gathered batch as it does today: demonstration rows are RAW rows like any other, and the running
+ * statistics still come from the learner's own collection only (no demonstration row is ever folded).  There is no nstep, prioritized
+ * or hindsight parameter: each of those has a gather of its own, and the pairs are out of scope. */
+typedef struct urgym_sac_demonstrating {
+  urgym_replay_demonstrations demonstrations;  /* count = D rows of each of the learner's M */
+  uint8_t* source;                             /* [M] scratch: the gather's source_out */
+  int32_t clone_demonstrations_only;           /* 0 or 1; 1 needs cloning */
+  int32_t reserved0;                           /* must be 0 */
+} urgym_sac_demonstrating;
+
+/* Every option after `demonstrating` may be NULL and is then as in the call without it.  Refused, nothing launched (the message names
+ * urgym_sac_train_demonstrated): NULL demonstrating; what urgym_replay_sample_mixed refuses; D > M; a NULL source where the call holds an
+ * update; clone_demonstrations_only other than 0 or 1, or 1 without cloning; reserved0 != 0; and what the call with the same options and
+ * no demonstrations refuses. */
+int urgym_sac_train_demonstrated(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_demonstrating* demonstrating, const urgym_sac_cloning* cloning_or_NULL, const urgym_sac_planning* planning_or_NULL, const urgym_mppi_temper* temper_or_NULL, const urgym_mppi_noise* noise_or_NULL, const urgym_normalization* normalization_or_NULL, const urgym_sac_clipping* clipping_or_NULL, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream);
+
 /* Replaces Reach*.set_goal / set_goal_and_obstacle (reach.py:202-204, 328-335, 702-713): the caller has
  * overwritten goal / obst_start / obst_end (and possibly q) for the masked envs; this recomputes obstacle pose,
  * velocity, collision, link_dist and the observation for them, leaving step_count untouched. */

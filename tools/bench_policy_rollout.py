@@ -73,6 +73,14 @@ clipped route; the unclipped one is compared with the parent commit's --entropy 
 clipped native updates alone: the program of a kernel-trace run.
     python tools/bench_policy_rollout.py --clip --windows 8 --launches 200 --out profiles/policy_rollout/dyn65536_clip.json
 
+--demos measures the demonstration ring.  The launches alone, each pair alternating in one process: urgym_replay_sample
+against urgym_replay_sample_mixed with D = M / 2 rows from a second ring of an eighth of the envs, and urgym_sac_policy_terms_cloned against
+urgym_sac_policy_terms_cloned_masked with the first M / 2 rows marked, at M = 256 and M = 65536, --launches per window, --windows windows per
+kind, timed with device events.  Then one SAC update (4096 envs, batch 256, H = 256) as one native call per window: without the option, with
+128 demonstration rows, with cloning, and with cloning on the demonstration rows only.
+
+    python tools/bench_policy_rollout.py --demos --windows 10 --launches 200 --out profiles/policy_rollout/demo_time.json
+
 --clone measures behaviour cloning in the policy terms.  First the launch alone: urgym_sac_policy_terms against
 urgym_sac_policy_terms_cloned (weight 1, scale_by_q and q_filter on) on the same seeded device tensors at M = 256 and M = 65536, --launches
 back-to-back launches per window between two device events and a synchronise, the two alternating, median of --windows; both and the
@@ -1170,6 +1178,133 @@ def clone_mode(args):
     env.close()
 
 
+def demos_mode(args):
+    """--demos: the mixed gather beside urgym_replay_sample and the masked terms beside urgym_sac_policy_terms_cloned at two batch sizes, and
+    the update without and with a demonstration ring (see above).  Every pair alternates in one process."""
+    import torch
+
+    from ur_gym_amd import make_vec
+    from ur_gym_amd.evaluation import DeviceReplay
+    from ur_gym_amd.training import SACLearner
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_policy_rollout.py measures on a GPU; none is visible")
+    dev, n, per_window = "cuda:0", min(args.num_envs, 4096), args.launches
+    env = make_vec(args.env, num_envs=n, device=dev, seed=0, auto_reset=True)
+    env.reset(seed=0)
+    env_d = make_vec(args.env, num_envs=max(1, n // 8), device=dev, seed=1, auto_reset=True)
+    env_d.reset(seed=1)
+    sync = lambda: torch.cuda.synchronize(env.device)  # noqa: E731
+    options = dict(device_action_gradient=True, device_critic_gradient=True, device_actor_gradient=True, device_optimizer=True, device_entropy=True)
+    filler = SACLearner(env_d, seed=2, batch_size=256, hidden_width=256, learning_starts=0, **options)
+    demos = DeviceReplay(env_d, 64)
+    filler.collect(demos, 64)  # the ring's content does not matter to a time: a policy fills it
+    own = DeviceReplay(env, 64)
+    plain_learner = SACLearner(env, seed=0, batch_size=256, hidden_width=256, learning_starts=0, **options)
+    plain_learner.collect(own, 64)
+
+    def windows(calls):
+        def window(call):
+            first, last = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            sync()
+            t0 = time.perf_counter()
+            first.record()
+            for _ in range(per_window):
+                call()
+            last.record()
+            sync()
+            return first.elapsed_time(last) * 1e3 / per_window, (time.perf_counter() - t0) * 1e6 / per_window
+
+        for call in calls.values():
+            for _ in range(20):
+                call()
+        wdw = {k: [] for k in calls}
+        for _ in range(args.windows):
+            for k, call in calls.items():
+                wdw[k].append(window(call))
+        sync()
+        return {"us_per_launch_device_events_median": {k: float(np.median([w[0] for w in v])) for k, v in wdw.items()},
+                "us_per_launch_wall_median": {k: float(np.median([w[1] for w in v])) for k, v in wdw.items()},
+                "us_per_launch_device_events_min": {k: float(min(w[0] for w in v)) for k, v in wdw.items()},
+                "us_per_launch_device_events_max": {k: float(max(w[0] for w in v)) for k, v in wdw.items()}}
+
+    gather, terms = {}, {}
+    for M in (256, 65536):
+        D, draw = M // 2, [0]
+        batch = own.sample(M, 0, 0, demonstrations=(demos, D))  # the tensors both gathers write
+        flat = {**batch["observations"], **{"next_" + k: v for k, v in batch["next_observations"].items()}, "action": batch["actions"], "reward": batch["rewards"],
+                "terminated": batch["terminated"], "truncated": batch["truncated"], "is_success": batch["is_success"], "index": batch["index"]}
+
+        def sample(**more):
+            draw[0] += 1
+            own.sample_into(dict(flat, **({"source": batch["source"]} if more else {})), 1, draw[0], **more)
+
+        got = windows({"replay_sample": sample, "replay_sample_mixed": lambda: sample(demonstrations=(demos, D))})
+        med = got["us_per_launch_device_events_median"]
+        gather[str(M)] = dict(got, demo_rows=D, mixed_minus_plain_us=med["replay_sample_mixed"] - med["replay_sample"])
+
+        rng = np.random.default_rng(M)
+        t = {k: torch.from_numpy(rng.standard_normal(shape).astype(np.float32)).to(dev)
+             for k, shape in dict(dqmin_da=(M, 6), q=(2, M), y=(M,), log_prob=(M,), q_min=(M,), action_pi=(M, 6), action_data=(M, 6)).items()}
+        t["action_pi"], t["action_data"] = torch.tanh(t["action_pi"]), torch.tanh(t["action_data"])
+        out = {k: torch.zeros(shape, dtype=torch.float32, device=dev) for k, shape in dict(d_action=(M, 6), critic_loss=(1,), actor_loss=(1,), bc_loss=(1,), bc_weight=(1,)).items()}
+        out["bc_rows"], ent_coef = torch.zeros((1,), dtype=torch.int32, device=dev), torch.full((1,), 0.2, dtype=torch.float32, device=dev)
+        mask = (torch.arange(M, device=dev) < D).to(torch.uint8)
+        kw = dict(dqmin_da=t["dqmin_da"], scale=-1.0 / M, d_action_out=out["d_action"], q=t["q"], y=t["y"], critic_loss_out=out["critic_loss"], log_prob=t["log_prob"],
+                  q_min=t["q_min"], actor_loss_out=out["actor_loss"], action_pi=t["action_pi"], action_data=t["action_data"], weight=1.0, bc_scale=1.0 / M, scale_by_q=True,
+                  q_filter=True, bc_loss_out=out["bc_loss"], bc_weight_out=out["bc_weight"], bc_rows_out=out["bc_rows"])
+        got = windows({"policy_terms_cloned": lambda: env.policy_terms_cloned(ent_coef, M, **kw),
+                       "policy_terms_cloned_masked": lambda: env.policy_terms_cloned_masked(ent_coef, M, row_mask=mask, **kw)})
+        med = got["us_per_launch_device_events_median"]
+        terms[str(M)] = dict(got, masked_rows=D, cloned_rows=int(out["bc_rows"].item()), masked_minus_cloned_us=med["policy_terms_cloned_masked"] - med["policy_terms_cloned"])
+
+    bc = dict(bc_weight=1.0, bc_scale_by_q=True, bc_q_filter=True)
+    demo = dict(demonstrations=demos, demo_batch_size=128)
+    routes = {"native": {}, "native_demo": demo, "native_cloned": bc, "native_demo_cloned_demo_only": dict(bc, bc_demo_only=True, **demo)}
+    learners = {}
+    for label, extra in routes.items():
+        learner = SACLearner(env, seed=0, batch_size=256, hidden_width=256, learning_starts=0, **options, **extra)
+        replay = DeviceReplay(env, 64)
+        learner.collect(replay, 4)
+        learners[label] = (learner, replay, [0])
+
+    def updates(label, count):
+        learner, replay, draw = learners[label]
+        learner.train(replay, 1, 0, count, seed=1, first_draw=draw[0] + 1)
+        draw[0] += count
+
+    def update_window(label):
+        sync()
+        t0 = time.perf_counter()
+        updates(label, per_window)
+        sync()
+        return (time.perf_counter() - t0) * 1e6 / per_window
+
+    for label in learners:
+        updates(label, 10)
+    wdw = {label: [] for label in learners}
+    for _ in range(args.windows):
+        for label in learners:
+            wdw[label].append(update_window(label))
+    med = {k: float(np.median(v)) for k, v in wdw.items()}
+    result = {"tool": "bench_policy_rollout --demos", "env": args.env, "num_envs": n, "demo_envs": env_d.num_envs, "windows": args.windows, "launches_per_window": per_window,
+              "device": torch.cuda.get_device_name(0), "gather": gather, "terms": terms, "update": {
+                  "batch": 256, "demo_batch_size": 128, "hidden_width": 256, "us_per_update_median": med, "us_per_update_min": {k: float(min(v)) for k, v in wdw.items()},
+                  "us_per_update_max": {k: float(max(v)) for k, v in wdw.items()}, "us_per_update_windows": {k: [round(x, 2) for x in v] for k, v in wdw.items()},
+                  "native_demo_minus_native_us": med["native_demo"] - med["native"],
+                  "native_demo_cloned_demo_only_minus_native_cloned_us": med["native_demo_cloned_demo_only"] - med["native_cloned"]}}
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    for learner, _, _ in learners.values():
+        learner.close()
+    filler.close(), plain_learner.close()
+    env_d.close(), env.close()
+
+
 def normalize_mode(args):
     """--normalize: the update without and with normalize, the collection step without and with the normalize launch, the fold (see above)."""
     import torch
@@ -1941,6 +2076,7 @@ def main():
     ap.add_argument("--entropy", action="store_true", help="measure the learner's update with device_optimizer only against the same plus device_entropy (see above)")
     ap.add_argument("--clip", action="store_true", help="measure the update with max_grad_norm against the update without it, as update() calls and as one native call per window (see above)")
     ap.add_argument("--clone", action="store_true", help="measure urgym_sac_policy_terms_cloned against urgym_sac_policy_terms at M = 256 and 65536, and the update with and without bc_weight (see above)")
+    ap.add_argument("--demos", action="store_true", help="measure urgym_replay_sample_mixed against urgym_replay_sample and the masked cloned terms against the cloned ones at M = 256 and 65536 (D = M / 2), and the update with and without a demonstration ring (see above)")
     ap.add_argument("--normalize", action="store_true", help="measure the update with normalize against the update without it, the collection step without and with the normalize launch, and the fold (see above)")
     ap.add_argument("--normalize-only", action="store_true", help="--normalize: run only the normalized collection, the fold and the normalized native updates (for a kernel trace)")
     ap.add_argument("--collect-steps", type=int, default=8, help="--normalize: steps per collection and per fold")
@@ -1970,6 +2106,8 @@ def main():
         return evaluate_mode(args)
     if args.clone:
         return clone_mode(args)
+    if args.demos:
+        return demos_mode(args)
     if args.clip or args.clip_only:
         return clip_mode(args)
     if args.normalize or args.normalize_only:

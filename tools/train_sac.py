@@ -49,6 +49,11 @@ policy's action is pulled towards the action the ring holds -- the planner's, wi
 times the batch's mean |min Q| (TD3+BC's normalisation), on every row or with --bc-q-filter on the rows where the critics rate the ring's
 action above the policy's own; with --native urgym_sac_train_cloned.  Every evaluation line then also carries the three losses, bc_loss,
 bc_weight and the cloned share of the batch of the latest update.
+--demo-steps T --demo-envs N_d fills a demonstration ring first: T steps of the planner the --planner* flags describe
+on a second env of N_d envs, filed into a ring of T slots that the run never writes again (--demo-save PATH keeps it as an .npz,
+--demo-load PATH reads one instead of filling).  --demo-batch-size D then draws the first D rows of every minibatch from it
+(SACLearner(demonstrations=, demo_batch_size=D), urgym_replay_sample_mixed; with --native urgym_sac_train_demonstrated), and --bc-demo-only
+restricts --bc-weight's cloning to those rows: the evaluation lines then also carry the cloned share of the demonstration rows.
 """
 import argparse
 import json
@@ -108,6 +113,20 @@ def main():
                          "cloned share with the losses (needs --device-entropy; DESIGN.md section 33)")
     ap.add_argument("--bc-scale-by-q", action="store_true", help="--bc-weight: multiply the weight by the batch's mean |min Q| (TD3+BC's normalisation)")
     ap.add_argument("--bc-q-filter", action="store_true", help="--bc-weight: clone only the rows where the critics rate the ring's action above the policy's own")
+    ap.add_argument("--demo-steps", type=int, default=0, metavar="T",
+                    help="fill a demonstration ring of T slots first, on a second env of the same kind, with the planner the --planner* flags describe "
+                         "(guided by the learner's initial networks where they ask for a guide; --planner itself is not needed; DESIGN.md section 34)")
+    ap.add_argument("--demo-guide", nargs=3, metavar=("ACTOR.npz", "CRITIC0.npz", "CRITIC1.npz"), default=None,
+                    help="--demo-steps: guide the demonstrating planner with these plain parameter files (as --init-from reads them) instead of the "
+                         "learner's initial networks: a demonstrator that already knows the task")
+    ap.add_argument("--demo-envs", type=int, default=64, metavar="N_d", help="--demo-steps, --demo-load: envs of the demonstration ring's env")
+    ap.add_argument("--demo-save", metavar="PATH", default=None, help="write the demonstration ring as an .npz (DeviceReplay.save) once it is filled")
+    ap.add_argument("--demo-load", metavar="PATH", default=None,
+                    help="read the demonstration ring from a file --demo-save wrote, with the same --demo-steps (its capacity) and --demo-envs, instead of filling it")
+    ap.add_argument("--demo-batch-size", type=int, default=None, metavar="D",
+                    help="draw the first D rows of every minibatch from the demonstration ring (needs --device-entropy and --demo-steps; not with "
+                         "--n-steps above 1, --prioritized or --hindsight)")
+    ap.add_argument("--bc-demo-only", action="store_true", help="--bc-weight with --demo-batch-size: clone only the demonstration rows")
     ap.add_argument("--normalize", action="store_true",
                     help="running observation and reward normalization on the device (SB3's VecNormalize; needs --device-entropy)")
     ap.add_argument("--no-norm-obs", action="store_true", help="--normalize: leave the observations as they are")
@@ -163,6 +182,12 @@ def main():
         raise SystemExit("--planner plans on raw rows: not with --normalize (the planner's actor and critic read raw rows)")
     if (args.bc_scale_by_q or args.bc_q_filter) and args.bc_weight is None:
         raise SystemExit("--bc-scale-by-q and --bc-q-filter qualify --bc-weight and need it")
+    if args.demo_batch_size is not None and args.demo_steps < 1:
+        raise SystemExit("--demo-batch-size needs a demonstration ring: give --demo-steps T (with --demo-load, the capacity of the file's ring)")
+    if (args.demo_save or args.demo_load) and args.demo_steps < 1:
+        raise SystemExit("--demo-save and --demo-load need --demo-steps T, the capacity of the ring")
+    if args.bc_demo_only and (args.bc_weight is None or args.demo_batch_size is None):
+        raise SystemExit("--bc-demo-only needs --bc-weight and --demo-batch-size")
     if args.save_every and not args.save:
         raise SystemExit("--save-every needs --save")
     if args.save_every < 0:
@@ -181,6 +206,15 @@ def main():
     env = make_vec(args.env, num_envs=args.num_envs, seed=args.seed, auto_reset=True)
     env.reset(seed=args.seed)
     test_env = make_vec(args.env, num_envs=args.eval_envs, seed=args.seed + 1, auto_reset=False)
+    demo_env = demos = None
+    if args.demo_steps > 0:  # the ring exists before the learner, which checks it; it is filled below, once the planner can be made
+        demo_env = make_vec(args.env, num_envs=args.demo_envs, seed=args.seed + 2, auto_reset=True)
+        demo_env.reset(seed=args.seed + 2)
+        demos = DeviceReplay(demo_env, args.demo_steps)
+        if args.demo_load:
+            demos.load_file(args.demo_load)
+        else:
+            demos.cursor, demos.filled = 0, args.demo_steps  # what the fill below leaves: the learner refuses an empty ring
     learner = SACLearner(env, seed=args.seed, hidden_width=args.hidden_width, batch_size=args.batch_size,
                          device_action_gradient=args.device_action_gradient, device_critic_gradient=args.device_critic_gradient,
                          device_actor_gradient=args.device_actor_gradient, device_optimizer=args.device_optimizer,
@@ -189,15 +223,26 @@ def main():
                          **(dict(hindsight=True, her_n_sampled_goal=args.her_n_sampled_goal, her_strategy=args.her_strategy) if args.hindsight else {}),
                          **(dict(max_grad_norm=args.max_grad_norm) if args.max_grad_norm is not None else {}),
                          **(dict(bc_weight=args.bc_weight, bc_scale_by_q=args.bc_scale_by_q, bc_q_filter=args.bc_q_filter) if args.bc_weight is not None else {}),
+                         **(dict(demonstrations=demos, demo_batch_size=args.demo_batch_size, bc_demo_only=args.bc_demo_only) if args.demo_batch_size is not None else {}),
                          **(dict(normalize=True, norm_obs=not args.no_norm_obs, norm_reward=not args.no_norm_reward, clip_obs=args.clip_obs,
                                  clip_reward=args.clip_reward, norm_epsilon=args.norm_epsilon) if args.normalize else {}))
     normalizer = learner.normalizer  # None without --normalize
     eval_actor = DeviceActor(host_arrays(learner.actor.tensors()), test_env)  # actors belong to the environment they were made for
     replay = DevicePrioritizedReplay(env, args.capacity, alpha=args.per_alpha) if args.prioritized else DeviceReplay(env, args.capacity)
-    planner = None
-    if args.planner:  # guided by copies of the learner's own networks, kept current by sync_planner
+    planner, t_demo = None, time.perf_counter()
+
+    def make_planner(of_env, guide=None):
         guided = args.planner_policy_samples > 0 or args.planner_terminal_value
-        planner = DeviceMPPI(env, samples=args.planner_samples, horizon=args.planner_horizon, sigma=args.planner_sigma, lam=args.planner_lam,
+        if guide is not None:
+            import numpy as np
+
+            return DeviceMPPI(of_env, samples=args.planner_samples, horizon=args.planner_horizon, sigma=args.planner_sigma, lam=args.planner_lam,
+                              gamma=learner.hp["gamma"] if args.planner_terminal_value else 1.0, seed=args.seed, actor=dict(np.load(guide[0])) if guided else None,
+                              critic=[dict(np.load(p)) for p in guide[1:]] if args.planner_terminal_value else None, policy_samples=args.planner_policy_samples,
+                              policy_sigma=args.planner_policy_sigma if args.planner_policy_samples else 0.0, terminal_value=args.planner_terminal_value,
+                              fail_cost=args.planner_fail_cost, iterations=args.planner_iterations, elites=args.planner_elites, adapt_std=args.planner_adapt_std,
+                              std_min=args.planner_std_min, std_max=args.planner_std_max, ess_target=args.planner_ess_target, noise_beta=args.planner_noise_beta)
+        return DeviceMPPI(of_env, samples=args.planner_samples, horizon=args.planner_horizon, sigma=args.planner_sigma, lam=args.planner_lam,
                              gamma=learner.hp["gamma"] if args.planner_terminal_value else 1.0, seed=args.seed,
                              actor=host_arrays(learner.actor.tensors()) if guided else None,
                              critic=host_arrays(learner.critic.tensors()) if args.planner_terminal_value else None,
@@ -205,6 +250,20 @@ def main():
                              terminal_value=args.planner_terminal_value, fail_cost=args.planner_fail_cost, iterations=args.planner_iterations,
                              elites=args.planner_elites, adapt_std=args.planner_adapt_std, std_min=args.planner_std_min, std_max=args.planner_std_max,
                              ess_target=args.planner_ess_target, noise_beta=args.planner_noise_beta)
+
+    if args.planner:  # guided by copies of the learner's own networks, kept current by sync_planner
+        planner = make_planner(env)
+    if demos is not None and not args.demo_load:  # the demonstrations: the planner's own transitions on the second env, T steps into T slots
+        demonstrator = make_planner(demo_env, args.demo_guide)
+        demos.cursor = demos.filled = 0
+        demos.collect_planned(demonstrator, args.demo_steps, first_draw=0, explore_sigma=args.planner_explore_sigma)
+        torch.cuda.synchronize()
+        ok = demos.ring["is_success"].float().mean().item()
+        print(json.dumps({"demo_steps": args.demo_steps, "demo_envs": args.demo_envs, "demo_transitions": len(demos), "demo_success_flag_share": ok,
+                          "demo_mean_reward": demos.ring["reward"].mean().item(), "seconds": round(time.perf_counter() - t_demo, 1)}), flush=True)
+        demonstrator.close()
+    if demos is not None and args.demo_save:
+        demos.save(args.demo_save)
     updates, t0 = 0, time.perf_counter()
     best = dict(mean=-float("inf"), tensors=None)  # the Python route's own best_model
     if args.monitor and args.log_every < 1:
@@ -217,6 +276,8 @@ def main():
     def cloned_share(values):
         """bc_rows of a line becomes the share of the batch that was cloned."""
         if "bc_rows" in values:
+            if args.bc_demo_only and args.demo_batch_size:  # only demonstration rows can be cloned: their cloned share as well
+                values["bc_cloned_share_of_demos"] = values["bc_rows"] / args.demo_batch_size
             values["bc_cloned_share"] = values.pop("bc_rows") / args.batch_size
         return values
 
@@ -254,7 +315,7 @@ def main():
     points = evaluation_points(1, args.steps, args.updates_per_step, idle, args.eval_every) if args.steps > 0 else []
     ev = DeviceEvaluation(test_env, learner.actor.tensors(), seed=args.seed + 1, capacity=max(1, len(points)),
                           **(dict(normalizer=normalizer) if normalizer is not None else {})) if args.native else None
-    parts = dict(replay=replay, monitor=mon, evaluation=ev)
+    parts = dict(replay=replay, monitor=mon, evaluation=ev, **(dict(demonstrations=demos) if args.demo_batch_size is not None else {}))
     step = shown_evals = shown_curve = 0
     if args.resume:
         extra = learner.load(args.resume, **parts)  # refuses another env, width, option set or hyperparameter, naming it
@@ -345,6 +406,8 @@ def main():
     learner.close()
     test_env.close()
     env.close()
+    if demo_env is not None:
+        demo_env.close()
 
 
 if __name__ == "__main__":

@@ -223,6 +223,7 @@ class ActorParamGrads(C.Structure):
 ACTOR_GRADIENTS_MAX_COUNT = 65536  # URGYM_ACTOR_GRADIENTS_MAX_COUNT
 
 REPLAY_TAG = 0x52504C00  # word 3 of the Philox counter of urgym_replay_sample's index draw
+DEMO_TAG = 0x44454D00  # URGYM_DEMO_TAG: word 3 of the counter of a draw from the demonstrations (urgym_replay_sample_mixed)
 
 # urgym_replay_ring after capacity_steps / reserved0: name -> (ctype of element, shape given (C, N, obs_dim, goal_dim), required)
 REPLAY_RING_FIELDS = [
@@ -670,6 +671,19 @@ class SacCloning(C.Structure):
                 ("bc_loss", C.POINTER(C.c_float)), ("bc_weight", C.POINTER(C.c_float)), ("bc_rows", C.POINTER(C.c_int32))]
 
 
+class ReplayDemonstrations(C.Structure):
+    """urgym_replay_demonstrations: the demonstration ring of urgym_replay_sample_mixed -- a ring of the same env kind with its own env
+    count, cursor and fill level, and D, the number of leading rows of a minibatch that come from it."""
+    _fields_ = [("ring", ReplayRing), ("num_envs", C.c_int32), ("oldest_slot", C.c_int32), ("filled_steps", C.c_int32), ("count", C.c_int32)]
+
+
+class SacDemonstrating(C.Structure):
+    """urgym_sac_demonstrating: the option of urgym_sac_train_demonstrated -- the demonstrations, the [M] scratch the gather's source goes
+    to, and whether cloning applies to demonstration rows only."""
+    _fields_ = [("demonstrations", ReplayDemonstrations), ("source", C.POINTER(C.c_uint8)), ("clone_demonstrations_only", C.c_int32),
+                ("reserved0", C.c_int32)]
+
+
 # Every symbol include/urgym.h declares (tests check that the built library exports each of them).
 EXPORTED_SYMBOLS = [
     "urgym_abi_version",
@@ -774,6 +788,9 @@ EXPORTED_SYMBOLS = [
     "urgym_sac_train_colored",
     "urgym_sac_policy_terms_cloned",
     "urgym_sac_train_cloned",
+    "urgym_replay_sample_mixed",
+    "urgym_sac_policy_terms_cloned_masked",
+    "urgym_sac_train_demonstrated",
     "urgym_refresh",
     "urgym_invalidate_records",
     "urgym_derive_obstacle_motion",

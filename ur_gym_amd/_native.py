@@ -191,6 +191,13 @@ def lib():
                                          C.POINTER(_abi.SacPlanning), C.POINTER(_abi.MppiTemper), C.POINTER(_abi.MppiNoise), C.POINTER(_abi.Normalization),
                                          C.POINTER(_abi.SacClipping), C.POINTER(_abi.SacNstep), C.POINTER(_abi.SacPrioritized), C.POINTER(_abi.SacHindsight),
                                          C.POINTER(_abi.SacEvaluation), C.POINTER(_abi.SacMonitoring), C.c_void_p]
+    L.urgym_replay_sample_mixed.argtypes = [C.c_void_p, C.POINTER(_abi.ReplayRing), C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_int,
+                                            C.POINTER(_abi.ReplayBatch), C.POINTER(_abi.ReplayDemonstrations), C.c_void_p, C.c_void_p]
+    L.urgym_sac_policy_terms_cloned_masked.argtypes = [C.c_void_p, C.POINTER(_abi.SacPolicyArgs), C.POINTER(_abi.SacCloneArgs), C.c_void_p, C.c_void_p]
+    L.urgym_sac_train_demonstrated.argtypes = [C.c_void_p, C.POINTER(_abi.SacLearner), C.POINTER(_abi.SacSchedule), C.POINTER(_abi.SacDemonstrating),
+                                               C.POINTER(_abi.SacCloning), C.POINTER(_abi.SacPlanning), C.POINTER(_abi.MppiTemper), C.POINTER(_abi.MppiNoise),
+                                               C.POINTER(_abi.Normalization), C.POINTER(_abi.SacClipping), C.POINTER(_abi.SacEvaluation),
+                                               C.POINTER(_abi.SacMonitoring), C.c_void_p]
     L.urgym_actor_read_packed.argtypes =[C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.urgym_critic_read_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.urgym_refresh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]

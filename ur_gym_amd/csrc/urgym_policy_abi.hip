@@ -2,7 +2,7 @@
 // added here leaves every kernel's object file alone.  Every check is made here, before the first launch; every launch goes through the
 // kernel units' headers (urgym_actor.h ... urgym_norm.h) or through do_step of urgym_hip.hip (urgym_handle.h).  In file order:
 //   - actors: create / forward / sample, the rollouts, urgym_rollout_collect; the replay ring and its gathers (urgym_replay.h,
-//     urgym_nstep.h, urgym_her.h)
+//     urgym_nstep.h, urgym_her.h, urgym_demo.h)
 //   - the twin critic, its action gradient and parameter gradients; the actor's parameter gradients
 //   - the Adam steps (urgym_adam.h) and gradient-norm clipping (urgym_grad_clip.h)
 //   - SAC's entropy step and loss terms (urgym_sac_terms.h)
@@ -27,6 +27,7 @@
 #include "urgym_pack_map.h"
 #include "urgym_weights.h"
 #include "urgym_replay.h"
+#include "urgym_demo.h"
 #include "urgym_nstep.h"
 #include "urgym_her.h"
 #include "urgym_adam.h"
@@ -566,6 +567,34 @@ int check_replay_sample(Handle* h, const urgym_replay_ring* ring, int oldest_slo
   return URGYM_OK;
 }
 
+// urgym_replay_sample_mixed: check_replay_sample's refusals first, then the demonstrations'
+int check_replay_sample_mixed(Handle* h, const urgym_replay_ring* ring, int oldest_slot, int filled_steps, uint64_t seed, uint64_t draw, int count,
+                              const urgym_replay_batch* batch, const urgym_replay_demonstrations* demo, uint8_t* source_out, const char* who, ReplayGatherMixed* out) {
+  static_assert(URGYM_DEMO_TAG == DEMO_TAG, "include/urgym.h");
+  if (int rc = check_replay_sample(h, ring, oldest_slot, filled_steps, seed, draw, count, batch, who, &out->g)) return rc;
+  if (!demo) return fail_in(h, URGYM_ERR_ARG, who, "null demonstrations");
+  const urgym_replay_demonstrations& d = *demo;
+  const urgym_replay_ring& r = d.ring;
+  if (r.capacity_steps <= 0) return fail_in(h, URGYM_ERR_ARG, who, "demonstrations: ring.capacity_steps must be positive");
+  if (r.reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "demonstrations: urgym_replay_ring.reserved0 must be 0");
+  if (!r.observation || !r.achieved_goal || !r.desired_goal || !r.action || !r.reward || !r.next_observation || !r.next_achieved_goal ||
+      !r.next_desired_goal || !r.terminated)
+    return fail_in(h, URGYM_ERR_ARG, who, "demonstrations: a required ring pointer is null (all but truncated and is_success)");
+  if (d.num_envs < 1) return fail_in(h, URGYM_ERR_ARG, who, "demonstrations: num_envs must be at least 1");
+  if (d.oldest_slot < 0 || d.oldest_slot >= r.capacity_steps) return fail_in(h, URGYM_ERR_ARG, who, "demonstrations: oldest_slot outside [0, capacity_steps)");
+  if (d.filled_steps < 1 || d.filled_steps > r.capacity_steps) return fail_in(h, URGYM_ERR_ARG, who, "demonstrations: filled_steps outside [1, capacity_steps]");
+  if (d.count < 0 || d.count > count) return fail_in(h, URGYM_ERR_ARG, who, "demonstrations: count outside [0, count]");
+  // two positive int32: the product is below 2^62, stated as a check so that the entry arithmetic never depends on the types
+  const uint64_t size_d = (uint64_t)d.filled_steps * (uint64_t)d.num_envs;
+  if (size_d >= (uint64_t)1 << 63) return fail_in(h, URGYM_ERR_ARG, who, "demonstrations: filled_steps * num_envs must be below 2^63");
+  if ((batch->truncated && !r.truncated) || (batch->is_success && !r.is_success))
+    return fail_in(h, URGYM_ERR_ARG, who, "truncated / is_success asked while the demonstration ring does not keep it");
+  out->demo = r;
+  out->demo_side = DemoSide{size_d, d.num_envs, r.capacity_steps, d.oldest_slot};
+  out->demo_count = d.count, out->source_out = source_out;
+  return URGYM_OK;
+}
+
 // urgym_replay_sample_nstep: check_replay_sample's refusals first, then the window's
 int check_replay_sample_nstep(Handle* h, const urgym_replay_ring* ring, int oldest_slot, int filled_steps, uint64_t seed, uint64_t draw, int count,
                               const urgym_replay_batch* batch, const urgym_replay_nstep* nstep, const char* who, ReplayGatherNstep* out) {
@@ -859,6 +888,21 @@ int urgym_sac_policy_terms_cloned(void* handle, const urgym_sac_policy_args* arg
   return launched(h);
 }
 
+// the cloned policy terms on marked rows only (urgym_sac_bc_masked.hip)
+int urgym_sac_policy_terms_cloned_masked(void* handle, const urgym_sac_policy_args* args, const urgym_sac_clone_args* clone, const uint8_t* row_mask, void* stream) {
+  const char* who = "urgym_sac_policy_terms_cloned_masked";
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  SacPolicyCall c;
+  SacCloneCall b;
+  if (int rc = check_policy_terms(h, args, who, &c)) return rc;
+  if (int rc = check_policy_terms_cloned(h, c, clone, who, &b)) return rc;
+  if (!row_mask) return fail_in(h, URGYM_ERR_ARG, who, "null row_mask");
+  HIP_TRY(h, hipSetDevice(h->device));
+  sac_policy_bc_masked_launch(c, b, row_mask, (hipStream_t)stream);
+  return launched(h);
+}
+
 // ---- weights from the device (urgym_weights.hip): everything is checked here, before the launch
 int urgym_actor_load(void* handle, void* actor, const urgym_actor_params_dev* p, void* stream) {
   Handle* h = (Handle*)handle;
@@ -1086,6 +1130,17 @@ int urgym_replay_sample(void* handle, const urgym_replay_ring* ring, int oldest_
   if (int rc = check_replay_sample(h, ring, oldest_slot, filled_steps, seed, draw, count, batch, "urgym_replay_sample", &g)) return rc;
   HIP_TRY(h, hipSetDevice(h->device));
   replay_gather_launch(g, (hipStream_t)stream);
+  return launched(h);
+}
+
+// the mixed gather of the demonstration ring (urgym_demo.hip)
+int urgym_replay_sample_mixed(void* handle, const urgym_replay_ring* ring, int oldest_slot, int filled_steps, uint64_t seed, uint64_t draw, int count, const urgym_replay_batch* batch, const urgym_replay_demonstrations* demo, uint8_t* source_out, void* stream) {
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  ReplayGatherMixed g;
+  if (int rc = check_replay_sample_mixed(h, ring, oldest_slot, filled_steps, seed, draw, count, batch, demo, source_out, "urgym_replay_sample_mixed", &g)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  replay_gather_mixed_launch(g, (hipStream_t)stream);
   return launched(h);
 }
 
@@ -1801,6 +1856,8 @@ struct TrainOptions {
   const urgym_mppi_temper* temper;         // with planning: the planner's update is the tempered one (urgym_sac_train_tempered)
   const urgym_mppi_noise* noise;           // with planning: the planner's sample is the coloured one (urgym_sac_train_colored)
   const urgym_sac_cloning* cloning;        // the update whose policy terms are urgym_sac_policy_terms_cloned's (urgym_sac_train_cloned)
+  const urgym_sac_demonstrating* demonstrating;  // the update whose gather is urgym_replay_sample_mixed's; with cloning and
+                                                 // clone_demonstrations_only its policy terms are the masked ones (urgym_sac_train_demonstrated)
 };
 
 // The evaluations and the training-episode statistics of one training call: what the body runs beside its own checks and launches.
@@ -1907,7 +1964,7 @@ struct TrainExtras {
   }
 };
 
-// The one driver of the twelve urgym_sac_train* entry points: `who` is the entry point's own name in every refusal, `opt` what it was given.
+// The one driver of the thirteen urgym_sac_train* entry points: `who` is the entry point's own name in every refusal, `opt` what it was given.
 int sac_train_body(const char* who, Handle* h, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, hipStream_t s, const TrainOptions& opt) {
   if (!learner) return fail_in(h, URGYM_ERR_ARG, who, "null learner");
   if (!schedule) return fail_in(h, URGYM_ERR_ARG, who, "null schedule");
@@ -1918,6 +1975,7 @@ int sac_train_body(const char* who, Handle* h, const urgym_sac_learner* learner,
   const urgym_normalization* const norm = opt.norm;
   const urgym_sac_planning* const planning = opt.planning;
   const urgym_sac_cloning* const cloning = opt.cloning;
+  const urgym_sac_demonstrating* const demonstrating = opt.demonstrating;
   PlannedCall planned;
   TrainExtras extras{who, h, learner, schedule, s, opt.evaluation, opt.monitoring, norm, planning ? &planned : nullptr};
   const urgym_sac_learner& L = *learner;
@@ -1981,6 +2039,17 @@ int sac_train_body(const char* who, Handle* h, const urgym_sac_learner* learner,
     if (const char* what = clone_option_refusal(cloning->weight, cloning->scale_by_q, cloning->q_filter, cloning->reserved0)) return fail_in(h, URGYM_ERR_ARG, who, what);
     if ((!cloning->bc_loss || !cloning->bc_weight || !cloning->bc_rows) && sac_schedule_updates(S) > 0)  // zero slots need no array
       return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_cloning.bc_loss, bc_weight or bc_rows is null");
+  }
+  ReplayGatherMixed gather_mixed;
+  if (demonstrating) {  // the option's own refusals, whether or not the call holds an update: the gather's checks on the ring as it stands
+    const urgym_sac_demonstrating& dm = *demonstrating;
+    if (dm.reserved0 != 0) return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_demonstrating.reserved0 must be 0");
+    if (dm.clone_demonstrations_only != 0 && dm.clone_demonstrations_only != 1) return fail_in(h, URGYM_ERR_ARG, who, "clone_demonstrations_only must be 0 or 1");
+    if (dm.clone_demonstrations_only != 0 && !cloning) return fail_in(h, URGYM_ERR_ARG, who, "clone_demonstrations_only needs cloning");
+    if (L.count <= 0) return fail_in(h, URGYM_ERR_ARG, who, "count must be positive");
+    if (dm.demonstrations.count > L.count) return fail_in(h, URGYM_ERR_ARG, who, "demonstrations.count is above the learner's count (D > M)");
+    if (int rc = check_replay_sample_mixed(h, &L.ring, 0, 1, L.update_seed, 0, L.count, &L.batch, &dm.demonstrations, dm.source, who, &gather_mixed)) return rc;
+    if (!dm.source && sac_schedule_updates(S) > 0) return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_demonstrating.source is null");
   }
   if (planning) {  // the planner's own refusals and the collection's, whether or not the call holds an update
     if (int rc = planned_check(who, h, planning, &L.ring, S, &planned, opt.temper, opt.noise)) return rc;
@@ -2075,6 +2144,10 @@ int sac_train_body(const char* who, Handle* h, const urgym_sac_learner* learner,
   if (her)
     if (int rc = check_replay_sample_hindsight(h, &L.ring, view.oldest_slot, view.filled_steps, L.update_seed, first.gather_draw, M, &L.batch, &her_rule, who, &gather_her))
       return rc;
+  if (demonstrating)
+    if (int rc = check_replay_sample_mixed(h, &L.ring, view.oldest_slot, view.filled_steps, L.update_seed, first.gather_draw, M, &L.batch,
+                                           &demonstrating->demonstrations, demonstrating->source, who, &gather_mixed))
+      return rc;
   PerGather per_gather;
   memset(&per_gather, 0, sizeof(per_gather));
   if (per) {  // urgym_replay_sample_prioritized
@@ -2168,6 +2241,7 @@ int sac_train_body(const char* who, Handle* h, const urgym_sac_learner* learner,
     ca.bc_loss_out = cloning->bc_loss, ca.bc_weight_out = cloning->bc_weight, ca.bc_rows_out = cloning->bc_rows;
     if (int rc = check_policy_terms_cloned(h, terms_call, &ca, who, &clone_call)) return rc;
   }
+  const bool clone_masked = cloning && demonstrating && demonstrating->clone_demonstrations_only != 0;  // row_mask = source
   const urgym_actor_upstream upstream{L.d_action, L.d_log_prob, nullptr, nullptr};
   urgym_actor_param_grads ag;
   memset(&ag, 0, sizeof(ag));
@@ -2203,13 +2277,17 @@ int sac_train_body(const char* who, Handle* h, const urgym_sac_learner* learner,
     gather.oldest_slot = it.oldest_slot, gather.size = (uint64_t)it.filled_steps * (uint64_t)h->cfg.num_envs;
     gather_nstep.filled_steps = it.filled_steps;
     if (her) gather_her.g.oldest_slot = gather.oldest_slot, gather_her.g.size = gather.size, gather_her.filled_steps = it.filled_steps;
+    if (demonstrating) gather_mixed.g.oldest_slot = gather.oldest_slot, gather_mixed.g.size = gather.size;
     for (int g = 0; g < G; g++, u++) {
       const SacUpdate up = sac_schedule_update(S, u);
       const AdamCoef coef = adam_coefficients(L.lr, L.beta1, L.beta2, L.eps, up.adam_step);  // urgym_adam_coefficients' own function
       gather.draw = up.gather_draw;
       per_gather.g.draw = up.gather_draw;
       gather_her.g.draw = up.gather_draw;
-      if (her)
+      gather_mixed.g.draw = up.gather_draw;
+      if (demonstrating)
+        replay_gather_mixed_launch(gather_mixed, s);
+      else if (her)
         replay_gather_hindsight_launch(gather_her, s);
       else if (per)
         per_gather_launch(per_gather, s);
@@ -2263,7 +2341,10 @@ int sac_train_body(const char* who, Handle* h, const urgym_sac_learner* learner,
       if (cloning) {
         clone_call.bc_loss_out = cloning->bc_loss + up.loss_slot, clone_call.bc_weight_out = cloning->bc_weight + up.loss_slot;
         clone_call.bc_rows_out = cloning->bc_rows + up.loss_slot;
-        sac_policy_bc_launch(terms_call, clone_call, s);
+        if (clone_masked)
+          sac_policy_bc_masked_launch(terms_call, clone_call, demonstrating->source, s);
+        else
+          sac_policy_bc_launch(terms_call, clone_call, s);
       } else {
         sac_policy_launch(terms_call, s);
       }
@@ -2314,7 +2395,7 @@ const char* const ONE_GATHER = "at most one of nstep, prioritized and hindsight 
 extern "C" {
 
 // Each entry point: the null handle, its own required option, then the driver with what it was given.  TrainOptions' order is
-// {nstep, per, her, clip, norm, evaluation, monitoring, planning, temper, noise, cloning}.
+// {nstep, per, her, clip, norm, evaluation, monitoring, planning, temper, noise, cloning, demonstrating}.
 
 int urgym_sac_train(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, void* stream) {
   Handle* h = (Handle*)handle;
@@ -2418,6 +2499,16 @@ int urgym_sac_train_cloned(void* handle, const urgym_sac_learner* learner, const
   if (planning_or_NULL && normalization_or_NULL) return fail_in(h, URGYM_ERR_ARG, who, "normalization together with planning is out of scope (the planner's actor and critic read raw rows)");
   if ((nstep_or_NULL != nullptr) + (prioritized_or_NULL != nullptr) + (hindsight_or_NULL != nullptr) > 1) return fail_in(h, URGYM_ERR_ARG, who, ONE_GATHER);
   return sac_train_body(who, h, learner, schedule, (hipStream_t)stream, TrainOptions{nstep_or_NULL, prioritized_or_NULL, hindsight_or_NULL, clipping_or_NULL, normalization_or_NULL, evaluation_or_NULL, monitoring_or_NULL, planning_or_NULL, temper_or_NULL, noise_or_NULL, cloning});
+}
+
+int urgym_sac_train_demonstrated(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_demonstrating* demonstrating, const urgym_sac_cloning* cloning_or_NULL, const urgym_sac_planning* planning_or_NULL, const urgym_mppi_temper* temper_or_NULL, const urgym_mppi_noise* noise_or_NULL, const urgym_normalization* normalization_or_NULL, const urgym_sac_clipping* clipping_or_NULL, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream) {
+  const char* who = "urgym_sac_train_demonstrated";
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (!demonstrating) return fail_in(h, URGYM_ERR_ARG, who, "null demonstrating");
+  if (!planning_or_NULL && (temper_or_NULL || noise_or_NULL)) return fail_in(h, URGYM_ERR_ARG, who, "temper and noise are the planner's and need planning");
+  if (planning_or_NULL && normalization_or_NULL) return fail_in(h, URGYM_ERR_ARG, who, "normalization together with planning is out of scope (the planner's actor and critic read raw rows)");
+  return sac_train_body(who, h, learner, schedule, (hipStream_t)stream, TrainOptions{nullptr, nullptr, nullptr, clipping_or_NULL, normalization_or_NULL, evaluation_or_NULL, monitoring_or_NULL, planning_or_NULL, temper_or_NULL, noise_or_NULL, cloning_or_NULL, demonstrating});
 }
 
 }  // extern "C"

@@ -20,6 +20,12 @@ URGYM_HD inline float sac_bc_q_data(float q0, float q1) { return q1 < q0 ? q1 : 
 // either side, or a tie, gives not cloned.  Without the filter every row is cloned.
 URGYM_HD inline bool sac_bc_cloned(bool q_filter, float q_data, float q_min) { return q_filter ? (q_data > q_min) : true; }
 
+// THE MASKED VERDICT (urgym_sac_policy_terms_cloned_masked): only a row the caller marks -- one a demonstrator
+// filed -- can be cloned; a marked row is cloned as above.  ur_gym_amd.evaluation.policy_terms_cloned(row_mask=) restates it.
+URGYM_HD inline bool sac_bc_cloned_masked(uint8_t mask, bool q_filter, float q_data, float q_min) {
+  return mask != 0 && sac_bc_cloned(q_filter, q_data, q_min);
+}
+
 // one difference of the two actions
 URGYM_HD inline float sac_bc_difference(float action_pi, float action_data) { return action_pi - action_data; }
 
@@ -62,6 +68,9 @@ struct SacCloneCall {
 
 // ONE launch of ONE workgroup of SAC_TERMS_LANES lanes on `s`.  The caller has validated everything: all three groups of `call` given.
 void sac_policy_bc_launch(const SacPolicyCall& call, const SacCloneCall& clone, hipStream_t s);
+
+// The same launch with the masked verdict (urgym_sac_bc_masked.hip, a unit of its own): row_mask is a DEVICE pointer, [count], not null
+void sac_policy_bc_masked_launch(const SacPolicyCall& call, const SacCloneCall& clone, const uint8_t* row_mask, hipStream_t s);
 
 }  // namespace urgym
 #endif

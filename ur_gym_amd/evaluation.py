@@ -104,6 +104,38 @@ def replay_indices(seed, draw, count, size):
     return np.array([((int(hi) << 32 | int(lo)) * size) >> 64 for hi, lo in zip(w[0], w[1])], dtype=np.int64).reshape(count)
 
 
+def mixed_indices(seed, draw, count, size, demo_count, demo_size):
+    """The entries urgym_replay_sample_mixed draws, restated from include/urgym.h ("the demonstration ring"): int64 [count].  Row i <
+    `demo_count` holds e = (w * demo_size) >> 64 with w of the Philox call at the counter (i, draw lo, draw hi, DEMO_TAG), an entry number
+    of the DEMONSTRATION ring's `demo_size` = filled_d * N_d entries; row i >= `demo_count` holds ``replay_indices``' row i.  A function
+    of (seed, draw, i, size, demo_size) alone.  The caller maps e to slot and env with the numbers of the row's own ring; ``source`` is
+    ``arange(count) < demo_count``.  With ``demo_count == 0`` `demo_size` is not looked at beyond its range."""
+    from . import _abi
+
+    seed, draw, count, size, D, size_d = int(seed), int(draw), int(count), int(size), int(demo_count), int(demo_size)
+    if not 0 <= D <= count:
+        raise ValueError(f"demo_count must be in [0, count], got {D} of {count}")
+    if not 0 < size_d < 1 << 63:
+        raise ValueError(f"demo_size must be in [1, 2^63), got {size_d}")
+    out = replay_indices(seed, draw, count, size)
+    key = (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
+    w = philox4x32_10(key, (np.arange(D, dtype=np.uint64), np.uint64(draw & 0xFFFFFFFF), np.uint64((draw >> 32) & 0xFFFFFFFF), np.uint64(_abi.DEMO_TAG)))
+    out[:D] = np.array([((int(hi) << 32 | int(lo)) * size_d) >> 64 for hi, lo in zip(w[0], w[1])], dtype=np.int64).reshape(D)
+    return out
+
+
+def mixed_entries(seed, draw, count, own, demo_count, demo):
+    """``mixed_indices`` mapped to flat ring entries: `own` and `demo` are (oldest_slot, filled_steps, num_envs, capacity_steps) of the
+    learner's ring and of the demonstration ring.  Returns (index int64 [count], source bool [count]): index = slot * N + env in the
+    row's own ring, slot = (oldest_slot + e // N) % C, env = e % N."""
+    e = mixed_indices(seed, draw, count, own[1] * own[2], demo_count, demo[1] * demo[2])
+    source = np.arange(int(count)) < int(demo_count)
+    index = np.empty(int(count), dtype=np.int64)
+    for mask, (oldest, _, n, cap) in ((source, demo), (~source, own)):
+        index[mask] = ((oldest + e[mask] // n) % cap) * n + e[mask] % n
+    return index, source
+
+
 def training_schedule(*, first_slot, filled_steps, capacity_steps, num_iterations, steps_per_iteration=1, updates_per_iteration=1,
                       uniform_iterations=0, idle_iterations=0, collect_first_draw=0, update_first_draw=0, first_step=1):
     """The index arithmetic of one urgym_sac_train call, restated from include/urgym.h (``urgym_sac_schedule``) and
@@ -801,13 +833,16 @@ def policy_terms(alpha, *, dqmin_da=None, scale=None, q=None, y=None, log_prob=N
 
 
 def policy_terms_cloned(alpha, *, dqmin_da, scale, q, y, log_prob, q_min, action_pi, action_data, weight, bc_scale, scale_by_q=False, q_filter=False,
-                        w_mean_abs=None):
+                        w_mean_abs=None, row_mask=None):
     """urgym_sac_policy_terms_cloned restated from include/urgym.h in numpy float32, line by line, the means by ``ordered_sum``.  The
     arguments of ``policy_terms`` (all three groups, `q` the online critics at the replayed action) and `action_pi`, `action_data`
     [count, 6], `weight`, `bc_scale`, the two flags.  `w_mean_abs`: None, or the float32 to take for the mean of ``|q_min|`` in the
     weight instead of this function's own (a test that feeds another reduction's value).  Returns a dict: ``d_action`` [count, 6],
     ``critic_loss``, ``actor_loss``, ``bc_loss``, ``bc_weight`` (float32 scalars), ``bc_rows`` (int32), ``cloned`` (bool [count]),
-    ``mean_abs`` (float32) and ``bc_terms`` (h, float32 [count])."""
+    ``mean_abs`` (float32) and ``bc_terms`` (h, float32 [count]).
+
+    With `row_mask` ([count], uint8 or bool) the call restated is urgym_sac_policy_terms_cloned_masked: a row is cloned only where its
+    mask is nonzero AND the verdict above holds; everything else is unchanged (the means stay over all rows)."""
     f = np.float32
     out = policy_terms(alpha, dqmin_da=dqmin_da, scale=scale, q=q, y=y, log_prob=log_prob, q_min=q_min)
     g = out.pop("d_action")
@@ -820,6 +855,11 @@ def policy_terms_cloned(alpha, *, dqmin_da, scale, q, y, log_prob, q_min, action
             raise ValueError(f"weight must be finite and >= 0 and bc_scale finite in float32, got {weight!r}, {bc_scale!r}")
         qd = np.where(q[1] < q[0], q[1], q[0])
         cloned = (qd > q_min) if q_filter else np.ones(count, dtype=bool)
+        if row_mask is not None:
+            mask = np.asarray(row_mask)
+            if mask.shape != (count,) or mask.dtype not in (np.dtype(np.uint8), np.dtype(bool)):
+                raise ValueError(f"row_mask must be uint8 or bool [{count}], got {mask.dtype} {mask.shape}")
+            cloned = (mask != 0) & cloned
         d = action_pi - action_data
         s = np.zeros(count, dtype=f)
         for k in range(6):
@@ -1386,6 +1426,9 @@ class DeviceCritic:
             pass
 
 
+DEMO_OUT_OF_SCOPE = "demonstrations together with multi-step returns, prioritized replay or hindsight is out of scope"
+
+
 class DeviceReplay:
     """SAC's replay buffer (train.py:40-48, SB3 DictReplayBuffer) as a ring of `capacity_steps` slots x N transitions in device
     memory, filled by ``collect`` (urgym_rollout_collect: the transitions are written as the rollout runs, terminal observations
@@ -1517,7 +1560,7 @@ class DeviceReplay:
         self.cursor = (self.cursor + K) % self.capacity
         self.filled = min(self.capacity, self.filled + K)
 
-    def sample_into(self, out, seed, draw, n_steps=None, gamma=None, hindsight=None):
+    def sample_into(self, out, seed, draw, n_steps=None, gamma=None, hindsight=None, demonstrations=None):
         """The gather itself: `out` maps ring field names (and ``index``, int64) to contiguous device tensors with one leading
         length, the batch size; only those are written.  The rows are ``replay_indices(seed, draw, count, len(self))``.
 
@@ -1525,7 +1568,12 @@ class DeviceReplay:
         its env (``nstep_batch``), `out` must hold ``discount`` (float32) and may hold ``steps`` (int32) and ``last_index`` (int64).
 
         With `hindsight` (a dict: ``threshold`` in [0, 2^32], ``strategy``, ``horizon``; not together with `n_steps`) the launch is
-        urgym_replay_sample_hindsight (``hindsight_batch``): `out` may hold ``goal_index`` (int64) and ``pose_terms`` (float64 [count, 4])."""
+        urgym_replay_sample_hindsight (``hindsight_batch``): `out` may hold ``goal_index`` (int64) and ``pose_terms`` (float64 [count, 4]).
+
+        With `demonstrations` = (other_replay, D) (not together with `n_steps` or `hindsight`) the launch is urgym_replay_sample_mixed
+        (``env.replay_sample_mixed``): rows 0 .. D - 1 come from `other_replay`, a ``DeviceReplay`` of another env of the same kind with any
+        env count, read at its own ``oldest_slot`` and ``filled``; `out` may hold ``source`` (uint8: 1 = a demonstration row).  The rows
+        are ``mixed_entries``'."""
         import ctypes as C
 
         import torch
@@ -1545,6 +1593,10 @@ class DeviceReplay:
                 raise ValueError("hindsight together with multi-step returns is out of scope")
             extra = {"goal_index": (C.c_int64, ()), "pose_terms": (C.c_double, (4,))}
             her.relabel_threshold, her.strategy, her.horizon = _her_arguments(hindsight["threshold"], hindsight["strategy"], hindsight["horizon"])
+        if demonstrations is not None:
+            if n_steps is not None or hindsight is not None:
+                raise ValueError(DEMO_OUT_OF_SCOPE)
+            extra = {"source": (C.c_uint8, ())}
         kinds.update(extra)
         dtypes = {C.c_int64: torch.int64, C.c_int32: torch.int32, C.c_double: torch.float64}
         batch, nstep, count = _abi.ReplayBatch(), _abi.ReplayNstep(), None
@@ -1560,6 +1612,8 @@ class DeviceReplay:
                 count = int(t.shape[0])
             elif int(t.shape[0]) != count:
                 raise ValueError(f"{name} has {int(t.shape[0])} rows, the others {count}")
+            if name == "source":
+                continue
             setattr((nstep if hindsight is None else her) if name in extra else batch, name, C.cast(t.data_ptr(), C.POINTER(ct)))
         if count is None:
             raise ValueError("no output requested")
@@ -1579,10 +1633,39 @@ class DeviceReplay:
             _native.check(env.lib.urgym_replay_sample_hindsight(env._h, C.byref(self._ring), self.oldest_slot, self.filled, int(seed), int(draw), count,
                                                                 C.byref(batch), C.byref(her), env._stream()), env._h)
             return
+        if demonstrations is not None:
+            other, D = demonstrations
+            env.replay_sample_mixed(self, other, D, seed, draw, count, batch, source=out.get("source"))
+            return
         _native.check(env.lib.urgym_replay_sample(env._h, C.byref(self._ring), self.oldest_slot, self.filled, int(seed), int(draw), count,
                                                   C.byref(batch), env._stream()), env._h)
 
-    def sample(self, batch_size, seed, draw, n_steps=None, gamma=None):
+    def demonstrations_struct(self, count):
+        """This ring as the urgym_replay_demonstrations of a mixed gather with `count` demonstration rows: read at its own ``oldest_slot``
+        and ``filled``.  Raises ValueError for an empty ring or a negative count."""
+        from . import _abi
+
+        if isinstance(count, bool) or int(count) != count or not 0 <= int(count) < 1 << 31:
+            raise ValueError(f"the number of demonstration rows must be an integer >= 0, got {count!r}")
+        self.check_args(self.capacity, filled_steps=self.filled, oldest_slot=self.oldest_slot)
+        return _abi.ReplayDemonstrations(self._ring, self.env.num_envs, self.oldest_slot, self.filled, int(count))
+
+    def save(self, path):
+        """The ring alone as one ``.npz`` (``checkpoint.write`` of ``state_dict()``): a demonstration set that outlives the process."""
+        from . import checkpoint
+
+        checkpoint.write(path, {"replay": self.state_dict()})
+
+    def load_file(self, path):
+        """Restores what ``save`` wrote into this ring (the same capacity and env shape, ``load_state_dict``)."""
+        from . import checkpoint
+
+        state = checkpoint.read(path)
+        if not isinstance(state, dict) or "replay" not in state:
+            raise ValueError(f"{path}: not a file of DeviceReplay.save (no 'replay' entry)")
+        self.load_state_dict(state["replay"])
+
+    def sample(self, batch_size, seed, draw, n_steps=None, gamma=None, demonstrations=None):
         """A minibatch of `batch_size` transitions drawn uniformly with replacement, one launch: a dict of fresh device tensors --
         ``observations`` and ``next_observations`` (each {observation, achieved_goal, desired_goal}: the `rows` of
         ``env.policy_actions`` / ``env.critic_values``), ``actions``, ``rewards``, ``terminated``, ``truncated``, ``is_success``
@@ -1590,7 +1673,10 @@ class DeviceReplay:
 
         With `n_steps` and `gamma` the rows are multi-step transitions (``sample_into``): ``rewards`` is the discounted return over
         the m steps taken, ``next_observations`` and the flags are those of the last of them, and the dict also holds ``discount``
-        (gamma^m, float32), ``steps`` (m, int32) and ``last_index`` (int64)."""
+        (gamma^m, float32), ``steps`` (m, int32) and ``last_index`` (int64).
+
+        With `demonstrations` = (other_replay, D) the first D rows come from `other_replay` (``sample_into``) and the dict also holds
+        ``source`` (uint8 [batch_size]: 1 = a demonstration row); ``index`` of such a row is an entry of `other_replay`."""
         import ctypes as C
 
         import torch
@@ -1606,9 +1692,13 @@ class DeviceReplay:
         if n_steps is not None:
             flat.update(discount=torch.empty((B,), dtype=torch.float32, device=env.device), steps=torch.empty((B,), dtype=torch.int32, device=env.device),
                         last_index=torch.empty((B,), dtype=torch.int64, device=env.device))
-        self.sample_into(flat, seed, draw, n_steps=n_steps, gamma=gamma)
+        if demonstrations is not None:
+            flat["source"] = torch.empty((B,), dtype=torch.uint8, device=env.device)
+        self.sample_into(flat, seed, draw, n_steps=n_steps, gamma=gamma, demonstrations=demonstrations)
         rows = ("observation", "achieved_goal", "desired_goal")
         more = {k: flat[k] for k in ("discount", "steps", "last_index")} if n_steps is not None else {}
+        if demonstrations is not None:
+            more["source"] = flat["source"]
         return {**more, "observations": {k: flat[k] for k in rows}, "next_observations": {k: flat["next_" + k] for k in rows},
                 "actions": flat["action"], "rewards": flat["reward"], "terminated": flat["terminated"].view(torch.bool),
                 "truncated": flat["truncated"].view(torch.bool), "is_success": flat["is_success"].view(torch.bool), "index": flat["index"]}
@@ -1641,7 +1731,8 @@ class DeviceReplay:
                 "actions": flat["action"], "rewards": flat["reward"], "terminated": flat["terminated"].view(torch.bool),
                 "truncated": flat["truncated"].view(torch.bool), "is_success": flat["is_success"].view(torch.bool), "index": flat["index"]}
 
-    def sample_targets(self, actor, critic, batch_size, seed, draw, gamma, ent_coef, sample=None, n_steps=None, hindsight=None, normalizer=None):
+    def sample_targets(self, actor, critic, batch_size, seed, draw, gamma, ent_coef, sample=None, n_steps=None, hindsight=None, normalizer=None,
+                       demonstrations=None):
         """``sample``, then a' ~ pi(.|s') on the gathered next observations (``env.policy_actions(rows=)``), then SAC's target
         y = r + gamma (1 - terminated) (min_i Q_i(s', a') - ent_coef log pi(a'|s')) (``env.critic_values``): three launches.
         `sample` = how a' is drawn (default: gaussian with this call's seed and draw).  Returns the batch with ``next_actions``,
@@ -1652,13 +1743,18 @@ class DeviceReplay:
         y from them); `ent_coef` is not used.
 
         With `normalizer` (a ``DeviceNormalizer``) the gathered batch is normalized in place right after the gather
-        (``env.norm_batch``: one more launch); with `n_steps` the normalized reward is the row's accumulated return."""
+        (``env.norm_batch``: one more launch); with `n_steps` the normalized reward is the row's accumulated return.
+
+        With `demonstrations` = (other_replay, D) the batch is ``sample(..., demonstrations=)`` (not with `n_steps` or `hindsight`);
+        demonstration rows are raw rows like any other and are normalized with the batch."""
+        if demonstrations is not None and (hindsight is not None or n_steps is not None):
+            raise ValueError(DEMO_OUT_OF_SCOPE)
         if hindsight is not None:  # dict(n_sampled_goal=, strategy=): the batch is ``sample_hindsight``'s, the rest as below
             if n_steps is not None:
                 raise ValueError("hindsight together with multi-step returns is out of scope")
             batch = self.sample_hindsight(batch_size, seed, draw, **hindsight)
         else:
-            batch = self.sample(batch_size, seed, draw, n_steps=n_steps, gamma=None if n_steps is None else gamma)
+            batch = self.sample(batch_size, seed, draw, n_steps=n_steps, gamma=None if n_steps is None else gamma, demonstrations=demonstrations)
         if normalizer is not None:
             self.env.norm_batch(normalizer, batch)
         how = dict(mode="gaussian", seed=seed, first_draw=draw) if sample is None else sample

@@ -109,6 +109,11 @@ NORM_DEFAULTS = dict(normalize=False, norm_obs=True, norm_reward=True, clip_obs=
 # TD3+BC's normalisation by the mean |Q| (bc_scale_by_q) and the Q-filter (bc_q_filter).  None, the default, is the learner as it was.
 # Kept apart like the four above: a run without it saves none of the three.
 BC_DEFAULTS = dict(bc_weight=None, bc_scale_by_q=False, bc_q_filter=False)
+# The demonstration ring: SACLearner(demonstrations=replay_d, demo_batch_size=D) draws the first D rows of every
+# minibatch from a second ring that collection never overwrites; with bc_demo_only the cloning term applies to those rows only.  None,
+# the default, is the learner as it was; demo_batch_size=0 takes the new calls and leaves the same bits.  Kept apart like the five above:
+# a run without it saves neither key.
+DEMO_DEFAULTS = dict(demo_batch_size=None, bc_demo_only=False)
 
 
 def _mlp(n_in, hidden, n_out=None):
@@ -194,16 +199,44 @@ class SACLearner:
     (HER_DEFAULTS: ``her_n_sampled_goal``, ``her_strategy`` "future" or "final"; needs ``device_entropy=True``) relabels the goals of each
     minibatch in the gather (``DeviceReplay.sample_hindsight``); not together with ``n_steps`` > 1 or ``prioritized``.
     ``max_grad_norm=X`` (CLIP_DEFAULTS; needs ``device_entropy=True``) clips the critics' and the actor's gradients by their global norm on
-    the device, inside the Adam steps; with any of the options above."""
+    the device, inside the Adam steps; with any of the options above.
 
-    def __init__(self, env, seed=0, **overrides):
+    ``demonstrations=replay_d, demo_batch_size=D`` (DEMO_DEFAULTS; needs ``device_entropy=True``): `replay_d` is a
+    ``DeviceReplay`` of ANOTHER env of the same kind, with any env count, filled beforehand (by a planner, say) and never written by this
+    learner; rows 0 .. D - 1 of every minibatch come from it (``DeviceReplay.sample_targets(demonstrations=)``, one mixed gather launch),
+    the rest from the learner's own ring, in ``update`` and ``train`` alike.  With ``bc_demo_only=True`` (it needs ``bc_weight``) only those
+    rows can be cloned (``env.policy_terms_cloned_masked``).  The learner keeps passing ``bc_scale = 1 / M``, not 1 / D, so a weight means
+    the same at every demonstration share.  ``demo_batch_size=0`` goes through the new calls and leaves the bits of a learner without the
+    option.  Not together with ``n_steps`` > 1, ``prioritized`` or ``hindsight``."""
+
+    def __init__(self, env, seed=0, demonstrations=None, **overrides):
         unknown = [k for k in overrides if k not in SAC_DEFAULTS and k not in PER_DEFAULTS and k not in HER_DEFAULTS and k not in CLIP_DEFAULTS and k not in NORM_DEFAULTS
-                   and k not in BC_DEFAULTS]
+                   and k not in BC_DEFAULTS and k not in DEMO_DEFAULTS]
         if unknown:
             raise TypeError(f"unknown hyperparameters {unknown}; available: "
-                            f"{sorted(SAC_DEFAULTS) + sorted(PER_DEFAULTS) + sorted(HER_DEFAULTS) + sorted(CLIP_DEFAULTS) + sorted(NORM_DEFAULTS) + sorted(BC_DEFAULTS)}")
-        hp = dict(SAC_DEFAULTS, **PER_DEFAULTS, **HER_DEFAULTS, **CLIP_DEFAULTS, **NORM_DEFAULTS, **BC_DEFAULTS)
+                            f"{sorted(SAC_DEFAULTS) + sorted(PER_DEFAULTS) + sorted(HER_DEFAULTS) + sorted(CLIP_DEFAULTS) + sorted(NORM_DEFAULTS) + sorted(BC_DEFAULTS) + sorted(DEMO_DEFAULTS)}")
+        hp = dict(SAC_DEFAULTS, **PER_DEFAULTS, **HER_DEFAULTS, **CLIP_DEFAULTS, **NORM_DEFAULTS, **BC_DEFAULTS, **DEMO_DEFAULTS)
         hp.update(overrides)
+        if not isinstance(hp["bc_demo_only"], bool):
+            raise ValueError(f"bc_demo_only must be True or False, got {hp['bc_demo_only']!r}")
+        if hp["demo_batch_size"] is None:
+            if demonstrations is not None:
+                raise ValueError("demonstrations= needs demo_batch_size (the number of rows of every minibatch drawn from it; 0 is allowed)")
+            if hp["bc_demo_only"]:
+                raise ValueError("bc_demo_only qualifies demo_batch_size and needs it")
+        else:
+            D = hp["demo_batch_size"]
+            if isinstance(D, bool) or not isinstance(D, (int, np.integer)) or not 0 <= int(D) <= int(hp["batch_size"]):
+                raise ValueError(f"demo_batch_size must be None or an integer in [0, batch_size = {hp['batch_size']}], got {D!r}")
+            hp["demo_batch_size"] = int(D)
+            if not hp["device_entropy"]:
+                raise ValueError("demo_batch_size needs device_entropy=True (the mixed minibatch is gathered and used by the device's launches)")
+            if hp["bc_demo_only"] and hp["bc_weight"] is None:
+                raise ValueError("bc_demo_only needs bc_weight (it restricts the cloning term to the demonstration rows)")
+            if hp["prioritized"] is True or hp["hindsight"] is True or (not isinstance(hp["n_steps"], bool) and hp["n_steps"] != 1):
+                raise ValueError("demo_batch_size with n_steps > 1, prioritized=True or hindsight=True is out of scope: each of the three has a gather of its own")
+            if demonstrations is None:
+                raise ValueError("demo_batch_size needs demonstrations= (a DeviceReplay of another env of the same kind)")
         for k in ("bc_scale_by_q", "bc_q_filter"):
             if not isinstance(hp[k], bool):
                 raise ValueError(f"{k} must be True or False, got {hp[k]!r}")
@@ -344,6 +377,12 @@ class SACLearner:
 
             self.normalizer = DeviceNormalizer(env, gamma=hp["gamma"], norm_obs=hp["norm_obs"], norm_reward=hp["norm_reward"], clip_obs=hp["clip_obs"],
                                                clip_reward=hp["clip_reward"], epsilon=hp["norm_epsilon"])
+        # with demo_batch_size the demonstration ring is the caller's; the gather's source bytes are a tensor of the learner's; never saved
+        self.demonstrations = self.demo_source = None
+        if hp["demo_batch_size"] is not None:
+            env._demonstrations("SACLearner", demonstrations, hp["demo_batch_size"])  # another env of this kind and device, and not empty
+            self.demonstrations = demonstrations
+            self.demo_source = torch.zeros((int(hp["batch_size"]),), dtype=torch.uint8, device=dev)
         self._train = None  # the scratch and the checked struct of train(), per replay
         self.env_steps = 0  # per env; decides between the warm-up and the policy
         self.draw = 0       # draw index of the next collection pass
@@ -492,7 +531,8 @@ class SACLearner:
             return self._update_prioritized(replay, seed, draw)
         her = dict(hindsight=dict(n_sampled_goal=hp["her_n_sampled_goal"], strategy=hp["her_strategy"])) if hp.get("hindsight") else {}
         norm = {} if self.normalizer is None else dict(normalizer=self.normalizer)
-        batch = replay.sample_targets(self.device_actor, self.target, M, seed, draw, gamma, 0.0, **({} if n_steps == 1 else dict(n_steps=n_steps)), **her, **norm)
+        demo = {} if self.demonstrations is None else dict(demonstrations=(self.demonstrations, hp["demo_batch_size"]))
+        batch = replay.sample_targets(self.device_actor, self.target, M, seed, draw, gamma, 0.0, **({} if n_steps == 1 else dict(n_steps=n_steps)), **her, **norm, **demo)
         rows = batch["observations"]
         how = dict(mode="gaussian", seed=seed, first_draw=int(draw) | 1 << 63)
         action_pi, log_prob = env.policy_actions(self.device_actor, sample=how, rows=rows)
@@ -514,25 +554,29 @@ class SACLearner:
                              **self._clip("critic"))
         grad = env.critic_action_gradient(self.online, action_pi, rows=rows)
         # d_action = -g / M and the critic's and the actor's loss values
-        self._policy_terms(M, grad, got, log_prob, action_pi, batch["actions"])
+        self._policy_terms(M, grad, got, log_prob, action_pi, batch["actions"], source=batch.get("source"))
         env.actor_parameter_gradients(self.device_actor, sample=how, rows=rows, d_action=self.actor_d_action, d_log_prob=self.actor_d_log_prob,
                                       out=self.actor_grads, workspace=self.actor_workspace)
         env.actor_adam_step(self.device_actor, self.actor.tensors(), self.actor_grads, *st["actor"], **adam, **self._clip("actor"))
-        self.last_update = dict(log_prob=log_prob, y=es["y"], q=got["q"], q_min=grad["q_min"], dqmin_da=grad["dqmin_da"], **self._clip_record(), **self._bc_record(action_pi, batch["actions"]))
+        self.last_update = dict(log_prob=log_prob, y=es["y"], q=got["q"], q_min=grad["q_min"], dqmin_da=grad["dqmin_da"], **self._clip_record(), **self._bc_record(action_pi, batch["actions"]),
+                                **({} if self.demonstrations is None else dict(source=batch["source"])))
         return dict(es["losses"])
 
-    def _policy_terms(self, M, grad, got, log_prob, action_pi, actions):
+    def _policy_terms(self, M, grad, got, log_prob, action_pi, actions, source=None):
         """d_action = -g / M and the critic's and the actor's loss values: ``env.policy_terms``, or with ``bc_weight`` the ONE launch of
-        ``env.policy_terms_cloned`` in its place, which adds the cloning term on the rows it clones (`actions`: the ring's)."""
+        ``env.policy_terms_cloned`` in its place, which adds the cloning term on the rows it clones (`actions`: the ring's); with
+        ``bc_demo_only`` that launch is ``env.policy_terms_cloned_masked``'s with the gather's `source` as the mask.  ``bc_scale`` stays
+        1 / M whatever the demonstration share."""
         hp, es, bc = self.hp, self.entropy_state, self.bc_state
         common = dict(dqmin_da=grad["dqmin_da"], scale=-1.0 / M, d_action_out=self.actor_d_action, q=got["q"], y=es["y"], critic_loss_out=es["critic_loss"],
                       log_prob=log_prob, q_min=grad["q_min"], actor_loss_out=es["actor_loss"])
         if bc is None:
             self.env.policy_terms(es["ent_coef"], M, **common)
         else:
-            self.env.policy_terms_cloned(es["ent_coef"], M, **common, action_pi=action_pi, action_data=actions, weight=hp["bc_weight"], bc_scale=1.0 / M,
-                                         scale_by_q=hp["bc_scale_by_q"], q_filter=hp["bc_q_filter"], bc_loss_out=bc["bc_loss"], bc_weight_out=bc["bc_weight"],
-                                         bc_rows_out=bc["bc_rows"])
+            masked = dict(row_mask=source) if hp["bc_demo_only"] else {}
+            (self.env.policy_terms_cloned_masked if masked else self.env.policy_terms_cloned)(
+                es["ent_coef"], M, **common, **masked, action_pi=action_pi, action_data=actions, weight=hp["bc_weight"], bc_scale=1.0 / M, scale_by_q=hp["bc_scale_by_q"],
+                q_filter=hp["bc_q_filter"], bc_loss_out=bc["bc_loss"], bc_weight_out=bc["bc_weight"], bc_rows_out=bc["bc_rows"])
 
     def _bc_record(self, action_pi, actions):
         """What ``last_update`` gains with ``bc_weight``: references to the cloning loss, the weight used and the number of cloned rows, and
@@ -713,6 +757,8 @@ class SACLearner:
             bc_out = dict(bc_loss=torch.empty((updates,), dtype=torch.float32, device=env.device), bc_weight=torch.empty((updates,), dtype=torch.float32, device=env.device),
                           bc_rows=torch.empty((updates,), dtype=torch.int32, device=env.device))
             cloning = dict(cloning=dict(weight=hp["bc_weight"], scale_by_q=hp["bc_scale_by_q"], q_filter=hp["bc_q_filter"], **bc_out))
+        if self.demonstrations is not None:  # read at its own oldest_slot and filled as they stand now
+            cloning["demonstrating"] = dict(replay=self.demonstrations, count=hp["demo_batch_size"], source=self.demo_source, clone_only=hp["bc_demo_only"])
         tr["binding"].struct.update_seed = int(seed)
         env.sac_train(tr["binding"], losses[0], losses[1], losses[2], first_slot=replay.cursor, filled_steps=replay.filled, num_iterations=n,
                       steps_per_iteration=K, updates_per_iteration=G, uniform_iterations=uniform, idle_iterations=idle,
@@ -738,6 +784,8 @@ class SACLearner:
             if cs is not None:  # the last update's norms, as views of the call's slots; the coefficients are the scratch's
                 self.last_update.update(critic_grad_norm=norms[0, updates - 1:], actor_grad_norm=norms[1, updates - 1:], critic_scale=cs["critic_scale"],
                                         actor_scale=cs["actor_scale"])
+            if self.demonstrations is not None:
+                self.last_update.update(source=self.demo_source)
             if bc_out:  # the last update's three, as views of the call's slots
                 self.last_update.update({k: v[updates - 1:] for k, v in bc_out.items()}, action_pi=sc["action_pi"], action_data=tr["batch"]["action"])
         extra = {"plan_stats": planner.records[first_record:monitor.count]} if plan_stats else {}
@@ -757,7 +805,8 @@ class SACLearner:
         what it was before the option existed (``check_state_dict`` reads an absent ``n_steps`` as 1)."""
         return {k: v for k, v in self.hp.items() if (k != "n_steps" or int(v) != 1) and (k not in PER_DEFAULTS or self.hp.get("prioritized"))
                 and (k not in HER_DEFAULTS or self.hp.get("hindsight")) and (k not in CLIP_DEFAULTS or v is not None)
-                and (k not in NORM_DEFAULTS or self.hp.get("normalize")) and (k not in BC_DEFAULTS or self.hp.get("bc_weight") is not None)}
+                and (k not in NORM_DEFAULTS or self.hp.get("normalize")) and (k not in BC_DEFAULTS or self.hp.get("bc_weight") is not None)
+                and (k not in DEMO_DEFAULTS or self.hp.get("demo_batch_size") is not None)}
 
     def state_dict(self):
         """Everything the learner is, as host arrays and scalars: the actor's eight and the critics' twelve parameter tensors, the
@@ -845,6 +894,9 @@ class SACLearner:
             if state["hp"].get(k, default) != self.hp.get(k, default):
                 raise ValueError(f"load_state_dict: {k} is {state['hp'].get(k, default)!r} in the checkpoint, {self.hp.get(k, default)!r} here")
         for k, default in BC_DEFAULTS.items():  # a file without cloning holds none of the three
+            if state["hp"].get(k, default) != self.hp.get(k, default):
+                raise ValueError(f"load_state_dict: {k} is {state['hp'].get(k, default)!r} in the checkpoint, {self.hp.get(k, default)!r} here")
+        for k, default in DEMO_DEFAULTS.items():  # a file without demonstrations holds neither
             if state["hp"].get(k, default) != self.hp.get(k, default):
                 raise ValueError(f"load_state_dict: {k} is {state['hp'].get(k, default)!r} in the checkpoint, {self.hp.get(k, default)!r} here")
         for k, default in NORM_DEFAULTS.items():  # a file without normalization holds none of the six, and no statistics
@@ -953,19 +1005,23 @@ class SACLearner:
             opt.state.clear()  # torch's Adam starts again: zero moments, step 0
         self._repack([{k: torch.from_numpy(np.ascontiguousarray(a)).to(dev) for k, a in w.items()} for w in target])
 
-    def save(self, path, replay=None, monitor=None, evaluation=None, env_state=True, extra=None):
+    def save(self, path, replay=None, monitor=None, evaluation=None, env_state=True, extra=None, demonstrations=None):
         """One ``.npz`` (``ur_gym_amd.checkpoint``: plain arrays and one JSON string, readable with ``allow_pickle=False``) holding
         ``state_dict()`` and, where given, the ``state_dict`` of `replay`, `monitor` and `evaluation`, the training environment's
         ``checkpoint_state`` (`env_state`) and `extra`, the caller's own counters as JSON scalars (tools/train_sac.py keeps its update
-        draw there).  Written to a temporary name and renamed: a job killed mid-save leaves the previous file whole."""
+        draw there).  Written to a temporary name and renamed: a job killed mid-save leaves the previous file whole.  With
+        `demonstrations` (the learner's demonstration ring) its ``state_dict`` goes under ``demonstrations``, a key a file without it does
+        not hold."""
         from . import checkpoint
 
         state = dict(learner=self.state_dict(), extra=extra,
                      replay=None if replay is None else replay.state_dict(), monitor=None if monitor is None else monitor.state_dict(),
                      evaluation=None if evaluation is None else evaluation.state_dict(), env=self.env.checkpoint_state() if env_state else None)
+        if demonstrations is not None:
+            state["demonstrations"] = demonstrations.state_dict()
         checkpoint.write(path, state)
 
-    def load(self, path, replay=None, monitor=None, evaluation=None, env_state=True, override=()):
+    def load(self, path, replay=None, monitor=None, evaluation=None, env_state=True, override=(), demonstrations=None):
         """Reads what ``save`` wrote into this learner and the same objects; returns `extra`.  A part that was saved but has no object
         handed in, or the reverse, raises ValueError, and so does everything ``load_state_dict`` and the parts' own loads refuse -- the
         learner's, the ring's and the environment's checks are all made before anything is written."""
@@ -977,9 +1033,14 @@ class SACLearner:
             if (state[name] is None) != (obj is None):
                 raise ValueError(f"load: {name} is {'absent from' if state[name] is None else 'present in'} the checkpoint, "
                                  f"and the call has {'no' if obj is None else 'an'} object for it")
+        if ("demonstrations" in state) != (demonstrations is not None):
+            raise ValueError(f"load: demonstrations is {'present in' if 'demonstrations' in state else 'absent from'} the checkpoint, "
+                             f"and the call has {'no' if demonstrations is None else 'an'} object for it")
         self.check_state_dict(state["learner"], override)
         if replay is not None:
             replay.check_state_dict(state["replay"])
+        if demonstrations is not None:
+            demonstrations.check_state_dict(state["demonstrations"])
         if env_state:
             self.env.check_checkpoint(state["env"])
         self.load_state_dict(state["learner"], override)
@@ -988,6 +1049,8 @@ class SACLearner:
         for name in ("replay", "monitor", "evaluation"):
             if given[name] is not None:
                 given[name].load_state_dict(state[name])
+        if demonstrations is not None:
+            demonstrations.load_state_dict(state["demonstrations"])
         return state["extra"]
 
     def close(self):

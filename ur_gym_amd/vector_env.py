@@ -67,7 +67,10 @@ _SAC_TRAIN_ENTRIES = (
 # The entry points ``sac_train`` tries ahead of that table, in the same form: a planner with coloured sampling noise
 # goes to urgym_sac_train_colored whatever else is given; its temper struct, like every option after it, may be absent.  Ahead of that,
 # behaviour cloning goes to urgym_sac_train_cloned, which takes every other option, each of which may be absent.
+# Ahead of both, a demonstration ring goes to urgym_sac_train_demonstrated, which takes cloning and every other
+# option but the three gathers' (each of those has a gather of its own).
 _SAC_TRAIN_ENTRIES_AHEAD = (
+    ("urgym_sac_train_demonstrated", "demonstrating", ("demonstrating", "cloning", "planner", "temper", "noise", "normalizer", "clipping", "evaluation", "monitor")),
     ("urgym_sac_train_cloned", "cloning", ("cloning", "planner", "temper", "noise", "normalizer", "clipping", "nstep", "prioritized", "hindsight", "evaluation", "monitor")),
     ("urgym_sac_train_colored", "noise", ("planner", "noise", "temper", "clipping", "nstep", "prioritized", "hindsight", "evaluation", "monitor")),
 )
@@ -76,7 +79,7 @@ _SAC_TRAIN_ENTRIES_AHEAD = (
 def _sac_train_entry(present):
     """(symbol, option names) of the entry point that serves a call with the options in `present` (any container of names out of
     evaluation, monitor, nstep, prioritized, hindsight, clipping, normalizer, planner, temper -- the planner's temper struct, given where
-    the planner has an ess_target -- noise, its noise struct, given where it has a noise_beta, and cloning): the first row of
+    the planner has an ess_target -- noise, its noise struct, given where it has a noise_beta, cloning and demonstrating): the first row of
     ``_SAC_TRAIN_ENTRIES_AHEAD``, then of ``_SAC_TRAIN_ENTRIES``, whose option is given."""
     for symbol, selects, options in _SAC_TRAIN_ENTRIES_AHEAD + _SAC_TRAIN_ENTRIES:
         if selects is None or selects in present:
@@ -724,7 +727,8 @@ class UR5ReachVectorEnv:
         _native.check(self.lib.urgym_sac_policy_terms(self._h, C.byref(a), self._stream()), self._h)
 
     def policy_terms_cloned(self, ent_coef, count, *, dqmin_da, scale, d_action_out, q, y, critic_loss_out, log_prob, q_min, actor_loss_out,
-                            action_pi, action_data, weight, bc_scale, scale_by_q=False, q_filter=False, bc_loss_out, bc_weight_out, bc_rows_out):
+                            action_pi, action_data, weight, bc_scale, scale_by_q=False, q_filter=False, bc_loss_out, bc_weight_out, bc_rows_out,
+                            _row_mask=None):
         """``policy_terms`` with behaviour cloning, in ONE launch in its place (urgym_sac_policy_terms_cloned): all
         three groups of ``policy_terms`` are required, `q` being the online critics at the REPLAYED action.  `action_pi`, `action_data`
         [count, 6]: the policy's action and the ring's on the batch rows.  A row is cloned where `q_filter` is off or ``min(q[0], q[1])
@@ -733,7 +737,7 @@ class UR5ReachVectorEnv:
         mean over all rows of half the squared distance of the cloned rows, ``bc_weight_out`` [1] w, ``bc_rows_out`` (int32 [1]) the
         number of cloned rows.  Tensors are checked as in ``policy_terms``; the arithmetic is ``evaluation.policy_terms_cloned``,
         bitwise.  On torch's current stream, nothing is synchronised."""
-        who = "policy_terms_cloned"
+        who = "policy_terms_cloned" if _row_mask is None else "policy_terms_cloned_masked"
         count = int(count)
         if not 1 <= count <= _abi.SAC_TERMS_MAX_COUNT:
             raise ValueError(f"{who}: count must be in [1, {_abi.SAC_TERMS_MAX_COUNT}], got {count}")
@@ -763,7 +767,55 @@ class UR5ReachVectorEnv:
         b.bc_rows_out = self._float_ptr(who, "bc_rows_out", bc_rows_out, (1,), torch.int32, C.c_int32)
         if d_action_out.data_ptr() in (action_pi.data_ptr(), action_data.data_ptr()):
             raise ValueError(f"{who}: d_action_out must not be action_pi or action_data (the actions are read again after it is written)")
+        if _row_mask is not None:  # policy_terms_cloned_masked has checked the tensor
+            _native.check(self.lib.urgym_sac_policy_terms_cloned_masked(self._h, C.byref(a), C.byref(b), _row_mask.data_ptr(), self._stream()), self._h)
+            return
         _native.check(self.lib.urgym_sac_policy_terms_cloned(self._h, C.byref(a), C.byref(b), self._stream()), self._h)
+
+    def policy_terms_cloned_masked(self, ent_coef, count, *, row_mask, **terms):
+        """``policy_terms_cloned`` on marked rows only, ONE launch in its place (urgym_sac_policy_terms_cloned_masked; DESIGN.md section
+        34): `row_mask` is a contiguous uint8 (or bool) [count] tensor, and a row is cloned only where its mask is nonzero and
+        ``policy_terms_cloned``'s verdict holds.  Every other argument and every output is that call's; the means stay over all rows.
+        The arithmetic is ``evaluation.policy_terms_cloned(row_mask=)``, bitwise."""
+        who = "policy_terms_cloned_masked"
+        if not isinstance(row_mask, torch.Tensor):
+            raise ValueError(f"{who}: row_mask must be a uint8 [count] tensor on {self.device}, got {type(row_mask).__name__}")
+        mask = row_mask.view(torch.uint8) if row_mask.dtype == torch.bool else row_mask
+        self._float_ptr(who, "row_mask", mask, (int(count),), torch.uint8, C.c_uint8)
+        self.policy_terms_cloned(ent_coef, count, _row_mask=mask, **terms)
+
+    def replay_sample_mixed(self, replay, demonstrations, demo_count, seed, draw, count, batch, source=None):
+        """ONE gather launch whose first `demo_count` rows come from `demonstrations` and the rest from `replay` (urgym_replay_sample_mixed;
+        DESIGN.md section 34).  `replay`: a ``DeviceReplay`` of this environment; `demonstrations`: a ``DeviceReplay`` of another
+        environment of the same kind on this device, with any env count, read at its own ``oldest_slot`` and ``filled``; `batch`: an
+        ``_abi.ReplayBatch`` of `count` rows (``DeviceReplay.sample_into(demonstrations=)`` builds it); `source`: None or a contiguous
+        uint8 [count] tensor that receives 1 for a demonstration row and 0 otherwise.  The rows are ``evaluation.mixed_entries``'; rows from
+        `demo_count` on are bitwise those of the plain gather at the same seed and draw."""
+        from .evaluation import DeviceReplay
+
+        who = "replay_sample_mixed"
+        if not isinstance(replay, DeviceReplay) or replay.env is not self:
+            raise ValueError(f"{who}: replay must be a DeviceReplay of this environment")
+        demo = self._demonstrations(who, demonstrations, demo_count)
+        count = int(count)
+        if demo.count > count:
+            raise ValueError(f"{who}: demo_count must be in [0, {count}], got {demo.count}")
+        ptr = None if source is None else self._float_ptr(who, "source", source, (count,), torch.uint8, C.c_uint8)
+        _native.check(self.lib.urgym_replay_sample_mixed(self._h, C.byref(replay._ring), replay.oldest_slot, replay.filled, int(seed), int(draw), count, C.byref(batch),
+                                                         C.byref(demo), C.cast(ptr, C.c_void_p) if ptr is not None else None, self._stream()), self._h)
+
+    def _demonstrations(self, who, demonstrations, demo_count):
+        """The urgym_replay_demonstrations of `demonstrations`, a ``DeviceReplay`` of ANOTHER environment of this kind and device."""
+        from .evaluation import DeviceReplay
+
+        if not isinstance(demonstrations, DeviceReplay) or demonstrations.env is self:
+            raise ValueError(f"{who}: demonstrations must be a DeviceReplay of another environment of the same kind")
+        other = demonstrations.env
+        if other.env_id != self.env_id or (other.obs_dim, other.goal_dim) != (self.obs_dim, self.goal_dim):
+            raise ValueError(f"{who}: the demonstrations come from {other.env_id}, this environment is {self.env_id} (another env kind is out of scope)")
+        if torch.device(other.device) != torch.device(self.device):
+            raise ValueError(f"{who}: the demonstrations are on {other.device}, this environment on {self.device}")
+        return demonstrations.demonstrations_struct(demo_count)
 
     def evaluation_stats(self, returns, last_step, success, best_mean, best_index, record, eval_index):
         """The statistics of N evaluation episodes, the improvement decision and the best state, in ONE launch of one workgroup
@@ -939,7 +991,7 @@ class UR5ReachVectorEnv:
     def sac_train(self, learner, critic_loss, actor_loss, ent_coef_loss, *, first_slot, filled_steps, num_iterations, steps_per_iteration=1,
                   updates_per_iteration=1, uniform_iterations=0, idle_iterations=0, collect_first_draw=0, update_first_draw=0, first_step=1,
                   evaluation=None, eval_every=None, monitor=None, log_every=None, nstep=None, prioritized=None, hindsight=None, clipping=None,
-                  normalizer=None, planner=None, cloning=None):
+                  normalizer=None, planner=None, cloning=None, demonstrating=None):
         """``num_iterations`` x (a collection of ``steps_per_iteration`` steps, ``updates_per_iteration`` SAC updates) in ONE native
         call (urgym_sac_train): the launches of ``collect`` and of the thirteen calls of an update, bit for bit, without returning to
         Python in between.  `learner`: what ``sac_learner`` returned, or a dict of its keyword arguments (then built and checked here).
@@ -990,7 +1042,13 @@ class UR5ReachVectorEnv:
         With `cloning` (a dict: ``weight``, optionally ``scale_by_q`` and ``q_filter`` (False), and ``bc_loss``, ``bc_weight`` (float32)
         and ``bc_rows`` (int32), tensors of one entry per update of the call like the losses): every update's ``policy_terms`` is
         ``policy_terms_cloned`` on the policy's action and the batch's (urgym_sac_train_cloned), ``bc_scale`` = 1 / count; update u
-        writes entry u of the three.  With any of the options above."""
+        writes entry u of the three.  With any of the options above.
+
+        With `demonstrating` (a dict: ``replay``, a ``DeviceReplay`` of another environment of the same kind holding the demonstrations,
+        ``count`` = D of the learner's rows, ``source``, a uint8 [count of the learner] scratch tensor, and optionally ``clone_only``
+        (False; True needs `cloning`)): every update's gather is the mixed one (``DeviceReplay.sample_into(demonstrations=)``,
+        urgym_sac_train_demonstrated) and, with ``clone_only``, its policy terms are ``policy_terms_cloned_masked`` with ``row_mask =
+        source``.  Not together with `nstep`, `prioritized` or `hindsight`."""
         from .evaluation import DeviceEvaluation, DeviceMonitor, DeviceMPPI, _her_arguments, evaluation_points, monitor_points, relabel_threshold, training_schedule
 
         who = "sac_train"
@@ -1108,6 +1166,24 @@ class UR5ReachVectorEnv:
             given["cloning"] = _abi.SacCloning(float(weight), int(flags[0]), int(flags[1]), 0, self._float_ptr(who, "cloning['bc_loss']", cloning["bc_loss"], (updates,)),
                                                self._float_ptr(who, "cloning['bc_weight']", cloning["bc_weight"], (updates,)),
                                                self._float_ptr(who, "cloning['bc_rows']", cloning["bc_rows"], (updates,), torch.int32, C.c_int32))
+        if demonstrating is not None:
+            from .evaluation import DEMO_OUT_OF_SCOPE
+
+            unknown = [k for k in demonstrating if k not in ("replay", "count", "source", "clone_only")]
+            if unknown:
+                raise ValueError(f"{who}: unknown demonstrating options {unknown}; available: replay, count, source, clone_only")
+            if nstep is not None or prioritized is not None or hindsight is not None:
+                raise ValueError(f"{who}: {DEMO_OUT_OF_SCOPE}")
+            clone_only = demonstrating.get("clone_only", False)
+            if not isinstance(clone_only, (bool, np.bool_)):
+                raise ValueError(f"{who}: demonstrating['clone_only'] must be True or False")
+            if clone_only and cloning is None:
+                raise ValueError(f"{who}: demonstrating['clone_only'] needs cloning")
+            demo = self._demonstrations(who, demonstrating["replay"], demonstrating["count"])
+            if demo.count > int(L.count):
+                raise ValueError(f"{who}: demonstrating['count'] must be in [0, {int(L.count)}], got {demo.count}")
+            given["demonstrating"] = _abi.SacDemonstrating(demo, self._float_ptr(who, "demonstrating['source']", demonstrating["source"], (int(L.count),), torch.uint8, C.c_uint8),
+                                                           int(bool(clone_only)), 0)
         symbol, options = _sac_train_entry(given)
         try:
             _native.check(getattr(self.lib, symbol)(self._h, C.byref(L), C.byref(S), *[C.byref(given[o]) if o in given else None for o in options], self._stream()), self._h)
