@@ -2419,6 +2419,81 @@ typedef struct urgym_sac_demonstrating {
  * no demonstrations refuses. */
 int urgym_sac_train_demonstrated(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_demonstrating* demonstrating, const urgym_sac_cloning* cloning_or_NULL, const urgym_sac_planning* planning_or_NULL, const urgym_mppi_temper* temper_or_NULL, const urgym_mppi_noise* noise_or_NULL, const urgym_normalization* normalization_or_NULL, const urgym_sac_clipping* clipping_or_NULL, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream);
 
+/* ---- advantage-weighted cloning in the policy loss.  The Q-filter above is a hard gate: a row is cloned whole or
+ * not at all, and it drops nearly every demonstration as soon as the critics rate the policy's own action marginally higher.  The soft
+ * form weights each cloned row by exp(advantage / temperature), normalised over the batch: AWAC (Nair et al. 2020; rlkit's
+ * softmax(A / beta) * batch_size) and the exponential variant of CRR (Wang et al. 2020), whose binary variant the Q-filter is.  Every row
+ * still pulls, better rows pull harder, and one temperature moves between "every row alike" and "the best row alone".  Added WITHIN ABI
+ * version 4: no struct above changed, no symbol above changed, URGYM_ABI_VERSION did not move, the two symbols below
+ * (urgym_sac_policy_terms_weighted, urgym_sac_train_weighted) are found by lookup.  All pointers are DEVICE pointers. */
+typedef struct urgym_sac_advantage_args {
+  float temperature;         /* finite, > 0 */
+  float max_weight;          /* > 0, finite or +infinity (no cap) */
+  const uint8_t* row_mask;   /* [count], or NULL: every row is marked */
+  float* adv_ess_out;        /* [1] */
+  float* adv_max_out;        /* [1] */
+  int32_t* adv_clipped_out;  /* [1] */
+  int32_t reserved0;         /* must be 0 */
+} urgym_sac_advantage_args;
+
+/* urgym_sac_policy_terms_cloned (q_filter = 0) with a weight per row in the place of the verdict.  ONE launch of ONE workgroup of 1024
+ * lanes, in its place, in three sweeps of the rows (lane t takes rows t, t + 1024, ...) with the folds between them; nothing per row is
+ * kept between the sweeps.  With q = args->q (the ONLINE critics at the REPLAYED action) and q_min = args->q_min (at the policy's):
+ *   per row m:
+ *     qd      = q[1][m] < q[0][m] ? q[1][m] : q[0][m]
+ *     A[m]    = qd - q_min[m]                                   one float32 subtraction
+ *     elig[m] = (row_mask == NULL || row_mask[m] != 0) && isfinite(A[m])      a NaN or an infinity on either side: not eligible
+ *   sweep 1:  n = the number of eligible rows;  A_max = the largest A over them (float32 comparisons of finite values: any order)
+ *   sweep 2, float64:
+ *     d = (double)A[m] - (double)A_max;  x = d / (double)temperature          never positive
+ *     e[m] = THE EXPONENTIAL of "the temperature from a target effective sample size" at x (+0.0 below -708; exactly 1 on the A_max
+ *            row), +0.0 where the row is not eligible
+ *     Z = THE ORDERED SUM of e over all count rows;  Q = THE ORDERED SUM of e * e;  the four sums of urgym_sac_policy_terms_cloned
+ *     (the two critic terms, the actor's, absq) are formed as there, over ALL rows
+ *   scalars:  mean_e = Z / (double)n;  mean_abs and w = scale_by_q ? weight * mean_abs : weight as in urgym_sac_policy_terms_cloned
+ *   sweep 3, per row (e[m] formed again):
+ *     u = e[m] / mean_e;  v = u > (double)max_weight ? (double)max_weight : u;  a[m] = (float)v       +0.0f where not eligible
+ *     clipped counts the rows with u > max_weight
+ *     h[m] = 0.5f * s as in urgym_sac_policy_terms_cloned where the row is eligible, +0.0f where it is not
+ *     bc_loss = ordered mean over all count rows of the float32 product a[m] * h[m]
+ *     g = dqmin_da[m][k] * scale
+ *     not eligible:  d_action_out[m][k] = g                     bitwise what urgym_sac_policy_terms writes
+ *     eligible:      wr = w * a[m];  t = d_k * wr;  u = t * bc_scale;  d_action_out[m][k] = g + u
+ *   critic_loss_out and actor_loss_out are bitwise urgym_sac_policy_terms'; bc_loss_out[0] = bc_loss; bc_weight_out[0] = w;
+ *   bc_rows_out[0] = n; adv_ess_out[0] = (float)((Z * Z) / Q), the effective number of rows the weights spread over, in [1, n];
+ *   adv_max_out[0] = a of the A_max row = (float)min(1 / mean_e, max_weight), the largest weight; adv_clipped_out[0] = clipped.
+ *   With n == 0 nothing is divided: every a is +0.0f, d_action_out is urgym_sac_policy_terms' bits, bc_loss, adv_ess and adv_max are
+ *   +0.0f and both counts are 0.
+ * With the largest finite temperature and max_weight = +infinity every e is 1 for ordinary advantages, every a is exactly 1.0f and
+ * wr = w: the bits of urgym_sac_policy_terms_cloned (with a mask, of urgym_sac_policy_terms_cloned_masked) at q_filter = 0.
+ * A NaN in action_pi or action_data of an eligible row reaches that row of d_action_out and bc_loss_out only; the actions of a row that
+ * is not eligible are never read.  A row's six elements are read from dqmin_da before they are written: d_action_out may be dqmin_da.
+ *
+ * Refused (URGYM_ERR_ARG, nothing is launched, nothing is written): what urgym_sac_policy_terms_cloned refuses; clone->q_filter != 0
+ * (the two gates are alternatives); NULL advantage or a NULL output pointer in it; temperature not finite or not > 0; max_weight a NaN
+ * or not > 0; reserved0 != 0. */
+int urgym_sac_policy_terms_weighted(void* handle, const urgym_sac_policy_args* args, const urgym_sac_clone_args* clone, const urgym_sac_advantage_args* advantage, void* stream);
+
+/* The training call with advantage-weighted cloning: in every update the policy-terms launch is urgym_sac_policy_terms_weighted's, with
+ * the clone args urgym_sac_train_cloned forms, temperature and max_weight as given here, and row_mask = demonstrating->source where
+ * demonstrating is given with clone_demonstrations_only, NULL otherwise.  Update u of the call writes slot u of adv_ess, adv_max and
+ * adv_clipped beside cloning's three.  Nothing else in the sequence moves: an update stays thirteen launches. */
+typedef struct urgym_sac_weighting {
+  float temperature;     /* finite, > 0 */
+  float max_weight;      /* > 0, finite or +infinity */
+  int32_t reserved0;     /* must be 0 */
+  float* adv_ess;        /* [updates of the call] */
+  float* adv_max;        /* the same */
+  int32_t* adv_clipped;  /* the same */
+} urgym_sac_weighting;
+
+/* `weighting` and `cloning` are required; every option after them may be NULL and is then as in the call without it.  Refused, nothing
+ * launched (the message names urgym_sac_train_weighted): NULL weighting or cloning; cloning->q_filter != 0; what
+ * urgym_sac_policy_terms_weighted refuses about temperature, max_weight and reserved0; a NULL adv_ess, adv_max or adv_clipped where the
+ * call holds an update; what urgym_sac_train_cloned and urgym_sac_train_demonstrated refuse, demonstrating together with nstep,
+ * prioritized or hindsight among it. */
+int urgym_sac_train_weighted(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_weighting* weighting, const urgym_sac_cloning* cloning, const urgym_sac_demonstrating* demonstrating_or_NULL, const urgym_sac_planning* planning_or_NULL, const urgym_mppi_temper* temper_or_NULL, const urgym_mppi_noise* noise_or_NULL, const urgym_normalization* normalization_or_NULL, const urgym_sac_clipping* clipping_or_NULL, const urgym_sac_nstep* nstep_or_NULL, const urgym_sac_prioritized* prioritized_or_NULL, const urgym_sac_hindsight* hindsight_or_NULL, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream);
+
 /* Replaces Reach*.set_goal / set_goal_and_obstacle (reach.py:202-204, 328-335, 702-713): the caller has
  * overwritten goal / obst_start / obst_end (and possibly q) for the masked envs; this recomputes obstacle pose,
  * velocity, collision, link_dist and the observation for them, leaving step_count untouched. */

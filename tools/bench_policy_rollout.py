@@ -81,6 +81,13 @@ kind, timed with device events.  Then one SAC update (4096 envs, batch 256, H = 
 
     python tools/bench_policy_rollout.py --demos --windows 10 --launches 200 --out profiles/policy_rollout/demo_time.json
 
+--clone-weighted measures advantage-weighted cloning.  The launch alone: urgym_sac_policy_terms_cloned (weight 1,
+scale_by_q on, no filter) against urgym_sac_policy_terms_weighted (temperature 1, cap 20) on the same seeded device tensors at M = 256 and
+M = 65536, alternating in one process, --launches per window, --windows windows per kind, timed with device events.  Then one SAC update
+(4096 envs, batch 256, H = 256) as one native call per window: without cloning, with plain cloning, with the advantage weight.
+
+    python tools/bench_policy_rollout.py --clone-weighted --windows 10 --launches 200 --out profiles/policy_rollout/bc_weighted_time.json
+
 --clone measures behaviour cloning in the policy terms.  First the launch alone: urgym_sac_policy_terms against
 urgym_sac_policy_terms_cloned (weight 1, scale_by_q and q_filter on) on the same seeded device tensors at M = 256 and M = 65536, --launches
 back-to-back launches per window between two device events and a synchronise, the two alternating, median of --windows; both and the
@@ -1178,6 +1185,113 @@ def clone_mode(args):
     env.close()
 
 
+def clone_weighted_mode(args):
+    """--clone-weighted: urgym_sac_policy_terms_cloned against urgym_sac_policy_terms_weighted at two batch sizes, and the native update
+    without cloning, with plain cloning and with the advantage weight (see above).  Every set alternates in one process."""
+    import torch
+
+    from ur_gym_amd import make_vec
+    from ur_gym_amd.evaluation import DeviceReplay
+    from ur_gym_amd.training import SACLearner
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_policy_rollout.py measures on a GPU; none is visible")
+    dev, n, per_window = "cuda:0", min(args.num_envs, 4096), args.launches
+    env = make_vec(args.env, num_envs=n, device=dev, seed=0, auto_reset=True)
+    env.reset(seed=0)
+    sync = lambda: torch.cuda.synchronize(env.device)  # noqa: E731
+
+    def window(call):
+        first, last = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        sync()
+        first.record()
+        for _ in range(per_window):
+            call()
+        last.record()
+        sync()
+        return first.elapsed_time(last) * 1e3 / per_window
+
+    launch = {}
+    for M in (256, 65536):
+        rng = np.random.default_rng(M)
+        t = {k: torch.from_numpy(rng.standard_normal(shape).astype(np.float32)).to(dev)
+             for k, shape in dict(dqmin_da=(M, 6), q=(2, M), y=(M,), log_prob=(M,), q_min=(M,), action_pi=(M, 6), action_data=(M, 6)).items()}
+        t["action_pi"], t["action_data"] = torch.tanh(t["action_pi"]), torch.tanh(t["action_data"])
+        out = {k: torch.zeros(shape, dtype=torch.float32, device=dev)
+               for k, shape in dict(d_action=(M, 6), critic_loss=(1,), actor_loss=(1,), bc_loss=(1,), bc_weight=(1,), adv_ess=(1,), adv_max=(1,)).items()}
+        out["bc_rows"], out["adv_clipped"] = torch.zeros((1,), dtype=torch.int32, device=dev), torch.zeros((1,), dtype=torch.int32, device=dev)
+        ent_coef = torch.full((1,), 0.2, dtype=torch.float32, device=dev)
+        kw = dict(dqmin_da=t["dqmin_da"], scale=-1.0 / M, d_action_out=out["d_action"], q=t["q"], y=t["y"], critic_loss_out=out["critic_loss"], log_prob=t["log_prob"],
+                  q_min=t["q_min"], actor_loss_out=out["actor_loss"], action_pi=t["action_pi"], action_data=t["action_data"], weight=1.0, bc_scale=1.0 / M, scale_by_q=True,
+                  bc_loss_out=out["bc_loss"], bc_weight_out=out["bc_weight"], bc_rows_out=out["bc_rows"])
+        calls = {"policy_terms_cloned": lambda: env.policy_terms_cloned(ent_coef, M, q_filter=False, **kw),
+                 "policy_terms_weighted": lambda: env.policy_terms_weighted(ent_coef, M, temperature=1.0, max_weight=20.0, adv_ess_out=out["adv_ess"], adv_max_out=out["adv_max"],
+                                                                           adv_clipped_out=out["adv_clipped"], **kw)}
+        for call in calls.values():
+            for _ in range(20):
+                call()
+        wdw = {k: [] for k in calls}
+        for _ in range(args.windows):
+            for k, call in calls.items():
+                wdw[k].append(window(call))
+        sync()
+        med = {k: float(np.median(v)) for k, v in wdw.items()}
+        launch[str(M)] = {"us_per_launch_device_events_median": med, "us_per_launch_device_events_min": {k: float(min(v)) for k, v in wdw.items()},
+                          "us_per_launch_device_events_max": {k: float(max(v)) for k, v in wdw.items()},
+                          "weighted_minus_cloned_us": med["policy_terms_weighted"] - med["policy_terms_cloned"],
+                          "weighted_over_cloned": med["policy_terms_weighted"] / med["policy_terms_cloned"], "adv_ess": float(out["adv_ess"].item()),
+                          "adv_max": float(out["adv_max"].item()), "adv_clipped": int(out["adv_clipped"].item()), "rows": int(out["bc_rows"].item())}
+
+    options = dict(device_action_gradient=True, device_critic_gradient=True, device_actor_gradient=True, device_optimizer=True, device_entropy=True)
+    bc = dict(bc_weight=1.0, bc_scale_by_q=True)
+    routes = {"native": {}, "native_cloned": bc, "native_weighted": dict(bc, bc_advantage_temperature=1.0, bc_advantage_max_weight=20.0)}
+    learners = {}
+    for label, extra in routes.items():
+        learner = SACLearner(env, seed=0, batch_size=256, hidden_width=256, learning_starts=0, **options, **extra)
+        replay = DeviceReplay(env, 64)
+        learner.collect(replay, 4)
+        learners[label] = (learner, replay, [0])
+
+    def updates(label, count):
+        learner, replay, draw = learners[label]
+        learner.train(replay, 1, 0, count, seed=1, first_draw=draw[0] + 1)
+        draw[0] += count
+
+    def update_window(label):
+        sync()
+        t0 = time.perf_counter()
+        updates(label, per_window)
+        sync()
+        return (time.perf_counter() - t0) * 1e6 / per_window
+
+    for label in learners:
+        updates(label, 10)
+    wdw = {label: [] for label in learners}
+    for _ in range(args.windows):
+        for label in learners:
+            wdw[label].append(update_window(label))
+    med = {k: float(np.median(v)) for k, v in wdw.items()}
+    last = learners["native_weighted"][0].last_update
+    result = {"tool": "bench_policy_rollout --clone-weighted", "env": args.env, "num_envs": n, "windows": args.windows, "launches_per_window": per_window,
+              "device": torch.cuda.get_device_name(0), "launch": launch, "update": {
+                  "batch": 256, "hidden_width": 256, "options": routes["native_weighted"], "us_per_update_median": med,
+                  "us_per_update_min": {k: float(min(v)) for k, v in wdw.items()}, "us_per_update_max": {k: float(max(v)) for k, v in wdw.items()},
+                  "us_per_update_windows": {k: [round(x, 2) for x in v] for k, v in wdw.items()},
+                  "native_weighted_minus_native_cloned_us": med["native_weighted"] - med["native_cloned"],
+                  "native_cloned_minus_native_us": med["native_cloned"] - med["native"],
+                  "last_update": {"bc_loss": float(last["bc_loss"][0]), "bc_weight": float(last["bc_weight"][0]), "bc_rows": int(last["bc_rows"][0]),
+                                  "adv_ess": float(last["adv_ess"][0]), "adv_max": float(last["adv_max"][0]), "adv_clipped": int(last["adv_clipped"][0])}}}
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    for learner, _, _ in learners.values():
+        learner.close()
+    env.close()
+
+
 def demos_mode(args):
     """--demos: the mixed gather beside urgym_replay_sample and the masked terms beside urgym_sac_policy_terms_cloned at two batch sizes, and
     the update without and with a demonstration ring (see above).  Every pair alternates in one process."""
@@ -2076,6 +2190,7 @@ def main():
     ap.add_argument("--entropy", action="store_true", help="measure the learner's update with device_optimizer only against the same plus device_entropy (see above)")
     ap.add_argument("--clip", action="store_true", help="measure the update with max_grad_norm against the update without it, as update() calls and as one native call per window (see above)")
     ap.add_argument("--clone", action="store_true", help="measure urgym_sac_policy_terms_cloned against urgym_sac_policy_terms at M = 256 and 65536, and the update with and without bc_weight (see above)")
+    ap.add_argument("--clone-weighted", action="store_true", help="measure urgym_sac_policy_terms_weighted against urgym_sac_policy_terms_cloned at M = 256 and 65536, and the native update without cloning, with plain cloning and with the advantage weight (see above)")
     ap.add_argument("--demos", action="store_true", help="measure urgym_replay_sample_mixed against urgym_replay_sample and the masked cloned terms against the cloned ones at M = 256 and 65536 (D = M / 2), and the update with and without a demonstration ring (see above)")
     ap.add_argument("--normalize", action="store_true", help="measure the update with normalize against the update without it, the collection step without and with the normalize launch, and the fold (see above)")
     ap.add_argument("--normalize-only", action="store_true", help="--normalize: run only the normalized collection, the fold and the normalized native updates (for a kernel trace)")
@@ -2104,6 +2219,8 @@ def main():
         return monitor_mode(args)
     if args.evaluate:
         return evaluate_mode(args)
+    if args.clone_weighted:
+        return clone_weighted_mode(args)
     if args.clone:
         return clone_mode(args)
     if args.demos:

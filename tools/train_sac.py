@@ -49,6 +49,10 @@ policy's action is pulled towards the action the ring holds -- the planner's, wi
 times the batch's mean |min Q| (TD3+BC's normalisation), on every row or with --bc-q-filter on the rows where the critics rate the ring's
 action above the policy's own; with --native urgym_sac_train_cloned.  Every evaluation line then also carries the three losses, bc_loss,
 bc_weight and the cloned share of the batch of the latest update.
+--bc-advantage-temperature T (with --bc-weight, not with --bc-q-filter) weights every cloned row by exp(advantage / T),
+normalised over the batch and capped at --bc-advantage-max-weight (SACLearner(bc_advantage_temperature=T, bc_advantage_max_weight=);
+with --native urgym_sac_train_weighted): the evaluation lines then also carry adv_ess (the effective number of rows the weights spread over),
+adv_max (the largest weight) and adv_clipped (the rows the cap held), and with --native one more line gives adv_ess over the whole run.
 --demo-steps T --demo-envs N_d fills a demonstration ring first: T steps of the planner the --planner* flags describe
 on a second env of N_d envs, filed into a ring of T slots that the run never writes again (--demo-save PATH keeps it as an .npz,
 --demo-load PATH reads one instead of filling).  --demo-batch-size D then draws the first D rows of every minibatch from it
@@ -113,6 +117,10 @@ def main():
                          "cloned share with the losses (needs --device-entropy; DESIGN.md section 33)")
     ap.add_argument("--bc-scale-by-q", action="store_true", help="--bc-weight: multiply the weight by the batch's mean |min Q| (TD3+BC's normalisation)")
     ap.add_argument("--bc-q-filter", action="store_true", help="--bc-weight: clone only the rows where the critics rate the ring's action above the policy's own")
+    ap.add_argument("--bc-advantage-temperature", type=float, default=None, metavar="T",
+                    help="--bc-weight: weight every cloned row by exp(advantage / T), normalised over the batch (AWAC's weight; not with --bc-q-filter; "
+                         "DESIGN.md section 35)")
+    ap.add_argument("--bc-advantage-max-weight", type=float, default=None, metavar="C", help="--bc-advantage-temperature: cap a row's weight at C (default: no cap)")
     ap.add_argument("--demo-steps", type=int, default=0, metavar="T",
                     help="fill a demonstration ring of T slots first, on a second env of the same kind, with the planner the --planner* flags describe "
                          "(guided by the learner's initial networks where they ask for a guide; --planner itself is not needed; DESIGN.md section 34)")
@@ -182,6 +190,10 @@ def main():
         raise SystemExit("--planner plans on raw rows: not with --normalize (the planner's actor and critic read raw rows)")
     if (args.bc_scale_by_q or args.bc_q_filter) and args.bc_weight is None:
         raise SystemExit("--bc-scale-by-q and --bc-q-filter qualify --bc-weight and need it")
+    if args.bc_advantage_temperature is not None and (args.bc_weight is None or args.bc_q_filter):
+        raise SystemExit("--bc-advantage-temperature needs --bc-weight and is the alternative to --bc-q-filter")
+    if args.bc_advantage_max_weight is not None and args.bc_advantage_temperature is None:
+        raise SystemExit("--bc-advantage-max-weight qualifies --bc-advantage-temperature and needs it")
     if args.demo_batch_size is not None and args.demo_steps < 1:
         raise SystemExit("--demo-batch-size needs a demonstration ring: give --demo-steps T (with --demo-load, the capacity of the file's ring)")
     if (args.demo_save or args.demo_load) and args.demo_steps < 1:
@@ -223,6 +235,8 @@ def main():
                          **(dict(hindsight=True, her_n_sampled_goal=args.her_n_sampled_goal, her_strategy=args.her_strategy) if args.hindsight else {}),
                          **(dict(max_grad_norm=args.max_grad_norm) if args.max_grad_norm is not None else {}),
                          **(dict(bc_weight=args.bc_weight, bc_scale_by_q=args.bc_scale_by_q, bc_q_filter=args.bc_q_filter) if args.bc_weight is not None else {}),
+                         **(dict(bc_advantage_temperature=args.bc_advantage_temperature, bc_advantage_max_weight=args.bc_advantage_max_weight)
+                            if args.bc_advantage_temperature is not None else {}),
                          **(dict(demonstrations=demos, demo_batch_size=args.demo_batch_size, bc_demo_only=args.bc_demo_only) if args.demo_batch_size is not None else {}),
                          **(dict(normalize=True, norm_obs=not args.no_norm_obs, norm_reward=not args.no_norm_reward, clip_obs=args.clip_obs,
                                  clip_reward=args.clip_reward, norm_epsilon=args.norm_epsilon) if args.normalize else {}))
@@ -288,7 +302,8 @@ def main():
         norms = {}
         if with_losses:  # the run is synchronised here anyway
             norms = {k: float(v) for k, v in latest.items()}
-            keys = (("critic_grad_norm", "actor_grad_norm") if args.max_grad_norm is not None else ()) + (("bc_loss", "bc_weight", "bc_rows") if args.bc_weight is not None else ())
+            keys = (("critic_grad_norm", "actor_grad_norm") if args.max_grad_norm is not None else ()) + (("bc_loss", "bc_weight", "bc_rows") if args.bc_weight is not None else ()) + \
+                (("adv_ess", "adv_max", "adv_clipped") if args.bc_advantage_temperature is not None else ())
             norms.update({k: float(learner.last_update[k][0]) for k in keys})
             cloned_share(norms)
         if args.save_best and res["mean_episode_reward"] > best["mean"]:  # strictly above, as the reference's EvalCallback decides
@@ -370,6 +385,11 @@ def main():
             print(json.dumps({"updates": done, "env_steps": (trip + 1) * env.num_envs, "seconds": seconds, "mean_episode_return": rec["mean_return"],
                               "success_rate_percent": 100.0 * rec["success_rate"], "std_episode_return": rec["std_return"],
                               "mean_episode_length": rec["mean_length"], "improved": bool(rec["improved"]), **norms}), flush=True)
+        if "adv_ess" in curve and curve["adv_ess"].size:  # the weights' effective sample size over every update of this process
+            ess, rows = curve["adv_ess"], curve["bc_rows"]
+            print(json.dumps({"adv_updates": int(ess.size), "adv_ess_mean": float(ess.mean()), "adv_ess_min": float(ess.min()), "adv_ess_max": float(ess.max()),
+                              "adv_ess_share_of_rows_mean": float((ess / rows.clip(1)).mean()), "adv_max_mean": float(curve["adv_max"].mean()),
+                              "adv_clipped_mean": float(curve["adv_clipped"].mean())}), flush=True)
         if mon is not None:
             print_curve(round(time.perf_counter() - t0, 1) if seconds is None else seconds)
             if planner is not None:

@@ -684,6 +684,19 @@ class SacDemonstrating(C.Structure):
                 ("reserved0", C.c_int32)]
 
 
+class SacAdvantageArgs(C.Structure):
+    """urgym_sac_advantage_args: what urgym_sac_policy_terms_weighted takes beside the clone args -- the temperature and the cap of the
+    advantage weight, the optional row mask and the three outputs."""
+    _fields_ = [("temperature", C.c_float), ("max_weight", C.c_float), ("row_mask", C.POINTER(C.c_uint8)), ("adv_ess_out", C.POINTER(C.c_float)),
+                ("adv_max_out", C.POINTER(C.c_float)), ("adv_clipped_out", C.POINTER(C.c_int32)), ("reserved0", C.c_int32)]
+
+
+class SacWeighting(C.Structure):
+    """urgym_sac_weighting: the option of urgym_sac_train_weighted -- the temperature, the cap and the per-update records."""
+    _fields_ = [("temperature", C.c_float), ("max_weight", C.c_float), ("reserved0", C.c_int32), ("adv_ess", C.POINTER(C.c_float)),
+                ("adv_max", C.POINTER(C.c_float)), ("adv_clipped", C.POINTER(C.c_int32))]
+
+
 # Every symbol include/urgym.h declares (tests check that the built library exports each of them).
 EXPORTED_SYMBOLS = [
     "urgym_abi_version",
@@ -791,6 +804,8 @@ EXPORTED_SYMBOLS = [
     "urgym_replay_sample_mixed",
     "urgym_sac_policy_terms_cloned_masked",
     "urgym_sac_train_demonstrated",
+    "urgym_sac_policy_terms_weighted",
+    "urgym_sac_train_weighted",
     "urgym_refresh",
     "urgym_invalidate_records",
     "urgym_derive_obstacle_motion",

@@ -198,6 +198,12 @@ def lib():
                                                C.POINTER(_abi.SacCloning), C.POINTER(_abi.SacPlanning), C.POINTER(_abi.MppiTemper), C.POINTER(_abi.MppiNoise),
                                                C.POINTER(_abi.Normalization), C.POINTER(_abi.SacClipping), C.POINTER(_abi.SacEvaluation),
                                                C.POINTER(_abi.SacMonitoring), C.c_void_p]
+    L.urgym_sac_policy_terms_weighted.argtypes = [C.c_void_p, C.POINTER(_abi.SacPolicyArgs), C.POINTER(_abi.SacCloneArgs), C.POINTER(_abi.SacAdvantageArgs), C.c_void_p]
+    L.urgym_sac_train_weighted.argtypes = [C.c_void_p, C.POINTER(_abi.SacLearner), C.POINTER(_abi.SacSchedule), C.POINTER(_abi.SacWeighting),
+                                           C.POINTER(_abi.SacCloning), C.POINTER(_abi.SacDemonstrating), C.POINTER(_abi.SacPlanning), C.POINTER(_abi.MppiTemper),
+                                           C.POINTER(_abi.MppiNoise), C.POINTER(_abi.Normalization), C.POINTER(_abi.SacClipping), C.POINTER(_abi.SacNstep),
+                                           C.POINTER(_abi.SacPrioritized), C.POINTER(_abi.SacHindsight), C.POINTER(_abi.SacEvaluation),
+                                           C.POINTER(_abi.SacMonitoring), C.c_void_p]
     L.urgym_actor_read_packed.argtypes =[C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.urgym_critic_read_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.urgym_refresh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]

@@ -519,6 +519,26 @@ int check_policy_terms_cloned(Handle* h, const SacPolicyCall& call, const urgym_
   return URGYM_OK;
 }
 
+// what urgym_sac_policy_terms_weighted and urgym_sac_train_weighted refuse about the option's numbers, or null
+const char* weight_option_refusal(float temperature, float max_weight, int32_t reserved0, int32_t q_filter) {
+  if (reserved0 != 0) return "reserved0 of the advantage-weight struct must be 0";
+  if (q_filter != 0) return "q_filter must be 0 with the advantage weight (the two gates are alternatives)";
+  if (!(temperature > 0.0f && temperature < INFINITY)) return "the advantage temperature must be finite and > 0";  // refuses NaN too
+  if (!(max_weight > 0.0f)) return "max_weight must be > 0 (finite or +infinity)";                               // refuses NaN too
+  return nullptr;
+}
+
+// urgym_sac_policy_terms_weighted: after check_policy_terms and check_policy_terms_cloned of the same call
+int check_policy_terms_weighted(Handle* h, const SacCloneCall& clone, const urgym_sac_advantage_args* advantage, const char* who, SacAdvantageCall* out) {
+  if (!advantage) return fail_in(h, URGYM_ERR_ARG, who, "null advantage args");
+  const urgym_sac_advantage_args& a = *advantage;
+  if (!a.adv_ess_out || !a.adv_max_out || !a.adv_clipped_out)
+    return fail_in(h, URGYM_ERR_ARG, who, "an output pointer of urgym_sac_advantage_args is null (adv_ess_out, adv_max_out, adv_clipped_out)");
+  if (const char* what = weight_option_refusal(a.temperature, a.max_weight, a.reserved0, clone.q_filter)) return fail_in(h, URGYM_ERR_ARG, who, what);
+  *out = SacAdvantageCall{a.temperature, a.max_weight, a.row_mask, a.adv_ess_out, a.adv_max_out, a.adv_clipped_out};
+  return URGYM_OK;
+}
+
 int check_sample_rows(Handle* h, void* actor, const urgym_sampling* how, const urgym_critic_rows* rows, int count, float* actions_dev, float* log_prob_dev,
                       const char* who, SampleRows* out) {
   Actor* a = nullptr;
@@ -900,6 +920,22 @@ int urgym_sac_policy_terms_cloned_masked(void* handle, const urgym_sac_policy_ar
   if (!row_mask) return fail_in(h, URGYM_ERR_ARG, who, "null row_mask");
   HIP_TRY(h, hipSetDevice(h->device));
   sac_policy_bc_masked_launch(c, b, row_mask, (hipStream_t)stream);
+  return launched(h);
+}
+
+// the cloned policy terms with the advantage weight in the place of the verdict (urgym_sac_bc_weighted.hip)
+int urgym_sac_policy_terms_weighted(void* handle, const urgym_sac_policy_args* args, const urgym_sac_clone_args* clone, const urgym_sac_advantage_args* advantage, void* stream) {
+  const char* who = "urgym_sac_policy_terms_weighted";
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  SacPolicyCall c;
+  SacCloneCall b;
+  SacAdvantageCall w;
+  if (int rc = check_policy_terms(h, args, who, &c)) return rc;
+  if (int rc = check_policy_terms_cloned(h, c, clone, who, &b)) return rc;
+  if (int rc = check_policy_terms_weighted(h, b, advantage, who, &w)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  sac_policy_bc_weighted_launch(c, b, w, (hipStream_t)stream);
   return launched(h);
 }
 
@@ -1858,6 +1894,7 @@ struct TrainOptions {
   const urgym_sac_cloning* cloning;        // the update whose policy terms are urgym_sac_policy_terms_cloned's (urgym_sac_train_cloned)
   const urgym_sac_demonstrating* demonstrating;  // the update whose gather is urgym_replay_sample_mixed's; with cloning and
                                                  // clone_demonstrations_only its policy terms are the masked ones (urgym_sac_train_demonstrated)
+  const urgym_sac_weighting* weighting;    // with cloning: the policy terms are urgym_sac_policy_terms_weighted's (urgym_sac_train_weighted)
 };
 
 // The evaluations and the training-episode statistics of one training call: what the body runs beside its own checks and launches.
@@ -1964,7 +2001,7 @@ struct TrainExtras {
   }
 };
 
-// The one driver of the thirteen urgym_sac_train* entry points: `who` is the entry point's own name in every refusal, `opt` what it was given.
+// The one driver of the fourteen urgym_sac_train* entry points: `who` is the entry point's own name in every refusal, `opt` what it was given.
 int sac_train_body(const char* who, Handle* h, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, hipStream_t s, const TrainOptions& opt) {
   if (!learner) return fail_in(h, URGYM_ERR_ARG, who, "null learner");
   if (!schedule) return fail_in(h, URGYM_ERR_ARG, who, "null schedule");
@@ -1976,6 +2013,7 @@ int sac_train_body(const char* who, Handle* h, const urgym_sac_learner* learner,
   const urgym_sac_planning* const planning = opt.planning;
   const urgym_sac_cloning* const cloning = opt.cloning;
   const urgym_sac_demonstrating* const demonstrating = opt.demonstrating;
+  const urgym_sac_weighting* const weighting = opt.weighting;
   PlannedCall planned;
   TrainExtras extras{who, h, learner, schedule, s, opt.evaluation, opt.monitoring, norm, planning ? &planned : nullptr};
   const urgym_sac_learner& L = *learner;
@@ -2039,6 +2077,12 @@ int sac_train_body(const char* who, Handle* h, const urgym_sac_learner* learner,
     if (const char* what = clone_option_refusal(cloning->weight, cloning->scale_by_q, cloning->q_filter, cloning->reserved0)) return fail_in(h, URGYM_ERR_ARG, who, what);
     if ((!cloning->bc_loss || !cloning->bc_weight || !cloning->bc_rows) && sac_schedule_updates(S) > 0)  // zero slots need no array
       return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_cloning.bc_loss, bc_weight or bc_rows is null");
+  }
+  if (weighting) {  // the option's own refusals, whether or not the call holds an update
+    if (!cloning) return fail_in(h, URGYM_ERR_ARG, who, "weighting needs cloning");
+    if (const char* what = weight_option_refusal(weighting->temperature, weighting->max_weight, weighting->reserved0, cloning->q_filter)) return fail_in(h, URGYM_ERR_ARG, who, what);
+    if ((!weighting->adv_ess || !weighting->adv_max || !weighting->adv_clipped) && sac_schedule_updates(S) > 0)  // zero slots need no array
+      return fail_in(h, URGYM_ERR_ARG, who, "urgym_sac_weighting.adv_ess, adv_max or adv_clipped is null");
   }
   ReplayGatherMixed gather_mixed;
   if (demonstrating) {  // the option's own refusals, whether or not the call holds an update: the gather's checks on the ring as it stands
@@ -2242,6 +2286,14 @@ int sac_train_body(const char* who, Handle* h, const urgym_sac_learner* learner,
     if (int rc = check_policy_terms_cloned(h, terms_call, &ca, who, &clone_call)) return rc;
   }
   const bool clone_masked = cloning && demonstrating && demonstrating->clone_demonstrations_only != 0;  // row_mask = source
+  SacAdvantageCall weight_call;
+  if (weighting) {
+    urgym_sac_advantage_args wa;
+    memset(&wa, 0, sizeof(wa));
+    wa.temperature = weighting->temperature, wa.max_weight = weighting->max_weight, wa.row_mask = clone_masked ? demonstrating->source : nullptr;
+    wa.adv_ess_out = weighting->adv_ess, wa.adv_max_out = weighting->adv_max, wa.adv_clipped_out = weighting->adv_clipped;
+    if (int rc = check_policy_terms_weighted(h, clone_call, &wa, who, &weight_call)) return rc;
+  }
   const urgym_actor_upstream upstream{L.d_action, L.d_log_prob, nullptr, nullptr};
   urgym_actor_param_grads ag;
   memset(&ag, 0, sizeof(ag));
@@ -2341,7 +2393,11 @@ int sac_train_body(const char* who, Handle* h, const urgym_sac_learner* learner,
       if (cloning) {
         clone_call.bc_loss_out = cloning->bc_loss + up.loss_slot, clone_call.bc_weight_out = cloning->bc_weight + up.loss_slot;
         clone_call.bc_rows_out = cloning->bc_rows + up.loss_slot;
-        if (clone_masked)
+        if (weighting) {
+          weight_call.adv_ess_out = weighting->adv_ess + up.loss_slot, weight_call.adv_max_out = weighting->adv_max + up.loss_slot;
+          weight_call.adv_clipped_out = weighting->adv_clipped + up.loss_slot;
+          sac_policy_bc_weighted_launch(terms_call, clone_call, weight_call, s);
+        } else if (clone_masked)
           sac_policy_bc_masked_launch(terms_call, clone_call, demonstrating->source, s);
         else
           sac_policy_bc_launch(terms_call, clone_call, s);
@@ -2395,7 +2451,7 @@ const char* const ONE_GATHER = "at most one of nstep, prioritized and hindsight 
 extern "C" {
 
 // Each entry point: the null handle, its own required option, then the driver with what it was given.  TrainOptions' order is
-// {nstep, per, her, clip, norm, evaluation, monitoring, planning, temper, noise, cloning, demonstrating}.
+// {nstep, per, her, clip, norm, evaluation, monitoring, planning, temper, noise, cloning, demonstrating, weighting}.
 
 int urgym_sac_train(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, void* stream) {
   Handle* h = (Handle*)handle;
@@ -2509,6 +2565,20 @@ int urgym_sac_train_demonstrated(void* handle, const urgym_sac_learner* learner,
   if (!planning_or_NULL && (temper_or_NULL || noise_or_NULL)) return fail_in(h, URGYM_ERR_ARG, who, "temper and noise are the planner's and need planning");
   if (planning_or_NULL && normalization_or_NULL) return fail_in(h, URGYM_ERR_ARG, who, "normalization together with planning is out of scope (the planner's actor and critic read raw rows)");
   return sac_train_body(who, h, learner, schedule, (hipStream_t)stream, TrainOptions{nullptr, nullptr, nullptr, clipping_or_NULL, normalization_or_NULL, evaluation_or_NULL, monitoring_or_NULL, planning_or_NULL, temper_or_NULL, noise_or_NULL, cloning_or_NULL, demonstrating});
+}
+
+int urgym_sac_train_weighted(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_weighting* weighting, const urgym_sac_cloning* cloning, const urgym_sac_demonstrating* demonstrating_or_NULL, const urgym_sac_planning* planning_or_NULL, const urgym_mppi_temper* temper_or_NULL, const urgym_mppi_noise* noise_or_NULL, const urgym_normalization* normalization_or_NULL, const urgym_sac_clipping* clipping_or_NULL, const urgym_sac_nstep* nstep_or_NULL, const urgym_sac_prioritized* prioritized_or_NULL, const urgym_sac_hindsight* hindsight_or_NULL, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream) {
+  const char* who = "urgym_sac_train_weighted";
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (!weighting) return fail_in(h, URGYM_ERR_ARG, who, "null weighting");
+  if (!cloning) return fail_in(h, URGYM_ERR_ARG, who, "null cloning");
+  if (!planning_or_NULL && (temper_or_NULL || noise_or_NULL)) return fail_in(h, URGYM_ERR_ARG, who, "temper and noise are the planner's and need planning");
+  if (planning_or_NULL && normalization_or_NULL) return fail_in(h, URGYM_ERR_ARG, who, "normalization together with planning is out of scope (the planner's actor and critic read raw rows)");
+  if ((nstep_or_NULL != nullptr) + (prioritized_or_NULL != nullptr) + (hindsight_or_NULL != nullptr) > 1) return fail_in(h, URGYM_ERR_ARG, who, ONE_GATHER);
+  if (demonstrating_or_NULL && (nstep_or_NULL || prioritized_or_NULL || hindsight_or_NULL))
+    return fail_in(h, URGYM_ERR_ARG, who, "demonstrations together with nstep, prioritized or hindsight is out of scope (each of those has a gather of its own)");
+  return sac_train_body(who, h, learner, schedule, (hipStream_t)stream, TrainOptions{nstep_or_NULL, prioritized_or_NULL, hindsight_or_NULL, clipping_or_NULL, normalization_or_NULL, evaluation_or_NULL, monitoring_or_NULL, planning_or_NULL, temper_or_NULL, noise_or_NULL, cloning, demonstrating_or_NULL, weighting});
 }
 
 }  // extern "C"

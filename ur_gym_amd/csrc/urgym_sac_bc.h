@@ -6,6 +6,7 @@
 #pragma once
 #include <stdint.h>
 
+#include "urgym_mppi_temper.h"  // mppi_temper_weight / mppi_temper_exp, mppi_square_term, mppi_ess: the advantage weight's float64 (section 35)
 #include "urgym_sac_terms.h"
 
 namespace urgym {
@@ -50,6 +51,40 @@ URGYM_HD inline float sac_bc_upstream(float g, float d, float w, float bc_scale)
   return g + u;
 }
 
+// ---- ADVANTAGE-WEIGHTED CLONING (urgym_sac_policy_terms_weighted): every eligible row is cloned, with a weight
+// exp(A / temperature) normalised to mean 1 over the eligible rows (AWAC, Nair et al. 2020; the exponential variant of CRR, Wang et al.
+// 2020), capped at max_weight.  The exponential, the square and the effective sample size are urgym_mppi_temper.h's and urgym_mppi.h's,
+// used as they are.  ur_gym_amd.evaluation.policy_terms_weighted restates the lines below.
+
+// the advantage of the replayed action over the policy's own: one float32 subtraction
+URGYM_HD inline float sac_adv_advantage(float q_data, float q_min) { return q_data - q_min; }
+// false for a NaN and for either infinity
+URGYM_HD inline bool sac_adv_finite(float a) { return a - a == 0.0f; }
+// THE ELIGIBLE ROW: marked (or no mask at all) and a finite advantage
+URGYM_HD inline bool sac_adv_eligible(bool masked, uint8_t mask, float advantage) { return (!masked || mask != 0) && sac_adv_finite(advantage); }
+// one term of A_max: a row that is not eligible is passed over.  Comparisons of finite float32: the order does not matter
+URGYM_HD inline float sac_adv_max_term(bool eligible, float advantage) { return eligible ? advantage : -INFINITY; }
+URGYM_HD inline float sac_adv_max(float a, float b) { return b > a ? b : a; }
+// e = exp((A - A_max) / temperature) in float64, +0.0 for a row that is not eligible: the argument is never positive
+URGYM_HD inline double sac_adv_e(float advantage, float a_max, float temperature, bool eligible) {
+  return mppi_temper_weight((double)advantage, (double)a_max, (double)temperature, eligible);
+}
+// the mean of e over the n eligible rows (n >= 1: the A_max row has e = 1, so the mean is positive)
+URGYM_HD inline double sac_adv_mean_e(double Z, int n) { return Z / (double)n; }
+// the weight of a row: u = e / mean_e, capped; `over` says whether the cap held it
+URGYM_HD inline float sac_adv_row_weight(double e, double mean_e, float max_weight, bool& over) {
+  const double u = e / mean_e;
+  over = u > (double)max_weight;
+  const double v = over ? (double)max_weight : u;
+  return (float)v;
+}
+// the term of the weighted cloning loss of one row: one float32 product
+URGYM_HD inline float sac_adv_term(float a, float h) { return a * h; }
+// the weight of one element of an eligible row: the scalar w times the row's a
+URGYM_HD inline float sac_adv_element_weight(float w, float a) { return w * a; }
+// the effective sample size of the weights, rounded to float32 once
+URGYM_HD inline float sac_adv_ess(double Z, double Q) { return (float)mppi_ess(Z, Q); }
+
 }  // namespace urgym
 
 #if defined(__HIPCC__)
@@ -71,6 +106,18 @@ void sac_policy_bc_launch(const SacPolicyCall& call, const SacCloneCall& clone, 
 
 // The same launch with the masked verdict (urgym_sac_bc_masked.hip, a unit of its own): row_mask is a DEVICE pointer, [count], not null
 void sac_policy_bc_masked_launch(const SacPolicyCall& call, const SacCloneCall& clone, const uint8_t* row_mask, hipStream_t s);
+
+// include/urgym.h, urgym_sac_advantage_args, validated: DEVICE pointers; row_mask may be null, the outputs are not
+struct SacAdvantageCall {
+  float temperature, max_weight;
+  const uint8_t* row_mask;
+  float *adv_ess_out, *adv_max_out;
+  int32_t* adv_clipped_out;
+};
+
+// The launch with the advantage weight in the place of the verdict (urgym_sac_bc_weighted.hip, a unit of its own): ONE workgroup of
+// SAC_TERMS_LANES lanes, three sweeps.  clone.q_filter is 0 (the caller has refused anything else).
+void sac_policy_bc_weighted_launch(const SacPolicyCall& call, const SacCloneCall& clone, const SacAdvantageCall& adv, hipStream_t s);
 
 }  // namespace urgym
 #endif

@@ -880,6 +880,83 @@ def policy_terms_cloned(alpha, *, dqmin_da, scale, q, y, log_prob, q_min, action
     return out
 
 
+def policy_terms_weighted(alpha, *, dqmin_da, scale, q, y, log_prob, q_min, action_pi, action_data, weight, bc_scale, temperature, max_weight=np.inf,
+                          scale_by_q=False, row_mask=None):
+    """urgym_sac_policy_terms_weighted restated from include/urgym.h ("advantage-weighted cloning in the policy loss") in numpy, line by
+    line: float32 where the header says float32, float64 where it says float64, the sums by ``ordered_sum``, the exponential by
+    ``mppi_temper_exp``.  The arguments of ``policy_terms_cloned`` without the Q-filter, and `temperature` (finite, > 0 in float32),
+    `max_weight` (> 0, finite or inf), `row_mask` (None, or uint8 / bool [count]).  Returns a dict: ``d_action`` [count, 6],
+    ``critic_loss``, ``actor_loss``, ``bc_loss``, ``bc_weight``, ``adv_ess``, ``adv_max`` (float32 scalars), ``bc_rows``, ``adv_clipped``
+    (int32), ``eligible`` (bool [count]), ``advantage`` (A, float32 [count]), ``a`` (the weights, float32 [count]), ``e`` (float64
+    [count]), ``Z``, ``Q`` (float64), ``mean_abs`` (float32), ``bc_terms`` (h, float32 [count]) and ``weighted_terms`` (a * h)."""
+    f, d8 = np.float32, np.float64
+    out = policy_terms(alpha, dqmin_da=dqmin_da, scale=scale, q=q, y=y, log_prob=log_prob, q_min=q_min)
+    g = out.pop("d_action")
+    count = g.shape[0]
+    q, q_min = np.asarray(q), np.asarray(q_min)
+    action_pi, action_data = _rows32("action_pi", action_pi, (count, 6)), _rows32("action_data", action_data, (count, 6))
+    with np.errstate(all="ignore"):
+        weight, bc_scale, temperature, max_weight = f(weight), f(bc_scale), f(temperature), f(max_weight)
+        if not (np.isfinite(weight) and weight >= 0 and np.isfinite(bc_scale)):
+            raise ValueError(f"weight must be finite and >= 0 and bc_scale finite in float32, got {weight!r}, {bc_scale!r}")
+        if not (np.isfinite(temperature) and temperature > 0):
+            raise ValueError(f"temperature must be finite and > 0 in float32, got {temperature!r}")
+        if not max_weight > 0:
+            raise ValueError(f"max_weight must be > 0 (finite or inf), got {max_weight!r}")
+        qd = np.where(q[1] < q[0], q[1], q[0])
+        A = qd - q_min
+        eligible = np.isfinite(A)
+        if row_mask is not None:
+            mask = np.asarray(row_mask)
+            if mask.shape != (count,) or mask.dtype not in (np.dtype(np.uint8), np.dtype(bool)):
+                raise ValueError(f"row_mask must be uint8 or bool [{count}], got {mask.dtype} {mask.shape}")
+            eligible = (mask != 0) & eligible
+        n = int(np.count_nonzero(eligible))
+        absq = np.abs(q_min)
+        mean_abs = _ordered_mean(absq)
+        w = weight * mean_abs if scale_by_q else weight
+        d = action_pi - action_data
+        s = np.zeros(count, dtype=f)
+        for k in range(6):
+            p = d[:, k] * d[:, k]
+            s = s + p
+        h = np.where(eligible, f(0.5) * s, f(0.0))
+        e = np.zeros(count, dtype=d8)
+        a = np.zeros(count, dtype=f)
+        Z = Q = d8(0.0)
+        adv_ess = adv_max = f(0.0)
+        clipped = 0
+        if n > 0:
+            A_max = A[eligible].max()
+            dd = np.where(eligible, A.astype(d8) - d8(A_max), d8(0.0))
+            x = dd / d8(temperature)
+            e = np.where(eligible, mppi_temper_exp(x), d8(0.0))
+            Z, Q = ordered_sum(e, d8), ordered_sum(e * e, d8)
+            mean_e = Z / d8(n)
+            u = e / mean_e
+            over = eligible & (u > d8(max_weight))
+            v = np.where(over, d8(max_weight), u)
+            a = np.where(eligible, v, d8(0.0)).astype(f)
+            clipped = int(np.count_nonzero(over))
+            zz = Z * Z
+            adv_ess = f(zz / Q)
+            top = d8(1.0) / mean_e
+            adv_max = f(d8(max_weight) if top > d8(max_weight) else top)
+            for x64 in (dd, x, e, mean_e, u, v, zz):
+                assert x64.dtype == d8, x64.dtype
+        ah = a * h
+        bc_loss = _ordered_mean(ah)
+        wr = w * a
+        t = d * wr[:, None]
+        uu = t * bc_scale
+        d_action = np.where(eligible[:, None], g + uu, g)
+    for x32 in (qd, A, d, s, h, absq, mean_abs, a, ah, bc_loss, w, wr, t, uu, d_action, adv_ess, adv_max):
+        assert x32.dtype == f, x32.dtype  # no intermediate was promoted
+    out.update(d_action=d_action, bc_loss=bc_loss, bc_weight=w, bc_rows=np.int32(n), adv_ess=adv_ess, adv_max=adv_max, adv_clipped=np.int32(clipped),
+               eligible=eligible, advantage=A, a=a, e=e, Z=d8(Z), Q=d8(Q), mean_abs=mean_abs, bc_terms=h, weighted_terms=ah)
+    return out
+
+
 def _check_device_tensors(tensors, wanted, device, who):
     """`wanted`: name -> shape.  Raises ValueError unless every one is a contiguous float32 torch tensor of that shape on `device`."""
     import torch

@@ -70,6 +70,10 @@ minibatch gather on the HIP kernels, and gradients and optimisers in torch autog
     stand -- which adds ``X' (action_pi - action) / M`` to d_action on the rows it clones, X' = X or, with ``bc_scale_by_q``, X times the
     mean |min Q| (TD3+BC's normalisation), the rows being all of them or, with ``bc_q_filter``, those where the critics rate the ring's
     action above the policy's own.  ``None``, the default, makes exactly the calls above.
+    With ``bc_advantage_temperature=T`` (it needs ``bc_weight``, and not ``bc_q_filter``) that launch is
+    ``env.policy_terms_weighted``: every row is cloned with the weight exp(A / T) normalised to mean 1 over the batch, A the critics'
+    advantage of the ring's action over the policy's own, capped at ``bc_advantage_max_weight``; ``last_update`` and ``train``'s result
+    gain ``adv_ess``, ``adv_max`` and ``adv_clipped``.  ``None``, the default, makes exactly the calls above.
     None of them synchronises with the host.  ``train`` runs the whole loop in one native call and, given an
     ``evaluation.DeviceEvaluation``, the reference's EvalCallback inside it: evaluations of the deterministic policy at a fixed interval of
     updates, their statistics as records on the device, and the best actor's tensors, which ``DeviceEvaluation.save_best`` writes as an
@@ -114,6 +118,10 @@ BC_DEFAULTS = dict(bc_weight=None, bc_scale_by_q=False, bc_q_filter=False)
 # the default, is the learner as it was; demo_batch_size=0 takes the new calls and leaves the same bits.  Kept apart like the five above:
 # a run without it saves neither key.
 DEMO_DEFAULTS = dict(demo_batch_size=None, bc_demo_only=False)
+# Advantage-weighted cloning: SACLearner(bc_weight=X, bc_advantage_temperature=T) weights every cloned row by
+# exp(advantage / T), normalised over the batch and capped at bc_advantage_max_weight (None: no cap) -- AWAC's weight, the soft
+# alternative to bc_q_filter.  None, the default, is the learner as it was.  Kept apart like the six above: a run without it saves neither.
+ADV_DEFAULTS = dict(bc_advantage_temperature=None, bc_advantage_max_weight=None)
 
 
 def _mlp(n_in, hidden, n_out=None):
@@ -211,12 +219,29 @@ class SACLearner:
 
     def __init__(self, env, seed=0, demonstrations=None, **overrides):
         unknown = [k for k in overrides if k not in SAC_DEFAULTS and k not in PER_DEFAULTS and k not in HER_DEFAULTS and k not in CLIP_DEFAULTS and k not in NORM_DEFAULTS
-                   and k not in BC_DEFAULTS and k not in DEMO_DEFAULTS]
+                   and k not in BC_DEFAULTS and k not in DEMO_DEFAULTS and k not in ADV_DEFAULTS]
         if unknown:
             raise TypeError(f"unknown hyperparameters {unknown}; available: "
-                            f"{sorted(SAC_DEFAULTS) + sorted(PER_DEFAULTS) + sorted(HER_DEFAULTS) + sorted(CLIP_DEFAULTS) + sorted(NORM_DEFAULTS) + sorted(BC_DEFAULTS) + sorted(DEMO_DEFAULTS)}")
-        hp = dict(SAC_DEFAULTS, **PER_DEFAULTS, **HER_DEFAULTS, **CLIP_DEFAULTS, **NORM_DEFAULTS, **BC_DEFAULTS, **DEMO_DEFAULTS)
+                            f"{sorted(SAC_DEFAULTS) + sorted(PER_DEFAULTS) + sorted(HER_DEFAULTS) + sorted(CLIP_DEFAULTS) + sorted(NORM_DEFAULTS) + sorted(BC_DEFAULTS) + sorted(DEMO_DEFAULTS) + sorted(ADV_DEFAULTS)}")
+        hp = dict(SAC_DEFAULTS, **PER_DEFAULTS, **HER_DEFAULTS, **CLIP_DEFAULTS, **NORM_DEFAULTS, **BC_DEFAULTS, **DEMO_DEFAULTS, **ADV_DEFAULTS)
         hp.update(overrides)
+        if hp["bc_advantage_temperature"] is None:
+            if hp["bc_advantage_max_weight"] is not None:
+                raise ValueError("bc_advantage_max_weight qualifies bc_advantage_temperature and needs it")
+        else:
+            with np.errstate(over="ignore"):
+                T, cap = hp["bc_advantage_temperature"], hp["bc_advantage_max_weight"]
+                ok = not isinstance(T, bool) and isinstance(T, (int, float, np.integer, np.floating)) and bool(np.isfinite(np.float32(T))) and float(np.float32(T)) > 0.0
+                if not ok:
+                    raise ValueError(f"bc_advantage_temperature must be None or a number that is finite and > 0 in float32, got {T!r}")
+                ok = cap is None or (not isinstance(cap, bool) and isinstance(cap, (int, float, np.integer, np.floating)) and float(np.float32(cap)) > 0.0)
+                if not ok:
+                    raise ValueError(f"bc_advantage_max_weight must be None or a number > 0 in float32, got {cap!r}")
+            if hp["bc_weight"] is None:
+                raise ValueError("bc_advantage_temperature needs bc_weight (it weights the cloning term)")
+            if hp["bc_q_filter"] is True:
+                raise ValueError("bc_advantage_temperature together with bc_q_filter is refused: the two gates are alternatives")
+            hp["bc_advantage_temperature"], hp["bc_advantage_max_weight"] = float(T), None if cap is None else float(cap)
         if not isinstance(hp["bc_demo_only"], bool):
             raise ValueError(f"bc_demo_only must be True or False, got {hp['bc_demo_only']!r}")
         if hp["demo_batch_size"] is None:
@@ -370,6 +395,11 @@ class SACLearner:
         if hp["bc_weight"] is not None:
             self.bc_state = dict(bc_loss=torch.zeros((1,), dtype=torch.float32, device=dev), bc_weight=torch.zeros((1,), dtype=torch.float32, device=dev),
                                  bc_rows=torch.zeros((1,), dtype=torch.int32, device=dev))
+        # with bc_advantage_temperature the weights' effective sample size, the largest weight and the capped rows of the running update; never saved
+        self.adv_state = None
+        if hp["bc_advantage_temperature"] is not None:
+            self.adv_state = dict(adv_ess=torch.zeros((1,), dtype=torch.float32, device=dev), adv_max=torch.zeros((1,), dtype=torch.float32, device=dev),
+                                  adv_clipped=torch.zeros((1,), dtype=torch.int32, device=dev))
         # with normalize the running statistics, the actor's scratch rows and the fold's workspace are the normalizer's
         self.normalizer = None
         if hp["normalize"]:
@@ -572,6 +602,13 @@ class SACLearner:
                       log_prob=log_prob, q_min=grad["q_min"], actor_loss_out=es["actor_loss"])
         if bc is None:
             self.env.policy_terms(es["ent_coef"], M, **common)
+        elif self.adv_state is not None:  # the advantage weight in the place of the verdict: still ONE launch
+            adv = self.adv_state
+            self.env.policy_terms_weighted(
+                es["ent_coef"], M, **common, **(dict(row_mask=source) if hp["bc_demo_only"] else {}), action_pi=action_pi, action_data=actions, weight=hp["bc_weight"],
+                bc_scale=1.0 / M, scale_by_q=hp["bc_scale_by_q"], bc_loss_out=bc["bc_loss"], bc_weight_out=bc["bc_weight"], bc_rows_out=bc["bc_rows"],
+                temperature=hp["bc_advantage_temperature"], max_weight=hp["bc_advantage_max_weight"], adv_ess_out=adv["adv_ess"], adv_max_out=adv["adv_max"],
+                adv_clipped_out=adv["adv_clipped"])
         else:
             masked = dict(row_mask=source) if hp["bc_demo_only"] else {}
             (self.env.policy_terms_cloned_masked if masked else self.env.policy_terms_cloned)(
@@ -581,7 +618,7 @@ class SACLearner:
     def _bc_record(self, action_pi, actions):
         """What ``last_update`` gains with ``bc_weight``: references to the cloning loss, the weight used and the number of cloned rows, and
         to the two actions the cloning term was formed from."""
-        return {} if self.bc_state is None else dict(self.bc_state, action_pi=action_pi, action_data=actions)
+        return {} if self.bc_state is None else dict(self.bc_state, **(self.adv_state or {}), action_pi=action_pi, action_data=actions)
 
     def _clip(self, which):
         """With ``max_grad_norm``: ONE launch reduces the global norm of the critics' (or the actor's) gradients into the learner's
@@ -757,6 +794,11 @@ class SACLearner:
             bc_out = dict(bc_loss=torch.empty((updates,), dtype=torch.float32, device=env.device), bc_weight=torch.empty((updates,), dtype=torch.float32, device=env.device),
                           bc_rows=torch.empty((updates,), dtype=torch.int32, device=env.device))
             cloning = dict(cloning=dict(weight=hp["bc_weight"], scale_by_q=hp["bc_scale_by_q"], q_filter=hp["bc_q_filter"], **bc_out))
+        if self.adv_state is not None:
+            adv_out = dict(adv_ess=torch.empty((updates,), dtype=torch.float32, device=env.device), adv_max=torch.empty((updates,), dtype=torch.float32, device=env.device),
+                           adv_clipped=torch.empty((updates,), dtype=torch.int32, device=env.device))
+            cloning["weighting"] = dict(temperature=hp["bc_advantage_temperature"], max_weight=hp["bc_advantage_max_weight"], **adv_out)
+            bc_out.update(adv_out)
         if self.demonstrations is not None:  # read at its own oldest_slot and filled as they stand now
             cloning["demonstrating"] = dict(replay=self.demonstrations, count=hp["demo_batch_size"], source=self.demo_source, clone_only=hp["bc_demo_only"])
         tr["binding"].struct.update_seed = int(seed)
@@ -786,7 +828,7 @@ class SACLearner:
                                         actor_scale=cs["actor_scale"])
             if self.demonstrations is not None:
                 self.last_update.update(source=self.demo_source)
-            if bc_out:  # the last update's three, as views of the call's slots
+            if bc_out:  # the last update's three (six with the advantage weight), as views of the call's slots
                 self.last_update.update({k: v[updates - 1:] for k, v in bc_out.items()}, action_pi=sc["action_pi"], action_data=tr["batch"]["action"])
         extra = {"plan_stats": planner.records[first_record:monitor.count]} if plan_stats else {}
         extra.update(bc_out)
@@ -806,7 +848,8 @@ class SACLearner:
         return {k: v for k, v in self.hp.items() if (k != "n_steps" or int(v) != 1) and (k not in PER_DEFAULTS or self.hp.get("prioritized"))
                 and (k not in HER_DEFAULTS or self.hp.get("hindsight")) and (k not in CLIP_DEFAULTS or v is not None)
                 and (k not in NORM_DEFAULTS or self.hp.get("normalize")) and (k not in BC_DEFAULTS or self.hp.get("bc_weight") is not None)
-                and (k not in DEMO_DEFAULTS or self.hp.get("demo_batch_size") is not None)}
+                and (k not in DEMO_DEFAULTS or self.hp.get("demo_batch_size") is not None)
+                and (k not in ADV_DEFAULTS or self.hp.get("bc_advantage_temperature") is not None)}
 
     def state_dict(self):
         """Everything the learner is, as host arrays and scalars: the actor's eight and the critics' twelve parameter tensors, the
@@ -897,6 +940,9 @@ class SACLearner:
             if state["hp"].get(k, default) != self.hp.get(k, default):
                 raise ValueError(f"load_state_dict: {k} is {state['hp'].get(k, default)!r} in the checkpoint, {self.hp.get(k, default)!r} here")
         for k, default in DEMO_DEFAULTS.items():  # a file without demonstrations holds neither
+            if state["hp"].get(k, default) != self.hp.get(k, default):
+                raise ValueError(f"load_state_dict: {k} is {state['hp'].get(k, default)!r} in the checkpoint, {self.hp.get(k, default)!r} here")
+        for k, default in ADV_DEFAULTS.items():  # a file without the advantage weight holds neither
             if state["hp"].get(k, default) != self.hp.get(k, default):
                 raise ValueError(f"load_state_dict: {k} is {state['hp'].get(k, default)!r} in the checkpoint, {self.hp.get(k, default)!r} here")
         for k, default in NORM_DEFAULTS.items():  # a file without normalization holds none of the six, and no statistics

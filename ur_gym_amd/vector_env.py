@@ -68,8 +68,11 @@ _SAC_TRAIN_ENTRIES = (
 # goes to urgym_sac_train_colored whatever else is given; its temper struct, like every option after it, may be absent.  Ahead of that,
 # behaviour cloning goes to urgym_sac_train_cloned, which takes every other option, each of which may be absent.
 # Ahead of both, a demonstration ring goes to urgym_sac_train_demonstrated, which takes cloning and every other
-# option but the three gathers' (each of those has a gather of its own).
+# option but the three gathers' (each of those has a gather of its own).  Ahead of all three, the advantage weight on the cloning term
+#  goes to urgym_sac_train_weighted, which needs cloning and takes every other option.
 _SAC_TRAIN_ENTRIES_AHEAD = (
+    ("urgym_sac_train_weighted", "weighting", ("weighting", "cloning", "demonstrating", "planner", "temper", "noise", "normalizer", "clipping", "nstep", "prioritized",
+                                               "hindsight", "evaluation", "monitor")),
     ("urgym_sac_train_demonstrated", "demonstrating", ("demonstrating", "cloning", "planner", "temper", "noise", "normalizer", "clipping", "evaluation", "monitor")),
     ("urgym_sac_train_cloned", "cloning", ("cloning", "planner", "temper", "noise", "normalizer", "clipping", "nstep", "prioritized", "hindsight", "evaluation", "monitor")),
     ("urgym_sac_train_colored", "noise", ("planner", "noise", "temper", "clipping", "nstep", "prioritized", "hindsight", "evaluation", "monitor")),
@@ -80,7 +83,7 @@ def _sac_train_entry(present):
     """(symbol, option names) of the entry point that serves a call with the options in `present` (any container of names out of
     evaluation, monitor, nstep, prioritized, hindsight, clipping, normalizer, planner, temper -- the planner's temper struct, given where
     the planner has an ess_target -- noise, its noise struct, given where it has a noise_beta, cloning and demonstrating): the first row of
-    ``_SAC_TRAIN_ENTRIES_AHEAD``, then of ``_SAC_TRAIN_ENTRIES``, whose option is given."""
+    ``_SAC_TRAIN_ENTRIES_AHEAD``, then of ``_SAC_TRAIN_ENTRIES``, whose option is given (weighting, too, is such a name)."""
     for symbol, selects, options in _SAC_TRAIN_ENTRIES_AHEAD + _SAC_TRAIN_ENTRIES:
         if selects is None or selects in present:
             return symbol, options
@@ -728,7 +731,7 @@ class UR5ReachVectorEnv:
 
     def policy_terms_cloned(self, ent_coef, count, *, dqmin_da, scale, d_action_out, q, y, critic_loss_out, log_prob, q_min, actor_loss_out,
                             action_pi, action_data, weight, bc_scale, scale_by_q=False, q_filter=False, bc_loss_out, bc_weight_out, bc_rows_out,
-                            _row_mask=None):
+                            _row_mask=None, _advantage=None):
         """``policy_terms`` with behaviour cloning, in ONE launch in its place (urgym_sac_policy_terms_cloned): all
         three groups of ``policy_terms`` are required, `q` being the online critics at the REPLAYED action.  `action_pi`, `action_data`
         [count, 6]: the policy's action and the ring's on the batch rows.  A row is cloned where `q_filter` is off or ``min(q[0], q[1])
@@ -737,7 +740,7 @@ class UR5ReachVectorEnv:
         mean over all rows of half the squared distance of the cloned rows, ``bc_weight_out`` [1] w, ``bc_rows_out`` (int32 [1]) the
         number of cloned rows.  Tensors are checked as in ``policy_terms``; the arithmetic is ``evaluation.policy_terms_cloned``,
         bitwise.  On torch's current stream, nothing is synchronised."""
-        who = "policy_terms_cloned" if _row_mask is None else "policy_terms_cloned_masked"
+        who = "policy_terms_weighted" if _advantage is not None else "policy_terms_cloned" if _row_mask is None else "policy_terms_cloned_masked"
         count = int(count)
         if not 1 <= count <= _abi.SAC_TERMS_MAX_COUNT:
             raise ValueError(f"{who}: count must be in [1, {_abi.SAC_TERMS_MAX_COUNT}], got {count}")
@@ -767,6 +770,9 @@ class UR5ReachVectorEnv:
         b.bc_rows_out = self._float_ptr(who, "bc_rows_out", bc_rows_out, (1,), torch.int32, C.c_int32)
         if d_action_out.data_ptr() in (action_pi.data_ptr(), action_data.data_ptr()):
             raise ValueError(f"{who}: d_action_out must not be action_pi or action_data (the actions are read again after it is written)")
+        if _advantage is not None:  # policy_terms_weighted has checked its own arguments; the mask, if any, is in the struct
+            _native.check(self.lib.urgym_sac_policy_terms_weighted(self._h, C.byref(a), C.byref(b), C.byref(_advantage), self._stream()), self._h)
+            return
         if _row_mask is not None:  # policy_terms_cloned_masked has checked the tensor
             _native.check(self.lib.urgym_sac_policy_terms_cloned_masked(self._h, C.byref(a), C.byref(b), _row_mask.data_ptr(), self._stream()), self._h)
             return
@@ -783,6 +789,49 @@ class UR5ReachVectorEnv:
         mask = row_mask.view(torch.uint8) if row_mask.dtype == torch.bool else row_mask
         self._float_ptr(who, "row_mask", mask, (int(count),), torch.uint8, C.c_uint8)
         self.policy_terms_cloned(ent_coef, count, _row_mask=mask, **terms)
+
+    def policy_terms_weighted(self, ent_coef, count, *, temperature, max_weight=None, row_mask=None, adv_ess_out, adv_max_out, adv_clipped_out, **terms):
+        """``policy_terms_cloned`` with an advantage weight per row in the place of the verdict, ONE launch in its place
+        (urgym_sac_policy_terms_weighted).  Every row with a finite advantage ``A = min(q[0], q[1]) - q_min`` -- and,
+        with `row_mask` (a contiguous uint8 or bool [count] tensor), a nonzero mask -- is cloned with the weight ``a = min(e / mean(e),
+        max_weight)``, ``e = exp((A - max A) / temperature)``: ``d_action_out = dqmin_da * scale + ((action_pi - action_data) * (w * a))
+        * bc_scale``.  `temperature`: finite and > 0 in float32; `max_weight`: None (no cap) or > 0.  ``bc_loss_out`` receives the mean
+        over all rows of ``a`` times half the squared distance, ``bc_rows_out`` the number of such rows, ``adv_ess_out`` [1] the effective
+        number of rows the weights spread over, ``adv_max_out`` [1] the largest weight, ``adv_clipped_out`` (int32 [1]) the rows the cap
+        held.  Every other argument is ``policy_terms_cloned``'s, without ``q_filter``.  The arithmetic is
+        ``evaluation.policy_terms_weighted``, bitwise.  On torch's current stream, nothing is synchronised."""
+        who = "policy_terms_weighted"
+        if not 1 <= int(count) <= _abi.SAC_TERMS_MAX_COUNT:
+            raise ValueError(f"{who}: count must be in [1, {_abi.SAC_TERMS_MAX_COUNT}], got {count}")
+        if "q_filter" in terms:
+            raise ValueError(f"{who}: q_filter is the other gate and is not taken here")
+        temperature, max_weight = self._advantage_numbers(who, temperature, max_weight)
+        adv = _abi.SacAdvantageArgs(temperature=temperature, max_weight=max_weight, reserved0=0)
+        if row_mask is not None:
+            if not isinstance(row_mask, torch.Tensor):
+                raise ValueError(f"{who}: row_mask must be a uint8 [count] tensor on {self.device}, got {type(row_mask).__name__}")
+            mask = row_mask.view(torch.uint8) if row_mask.dtype == torch.bool else row_mask
+            adv.row_mask = self._float_ptr(who, "row_mask", mask, (int(count),), torch.uint8, C.c_uint8)
+        adv.adv_ess_out = self._float_ptr(who, "adv_ess_out", adv_ess_out, (1,))
+        adv.adv_max_out = self._float_ptr(who, "adv_max_out", adv_max_out, (1,))
+        adv.adv_clipped_out = self._float_ptr(who, "adv_clipped_out", adv_clipped_out, (1,), torch.int32, C.c_int32)
+        self.policy_terms_cloned(ent_coef, count, _advantage=adv, **terms)
+
+    @staticmethod
+    def _advantage_numbers(who, temperature, max_weight):
+        """(temperature, max_weight) as the floats urgym_sac_policy_terms_weighted takes: a temperature that is finite and > 0 in float32,
+        a cap that is None (+infinity) or a number > 0 (a cap above float32's range is +infinity)."""
+        with np.errstate(over="ignore"):
+            ok = not isinstance(temperature, bool) and isinstance(temperature, (int, float, np.integer, np.floating)) and bool(np.isfinite(np.float32(temperature))) \
+                and float(np.float32(temperature)) > 0.0
+            if not ok:
+                raise ValueError(f"{who}: temperature must be a number that is finite and > 0 in float32, got {temperature!r}")
+            if max_weight is None:
+                return float(np.float32(temperature)), float("inf")
+            ok = not isinstance(max_weight, bool) and isinstance(max_weight, (int, float, np.integer, np.floating)) and float(np.float32(max_weight)) > 0.0
+            if not ok:
+                raise ValueError(f"{who}: max_weight must be None or a number > 0 in float32, got {max_weight!r}")
+            return float(np.float32(temperature)), float(np.float32(max_weight))
 
     def replay_sample_mixed(self, replay, demonstrations, demo_count, seed, draw, count, batch, source=None):
         """ONE gather launch whose first `demo_count` rows come from `demonstrations` and the rest from `replay` (urgym_replay_sample_mixed;
@@ -991,7 +1040,7 @@ class UR5ReachVectorEnv:
     def sac_train(self, learner, critic_loss, actor_loss, ent_coef_loss, *, first_slot, filled_steps, num_iterations, steps_per_iteration=1,
                   updates_per_iteration=1, uniform_iterations=0, idle_iterations=0, collect_first_draw=0, update_first_draw=0, first_step=1,
                   evaluation=None, eval_every=None, monitor=None, log_every=None, nstep=None, prioritized=None, hindsight=None, clipping=None,
-                  normalizer=None, planner=None, cloning=None, demonstrating=None):
+                  normalizer=None, planner=None, cloning=None, demonstrating=None, weighting=None):
         """``num_iterations`` x (a collection of ``steps_per_iteration`` steps, ``updates_per_iteration`` SAC updates) in ONE native
         call (urgym_sac_train): the launches of ``collect`` and of the thirteen calls of an update, bit for bit, without returning to
         Python in between.  `learner`: what ``sac_learner`` returned, or a dict of its keyword arguments (then built and checked here).
@@ -1048,7 +1097,12 @@ class UR5ReachVectorEnv:
         ``count`` = D of the learner's rows, ``source``, a uint8 [count of the learner] scratch tensor, and optionally ``clone_only``
         (False; True needs `cloning`)): every update's gather is the mixed one (``DeviceReplay.sample_into(demonstrations=)``,
         urgym_sac_train_demonstrated) and, with ``clone_only``, its policy terms are ``policy_terms_cloned_masked`` with ``row_mask =
-        source``.  Not together with `nstep`, `prioritized` or `hindsight`."""
+        source``.  Not together with `nstep`, `prioritized` or `hindsight`.
+
+        With `weighting` (a dict: ``temperature``, optionally ``max_weight`` (None: no cap), and ``adv_ess``, ``adv_max`` (float32) and
+        ``adv_clipped`` (int32) device tensors of one entry per update; it needs `cloning` without ``q_filter``): every update's policy
+        terms are ``policy_terms_weighted`` (urgym_sac_train_weighted), with ``row_mask = source`` where `demonstrating` has
+        ``clone_only``; update u writes entry u of the three.  With any of the options above."""
         from .evaluation import DeviceEvaluation, DeviceMonitor, DeviceMPPI, _her_arguments, evaluation_points, monitor_points, relabel_threshold, training_schedule
 
         who = "sac_train"
@@ -1184,6 +1238,18 @@ class UR5ReachVectorEnv:
                 raise ValueError(f"{who}: demonstrating['count'] must be in [0, {int(L.count)}], got {demo.count}")
             given["demonstrating"] = _abi.SacDemonstrating(demo, self._float_ptr(who, "demonstrating['source']", demonstrating["source"], (int(L.count),), torch.uint8, C.c_uint8),
                                                            int(bool(clone_only)), 0)
+        if weighting is not None:
+            unknown = [k for k in weighting if k not in ("temperature", "max_weight", "adv_ess", "adv_max", "adv_clipped")]
+            if unknown:
+                raise ValueError(f"{who}: unknown weighting options {unknown}; available: temperature, max_weight, adv_ess, adv_max, adv_clipped")
+            if cloning is None:
+                raise ValueError(f"{who}: weighting needs cloning (it weights the cloning term)")
+            if cloning.get("q_filter", False):
+                raise ValueError(f"{who}: weighting together with cloning['q_filter'] is refused (the two gates are alternatives)")
+            temperature, max_weight = self._advantage_numbers(who, weighting["temperature"], weighting.get("max_weight"))
+            given["weighting"] = _abi.SacWeighting(temperature, max_weight, 0, self._float_ptr(who, "weighting['adv_ess']", weighting["adv_ess"], (updates,)),
+                                                   self._float_ptr(who, "weighting['adv_max']", weighting["adv_max"], (updates,)),
+                                                   self._float_ptr(who, "weighting['adv_clipped']", weighting["adv_clipped"], (updates,), torch.int32, C.c_int32))
         symbol, options = _sac_train_entry(given)
         try:
             _native.check(getattr(self.lib, symbol)(self._h, C.byref(L), C.byref(S), *[C.byref(given[o]) if o in given else None for o in options], self._stream()), self._h)
