@@ -2494,6 +2494,82 @@ typedef struct urgym_sac_weighting {
  * prioritized or hindsight among it. */
 int urgym_sac_train_weighted(void* handle, const urgym_sac_learner* learner, const urgym_sac_schedule* schedule, const urgym_sac_weighting* weighting, const urgym_sac_cloning* cloning, const urgym_sac_demonstrating* demonstrating_or_NULL, const urgym_sac_planning* planning_or_NULL, const urgym_mppi_temper* temper_or_NULL, const urgym_mppi_noise* noise_or_NULL, const urgym_normalization* normalization_or_NULL, const urgym_sac_clipping* clipping_or_NULL, const urgym_sac_nstep* nstep_or_NULL, const urgym_sac_prioritized* prioritized_or_NULL, const urgym_sac_hindsight* hindsight_or_NULL, const urgym_sac_evaluation* evaluation_or_NULL, const urgym_sac_monitoring* monitoring_or_NULL, void* stream);
 
+/* ---- a scripted reach controller on the device: damped least-squares inverse kinematics.  The planner above is
+ * the only demonstrator and needs a second environment of E * K envs; a resolved-rate controller -- Jacobian, damped least squares, a
+ * step toward the goal pose -- is one small launch per control step.  It does not see obstacles: its failures are collisions on the way.
+ * Opt-in and added WITHIN ABI version 4: no struct above changed, no symbol above changed, URGYM_ABI_VERSION did not move, the three
+ * symbols below are found by lookup.  The library keeps no state for it.
+ *
+ * THE CHAIN WALK.  From q[0..5] of env n (the bound float64 state), with T = identity and for joint k = 0 .. 5 in turn, as the step
+ * kernels walk the URDF chain (data/ur5e_model.h):  o_k = T.t + T.R xyz_k;  T.t = o_k;  G = T.R rot_k;  z_k = the third column of G;
+ * T.R = G Rz(q_k).  The end-effector frame is link 6's: p = T.t, R = T.R.
+ * THE JACOBIAN, geometric, 6 x 6:  J[0:3][k] = z_k x (p - o_k);  J[3:6][k] = z_k.
+ * THE ERROR.  e[0:3] = goal[0:3] - p.  For the kinds whose goal has six floats: q_goal = pybullet's getQuaternionFromEuler(goal[3:6]),
+ * q_ee = the quaternion of R (largest-diagonal branch), d = q_goal (x) conj(q_ee), negated where d.w < 0 (the shortest arc);
+ * n = |d.xyz|;  ang = 2 atan2(n, d.w);  e[3:6] = d.xyz * (ang / n), or 2 d.xyz where n < 1e-12.  The target is the pose whose pybullet
+ * Euler read-out equals the goal; the task's own angular_distance reads the same three numbers as 'ZYX' angles, a different metric with
+ * the same zero.  For UR5ObsReach-v1 (a goal of three floats) rows 3..5 of e and of J are zero and goal rows 3..5 are not read.
+ * THE STEP, float64, one operation per line (ur_gym_amd/csrc/urgym_ik.h):  A = J J^T + damping^2 I (its lower triangle);  A = L L^T by
+ * Cholesky, no pivoting (A is symmetric positive definite by construction);  L w = e;  L^T y = w;  dq = gain * (J^T y);
+ * a = dq / cfg.action_scale;  m = max_c |a_c|;  where m > 1 every component is divided by m (the direction is kept; nothing is clamped
+ * per joint);  action[n][c] = (float)a_c, the one rounding to float32.  A row whose q or goal (the rows its kind reads) holds a value
+ * that is not finite, or whose a does not stay finite, gets six +0.0f.
+ * THE EXPLORATION NOISE is THE EXECUTE LINE of "planner-collected experience" restated on this action:  s = explore_sigma * eps[n][c];
+ * a' = action[n][c] + s;  action[n][c] = fminf(fmaxf(a', -1), 1).  eps is Box-Muller with THE SAMPLE's pairing of the words (pairs 0, 1, 2
+ * of w0 .. w5, m = w >> 8, u1 = (m1 + 1) 2^-24, the angle 2 pi m2 2^-24, r = sqrt(-2 ln u1), the pair (r cos, r sin)) but NOT its library
+ * calls: ln, cos and sin are float64 lines of their own (ur_gym_amd/csrc/urgym_ik.h: ik_ln_unit -- frexp, then the series of 2 atanh
+ * up to s^13 -- and ik_sincospi -- the angle reduced exactly to a quadrant and |x| <= pi / 4, Taylor polynomials up to x^13 and x^14),
+ * good to 1e-13, and r cos and r sin are rounded once to float32.  frexp, rint, sqrt and the basic operations are exact or correctly
+ * rounded everywhere, so explore_eps is, bit for bit, what ur_gym_amd.evaluation.ik_explore_noise computes on the host (logf and cospif
+ * of a device library cannot be restated that way: the planner's own eps is held to a bound instead).  The words are those of
+ * Philox4x32-10 with key = (seed & 0xFFFFFFFF, seed >> 32) and
+ *   counter = (n, 0, (uint32)draw, URGYM_IK_TAG | block),  block = 0, 1      (w0 .. w3 from block 0, w4 and w5 from block 1).
+ * URGYM_IK_TAG meets none of the tags in use: 0x504F4C00 | block (policy noise), 0x52504C00 (replay), 0x50455200 (prioritized replay),
+ * 0x4D505000 | block (the planner), 0x44454D00 (demonstrations), the reset sampler's blocks 0..4.  With explore_sigma == 0 no word is
+ * drawn, the action keeps the bits THE STEP gave it and explore_eps, where given, receives zeros.  The noise is a function of
+ * (seed, draw, n, c) only.
+ * The launch (urgym_ik.hip): one lane per env, 256 lanes a workgroup, q and goal read SoA, no LDS, no atomics, one writer per output;
+ * it writes actions and explore_eps only.  Row n is a function of env n's q and goal alone -- not of N or the launch geometry.
+ * ur_gym_amd.evaluation.ik_actions / ik_explore_noise restate it. */
+#define URGYM_IK_TAG 0x494B5200u   /* "IKR\0" */
+
+typedef struct urgym_reach_controller {
+  double damping;        /* finite, in [1e-2, 10] */
+  double gain;           /* finite, in (0, 10] */
+  uint64_t seed;         /* the Philox key of the exploration noise */
+  float explore_sigma;   /* finite, >= 0 */
+  int32_t reserved0;     /* must be 0 */
+  float* explore_eps;    /* [N][6] or NULL */
+} urgym_reach_controller;
+
+/* The single launch.  No allocation, no host synchronisation; everything is validated before the launch.  Refused (URGYM_ERR_ARG,
+ * nothing is launched, nothing is written): a NULL handle; a NULL c; a handle without bound buffers; a NULL actions; a non-zero
+ * reserved0; damping not finite or outside [1e-2, 10]; gain not finite or outside (0, 10]; explore_sigma not finite or < 0;
+ * draw >= 2^32. */
+int urgym_controller_actions(void* handle, const urgym_reach_controller* c, uint64_t draw, float* actions /* [N][6] */, void* stream);
+
+/* THE CLOSED LOOP: record pass 0 (THE RECORD of "sampling-based MPC on the device", without a mean to zero), then for t < num_steps:
+ * the action launch with draw = first_draw + t, written into row t of traj->action; urgym_step(handle, that row); record pass t + 1 --
+ * 2 num_steps + 1 launches besides the steps' own.  Bit for bit that sequence of single calls.  The library allocates nothing, so the
+ * action rows are the trajectory's: a call without traj->action (a NULL trajectory among them) has nowhere to put them and is refused --
+ * a loop that keeps no record is urgym_controller_collect into a ring of one slot.  c->explore_eps, where given, holds the noise of the
+ * LAST step.  Refused (URGYM_ERR_ARG, nothing launched): everything urgym_controller_actions refuses about handle and c; num_steps < 1;
+ * first_draw + num_steps > 2^32; a summary array of traj without episode_done; a NULL traj or traj->action; (URGYM_ERR_STATE) a handle
+ * that has observed nothing. */
+int urgym_controller_control(void* handle, const urgym_reach_controller* c, uint64_t first_draw, int num_steps, const urgym_trajectory* traj_or_NULL, void* stream);
+
+/* THE COLLECTION of "planner-collected experience" with the plan, the record pass and the execute launch replaced by the action launch.
+ * With C = ring->capacity_steps and slot(t) = (first_slot + t) % C, for t < num_steps: store pass t (urgym_rollout_collect's store
+ * launch, unchanged); the action launch with draw = first_draw + t and actions = the action rows of slot(t); urgym_step(handle, those
+ * rows).  After the loop store pass num_steps.  2 num_steps + 1 launches besides the steps' own.  A slot is complete when the call
+ * returns; num_steps may exceed C (the ring wraps); no launch writes a slot other than those of the call's own steps.  Two calls of a and
+ * b steps, the second with first_draw + a and the slot after the first's last, leave the bits of one call of a + b steps.  With
+ * explore_sigma == 0 the ring's action, reward and flags are, bit for bit, what urgym_controller_control records in its trajectory.
+ * c->explore_eps, where given, holds the noise of the LAST step.  Refused (URGYM_ERR_ARG, nothing launched, nothing written):
+ * everything urgym_controller_actions refuses about handle and c; everything urgym_rollout_collect refuses about the ring, first_slot and
+ * num_steps; first_draw + num_steps > 2^32; (URGYM_ERR_STATE) a handle that has observed nothing. */
+int urgym_controller_collect(void* handle, const urgym_reach_controller* c, uint64_t first_draw, int num_steps, const urgym_replay_ring* ring, int first_slot, void* stream);
+
 /* Replaces Reach*.set_goal / set_goal_and_obstacle (reach.py:202-204, 328-335, 702-713): the caller has
  * overwritten goal / obst_start / obst_end (and possibly q) for the masked envs; this recomputes obstacle pose,
  * velocity, collision, link_dist and the observation for them, leaving step_count untouched. */

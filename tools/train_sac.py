@@ -58,6 +58,8 @@ on a second env of N_d envs, filed into a ring of T slots that the run never wri
 --demo-load PATH reads one instead of filling).  --demo-batch-size D then draws the first D rows of every minibatch from it
 (SACLearner(demonstrations=, demo_batch_size=D), urgym_replay_sample_mixed; with --native urgym_sac_train_demonstrated), and --bc-demo-only
 restricts --bc-weight's cloning to those rows: the evaluation lines then also carry the cloned share of the demonstration rows.
+--demo-controller fills the ring with the scripted reach controller instead (damped least-squares IK, --demo-damping,
+--demo-gain; DeviceReplay.collect_scripted, urgym_controller_collect): one small launch per step and no planner env.
 """
 import argparse
 import json
@@ -127,6 +129,11 @@ def main():
     ap.add_argument("--demo-guide", nargs=3, metavar=("ACTOR.npz", "CRITIC0.npz", "CRITIC1.npz"), default=None,
                     help="--demo-steps: guide the demonstrating planner with these plain parameter files (as --init-from reads them) instead of the "
                          "learner's initial networks: a demonstrator that already knows the task")
+    ap.add_argument("--demo-controller", action="store_true",
+                    help="--demo-steps: fill the demonstration ring with the scripted reach controller (damped least-squares IK) instead of the planner; "
+                         "--planner-explore-sigma scales its exploration noise")
+    ap.add_argument("--demo-damping", type=float, default=0.2, metavar="L", help="--demo-controller: the damping of the least-squares step, in [1e-2, 10]")
+    ap.add_argument("--demo-gain", type=float, default=0.5, metavar="G", help="--demo-controller: the share of the solved step taken, in (0, 10]")
     ap.add_argument("--demo-envs", type=int, default=64, metavar="N_d", help="--demo-steps, --demo-load: envs of the demonstration ring's env")
     ap.add_argument("--demo-save", metavar="PATH", default=None, help="write the demonstration ring as an .npz (DeviceReplay.save) once it is filled")
     ap.add_argument("--demo-load", metavar="PATH", default=None,
@@ -200,6 +207,8 @@ def main():
         raise SystemExit("--demo-save and --demo-load need --demo-steps T, the capacity of the ring")
     if args.bc_demo_only and (args.bc_weight is None or args.demo_batch_size is None):
         raise SystemExit("--bc-demo-only needs --bc-weight and --demo-batch-size")
+    if args.demo_controller and (args.demo_steps < 1 or args.demo_load or args.demo_guide):
+        raise SystemExit("--demo-controller fills the ring of --demo-steps T itself: not with --demo-load or --demo-guide")
     if args.save_every and not args.save:
         raise SystemExit("--save-every needs --save")
     if args.save_every < 0:
@@ -210,7 +219,7 @@ def main():
     import torch
 
     from ur_gym_amd import make_vec
-    from ur_gym_amd.evaluation import DeviceActor, DeviceEvaluation, DeviceMonitor, DeviceMPPI, DevicePrioritizedReplay, DeviceReplay, evaluation_points, run_closed_loop_device, save_actor, warmup_iterations
+    from ur_gym_amd.evaluation import DeviceActor, DeviceEvaluation, DeviceMonitor, DeviceMPPI, DevicePrioritizedReplay, DeviceReachController, DeviceReplay, evaluation_points, run_closed_loop_device, save_actor, warmup_iterations
     from ur_gym_amd.training import SACLearner, host_arrays
 
     if not torch.cuda.is_available():
@@ -268,12 +277,16 @@ def main():
     if args.planner:  # guided by copies of the learner's own networks, kept current by sync_planner
         planner = make_planner(env)
     if demos is not None and not args.demo_load:  # the demonstrations: the planner's own transitions on the second env, T steps into T slots
-        demonstrator = make_planner(demo_env, args.demo_guide)
         demos.cursor = demos.filled = 0
-        demos.collect_planned(demonstrator, args.demo_steps, first_draw=0, explore_sigma=args.planner_explore_sigma)
+        if args.demo_controller:
+            demonstrator = DeviceReachController(demo_env, damping=args.demo_damping, gain=args.demo_gain, seed=args.seed)
+            demos.collect_scripted(demonstrator, args.demo_steps, first_draw=0, explore_sigma=args.planner_explore_sigma)
+        else:
+            demonstrator = make_planner(demo_env, args.demo_guide)
+            demos.collect_planned(demonstrator, args.demo_steps, first_draw=0, explore_sigma=args.planner_explore_sigma)
         torch.cuda.synchronize()
         ok = demos.ring["is_success"].float().mean().item()
-        print(json.dumps({"demo_steps": args.demo_steps, "demo_envs": args.demo_envs, "demo_transitions": len(demos), "demo_success_flag_share": ok,
+        print(json.dumps({"demonstrator": "controller" if args.demo_controller else "planner", "demo_steps": args.demo_steps, "demo_envs": args.demo_envs, "demo_transitions": len(demos), "demo_success_flag_share": ok,
                           "demo_mean_reward": demos.ring["reward"].mean().item(), "seconds": round(time.perf_counter() - t_demo, 1)}), flush=True)
         demonstrator.close()
     if demos is not None and args.demo_save:

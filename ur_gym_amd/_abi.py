@@ -697,6 +697,17 @@ class SacWeighting(C.Structure):
                 ("adv_max", C.POINTER(C.c_float)), ("adv_clipped", C.POINTER(C.c_int32))]
 
 
+IK_TAG = 0x494B5200  # URGYM_IK_TAG: word 3 of the Philox counter of the reach controller's exploration noise is IK_TAG | block (0, 1)
+IK_DAMPING_RANGE, IK_GAIN_MAX = (1e-2, 10.0), 10.0  # what urgym_controller_* accept: damping in [1e-2, 10], gain in (0, 10]
+
+
+class ReachController(C.Structure):
+    """urgym_reach_controller: the scalars of the scripted reach controller (damped least-squares IK) and where its exploration noise
+    goes; explore_eps ([N][6]) may be NULL."""
+    _fields_ = [("damping", C.c_double), ("gain", C.c_double), ("seed", C.c_uint64), ("explore_sigma", C.c_float), ("reserved0", C.c_int32),
+                ("explore_eps", C.POINTER(C.c_float))]
+
+
 # Every symbol include/urgym.h declares (tests check that the built library exports each of them).
 EXPORTED_SYMBOLS = [
     "urgym_abi_version",
@@ -806,6 +817,9 @@ EXPORTED_SYMBOLS = [
     "urgym_sac_train_demonstrated",
     "urgym_sac_policy_terms_weighted",
     "urgym_sac_train_weighted",
+    "urgym_controller_actions",
+    "urgym_controller_control",
+    "urgym_controller_collect",
     "urgym_refresh",
     "urgym_invalidate_records",
     "urgym_derive_obstacle_motion",

@@ -204,6 +204,9 @@ def lib():
                                            C.POINTER(_abi.MppiNoise), C.POINTER(_abi.Normalization), C.POINTER(_abi.SacClipping), C.POINTER(_abi.SacNstep),
                                            C.POINTER(_abi.SacPrioritized), C.POINTER(_abi.SacHindsight), C.POINTER(_abi.SacEvaluation),
                                            C.POINTER(_abi.SacMonitoring), C.c_void_p]
+    L.urgym_controller_actions.argtypes = [C.c_void_p, C.POINTER(_abi.ReachController), C.c_uint64, C.c_void_p, C.c_void_p]
+    L.urgym_controller_control.argtypes = [C.c_void_p, C.POINTER(_abi.ReachController), C.c_uint64, C.c_int, C.POINTER(_abi.Trajectory), C.c_void_p]
+    L.urgym_controller_collect.argtypes = [C.c_void_p, C.POINTER(_abi.ReachController), C.c_uint64, C.c_int, C.POINTER(_abi.ReplayRing), C.c_int, C.c_void_p]
     L.urgym_actor_read_packed.argtypes =[C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.urgym_critic_read_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.urgym_refresh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]

@@ -1,6 +1,8 @@
 // urgym_mppi_abi.hip -- the planner's entry points of include/urgym.h ("sampling-based MPC on the device", "MPPI with the learner in the
 // loop", "planner-collected experience", "elite samples and an adaptive std", "the planner inside the training call", "the temperature from a
-// target effective sample size", "temporally correlated sampling noise"; DESIGN.md sections 26 to 32).  Host code only, beside
+// target effective sample size", "temporally correlated sampling noise"; DESIGN.md sections 26 to 32), and those of the scripted reach
+// controller ("a scripted reach controller on the device"; its launch: urgym_ik.h), which share the planner's record
+// pass and the checks of its collection.  Host code only, beside
 // urgym_policy_abi.hip: every check is made here, before the first launch; every launch goes through urgym_mppi.h, urgym_mppi_guide.h,
 // urgym_mppi_collect.h, urgym_mppi_elite.h, urgym_mppi_temper.h, urgym_mppi_noise.h, the actor's and the critic's own launches (urgym_actor.h, urgym_critic.h), the ring's store
 // pass (urgym_replay.h) or through do_step of urgym_hip.hip (urgym_handle.h); the one exception is the device-to-device copy of new_std
@@ -17,6 +19,7 @@
 #include "urgym_actor.h"
 #include "urgym_critic.h"
 #include "urgym_handle.h"
+#include "urgym_ik.h"
 #include "urgym_mppi.h"
 #include "urgym_mppi_collect.h"
 #include "urgym_mppi_elite.h"
@@ -450,6 +453,70 @@ int collect(Handle* sh, Handle* ph, const urgym_mppi& m, const Guide* gd, const 
   }
   replay_store_launch(store_of(sh, ring, first_slot, num_steps, num_steps), s);
   mppi_record_launch(record_of(sh, m, nullptr, num_steps, num_steps), s);
+  return URGYM_OK;
+}
+
+// ---- the scripted reach controller (urgym_controller_actions, _control, _collect)
+
+// the checks of the three calls but the null handle; the handle keeps the message.  An unbound handle is an argument error here.
+int check_controller(Handle* h, const urgym_reach_controller* c, const char* who) {
+  static_assert(sizeof(urgym_reach_controller) == 40 && alignof(urgym_reach_controller) == 8, "include/urgym.h");
+  const char* what = nullptr;
+  if (!c) what = "null urgym_reach_controller";
+  else if (!h->bound) what = "urgym_bind() has not been called on the handle";
+  else if (c->reserved0 != 0) what = "urgym_reach_controller.reserved0 must be 0";
+  else if (!isfinite(c->damping) || c->damping < 1e-2 || c->damping > 10.0) what = "urgym_reach_controller.damping must be finite and in [1e-2, 10]";
+  else if (!isfinite(c->gain) || c->gain <= 0.0 || c->gain > 10.0) what = "urgym_reach_controller.gain must be finite and in (0, 10]";
+  else if (!isfinite(c->explore_sigma) || c->explore_sigma < 0.0f) what = "urgym_reach_controller.explore_sigma must be finite and not negative";
+  return what ? fail_in(h, URGYM_ERR_ARG, who, what) : URGYM_OK;
+}
+
+IkLaunch ik_of(const Handle* h, const urgym_reach_controller& c, uint64_t draw, float* actions) {
+  IkLaunch x;
+  x.N = h->cfg.num_envs, x.rotational = h->goal_dim == 6;
+  x.damping = c.damping, x.gain = c.gain, x.action_scale = h->cfg.action_scale;
+  x.explore_sigma = c.explore_sigma, x.seed = c.seed, x.draw = draw;
+  x.q = h->buf.q, x.goal = h->buf.goal;
+  x.actions = actions, x.explore_eps = c.explore_eps;
+  ik_model_fill(x.model);
+  return x;
+}
+
+// pass k of the closed loop's records: THE RECORD with the controller's action rows and no mean to zero (a horizon of 0 steps)
+MppiRecord controller_record_of(const Handle* h, const urgym_trajectory& traj, int k, int num_steps) {
+  urgym_mppi none;
+  memset(&none, 0, sizeof(none));
+  MppiRecord r = record_of(h, none, &traj, k, num_steps);
+  r.action_row = nullptr;  // nothing to copy: the action launch wrote the row where it belongs
+  return r;
+}
+
+// The launches of the closed loop; everything has been checked.  Every launch goes to `s`: stream order alone puts the action launch
+// behind the step that wrote q, and the step that reads the row behind the launch that wrote it.
+int controller_control(Handle* h, const urgym_reach_controller& c, uint64_t first_draw, int num_steps, const urgym_trajectory& traj, hipStream_t s) {
+  const size_t row = (size_t)h->cfg.num_envs * 6;
+  mppi_record_launch(controller_record_of(h, traj, 0, num_steps), s);
+  for (int t = 0; t < num_steps; t++) {
+    float* actions = traj.action + (size_t)t * row;
+    ik_actions_launch(ik_of(h, c, first_draw + (uint64_t)t, actions), s);
+    if (int rc = do_step(h, actions, s)) return rc;
+    mppi_record_launch(controller_record_of(h, traj, t + 1, num_steps), s);
+  }
+  return URGYM_OK;
+}
+
+// The launches of a collection; everything has been checked.  collect() above with the plan, the record pass and the execute launch
+// replaced by the action launch.
+int controller_collect(Handle* h, const urgym_reach_controller& c, uint64_t first_draw, int num_steps, const urgym_replay_ring& ring, int first_slot,
+                       hipStream_t s) {
+  const size_t row = (size_t)h->cfg.num_envs * 6, C = (size_t)ring.capacity_steps;
+  for (int t = 0; t < num_steps; t++) {
+    replay_store_launch(store_of(h, ring, first_slot, t, num_steps), s);
+    float* actions = ring.action + (((size_t)first_slot + (size_t)t) % C) * row;  // the action launch writes the slot, the step reads it
+    ik_actions_launch(ik_of(h, c, first_draw + (uint64_t)t, actions), s);
+    if (int rc = do_step(h, actions, s)) return rc;
+  }
+  replay_store_launch(store_of(h, ring, first_slot, num_steps, num_steps), s);
   return URGYM_OK;
 }
 
@@ -916,6 +983,46 @@ int urgym_mppi_stats(void* handle, const urgym_mppi* m, const urgym_mppi_adapt* 
   if (int rc = check_stats(h, m, a_or_NULL, record_dev, iteration, "urgym_mppi_stats", &c)) return rc;
   HIP_TRY(h, hipSetDevice(h->device));
   mppi_stats_launch(c, (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_controller_actions(void* handle, const urgym_reach_controller* c, uint64_t draw, float* actions, void* stream) {
+  const char* who = "urgym_controller_actions";
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (int rc = check_controller(h, c, who)) return rc;
+  if (!actions) return fail_in(h, URGYM_ERR_ARG, who, "actions is null");
+  if (int rc = check_draw(h, draw, 1, who)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  ik_actions_launch(ik_of(h, *c, draw, actions), (hipStream_t)stream);
+  return launched(h);
+}
+
+int urgym_controller_control(void* handle, const urgym_reach_controller* c, uint64_t first_draw, int num_steps, const urgym_trajectory* traj_or_NULL, void* stream) {
+  const char* who = "urgym_controller_control";
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (int rc = check_controller(h, c, who)) return rc;
+  if (!h->observed) return fail_in(h, URGYM_ERR_STATE, who, "nothing has been observed yet: urgym_reset() or urgym_refresh() first");
+  if (int rc = check_record(h, 0, num_steps, traj_or_NULL, who)) return rc;
+  if (!traj_or_NULL || !traj_or_NULL->action)
+    return fail_in(h, URGYM_ERR_ARG, who, "traj->action is null: the library allocates nothing, the action rows are the trajectory's");
+  if (int rc = check_draw(h, first_draw, num_steps, who)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  if (int rc = controller_control(h, *c, first_draw, num_steps, *traj_or_NULL, (hipStream_t)stream)) return rc;
+  return launched(h);
+}
+
+int urgym_controller_collect(void* handle, const urgym_reach_controller* c, uint64_t first_draw, int num_steps, const urgym_replay_ring* ring, int first_slot, void* stream) {
+  const char* who = "urgym_controller_collect";
+  Handle* h = (Handle*)handle;
+  if (!h) return fail(nullptr, URGYM_ERR_ARG, "null handle");
+  if (int rc = check_controller(h, c, who)) return rc;
+  if (!h->observed) return fail_in(h, URGYM_ERR_STATE, who, "nothing has been observed yet: urgym_reset() or urgym_refresh() first");
+  if (int rc = check_ring(h, ring, first_slot, num_steps, who)) return rc;
+  if (int rc = check_draw(h, first_draw, num_steps, who)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  if (int rc = controller_collect(h, *c, first_draw, num_steps, *ring, first_slot, (hipStream_t)stream)) return rc;
   return launched(h);
 }
 

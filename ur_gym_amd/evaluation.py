@@ -1637,6 +1637,16 @@ class DeviceReplay:
         self.cursor = (self.cursor + K) % self.capacity
         self.filled = min(self.capacity, self.filled + K)
 
+    def collect_scripted(self, controller, num_steps, first_draw=0, explore_sigma=0.0):
+        """``collect`` with the scripted reach controller as the policy: `num_steps` x (store pass, controller action, step) from slot
+        ``cursor`` on in one native call (urgym_controller_collect), `controller` a ``DeviceReachController`` of this ring's environment;
+        step t draws its exploration noise with ``first_draw + t``.  The slots are what a policy collection writes.  Advances ``cursor``
+        and ``filled`` as ``collect_planned`` does."""
+        K = int(num_steps)
+        controller.collect(self, K, first_draw=first_draw, explore_sigma=explore_sigma, first_slot=self.cursor)
+        self.cursor = (self.cursor + K) % self.capacity
+        self.filled = min(self.capacity, self.filled + K)
+
     def sample_into(self, out, seed, draw, n_steps=None, gamma=None, hindsight=None, demonstrations=None):
         """The gather itself: `out` maps ring field names (and ``index``, int64) to contiguous device tensors with one leading
         length, the batch size; only those are written.  The rows are ``replay_indices(seed, draw, count, len(self))``.
@@ -1957,6 +1967,12 @@ class DevicePrioritizedReplay(DeviceReplay):
         """``DeviceReplay.collect_planned``, then ``fill`` on the slots just written, as ``collect`` does."""
         first = self.cursor
         super().collect_planned(planner, num_steps, first_draw=first_draw, explore_sigma=explore_sigma)
+        self.fill(first, num_steps)
+
+    def collect_scripted(self, controller, num_steps, first_draw=0, explore_sigma=0.0):
+        """``DeviceReplay.collect_scripted``, then ``fill`` on the slots just written, as ``collect`` does."""
+        first = self.cursor
+        super().collect_scripted(controller, num_steps, first_draw=first_draw, explore_sigma=explore_sigma)
         self.fill(first, num_steps)
 
     def sample_prioritized(self, batch_size, seed, draw):
@@ -3754,3 +3770,247 @@ def run_closed_loop_mppi(env, points=None, max_steps=100, first_draw=0, **planne
     return {"success_rate_percent": 100.0 * success.mean(), "mean_episode_reward": float(reward.mean()),
             "mean_last_step_index": float(last.mean()), "success": success, "reward": reward, "last_step": last}
 
+
+
+# ------------------------------------------------------------------------------------------------ the scripted reach controller
+def _ik_model():
+    """joint_xyz [6, 3] and the fixed rotations [6, 3, 3] of the URDF's joint origins, R = Rz(yaw) Ry(pitch) Rx(roll) of joint_rpy
+    (data/ur5e_model.npz) -- formed here from the angles, not read from the table the kernels use."""
+    import os
+
+    if not hasattr(_ik_model, "cache"):
+        with np.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "data", "ur5e_model.npz")) as m:
+            xyz, rpy = np.array(m["joint_xyz"], np.float64), np.array(m["joint_rpy"], np.float64)
+        _ik_model.cache = (xyz, np.stack([_ik_rpy_matrix(a[None])[0] for a in rpy]))
+    return _ik_model.cache
+
+
+def _ik_rpy_matrix(rpy):
+    """[M, 3] fixed-axis roll-pitch-yaw -> [M, 3, 3], R = Rz(yaw) Ry(pitch) Rx(roll): the URDF's convention, and the rotation of
+    pybullet's getQuaternionFromEuler."""
+    (cr, cp, cy), (sr, sp, sy) = np.cos(rpy).T, np.sin(rpy).T
+    R = np.empty(rpy.shape[:1] + (3, 3))
+    R[:, 0, 0], R[:, 0, 1], R[:, 0, 2] = cy * cp, cy * sp * sr - sy * cr, cy * sp * cr + sy * sr
+    R[:, 1, 0], R[:, 1, 1], R[:, 1, 2] = sy * cp, sy * sp * sr + cy * cr, sy * sp * cr - cy * sr
+    R[:, 2, 0], R[:, 2, 1], R[:, 2, 2] = -sp, cp * sr, cp * cr
+    return R
+
+
+def _ik_rotation_quat(D):
+    """[M, 3, 3] rotations -> [M, 4] unit quaternions xyzw with w >= 0 (Shepperd: the largest of the four squares leads)."""
+    tr = D[:, 0, 0] + D[:, 1, 1] + D[:, 2, 2]
+    four = np.stack([1 + 2 * D[:, 0, 0] - tr, 1 + 2 * D[:, 1, 1] - tr, 1 + 2 * D[:, 2, 2] - tr, 1 + tr], 1)  # 4 x^2, 4 y^2, 4 z^2, 4 w^2
+    lead = four.argmax(1)
+    sym = lambda i, j: D[:, i, j] + D[:, j, i]
+    skew = np.stack([D[:, 2, 1] - D[:, 1, 2], D[:, 0, 2] - D[:, 2, 0], D[:, 1, 0] - D[:, 0, 1]], 1)  # 4 w (x, y, z)
+    rows = np.stack([np.stack([four[:, 0], sym(0, 1), sym(0, 2), skew[:, 0]], 1), np.stack([sym(0, 1), four[:, 1], sym(1, 2), skew[:, 1]], 1),
+                     np.stack([sym(0, 2), sym(1, 2), four[:, 2], skew[:, 2]], 1), np.stack([skew[:, 0], skew[:, 1], skew[:, 2], four[:, 3]], 1)], 1)
+    q = rows[np.arange(len(D)), lead]  # 4 q_lead q
+    q = q / np.linalg.norm(q, axis=1, keepdims=True)
+    return np.where(q[:, 3:] < 0, -q, q)
+
+
+def ik_chain(q):
+    """The chain walk in float64 numpy from the URDF's joint origins: `q` [M, 6] -> (z [M, 6, 3] joint axes, o [M, 6, 3] joint origins,
+    R [M, 3, 3] and p [M, 3] of the end-effector, link 6), all in the world frame."""
+    xyz, fixed = _ik_model()
+    q = np.asarray(q, np.float64)
+    M = len(q)
+    R, t = np.broadcast_to(np.eye(3), (M, 3, 3)).copy(), np.zeros((M, 3))
+    z, o = np.empty((M, 6, 3)), np.empty((M, 6, 3))
+    for k in range(6):
+        c, s = np.cos(q[:, k]), np.sin(q[:, k])
+        t = t + R @ xyz[k]
+        G = R @ fixed[k]
+        o[:, k], z[:, k] = t, G[:, :, 2]
+        Rz = np.zeros((M, 3, 3))
+        Rz[:, 0, 0], Rz[:, 0, 1], Rz[:, 1, 0], Rz[:, 1, 1], Rz[:, 2, 2] = c, -s, s, c, 1.0
+        R = G @ Rz
+    return z, o, R, t
+
+
+def ik_terms(q, goal, env_kind, damping):
+    """The Jacobian, the error, A = J J^T + damping^2 I and the solution y of A y = e of the reach controller (include/urgym.h, "a
+    scripted reach controller on the device"), float64 numpy: `q` [M, 6], `goal` [M, 6] or [M, 3] (rows 3.. are not read for
+    UR5ObsReach-v1).  Returns a dict J [M, 6, 6], e [M, 6], A [M, 6, 6], y [M, 6], dw [M] (the scalar part of the error quaternion
+    before the shortest-arc flip; 1 where the kind has no orientation)."""
+    from . import _abi
+
+    q, goal = np.atleast_2d(np.asarray(q, np.float64)), np.atleast_2d(np.asarray(goal, np.float64))
+    rotational = _abi.OBS_DIMS[env_kind][1] == 6
+    z, o, R, p = ik_chain(q)
+    M = len(q)
+    J, e, dw = np.zeros((M, 6, 6)), np.zeros((M, 6)), np.ones(M)
+    J[:, :3, :] = np.cross(z, p[:, None, :] - o).transpose(0, 2, 1)
+    e[:, :3] = goal[:, :3] - p
+    if rotational:
+        J[:, 3:, :] = z.transpose(0, 2, 1)
+        D = _ik_rpy_matrix(goal[:, 3:6]) @ R.transpose(0, 2, 1)  # the rotation of q_goal (x) conj(q_ee)
+        d = _ik_rotation_quat(D)
+        # the sign the product of the two quaternions carries before the flip is not a property of D: |d.w| is, and that is what the
+        # shortest-arc discontinuity depends on
+        dw = d[:, 3]
+        n = np.linalg.norm(d[:, :3], axis=1)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            scale = np.where(n < 1e-12, 2.0, 2.0 * np.arctan2(n, d[:, 3]) / n)
+        e[:, 3:] = d[:, :3] * scale[:, None]
+    A = J @ J.transpose(0, 2, 1) + float(damping) ** 2 * np.eye(6)
+    y = np.linalg.solve(A, e[:, :, None])[:, :, 0]
+    return dict(J=J, e=e, A=A, y=y, dw=dw)
+
+
+def ik_actions(q, goal, env_kind, damping, gain, action_scale):
+    """THE STEP of the reach controller in float64 numpy, rounded once to float32: `q` [M, 6] (or [6]), `goal` [M, 6] or [M, 3] ->
+    float32 [M, 6].  dq = gain J^T y with y of ``ik_terms``; a = dq / action_scale; the whole row is divided by max |a_c| where that
+    exceeds 1.  A row whose q or goal (the columns its kind reads) is not finite gets zeros.  Written from the URDF's joint origins, not
+    from ur_gym_amd/csrc/urgym_ik.h: the kernel is held to 2^-22 of this."""
+    from . import _abi
+
+    q, goal = np.atleast_2d(np.asarray(q, np.float64)), np.atleast_2d(np.asarray(goal, np.float64))
+    gd = _abi.OBS_DIMS[env_kind][1]
+    if q.shape[1] != 6 or goal.shape[0] != q.shape[0] or goal.shape[1] < gd:
+        raise ValueError(f"q must be [M, 6] and goal [M, >= {gd}], got {q.shape} and {goal.shape}")
+    ok = np.isfinite(q).all(1) & np.isfinite(goal[:, :gd]).all(1)
+    out = np.zeros((len(q), 6), np.float32)
+    if ok.any():
+        t = ik_terms(q[ok], goal[ok], env_kind, damping)
+        a = float(gain) * np.einsum("mrk,mr->mk", t["J"], t["y"]) / float(action_scale)
+        m = np.abs(a).max(1, keepdims=True)
+        a = np.where(m > 1.0, a / np.where(m > 1.0, m, 1.0), a)
+        fin = np.isfinite(a).all(1)
+        rows = np.flatnonzero(ok)
+        out[rows[fin]] = a[fin].astype(np.float32)
+    return out
+
+
+def ik_explore_counters(draw, envs):
+    """The two Philox counters of the reach controller's exploration noise of (env n, draw): 4-tuples (n, 0, draw, IK_TAG | block) for
+    block 0 and block 1, `envs` an integer or an integer array."""
+    from . import _abi
+
+    draw = int(draw)
+    if not 0 <= draw < 1 << 32:
+        raise ValueError(f"draw must be in [0, 2^32), got {draw}")
+    n = np.asarray(envs, dtype=np.uint64)
+    if n.size and int(n.max()) >= 1 << 31:
+        raise ValueError("envs must be env indices")
+    return tuple((n, np.uint64(0), np.uint64(draw), np.uint64(_abi.IK_TAG | b)) for b in (0, 1))
+
+
+def ik_box_muller(m):
+    """Box-Muller of the reach controller's noise, bit for bit (ur_gym_amd/csrc/urgym_ik.h: ik_ln_unit, ik_sincospi, ik_box_muller): `m`
+    integers below 2^24 of shape + (6,), the pairs (m[2p], m[2p + 1]); returns float32 of the same shape.  The pairing is the planner's
+    (u1 = (m1 + 1) 2^-24, angle = 2 pi m2 2^-24, r = sqrt(-2 ln u1), (r cos, r sin)), but ln, cos and sin are the float64 lines the
+    header states -- every operation below is one IEEE operation, in the header's order -- so the device's noise can be restated
+    exactly, which a library's logf and cospif cannot."""
+    m = np.asarray(m)
+    M = m[..., 0::2].astype(np.float64) + 1.0
+    f, e = np.frexp(M)
+    low = f < 0.7071067811865476
+    f, e = np.where(low, f * 2.0, f), np.where(low, e - 1, e)
+    s = (f - 1.0) / (f + 1.0)
+    z = s * s
+    p = np.full(z.shape, 1.0 / 13.0)
+    for c in (1.0 / 11.0, 1.0 / 9.0, 1.0 / 7.0, 1.0 / 5.0, 1.0 / 3.0, 1.0):
+        p = p * z
+        p = p + c
+    ln = (e - 24).astype(np.float64) * 0.6931471805599453 + 2.0 * (s * p)
+    with np.errstate(invalid="ignore"):
+        r = np.sqrt(-2.0 * ln)
+    t = m[..., 1::2].astype(np.float64) * (1.0 / 8388608.0)
+    k = np.rint(t * 2.0)
+    x = 3.141592653589793 * (t - k * 0.5)
+    z = x * x
+    ps = np.full(z.shape, 1.0 / 6227020800.0)
+    for c in (-1.0 / 39916800.0, 1.0 / 362880.0, -1.0 / 5040.0, 1.0 / 120.0, -1.0 / 6.0, 1.0):
+        ps = ps * z
+        ps = ps + c
+    sn = x * ps
+    pc = np.full(z.shape, -1.0 / 87178291200.0)
+    for c in (1.0 / 479001600.0, -1.0 / 3628800.0, 1.0 / 40320.0, -1.0 / 720.0, 1.0 / 24.0, -1.0 / 2.0):
+        pc = pc * z
+        pc = pc + c
+    cs = pc * z + 1.0
+    q = k.astype(np.int64) & 3
+    sin = np.select([q == 0, q == 1, q == 2], [sn, cs, -sn], -cs)
+    cos = np.select([q == 0, q == 1, q == 2], [cs, -sn, -cs], sn)
+    out = np.empty(m.shape, np.float32)
+    out[..., 0::2], out[..., 1::2] = (r * cos).astype(np.float32), (r * sin).astype(np.float32)
+    return out
+
+
+def ik_explore_noise(seed, draw, N, dtype=np.float32):
+    """The exploration noise of the reach controller, restated from include/urgym.h: six normals for each of the envs 0 .. N - 1, a
+    pure function of (seed, draw, env, component), on the words of the counters ``ik_explore_counters`` states with key (seed lo,
+    seed hi).  With the default `dtype` it is ``ik_box_muller``, BIT FOR BIT what the device reports in ``explore_eps``; with
+    ``np.float64`` it is the planner's ``_box_muller`` in float64 on the same words (numpy's log, cos and sin), the yardstick that says
+    the stated lines compute Box-Muller.  Returns [N, 6]; the executed action is ``mppi_execute(action, eps, explore_sigma)``."""
+    seed = int(seed)
+    key = (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
+    c0, c1 = ik_explore_counters(draw, np.arange(int(N)))
+    a, b = philox4x32_10(key, c0), philox4x32_10(key, c1)
+    if dtype is np.float32:
+        return ik_box_muller(_noise_integers(a, b, np.float64).astype(np.int64))
+    return _box_muller(_noise_integers(a, b, dtype), dtype)
+
+
+class DeviceReachController:
+    """A scripted expert for the reach tasks: resolved-rate control by damped least-squares inverse kinematics, one small launch per
+    control step on the environment's own state (urgym_controller_*).  It needs no second environment and no
+    training; it does not see obstacles, so its failures are collisions on the way.  `env` is a UR5ReachVectorEnv; `seed` keys the
+    exploration noise.  Holds no native object: there is nothing to close."""
+
+    def __init__(self, env, damping=0.2, gain=0.5, seed=0):
+        self.env = env
+        self.damping, self.gain, self.seed, _ = env.check_controller(damping, gain, seed, 0.0)
+        self.explore_eps = None
+
+    def _eps(self):
+        import torch
+
+        if self.explore_eps is None:
+            self.explore_eps = torch.zeros((self.env.num_envs, 6), dtype=torch.float32, device=self.env.device)
+        return self.explore_eps
+
+    def _keywords(self, explore_sigma):
+        return dict(damping=self.damping, gain=self.gain, seed=self.seed, explore_sigma=explore_sigma, explore_eps=self._eps())
+
+    def actions(self, draw=0, explore_sigma=0.0, out=None):
+        """The action of every env for the state it is in (``env.controller_actions``: one launch); ``self.explore_eps`` then holds the
+        noise of `draw` (zeros with ``explore_sigma == 0``).  Returns `out` (allocated if None).  NOT synchronised."""
+        return self.env.controller_actions(out=out, draw=draw, **self._keywords(explore_sigma))
+
+    def run(self, num_steps, first_draw=0, record=("reward", "terminated", "truncated", "is_success"), explore_sigma=0.0):
+        """`num_steps` x (action, step) in ONE native call (``env.controller_control``); returns its dict of device tensors."""
+        return self.env.controller_control(num_steps, first_draw=first_draw, record=record, **self._keywords(explore_sigma))
+
+    def collect(self, replay, num_steps, first_draw=0, explore_sigma=0.0, first_slot=None):
+        """`num_steps` x (store pass, action, step) in ONE native call that files every transition in `replay`
+        (``env.controller_collect``); does NOT move the ring's cursor -- ``replay.collect_scripted`` does."""
+        self.env.controller_collect(replay, num_steps, first_draw=first_draw, first_slot=first_slot, **self._keywords(explore_sigma))
+
+    def close(self):
+        self.explore_eps = None
+
+
+def run_closed_loop_controller(env, points=None, max_steps=100, first_draw=0, explore_sigma=0.0, **controller):
+    """``run_closed_loop_mppi`` with the scripted reach controller in place of the planner: model_test.py's protocol
+    (model_test.py:26-61) for all envs of `env` at once, a UR5ReachVectorEnv with auto-reset off that has been reset.  `points`, if
+    given, are one test point per env, set with ``set_goal`` (UR5OriReach-v1) or ``set_goal_and_obstacle`` first.  `controller` are
+    ``DeviceReachController``'s keywords.  One native call; returns the same dictionary."""
+    import torch
+
+    from . import _abi
+
+    if env.cfg.auto_reset:
+        raise ValueError("run_closed_loop_controller: env must be made with auto_reset=False")
+    if points is not None:
+        (env.set_goal if env.env_kind == _abi.ENV_ORI else env.set_goal_and_obstacle)(np.arange(env.num_envs), points)
+    rec = DeviceReachController(env, **controller).run(max_steps, first_draw, record=("episode_return", "episode_last_step", "episode_success"),
+                                                       explore_sigma=explore_sigma)
+    torch.cuda.synchronize(env.device)
+    reward = rec["episode_return"].cpu().numpy()
+    success = rec["episode_success"].cpu().numpy().astype(bool)
+    last = rec["episode_last_step"].cpu().numpy().astype(np.float64)
+    return {"success_rate_percent": 100.0 * success.mean(), "mean_episode_reward": float(reward.mean()),
+            "mean_last_step_index": float(last.mean()), "success": success, "reward": reward, "last_step": last}

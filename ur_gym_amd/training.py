@@ -417,7 +417,7 @@ class SACLearner:
         self.env_steps = 0  # per env; decides between the warm-up and the policy
         self.draw = 0       # draw index of the next collection pass
 
-    def collect(self, replay, num_steps, monitor=None, planner=None, explore_sigma=0.0):
+    def collect(self, replay, num_steps, monitor=None, planner=None, explore_sigma=0.0, controller=None):
         """`num_steps` env steps of all N envs into `replay`, with uniform actions before ``learning_starts`` env steps and the sampled
         policy afterwards (a call is one or the other: the mode is decided when it starts).  With `monitor` (an
         ``evaluation.DeviceMonitor``) the steps just collected are folded into its state: one more launch.  With ``normalize`` the actor
@@ -427,7 +427,28 @@ class SACLearner:
         (``replay.collect_planned``): ``learning_starts`` is not consulted, the planner's draw is ``self.draw``, and
         the executed action is the plan's plus `explore_sigma` times the exploration noise.  SAC is off-policy and trains on these
         transitions as they stand; ``sync_planner`` keeps the planner's actor and critic on this learner's parameters.  Not together
-        with ``normalize``: the planner's actor and critic read raw rows.  Without `planner` the calls are those above."""
+        with ``normalize``: the planner's actor and critic read raw rows.  Without `planner` the calls are those above.
+
+        With `controller` (an ``evaluation.DeviceReachController`` on this learner's env) every step is the scripted reach controller's
+        instead (``replay.collect_scripted``): as with a planner, ``learning_starts`` is not consulted, the draw is
+        ``self.draw`` and `explore_sigma` scales the exploration noise; the ring holds raw rows, and with ``normalize`` the steps are folded
+        into the statistics like any others.  Not together with `planner`."""
+        if controller is not None:
+            if planner is not None:
+                raise ValueError("collect: controller= and planner= are alternatives")
+            if getattr(controller, "env", None) is not self.env:
+                raise ValueError("collect: the controller's env is not this learner's env (DeviceReachController(learner.env, ...))")
+            if self.normalizer is not None and int(num_steps) > self.normalizer.fold_steps:
+                raise ValueError(f"collect: with normalize at most fold_steps = {self.normalizer.fold_steps} steps a call, got {num_steps}")
+            first = replay.cursor
+            replay.collect_scripted(controller, num_steps, first_draw=self.draw, explore_sigma=explore_sigma)
+            if self.normalizer is not None:
+                self.normalizer.fold(replay, first, num_steps)
+            if monitor is not None:
+                monitor.fold(replay, first, num_steps)
+            self.env_steps += int(num_steps)
+            self.draw += int(num_steps)
+            return
         if planner is not None:
             if self.normalizer is not None:
                 raise ValueError("collect: planner= together with normalize=True is out of scope (the planner's actor and critic read raw rows, not normalized ones)")
@@ -441,7 +462,7 @@ class SACLearner:
             self.draw += int(num_steps)
             return
         if explore_sigma:
-            raise ValueError("collect: explore_sigma is the planner's exploration noise and needs planner=")
+            raise ValueError("collect: explore_sigma is the planner's (or the controller's) exploration noise and needs planner= or controller=")
         mode = "uniform" if self.env_steps * self.env.num_envs < self.hp["learning_starts"] else "gaussian"
         first = replay.cursor
         if self.normalizer is not None:

@@ -1451,6 +1451,97 @@ class UR5ReachVectorEnv:
         how = self._sampling(sample if sample is not None else dict(mode="mean"))
         _native.check(self.lib.urgym_rollout_collect(self._h, a, C.byref(how), int(num_steps), C.byref(replay._ring), int(first), self._stream()), self._h)
 
+    # --------------------------------------------------------------------------------- the scripted reach controller
+    @staticmethod
+    def check_controller(damping=0.2, gain=0.5, seed=0, explore_sigma=0.0):
+        """Raises ValueError for what urgym_controller_* refuse about the controller's scalars (include/urgym.h): damping outside
+        [1e-2, 10], gain outside (0, 10], explore_sigma negative or not finite in float32, a seed that is no uint64.  Returns the four as
+        (float, float, int, float).  Needs no GPU."""
+        lo, hi = _abi.IK_DAMPING_RANGE
+        for name, v in (("damping", damping), ("gain", gain), ("explore_sigma", explore_sigma)):
+            if isinstance(v, bool) or not np.isfinite(np.float64(v)):
+                raise ValueError(f"{name} must be a finite number, got {v!r}")
+        if not lo <= float(damping) <= hi:
+            raise ValueError(f"damping must be in [{lo}, {hi}], got {damping}")
+        if not 0.0 < float(gain) <= _abi.IK_GAIN_MAX:
+            raise ValueError(f"gain must be in (0, {_abi.IK_GAIN_MAX}], got {gain}")
+        with np.errstate(over="ignore"):
+            if not (np.isfinite(np.float32(explore_sigma)) and float(explore_sigma) >= 0.0):
+                raise ValueError(f"explore_sigma must be finite (in float32) and >= 0, got {explore_sigma!r}")
+        if isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 1 << 64:
+            raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
+        return float(damping), float(gain), int(seed), float(explore_sigma)
+
+    def _controller(self, damping, gain, seed, explore_sigma, explore_eps):
+        c = _abi.ReachController(*self.check_controller(damping, gain, seed, explore_sigma), 0, None)
+        if explore_eps is not None:
+            if (explore_eps.dtype != torch.float32 or tuple(explore_eps.shape) != (self.num_envs, 6) or not explore_eps.is_contiguous()
+                    or explore_eps.device != self.device):
+                raise ValueError(f"explore_eps must be a contiguous float32 [{self.num_envs}, 6] tensor on {self.device}")
+            c.explore_eps = C.cast(explore_eps.data_ptr(), C.POINTER(C.c_float))
+        return c
+
+    @staticmethod
+    def _check_draw(first_draw, count):
+        if isinstance(first_draw, bool) or int(first_draw) != first_draw or not (0 <= int(first_draw) and int(first_draw) + int(count) <= 1 << 32):
+            raise ValueError(f"draws must stay in [0, 2^32), got {first_draw} + {count}")
+        return int(first_draw)
+
+    def controller_actions(self, out=None, draw=0, damping=0.2, gain=0.5, seed=0, explore_sigma=0.0, explore_eps=None):
+        """One damped least-squares IK step toward every env's goal pose as an action (urgym_controller_actions: ONE launch that reads
+        the bound ``q`` and ``goal``; ``evaluation.ik_actions`` restates it): float32 [N, 6] in `out` (allocated if None), plus
+        `explore_sigma` times the exploration noise of (`seed`, `draw`), clamped, where `explore_sigma` > 0; `explore_eps` ([N, 6],
+        optional) receives the noise.  Returns `out`.  NOT synchronised."""
+        if out is None:
+            out = torch.empty((self.num_envs, 6), dtype=torch.float32, device=self.device)
+        elif out.dtype != torch.float32 or tuple(out.shape) != (self.num_envs, 6) or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"out must be a contiguous float32 [{self.num_envs}, 6] tensor on {self.device}")
+        c = self._controller(damping, gain, seed, explore_sigma, explore_eps)
+        _native.check(self.lib.urgym_controller_actions(self._h, C.byref(c), self._check_draw(draw, 1), C.c_void_p(out.data_ptr()), self._stream()), self._h)
+        return out
+
+    def controller_control(self, num_steps, first_draw=0, record=("reward", "terminated", "truncated", "is_success"), damping=0.2, gain=0.5, seed=0,
+                           explore_sigma=0.0, explore_eps=None):
+        """`num_steps` x (controller action, step) in ONE native call (urgym_controller_control); step t draws with ``first_draw + t``.
+        `record` names what to keep, as ``rollout_policy`` does ("all" = every key); the action rows are always kept (the call writes
+        them into the trajectory).  Returns a dict of fresh device tensors (flags as bool views).  NOT synchronised."""
+        T = int(num_steps)
+        if T < 1:
+            raise ValueError(f"num_steps must be positive, got {num_steps}")
+        keys = tuple(name for name, _, _ in _abi.TRAJECTORY_FIELDS)
+        names = tuple(k for k in keys if k != "final_observation" or self.cfg.auto_reset) if record == "all" else tuple(record)
+        unknown = [n for n in names if n not in keys]
+        if unknown:
+            raise ValueError(f"unknown record {unknown}; available: {keys}")
+        if "final_observation" in names and not self.cfg.auto_reset:
+            raise ValueError("final_observation exists only with auto_reset")
+        if any(n.startswith("episode_") for n in names) and "episode_done" not in names:
+            names += ("episode_done",)
+        if "action" not in names:
+            names += ("action",)
+        c = self._controller(damping, gain, seed, explore_sigma, explore_eps)
+        traj, out = _abi.Trajectory(), {}
+        for name, ct, shape in _abi.TRAJECTORY_FIELDS:
+            if name in names:
+                t = torch.zeros(shape(T, self.num_envs, self.obs_dim, self.goal_dim), dtype=_TORCH_DTYPE[ct], device=self.device)
+                setattr(traj, name, C.cast(t.data_ptr(), C.POINTER(ct)))
+                out[name] = t.view(torch.bool) if ct is C.c_uint8 else t
+        _native.check(self.lib.urgym_controller_control(self._h, C.byref(c), self._check_draw(first_draw, T), T, C.byref(traj), self._stream()), self._h)
+        return out
+
+    def controller_collect(self, replay, num_steps, first_draw=0, first_slot=None, damping=0.2, gain=0.5, seed=0, explore_sigma=0.0, explore_eps=None):
+        """`num_steps` x (store pass, controller action, step) in ONE native call (urgym_controller_collect) that files every transition
+        in `replay` (an ``evaluation.DeviceReplay`` of this environment) as it happens: step t goes to slot (first_slot + t) % capacity
+        and draws with ``first_draw + t``.  `first_slot` defaults to the ring's cursor, which this method does NOT move --
+        ``replay.collect_scripted`` does.  NOT synchronised."""
+        if getattr(replay, "env", None) is not self or not hasattr(replay, "_ring"):
+            raise ValueError("replay must be a DeviceReplay allocated for this environment (DeviceReplay(env, capacity_steps))")
+        first = replay.cursor if first_slot is None else first_slot
+        replay.check_args(replay.capacity, num_steps=num_steps, first_slot=first)
+        c = self._controller(damping, gain, seed, explore_sigma, explore_eps)
+        _native.check(self.lib.urgym_controller_collect(self._h, C.byref(c), self._check_draw(first_draw, int(num_steps)), int(num_steps), C.byref(replay._ring),
+                                                        int(first), self._stream()), self._h)
+
     def close(self):
         if getattr(self, "_h", None):
             torch.cuda.synchronize(self.device)
